@@ -88,6 +88,54 @@ def count_flubbles(forest):
     return sum(n - 1 for n in forest.pvst_sizes())
 
 
+DUMP_BYTES = 64_000_000  # --dump-outputs: all files together stay below this
+DUMP_SEED = 20260612
+
+
+def forest_outputs(forest, budget=DUMP_BYTES):
+    """What a caller of the timed path receives (Forest.tree(i) of every PVST), as float arrays for --dump-outputs.
+    Per PVST, in component-id order: tree_component_id, tree_n_vtx, tree_n_links, tree_n_pvst.  Per PVST vertex (the trees
+    in that order, the vertices of a tree in emission order): pvst_a_id, pvst_z_id, pvst_parent (float64, exact) and
+    pvst_a_or, pvst_z_or (float32).  When all vertices would not fit `budget`, a fixed seeded sample of them is kept;
+    pvst_index holds the position of every row kept in the full order."""
+    import numpy as np
+    ids = forest.component_ids()
+    order = sorted(range(len(ids)), key=lambda i: ids[i])
+    sizes = np.array(forest.pvst_sizes(), dtype=np.int64)[order] if order else np.zeros(0, np.int64)
+    start = np.concatenate([[0], np.cumsum(sizes)])
+    total = int(start[-1])
+    room = max(0, (budget - 32 * len(order) - 16 * 1024) // 40)  # 40 bytes a row: 4 float64 + 2 float32 columns
+    if total <= room:
+        keep = np.arange(total, dtype=np.int64)
+    else:
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=room, replace=False))
+    cols = {k: [] for k in ("a_id", "z_id", "parent", "a_or", "z_or")}
+    trees = {k: np.zeros(len(order), np.float64) for k in ("component_id", "n_vtx", "n_links", "n_pvst")}
+    lo = np.searchsorted(keep, start[:-1])
+    hi = np.searchsorted(keep, start[1:])
+    for j, i in enumerate(order):
+        t = forest.tree(i)
+        trees["component_id"][j], trees["n_vtx"][j], trees["n_links"][j] = t.component_id, t.n_vtx, t.n_links
+        trees["n_pvst"][j] = sizes[j]
+        rows = keep[lo[j]:hi[j]] - start[j]
+        for k in cols:
+            cols[k].append(getattr(t, k)[rows])
+    out = {"tree_" + k: v for k, v in trees.items()}
+    for k, parts in cols.items():
+        v = np.concatenate(parts) if parts else np.zeros(0)
+        out["pvst_" + k] = v.astype(np.float32 if k.endswith("_or") else np.float64)
+    out["pvst_index"] = keep.astype(np.float64)
+    return out
+
+
+def dump_outputs(forest, outdir):
+    """--dump-outputs: the arrays of forest_outputs as <outdir>/<name>.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, arr in forest_outputs(forest).items():
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+
+
 def time_single(hip, g, steps, warmup, flags, overlap=True, pool_warm=True):
     """warmup + `steps` timed passes on one context; returns (seconds, HIP-event ms per pass, last forest, mean latency of a
     pass in ms).  With `overlap` the passes are issued back to back (POVU_HIP_F_ASYNC): a pass returns when its forest is laid
@@ -265,6 +313,8 @@ def main_one_process(args):
         prev = f
     prev.wait()
     dt_res = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(f, args.dump_outputs)
     F, n_trees = count_flubbles(f), len(f)
     ranks = [md.rank_info(r) for r in range(args.gpus)]
     alg = algorithmic_bytes(E, V, F)
@@ -322,7 +372,11 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="time the passes one at a time instead of back to back")
     ap.add_argument("--no-latency-leg", action="store_true", help="skip the three extra one-at-a-time passes (profiling runs)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of configs 2 / 3 / 5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the forest of the last one as DIR/<name>.npy (see forest_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -365,6 +419,8 @@ def main():
         up = hip.upload_times()
         dt, pass_ms, f, lat_ms = time_single(hip, g, args.steps, args.warmup, F_NO_STAGE_TIMES, overlap=not args.no_overlap,
                                              pool_warm=not args.no_latency_leg)  # (profiling runs: exactly warmup + steps + 1 passes)
+        if args.dump_outputs:  # (f = the forest of the last timed pass, complete in host memory)
+            dump_outputs(f, args.dump_outputs)
         # the same passes one at a time (each complete before the next starts): what a single decompose call costs
         if args.no_latency_leg:
             dt1, pass1_ms = (dt, pass_ms) if args.no_overlap else (float("nan"), float("nan"))
@@ -511,6 +567,8 @@ def main():
         t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt_res = float(t.item())
+        if rank == 0 and args.dump_outputs:  # (before the collective below: the merged forest reads the other ranks' blocks)
+            dump_outputs(sb.last, args.dump_outputs)
         info = sb.summary()  # collective: per-rank loads and phase times
         if rank == 0:
             E, V, F = info["links"], info["segments"], info["flubbles"]

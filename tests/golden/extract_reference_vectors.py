@@ -1,7 +1,7 @@
 """Extracts the known answers the reference's own conformance suite holds for the decompose path into
 tests/golden/reference_vectors.json (DATA: inputs and expected outputs; no source text is copied).
 
-Run in the build container, where /root/reference exists:   python tests/golden/extract_reference_vectors.py
+Run with a checkout of the upstream povu sources:   python tests/golden/extract_reference_vectors.py <checkout>
 
 Sources (read as text):
 * tests/lean4_conformance/lean_reference.lean -- `fixtureStructureOutput?` (:953-976) names the expected
@@ -15,7 +15,9 @@ import os
 import re
 import sys
 
-REF = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
+if len(sys.argv) != 2:
+    sys.exit("usage: extract_reference_vectors.py <checkout of the upstream povu sources>")
+REF = sys.argv[1]
 HERE = os.path.dirname(os.path.abspath(__file__))
 lean = open(os.path.join(REF, "tests/lean4_conformance/lean_reference.lean")).read()
 rs = open(os.path.join(REF, "tests/lean4_conformance/src/main.rs")).read()

@@ -1,5 +1,5 @@
 import sys, time, os
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, 'tests'))
 import numpy as np
 from povu_amd import HipDecomposer, workloads as W
 from povu_amd.hip import F_SUBFLUBBLES
