@@ -43,7 +43,7 @@
 enum { SS_AI_TRUNK, SS_AI_BRANCH, SS_ZI_TRUNK, SS_ZI_BRANCH, SS_NEST_TRUNK_AI, SS_NEST_BRANCH_AI, SS_NEST_TRUNK_ZI, SS_ZI_BRANCH_UNNESTED,
        SS_LEAF_BY_TREE_IDX, SS_MIDI, SS_MIDI_SAME_KIND, SS_MIDI_NEST, SS_SMO_G_TRUNK_TGT, SS_SMO_G_TRUNK_SRC, SS_SMO_G_BRANCH,
        SS_SMO_S_TRUNK, SS_SMO_S_BRANCH_SRC, SS_SMO_S_BRANCH_TGT, SS_SMO_NEST, SS_SMO_STALE_READ, SS_DEPTH_OF_INVALID, SS_SELF_LOOP_IN_LOA,
-       SS_OVERRIDE_JI, SS_N };
+       SS_OVERRIDE_JI, SS_NEST_OVER_PINNED, SS_N };
 static uint64_t g_sub_stats[SS_N];
 #define SS_INC(i) ((void)__atomic_fetch_add(&g_sub_stats[i], 1, __ATOMIC_RELAXED))
 void orc_sub_stats(uint64_t *out, int reset)
@@ -614,6 +614,7 @@ static void sub_find_concealed(const orc_tree *t, const sub_meta *s, spvst *p)
 		const fl_sls *F = &fls[q];
 		const uint32_t f = F->fl, ai = p->v[f].ai, zi = p->v[f].zi;
 		const int is_leaf = f < t->n && n_children(s, f) == 0; /* (sic) the SPANNING TREE's vertex f, concealed.cpp:1188 */
+		const uint32_t own0 = p->n; /* f's own concealed vertices from here on: one in [n0, own0) was pushed by its parent */
 		for (uint32_t k = 0; k < F->n_ai + F->n_zi; k++) {
 			const slub *x = &all.x[F->first + k];
 			svtx nv;
@@ -629,6 +630,12 @@ static void sub_find_concealed(const orc_tree *t, const sub_meta *s, spvst *p)
 				continue;
 			uint32_t nch;
 			uint32_t *ch = sp_children_copy(p, f, &nch);
+			if (x->loc != CL_ZI_BRANCH) /* the nestings run over the concealed vertex of the parent's z-side trunk record */
+				for (uint32_t c_k = 0; c_k < nch; c_k++)
+					if (ch[c_k] >= n0 && ch[c_k] < own0) {
+						SS_INC(SS_NEST_OVER_PINNED);
+						break;
+					}
 			for (uint32_t c_k = 0; c_k < nch; c_k++) {
 				const uint32_t c = ch[c_k];
 				if (!fl_like(p->v[c].fam))

@@ -1088,6 +1088,32 @@ __global__ void k_sub_x_init(uint32_t Q, const SubT t, const CompAt comp, const 
 		X.ai[x] = X.zi[x] = NIL;
 	}
 }
+// POVU_HIP_SUB_SERIAL_SPLICE (tests): X-space as a pass on another graph may have left it, before k_sub_x_init writes the
+// PVST slots.  Every slot gets a flubble whose bounds make cn_leaves say "leaves" for as many records as can be: zi the
+// component's root (depth 0, no bracket, below no vertex), ai its last vertex in preorder (below every vertex of the
+// rightmost path).  Each index stays inside the slot's own component (one lane per X slot; of_slot over xoff gives the
+// component that owns the slot: the stretches of components without a PVST are empty), so no stale read leaves an array.
+__global__ void k_sub_x_poison(uint32_t NX, const SubT t, const CompAt comp_x, const uint32_t *__restrict__ xoff, XArrays X)
+{
+	const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x;
+	if (x >= NX)
+		return;
+	const uint32_t c = comp_x.of_slot(x), base = t.base_of(c), N = t.c_ntree[c];
+	if (!N) { // (no tree: a slot nobody reads as a flubble)
+		X.fam[x] = FAM_DUMMY;
+		X.ai[x] = X.zi[x] = X.sl[x] = X.b_up[x] = X.b_lo[x] = NIL;
+		X.id1[x] = X.id2[x] = NIL;
+		X.loc[x] = 0, X.or1[x] = X.or2[x] = 0, X.route[x] = 0;
+		return;
+	}
+	const uint32_t root = base, last = base + N - 1;
+	X.fam[x] = FAM_FLUBBLE;
+	X.loc[x] = (uint8_t)((x - xoff[c]) & 3u);
+	X.ai[x] = last, X.zi[x] = root;
+	X.sl[x] = last, X.b_up[x] = root, X.b_lo[x] = last;
+	X.id1[x] = t.gid[root], X.id2[x] = t.gid[last];
+	X.or1[x] = 1, X.or2[x] = 1, X.route[x] = 'R';
+}
 // where the children of X slot x begin among the sorted (parent slot, child) pairs = how many pairs have a smaller key: a
 // binary search per slot (counting them with atomics put a million adds on the word of a chromosome's root)
 __device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *__restrict__ a, uint32_t n, uint32_t x)
@@ -1140,7 +1166,8 @@ __global__ void k_sub_x_place(uint32_t Q, uint32_t NX, const uint32_t *__restric
 // ------------------------------------------------------------------ the splice, in parallel
 // Until round 5 one wave spliced a whole component, flubble after flubble (94 ms for the whole-genome workload: 10^4
 // flubbles of a chromosome with a concealed bubble, some ten dependent trips to memory each).  What add_concealed does to
-// one flubble f depends on nothing another flubble's turn writes:
+// one flubble f depends on nothing another flubble's turn writes (the one vertex of another turn in f's vector, the one its
+// parent pushes, is known by its index alone: cn_leaves; tests/test_gpu_splice_schedule.py runs the turns in either order):
 //  * its records (cn[]: found before, in ascending idx) each become the vertex n0 + (index of the record in the
 //    component) -- no counter;
 //  * a record's nesting moves children of f under the new vertex, or (z-side trunk) pushes the new vertex into the vector
@@ -1171,9 +1198,14 @@ struct SpliceArgs {
 	uint8_t *md;	  // [Q] gets a midi bubble
 	const uint32_t *md_ps; // [Q + 1] exclusive scan of md
 };
-// what the nestings of add_concealed ask of a child of the flubble (ai, zi, n_of_f) for the slubble sl
-__device__ bool cn_leaves(const SubT &t, const XArrays &X, uint32_t xb, const Slub &sl, uint32_t ai, uint32_t zi, uint32_t n_of_f, uint32_t ch)
+// what the nestings of add_concealed ask of a child of the flubble (ai, zi, n_of_f) for the slubble sl.  A child past the
+// PVST (ch >= n0) is a concealed vertex -- the flubble's own, or the one its parent's z-side trunk record pushed (k_sub_pin)
+// -- and never F / T / O: decided by its index, since the parent's wave writes the fields of that one in the same launch
+__device__ bool cn_leaves(const SubT &t, const XArrays &X, uint32_t xb, uint32_t n0, const Slub &sl, uint32_t ai, uint32_t zi, uint32_t n_of_f,
+			  uint32_t ch)
 {
+	if (ch >= n0)
+		return false;
 	const uint8_t fam = X.fam[xb + ch];
 	if (!(fam == FAM_FLUBBLE || fam == FAM_TINY || fam == FAM_PARALLEL))
 		return false;
@@ -1233,7 +1265,7 @@ __global__ void k_sub_pin(uint32_t Q, const SpliceArgs A)
 					const Slub sl = A.cn[k];
 					if (sl.loc == CL_ZI_BRANCH)
 						continue;
-					if (cn_leaves(t, A.X, xb, sl, ai, zi, n_of_f, ch)) { // this record takes it out of f's vector
+					if (cn_leaves(t, A.X, xb, n0, sl, ai, zi, n_of_f, ch)) { // this record takes it out of f's vector
 						if (sl.loc == CL_ZI_TRUNK)
 							pin = n0 + (k - cn_b);
 						break;
@@ -1248,6 +1280,16 @@ __global__ void k_sub_pin(uint32_t Q, const SpliceArgs A)
 	A.md[q] = 0;
 }
 static constexpr unsigned SPLICE_WAVES = 8192; // waves of a splice kernel: each takes every SPLICE_WAVES-th entry of its list
+// POVU_HIP_SUB_SERIAL_SPLICE=reverse (tests): the compacted list back to front, so one wave takes every child before its parent
+__global__ void k_sub_reverse_list(uint32_t cap, const uint32_t *__restrict__ n_list, uint32_t *__restrict__ list)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, n = min(*n_list, cap);
+	if (i >= n / 2)
+		return;
+	const uint32_t a = list[i];
+	list[i] = list[n - 1 - i];
+	list[n - 1 - i] = a;
+}
 // ---- add_concealed, concealed.cpp:925-1196: one wave per flubble on the list
 __global__ void __launch_bounds__(64) k_sub_splice_cn(const uint32_t *__restrict__ n_list, const uint32_t *__restrict__ list, const SpliceArgs A)
 {
@@ -1325,7 +1367,7 @@ __global__ void __launch_bounds__(64) k_sub_splice_cn(const uint32_t *__restrict
 					continue;
 				// the nestings: which of the children (the new vertex among them: it is no flubble) leave for the slubble
 				const uint32_t nch = X.vn[xb + f];
-				if (!S.filter(f, nch, v, sl.loc == CL_ZI_TRUNK, [&](uint32_t ch) { return cn_leaves(t, X, xb, sl, ai, zi, n_of_f, ch); }))
+				if (!S.filter(f, nch, v, sl.loc == CL_ZI_TRUNK, [&](uint32_t ch) { return cn_leaves(t, X, xb, n0, sl, ai, zi, n_of_f, ch); }))
 					return;
 			}
 		}
@@ -1579,6 +1621,18 @@ void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, cons
 	const uint32_t NB0 = pw.nb0, NB = pw.nb0 + pw.ncap + pw.nsimp;
 	const uint32_t Q = (uint32_t)pw.d_total; // dense PVST slots
 	const LeafIn &in = ls.in;
+	// POVU_HIP_SUB_SERIAL_SPLICE=forward|reverse (tests; read on every call): X-space filled with a stale forest first, and
+	// the splice kernels on one wave that walks its list in order (reverse: children before their parents) -- the schedule
+	// the parallel splice must not depend on
+	enum { SPLICE_PARALLEL, SPLICE_FORWARD, SPLICE_REVERSE } sched = SPLICE_PARALLEL;
+	if (const char *e = getenv("POVU_HIP_SUB_SERIAL_SPLICE"); e && *e) {
+		if (!strcmp(e, "forward"))
+			sched = SPLICE_FORWARD;
+		else if (!strcmp(e, "reverse"))
+			sched = SPLICE_REVERSE;
+		else
+			throw HipError(std::string("POVU_HIP_SUB_SERIAL_SPLICE: forward or reverse, not ") + e);
+	}
 	// POVU_HIP_SUB_TIMES=1: wall-clock of the phases on stderr (each mark synchronises the stream)
 	const bool times = getenv("POVU_HIP_SUB_TIMES") != nullptr;
 	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1738,10 +1792,12 @@ void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, cons
 	X.pool = dev32((size_t)ps + 4);
 	HIP_CHECK(hipMemsetAsync(X.vn, 0, ((size_t)NX + 4) * 4, s));
 	HIP_CHECK(hipMemsetAsync(X.vcap, 0, ((size_t)NX + 4) * 4, s));
-	const CompAt comp_q{cs.voff, pw.doff, C};
+	const CompAt comp_q{cs.voff, pw.doff, C}, comp_x{cs.voff, xoff, C};
 	uint32_t *cap_ps = dev32((size_t)NX + 4);
 	const size_t tmpx_bytes = scan_tmp_bytes((size_t)NX + 8);
 	void *tmpx = bufs.emplace_back().get<char>(tmpx_bytes, arena, need);
+	if (sched != SPLICE_PARALLEL)
+		LAUNCH(k_sub_x_poison, NX, s, NX, t, comp_x, xoff, X);
 	LAUNCH(k_sub_x_init, Q, s, Q, t, comp_q, xoff, X);
 	{
 		uint32_t *k0 = dev32((size_t)Q + 4), *k1 = dev32((size_t)Q + 4), *v0 = dev32((size_t)Q + 4), *v1 = dev32((size_t)Q + 4);
@@ -1766,15 +1822,20 @@ void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, cons
 		void *ctmp = bufs.emplace_back().get<char>(ctmp_bytes, arena, need);
 		LAUNCH(k_sub_ptop, C, s, C, poff, sw.c_npvst, A.ptop);
 		LAUNCH(k_sub_pin, Q, s, Q, A);
+		const unsigned waves = sched == SPLICE_PARALLEL ? SPLICE_WAVES : 1u;
 		compact_flagged_u8(A.act, Q, list, n_list, ctmp, ctmp_bytes, s);
-		KLAUNCH(k_sub_splice_cn, dim3(SPLICE_WAVES), dim3(64), 0, s, n_list, list, A);
+		if (sched == SPLICE_REVERSE)
+			LAUNCH(k_sub_reverse_list, Q / 2 + 1, s, Q, n_list, list);
+		KLAUNCH(k_sub_splice_cn, dim3(waves), dim3(64), 0, s, n_list, list, A);
 		compact_flagged_u8(A.touched, Q, list, n_list, ctmp, ctmp_bytes, s);
-		KLAUNCH(k_sub_midi_find, dim3(SPLICE_WAVES), dim3(64), 0, s, n_list, list, A);
+		if (sched == SPLICE_REVERSE)
+			LAUNCH(k_sub_reverse_list, Q / 2 + 1, s, Q, n_list, list);
+		KLAUNCH(k_sub_midi_find, dim3(waves), dim3(64), 0, s, n_list, list, A);
 		HIP_CHECK(hipMemsetAsync(A.md + Q, 0, 1, s));
 		scan_exclusive_u8(A.md, md_ps, (size_t)Q + 1, nullptr, nullptr, 0, tmp, tmp_bytes, s);
-		KLAUNCH(k_sub_midi_add, dim3(SPLICE_WAVES), dim3(64), 0, s, n_list, list, A);
+		KLAUNCH(k_sub_midi_add, dim3(waves), dim3(64), 0, s, n_list, list, A);
 		if (NS)
-			KLAUNCH(k_sub_smothered, dim3(std::min<unsigned>(NC, SPLICE_WAVES)), dim3(64), 0, s, NC, A);
+			KLAUNCH(k_sub_smothered, dim3(std::min<unsigned>(NC, waves)), dim3(64), 0, s, NC, A);
 		LAUNCH(k_sub_counts, C, s, C, A, counts);
 	} else if (C) {
 		HIP_CHECK(hipMemsetAsync(counts, 0, 3 * (size_t)C * 4, s));
@@ -1787,7 +1848,6 @@ void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, cons
 		throw HipError("subflubble passes: more inserted vertices than the layout has room for (internal sizing bug)");
 	// ---- the children lists, compact
 	uint32_t *ccnt = dev32((size_t)NX + 4), *coff = dev32((size_t)NX + 4);
-	const CompAt comp_x{cs.voff, xoff, C};
 	LAUNCH(k_sub_child_counts, (size_t)NX + 1, s, NX, xoff, counts, sw.c_npvst, comp_x, X.vn, ccnt);
 	scan_exclusive_u32(ccnt, coff, (size_t)NX + 1, tmpx, tmpx_bytes, s);
 	const uint32_t NCH = host.read_u32(coff + NX, s);

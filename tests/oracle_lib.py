@@ -26,8 +26,8 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        src = os.path.join(_ROOT, "oracle", "povu_oracle.c")
-        if (not os.path.exists(_SO)) or os.path.getmtime(_SO) < os.path.getmtime(src):
+        srcs = [os.path.join(_ROOT, "oracle", n) for n in ("povu_oracle.c", "povu_oracle.h", "povu_oracle_sub.inc")]
+        if (not os.path.exists(_SO)) or os.path.getmtime(_SO) < max(os.path.getmtime(p) for p in srcs):
             subprocess.check_call(["make", "-C", os.path.join(_ROOT, "oracle"), "-s"])
         _lib = C.CDLL(_SO)
         _lib.orc_decompose_arrays.restype = C.POINTER(Forest)

@@ -16,7 +16,7 @@ from test_oracle import _load_gfa_links
 
 RULES = ("ai_trunk ai_branch zi_trunk zi_branch nest_trunk_ai nest_branch_ai nest_trunk_zi zi_branch_unnested leaf_by_tree_idx midi "
          "midi_same_kind midi_nest smo_g_trunk_tgt smo_g_trunk_src smo_g_branch smo_s_trunk smo_s_branch_src smo_s_branch_tgt smo_nest "
-         "smo_stale_read depth_of_invalid self_loop_in_loa override_ji").split()
+         "smo_stale_read depth_of_invalid self_loop_in_loa override_ji nest_over_pinned").split()
 # small random graphs (n_vtx, n_links, seed, self_loops, connected of workloads.random_bidirected) that reach a rule of the
 # three inserting passes, found by search (the oracle counts which rule fires: orc_sub_stats)
 RULE_SEEDS = {
@@ -28,7 +28,7 @@ RULE_SEEDS = {
     "smo_g_trunk_src": (9, 18, 141043583, True, False), "smo_g_branch": (8, 12, 302624343, False, True),
     "smo_s_trunk": (13, 20, 573077957, False, True), "smo_s_branch_src": (15, 20, 600991250, True, False),
     "smo_s_branch_tgt": (10, 12, 521325456, True, True), "depth_of_invalid": (12, 13, 528241921, False, True),
-    "override_ji": (7, 13, 811069680, True, True),
+    "override_ji": (7, 13, 811069680, True, True), "nest_over_pinned": (8, 17, 108198728, False, True),
     # a chain of bubbles / a bubble zoo with a few random extra links: (family, size..., fraction of extra links, seed)
     "smo_nest": ("chain", 11, 0.2333583231116823, 996436063), "smo_stale_read": ("chain", 32, 0.053941270117384026, 485877343),
     "leaf_by_tree_idx": ("zoo", 1, 9, 0.09662316694210007, 282500235),
@@ -40,6 +40,14 @@ RULE_SEEDS = {
 # flubble's ai (concealed.cpp:1006 reads get_src where get_tgt is meant: a bracket's source lies below, ai above);
 # midi_nest wants spanning-tree depths at two PVST indices a few apart to differ by more than the indices do.
 UNREACHED_RULES = ("nest_branch_ai", "midi_nest")
+# nest_over_pinned: a flubble whose parent's z-side trunk record pushed a concealed vertex into its vector runs its own
+# nestings over that vector.  One graph in some 10^5 of either family reaches it; these each reach it once (tests/
+# test_gpu_splice_schedule.py builds graphs with thousands of such flubbles from them)
+PINNED_SEEDS = ((10, 20, 848912932, False, False), (11, 16, 861612118, False, False), (8, 17, 108198728, False, True),
+                (13, 25, 488763382, True, True), (12, 25, 802778594, False, False), (19, 28, 110349806, True, True),
+                ("zoo", 3, 6, 0.37195334370125116, 15589636), ("zoo", 1, 10, 0.1701118826636954, 308349633),
+                ("zoo", 1, 9, 0.15304097245719245, 793243884), ("zoo", 1, 7, 0.0356302265593858, 657744224),
+                ("zoo", 4, 4, 0.09352339186772048, 426734502))
 
 
 def _with_extra(base, frac, seed):
@@ -54,7 +62,11 @@ def rule_tips(rule, g):
 
 
 def rule_graph(rule):
-    p = RULE_SEEDS[rule]
+    return seed_graph(RULE_SEEDS[rule])
+
+
+def seed_graph(p):
+    """the graph of one entry of RULE_SEEDS / PINNED_SEEDS"""
     if p[0] == "tipless":
         return W.random_bidirected(p[1], p[2], p[3], self_loops=False)
     if p[0] == "chain":
@@ -63,6 +75,22 @@ def rule_graph(rule):
         return _with_extra(W.bubble_zoo(p[1], p[2], p[4]), p[3], p[4] + 1)
     nv, ne, seed, sl, conn = p
     return W.random_bidirected(nv, ne, seed, self_loops=sl, connected=conn)
+
+
+def disjoint_union(graphs):
+    """the graphs side by side in one upload: each keeps its local vertex and link order, so each stays the component(s)
+    it was alone"""
+    vid, v1, s1, v2, s2 = [], [], [], [], []
+    off = id_off = 0
+    for g in graphs:
+        vid.append(g.vid.astype(np.int64) + id_off)
+        v1.append(g.v1.astype(np.int64) + off)
+        v2.append(g.v2.astype(np.int64) + off)
+        s1.append(g.s1)
+        s2.append(g.s2)
+        off += g.n_vtx
+        id_off += int(g.vid.max())
+    return W._mk(np.concatenate(vid), np.concatenate(v1), np.concatenate(s1), np.concatenate(v2), np.concatenate(s2))
 
 
 def sub_stats(reset=True):
@@ -223,3 +251,18 @@ def test_rule_seeds_reach_their_rules():
         g = rule_graph(rule)
         O.decompose(g, tips=rule_tips(rule, g), leaf=2)
         assert sub_stats()[rule] >= 1, rule
+
+
+def test_pinned_seeds_and_their_union():
+    """Every PINNED_SEEDS graph reaches nest_over_pinned; side by side, 50 copies of them reach it 50 times as often and
+    give 50 times their PVSTs, line kinds alike (the segment ids differ)."""
+    one = []
+    for p in PINNED_SEEDS:
+        sub_stats()
+        one.append(O.decompose(seed_graph(p), leaf=2))
+        assert sub_stats()["nest_over_pinned"] >= 1, p
+    sub_stats()
+    many = O.decompose(disjoint_union([seed_graph(p) for p in PINNED_SEEDS] * 50), leaf=2)
+    assert sub_stats()["nest_over_pinned"] == 50 * len(PINNED_SEEDS)
+    kinds = lambda texts: sorted("".join(l[0] for l in t.splitlines()) for t in texts)
+    assert kinds(many.values()) == kinds([t for texts in one for t in texts.values()] * 50)
