@@ -78,7 +78,15 @@ bool povu_graph_set_references_from_prefixes(PovuGraph *graph, const char **pref
 PovuFlubbles *povu_graph_find_flubbles(PovuGraph *graph, PovuError *error);
 void povu_flubbles_free(PovuFlubbles *flubbles);
 size_t povu_flubbles_count(const PovuFlubbles *flubbles);
-PovuFlubble *povu_flubbles_get(const PovuFlubbles *flubbles, size_t index); /* always NULL, as povu_ffi.cpp:402-411 */
+/* povu_flubbles_get: NULL for index 0 (the dummy root) and index >= povu_flubbles_count.  Otherwise flubble `index` (the
+ * trees' PVST vertices side by side, tree order then vertex order) with type_name "flubble" / "tiny" / "parallel" /
+ * "concealed" / "midi" / "smothered", its two boundary segment ids and its walks (PovuStep arrays, freed by
+ * povu_flubble_free): povu_hip_forest_walks with the default caps (64 walks, 1000 steps, 65 536 expansions; INTEGRATION.md
+ * "Flubble walks" -- decided here, the reference returns NULL).  The walks of the whole forest are computed on the GPU at the
+ * first call; PovuFlubbles keeps its HIP context and resident graph (not the decompose workspaces) until
+ * povu_flubbles_free.  NULL also when the walks cannot be computed (a builder graph whose ids were not added in ascending
+ * order; a transient failure, such as device memory, is tried again by the next call). */
+PovuFlubble *povu_flubbles_get(const PovuFlubbles *flubbles, size_t index);
 void povu_flubble_free(PovuFlubble *flubble);
 
 /* PVST view [ffi.h:358-364]; non-owning view into its PovuFlubbles */

@@ -48,6 +48,10 @@ int povu_hip_device_count(void);
 /* create / destroy a context on `device` */
 povu_hip_ctx *povu_hip_create(int device, char *err, size_t errlen);
 void povu_hip_destroy(povu_hip_ctx *ctx);
+/* gives the decompose workspaces of `ctx` back to the device, keeping the resident graph (a context kept only for
+ * povu_hip_forest_walks on a forest it made); the next povu_hip_decompose reserves them again.  Ends the debug exports of
+ * the last pass.  0 on success */
+int povu_hip_release_workspace(povu_hip_ctx *ctx);
 
 /*
  * Row A (device part).  Copies the link arrays to HBM and builds the per-side
@@ -314,6 +318,45 @@ char *povu_hip_pvst_format_subtree(const povu_hip_subtree *t, size_t *len);
 int povu_hip_forest_raw(const povu_hip_forest *f, const void **block, size_t *bytes, uint64_t *total, uint64_t offsets[5]);
 uint64_t povu_hip_forest_first(const povu_hip_forest *f, uint32_t i);
 void povu_hip_forest_free(povu_hip_forest *f);
+
+/* ---- walks of every flubble ("Flubble walks": decided here, not reference behaviour) ----
+ * A step is (segment, orientation); (v, '>') leaves v through its r side, (v, '<') through its l side, and a link from that
+ * side to side y of u gives the next step (u, '>') when y is l, (u, '<') when y is r (parallel links count once).  Every PVST
+ * vertex but the root of its tree is one query: from its first boundary step S to its second boundary step Z (for a forest
+ * of POVU_HIP_F_SUBFLUBBLES the vertices of the extended trees, povu_hip_forest_get_subtree).  A walk starts with S, ends
+ * with Z and holds no segment twice; walks come in lexicographic order of their (segment id, '>' before '<') keys -- the
+ * order of a DFS that tries successors by ascending id, '>' first.  That DFS counts one expansion per step it appends to a
+ * prefix (Z included, S not); a prefix of max_steps steps that does not end at Z is not extended (status LONG); it stops
+ * at the (max_walks + 1)-th walk (MORE: the first max_walks are reported) or when an expansion beyond max_expansions would
+ * be needed (BUDGET: the walks found so far are reported).  Queries are numbered in tree order, then PVST vertex order
+ * within the tree, each root skipped. */
+typedef struct {
+	uint32_t max_walks;	 /* K, 0 = 64 */
+	uint32_t max_steps;	 /* L, 0 = 1000 (the reference's MAX_FLUBBLE_STEPS) */
+	uint32_t max_expansions; /* E, 0 = 65536 */
+	uint32_t flags;		 /* POVU_HIP_W_* */
+} povu_hip_walk_opts;
+#define POVU_HIP_W_FORCE_TIER2 1u /* run every query with the second-tier kernel (tests) */
+#define POVU_HIP_WALK_MORE 1u	  /* status bits per query */
+#define POVU_HIP_WALK_LONG 2u
+#define POVU_HIP_WALK_BUDGET 4u
+typedef struct {
+	uint64_t n_queries, n_walks, n_steps;
+	const uint32_t *walk_off; /* [n_queries + 1] walks of query q: [walk_off[q], walk_off[q + 1]) */
+	const uint32_t *step_off; /* [n_walks + 1] steps of walk w: [step_off[w], step_off[w + 1]) */
+	const uint32_t *step_id;  /* [n_steps] segment id */
+	const uint8_t *step_or;	  /* [n_steps] 0 '>', 1 '<' */
+	const uint8_t *status;	  /* [n_queries] POVU_HIP_WALK_* bits */
+	uint64_t n_tier2;	  /* queries the second-tier kernel ran (the first tier hands over what outgrows its limits) */
+	double device_ms;	  /* HIP-event time of the call, first upload to last byte on the host */
+} povu_hip_walks;
+/* Enumerates the walks of every query of `f` on the graph resident in `ctx` (opts NULL = defaults).  Refused with a
+ * message when `f` was not made by povu_hip_decompose on this context from its current upload, when it is sharded, merged
+ * or attached, when the segment ids of the resident graph do not ascend with the vertex index, or when the output does
+ * not fit (32-bit offsets, device memory).  Free with povu_hip_walks_free. */
+povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_forest *f, const povu_hip_walk_opts *opts, char *err,
+				      size_t errlen);
+void povu_hip_walks_free(povu_hip_walks *w);
 
 /*
  * Serialises tree `i` exactly as mto::to_pvst::write_pvst does

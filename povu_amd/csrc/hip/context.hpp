@@ -258,6 +258,10 @@ struct povu_hip_forest {
 	void *xblk = nullptr;
 	size_t xblk_cap = 0;
 	int xblk_seg = -1;
+	// povu_hip_forest_walks: the context and upload generation whose graph a povu_hip_decompose of the whole resident graph
+	// (no shard) decomposed; merged, attached and sharded forests keep null / 0 and are refused
+	const void *walk_ctx = nullptr;
+	uint64_t walk_gen = 0;
 };
 
 struct povu_hip_ctx {
@@ -312,6 +316,7 @@ struct povu_hip_ctx {
 			wait_tail();
 		}
 	}
+	Arena wk_ws, wk_out; // povu_hip_forest_walks: queries, counts and tier-2 stacks / the walks themselves (walk_kernels.hip)
 	Arena part_arena;  // the packed shards of the last povu_hip_shard_partition (kept warm: a step of a sharded job re-partitions)
 	// bytes this context moved over PCIe / to peers since it was created (povu_hip_transfer_bytes)
 	uint64_t xfer_h2d = 0, xfer_d2h = 0, xfer_peer_out = 0, xfer_peer_in = 0;

@@ -24,6 +24,7 @@ struct ResidentGraph {
 	// device time of the last upload, by HIP events: host-to-device copies, CSR build, reverse-slot table
 	float h2d_ms = 0, csr_ms = 0, twin_ms = 0;
 	void *block = nullptr;			    // one allocation backing all of the above
+	uint64_t gen = 0;			    // upload generation (unique per process; povu_hip_forest_walks checks a forest against it)
 };
 
 static constexpr uint32_t LLE_ID = 0x1FFFFFFFu, LLE_TREE = 0x40000000u; // lle words (below)

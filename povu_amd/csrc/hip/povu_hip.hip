@@ -4,6 +4,7 @@
 #include "context.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <memory>
 #include <mutex>
@@ -169,6 +170,26 @@ void free_resident_graph(ResidentGraph &g)
 	g = ResidentGraph{}; // the block belongs to the context's graph arena, which keeps it for the next graph
 }
 
+extern "C" int povu_hip_release_workspace(povu_hip_ctx *ctx)
+{
+	if (!ctx)
+		return 1;
+	(void)hipSetDevice(ctx->device);
+	ctx->quiesce();
+	ctx->wait_tail();
+	(void)hipStreamSynchronize(ctx->stream);
+	ctx->have_state = false; // (the debug exports read the stage workspace)
+	ctx->ws.release();
+	ctx->ws_b.release();
+	ctx->ws2.release();
+	ctx->ws_seq.release();
+	ctx->ws_leaf.release();
+	ctx->ws_walk.release();
+	ctx->ws_sub.release();
+	ctx->upload_tmp.release();
+	return 0;
+}
+
 extern "C" void povu_hip_destroy(povu_hip_ctx *ctx)
 {
 	if (!ctx)
@@ -180,6 +201,8 @@ extern "C" void povu_hip_destroy(povu_hip_ctx *ctx)
 	ctx->ws2.release();
 	ctx->ws_seq.release();
 	ctx->ws_walk.release();
+	ctx->wk_ws.release();
+	ctx->wk_out.release();
 	ctx->ws_b.release();
 	ctx->upload_tmp.release();
 	ctx->shard_buf.release();
@@ -214,9 +237,11 @@ extern "C" void povu_hip_destroy(povu_hip_ctx *ctx)
 // arena (which only reallocates when a graph is larger than every one before it; the previous graph is gone afterwards)
 void alloc_resident_graph(Arena &arena, ResidentGraph &g, uint32_t n_vtx, uint32_t n_links, bool tips_given)
 {
+	static std::atomic<uint64_t> next_gen{1};
 	g.V = n_vtx;
 	g.E = n_links;
 	g.tips_given = tips_given;
+	g.gen = next_gen.fetch_add(1);
 	const size_t V = n_vtx, E = n_links;
 	const size_t bytes = Arena::padded(V, 4) + 2 * Arena::padded(E + 1, 4) + 2 * Arena::padded(E + 1, 1) + Arena::padded(V, 1) +
 			     Arena::padded(2 * V + 2, 4) + 3 * Arena::padded(2 * E + 8, 4) + 16 * 256;
@@ -1296,6 +1321,10 @@ extern "C" povu_hip_forest *povu_hip_decompose(povu_hip_ctx *ctx, const povu_hip
 		}
 		ctx->C = C;
 		ctx->have_state = true;
+		if (o.world == 1 && ctx->shard_comp_ids.empty()) { // (povu_hip_forest_walks: a forest of the whole resident graph)
+			f->walk_ctx = ctx;
+			f->walk_gen = g.gen;
+		}
 		return f.release();
 	} catch (const std::exception &e) {
 		if (ctx && ctx->stream)

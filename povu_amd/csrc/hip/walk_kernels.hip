@@ -1,0 +1,666 @@
+// walk_kernels.hip -- the walks of every flubble of a forest (povu_hip_forest_walks, include/povu_hip.h).
+//
+// The definition is this project's own ("Flubble walks"): the reference's enum_walks is a BFS whose output
+// depends on its queue cap and on std::set indices, so it is not restated.  A query is one PVST vertex (start step S, end
+// step Z); its walks are what a DFS from S yields that tries the successors of a step by ascending (segment id, '>' first),
+// never repeats a segment and stops at Z -- with three caps: walks (K), steps per walk (L), expansions (E).
+//
+// A step is kept as the side it ENTERS its segment by: (u, '>') enters through l = 2u, (u, '<') through r = 2u + 1, and
+// leaves through the other side (y ^ 1).  Segment ids ascend with the vertex index (checked), so the successor order
+// (id, '>' before '<') is the plain order of the entered sides, and the successors of a step are the other ends (aoth) of
+// its exit side's slots, ascending -- `ssucc`, one sorted copy of the adjacency per call.  Parallel links are equal
+// neighbours in that copy and count once.
+//
+// Shape: a count pass, an exclusive scan of walks and steps per query, an emit pass that runs the same DFS again and writes
+// into the scanned offsets.  Each pass has two tiers:
+//   tier 1: one lane per query, the DFS stack in LDS (T1_DEPTH frames, T1_EXPANSIONS expansions).  Leaf bubbles -- nearly
+//           every query -- end here.  A query that would need more is handed over (flag + compaction);
+//   tier 2: one lane per query, every lane taking its next query from an atomic work counter when it is done with one (a
+//           long query does not hold up a wave of short ones), the stack in global scratch (L frames per lane) beside a
+//           hash set of the segments on the path (the on-path test in O(1) at any depth).
+// Both passes run the same function (dfs below), so the emit pass writes exactly what the count pass sized; it still
+// checks every write against the query's own range.
+#include "context.hpp"
+
+namespace povu_hip
+{
+
+static constexpr int W_TPB = 256;
+static constexpr uint32_t T1_DEPTH = 16;	 // frames of a tier-1 stack (LDS: 16 x 256 x 8 B = 32 KiB per block)
+static constexpr uint32_t T1_EXPANSIONS = 4096; // expansions tier 1 spends before it hands a query over
+static constexpr uint32_t SORT_IN_LANE = 64;	 // sides up to this many slots are sorted by one lane
+static constexpr uint8_t ST_MORE = POVU_HIP_WALK_MORE, ST_LONG = POVU_HIP_WALK_LONG, ST_BUDGET = POVU_HIP_WALK_BUDGET;
+static constexpr uint32_t NO_QUERY = 0xFFFFFFFFu;
+
+static inline unsigned wblk(size_t n) { return (unsigned)((n + W_TPB - 1) / W_TPB); }
+
+struct WalkCaps {
+	uint32_t K, L, E;
+};
+
+// ---- the sorted successor copy
+
+// one lane per side: insertion-sort the side's other ends into ssucc when the side is small; a larger side only sets
+// *hub (the host then sorts every slot with the radix sort, below)
+__global__ void k_wk_ssucc(uint32_t nS, const uint32_t *__restrict__ off, const uint32_t *__restrict__ aoth,
+			      uint32_t *__restrict__ ssucc, uint32_t *__restrict__ hub)
+{
+	const uint32_t x = blockIdx.x * W_TPB + threadIdx.x;
+	if (x >= nS)
+		return;
+	const uint32_t b = off[x], e = off[x + 1];
+	if (e - b > SORT_IN_LANE) {
+		atomicOr(hub, 1u);
+		return;
+	}
+	for (uint32_t i = b; i < e; i++) {
+		const uint32_t v = aoth[i];
+		uint32_t j = i;
+		while (j > b && ssucc[j - 1] > v) {
+			ssucc[j] = ssucc[j - 1];
+			j--;
+		}
+		ssucc[j] = v;
+	}
+}
+
+// side of every slot (the key of the second, stable sort of the hub path)
+__global__ void k_wk_slot_side(uint32_t nS, const uint32_t *__restrict__ off, uint32_t *__restrict__ side_of)
+{
+	const uint32_t x = blockIdx.x * W_TPB + threadIdx.x;
+	if (x >= nS)
+		return;
+	for (uint32_t i = off[x], e = off[x + 1]; i < e; i++)
+		side_of[i] = x;
+}
+
+// ---- queries
+
+// segment ids must ascend with the vertex index (binary search; successor order = side order)
+__global__ void k_wk_vid_ascending(uint32_t V, const uint32_t *__restrict__ vid, uint32_t *__restrict__ bad)
+{
+	const uint32_t i = blockIdx.x * W_TPB + threadIdx.x;
+	if (i + 1 < V && vid[i] >= vid[i + 1])
+		atomicOr(bad, 1u);
+}
+
+__device__ __forceinline__ uint32_t find_vertex(const uint32_t *__restrict__ vid, uint32_t V, uint32_t id)
+{
+	uint32_t lo = 0, hi = V;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (vid[mid] < id)
+			lo = mid + 1;
+		else
+			hi = mid;
+	}
+	return (lo < V && vid[lo] == id) ? lo : NO_QUERY;
+}
+
+// (id, orientation) of both boundaries -> entered sides; a query whose two boundaries are one segment has no walk (NO_QUERY)
+__global__ void k_wk_resolve(uint32_t n, const uint32_t *__restrict__ qa, const uint32_t *__restrict__ qz,
+			       const uint8_t *__restrict__ qor, const uint32_t *__restrict__ vid, uint32_t V, uint32_t *__restrict__ ys,
+			       uint32_t *__restrict__ yz, uint32_t *__restrict__ bad)
+{
+	const uint32_t q = blockIdx.x * W_TPB + threadIdx.x;
+	if (q >= n)
+		return;
+	const uint32_t a = find_vertex(vid, V, qa[q]), z = find_vertex(vid, V, qz[q]);
+	if (a == NO_QUERY || z == NO_QUERY) {
+		atomicOr(bad, 2u);
+		ys[q] = yz[q] = NO_QUERY;
+		return;
+	}
+	const uint8_t o = qor[q];
+	ys[q] = a == z ? NO_QUERY : 2 * a + (o & 1u);
+	yz[q] = a == z ? NO_QUERY : 2 * z + ((o >> 1) & 1u);
+}
+
+// ---- the DFS (both tiers, both passes)
+
+struct DfsResult {
+	uint32_t walks, steps;
+	uint8_t status;
+	bool handover; // tier 1 only: the query needs more than the tier's limits
+};
+
+// where the emit pass writes the walks of one query
+struct WalkSink {
+	uint32_t *step_off, *step_id;
+	uint8_t *step_or;
+	const uint32_t *vid;
+	uint32_t w0, w_end, s0, s_end; // walks [w0, w_end), steps [s0, s_end) of this query
+};
+
+// One lane, stack in LDS: frame k of lane t at [k * W_TPB + t] (consecutive lanes, consecutive banks).
+struct LaneStack {
+	uint32_t *sy, *sc;
+	uint32_t t;
+	static constexpr uint32_t cap = T1_DEPTH;
+	__device__ uint32_t y(uint32_t k) const { return sy[k * W_TPB + t]; }
+	__device__ uint32_t cur(uint32_t k) const { return sc[k * W_TPB + t]; }
+	__device__ void set_cur(uint32_t k, uint32_t c) { sc[k * W_TPB + t] = c; }
+	__device__ void push(uint32_t k, uint32_t yy, uint32_t c)
+	{
+		sy[k * W_TPB + t] = yy;
+		sc[k * W_TPB + t] = c;
+	}
+	__device__ void pop(uint32_t) {}
+	__device__ bool on_path(uint32_t u, uint32_t depth) const
+	{
+		for (uint32_t k = 0; k < depth; k++)
+			if ((y(k) >> 1) == u)
+				return true;
+		return false;
+	}
+	__device__ void write_walk(const WalkSink &o, uint32_t w, uint32_t at, uint32_t depth, uint32_t yz) const
+	{
+		if (w >= o.w_end || at + depth + 1 > o.s_end)
+			return; // (cannot happen: the count pass ran the same search)
+		o.step_off[w] = at;
+		for (uint32_t k = 0; k < depth; k++) {
+			const uint32_t yy = y(k);
+			o.step_id[at + k] = o.vid[yy >> 1];
+			o.step_or[at + k] = (uint8_t)(yy & 1u);
+		}
+		o.step_id[at + depth] = o.vid[yz >> 1];
+		o.step_or[at + depth] = (uint8_t)(yz & 1u);
+	}
+};
+
+// One lane, stack in global scratch (L frames of its own): frame k at [k * stride] (the lanes of a wave side by side).  The
+// segments on the path are also kept in an open-addressed set of `tmask + 1` >= 2 L slots (linear probing, key = segment + 1,
+// 0 = empty, deletion by backward shift), so that "is u on the path" costs a probe or two however deep the stack is.
+struct GlobalStack {
+	uint32_t *sy, *sc, *tab;
+	uint32_t stride;
+	uint32_t cap;
+	uint32_t tbits;
+	__device__ uint32_t y(uint32_t k) const { return sy[(size_t)k * stride]; }
+	__device__ uint32_t cur(uint32_t k) const { return sc[(size_t)k * stride]; }
+	__device__ void set_cur(uint32_t k, uint32_t c) { sc[(size_t)k * stride] = c; }
+	__device__ uint32_t home(uint32_t u) const { return (u * 2654435761u) >> (32 - tbits); }
+	__device__ uint32_t &slot(uint32_t i) const { return tab[(size_t)i * stride]; }
+	__device__ void push(uint32_t k, uint32_t yy, uint32_t c)
+	{
+		sy[(size_t)k * stride] = yy;
+		sc[(size_t)k * stride] = c;
+		const uint32_t mask = (1u << tbits) - 1u, u = yy >> 1;
+		uint32_t i = home(u);
+		while (slot(i) != 0)
+			i = (i + 1) & mask;
+		slot(i) = u + 1;
+	}
+	__device__ void pop(uint32_t yy)
+	{
+		const uint32_t mask = (1u << tbits) - 1u, key = (yy >> 1) + 1;
+		uint32_t i = home(yy >> 1);
+		while (slot(i) != key)
+			i = (i + 1) & mask;
+		for (uint32_t j = (i + 1) & mask;; j = (j + 1) & mask) { // backward shift: close the gap at i
+			const uint32_t kj = slot(j);
+			if (kj == 0)
+				break;
+			const uint32_t h = home(kj - 1);
+			// kj may move to i when its home does not lie cyclically in (i, j]
+			if (((j - h) & mask) >= ((j - i) & mask)) {
+				slot(i) = kj;
+				i = j;
+			}
+		}
+		slot(i) = 0;
+	}
+	__device__ bool on_path(uint32_t u, uint32_t) const
+	{
+		const uint32_t mask = (1u << tbits) - 1u;
+		for (uint32_t i = home(u);; i = (i + 1) & mask) {
+			const uint32_t kk = slot(i);
+			if (kk == 0)
+				return false;
+			if (kk == u + 1)
+				return true;
+		}
+	}
+	__device__ void write_walk(const WalkSink &o, uint32_t w, uint32_t at, uint32_t depth, uint32_t yz) const
+	{
+		if (w >= o.w_end || at + depth + 1 > o.s_end)
+			return;
+		o.step_off[w] = at;
+		for (uint32_t k = 0; k < depth; k++) {
+			const uint32_t yy = y(k);
+			o.step_id[at + k] = o.vid[yy >> 1];
+			o.step_or[at + k] = (uint8_t)(yy & 1u);
+		}
+		o.step_id[at + depth] = o.vid[yz >> 1];
+		o.step_or[at + depth] = (uint8_t)(yz & 1u);
+	}
+};
+
+// The search of one query.  `ecap` <= E expansions and `st.cap` frames are what this tier may use: needing more hands the
+// query over (tier 1); tier 2 is called with ecap = E and room for L frames.
+template <bool EMIT, class Stack>
+__device__ DfsResult dfs(Stack &st, const uint32_t *__restrict__ off, const uint32_t *__restrict__ ssucc, uint32_t ys, uint32_t yz,
+			 WalkCaps c, uint32_t ecap, const WalkSink &sink)
+{
+	DfsResult r{0, 0, 0, false};
+	if (ys == NO_QUERY)
+		return r;
+	const uint32_t uz = yz >> 1;
+	if (c.L <= 1) { // the prefix [S] already has L steps
+		r.status = ST_LONG;
+		return r;
+	}
+	st.push(0, ys, off[ys ^ 1u]);
+	uint32_t depth = 1, exp = 0;
+	while (depth > 0) {
+		const uint32_t top = depth - 1;
+		const uint32_t yt = st.y(top);
+		const uint32_t beg = off[yt ^ 1u], end = off[(yt ^ 1u) + 1];
+		uint32_t cur = st.cur(top), nxt = NO_QUERY;
+		while (cur < end) {
+			const uint32_t cand = ssucc[cur++];
+			if (cur - 1 > beg && ssucc[cur - 2] == cand)
+				continue; // a parallel link: the same step again
+			const uint32_t u = cand >> 1;
+			if (u == uz) {
+				if (cand == yz) {
+					nxt = cand;
+					break;
+				}
+				continue; // Z's segment in the other orientation: a walk cannot pass through it
+			}
+			if (st.on_path(u, depth))
+				continue;
+			nxt = cand;
+			break;
+		}
+		st.set_cur(top, cur);
+		if (nxt == NO_QUERY) { // exhausted: back up
+			st.pop(yt);
+			depth--;
+			continue;
+		}
+		if (exp == c.E) {
+			r.status |= ST_BUDGET;
+			break;
+		}
+		if (exp == ecap) {
+			r.handover = true;
+			break;
+		}
+		exp++;
+		if (nxt == yz) {
+			if (r.walks == c.K) {
+				r.status |= ST_MORE;
+				break;
+			}
+			if (EMIT)
+				st.write_walk(sink, sink.w0 + r.walks, sink.s0 + r.steps, depth, yz);
+			r.walks++;
+			r.steps += depth + 1;
+			continue;
+		}
+		if (depth + 1 >= c.L) { // a prefix of L steps that does not end at Z is not extended
+			r.status |= ST_LONG;
+			continue;
+		}
+		if (depth == st.cap) {
+			r.handover = true;
+			break;
+		}
+		st.push(depth, nxt, off[nxt ^ 1u]);
+		depth++;
+	}
+	while (depth > 0) { // (stopped early: empty tier 2's path set for the next query)
+		st.pop(st.y(depth - 1));
+		depth--;
+	}
+	return r;
+}
+
+// tier 1, count pass: one lane per query.  Hands over (flag) what needs more than T1_DEPTH frames or T1_EXPANSIONS.
+template <bool EMIT>
+__global__ __launch_bounds__(W_TPB) void k_wk_t1(uint32_t n, const uint32_t *__restrict__ off, const uint32_t *__restrict__ ssucc,
+						   const uint32_t *__restrict__ ys, const uint32_t *__restrict__ yz, WalkCaps c, uint32_t force2,
+						   uint32_t *__restrict__ cntw, uint32_t *__restrict__ cnts, uint8_t *__restrict__ status,
+						   uint8_t *__restrict__ handover, const uint32_t *__restrict__ woff,
+						   const uint32_t *__restrict__ sbase, WalkSink sink)
+{
+	__shared__ uint32_t sy[T1_DEPTH * W_TPB], sc[T1_DEPTH * W_TPB];
+	const uint32_t q = blockIdx.x * W_TPB + threadIdx.x;
+	if (q >= n)
+		return;
+	if (EMIT && handover[q])
+		return;
+	if (!EMIT && force2) {
+		handover[q] = 1;
+		return;
+	}
+	LaneStack st{sy, sc, threadIdx.x};
+	if (EMIT) {
+		sink.w0 = woff[q];
+		sink.w_end = sink.w0 + cntw[q];
+		sink.s0 = sbase[q];
+		sink.s_end = sink.s0 + cnts[q];
+	}
+	const DfsResult r = dfs<EMIT>(st, off, ssucc, ys[q], yz[q], c, c.E < T1_EXPANSIONS ? c.E : T1_EXPANSIONS, sink);
+	if (EMIT)
+		return;
+	handover[q] = r.handover ? 1 : 0;
+	cntw[q] = r.handover ? 0 : r.walks;
+	cnts[q] = r.handover ? 0 : r.steps;
+	status[q] = r.handover ? 0 : r.status;
+}
+
+// tier 2: one lane per query of `list`, every lane taking its next query from `*next` (zeroed before the launch) as soon as
+// it is done with one; `lanes` lanes, lane i's words in scratch at [i, i + lanes, ...): 2 L stack words, then 2^tbits path-set
+// slots (zeroed before the launch; every search leaves its set empty)
+template <bool EMIT>
+__global__ __launch_bounds__(W_TPB) void k_wk_t2(const uint32_t *__restrict__ list, uint32_t n2, uint32_t *__restrict__ next,
+						 uint32_t lanes, uint32_t tbits, const uint32_t *__restrict__ off, const uint32_t *__restrict__ ssucc,
+						 const uint32_t *__restrict__ ys, const uint32_t *__restrict__ yz, WalkCaps c, uint32_t *scratch,
+						 uint32_t *__restrict__ cntw, uint32_t *__restrict__ cnts, uint8_t *__restrict__ status,
+						 const uint32_t *__restrict__ woff, const uint32_t *__restrict__ sbase, WalkSink sink)
+{
+	const uint32_t lane = blockIdx.x * W_TPB + threadIdx.x;
+	if (lane >= lanes)
+		return;
+	GlobalStack st{scratch + lane, scratch + (size_t)lanes * c.L + lane, scratch + (size_t)lanes * 2 * c.L + lane, lanes, c.L, tbits};
+	for (;;) {
+		const uint32_t k = atomicAdd(next, 1u);
+		if (k >= n2)
+			break;
+		const uint32_t q = list[k];
+		if (EMIT) {
+			sink.w0 = woff[q];
+			sink.w_end = sink.w0 + cntw[q];
+			sink.s0 = sbase[q];
+			sink.s_end = sink.s0 + cnts[q];
+		}
+		const DfsResult r = dfs<EMIT>(st, off, ssucc, ys[q], yz[q], c, c.E, sink);
+		if (!EMIT) {
+			cntw[q] = r.walks;
+			cnts[q] = r.steps;
+			status[q] = r.status;
+		}
+	}
+}
+
+// totals of walks and steps in 64 bits (the scans run in 32: the call is refused when a total does not fit)
+__global__ void k_wk_totals(uint32_t n, const uint32_t *__restrict__ cntw, const uint32_t *__restrict__ cnts,
+			      unsigned long long *__restrict__ tot)
+{
+	__shared__ unsigned long long sw, ss;
+	if (threadIdx.x == 0)
+		sw = ss = 0;
+	__syncthreads();
+	unsigned long long w = 0, s = 0;
+	for (uint32_t q = blockIdx.x * W_TPB + threadIdx.x; q < n; q += gridDim.x * W_TPB) {
+		w += cntw[q];
+		s += cnts[q];
+	}
+	atomicAdd(&sw, w);
+	atomicAdd(&ss, s);
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		atomicAdd(&tot[0], sw);
+		atomicAdd(&tot[1], ss);
+	}
+}
+
+} // namespace povu_hip
+
+// ---- C ABI
+
+namespace
+{
+struct WalksOwner {
+	povu_hip_walks view{}; // first member: the owner is recovered from it in povu_hip_walks_free
+	PinnedVec<uint32_t> walk_off, step_off, step_id;
+	PinnedVec<uint8_t> step_or, status;
+};
+} // namespace
+
+extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_forest *f, const povu_hip_walk_opts *opts, char *err,
+						 size_t errlen)
+{
+	XferScope xfer(ctx);
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	auto drop_events = [&] {
+		if (e0)
+			(void)hipEventDestroy(e0);
+		if (e1)
+			(void)hipEventDestroy(e1);
+		e0 = e1 = nullptr;
+	};
+	try {
+		if (!ctx || !f)
+			throw HipError("null context or forest");
+		if (!f->walk_ctx)
+			throw HipError("walks need a forest made by povu_hip_decompose of a whole resident graph (not a sharded, merged or attached forest)");
+		if (f->walk_ctx != ctx || !ctx->g.block || f->walk_gen != ctx->g.gen)
+			throw HipError("the forest was not decomposed from the graph now resident on this context (it was uploaded again, or the forest belongs to another context)");
+		WalkCaps c{64, 1000, 65536};
+		uint32_t flags = 0;
+		if (opts) {
+			if (opts->max_walks)
+				c.K = opts->max_walks;
+			if (opts->max_steps)
+				c.L = opts->max_steps;
+			if (opts->max_expansions)
+				c.E = opts->max_expansions;
+			flags = opts->flags;
+		}
+		if (c.L > (1u << 24))
+			throw HipError("max_steps above 2^24");
+		HIP_CHECK(hipSetDevice(ctx->device));
+		ctx->wait_tail();
+		f->ready();
+		const ResidentGraph &g = ctx->g;
+		hipStream_t s = ctx->stream;
+
+		// ---- the queries, in tree order then PVST vertex order, roots skipped
+		const uint32_t n_trees = (uint32_t)f->trees.size();
+		std::vector<uint32_t> qa, qz;
+		std::vector<uint8_t> qor;
+		for (uint32_t i = 0; i < n_trees; i++) {
+			povu_hip_subtree st;
+			if (povu_hip_forest_get_subtree(f, i, &st) == 0) {
+				for (uint32_t v = 1; v < st.n_total; v++) {
+					qa.push_back(st.id1[v]);
+					qz.push_back(st.id2[v]);
+					qor.push_back((uint8_t)((st.or1[v] & 1u) | ((st.or2[v] & 1u) << 1)));
+				}
+				continue;
+			}
+			povu_hip_tree t;
+			if (povu_hip_forest_get(f, i, &t) != 0)
+				throw HipError("forest tree " + std::to_string(i) + " unreadable");
+			for (uint32_t v = 1; v < t.n_pvst; v++) {
+				qa.push_back(t.a_id[v]);
+				qz.push_back(t.z_id[v]);
+				qor.push_back((uint8_t)((t.a_or[v] & 1u) | ((t.z_or[v] & 1u) << 1)));
+			}
+		}
+		if (qa.size() >= 0xFFFFFFFFull)
+			throw HipError("too many queries for 32-bit indices");
+		const uint32_t n = (uint32_t)qa.size();
+		const uint32_t nS = 2 * g.V;
+		const size_t slots = g.n_slots;
+
+		// ---- workspace: queries, counts, offsets, hand-over list, the sorted successors
+		const size_t n1 = (size_t)n + 1;
+		const size_t scan_b = scan_tmp_bytes(n1) + 256, comp_b = compact_tmp_bytes(n1) + 256;
+		const size_t ws_b = Arena::padded(n1, 4) * 9 + Arena::padded(n1, 1) * 3 + Arena::padded(8, 4) + scan_b + comp_b +
+				    Arena::padded(slots + 8, 4) + Arena::padded(2, 8) + 16 * 256;
+		ctx->wk_ws.reserve(ws_b);
+		Arena &A = ctx->wk_ws;
+		uint32_t *d_qa = A.take<uint32_t>(n1), *d_qz = A.take<uint32_t>(n1);
+		uint8_t *d_qor = A.take<uint8_t>(n1);
+		uint32_t *ys = A.take<uint32_t>(n1), *yz = A.take<uint32_t>(n1);
+		uint32_t *cntw = A.take<uint32_t>(n1), *cnts = A.take<uint32_t>(n1), *woff = A.take<uint32_t>(n1),
+			 *sbase = A.take<uint32_t>(n1), *list2 = A.take<uint32_t>(n1), *words = A.take<uint32_t>(8);
+		uint8_t *status = A.take<uint8_t>(n1), *handover = A.take<uint8_t>(n1);
+		unsigned long long *tot = A.take<unsigned long long>(2);
+		void *scan_tmp = A.take<char>(scan_b), *comp_tmp = A.take<char>(comp_b);
+		uint32_t *ssucc = A.take<uint32_t>(slots + 8);
+
+		HIP_CHECK(hipEventCreate(&e0));
+		HIP_CHECK(hipEventCreate(&e1));
+		HIP_CHECK(hipEventRecord(e0, s));
+		HIP_CHECK(hipMemsetAsync(words, 0, 8 * 4, s));
+		HIP_CHECK(hipMemsetAsync(tot, 0, 16, s));
+		if (n) {
+			HIP_CHECK(copy_async(d_qa, qa.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+			HIP_CHECK(copy_async(d_qz, qz.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+			HIP_CHECK(copy_async(d_qor, qor.data(), n, hipMemcpyHostToDevice, s));
+		}
+		// words: [0] vid not ascending | query boundary not found, [1] hand-over count, [2] / [3] tier-2 work counter of the
+		// count / emit pass, [4] a side has more than SORT_IN_LANE slots
+		KLAUNCH(k_wk_vid_ascending, dim3(wblk(g.V)), dim3(W_TPB), 0, s, g.V, g.vid, words);
+		if (n)
+			KLAUNCH(k_wk_resolve, dim3(wblk(n)), dim3(W_TPB), 0, s, n, d_qa, d_qz, d_qor, g.vid, g.V, ys, yz, words);
+		if (nS)
+			KLAUNCH(k_wk_ssucc, dim3(wblk(nS)), dim3(W_TPB), 0, s, nS, g.off, g.aoth, ssucc, words + 4);
+		uint32_t hw[8] = {0};
+		HIP_CHECK(copy_async(hw, words, 32, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		if (hw[0] & 1u)
+			throw HipError("walks need segment ids that ascend with the vertex index (the order the GFA loader gives)");
+		if (hw[0] & 2u)
+			throw HipError("a flubble boundary of the forest is no segment of the resident graph");
+		if (hw[4] && slots) { // a hub side: every slot's (other end, side) pair, sorted by other end, then stably by side
+			const size_t sort_b = sort_tmp_bytes(slots) + 256;
+			ctx->wk_out.reserve(4 * Arena::padded(slots + 8, 4) + sort_b + 8 * 256); // (free until the count pass's tier 2)
+			Arena &B = ctx->wk_out;
+			uint32_t *side_of = B.take<uint32_t>(slots + 8), *k1 = B.take<uint32_t>(slots + 8), *v1 = B.take<uint32_t>(slots + 8),
+				 *k2 = B.take<uint32_t>(slots + 8);
+			void *sort_tmp = B.take<char>(sort_b);
+			KLAUNCH(k_wk_slot_side, dim3(wblk(nS)), dim3(W_TPB), 0, s, nS, g.off, side_of);
+			const unsigned bits = bits_for(nS);
+			sort_pairs_u32(g.aoth, k1, side_of, v1, slots, bits, sort_tmp, sort_b, s);
+			sort_pairs_u32(v1, k2, k1, ssucc, slots, bits, sort_tmp, sort_b, s);
+			HIP_CHECK(hipStreamSynchronize(s)); // (the next reserve of wk_out may free these arrays)
+		}
+
+		// ---- count pass
+		const bool force2 = (flags & POVU_HIP_W_FORCE_TIER2) != 0;
+		WalkSink none{};
+		uint32_t n2 = 0;
+		if (n) {
+			KLAUNCH(k_wk_t1<false>, dim3(wblk(n)), dim3(W_TPB), 0, s, n, g.off, ssucc, ys, yz, c, force2 ? 1u : 0u, cntw, cnts,
+				status, handover, woff, sbase, none);
+			compact_flagged_u8(handover, n, list2, words + 1, comp_tmp, comp_b, s);
+			HIP_CHECK(copy_async(&n2, words + 1, 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipStreamSynchronize(s));
+		}
+		// tier-2 lanes: 2 L stack words + a path set of 2^tbits >= 2 L slots each, at most 16384 lanes and 256 MiB
+		uint32_t lanes = 0;
+		const uint32_t tbits = std::max(4u, bits_for(2 * (uint64_t)c.L - 1));
+		const size_t lane_words = (size_t)2 * c.L + (size_t(1) << tbits);
+		if (n2) {
+			lanes = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)n2, 16384, (size_t(256) << 20) / (lane_words * 4)}));
+			ctx->wk_out.reserve(Arena::padded((size_t)lanes * lane_words, 4) + 256);
+			uint32_t *scratch = ctx->wk_out.take<uint32_t>((size_t)lanes * lane_words);
+			HIP_CHECK(hipMemsetAsync(scratch + (size_t)lanes * 2 * c.L, 0, (size_t)lanes * (lane_words - 2 * (size_t)c.L) * 4, s));
+			KLAUNCH(k_wk_t2<false>, dim3(wblk(lanes)), dim3(W_TPB), 0, s, list2, n2, words + 2, lanes, tbits, g.off, ssucc, ys, yz, c,
+				scratch, cntw, cnts, status, woff, sbase, none);
+		}
+		uint64_t ht[2] = {0, 0};
+		if (n) {
+			KLAUNCH(k_wk_totals, dim3(std::min<unsigned>(wblk(n), 1024)), dim3(W_TPB), 0, s, n, cntw, cnts, tot);
+			HIP_CHECK(copy_async(ht, tot, 16, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipStreamSynchronize(s));
+		}
+		const uint64_t n_walks = ht[0], n_steps = ht[1];
+		if (n_walks >= 0xFFFFFFFFull || n_steps >= 0xFFFFFFFFull)
+			throw HipError("the walks do not fit 32-bit offsets: " + std::to_string(n_walks) + " walks, " + std::to_string(n_steps) +
+				       " steps (lower max_walks / max_steps)");
+
+		// ---- offsets, then the emit pass into them
+		uint32_t *step_off = nullptr, *step_id = nullptr;
+		uint8_t *step_or = nullptr;
+		if (n) {
+			HIP_CHECK(hipMemsetAsync(cntw + n, 0, 4, s));
+			HIP_CHECK(hipMemsetAsync(cnts + n, 0, 4, s));
+			scan_exclusive_u32_pair(cntw, woff, n1, cnts, sbase, n1, scan_tmp, scan_b, s);
+			const size_t scratch_b = lanes ? Arena::padded((size_t)lanes * lane_words, 4) : 0;
+			const size_t out_b = scratch_b + Arena::padded(n_walks + 1, 4) + Arena::padded(n_steps + 1, 4) +
+					     Arena::padded(n_steps + 1, 1) + 4 * 256;
+			uint32_t *scratch = nullptr;
+			if (out_b > ctx->wk_out.capacity()) {
+				size_t free_b = 0, total_b = 0;
+				(void)hipMemGetInfo(&free_b, &total_b);
+				if (out_b > free_b + ctx->wk_out.capacity())
+					throw HipError("the walks do not fit device memory: " + std::to_string(out_b >> 20) + " MiB needed, " +
+						       std::to_string(free_b >> 20) + " MiB free");
+			}
+			HIP_CHECK(hipStreamSynchronize(s)); // (the count pass's tier 2 used the scratch of wk_out)
+			ctx->wk_out.reserve(out_b);
+			if (lanes) {
+				scratch = ctx->wk_out.take<uint32_t>((size_t)lanes * lane_words);
+				HIP_CHECK(hipMemsetAsync(scratch + (size_t)lanes * 2 * c.L, 0, (size_t)lanes * (lane_words - 2 * (size_t)c.L) * 4, s));
+			}
+			step_off = ctx->wk_out.take<uint32_t>(n_walks + 1);
+			step_id = ctx->wk_out.take<uint32_t>(n_steps + 1);
+			step_or = ctx->wk_out.take<uint8_t>(n_steps + 1);
+			WalkSink sink{step_off, step_id, step_or, g.vid, 0, 0, 0, 0};
+			KLAUNCH(k_wk_t1<true>, dim3(wblk(n)), dim3(W_TPB), 0, s, n, g.off, ssucc, ys, yz, c, 0u, cntw, cnts, status, handover,
+				woff, sbase, sink);
+			if (lanes)
+				KLAUNCH(k_wk_t2<true>, dim3(wblk(lanes)), dim3(W_TPB), 0, s, list2, n2, words + 3, lanes, tbits, g.off, ssucc, ys, yz, c,
+					scratch, cntw, cnts, status, woff, sbase, sink);
+		}
+
+		// ---- to the host
+		auto o = std::make_unique<WalksOwner>();
+		o->walk_off.resize(n1, ctx->pool);
+		o->step_off.resize(n_walks + 1, ctx->pool);
+		o->status.resize(n1, ctx->pool);
+		if (n_steps) {
+			o->step_id.resize(n_steps, ctx->pool);
+			o->step_or.resize(n_steps, ctx->pool);
+		}
+		if (n) {
+			HIP_CHECK(copy_async(o->walk_off.data(), woff, n1 * 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(copy_async(o->status.data(), status, n, hipMemcpyDeviceToHost, s));
+			if (n_walks)
+				HIP_CHECK(copy_async(o->step_off.data(), step_off, n_walks * 4, hipMemcpyDeviceToHost, s));
+			if (n_steps) {
+				HIP_CHECK(copy_async(o->step_id.data(), step_id, n_steps * 4, hipMemcpyDeviceToHost, s));
+				HIP_CHECK(copy_async(o->step_or.data(), step_or, n_steps, hipMemcpyDeviceToHost, s));
+			}
+		} else {
+			o->walk_off[0] = 0;
+		}
+		HIP_CHECK(hipEventRecord(e1, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		o->step_off[n_walks] = (uint32_t)n_steps;
+		float ms = 0;
+		(void)hipEventElapsedTime(&ms, e0, e1);
+		drop_events();
+		o->view.n_queries = n;
+		o->view.n_walks = n_walks;
+		o->view.n_steps = n_steps;
+		o->view.walk_off = o->walk_off.data();
+		o->view.step_off = o->step_off.data();
+		o->view.step_id = o->step_id.data();
+		o->view.step_or = o->step_or.data();
+		o->view.status = o->status.data();
+		o->view.n_tier2 = n2;
+		o->view.device_ms = ms;
+		WalksOwner *raw = o.release();
+		return &raw->view;
+	} catch (const std::exception &e) {
+		if (ctx && ctx->stream)
+			(void)hipStreamSynchronize(ctx->stream);
+		drop_events();
+		set_err(err, errlen, e.what());
+		return nullptr;
+	}
+}
+
+extern "C" void povu_hip_walks_free(povu_hip_walks *w)
+{
+	delete reinterpret_cast<WalksOwner *>(w);
+}

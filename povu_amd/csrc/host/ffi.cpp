@@ -4,8 +4,10 @@
 #include "../../../include/povu_hip.h"
 #include "gfa.hpp"
 
+#include <algorithm>
 #include <cstring>
 #include <filesystem>
+#include <mutex>
 #include <thread>
 #include <fstream>
 #include <string>
@@ -31,6 +33,21 @@ struct PovuFlubbles {
 	PovuForest forest;
 	size_t pvst_vertices = 0;
 	PovuGraph *graph = nullptr;
+	// povu_flubbles_get: the context whose resident graph the forest was decomposed from (kept until povu_flubbles_free, its
+	// decompose workspaces given back), the first flubble index of every tree, and the walks of the whole forest, computed by
+	// the first get that succeeds (a failed computation is tried again by the next get; its message is kept in walks_err)
+	povu_hip_ctx *ctx = nullptr;
+	std::vector<size_t> tree_first;
+	std::mutex walks_m;
+	povu_hip_walks *walks = nullptr;
+	std::string walks_err;
+	~PovuFlubbles()
+	{
+		povu_hip_walks_free(walks);
+		povu_hip_forest_free(forest.f);
+		forest.f = nullptr;
+		povu_hip_destroy(ctx);
+	}
 };
 struct PovuPvstTree {
 	const PovuFlubbles *owner;
@@ -251,7 +268,8 @@ bool povu_graph_set_references_from_prefixes(PovuGraph *g, const char **prefixes
 	return true;
 }
 
-static povu_hip_forest *run_decompose(PovuGraph *g, int device, int hairpins, PovuError *error)
+// keep_ctx: on success the context (with the graph resident) is handed to the caller instead of destroyed
+static povu_hip_forest *run_decompose(PovuGraph *g, int device, int hairpins, PovuError *error, povu_hip_ctx **keep_ctx = nullptr)
 {
 	if (g->ids.empty()) {
 		set_error(error, 1, "graph has no vertices");
@@ -285,7 +303,11 @@ static povu_hip_forest *run_decompose(PovuGraph *g, int device, int hairpins, Po
 		povu_hip_opts o{0, 1, (hairpins ? POVU_HIP_F_HAIRPINS : 0u) | POVU_HIP_F_NO_STAGE_TIMES}; // (no per-stage timers: the pass starts kernels ahead of its host reads)
 		f = povu_hip_decompose(ctx, &o, err, sizeof err);
 	}
-	povu_hip_destroy(ctx);
+	if (f && keep_ctx) {
+		*keep_ctx = ctx;
+		povu_hip_release_workspace(ctx); // (only the resident graph is needed from here on)
+	} else
+		povu_hip_destroy(ctx);
 	if (!f)
 		set_error(error, 1, err);
 	return f;
@@ -298,16 +320,19 @@ PovuFlubbles *povu_graph_find_flubbles(PovuGraph *graph, PovuError *error)
 		return nullptr;
 	}
 	try {
-		povu_hip_forest *f = run_decompose(graph, 0, 0, error);
+		povu_hip_ctx *ctx = nullptr;
+		povu_hip_forest *f = run_decompose(graph, 0, 0, error, &ctx);
 		if (!f)
 			return nullptr;
 		auto *fl = new PovuFlubbles();
 		fl->forest.f = f;
 		fl->graph = graph;
+		fl->ctx = ctx;
 		size_t flub = 0;
 		for (uint32_t i = 0; i < povu_hip_forest_tree_count(f); i++) {
 			povu_hip_tree t;
 			povu_hip_forest_get(f, i, &t);
+			fl->tree_first.push_back(flub + 1);
 			flub += t.n_pvst - 1;
 		}
 		fl->pvst_vertices = flub + 1;
@@ -319,7 +344,68 @@ PovuFlubbles *povu_graph_find_flubbles(PovuGraph *graph, PovuError *error)
 }
 void povu_flubbles_free(PovuFlubbles *f) { delete f; }
 size_t povu_flubbles_count(const PovuFlubbles *f) { return f ? f->pvst_vertices : 0; }
-PovuFlubble *povu_flubbles_get(const PovuFlubbles *, size_t) { return nullptr; }
+// Flubble i >= 1 is PVST vertex i - tree_first[t] + 1 of tree t: the forest's trees side by side under one dummy root (0).
+// Its walks are those of povu_hip_forest_walks with the default caps, for the whole forest on the first call.
+PovuFlubble *povu_flubbles_get(const PovuFlubbles *cf, size_t index)
+{
+	if (!cf || index == 0 || index >= cf->pvst_vertices || !cf->ctx)
+		return nullptr;
+	auto *f = const_cast<PovuFlubbles *>(cf);
+	try {
+		const povu_hip_walks *w = nullptr;
+		{
+			std::lock_guard<std::mutex> lk(f->walks_m);
+			if (!f->walks) {
+				char err[512] = {0};
+				f->walks = povu_hip_forest_walks(f->ctx, f->forest.f, nullptr, err, sizeof err);
+				f->walks_err = f->walks ? std::string() : std::string(err);
+			}
+			w = f->walks;
+		}
+		if (!w)
+			return nullptr;
+		const size_t t = (size_t)(std::upper_bound(f->tree_first.begin(), f->tree_first.end(), index) - f->tree_first.begin()) - 1;
+		const uint32_t v = (uint32_t)(index - f->tree_first[t] + 1);
+		povu_hip_tree tr;
+		if (povu_hip_forest_get(f->forest.f, (uint32_t)t, &tr) != 0 || v >= tr.n_pvst)
+			return nullptr;
+		const uint8_t *fam = nullptr;
+		const char *type = "flubble";
+		if (povu_hip_forest_get_sub(f->forest.f, (uint32_t)t, nullptr, nullptr, &fam) == 0 && fam)
+			switch (fam[v]) {
+			case 'T': type = "tiny"; break;
+			case 'O': type = "parallel"; break;
+			case 'C': type = "concealed"; break;
+			case 'M': type = "midi"; break;
+			case 'S': type = "smothered"; break;
+			default: break;
+			}
+		const size_t q = index - 1, w0 = w->walk_off[q], w1 = w->walk_off[q + 1];
+		auto *out = new PovuFlubble();
+		out->id = index;
+		out->type_name = type;
+		out->start_vertex_id = tr.a_id[v];
+		out->end_vertex_id = tr.z_id[v];
+		out->walks_count = w1 - w0;
+		out->walks = out->walks_count ? new PovuStep *[out->walks_count]() : nullptr;
+		out->walk_lengths = out->walks_count ? new size_t[out->walks_count] : nullptr;
+		try {
+			for (size_t k = 0; k < out->walks_count; k++) {
+				const size_t a = w->step_off[w0 + k], b = w->step_off[w0 + k + 1];
+				out->walk_lengths[k] = b - a;
+				out->walks[k] = new PovuStep[b - a];
+				for (size_t j = a; j < b; j++)
+					out->walks[k][j - a] = PovuStep{w->step_id[j], w->step_or[j] ? POVU_ORIENTATION_REVERSE : POVU_ORIENTATION_FORWARD};
+			}
+		} catch (...) {
+			povu_flubble_free(out);
+			return nullptr;
+		}
+		return out;
+	} catch (...) {
+		return nullptr;
+	}
+}
 void povu_flubble_free(PovuFlubble *fl) // :413-424
 {
 	if (!fl)

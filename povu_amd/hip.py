@@ -53,6 +53,17 @@ class _MultiRank(C.Structure):
                 ("peer_in", C.c_uint64)]
 
 
+class _WalkOpts(C.Structure):
+    _fields_ = [("max_walks", C.c_uint32), ("max_steps", C.c_uint32), ("max_expansions", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class _Walks(C.Structure):
+    _fields_ = [("n_queries", C.c_uint64), ("n_walks", C.c_uint64), ("n_steps", C.c_uint64),
+                ("walk_off", C.POINTER(C.c_uint32)), ("step_off", C.POINTER(C.c_uint32)), ("step_id", C.POINTER(C.c_uint32)),
+                ("step_or", C.POINTER(C.c_uint8)), ("status", C.POINTER(C.c_uint8)), ("n_tier2", C.c_uint64),
+                ("device_ms", C.c_double)]
+
+
 class _StageTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("launches", C.c_uint32)]
 
@@ -71,6 +82,9 @@ F_CHECK_LAMINAR = 1024
 F_LEAF_SUBFLUBBLES = 2048
 F_ASYNC = 4096
 F_SUBFLUBBLES = 8192  # all five passes of -s (implies F_LEAF_SUBFLUBBLES): Forest.texts() then carry C / M / S lines
+
+W_FORCE_TIER2 = 1  # HipDecomposer.walks: every query through the second-tier kernel (tests)
+WALK_MORE, WALK_LONG, WALK_BUDGET = 1, 2, 4  # status bits of a query
 
 _lib = None
 
@@ -116,6 +130,9 @@ def load_lib():
     l.povu_hip_forest_raw.restype = C.c_int
     l.povu_hip_forest_raw.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
                                       C.POINTER(C.c_uint64)]
+    l.povu_hip_forest_walks.restype = C.POINTER(_Walks)
+    l.povu_hip_forest_walks.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_WalkOpts), C.c_char_p, C.c_size_t]
+    l.povu_hip_walks_free.argtypes = [C.POINTER(_Walks)]
     l.povu_hip_forest_first.restype = C.c_uint64
     l.povu_hip_forest_first.argtypes = [C.c_void_p, C.c_uint32]
     l.povu_hip_forest_pvst_text.restype = C.c_void_p
@@ -418,6 +435,50 @@ class Forest:
         return out
 
 
+class Walks:
+    """Walks of every query of a forest (HipDecomposer.walks): numpy views of the flat arrays of povu_hip_forest_walks --
+    walk_off [n_queries + 1], step_off [n_walks + 1], step_id / step_or [n_steps], status [n_queries] -- valid as long as
+    this object lives.  Queries are numbered in tree order, then PVST vertex order within the tree, each root skipped."""
+
+    def __init__(self, lib, ptr, forest: "Forest", first_query: List[int]):
+        self._lib, self._p = lib, ptr
+        w = ptr.contents
+        self.n_queries, self.n_walks, self.n_steps = int(w.n_queries), int(w.n_walks), int(w.n_steps)
+        self.n_tier2, self.device_ms = int(w.n_tier2), float(w.device_ms)
+        view = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)) if n else np.zeros(0, dt)  # noqa: E731
+        self.walk_off = view(w.walk_off, self.n_queries + 1, np.uint32)
+        self.step_off = view(w.step_off, self.n_walks + 1, np.uint32)
+        self.step_id = view(w.step_id, self.n_steps, np.uint32)
+        self.step_or = view(w.step_or, self.n_steps, np.uint8)
+        self.status = view(w.status, self.n_queries, np.uint8)
+        self._first = first_query  # query number of PVST vertex 1 of every tree
+        self._forest = forest
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            self._lib.povu_hip_walks_free(self._p)
+            self._p = None
+
+    def query(self, tree_index: int, pvst_vertex: int) -> int:
+        """Query number of a PVST vertex (not the root)."""
+        n = (self._first[tree_index + 1] if tree_index + 1 < len(self._first) else self.n_queries) - self._first[tree_index]
+        if not 1 <= pvst_vertex <= n:
+            raise IndexError((tree_index, pvst_vertex))
+        return self._first[tree_index] + pvst_vertex - 1
+
+    def walks_of_query(self, q: int):
+        out = []
+        for w in range(int(self.walk_off[q]), int(self.walk_off[q + 1])):
+            a, b = int(self.step_off[w]), int(self.step_off[w + 1])
+            out.append([(int(i), ">" if o == 0 else "<") for i, o in zip(self.step_id[a:b].tolist(), self.step_or[a:b].tolist())])
+        return out
+
+    def of(self, tree_index: int, pvst_vertex: int):
+        """([[(segment id, '>' | '<'), ...], ...], status bits) of PVST vertex `pvst_vertex` of tree `tree_index`."""
+        q = self.query(tree_index, pvst_vertex)
+        return self.walks_of_query(q), int(self.status[q])
+
+
 class Shards:
     """Device-resident partition of a resident graph into per-rank packed shards (povu_hip_shard_partition)."""
 
@@ -590,6 +651,29 @@ class HipDecomposer:
         if not h:
             raise RuntimeError(err.value.decode())
         return Forest(self._lib, h)
+
+    def walks(self, forest: Forest, max_walks: int = 64, max_steps: int = 1000, max_expansions: int = 65536,
+              flags: int = 0) -> Walks:
+        """The walks of every flubble of `forest` (a decompose of the graph now resident here), on the GPU."""
+        for k, v in (("max_walks", max_walks), ("max_steps", max_steps), ("max_expansions", max_expansions)):
+            if not 1 <= int(v) < 2 ** 32:
+                raise ValueError(f"{k} must be in [1, 2^32)")
+        o = _WalkOpts(max_walks, max_steps, max_expansions, flags)
+        err = C.create_string_buffer(512)
+        p = self._lib.povu_hip_forest_walks(self._ctx, forest._h, C.byref(o), err, 512)
+        if not p:
+            raise RuntimeError(err.value.decode())
+        first, q = [], 0
+        st = _SubTree()
+        t = _Tree()
+        for i in range(len(forest)):
+            first.append(q)
+            if self._lib.povu_hip_forest_get_subtree(forest._h, i, C.byref(st)) == 0:
+                q += st.n_total - 1
+            else:
+                self._lib.povu_hip_forest_get(forest._h, i, C.byref(t))
+                q += t.n_pvst - 1
+        return Walks(self._lib, p, forest, first)
 
     def stage_times(self) -> List[dict]:
         buf = (_StageTime * 64)()
