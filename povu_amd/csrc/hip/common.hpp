@@ -159,26 +159,33 @@ public:
 	{
 		for (auto &c : chunks_)
 			(void)hipHostFree(c.p);
-		if (ev_)
-			(void)hipEventDestroy(ev_);
+		for (hipEvent_t e : events_)
+			(void)hipEventDestroy(e);
 	}
 	HostScratch() = default;
 	HostScratch(const HostScratch &) = delete;
 	HostScratch &operator=(const HostScratch &) = delete;
 	// Words a kernel published into a span of this scratch (publish_words, or a kernel that writes page-locked memory itself)
 	// are read WITHOUT leaving the stream idle: mark() right behind the publishing kernel, then the stream is given the
-	// kernels that do not depend on the words, then wait() -- the host wakes up while they run.
-	void mark(hipStream_t s)
+	// kernels that do not depend on the words, then wait() on what mark() returned -- the host wakes up while they run.
+	// Every mark() of a pass takes an event of its own from a pool the scratch keeps (reset() gives them all back).
+	using Token = size_t;
+	Token mark(hipStream_t s)
 	{
-		if (!ev_)
-			HIP_CHECK(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
-		HIP_CHECK(hipEventRecord(ev_, s));
+		if (marks_ == events_.size()) {
+			hipEvent_t e = nullptr;
+			HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+			events_.push_back(e);
+		}
+		HIP_CHECK(hipEventRecord(events_[marks_], s));
+		return marks_++;
 	}
-	void wait() { HIP_CHECK(hipEventSynchronize(ev_)); }
+	void wait(Token t) { HIP_CHECK(hipEventSynchronize(events_[t])); }
 	void reset()
 	{
 		for (auto &c : chunks_)
 			c.top = 0;
+		marks_ = 0;
 	}
 	template <typename T>
 	T *take(size_t n)
@@ -210,7 +217,8 @@ private:
 		size_t cap, top;
 	};
 	std::vector<Chunk> chunks_;
-	hipEvent_t ev_ = nullptr;
+	std::vector<hipEvent_t> events_;
+	size_t marks_ = 0; // events_[0, marks_) recorded since the last reset()
 };
 
 // HIP-event stage timer on the context's stream.

@@ -13,6 +13,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <numeric>
 #include <string>
 
 using namespace povu_hip;
@@ -134,10 +135,10 @@ struct povu_hip_forest {
 	double pass_ms = -1.0;
 	// a merged forest took over blocks whose arrays were still on their way: the events behind those passes (owned here)
 	std::vector<hipEvent_t> more_events;
-	// (may be reached from several threads at once -- the writer threads of `povu decompose` read one forest: the waits are
-	// idempotent, and the pass time is taken exactly once)
-	std::once_flag pass_ms_once;
-	void ready()
+	// (may be reached from several threads at once -- the writer threads of `povu decompose` read one forest: the waits and
+	// the pass time are taken exactly once, and the destructor goes through the same flag)
+	std::once_flag ready_once;
+	void wait_arrays()
 	{
 		if (pending) {
 			if (ev1)
@@ -146,12 +147,15 @@ struct povu_hip_forest {
 				(void)hipEventSynchronize(e);
 			pending = false;
 		}
-		if (ev0 && ev1)
-			std::call_once(pass_ms_once, [this] {
-				float ms = 0;
-				if (pass_ms < 0 && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess)
-					pass_ms = ms;
-			});
+	}
+	void ready()
+	{
+		std::call_once(ready_once, [this] {
+			wait_arrays();
+			float ms = 0;
+			if (ev0 && ev1 && pass_ms < 0 && hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess)
+				pass_ms = ms;
+		});
 	}
 	std::shared_ptr<PinnedPool> pool;
 	void *block = nullptr;
@@ -159,23 +163,29 @@ struct povu_hip_forest {
 	int block_seg = -1;	 // shared-memory segment of the block (PinnedPool shared mode), else -1
 	size_t meta_reserve = 0; // trees the block leaves room for behind the arrays (povu_hip_forest_share writes their table there)
 	static size_t meta_bytes(size_t n_trees) { return 64 + 32 * n_trees; }
+	// the five arrays of a block of `total` PVST vertices, each padded to 64 B: a | z | parent | a_or | z_or; returns the
+	// bytes they take (out == nullptr: only measures)
+	struct Arrays {
+		uint32_t *a = nullptr, *z = nullptr, *parent = nullptr;
+		uint8_t *aor = nullptr, *zor = nullptr;
+	};
+	static size_t layout(void *q, size_t total, Arrays *out = nullptr)
+	{
+		const size_t w = (total * 4 + 63) & ~size_t(63), b = (total + 63) & ~size_t(63);
+		if (out) {
+			char *c = static_cast<char *>(q);
+			out->a = (uint32_t *)c, out->z = (uint32_t *)(c + w), out->parent = (uint32_t *)(c + 2 * w);
+			out->aor = (uint8_t *)(c + 3 * w), out->zor = (uint8_t *)(c + 3 * w + b);
+		}
+		return 3 * w + 2 * b;
+	}
 	void alloc(size_t total)
 	{
 		total_entries = total;
-		const size_t bytes = ((total * 4 + 63) & ~size_t(63)) * 3 + ((total + 63) & ~size_t(63)) * 2 + 64 + meta_bytes(meta_reserve);
-		block = pool->get(bytes, block_cap, &block_seg);
-		char *q = static_cast<char *>(block);
-		auto carve = [&](size_t b) {
-			char *r = q;
-			q += (b + 63) & ~size_t(63);
-			return r;
-		};
-		a_id.p = (uint32_t *)carve(total * 4);
-		z_id.p = (uint32_t *)carve(total * 4);
-		parent.p = (uint32_t *)carve(total * 4);
-		a_or.p = (uint8_t *)carve(total);
-		z_or.p = (uint8_t *)carve(total);
-		block_bytes = (size_t)(q - static_cast<char *>(block));
+		block = pool->get(layout(nullptr, total) + 64 + meta_bytes(meta_reserve), block_cap, &block_seg);
+		Arrays x;
+		block_bytes = layout(block, total, &x);
+		a_id.p = x.a, z_id.p = x.z, parent.p = x.parent, a_or.p = x.aor, z_or.p = x.zor;
 	}
 	void release_block()
 	{
@@ -187,42 +197,25 @@ struct povu_hip_forest {
 	}
 	// more page-locked blocks with the same five arrays: taken over from other forests or received from other ranks
 	// (povu_hip_forest_merge / povu_hip_comm_gather), so that merging never copies a PVST array
-	struct ExtraBlock {
+	struct ExtraBlock : Arrays {
 		void *p = nullptr;
 		size_t cap = 0, total = 0;
 		int seg = -1;
 		std::shared_ptr<PinnedPool> pool; // null: the memory is not this forest's (a segment of another rank, mapped by the context)
-		uint32_t *a = nullptr, *z = nullptr, *parent = nullptr;
-		uint8_t *aor = nullptr, *zor = nullptr;
 		PinnedVec<uint32_t> sub_ai, sub_zi; // with POVU_HIP_F_LEAF_SUBFLUBBLES (see the forest's own sub_ai)
 		PinnedVec<uint8_t> sub_fam;
 		std::shared_ptr<SubForest> subx;
 		void carve(size_t total_entries)
 		{
 			total = total_entries;
-			char *q = static_cast<char *>(p);
-			auto take = [&](size_t b) {
-				char *r = q;
-				q += (b + 63) & ~size_t(63);
-				return r;
-			};
-			a = (uint32_t *)take(total * 4);
-			z = (uint32_t *)take(total * 4);
-			parent = (uint32_t *)take(total * 4);
-			aor = (uint8_t *)take(total);
-			zor = (uint8_t *)take(total);
+			layout(p, total, this);
 		}
-		static size_t bytes_for(size_t total) { return ((total * 4 + 63) & ~size_t(63)) * 3 + ((total + 63) & ~size_t(63)) * 2 + 64; }
+		static size_t bytes_for(size_t total) { return layout(nullptr, total) + 64; }
 	};
 	std::vector<ExtraBlock> extra;
 	~povu_hip_forest()
 	{
-		if (pending) { // the copy engine may still be writing the blocks
-			if (ev1)
-				(void)hipEventSynchronize(ev1);
-			for (hipEvent_t e : more_events)
-				(void)hipEventSynchronize(e);
-		}
+		std::call_once(ready_once, [this] { wait_arrays(); }); // (the copy engine may still be writing the blocks)
 		if (ev0)
 			(void)hipEventDestroy(ev0);
 		if (ev1)
@@ -264,6 +257,31 @@ struct povu_hip_forest {
 	uint64_t walk_gen = 0;
 };
 
+// What a pass does, decided once from its options (plan_pass in povu_hip.hip).
+// all_seq: every stage on the one-lane kernels; seq_tree / par_tree: the tree stage on the one-lane / parallel kernels;
+// leaf_sub: the leaf subflubble passes (find_tiny, find_parallel); all_sub: all five passes of -s; timed: stage times;
+// overlap_tail: POVU_HIP_F_ASYNC on the one pass that has that form (the tail may overlap the next pass); heaviest_first:
+// components in LPT order (shard assignment, launch order of the one-lane kernels).
+struct PassPlan {
+	uint32_t rank = 0, world = 1;
+	bool hairpins = false, all_seq = false, seq_tree = false, par_tree = true, leaf_sub = false, all_sub = false;
+	bool sorted_adj = false, force_redo = false, redo_odd = false;
+	bool big_class_dfs = false, sparse_splitters = false, all_vertex_classes = false, check_laminar = false;
+	bool timed = true, overlap_tail = false, heaviest_first = false;
+};
+
+// What the last decompose of a context left in its stage workspace (debug / parity hooks): with plan.par_tree the
+// parallel tree stage's per-side state, unless plan.all_seq the classes in the parallel stage's own array (pw.gcls).
+struct LastPass {
+	bool valid = false; // false: no state, or a pass failed or something else has used the workspace since
+	PassPlan plan;
+	uint32_t C = 0, seq_redo = 0; // components, and those through the sequential redo
+	// mixed: SOME components redone (the stage state is half parallel layout, half sequential); redo_pvst_only: the redo
+	// only re-ran add_flubbles (tree, classes and stack are the parallel stages'); stack_export_pending: the parallel
+	// stages' candidate stack is still in its dense layout
+	bool mixed = false, redo_pvst_only = false, stack_export_pending = false;
+};
+
 struct povu_hip_ctx {
 	int device = 0;
 	hipStream_t stream = nullptr;
@@ -278,18 +296,11 @@ struct povu_hip_ctx {
 	std::vector<povu_hip_stage_time> last_times;
 	uint64_t last_links = 0;
 	// device state of the last decompose (debug / parity hooks)
-	bool have_state = false;
-	uint32_t C = 0;
 	CompState cs{};
 	SeqWs sw{};
 	ParWs pw{};
 	TreeWs tw{};
-	uint32_t last_seq_redo = 0;
-	bool redo_pvst_only = false; // the last redo only re-ran add_flubbles: tree, classes and stack are the parallel stages'
-	bool last_mixed = false; // the last pass redid SOME components sequentially: the stage state is half parallel layout, half sequential
-	bool stack_export_pending = false; // the parallel stages' candidate stack is still in its dense layout
-	bool tree_in_par = false;	   // the tree of the last pass came from the parallel kernels (their per-side state is still there)
-	bool classes_in_par = false;	   // the classes of the last pass sit in the parallel stage's own array (pw.gcls)
+	LastPass last;
 	// when the resident graph is a shard (povu_hip_graph_upload_shard): ids of its components in the whole graph
 	// (1-based, ascending = the shard's own component order) and the component count of the whole graph
 	std::vector<uint32_t> shard_comp_ids;
@@ -300,7 +311,6 @@ struct povu_hip_ctx {
 	// behind it; the next pass waits for it before it touches that workspace, every other entry point before anything
 	hipEvent_t tail_done = nullptr;
 	SideStream walk_side; // the wave walks' second stream (tree stage: the two forms of the walk run side by side)
-	hipEvent_t host_wait = nullptr; // recorded behind a kernel whose words the host reads while LATER kernels already run (povu_hip_decompose)
 	bool tail_pending = false;
 	void wait_tail()
 	{
@@ -344,6 +354,24 @@ struct XferScope {
 };
 
 
+// Greedy longest-processing-time assignment of n weighted components to `world` ranks, the same on every rank: `order`
+// gets the components heaviest first (stable), owner[c] the least-loaded rank at c's turn (each component adds weight + 1).
+static inline void lpt_assign(const uint64_t *weights, uint32_t n, uint32_t world, uint32_t *order, uint32_t *owner)
+{
+	std::iota(order, order + n, 0u);
+	std::stable_sort(order, order + n, [&](uint32_t a, uint32_t b) { return weights[a] > weights[b]; });
+	std::vector<uint64_t> load(world, 0);
+	for (uint32_t k = 0; k < n; k++) {
+		const uint32_t c = order[k];
+		uint32_t best = 0;
+		for (uint32_t r = 1; r < world; r++)
+			if (load[r] < load[best])
+				best = r;
+		owner[c] = best;
+		load[best] += weights[c] + 1;
+	}
+}
+
 // device block of a resident graph (link arrays + CSR); build_global_csr fills the CSR part
 void alloc_resident_graph(Arena &arena, ResidentGraph &g, uint32_t n_vtx, uint32_t n_links, bool tips_given);
 void free_resident_graph(ResidentGraph &g);
@@ -351,7 +379,8 @@ void check_graph_size(uint32_t n_vtx, uint32_t n_links);
 void set_err(char *err, size_t errlen, const std::string &msg);
 
 struct Sizes {
-	size_t V, E, Cmax, T, B, nS, slots;
+	size_t V, E, Cmax, T, B, nS, slots; // (rows A/B are sized before the component count is known: Cmax = V, T = B = 0)
+	void set_components(size_t C) { Cmax = C, T = 2 * V + C, B = E + V + 2 * T; }
 };
 // Rows A/B in two steps (povu_hip_decompose): before the components are labelled only what the labelling writes is carved
 // (rowb_carve_label); what the re-index needs follows when the component count, the order of the vertices and the

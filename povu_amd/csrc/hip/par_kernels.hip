@@ -1363,13 +1363,13 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	publish_words(extra, WordSrc{{tcap + ntiles, tsimp + ntiles, pw.err + 5, pw.err + 6}}, 4, s); // counts | literal-rule flag | back edges of the tree stage
 	// The stream is not left idle while the host reads them (HostScratch::mark): the kernel that places the capping and
 	// simplifying brackets takes the counts from the device, and the scan behind it does not need them at all.
-	pw.host->mark(s);
+	const HostScratch::Token extra_ready = pw.host->mark(s);
 	LAUNCH(k_bracket_extra, ((size_t)T + 3) / 4, s, T, NB0, dense_nb0 == NB0_ON_DEVICE ? pw.err + 6 : nullptr, ntiles,
 	       (uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu), capf, tcap, simp, tsimp, pw.cap_tgt, root_of, pw.b_src, pw.b_tgt,
 	       dense_nb0 >= 0 ? pw.lsz : nullptr, pw.gsize, pw.mpre, pw.incnt, srccnt);
 	if (dense_nb0 >= 0) // ranks inside every source and the counts per source are known: place directly
 		scan2(pw.incnt, pw.psin, (size_t)T + 1, srccnt, bstart, (size_t)T + 1);
-	pw.host->wait();
+	pw.host->wait(extra_ready);
 	if (dense_nb0 == NB0_ON_DEVICE) {
 		NB0 = extra[3];
 		if (NB0 > pw.nb_cap)
@@ -1486,7 +1486,7 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 		HIP_CHECK(hipEventRecord(side.fork, s));
 	// The stream is not left idle while the host reads the PVST count (HostScratch::mark): levels and parents of the
 	// flubbles need the stack only, their kernels go out first.
-	pw.host->mark(s);
+	const HostScratch::Token early_ready = pw.host->mark(s);
 	// The (prev, i) intervals of exact cycle-equivalence classes never cross ("Row G"): the laminarity
 	// check is only needed when the literal hi_2 rule capped differently from the second-highest reach (extra[2]), i.e. when
 	// the classes may not be the exact ones -- or when a caller asks for it.  Without it nothing that follows can flag a
@@ -1510,7 +1510,7 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	LAUNCH(k_walk_bias, ((size_t)S + 3) / 4, s, S, pw.walk, pw.walk_ps, wb, wneg);
 	scan_exclusive_max_u32(wneg, wrun, (size_t)S, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	LAUNCH(k_levels, ((size_t)S + 3) / 4, s, S, dflag, pw.erank, pw.s_comp, pw.soff, wb, wrun, pw.lev, pw.e_i);
-	pw.host->wait();
+	pw.host->wait(early_ready);
 	const size_t total = early[4 + 4 * (size_t)C + C]; // doff[C] = flubbles + one root per processed component
 	if (total < n_processed || total - n_processed > S)
 		throw HipError("internal error: PVST size out of range");

@@ -156,7 +156,6 @@ extern "C" povu_hip_ctx *povu_hip_create(int device, char *err, size_t errlen)
 		HIP_CHECK(hipEventCreateWithFlags(&ctx->walk_side.fork, hipEventDisableTiming));
 		HIP_CHECK(hipEventCreateWithFlags(&ctx->walk_side.join, hipEventDisableTiming));
 		HIP_CHECK(hipEventCreateWithFlags(&ctx->tail_done, hipEventDisableTiming));
-		HIP_CHECK(hipEventCreateWithFlags(&ctx->host_wait, hipEventDisableTiming));
 		ctx->timer.stream = ctx->stream;
 		return ctx.release();
 	} catch (const std::exception &e) {
@@ -178,7 +177,7 @@ extern "C" int povu_hip_release_workspace(povu_hip_ctx *ctx)
 	ctx->quiesce();
 	ctx->wait_tail();
 	(void)hipStreamSynchronize(ctx->stream);
-	ctx->have_state = false; // (the debug exports read the stage workspace)
+	ctx->last.valid = false; // (the debug exports read the stage workspace)
 	ctx->ws.release();
 	ctx->ws_b.release();
 	ctx->ws2.release();
@@ -228,8 +227,6 @@ extern "C" void povu_hip_destroy(povu_hip_ctx *ctx)
 		(void)hipEventDestroy(ctx->walk_side.join);
 	if (ctx->tail_done)
 		(void)hipEventDestroy(ctx->tail_done);
-	if (ctx->host_wait)
-		(void)hipEventDestroy(ctx->host_wait);
 	delete ctx;
 }
 
@@ -282,7 +279,7 @@ extern "C" int povu_hip_graph_upload(povu_hip_ctx *ctx, uint32_t n_vtx, const ui
 		ctx->wait_tail(); // (an overlapped pass may still be reading its workspace)
 		// the old graph (or shard) goes first, whatever happens next: a failed upload leaves the context without a graph
 		free_resident_graph(ctx->g);
-		ctx->have_state = false;
+		ctx->last.valid = false;
 		ctx->shard_comp_ids.clear();
 		ctx->shard_total_components = 0;
 		check_graph_size(n_vtx, n_links);
@@ -554,16 +551,10 @@ extern "C" povu_hip_components *povu_hip_componetize(povu_hip_ctx *ctx, char *er
 		ctx->wait_tail();
 		const ResidentGraph &g = ctx->g;
 		hipStream_t s = ctx->stream;
-		Sizes z;
-		z.V = g.V;
-		z.E = g.E;
-		z.Cmax = g.V;
-		z.nS = 2 * z.V;
-		z.slots = g.n_slots;
-		z.T = z.B = 0;
+		const Sizes z{g.V, g.E, g.V, 0, 0, 2 * (size_t)g.V, g.n_slots};
 		CompState &cs = ctx->cs;
 		SeqWs &sw = ctx->sw;
-		ctx->have_state = false;
+		ctx->last.valid = false;
 		ctx->host.reset();
 		cs.host = &ctx->host;
 		cs.host_pub = nullptr;
@@ -638,22 +629,14 @@ static StageWsOpts stage_opts(size_t V, size_t E, size_t C, size_t empty_sides, 
 extern "C" uint64_t povu_hip_workspace_estimate(uint32_t n_vtx, uint32_t n_links, uint32_t n_components)
 {
 	try {
-		Sizes z;
-		z.V = n_vtx;
-		z.E = n_links;
-		z.nS = 2 * z.V;
-		z.slots = 2 * z.E;
+		Sizes z{n_vtx, n_links, n_vtx, 0, 0, 2 * (size_t)n_vtx, 2 * (size_t)n_links};
 		CompState cs{};
 		SeqWs sw{};
-		z.Cmax = n_vtx;
-		z.T = z.B = 0;
 		// (rows A/B of a graph whose vertices come grouped by component, without hub vertices or self loops: the pangenome
 		// case; povu_hip_workspace_breakdown's out[6] has the general case)
 		const RowBNeeds lean{true, true, false};
 		uint64_t total = rowb_carve_label(nullptr, z, cs) + rowb_carve_reindex(nullptr, z, n_components ? n_components : n_vtx, lean, cs);
-		z.Cmax = n_components ? n_components : n_vtx;
-		z.T = 2 * z.V + z.Cmax;
-		z.B = z.E + z.V + 2 * z.T;
+		z.set_components(n_components ? n_components : n_vtx);
 		// (sides without links: two per component and a few more -- an estimate; a graph full of tips reserves more)
 		total += carve_workspace(nullptr, 1, z, cs, sw, false) +
 			 stage_workspace_bytes(z.V, z.E, z.Cmax, stage_opts(z.V, z.E, z.Cmax, 2 * z.Cmax + z.V / 64, false, false));
@@ -666,19 +649,14 @@ extern "C" uint64_t povu_hip_workspace_estimate(uint32_t n_vtx, uint32_t n_links
 extern "C" int povu_hip_workspace_breakdown(uint32_t n_vtx, uint32_t n_links, uint32_t n_components, uint64_t out[7])
 {
 	try {
-		Sizes z;
-		z.V = n_vtx, z.E = n_links, z.nS = 2 * z.V, z.slots = 2 * z.E;
+		Sizes z{n_vtx, n_links, n_vtx, 0, 0, 2 * (size_t)n_vtx, 2 * (size_t)n_links};
 		CompState cs{};
 		SeqWs sw{};
-		z.Cmax = n_vtx;
-		z.T = z.B = 0;
 		const RowBNeeds lean{true, true, false}, general{false, false, true};
 		const size_t Cn = n_components ? n_components : n_vtx;
 		out[0] = rowb_carve_label(nullptr, z, cs) + rowb_carve_reindex(nullptr, z, Cn, lean, cs);
 		out[6] = rowb_carve_label(nullptr, z, cs) + rowb_carve_reindex(nullptr, z, Cn, general, cs);
-		z.Cmax = Cn;
-		z.T = 2 * z.V + z.Cmax;
-		z.B = z.E + z.V + 2 * z.T;
+		z.set_components(Cn);
 		out[1] = carve_workspace(nullptr, 1, z, cs, sw, false);
 		const StageWsOpts so = stage_opts(z.V, z.E, z.Cmax, 2 * z.Cmax + z.V / 64, false, false);
 		out[2] = par_workspace_bytes(z.V, z.E, z.Cmax, 1, so);
@@ -702,7 +680,7 @@ extern "C" int povu_hip_prewarm(povu_hip_ctx *ctx, uint32_t n_vtx, uint32_t n_li
 		if (!ctx)
 			throw HipError("null context");
 		ctx->wait_tail();
-		if (ctx->g.block || ctx->have_state)
+		if (ctx->g.block || ctx->last.valid)
 			return 0; // (only for a context that holds nothing yet: a reserve invalidates what an arena holds)
 		check_graph_size(n_vtx, n_links);
 		HIP_CHECK(hipSetDevice(ctx->device));
@@ -721,8 +699,7 @@ extern "C" int povu_hip_prewarm(povu_hip_ctx *ctx, uint32_t n_vtx, uint32_t n_li
 		SeqWs sw{};
 		z.Cmax = std::min<size_t>(V, std::max<size_t>(1024, V / 64));
 		const size_t ws_b = rowb_carve_label(nullptr, z, cs), ws_b2 = rowb_carve_reindex(nullptr, z, z.Cmax, RowBNeeds{true, true, false}, cs);
-		z.T = 2 * V + z.Cmax;
-		z.B = E + V + 2 * z.T;
+		z.set_components(z.Cmax);
 		const size_t ws2_b = carve_workspace(nullptr, 1, z, cs, sw, false) +
 				     stage_workspace_bytes(V, E, z.Cmax, stage_opts(V, E, z.Cmax, 2 * z.Cmax + V / 64, false, false));
 		const size_t need = graph_b + tmp_b + ws_b + ws_b2 + ws2_b;
@@ -747,6 +724,600 @@ extern "C" uint64_t povu_hip_leaf_workspace_estimate(uint32_t n_vtx, uint32_t n_
 	return leaf_workspace_bytes(n_vtx, n_components ? n_components : n_vtx, (size_t)n_vtx + (n_components ? n_components : n_vtx));
 }
 
+// ---- povu_hip_decompose: the plan of a pass, then its steps
+namespace
+{
+
+static const char *const SUB_REDO_REFUSAL = "subflubble passes: a component went (or was sent) through the sequential redo of add_flubbles, "
+					    "whose PVST layout the inserting passes do not read";
+
+// Every decision a pass takes from its options, in one place.  Refusals that depend on the flags alone are made here;
+// those that depend on what the pass finds (a component the laminarity check flags) where it finds it.
+static PassPlan plan_pass(const povu_hip_opts *opts)
+{
+	povu_hip_opts o{0, 1, 0};
+	if (opts)
+		o = *opts;
+	if (o.world == 0)
+		o.world = 1;
+	if (o.rank >= o.world)
+		throw HipError("shard rank >= world");
+	auto has = [&](uint32_t flag) { return (o.flags & flag) != 0; };
+	PassPlan p;
+	p.rank = o.rank, p.world = o.world, p.hairpins = has(POVU_HIP_F_HAIRPINS), p.timed = !has(POVU_HIP_F_NO_STAGE_TIMES);
+	p.all_seq = has(POVU_HIP_F_SEQUENTIAL), p.seq_tree = has(POVU_HIP_F_SEQ_TREE), p.par_tree = !p.all_seq && !p.seq_tree;
+	p.all_sub = has(POVU_HIP_F_SUBFLUBBLES), p.leaf_sub = p.all_sub || has(POVU_HIP_F_LEAF_SUBFLUBBLES);
+	p.force_redo = has(POVU_HIP_F_FORCE_REDO), p.redo_odd = has(POVU_HIP_F_REDO_ODD), p.sorted_adj = has(POVU_HIP_F_SORTED_ADJ);
+	p.big_class_dfs = has(POVU_HIP_F_BIG_CLASS_DFS), p.sparse_splitters = has(POVU_HIP_F_SPARSE_SPLITTERS);
+	p.all_vertex_classes = has(POVU_HIP_F_ALL_VERTEX_CLASSES), p.check_laminar = has(POVU_HIP_F_CHECK_LAMINAR);
+	// POVU_HIP_F_ASYNC: the pass may leave its last kernels and the copies of the PVST arrays in flight when it returns
+	// (and the next pass may then start under them).  Only the plain all-parallel pass has that form.
+	p.overlap_tail = has(POVU_HIP_F_ASYNC) && !p.timed && p.par_tree && !p.hairpins && !p.force_redo && !p.redo_odd && !p.leaf_sub &&
+			 !p.check_laminar;
+	// heaviest first: the shard assignment and the launch order of the one-lane kernels (the parallel stages do not care,
+	// so a single-shard parallel pass skips the sort)
+	p.heaviest_first = p.world > 1 || p.all_seq || p.seq_tree || p.force_redo;
+	if (p.leaf_sub && (p.all_seq || p.seq_tree))
+		throw HipError("the leaf subflubble passes read the state of the parallel stages: not with the sequential tree / all-sequential test modes");
+	if (p.all_sub && (p.force_redo || p.redo_odd) && !p.hairpins) // (with --hairpins a flagged component is refused first, leaf_passes)
+		throw HipError(SUB_REDO_REFUSAL);
+	return p;
+}
+
+// The tail of the pass before (POVU_HIP_F_ASYNC) reads the stage workspace (ws2) from the side stream.  A pass that may
+// itself overlap waits for it ON THE STREAM, right before its own first write there (carve_stages, component_tables);
+// every other pass -- and any pass whose arenas must grow, which frees them -- waits on the host.
+static void reserve(povu_hip_ctx *ctx, Arena &ar, size_t bytes)
+{
+	if (bytes > ar.capacity())
+		ctx->wait_tail();
+	ar.reserve(bytes);
+}
+
+// What row B publishes: the component count, and the components' sizes in page-locked scratch once `sizes` is waited for.
+struct RowB {
+	uint32_t C;
+	const uint32_t *voff, *eoff, *gstats;
+	HostScratch::Token sizes;
+};
+
+// ---- row B: labelling, speculative adjacency, re-index
+// The host has to know the component count (it sizes the workspaces) and then the components' sizes (the tables of the
+// stages): two reads.  Neither is waited for with the stream idle: the words are published by a kernel, an event is
+// recorded behind it (HostScratch::mark), and the stream is given its next kernel before the host waits for the event --
+//  (1) behind the labelling: the re-index's adjacency kernel, on the assumption that holds for nearly every GFA (vertices
+//      grouped by component, no hub, no self loop: it then needs nothing the labels say but the hooks; when the
+//      assumption fails its output is simply overwritten by the real re-index);
+//  (2) behind the re-index: the tree stage's first kernel (it reads the re-indexed adjacency only; carve_stages).
+// Not with stage timers (the kernels would be booked on the wrong stage).
+static RowB row_b(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, StageTimer &tm)
+{
+	const ResidentGraph &g = ctx->g;
+	CompState &cs = ctx->cs;
+	hipStream_t s = ctx->stream;
+	uint32_t *lab = label_components_enqueue(g, cs, tm, s);
+	const HostScratch::Token labelled = ctx->host.mark(s);
+	bool spec_adj = false;
+	if (!tm.enabled && g.E && sort_free_adjacency(g, p.sorted_adj) && ctx->ws_b.capacity() >= rowb_speculative_adj_bytes(z)) {
+		ctx->ws_b.reserve(0); // (rewinds the arena: the two arrays get the places rowb_carve_reindex will give them)
+		uint32_t *ladj = ctx->ws_b.take<uint32_t>(2 * z.E + 8), *lle = ctx->ws_b.take<uint32_t>(2 * z.E + 8);
+		reindex_speculative_adj(g, cs, ladj, lle, s);
+		spec_adj = true;
+	}
+	ctx->host.wait(labelled);
+	const uint32_t C = label_components_finish(cs, lab);
+	// what the re-index of THIS graph needs, now that the count, the order and the self loops are known
+	const RowBNeeds need{C == 1 || cs.comp_sorted, sort_free_adjacency(g, p.sorted_adj), cs.has_self_loops};
+	const size_t need_b = rowb_carve_reindex(nullptr, z, C, need, cs);
+	if (spec_adj && need_b > ctx->ws_b.capacity()) { // the arena has to grow under a kernel that writes into it: let it finish, forget it
+		HIP_CHECK(hipStreamSynchronize(s));
+		spec_adj = false;
+	}
+	reserve(ctx, ctx->ws_b, need_b);
+	rowb_carve_reindex(&ctx->ws_b, z, C, need, cs);
+	spec_adj = spec_adj && need.identity && need.sort_free && !need.self_loops; // (else: a kernel that wrote nonsense into arrays about to be rewritten)
+	// component sizes on the host (shard assignment, launch order): the last re-index kernel writes them into pinned
+	// memory itself
+	uint32_t *pub = ctx->host.take<uint32_t>(2 * ((size_t)C + 1) + 4);
+	HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&cs.host_pub), pub, 0));
+	count_kernel_d2h((2 * ((size_t)C + 1) + 4) * 4);
+	reindex_components(g, cs, C, tm, s, p.sorted_adj, spec_adj);
+	return RowB{C, pub, pub + (size_t)C + 1, pub + 2 * ((size_t)C + 1), ctx->host.mark(s)};
+}
+
+// ---- stage workspaces, sized with the real component count (z), and the tree stage's first kernel, which goes out
+// before the host waits for the component sizes.  Returns whether the stream already waits for the tail of the pass before.
+static bool carve_stages(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, uint32_t C, const StageTimer &tm)
+{
+	const StageWsOpts so = stage_opts(z.V, z.E, C, ctx->g.n_empty_sides, p.seq_tree, p.hairpins);
+	reserve(ctx, ctx->ws2, carve_workspace(nullptr, 1, z, ctx->cs, ctx->sw, p.hairpins) + (p.all_seq ? 0 : stage_workspace_bytes(z.V, z.E, C, so)));
+	carve_workspace(&ctx->ws2, 1, z, ctx->cs, ctx->sw, p.hairpins);
+	if (p.all_seq)
+		return false;
+	TreeWs &tw = ctx->tw;
+	stage_workspace_carve(ctx->ws2, ctx->pw, tw, z.V, z.E, C, so);
+	tw.walk_arena = &ctx->ws_walk;
+	tw.walk_stream = ctx->walk_side.stream;
+	tw.walk_fork = ctx->walk_side.fork;
+	tw.walk_join = ctx->walk_side.join;
+	tw.tour_words_done = false;
+	if (!p.par_tree || tm.enabled)
+		return false;
+	if (ctx->tail_pending) // first write into the stage workspace: behind the tail of the pass before
+		HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->tail_done, 0));
+	tree_tour_words(ctx->cs, (uint32_t)z.V, (uint32_t)z.E, tw, p.sparse_splitters, ctx->stream);
+	return ctx->tail_pending;
+}
+
+// What the component tables tell the stages.
+struct CompTables {
+	uint32_t event_lists = 0, n_stack = 0, n_processed = 0;
+};
+
+// ---- component tables: launch order, owner (LPT over vertices + links, the same on every rank), processed components
+// (>= 3 vertices, owned by this shard) and their running count `pc` = where a component starts in the dense PVST output,
+// and where each component's candidate stack starts.  Host-built in pinned scratch: the upload needs no synchronisation.
+static CompTables component_tables(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, const uint32_t *voff, const uint32_t *eoff,
+				   bool tail_waited)
+{
+	uint32_t *tab_h = ctx->host.take<uint32_t>(5 * ((size_t)C + 1));
+	uint32_t *order = tab_h, *owner = tab_h + ((size_t)C + 1), *pc = tab_h + 2 * ((size_t)C + 1), *cproc = tab_h + 3 * ((size_t)C + 1),
+		 *stack_off = tab_h + 4 * ((size_t)C + 1);
+	if (p.heaviest_first) {
+		std::vector<uint64_t> weight(C);
+		for (uint32_t c = 0; c < C; c++)
+			weight[c] = (uint64_t)(eoff[c + 1] - eoff[c]) + (voff[c + 1] - voff[c]);
+		lpt_assign(weight.data(), C, p.world, order, owner);
+	} else {
+		std::iota(order, order + C, 0u);
+		std::fill(owner, owner + C, 0u);
+	}
+	uint64_t links = 0;
+	for (uint32_t c = 0; c < C; c++)
+		if (owner[c] == p.rank || p.world == 1)
+			links += eoff[c + 1] - eoff[c];
+	ctx->last_links = links;
+	CompTables t;
+	order[C] = owner[C] = cproc[C] = 0;
+	pc[0] = 0;
+	for (uint32_t c = 0; c < C; c++) {
+		const uint32_t nv = voff[c + 1] - voff[c];
+		cproc[c] = (nv >= 3 && (p.world == 1 || owner[c] == p.rank)) ? 1u : 0u;
+		pc[c + 1] = pc[c] + cproc[c];
+		t.event_lists += cproc[c] ? 1u : 2 * nv; // (the event lists of the pre-order ranking)
+		stack_off[c] = t.n_stack;
+		t.n_stack += cproc[c] ? nv : 0u; // one candidate-stack entry per segment (its black tree edge)
+	}
+	stack_off[C] = t.n_stack;
+	t.n_processed = pc[C];
+	if (ctx->tail_pending && !tail_waited) // first write into the stage workspace: behind the tail of the pass before
+		HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->tail_done, 0));
+	HIP_CHECK(copy_async(ctx->sw.tables, tab_h, 5 * ((size_t)C + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+	return t;
+}
+
+// The one-lane kernels' lists live in their own arena, carved -- and emptied, as the kernels expect them -- only when a
+// pass runs those kernels.
+struct SeqLanes {
+	povu_hip_ctx *ctx;
+	const Sizes &z;
+	bool hairpins;
+	bool carved = false;
+	void carve()
+	{
+		if (carved)
+			return;
+		ctx->wait_tail();
+		ctx->ws_seq.reserve(carve_workspace(nullptr, 2, z, ctx->cs, ctx->sw, hairpins));
+		carve_workspace(&ctx->ws_seq, 2, z, ctx->cs, ctx->sw, hairpins);
+		carved = true;
+	}
+	void init(hipStream_t s)
+	{
+		carve();
+		const SeqWs &sw = ctx->sw;
+		for (uint32_t *p : {sw.first_child, sw.o_head, sw.i_head, sw.bl, sw.t_hi, sw.t_cls, sw.st_head, sw.st_tail})
+			HIP_CHECK(hipMemsetAsync(p, 0xFF, z.T * 4, s));
+		HIP_CHECK(hipMemsetAsync(sw.ctr, 0xFF, z.nS * 4, s));
+		HIP_CHECK(hipMemsetAsync(sw.cur, 0, z.nS * 4, s));
+		HIP_CHECK(hipMemsetAsync(sw.selfloop, 0, z.V, s));
+		HIP_CHECK(hipMemsetAsync(sw.last, 0xFF, (z.B + z.T) * 4, s));
+		HIP_CHECK(hipMemsetAsync(sw.in_s, 0, z.B + z.T, s));
+	}
+};
+
+// What rows C-G leave for the result fetch and the record of the pass.
+struct RowsOut {
+	const uint32_t *sum = nullptr; // outcome of the pass in pinned memory (pass_summary); null: read it when the pass is done
+	uint32_t nbad = 0;	       // components through the sequential redo
+	bool mixed = false;	       // parallel result for most components, sequential redo for the flagged ones
+	bool redo_pvst_only = false, stack_export_pending = false;
+	bool fast_tail = false; // the summary came with the PVST count: nothing was synchronised after the tail was enqueued
+	PassTail tail;
+};
+
+// pass_summary's words, read with the stream drained; f's ev1 goes behind them (recorded again if more work follows)
+static const uint32_t *read_summary(povu_hip_ctx *ctx, uint32_t C, bool with_par, const povu_hip_forest &f)
+{
+	uint32_t *h = ctx->host.take<uint32_t>(5 * (size_t)C + 8);
+	count_kernel_d2h((5 * (size_t)C + 8) * 4);
+	pass_summary(ctx->sw, with_par ? &ctx->pw : nullptr, C, h, ctx->stream);
+	HIP_CHECK(hipEventRecord(f.ev1, ctx->stream));
+	HIP_CHECK(hipStreamSynchronize(ctx->stream));
+	return h;
+}
+
+// ---- rows C-G on the parallel kernels (the tree on the one-lane kernels with POVU_HIP_F_SEQ_TREE), up to the count of
+// the components the laminarity check flags; returns the bracket count given to the class stage (< 0: sequential tree)
+static int64_t parallel_rows(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, const uint32_t *gstats, const CompTables &t,
+			     povu_hip_forest &f, SeqLanes &lanes, StageTimer &tm, RowsOut &out)
+{
+	SeqWs &sw = ctx->sw;
+	ParWs &pw = ctx->pw;
+	hipStream_t s = ctx->stream;
+	int64_t dense_nb0 = -1;
+	pw.cproc_ps = sw.tables + 2 * ((size_t)C + 1);
+	ctx->tw.cproc = sw.tables + 3 * ((size_t)C + 1);
+	pw.soff = sw.tables + 4 * ((size_t)C + 1);
+	if (p.seq_tree) {
+		lanes.init(s);
+		tm.begin("tree_seq");
+		sw.stages = SEQ_STAGE_TREE;
+		launch_seq_components(sw, s);
+		tm.end(1);
+	} else {
+		dense_nb0 = run_parallel_tree(ctx->cs, sw, pw, ctx->tw, C, t.event_lists, gstats[0], p.big_class_dfs, p.sparse_splitters, tm, s);
+	}
+	pw.all_vertex_classes = p.all_vertex_classes;
+	pw.check_laminar = p.check_laminar;
+	out.tail.want_overlap = p.overlap_tail;
+	out.tail.done = f.ev1;
+	out.tail.done2 = ctx->tail_done;
+	// the result block is allocated as soon as the number of PVST vertices is known (before the emit kernel): the parallel
+	// stages write it straight into pinned host memory, there is no device-to-host copy
+	auto alloc_result_block = [&f](size_t total) -> void * {
+		f.release_block();
+		f.alloc(total);
+		void *dev = nullptr;
+		HIP_CHECK(hipHostGetDevicePointer(&dev, f.block, 0));
+		return dev;
+	};
+	run_parallel_dg(ctx->cs, sw, pw, C, t.n_processed, t.n_stack, dense_nb0, alloc_result_block, tm, s, ctx->side, out.tail);
+	out.stack_export_pending = true;
+	if (p.redo_odd) // (tests: flag every other component as if its stack were not laminar)
+		mark_odd_u32(pw.comp_bad, C, s);
+	// Everything the host needs came back with the PVST count, unless something after it can still flag a component (the
+	// laminarity check, the test modes) or add to the result (labels, boundaries): then the summary is read again when all
+	// of that is done.
+	out.fast_tail = out.tail.summary_final && !p.leaf_sub && !p.hairpins && !p.force_redo && !p.redo_odd;
+	const uint32_t *sum = out.sum = out.fast_tail ? out.tail.early_summary : read_summary(ctx, C, true, f);
+	if (sum[0])
+		throw HipError("parallel class stage: a tree vertex has no live bracket (internal invariant broken)");
+	if (sum[1] & 1u)
+		throw HipError("list ranking: splitter capacity exceeded (internal sizing bug)");
+	if (sum[1] & 2u)
+		throw HipError("class walk: stack pool exhausted (internal sizing bug)");
+	if (sum[2])
+		throw HipError("spanning forest of the links has the wrong size (internal)");
+	if (sum[3])
+		throw HipError("candidate stack has the wrong size (internal)");
+	for (uint32_t c = 0; c < C; c++)
+		out.nbad += sum[4 + c] ? 1 : 0;
+	return dense_nb0;
+}
+
+// ---- the leaf subflubble passes -- find_tiny + find_parallel relabel leaf flubbles (leaf_kernels.hip): the PVSTs the
+// parallel stages just emitted here, those of components that go through the redo of add_flubbles after it (redo) --
+// and with -s the inserting passes
+static void leaf_passes(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, uint32_t nbad, povu_hip_forest &f, LeafState &leaf_state,
+			StageTimer &tm)
+{
+	hipStream_t s = ctx->stream;
+	if (nbad && p.hairpins)
+		throw HipError("leaf subflubble passes: with --hairpins a component that needs the sequential redo is rebuilt "
+			       "from scratch by the one-lane kernels, whose tree state the passes do not read");
+	tm.begin("leaf_subflubbles");
+	leaf_prepare(ctx->cs, ctx->sw, ctx->pw, ctx->tw, C, ctx->ws_leaf, leaf_state, s);
+	leaf_dense(leaf_state, ctx->sw, ctx->pw, C, s);
+	const size_t n = ctx->pw.d_total;
+	f.sub_ai.resize(n, ctx->pool); // (page-locked, out of the context's pool)
+	f.sub_zi.resize(n, ctx->pool);
+	f.sub_fam.resize(n, ctx->pool);
+	if (n) {
+		HIP_CHECK(copy_async(f.sub_ai.data(), leaf_state.dense.ai, n * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(f.sub_zi.data(), leaf_state.dense.zi, n * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(f.sub_fam.data(), leaf_state.dense.fam, n, hipMemcpyDeviceToHost, s));
+	}
+	tm.end(16);
+	HIP_CHECK(hipStreamSynchronize(s));
+	if (!p.all_sub)
+		return;
+	// find_concealed, find_midi, find_smothered insert vertices (sub_kernels.hip); they read the dense PVST the parallel
+	// stages wrote, so a component that needs the sequential redo has no place here
+	if (nbad || p.force_redo || p.redo_odd)
+		throw HipError(SUB_REDO_REFUSAL);
+	tm.begin("subflubbles_insert");
+	f.subx = std::make_shared<SubForest>();
+	run_subflubbles(ctx->cs, ctx->sw, ctx->pw, ctx->tw, leaf_state, C, ctx->host, *f.subx, ctx->pool, s, &ctx->ws_sub, &ctx->ws_sub_hint);
+	tm.end(40);
+}
+
+// ---- the redo decision: components whose candidate stack is not laminar go through the exact sequential kernels (every
+// component with POVU_HIP_F_FORCE_REDO, or for the hairpin report, which the parallel path only has for a whole pass)
+static void redo(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, int64_t dense_nb0, SeqLanes &lanes, const LeafState &leaf_state,
+		 StageTimer &tm, RowsOut &out)
+{
+	SeqWs &sw = ctx->sw;
+	hipStream_t s = ctx->stream;
+	if (p.force_redo || (out.nbad && p.hairpins)) {
+		fill_u32(ctx->pw.comp_bad, C, 1u, s);
+		out.nbad = C;
+	} else if (out.nbad) {
+		out.mixed = true; // (the others keep the dense result the parallel stages wrote)
+	}
+	if (!out.nbad)
+		return;
+	tm.begin("redo_seq");
+	if (dense_nb0 >= 0 && !p.hairpins) {
+		// Only add_flubbles' stack machine (flubbles.cpp:316-365) cannot be evaluated in closed form on such a stack; tree,
+		// classes, candidate stack and next_seen of the parallel stages stand.  They are copied into the per-component
+		// layout, one lane per flagged component runs the machine.
+		lanes.carve();
+		export_parallel_stack(ctx->cs, sw, ctx->pw, s);
+		out.stack_export_pending = false;
+		HIP_CHECK(hipMemsetAsync(sw.in_s, 0, lanes.z.B + lanes.z.T, s));
+		sw.stages = SEQ_STAGE_PVST | SEQ_STAGE_GIVEN_STACK;
+		out.redo_pvst_only = true;
+	} else {
+		if (p.leaf_sub)
+			throw HipError("leaf subflubble passes: this pass rebuilds the flagged components from scratch with the "
+				       "one-lane kernels, whose tree state the passes do not read");
+		if (dense_nb0 >= 0) // parallel tree: the one-lane kernels start from scratch
+			lanes.init(s);
+		sw.stages = dense_nb0 >= 0 ? SEQ_STAGE_ALL : (SEQ_STAGE_CLASSES | SEQ_STAGE_STACK | SEQ_STAGE_PVST);
+	}
+	sw.comp_sel = ctx->pw.comp_bad;
+	if (p.leaf_sub) { // (only reached with the PVST-only redo, see above)
+		sw.p_ai = leaf_state.p_ai;
+		sw.p_zi = leaf_state.p_zi;
+	}
+	launch_seq_components(sw, s);
+	sw.comp_sel = nullptr;
+	if (p.leaf_sub)
+		leaf_seq(leaf_state, ctx->cs, sw, ctx->pw.comp_bad, C, s);
+	tm.end(1);
+	out.sum = nullptr;
+}
+
+// ---- rows C-G, on the one-lane kernels (POVU_HIP_F_SEQUENTIAL) or the parallel ones with their leaf passes, hairpin
+// report and redo
+static RowsOut rows_c_to_g(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, const uint32_t *gstats, const CompTables &t,
+			   povu_hip_forest &f, SeqLanes &lanes, LeafState &leaf_state, StageTimer &tm)
+{
+	const CompState &cs = ctx->cs;
+	SeqWs &sw = ctx->sw;
+	hipStream_t s = ctx->stream;
+	sw.V = ctx->g.V, sw.E = ctx->g.E, sw.C = C, sw.rank = p.rank, sw.world = p.world, sw.want_depth = p.all_sub;
+	sw.voff = cs.voff, sw.eoff = cs.eoff, sw.loff = cs.loff, sw.ladj = cs.ladj, sw.gid_s = cs.gid_s, sw.tip_s = cs.tip_s;
+	sw.start_key = cs.start_key, sw.p_ai = sw.p_zi = nullptr;
+	tm.begin("traversal_init");
+	zero_component_counters(sw, C, p.all_seq ? nullptr : ctx->pw.comp_bad, p.all_seq ? nullptr : ctx->pw.err, s);
+	if (p.all_seq)
+		lanes.init(s);
+	tm.end(p.all_seq ? 14 : 1);
+	sw.comp_sel = nullptr;
+	RowsOut out;
+	if (p.all_seq) {
+		tm.begin("traversal_seq");
+		sw.stages = SEQ_STAGE_ALL;
+		launch_seq_components(sw, s);
+		tm.end(1);
+		return out;
+	}
+	const int64_t dense_nb0 = parallel_rows(ctx, p, C, gstats, t, f, lanes, tm, out);
+	if (p.leaf_sub) {
+		leaf_passes(ctx, p, C, out.nbad, f, leaf_state, tm);
+		out.sum = nullptr; // (read again when the pass is done: its total then includes these stages)
+	}
+	if (p.hairpins && !out.nbad) {
+		run_parallel_hairpins(cs, sw, ctx->pw, C, tm, s);
+		out.sum = nullptr;
+	}
+	redo(ctx, p, C, dense_nb0, lanes, leaf_state, tm, out);
+	return out;
+}
+
+// One array of the one-lane kernels' per-component layout (component c's PVST starts at voff[c] + c) and where it goes:
+// `dst` at every tree's `off` -- or, for the hairpin boundaries (`hp`, 16 bytes each), at its `hp_off`.
+struct SeqArray {
+	const void *src;
+	void *dst;
+	size_t esz; // bytes per entry
+	bool hp = false;
+};
+
+// The spans of the trees `ts` in `arrays` to the host: for a few trees (when `spans_if_few`) one copy per span, else one
+// bulk copy per array, sliced on the host.  `done`, if given, is recorded behind the copies.
+static void fetch_seq(const std::vector<povu_hip_forest::Tree *> &ts, const uint32_t *voff, size_t P, const std::vector<SeqArray> &arrays,
+		      bool spans_if_few, hipEvent_t done, hipStream_t s)
+{
+	struct Span {
+		size_t src, dst, bytes;
+	};
+	auto span = [&](const povu_hip_forest::Tree &t, const SeqArray &x) {
+		const size_t pb = (size_t)voff[t.component_id - 1] + (t.component_id - 1);
+		return Span{pb * x.esz, (x.hp ? t.hp_off : t.off) * x.esz, (x.hp ? t.n_hairpins : t.n_pvst) * x.esz};
+	};
+	const bool spans = spans_if_few && ts.size() <= 32;
+	std::vector<std::vector<char>> bulk;
+	for (const SeqArray &x : arrays)
+		if (!spans) {
+			bulk.emplace_back(P * x.esz);
+			HIP_CHECK(copy_async(bulk.back().data(), x.src, bulk.back().size(), hipMemcpyDeviceToHost, s));
+		}
+	for (const auto *t : ts)
+		for (size_t k = 0; spans && k < arrays.size(); k++) {
+			const Span sp = span(*t, arrays[k]);
+			if (sp.bytes)
+				HIP_CHECK(copy_async((char *)arrays[k].dst + sp.dst, (const char *)arrays[k].src + sp.src, sp.bytes, hipMemcpyDeviceToHost, s));
+		}
+	if (done)
+		HIP_CHECK(hipEventRecord(done, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	for (const auto *t : ts)
+		for (size_t k = 0; !spans && k < arrays.size(); k++) {
+			const Span sp = span(*t, arrays[k]);
+			if (sp.bytes)
+				memcpy((char *)arrays[k].dst + sp.dst, bulk[k].data() + sp.src, sp.bytes);
+		}
+}
+
+// the one-lane kernels' PVST arrays (and hairpin boundaries) of the trees `ts` into `dst` ...
+static void fetch_seq_pvst(const std::vector<povu_hip_forest::Tree *> &ts, const uint32_t *voff, size_t P, const SeqWs &sw, bool hairpins,
+			   const povu_hip_forest::Arrays &dst, size_t n_total, povu_hip_forest &f, hipStream_t s)
+{
+	std::vector<uint8_t> ors(n_total);
+	std::vector<SeqArray> arrays{{sw.p_a, dst.a, 4}, {sw.p_z, dst.z, 4}, {sw.p_parent, dst.parent, 4}, {sw.p_or, ors.data(), 1}};
+	if (hairpins)
+		arrays.push_back({sw.hairpins, f.hairpins.data(), 16, true});
+	fetch_seq(ts, voff, P, arrays, true, f.ev1, s);
+	for (size_t i = 0; i < n_total; i++) {
+		dst.aor[i] = ors[i] & 1;
+		dst.zor[i] = (ors[i] >> 1) & 1;
+	}
+}
+
+// ... and their subflubble labels (leaf_seq wrote them in the same per-component layout)
+static void fetch_seq_labels(const std::vector<povu_hip_forest::Tree *> &ts, const uint32_t *voff, size_t P, const LeafState &ls,
+			     PinnedVec<uint32_t> &ai, PinnedVec<uint32_t> &zi, PinnedVec<uint8_t> &fam, size_t n_total, hipStream_t s)
+{
+	ai.assign(n_total, POVU_NIL);
+	zi.assign(n_total, POVU_NIL);
+	fam.assign(n_total, 0);
+	fetch_seq(ts, voff, P, {{ls.p_ai, ai.data(), 4}, {ls.p_zi, zi.data(), 4}, {ls.p_fam, fam.data(), 1}}, false, nullptr, s);
+}
+
+// ---- the result fetch: the dense layout the parallel stages wrote into f's block (a mixed pass: plus a block of its
+// own for the redone components), or the one-lane kernels' per-component layout
+static void fetch_result(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, const uint32_t *voff, const uint32_t *eoff, RowsOut &out,
+			 povu_hip_forest &f, const LeafState &leaf_state, StageTimer &tm)
+{
+	hipStream_t s = ctx->stream;
+	const size_t P = (size_t)ctx->g.V + C;
+	tm.begin("pvst_d2h");
+	const uint32_t *sum = out.sum ? out.sum : read_summary(ctx, C, !p.all_seq, f);
+	const uint32_t *bad = sum + 4, *cstat = sum + 4 + (size_t)C, *npvst = sum + 4 + 2 * (size_t)C, *nbry = sum + 4 + 3 * (size_t)C,
+		       *doff = sum + 4 + 4 * (size_t)C;
+	for (uint32_t c = 0; c < C; c++)
+		if (cstat[c] == 2)
+			throw HipError("internal error: the spanning tree of component " + std::to_string(c + 1) + " did not reach every side");
+	f.total_components = C;
+	size_t total = 0, total_hp = 0;
+	for (uint32_t c = 0; c < C; c++) {
+		if (npvst[c] == 0)
+			continue;
+		povu_hip_forest::Tree t;
+		t.component_id = c + 1; // decompose.cpp:129
+		t.n_vtx = voff[c + 1] - voff[c];
+		t.n_links = eoff[c + 1] - eoff[c];
+		t.n_pvst = npvst[c];
+		t.off = total;
+		t.hp_off = total_hp;
+		t.n_hairpins = p.hairpins ? nbry[c] : 0;
+		t.sub_c = c;
+		total += npvst[c];
+		total_hp += t.n_hairpins;
+		f.trees.push_back(t);
+	}
+	f.hairpins.resize(2 * total_hp);
+	std::vector<povu_hip_forest::Tree *> redone;
+	if (p.all_seq || (out.nbad && !out.mixed)) { // the one-lane kernels' layout for every tree
+		if (f.block && f.total_entries != total)
+			f.release_block();
+		if (!f.block)
+			f.alloc(total);
+		for (auto &t : f.trees)
+			redone.push_back(&t);
+		tm.end(0);
+		fetch_seq_pvst(redone, voff, P, ctx->sw, p.hairpins, {f.a_id.p, f.z_id.p, f.parent.p, f.a_or.p, f.z_or.p}, total, f, s);
+		if (p.leaf_sub)
+			fetch_seq_labels(redone, voff, P, leaf_state, f.sub_ai, f.sub_zi, f.sub_fam, total, s);
+		return;
+	}
+	// the parallel stages wrote every PVST back to back into f's block
+	if (!out.mixed && (doff[C] != total || total != ctx->pw.d_total))
+		throw HipError("internal error: dense PVST size mismatch");
+	if (!f.block)
+		f.alloc(ctx->pw.d_total);
+	size_t redo_total = 0;
+	for (auto &t : f.trees) {
+		if (out.mixed && bad[t.component_id - 1]) {
+			t.off = redo_total;
+			redo_total += t.n_pvst;
+			redone.push_back(&t);
+		} else {
+			t.off = doff[t.component_id - 1];
+		}
+	}
+	bool more = false;
+	for (const auto &t : f.trees)
+		if (t.n_hairpins) {
+			const size_t pb = (size_t)voff[t.component_id - 1] + (t.component_id - 1);
+			HIP_CHECK(copy_async(f.hairpins.data() + 2 * t.hp_off, ctx->sw.hairpins + 2 * pb, (size_t)t.n_hairpins * 16,
+					     hipMemcpyDeviceToHost, s));
+			more = true;
+		}
+	tm.end(0);
+	if (!redone.empty()) { // the redone components get a block of their own
+		povu_hip_forest::ExtraBlock blk;
+		blk.pool = ctx->pool;
+		blk.p = ctx->pool->get(povu_hip_forest::ExtraBlock::bytes_for(redo_total), blk.cap);
+		blk.carve(redo_total);
+		f.extra.push_back(std::move(blk));
+		povu_hip_forest::ExtraBlock &x = f.extra[0];
+		for (auto *t : redone)
+			t->blk = 0;
+		fetch_seq_pvst(redone, voff, P, ctx->sw, p.hairpins, x, redo_total, f, s);
+		if (p.leaf_sub)
+			fetch_seq_labels(redone, voff, P, leaf_state, x.sub_ai, x.sub_zi, x.sub_fam, redo_total, s);
+	} else if (out.fast_tail && out.tail.overlapped && !more) {
+		// the arrays are still on their way: the caller (or the next accessor of the forest) waits for ev1
+		f.pending = true;
+		ctx->tail_pending = true;
+	} else if (out.fast_tail && !more) {
+		HIP_CHECK(hipEventSynchronize(f.ev1)); // (recorded behind the last copy by run_parallel_dg)
+		if (tm.enabled)
+			HIP_CHECK(hipStreamSynchronize(s)); // (the stage events themselves have to complete before they are read)
+	} else if (more || tm.enabled || out.fast_tail) {
+		HIP_CHECK(hipEventRecord(f.ev1, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+	}
+}
+
+// ---- stage times, and the pass total unless its arrays are still on their way
+static void stage_times(povu_hip_ctx *ctx, const StageTimer &tm, povu_hip_forest &f)
+{
+	ctx->last_times.clear();
+	for (auto &r : tm.recs) {
+		povu_hip_stage_time st{};
+		snprintf(st.name, sizeof st.name, "%s", r.name.c_str());
+		float ms = 0;
+		HIP_CHECK(hipEventElapsedTime(&ms, r.a, r.b));
+		st.ms = ms;
+		st.launches = r.launches;
+		ctx->last_times.push_back(st);
+	}
+	if (!f.pending) {
+		povu_hip_stage_time st{};
+		snprintf(st.name, sizeof st.name, "total");
+		f.ready();
+		st.ms = f.pass_ms;
+		ctx->last_times.push_back(st);
+	}
+}
+
+} // namespace
+
 extern "C" povu_hip_forest *povu_hip_decompose(povu_hip_ctx *ctx, const povu_hip_opts *opts, char *err, size_t errlen)
 {
 	// declared outside the try block: on a failure the stream is drained BEFORE the forest returns its pinned
@@ -765,563 +1336,46 @@ extern "C" povu_hip_forest *povu_hip_decompose(povu_hip_ctx *ctx, const povu_hip
 		if (!ctx || !ctx->g.block)
 			throw HipError("no graph resident: call povu_hip_graph_upload first");
 		HIP_CHECK(hipSetDevice(ctx->device));
-		const ResidentGraph &g = ctx->g;
-		hipStream_t s = ctx->stream;
-		povu_hip_opts o{0, 1, 0};
-		if (opts)
-			o = *opts;
-		if (o.world == 0)
-			o.world = 1;
-		if (o.rank >= o.world)
-			throw HipError("shard rank >= world");
-		const bool hairpins = (o.flags & POVU_HIP_F_HAIRPINS) != 0;
-		// POVU_HIP_F_ASYNC: the pass may leave its last kernels and the copies of the PVST arrays in flight when it returns
-		// (and the next pass may then start under them).  Only the plain all-parallel pass has that form.
-		const bool want_async = (o.flags & POVU_HIP_F_ASYNC) && (o.flags & POVU_HIP_F_NO_STAGE_TIMES) && !hairpins &&
-					!(o.flags & (POVU_HIP_F_SEQUENTIAL | POVU_HIP_F_SEQ_TREE | POVU_HIP_F_FORCE_REDO | POVU_HIP_F_REDO_ODD |
-						     POVU_HIP_F_LEAF_SUBFLUBBLES | POVU_HIP_F_SUBFLUBBLES | POVU_HIP_F_CHECK_LAMINAR));
-		// The tail of the pass before (POVU_HIP_F_ASYNC) reads the stage workspace (ws2) from the side stream.  A pass that may
-		// itself overlap waits for it ON THE STREAM, right before its own first write there (below); every other pass -- and
-		// any pass whose arenas must grow, which frees them -- waits here.
-		auto reserve = [&](Arena &ar, size_t bytes) {
-			if (bytes > ar.capacity())
-				ctx->wait_tail();
-			ar.reserve(bytes);
-		};
-		if (!want_async)
+		const PassPlan p = plan_pass(opts);
+		if (!p.overlap_tail)
 			ctx->wait_tail();
-
-		Sizes z;
-		z.V = g.V;
-		z.E = g.E;
-		z.Cmax = g.V; // rows A/B run before the component count is known
-		z.nS = 2 * z.V;
-		z.slots = g.n_slots;
-		z.T = z.B = 0;
-		CompState &cs = ctx->cs;
-		SeqWs &sw = ctx->sw;
-		ctx->have_state = false;
-		ctx->last_mixed = false;
-		ctx->redo_pvst_only = false;
-		ctx->stack_export_pending = false;
-		ctx->classes_in_par = false;
-		ctx->tree_in_par = false;
+		const ResidentGraph &g = ctx->g;
+		Sizes z{g.V, g.E, g.V, 0, 0, 2 * (size_t)g.V, g.n_slots}; // (rows A/B run before the component count is known)
+		ctx->last = LastPass{};
 		ctx->host.reset();
-		cs.host = ctx->pw.host = ctx->tw.host = &ctx->host;
-		const bool all_seq = (o.flags & POVU_HIP_F_SEQUENTIAL) != 0;
-		const bool all_sub = (o.flags & POVU_HIP_F_SUBFLUBBLES) != 0; // all five passes of -s
-		const bool leaf_sub = all_sub || (o.flags & POVU_HIP_F_LEAF_SUBFLUBBLES) != 0;
-		LeafState leaf_state;
-		if (leaf_sub && (o.flags & (POVU_HIP_F_SEQUENTIAL | POVU_HIP_F_SEQ_TREE)))
-			throw HipError("the leaf subflubble passes read the state of the parallel stages: not with the sequential tree / all-sequential test modes");
-		reserve(ctx->ws, rowb_carve_label(nullptr, z, cs));
-		rowb_carve_label(&ctx->ws, z, cs);
-
+		ctx->cs.host = ctx->pw.host = ctx->tw.host = &ctx->host;
+		reserve(ctx, ctx->ws, rowb_carve_label(nullptr, z, ctx->cs));
+		rowb_carve_label(&ctx->ws, z, ctx->cs);
 		StageTimer &tm = ctx->timer;
 		tm.reset();
-		tm.enabled = (o.flags & POVU_HIP_F_NO_STAGE_TIMES) == 0;
+		tm.enabled = p.timed;
 		// the forest owns the two events that time its pass: ev0 at the first kernel, ev1 behind the last byte that reaches the host
 		f = std::make_unique<povu_hip_forest>();
+		f->pool = ctx->pool;
 		HIP_CHECK(hipEventCreate(&f->ev0));
 		HIP_CHECK(hipEventCreate(&f->ev1));
-		HIP_CHECK(hipEventRecord(f->ev0, s));
+		HIP_CHECK(hipEventRecord(f->ev0, ctx->stream));
 
-		// ---- row B
-		// The host has to know the component count (it sizes the workspaces) and then the components' sizes (the tables of the
-		// stages): two reads.  Neither is waited for with the stream idle: the words are published by a kernel, an EVENT is
-		// recorded behind it, and the stream is given its next kernel before the host waits for the event --
-		//  (1) behind the labelling: the re-index's adjacency kernel, on the assumption that holds for nearly every GFA (vertices
-		//      grouped by component, no hub, no self loop: it then needs nothing the labels say but the hooks; when the
-		//      assumption fails its output is simply overwritten by the real re-index);
-		//  (2) behind the re-index: the tree stage's first kernel (it reads the re-indexed adjacency only).
-		// Not with stage timers (the kernels would be booked on the wrong stage).
-		const bool force_sorted = (o.flags & POVU_HIP_F_SORTED_ADJ) != 0;
-		const bool par_tree = !all_seq && !(o.flags & POVU_HIP_F_SEQ_TREE);
-		uint32_t *lab = label_components_enqueue(g, cs, tm, s);
-		HIP_CHECK(hipEventRecord(ctx->host_wait, s));
-		bool spec_adj = false;
-		if (!tm.enabled && g.E && sort_free_adjacency(g, force_sorted) && ctx->ws_b.capacity() >= rowb_speculative_adj_bytes(z)) {
-			ctx->ws_b.reserve(0); // (rewinds the arena: the two arrays get the places rowb_carve_reindex will give them)
-			uint32_t *ladj = ctx->ws_b.take<uint32_t>(2 * z.E + 8), *lle = ctx->ws_b.take<uint32_t>(2 * z.E + 8);
-			reindex_speculative_adj(g, cs, ladj, lle, s);
-			spec_adj = true;
-		}
-		HIP_CHECK(hipEventSynchronize(ctx->host_wait));
-		const uint32_t C = label_components_finish(cs, lab);
-		{ // what the re-index of THIS graph needs, now that the count, the order and the self loops are known
-			const RowBNeeds need{C == 1 || cs.comp_sorted, sort_free_adjacency(g, force_sorted), cs.has_self_loops};
-			const size_t need_b = rowb_carve_reindex(nullptr, z, C, need, cs);
-			if (spec_adj && need_b > ctx->ws_b.capacity()) { // the arena has to grow under a kernel that writes into it: let it finish, forget it
-				HIP_CHECK(hipStreamSynchronize(s));
-				spec_adj = false;
-			}
-			reserve(ctx->ws_b, need_b);
-			rowb_carve_reindex(&ctx->ws_b, z, C, need, cs);
-			spec_adj = spec_adj && need.identity && need.sort_free && !need.self_loops; // (else: a kernel that wrote nonsense into arrays about to be rewritten)
-		}
-		// component sizes on the host (shard assignment = LPT over link counts, launch order): the last
-		// re-index kernel writes them into pinned memory itself
-		uint32_t *pub = ctx->host.take<uint32_t>(2 * ((size_t)C + 1) + 4);
-		HIP_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&cs.host_pub), pub, 0));
-		count_kernel_d2h((2 * ((size_t)C + 1) + 4) * 4);
-		reindex_components(g, cs, C, tm, s, force_sorted, spec_adj);
-		HIP_CHECK(hipEventRecord(ctx->host_wait, s));
-		const uint32_t *voff = pub, *eoff = pub + (size_t)C + 1, *gstats = pub + 2 * ((size_t)C + 1);
-		// stage workspaces, sized with the real component count
-		z.Cmax = C;
-		z.T = 2 * z.V + C;
-		z.B = z.E + z.V + 2 * z.T;
-		const StageWsOpts so = stage_opts(z.V, z.E, C, g.n_empty_sides, (o.flags & POVU_HIP_F_SEQ_TREE) != 0, hairpins);
-		reserve(ctx->ws2, carve_workspace(nullptr, 1, z, cs, sw, hairpins) + (all_seq ? 0 : stage_workspace_bytes(z.V, z.E, C, so)));
-		carve_workspace(&ctx->ws2, 1, z, cs, sw, hairpins);
-		bool tail_waited = false;
-		if (!all_seq) {
-			stage_workspace_carve(ctx->ws2, ctx->pw, ctx->tw, z.V, z.E, C, so);
-			ctx->tw.walk_arena = &ctx->ws_walk;
-			ctx->tw.walk_stream = ctx->walk_side.stream;
-			ctx->tw.walk_fork = ctx->walk_side.fork;
-			ctx->tw.walk_join = ctx->walk_side.join;
-			ctx->tw.tour_words_done = false;
-			if (par_tree && !tm.enabled) {
-				if (ctx->tail_pending) { // first write into the stage workspace: behind the tail of the pass before
-					HIP_CHECK(hipStreamWaitEvent(s, ctx->tail_done, 0));
-					tail_waited = true;
-				}
-				cs.host = ctx->pw.host = ctx->tw.host = &ctx->host;
-				tree_tour_words(cs, (uint32_t)z.V, (uint32_t)z.E, ctx->tw, (o.flags & POVU_HIP_F_SPARSE_SPLITTERS) != 0, s);
-			}
-		}
-		HIP_CHECK(hipEventSynchronize(ctx->host_wait)); // the component sizes are in `pub`
-		bool seq_ws_ready = false;
-		auto need_seq_workspace = [&]() { // the one-lane kernels' lists live in their own arena
-			if (seq_ws_ready)
-				return;
-			ctx->wait_tail();
-			ctx->ws_seq.reserve(carve_workspace(nullptr, 2, z, cs, sw, hairpins));
-			carve_workspace(&ctx->ws_seq, 2, z, cs, sw, hairpins);
-			seq_ws_ready = true;
-		};
-		// host-built tables live in pinned scratch: their uploads need no synchronisation
-		uint32_t *tab_h = ctx->host.take<uint32_t>(5 * ((size_t)C + 1));
-		uint32_t *order = tab_h, *owner = tab_h + ((size_t)C + 1), *pc = tab_h + 2 * ((size_t)C + 1),
-			 *cproc = tab_h + 3 * ((size_t)C + 1), *stack_off = tab_h + 4 * ((size_t)C + 1);
-		std::iota(order, order + C, 0u);
-		std::fill(owner, owner + C, 0u);
-		auto weight = [&](uint32_t c) { return (uint64_t)(eoff[c + 1] - eoff[c]) + (voff[c + 1] - voff[c]); };
-		// heaviest first: the shard assignment below and the launch order of the one-lane kernels (the parallel
-		// stages do not care, so a single-shard parallel pass skips the sort)
-		if (o.world > 1 || (o.flags & (POVU_HIP_F_SEQUENTIAL | POVU_HIP_F_SEQ_TREE | POVU_HIP_F_FORCE_REDO)))
-			std::stable_sort(order, order + C, [&](uint32_t a, uint32_t b) { return weight(a) > weight(b); });
-		if (o.world > 1) { // greedy longest-processing-time assignment, deterministic on every rank
-			std::vector<uint64_t> load(o.world, 0);
-			for (uint32_t k = 0; k < C; k++) {
-				const uint32_t c = order[k];
-				uint32_t best = 0;
-				for (uint32_t r = 1; r < o.world; r++)
-					if (load[r] < load[best])
-						best = r;
-				owner[c] = best;
-				load[best] += weight(c) + 1;
-			}
-		}
-		uint64_t links = 0;
-		for (uint32_t c = 0; c < C; c++)
-			if (owner[c] == o.rank || o.world == 1)
-				links += eoff[c + 1] - eoff[c];
-		ctx->last_links = links;
-		// processed components (>= 3 vertices, owned by this shard), their running count = where a component
-		// starts in the dense PVST output, and the number of event lists of the pre-order ranking
-		uint32_t event_lists = 0, n_stack = 0;
-		order[C] = owner[C] = cproc[C] = 0;
-		pc[0] = 0;
-		for (uint32_t c = 0; c < C; c++) {
-			const uint32_t nv = voff[c + 1] - voff[c];
-			cproc[c] = (nv >= 3 && (o.world == 1 || owner[c] == o.rank)) ? 1u : 0u;
-			pc[c + 1] = pc[c] + cproc[c];
-			event_lists += cproc[c] ? 1u : 2 * nv;
-			stack_off[c] = n_stack;
-			n_stack += cproc[c] ? nv : 0u; // one candidate-stack entry per segment (its black tree edge)
-		}
-		stack_off[C] = n_stack;
-		const uint32_t n_processed = pc[C];
-		if (ctx->tail_pending && !tail_waited) // first write into the stage workspace: behind the tail of the pass before (see above)
-			HIP_CHECK(hipStreamWaitEvent(s, ctx->tail_done, 0));
-		HIP_CHECK(copy_async(sw.tables, tab_h, 5 * ((size_t)C + 1) * 4, hipMemcpyHostToDevice, s));
-
-		// ---- rows C-G
-		sw.V = g.V;
-		sw.E = g.E;
-		sw.C = C;
-		sw.rank = o.rank;
-		sw.world = o.world;
-		sw.flags = o.flags;
-		sw.want_depth = all_sub;
-		sw.voff = cs.voff;
-		sw.eoff = cs.eoff;
-		sw.loff = cs.loff;
-		sw.ladj = cs.ladj;
-		sw.gid_s = cs.gid_s;
-		sw.tip_s = cs.tip_s;
-		sw.start_key = cs.start_key;
-		sw.p_ai = sw.p_zi = nullptr;
-		const size_t T = 2 * (size_t)g.V + C, B = (size_t)g.E + g.V + 2 * T;
-		// the one-lane kernels expect their lists empty; only paid for when they actually run
-		auto init_seq_workspace = [&]() {
-			need_seq_workspace();
-			for (uint32_t *p : {sw.first_child, sw.o_head, sw.i_head, sw.bl, sw.t_hi, sw.t_cls, sw.st_head, sw.st_tail})
-				HIP_CHECK(hipMemsetAsync(p, 0xFF, T * 4, s));
-			HIP_CHECK(hipMemsetAsync(sw.ctr, 0xFF, z.nS * 4, s));
-			HIP_CHECK(hipMemsetAsync(sw.cur, 0, z.nS * 4, s));
-			HIP_CHECK(hipMemsetAsync(sw.selfloop, 0, g.V, s));
-			HIP_CHECK(hipMemsetAsync(sw.last, 0xFF, (B + T) * 4, s));
-			HIP_CHECK(hipMemsetAsync(sw.in_s, 0, B + T, s));
-		};
-		// the result block is allocated as soon as the number of PVST vertices is known (before the emit kernel):
-		// the parallel stages write it straight into pinned host memory, there is no device-to-host copy
-		f->pool = ctx->pool;
+		const RowB rb = row_b(ctx, p, z, tm);
+		const uint32_t C = rb.C;
+		z.set_components(C);
+		const bool tail_waited = carve_stages(ctx, p, z, C, tm);
+		ctx->host.wait(rb.sizes);
+		const CompTables tables = component_tables(ctx, p, C, rb.voff, rb.eoff, tail_waited);
 		f->meta_reserve = (size_t)C + 1; // room behind the arrays for the tree table of povu_hip_forest_share
-		auto alloc_result_block = [&](size_t total) -> void * {
-			f->release_block();
-			f->alloc(total);
-			void *dev = nullptr;
-			HIP_CHECK(hipHostGetDevicePointer(&dev, f->block, 0));
-			return dev;
-		};
-		const uint32_t *sum = nullptr; // outcome of the pass in pinned memory (pass_summary)
-		PassTail tail;
-		bool fast_tail = false; // the summary came with the PVST count: nothing was synchronised after the tail was enqueued
-		auto read_summary = [&](bool with_par) -> const uint32_t * {
-			uint32_t *h = ctx->host.take<uint32_t>(5 * (size_t)C + 8);
-			count_kernel_d2h((5 * (size_t)C + 8) * 4);
-			pass_summary(sw, with_par ? &ctx->pw : nullptr, C, h, s);
-			HIP_CHECK(hipEventRecord(f->ev1, s)); // (recorded again if more work follows)
-			HIP_CHECK(hipStreamSynchronize(s));
-			return h;
-		};
-		tm.begin("traversal_init");
-		zero_component_counters(sw, C, all_seq ? nullptr : ctx->pw.comp_bad, all_seq ? nullptr : ctx->pw.err, s);
-		if (all_seq)
-			init_seq_workspace();
-		tm.end(all_seq ? 14 : 1);
-		sw.comp_sel = nullptr;
-		ctx->last_seq_redo = 0;
-		bool mixed = false; // parallel result for most components, sequential redo for the flagged ones
-		if (all_seq) {
-			tm.begin("traversal_seq");
-			sw.stages = SEQ_STAGE_ALL;
-			launch_seq_components(sw, s);
-			tm.end(1);
-		} else {
-			int64_t dense_nb0 = -1;
-			ctx->pw.cproc_ps = sw.tables + 2 * ((size_t)C + 1);
-			ctx->tw.cproc = sw.tables + 3 * ((size_t)C + 1);
-			ctx->pw.soff = sw.tables + 4 * ((size_t)C + 1);
-			if (o.flags & POVU_HIP_F_SEQ_TREE) {
-				init_seq_workspace();
-				tm.begin("tree_seq");
-				sw.stages = SEQ_STAGE_TREE;
-				launch_seq_components(sw, s);
-				tm.end(1);
-			} else {
-				dense_nb0 = run_parallel_tree(cs, sw, ctx->pw, ctx->tw, C, event_lists, gstats[0],
-							      (o.flags & POVU_HIP_F_BIG_CLASS_DFS) != 0,
-							      (o.flags & POVU_HIP_F_SPARSE_SPLITTERS) != 0, tm, s);
-				ctx->tree_in_par = true;
-			}
-			ctx->pw.all_vertex_classes = (o.flags & POVU_HIP_F_ALL_VERTEX_CLASSES) != 0;
-			ctx->pw.check_laminar = (o.flags & POVU_HIP_F_CHECK_LAMINAR) != 0;
-			tail.want_overlap = want_async;
-			tail.done = f->ev1;
-			tail.done2 = ctx->tail_done;
-			run_parallel_dg(cs, sw, ctx->pw, C, n_processed, n_stack, dense_nb0, alloc_result_block, tm, s, ctx->side, tail);
-			ctx->stack_export_pending = true;
-			ctx->classes_in_par = true;
-			if (o.flags & POVU_HIP_F_REDO_ODD) // (tests: flag every other component as if its stack were not laminar)
-				mark_odd_u32(ctx->pw.comp_bad, C, s);
-			// Everything the host needs came back with the PVST count, unless something after it can still flag a component
-			// (the laminarity check, the test modes) or add to the result (labels, boundaries): then the summary is read again
-			// when all of that is done.
-			fast_tail = tail.summary_final && !leaf_sub && !hairpins && !(o.flags & (POVU_HIP_F_FORCE_REDO | POVU_HIP_F_REDO_ODD));
-			sum = fast_tail ? tail.early_summary : read_summary(true);
-			if (sum[0])
-				throw HipError("parallel class stage: a tree vertex has no live bracket (internal invariant broken)");
-			if (sum[1] & 1u)
-				throw HipError("list ranking: splitter capacity exceeded (internal sizing bug)");
-			if (sum[1] & 2u)
-				throw HipError("class walk: stack pool exhausted (internal sizing bug)");
-			if (sum[2])
-				throw HipError("spanning forest of the links has the wrong size (internal)");
-			if (sum[3])
-				throw HipError("candidate stack has the wrong size (internal)");
-			uint32_t nbad = 0;
-			for (uint32_t c = 0; c < C; c++)
-				nbad += sum[4 + c] ? 1 : 0;
-			if (leaf_sub) {
-				// find_tiny + find_parallel relabel leaf flubbles (leaf_kernels.hip): the PVSTs the parallel stages just
-				// emitted here, those of components that go through the redo of add_flubbles after it (below)
-				if (nbad && hairpins)
-					throw HipError("leaf subflubble passes: with --hairpins a component that needs the sequential redo is rebuilt "
-						       "from scratch by the one-lane kernels, whose tree state the passes do not read");
-				tm.begin("leaf_subflubbles");
-				leaf_prepare(cs, sw, ctx->pw, ctx->tw, C, ctx->ws_leaf, leaf_state, s);
-				leaf_dense(leaf_state, sw, ctx->pw, C, s);
-				const size_t n = ctx->pw.d_total;
-				f->sub_ai.resize(n, ctx->pool); // (page-locked, out of the context's pool)
-				f->sub_zi.resize(n, ctx->pool);
-				f->sub_fam.resize(n, ctx->pool);
-				if (n) {
-					HIP_CHECK(copy_async(f->sub_ai.data(), leaf_state.dense.ai, n * 4, hipMemcpyDeviceToHost, s));
-					HIP_CHECK(copy_async(f->sub_zi.data(), leaf_state.dense.zi, n * 4, hipMemcpyDeviceToHost, s));
-					HIP_CHECK(copy_async(f->sub_fam.data(), leaf_state.dense.fam, n, hipMemcpyDeviceToHost, s));
-				}
-				tm.end(16);
-				HIP_CHECK(hipStreamSynchronize(s));
-				if (all_sub) {
-					// find_concealed, find_midi, find_smothered insert vertices (sub_kernels.hip); they read the dense PVST the
-					// parallel stages wrote, so a component that needs the sequential redo has no place here
-					if (nbad || (o.flags & (POVU_HIP_F_FORCE_REDO | POVU_HIP_F_REDO_ODD)))
-						throw HipError("subflubble passes: a component went (or was sent) through the sequential redo of add_flubbles, "
-							       "whose PVST layout the inserting passes do not read");
-					tm.begin("subflubbles_insert");
-					f->subx = std::make_shared<SubForest>();
-					run_subflubbles(cs, sw, ctx->pw, ctx->tw, leaf_state, C, ctx->host, *f->subx, ctx->pool, s, &ctx->ws_sub, &ctx->ws_sub_hint);
-					tm.end(40);
-				}
-				sum = nullptr; // (read again below: the pass total then includes this stage)
-			}
-			if (hairpins && !nbad) {
-				run_parallel_hairpins(cs, sw, ctx->pw, C, tm, s);
-				sum = nullptr;
-			}
-			if ((o.flags & POVU_HIP_F_FORCE_REDO) || (nbad && hairpins)) {
-				// (tests; and the boundary report, which the parallel path only has for a whole pass)
-				fill_u32(ctx->pw.comp_bad, C, 1u, s);
-				nbad = C;
-			} else if (nbad) {
-				// only the flagged components go through the sequential kernels; the others keep the dense
-				// result the parallel stages wrote
-				mixed = true;
-			}
-			ctx->last_seq_redo = nbad;
-			ctx->last_mixed = mixed;
-			if (nbad) { // components whose candidate stack is not laminar: exact sequential redo
-				tm.begin("redo_seq");
-				if (dense_nb0 >= 0 && !hairpins) {
-					// Only add_flubbles' stack machine (flubbles.cpp:316-365) cannot be evaluated in closed form on
-					// such a stack; tree, classes, candidate stack and next_seen of the parallel stages stand.  They
-					// are copied into the per-component layout, one lane per flagged component runs the machine.
-					need_seq_workspace();
-					export_parallel_stack(cs, sw, ctx->pw, s);
-					ctx->stack_export_pending = false;
-					HIP_CHECK(hipMemsetAsync(sw.in_s, 0, B + T, s));
-					sw.stages = SEQ_STAGE_PVST | SEQ_STAGE_GIVEN_STACK;
-					ctx->redo_pvst_only = true;
-				} else {
-					if (leaf_sub)
-						throw HipError("leaf subflubble passes: this pass rebuilds the flagged components from scratch with the "
-							       "one-lane kernels, whose tree state the passes do not read");
-					if (dense_nb0 >= 0) // parallel tree: the one-lane kernels start from scratch
-						init_seq_workspace();
-					sw.stages = dense_nb0 >= 0 ? SEQ_STAGE_ALL : (SEQ_STAGE_CLASSES | SEQ_STAGE_STACK | SEQ_STAGE_PVST);
-				}
-				sw.comp_sel = ctx->pw.comp_bad;
-				if (leaf_sub) { // (only reached with the PVST-only redo, see above)
-					sw.p_ai = leaf_state.p_ai;
-					sw.p_zi = leaf_state.p_zi;
-				}
-				launch_seq_components(sw, s);
-				sw.comp_sel = nullptr;
-				if (leaf_sub)
-					leaf_seq(leaf_state, cs, sw, ctx->pw.comp_bad, C, s);
-				tm.end(1);
-				sum = nullptr;
-			}
-		}
-
-		// ---- PVST arrays back to the host
-		tm.begin("pvst_d2h");
-		if (!sum)
-			sum = read_summary(!all_seq);
-		const uint32_t *cstat = sum + 4 + (size_t)C, *npvst = sum + 4 + 2 * (size_t)C, *nbry = sum + 4 + 3 * (size_t)C,
-			       *doff = sum + 4 + 4 * (size_t)C;
-		for (uint32_t c = 0; c < C; c++)
-			if (cstat[c] == 2)
-				throw HipError("internal error: the spanning tree of component " + std::to_string(c + 1) +
-					       " did not reach every side");
-		f->total_components = C;
-		size_t total = 0, total_hp = 0;
-		for (uint32_t c = 0; c < C; c++) {
-			if (npvst[c] == 0)
-				continue;
-			povu_hip_forest::Tree t;
-			t.component_id = c + 1; // decompose.cpp:129
-			t.n_vtx = voff[c + 1] - voff[c];
-			t.n_links = eoff[c + 1] - eoff[c];
-			t.n_pvst = npvst[c];
-			t.off = total;
-			t.hp_off = total_hp;
-			t.n_hairpins = hairpins ? nbry[c] : 0;
-			t.sub_c = c;
-			total += npvst[c];
-			total_hp += t.n_hairpins;
-			f->trees.push_back(t);
-		}
-		const bool dense_out = !all_seq && (ctx->last_seq_redo == 0 || mixed);
-		const uint32_t *bad = sum + 4;
-		// results of the sequential kernels (per-component layout sw.p_*) -> `dst` arrays at every tree's `off`
-		auto fetch_seq = [&](std::vector<povu_hip_forest::Tree *> &ts, uint32_t *da, uint32_t *dz, uint32_t *dp, uint8_t *dao,
-				     uint8_t *dzo, size_t n_total) {
-			std::vector<uint8_t> ors(n_total);
-			if (ts.size() <= 32) { // few trees: copy exactly their spans
-				for (const auto *t : ts) {
-					const size_t pb = (size_t)voff[t->component_id - 1] + (t->component_id - 1);
-					HIP_CHECK(copy_async(da + t->off, sw.p_a + pb, (size_t)t->n_pvst * 4, hipMemcpyDeviceToHost, s));
-					HIP_CHECK(copy_async(dz + t->off, sw.p_z + pb, (size_t)t->n_pvst * 4, hipMemcpyDeviceToHost, s));
-					HIP_CHECK(copy_async(dp + t->off, sw.p_parent + pb, (size_t)t->n_pvst * 4, hipMemcpyDeviceToHost, s));
-					HIP_CHECK(copy_async(ors.data() + t->off, sw.p_or + pb, t->n_pvst, hipMemcpyDeviceToHost, s));
-					if (t->n_hairpins)
-						HIP_CHECK(copy_async(f->hairpins.data() + 2 * t->hp_off, sw.hairpins + 2 * pb,
-									 (size_t)t->n_hairpins * 16, hipMemcpyDeviceToHost, s));
-				}
-				HIP_CHECK(hipEventRecord(f->ev1, s));
-				HIP_CHECK(hipStreamSynchronize(s));
-			} else { // many trees: one bulk copy per array, sliced on the host
-				const size_t P = (size_t)g.V + C;
-				std::vector<uint32_t> ha(P), hz(P), hp(P);
-				std::vector<uint8_t> ho(P);
-				std::vector<uint64_t> hh(hairpins ? 2 * P : 0);
-				HIP_CHECK(copy_async(ha.data(), sw.p_a, P * 4, hipMemcpyDeviceToHost, s));
-				HIP_CHECK(copy_async(hz.data(), sw.p_z, P * 4, hipMemcpyDeviceToHost, s));
-				HIP_CHECK(copy_async(hp.data(), sw.p_parent, P * 4, hipMemcpyDeviceToHost, s));
-				HIP_CHECK(copy_async(ho.data(), sw.p_or, P, hipMemcpyDeviceToHost, s));
-				if (hairpins)
-					HIP_CHECK(copy_async(hh.data(), sw.hairpins, 2 * P * 8, hipMemcpyDeviceToHost, s));
-				HIP_CHECK(hipEventRecord(f->ev1, s));
-				HIP_CHECK(hipStreamSynchronize(s));
-				for (const auto *t : ts) {
-					const size_t pb = (size_t)voff[t->component_id - 1] + (t->component_id - 1);
-					std::copy_n(ha.begin() + pb, t->n_pvst, da + t->off);
-					std::copy_n(hz.begin() + pb, t->n_pvst, dz + t->off);
-					std::copy_n(hp.begin() + pb, t->n_pvst, dp + t->off);
-					std::copy_n(ho.begin() + pb, t->n_pvst, ors.begin() + t->off);
-					if (t->n_hairpins)
-						std::copy_n(hh.begin() + 2 * pb, 2 * (size_t)t->n_hairpins, f->hairpins.begin() + 2 * t->hp_off);
-				}
-			}
-			for (size_t i = 0; i < n_total; i++) {
-				dao[i] = ors[i] & 1;
-				dzo[i] = (ors[i] >> 1) & 1;
-			}
-		};
-		// ... and their subflubble labels (leaf_seq wrote them in the same per-component layout)
-		auto fetch_seq_sub = [&](std::vector<povu_hip_forest::Tree *> &ts, PinnedVec<uint32_t> &dai, PinnedVec<uint32_t> &dzi,
-					 PinnedVec<uint8_t> &dfam, size_t n_total) {
-			dai.assign(n_total, POVU_NIL);
-			dzi.assign(n_total, POVU_NIL);
-			dfam.assign(n_total, 0);
-			const size_t P = (size_t)g.V + C;
-			std::vector<uint32_t> ha(P), hz(P);
-			std::vector<uint8_t> hf(P);
-			HIP_CHECK(copy_async(ha.data(), leaf_state.p_ai, P * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(hz.data(), leaf_state.p_zi, P * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(hf.data(), leaf_state.p_fam, P, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
-			for (const auto *t : ts) {
-				const size_t pb = (size_t)voff[t->component_id - 1] + (t->component_id - 1);
-				std::copy_n(ha.begin() + pb, t->n_pvst, dai.begin() + t->off);
-				std::copy_n(hz.begin() + pb, t->n_pvst, dzi.begin() + t->off);
-				std::copy_n(hf.begin() + pb, t->n_pvst, dfam.begin() + t->off);
-			}
-		};
-		f->hairpins.resize(2 * total_hp);
-		if (dense_out) { // the parallel stages wrote every PVST back to back into f->block
-			if (!mixed && (doff[C] != total || total != ctx->pw.d_total))
-				throw HipError("internal error: dense PVST size mismatch");
-			if (!f->block)
-				f->alloc(ctx->pw.d_total);
-			std::vector<povu_hip_forest::Tree *> redo;
-			size_t redo_total = 0;
-			for (auto &t : f->trees) {
-				if (mixed && bad[t.component_id - 1]) {
-					t.off = redo_total;
-					redo_total += t.n_pvst;
-					redo.push_back(&t);
-				} else {
-					t.off = doff[t.component_id - 1];
-				}
-			}
-			bool more = false;
-			for (const auto &t : f->trees)
-				if (t.n_hairpins) {
-					const size_t pb = (size_t)voff[t.component_id - 1] + (t.component_id - 1);
-					HIP_CHECK(copy_async(f->hairpins.data() + 2 * t.hp_off, sw.hairpins + 2 * pb,
-								 (size_t)t.n_hairpins * 16, hipMemcpyDeviceToHost, s));
-					more = true;
-				}
-			tm.end(0);
-			if (!redo.empty()) { // the redone components get a block of their own
-				povu_hip_forest::ExtraBlock blk;
-				blk.pool = ctx->pool;
-				blk.p = ctx->pool->get(povu_hip_forest::ExtraBlock::bytes_for(redo_total), blk.cap);
-				blk.carve(redo_total);
-				f->extra.push_back(std::move(blk)); // (the raw pointers of blk stay valid: only the owning members move)
-				for (auto *t : redo)
-					t->blk = 0;
-				fetch_seq(redo, blk.a, blk.z, blk.parent, blk.aor, blk.zor, redo_total);
-				if (leaf_sub)
-					fetch_seq_sub(redo, f->extra[0].sub_ai, f->extra[0].sub_zi, f->extra[0].sub_fam, redo_total);
-			} else if (fast_tail && tail.overlapped && !more) {
-				// the arrays are still on their way: the caller (or the next accessor of the forest) waits for ev1
-				f->pending = true;
-				ctx->tail_pending = true;
-			} else if (fast_tail && !more) {
-				HIP_CHECK(hipEventSynchronize(f->ev1)); // (recorded behind the last copy by run_parallel_dg)
-				if (tm.enabled)
-					HIP_CHECK(hipStreamSynchronize(s)); // (the stage events themselves have to complete before they are read)
-			} else if (more || tm.enabled || fast_tail) {
-				HIP_CHECK(hipEventRecord(f->ev1, s));
-				HIP_CHECK(hipStreamSynchronize(s));
-			}
-		} else {
-			if (f->block && f->total_entries != total)
-				f->release_block();
-			if (!f->block)
-				f->alloc(total);
-			std::vector<povu_hip_forest::Tree *> all;
-			for (auto &t : f->trees)
-				all.push_back(&t);
-			tm.end(0);
-			fetch_seq(all, f->a_id.data(), f->z_id.data(), f->parent.data(), f->a_or.data(), f->z_or.data(), total);
-			if (leaf_sub)
-				fetch_seq_sub(all, f->sub_ai, f->sub_zi, f->sub_fam, total);
-		}
-		if (!leaf_sub)
+		SeqLanes lanes{ctx, z, p.hairpins};
+		LeafState leaf_state;
+		RowsOut out = rows_c_to_g(ctx, p, C, rb.gstats, tables, *f, lanes, leaf_state, tm);
+		fetch_result(ctx, p, C, rb.voff, rb.eoff, out, *f, leaf_state, tm);
+		if (!p.leaf_sub)
 			ctx->ws_leaf.release(); // (kept from one -s pass to the next, like the inserting passes' arena below: a hipMalloc of
 						// several GB right after the hipFree of the pass before stalled for over a second once; a
 						// pass without the leaf passes gives it back)
-		if (!all_sub)
+		if (!p.all_sub)
 			ctx->ws_sub.release(); // (the inserting passes keep their tables' arena from one -s pass to the next, no longer)
-		// stage times
-		ctx->last_times.clear();
-		for (auto &r : tm.recs) {
-			povu_hip_stage_time st{};
-			snprintf(st.name, sizeof st.name, "%s", r.name.c_str());
-			float ms = 0;
-			HIP_CHECK(hipEventElapsedTime(&ms, r.a, r.b));
-			st.ms = ms;
-			st.launches = r.launches;
-			ctx->last_times.push_back(st);
-		}
-		if (!f->pending) {
-			povu_hip_stage_time st{};
-			snprintf(st.name, sizeof st.name, "total");
-			f->ready();
-			st.ms = f->pass_ms;
-			ctx->last_times.push_back(st);
-		}
-		ctx->C = C;
-		ctx->have_state = true;
-		if (o.world == 1 && ctx->shard_comp_ids.empty()) { // (povu_hip_forest_walks: a forest of the whole resident graph)
+		stage_times(ctx, tm, *f);
+		ctx->last = LastPass{true, p, C, out.nbad, out.mixed, out.redo_pvst_only, out.stack_export_pending};
+		if (p.world == 1 && ctx->shard_comp_ids.empty()) { // (povu_hip_forest_walks: a forest of the whole resident graph)
 			f->walk_ctx = ctx;
 			f->walk_gen = g.gen;
 		}
@@ -1635,7 +1689,7 @@ extern "C" int povu_hip_last_stage_times(const povu_hip_ctx *ctx, povu_hip_stage
 	return n;
 }
 
-extern "C" uint32_t povu_hip_last_seq_redo(const povu_hip_ctx *ctx) { return ctx ? ctx->last_seq_redo : 0; }
+extern "C" uint32_t povu_hip_last_seq_redo(const povu_hip_ctx *ctx) { return ctx ? ctx->last.seq_redo : 0; }
 
 extern "C" uint64_t povu_hip_last_links_processed(const povu_hip_ctx *ctx) { return ctx ? ctx->last_links : 0; }
 
@@ -1710,12 +1764,12 @@ extern "C" double povu_hip_debug_scan_time(povu_hip_ctx *ctx, size_t n, int reps
 // ---- stage-level parity hooks
 extern "C" int povu_hip_debug_components(povu_hip_ctx *ctx, uint32_t *comp_of, uint32_t *local_idx)
 {
-	if (!ctx || !ctx->have_state)
+	if (!ctx || !ctx->last.valid)
 		return 1;
 	ctx->quiesce();
 	try {
 		HIP_CHECK(hipSetDevice(ctx->device));
-		const uint32_t V = ctx->g.V, C = ctx->C;
+		const uint32_t V = ctx->g.V, C = ctx->last.C;
 		std::vector<uint32_t> pos(V), voff(C + 1);
 		HIP_CHECK(hipMemcpy(comp_of, ctx->cs.comp_of, (size_t)V * 4, hipMemcpyDeviceToHost));
 		if (ctx->cs.lean_identity)
@@ -1734,9 +1788,9 @@ extern "C" int povu_hip_debug_components(povu_hip_ctx *ctx, uint32_t *comp_of, u
 extern "C" int povu_hip_debug_tree(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, uint32_t *gid, uint8_t *typ,
 				   uint32_t *par, uint32_t *cls)
 {
-	if (!ctx || !ctx->have_state || comp >= ctx->C || !n_tree)
+	if (!ctx || !ctx->last.valid || comp >= ctx->last.C || !n_tree)
 		return 1;
-	if (cls && ctx->last_mixed)
+	if (cls && ctx->last.mixed)
 		return 4; // classes of a mixed pass sit in two layouts (parallel stage / one-lane kernels): not exported
 	ctx->quiesce();
 	try {
@@ -1750,7 +1804,7 @@ extern "C" int povu_hip_debug_tree(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n
 			HIP_CHECK(hipMemcpy(gid, ctx->sw.t_gid + tb, (size_t)N * 4, hipMemcpyDeviceToHost));
 		if (par)
 			HIP_CHECK(hipMemcpy(par, ctx->sw.t_par + tb, (size_t)N * 4, hipMemcpyDeviceToHost));
-		const bool par_cls = ctx->classes_in_par && (ctx->last_seq_redo == 0 || ctx->redo_pvst_only);
+		const bool par_cls = !ctx->last.plan.all_seq && (ctx->last.seq_redo == 0 || ctx->last.redo_pvst_only);
 		if (cls && par_cls) {
 			classes_to_tree_space(ctx->pw, ctx->stream);
 			HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -1767,7 +1821,7 @@ extern "C" int povu_hip_debug_tree(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n
 
 extern "C" int povu_hip_last_black_only_classes(const povu_hip_ctx *ctx)
 {
-	return ctx && ctx->have_state && ctx->classes_in_par && ctx->pw.black_only_used ? 1 : 0;
+	return ctx && ctx->last.valid && !ctx->last.plan.all_seq && ctx->pw.black_only_used ? 1 : 0;
 }
 
 extern "C" int povu_hip_last_crossings(povu_hip_ctx *ctx, uint32_t out[2])
@@ -1775,7 +1829,7 @@ extern "C" int povu_hip_last_crossings(povu_hip_ctx *ctx, uint32_t out[2])
 	if (!ctx || !out)
 		return 1;
 	out[0] = out[1] = 0;
-	if (!ctx->have_state || !ctx->classes_in_par || !ctx->pw.laminar_checked)
+	if (!ctx->last.valid || ctx->last.plan.all_seq || !ctx->pw.laminar_checked)
 		return 0;
 	ctx->quiesce();
 	if (hipSetDevice(ctx->device) != hipSuccess)
@@ -1785,16 +1839,16 @@ extern "C" int povu_hip_last_crossings(povu_hip_ctx *ctx, uint32_t out[2])
 
 extern "C" int povu_hip_last_laminar_check_ran(const povu_hip_ctx *ctx)
 {
-	return ctx && ctx->have_state && ctx->classes_in_par && ctx->pw.laminar_checked ? 1 : 0;
+	return ctx && ctx->last.valid && !ctx->last.plan.all_seq && ctx->pw.laminar_checked ? 1 : 0;
 }
 
 extern "C" int povu_hip_debug_edge_ids(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, uint32_t *tree_edge_id)
 {
-	if (!ctx || !ctx->have_state || comp >= ctx->C || !n_tree)
+	if (!ctx || !ctx->last.valid || comp >= ctx->last.C || !n_tree)
 		return 1;
-	if (!ctx->tree_in_par)
+	if (!ctx->last.plan.par_tree)
 		return 3; // the one-lane tree kernels keep no per-side scan state
-	if (ctx->last_mixed)
+	if (ctx->last.mixed)
 		return 4; // (see povu_hip_debug_tree)
 	uint32_t *dw = nullptr;
 	ctx->quiesce();
@@ -1806,7 +1860,7 @@ extern "C" int povu_hip_debug_edge_ids(povu_hip_ctx *ctx, uint32_t comp, uint32_
 		*n_tree = N;
 		if (!tree_edge_id || N == 0)
 			return 0;
-		const size_t T = 2 * (size_t)ctx->sw.V + ctx->C, tb = 2 * (size_t)voff + comp;
+		const size_t T = 2 * (size_t)ctx->sw.V + ctx->last.C, tb = 2 * (size_t)voff + comp;
 		HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dw), 2 * T * 4));
 		HIP_CHECK(hipMemsetAsync(dw, 0, 2 * T * 4, ctx->stream));
 		debug_edge_id_weights(ctx->cs, ctx->sw, ctx->tw, dw, dw + T, ctx->stream);
@@ -1840,17 +1894,17 @@ extern "C" int povu_hip_debug_edge_ids(povu_hip_ctx *ctx, uint32_t comp, uint32_
 extern "C" int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t *tree_vtx, uint32_t *cls,
 				    uint32_t *next_seen)
 {
-	if (!ctx || !ctx->have_state || comp >= ctx->C || !n)
+	if (!ctx || !ctx->last.valid || comp >= ctx->last.C || !n)
 		return 1;
-	if (ctx->last_mixed)
+	if (ctx->last.mixed)
 		return 4; // the candidate stacks of a mixed pass sit in two layouts: not exported (see povu_hip_debug_tree)
 	ctx->quiesce();
 	try {
 		HIP_CHECK(hipSetDevice(ctx->device));
-		if (ctx->stack_export_pending && ctx->last_seq_redo == 0) {
+		if (ctx->last.stack_export_pending && ctx->last.seq_redo == 0) {
 			export_parallel_stack(ctx->cs, ctx->sw, ctx->pw, ctx->stream);
 			HIP_CHECK(hipStreamSynchronize(ctx->stream));
-			ctx->stack_export_pending = false;
+			ctx->last.stack_export_pending = false;
 		}
 		uint32_t voff = 0, ns = 0;
 		HIP_CHECK(hipMemcpy(&voff, ctx->cs.voff + comp, 4, hipMemcpyDeviceToHost));

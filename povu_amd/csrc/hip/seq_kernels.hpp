@@ -24,7 +24,7 @@ namespace povu_hip
 //   PVST vertices: <= nv_c + 1, component c owns [voff[c] + c, ...)
 struct SeqWs {
 	uint32_t V, E, C;
-	uint32_t rank, world, flags;
+	uint32_t rank, world;
 	uint32_t stages;	  // SEQ_STAGE_* mask
 	const uint32_t *comp_sel; // optional [C]: only components with a non-zero entry are processed
 	// inputs (sorted space)

@@ -138,18 +138,7 @@ extern "C" int povu_hip_lpt_assign(const uint64_t *weights, uint32_t n, uint32_t
 	if ((!weights && n) || !owner_out || world == 0)
 		return 1;
 	std::vector<uint32_t> order(n);
-	std::iota(order.begin(), order.end(), 0u);
-	std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return weights[a] > weights[b]; });
-	std::vector<uint64_t> load(world, 0);
-	for (uint32_t k = 0; k < n; k++) {
-		const uint32_t c = order[k];
-		uint32_t best = 0;
-		for (uint32_t r = 1; r < world; r++)
-			if (load[r] < load[best])
-				best = r;
-		owner_out[c] = best;
-		load[best] += weights[c] + 1;
-	}
+	lpt_assign(weights, n, world, order.data(), owner_out);
 	return 0;
 }
 
@@ -189,7 +178,7 @@ extern "C" povu_hip_shards *povu_hip_shard_partition(povu_hip_ctx *ctx, uint32_t
 		z.slots = g.n_slots;
 		z.T = z.B = 0;
 		CompState &cs = ctx->cs;
-		ctx->have_state = false;
+		ctx->last.valid = false;
 		ctx->host.reset();
 		cs.host = &ctx->host;
 		cs.host_pub = nullptr;
@@ -377,14 +366,14 @@ extern "C" int povu_hip_graph_upload_shard(povu_hip_ctx *ctx, const void *packed
 			throw HipError("packed shard has the wrong size");
 		if (nv == 0) { // a rank that owns no component: nothing resident, decompose returns an empty forest
 			free_resident_graph(ctx->g);
-			ctx->have_state = false;
+			ctx->last.valid = false;
 			ctx->shard_comp_ids.clear();
 			ctx->shard_total_components = (uint32_t)h[4];
 			return 0;
 		}
 		check_graph_size(nv, ne);
 		free_resident_graph(ctx->g);
-		ctx->have_state = false;
+		ctx->last.valid = false;
 		alloc_resident_graph(ctx->graph_arena, g, nv, ne, true);
 		const char *b = static_cast<const char *>(packed);
 		hipEvent_t e0, e1;

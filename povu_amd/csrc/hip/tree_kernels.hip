@@ -1966,9 +1966,9 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 		if (!tm.enabled) {
 			uint32_t *w = tw.host->take<uint32_t>(1);
 			publish_words(w, WordSrc{{n_over}}, 1, s);
-			tw.host->mark(s);
+			const HostScratch::Token published = tw.host->mark(s);
 			enqueue_events();
-			tw.host->wait();
+			tw.host->wait(published);
 			n_big = *w;
 			events_done = n_big == 0;
 		} else {

@@ -105,6 +105,20 @@ def test_subtree_arrays_and_the_plain_forest(hip):
         f0.subtree(0)
 
 
+def test_not_with_a_forced_or_odd_redo(hip):
+    """The inserting passes read the dense PVST: a pass that sends components through the redo is refused.  With
+    --hairpins the refusal of a component the pass flags comes first, as before."""
+    from povu_amd.hip import F_FORCE_REDO, F_HAIRPINS, F_REDO_ODD
+    g = W.bubble_zoo(12, 6, 77)
+    hip.upload(g)
+    for fl in (F_FORCE_REDO, F_REDO_ODD):
+        with pytest.raises(RuntimeError, match="subflubble passes: a component went \\(or was sent\\) through the sequential redo"):
+            hip.decompose(flags=F_SUBFLUBBLES | fl)
+    with pytest.raises(RuntimeError, match="with --hairpins a component that needs the sequential redo"):
+        hip.decompose(flags=F_SUBFLUBBLES | F_REDO_ODD | F_HAIRPINS)
+    assert hip.decompose(flags=F_SUBFLUBBLES).texts() == O.decompose(g, leaf=2)  # (the context is still good)
+
+
 def test_cli_subflubbles(tmp_path):
     g = W.random_bidirected(400, 560, 11)
     gfa = tmp_path / "g.gfa"
