@@ -440,6 +440,13 @@ int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t
  * 1 = running maximum) and, when in2 is given, an independent sum scan of in2[0..n2) in the same launch */
 int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,
 			uint32_t *out2, size_t n2);
+/* unit-test hook for the list ranking of the tree stage: suffix sums (inclusive, mod 2^32) along the lists next[0..n)
+ * (NIL = end of a list; heads[0..nh) = their first elements, NIL entries allowed) -- mode 0: ra of the 0/1 weights w;
+ * mode 1: the pre-order events' two sums (element x enters when x % 3 == 0, see tree_kernels.hip), ra and rb.  bits =
+ * splitter bucket bits, 2..6 (0: the default).  Elements in no list get no defined value.  0 = ok, 1 = bad arguments,
+ * 2 = device error. */
+int povu_hip_debug_list_rank(povu_hip_ctx *ctx, uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads,
+			     uint32_t nh, int mode, uint32_t bits, uint32_t *ra, uint32_t *rb);
 /* timing hook (tools/scan_time.py): `reps` exclusive scans (op as above) of n device-resident words, ms per scan by HIP
  * events; < 0 on error */
 double povu_hip_debug_scan_time(povu_hip_ctx *ctx, size_t n, int reps, int op);

@@ -1727,6 +1727,21 @@ extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in
 	}
 }
 
+// ---- unit-test hook for the list ranking of the tree stage (tree_kernels.hip, debug_list_rank)
+extern "C" int povu_hip_debug_list_rank(povu_hip_ctx *ctx, uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads,
+					uint32_t nh, int mode, uint32_t bits, uint32_t *ra, uint32_t *rb)
+{
+	if (!ctx || !next || !w || (nh && !heads) || !ra || (mode != 0 && !rb) || mode < 0 || mode > 1)
+		return 1;
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		debug_list_rank(n, next, w, heads, nh, mode, bits, ra, rb, ctx->stream);
+		return 0;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
 // ---- timing hook for the scans: `reps` exclusive sum scans of n words (device resident, all ones), ms per scan by HIP events
 extern "C" double povu_hip_debug_scan_time(povu_hip_ctx *ctx, size_t n, int reps, int op)
 {

@@ -32,6 +32,7 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <vector>
 
 namespace povu_hip
 {
@@ -328,8 +329,9 @@ static int list_rank(uint32_t n, unsigned bits, uint32_t *nxtA, uint32_t *nxtB, 
 // ---- work-efficient list ranking, recursive.  Level 0 is the list itself (packed words, 0/1 weights).  One lane per
 // splitter (= per bucket, plus one per list head) walks its segment and leaves {next splitter, segment sums} -- the
 // element of the next level, whose index is the bucket idx.  Levels shrink by 2^b until one workgroup ranks the top in
-// LDS (pointer jumping); then every level hands its elements their suffix sums on the way back down.  A list of n
-// elements costs about n(1 + 2^-b + ...) dependent loads up and the same down.
+// LDS (pointer jumping); then every level above the list hands its elements their suffix sums on the way back down.
+// The list itself is walked once: its walk up leaves a record per element, from which the readers work out the rank
+// (see k_rank_up).  A list of n elements costs about n(1 + 2^-b + ...) dependent loads up and n 2^-b(1 + ...) down.
 // Heads: an element that heads a list is never reached through its bucket (its lane stays idle); head h of the caller's
 // head array is element m + h of every level above 0 (m = buckets of the level below) and is walked by its own lane.
 // TWO: second weight = +1 where the first is 1, -1 where it is 0 (enter / leave events).
@@ -371,16 +373,24 @@ __device__ __forceinline__ void rank_l0_weights(uint32_t x, uint32_t p, uint32_t
 		wb = wa ? 1u : 0xFFFFFFFFu;
 	}
 }
+// Level 0 leaves an 8-byte RECORD per element on the walk up, and no walk goes down it again: the lane's id (= the
+// element one level up whose rank the walks above hand out) and the sums from the splitter up to, not including, the
+// element.  Its rank is then R[owner] - partial (rank_l0 / rank_l0_pair), resolved by the kernels that read it -- one
+// store per element, where the way back stored the rank itself.  rec[x] = {owner, partial}; with TWO the second word
+// holds partial(a) | (partial(a) - partial(b)) << 16 (both never negative, at most two per element), and a segment
+// whose sums outgrow 16 bits raises *ovf: k_rank_l0_fallback then walks the list once more and stores final ranks.
+static constexpr uint32_t REC_MAX = 0xFFFFu;
 template <bool L0, bool TWO, bool EVT3 = false>
 __global__ void k_rank_up(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ nx_in, const uint32_t *__restrict__ a_in,
 			  const uint32_t *__restrict__ b_in, const uint32_t *__restrict__ heads, uint32_t *__restrict__ nx_out,
-			  uint32_t *__restrict__ a_out, uint32_t *__restrict__ b_out)
+			  uint32_t *__restrict__ a_out, uint32_t *__restrict__ b_out, uint2 *__restrict__ rec, uint32_t *__restrict__ ovf)
 {
 	const uint32_t id = BIDX * blockDim.x + threadIdx.x;
 	if (id >= A.M)
 		return;
 	uint32_t x = rank_lane_start<L0>(id, A, b, nx_in, heads);
 	uint32_t sa = 0, sb = 0, out = PK_END | PK_STOP;
+	bool big = false;
 	if (x != NIL) {
 		uint32_t p;
 		bool stop;
@@ -389,6 +399,12 @@ __global__ void k_rank_up(RankLevelArgs A, unsigned b, const uint32_t *__restric
 			if (L0) {
 				uint32_t wa, wb;
 				rank_l0_weights<EVT3>(x, p, wa, wb);
+				if (TWO) {
+					big |= sa > REC_MAX || sa - sb > REC_MAX;
+					rec[x] = make_uint2(id, sa | ((sa - sb) << 16));
+				} else {
+					rec[x] = make_uint2(id, sa);
+				}
 				sa += wa;
 				if (TWO)
 					sb += wb;
@@ -411,53 +427,59 @@ __global__ void k_rank_up(RankLevelArgs A, unsigned b, const uint32_t *__restric
 	a_out[id] = sa;
 	if (TWO)
 		b_out[id] = sb;
+	if (L0 && TWO && big)
+		*ovf = 1u;
 }
-// the way back: lane `id` knows the suffix sums at its splitter (ra / rb of the level above) and hands every element of
-// its segment its own.  Level 0 writes the caller's arrays, the levels above overwrite their weights in place.
-template <bool L0, bool TWO, bool EVT3 = false>
+// (a pass whose level-0 walk raised *ovf: the old way back over the list, final ranks {a, b} into rec; a grid-stride loop
+// over the lanes, so that the launch costs next to nothing when the flag is down)
+template <bool EVT3>
+__global__ void k_rank_l0_fallback(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ pk, const uint32_t *__restrict__ heads,
+				   const uint32_t *__restrict__ ra, const uint32_t *__restrict__ rb, uint2 *__restrict__ rec,
+				   const uint32_t *__restrict__ ovf)
+{
+	if (!*ovf)
+		return;
+	for (uint32_t id = BIDX * blockDim.x + threadIdx.x; id < A.M; id += gridDim.x * blockDim.x) {
+		uint32_t x = rank_lane_start<true>(id, A, b, pk, heads);
+		if (x == NIL)
+			continue;
+		uint32_t sa = ra[id], sb = rb[id];
+		do {
+			const uint32_t p = pk[x];
+			uint32_t wa, wb;
+			rank_l0_weights<EVT3>(x, p, wa, wb);
+			rec[x] = make_uint2(sa, sb);
+			sa -= wa;
+			sb -= wb;
+			x = p & P0_END;
+		} while (!rank_l0_stop(x, b));
+	}
+}
+// the way back (levels >= 1): lane `id` knows the suffix sums at its splitter (ra / rb of the level above) and hands
+// every element of its segment its own, in place of its weights.
+template <bool TWO>
 __global__ void k_rank_down(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ nx_in, uint32_t *a_io, uint32_t *b_io,
-			    const uint32_t *__restrict__ heads, const uint32_t *__restrict__ ra, const uint32_t *__restrict__ rb,
-			    uint32_t *__restrict__ out1, uint2 *__restrict__ out12)
+			    const uint32_t *__restrict__ ra, const uint32_t *__restrict__ rb)
 {
 	const uint32_t id = BIDX * blockDim.x + threadIdx.x;
 	if (id >= A.M)
 		return;
-	uint32_t x = rank_lane_start<L0>(id, A, b, nx_in, heads);
+	uint32_t x = rank_lane_start<false>(id, A, b, nx_in, nullptr);
 	if (x == NIL)
 		return;
 	uint32_t sa = ra[id], sb = TWO ? rb[id] : 0, p;
 	do {
 		p = nx_in[x];
-		if (L0) {
-			uint32_t wa, wb;
-			rank_l0_weights<EVT3>(x, p, wa, wb);
-			if (TWO) { // both sums in one 8-byte store
-				out12[x] = make_uint2(sa, sb);
-				sb -= wb;
-			} else {
-				out1[x] = sa;
-			}
-			sa -= wa;
-		} else {
-			const uint32_t wa = a_io[x];
-			a_io[x] = sa;
-			sa -= wa;
-			if (TWO) {
-				const uint32_t wb = b_io[x];
-				b_io[x] = sb;
-				sb -= wb;
-			}
+		const uint32_t wa = a_io[x];
+		a_io[x] = sa;
+		sa -= wa;
+		if (TWO) {
+			const uint32_t wb = b_io[x];
+			b_io[x] = sb;
+			sb -= wb;
 		}
-		if (L0) {
-			x = p & P0_END;
-			if (rank_l0_stop(x, b))
-				break;
-		} else {
-			x = p & PK_END;
-			if (p & PK_STOP)
-				break;
-		}
-	} while (true);
+		x = p & PK_END;
+	} while (!(p & PK_STOP));
 }
 // top level: inclusive suffix sums of at most RANK_TOP elements by pointer jumping in LDS, one workgroup
 template <bool TWO>
@@ -528,10 +550,38 @@ static constexpr int RANK_MAX_LEVELS = 12;
 // the one before it again -- < 3.2 M in all
 static size_t rank_pool_words(size_t n, size_t nh) { return n / 2 + 4 * nh + 64; }
 
-// suffix sums (inclusive) along the lists packed in rb.pk: out1 of the 0/1 weights or, when TWO, out12 = {that sum,
-// the sum of the +-1 weights derived from them}
+// Where a level-0 rank is read (k_t0_parents, k_bridges, k_tree_emit): R = the inclusive suffix sums of the level-1
+// elements (rb.wa, and rb.wb when TWO), M of them; with TWO, fin = the overflow word (set: the records hold final
+// ranks).  (An owner outside R -- only a slot no tour reaches, which k_t0_parents reports as an error -- reads 0
+// instead of memory past the pool.)
+struct L0Ranks {
+	const uint32_t *ra, *rb, *fin;
+	uint32_t M;
+};
+// rank of an element (the 0/1 weights) from its record {owner, partial} ...
+__device__ __forceinline__ uint32_t rank_l0(const L0Ranks &R, uint2 rec)
+{
+	return (rec.x < R.M ? R.ra[rec.x] : 0u) - rec.y;
+}
+// ... and with TWO (fin read once per lane by the caller) the first sum or both
+__device__ __forceinline__ uint32_t rank_l0_a(const L0Ranks &R, uint2 rec, bool fin)
+{
+	return fin ? rec.x : (rec.x < R.M ? R.ra[rec.x] : 0u) - (rec.y & REC_MAX);
+}
+__device__ __forceinline__ uint2 rank_l0_pair(const L0Ranks &R, uint2 rec, bool fin)
+{
+	if (fin)
+		return rec;
+	const bool in = rec.x < R.M;
+	const uint32_t ra = in ? R.ra[rec.x] : 0u, rb = in ? R.rb[rec.x] : 0u, pa = rec.y & REC_MAX;
+	return make_uint2(ra - pa, rb - pa + (rec.y >> 16));
+}
+
+// suffix sums (inclusive) along the lists packed in rb.pk, left as level-0 records rec[x] (k_rank_up) to be resolved
+// by rank_l0 (the 0/1 weights) or rank_l0_pair (TWO: that sum and the sum of the +-1 weights derived from them; `ovf`
+// = a device word for the overflow flag).  R stays valid until the pools are used again.
 template <bool TWO, bool EVT3 = false>
-static void list_rank_splitters(uint32_t n, unsigned b, uint32_t *out1, uint2 *out12, uint32_t nh, RankBufs &rb, hipStream_t s)
+static L0Ranks list_rank_splitters(uint32_t n, unsigned b, uint2 *rec, uint32_t *ovf, uint32_t nh, RankBufs &rb, hipStream_t s)
 {
 	if (n >= P0_END)
 		throw HipError("list ranking: more than 2^30 elements (graph too large for the packed walk)");
@@ -563,12 +613,15 @@ static void list_rank_splitters(uint32_t n, unsigned b, uint32_t *out1, uint2 *o
 		}
 		cur_n = next_n;
 	}
+	if (TWO)
+		HIP_CHECK(hipMemsetAsync(ovf, 0, 4, s));
 	for (int L = 0; L < levels; L++) {
 		const RankLevelArgs &A = lv[L];
 		if (L == 0)
-			LAUNCH((k_rank_up<true, TWO, EVT3>), A.M, s, A, b, nxp[0], nullptr, nullptr, rb.heads, nxp[1], wap[1], wbp[1]);
+			LAUNCH((k_rank_up<true, TWO, EVT3>), A.M, s, A, b, nxp[0], nullptr, nullptr, rb.heads, nxp[1], wap[1], wbp[1], rec, ovf);
 		else
-			LAUNCH((k_rank_up<false, TWO>), A.M, s, A, b, nxp[L], wap[L], wbp[L], nullptr, nxp[L + 1], wap[L + 1], wbp[L + 1]);
+			LAUNCH((k_rank_up<false, TWO>), A.M, s, A, b, nxp[L], wap[L], wbp[L], nullptr, nxp[L + 1], wap[L + 1], wbp[L + 1],
+			       nullptr, nullptr);
 	}
 	const uint32_t nt = cur_n; // elements of the top level
 	if (nt <= RANK_TOP) {
@@ -587,18 +640,78 @@ static void list_rank_splitters(uint32_t n, unsigned b, uint32_t *out1, uint2 *o
 				HIP_CHECK(copy_async(wbp[levels], bA, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
 		}
 	}
-	for (int L = levels - 1; L >= 0; L--) {
+	// (level 0 has no way back: its records are resolved where they are read)
+	for (int L = levels - 1; L >= 1; L--) {
 		const RankLevelArgs &A = lv[L];
-		if (L == 0)
-			LAUNCH((k_rank_down<true, TWO, EVT3>), A.M, s, A, b, nxp[0], nullptr, nullptr, rb.heads, wap[1], wbp[1], out1, out12);
-		else
-			LAUNCH((k_rank_down<false, TWO>), A.M, s, A, b, nxp[L], wap[L], wbp[L], nullptr, wap[L + 1], wbp[L + 1], nullptr,
-			       nullptr);
+		LAUNCH((k_rank_down<TWO>), A.M, s, A, b, nxp[L], wap[L], wbp[L], wap[L + 1], wbp[L + 1]);
 	}
+	if (TWO)
+		KLAUNCH((k_rank_l0_fallback<EVT3>), dim3(std::min(nblk(lv[0].M), 2048u)), dim3(TPB), 0, s, lv[0], b, rb.pk, rb.heads, wap[1],
+			wbp[1], rec, ovf);
+	return L0Ranks{wap[1], TWO ? wbp[1] : nullptr, TWO ? ovf : nullptr, lv[0].M};
+}
+
+// (unit-test hook, debug_list_rank) every element's rank resolved from its record, as the readers do
+template <bool TWO>
+__global__ void k_rank_resolve(uint32_t n, const uint2 *__restrict__ rec, L0Ranks R, uint32_t *__restrict__ ra, uint32_t *__restrict__ rb)
+{
+	const uint32_t x = BIDX * blockDim.x + threadIdx.x;
+	if (x >= n)
+		return;
+	if (TWO) {
+		const uint2 r = rank_l0_pair(R, rec[x], *R.fin != 0);
+		ra[x] = r.x;
+		rb[x] = r.y;
+	} else {
+		ra[x] = rank_l0(R, rec[x]);
+	}
+}
+void debug_list_rank(uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads, uint32_t nh, int mode,
+		     unsigned bits, uint32_t *ra, uint32_t *rb, hipStream_t s)
+{
+	if (n == 0 || n >= P0_END)
+		throw HipError("debug_list_rank: n must be in [1, 2^30)");
+	const unsigned b = bits ? std::min(6u, std::max(2u, bits)) : rank_bucket_bits(n);
+	std::vector<uint32_t> pk(n);
+	for (uint32_t x = 0; x < n; x++) {
+		if (next[x] != NIL && next[x] >= n)
+			throw HipError("debug_list_rank: successor out of range");
+		pk[x] = (next[x] == NIL ? P0_END : next[x]) | (w[x] ? P0_W : 0u);
+	}
+	for (uint32_t h = 0; h < nh; h++)
+		if (heads[h] != NIL) {
+			if (heads[h] >= n)
+				throw HipError("debug_list_rank: head out of range");
+			pk[heads[h]] |= P0_HEAD;
+		}
+	const size_t pool = rank_pool_words(n, nh);
+	Arena ar;
+	ar.reserve(Arena::padded(n + 16, 4) * 3 + Arena::padded(n + 16, 8) + Arena::padded(nh + 1, 4) + 6 * Arena::padded(pool, 4) + 8192, false);
+	RankBufs rbf{};
+	rbf.pk = ar.take<uint32_t>(n + 16);
+	rbf.heads = ar.take<uint32_t>(nh + 1);
+	for (uint32_t **q : {&rbf.nx, &rbf.wa, &rbf.wb, &rbf.tA, &rbf.tB, &rbf.tC})
+		*q = ar.take<uint32_t>(pool);
+	uint32_t *da = ar.take<uint32_t>(n + 16), *db = ar.take<uint32_t>(n + 16), *ovf = ar.take<uint32_t>(4);
+	uint2 *rec = ar.take<uint2>(n + 16);
+	HIP_CHECK(copy_async(rbf.pk, pk.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+	if (nh)
+		HIP_CHECK(copy_async(rbf.heads, heads, (size_t)nh * 4, hipMemcpyHostToDevice, s));
+	if (mode == 0) {
+		const L0Ranks R = list_rank_splitters<false>(n, b, rec, nullptr, nh, rbf, s);
+		LAUNCH(k_rank_resolve<false>, n, s, n, rec, R, da, nullptr);
+	} else {
+		const L0Ranks R = list_rank_splitters<true, true>(n, b, rec, ovf, nh, rbf, s);
+		LAUNCH(k_rank_resolve<true>, n, s, n, rec, R, da, db);
+	}
+	HIP_CHECK(copy_async(ra, da, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+	if (mode != 0)
+		HIP_CHECK(copy_async(rb, db, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
 }
 
 // ------------------------------------------------------------------ 2. rooted forest T0 and 3. its bridges
-// dist[a] = arcs after a in its tour; position of arc a = (arcs of the components before) + L - 1 - dist[a], L = 2 (nv - 1).
+// dist[a] = arcs after a in its tour (rank_l0 of the tour's record trec[a]); position of arc a = (arcs of the components before) + L - 1 - dist[a], L = 2 (nv - 1).
 // u->w is the advance arc of the hooked link {u,w} iff it comes first: then w is the side its segment is ENTERED
 // through (parent u), the segment's other side is the child of w over the black edge, and the segment's subtree is the
 // stretch of the tour from that arc (position tin) to its twin (position tout).  One record per segment:
@@ -619,7 +732,7 @@ static void list_rank_splitters(uint32_t n, unsigned b, uint32_t *out1, uint2 *o
 // idx, so a result is reproducible).  This replaces two range-min queries per side over segment trees of the far ends'
 // pre-order numbers, and the forest needs no pre-order numbering at all.
 static constexpr uint32_t T0_RBIT = 0x80000000u;
-__global__ void k_t0_parents(uint32_t V, const uint32_t *__restrict__ dist, const uint32_t *__restrict__ ckey,
+__global__ void k_t0_parents(uint32_t V, const uint2 *__restrict__ trec, L0Ranks R, const uint32_t *__restrict__ ckey,
 			     const uint32_t *__restrict__ voff, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
 			     const uint32_t *__restrict__ lle,
 			     const uint32_t *__restrict__ ft, const uint32_t *__restrict__ heads,
@@ -634,7 +747,7 @@ __global__ void k_t0_parents(uint32_t V, const uint32_t *__restrict__ dist, cons
 		t0seg[r >> 1] = make_uint4(NIL, (r & 1u) ? T0_RBIT : 0u, 0u, L ? L - 1 : 0u);
 		// the tour of the component covers all its arcs iff the hooks of the union-find are a spanning tree
 		const uint32_t h = heads[g];
-		if (h == NIL ? L != 0 : dist[h] != L - 1)
+		if (h == NIL ? L != 0 : rank_l0(R, trec[h]) != L - 1)
 			atomicExch(err, 1u);
 	}
 	if (g >= V)
@@ -649,11 +762,20 @@ __global__ void k_t0_parents(uint32_t V, const uint32_t *__restrict__ dist, cons
 	const uint32_t sb = loff[2 * g], sm = loff[2 * g + 1], se = loff[2 * g + 2];
 	uint32_t at_e = NIL, dmin = 0xFFFFFFFFu, dmax = 0u;
 	for (uint32_t at0 = sb; at0 < se; at0 += 4) {
-		const uint4 lw4 = load4_unaligned(lle + at0), d4 = load4_unaligned(dist + at0);
-		const uint32_t lws[4] = {lw4.x, lw4.y, lw4.z, lw4.w}, ds[4] = {d4.x, d4.y, d4.z, d4.w};
+		const uint32_t *r32 = reinterpret_cast<const uint32_t *>(trec + at0);
+		const uint4 lw4 = load4_unaligned(lle + at0), r01 = load4_unaligned(r32), r23 = load4_unaligned(r32 + 4);
+		const uint32_t lws[4] = {lw4.x, lw4.y, lw4.z, lw4.w};
+		const uint2 rs[4] = {make_uint2(r01.x, r01.y), make_uint2(r01.z, r01.w), make_uint2(r23.x, r23.y), make_uint2(r23.z, r23.w)};
+		bool tree[4];
+		uint32_t ds[4];
+#pragma unroll
+		for (uint32_t q = 0; q < 4; q++) { // (the four gathers of R issued together)
+			tree[q] = at0 + q < se && (lws[q] & LLE_TREE);
+			ds[q] = tree[q] ? rank_l0(R, rs[q]) : 0u;
+		}
 #pragma unroll
 		for (uint32_t q = 0; q < 4; q++) {
-			if (at0 + q >= se || !(lws[q] & LLE_TREE))
+			if (!tree[q])
 				continue;
 			if (ds[q] < dmin) {
 				dmin = ds[q];
@@ -731,7 +853,7 @@ static constexpr uint32_t CS_VISITED = 0x40000000u; // (side ids stay below 2^29
 __global__ void k_bridges(uint32_t V, const uint4 *__restrict__ t0seg, const ulonglong2 *__restrict__ xps,
 			  const uint4 *__restrict__ xrec,
 			  const ulonglong2 *__restrict__ hside, const uint32_t *__restrict__ ft,
-			  const uint32_t *__restrict__ dist, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ lle,
+			  const uint2 *__restrict__ trec, L0Ranks R, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ lle,
 			  const uint32_t *__restrict__ ckey, const uint32_t *__restrict__ cproc, const uint32_t *__restrict__ voff,
 			  uint8_t *multi, uint32_t *__restrict__ cstate, uint2 *__restrict__ dps)
 {
@@ -773,10 +895,10 @@ __global__ void k_bridges(uint32_t V, const uint4 *__restrict__ t0seg, const ulo
 		if (r.x == NIL) // root segment: the start side's arcs come first, the far side's are the rest of the tour
 			end = abase + L;
 		else if (a3 != FT_NONE && (lle[a3] & LLE_ID) != (r.y & ~T0_RBIT)) // arcs of the entered side in front of the entering one follow
-			end = abase + (L - 1 - dist[a3]);
+			end = abase + (L - 1 - rank_l0(R, trec[a3]));
 		else
 			end = r.w;
-		x = hx(x, stretch(abase + (L - 1 - dist[a1]), end));
+		x = hx(x, stretch(abase + (L - 1 - rank_l0(R, trec[a1])), end));
 	}
 	uint32_t pvF;
 	if (hzero(x)) {
@@ -1397,7 +1519,7 @@ __global__ void k_events(uint32_t V, const uint2 *__restrict__ dps, const uint32
 }
 
 // ------------------------------------------------------------------ 8. tree arrays + back edges
-__global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ cd, const uint8_t *__restrict__ merged,
+__global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks R, const uint8_t *__restrict__ merged,
 			    const uint2 *__restrict__ dps, const uint32_t *__restrict__ ckey,
 			    const uint32_t *__restrict__ cproc, const uint32_t *__restrict__ voff,
 			    const unsigned long long *__restrict__ start_key, const uint32_t *__restrict__ gid_s,
@@ -1466,19 +1588,27 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ cd, const uin
 		return;
 	}
 	const uint32_t Nh = 2 * (voff[c + 1] - v0), hd = start_key[c] != ~0ull ? 1u : 0u;
-	// cd[event] = {sides entered from this event to the end of the list, net depth change from here to the end}
-	const uint4 cd01 = load4_unaligned(reinterpret_cast<const uint32_t *>(cd + 3 * g)); // cd[3g], cd[3g + 1]
-	const uint2 ent = make_uint2(cd01.x, cd01.y), lv_o = make_uint2(cd01.z, cd01.w);
+	// cd(event) = {sides entered from this event to the end of the list, net depth change from here to the end}, worked out
+	// from the event's record (rank_l0_pair)
+	const bool fin = *R.fin != 0;
+	const uint4 r01 = load4_unaligned(reinterpret_cast<const uint32_t *>(erec + 3 * g)); // records of 3g, 3g + 1
+	const uint2 ent = rank_l0_pair(R, make_uint2(r01.x, r01.y), fin);
+	const uint2 lv_o = make_uint2(rank_l0_a(R, make_uint2(r01.z, r01.w), fin), 0u);
 	const uint4 d4 = *reinterpret_cast<const uint4 *>(dps + 2 * g); // the DFS records of both sides
 	const uint32_t o = d4.x == 2 * g + 1 ? 2 * g : 2 * g + 1, e = o ^ 1u; // far side: its DFS parent is the other side
 	const uint32_t p = (e & 1u) ? d4.z : d4.x;			       // the entered side's parent
 	const uint32_t pre_e = Nh - ent.x, depth_e = 0u - ent.y;
-	const uint32_t size_o = ent.x - 1 - lv_o.x, size_e = ent.x - (merged[g] ? lv_o.x : cd[3 * g + 2].x);
+	uint32_t lv_e = lv_o.x;
+	if (!merged[g]) {
+		lv_e = rank_l0_a(R, erec[3 * g + 2], fin);
+	}
+	const uint32_t size_o = ent.x - 1 - lv_o.x, size_e = ent.x - lv_e;
 	uint32_t par_e;
 	if (p == NIL)
 		par_e = hd ? 0u : NIL;
-	else
-		par_e = hd + (Nh - cd[3 * (p >> 1)].x) + (dps[p].x == (p ^ 1u) ? 1u : 0u);
+	else {
+		par_e = hd + (Nh - rank_l0_a(R, erec[3 * (p >> 1)], fin)) + (dps[p].x == (p ^ 1u) ? 1u : 0u);
+	}
 	const uint32_t l = hd + pre_e, t = tb + l; // e sits at t, o at t + 1
 	const uint32_t gid = gid_s[g];
 	store2_unaligned(t_gid + t, gid, gid);
@@ -1781,7 +1911,7 @@ static void tree_spans(TreeWs &tw, size_t V, size_t E, size_t Cmax, int groups, 
 	take1((void **)&tw.dvis_slots, std::max(2 * E, 2 * V) + 16); // per-slot duplicate flags (hub graphs); earlier: per-side class flags
 	take1((void **)&tw.side_tidx, nS * 4);
 	take1((void **)&tw.dps, nS * 8);
-	take((void **)&tw.dist, NSL * 4);
+	take((void **)&tw.dist, (2 * E + 16) * 8);
 	take((void **)&tw.xrec, (NA / 64 + 4) * 16);
 	take((void **)&tw.xrank, (NA / 64 + 4) * 4);
 	take((void **)&tw.evt, NA * 8);
@@ -1901,12 +2031,13 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 		tree_tour_words(cs, V, E, tw, force_sparse_splitters, s);
 	tw.tour_words_done = false;
 	LAUNCH(k_tour_ends, C, s, C, cs.voff, start_key, cs.loff, cs.ladj, cs.lle, rb.pk, rb.heads);
+	// the tour's ranks stay records (tw.dist), R in the pools (free until the class walks)
+	L0Ranks tour_r{};
 	if (n_slots)
-		list_rank_splitters<false>((uint32_t)n_slots, bitsA, tw.dist, nullptr, C, rb, s);
-	const uint32_t *dist = tw.dist;
+		tour_r = list_rank_splitters<false>((uint32_t)n_slots, bitsA, tw.dist, nullptr, C, rb, s);
 	const uint32_t XW = NA / 64 + 1; // words of the position bitmap
 	HIP_CHECK(hipMemsetAsync(tw.xrec, 0, ((size_t)XW + 2) * 16, s));
-	LAUNCH(k_t0_parents, std::max(V, C), s, V, dist, cs.ckey, cs.voff, cs.loff, cs.ladj, cs.lle, ft, rb.heads,
+	LAUNCH(k_t0_parents, std::max(V, C), s, V, tw.dist, tour_r, cs.ckey, cs.voff, cs.loff, cs.ladj, cs.lle, ft, rb.heads,
 	       tw.t0seg, tw.xrec, C, start_key, pw.err + 2, tw.dvis_slots);
 	tm.end(40);
 
@@ -1921,7 +2052,7 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 	scan_exclusive_xor_u128(tw.xval, tw.xps, (size_t)V + 1, pw.scan_tmp, pw.scan_tmp_bytes, s, tw.xrank + XW);
 	uint8_t *multi = tw.dvis_slots; // (see tree_spans: sized for max(2E, 2V) + 16; cleared by k_t0_parents)
 	uint32_t *cstate = sw.cur; // [nS+1]
-	LAUNCH(k_bridges, V, s, V, tw.t0seg, tw.xps, tw.xrec, hside, ft, dist, cs.loff, cs.lle, cs.ckey, tw.cproc, cs.voff, multi, cstate, tw.dps);
+	LAUNCH(k_bridges, V, s, V, tw.t0seg, tw.xps, tw.xrec, hside, ft, tw.dist, tour_r, cs.loff, cs.lle, cs.ckey, tw.cproc, cs.voff, multi, cstate, tw.dps);
 	tm.end(8 + 44);
 
 	// ---- 5-6. entries and the per-class DFS
@@ -2015,13 +2146,13 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 	(void)max_side_links;
 	if (!events_done)
 		enqueue_events();
-	list_rank_splitters<true, true>(n_events, bitsE, nullptr, tw.evt, C, rb, s);
+	const L0Ranks evr = list_rank_splitters<true, true>(n_events, bitsE, tw.evt, pw.err + 13, C, rb, s); // records, see k_tree_emit
 	(void)event_lists;
 	tm.end(40);
 
 	// ---- 8. tree arrays in pre-order and the from_bd back edges
 	tm.begin("tree_emit");
-	LAUNCH(k_tree_emit, std::max(V, C), s, nS, tw.evt, merged, tw.dps, cs.ckey, tw.cproc, cs.voff, start_key, cs.gid_s, sw.t_gid, sw.t_flags,
+	LAUNCH(k_tree_emit, std::max(V, C), s, nS, tw.evt, evr, merged, tw.dps, cs.ckey, tw.cproc, cs.voff, start_key, cs.gid_s, sw.t_gid, sw.t_flags,
 	       sw.t_par, sw.t_size, (sw.hairpins || sw.want_depth) ? sw.t_depth : nullptr, tw.side_tidx, C, sw.c_ntree, pw.lsz, pw.hi0, pw.mpre, pw.dlt,
 	       pw.sdl, pw.incnt); // (incnt: k_back_edges counts the brackets that end at a vertex into it)
 	pw.sdl_filled = true;

@@ -11,7 +11,7 @@ namespace povu_hip
 struct TreeWs {
 	HostScratch *host; // pinned read-back scratch of the owning context
 	// unrooted spanning forest of the biedged graph H, as arcs
-	uint32_t *dist;					  // [2E] arcs behind an adjacency slot in its Euler tour (slots of hooked links = arcs, see tree_kernels.hip)
+	uint2 *dist;					  // [2E] record {owner, partial} of an adjacency slot in the Euler-tour ranking (slots of hooked links = arcs; its rank, the arcs behind it: rank_l0, see tree_kernels.hip)
 	ulonglong2 *xval, *xps;				  // [max(V, E) + 16] xor values (two 64-bit hashes) of the segments that have any, in tour order, and their running xor (inside the shared block, see tree_spans)
 	uint4 *xrec;					  // [(4V+8)/64 + 4] per 64 tour positions {which of them carry a value (64 bits), set bits in front of the word, -}
 	uint32_t *xrank;				  // [(4V+8)/64 + 4] scan buffer of the bit counts (the last entry: their total)
@@ -29,7 +29,7 @@ struct TreeWs {
 	uint32_t *be_cnt;				  // [2V+1] first arc of a side (tour); free afterwards
 	uint32_t *rk_pk, *rk_heads;			  // list ranking: packed list words [4V+8], list heads [C]
 	uint32_t *rk_nx, *rk_wa, *rk_wb, *rk_tA, *rk_tB, *rk_tC; // pools of the levels above the list itself
-	uint2 *evt;					  // [4V+2] event ranks {enter count, depth} of the pre-order ranking
+	uint2 *evt;					  // [4V+2] event records {owner, partial} of the pre-order ranking (ranks {enter count, depth}: rank_l0_pair)
 	uint32_t *cproc;				  // [C+1] 1 = component is decomposed by this shard
 	const uint8_t *last_dupflag;			  // dvis_slots when the last pass filled it, else null
 	bool tour_words_done = false;			  // tree_tour_words ran for this pass already (started ahead of the host's wait for the component sizes)
@@ -57,6 +57,12 @@ void tree_tour_words(const CompState &cs, uint32_t V, uint32_t E, TreeWs &tw, bo
 int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw, uint32_t C, uint32_t event_lists,
 			   uint32_t max_side_links, bool force_big_class_dfs, bool force_sparse_splitters, StageTimer &tm,
 			   hipStream_t s);
+
+// unit-test hook: the level-0 ranks of list_rank_splitters for the lists next[] (NIL = end) with heads[nh], as the readers
+// resolve them -- mode 0: ra = suffix sums of the 0/1 weights w; mode 1 (the pre-order events): ra, rb = the two sums of the
+// EVT3 weights.  bits = bucket bits (0: the default).  Elements that are in no list get no defined value.
+void debug_list_rank(uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads, uint32_t nh, int mode,
+		     unsigned bits, uint32_t *ra, uint32_t *rb, hipStream_t s);
 
 // conformance export: back edges from_bd creates just before each tree vertex (w, T-space) and after the last child of
 // each (tail, T-space); both arrays must be zeroed by the caller.  Reads the state of the last run_parallel_tree.

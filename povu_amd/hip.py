@@ -164,6 +164,9 @@ def load_lib():
     l.povu_hip_debug_scan.restype = C.c_int
     l.povu_hip_debug_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                       C.c_size_t]
+    l.povu_hip_debug_list_rank.restype = C.c_int
+    l.povu_hip_debug_list_rank.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                           C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
     l.povu_hip_workspace_estimate.restype = C.c_uint64
     l.povu_hip_workspace_estimate.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     l.povu_hip_prewarm.restype = C.c_int
@@ -704,6 +707,23 @@ class HipDecomposer:
         if rc:
             raise RuntimeError(f"debug_scan failed ({rc})")
         return out, out2
+
+    def debug_list_rank(self, nxt, w, heads, events: bool = False, bits: int = 0):
+        """Unit-test hook: the tree stage's list ranking of the lists `nxt` (NIL ends a list) headed by `heads`,
+        ranks as its readers resolve them.  Suffix sums (inclusive, mod 2^32) of the 0/1 weights `w`; with
+        `events`, the pair of sums of the pre-order events' weights (x % 3 == 0 enters).  `bits`: splitter
+        bucket bits (0 = the default).  Elements in no list get no defined value."""
+        nxt = np.ascontiguousarray(nxt, dtype=np.uint32)
+        w = np.ascontiguousarray(w, dtype=np.uint8)
+        heads = np.ascontiguousarray(heads, dtype=np.uint32)
+        ra = np.zeros(nxt.size, dtype=np.uint32)
+        rb = np.zeros(nxt.size, dtype=np.uint32)
+        rc = self._lib.povu_hip_debug_list_rank(self._ctx, nxt.size, nxt.ctypes.data, w.ctypes.data,
+                                                heads.ctypes.data if heads.size else None, heads.size,
+                                                1 if events else 0, bits, ra.ctypes.data, rb.ctypes.data)
+        if rc:
+            raise RuntimeError(f"debug_list_rank failed ({rc})")
+        return (ra, rb) if events else ra
 
     def debug_components(self, n_vtx: int):
         comp = np.zeros(n_vtx, dtype=np.uint32)
