@@ -88,6 +88,24 @@ size_t povu_flubbles_count(const PovuFlubbles *flubbles);
  * order; a transient failure, such as device memory, is tried again by the next call). */
 PovuFlubble *povu_flubbles_get(const PovuFlubbles *flubbles, size_t index);
 void povu_flubble_free(PovuFlubble *flubble);
+/* Traversals of flubble `index` by the graph's own paths (INTEGRATION.md "Flubble traversals", decided here): for every
+ * traversal the path index (GFA order), its first and last step within the path, whether it reads the flubble from end to
+ * start, and its allele; the alleles as PovuStep arrays from the start boundary to the end boundary, numbered in the order of
+ * their first traversal; the POVU_HIP_TRAV_* status bits (include/povu_hip.h).  max_steps is 65 536.  Computed for the whole
+ * forest on the GPU at the first call.  A builder graph has no paths (povu_graph_add_path adds none): its flubbles have no
+ * traversals.  NULL for index 0 and index >= povu_flubbles_count, and when the traversals cannot be computed (a path step
+ * names a segment the graph does not have; a transient failure is tried again by the next call).  Free with
+ * povu_flubble_traversals_free. */
+typedef struct {
+	size_t path; size_t first; size_t last; int reverse; size_t allele;
+} PovuTraversal;
+typedef struct {
+	PovuTraversal *traversals; size_t traversals_count;
+	PovuStep **alleles; size_t *allele_lengths; size_t alleles_count;
+	uint32_t status;
+} PovuFlubbleTraversals;
+PovuFlubbleTraversals *povu_flubbles_get_traversals(const PovuFlubbles *flubbles, size_t index);
+void povu_flubble_traversals_free(PovuFlubbleTraversals *t);
 
 /* PVST view [ffi.h:358-364]; non-owning view into its PovuFlubbles */
 PovuPvstTree *povu_flubbles_get_pvst_tree(const PovuFlubbles *flubbles);

@@ -48,8 +48,8 @@ int povu_hip_device_count(void);
 /* create / destroy a context on `device` */
 povu_hip_ctx *povu_hip_create(int device, char *err, size_t errlen);
 void povu_hip_destroy(povu_hip_ctx *ctx);
-/* gives the decompose workspaces of `ctx` back to the device, keeping the resident graph (a context kept only for
- * povu_hip_forest_walks on a forest it made); the next povu_hip_decompose reserves them again.  Ends the debug exports of
+/* gives the decompose and traversal workspaces of `ctx` back to the device, keeping the resident graph and paths (a context
+ * kept only for povu_hip_forest_walks / _traversals on a forest it made); the next call reserves them again.  Ends the debug exports of
  * the last pass.  0 on success */
 int povu_hip_release_workspace(povu_hip_ctx *ctx);
 
@@ -357,6 +357,52 @@ typedef struct {
 povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_forest *f, const povu_hip_walk_opts *opts, char *err,
 				      size_t errlen);
 void povu_hip_walks_free(povu_hip_walks *w);
+
+/* ---- traversals of every flubble by the paths of the graph ("Flubble traversals": decided here, not
+ * reference behaviour) ----
+ * Makes `n_paths` paths resident beside the graph now uploaded: the steps of path k are [step_off[k], step_off[k + 1]),
+ * step_id the segment id, step_rev 0 for '>' (GFA '+'), 1 for '<'.  The paths belong to this upload: the next
+ * povu_hip_graph_upload drops them.  Refused when no graph is resident, when its segment ids do not ascend with the vertex
+ * index, when a step names an id the graph does not have (the message names the path and the step), when a path has 2^32
+ * steps or more, or when device memory runs out.  0 on success */
+int povu_hip_paths_upload(povu_hip_ctx *ctx, uint32_t n_paths, const uint64_t *step_off, const uint32_t *step_id,
+			  const uint8_t *step_rev, char *err, size_t errlen);
+/* The queries are those of povu_hip_forest_walks.  Every occurrence of S in a path starts a forward scan and every occurrence
+ * of flip(Z) a reverse scan; a scan ends at the next step on either boundary segment and is a traversal when that step is Z
+ * (flip(S)) within max_steps steps.  The alleles of a query are the distinct S -> Z step sequences of its traversals,
+ * numbered in the order of their first traversal; traversals come in (path, first step) order. */
+typedef struct {
+	uint32_t max_steps; /* 0 = 65 536; else at least 2 */
+	uint32_t flags;	    /* POVU_HIP_T_* */
+} povu_hip_trav_opts;
+#define POVU_HIP_T_FORCE_TIER2 1u /* run every scan with the wave-per-scan kernel (tests) */
+#define POVU_HIP_TRAV_LONG 1u	  /* status bits per query: a scan would need more than max_steps steps */
+#define POVU_HIP_TRAV_STRAY 2u	  /* a scan met a boundary step that does not close it */
+#define POVU_HIP_TRAV_OPEN 4u	  /* a scan reached the end of its path */
+typedef struct {
+	uint64_t n_queries, n_traversals, n_alleles, n_steps;
+	const uint64_t *trav_off;   /* [n_queries + 1] traversals of query q: [trav_off[q], trav_off[q + 1]) */
+	const uint64_t *allele_off; /* [n_queries + 1] alleles of query q: [allele_off[q], allele_off[q + 1]) */
+	const uint8_t *status;	    /* [n_queries] POVU_HIP_TRAV_* bits */
+	const uint32_t *path;	    /* [n_traversals] path index (upload order) */
+	const uint32_t *first;	    /* [n_traversals] step of the path where the traversal begins (S, or flip(Z) when reverse) */
+	const uint32_t *last;	    /* [n_traversals] step of the path where it ends */
+	const uint32_t *allele;	    /* [n_traversals] allele number within its query */
+	const uint8_t *reverse;	    /* [n_traversals] 1: the path reads the flubble from Z to S */
+	const uint64_t *step_off;   /* [n_alleles + 1] steps of allele a: [step_off[a], step_off[a + 1]) */
+	const uint32_t *step_id;    /* [n_steps] segment id, S -> Z */
+	const uint8_t *step_or;	    /* [n_steps] 0 '>', 1 '<' */
+	uint64_t n_tier2;	    /* scans the wave-per-scan kernel ran */
+	uint64_t n_hash_splits;	    /* alleles split off a group of equal (length, hash) by the exact comparison */
+	double device_ms;	    /* HIP-event time of the call, first upload to last byte on the host */
+} povu_hip_traversals;
+/* Traversals of every query of `f` by the paths resident in `ctx` (opts NULL = defaults).  Refused like
+ * povu_hip_forest_walks (forest not made from this context's current upload; sharded, merged or attached forest; ids not
+ * ascending), when no paths are resident, and when the scan tasks, traversals or allele steps reach 2^32 (the scans are
+ * 32-bit) or do not fit device memory.  Free with povu_hip_traversals_free. */
+povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, povu_hip_forest *f, const povu_hip_trav_opts *opts, char *err,
+						size_t errlen);
+void povu_hip_traversals_free(povu_hip_traversals *t);
 
 /*
  * Serialises tree `i` exactly as mto::to_pvst::write_pvst does

@@ -327,6 +327,17 @@ struct povu_hip_ctx {
 		}
 	}
 	Arena wk_ws, wk_out; // povu_hip_forest_walks: queries, counts and tier-2 stacks / the walks themselves (walk_kernels.hip)
+	// povu_hip_paths_upload: the paths of the resident graph, one word a step (vertex index << 1 | '<'), and their u64 step
+	// offsets; they belong to upload `paths_gen` (a later graph upload leaves them stale: refused)
+	Arena paths_buf;
+	uint32_t *path_steps = nullptr;
+	uint64_t *path_off = nullptr;
+	uint32_t n_paths = 0;
+	uint64_t n_path_steps = 0, paths_gen = 0;
+	bool paths_valid = false;
+	// povu_hip_forest_traversals (trav_kernels.hip): queries and the boundary table / scan tasks / traversals and dedup /
+	// allele steps
+	Arena tr_ws, tr_task, tr_trav, tr_steps;
 	Arena part_arena;  // the packed shards of the last povu_hip_shard_partition (kept warm: a step of a sharded job re-partitions)
 	// bytes this context moved over PCIe / to peers since it was created (povu_hip_transfer_bytes)
 	uint64_t xfer_h2d = 0, xfer_d2h = 0, xfer_peer_out = 0, xfer_peer_in = 0;

@@ -186,6 +186,10 @@ extern "C" int povu_hip_release_workspace(povu_hip_ctx *ctx)
 	ctx->ws_walk.release();
 	ctx->ws_sub.release();
 	ctx->upload_tmp.release();
+	ctx->tr_ws.release();
+	ctx->tr_task.release();
+	ctx->tr_trav.release();
+	ctx->tr_steps.release();
 	return 0;
 }
 

@@ -20,7 +20,7 @@
 //           hash set of the segments on the path (the on-path test in O(1) at any depth).
 // Both passes run the same function (dfs below), so the emit pass writes exactly what the count pass sized; it still
 // checks every write against the query's own range.
-#include "context.hpp"
+#include "query_common.hpp"
 
 namespace povu_hip
 {
@@ -30,7 +30,6 @@ static constexpr uint32_t T1_DEPTH = 16;	 // frames of a tier-1 stack (LDS: 16 x
 static constexpr uint32_t T1_EXPANSIONS = 4096; // expansions tier 1 spends before it hands a query over
 static constexpr uint32_t SORT_IN_LANE = 64;	 // sides up to this many slots are sorted by one lane
 static constexpr uint8_t ST_MORE = POVU_HIP_WALK_MORE, ST_LONG = POVU_HIP_WALK_LONG, ST_BUDGET = POVU_HIP_WALK_BUDGET;
-static constexpr uint32_t NO_QUERY = 0xFFFFFFFFu;
 
 static inline unsigned wblk(size_t n) { return (unsigned)((n + W_TPB - 1) / W_TPB); }
 
@@ -84,19 +83,6 @@ __global__ void k_wk_vid_ascending(uint32_t V, const uint32_t *__restrict__ vid,
 		atomicOr(bad, 1u);
 }
 
-__device__ __forceinline__ uint32_t find_vertex(const uint32_t *__restrict__ vid, uint32_t V, uint32_t id)
-{
-	uint32_t lo = 0, hi = V;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (vid[mid] < id)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return (lo < V && vid[lo] == id) ? lo : NO_QUERY;
-}
-
 // (id, orientation) of both boundaries -> entered sides; a query whose two boundaries are one segment has no walk (NO_QUERY)
 __global__ void k_wk_resolve(uint32_t n, const uint32_t *__restrict__ qa, const uint32_t *__restrict__ qz,
 			       const uint8_t *__restrict__ qor, const uint32_t *__restrict__ vid, uint32_t V, uint32_t *__restrict__ ys,
@@ -114,6 +100,55 @@ __global__ void k_wk_resolve(uint32_t n, const uint32_t *__restrict__ qa, const 
 	const uint8_t o = qor[q];
 	ys[q] = a == z ? NO_QUERY : 2 * a + (o & 1u);
 	yz[q] = a == z ? NO_QUERY : 2 * z + ((o >> 1) & 1u);
+}
+
+void launch_vid_ascending(uint32_t V, const uint32_t *vid, uint32_t *bad, hipStream_t s)
+{
+	KLAUNCH(k_wk_vid_ascending, dim3(wblk(V)), dim3(W_TPB), 0, s, V, vid, bad);
+}
+
+void launch_resolve(uint32_t n, const uint32_t *qa, const uint32_t *qz, const uint8_t *qor, const uint32_t *vid, uint32_t V,
+		    uint32_t *ys, uint32_t *yz, uint32_t *bad, hipStream_t s)
+{
+	if (n)
+		KLAUNCH(k_wk_resolve, dim3(wblk(n)), dim3(W_TPB), 0, s, n, qa, qz, qor, vid, V, ys, yz, bad);
+}
+
+void check_query_forest(const povu_hip_ctx *ctx, const povu_hip_forest *f, const char *what)
+{
+	if (!ctx || !f)
+		throw HipError("null context or forest");
+	if (!f->walk_ctx)
+		throw HipError(std::string(what) +
+			       " need a forest made by povu_hip_decompose of a whole resident graph (not a sharded, merged or attached forest)");
+	if (f->walk_ctx != ctx || !ctx->g.block || f->walk_gen != ctx->g.gen)
+		throw HipError("the forest was not decomposed from the graph now resident on this context (it was uploaded again, or the forest belongs to another context)");
+}
+
+void forest_queries(povu_hip_forest *f, std::vector<uint32_t> &qa, std::vector<uint32_t> &qz, std::vector<uint8_t> &qor)
+{
+	const uint32_t n_trees = (uint32_t)f->trees.size();
+	for (uint32_t i = 0; i < n_trees; i++) {
+		povu_hip_subtree st;
+		if (povu_hip_forest_get_subtree(f, i, &st) == 0) {
+			for (uint32_t v = 1; v < st.n_total; v++) {
+				qa.push_back(st.id1[v]);
+				qz.push_back(st.id2[v]);
+				qor.push_back((uint8_t)((st.or1[v] & 1u) | ((st.or2[v] & 1u) << 1)));
+			}
+			continue;
+		}
+		povu_hip_tree t;
+		if (povu_hip_forest_get(f, i, &t) != 0)
+			throw HipError("forest tree " + std::to_string(i) + " unreadable");
+		for (uint32_t v = 1; v < t.n_pvst; v++) {
+			qa.push_back(t.a_id[v]);
+			qz.push_back(t.z_id[v]);
+			qor.push_back((uint8_t)((t.a_or[v] & 1u) | ((t.z_or[v] & 1u) << 1)));
+		}
+	}
+	if (qa.size() >= 0xFFFFFFFFull)
+		throw HipError("too many queries for 32-bit indices");
 }
 
 // ---- the DFS (both tiers, both passes)
@@ -434,12 +469,7 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 		e0 = e1 = nullptr;
 	};
 	try {
-		if (!ctx || !f)
-			throw HipError("null context or forest");
-		if (!f->walk_ctx)
-			throw HipError("walks need a forest made by povu_hip_decompose of a whole resident graph (not a sharded, merged or attached forest)");
-		if (f->walk_ctx != ctx || !ctx->g.block || f->walk_gen != ctx->g.gen)
-			throw HipError("the forest was not decomposed from the graph now resident on this context (it was uploaded again, or the forest belongs to another context)");
+		check_query_forest(ctx, f, "walks");
 		WalkCaps c{64, 1000, 65536};
 		uint32_t flags = 0;
 		if (opts) {
@@ -460,30 +490,9 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 		hipStream_t s = ctx->stream;
 
 		// ---- the queries, in tree order then PVST vertex order, roots skipped
-		const uint32_t n_trees = (uint32_t)f->trees.size();
 		std::vector<uint32_t> qa, qz;
 		std::vector<uint8_t> qor;
-		for (uint32_t i = 0; i < n_trees; i++) {
-			povu_hip_subtree st;
-			if (povu_hip_forest_get_subtree(f, i, &st) == 0) {
-				for (uint32_t v = 1; v < st.n_total; v++) {
-					qa.push_back(st.id1[v]);
-					qz.push_back(st.id2[v]);
-					qor.push_back((uint8_t)((st.or1[v] & 1u) | ((st.or2[v] & 1u) << 1)));
-				}
-				continue;
-			}
-			povu_hip_tree t;
-			if (povu_hip_forest_get(f, i, &t) != 0)
-				throw HipError("forest tree " + std::to_string(i) + " unreadable");
-			for (uint32_t v = 1; v < t.n_pvst; v++) {
-				qa.push_back(t.a_id[v]);
-				qz.push_back(t.z_id[v]);
-				qor.push_back((uint8_t)((t.a_or[v] & 1u) | ((t.z_or[v] & 1u) << 1)));
-			}
-		}
-		if (qa.size() >= 0xFFFFFFFFull)
-			throw HipError("too many queries for 32-bit indices");
+		forest_queries(f, qa, qz, qor);
 		const uint32_t n = (uint32_t)qa.size();
 		const uint32_t nS = 2 * g.V;
 		const size_t slots = g.n_slots;
@@ -517,9 +526,8 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 		}
 		// words: [0] vid not ascending | query boundary not found, [1] hand-over count, [2] / [3] tier-2 work counter of the
 		// count / emit pass, [4] a side has more than SORT_IN_LANE slots
-		KLAUNCH(k_wk_vid_ascending, dim3(wblk(g.V)), dim3(W_TPB), 0, s, g.V, g.vid, words);
-		if (n)
-			KLAUNCH(k_wk_resolve, dim3(wblk(n)), dim3(W_TPB), 0, s, n, d_qa, d_qz, d_qor, g.vid, g.V, ys, yz, words);
+		launch_vid_ascending(g.V, g.vid, words, s);
+		launch_resolve(n, d_qa, d_qz, d_qor, g.vid, g.V, ys, yz, words, s);
 		if (nS)
 			KLAUNCH(k_wk_ssucc, dim3(wblk(nS)), dim3(W_TPB), 0, s, nS, g.off, g.aoth, ssucc, words + 4);
 		uint32_t hw[8] = {0};

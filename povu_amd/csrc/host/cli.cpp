@@ -41,6 +41,8 @@ static void usage(std::ostream &os)
 	      "                                          (tiny, parallel, concealed, midi and smothered: T O C M S lines)\n"
 	      "        --leaf-subflubbles                Relabel leaf flubbles as tiny (T) / parallel (O): the find_tiny and\n"
 	      "                                          find_parallel passes of -s, without its three inserting passes\n"
+	      "        --traversals                      Also write <component id>.trav: the traversals of every flubble by the\n"
+	      "                                          GFA's P / W paths and their alleles (one GPU only)\n"
 	      "        --gpus=[n]                        Shard the components over n GPUs of this node, one worker per GPU\n"
 	      "                                          [default: 1; devices 0..n-1 or $POVU_HIP_DEVICES]\n"
 	      "        --structure-export=[structure_json]\n"
@@ -100,6 +102,8 @@ int main(int argc, char **argv)
 			cfg.subflubbles = true;
 		} else if ((command == "decompose" || command == "gfa2vcf") && !strcmp(a, "--leaf-subflubbles")) {
 			cfg.leaf_subflubbles = true;
+		} else if (command == "decompose" && !strcmp(a, "--traversals")) {
+			cfg.traversals = true;
 		} else if (command == "decompose" && value(i, a, "--gpus", "--gpus", v)) {
 			cfg.gpus = atoi(v.c_str());
 			if (cfg.gpus < 1 || cfg.gpus > 64) {
@@ -128,6 +132,10 @@ int main(int argc, char **argv)
 				return 1;
 			}
 		}
+	}
+	if (cfg.traversals && cfg.gpus > 1) { // (the traversals need a forest of the whole resident graph: sharded ones are refused)
+		std::cerr << "Flag '--traversals' cannot be combined with '--gpus' above 1" << std::endl;
+		return 1;
 	}
 	if (version) {
 		std::cout << VERSION << std::endl;

@@ -263,6 +263,67 @@ std::vector<int> multi_devices(int gpus, const char *env, int visible)
 	return d;
 }
 
+// one <output_dir>/<component id>.trav per tree of `f` (INTEGRATION.md "Flubble traversals"): for every PVST vertex in order,
+// its alleles ("A <vertex> <label> <allele> <steps>"), then its traversals ("T <vertex> <label> <allele> <path name> <first>
+// <last> <+|->"); the paths go to the context first
+void write_traversals(povu_hip_ctx *ctx, povu_hip_forest *f, const std::vector<GfaPath> &paths, const Config &cfg, std::atomic<bool> &failed)
+{
+	char err[512] = {0};
+	std::vector<uint64_t> off(1, 0);
+	std::vector<uint32_t> ids;
+	std::vector<uint8_t> rev;
+	for (const auto &p : paths) {
+		ids.insert(ids.end(), p.step_ids.begin(), p.step_ids.end());
+		rev.insert(rev.end(), p.step_rev.begin(), p.step_rev.end());
+		off.push_back(ids.size());
+	}
+	if (paths.size() >= 0xFFFFFFFFull)
+		throw std::runtime_error("too many paths for the traversals");
+	if (povu_hip_paths_upload(ctx, (uint32_t)paths.size(), off.data(), ids.data(), rev.data(), err, sizeof err) != 0)
+		throw std::runtime_error(std::string("povu_hip: ") + err);
+	povu_hip_traversals *tr = povu_hip_forest_traversals(ctx, f, nullptr, err, sizeof err);
+	if (!tr)
+		throw std::runtime_error(std::string("povu_hip: ") + err);
+	const uint32_t n = povu_hip_forest_tree_count(f);
+	size_t q = 0;
+	std::string out;
+	for (uint32_t i = 0; i < n && !failed; i++) {
+		povu_hip_tree t;
+		povu_hip_forest_get(f, i, &t);
+		povu_hip_subtree st;
+		const bool sub = povu_hip_forest_get_subtree(f, i, &st) == 0;
+		const uint32_t nv = sub ? st.n_total : t.n_pvst;
+		out.clear();
+		for (uint32_t v = 1; v < nv; v++, q++) {
+			const uint32_t a = sub ? st.id1[v] : t.a_id[v], z = sub ? st.id2[v] : t.z_id[v];
+			const uint8_t ao = sub ? st.or1[v] : t.a_or[v], zo = sub ? st.or2[v] : t.z_or[v];
+			const std::string head = std::to_string(v) + "\t" + (ao ? "<" : ">") + std::to_string(a) + (zo ? "<" : ">") + std::to_string(z) + "\t";
+			for (uint64_t k = tr->allele_off[q]; k < tr->allele_off[q + 1]; k++) {
+				out += "A\t" + head + std::to_string(k - tr->allele_off[q]) + "\t";
+				for (uint64_t j = tr->step_off[k]; j < tr->step_off[k + 1]; j++)
+					out += (tr->step_or[j] ? "<" : ">") + std::to_string(tr->step_id[j]);
+				out += "\n";
+			}
+			for (uint64_t k = tr->trav_off[q]; k < tr->trav_off[q + 1]; k++)
+				out += "T\t" + head + std::to_string(tr->allele[k]) + "\t" + paths[tr->path[k]].name + "\t" + std::to_string(tr->first[k]) +
+				       "\t" + std::to_string(tr->last[k]) + "\t" + (tr->reverse[k] ? "-" : "+") + "\n";
+		}
+		const std::string fn = cfg.output_dir + "/" + std::to_string(t.component_id) + ".trav";
+		FILE *o = fopen(fn.c_str(), "wb");
+		if (!o) {
+			std::cerr << "ERR Could not open file " << fn << std::endl;
+			failed = true;
+			break;
+		}
+		const bool short_write = fwrite(out.data(), 1, out.size(), o) != out.size();
+		if ((fclose(o) != 0) | short_write) {
+			std::cerr << "ERR Could not write file " << fn << std::endl;
+			failed = true;
+		}
+	}
+	povu_hip_traversals_free(tr);
+}
+
 void do_decompose(const Config &cfg)
 {
 	const int ll = cfg.verbosity;
@@ -306,7 +367,7 @@ void do_decompose(const Config &cfg)
 	GfaGraph g;
 	bool counted = false;
 	try {
-		g = load_gfa(cfg.input_gfa, false, false, cfg.threads, [&](size_t v, size_t e) {
+		g = load_gfa(cfg.input_gfa, false, cfg.traversals, cfg.threads, [&](size_t v, size_t e) {
 			counted = true;
 			counts_p.set_value({v, e});
 		}, &releaser.scratch);
@@ -362,6 +423,15 @@ void do_decompose(const Config &cfg)
 	// one <id>.pvst per component; formatting + writing spread over -t threads
 	std::atomic<bool> failed{false};
 	write_forest(f, cfg, (unsigned)std::max(1, cfg.threads), failed);
+	if (cfg.traversals && !failed) {
+		try {
+			write_traversals(ctx, f, g.paths, cfg, failed);
+		} catch (...) {
+			povu_hip_forest_free(f);
+			povu_hip_destroy(ctx);
+			throw;
+		}
+	}
 	const double t4 = now_ms();
 
 	// per-stage cost lines, same shape as povu::stage_cost::write_report (stage_cost.cpp:59-78)

@@ -21,6 +21,7 @@ struct Config {
 	bool subflubbles = false;
 	bool leaf_subflubbles = false; // --leaf-subflubbles: find_tiny + find_parallel only (the two passes of -s that relabel leaf flubbles)
 	int device = 0;
+	bool traversals = false; // --traversals: also <output_dir>/<component id>.trav, the traversals of every flubble by the GFA's paths
 	int gpus = 1; // --gpus N (additive): components sharded over N GPUs of this node, one worker thread per GPU
 	// --structure-export <path>: also write <path>.flubble-debug.jsonl (one frame per decomposed component)
 	std::string structure_export;

@@ -41,8 +41,14 @@ struct PovuFlubbles {
 	std::mutex walks_m;
 	povu_hip_walks *walks = nullptr;
 	std::string walks_err;
+	// povu_flubbles_get_traversals: the graph's paths made resident on ctx and the traversals of the whole forest, computed
+	// by the first call that succeeds (under their own mutex, like the walks)
+	std::mutex trav_m;
+	povu_hip_traversals *trav = nullptr;
+	std::string trav_err;
 	~PovuFlubbles()
 	{
+		povu_hip_traversals_free(trav);
 		povu_hip_walks_free(walks);
 		povu_hip_forest_free(forest.f);
 		forest.f = nullptr;
@@ -417,6 +423,85 @@ void povu_flubble_free(PovuFlubble *fl) // :413-424
 	}
 	delete[] fl->walk_lengths;
 	delete fl;
+}
+
+// The graph's paths go to the context once (0 paths for a builder graph), then povu_hip_forest_traversals with the default
+// max_steps; flubble i is query i - 1, as for the walks.
+PovuFlubbleTraversals *povu_flubbles_get_traversals(const PovuFlubbles *cf, size_t index)
+{
+	if (!cf || index == 0 || index >= cf->pvst_vertices || !cf->ctx || !cf->graph)
+		return nullptr;
+	auto *f = const_cast<PovuFlubbles *>(cf);
+	try {
+		const povu_hip_traversals *tr = nullptr;
+		{
+			std::lock_guard<std::mutex> lk(f->trav_m);
+			if (!f->trav) {
+				char err[512] = {0};
+				const auto &paths = f->graph->paths;
+				std::vector<uint64_t> off(1, 0);
+				std::vector<uint32_t> ids;
+				std::vector<uint8_t> rev;
+				bool fits = paths.size() < 0xFFFFFFFFull;
+				for (const auto &p : paths) {
+					for (uint64_t id : p.step_ids) {
+						fits &= id <= 0xFFFFFFFEull;
+						ids.push_back((uint32_t)id);
+					}
+					rev.insert(rev.end(), p.step_rev.begin(), p.step_rev.end());
+					off.push_back(ids.size());
+				}
+				if (!fits)
+					return nullptr;
+				if (povu_hip_paths_upload(f->ctx, (uint32_t)paths.size(), off.data(), ids.data(), rev.data(), err, sizeof err) == 0)
+					f->trav = povu_hip_forest_traversals(f->ctx, f->forest.f, nullptr, err, sizeof err);
+				f->trav_err = f->trav ? std::string() : std::string(err);
+			}
+			tr = f->trav;
+		}
+		if (!tr)
+			return nullptr;
+		const size_t q = index - 1;
+		auto *out = new PovuFlubbleTraversals();
+		try {
+			const uint64_t t0 = tr->trav_off[q], t1 = tr->trav_off[q + 1], a0 = tr->allele_off[q], a1 = tr->allele_off[q + 1];
+			out->status = tr->status[q];
+			out->traversals_count = t1 - t0;
+			out->traversals = out->traversals_count ? new PovuTraversal[out->traversals_count] : nullptr;
+			for (uint64_t t = t0; t < t1; t++)
+				out->traversals[t - t0] = PovuTraversal{tr->path[t], tr->first[t], tr->last[t], tr->reverse[t] ? 1 : 0, tr->allele[t]};
+			out->alleles_count = a1 - a0;
+			out->alleles = out->alleles_count ? new PovuStep *[out->alleles_count]() : nullptr;
+			out->allele_lengths = out->alleles_count ? new size_t[out->alleles_count] : nullptr;
+			for (uint64_t a = a0; a < a1; a++) {
+				const uint64_t b = tr->step_off[a], e = tr->step_off[a + 1];
+				out->allele_lengths[a - a0] = e - b;
+				out->alleles[a - a0] = new PovuStep[e - b];
+				for (uint64_t j = b; j < e; j++)
+					out->alleles[a - a0][j - b] =
+						PovuStep{tr->step_id[j], tr->step_or[j] ? POVU_ORIENTATION_REVERSE : POVU_ORIENTATION_FORWARD};
+			}
+		} catch (...) {
+			povu_flubble_traversals_free(out);
+			return nullptr;
+		}
+		return out;
+	} catch (...) {
+		return nullptr;
+	}
+}
+void povu_flubble_traversals_free(PovuFlubbleTraversals *t)
+{
+	if (!t)
+		return;
+	if (t->alleles) {
+		for (size_t i = 0; i < t->alleles_count; i++)
+			delete[] t->alleles[i];
+		delete[] t->alleles;
+	}
+	delete[] t->allele_lengths;
+	delete[] t->traversals;
+	delete t;
 }
 
 PovuPvstTree *povu_flubbles_get_pvst_tree(const PovuFlubbles *f) { return f ? new PovuPvstTree{f} : nullptr; }

@@ -64,6 +64,19 @@ class _Walks(C.Structure):
                 ("device_ms", C.c_double)]
 
 
+class _TravOpts(C.Structure):
+    _fields_ = [("max_steps", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class _Traversals(C.Structure):
+    _fields_ = [("n_queries", C.c_uint64), ("n_traversals", C.c_uint64), ("n_alleles", C.c_uint64), ("n_steps", C.c_uint64),
+                ("trav_off", C.POINTER(C.c_uint64)), ("allele_off", C.POINTER(C.c_uint64)), ("status", C.POINTER(C.c_uint8)),
+                ("path", C.POINTER(C.c_uint32)), ("first", C.POINTER(C.c_uint32)), ("last", C.POINTER(C.c_uint32)),
+                ("allele", C.POINTER(C.c_uint32)), ("reverse", C.POINTER(C.c_uint8)), ("step_off", C.POINTER(C.c_uint64)),
+                ("step_id", C.POINTER(C.c_uint32)), ("step_or", C.POINTER(C.c_uint8)), ("n_tier2", C.c_uint64),
+                ("n_hash_splits", C.c_uint64), ("device_ms", C.c_double)]
+
+
 class _StageTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("launches", C.c_uint32)]
 
@@ -85,6 +98,8 @@ F_SUBFLUBBLES = 8192  # all five passes of -s (implies F_LEAF_SUBFLUBBLES): Fore
 
 W_FORCE_TIER2 = 1  # HipDecomposer.walks: every query through the second-tier kernel (tests)
 WALK_MORE, WALK_LONG, WALK_BUDGET = 1, 2, 4  # status bits of a query
+T_FORCE_TIER2 = 1  # HipDecomposer.traversals: every scan through the wave-per-scan kernel (tests)
+TRAV_LONG, TRAV_STRAY, TRAV_OPEN = 1, 2, 4  # status bits of a query
 
 _lib = None
 
@@ -133,6 +148,11 @@ def load_lib():
     l.povu_hip_forest_walks.restype = C.POINTER(_Walks)
     l.povu_hip_forest_walks.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_WalkOpts), C.c_char_p, C.c_size_t]
     l.povu_hip_walks_free.argtypes = [C.POINTER(_Walks)]
+    l.povu_hip_paths_upload.restype = C.c_int
+    l.povu_hip_paths_upload.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    l.povu_hip_forest_traversals.restype = C.POINTER(_Traversals)
+    l.povu_hip_forest_traversals.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_TravOpts), C.c_char_p, C.c_size_t]
+    l.povu_hip_traversals_free.argtypes = [C.POINTER(_Traversals)]
     l.povu_hip_forest_first.restype = C.c_uint64
     l.povu_hip_forest_first.argtypes = [C.c_void_p, C.c_uint32]
     l.povu_hip_forest_pvst_text.restype = C.c_void_p
@@ -482,6 +502,78 @@ class Walks:
         return self.walks_of_query(q), int(self.status[q])
 
 
+def _query_firsts(lib, forest: "Forest") -> List[int]:
+    """Query number of PVST vertex 1 of every tree (queries: tree order, then PVST vertex order, roots skipped)."""
+    first, q = [], 0
+    st = _SubTree()
+    t = _Tree()
+    for i in range(len(forest)):
+        first.append(q)
+        if lib.povu_hip_forest_get_subtree(forest._h, i, C.byref(st)) == 0:
+            q += st.n_total - 1
+        else:
+            lib.povu_hip_forest_get(forest._h, i, C.byref(t))
+            q += t.n_pvst - 1
+    return first
+
+
+class Traversals:
+    """Traversals of every query of a forest by the resident paths (HipDecomposer.traversals): numpy views of the flat
+    arrays of povu_hip_forest_traversals -- trav_off / allele_off [n_queries + 1], status [n_queries], path / first / last /
+    allele / reverse [n_traversals], step_off [n_alleles + 1], step_id / step_or [n_steps] -- valid as long as this object
+    lives.  Queries are numbered like those of Walks."""
+
+    def __init__(self, lib, ptr, forest: "Forest", first_query: List[int]):
+        self._lib, self._p = lib, ptr
+        t = ptr.contents
+        self.n_queries, self.n_traversals = int(t.n_queries), int(t.n_traversals)
+        self.n_alleles, self.n_steps = int(t.n_alleles), int(t.n_steps)
+        self.n_tier2, self.n_hash_splits, self.device_ms = int(t.n_tier2), int(t.n_hash_splits), float(t.device_ms)
+        view = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)) if n else np.zeros(0, dt)  # noqa: E731
+        self.trav_off = view(t.trav_off, self.n_queries + 1, np.uint64)
+        self.allele_off = view(t.allele_off, self.n_queries + 1, np.uint64)
+        self.status = view(t.status, self.n_queries, np.uint8)
+        self.path = view(t.path, self.n_traversals, np.uint32)
+        self.first = view(t.first, self.n_traversals, np.uint32)
+        self.last = view(t.last, self.n_traversals, np.uint32)
+        self.allele = view(t.allele, self.n_traversals, np.uint32)
+        self.reverse = view(t.reverse, self.n_traversals, np.uint8)
+        self.step_off = view(t.step_off, self.n_alleles + 1, np.uint64)
+        self.step_id = view(t.step_id, self.n_steps, np.uint32)
+        self.step_or = view(t.step_or, self.n_steps, np.uint8)
+        self._first = first_query
+        self._forest = forest
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            self._lib.povu_hip_traversals_free(self._p)
+            self._p = None
+
+    def query(self, tree_index: int, pvst_vertex: int) -> int:
+        """Query number of a PVST vertex (not the root)."""
+        n = (self._first[tree_index + 1] if tree_index + 1 < len(self._first) else self.n_queries) - self._first[tree_index]
+        if not 1 <= pvst_vertex <= n:
+            raise IndexError((tree_index, pvst_vertex))
+        return self._first[tree_index] + pvst_vertex - 1
+
+    def of_query(self, q: int):
+        alleles = []
+        for a in range(int(self.allele_off[q]), int(self.allele_off[q + 1])):
+            b, e = int(self.step_off[a]), int(self.step_off[a + 1])
+            alleles.append([(int(i), ">" if o == 0 else "<")
+                            for i, o in zip(self.step_id[b:e].tolist(), self.step_or[b:e].tolist())])
+        trav = []
+        for t in range(int(self.trav_off[q]), int(self.trav_off[q + 1])):
+            trav.append((int(self.path[t]), int(self.first[t]), int(self.last[t]), "-" if self.reverse[t] else "+",
+                         int(self.allele[t])))
+        return alleles, trav, int(self.status[q])
+
+    def of(self, tree_index: int, pvst_vertex: int):
+        """(alleles [[(segment id, '>' | '<'), ...], ...], traversals [(path, first, last, '+' | '-', allele), ...],
+        status bits) of PVST vertex `pvst_vertex` of tree `tree_index`."""
+        return self.of_query(self.query(tree_index, pvst_vertex))
+
+
 class Shards:
     """Device-resident partition of a resident graph into per-rank packed shards (povu_hip_shard_partition)."""
 
@@ -677,6 +769,36 @@ class HipDecomposer:
                 self._lib.povu_hip_forest_get(forest._h, i, C.byref(t))
                 q += t.n_pvst - 1
         return Walks(self._lib, p, forest, first)
+
+    def upload_paths(self, paths) -> None:
+        """Makes the paths of the graph now uploaded resident (povu_hip_paths_upload): a workloads.Paths record, or a
+        list of step lists [(segment id, 0 '>' | 1 '<'), ...].  The next upload drops them."""
+        if hasattr(paths, "off"):
+            off = np.ascontiguousarray(paths.off, dtype=np.uint64)
+            ids = np.ascontiguousarray(paths.ids, dtype=np.uint32)
+            rev = np.ascontiguousarray(paths.rev, dtype=np.uint8)
+        else:
+            lens = [len(p) for p in paths]
+            off = np.zeros(len(lens) + 1, np.uint64)
+            off[1:] = np.cumsum(lens, dtype=np.uint64)
+            flat = [s for p in paths for s in p]
+            ids = np.array([a for a, _ in flat], dtype=np.uint32)
+            rev = np.array([b for _, b in flat], dtype=np.uint8)
+        err = C.create_string_buffer(512)
+        if self._lib.povu_hip_paths_upload(self._ctx, len(off) - 1, off.ctypes.data, ids.ctypes.data if ids.size else None,
+                                           rev.ctypes.data if rev.size else None, err, 512) != 0:
+            raise RuntimeError(err.value.decode())
+
+    def traversals(self, forest: Forest, max_steps: int = 65536, flags: int = 0) -> Traversals:
+        """The traversals of every flubble of `forest` by the resident paths, on the GPU."""
+        if not 2 <= int(max_steps) < 2 ** 32:
+            raise ValueError("max_steps must be in [2, 2^32)")
+        o = _TravOpts(max_steps, flags)
+        err = C.create_string_buffer(512)
+        p = self._lib.povu_hip_forest_traversals(self._ctx, forest._h, C.byref(o), err, 512)
+        if not p:
+            raise RuntimeError(err.value.decode())
+        return Traversals(self._lib, p, forest, _query_firsts(self._lib, forest))
 
     def stage_times(self) -> List[dict]:
         buf = (_StageTime * 64)()

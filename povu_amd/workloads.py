@@ -450,3 +450,122 @@ def hanger_family(prefix: int, suffix: int, variant: int, direct_first: bool = T
         last = prefix + 4 + i
     arr = np.array(links, dtype=np.int64)
     return _mk(np.arange(1, n + 1, dtype=np.uint32), arr[:, 0], arr[:, 1], arr[:, 2], arr[:, 3])
+
+
+# ---- paths (haplotypes) over a graph: the input of HipDecomposer.traversals
+
+
+@dataclass
+class Paths:
+    names: list      # [n] path names (GFA P-line order)
+    off: np.ndarray  # uint64 [n + 1] steps of path k: [off[k], off[k + 1])
+    ids: np.ndarray  # uint32 [off[-1]] segment id of every step
+    rev: np.ndarray  # uint8  [off[-1]] 0 '>' (GFA '+'), 1 '<' (GFA '-')
+
+    def __len__(self) -> int:
+        return len(self.names)
+
+    @property
+    def n_steps(self) -> int:
+        return int(self.off[-1])
+
+    def steps(self, k: int):
+        """[(segment id, 0 | 1), ...] of path k."""
+        a, b = int(self.off[k]), int(self.off[k + 1])
+        return list(zip(self.ids[a:b].tolist(), self.rev[a:b].tolist()))
+
+    def to_gfa(self) -> str:
+        """P lines, one per path (append to Links.to_gfa() for one GFA)."""
+        out = []
+        for k, name in enumerate(self.names):
+            a, b = int(self.off[k]), int(self.off[k + 1])
+            ids, rev = self.ids[a:b].tolist(), self.rev[a:b].tolist()
+            out.append(f"P\t{name}\t" + ",".join(f"{i}{'-' if r else '+'}" for i, r in zip(ids, rev)) + "\t*")
+        return "\n".join(out) + ("\n" if out else "")
+
+
+def _paths(names, pieces) -> Paths:
+    """Paths from per-path (ids, rev) arrays."""
+    lens = np.array([len(i) for i, _ in pieces], dtype=np.uint64)
+    off = np.zeros(len(pieces) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lens, dtype=np.uint64)
+    ids = np.concatenate([np.asarray(i, dtype=np.uint32) for i, _ in pieces]) if pieces else np.zeros(0, np.uint32)
+    rev = np.concatenate([np.asarray(r, dtype=np.uint8) for _, r in pieces]) if pieces else np.zeros(0, np.uint8)
+    return Paths(list(names), off, ids, rev)
+
+
+def _side_csr(links: Links):
+    """Per side (2 vertex + side): the other ends (2 u + side) of its links, CSR."""
+    nS = 2 * links.n_vtx
+    a = 2 * links.v1.astype(np.int64) + links.s1
+    b = 2 * links.v2.astype(np.int64) + links.s2
+    src = np.concatenate([a, b])
+    dst = np.concatenate([b, a])
+    order = np.argsort(src, kind="stable")
+    src, dst = src[order], dst[order]
+    off = np.zeros(nS + 1, dtype=np.int64)
+    np.add.at(off, src + 1, 1)
+    return np.cumsum(off), dst
+
+
+def random_walk_paths(links: Links, n: int, length: int, seed: int, jump: float = 0.0) -> Paths:
+    """`n` paths of up to `length` steps that follow the links: from a random step, each next step goes out of the current
+    step's exit side over a random link ('>' enters a segment by its l side and leaves by r).  A path ends early at a
+    side without links.  With `jump` > 0 every next step is, with that probability, a random (segment, orientation)
+    instead -- steps no link joins, which make scans meet stray boundaries (noise_paths)."""
+    rng = np.random.default_rng(seed)
+    off, dst = _side_csr(links)
+    V = links.n_vtx
+    cur = 2 * rng.integers(0, V, size=n) + rng.integers(0, 2, size=n)  # step word: 2 v + orientation (entered side)
+    alive = np.ones(n, dtype=bool)
+    out = np.full((n, length), -1, dtype=np.int64)
+    for t in range(length):
+        out[alive, t] = cur[alive]
+        ex = cur ^ 1  # exit side: the other side of the segment
+        deg = off[ex + 1] - off[ex]
+        pick = off[ex] + (rng.random(n) * np.maximum(deg, 1)).astype(np.int64)
+        nxt = dst[np.minimum(pick, len(dst) - 1)] if len(dst) else cur
+        if jump > 0:
+            j = rng.random(n) < jump
+            nxt = np.where(j, 2 * rng.integers(0, V, size=n) + rng.integers(0, 2, size=n), nxt)
+            alive &= (deg > 0) | j
+        else:
+            alive &= deg > 0
+        cur = nxt
+    pieces = []
+    for k in range(n):
+        w = out[k][out[k] >= 0]
+        pieces.append((links.vid[w >> 1], (w & 1).astype(np.uint8)))
+    return _paths([f"walk{k}" for k in range(n)], pieces)
+
+
+def noise_paths(links: Links, n: int, length: int, seed: int, jump: float = 0.2) -> Paths:
+    """Random-walk paths with random jumps (see random_walk_paths): they reach every way a scan can fail -- a stray
+    boundary, the end of the path, more than max_steps steps."""
+    p = random_walk_paths(links, n, length, seed, jump=jump)
+    p.names = [f"noise{k}" for k in range(n)]
+    return p
+
+
+def chain_haplotypes(k: int, n: int, seed: int, reverse_every: int = 4) -> Paths:
+    """`n` haplotypes of chain_of_bubbles(k), in closed form: unit i (a = 3i + 1) is crossed by x (a + 1), by y (a + 2) or
+    by the a > b skip, chosen at random; every `reverse_every`-th haplotype is written reversed ('<' steps from the last
+    segment to the first).  Vectorised per haplotype: 10^8 segments x 32 haplotypes in seconds."""
+    rng = np.random.default_rng(seed)
+    a = 3 * np.arange(k, dtype=np.int64) + 1
+    pieces = []
+    for h in range(n):
+        c = rng.integers(0, 3, size=k, dtype=np.int8)
+        two = c < 2
+        ln = np.where(two, 2, 1)
+        start = np.zeros(k + 1, dtype=np.int64)
+        np.cumsum(ln, out=start[1:])
+        ids = np.empty(int(start[-1]) + 1, dtype=np.uint32)
+        ids[start[:-1]] = a
+        ids[start[:-1][two] + 1] = (a[two] + 1 + c[two]).astype(np.uint32)
+        ids[-1] = 3 * k + 1
+        if reverse_every and h % reverse_every == reverse_every - 1:
+            pieces.append((ids[::-1].copy(), np.ones(ids.size, dtype=np.uint8)))
+        else:
+            pieces.append((ids, np.zeros(ids.size, dtype=np.uint8)))
+    return _paths([f"hap{h}" for h in range(n)], pieces)
