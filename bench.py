@@ -7,8 +7,10 @@ to "PVST arrays on the host" (SURVEY.md 8d).
 
 N = 1   the workload is the configuration BASELINE.json's metric is quoted on: the HPRC-shaped
         whole-genome graph (configs[3]) at full size -- 24 chromosome-sized components + 2 000 tiny
-        ones, 99.9 M segments / 122.4 M links; it fits one MI355X (~190 GB of the 288 GB).  Configs
-        2 / 3 / 5 are timed briefly afterwards and reported as secondary keys of the same line.
+        ones, 99.9 M segments / 122.4 M links; it fits one MI355X (~190 GB of the 288 GB).  A plain run
+        sets up, warms up, times the steps, writes --dump-outputs and prints the line.  With --full it
+        then also times the passes one at a time, the per-stage breakdown, -s, configs 2 / 3 / 5 and
+        the cliff workloads (secondary keys of the same line), the CLI end to end and the CPU baseline.
 N > 1   STRONG scaling of the same graph (`povu_amd/sharded.py`): rank 0 holds the graph; every step
         it labels the components on its GPU, bin-packs them over the ranks (LPT), partitions the
         links on the device and scatters the shards (RCCL send/recv over xGMI); every rank builds the
@@ -368,10 +370,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="hprc-wg", choices=["hprc-wg", "chain", "hprc-chr", "nest", "tangled", "circular", "hub"])
     ap.add_argument("--scale", type=float, default=1.0, help="size factor of the workload (1.0 = BASELINE size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="at --gpus 1, after the headline steps also measure what the headline figure does not need: the "
+                         "passes one at a time, the per-stage breakdown, -s and the other workloads, the CLI end to end and "
+                         "the CPU baseline (the --gpus N lines measure the same with and without it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-overlap", action="store_true", help="time the passes one at a time instead of back to back")
-    ap.add_argument("--no-latency-leg", action="store_true", help="skip the three extra one-at-a-time passes (profiling runs)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short runs of configs 2 / 3 / 5")
+    ap.add_argument("--no-latency-leg", action="store_true",
+                    help="no warm-up passes beyond --warmup (one at the least), and with --full skip the three extra "
+                         "one-at-a-time passes (profiling runs)")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip -s, the short runs of the other workloads and the CLI end to end")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the forest of the last one as DIR/<name>.npy (see forest_outputs)")
     args = ap.parse_args()
@@ -418,23 +427,20 @@ def main():
         upload_s = time.perf_counter() - t_up
         up = hip.upload_times()
         dt, pass_ms, f, lat_ms = time_single(hip, g, args.steps, args.warmup, F_NO_STAGE_TIMES, overlap=not args.no_overlap,
-                                             pool_warm=not args.no_latency_leg)  # (profiling runs: exactly warmup + steps + 1 passes)
+                                             pool_warm=not args.no_latency_leg)  # (profiling runs: exactly warmup + steps passes, + 1 with --full)
         if args.dump_outputs:  # (f = the forest of the last timed pass, complete in host memory)
             dump_outputs(f, args.dump_outputs)
-        # the same passes one at a time (each complete before the next starts): what a single decompose call costs
-        if args.no_latency_leg:
-            dt1, pass1_ms = (dt, pass_ms) if args.no_overlap else (float("nan"), float("nan"))
-        else:
-            dt1, pass1_ms, _f1, _ = time_single(hip, g, 3, 0, F_NO_STAGE_TIMES, overlap=False)
-            dt1 = dt1 / 3 * args.steps
-            del _f1
+        if args.full:
+            # the same passes one at a time (each complete before the next starts): what a single decompose call costs
+            if args.no_latency_leg:
+                dt1, pass1_ms = (dt, pass_ms) if args.no_overlap else (float("nan"), float("nan"))
+            else:
+                dt1, pass1_ms, _f1, _ = time_single(hip, g, 3, 0, F_NO_STAGE_TIMES, overlap=False)
+                dt1 = dt1 / 3 * args.steps
+                del _f1
         E, V, F = g.n_links, g.n_vtx, count_flubbles(f)
         n_trees = len(f)
         del f
-        hip.decompose()  # untimed: per-stage HIP events for the breakdown
-        stages = {st["name"]: st["ms"] for st in hip.stage_times()}
-        stages["total"] = pass_ms
-        dom = max((k for k in stages if k != "total"), key=lambda k: stages[k])
         alg = algorithmic_bytes(E, V, F)
         achieved = alg / (pass_ms * 1e-3) / 1e9
         traffic, traffic_note = None, "no PMC run of this workload under profiles/"
@@ -470,11 +476,9 @@ def main():
                                     "kernels of the next pass; ms_per_launch = HIP events from the first kernel of the first timed "
                                     "pass to the last byte of the last, / steps" if not args.no_overlap else
                                     "one pass at a time"),
-                         "pass_latency_ms": lat_ms, "ms_per_launch_one_pass_at_a_time": pass1_ms,
+                         "pass_latency_ms": lat_ms,
                          # what ONE call of povu_hip_decompose (the CLI, the FFI) reaches: the same bytes over the latency of a pass
-                         "frac_single_call": alg / (lat_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "dominant_stage": {"name": dom, "ms": stages[dom]}},
-            "stage_ms": stages,
+                         "frac_single_call": alg / (lat_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
             # what happens before the timed region (povu_hip_graph_upload), split by HIP events:
             "upload": {"wall_ms": upload_s * 1e3, "h2d_ms": up["h2d_ms"], "csr_build_ms": up["csr_ms"],
                        "twin_index_ms": up["twin_ms"],
@@ -486,9 +490,17 @@ def main():
             "value_from_resident_shards": E * args.steps / dt,
             "value_whole_job": E / (step_s + (up["csr_ms"] + up["twin_ms"]) * 1e-3),
             "pcie_inclusive_value": E / (step_s + upload_s),
-            "ms_per_step_one_pass_at_a_time": dt1 / args.steps * 1e3,
         }
-        if not args.no_secondary and args.workload == "hprc-wg":
+        if args.full:
+            hip.decompose()  # untimed: per-stage HIP events for the breakdown
+            stages = {st["name"]: st["ms"] for st in hip.stage_times()}
+            stages["total"] = pass_ms
+            dom = max((k for k in stages if k != "total"), key=lambda k: stages[k])
+            out["roofline"]["ms_per_launch_one_pass_at_a_time"] = pass1_ms
+            out["roofline"]["dominant_stage"] = {"name": dom, "ms": stages[dom]}
+            out["stage_ms"] = stages
+            out["ms_per_step_one_pass_at_a_time"] = dt1 / args.steps * 1e3
+        if args.full and not args.no_secondary and args.workload == "hprc-wg":
             # `povu decompose -s` on the same graph: all five subflubble passes on top of the pass (not part of `value`)
             for _ in range(3):  # (untimed: the first call sizes the stage's arena, the second reserves it, the third finds its page-locked blocks in the pool)
                 hip.decompose(flags=F_SUBFLUBBLES)
@@ -536,10 +548,10 @@ def main():
                     del f_s
                 del f2, g2
             out["secondary"] = sec
-        if not args.no_secondary:
+        if args.full and not args.no_secondary:
             hip.close()  # the CLI child takes the GPU memory this context holds
             out["end_to_end"] = end_to_end_cli(g, wl)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(g, wl)
     else:
         from povu_amd.sharded import ShardedBench

@@ -8,7 +8,7 @@ WL=${WL:-hprc-wg}
 O=$R/gpurun_out/$TAG
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-A="--workload $WL --no-cpu-baseline --no-secondary --no-latency-leg"
+A="--workload $WL --full --no-cpu-baseline --no-secondary --no-latency-leg"
 python3 $R/bench.py $A --steps 10 --warmup 3 > $O/bench_new.json 2> $O/err_new.log || { tail -5 $O/err_new.log; exit 2; }
 export $KV
 python3 $R/bench.py $A --steps 10 --warmup 3 > $O/bench_old.json 2> $O/err_old.log || { tail -5 $O/err_old.log; exit 2; }

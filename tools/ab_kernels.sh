@@ -11,7 +11,7 @@ rm -rf $O && mkdir -p $O
 L=$R/povu_amd/lib/libpovu_hip.so
 cp $L $O/a.so
 cd /tmp && export TMPDIR=/tmp
-A="--workload $WL --no-cpu-baseline --no-secondary --steps 3 --warmup 1"
+A="--workload $WL --full --no-cpu-baseline --no-secondary --steps 3 --warmup 1"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_a -- python3 $R/bench.py $A > $O/a.json 2> $O/a.err || { cp $O/a.so $L; exit 2; }
 cp $V $L
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_b -- python3 $R/bench.py $A > $O/b.json 2> $O/b.err; rc=$?

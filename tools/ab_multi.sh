@@ -11,7 +11,7 @@ rm -rf $O && mkdir -p $O
 L=$R/povu_amd/lib/libpovu_hip.so
 cp $L $O/base.so
 cd /tmp && export TMPDIR=/tmp
-A="--workload $WL --no-cpu-baseline --no-secondary --no-latency-leg --steps 2 --warmup 1"
+A="--workload $WL --full --no-cpu-baseline --no-secondary --no-latency-leg --steps 2 --warmup 1"
 i=0
 for V in base "$@"; do
   [ $V = base ] || cp $R/$V $L

@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 b = json.load(open(os.path.join(ROOT, "profiles", f"{tag}_hprc-wg_bench.json")))
 L = [f"# Round {tag[1:]}: the other workloads of the bench line (`{tag}_hprc-wg_bench.json`, one MI355X)\n",
-     "Secondary keys of the default `python bench.py` run (5 timed passes each, 2 for the tangled and the hub graph), same context, same code as the headline number; "
+     "Secondary keys of the `python bench.py --full` run (5 timed passes each, 2 for the tangled and the hub graph), same context, same code as the headline number; "
      "`-s ms` = one decompose with all five subflubble passes (wall clock) where the line carries it.\n",
      "| key | workload | ms/pass | links/s | roofline frac | -s ms | heaviest stages |", "|---|---|---|---|---|---|---|"]
 for k, v in b["secondary"].items():

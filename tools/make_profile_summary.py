@@ -7,7 +7,7 @@ import bench  # kernel_source_digest
 F = os.path.join(ROOT, "gpurun_out", "final")
 P = os.path.join(ROOT, "profiles")
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
-PASSES = 4  # bench.py --no-overlap --no-latency-leg --steps 2 --warmup 1: 1 warm-up + 2 timed + 1 stage-breakdown pass, one at a time
+PASSES = 4  # bench.py --full --no-overlap --no-latency-leg --steps 2 --warmup 1: 1 warm-up + 2 timed + 1 stage-breakdown pass, one at a time
 
 
 def short(n):
@@ -52,7 +52,7 @@ for wl, title in (("hprc-wg", "BASELINE config 4 at full size (the headline work
                     "write_size_kb_per_pass": write["per_pass"], "fetch_calibration": cal,
                     "kernel_source_digest": bench.kernel_source_digest(),
                     "note": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate runs of `bench.py --workload " + wl +
-                            " --steps 2 --warmup 1` (4 decompose passes + one upload, divided by 4). Counter values are KB. "
+                            " --full --steps 2 --warmup 1` (4 decompose passes + one upload, divided by 4). Counter values are KB. "
                             "Correction per MI355X_MICROARCH.md (gfx950 counts coalesced streaming reads at half): FETCH_SIZE is "
                             "doubled -- fetch_calibration = counted / known bytes on the xor-scan kernels of this run shows ~0.5 "
                             "for wide and for narrow per lane loads alike; WRITE_SIZE as counted; scattered gathers are "
@@ -68,7 +68,7 @@ for wl, title in (("hprc-wg", "BASELINE config 4 at full size (the headline work
              f"the pass {bench_line['roofline']['ms_per_launch']:.2f} ms, roofline frac {bench_line['roofline']['frac']:.4f} (algorithmic 48E+108V+16F = "
              f"{alg/1e9:.3f} GB per pass)" + (f"; CPU port on the box: {cb['value']:.3e} links/s on {cb['cores']} threads (reference scheme), "
                                               f"{cb['value_lpt_threads']:.3e} bin-packed, {cb['value_one_thread']:.3e} on one thread ({cb.get('one_thread_sample', '')})" if cb else "") + ".\n")
-    L.append(f"### Kernel trace\n\n`rocprofv3 --kernel-trace --stats -- python3 bench.py --workload {wl} --no-cpu-baseline --no-secondary --no-overlap --no-latency-leg --steps 2 --warmup 1` "
+    L.append(f"### Kernel trace\n\n`rocprofv3 --kernel-trace --stats -- python3 bench.py --workload {wl} --full --no-cpu-baseline --no-secondary --no-overlap --no-latency-leg --steps 2 --warmup 1` "
              f"({passes} passes + one upload): sum of kernel durations {tot_ns/1e6:.2f} ms over {calls} launches; the last pass: "
              f"`{open(os.path.join(D, 'timeline_summary.txt')).read().strip()}` (HIP-event time of a pass in that run: {under['roofline']['ms_per_launch']:.2f} ms).\n")
     agg = {}
@@ -125,7 +125,7 @@ for wl, title in (("nest", "BASELINE config 5 (nested towers)"), ("tangled", "ta
         a = agg.setdefault(short(r["Name"]), [0, 0])
         a[0] += int(r["Calls"]); a[1] += int(r["TotalDurationNs"])
     L.append(f"## {title}: kernel trace of the shipped walk\n")
-    L.append(f"Workload: {under['config']['workload']}.  `rocprofv3 --kernel-trace --stats -- python3 bench.py --workload {wl} --no-cpu-baseline --no-secondary "
+    L.append(f"Workload: {under['config']['workload']}.  `rocprofv3 --kernel-trace --stats -- python3 bench.py --workload {wl} --full --no-cpu-baseline --no-secondary "
              f"--no-overlap --no-latency-leg --steps 2 --warmup 1` ({PASSES} passes): {under['ms_per_step']:.2f} ms per pass under the tracer; full table `{tag}_{wl}_kernel_stats.csv`.\n")
     L.append("| kernel | calls/pass | ms/pass |\n|---|---|---|")
     for k, v in sorted(agg.items(), key=lambda x: -x[1][1])[:8]:

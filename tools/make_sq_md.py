@@ -10,7 +10,7 @@ for r in csv.DictReader(open(f"profiles/{rnd}_hprc-wg_kernel_stats.csv")):
     n = r["Name"].split("(")[0].replace("povu_hip::", "").replace("void ", "")
     ms[n] = float(r["TotalDurationNs"]) / 1e6 / 4
 out = [f"# Round {rnd[1:]}: SQ counters per kernel, headline workload", "",
-       "`bash tools/pmc_sq.sh` (three `rocprofv3 --pmc` runs of `bench.py --workload hprc-wg --steps 2 --warmup 1`, counters only; per pass =",
+       "`bash tools/pmc_sq.sh` (three `rocprofv3 --pmc` runs of `bench.py --workload hprc-wg --full --no-cpu-baseline --no-secondary --steps 2 --warmup 1`, counters only; per pass =",
        "total / 4).  Read with `DESIGN.md` section 4: the adjacency-walking kernels issue few instructions per wave, are far from",
        "the HBM rate of their own traffic, and spend 25-35 cycles of their CU per vector-memory instruction -- the address unit takes",
        "one cycle per distinct line a wave instruction touches.  `cyc/VMEM` = kernel time x 2.1 GHz x 256 CUs / vector-memory instructions.", "",

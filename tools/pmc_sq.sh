@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/sq
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-A="--workload hprc-wg --no-cpu-baseline --no-secondary --steps 2 --warmup 1"
+A="--workload hprc-wg --full --no-cpu-baseline --no-secondary --steps 2 --warmup 1"
 i=0
 for SET in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_INSTS_LDS" "SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" "SQ_LEVEL_WAVES SQ_CYCLES SQ_INST_LEVEL_VMEM SQ_THREAD_CYCLES_VALU SQ_INSTS_BRANCH GRBM_GUI_ACTIVE"; do
   i=$((i+1))
