@@ -149,6 +149,48 @@ private:
 	size_t cap_ = 0, top_ = 0;
 };
 
+// An arena layout declared once: a list of spans, `take(n, p...)` for n elements of each pointer's type (n bytes for a
+// void *), run first with no arena behind it to measure, then to carve.  The measure holds from any starting offset: every
+// span counts its padded size and one alignment step more.
+struct Spans {
+	Arena *ar = nullptr; // null: measure only
+	size_t bytes = 0;
+	template <typename... P>
+	void operator()(size_t n, P *&...p)
+	{
+		(one(p, n), ...);
+	}
+	template <typename T>
+	void one(T *&p, size_t n)
+	{
+		bytes += Arena::padded(n, sizeof(T)) + 256;
+		if (ar)
+			p = ar->take<T>(n);
+	}
+	void one(void *&p, size_t n)
+	{
+		char *c = nullptr;
+		one(c, n);
+		if (ar)
+			p = c;
+	}
+};
+template <class List>
+size_t measure(List &&list)
+{
+	Spans m;
+	list(m);
+	return m.bytes;
+}
+// reserves what `list` measures in `A` (from offset 0: earlier spans are invalidated) and carves it
+template <class List>
+void carve(Arena &A, List &&list, bool head_room = true)
+{
+	A.reserve(measure(list), head_room);
+	Spans c{&A};
+	list(c);
+}
+
 // Page-locked host scratch of one context.  Every small read-back (a count that sizes the next
 // launch) and every host-built table goes through it, so no copy is staged through pageable
 // memory; spans stay valid until the next reset() (= the next decompose on that context).
@@ -389,6 +431,9 @@ struct WordSrc {
 void publish_words(uint32_t *host_dst, const WordSrc &src, int n, hipStream_t s);
 void compact_flagged_u8(const uint8_t *flag, size_t n, uint32_t *out, uint32_t *count_dev, void *tmp, size_t tmp_bytes, hipStream_t s);
 size_t compact_tmp_bytes(size_t n);
+// 64-bit sums of n u32 counts, of `a` into h[0] and of `b` (optional) into h[1], in one launch; tot: as many words of device
+// memory (cleared here).  Waits for the stream.
+void totals_u32(const uint32_t *a, const uint32_t *b, uint64_t n, unsigned long long *tot, uint64_t *h, hipStream_t s);
 // exclusive running maximum (identity 0)
 void scan_exclusive_max_u32(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s);
 // stable LSD radix sort of (key,value) pairs on the low `bits` bits of the key

@@ -9,7 +9,6 @@
 #include <memory>
 #include <mutex>
 #include <numeric>
-#include <type_traits>
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -338,140 +337,77 @@ extern "C" int povu_hip_last_upload_times(const povu_hip_ctx *ctx, double out_ms
 //           sequential kernels actually run (POVU_HIP_F_SEQUENTIAL / _SEQ_TREE, or a redo)
 size_t carve_workspace(Arena *ar, int part, const Sizes &z, CompState &cs, SeqWs &sw, bool hairpins)
 {
-	size_t total = 0;
-	auto take = [&](auto **dst, size_t n, size_t elem) {
-		total += Arena::padded(n, elem) + 256;
-		if (ar) {
-			using P = std::remove_reference_t<decltype(*dst)>;
-			*dst = reinterpret_cast<P>(ar->take<char>(n * elem));
-		}
-	};
+	Spans take{ar};
 	const size_t V = z.V, E = z.E, C = z.Cmax, T = z.T, B = z.B, nS = z.nS;
 	if (part == 0) {
-		take(&cs.label, V + 1, 4);
-		take(&cs.flag, std::max(V, z.slots) + 2, 4);
-		take(&cs.crank, V + 2, 4);
-		take(&cs.comp_of, V + 1, 4);
-		take(&cs.tmp_a, V + 1, 4);
-		take(&cs.ckey, V + 1, 4);
-		take(&cs.perm, V + 1, 4);
-		take(&cs.pos, V + 1, 4);
-		take(&cs.voff, C + 2, 4);
-		take(&cs.eoff, C + 2, 4);
-		take(&cs.vdeg, V + 2, 4);
-		take(&cs.sbase, V + 2, 4);
-		take(&cs.first, E + 1, 4);
-		take(&cs.erank, z.slots + 2, 4);
-		take(&cs.ldeg, nS + 2, 4);
-		take(&cs.loff, nS + 2, 4);
-		take(&cs.ladj, 2 * E + 8, 4); // (+8: the class walk reads a side's list words four at a time)
-		take(&cs.keys, 2 * E + 2, 4);
-		take(&cs.vals, 2 * E + 2, 4);
-		take(&cs.keys2, 2 * E + 2, 4);
-		take(&cs.vals2, 2 * E + 2, 4);
-		take(&cs.hook, 2 * E + 32, 1);
-		take(&cs.la, E + 2, 4);
-		take(&cs.lb, E + 2, 4);
-		take(&cs.lle, 2 * E + 8, 4); // (+8: the tour kernel reads a segment's slot words four at a time)
-		take(&cs.tgray, E + 32, 1);
-		take(&cs.stats, 16, 4);
-		take(&cs.gid_s, V + 1, 4);
-		take(&cs.tip_s, V + 1, 1);
-		take(&cs.start_key, C + 2, 8);
+		take(V + 1, cs.label);
+		take(std::max(V, z.slots) + 2, cs.flag);
+		take(V + 2, cs.crank);
+		take(V + 1, cs.comp_of, cs.tmp_a, cs.ckey, cs.perm, cs.pos);
+		take(C + 2, cs.voff, cs.eoff);
+		take(V + 2, cs.vdeg, cs.sbase);
+		take(E + 1, cs.first);
+		take(z.slots + 2, cs.erank);
+		take(nS + 2, cs.ldeg, cs.loff);
+		take(2 * E + 8, cs.ladj); // (+8: the class walk reads a side's list words four at a time)
+		take(2 * E + 2, cs.keys, cs.vals, cs.keys2, cs.vals2);
+		take(2 * E + 32, cs.hook);
+		take(E + 2, cs.la, cs.lb);
+		take(2 * E + 8, cs.lle); // (+8: the tour kernel reads a segment's slot words four at a time)
+		take(E + 32, cs.tgray);
+		take(16, cs.stats);
+		take(V + 1, cs.gid_s, cs.tip_s);
+		take(C + 2, cs.start_key);
 		cs.scan_tmp_bytes = scan_tmp_bytes(std::max<size_t>(nS, z.slots) + 2);
 		cs.sort_tmp_bytes = sort_tmp_bytes(std::max<size_t>(2 * E, V) + 2);
-		take((char **)&cs.scan_tmp, cs.scan_tmp_bytes, 1);
-		take((char **)&cs.sort_tmp, cs.sort_tmp_bytes, 1);
+		take(cs.scan_tmp_bytes, cs.scan_tmp);
+		take(cs.sort_tmp_bytes, cs.sort_tmp);
 	} else if (part == 1) {
 		// host-built per-component tables, one upload: order | owner | processed-before | processed | stack entries before
 		uint32_t *tables = nullptr;
-		take(&tables, 5 * (C + 1), 4);
+		take(5 * (C + 1), tables);
 		sw.order = tables;
 		sw.owner = tables + (C + 1);
 		sw.tables = tables;
-		take(&sw.t_gid, T, 4);
-		take(&sw.t_par, T, 4);
-		take(&sw.t_cls, T, 4);
-		take(&sw.t_size, T + 8, 4); // (+8: the class stage reads sizes eight words at a time)
-		take(&sw.t_depth, T, 4);
-		take(&sw.t_flags, T, 1);
-		take(&sw.cur, nS + 1, 4);
-		take(&sw.s_vtx, V + 1, 4);
-		take(&sw.s_cls, V + 1, 4);
-		take(&sw.next_seen, V + 1, 4);
+		take(T, sw.t_gid, sw.t_par, sw.t_cls);
+		take(T + 8, sw.t_size); // (+8: the class stage reads sizes eight words at a time)
+		take(T, sw.t_depth, sw.t_flags);
+		take(nS + 1, sw.cur);
+		take(V + 1, sw.s_vtx, sw.s_cls, sw.next_seen);
 		if (hairpins)
-			take(&sw.hairpins, 2 * (V + C + 1), 8);
+			take(2 * (V + C + 1), sw.hairpins);
 		else
 			sw.hairpins = nullptr;
-		take(&sw.c_ntree, C + 1, 4);
-		take(&sw.c_nbe0, C + 1, 4);
-		take(&sw.c_nbe, C + 1, 4);
-		take(&sw.c_nstack, C + 1, 4);
-		take(&sw.c_npvst, C + 1, 4);
-		take(&sw.c_nclass, C + 1, 4);
-		take(&sw.c_nbry, C + 1, 4);
-		take(&sw.c_status, C + 1, 4);
+		take(C + 1, sw.c_ntree, sw.c_nbe0, sw.c_nbe, sw.c_nstack, sw.c_npvst, sw.c_nclass, sw.c_nbry, sw.c_status);
 	} else {
-		take(&sw.t_hi, T, 4);
-		take(&sw.first_child, T, 4);
-		take(&sw.next_sib, T, 4);
-		take(&sw.last_child, T, 4);
-		take(&sw.ctr, nS + 1, 4);
-		take(&sw.stk, T, 4);
-		take(&sw.selfloop, V + 1, 1);
-		take(&sw.be_src, B, 4);
-		take(&sw.be_tgt, B, 4);
-		take(&sw.o_next, B, 4);
-		take(&sw.i_next, B, 4);
-		take(&sw.b_prev, B, 4);
-		take(&sw.b_next, B, 4);
-		take(&sw.b_rsize, B, 4);
-		take(&sw.b_rclass, B, 4);
-		take(&sw.be_type, B, 1);
-		take(&sw.b_in, B, 1);
-		take(&sw.be_cdef, B, 1);
-		take(&sw.o_head, T, 4);
-		take(&sw.o_tail, T, 4);
-		take(&sw.i_head, T, 4);
-		take(&sw.i_tail, T, 4);
-		take(&sw.l_head, T, 4);
-		take(&sw.l_tail, T, 4);
-		take(&sw.l_size, T, 4);
-		take(&sw.bl, T, 4);
-		take(&sw.nxt, T, 4);
-		take(&sw.st_head, T, 4);
-		take(&sw.st_tail, T, 4);
-		take(&sw.last, B + T, 4);
-		take(&sw.p_parent, V + C + 1, 4);
-		take(&sw.p_a, V + C + 1, 4);
-		take(&sw.p_z, V + C + 1, 4);
-		take(&sw.p_or, V + C + 1, 1);
-		take(&sw.aux, V + C + 1, 4);
-		take(&sw.in_s, B + T, 1);
+		take(T, sw.t_hi, sw.first_child, sw.next_sib, sw.last_child);
+		take(nS + 1, sw.ctr);
+		take(T, sw.stk);
+		take(V + 1, sw.selfloop);
+		take(B, sw.be_src, sw.be_tgt, sw.o_next, sw.i_next, sw.b_prev, sw.b_next, sw.b_rsize, sw.b_rclass);
+		take(B, sw.be_type, sw.b_in, sw.be_cdef);
+		take(T, sw.o_head, sw.o_tail, sw.i_head, sw.i_tail, sw.l_head, sw.l_tail, sw.l_size, sw.bl);
+		take(T, sw.nxt, sw.st_head, sw.st_tail);
+		take(B + T, sw.last);
+		take(V + C + 1, sw.p_parent, sw.p_a, sw.p_z, sw.p_or, sw.aux);
+		take(B + T, sw.in_s);
 	}
-	return total + (1 << 20);
+	return take.bytes + (1 << 20);
 }
 
 size_t rowb_carve_label(Arena *ar, const Sizes &z, CompState &cs)
 {
-	size_t total = 0;
-	auto take = [&](auto **dst, size_t n, size_t elem) {
-		total += Arena::padded(n, elem) + 256;
-		if (ar) {
-			using P = std::remove_reference_t<decltype(*dst)>;
-			*dst = reinterpret_cast<P>(ar->take<char>(n * elem));
-		}
-	};
+	Spans take{ar};
 	const size_t V = z.V, E = z.E;
-	take(&cs.label, V + 1, 4);
-	take(&cs.flag, V / 4 + 16, 4); // (one byte per vertex: is-root flags)
-	take(&cs.crank, V + 2, 4);
-	take(&cs.comp_of, V + 1, 4);
-	take(&cs.keys, 2 * E + 2, 4); // the cross list of the union-find tiles: [E] pairs
-	take(&cs.hook, 2 * E + 32, 1);
-	take(&cs.stats, 16, 4);
+	take(V + 1, cs.label);
+	take(V / 4 + 16, cs.flag); // (one byte per vertex: is-root flags)
+	take(V + 2, cs.crank);
+	take(V + 1, cs.comp_of);
+	take(2 * E + 2, cs.keys); // the cross list of the union-find tiles: [E] pairs
+	take(2 * E + 32, cs.hook);
+	take(16, cs.stats);
 	cs.scan_tmp_bytes = scan_tmp_bytes(std::max<size_t>(z.nS, z.slots) + 2);
-	take((char **)&cs.scan_tmp, cs.scan_tmp_bytes, 1);
+	take(cs.scan_tmp_bytes, cs.scan_tmp);
 	if (ar) { // (what rowb_carve_reindex adds; null until then so that a use before it is a clean failure, not a stale pointer)
 		cs.tmp_a = cs.ckey = cs.perm = cs.pos = cs.voff = cs.eoff = cs.vdeg = cs.sbase = cs.first = cs.erank = cs.ldeg = cs.loff =
 			cs.ladj = cs.vals = cs.keys2 = cs.vals2 = cs.la = cs.lb = cs.lle = cs.gid_s = nullptr;
@@ -480,7 +416,7 @@ size_t rowb_carve_label(Arena *ar, const Sizes &z, CompState &cs)
 		cs.sort_tmp = nullptr;
 		cs.sort_tmp_bytes = 0;
 	}
-	return total + (1 << 16);
+	return take.bytes + (1 << 16);
 }
 
 // what the re-index arena must hold already for the adjacency kernel to be started ahead of the component count
@@ -488,53 +424,34 @@ size_t rowb_speculative_adj_bytes(const Sizes &z) { return 2 * (Arena::padded(2 
 
 size_t rowb_carve_reindex(Arena *ar, const Sizes &z, size_t C, const RowBNeeds &need, CompState &cs)
 {
-	size_t total = 0;
-	auto take = [&](auto **dst, size_t n, size_t elem) {
-		total += Arena::padded(n, elem) + 256;
-		if (ar) {
-			using P = std::remove_reference_t<decltype(*dst)>;
-			*dst = reinterpret_cast<P>(ar->take<char>(n * elem));
-		}
-	};
+	Spans take{ar};
 	const size_t V = z.V, E = z.E, nS = z.nS;
 	const bool lean = need.identity && need.sort_free; // sorted space = global vertex space, nothing is renumbered
 	// (ladj and lle FIRST: their place in the arena does not depend on the component count -- povu_hip_decompose starts the
 	// kernel that fills them before the count has reached the host, rowb_speculative_adj_bytes)
-	take(&cs.ladj, 2 * E + 8, 4); // (+8: the class walk reads a side's list words four at a time)
-	take(&cs.lle, 2 * E + 8, 4);  // (+8: the tour kernel reads a segment's slot words four at a time)
-	take(&cs.voff, C + 2, 4);
-	take(&cs.eoff, C + 2, 4);
-	take(&cs.start_key, C + 2, 8);
+	take(2 * E + 8, cs.ladj); // (+8: the class walk reads a side's list words four at a time)
+	take(2 * E + 8, cs.lle);  // (+8: the tour kernel reads a segment's slot words four at a time)
+	take(C + 2, cs.voff, cs.eoff, cs.start_key);
 	if (!lean) { // the vertices are renumbered (or the sorting builder wants the tables anyway)
-		take(&cs.tmp_a, V + 1, 4);
-		take(&cs.ckey, V + 1, 4);
-		take(&cs.perm, V + 1, 4);
-		take(&cs.pos, V + 1, 4);
-		take(&cs.vdeg, V + 2, 4);
-		take(&cs.sbase, V + 2, 4);
-		take(&cs.gid_s, V + 1, 4);
-		take(&cs.tip_s, V + 1, 1);
+		take(V + 1, cs.tmp_a, cs.ckey, cs.perm, cs.pos);
+		take(V + 2, cs.vdeg, cs.sbase);
+		take(V + 1, cs.gid_s, cs.tip_s);
 	}
-	if (!(lean && !need.self_loops)) { // local degrees and offsets of the sides (else the CSR's own)
-		take(&cs.ldeg, nS + 2, 4);
-		take(&cs.loff, nS + 2, 4);
-	}
+	if (!(lean && !need.self_loops)) // local degrees and offsets of the sides (else the CSR's own)
+		take(nS + 2, cs.ldeg, cs.loff);
 	if (!need.sort_free) { // the builder that numbers the local edges densely (hub vertices; povu_hip_componetize takes the full set)
-		take(&cs.flag, std::max(V, z.slots) + 2, 4);
-		take(&cs.first, E + 1, 4);
-		take(&cs.erank, z.slots + 2, 4);
-		take(&cs.vals, 2 * E + 2, 4);
-		take(&cs.keys2, 2 * E + 2, 4);
-		take(&cs.vals2, 2 * E + 2, 4);
-		take(&cs.la, E + 2, 4);
-		take(&cs.lb, E + 2, 4);
-		take(&cs.tgray, E + 32, 1);
+		take(std::max(V, z.slots) + 2, cs.flag);
+		take(E + 1, cs.first);
+		take(z.slots + 2, cs.erank);
+		take(2 * E + 2, cs.vals, cs.keys2, cs.vals2);
+		take(E + 2, cs.la, cs.lb);
+		take(E + 32, cs.tgray);
 	}
 	if (!need.identity || !need.sort_free) {
 		cs.sort_tmp_bytes = sort_tmp_bytes(std::max<size_t>(2 * E, V) + 2);
-		take((char **)&cs.sort_tmp, cs.sort_tmp_bytes, 1);
+		take(cs.sort_tmp_bytes, cs.sort_tmp);
 	}
-	return total + (1 << 16);
+	return take.bytes + (1 << 16);
 }
 
 namespace

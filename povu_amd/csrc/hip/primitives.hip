@@ -507,6 +507,41 @@ void scan_exclusive_max_u32(const uint32_t *in, uint32_t *out, size_t n, void *t
 	scan_exclusive<1>(in, out, n, tmp, tmp_bytes, s);
 }
 
+// ---- 64-bit totals of u32 counts: one array, or two of the same length side by side
+__global__ void __launch_bounds__(SC_TPB) k_totals_u32(uint64_t n, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b,
+						      unsigned long long *__restrict__ tot)
+{
+	__shared__ unsigned long long sa, sb;
+	if (threadIdx.x == 0)
+		sa = sb = 0;
+	__syncthreads();
+	unsigned long long x = 0, y = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * SC_TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * SC_TPB) {
+		x += a[i];
+		if (b)
+			y += b[i];
+	}
+	atomicAdd(&sa, x);
+	if (b)
+		atomicAdd(&sb, y);
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		atomicAdd(&tot[0], sa);
+		if (b)
+			atomicAdd(&tot[1], sb);
+	}
+}
+
+void totals_u32(const uint32_t *a, const uint32_t *b, uint64_t n, unsigned long long *tot, uint64_t *h, hipStream_t s)
+{
+	const size_t bytes = b ? 16 : 8;
+	HIP_CHECK(hipMemsetAsync(tot, 0, bytes, s));
+	if (n)
+		KLAUNCH(k_totals_u32, dim3((unsigned)std::min<uint64_t>((n + SC_TPB - 1) / SC_TPB, 1024)), dim3(SC_TPB), 0, s, n, a, b, tot);
+	HIP_CHECK(copy_async(h, tot, bytes, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+}
+
 // ---- exclusive running xor of 128-bit words (the bridge test's two hashes): same two-launch scheme, 2 words per lane
 static constexpr int X128_ITEMS = 2, X128_TILE = SC_TPB * X128_ITEMS;
 struct Xor128Job {

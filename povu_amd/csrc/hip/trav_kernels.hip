@@ -519,33 +519,6 @@ __global__ __launch_bounds__(T_TPB) void k_tr_allele_steps(uint32_t n_al, const 
 	}
 }
 
-// 64-bit total of n u32 counts
-__global__ void k_tr_total(uint64_t n, const uint32_t *__restrict__ c, unsigned long long *__restrict__ tot)
-{
-	__shared__ unsigned long long s;
-	if (threadIdx.x == 0)
-		s = 0;
-	__syncthreads();
-	unsigned long long x = 0;
-	for (uint64_t i = (uint64_t)blockIdx.x * T_TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * T_TPB)
-		x += c[i];
-	atomicAdd(&s, x);
-	__syncthreads();
-	if (threadIdx.x == 0)
-		atomicAdd(tot, s);
-}
-
-static uint64_t total_u32(const uint32_t *c, uint64_t n, unsigned long long *tot, hipStream_t s)
-{
-	HIP_CHECK(hipMemsetAsync(tot, 0, 8, s));
-	if (n)
-		KLAUNCH(k_tr_total, dim3(std::min<uint64_t>((n + T_TPB - 1) / T_TPB, 1024)), dim3(T_TPB), 0, s, n, c, tot);
-	uint64_t h = 0;
-	HIP_CHECK(copy_async(&h, tot, 8, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(hipStreamSynchronize(s));
-	return h;
-}
-
 static void check_32(uint64_t v, const char *what)
 {
 	if (v >= 0xFFFFFFFFull)
@@ -569,8 +542,7 @@ static uint32_t hash_bits_hook()
 extern "C" int povu_hip_paths_upload(povu_hip_ctx *ctx, uint32_t n_paths, const uint64_t *step_off, const uint32_t *step_id,
 				     const uint8_t *step_rev, char *err, size_t errlen)
 {
-	XferScope xfer(ctx);
-	try {
+	return guarded_call(ctx, err, errlen, 1, [&] {
 		if (!ctx)
 			throw HipError("null context");
 		if (!ctx->g.block)
@@ -596,13 +568,21 @@ extern "C" int povu_hip_paths_upload(povu_hip_ctx *ctx, uint32_t n_paths, const 
 		HIP_CHECK(hipSetDevice(ctx->device));
 		ctx->wait_tail();
 		hipStream_t s = ctx->stream;
-		ctx->paths_buf.reserve(Arena::padded(N + 4, 4) + Arena::padded((size_t)n_paths + 1, 8) + 4 * 256, false);
-		ctx->path_steps = ctx->paths_buf.take<uint32_t>(N + 4);
-		ctx->path_off = ctx->paths_buf.take<uint64_t>((size_t)n_paths + 1);
-		ctx->tr_ws.reserve(Arena::padded(N + 1, 1) + Arena::padded(8, 8) + 4 * 256);
-		uint8_t *rev = ctx->tr_ws.take<uint8_t>(N + 1);
-		uint32_t *words = ctx->tr_ws.take<uint32_t>(4);
-		unsigned long long *bad = ctx->tr_ws.take<unsigned long long>(1);
+		carve(
+			ctx->paths_buf,
+			[&](Spans &take) {
+				take(N + 4, ctx->path_steps);
+				take((size_t)n_paths + 1, ctx->path_off);
+			},
+			false);
+		uint8_t *rev;
+		uint32_t *words;
+		unsigned long long *bad;
+		carve(ctx->tr_ws, [&](Spans &take) {
+			take(N + 1, rev);
+			take(4, words);
+			take(1, bad);
+		});
 		HIP_CHECK(hipMemsetAsync(words, 0, 16, s));
 		HIP_CHECK(hipMemsetAsync(bad, 0xFF, 8, s));
 		HIP_CHECK(copy_async(ctx->path_off, step_off, ((size_t)n_paths + 1) * 8, hipMemcpyHostToDevice, s));
@@ -618,8 +598,7 @@ extern "C" int povu_hip_paths_upload(povu_hip_ctx *ctx, uint32_t n_paths, const 
 		HIP_CHECK(copy_async(hw, words, 16, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(copy_async(&hb, bad, 8, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
-		if (hw[0] & 1u)
-			throw HipError("paths need segment ids that ascend with the vertex index (the order the GFA loader gives)");
+		query_refusals(hw[0], "paths");
 		if (hb != ~0ull) {
 			const uint32_t k = (uint32_t)(std::upper_bound(step_off, step_off + n_paths + 1, hb) - step_off) - 1;
 			throw HipError("path " + std::to_string(k) + " step " + std::to_string(hb - step_off[k]) + ": segment " +
@@ -630,14 +609,8 @@ extern "C" int povu_hip_paths_upload(povu_hip_ctx *ctx, uint32_t n_paths, const 
 		ctx->paths_gen = g.gen;
 		ctx->paths_valid = true;
 		return 0;
-	} catch (const std::exception &e) {
-		if (ctx && ctx->stream)
-			(void)hipStreamSynchronize(ctx->stream);
-		set_err(err, errlen, e.what());
-		return 1;
-	}
+	});
 }
-
 namespace
 {
 struct TraversalsOwner {
@@ -652,16 +625,8 @@ struct TraversalsOwner {
 extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, povu_hip_forest *f, const povu_hip_trav_opts *opts,
 							   char *err, size_t errlen)
 {
-	XferScope xfer(ctx);
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	auto drop_events = [&] {
-		if (e0)
-			(void)hipEventDestroy(e0);
-		if (e1)
-			(void)hipEventDestroy(e1);
-		e0 = e1 = nullptr;
-	};
-	try {
+	CallTimer timer;
+	return guarded_call(ctx, err, errlen, (povu_hip_traversals *)nullptr, [&] {
 		check_query_forest(ctx, f, "traversals");
 		if (!ctx->paths_valid || ctx->paths_gen != ctx->g.gen)
 			throw HipError("no paths are resident for the graph now uploaded (povu_hip_paths_upload after povu_hip_graph_upload)");
@@ -674,61 +639,39 @@ extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, po
 			flags = opts->flags;
 		}
 		const uint32_t hbits = hash_bits_hook();
-		HIP_CHECK(hipSetDevice(ctx->device));
-		ctx->wait_tail();
-		f->ready();
 		const ResidentGraph &g = ctx->g;
 		hipStream_t s = ctx->stream;
 		const uint64_t N = ctx->n_path_steps;
 		const uint32_t P = ctx->n_paths, nS = 2 * g.V;
-
-		std::vector<uint32_t> qa, qz;
-		std::vector<uint8_t> qor;
-		forest_queries(f, qa, qz, qor);
-		const uint32_t n = (uint32_t)qa.size();
-		const size_t n1 = (size_t)n + 1, n2q = 2 * (size_t)n + 1;
 		const uint64_t n_tiles = (N + T_TILE - 1) / T_TILE;
 		check_32(n_tiles + 1, "start-task tiles");
 
 		// ---- phase A: queries, the boundary table, tile counts
-		const size_t sort_a = sort_tmp_bytes(n2q) + 256;
+		uint32_t *qstatus, *bkey, *bval, *bkey2, *bval2, *bcnt, *boff, *tile_cnt, *tile_off;
+		unsigned long long *tot;
+		void *sort_tmp_a, *scan_tmp_a;
+		size_t sort_a = 0;
 		const size_t scan_a = scan_tmp_bytes(std::max<size_t>((size_t)nS + 1, n_tiles + 1)) + 256;
-		const size_t ws_b = Arena::padded(n1, 4) * 5 + Arena::padded(n1, 1) + Arena::padded(n2q, 4) * 4 +
-				    Arena::padded((size_t)nS + 1, 4) * 2 + Arena::padded(n_tiles + 1, 4) * 2 + Arena::padded(8, 8) +
-				    sort_a + scan_a + 16 * 256;
-		ctx->tr_ws.reserve(ws_b);
-		Arena &A = ctx->tr_ws;
-		uint32_t *d_qa = A.take<uint32_t>(n1), *d_qz = A.take<uint32_t>(n1), *ys = A.take<uint32_t>(n1), *yz = A.take<uint32_t>(n1);
-		uint32_t *qstatus = A.take<uint32_t>(n1);
-		uint8_t *d_qor = A.take<uint8_t>(n1);
-		uint32_t *bkey = A.take<uint32_t>(n2q), *bval = A.take<uint32_t>(n2q), *bkey2 = A.take<uint32_t>(n2q),
-			 *bval2 = A.take<uint32_t>(n2q);
-		uint32_t *bcnt = A.take<uint32_t>((size_t)nS + 1), *boff = A.take<uint32_t>((size_t)nS + 1);
-		uint32_t *tile_cnt = A.take<uint32_t>(n_tiles + 1), *tile_off = A.take<uint32_t>(n_tiles + 1);
-		uint32_t *words = A.take<uint32_t>(8);
-		unsigned long long *tot = A.take<unsigned long long>(2);
-		void *sort_tmp_a = A.take<char>(sort_a), *scan_tmp_a = A.take<char>(scan_a);
-
-		HIP_CHECK(hipEventCreate(&e0));
-		HIP_CHECK(hipEventCreate(&e1));
-		HIP_CHECK(hipEventRecord(e0, s));
-		HIP_CHECK(hipMemsetAsync(words, 0, 32, s));
+		const QueryFront q = query_front(ctx, f, ctx->tr_ws, timer, [&](Spans &take, uint32_t n) {
+			const size_t n2q = 2 * (size_t)n + 1;
+			sort_a = sort_tmp_bytes(n2q) + 256;
+			take((size_t)n + 1, qstatus);
+			take(n2q, bkey, bval, bkey2, bval2);
+			take((size_t)nS + 1, bcnt, boff);
+			take(n_tiles + 1, tile_cnt, tile_off);
+			take(2, tot);
+			take(sort_a, sort_tmp_a);
+			take(scan_a, scan_tmp_a);
+		});
+		const uint32_t n = q.n, *ys = q.ys, *yz = q.yz;
+		uint32_t *words = q.words;
+		const size_t n1 = (size_t)n + 1;
 		HIP_CHECK(hipMemsetAsync(qstatus, 0, n1 * 4, s));
 		HIP_CHECK(hipMemsetAsync(bcnt, 0, ((size_t)nS + 1) * 4, s));
-		if (n) {
-			HIP_CHECK(copy_async(d_qa, qa.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-			HIP_CHECK(copy_async(d_qz, qz.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-			HIP_CHECK(copy_async(d_qor, qor.data(), n, hipMemcpyHostToDevice, s));
-		}
-		launch_vid_ascending(g.V, g.vid, words, s);
-		launch_resolve(n, d_qa, d_qz, d_qor, g.vid, g.V, ys, yz, words, s);
 		uint32_t hw[8] = {0};
 		HIP_CHECK(copy_async(hw, words, 32, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
-		if (hw[0] & 1u)
-			throw HipError("traversals need segment ids that ascend with the vertex index (the order the GFA loader gives)");
-		if (hw[0] & 2u)
-			throw HipError("a flubble boundary of the forest is no segment of the resident graph");
+		query_refusals(hw[0], "traversals");
 		if (n) {
 			KLAUNCH(k_tr_keys, dim3(tblk(n)), dim3(T_TPB), 0, s, n, nS, ys, yz, bkey, bval, bcnt);
 			sort_pairs_u32(bkey, bkey2, bval, bval2, 2 * (size_t)n, bits_for(nS), sort_tmp_a, sort_a, s);
@@ -739,7 +682,8 @@ extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, po
 		if (n_tiles)
 			KLAUNCH(k_tr_count, dim3((unsigned)n_tiles), dim3(T_TPB), 0, s, N, ctx->path_steps, boff, tile_cnt);
 		HIP_CHECK(hipMemsetAsync(tile_cnt + n_tiles, 0, 4, s));
-		const uint64_t T64 = total_u32(tile_cnt, n_tiles, tot, s);
+		uint64_t T64 = 0;
+		totals_u32(tile_cnt, nullptr, n_tiles, tot, &T64, s);
 		check_32(T64, "scan tasks");
 		const uint32_t T = (uint32_t)T64;
 		scan_exclusive_u32(tile_cnt, tile_off, n_tiles + 1, scan_tmp_a, scan_a, s);
@@ -747,14 +691,15 @@ extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, po
 		// ---- phase B: the tasks, sorted by query, and their scans
 		const size_t T1 = (size_t)T + 1;
 		const size_t sort_b = sort_tmp_bytes(T1) + 256, comp_b = compact_tmp_bytes(T1) + 256;
-		ctx->tr_task.reserve(Arena::padded(T1, 8) * 3 + Arena::padded(T1, 4) * 6 + Arena::padded(T1, 1) * 2 + sort_b + comp_b +
-				     16 * 256);
-		Arena &B = ctx->tr_task;
-		uint64_t *tpos = B.take<uint64_t>(T1), *spos = B.take<uint64_t>(T1), *thash = B.take<uint64_t>(T1);
-		uint32_t *tkey = B.take<uint32_t>(T1), *tval = B.take<uint32_t>(T1), *sq = B.take<uint32_t>(T1), *perm = B.take<uint32_t>(T1),
-			 *tlen = B.take<uint32_t>(T1), *list = B.take<uint32_t>(T1);
-		uint8_t *handover = B.take<uint8_t>(T1), *closed = B.take<uint8_t>(T1);
-		void *sort_tmp_b = B.take<char>(sort_b), *comp_tmp_b = B.take<char>(comp_b);
+		uint64_t *tpos, *spos, *thash;
+		uint32_t *tkey, *tval, *sq, *perm, *tlen, *list;
+		uint8_t *handover, *closed;
+		void *sort_tmp_b, *comp_tmp_b;
+		carve(ctx->tr_task, [&](Spans &take) {
+			take(T1, tpos, spos, thash, tkey, tval, sq, perm, tlen, list, handover, closed);
+			take(sort_b, sort_tmp_b);
+			take(comp_b, comp_tmp_b);
+		});
 		uint32_t n2 = 0, R = 0;
 		ScanArgs SA{ctx->path_steps, ctx->path_off, P, ys, yz, max_steps, hbits >= 64 ? 0xFFFFFFFFu : hbits > 32 ? (1u << (hbits - 32)) - 1 : 0u,
 			    hbits >= 32 ? 0xFFFFFFFFu : (1u << hbits) - 1};
@@ -781,18 +726,20 @@ extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, po
 		// ---- phase C: the traversals, grouped into alleles
 		const size_t R1 = (size_t)R + 1;
 		const size_t sort_c = sort_tmp_bytes(R1) + 256, scan_c = scan_tmp_bytes(std::max(R1, n1)) + 256, comp_c = compact_tmp_bytes(R1) + 256;
-		ctx->tr_trav.reserve(Arena::padded(R1, 8) * 2 + Arena::padded(R1, 4) * 17 + Arena::padded(n1, 4) * 2 + Arena::padded(R1, 1) +
-				     sort_c + scan_c + comp_c + 32 * 256);
-		Arena &C = ctx->tr_trav;
-		uint64_t *rpos = C.take<uint64_t>(R1), *rhash = C.take<uint64_t>(R1);
-		uint32_t *rq = C.take<uint32_t>(R1), *rlen = C.take<uint32_t>(R1), *pa = C.take<uint32_t>(R1), *pb = C.take<uint32_t>(R1),
-			 *key = C.take<uint32_t>(R1), *kout = C.take<uint32_t>(R1), *mark = C.take<uint32_t>(R1), *hmax = C.take<uint32_t>(R1),
-			 *head = C.take<uint32_t>(R1), *rep = C.take<uint32_t>(R1), *firstf = C.take<uint32_t>(R1), *aidx = C.take<uint32_t>(R1),
-			 *rallele = C.take<uint32_t>(R1), *afirst = C.take<uint32_t>(R1), *alen = C.take<uint32_t>(R1),
-			 *soff = C.take<uint32_t>(R1), *blist = C.take<uint32_t>(R1);
-		uint32_t *toff = C.take<uint32_t>(n1), *aoff = C.take<uint32_t>(n1);
-		uint8_t *rbad = C.take<uint8_t>(R1);
-		void *sort_tmp_c = C.take<char>(sort_c), *scan_tmp_c = C.take<char>(scan_c), *comp_tmp_c = C.take<char>(comp_c);
+		uint64_t *rpos, *rhash;
+		uint32_t *rq, *rlen, *pa, *pb, *key, *kout, *mark, *hmax, *head, *rep, *firstf, *aidx, *rallele, *afirst, *alen, *soff, *blist;
+		uint32_t *toff, *aoff;
+		uint8_t *rbad;
+		void *sort_tmp_c, *scan_tmp_c, *comp_tmp_c;
+		carve(ctx->tr_trav, [&](Spans &take) {
+			take(R1, rpos, rhash, rq, rlen, pa, pb, key, kout, mark, hmax, head, rep);
+			take(R1, firstf, aidx, rallele, afirst, alen, soff, blist);
+			take(n1, toff, aoff);
+			take(R1, rbad);
+			take(sort_c, sort_tmp_c);
+			take(scan_c, scan_tmp_c);
+			take(comp_c, comp_tmp_c);
+		});
 		// (`list` of tr_task holds the traversals' task indices)
 		uint64_t n_splits = 0;
 		uint32_t n_al = 0;
@@ -838,21 +785,22 @@ extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, po
 			HIP_CHECK(hipMemsetAsync(aidx, 0, 4, s));
 		}
 		KLAUNCH(k_tr_allele_off, dim3(tblk(n1)), dim3(T_TPB), 0, s, n, toff, aidx, aoff);
-		const uint64_t n_steps = n_al ? total_u32(alen, n_al, tot, s) : 0;
+		uint64_t n_steps = 0;
+		if (n_al)
+			totals_u32(alen, nullptr, n_al, tot, &n_steps, s);
 		check_32(n_steps, "allele steps");
 		if (n_al) {
 			HIP_CHECK(hipMemsetAsync(alen + n_al, 0, 4, s));
 			scan_exclusive_u32(alen, soff, (size_t)n_al + 1, scan_tmp_c, scan_c, s);
 		}
 
-		// ---- outputs: per traversal in tr_task (its sort scratch is free now), allele steps in tr_steps
-		ctx->tr_steps.reserve(Arena::padded(R1, 4) * 4 + Arena::padded(R1, 1) + Arena::padded(n_steps + 1, 4) +
-				      Arena::padded(n_steps + 1, 1) + 8 * 256);
-		Arena &D = ctx->tr_steps;
-		uint32_t *op = D.take<uint32_t>(R1), *of = D.take<uint32_t>(R1), *ol = D.take<uint32_t>(R1), *oa = D.take<uint32_t>(R1);
-		uint8_t *orv = D.take<uint8_t>(R1);
-		uint32_t *sid = D.take<uint32_t>(n_steps + 1);
-		uint8_t *sor = D.take<uint8_t>(n_steps + 1);
+		// ---- outputs: per traversal and allele steps, in tr_steps
+		uint32_t *op, *of, *ol, *oa, *sid;
+		uint8_t *orv, *sor;
+		carve(ctx->tr_steps, [&](Spans &take) {
+			take(R1, op, of, ol, oa, orv);
+			take(n_steps + 1, sid, sor);
+		});
 		if (R)
 			KLAUNCH(k_tr_out, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, ctx->path_off, P, rq, rpos, rlen, rallele, aidx, toff, op, of, ol, oa, orv);
 		if (n_al)
@@ -862,35 +810,20 @@ extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, po
 		// ---- to the host
 		auto o = std::make_unique<TraversalsOwner>();
 		std::vector<uint32_t> h_toff(n1), h_aoff(n1), h_status(n1), h_soff((size_t)n_al + 1);
-		if (R) {
-			o->path.resize(R, ctx->pool);
-			o->first.resize(R, ctx->pool);
-			o->last.resize(R, ctx->pool);
-			o->allele.resize(R, ctx->pool);
-			o->reverse.resize(R, ctx->pool);
-			HIP_CHECK(copy_async(o->path.data(), op, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(o->first.data(), of, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(o->last.data(), ol, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(o->allele.data(), oa, (size_t)R * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(o->reverse.data(), orv, R, hipMemcpyDeviceToHost, s));
-		}
-		if (n_steps) {
-			o->step_id.resize(n_steps, ctx->pool);
-			o->step_or.resize(n_steps, ctx->pool);
-			HIP_CHECK(copy_async(o->step_id.data(), sid, n_steps * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(o->step_or.data(), sor, n_steps, hipMemcpyDeviceToHost, s));
-		}
+		hand_off(o->path, R, op, R, ctx);
+		hand_off(o->first, R, of, R, ctx);
+		hand_off(o->last, R, ol, R, ctx);
+		hand_off(o->allele, R, oa, R, ctx);
+		hand_off(o->reverse, R, orv, R, ctx);
+		hand_off(o->step_id, n_steps, sid, n_steps, ctx);
+		hand_off(o->step_or, n_steps, sor, n_steps, ctx);
 		HIP_CHECK(copy_async(h_toff.data(), toff, n1 * 4, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(copy_async(h_aoff.data(), aoff, n1 * 4, hipMemcpyDeviceToHost, s));
 		if (n)
 			HIP_CHECK(copy_async(h_status.data(), qstatus, (size_t)n * 4, hipMemcpyDeviceToHost, s));
 		if (n_al)
 			HIP_CHECK(copy_async(h_soff.data(), soff, ((size_t)n_al + 1) * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipEventRecord(e1, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		float ms = 0;
-		(void)hipEventElapsedTime(&ms, e0, e1);
-		drop_events();
+		o->view.device_ms = timer.stop(s);
 		o->trav_off.assign(h_toff.begin(), h_toff.end());
 		o->allele_off.assign(h_aoff.begin(), h_aoff.end());
 		o->status.resize(n);
@@ -914,18 +847,10 @@ extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, po
 		o->view.step_or = o->step_or.data();
 		o->view.n_tier2 = n2;
 		o->view.n_hash_splits = n_splits;
-		o->view.device_ms = ms;
 		TraversalsOwner *raw = o.release();
 		return &raw->view;
-	} catch (const std::exception &e) {
-		if (ctx && ctx->stream)
-			(void)hipStreamSynchronize(ctx->stream);
-		drop_events();
-		set_err(err, errlen, e.what());
-		return nullptr;
-	}
+	});
 }
-
 extern "C" void povu_hip_traversals_free(povu_hip_traversals *t)
 {
 	delete reinterpret_cast<TraversalsOwner *>(t);

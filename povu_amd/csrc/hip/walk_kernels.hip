@@ -73,84 +73,6 @@ __global__ void k_wk_slot_side(uint32_t nS, const uint32_t *__restrict__ off, ui
 		side_of[i] = x;
 }
 
-// ---- queries
-
-// segment ids must ascend with the vertex index (binary search; successor order = side order)
-__global__ void k_wk_vid_ascending(uint32_t V, const uint32_t *__restrict__ vid, uint32_t *__restrict__ bad)
-{
-	const uint32_t i = blockIdx.x * W_TPB + threadIdx.x;
-	if (i + 1 < V && vid[i] >= vid[i + 1])
-		atomicOr(bad, 1u);
-}
-
-// (id, orientation) of both boundaries -> entered sides; a query whose two boundaries are one segment has no walk (NO_QUERY)
-__global__ void k_wk_resolve(uint32_t n, const uint32_t *__restrict__ qa, const uint32_t *__restrict__ qz,
-			       const uint8_t *__restrict__ qor, const uint32_t *__restrict__ vid, uint32_t V, uint32_t *__restrict__ ys,
-			       uint32_t *__restrict__ yz, uint32_t *__restrict__ bad)
-{
-	const uint32_t q = blockIdx.x * W_TPB + threadIdx.x;
-	if (q >= n)
-		return;
-	const uint32_t a = find_vertex(vid, V, qa[q]), z = find_vertex(vid, V, qz[q]);
-	if (a == NO_QUERY || z == NO_QUERY) {
-		atomicOr(bad, 2u);
-		ys[q] = yz[q] = NO_QUERY;
-		return;
-	}
-	const uint8_t o = qor[q];
-	ys[q] = a == z ? NO_QUERY : 2 * a + (o & 1u);
-	yz[q] = a == z ? NO_QUERY : 2 * z + ((o >> 1) & 1u);
-}
-
-void launch_vid_ascending(uint32_t V, const uint32_t *vid, uint32_t *bad, hipStream_t s)
-{
-	KLAUNCH(k_wk_vid_ascending, dim3(wblk(V)), dim3(W_TPB), 0, s, V, vid, bad);
-}
-
-void launch_resolve(uint32_t n, const uint32_t *qa, const uint32_t *qz, const uint8_t *qor, const uint32_t *vid, uint32_t V,
-		    uint32_t *ys, uint32_t *yz, uint32_t *bad, hipStream_t s)
-{
-	if (n)
-		KLAUNCH(k_wk_resolve, dim3(wblk(n)), dim3(W_TPB), 0, s, n, qa, qz, qor, vid, V, ys, yz, bad);
-}
-
-void check_query_forest(const povu_hip_ctx *ctx, const povu_hip_forest *f, const char *what)
-{
-	if (!ctx || !f)
-		throw HipError("null context or forest");
-	if (!f->walk_ctx)
-		throw HipError(std::string(what) +
-			       " need a forest made by povu_hip_decompose of a whole resident graph (not a sharded, merged or attached forest)");
-	if (f->walk_ctx != ctx || !ctx->g.block || f->walk_gen != ctx->g.gen)
-		throw HipError("the forest was not decomposed from the graph now resident on this context (it was uploaded again, or the forest belongs to another context)");
-}
-
-void forest_queries(povu_hip_forest *f, std::vector<uint32_t> &qa, std::vector<uint32_t> &qz, std::vector<uint8_t> &qor)
-{
-	const uint32_t n_trees = (uint32_t)f->trees.size();
-	for (uint32_t i = 0; i < n_trees; i++) {
-		povu_hip_subtree st;
-		if (povu_hip_forest_get_subtree(f, i, &st) == 0) {
-			for (uint32_t v = 1; v < st.n_total; v++) {
-				qa.push_back(st.id1[v]);
-				qz.push_back(st.id2[v]);
-				qor.push_back((uint8_t)((st.or1[v] & 1u) | ((st.or2[v] & 1u) << 1)));
-			}
-			continue;
-		}
-		povu_hip_tree t;
-		if (povu_hip_forest_get(f, i, &t) != 0)
-			throw HipError("forest tree " + std::to_string(i) + " unreadable");
-		for (uint32_t v = 1; v < t.n_pvst; v++) {
-			qa.push_back(t.a_id[v]);
-			qz.push_back(t.z_id[v]);
-			qor.push_back((uint8_t)((t.a_or[v] & 1u) | ((t.z_or[v] & 1u) << 1)));
-		}
-	}
-	if (qa.size() >= 0xFFFFFFFFull)
-		throw HipError("too many queries for 32-bit indices");
-}
-
 // ---- the DFS (both tiers, both passes)
 
 struct DfsResult {
@@ -421,28 +343,6 @@ __global__ __launch_bounds__(W_TPB) void k_wk_t2(const uint32_t *__restrict__ li
 	}
 }
 
-// totals of walks and steps in 64 bits (the scans run in 32: the call is refused when a total does not fit)
-__global__ void k_wk_totals(uint32_t n, const uint32_t *__restrict__ cntw, const uint32_t *__restrict__ cnts,
-			      unsigned long long *__restrict__ tot)
-{
-	__shared__ unsigned long long sw, ss;
-	if (threadIdx.x == 0)
-		sw = ss = 0;
-	__syncthreads();
-	unsigned long long w = 0, s = 0;
-	for (uint32_t q = blockIdx.x * W_TPB + threadIdx.x; q < n; q += gridDim.x * W_TPB) {
-		w += cntw[q];
-		s += cnts[q];
-	}
-	atomicAdd(&sw, w);
-	atomicAdd(&ss, s);
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		atomicAdd(&tot[0], sw);
-		atomicAdd(&tot[1], ss);
-	}
-}
-
 } // namespace povu_hip
 
 // ---- C ABI
@@ -459,16 +359,8 @@ struct WalksOwner {
 extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_forest *f, const povu_hip_walk_opts *opts, char *err,
 						 size_t errlen)
 {
-	XferScope xfer(ctx);
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	auto drop_events = [&] {
-		if (e0)
-			(void)hipEventDestroy(e0);
-		if (e1)
-			(void)hipEventDestroy(e1);
-		e0 = e1 = nullptr;
-	};
-	try {
+	CallTimer timer;
+	return guarded_call(ctx, err, errlen, (povu_hip_walks *)nullptr, [&] {
 		check_query_forest(ctx, f, "walks");
 		WalkCaps c{64, 1000, 65536};
 		uint32_t flags = 0;
@@ -483,67 +375,46 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 		}
 		if (c.L > (1u << 24))
 			throw HipError("max_steps above 2^24");
-		HIP_CHECK(hipSetDevice(ctx->device));
-		ctx->wait_tail();
-		f->ready();
 		const ResidentGraph &g = ctx->g;
 		hipStream_t s = ctx->stream;
-
-		// ---- the queries, in tree order then PVST vertex order, roots skipped
-		std::vector<uint32_t> qa, qz;
-		std::vector<uint8_t> qor;
-		forest_queries(f, qa, qz, qor);
-		const uint32_t n = (uint32_t)qa.size();
 		const uint32_t nS = 2 * g.V;
 		const size_t slots = g.n_slots;
 
-		// ---- workspace: queries, counts, offsets, hand-over list, the sorted successors
+		// ---- the queries (tree order, then PVST vertex order, roots skipped); beside them counts, offsets, the hand-over
+		// list, the sorted successors
+		uint32_t *cntw, *cnts, *woff, *sbase, *list2, *ssucc;
+		uint8_t *status, *handover;
+		unsigned long long *tot;
+		void *scan_tmp, *comp_tmp;
+		size_t scan_b = 0, comp_b = 0;
+		const QueryFront q = query_front(ctx, f, ctx->wk_ws, timer, [&](Spans &take, uint32_t n) {
+			const size_t n1 = (size_t)n + 1;
+			scan_b = scan_tmp_bytes(n1) + 256, comp_b = compact_tmp_bytes(n1) + 256;
+			take(n1, cntw, cnts, woff, sbase, list2, status, handover);
+			take(2, tot);
+			take(scan_b, scan_tmp);
+			take(comp_b, comp_tmp);
+			take(slots + 8, ssucc);
+		});
+		const uint32_t n = q.n, *ys = q.ys, *yz = q.yz;
+		uint32_t *words = q.words;
 		const size_t n1 = (size_t)n + 1;
-		const size_t scan_b = scan_tmp_bytes(n1) + 256, comp_b = compact_tmp_bytes(n1) + 256;
-		const size_t ws_b = Arena::padded(n1, 4) * 9 + Arena::padded(n1, 1) * 3 + Arena::padded(8, 4) + scan_b + comp_b +
-				    Arena::padded(slots + 8, 4) + Arena::padded(2, 8) + 16 * 256;
-		ctx->wk_ws.reserve(ws_b);
-		Arena &A = ctx->wk_ws;
-		uint32_t *d_qa = A.take<uint32_t>(n1), *d_qz = A.take<uint32_t>(n1);
-		uint8_t *d_qor = A.take<uint8_t>(n1);
-		uint32_t *ys = A.take<uint32_t>(n1), *yz = A.take<uint32_t>(n1);
-		uint32_t *cntw = A.take<uint32_t>(n1), *cnts = A.take<uint32_t>(n1), *woff = A.take<uint32_t>(n1),
-			 *sbase = A.take<uint32_t>(n1), *list2 = A.take<uint32_t>(n1), *words = A.take<uint32_t>(8);
-		uint8_t *status = A.take<uint8_t>(n1), *handover = A.take<uint8_t>(n1);
-		unsigned long long *tot = A.take<unsigned long long>(2);
-		void *scan_tmp = A.take<char>(scan_b), *comp_tmp = A.take<char>(comp_b);
-		uint32_t *ssucc = A.take<uint32_t>(slots + 8);
-
-		HIP_CHECK(hipEventCreate(&e0));
-		HIP_CHECK(hipEventCreate(&e1));
-		HIP_CHECK(hipEventRecord(e0, s));
-		HIP_CHECK(hipMemsetAsync(words, 0, 8 * 4, s));
-		HIP_CHECK(hipMemsetAsync(tot, 0, 16, s));
-		if (n) {
-			HIP_CHECK(copy_async(d_qa, qa.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-			HIP_CHECK(copy_async(d_qz, qz.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-			HIP_CHECK(copy_async(d_qor, qor.data(), n, hipMemcpyHostToDevice, s));
-		}
-		// words: [0] vid not ascending | query boundary not found, [1] hand-over count, [2] / [3] tier-2 work counter of the
-		// count / emit pass, [4] a side has more than SORT_IN_LANE slots
-		launch_vid_ascending(g.V, g.vid, words, s);
-		launch_resolve(n, d_qa, d_qz, d_qor, g.vid, g.V, ys, yz, words, s);
+		// words: [0] the checks, [1] hand-over count, [2] / [3] tier-2 work counter of the count / emit pass, [4] a side has
+		// more than SORT_IN_LANE slots
 		if (nS)
 			KLAUNCH(k_wk_ssucc, dim3(wblk(nS)), dim3(W_TPB), 0, s, nS, g.off, g.aoth, ssucc, words + 4);
 		uint32_t hw[8] = {0};
 		HIP_CHECK(copy_async(hw, words, 32, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
-		if (hw[0] & 1u)
-			throw HipError("walks need segment ids that ascend with the vertex index (the order the GFA loader gives)");
-		if (hw[0] & 2u)
-			throw HipError("a flubble boundary of the forest is no segment of the resident graph");
+		query_refusals(hw[0], "walks");
 		if (hw[4] && slots) { // a hub side: every slot's (other end, side) pair, sorted by other end, then stably by side
 			const size_t sort_b = sort_tmp_bytes(slots) + 256;
-			ctx->wk_out.reserve(4 * Arena::padded(slots + 8, 4) + sort_b + 8 * 256); // (free until the count pass's tier 2)
-			Arena &B = ctx->wk_out;
-			uint32_t *side_of = B.take<uint32_t>(slots + 8), *k1 = B.take<uint32_t>(slots + 8), *v1 = B.take<uint32_t>(slots + 8),
-				 *k2 = B.take<uint32_t>(slots + 8);
-			void *sort_tmp = B.take<char>(sort_b);
+			uint32_t *side_of, *k1, *v1, *k2;
+			void *sort_tmp;
+			carve(ctx->wk_out, [&](Spans &take) { // (free until the count pass's tier 2)
+				take(slots + 8, side_of, k1, v1, k2);
+				take(sort_b, sort_tmp);
+			});
 			KLAUNCH(k_wk_slot_side, dim3(wblk(nS)), dim3(W_TPB), 0, s, nS, g.off, side_of);
 			const unsigned bits = bits_for(nS);
 			sort_pairs_u32(g.aoth, k1, side_of, v1, slots, bits, sort_tmp, sort_b, s);
@@ -566,20 +437,17 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 		uint32_t lanes = 0;
 		const uint32_t tbits = std::max(4u, bits_for(2 * (uint64_t)c.L - 1));
 		const size_t lane_words = (size_t)2 * c.L + (size_t(1) << tbits);
+		uint32_t *scratch = nullptr;
 		if (n2) {
 			lanes = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)n2, 16384, (size_t(256) << 20) / (lane_words * 4)}));
-			ctx->wk_out.reserve(Arena::padded((size_t)lanes * lane_words, 4) + 256);
-			uint32_t *scratch = ctx->wk_out.take<uint32_t>((size_t)lanes * lane_words);
+			carve(ctx->wk_out, [&](Spans &take) { take((size_t)lanes * lane_words, scratch); });
 			HIP_CHECK(hipMemsetAsync(scratch + (size_t)lanes * 2 * c.L, 0, (size_t)lanes * (lane_words - 2 * (size_t)c.L) * 4, s));
 			KLAUNCH(k_wk_t2<false>, dim3(wblk(lanes)), dim3(W_TPB), 0, s, list2, n2, words + 2, lanes, tbits, g.off, ssucc, ys, yz, c,
 				scratch, cntw, cnts, status, woff, sbase, none);
 		}
 		uint64_t ht[2] = {0, 0};
-		if (n) {
-			KLAUNCH(k_wk_totals, dim3(std::min<unsigned>(wblk(n), 1024)), dim3(W_TPB), 0, s, n, cntw, cnts, tot);
-			HIP_CHECK(copy_async(ht, tot, 16, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
-		}
+		if (n)
+			totals_u32(cntw, cnts, n, tot, ht, s);
 		const uint64_t n_walks = ht[0], n_steps = ht[1];
 		if (n_walks >= 0xFFFFFFFFull || n_steps >= 0xFFFFFFFFull)
 			throw HipError("the walks do not fit 32-bit offsets: " + std::to_string(n_walks) + " walks, " + std::to_string(n_steps) +
@@ -592,10 +460,13 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 			HIP_CHECK(hipMemsetAsync(cntw + n, 0, 4, s));
 			HIP_CHECK(hipMemsetAsync(cnts + n, 0, 4, s));
 			scan_exclusive_u32_pair(cntw, woff, n1, cnts, sbase, n1, scan_tmp, scan_b, s);
-			const size_t scratch_b = lanes ? Arena::padded((size_t)lanes * lane_words, 4) : 0;
-			const size_t out_b = scratch_b + Arena::padded(n_walks + 1, 4) + Arena::padded(n_steps + 1, 4) +
-					     Arena::padded(n_steps + 1, 1) + 4 * 256;
-			uint32_t *scratch = nullptr;
+			auto out = [&](Spans &take) {
+				if (lanes)
+					take((size_t)lanes * lane_words, scratch);
+				take(n_walks + 1, step_off);
+				take(n_steps + 1, step_id, step_or);
+			};
+			const size_t out_b = measure(out);
 			if (out_b > ctx->wk_out.capacity()) {
 				size_t free_b = 0, total_b = 0;
 				(void)hipMemGetInfo(&free_b, &total_b);
@@ -604,14 +475,9 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 						       std::to_string(free_b >> 20) + " MiB free");
 			}
 			HIP_CHECK(hipStreamSynchronize(s)); // (the count pass's tier 2 used the scratch of wk_out)
-			ctx->wk_out.reserve(out_b);
-			if (lanes) {
-				scratch = ctx->wk_out.take<uint32_t>((size_t)lanes * lane_words);
+			carve(ctx->wk_out, out);
+			if (lanes)
 				HIP_CHECK(hipMemsetAsync(scratch + (size_t)lanes * 2 * c.L, 0, (size_t)lanes * (lane_words - 2 * (size_t)c.L) * 4, s));
-			}
-			step_off = ctx->wk_out.take<uint32_t>(n_walks + 1);
-			step_id = ctx->wk_out.take<uint32_t>(n_steps + 1);
-			step_or = ctx->wk_out.take<uint8_t>(n_steps + 1);
 			WalkSink sink{step_off, step_id, step_or, g.vid, 0, 0, 0, 0};
 			KLAUNCH(k_wk_t1<true>, dim3(wblk(n)), dim3(W_TPB), 0, s, n, g.off, ssucc, ys, yz, c, 0u, cntw, cnts, status, handover,
 				woff, sbase, sink);
@@ -622,31 +488,15 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 
 		// ---- to the host
 		auto o = std::make_unique<WalksOwner>();
-		o->walk_off.resize(n1, ctx->pool);
-		o->step_off.resize(n_walks + 1, ctx->pool);
-		o->status.resize(n1, ctx->pool);
-		if (n_steps) {
-			o->step_id.resize(n_steps, ctx->pool);
-			o->step_or.resize(n_steps, ctx->pool);
-		}
-		if (n) {
-			HIP_CHECK(copy_async(o->walk_off.data(), woff, n1 * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(o->status.data(), status, n, hipMemcpyDeviceToHost, s));
-			if (n_walks)
-				HIP_CHECK(copy_async(o->step_off.data(), step_off, n_walks * 4, hipMemcpyDeviceToHost, s));
-			if (n_steps) {
-				HIP_CHECK(copy_async(o->step_id.data(), step_id, n_steps * 4, hipMemcpyDeviceToHost, s));
-				HIP_CHECK(copy_async(o->step_or.data(), step_or, n_steps, hipMemcpyDeviceToHost, s));
-			}
-		} else {
+		hand_off(o->walk_off, n1, woff, n ? n1 : 0, ctx);
+		hand_off(o->status, n1, status, n, ctx);
+		hand_off(o->step_off, n_walks + 1, step_off, n_walks, ctx);
+		hand_off(o->step_id, n_steps, step_id, n_steps, ctx);
+		hand_off(o->step_or, n_steps, step_or, n_steps, ctx);
+		if (!n)
 			o->walk_off[0] = 0;
-		}
-		HIP_CHECK(hipEventRecord(e1, s));
-		HIP_CHECK(hipStreamSynchronize(s));
+		o->view.device_ms = timer.stop(s);
 		o->step_off[n_walks] = (uint32_t)n_steps;
-		float ms = 0;
-		(void)hipEventElapsedTime(&ms, e0, e1);
-		drop_events();
 		o->view.n_queries = n;
 		o->view.n_walks = n_walks;
 		o->view.n_steps = n_steps;
@@ -656,18 +506,10 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 		o->view.step_or = o->step_or.data();
 		o->view.status = o->status.data();
 		o->view.n_tier2 = n2;
-		o->view.device_ms = ms;
 		WalksOwner *raw = o.release();
 		return &raw->view;
-	} catch (const std::exception &e) {
-		if (ctx && ctx->stream)
-			(void)hipStreamSynchronize(ctx->stream);
-		drop_events();
-		set_err(err, errlen, e.what());
-		return nullptr;
-	}
+	});
 }
-
 extern "C" void povu_hip_walks_free(povu_hip_walks *w)
 {
 	delete reinterpret_cast<WalksOwner *>(w);

@@ -269,17 +269,8 @@ std::vector<int> multi_devices(int gpus, const char *env, int visible)
 void write_traversals(povu_hip_ctx *ctx, povu_hip_forest *f, const std::vector<GfaPath> &paths, const Config &cfg, std::atomic<bool> &failed)
 {
 	char err[512] = {0};
-	std::vector<uint64_t> off(1, 0);
-	std::vector<uint32_t> ids;
-	std::vector<uint8_t> rev;
-	for (const auto &p : paths) {
-		ids.insert(ids.end(), p.step_ids.begin(), p.step_ids.end());
-		rev.insert(rev.end(), p.step_rev.begin(), p.step_rev.end());
-		off.push_back(ids.size());
-	}
-	if (paths.size() >= 0xFFFFFFFFull)
-		throw std::runtime_error("too many paths for the traversals");
-	if (povu_hip_paths_upload(ctx, (uint32_t)paths.size(), off.data(), ids.data(), rev.data(), err, sizeof err) != 0)
+	const FlatPaths fp = flatten_paths(paths);
+	if (povu_hip_paths_upload(ctx, (uint32_t)paths.size(), fp.off.data(), fp.ids.data(), fp.rev.data(), err, sizeof err) != 0)
 		throw std::runtime_error(std::string("povu_hip: ") + err);
 	povu_hip_traversals *tr = povu_hip_forest_traversals(ctx, f, nullptr, err, sizeof err);
 	if (!tr)

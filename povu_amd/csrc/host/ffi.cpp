@@ -29,27 +29,40 @@ struct PovuForest {
 	povu_hip_forest *f = nullptr;
 	~PovuForest() { povu_hip_forest_free(f); }
 };
+// A result of the whole forest, computed by the first get that succeeds: compute(err, errlen) returns it or null with a
+// message, which is kept in `err`; a failed computation is tried again by the next get
+template <class T>
+struct ComputeOnce {
+	std::mutex m;
+	T *value = nullptr;
+	std::string err;
+	template <class F>
+	const T *get(F &&compute)
+	{
+		std::lock_guard<std::mutex> lk(m);
+		if (!value) {
+			char e[512] = {0};
+			value = compute(e, sizeof e);
+			err = value ? std::string() : std::string(e);
+		}
+		return value;
+	}
+};
 struct PovuFlubbles {
 	PovuForest forest;
 	size_t pvst_vertices = 0;
 	PovuGraph *graph = nullptr;
-	// povu_flubbles_get: the context whose resident graph the forest was decomposed from (kept until povu_flubbles_free, its
-	// decompose workspaces given back), the first flubble index of every tree, and the walks of the whole forest, computed by
-	// the first get that succeeds (a failed computation is tried again by the next get; its message is kept in walks_err)
+	// the context whose resident graph the forest was decomposed from (kept until povu_flubbles_free, its decompose
+	// workspaces given back), the first flubble index of every tree, the walks of the whole forest (povu_flubbles_get) and
+	// its traversals by the graph's paths, made resident on ctx first (povu_flubbles_get_traversals)
 	povu_hip_ctx *ctx = nullptr;
 	std::vector<size_t> tree_first;
-	std::mutex walks_m;
-	povu_hip_walks *walks = nullptr;
-	std::string walks_err;
-	// povu_flubbles_get_traversals: the graph's paths made resident on ctx and the traversals of the whole forest, computed
-	// by the first call that succeeds (under their own mutex, like the walks)
-	std::mutex trav_m;
-	povu_hip_traversals *trav = nullptr;
-	std::string trav_err;
+	ComputeOnce<povu_hip_walks> walks;
+	ComputeOnce<povu_hip_traversals> trav;
 	~PovuFlubbles()
 	{
-		povu_hip_traversals_free(trav);
-		povu_hip_walks_free(walks);
+		povu_hip_traversals_free(trav.value);
+		povu_hip_walks_free(walks.value);
 		povu_hip_forest_free(forest.f);
 		forest.f = nullptr;
 		povu_hip_destroy(ctx);
@@ -358,16 +371,8 @@ PovuFlubble *povu_flubbles_get(const PovuFlubbles *cf, size_t index)
 		return nullptr;
 	auto *f = const_cast<PovuFlubbles *>(cf);
 	try {
-		const povu_hip_walks *w = nullptr;
-		{
-			std::lock_guard<std::mutex> lk(f->walks_m);
-			if (!f->walks) {
-				char err[512] = {0};
-				f->walks = povu_hip_forest_walks(f->ctx, f->forest.f, nullptr, err, sizeof err);
-				f->walks_err = f->walks ? std::string() : std::string(err);
-			}
-			w = f->walks;
-		}
+		const povu_hip_walks *w =
+			f->walks.get([&](char *err, size_t errlen) { return povu_hip_forest_walks(f->ctx, f->forest.f, nullptr, err, errlen); });
 		if (!w)
 			return nullptr;
 		const size_t t = (size_t)(std::upper_bound(f->tree_first.begin(), f->tree_first.end(), index) - f->tree_first.begin()) - 1;
@@ -433,32 +438,13 @@ PovuFlubbleTraversals *povu_flubbles_get_traversals(const PovuFlubbles *cf, size
 		return nullptr;
 	auto *f = const_cast<PovuFlubbles *>(cf);
 	try {
-		const povu_hip_traversals *tr = nullptr;
-		{
-			std::lock_guard<std::mutex> lk(f->trav_m);
-			if (!f->trav) {
-				char err[512] = {0};
-				const auto &paths = f->graph->paths;
-				std::vector<uint64_t> off(1, 0);
-				std::vector<uint32_t> ids;
-				std::vector<uint8_t> rev;
-				bool fits = paths.size() < 0xFFFFFFFFull;
-				for (const auto &p : paths) {
-					for (uint64_t id : p.step_ids) {
-						fits &= id <= 0xFFFFFFFEull;
-						ids.push_back((uint32_t)id);
-					}
-					rev.insert(rev.end(), p.step_rev.begin(), p.step_rev.end());
-					off.push_back(ids.size());
-				}
-				if (!fits)
-					return nullptr;
-				if (povu_hip_paths_upload(f->ctx, (uint32_t)paths.size(), off.data(), ids.data(), rev.data(), err, sizeof err) == 0)
-					f->trav = povu_hip_forest_traversals(f->ctx, f->forest.f, nullptr, err, sizeof err);
-				f->trav_err = f->trav ? std::string() : std::string(err);
-			}
-			tr = f->trav;
-		}
+		const povu_hip_traversals *tr = f->trav.get([&](char *err, size_t errlen) -> povu_hip_traversals * {
+			const auto &paths = f->graph->paths;
+			const povu_host::FlatPaths fp = povu_host::flatten_paths(paths);
+			if (povu_hip_paths_upload(f->ctx, (uint32_t)paths.size(), fp.off.data(), fp.ids.data(), fp.rev.data(), err, errlen) != 0)
+				return nullptr;
+			return povu_hip_forest_traversals(f->ctx, f->forest.f, nullptr, err, errlen);
+		});
 		if (!tr)
 			return nullptr;
 		const size_t q = index - 1;

@@ -513,4 +513,23 @@ GfaGraph load_gfa(const std::string &fp, bool want_labels, bool want_paths, int 
 	return g;
 }
 
+FlatPaths flatten_paths(const std::vector<GfaPath> &paths)
+{
+	if (paths.size() >= 0xFFFFFFFFull)
+		throw std::runtime_error("too many paths for the traversals");
+	FlatPaths fp;
+	fp.off.reserve(paths.size() + 1);
+	fp.off.push_back(0);
+	for (const auto &p : paths) {
+		for (uint64_t id : p.step_ids) {
+			if (id > 0xFFFFFFFEull)
+				throw std::runtime_error("path '" + p.name + "': step id " + std::to_string(id) + " does not fit 32 bits");
+			fp.ids.push_back((uint32_t)id);
+		}
+		fp.rev.insert(fp.rev.end(), p.step_rev.begin(), p.step_rev.end());
+		fp.off.push_back(fp.ids.size());
+	}
+	return fp;
+}
+
 } // namespace povu_host

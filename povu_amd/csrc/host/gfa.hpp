@@ -86,4 +86,13 @@ struct GfaScratch {
 GfaGraph load_gfa(const std::string &path, bool want_labels = false, bool want_paths = false, int threads = 1,
 		  const std::function<void(size_t, size_t)> &on_counts = nullptr, GfaScratch *keep = nullptr);
 
+// The steps of `paths` side by side, as povu_hip_paths_upload takes them: off [paths + 1], ids and rev [steps].  Throws when
+// there are 2^32 - 1 paths or more, or a step id does not fit 32 bits (0xFFFFFFFF is no segment id).
+struct FlatPaths {
+	std::vector<uint64_t> off;
+	std::vector<uint32_t> ids;
+	std::vector<uint8_t> rev;
+};
+FlatPaths flatten_paths(const std::vector<GfaPath> &paths);
+
 } // namespace povu_host

@@ -458,29 +458,19 @@ class Forest:
         return out
 
 
-class Walks:
-    """Walks of every query of a forest (HipDecomposer.walks): numpy views of the flat arrays of povu_hip_forest_walks --
-    walk_off [n_queries + 1], step_off [n_walks + 1], step_id / step_or [n_steps], status [n_queries] -- valid as long as
-    this object lives.  Queries are numbered in tree order, then PVST vertex order within the tree, each root skipped."""
+def _view(p, n: int, dt):
+    """numpy view of the n elements at C pointer p (an empty array when n is 0: p may then be null)."""
+    return np.ctypeslib.as_array(p, shape=(n,)) if n else np.zeros(0, dt)
+
+
+class _PerQuery:
+    """Results of every query of a forest: queries are numbered in tree order, then PVST vertex order within the tree, each
+    root skipped (first_query: query number of PVST vertex 1 of every tree, _query_firsts)."""
 
     def __init__(self, lib, ptr, forest: "Forest", first_query: List[int]):
         self._lib, self._p = lib, ptr
-        w = ptr.contents
-        self.n_queries, self.n_walks, self.n_steps = int(w.n_queries), int(w.n_walks), int(w.n_steps)
-        self.n_tier2, self.device_ms = int(w.n_tier2), float(w.device_ms)
-        view = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)) if n else np.zeros(0, dt)  # noqa: E731
-        self.walk_off = view(w.walk_off, self.n_queries + 1, np.uint32)
-        self.step_off = view(w.step_off, self.n_walks + 1, np.uint32)
-        self.step_id = view(w.step_id, self.n_steps, np.uint32)
-        self.step_or = view(w.step_or, self.n_steps, np.uint8)
-        self.status = view(w.status, self.n_queries, np.uint8)
-        self._first = first_query  # query number of PVST vertex 1 of every tree
+        self._first = first_query
         self._forest = forest
-
-    def __del__(self):
-        if getattr(self, "_p", None):
-            self._lib.povu_hip_walks_free(self._p)
-            self._p = None
 
     def query(self, tree_index: int, pvst_vertex: int) -> int:
         """Query number of a PVST vertex (not the root)."""
@@ -488,6 +478,28 @@ class Walks:
         if not 1 <= pvst_vertex <= n:
             raise IndexError((tree_index, pvst_vertex))
         return self._first[tree_index] + pvst_vertex - 1
+
+
+class Walks(_PerQuery):
+    """Walks of every query of a forest (HipDecomposer.walks): numpy views of the flat arrays of povu_hip_forest_walks --
+    walk_off [n_queries + 1], step_off [n_walks + 1], step_id / step_or [n_steps], status [n_queries] -- valid as long as
+    this object lives."""
+
+    def __init__(self, lib, ptr, forest: "Forest", first_query: List[int]):
+        super().__init__(lib, ptr, forest, first_query)
+        w = ptr.contents
+        self.n_queries, self.n_walks, self.n_steps = int(w.n_queries), int(w.n_walks), int(w.n_steps)
+        self.n_tier2, self.device_ms = int(w.n_tier2), float(w.device_ms)
+        self.walk_off = _view(w.walk_off, self.n_queries + 1, np.uint32)
+        self.step_off = _view(w.step_off, self.n_walks + 1, np.uint32)
+        self.step_id = _view(w.step_id, self.n_steps, np.uint32)
+        self.step_or = _view(w.step_or, self.n_steps, np.uint8)
+        self.status = _view(w.status, self.n_queries, np.uint8)
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            self._lib.povu_hip_walks_free(self._p)
+            self._p = None
 
     def walks_of_query(self, q: int):
         out = []
@@ -517,44 +529,34 @@ def _query_firsts(lib, forest: "Forest") -> List[int]:
     return first
 
 
-class Traversals:
+class Traversals(_PerQuery):
     """Traversals of every query of a forest by the resident paths (HipDecomposer.traversals): numpy views of the flat
     arrays of povu_hip_forest_traversals -- trav_off / allele_off [n_queries + 1], status [n_queries], path / first / last /
     allele / reverse [n_traversals], step_off [n_alleles + 1], step_id / step_or [n_steps] -- valid as long as this object
-    lives.  Queries are numbered like those of Walks."""
+    lives."""
 
     def __init__(self, lib, ptr, forest: "Forest", first_query: List[int]):
-        self._lib, self._p = lib, ptr
+        super().__init__(lib, ptr, forest, first_query)
         t = ptr.contents
         self.n_queries, self.n_traversals = int(t.n_queries), int(t.n_traversals)
         self.n_alleles, self.n_steps = int(t.n_alleles), int(t.n_steps)
         self.n_tier2, self.n_hash_splits, self.device_ms = int(t.n_tier2), int(t.n_hash_splits), float(t.device_ms)
-        view = lambda p, n, dt: np.ctypeslib.as_array(p, shape=(n,)) if n else np.zeros(0, dt)  # noqa: E731
-        self.trav_off = view(t.trav_off, self.n_queries + 1, np.uint64)
-        self.allele_off = view(t.allele_off, self.n_queries + 1, np.uint64)
-        self.status = view(t.status, self.n_queries, np.uint8)
-        self.path = view(t.path, self.n_traversals, np.uint32)
-        self.first = view(t.first, self.n_traversals, np.uint32)
-        self.last = view(t.last, self.n_traversals, np.uint32)
-        self.allele = view(t.allele, self.n_traversals, np.uint32)
-        self.reverse = view(t.reverse, self.n_traversals, np.uint8)
-        self.step_off = view(t.step_off, self.n_alleles + 1, np.uint64)
-        self.step_id = view(t.step_id, self.n_steps, np.uint32)
-        self.step_or = view(t.step_or, self.n_steps, np.uint8)
-        self._first = first_query
-        self._forest = forest
+        self.trav_off = _view(t.trav_off, self.n_queries + 1, np.uint64)
+        self.allele_off = _view(t.allele_off, self.n_queries + 1, np.uint64)
+        self.status = _view(t.status, self.n_queries, np.uint8)
+        self.path = _view(t.path, self.n_traversals, np.uint32)
+        self.first = _view(t.first, self.n_traversals, np.uint32)
+        self.last = _view(t.last, self.n_traversals, np.uint32)
+        self.allele = _view(t.allele, self.n_traversals, np.uint32)
+        self.reverse = _view(t.reverse, self.n_traversals, np.uint8)
+        self.step_off = _view(t.step_off, self.n_alleles + 1, np.uint64)
+        self.step_id = _view(t.step_id, self.n_steps, np.uint32)
+        self.step_or = _view(t.step_or, self.n_steps, np.uint8)
 
     def __del__(self):
         if getattr(self, "_p", None):
             self._lib.povu_hip_traversals_free(self._p)
             self._p = None
-
-    def query(self, tree_index: int, pvst_vertex: int) -> int:
-        """Query number of a PVST vertex (not the root)."""
-        n = (self._first[tree_index + 1] if tree_index + 1 < len(self._first) else self.n_queries) - self._first[tree_index]
-        if not 1 <= pvst_vertex <= n:
-            raise IndexError((tree_index, pvst_vertex))
-        return self._first[tree_index] + pvst_vertex - 1
 
     def of_query(self, q: int):
         alleles = []
@@ -758,17 +760,7 @@ class HipDecomposer:
         p = self._lib.povu_hip_forest_walks(self._ctx, forest._h, C.byref(o), err, 512)
         if not p:
             raise RuntimeError(err.value.decode())
-        first, q = [], 0
-        st = _SubTree()
-        t = _Tree()
-        for i in range(len(forest)):
-            first.append(q)
-            if self._lib.povu_hip_forest_get_subtree(forest._h, i, C.byref(st)) == 0:
-                q += st.n_total - 1
-            else:
-                self._lib.povu_hip_forest_get(forest._h, i, C.byref(t))
-                q += t.n_pvst - 1
-        return Walks(self._lib, p, forest, first)
+        return Walks(self._lib, p, forest, _query_firsts(self._lib, forest))
 
     def upload_paths(self, paths) -> None:
         """Makes the paths of the graph now uploaded resident (povu_hip_paths_upload): a workloads.Paths record, or a
