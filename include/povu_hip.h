@@ -404,6 +404,60 @@ povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, povu_hip_fore
 						size_t errlen);
 void povu_hip_traversals_free(povu_hip_traversals *t);
 
+/* ---- variant calls ("Variant calls": decided here, not reference behaviour) ----
+ * Makes the sequences of the graph now uploaded resident beside it: segment of vertex index v (ascending segment id) has
+ * the bytes seq[seq_off[v] .. seq_off[v + 1]).  The next povu_hip_graph_upload drops them.  Refused when `n_vtx` is not the
+ * resident graph's vertex count or the offsets decrease.  0 on success */
+int povu_hip_segments_upload(povu_hip_ctx *ctx, uint32_t n_vtx, const uint64_t *seq_off, const char *seq, char *err, size_t errlen);
+/* the PVST vertices to call, one query each, in tree order then vertex order (the queries of povu_hip_forest_walks) */
+typedef struct {
+	uint32_t n;
+	const uint32_t *id1, *id2; /* boundary segment ids */
+	const uint8_t *or1, *or2;  /* 0 '>', 1 '<' */
+	const uint32_t *parent;	   /* query of the parent vertex, POVU_HIP_NIL for a child of the root */
+	const uint32_t *height;	   /* PVST height, the root's children 1 (LV = height - 1) */
+	const uint8_t *family;	   /* line letter: 'F', or 'T' 'O' 'C' 'M' 'S' (a subflubble: skipped with its subtree) */
+	const uint32_t *tree;	   /* tree of the vertex (presence of the reference paths is per tree) */
+} povu_hip_sites;
+/* the reference paths (ascending path indices) and the genotype slots: slot of every resident path, sample of every slot
+ * (slots of a sample are consecutive) */
+typedef struct {
+	uint32_t n_refs;
+	const uint32_t *ref_path;
+	uint32_t n_slots, n_samples;
+	const uint32_t *sample_of_slot;
+} povu_hip_call_refs;
+#define POVU_HIP_CALL_ANCHORED 1u /* record flags */
+#define POVU_HIP_CALL_TANGLED 2u
+#define POVU_HIP_CALL_INS 4u
+#define POVU_HIP_CALL_DEL 8u /* neither INS nor DEL: SUB */
+#define POVU_HIP_GT_MISSING 0xFFFFu
+typedef struct {
+	uint64_t n_records, n_slots, n_blocks, n_spelled, n_seq_bytes, n_at_bytes, n_refs;
+	/* per record, in (reference path, POS, query) order */
+	const uint32_t *query, *path, *first, *ref_allele, *n_alleles, *an, *ns, *block;
+	const uint64_t *pos;
+	const uint8_t *flags;	 /* POVU_HIP_CALL_* */
+	const uint64_t *ac_off;	 /* [n_records + 1] AC of ALT i (1-based) of record r: ac[ac_off[r] + i - 1] */
+	const uint32_t *ac;
+	const uint16_t *gt;	 /* [n_records * n_slots] allele in record numbering (REF 0), POVU_HIP_GT_MISSING for '.' */
+	/* the alleles of a query spelled in one orientation ("block", the query and the orientation its records need): allele
+	 * a of the block's query is spelled allele block_off[b] + a */
+	const uint64_t *block_off; /* [n_blocks + 1] */
+	const uint64_t *seq_off, *at_off; /* [n_spelled + 1] byte offsets into seq / at */
+	const char *seq, *at;	   /* the bases (anchor base first when anchored) and the AT step strings ('>id<id...') */
+	const uint64_t *contig_len; /* [n_refs] bases of every reference path */
+	double device_ms;
+} povu_hip_calls;
+/* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
+ * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
+ * site's boundary is no segment of the graph, for a query of more than 65 534 alleles in a called site, 2^32 records or
+ * more, a spelled byte that is no nucleotide code (the message names the segment), and output beyond device memory.  Free
+ * with povu_hip_calls_free. */
+povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+			      const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, char *err, size_t errlen);
+void povu_hip_calls_free(povu_hip_calls *c);
+
 /*
  * Serialises tree `i` exactly as mto::to_pvst::write_pvst does
  * (src/mto/to_pvst.cpp:23-109).  Returns a malloc'd buffer (free with

@@ -338,6 +338,13 @@ struct povu_hip_ctx {
 	// povu_hip_forest_traversals (trav_kernels.hip): queries and the boundary table / scan tasks / traversals and dedup /
 	// allele steps
 	Arena tr_ws, tr_task, tr_trav, tr_steps;
+	// povu_hip_segments_upload: the sequences of the resident graph (u64 offsets by vertex index, then the bytes), of upload
+	// `seq_gen`; povu_hip_call's workspace and outputs (call_kernels.hip)
+	Arena seq_buf, cl_ws, cl_slot, cl_rec, cl_spell, cl_bytes;
+	uint64_t *seq_off = nullptr;
+	char *seq = nullptr;
+	uint64_t seq_gen = 0;
+	bool seq_valid = false;
 	Arena part_arena;  // the packed shards of the last povu_hip_shard_partition (kept warm: a step of a sharded job re-partitions)
 	// bytes this context moved over PCIe / to peers since it was created (povu_hip_transfer_bytes)
 	uint64_t xfer_h2d = 0, xfer_d2h = 0, xfer_peer_out = 0, xfer_peer_in = 0;

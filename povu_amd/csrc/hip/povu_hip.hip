@@ -189,6 +189,11 @@ extern "C" int povu_hip_release_workspace(povu_hip_ctx *ctx)
 	ctx->tr_task.release();
 	ctx->tr_trav.release();
 	ctx->tr_steps.release();
+	ctx->cl_ws.release();
+	ctx->cl_slot.release();
+	ctx->cl_rec.release();
+	ctx->cl_spell.release();
+	ctx->cl_bytes.release();
 	return 0;
 }
 

@@ -84,11 +84,21 @@ QueryFront query_front(povu_hip_ctx *ctx, povu_hip_forest *f, Arena &A, CallTime
 	HIP_CHECK(hipSetDevice(ctx->device));
 	ctx->wait_tail();
 	f->ready();
-	const ResidentGraph &g = ctx->g;
-	const hipStream_t s = ctx->stream;
 	std::vector<uint32_t> qa, qz;
 	std::vector<uint8_t> qor;
 	forest_queries(f, qa, qz, qor);
+	return query_front(ctx, std::move(qa), std::move(qz), std::move(qor), A, timer, more);
+}
+
+QueryFront query_front(povu_hip_ctx *ctx, std::vector<uint32_t> qa, std::vector<uint32_t> qz, std::vector<uint8_t> qor, Arena &A,
+		       CallTimer &timer, const QueryLayout &more)
+{
+	HIP_CHECK(hipSetDevice(ctx->device));
+	ctx->wait_tail();
+	if (qa.size() >= 0xFFFFFFFFull)
+		throw HipError("too many queries for 32-bit indices");
+	const ResidentGraph &g = ctx->g;
+	const hipStream_t s = ctx->stream;
 	QueryFront q;
 	q.n = (uint32_t)qa.size();
 	const size_t n1 = (size_t)q.n + 1;
@@ -99,6 +109,8 @@ QueryFront query_front(povu_hip_ctx *ctx, povu_hip_forest *f, Arena &A, CallTime
 		take(8, q.words);
 		more(take, q.n);
 	});
+	q.qa = d_qa;
+	q.qz = d_qz;
 	q.ys = ys;
 	q.yz = yz;
 

@@ -69,6 +69,7 @@ private:
 // The device side of a forest's queries (query_front)
 struct QueryFront {
 	uint32_t n = 0;			      // queries
+	const uint32_t *qa = nullptr, *qz = nullptr; // [n + 1] segment ids of both boundaries
 	const uint32_t *ys = nullptr, *yz = nullptr; // [n + 1] entered sides of both boundaries, NO_QUERY for a query whose
 						      // boundaries are one segment
 	uint32_t *words = nullptr;		      // [8] cleared: word 0 takes the checks' bits (query_refusals), 1..7 are the caller's
@@ -80,6 +81,9 @@ using QueryLayout = std::function<void(Spans &take, uint32_t n)>;
 // both checks enqueued.  Nothing is waited for: the caller reads `words` back with what it enqueues behind them and hands
 // word 0 to query_refusals.
 QueryFront query_front(povu_hip_ctx *ctx, povu_hip_forest *f, Arena &A, CallTimer &timer, const QueryLayout &more);
+// ... of explicit queries: per query the S id, the Z id and or1 | or2 << 1 (povu_hip_call's sites)
+QueryFront query_front(povu_hip_ctx *ctx, std::vector<uint32_t> qa, std::vector<uint32_t> qz, std::vector<uint8_t> qor, Arena &A,
+		       CallTimer &timer, const QueryLayout &more);
 // the refusals of the checks, from bits of word 0 (bit 0: vid does not ascend, bit 1: a boundary is no segment of the graph);
 // `what` names the caller in the first ("walks", "traversals", "paths")
 void query_refusals(uint32_t word0, const char *what);
@@ -108,5 +112,22 @@ void hand_off(PinnedVec<T> &v, size_t size, const T *dev, size_t n, povu_hip_ctx
 	if (n)
 		HIP_CHECK(copy_async(v.data(), dev, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
 }
+
+// The traversal pipeline of povu_hip_forest_traversals behind a query front end (`front` carves the queries from the
+// traversals' first arena): its refusals of the options and of missing paths, its kernels, and its results left on the
+// device in the context's traversal arenas (valid until the next traversal call on the context).  Per query: toff, aoff
+// (u32 offsets), qstatus; per traversal (in (query, path, first) order): rq (query), op (path), of / ol (first / last step),
+// oa (allele within the query), orv (reverse), rpos (global position of its first step | ROLE_BIT when reverse), rlen
+// (steps); per allele: afirst (its first traversal), soff (u32 step offsets); per allele step: sid (segment id), sor.
+using QueryFrontFn = std::function<QueryFront(CallTimer &timer, const QueryLayout &more)>;
+struct TravDevice {
+	QueryFront q;
+	uint32_t R = 0, n_al = 0, n2 = 0;
+	uint64_t n_steps = 0, n_splits = 0;
+	uint32_t *op, *of, *ol, *oa, *sid, *toff, *aoff, *qstatus, *soff, *rq, *rlen, *afirst;
+	uint8_t *orv, *sor;
+	uint64_t *rpos;
+};
+TravDevice trav_pipeline(povu_hip_ctx *ctx, const QueryFrontFn &front, const povu_hip_trav_opts *opts, CallTimer &timer);
 
 } // namespace povu_hip

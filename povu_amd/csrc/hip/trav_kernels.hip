@@ -622,207 +622,230 @@ struct TraversalsOwner {
 };
 } // namespace
 
+namespace povu_hip
+{
+TravDevice trav_pipeline(povu_hip_ctx *ctx, const QueryFrontFn &front, const povu_hip_trav_opts *opts, CallTimer &timer)
+{
+	if (!ctx->paths_valid || ctx->paths_gen != ctx->g.gen)
+		throw HipError("no paths are resident for the graph now uploaded (povu_hip_paths_upload after povu_hip_graph_upload)");
+	uint32_t max_steps = 65536, flags = 0;
+	if (opts) {
+		if (opts->max_steps == 1)
+			throw HipError("max_steps must be at least 2");
+		if (opts->max_steps)
+			max_steps = opts->max_steps;
+		flags = opts->flags;
+	}
+	const uint32_t hbits = hash_bits_hook();
+	const ResidentGraph &g = ctx->g;
+	hipStream_t s = ctx->stream;
+	const uint64_t N = ctx->n_path_steps;
+	const uint32_t P = ctx->n_paths, nS = 2 * g.V;
+	const uint64_t n_tiles = (N + T_TILE - 1) / T_TILE;
+	check_32(n_tiles + 1, "start-task tiles");
+
+	// ---- phase A: queries, the boundary table, tile counts
+	uint32_t *qstatus, *bkey, *bval, *bkey2, *bval2, *bcnt, *boff, *tile_cnt, *tile_off;
+	unsigned long long *tot;
+	void *sort_tmp_a, *scan_tmp_a;
+	size_t sort_a = 0;
+	const size_t scan_a = scan_tmp_bytes(std::max<size_t>((size_t)nS + 1, n_tiles + 1)) + 256;
+	const QueryFront q = front(timer, [&](Spans &take, uint32_t n) {
+		const size_t n2q = 2 * (size_t)n + 1;
+		sort_a = sort_tmp_bytes(n2q) + 256;
+		take((size_t)n + 1, qstatus);
+		take(n2q, bkey, bval, bkey2, bval2);
+		take((size_t)nS + 1, bcnt, boff);
+		take(n_tiles + 1, tile_cnt, tile_off);
+		take(2, tot);
+		take(sort_a, sort_tmp_a);
+		take(scan_a, scan_tmp_a);
+	});
+	const uint32_t n = q.n, *ys = q.ys, *yz = q.yz;
+	uint32_t *words = q.words;
+	const size_t n1 = (size_t)n + 1;
+	HIP_CHECK(hipMemsetAsync(qstatus, 0, n1 * 4, s));
+	HIP_CHECK(hipMemsetAsync(bcnt, 0, ((size_t)nS + 1) * 4, s));
+	uint32_t hw[8] = {0};
+	HIP_CHECK(copy_async(hw, words, 32, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	query_refusals(hw[0], "traversals");
+	if (n) {
+		KLAUNCH(k_tr_keys, dim3(tblk(n)), dim3(T_TPB), 0, s, n, nS, ys, yz, bkey, bval, bcnt);
+		sort_pairs_u32(bkey, bkey2, bval, bval2, 2 * (size_t)n, bits_for(nS), sort_tmp_a, sort_a, s);
+	}
+	scan_exclusive_u32(bcnt, boff, (size_t)nS + 1, scan_tmp_a, scan_a, s);
+
+	// ---- start tasks: count per tile, scan, emit
+	if (n_tiles)
+		KLAUNCH(k_tr_count, dim3((unsigned)n_tiles), dim3(T_TPB), 0, s, N, ctx->path_steps, boff, tile_cnt);
+	HIP_CHECK(hipMemsetAsync(tile_cnt + n_tiles, 0, 4, s));
+	uint64_t T64 = 0;
+	totals_u32(tile_cnt, nullptr, n_tiles, tot, &T64, s);
+	check_32(T64, "scan tasks");
+	const uint32_t T = (uint32_t)T64;
+	scan_exclusive_u32(tile_cnt, tile_off, n_tiles + 1, scan_tmp_a, scan_a, s);
+
+	// ---- phase B: the tasks, sorted by query, and their scans
+	const size_t T1 = (size_t)T + 1;
+	const size_t sort_b = sort_tmp_bytes(T1) + 256, comp_b = compact_tmp_bytes(T1) + 256;
+	uint64_t *tpos, *spos, *thash;
+	uint32_t *tkey, *tval, *sq, *perm, *tlen, *list;
+	uint8_t *handover, *closed;
+	void *sort_tmp_b, *comp_tmp_b;
+	carve(ctx->tr_task, [&](Spans &take) {
+		take(T1, tpos, spos, thash, tkey, tval, sq, perm, tlen, list, handover, closed);
+		take(sort_b, sort_tmp_b);
+		take(comp_b, comp_tmp_b);
+	});
+	uint32_t n2 = 0, R = 0;
+	ScanArgs SA{ctx->path_steps, ctx->path_off, P, ys, yz, max_steps, hbits >= 64 ? 0xFFFFFFFFu : hbits > 32 ? (1u << (hbits - 32)) - 1 : 0u,
+		    hbits >= 32 ? 0xFFFFFFFFu : (1u << hbits) - 1};
+	ScanOut SO{tlen, thash, qstatus};
+	if (T) {
+		KLAUNCH(k_tr_emit, dim3((unsigned)n_tiles), dim3(T_TPB), 0, s, N, ctx->path_steps, boff, bval2, tile_off, tpos, tkey);
+		KLAUNCH(k_tr_iota, dim3(tgrid(T)), dim3(T_TPB), 0, s, T, tval);
+		sort_pairs_u32(tkey, sq, tval, perm, T, bits_for(n), sort_tmp_b, sort_b, s);
+		KLAUNCH(k_tr_gather64, dim3(tgrid(T)), dim3(T_TPB), 0, s, T, perm, tpos, spos);
+		KLAUNCH(k_tr_t1, dim3(tblk(T)), dim3(T_TPB), 0, s, T, SA, sq, spos, (flags & POVU_HIP_T_FORCE_TIER2) ? 1u : 0u, SO, handover);
+		compact_flagged_u8(handover, T, list, words + 1, comp_tmp_b, comp_b, s);
+		HIP_CHECK(copy_async(&n2, words + 1, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		if (n2) {
+			const unsigned wg = (unsigned)std::min<uint64_t>(((uint64_t)n2 + T_TPB / 64 - 1) / (T_TPB / 64), 4096);
+			KLAUNCH(k_tr_t2, dim3(wg), dim3(T_TPB), 0, s, list, n2, words + 2, SA, sq, spos, SO);
+		}
+		KLAUNCH(k_tr_closed, dim3(tgrid(T)), dim3(T_TPB), 0, s, T, tlen, closed);
+		compact_flagged_u8(closed, T, list, words + 3, comp_tmp_b, comp_b, s);
+		HIP_CHECK(copy_async(&R, words + 3, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+	}
+
+	// ---- phase C: the traversals, grouped into alleles
+	const size_t R1 = (size_t)R + 1;
+	const size_t sort_c = sort_tmp_bytes(R1) + 256, scan_c = scan_tmp_bytes(std::max(R1, n1)) + 256, comp_c = compact_tmp_bytes(R1) + 256;
+	uint64_t *rpos, *rhash;
+	uint32_t *rq, *rlen, *pa, *pb, *key, *kout, *mark, *hmax, *head, *rep, *firstf, *aidx, *rallele, *afirst, *alen, *soff, *blist;
+	uint32_t *toff, *aoff;
+	uint8_t *rbad;
+	void *sort_tmp_c, *scan_tmp_c, *comp_tmp_c;
+	carve(ctx->tr_trav, [&](Spans &take) {
+		take(R1, rpos, rhash, rq, rlen, pa, pb, key, kout, mark, hmax, head, rep);
+		take(R1, firstf, aidx, rallele, afirst, alen, soff, blist);
+		take(n1, toff, aoff);
+		take(R1, rbad);
+		take(sort_c, sort_tmp_c);
+		take(scan_c, scan_tmp_c);
+		take(comp_c, comp_tmp_c);
+	});
+	// (`list` of tr_task holds the traversals' task indices)
+	uint64_t n_splits = 0;
+	uint32_t n_al = 0;
+	if (R) {
+		KLAUNCH(k_tr_trav_fields, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, list, sq, spos, tlen, thash, rq, rpos, rlen, rhash);
+	}
+	KLAUNCH(k_tr_query_off, dim3(tblk(n1)), dim3(T_TPB), 0, s, n, R, rq, toff);
+	if (R) {
+		// stable LSD sort of the traversal indices by (query, length, hash): least significant key first
+		KLAUNCH(k_tr_iota, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, pa);
+		uint32_t *cur = pa, *nxt = pb;
+		auto pass = [&](int which, unsigned bits) {
+			KLAUNCH(k_tr_sort_key, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, which, cur, rhash, rlen, rq, key);
+			sort_pairs_u32(key, kout, cur, nxt, R, bits, sort_tmp_c, sort_c, s);
+			std::swap(cur, nxt);
+		};
+		pass(0, std::min(hbits, 32u));
+		if (hbits > 32)
+			pass(1, hbits - 32);
+		pass(2, bits_for(max_steps));
+		pass(3, bits_for(n));
+		const uint32_t *sp = cur;
+		KLAUNCH(k_tr_heads, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, sp, rhash, rlen, rq, mark);
+		scan_exclusive_max_u32(mark, hmax, R, scan_tmp_c, scan_c, s);
+		HIP_CHECK(hipMemsetAsync(rbad, 0, R1, s));
+		HIP_CHECK(hipMemsetAsync(tot, 0, 16, s));
+		KLAUNCH(k_tr_check, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, ctx->path_steps, sp, hmax, mark, rpos, rlen, head, rep, rbad);
+		compact_flagged_u8(rbad, R, blist, words + 4, comp_tmp_c, comp_c, s);
+		uint32_t nb = 0;
+		HIP_CHECK(copy_async(&nb, words + 4, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		if (nb) {
+			KLAUNCH(k_tr_regroup, dim3(tblk(nb)), dim3(T_TPB), 0, s, nb, blist, R, ctx->path_steps, sp, head, rpos, rlen, rep, tot + 1);
+			HIP_CHECK(copy_async(&n_splits, tot + 1, 8, hipMemcpyDeviceToHost, s));
+		}
+		HIP_CHECK(hipMemsetAsync(firstf, 0, R1 * 4, s));
+		KLAUNCH(k_tr_first, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, sp, rep, firstf);
+		scan_exclusive_u32(firstf, aidx, R1, scan_tmp_c, scan_c, s);
+		HIP_CHECK(copy_async(&n_al, aidx + R, 4, hipMemcpyDeviceToHost, s));
+		KLAUNCH(k_tr_allele, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, sp, rep, aidx, rlen, rallele, afirst, alen);
+		HIP_CHECK(hipStreamSynchronize(s));
+	} else {
+		HIP_CHECK(hipMemsetAsync(aidx, 0, 4, s));
+	}
+	KLAUNCH(k_tr_allele_off, dim3(tblk(n1)), dim3(T_TPB), 0, s, n, toff, aidx, aoff);
+	uint64_t n_steps = 0;
+	if (n_al)
+		totals_u32(alen, nullptr, n_al, tot, &n_steps, s);
+	check_32(n_steps, "allele steps");
+	if (n_al) {
+		HIP_CHECK(hipMemsetAsync(alen + n_al, 0, 4, s));
+		scan_exclusive_u32(alen, soff, (size_t)n_al + 1, scan_tmp_c, scan_c, s);
+	}
+
+	// ---- outputs: per traversal and allele steps, in tr_steps
+	uint32_t *op, *of, *ol, *oa, *sid;
+	uint8_t *orv, *sor;
+	carve(ctx->tr_steps, [&](Spans &take) {
+		take(R1, op, of, ol, oa, orv);
+		take(n_steps + 1, sid, sor);
+	});
+	if (R)
+		KLAUNCH(k_tr_out, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, ctx->path_off, P, rq, rpos, rlen, rallele, aidx, toff, op, of, ol, oa, orv);
+	if (n_al)
+		KLAUNCH(k_tr_allele_steps, dim3((unsigned)std::min<uint64_t>(((uint64_t)n_al + 3) / 4, 65536)), dim3(T_TPB), 0, s, n_al,
+			ctx->path_steps, g.vid, afirst, rpos, rlen, soff, sid, sor);
+
+	TravDevice d;
+	d.q = q;
+	d.R = R;
+	d.n_al = n_al;
+	d.n2 = n2;
+	d.n_steps = n_steps;
+	d.n_splits = n_splits;
+	d.op = op, d.of = of, d.ol = ol, d.oa = oa, d.sid = sid, d.toff = toff, d.aoff = aoff, d.qstatus = qstatus;
+	d.soff = soff, d.rq = rq, d.rlen = rlen, d.afirst = afirst, d.orv = orv, d.sor = sor, d.rpos = rpos;
+	return d;
+}
+} // namespace povu_hip
+
 extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, povu_hip_forest *f, const povu_hip_trav_opts *opts,
 							   char *err, size_t errlen)
 {
 	CallTimer timer;
 	return guarded_call(ctx, err, errlen, (povu_hip_traversals *)nullptr, [&] {
 		check_query_forest(ctx, f, "traversals");
-		if (!ctx->paths_valid || ctx->paths_gen != ctx->g.gen)
-			throw HipError("no paths are resident for the graph now uploaded (povu_hip_paths_upload after povu_hip_graph_upload)");
-		uint32_t max_steps = 65536, flags = 0;
-		if (opts) {
-			if (opts->max_steps == 1)
-				throw HipError("max_steps must be at least 2");
-			if (opts->max_steps)
-				max_steps = opts->max_steps;
-			flags = opts->flags;
-		}
-		const uint32_t hbits = hash_bits_hook();
-		const ResidentGraph &g = ctx->g;
+		const TravDevice d = trav_pipeline(
+			ctx, [&](CallTimer &tm, const QueryLayout &more) { return query_front(ctx, f, ctx->tr_ws, tm, more); }, opts, timer);
 		hipStream_t s = ctx->stream;
-		const uint64_t N = ctx->n_path_steps;
-		const uint32_t P = ctx->n_paths, nS = 2 * g.V;
-		const uint64_t n_tiles = (N + T_TILE - 1) / T_TILE;
-		check_32(n_tiles + 1, "start-task tiles");
-
-		// ---- phase A: queries, the boundary table, tile counts
-		uint32_t *qstatus, *bkey, *bval, *bkey2, *bval2, *bcnt, *boff, *tile_cnt, *tile_off;
-		unsigned long long *tot;
-		void *sort_tmp_a, *scan_tmp_a;
-		size_t sort_a = 0;
-		const size_t scan_a = scan_tmp_bytes(std::max<size_t>((size_t)nS + 1, n_tiles + 1)) + 256;
-		const QueryFront q = query_front(ctx, f, ctx->tr_ws, timer, [&](Spans &take, uint32_t n) {
-			const size_t n2q = 2 * (size_t)n + 1;
-			sort_a = sort_tmp_bytes(n2q) + 256;
-			take((size_t)n + 1, qstatus);
-			take(n2q, bkey, bval, bkey2, bval2);
-			take((size_t)nS + 1, bcnt, boff);
-			take(n_tiles + 1, tile_cnt, tile_off);
-			take(2, tot);
-			take(sort_a, sort_tmp_a);
-			take(scan_a, scan_tmp_a);
-		});
-		const uint32_t n = q.n, *ys = q.ys, *yz = q.yz;
-		uint32_t *words = q.words;
+		const uint32_t n = d.q.n, R = d.R, n_al = d.n_al;
+		const uint64_t n_steps = d.n_steps;
 		const size_t n1 = (size_t)n + 1;
-		HIP_CHECK(hipMemsetAsync(qstatus, 0, n1 * 4, s));
-		HIP_CHECK(hipMemsetAsync(bcnt, 0, ((size_t)nS + 1) * 4, s));
-		uint32_t hw[8] = {0};
-		HIP_CHECK(copy_async(hw, words, 32, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		query_refusals(hw[0], "traversals");
-		if (n) {
-			KLAUNCH(k_tr_keys, dim3(tblk(n)), dim3(T_TPB), 0, s, n, nS, ys, yz, bkey, bval, bcnt);
-			sort_pairs_u32(bkey, bkey2, bval, bval2, 2 * (size_t)n, bits_for(nS), sort_tmp_a, sort_a, s);
-		}
-		scan_exclusive_u32(bcnt, boff, (size_t)nS + 1, scan_tmp_a, scan_a, s);
-
-		// ---- start tasks: count per tile, scan, emit
-		if (n_tiles)
-			KLAUNCH(k_tr_count, dim3((unsigned)n_tiles), dim3(T_TPB), 0, s, N, ctx->path_steps, boff, tile_cnt);
-		HIP_CHECK(hipMemsetAsync(tile_cnt + n_tiles, 0, 4, s));
-		uint64_t T64 = 0;
-		totals_u32(tile_cnt, nullptr, n_tiles, tot, &T64, s);
-		check_32(T64, "scan tasks");
-		const uint32_t T = (uint32_t)T64;
-		scan_exclusive_u32(tile_cnt, tile_off, n_tiles + 1, scan_tmp_a, scan_a, s);
-
-		// ---- phase B: the tasks, sorted by query, and their scans
-		const size_t T1 = (size_t)T + 1;
-		const size_t sort_b = sort_tmp_bytes(T1) + 256, comp_b = compact_tmp_bytes(T1) + 256;
-		uint64_t *tpos, *spos, *thash;
-		uint32_t *tkey, *tval, *sq, *perm, *tlen, *list;
-		uint8_t *handover, *closed;
-		void *sort_tmp_b, *comp_tmp_b;
-		carve(ctx->tr_task, [&](Spans &take) {
-			take(T1, tpos, spos, thash, tkey, tval, sq, perm, tlen, list, handover, closed);
-			take(sort_b, sort_tmp_b);
-			take(comp_b, comp_tmp_b);
-		});
-		uint32_t n2 = 0, R = 0;
-		ScanArgs SA{ctx->path_steps, ctx->path_off, P, ys, yz, max_steps, hbits >= 64 ? 0xFFFFFFFFu : hbits > 32 ? (1u << (hbits - 32)) - 1 : 0u,
-			    hbits >= 32 ? 0xFFFFFFFFu : (1u << hbits) - 1};
-		ScanOut SO{tlen, thash, qstatus};
-		if (T) {
-			KLAUNCH(k_tr_emit, dim3((unsigned)n_tiles), dim3(T_TPB), 0, s, N, ctx->path_steps, boff, bval2, tile_off, tpos, tkey);
-			KLAUNCH(k_tr_iota, dim3(tgrid(T)), dim3(T_TPB), 0, s, T, tval);
-			sort_pairs_u32(tkey, sq, tval, perm, T, bits_for(n), sort_tmp_b, sort_b, s);
-			KLAUNCH(k_tr_gather64, dim3(tgrid(T)), dim3(T_TPB), 0, s, T, perm, tpos, spos);
-			KLAUNCH(k_tr_t1, dim3(tblk(T)), dim3(T_TPB), 0, s, T, SA, sq, spos, (flags & POVU_HIP_T_FORCE_TIER2) ? 1u : 0u, SO, handover);
-			compact_flagged_u8(handover, T, list, words + 1, comp_tmp_b, comp_b, s);
-			HIP_CHECK(copy_async(&n2, words + 1, 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
-			if (n2) {
-				const unsigned wg = (unsigned)std::min<uint64_t>(((uint64_t)n2 + T_TPB / 64 - 1) / (T_TPB / 64), 4096);
-				KLAUNCH(k_tr_t2, dim3(wg), dim3(T_TPB), 0, s, list, n2, words + 2, SA, sq, spos, SO);
-			}
-			KLAUNCH(k_tr_closed, dim3(tgrid(T)), dim3(T_TPB), 0, s, T, tlen, closed);
-			compact_flagged_u8(closed, T, list, words + 3, comp_tmp_b, comp_b, s);
-			HIP_CHECK(copy_async(&R, words + 3, 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
-		}
-
-		// ---- phase C: the traversals, grouped into alleles
-		const size_t R1 = (size_t)R + 1;
-		const size_t sort_c = sort_tmp_bytes(R1) + 256, scan_c = scan_tmp_bytes(std::max(R1, n1)) + 256, comp_c = compact_tmp_bytes(R1) + 256;
-		uint64_t *rpos, *rhash;
-		uint32_t *rq, *rlen, *pa, *pb, *key, *kout, *mark, *hmax, *head, *rep, *firstf, *aidx, *rallele, *afirst, *alen, *soff, *blist;
-		uint32_t *toff, *aoff;
-		uint8_t *rbad;
-		void *sort_tmp_c, *scan_tmp_c, *comp_tmp_c;
-		carve(ctx->tr_trav, [&](Spans &take) {
-			take(R1, rpos, rhash, rq, rlen, pa, pb, key, kout, mark, hmax, head, rep);
-			take(R1, firstf, aidx, rallele, afirst, alen, soff, blist);
-			take(n1, toff, aoff);
-			take(R1, rbad);
-			take(sort_c, sort_tmp_c);
-			take(scan_c, scan_tmp_c);
-			take(comp_c, comp_tmp_c);
-		});
-		// (`list` of tr_task holds the traversals' task indices)
-		uint64_t n_splits = 0;
-		uint32_t n_al = 0;
-		if (R) {
-			KLAUNCH(k_tr_trav_fields, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, list, sq, spos, tlen, thash, rq, rpos, rlen, rhash);
-		}
-		KLAUNCH(k_tr_query_off, dim3(tblk(n1)), dim3(T_TPB), 0, s, n, R, rq, toff);
-		if (R) {
-			// stable LSD sort of the traversal indices by (query, length, hash): least significant key first
-			KLAUNCH(k_tr_iota, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, pa);
-			uint32_t *cur = pa, *nxt = pb;
-			auto pass = [&](int which, unsigned bits) {
-				KLAUNCH(k_tr_sort_key, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, which, cur, rhash, rlen, rq, key);
-				sort_pairs_u32(key, kout, cur, nxt, R, bits, sort_tmp_c, sort_c, s);
-				std::swap(cur, nxt);
-			};
-			pass(0, std::min(hbits, 32u));
-			if (hbits > 32)
-				pass(1, hbits - 32);
-			pass(2, bits_for(max_steps));
-			pass(3, bits_for(n));
-			const uint32_t *sp = cur;
-			KLAUNCH(k_tr_heads, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, sp, rhash, rlen, rq, mark);
-			scan_exclusive_max_u32(mark, hmax, R, scan_tmp_c, scan_c, s);
-			HIP_CHECK(hipMemsetAsync(rbad, 0, R1, s));
-			HIP_CHECK(hipMemsetAsync(tot, 0, 16, s));
-			KLAUNCH(k_tr_check, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, ctx->path_steps, sp, hmax, mark, rpos, rlen, head, rep, rbad);
-			compact_flagged_u8(rbad, R, blist, words + 4, comp_tmp_c, comp_c, s);
-			uint32_t nb = 0;
-			HIP_CHECK(copy_async(&nb, words + 4, 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
-			if (nb) {
-				KLAUNCH(k_tr_regroup, dim3(tblk(nb)), dim3(T_TPB), 0, s, nb, blist, R, ctx->path_steps, sp, head, rpos, rlen, rep, tot + 1);
-				HIP_CHECK(copy_async(&n_splits, tot + 1, 8, hipMemcpyDeviceToHost, s));
-			}
-			HIP_CHECK(hipMemsetAsync(firstf, 0, R1 * 4, s));
-			KLAUNCH(k_tr_first, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, sp, rep, firstf);
-			scan_exclusive_u32(firstf, aidx, R1, scan_tmp_c, scan_c, s);
-			HIP_CHECK(copy_async(&n_al, aidx + R, 4, hipMemcpyDeviceToHost, s));
-			KLAUNCH(k_tr_allele, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, sp, rep, aidx, rlen, rallele, afirst, alen);
-			HIP_CHECK(hipStreamSynchronize(s));
-		} else {
-			HIP_CHECK(hipMemsetAsync(aidx, 0, 4, s));
-		}
-		KLAUNCH(k_tr_allele_off, dim3(tblk(n1)), dim3(T_TPB), 0, s, n, toff, aidx, aoff);
-		uint64_t n_steps = 0;
-		if (n_al)
-			totals_u32(alen, nullptr, n_al, tot, &n_steps, s);
-		check_32(n_steps, "allele steps");
-		if (n_al) {
-			HIP_CHECK(hipMemsetAsync(alen + n_al, 0, 4, s));
-			scan_exclusive_u32(alen, soff, (size_t)n_al + 1, scan_tmp_c, scan_c, s);
-		}
-
-		// ---- outputs: per traversal and allele steps, in tr_steps
-		uint32_t *op, *of, *ol, *oa, *sid;
-		uint8_t *orv, *sor;
-		carve(ctx->tr_steps, [&](Spans &take) {
-			take(R1, op, of, ol, oa, orv);
-			take(n_steps + 1, sid, sor);
-		});
-		if (R)
-			KLAUNCH(k_tr_out, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, ctx->path_off, P, rq, rpos, rlen, rallele, aidx, toff, op, of, ol, oa, orv);
-		if (n_al)
-			KLAUNCH(k_tr_allele_steps, dim3((unsigned)std::min<uint64_t>(((uint64_t)n_al + 3) / 4, 65536)), dim3(T_TPB), 0, s, n_al,
-				ctx->path_steps, g.vid, afirst, rpos, rlen, soff, sid, sor);
-
 		// ---- to the host
 		auto o = std::make_unique<TraversalsOwner>();
 		std::vector<uint32_t> h_toff(n1), h_aoff(n1), h_status(n1), h_soff((size_t)n_al + 1);
-		hand_off(o->path, R, op, R, ctx);
-		hand_off(o->first, R, of, R, ctx);
-		hand_off(o->last, R, ol, R, ctx);
-		hand_off(o->allele, R, oa, R, ctx);
-		hand_off(o->reverse, R, orv, R, ctx);
-		hand_off(o->step_id, n_steps, sid, n_steps, ctx);
-		hand_off(o->step_or, n_steps, sor, n_steps, ctx);
-		HIP_CHECK(copy_async(h_toff.data(), toff, n1 * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(copy_async(h_aoff.data(), aoff, n1 * 4, hipMemcpyDeviceToHost, s));
+		hand_off(o->path, R, d.op, R, ctx);
+		hand_off(o->first, R, d.of, R, ctx);
+		hand_off(o->last, R, d.ol, R, ctx);
+		hand_off(o->allele, R, d.oa, R, ctx);
+		hand_off(o->reverse, R, d.orv, R, ctx);
+		hand_off(o->step_id, n_steps, d.sid, n_steps, ctx);
+		hand_off(o->step_or, n_steps, d.sor, n_steps, ctx);
+		HIP_CHECK(copy_async(h_toff.data(), d.toff, n1 * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(h_aoff.data(), d.aoff, n1 * 4, hipMemcpyDeviceToHost, s));
 		if (n)
-			HIP_CHECK(copy_async(h_status.data(), qstatus, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(copy_async(h_status.data(), d.qstatus, (size_t)n * 4, hipMemcpyDeviceToHost, s));
 		if (n_al)
-			HIP_CHECK(copy_async(h_soff.data(), soff, ((size_t)n_al + 1) * 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(copy_async(h_soff.data(), d.soff, ((size_t)n_al + 1) * 4, hipMemcpyDeviceToHost, s));
 		o->view.device_ms = timer.stop(s);
 		o->trav_off.assign(h_toff.begin(), h_toff.end());
 		o->allele_off.assign(h_aoff.begin(), h_aoff.end());
@@ -845,8 +868,8 @@ extern "C" povu_hip_traversals *povu_hip_forest_traversals(povu_hip_ctx *ctx, po
 		o->view.step_off = o->step_off.data();
 		o->view.step_id = o->step_id.data();
 		o->view.step_or = o->step_or.data();
-		o->view.n_tier2 = n2;
-		o->view.n_hash_splits = n_splits;
+		o->view.n_tier2 = d.n2;
+		o->view.n_hash_splits = d.n_splits;
 		TraversalsOwner *raw = o.release();
 		return &raw->view;
 	});

@@ -3,6 +3,8 @@
 //   povu [--version] [-v <int>] [-t <int>] decompose -i <gfa> [-o <dir>] [-h|--hairpins] [-s|--subflubbles]
 //   povu ... decompose ... --structure-export <json>   (additive: writes the flubble debug sidecar gfa2vcf writes)
 //   povu ... gfa2vcf -i <gfa> [-h] [-s] [--structure-export <json>] <options of `call`>   (app/cli/cli.cpp:154-193)
+//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout]   (the variant calls
+//   of INTEGRATION.md "Variant calls", on the GPU)
 #include "decompose.hpp"
 
 #include <cstdlib>
@@ -25,7 +27,7 @@ static void usage(std::ostream &os)
 	      "        info                              Print graph information [uses 1 thread]\n"
 	      "        prune                             Reduce GFA to graph structure\n"
 	      "        gfa2vcf                           Convert GFA to VCF (decompose here + `call` of $POVU_CALL_EXE)\n"
-	      "        call, vcf                         (not part of the MI355X decompose build)\n"
+	      "        call                              Call variants of a forest on the GPU and write VCF\n"
 	      "      arguments\n"
 	      "        --version                         The current version of povu\n"
 	      "        -v[verbosity],\n"
@@ -47,7 +49,20 @@ static void usage(std::ostream &os)
 	      "                                          [default: 1; devices 0..n-1 or $POVU_HIP_DEVICES]\n"
 	      "        --structure-export=[structure_json]\n"
 	      "                                          Write the flubble debug sidecar <structure_json>.flubble-debug.jsonl\n"
-	      "                                          [conformance]\n";
+	      "                                          [conformance]\n\n"
+	      "  call OPTIONS:\n"
+	      "        -i[gfa], --input-gfa=[gfa]        path to input gfa [required]\n"
+	      "        -f[forest_dir], --forest-dir=[forest_dir]\n"
+	      "                                          directory of the <component id>.pvst files [default: .]\n"
+	      "        -r[ref_list], --ref-list=[ref_list]\n"
+	      "                                          file of reference path name prefixes, one per line\n"
+	      "        -P[prefix], --path-prefix=[prefix]\n"
+	      "                                          reference paths: every path whose name starts with it (repeatable)\n"
+	      "        prefixes...                       reference path name prefixes (exactly one of -r, -P, positional)\n"
+	      "        -o[output_dir], --output-dir=[output_dir]\n"
+	      "                                          write <output_dir>/<prefix>.vcf per prefix\n"
+	      "        --stdout                          one VCF of every reference path to stdout [default]\n"
+	      "        -c, -q                            accepted and ignored (no streaming here)\n";
 }
 
 int main(int argc, char **argv)
@@ -90,7 +105,7 @@ int main(int argc, char **argv)
 			print_tips = true; // inside `info`, -t means "print the tips" (cli.cpp:220)
 		} else if (value(i, a, "-t", "--threads", v)) {
 			cfg.threads = atoi(v.c_str());
-		} else if ((command == "decompose" || command == "info" || command == "prune" || command == "gfa2vcf") &&
+		} else if ((command == "decompose" || command == "info" || command == "prune" || command == "gfa2vcf" || command == "call") &&
 			   value(i, a, "-i", "--input-gfa", v)) {
 			cfg.input_gfa = v;
 			have_input = true;
@@ -121,7 +136,7 @@ int main(int argc, char **argv)
 				usage(std::cerr);
 				return 1;
 			}
-		} else if (command == "gfa2vcf") {
+		} else if (command == "gfa2vcf" || command == "call") {
 			call_args.push_back(a); // streaming / output / reference options of `call` (cli.cpp:28-88)
 		} else if (command.empty() && a[0] != '-') {
 			command = a;
@@ -145,8 +160,8 @@ int main(int argc, char **argv)
 		usage(std::cout);
 		return 0;
 	}
-	if (command != "decompose" && command != "info" && command != "prune" && command != "gfa2vcf") {
-		std::cerr << "povu (MI355X build): only `decompose`, `info`, `prune` and `gfa2vcf` are provided; `" << command
+	if (command != "decompose" && command != "info" && command != "prune" && command != "gfa2vcf" && command != "call") {
+		std::cerr << "povu (MI355X build): only `decompose`, `info`, `prune`, `gfa2vcf` and `call` are provided; `" << command
 			  << "` belongs to the reference CPU tool" << std::endl;
 		return 1;
 	}
@@ -166,6 +181,8 @@ int main(int argc, char **argv)
 			povu_host::do_prune(cfg);
 		else if (command == "gfa2vcf")
 			povu_host::do_gfa2vcf(cfg, call_args);
+		else if (command == "call")
+			povu_host::do_call(cfg, call_args);
 		else {
 			povu_host::reset_debug_sidecar(cfg);
 			cfg.exit_when_done = true;

@@ -52,6 +52,9 @@ void write_debug_sidecar_frame(std::ostream &out, povu_hip_ctx *ctx, uint32_t co
 // povu binary named by POVU_CALL_EXE on it (a child process); `call_args` are handed to it unchanged.
 void do_gfa2vcf(const Config &cfg, const std::vector<std::string> &call_args);
 void do_prune(const Config &cfg);
+// `povu call` (INTEGRATION.md "Variant calls"): the PVSTs of -f <dir> called on the GPU with the GFA's paths and sequences,
+// written as VCF; `args` are the options after `call` that main() does not parse itself
+void do_call(const Config &cfg, const std::vector<std::string> &args);
 
 // device of every rank of `--gpus N` (POVU_HIP_DEVICES or 0 .. N-1), checked against the number of visible devices
 std::vector<int> multi_devices(int gpus, const char *env, int visible);

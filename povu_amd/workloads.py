@@ -31,10 +31,13 @@ class Links:
     def n_links(self) -> int:
         return int(self.v1.shape[0])
 
-    def to_gfa(self) -> str:
-        """GFA text: S lines first (sequence `A`), then L lines, all `0M`."""
+    def to_gfa(self, seqs=None) -> str:
+        """GFA text: S lines first (sequence `A`, or seqs[k] for vertex k when given), then L lines, all `0M`."""
         out = ["H\tVN:Z:1.0"]
-        out += [f"S\t{i}\tA" for i in self.vid.tolist()]
+        if seqs is None:
+            out += [f"S\t{i}\tA" for i in self.vid.tolist()]
+        else:
+            out += [f"S\t{i}\t{q}" for i, q in zip(self.vid.tolist(), seqs)]
         vid = self.vid
         for a, sa, b, sb in zip(self.v1.tolist(), self.s1.tolist(), self.v2.tolist(), self.s2.tolist()):
             out.append(f"L\t{vid[a]}\t{'+' if sa == R else '-'}\t{vid[b]}\t{'+' if sb == L else '-'}\t0M")
@@ -569,3 +572,30 @@ def chain_haplotypes(k: int, n: int, seed: int, reverse_every: int = 4) -> Paths
         else:
             pieces.append((ids, np.zeros(ids.size, dtype=np.uint8)))
     return _paths([f"hap{h}" for h in range(n)], pieces)
+
+
+def random_sequences(links: Links, seed: int, max_len: int = 300, empty: float = 0.1) -> list:
+    """A random sequence per vertex (index order): lengths 0 to max_len (a share `empty` of them empty, half of the rest a
+    single base), mostly ACGT with some lower case and IUPAC codes -- every VARTYPE and anchoring case of a call."""
+    rng = np.random.default_rng(seed)
+    n = links.n_vtx
+    kind = rng.random(n)
+    lens = np.where(kind < empty, 0, np.where(kind < (1 + empty) / 2, 1, rng.integers(1, max_len + 1, size=n)))
+    alphabet = np.frombuffer(b"ACGTACGTACGTACGTacgtNRYKMSWBDHV", np.uint8)
+    pool = alphabet[rng.integers(0, alphabet.size, size=int(lens.sum()) + 1)].tobytes().decode()
+    out, at = [], 0
+    for ln in lens.tolist():
+        out.append(pool[at:at + ln])
+        at += ln
+    return out
+
+
+def pansn(paths: Paths, samples: int, haps: int = 2, contig: str = "chr1") -> Paths:
+    """The same paths renamed `sample<k>#<hap>#<contig>`: path j is hap (j % haps) + 1 of sample j // haps (modulo
+    `samples`, so that later paths become further contigs of the same slots)."""
+    names = []
+    for j in range(len(paths)):
+        sm = (j // haps) % samples
+        rnd = j // (haps * samples)
+        names.append(f"sample{sm}#{j % haps + 1}#{contig}" + (f"_{rnd}" if rnd else ""))
+    return Paths(names, paths.off, paths.ids, paths.rev)
