@@ -493,6 +493,41 @@ int povu_hip_gfa_write(const char *path, uint32_t n_vtx, const uint32_t *vid, ui
 		       const uint8_t *s1, const uint32_t *v2, const uint8_t *s2, char *err, size_t errlen);
 void povu_pvst_doc_free(povu_pvst_doc *doc);
 
+/* ---- the host half of a call (host only, no GPU needed): what povu_hip_call takes, from names and trees, and what it gives,
+ * as VCF text (INTEGRATION.md "Variant calls": reference paths, samples and slots, the VCF) ---- */
+/* The reference paths and the PanSN samples and slots of the paths named `path_name`: refs.ref_path the paths whose name
+ * starts with one of the prefixes (ascending), a name `sample#hap#rest` with an all-digit hap that sample's slot `hap` (a
+ * sample's slots consecutive, ascending by hap), any other name a sample of its own; samples in order of their first path. */
+typedef struct {
+	povu_hip_call_refs refs;	/* for povu_hip_call */
+	uint32_t n_paths;
+	const uint32_t *slot_of_path; /* [n_paths] for povu_hip_call */
+	const char *const *sample;	/* [refs.n_samples] names, in column order */
+} povu_hip_call_names;
+/* NULL and a message that lists the prefixes when no name starts with one of them.  Free with _free. */
+povu_hip_call_names *povu_hip_call_names_make(uint32_t n_paths, const char *const *path_name, uint32_t n_prefixes,
+					      const char *const *prefix, char *err, size_t errlen);
+void povu_hip_call_names_free(povu_hip_call_names *n);
+/* Appends the sites of tree number `tree` to the owned `s` (of _sites_of_docs / _forest_sites, or zeroed by the caller and freed
+ * with _sites_free): n vertices in PVST vertex order, a root (family 'D'; family NULL: entry 0, every other vertex 'F') is
+ * skipped and the others numbered on; parent the vertex index (POVU_HIP_NIL or a root: none), height 1 under a root and one
+ * more than the parent's elsewhere (0 for a vertex without parent).  0 on success */
+int povu_hip_sites_add_tree(povu_hip_sites *s, uint32_t tree, uint32_t n, const uint32_t *id1, const uint32_t *id2,
+			    const uint8_t *or1, const uint8_t *or2, const uint32_t *parent, const uint8_t *family);
+/* the sites of parsed PVST files in component order (tree k = docs[k]) */
+povu_hip_sites *povu_hip_sites_of_docs(const povu_pvst_doc *const *docs, uint32_t n);
+/* the sites of a forest: the extended trees of POVU_HIP_F_SUBFLUBBLES when it carries them (parent = the last vertex that
+ * lists it as child), else its PVSTs with the line letters of POVU_HIP_F_LEAF_SUBFLUBBLES when it carries those */
+povu_hip_sites *povu_hip_forest_sites(const povu_hip_forest *f);
+void povu_hip_sites_free(povu_hip_sites *s);
+/* The VCF of `c` (made by povu_hip_call from `sites` and `names`; path_name as given to _names_make): header, a contig line
+ * per reference path, the column line, the records.  date NULL = today (%Y%m%d); only_prefix NULL = every reference, else the
+ * contig lines and records of the reference paths whose name starts with it; the records are formatted in chunks on up to
+ * `threads` threads (at least 1024 records each).  malloc'd, free with povu_hip_buffer_free; NULL on arguments that do not
+ * belong together. */
+char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
+			 const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, size_t *len);
+
 /* ---- measurement (bench.py, povu-stage-cost lines) ---- */
 typedef struct {
 	char name[48];	  /* kernel group */

@@ -1398,7 +1398,6 @@ extern "C" uint64_t povu_hip_forest_first(const povu_hip_forest *f, uint32_t i)
 }
 
 extern "C" void povu_hip_forest_free(povu_hip_forest *f) { delete f; }
-extern "C" void povu_hip_buffer_free(void *p) { free(p); }
 
 // mto::to_pvst::write_pvst, src/mto/to_pvst.cpp:23-109
 extern "C" int povu_hip_forest_get_sub(const povu_hip_forest *f, uint32_t i, const uint32_t **ai, const uint32_t **zi,
@@ -1445,6 +1444,37 @@ extern "C" int povu_hip_forest_get_subtree(const povu_hip_forest *f, uint32_t i,
 	out->child_off = x->coff + b;
 	out->child = x->child;
 	return 0;
+}
+
+// the sites of every tree through povu_hip_sites_add_tree (host/vcf.cpp): the extended tree of -s, else the PVST with the T / O
+// letters of --leaf-subflubbles, else the PVST as it is
+extern "C" povu_hip_sites *povu_hip_forest_sites(const povu_hip_forest *f)
+{
+	auto *s = f ? static_cast<povu_hip_sites *>(calloc(1, sizeof(povu_hip_sites))) : nullptr;
+	std::vector<uint32_t> par;
+	for (uint32_t i = 0; s && i < f->trees.size(); i++) {
+		povu_hip_subtree x;
+		povu_hip_tree t;
+		const uint8_t *fam = nullptr;
+		int rc;
+		if (povu_hip_forest_get_subtree(f, i, &x) == 0) {
+			par.assign(x.n_total, POVU_HIP_NIL);
+			for (uint32_t v = 0; v < x.n_total; v++)
+				for (uint32_t k = x.child_off[v]; k < x.child_off[v + 1]; k++)
+					if (x.child[k] < x.n_total)
+						par[x.child[k]] = v;
+			rc = povu_hip_sites_add_tree(s, i, x.n_total, x.id1, x.id2, x.or1, x.or2, par.data(), x.fam);
+		} else {
+			rc = povu_hip_forest_get(f, i, &t);
+			povu_hip_forest_get_sub(f, i, nullptr, nullptr, &fam); // (leaves fam null when the forest carries no letters)
+			rc = rc ? rc : povu_hip_sites_add_tree(s, i, t.n_pvst, t.a_id, t.z_id, t.a_or, t.z_or, t.parent, fam);
+		}
+		if (rc) {
+			povu_hip_sites_free(s);
+			s = nullptr;
+		}
+	}
+	return s;
 }
 
 // write_pvst, src/mto/to_pvst.cpp:31-109, of a tree with its -s vertices

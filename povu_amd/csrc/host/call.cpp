@@ -1,5 +1,6 @@
 // call.cpp -- `povu call` (INTEGRATION.md "Variant calls"): the GFA's paths and sequences and the PVSTs of a forest
-// directory to the GPU (povu_hip_call), the records formatted on up to -t threads and written as VCF.
+// directory to the GPU (povu_hip_call), the records written as VCF.  References, slots, sites and the VCF text are the
+// library's (host/vcf.cpp); what stays here is the command line and the files.
 #include "decompose.hpp"
 #include "gfa.hpp"
 
@@ -9,35 +10,18 @@
 #include <cerrno>
 #include <cstdio>
 #include <cstring>
-#include <ctime>
 #include <dirent.h>
 #include <fstream>
 #include <iostream>
 #include <sys/stat.h>
-#include <map>
 #include <sstream>
 #include <stdexcept>
-#include <thread>
 
 namespace povu_host
 {
 
 namespace
 {
-
-const char *VCF_HEADER =
-	"##source=povu\n"
-	"##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
-	"##INFO=<ID=AC,Number=A,Type=Integer,Description=\"Total number of alternate alleles in called genotypes\">\n"
-	"##INFO=<ID=AT,Number=R,Type=String,Description=\"Allele traversal path through the graph\">\n"
-	"##INFO=<ID=AN,Number=1,Type=String,Description=\"Total number of alleles in called genotypes\">\n"
-	"##INFO=<ID=AF,Number=A,Type=Float,Description=\"Allele frequency in the population\">\n"
-	"##INFO=<ID=NS,Number=1,Type=Integer,Description=\"Number of samples with data\">\n"
-	"##INFO=<ID=VARTYPE,Number=1,Type=String,Description=\"Type of variation: INS (insertion), DEL (deletion), SUB (substitution), "
-	"SUBR(substitution in reverse) \">\n"
-	"##INFO=<ID=TANGLED,Number=1,Type=String,Description=\"Variant lies in a tangled region of the graph: T or F\">\n"
-	"##INFO=<ID=LV,Number=1,Type=Integer,Description=\"Level in the PVST (0=top level)\">\n"
-	"##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
 
 struct CallArgs {
 	std::string forest_dir = ".", out_dir;
@@ -103,25 +87,8 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 	return c;
 }
 
-std::pair<std::string, long> pansn(const std::string &n)
-{
-	const size_t a = n.find('#');
-	if (a != std::string::npos) {
-		const size_t b = n.find('#', a + 1);
-		if (b != std::string::npos && b > a + 1 && std::all_of(n.begin() + a + 1, n.begin() + b, [](char ch) { return ch >= '0' && ch <= '9'; }))
-			return {n.substr(0, a), std::stol(n.substr(a + 1, b - a - 1))};
-	}
-	return {n, -1};
-}
-
-struct Sites {
-	std::vector<uint32_t> id1, id2, parent, height, tree;
-	std::vector<uint8_t> or1, or2, fam;
-	std::vector<std::string> label;
-};
-
-// every <component id>.pvst of `dir`, in component order
-Sites read_forest(const std::string &dir)
+// the sites of every <component id>.pvst of `dir`, in component order
+povu_hip_sites *read_forest(const std::string &dir)
 {
 	std::vector<std::pair<unsigned long, std::string>> files;
 	DIR *d = opendir(dir.c_str());
@@ -135,52 +102,27 @@ Sites read_forest(const std::string &dir)
 	}
 	closedir(d);
 	std::sort(files.begin(), files.end());
-	Sites s;
-	uint32_t tree = 0;
+	std::vector<povu_pvst_doc *> docs;
+	std::string bad;
 	for (auto &[cid, path] : files) {
 		std::ifstream in(path, std::ios::binary);
 		std::stringstream buf;
 		buf << in.rdbuf();
 		const std::string text = buf.str();
 		char err[512] = {0};
-		povu_pvst_doc *doc = povu_pvst_parse(text.data(), text.size(), err, sizeof err);
-		if (!doc)
-			throw std::runtime_error(path + ": " + err);
-		std::vector<uint32_t> qnum(doc->n, POVU_HIP_NIL);
-		uint32_t next = (uint32_t)s.id1.size();
-		for (uint32_t v = 0; v < doc->n; v++)
-			if (doc->type[v] != 'D')
-				qnum[v] = next++;
-		for (uint32_t v = 0; v < doc->n; v++) {
-			if (doc->type[v] == 'D')
-				continue;
-			s.id1.push_back(doc->a_id[v]);
-			s.id2.push_back(doc->z_id[v]);
-			s.or1.push_back(doc->a_or[v]);
-			s.or2.push_back(doc->z_or[v]);
-			const uint32_t p = doc->parent[v];
-			s.parent.push_back(p == POVU_HIP_NIL || p >= doc->n ? POVU_HIP_NIL : qnum[p]);
-			s.height.push_back(doc->height[v]);
-			s.fam.push_back((uint8_t)doc->type[v]);
-			s.tree.push_back(tree);
-			s.label.push_back(std::string(doc->a_or[v] ? "<" : ">") + std::to_string(doc->a_id[v]) + (doc->z_or[v] ? "<" : ">") +
-					  std::to_string(doc->z_id[v]));
+		docs.push_back(povu_pvst_parse(text.data(), text.size(), err, sizeof err));
+		if (!docs.back()) {
+			bad = path + ": " + err;
+			break;
 		}
-		povu_pvst_doc_free(doc);
-		tree++;
 		(void)cid;
 	}
+	povu_hip_sites *s = bad.empty() ? povu_hip_sites_of_docs(docs.data(), (uint32_t)docs.size()) : nullptr;
+	for (povu_pvst_doc *x : docs)
+		povu_pvst_doc_free(x);
+	if (!s)
+		throw std::runtime_error(bad.empty() ? "cannot build the sites of " + dir : bad);
 	return s;
-}
-
-std::string today()
-{
-	char b[16];
-	const time_t t = time(nullptr);
-	struct tm tmv;
-	localtime_r(&t, &tmv);
-	strftime(b, sizeof b, "%Y%m%d", &tmv);
-	return b;
 }
 
 } // namespace
@@ -200,50 +142,17 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 	seq.reserve(seq_off[V]);
 	for (auto &x : g.seq)
 		seq += x;
-	std::vector<std::string> names(P);
+	std::vector<const char *> names(P), prefixes;
 	for (uint32_t k = 0; k < P; k++)
-		names[k] = g.paths[k].name;
-	std::vector<uint32_t> ref_path;
-	for (uint32_t k = 0; k < P; k++)
-		for (auto &p : ca.prefixes)
-			if (!names[k].compare(0, p.size(), p)) {
-				ref_path.push_back(k);
-				break;
-			}
-	if (ref_path.empty()) {
-		std::string l;
-		for (auto &p : ca.prefixes)
-			l += (l.empty() ? "" : ", ") + p;
-		throw std::runtime_error("no path name starts with any of the reference prefixes " + l);
-	}
-	// PanSN slots
-	std::vector<std::string> samples;
-	std::map<std::string, std::vector<long>> haps;
-	for (auto &n : names) {
-		auto [sm, h] = pansn(n);
-		if (!haps.count(sm))
-			samples.push_back(sm);
-		auto &hv = haps[sm];
-		if (std::find(hv.begin(), hv.end(), h) == hv.end())
-			hv.push_back(h);
-	}
-	std::map<std::pair<std::string, long>, uint32_t> slot_id;
-	std::vector<uint32_t> sample_of_slot, slot_first{0};
-	for (uint32_t si = 0; si < samples.size(); si++) {
-		auto hv = haps[samples[si]];
-		std::sort(hv.begin(), hv.end());
-		for (long h : hv) {
-			slot_id[{samples[si], h}] = (uint32_t)sample_of_slot.size();
-			sample_of_slot.push_back(si);
-		}
-		slot_first.push_back((uint32_t)sample_of_slot.size());
-	}
-	std::vector<uint32_t> slot_of_path(P);
-	for (uint32_t k = 0; k < P; k++)
-		slot_of_path[k] = slot_id[pansn(names[k])];
-	const Sites st = read_forest(ca.forest_dir);
-
+		names[k] = g.paths[k].name.c_str();
+	for (auto &p : ca.prefixes)
+		prefixes.push_back(p.c_str());
 	char err[512] = {0};
+	povu_hip_call_names *nm = povu_hip_call_names_make(P, names.data(), (uint32_t)prefixes.size(), prefixes.data(), err, sizeof err);
+	if (!nm)
+		throw std::runtime_error(err);
+	povu_hip_sites *sites = read_forest(ca.forest_dir);
+
 	povu_hip_ctx *ctx = povu_hip_create(cfg.device, err, sizeof err);
 	if (!ctx)
 		throw std::runtime_error(std::string("povu_hip: ") + err);
@@ -259,118 +168,18 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 		fail("paths");
 	if (povu_hip_segments_upload(ctx, V, seq_off.data(), seq.data(), err, sizeof err) != 0)
 		fail("sequences");
-	povu_hip_sites sites{(uint32_t)st.id1.size(), st.id1.data(), st.id2.data(), st.or1.data(), st.or2.data(), st.parent.data(),
-			     st.height.data(), st.fam.data(), st.tree.data()};
-	povu_hip_call_refs refs{(uint32_t)ref_path.size(), ref_path.data(), (uint32_t)sample_of_slot.size(), (uint32_t)samples.size(),
-				sample_of_slot.data()};
-	povu_hip_calls *c = povu_hip_call(ctx, &sites, &refs, slot_of_path.data(), nullptr, err, sizeof err);
+	povu_hip_calls *c = povu_hip_call(ctx, sites, &nm->refs, nm->slot_of_path, nullptr, err, sizeof err);
 	if (!c)
 		fail("call");
 
-	// ---- the records as text, in chunks of records on up to -t threads
-	const uint64_t n = c->n_records, S = c->n_slots;
-	const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)std::max(1, cfg.threads), (n + 1023) / 1024));
-	std::vector<std::string> chunk(T);
-	auto format = [&](int t) {
-		std::string &o = chunk[t];
-		const uint64_t lo = n * t / T, hi = n * (t + 1) / T;
-		std::vector<uint64_t> order;
-		char num[32];
-		for (uint64_t i = lo; i < hi; i++) {
-			const uint32_t q = c->query[i], na = c->n_alleles[i], ra = c->ref_allele[i];
-			const uint64_t b = c->block_off[c->block[i]];
-			order.clear();
-			order.push_back(b + ra);
-			for (uint32_t a = 0; a < na; a++)
-				if (a != ra)
-					order.push_back(b + a);
-			o += names[c->path[i]];
-			o += '\t';
-			o += std::to_string(c->pos[i]);
-			o += '\t';
-			o += st.label[q];
-			for (size_t k = 0; k < order.size(); k++) {
-				o += k <= 1 ? '\t' : ',';
-				o.append(c->seq + c->seq_off[order[k]], c->seq_off[order[k] + 1] - c->seq_off[order[k]]);
-			}
-			o += "\t60\tPASS\tAC=";
-			const uint64_t a0 = c->ac_off[i], a1 = c->ac_off[i + 1];
-			const uint32_t an = c->an[i];
-			for (uint64_t k = a0; k < a1; k++)
-				o += (k > a0 ? "," : "") + std::to_string(c->ac[k]);
-			o += ";AF=";
-			for (uint64_t k = a0; k < a1; k++) {
-				snprintf(num, sizeof num, "%.1f", an ? (double)c->ac[k] / an : 0.0);
-				o += (k > a0 ? "," : "");
-				o += num;
-			}
-			o += ";AN=" + std::to_string(an) + ";NS=" + std::to_string(c->ns[i]) + ";AT=";
-			for (size_t k = 0; k < order.size(); k++) {
-				if (k)
-					o += ',';
-				o.append(c->at + c->at_off[order[k]], c->at_off[order[k] + 1] - c->at_off[order[k]]);
-			}
-			const uint8_t f = c->flags[i];
-			o += (f & POVU_HIP_CALL_INS) ? ";VARTYPE=INS" : (f & POVU_HIP_CALL_DEL) ? ";VARTYPE=DEL" : ";VARTYPE=SUB";
-			o += (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
-			o += ";ES=" + st.label[q] + ";LV=" + std::to_string((long)st.height[q] - 1) + "\tGT";
-			const uint16_t *row = c->gt + i * S;
-			for (uint32_t sm = 0; sm < samples.size(); sm++) {
-				o += '\t';
-				bool any = false;
-				for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++)
-					any |= row[sl] != POVU_HIP_GT_MISSING;
-				if (!any) {
-					o += '.';
-					continue;
-				}
-				for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++) {
-					if (sl > slot_first[sm])
-						o += '|';
-					o += row[sl] == POVU_HIP_GT_MISSING ? "." : std::to_string(row[sl]);
-				}
-			}
-			o += '\n';
-		}
-	};
-	std::vector<std::thread> th;
-	for (int t = 1; t < T; t++)
-		th.emplace_back(format, t);
-	format(0);
-	for (auto &x : th)
-		x.join();
-
 	// ---- the files: one VCF of every reference (--stdout), or <dir>/<prefix>.vcf per prefix with its references' records
-	const std::string head = "##fileformat=VCFv4.2\n##fileDate=" + today() + "\n" + VCF_HEADER;
-	std::string cols = "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
-	for (auto &sm : samples)
-		cols += "\t" + sm;
-	cols += "\n";
-	auto write = [&](std::ostream &os, const std::string *only) {
-		os << head;
-		for (uint32_t r = 0; r < ref_path.size(); r++) {
-			const std::string &nm = names[ref_path[r]];
-			if (only && nm.compare(0, only->size(), *only))
-				continue;
-			os << "##contig=<ID=" << nm << ",length=" << c->contig_len[r] << ">\n";
-		}
-		os << cols;
-		if (!only) {
-			for (auto &x : chunk)
-				os << x;
-			return;
-		}
-		for (auto &x : chunk) { // (records of the prefix's references only: lines start with the path name)
-			size_t at = 0;
-			while (at < x.size()) {
-				const size_t e = x.find('\n', at);
-				const size_t tab = x.find('\t', at);
-				const std::string nm = x.substr(at, tab - at);
-				if (!nm.compare(0, only->size(), *only))
-					os.write(x.data() + at, e + 1 - at);
-				at = e + 1;
-			}
-		}
+	auto write = [&](std::ostream &os, const char *only) {
+		size_t len = 0;
+		char *text = povu_hip_calls_vcf(c, sites, nm, names.data(), nullptr, only, (uint32_t)std::max(1, cfg.threads), &len);
+		if (!text)
+			throw std::runtime_error("cannot format the calls as VCF");
+		os.write(text, (std::streamsize)len);
+		povu_hip_buffer_free(text);
 	};
 	if (ca.to_stdout) {
 		write(std::cout, nullptr);
@@ -382,11 +191,13 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 			std::ofstream os(ca.out_dir + "/" + p + ".vcf");
 			if (!os)
 				throw std::runtime_error("cannot write " + ca.out_dir + "/" + p + ".vcf");
-			write(os, &p);
+			write(os, p.c_str());
 		}
 	}
 	povu_hip_calls_free(c);
 	povu_hip_destroy(ctx);
+	povu_hip_sites_free(sites);
+	povu_hip_call_names_free(nm);
 }
 
 } // namespace povu_host

@@ -21,6 +21,8 @@ void set_err(char *err, size_t n, const std::string &m)
 }
 } // namespace
 
+extern "C" void povu_hip_buffer_free(void *p) { free(p); }
+
 // GFA v1 text of a whole graph, the inverse of the loader contract (host/gfa.cpp; mto::to_gfa::write_gfa,
 // src/mto/to_gfa.cpp:13-56, writes the same three record shapes): header, one `S <id> A` per segment in vertex order, one
 // `L <a> <+|-> <b> <+|-> 0M` per link in link order, `+` = leaves a through its r side / enters b through its l side.

@@ -1,0 +1,324 @@
+// vcf.cpp -- the host half of a variant call (INTEGRATION.md "Variant calls"), host only: path names to reference paths and
+// PanSN slots, PVST vertices to sites, and the records of povu_hip_call to VCF text.  The one place that holds these rules
+// for `povu call` and for povu_amd/hip.py alike; tests/vcf_ref.py restates them as the yardstick.
+#include "../../../include/povu_hip.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <ctime>
+#include <map>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace
+{
+
+const char *VCF_HEADER =
+	"##source=povu\n"
+	"##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n"
+	"##INFO=<ID=AC,Number=A,Type=Integer,Description=\"Total number of alternate alleles in called genotypes\">\n"
+	"##INFO=<ID=AT,Number=R,Type=String,Description=\"Allele traversal path through the graph\">\n"
+	"##INFO=<ID=AN,Number=1,Type=String,Description=\"Total number of alleles in called genotypes\">\n"
+	"##INFO=<ID=AF,Number=A,Type=Float,Description=\"Allele frequency in the population\">\n"
+	"##INFO=<ID=NS,Number=1,Type=Integer,Description=\"Number of samples with data\">\n"
+	"##INFO=<ID=VARTYPE,Number=1,Type=String,Description=\"Type of variation: INS (insertion), DEL (deletion), SUB (substitution), "
+	"SUBR(substitution in reverse) \">\n"
+	"##INFO=<ID=TANGLED,Number=1,Type=String,Description=\"Variant lies in a tangled region of the graph: T or F\">\n"
+	"##INFO=<ID=LV,Number=1,Type=Integer,Description=\"Level in the PVST (0=top level)\">\n"
+	"##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
+
+// (sample, hap) of a path name: `sample#hap#rest` with an all-digit hap, any other name a sample of its own with hap -1
+std::pair<std::string, long long> pansn(const std::string &n)
+{
+	const size_t a = n.find('#');
+	if (a != std::string::npos) {
+		const size_t b = n.find('#', a + 1);
+		if (b != std::string::npos && b > a + 1 && std::all_of(n.begin() + a + 1, n.begin() + b, [](char ch) { return ch >= '0' && ch <= '9'; }))
+			return {n.substr(0, a), strtoll(n.c_str() + a + 1, nullptr, 10)};
+	}
+	return {n, -1};
+}
+
+void set_err(char *err, size_t n, const std::string &m)
+{
+	if (err && n)
+		snprintf(err, n, "%s", m.c_str());
+}
+
+struct Names {
+	povu_hip_call_names pub; // (first: the handle points at it)
+	std::vector<uint32_t> ref_path, sample_of_slot, slot_of_path;
+	std::vector<std::string> sample;
+	std::vector<const char *> sample_ptr;
+};
+
+template <class T> bool grow(const T *&p, size_t n)
+{
+	void *q = realloc(const_cast<T *>(p), (n + 1) * sizeof(T));
+	if (q)
+		p = static_cast<const T *>(q);
+	return q != nullptr;
+}
+
+} // namespace
+
+extern "C" povu_hip_call_names *povu_hip_call_names_make(uint32_t n_paths, const char *const *path_name, uint32_t n_prefixes,
+							 const char *const *prefix, char *err, size_t errlen)
+try {
+	if ((n_paths && !path_name) || (n_prefixes && !prefix)) {
+		set_err(err, errlen, "call names: bad arguments");
+		return nullptr;
+	}
+	std::unique_ptr<Names> nm(new Names);
+	std::map<std::string, std::vector<long long>> haps;
+	std::vector<std::pair<std::string, long long>> key(n_paths);
+	for (uint32_t k = 0; k < n_paths; k++) {
+		const std::string name = path_name[k];
+		for (uint32_t p = 0; p < n_prefixes; p++)
+			if (!name.compare(0, strlen(prefix[p]), prefix[p])) {
+				nm->ref_path.push_back(k);
+				break;
+			}
+		key[k] = pansn(name);
+		if (!haps.count(key[k].first))
+			nm->sample.push_back(key[k].first);
+		auto &hv = haps[key[k].first];
+		if (std::find(hv.begin(), hv.end(), key[k].second) == hv.end())
+			hv.push_back(key[k].second);
+	}
+	if (nm->ref_path.empty()) {
+		std::string l;
+		for (uint32_t p = 0; p < n_prefixes; p++)
+			l += std::string(l.empty() ? "" : ", ") + prefix[p];
+		set_err(err, errlen, "no path name starts with any of the reference prefixes " + l);
+		return nullptr;
+	}
+	std::map<std::pair<std::string, long long>, uint32_t> slot_id;
+	for (uint32_t si = 0; si < nm->sample.size(); si++) {
+		auto &hv = haps[nm->sample[si]];
+		std::sort(hv.begin(), hv.end());
+		for (long long h : hv) {
+			slot_id[{nm->sample[si], h}] = (uint32_t)nm->sample_of_slot.size();
+			nm->sample_of_slot.push_back(si);
+		}
+		nm->sample_ptr.push_back(nm->sample[si].c_str());
+	}
+	for (uint32_t k = 0; k < n_paths; k++)
+		nm->slot_of_path.push_back(slot_id[key[k]]);
+	nm->pub = {{(uint32_t)nm->ref_path.size(), nm->ref_path.data(), (uint32_t)nm->sample_of_slot.size(), (uint32_t)nm->sample.size(),
+		    nm->sample_of_slot.data()},
+		   n_paths, nm->slot_of_path.data(), nm->sample_ptr.data()};
+	return &nm.release()->pub;
+} catch (const std::bad_alloc &) {
+	set_err(err, errlen, "call names: out of memory");
+	return nullptr;
+}
+
+extern "C" void povu_hip_call_names_free(povu_hip_call_names *n) { delete reinterpret_cast<Names *>(n); }
+
+extern "C" int povu_hip_sites_add_tree(povu_hip_sites *s, uint32_t tree, uint32_t n, const uint32_t *id1, const uint32_t *id2,
+				       const uint8_t *or1, const uint8_t *or2, const uint32_t *parent, const uint8_t *family)
+try {
+	if (!s || (n && (!id1 || !id2 || !or1 || !or2 || !parent)) || (uint64_t)s->n + n >= POVU_HIP_NIL)
+		return 1;
+	auto root = [&](uint32_t v) { return family ? family[v] == 'D' : v == 0; };
+	auto up = [&](uint32_t v) { return root(v) || parent[v] >= n ? POVU_HIP_NIL : parent[v]; };
+	// heights without recursion, whatever the order of the vertices: walk up to the first vertex seen before, number the
+	// chain on the way back (a vertex on a cycle of parent pointers counts as seen with height 0: the walk ends)
+	std::vector<uint32_t> qnum(n, POVU_HIP_NIL), height(n, 0), chain;
+	std::vector<char> seen(n, 0);
+	uint32_t m = s->n;
+	for (uint32_t v = 0; v < n; v++) {
+		if (!root(v))
+			qnum[v] = m++;
+		for (uint32_t u = v; u != POVU_HIP_NIL && !seen[u]; u = up(u)) {
+			seen[u] = 1;
+			chain.push_back(u);
+		}
+		for (; !chain.empty(); chain.pop_back())
+			height[chain.back()] = up(chain.back()) == POVU_HIP_NIL ? 0 : height[up(chain.back())] + 1;
+	}
+	if (!grow(s->id1, m) || !grow(s->id2, m) || !grow(s->or1, m) || !grow(s->or2, m) || !grow(s->parent, m) || !grow(s->height, m) ||
+	    !grow(s->family, m) || !grow(s->tree, m))
+		return 1;
+	for (uint32_t v = 0; v < n; v++) {
+		const uint32_t q = qnum[v];
+		if (q == POVU_HIP_NIL)
+			continue;
+		const_cast<uint32_t *>(s->id1)[q] = id1[v];
+		const_cast<uint32_t *>(s->id2)[q] = id2[v];
+		const_cast<uint8_t *>(s->or1)[q] = or1[v];
+		const_cast<uint8_t *>(s->or2)[q] = or2[v];
+		const_cast<uint32_t *>(s->parent)[q] = up(v) == POVU_HIP_NIL ? POVU_HIP_NIL : qnum[up(v)];
+		const_cast<uint32_t *>(s->height)[q] = height[v];
+		const_cast<uint8_t *>(s->family)[q] = family ? family[v] : (uint8_t)'F';
+		const_cast<uint32_t *>(s->tree)[q] = tree;
+	}
+	s->n = m;
+	return 0;
+} catch (const std::bad_alloc &) {
+	return 1;
+}
+
+extern "C" povu_hip_sites *povu_hip_sites_of_docs(const povu_pvst_doc *const *docs, uint32_t n)
+{
+	auto *s = static_cast<povu_hip_sites *>(calloc(1, sizeof(povu_hip_sites)));
+	for (uint32_t k = 0; s && k < n; k++) {
+		const povu_pvst_doc *d = docs[k];
+		if (!d || povu_hip_sites_add_tree(s, k, d->n, d->a_id, d->z_id, d->a_or, d->z_or, d->parent, (const uint8_t *)d->type)) {
+			povu_hip_sites_free(s);
+			s = nullptr;
+		}
+	}
+	return s;
+}
+
+extern "C" void povu_hip_sites_free(povu_hip_sites *s)
+{
+	if (!s)
+		return;
+	for (const void *p : {(const void *)s->id1, (const void *)s->id2, (const void *)s->or1, (const void *)s->or2, (const void *)s->parent,
+			      (const void *)s->height, (const void *)s->family, (const void *)s->tree})
+		free(const_cast<void *>(p));
+	free(s);
+}
+
+extern "C" char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
+				    const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, size_t *len)
+try {
+	if (!c || !sites || !names || !path_name || !len || c->n_slots != names->refs.n_slots || c->n_refs != names->refs.n_refs)
+		return nullptr;
+	const uint64_t n = c->n_records, S = c->n_slots;
+	const uint32_t P = names->n_paths, n_samples = names->refs.n_samples;
+	for (uint64_t i = 0; i < n; i++)
+		if (c->query[i] >= sites->n || c->path[i] >= P)
+			return nullptr;
+	std::vector<uint32_t> slot_first(n_samples + 1, 0); // (the slots of a sample are consecutive)
+	for (uint32_t sl = 0; sl < S; sl++) {
+		if (names->refs.sample_of_slot[sl] >= n_samples)
+			return nullptr;
+		slot_first[names->refs.sample_of_slot[sl] + 1] = sl + 1;
+	}
+	char today[16];
+	if (!date) {
+		const time_t t = time(nullptr);
+		struct tm tmv;
+		localtime_r(&t, &tmv);
+		strftime(today, sizeof today, "%Y%m%d", &tmv);
+		date = today;
+	}
+	// ---- header, a contig line per reference path of the prefix, the column line
+	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER;
+	std::vector<char> keep(P, 0);
+	for (uint32_t r = 0; r < names->refs.n_refs; r++) {
+		const uint32_t p = names->refs.ref_path[r];
+		if (p >= P)
+			return nullptr;
+		if (only_prefix && strncmp(path_name[p], only_prefix, strlen(only_prefix)))
+			continue;
+		keep[p] = 1;
+		head += std::string("##contig=<ID=") + path_name[p] + ",length=" + std::to_string(c->contig_len[r]) + ">\n";
+	}
+	head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
+	for (uint32_t sm = 0; sm < n_samples; sm++)
+		head += std::string("\t") + names->sample[sm];
+	head += "\n";
+	// ---- the records as text, in chunks of records on up to `threads` threads
+	const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>(threads, (n + 1023) / 1024));
+	std::vector<std::string> chunk(T);
+	auto format = [&](int t) {
+		std::string &o = chunk[t];
+		const uint64_t lo = n * t / T, hi = n * (t + 1) / T;
+		std::vector<uint64_t> order;
+		std::string label;
+		char num[32];
+		for (uint64_t i = lo; i < hi; i++) {
+			if (!keep[c->path[i]])
+				continue;
+			const uint32_t q = c->query[i], na = c->n_alleles[i], ra = c->ref_allele[i];
+			const uint64_t b = c->block_off[c->block[i]];
+			order.clear();
+			order.push_back(b + ra); // REF first, the others in the query's allele order
+			for (uint32_t a = 0; a < na; a++)
+				if (a != ra)
+					order.push_back(b + a);
+			label = (sites->or1[q] ? "<" : ">") + std::to_string(sites->id1[q]) + (sites->or2[q] ? "<" : ">") + std::to_string(sites->id2[q]);
+			o += path_name[c->path[i]];
+			o += '\t';
+			o += std::to_string(c->pos[i]);
+			o += '\t';
+			o += label;
+			for (size_t k = 0; k < order.size(); k++) {
+				o += k <= 1 ? '\t' : ',';
+				o.append(c->seq + c->seq_off[order[k]], c->seq_off[order[k] + 1] - c->seq_off[order[k]]);
+			}
+			o += "\t60\tPASS\tAC=";
+			const uint64_t a0 = c->ac_off[i], a1 = c->ac_off[i + 1];
+			const uint32_t an = c->an[i];
+			for (uint64_t k = a0; k < a1; k++)
+				o += (k > a0 ? "," : "") + std::to_string(c->ac[k]);
+			o += ";AF=";
+			for (uint64_t k = a0; k < a1; k++) {
+				snprintf(num, sizeof num, "%.1f", an ? (double)c->ac[k] / an : 0.0);
+				o += (k > a0 ? "," : "");
+				o += num;
+			}
+			o += ";AN=" + std::to_string(an) + ";NS=" + std::to_string(c->ns[i]) + ";AT=";
+			for (size_t k = 0; k < order.size(); k++) {
+				if (k)
+					o += ',';
+				o.append(c->at + c->at_off[order[k]], c->at_off[order[k] + 1] - c->at_off[order[k]]);
+			}
+			const uint8_t f = c->flags[i];
+			o += (f & POVU_HIP_CALL_INS) ? ";VARTYPE=INS" : (f & POVU_HIP_CALL_DEL) ? ";VARTYPE=DEL" : ";VARTYPE=SUB";
+			o += (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
+			o += ";ES=" + label + ";LV=" + std::to_string((long)sites->height[q] - 1) + "\tGT";
+			const uint16_t *row = c->gt + i * S;
+			for (uint32_t sm = 0; sm < n_samples; sm++) {
+				o += '\t';
+				bool any = false;
+				for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++)
+					any |= row[sl] != POVU_HIP_GT_MISSING;
+				if (!any) {
+					o += '.';
+					continue;
+				}
+				for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++) {
+					if (sl > slot_first[sm])
+						o += '|';
+					o += row[sl] == POVU_HIP_GT_MISSING ? "." : std::to_string(row[sl]);
+				}
+			}
+			o += '\n';
+		}
+	};
+	auto on_threads = [&](auto &&work) {
+		std::vector<std::thread> th;
+		for (int t = 1; t < T; t++)
+			th.emplace_back(work, t);
+		work(0);
+		for (auto &x : th)
+			x.join();
+	};
+	on_threads(format);
+	// ---- one buffer: every thread copies its own chunk into place (the pages of a large text are first touched in parallel)
+	std::vector<size_t> first(T + 1, head.size());
+	for (int t = 0; t < T; t++)
+		first[t + 1] = first[t] + chunk[t].size();
+	const size_t total = first[T];
+	char *out = static_cast<char *>(malloc(total + 1));
+	if (!out)
+		return nullptr;
+	head.copy(out, head.size());
+	on_threads([&](int t) { chunk[t].copy(out + first[t], chunk[t].size()); });
+	char *at = out + total;
+	*at = 0;
+	*len = total;
+	return out;
+} catch (const std::bad_alloc &) {
+	return nullptr;
+}

@@ -78,13 +78,19 @@ class _Traversals(C.Structure):
 
 
 class _Sites(C.Structure):
-    _fields_ = [("n", C.c_uint32), ("id1", C.c_void_p), ("id2", C.c_void_p), ("or1", C.c_void_p), ("or2", C.c_void_p),
-                ("parent", C.c_void_p), ("height", C.c_void_p), ("family", C.c_void_p), ("tree", C.c_void_p)]
+    _fields_ = [("n", C.c_uint32), ("id1", C.POINTER(C.c_uint32)), ("id2", C.POINTER(C.c_uint32)), ("or1", C.POINTER(C.c_uint8)),
+                ("or2", C.POINTER(C.c_uint8)), ("parent", C.POINTER(C.c_uint32)), ("height", C.POINTER(C.c_uint32)),
+                ("family", C.POINTER(C.c_uint8)), ("tree", C.POINTER(C.c_uint32))]
 
 
 class _CallRefs(C.Structure):
-    _fields_ = [("n_refs", C.c_uint32), ("ref_path", C.c_void_p), ("n_slots", C.c_uint32), ("n_samples", C.c_uint32),
-                ("sample_of_slot", C.c_void_p)]
+    _fields_ = [("n_refs", C.c_uint32), ("ref_path", C.POINTER(C.c_uint32)), ("n_slots", C.c_uint32), ("n_samples", C.c_uint32),
+                ("sample_of_slot", C.POINTER(C.c_uint32))]
+
+
+class _CallNames(C.Structure):
+    _fields_ = [("refs", _CallRefs), ("n_paths", C.c_uint32), ("slot_of_path", C.POINTER(C.c_uint32)),
+                ("sample", C.POINTER(C.c_char_p))]
 
 
 class _Calls(C.Structure):
@@ -175,10 +181,22 @@ def load_lib():
     l.povu_hip_forest_first.restype = C.c_uint64
     l.povu_hip_segments_upload.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
     l.povu_hip_segments_upload.restype = C.c_int
-    l.povu_hip_call.argtypes = [C.c_void_p, C.POINTER(_Sites), C.POINTER(_CallRefs), C.c_void_p, C.POINTER(_TravOpts), C.c_char_p,
-                                C.c_size_t]
+    l.povu_hip_call.argtypes = [C.c_void_p, C.POINTER(_Sites), C.POINTER(_CallRefs), C.POINTER(C.c_uint32), C.POINTER(_TravOpts),
+                                C.c_char_p, C.c_size_t]
     l.povu_hip_call.restype = C.POINTER(_Calls)
     l.povu_hip_calls_free.argtypes = [C.POINTER(_Calls)]
+    l.povu_hip_call_names_make.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_char_p,
+                                           C.c_size_t]
+    l.povu_hip_call_names_make.restype = C.POINTER(_CallNames)
+    l.povu_hip_call_names_free.argtypes = [C.POINTER(_CallNames)]
+    l.povu_hip_sites_of_docs.argtypes = [C.c_void_p, C.c_uint32]  # (an array of povu_pvst_doc pointers)
+    l.povu_hip_sites_of_docs.restype = C.POINTER(_Sites)
+    l.povu_hip_forest_sites.argtypes = [C.c_void_p]
+    l.povu_hip_forest_sites.restype = C.POINTER(_Sites)
+    l.povu_hip_sites_free.argtypes = [C.POINTER(_Sites)]
+    l.povu_hip_calls_vcf.argtypes = [C.POINTER(_Calls), C.POINTER(_Sites), C.POINTER(_CallNames), C.POINTER(C.c_char_p), C.c_char_p,
+                                     C.c_char_p, C.c_uint32, C.POINTER(C.c_size_t)]
+    l.povu_hip_calls_vcf.restype = C.c_void_p
     l.povu_hip_forest_first.argtypes = [C.c_void_p, C.c_uint32]
     l.povu_hip_forest_pvst_text.restype = C.c_void_p
     l.povu_hip_forest_pvst_text.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]
@@ -417,6 +435,14 @@ class Forest:
                     n_smothered=st.n_smothered, fam=a8(st.fam), or1=a8(st.or1), or2=a8(st.or2), route=a8(st.route),
                     id1=a32(st.id1), id2=a32(st.id2), child_off=off - lo, child=child)
 
+    def sites(self) -> "Sites":
+        """The sites of this forest (povu_hip_forest_sites): every PVST vertex but the roots, the extended trees of -s when
+        the forest carries them."""
+        p = self._lib.povu_hip_forest_sites(self._h)
+        if not p:
+            raise RuntimeError("cannot build the sites of this forest")
+        return Sites(self._lib, p)
+
     def raw(self):
         """Zero-copy view of the whole result: (uint8 block over the pinned host memory, total entries,
         byte offsets of a_id/z_id/parent/a_or/z_or, header int64 [n_trees, 3] = (component id, n_pvst, first))."""
@@ -640,53 +666,40 @@ class Shards:
         return buf
 
 
-VCF_HEADER = (
-    "##fileformat=VCFv4.2\n##fileDate={date}\n##source=povu\n"
-    '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">\n'
-    '##INFO=<ID=AC,Number=A,Type=Integer,Description="Total number of alternate alleles in called genotypes">\n'
-    '##INFO=<ID=AT,Number=R,Type=String,Description="Allele traversal path through the graph">\n'
-    '##INFO=<ID=AN,Number=1,Type=String,Description="Total number of alleles in called genotypes">\n'
-    '##INFO=<ID=AF,Number=A,Type=Float,Description="Allele frequency in the population">\n'
-    '##INFO=<ID=NS,Number=1,Type=Integer,Description="Number of samples with data">\n'
-    '##INFO=<ID=VARTYPE,Number=1,Type=String,Description="Type of variation: INS (insertion), DEL (deletion), '
-    'SUB (substitution), SUBR(substitution in reverse) ">\n'
-    '##INFO=<ID=TANGLED,Number=1,Type=String,Description="Variant lies in a tangled region of the graph: T or F">\n'
-    '##INFO=<ID=LV,Number=1,Type=Integer,Description="Level in the PVST (0=top level)">\n'
-    '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">\n')
 CALL_ANCHORED, CALL_TANGLED, CALL_INS, CALL_DEL = 1, 2, 4, 8
 GT_MISSING = 0xFFFF
 
 
-def pansn_slots(names):
-    """(samples in order of their first path, slot of every path, sample of every slot): a name `sample#hap#rest` with an
-    all-digit hap is that sample's slot `hap` (slots ascending), any other name a sample of its own."""
-    samples, haps = [], {}
+class Sites:
+    """The sites of a forest (its queries; Forest.sites()): numpy views of the arrays of povu_hip_sites -- id1 / or1 / id2 / or2,
+    parent (a query, 0xFFFFFFFF under the root), height, family (the line letter's byte), tree -- valid as long as this
+    object lives."""
 
-    def key(n):
-        f = n.split("#")
-        return (f[0], int(f[1])) if len(f) >= 3 and f[1].isdigit() else (n, -1)
-    for n in names:
-        sm, h = key(n)
-        if sm not in haps:
-            samples.append(sm)
-            haps[sm] = set()
-        haps[sm].add(h)
-    slot, sample_of = {}, []
-    for si, sm in enumerate(samples):
-        for h in sorted(haps[sm]):
-            slot[(sm, h)] = len(sample_of)
-            sample_of.append(si)
-    return samples, [slot[key(n)] for n in names], sample_of
+    def __init__(self, lib, ptr):
+        self._lib, self._p = lib, ptr
+        s = ptr.contents
+        self.n = int(s.n)
+        for k, dt in (("id1", np.uint32), ("id2", np.uint32), ("or1", np.uint8), ("or2", np.uint8), ("parent", np.uint32),
+                      ("height", np.uint32), ("family", np.uint8), ("tree", np.uint32)):
+            setattr(self, k, _view(getattr(s, k), self.n, dt))
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            self._lib.povu_hip_sites_free(self._p)
+            self._p = None
 
 
 class Calls:
     """Variant calls (HipDecomposer.call): numpy views of the flat arrays of povu_hip_call, valid as long as this object
-    lives, and vcf_text()."""
+    lives, and vcf_text().  It keeps the names record (povu_hip_call_names) and the sites it was made from alive."""
 
-    def __init__(self, lib, ptr, names, refs, samples, sites):
+    def __init__(self, lib, ptr, names, names_rec, name_array, sites):
         self._lib, self._p = lib, ptr
-        c = ptr.contents
-        self.names, self.refs, self.samples, self._sites = names, refs, samples, sites
+        self._names_rec, self._name_array, self._sites = names_rec, name_array, sites
+        c, nr = ptr.contents, names_rec.contents
+        self.names = names
+        self.refs = [int(nr.refs.ref_path[k]) for k in range(nr.refs.n_refs)]
+        self.samples = [nr.sample[k].decode() for k in range(nr.refs.n_samples)]
         self.n_records, self.n_slots = int(c.n_records), int(c.n_slots)
         self.device_ms = float(c.device_ms)
         self.n_seq_bytes, self.n_at_bytes = int(c.n_seq_bytes), int(c.n_at_bytes)
@@ -703,90 +716,28 @@ class Calls:
         self.at_off = _view(c.at_off, nsp + 1, np.uint64)
         self.seq = _view(c.seq, self.n_seq_bytes, np.uint8)
         self.at = _view(c.at, self.n_at_bytes, np.uint8)
-        self.contig_len = _view(c.contig_len, len(refs), np.uint64)
+        self.contig_len = _view(c.contig_len, len(self.refs), np.uint64)
 
     def __del__(self):
         if getattr(self, "_p", None):
             self._lib.povu_hip_calls_free(self._p)
             self._p = None
+        if getattr(self, "_names_rec", None):
+            self._lib.povu_hip_call_names_free(self._names_rec)
+            self._names_rec = None
 
-    def _alleles(self, i):
-        """(spelled bases, AT strings) of record i, REF first."""
-        b, na, ra = int(self.block[i]), int(self.n_alleles[i]), int(self.ref_allele[i])
-        first = int(self.block_off[b])
-        order = [ra] + [a for a in range(na) if a != ra]
-        seq = self.seq.tobytes()
-        at = self.at.tobytes()
-        j = [first + a for a in order]
-        return ([seq[int(self.seq_off[k]):int(self.seq_off[k + 1])].decode() for k in j],
-                [at[int(self.at_off[k]):int(self.at_off[k + 1])].decode() for k in j])
-
-    def record_line(self, i, sample_of_slot) -> str:
-        st = self._sites[int(self.query[i])]
-        bases, ats = self._alleles(i)
-        a0, a1 = int(self.ac_off[i]), int(self.ac_off[i + 1])
-        ac = [int(x) for x in self.ac[a0:a1]]
-        an = int(self.an[i])
-        f = int(self.flags[i])
-        vt = "INS" if f & CALL_INS else "DEL" if f & CALL_DEL else "SUB"
-        lbl = st["label"]
-        info = (f"AC={','.join(map(str, ac))};AF={','.join('%.1f' % (x / an) for x in ac)};AN={an};NS={int(self.ns[i])};"
-                f"AT={','.join(ats)};VARTYPE={vt};TANGLED={'T' if f & CALL_TANGLED else 'F'};ES={lbl};LV={st['height'] - 1}")
-        gt = []
-        row = self.gt[i]
-        for sm in range(len(self.samples)):
-            vals = [int(row[sl]) for sl in range(self.n_slots) if sample_of_slot[sl] == sm]
-            gt.append("." if all(v == GT_MISSING for v in vals) else "|".join("." if v == GT_MISSING else str(v) for v in vals))
-        return "\t".join([self.names[int(self.path[i])], str(int(self.pos[i])), lbl, bases[0], ",".join(bases[1:]), "60", "PASS",
-                          info, "GT"] + gt)
-
-    def vcf_text(self, date=None) -> str:
-        """One VCF of every reference path: header (fileDate today unless given), contig lines, records."""
-        import datetime
-        if date is None:
-            date = datetime.date.today().strftime("%Y%m%d")
-        _, _, sample_of = pansn_slots(self.names)
-        out = [VCF_HEADER.format(date=date)]
-        out += [f"##contig=<ID={self.names[r]},length={int(self.contig_len[k])}>\n" for k, r in enumerate(self.refs)]
-        out.append("\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"] + self.samples) + "\n")
-        out += [self.record_line(i, sample_of) + "\n" for i in range(self.n_records)]
-        return "".join(out)
-
-
-def forest_sites(forest: "Forest"):
-    """The sites of a forest (its queries): per query s, z, parent (query number, -1 for a child of the root), height, fam,
-    tree, label; the extended trees of -s when the forest carries them."""
-    out = []
-    for i in range(len(forest)):
-        try:
-            t = forest.subtree(i)
-            n = t["n_total"]
-            par = [-1] * n
-            for v in range(n):
-                for c in t["child"][t["child_off"][v]:t["child_off"][v + 1]]:
-                    par[int(c)] = v
-            id1, or1, id2, or2, fam = t["id1"], t["or1"], t["id2"], t["or2"], [chr(int(x)) for x in t["fam"]]
-        except RuntimeError:
-            t = forest.tree(i)
-            n = len(t.a_id)
-            par = [int(x) if v else -1 for v, x in enumerate(t.parent)]
-            try:  # (the T / O letters of --leaf-subflubbles: those vertices are skipped like the PVST lines)
-                fam = [chr(int(x)) for x in forest.sub(i)[2]]
-            except RuntimeError:
-                fam = ["F"] * n
-            id1, or1, id2, or2 = t.a_id, t.a_or, t.z_id, t.z_or
-        base = len(out) - 1
-        height = [0] * n
-
-        def h(v):
-            if v > 0 and not height[v]:
-                height[v] = h(par[v]) + 1
-            return height[v]
-        for v in range(1, n):
-            s, z = (int(id1[v]), int(or1[v])), (int(id2[v]), int(or2[v]))
-            lbl = (">" if s[1] == 0 else "<") + str(s[0]) + (">" if z[1] == 0 else "<") + str(z[0])
-            out.append(dict(s=s, z=z, parent=-1 if par[v] <= 0 else base + par[v], height=h(v), fam=fam[v], tree=i, label=lbl))
-    return out
+    def vcf_text(self, date=None, only=None, threads: int = 1) -> str:
+        """One VCF of every reference path (povu_hip_calls_vcf): header (fileDate today unless given), contig lines, records;
+        with `only` those of the reference paths whose name starts with it."""
+        ln = C.c_size_t(0)
+        p = self._lib.povu_hip_calls_vcf(self._p, self._sites._p, self._names_rec, self._name_array,
+                                         None if date is None else str(date).encode(), None if only is None else only.encode(),
+                                         threads, C.byref(ln))
+        if not p:
+            raise RuntimeError("the calls, sites and names do not belong together")
+        s = C.string_at(p, ln.value).decode()
+        self._lib.povu_hip_buffer_free(p)
+        return s
 
 
 class HipDecomposer:
@@ -977,28 +928,22 @@ class HipDecomposer:
         names = self._path_names
         if isinstance(refs, str):
             refs = [refs]
-        ref_paths = [k for k, n in enumerate(names) if any(n.startswith(p) for p in refs)]
-        if not ref_paths:
-            raise RuntimeError("no path name starts with any of the reference prefixes " + ", ".join(refs))
-        samples, slot, sample_of = pansn_slots(names)
-        sites = forest_sites(forest)
-        u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32)  # noqa: E731
-        u8 = lambda x: np.ascontiguousarray(x, dtype=np.uint8)  # noqa: E731
-        arr = dict(id1=u32([st["s"][0] for st in sites]), id2=u32([st["z"][0] for st in sites]),
-                   or1=u8([st["s"][1] for st in sites]), or2=u8([st["z"][1] for st in sites]),
-                   parent=u32([0xFFFFFFFF if st["parent"] < 0 else st["parent"] for st in sites]),
-                   height=u32([st["height"] for st in sites]), family=u8([ord(st["fam"]) for st in sites]),
-                   tree=u32([st["tree"] for st in sites]))
-        ptr = lambda a: a.ctypes.data if a.size else None  # noqa: E731
-        st = _Sites(len(sites), *[ptr(arr[k]) for k in ("id1", "id2", "or1", "or2", "parent", "height", "family", "tree")])
-        rp, sl, so = u32(ref_paths), u32(slot), u32(sample_of)
-        rf = _CallRefs(len(ref_paths), ptr(rp), len(sample_of), len(samples), ptr(so))
-        o = _TravOpts(max_steps, flags)
+        name_array = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        prefixes = (C.c_char_p * max(len(refs), 1))(*[p.encode() for p in refs])
         err = C.create_string_buffer(512)
-        p = self._lib.povu_hip_call(self._ctx, C.byref(st), C.byref(rf), ptr(sl), C.byref(o), err, 512)
-        if not p:
+        nr = self._lib.povu_hip_call_names_make(len(names), name_array, len(refs), prefixes, err, 512)
+        if not nr:
             raise RuntimeError(err.value.decode())
-        return Calls(self._lib, p, names, ref_paths, samples, sites)
+        try:
+            sites = forest.sites()
+            o = _TravOpts(max_steps, flags)
+            p = self._lib.povu_hip_call(self._ctx, sites._p, C.byref(nr.contents.refs), nr.contents.slot_of_path, C.byref(o), err, 512)
+            if not p:
+                raise RuntimeError(err.value.decode())
+        except Exception:
+            self._lib.povu_hip_call_names_free(nr)
+            raise
+        return Calls(self._lib, p, names, nr, name_array, sites)
 
     def traversals(self, forest: Forest, max_steps: int = 65536, flags: int = 0) -> Traversals:
         """The traversals of every flubble of `forest` by the resident paths, on the GPU."""

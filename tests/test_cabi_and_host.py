@@ -520,8 +520,9 @@ def test_pvst_reader_subflubble_lines():
 
 
 def test_host_code_under_address_and_ub_sanitizers(golden_dir, tmp_path):
-    """The tokenizer and the PVST reader under -fsanitize=address,undefined (CPU build; the GPU pool has no sanitizer
-    runs) over every golden input, the malformed fixtures and truncated PVST texts."""
+    """The tokenizer, the PVST reader and the call's host half (sites of every PVST that parses; names and the VCF writer on a
+    hand-made povu_hip_calls) under -fsanitize=address,undefined (CPU build; the GPU pool has no sanitizer runs) over every
+    golden input, the malformed fixtures and truncated PVST texts."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     subprocess.check_call(["make", "-C", os.path.join(root, "povu_amd", "csrc"), "asan", "-s"])
     exe = os.path.join(root, "build", "obj", "host_asan_check")

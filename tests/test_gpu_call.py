@@ -38,7 +38,15 @@ def _check(d, g, paths, prefixes, flags=0, tflags=0, seed=1, max_len=300):
     c = d.call(f, prefixes, flags=tflags)
     steps = [paths.steps(k) for k in range(len(paths))]
     sq = dict(zip(g.vid.tolist(), seqs))
-    sites = H.forest_sites(f)
+    # the yardstick's own sites, from the forest's PVST texts; the library's sites (povu_hip_forest_sites) equal them
+    sites = V.sites_of_pvst([f.text(i) for i in range(len(f))])
+    got = f.sites()
+    assert got.n == len(sites)
+    for k, col in (("id1", [s["s"][0] for s in sites]), ("or1", [s["s"][1] for s in sites]), ("id2", [s["z"][0] for s in sites]),
+                   ("or2", [s["z"][1] for s in sites]), ("parent", [s["parent"] & 0xFFFFFFFF for s in sites]),
+                   ("height", [s["height"] for s in sites]), ("family", [ord(s["fam"]) for s in sites]),
+                   ("tree", [s["tree"] for s in sites])):
+        assert getattr(got, k).tolist() == col, k
     want = V.call(sites, list(paths.names), steps, sq, prefixes)
     assert c.n_records == len(want)
     assert [(int(c.path[i]), int(c.pos[i]), int(c.query[i]), int(c.first[i])) for i in range(c.n_records)] == \

@@ -3,7 +3,8 @@ of `povu call`.
 
 Built on traversals_ref (the traversals and alleles of every query).  Sites are the queries with what the call needs of
 their PVST vertex: `sites_of_pvst` reads PVST texts (component order), `sites_of_trees` a forest's arrays.  `call` gives
-the records (dicts) and `vcf_text` the VCF.
+the records (dicts; `slots` holds the allele of every genotype slot in record numbering, None for '.') and `vcf_text` the
+VCF.
 """
 from __future__ import annotations
 
@@ -227,7 +228,7 @@ def call(sites, names, paths, seqs: Dict[int, str], prefixes, max_steps=TR.DEFAU
             vt = "SUB" if not anchored else "INS" if inner_len[ra] == 0 else "DEL"
             recs.append(dict(path=pi, q=q, first=first, chrom=names[pi], pos=pos, id=label(st["s"], st["z"]),
                              ref=texts[0], alts=texts[1:], at=ats, vartype=vt, tangled=tangled, lv=st["height"] - 1,
-                             gt=gt, ac=ac, an=an, ns=ns))
+                             gt=gt, slots=gts, ac=ac, an=an, ns=ns))
     recs.sort(key=lambda r: (r["path"], r["pos"], r["q"], r["first"]))
     return recs
 
