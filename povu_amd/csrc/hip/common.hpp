@@ -348,6 +348,15 @@ __device__ __forceinline__ bool bitrank_test(const uint4 *__restrict__ rec, uint
 	const uint4 r = rec[x >> 6];
 	return (((x & 32u) ? r.y : r.x) >> (x & 31u)) & 1u;
 }
+// Component of a candidate-stack entry, looked up instead of stored (a word per entry was 0.4 GB written and as much read
+// by every consumer).  Entry i belongs to the last non-empty component that starts at or before i: `rec` is a bit-rank
+// directory over the stack positions with a bit where a non-empty component starts, `list` those components in order.
+// The cost is the same for 24 large components and for a million tiny ones: one 16-byte look-up and one word.
+struct StackComp {
+	const uint4 *rec;
+	const uint32_t *list;
+	__device__ __forceinline__ uint32_t operator()(uint32_t i) const { return list[bitrank(rec, i + 1) - 1u]; }
+};
 // spreads the low 16 bits of x to every fourth bit position (bit k -> bit 4 k)
 __device__ __forceinline__ unsigned long long spread4(unsigned long long x)
 {

@@ -245,7 +245,7 @@ __global__ void k_leaf_flubbles(const LeafIn in, LeafOut out)
 	uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
 	if (j >= in.NE)
 		return;
-	const uint32_t i = in.e_i[j], c = in.s_comp[i], base = 2 * in.voff[c] + c, N = in.c_ntree[c];
+	const uint32_t i = in.e_i[j], c = in.comp_of(i), base = 2 * in.voff[c] + c, N = in.c_ntree[c];
 	const uint32_t va = in.s_vtx[i], vz = in.s_vtx[in.ns[i]];
 	// compute_ai_zi, flubbles.cpp:264-290: the middle two of the four end vertices of the two boundary tree edges
 	uint32_t v[4] = {va, in.gp[va], vz, in.gp[vz]};
@@ -256,7 +256,7 @@ __global__ void k_leaf_flubbles(const LeafIn in, LeafOut out)
 	out.zi[q] = zi - base;
 	// the next emitted flubble is this one's child iff it lies deeper (k_pvst_emit: parent = nearest earlier flubble
 	// with a smaller level)
-	const bool leaf = !(j + 1 < in.NE && in.s_comp[in.e_i[j + 1]] == c && in.lev[j + 1] > in.lev[j]);
+	const bool leaf = !(j + 1 < in.NE && in.comp_of(in.e_i[j + 1]) == c && in.lev[j + 1] > in.lev[j]);
 	out.fam[q] = leaf_label(in, ai, zi, base, N, leaf);
 }
 __global__ void k_leaf_roots(uint32_t C, const uint32_t *__restrict__ c_ntree, const uint32_t *__restrict__ doff, LeafOut out)
@@ -393,7 +393,7 @@ void leaf_prepare(const CompState &cs, const SeqWs &sw, const ParWs &pw, const T
 	in.cproc_ps = pw.cproc_ps;
 	in.e_i = pw.e_i;
 	in.lev = pw.lev;
-	in.s_comp = pw.s_comp;
+	in.comp_of = pw.stack_comp();
 	in.s_vtx = pw.s_vtx;
 	in.ns = pw.ns;
 	in.t_size = sw.t_size;

@@ -21,7 +21,8 @@ struct LeafOut {
 struct LeafIn {
 	uint32_t NE, C;
 	const uint32_t *voff, *c_ntree, *cproc_ps;
-	const uint32_t *e_i, *lev, *s_comp, *s_vtx, *ns;
+	const uint32_t *e_i, *lev, *s_vtx, *ns;
+	StackComp comp_of; // component of a candidate-stack entry (common.hpp)
 	const uint32_t *t_size, *gp, *nchild;
 	const uint8_t *t_flags;
 	const uint32_t *out_ord, *in_ord, *nself, *in_ext;

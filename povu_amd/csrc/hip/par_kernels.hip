@@ -492,7 +492,7 @@ __global__ void k_gather_u32(uint32_t n, const uint32_t *__restrict__ idx, const
 // where the candidate-stack entry of a black vertex goes (row E worked out before the class pass)
 struct StackPlace {
 	const uint32_t *voff, *soff, *dlt, *dlt_ps;
-	uint32_t *s_vtx, *s_comp;
+	uint32_t *s_vtx;
 };
 // BLACK: only the child ends of black tree edges take part (n = V of them: segment slot g of component c is tree
 // vertex 2g + c + [dummy root] + 1, the opposite side follows the entered side in pre-order) -- the candidate stack
@@ -524,12 +524,11 @@ __global__ void k_top_bracket(uint32_t n, const uint32_t *__restrict__ gsize, co
 		return;
 	}
 	// BLACK: everything downstream lives in candidate-stack order, so the sort carries the entry's stack index and the
-	// entry itself (its tree vertex, its component) is written here; lsz is indexed by stack position too
+	// entry itself (its tree vertex) is written here; lsz is indexed by stack position too
 	uint32_t at = v;
 	if (BLACK) {
 		at = sp.soff[c] + (g - sp.voff[c]) + sp.dlt_ps[g] + sp.dlt[g];
-		sp.s_vtx[at] = v;
-		sp.s_comp[at] = c;
+		sp.s_vtx[at] = v; // (its component is looked up where it is needed: StackComp)
 	}
 	cval[q] = at;
 	uint32_t m = mpre[v];
@@ -644,7 +643,7 @@ __global__ void k_stack_emit(uint32_t V, const uint32_t *__restrict__ seg_comp, 
 			     const uint32_t *__restrict__ voff, const uint32_t *__restrict__ soff,
 			     const uint32_t *__restrict__ dlt, const uint32_t *__restrict__ dlt_ps,
 			     const uint32_t *__restrict__ gsize, const uint32_t *__restrict__ gcls,
-			     uint32_t *__restrict__ s_vtx, uint32_t *__restrict__ s_cls, uint32_t *__restrict__ s_comp,
+			     uint32_t *__restrict__ s_vtx, uint32_t *__restrict__ s_cls,
 			     uint32_t *__restrict__ sidx, uint32_t *__restrict__ ns, uint32_t *__restrict__ prev)
 {
 	uint32_t g = BIDX * blockDim.x + threadIdx.x;
@@ -656,7 +655,6 @@ __global__ void k_stack_emit(uint32_t V, const uint32_t *__restrict__ seg_comp, 
 	const uint32_t i = soff[c] + (g - voff[c]) + dlt_ps[g] + dlt[g];
 	s_vtx[i] = b;
 	s_cls[i] = gcls[b];
-	s_comp[i] = c;
 	sidx[b] = i;
 	ns[i] = i; // "no later occurrence" until k_next_from_runs says otherwise (flubbles.cpp:391-399)
 	prev[i] = NIL;
@@ -684,14 +682,18 @@ __global__ void k_next_from_runs(uint32_t T, const uint32_t *__restrict__ mark, 
 	prev[id] = iu;
 }
 
+// The flag byte of a candidate-stack entry: bit 0 = it opens a flubble (D), bit 1 = its class occurred before (U).
+static constexpr uint32_t DF_OPENS = 1u, DF_SEEN = 2u;
 // BLACK pass, all in one: next_seen / prev and the "opens a flubble" flag of the entry at sorted position q, written at
 // its stack index (the sort's payload).  Consecutive entries of a run are consecutive members of a class (deeper
 // first), so next_seen[u] = the entry before it in the run, prev[u] = the entry after it.  Nothing downstream needs the
 // classes as numbers; the debug hooks number them on demand (k_class_ids_black).
 __global__ void k_class_finish_black(uint32_t n, uint32_t S, const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sval,
 				     const uint32_t *__restrict__ lsz, uint8_t *__restrict__ flag, uint32_t *__restrict__ ns,
-				     uint32_t *__restrict__ prev, uint8_t *__restrict__ dflag)
+				     uint32_t *__restrict__ prev, bool write_prev, uint8_t *__restrict__ dflag)
 {
+	// prev is a word per entry at scattered addresses, and with exact classes all the walk asks of it is "is there one":
+	// that goes into bit 1 (DF_SEEN) of the flag byte written anyway.  Only the laminarity check reads the word itself.
 	// Four sorted positions a lane (the sorted keys, the stack indices and the flags move in 16-byte words), and the
 	// "opens a new class" flags (k_class_flags<true>: a bracket hands out a new class whenever the list size differs from
 	// the one it saw last, flubbles.cpp:668-676) are worked out right here, for the four and the one behind them.
@@ -731,8 +733,11 @@ __global__ void k_class_finish_black(uint32_t n, uint32_t S, const uint32_t *__r
 		fw |= (fresh[j] ? 1u : 0u) << (8 * (j - 1));
 		const uint32_t nx = fresh[j] ? u : U[j - 1];
 		ns[u] = nx;
-		prev[u] = (K[j + 1] != NIL && !fresh[j + 1]) ? U[j + 1] : NIL;
-		dflag[u] = (u + 1 < nx) ? 1 : 0; // entry u opens a flubble iff its class comes back later than at the next entry
+		const bool seen = K[j + 1] != NIL && !fresh[j + 1];
+		if (write_prev)
+			prev[u] = seen ? U[j + 1] : NIL;
+		// entry u opens a flubble iff its class comes back later than at the next entry
+		dflag[u] = (uint8_t)(((u + 1 < nx) ? DF_OPENS : 0u) | (seen ? DF_SEEN : 0u));
 	}
 	if (q0 + 4 <= n) {
 		*reinterpret_cast<uint32_t *>(flag + q0) = fw;
@@ -796,52 +801,57 @@ __device__ __forceinline__ void laminar_check_one(uint32_t i, uint32_t p, const 
 	if (lowest < p)
 		xflag[i] = 1; // (cleared by the caller)
 }
-__global__ void k_laminar_walk(uint32_t S, const uint32_t *__restrict__ prev, const SegTree segP, bool check,
-			       const uint32_t *__restrict__ s_comp, const uint32_t *__restrict__ soff, uint8_t *__restrict__ xflag,
-			       const uint8_t *__restrict__ dflag, uint32_t *__restrict__ walk)
+__global__ void k_laminar_walk(uint32_t S, const uint32_t *__restrict__ prev, const SegTree segP, bool check, const StackComp comp_of,
+			       const uint32_t *__restrict__ soff, uint8_t *__restrict__ xflag, const uint8_t *__restrict__ dflag,
+			       uint32_t *__restrict__ walk)
 {
-	// four entries a lane (16-byte loads and one 16-byte store: a kernel of a few loads per element is bound by the memory
-	// instructions it issues)
+	// four entries a lane (one 4-byte load of their flag bytes and one 16-byte store: a kernel of a few loads per element is
+	// bound by the memory instructions it issues).  U and D are bits of the flag bytes; where a component starts is a bit of
+	// the component directory, and only there (a few thousand entries) the component in front is looked up.  prev is read
+	// by the laminarity check alone.
 	const uint32_t i0 = (BIDX * blockDim.x + threadIdx.x) * 4u;
 	if (i0 >= S)
 		return;
+	// the drop in front of a component's first entry: further than the walk of the component before it can have moved
+	auto drop = [&](uint32_t i) { return 2 * (i - soff[comp_of(i - 1)]) + 2; };
 	if (i0 + 4 <= S) {
-		const uint4 p4 = *reinterpret_cast<const uint4 *>(prev + i0), c4 = *reinterpret_cast<const uint4 *>(s_comp + i0);
-		const uint32_t d4 = *reinterpret_cast<const uint32_t *>(dflag + i0); // D of the entries i0 .. i0 + 3
-		const uint32_t cm = i0 ? s_comp[i0 - 1] : c4.x, dm = i0 ? dflag[i0 - 1] : 0u;
-		const uint32_t ps[4] = {p4.x, p4.y, p4.z, p4.w}, cs[5] = {cm, c4.x, c4.y, c4.z, c4.w};
-		const uint32_t ds[4] = {dm, d4 & 0xFFu, (d4 >> 8) & 0xFFu, (d4 >> 16) & 0xFFu}; // D of the entry before each
+		const uint32_t d4 = *reinterpret_cast<const uint32_t *>(dflag + i0); // flags of the entries i0 .. i0 + 3
+		const uint32_t dm = i0 ? dflag[i0 - 1] : 0u;
+		const uint4 r = comp_of.rec[i0 >> 6]; // (i0 is a multiple of four: one record holds the four bits)
+		const uint32_t starts = (((i0 & 32u) ? r.y : r.x) >> (i0 & 31u)) & 15u;
+		const uint32_t dprev = (dm & DF_OPENS) | ((d4 & 0x00010101u) << 8); // byte j: D of the entry before entry i0 + j
 		uint32_t w[4];
 #pragma unroll
 		for (uint32_t j = 0; j < 4; j++) {
 			const uint32_t i = i0 + j;
-			uint32_t step = ps[j] != NIL ? 0xFFFFFFFFu : 0u; // U: -1
+			uint32_t step = ((d4 >> (8 * j)) & DF_SEEN) ? 0xFFFFFFFFu : 0u; // U: -1
 			if (i > 0) {
-				step += ds[j]; // D of the entry before
-				if (cs[j] != cs[j + 1])
-					step -= 2 * (i - soff[cs[j]]) + 2;
+				step += (dprev >> (8 * j)) & 1u; // D of the entry before
+				if ((starts >> j) & 1u)
+					step -= drop(i);
 			}
 			w[j] = step;
 		}
 		*reinterpret_cast<uint4 *>(walk + i0) = make_uint4(w[0], w[1], w[2], w[3]);
-		if (check) // (!check: the class stage was exact, the intervals are laminar by construction)
-#pragma unroll
-			for (uint32_t j = 0; j < 4; j++)
-				laminar_check_one(i0 + j, ps[j], prev, segP, xflag);
+		if (check) { // (!check: the class stage was exact, the intervals are laminar by construction)
+			const uint4 p4 = *reinterpret_cast<const uint4 *>(prev + i0);
+			laminar_check_one(i0, p4.x, prev, segP, xflag);
+			laminar_check_one(i0 + 1, p4.y, prev, segP, xflag);
+			laminar_check_one(i0 + 2, p4.z, prev, segP, xflag);
+			laminar_check_one(i0 + 3, p4.w, prev, segP, xflag);
+		}
 		return;
 	}
 	for (uint32_t i = i0; i < S; i++) {
-		const uint32_t p = prev[i];
-		uint32_t step = p != NIL ? 0xFFFFFFFFu : 0u; // U: -1
+		uint32_t step = (dflag[i] & DF_SEEN) ? 0xFFFFFFFFu : 0u; // U: -1
 		if (i > 0) {
-			step += dflag[i - 1]; // D of the entry before
-			const uint32_t cp = s_comp[i - 1];
-			if (cp != s_comp[i])
-				step -= 2 * (i - soff[cp]) + 2;
+			step += dflag[i - 1] & DF_OPENS; // D of the entry before
+			if (bitrank_test(comp_of.rec, i))
+				step -= drop(i);
 		}
 		walk[i] = step;
 		if (check)
-			laminar_check_one(i, p, prev, segP, xflag);
+			laminar_check_one(i, prev[i], prev, segP, xflag);
 	}
 }
 // the flagged entries of every component, in stack order (xlist is ascending): crossed ones get xflag 2 and their U undone
@@ -905,40 +915,74 @@ __global__ void k_walk_bias(uint32_t n, const uint32_t *walk, const uint32_t *ps
 	}
 }
 // entry i opens a flubble iff its class comes back later than at the next entry (flubbles.cpp:344)
-__global__ void k_dflag(uint32_t S, const uint32_t *__restrict__ ns, uint8_t *__restrict__ dflag)
+// (all-vertex class pass: next_seen and prev were scattered by k_next_from_runs; the flag byte takes both bits here)
+__global__ void k_dflag(uint32_t S, const uint32_t *__restrict__ ns, const uint32_t *__restrict__ prev, uint8_t *__restrict__ dflag)
 {
 	uint32_t i = BIDX * blockDim.x + threadIdx.x;
 	if (i < S)
-		dflag[i] = (i + 1 < ns[i]) ? 1 : 0;
+		dflag[i] = (uint8_t)(((i + 1 < ns[i]) ? DF_OPENS : 0u) | (prev[i] != NIL ? DF_SEEN : 0u));
 	if (i == S)
 		dflag[S] = 0;
+}
+// The "opens a flubble" bits of the flag bytes as a bit-rank directory (common.hpp): "flubbles emitted in front of entry i"
+// is then one 16-byte look-up into S / 4 bytes, where a 4-byte prefix per entry was written once and gathered by four
+// kernels.  Four entries a lane, whole waves; positions from S on (stale bytes of an earlier, larger pass) read as 0.
+__global__ void __launch_bounds__(TPB) k_pack_opens(uint32_t S, const uint8_t *__restrict__ dflag, uint4 *__restrict__ erec)
+{
+	const uint32_t i0 = (BIDX * blockDim.x + threadIdx.x) * 4u;
+	uint32_t f = 0;
+	if (i0 + 4 <= S) {
+		const uint32_t d4 = *reinterpret_cast<const uint32_t *>(dflag + i0);
+		f = (d4 & 1u) | ((d4 >> 7) & 2u) | ((d4 >> 14) & 4u) | ((d4 >> 21) & 8u);
+	} else {
+		for (uint32_t i = i0; i < S; i++)
+			f |= (dflag[i] & DF_OPENS) << (i - i0);
+	}
+	const uint32_t w0 = (BIDX * blockDim.x + (threadIdx.x & ~63u)) / 16u; // first record of this wave's 256 entries
+	bitrank_store_wave(erec + w0, f, w0 + (threadIdx.x & 63u) <= S / 64u);
+}
+// The component directory (StackComp, common.hpp): a bit where a non-empty component's entries start (the records were
+// cleared), and, once the bits are ranked, the list of those components.  soff is the host's table; components that are not
+// decomposed have empty ranges and leave no trace.
+__global__ void k_comp_starts(uint32_t C, const uint32_t *__restrict__ soff, uint4 *__restrict__ crec)
+{
+	const uint32_t c = BIDX * blockDim.x + threadIdx.x;
+	if (c >= C)
+		return;
+	const uint32_t i = soff[c];
+	if (i < soff[c + 1])
+		atomicOr(reinterpret_cast<uint32_t *>(crec + (i >> 6)) + ((i >> 5) & 1u), 1u << (i & 31u));
+}
+__global__ void k_comp_list(uint32_t C, const uint32_t *__restrict__ soff, const uint4 *__restrict__ crec, uint32_t *__restrict__ clist)
+{
+	const uint32_t c = BIDX * blockDim.x + threadIdx.x;
+	if (c < C && soff[c] < soff[c + 1])
+		clist[bitrank(crec, soff[c])] = c;
 }
 // Endpoints and orientations of every flubble straight into the (page-locked host) PVST arrays.  They only depend on
 // the candidate stack and next_seen, so this kernel runs on the context's side stream while the main stream still
 // computes levels and parents: the PCIe writes (10 of the 14 bytes per PVST vertex) hide behind that work.  A small
 // grid-stride launch: a few ten thousand lanes keep the link busy and leave the CUs to the main stream.
-__global__ void __launch_bounds__(TPB) k_emit_endpoints(uint32_t S, const uint8_t *__restrict__ dflag, const uint32_t *__restrict__ erank,
-							 const uint32_t *__restrict__ s_comp, const uint32_t *__restrict__ ns,
+__global__ void __launch_bounds__(TPB) k_emit_endpoints(uint32_t S, const uint4 *__restrict__ erec, const StackComp comp_of,
+							 const uint32_t *__restrict__ ns,
 							 const uint32_t *__restrict__ s_vtx, const uint8_t *__restrict__ tf,
 							 const uint32_t *__restrict__ t_gid, const uint32_t *__restrict__ cproc_ps,
 							 uint32_t *__restrict__ p_a, uint32_t *__restrict__ p_z, uint8_t *__restrict__ p_aor,
 							 uint8_t *__restrict__ p_zor)
 {
-	// Only one entry in four or five opens a flubble.  A wave reads the flags of 256 entries (four a lane, one load),
+	// Only one entry in four or five opens a flubble.  A wave reads the flags of 256 entries (four bits a lane, out of their record),
 	// lists the ones that do in LDS, and then every lane takes one of THOSE: the ten gathers behind an emitted flubble run
 	// with full waves instead of waves that are four fifths idle.
 	__shared__ uint32_t list[TPB / 64][256];
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 	for (uint32_t b0 = blockIdx.x * (4u * TPB); b0 < S; b0 += gridDim.x * (4u * TPB)) { // (uniform per workgroup: the barriers below are safe)
 		const uint32_t i0 = b0 + wave * 256u + lane * 4u;
-		uint32_t fl = 0;
-		if (i0 + 4 <= S) {
-			fl = *reinterpret_cast<const uint32_t *>(dflag + i0);
-		} else {
-			for (uint32_t k = 0; i0 + k < S && k < 4; k++)
-				fl |= (dflag[i0 + k] ? 1u : 0u) << (8 * k);
+		uint32_t fl = 0; // (the directory holds no bits from S on, but its records end at S / 64)
+		if (i0 < S) {
+			const uint4 r = erec[i0 >> 6];
+			fl = (((i0 & 32u) ? r.y : r.x) >> (i0 & 31u)) & 15u;
 		}
-		const uint32_t cnt = ((fl & 0xFFu) ? 1u : 0u) + ((fl & 0xFF00u) ? 1u : 0u) + ((fl & 0xFF0000u) ? 1u : 0u) + ((fl & 0xFF000000u) ? 1u : 0u);
+		const uint32_t cnt = (uint32_t)__popc(fl);
 		uint32_t inc = cnt;
 		for (int off = 1; off < 64; off <<= 1) {
 			const uint32_t y = __shfl_up(inc, off);
@@ -949,13 +993,13 @@ __global__ void __launch_bounds__(TPB) k_emit_endpoints(uint32_t S, const uint8_
 		uint32_t at = inc - cnt;
 #pragma unroll
 		for (uint32_t k = 0; k < 4; k++)
-			if ((fl >> (8 * k)) & 0xFFu)
+			if ((fl >> k) & 1u)
 				list[wave][at++] = i0 + k;
 		__syncthreads();
 		for (uint32_t k = lane; k < total; k += 64) {
 			const uint32_t i = list[wave][k];
 			// dense output slot: flubbles emitted before + one root per earlier component, + 1 for this component's root
-			const uint64_t q = (uint64_t)erank[i] + cproc_ps[s_comp[i]] + 1;
+			const uint64_t q = (uint64_t)bitrank(erec, i) + cproc_ps[comp_of(i)] + 1;
 			uint32_t va = s_vtx[i], vz = s_vtx[ns[i]];
 			uint32_t ra = ((tf[va] & TF_TYPE_MASK) == 1) ? 0u : 1u, rz = ((tf[vz] & TF_TYPE_MASK) == 1) ? 0u : 1u;
 			if (ra && rz) { // normalize_endpoints, flubbles.cpp:233-244
@@ -974,67 +1018,67 @@ __global__ void __launch_bounds__(TPB) k_emit_endpoints(uint32_t S, const uint8_
 	}
 }
 // level of every emitted flubble
-__global__ void k_levels(uint32_t S, const uint8_t *__restrict__ dflag, const uint32_t *__restrict__ erank,
-			 const uint32_t *__restrict__ s_comp, const uint32_t *__restrict__ soff,
+__global__ void k_levels(uint32_t S, const uint4 *__restrict__ erec, const StackComp comp_of, const uint32_t *__restrict__ soff,
 			 const uint32_t *__restrict__ wb, const uint32_t *__restrict__ negmax,
 			 uint32_t *__restrict__ lev, uint32_t *__restrict__ e_i)
 {
-	// four entries a lane: one load says which of them open a flubble (one in four or five does)
+	// four entries a lane: their record says which of them open a flubble (one in four or five does) and how many did
+	// in front of them (the directory holds no bits from S on)
 	const uint32_t i0 = (BIDX * blockDim.x + threadIdx.x) * 4u;
 	if (i0 >= S)
 		return;
-	uint32_t fl = 0;
-	if (i0 + 4 <= S) {
-		fl = *reinterpret_cast<const uint32_t *>(dflag + i0);
-	} else {
-		for (uint32_t k = 0; i0 + k < S; k++)
-			fl |= (dflag[i0 + k] ? 1u : 0u) << (8 * k);
-	}
+	const uint4 r = erec[i0 >> 6];
+	const unsigned long long bits = (unsigned long long)r.x | ((unsigned long long)r.y << 32);
+	const uint32_t fl = (uint32_t)(bits >> (i0 & 63u)) & 15u;
+	if (!fl)
+		return;
+	uint32_t j = r.z + (uint32_t)__popcll(bits & ((1ull << (i0 & 63u)) - 1ull));
 #pragma unroll
 	for (uint32_t k = 0; k < 4; k++) {
-		if (!((fl >> (8 * k)) & 0xFFu))
+		if (!((fl >> k) & 1u))
 			continue;
-		const uint32_t i = i0 + k, c = s_comp[i], f0 = soff[c];
+		const uint32_t i = i0 + k, c = comp_of(i), f0 = soff[c];
 		// zero of this component's walk = its value at the component's first entry (after the drop B_c, before any U or D)
 		const uint32_t zero = wb[f0];
 		// running minimum up to i (negmax = exclusive running maximum of ~wb): everything in front of f0 lies above `zero`
 		const uint32_t cur = wb[i], run = min(cur, ~negmax[i]);
-		const uint32_t j = erank[i];
 		lev[j] = cur + 1 - min(zero, run); // depth of the new flubble (>= 1): the walk after this entry's own D
 		e_i[j] = i;
+		j++;
 	}
 }
 // PVST parent of every flubble = nearest earlier flubble of its component with a smaller level
 __global__ void k_pvst_emit(uint32_t NE, const uint32_t *__restrict__ lev, const uint32_t *__restrict__ e_i,
-			    const SegTree segL, const uint32_t *__restrict__ s_comp,
-			    const uint32_t *__restrict__ soff, const uint32_t *__restrict__ erank,
+			    const SegTree segL, const StackComp comp_of, const uint32_t *__restrict__ doff,
 			    const uint32_t *__restrict__ cproc_ps, uint32_t *__restrict__ p_parent)
 {
 	uint32_t j = BIDX * blockDim.x + threadIdx.x;
 	if (j >= NE)
 		return;
-	uint32_t i = e_i[j], c = s_comp[i], jb = erank[soff[c]];
+	// dense slot of the component's root (k_pvst_counts): flubbles emitted before + one root per earlier component
+	const uint32_t i = e_i[j], c = comp_of(i);
+	const uint64_t pb = doff[c];
+	const uint32_t jb = (uint32_t)pb - cproc_ps[c]; // first flubble of the component
 	uint32_t jp = seg_last_less(segL, jb, j, lev[j]);
-	uint64_t pb = (uint64_t)jb + cproc_ps[c]; // dense: flubbles emitted before + one root per earlier component
 	p_parent[pb + 1 + (j - jb)] = jp == NIL ? 0u : 1 + (jp - jb);
 }
 // per component: where its PVST starts in the dense output, its size, its stack entries -- everything the host needs for
 // the forest's tree table, known as soon as the "opens a flubble" flags are ranked (before the result block exists)
 __global__ void k_pvst_counts(uint32_t C, const uint32_t *__restrict__ c_ntree, const uint32_t *__restrict__ soff,
-			      const uint32_t *__restrict__ erank, const uint32_t *__restrict__ cproc_ps, uint32_t *__restrict__ doff,
+			      const uint4 *__restrict__ erec, const uint32_t *__restrict__ cproc_ps, uint32_t *__restrict__ doff,
 			      uint32_t *__restrict__ c_npvst, uint32_t *__restrict__ c_nstack)
 {
 	uint32_t c = BIDX * blockDim.x + threadIdx.x;
 	if (c > C)
 		return;
-	doff[c] = erank[soff[c]] + cproc_ps[c];
+	doff[c] = bitrank(erec, soff[c]) + cproc_ps[c];
 	if (c == C)
 		return;
 	if (c_ntree[c] == 0) {
 		c_npvst[c] = 0;
 		return;
 	}
-	c_npvst[c] = 1 + (erank[soff[c + 1]] - erank[soff[c]]);
+	c_npvst[c] = 1 + (bitrank(erec, soff[c + 1]) - bitrank(erec, soff[c]));
 	c_nstack[c] = soff[c + 1] - soff[c];
 }
 // the root vertex of every PVST (flubbles.cpp:736-741)
@@ -1051,7 +1095,7 @@ __global__ void k_pvst_roots(uint32_t C, const uint32_t *__restrict__ c_ntree, c
 	p_aor[pb] = p_zor[pb] = 0;
 }
 // copies of the parallel results into the per-component layout the debug hooks read
-__global__ void k_export_stack(uint32_t S, const uint32_t *__restrict__ s_comp, const uint32_t *__restrict__ soff,
+__global__ void k_export_stack(uint32_t S, const StackComp comp_of, const uint32_t *__restrict__ soff,
 			       const uint32_t *__restrict__ voff, const uint32_t *__restrict__ s_vtx,
 			       const uint32_t *__restrict__ s_cls, const uint32_t *__restrict__ ns,
 			       uint32_t *__restrict__ o_vtx, uint32_t *__restrict__ o_cls, uint32_t *__restrict__ o_ns)
@@ -1059,7 +1103,7 @@ __global__ void k_export_stack(uint32_t S, const uint32_t *__restrict__ s_comp, 
 	uint32_t i = BIDX * blockDim.x + threadIdx.x;
 	if (i >= S)
 		return;
-	uint32_t c = s_comp[i], l = i - soff[c], base = 2 * voff[c] + c;
+	uint32_t c = comp_of(i), l = i - soff[c], base = 2 * voff[c] + c;
 	o_vtx[voff[c] + l] = s_vtx[i] - base;
 	o_cls[voff[c] + l] = s_cls[i];
 	o_ns[voff[c] + l] = ns[i] - soff[c];
@@ -1208,8 +1252,13 @@ static void for_each_span(ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 		else if (groups & 2)
 			skip(p);
 	}
-	for (uint32_t **p : {&pw.s_vtx, &pw.s_cls, &pw.s_comp, &pw.ns, &pw.prev, &pw.erank, &pw.lev, &pw.e_i})
+	for (uint32_t **p : {&pw.s_vtx, &pw.s_cls, &pw.ns, &pw.prev, &pw.lev, &pw.e_i})
 		take((void **)p, (S + 2) * 4);
+	// the two directories over the stack positions [0, S]: S / 64 + 1 records and the closing one (+ one of slack)
+	take((void **)&pw.erec, (S / 64 + 3) * 16);
+	take((void **)&pw.crec, (S / 64 + 3) * 16);
+	take((void **)&pw.rk_cnt, (S / 64 + 3) * 4);
+	take((void **)&pw.clist, (Cmax + 2) * 4);
 	take((void **)&pw.walk, (S + 4) * 4);
 	take((void **)&pw.walk_ps, (S + 4) * 4);
 	take((void **)&pw.wrun, (S + 4) * 4);
@@ -1425,7 +1474,7 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 		}
 		uint32_t *shift_ps = pw.topi; // (dlt_ps still holds the bracket range starts; nobody needs vertex -> stack index here)
 		scan(sdl, shift_ps, (size_t)V + 1);
-		const StackPlace sp{cs.voff, pw.soff, sdl, shift_ps, pw.s_vtx, pw.s_comp};
+		const StackPlace sp{cs.voff, pw.soff, sdl, shift_ps, pw.s_vtx};
 		LAUNCH(k_top_bracket<true>, NC, s, NC, pw.gsize, pw.gpar, pw.mpre, bstart, pw.segB, pw.tgtR, pw.psin, ck,
 		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, NB0 + ncap, nullptr, cs.ckey, sw.c_ntree, sp);
 		sort_pairs_u32(ck, ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
@@ -1433,15 +1482,16 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 		tm.end(30 + 2 * 22);
 		tm.begin("par_stack");
 		// (the class flags are worked out by the same kernel: invalid entries carry NIL and sort behind every valid key)
+		// (black_only: the literal hi_2 rule did not fire, so the laminarity check -- prev's one reader -- runs only on request)
 		LAUNCH(k_class_finish_black, std::max<size_t>(((size_t)NC + 3) / 4, 1), s, NC, S, ck2, pw.vals_t2, pw.lsz, cflag, pw.ns, pw.prev,
-		       dflag);
+		       pw.check_laminar, dflag);
 		tm.end(1);
 		tm.begin("par_next_seen"); // (folded into the kernel above)
 		tm.end(0);
 		pw.gcls_valid = false;
 		pw.s_cls_valid = false; // (cflag, the sorted keys and their stack indices stay where they are for stack_class_ids)
 	} else {
-		const StackPlace none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+		const StackPlace none{nullptr, nullptr, nullptr, nullptr, nullptr};
 		LAUNCH(k_top_bracket<false>, NC, s, NC, pw.gsize, pw.gpar, pw.mpre, bstart, pw.segB, pw.tgtR, pw.psin, ck,
 		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, NB0 + ncap, want_hp ? pw.hpf : nullptr, nullptr, nullptr, none);
 		sort_pairs_u32(ck, ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
@@ -1460,7 +1510,7 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 		// one candidate-stack entry per black tree edge = per segment of a processed component: the host knows where
 		// every component's entries start (pw.soff) and the total
 		LAUNCH(k_stack_emit, V, s, V, cs.ckey, sw.c_ntree, cs.voff, pw.soff, pw.dlt, pw.dlt_ps, pw.gsize, pw.gcls, pw.s_vtx, pw.s_cls,
-		       pw.s_comp, pw.topi, pw.ns, pw.prev);
+		       pw.topi, pw.ns, pw.prev);
 		tm.end(9);
 
 		// ---- row F
@@ -1469,15 +1519,23 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 		scan_exclusive_max_u32(mark, lastb, T, pw.scan_tmp, pw.scan_tmp_bytes, s);
 		LAUNCH(k_next_from_runs, T, s, T, mark, lastb, pw.vals_t2, pw.gcls, pw.topi, pw.ns, pw.prev);
 		tm.end(4);
-		LAUNCH(k_dflag, (size_t)S + 1, s, S, pw.ns, dflag);
+		LAUNCH(k_dflag, (size_t)S + 1, s, S, pw.ns, pw.prev, dflag);
 	}
 
 	// ---- row G
 	tm.begin("par_pvst");
-	scan8(dflag, pw.erank, (size_t)S + 1);
+	// the two directories over the stack positions: flubbles opened in front of an entry, and the entry's component
+	const size_t n_rec = (size_t)S / 64 + 1;
+	const StackComp comp_of = pw.stack_comp();
+	KLAUNCH(k_pack_opens, dim3(nblk(((size_t)S / 256 + 1) * 64)), dim3(TPB), 0, s, S, dflag, pw.erec); // (whole waves: every record of [0, S] is written)
+	bitrank_build(pw.erec, n_rec, pw.rk_cnt, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	HIP_CHECK(hipMemsetAsync(pw.crec, 0, n_rec * 16, s));
+	LAUNCH(k_comp_starts, (size_t)C, s, C, pw.soff, pw.crec);
+	bitrank_build(pw.crec, n_rec, pw.rk_cnt, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	LAUNCH(k_comp_list, (size_t)C, s, C, pw.soff, pw.crec, pw.clist);
 	// What the host needs to lay out the forest -- PVST size and offset of every component, the error words -- goes back in
 	// ONE read together with the PVST count: after this synchronisation only the PVST arrays themselves are still to come.
-	LAUNCH(k_pvst_counts, (size_t)C + 1, s, C, sw.c_ntree, pw.soff, pw.erank, pw.cproc_ps, pw.doff, sw.c_npvst, sw.c_nstack);
+	LAUNCH(k_pvst_counts, (size_t)C + 1, s, C, sw.c_ntree, pw.soff, pw.erec, pw.cproc_ps, pw.doff, sw.c_npvst, sw.c_nstack);
 	uint32_t *early = pw.host->take<uint32_t>(5 * (size_t)C + 8);
 	count_kernel_d2h((5 * (size_t)C + 8) * 4);
 	pass_summary(sw, &pw, C, early, s);
@@ -1497,7 +1555,7 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 		seg_build(pw.segP, pw.prev, S, s); // NIL (= +inf) where a class has no earlier occurrence
 		HIP_CHECK(hipMemsetAsync(xflag, 0, (size_t)S + 1, s));
 	}
-	LAUNCH(k_laminar_walk, ((size_t)S + 3) / 4, s, S, pw.prev, pw.segP, pw.laminar_checked, pw.s_comp, pw.soff, xflag, dflag, pw.walk);
+	LAUNCH(k_laminar_walk, ((size_t)S + 3) / 4, s, S, pw.prev, pw.segP, pw.laminar_checked, comp_of, pw.soff, xflag, dflag, pw.walk);
 	if (pw.laminar_checked && S) { // the entries whose interval is crossed: decided in stack order, U undone where the class was popped
 		uint32_t *xlist = pw.wrun, *n_x = pw.err + 11, *n_crossed = pw.err + 12; // (wrun is written by the max-scan below; err words cleared at the start of the pass)
 		compact_flagged_u8(xflag, S, xlist, n_x, pw.scan_tmp, pw.scan_tmp_bytes, s);
@@ -1509,7 +1567,7 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	uint32_t *wneg = pw.walk, *wrun = pw.wrun; // the steps themselves are dead after the bias kernel read them
 	LAUNCH(k_walk_bias, ((size_t)S + 3) / 4, s, S, pw.walk, pw.walk_ps, wb, wneg);
 	scan_exclusive_max_u32(wneg, wrun, (size_t)S, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	LAUNCH(k_levels, ((size_t)S + 3) / 4, s, S, dflag, pw.erank, pw.s_comp, pw.soff, wb, wrun, pw.lev, pw.e_i);
+	LAUNCH(k_levels, ((size_t)S + 3) / 4, s, S, pw.erec, comp_of, pw.soff, wb, wrun, pw.lev, pw.e_i);
 	pw.host->wait(early_ready);
 	const size_t total = early[4 + 4 * (size_t)C + C]; // doff[C] = flubbles + one root per processed component
 	if (total < n_processed || total - n_processed > S)
@@ -1540,8 +1598,8 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 		// (the roots' slots with the endpoints: the copies behind them take whole arrays)
 		HIP_CHECK(hipStreamWaitEvent(side.stream, side.fork, 0));
 		KLAUNCH(k_pvst_roots, dim3(nblk((size_t)C)), dim3(TPB), 0, side.stream, C, sw.c_ntree, pw.doff, pw.d_parent, pw.d_a, pw.d_z, pw.d_aor, pw.d_zor);
-		KLAUNCH(k_emit_endpoints, dim3(staged ? nblk((S + 3) / 4) : std::min<unsigned>(nblk((S + 3) / 4), 160)), dim3(TPB), 0, side.stream, S, dflag, pw.erank,
-			pw.s_comp, pw.ns, pw.s_vtx, sw.t_flags, sw.t_gid, pw.cproc_ps, pw.d_a, pw.d_z, pw.d_aor, pw.d_zor);
+		KLAUNCH(k_emit_endpoints, dim3(staged ? nblk((S + 3) / 4) : std::min<unsigned>(nblk((S + 3) / 4), 160)), dim3(TPB), 0, side.stream, S, pw.erec,
+			comp_of, pw.ns, pw.s_vtx, sw.t_flags, sw.t_gid, pw.cproc_ps, pw.d_a, pw.d_z, pw.d_aor, pw.d_zor);
 		if (staged) {
 			HIP_CHECK(copy_async(host_blk, blk, 2 * p4, hipMemcpyDeviceToHost, side.stream));
 			HIP_CHECK(copy_async(host_blk + 3 * p4, blk + 3 * p4, 2 * p1, hipMemcpyDeviceToHost, side.stream));
@@ -1549,11 +1607,11 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	} else {
 		LAUNCH(k_pvst_roots, (size_t)C, s, C, sw.c_ntree, pw.doff, pw.d_parent, pw.d_a, pw.d_z, pw.d_aor, pw.d_zor);
 		if (S)
-			KLAUNCH(k_emit_endpoints, dim3(nblk((S + 3) / 4)), dim3(TPB), 0, s, S, dflag, pw.erank, pw.s_comp, pw.ns, pw.s_vtx, sw.t_flags,
+			KLAUNCH(k_emit_endpoints, dim3(nblk((S + 3) / 4)), dim3(TPB), 0, s, S, pw.erec, comp_of, pw.ns, pw.s_vtx, sw.t_flags,
 				sw.t_gid, pw.cproc_ps, pw.d_a, pw.d_z, pw.d_aor, pw.d_zor);
 	}
 	seg_build(pw.segL, pw.lev, NE, s);
-	LAUNCH(k_pvst_emit, NE, s, NE, pw.lev, pw.e_i, pw.segL, pw.s_comp, pw.soff, pw.erank, pw.cproc_ps,
+	LAUNCH(k_pvst_emit, NE, s, NE, pw.lev, pw.e_i, pw.segL, comp_of, pw.doff, pw.cproc_ps,
 	       pw.d_parent);
 	// the parents follow the endpoints on the side stream (the copy engine takes one array after the other anyway): the main
 	// stream ends with its last kernel
@@ -1611,7 +1669,7 @@ void export_parallel_stack(const CompState &cs, SeqWs &sw, ParWs &pw, hipStream_
 {
 	stack_class_ids(pw, s);
 	const uint32_t S = pw.n_stack;
-	LAUNCH(k_export_stack, S, s, S, pw.s_comp, pw.soff, cs.voff, pw.s_vtx, pw.s_cls, pw.ns, sw.s_vtx, sw.s_cls,
+	LAUNCH(k_export_stack, S, s, S, pw.stack_comp(), pw.soff, cs.voff, pw.s_vtx, pw.s_cls, pw.ns, sw.s_vtx, sw.s_cls,
 	       sw.next_seen);
 }
 

@@ -52,10 +52,16 @@ struct ParWs {
 	uint32_t *b_key, *b_key2;	 // [NBmax] (only behind a sequential tree stage)
 	size_t nb_cap = 0;		 // entries the bracket arrays were carved for
 	// candidate stack space
-	uint32_t *s_vtx, *s_cls, *s_comp, *ns, *prev; // [V+1]
+	uint32_t *s_vtx, *s_cls, *ns, *prev; // [V+1] (prev: only written when the laminarity check runs or all vertices get a class)
 	uint32_t *soff;				     // [C+1] first stack entry of a component (host-built table, set by the caller)
 	uint32_t *walk, *walk_ps, *wrun; // [V+2] steps of the stack machine (one per entry), their prefix sums, running minimum (complemented)
-	uint32_t *erank, *lev, *e_i;	 // [V+1]
+	uint32_t *lev, *e_i;		 // [V+1]
+	// two bit-rank directories over the stack positions (common.hpp), (n_stack / 64 + 2) records each: erec counts the entries
+	// that open a flubble in front of a position, crec has a bit where a non-empty component starts; clist [C] names those
+	// components in order (StackComp), rk_cnt is the scratch of bitrank_build
+	uint4 *erec, *crec;
+	uint32_t *clist, *rk_cnt;
+	StackComp stack_comp() const { return StackComp{crec, clist}; }
 	uint32_t *comp_bad;		 // [C+1] components that must be redone sequentially
 	// dense PVST output (all processed components back to back): what goes over PCIe
 	uint32_t *cproc_ps, *doff;	 // [C+1] processed components before c; first dense PVST slot of c
