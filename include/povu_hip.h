@@ -376,6 +376,7 @@ typedef struct {
 	uint32_t flags;	    /* POVU_HIP_T_* */
 } povu_hip_trav_opts;
 #define POVU_HIP_T_FORCE_TIER2 1u /* run every scan with the wave-per-scan kernel (tests) */
+#define POVU_HIP_T_INVERSIONS 2u  /* povu_hip_call only: SUBR records too ("Inversion calls"); ignored elsewhere */
 #define POVU_HIP_TRAV_LONG 1u	  /* status bits per query: a scan would need more than max_steps steps */
 #define POVU_HIP_TRAV_STRAY 2u	  /* a scan met a boundary step that does not close it */
 #define POVU_HIP_TRAV_OPEN 4u	  /* a scan reached the end of its path */
@@ -431,6 +432,10 @@ typedef struct {
 #define POVU_HIP_CALL_TANGLED 2u
 #define POVU_HIP_CALL_INS 4u
 #define POVU_HIP_CALL_DEL 8u /* neither INS nor DEL: SUB */
+/* an inversion record (POVU_HIP_T_INVERSIONS): query = POVU_HIP_NIL, first = the step of `path` where the inverted run
+ * begins, n_steps its steps, ref_allele 0, n_alleles 2, one AC; its block holds REF (the run's bases) and then ALT (their
+ * reverse complement), the AT strings every step of the run and the flipped steps backwards */
+#define POVU_HIP_CALL_SUBR 16u
 #define POVU_HIP_GT_MISSING 0xFFFFu
 typedef struct {
 	uint64_t n_records, n_slots, n_blocks, n_spelled, n_seq_bytes, n_at_bytes, n_refs;
@@ -448,12 +453,20 @@ typedef struct {
 	const char *seq, *at;	   /* the bases (anchor base first when anchored) and the AT step strings ('>id<id...') */
 	const uint64_t *contig_len; /* [n_refs] bases of every reference path */
 	double device_ms;
+	/* with POVU_HIP_T_INVERSIONS (else n_steps all 0 and the counters 0) */
+	const uint32_t *n_steps; /* [n_records] steps of an inversion record's run, 0 for a flubble record */
+	uint64_t n_inv_records;	 /* records with POVU_HIP_CALL_SUBR */
+	uint64_t n_inv_heads;	 /* run heads found */
+	uint64_t n_inv_long;	 /* runs of more than max_steps steps (dropped) */
+	uint64_t n_inv_tier2;	 /* runs the wave-per-run kernel extended (longer than 64 steps, or all with _T_FORCE_TIER2) */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
  * site's boundary is no segment of the graph, for a query of more than 65 534 alleles in a called site, 2^32 records or
- * more, a spelled byte that is no nucleotide code (the message names the segment), and output beyond device memory.  Free
- * with povu_hip_calls_free. */
+ * more, a spelled byte that is no nucleotide code (the message names the segment), and output beyond device memory.  With
+ * POVU_HIP_T_INVERSIONS in opts->flags the inversion records of the reference paths against every other resident path are
+ * merged in ((reference path, POS, query, first, n_steps) order; `sites` may be empty); refused then too for 2^32 path
+ * steps or run heads or more.  Free with povu_hip_calls_free. */
 povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
 			      const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, char *err, size_t errlen);
 void povu_hip_calls_free(povu_hip_calls *c);
@@ -521,10 +534,11 @@ povu_hip_sites *povu_hip_sites_of_docs(const povu_pvst_doc *const *docs, uint32_
 povu_hip_sites *povu_hip_forest_sites(const povu_hip_forest *f);
 void povu_hip_sites_free(povu_hip_sites *s);
 /* The VCF of `c` (made by povu_hip_call from `sites` and `names`; path_name as given to _names_make): header, a contig line
- * per reference path, the column line, the records.  date NULL = today (%Y%m%d); only_prefix NULL = every reference, else the
- * contig lines and records of the reference paths whose name starts with it; the records are formatted in chunks on up to
- * `threads` threads (at least 1024 records each).  malloc'd, free with povu_hip_buffer_free; NULL on arguments that do not
- * belong together. */
+ * per reference path, the column line, the records (a POVU_HIP_CALL_SUBR record: ID from the first and last step of its
+ * REF AT string, both written '>' when both are '<'; VARTYPE=SUBR, no ES, no LV).  date NULL = today (%Y%m%d); only_prefix
+ * NULL = every reference, else the contig lines and records of the reference paths whose name starts with it; the records
+ * are formatted in chunks on up to `threads` threads (at least 1024 records each).  malloc'd, free with
+ * povu_hip_buffer_free; NULL on arguments that do not belong together. */
 char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
 			 const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, size_t *len);
 

@@ -16,73 +16,18 @@
 //   spelling           per (site, orientation) a record needs, every allele: lengths, u64 scans, then one wave per allele
 //                      copies the bases (reverse-complemented on '<' steps, lanes across a segment's bytes) and writes the
 //                      AT step string (lanes across steps, a wave prefix sum of their decimal widths).
-#include "query_common.hpp"
+#include "call_common.hpp"
 
 namespace povu_hip
 {
 
-static constexpr int C_TPB = 256;
 static constexpr int SC_E = 4, SC_N = C_TPB * SC_E; // u64 scan: elements per thread / per block
 static constexpr uint32_t MAX_ALLELES = 65534;
 static constexpr uint64_t ROLE = 1ull << 63; // (trav_kernels.hip: reverse traversals carry it in rpos)
-
-static inline unsigned cblk(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + C_TPB - 1) / C_TPB, 65536)); }
-static inline unsigned wblk(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 3) / 4, 65536)); } // a wave each
-
-// complement of a nucleotide code (ACGTN, lower case, IUPAC), 0 for any other byte
-__device__ __forceinline__ uint8_t comp(uint8_t c)
-{
-	const bool lower = c >= 'a' && c <= 'z';
-	uint8_t u = lower ? (uint8_t)(c - 32) : c, r;
-	switch (u) {
-	case 'A': r = 'T'; break;
-	case 'C': r = 'G'; break;
-	case 'G': r = 'C'; break;
-	case 'T': r = 'A'; break;
-	case 'N': r = 'N'; break;
-	case 'R': r = 'Y'; break;
-	case 'Y': r = 'R'; break;
-	case 'K': r = 'M'; break;
-	case 'M': r = 'K'; break;
-	case 'S': r = 'S'; break;
-	case 'W': r = 'W'; break;
-	case 'B': r = 'V'; break;
-	case 'V': r = 'B'; break;
-	case 'D': r = 'H'; break;
-	case 'H': r = 'D'; break;
-	default: return 0;
-	}
-	return lower ? (uint8_t)(r + 32) : r;
-}
-
-__device__ __forceinline__ uint32_t ndig(uint32_t x)
-{
-	uint32_t d = 1;
-	while (x >= 10) {
-		x /= 10;
-		d++;
-	}
-	return d;
-}
-
 // step k (S -> Z) of a traversal at path words [pos, pos + len), reversed and flipped when rev (as trav_kernels.hip reads it)
 __device__ __forceinline__ uint32_t tstep(const uint32_t *__restrict__ steps, uint64_t pos, uint32_t len, bool rev, uint32_t k)
 {
 	return rev ? steps[pos + len - 1 - k] ^ 1u : steps[pos + k];
-}
-
-// the last u with a[u] <= x, a ascending over [0, n)
-__device__ __forceinline__ uint32_t seg_of(const uint64_t *__restrict__ a, uint32_t n, uint64_t x)
-{
-	uint32_t lo = 0, hi = n;
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (a[mid] <= x)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
 }
 
 // ---- exclusive u64 scan: per block of SC_N an LDS scan, the block sums scanned recursively, then added
@@ -119,7 +64,7 @@ __global__ __launch_bounds__(C_TPB) void k_c64_add(uint64_t *out, size_t n, cons
 	for (size_t i = base + threadIdx.x; i < n && i < base + SC_N; i += C_TPB)
 		out[i] += o;
 }
-static size_t scan64_tmp(size_t n)
+size_t scan64_tmp(size_t n)
 {
 	size_t t = 2;
 	while (n > 1) {
@@ -128,8 +73,7 @@ static size_t scan64_tmp(size_t n)
 	}
 	return t;
 }
-// in == out allowed; tmp holds scan64_tmp(n) words
-static void scan64(const uint64_t *in, uint64_t *out, size_t n, uint64_t *tmp, hipStream_t s)
+void scan64(const uint64_t *in, uint64_t *out, size_t n, uint64_t *tmp, hipStream_t s)
 {
 	if (!n)
 		return;
@@ -328,32 +272,35 @@ __global__ void k_cl_key(uint32_t nrec, int which, const uint32_t *__restrict__ 
 	}
 }
 
-// per record (sorted): its fields, the ALT count for the AC offsets, the (site, orientation) it needs spelled
+// per record (sorted; row dst[i] of the record list when inversion records are merged in, else row i): its fields, the ALT count for the AC offsets, the (site, orientation) it needs spelled
 __global__ void k_cl_rec_fields(uint32_t nrec, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rlist, const uint64_t *__restrict__ pos,
 				const uint32_t *__restrict__ rq, const uint32_t *__restrict__ op, const uint32_t *__restrict__ of,
 				const uint32_t *__restrict__ oa, const uint8_t *__restrict__ orv, const uint32_t *__restrict__ aoff,
 				uint32_t *__restrict__ o_q, uint32_t *__restrict__ o_path, uint32_t *__restrict__ o_first,
 				uint32_t *__restrict__ o_ref, uint32_t *__restrict__ o_nal, uint64_t *__restrict__ o_pos, uint64_t *__restrict__ nalt,
-				uint32_t *__restrict__ need)
+				uint32_t *__restrict__ need, const uint32_t *__restrict__ dst)
 {
 	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < nrec; i += gridDim.x * C_TPB) {
-		const uint32_t j = perm[i], t = rlist[j], q = rq[t];
-		o_q[i] = q;
-		o_path[i] = op[t];
-		o_first[i] = of[t];
-		o_ref[i] = oa[t];
-		o_nal[i] = aoff[q + 1] - aoff[q];
-		o_pos[i] = pos[j];
-		nalt[i] = aoff[q + 1] - aoff[q] - 1;
+		const uint32_t j = perm[i], t = rlist[j], q = rq[t], d = dst ? dst[i] : i;
+		o_q[d] = q;
+		o_path[d] = op[t];
+		o_first[d] = of[t];
+		o_ref[d] = oa[t];
+		o_nal[d] = aoff[q + 1] - aoff[q];
+		o_pos[d] = pos[j];
+		nalt[d] = aoff[q + 1] - aoff[q] - 1;
 		need[2 * (size_t)q + orv[t]] = 1;
 	}
 }
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+// reference number and POS of the sorted records (the inversion records are merged in by them)
+__global__ void k_cl_sorted_keys(uint32_t nrec, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ op,
+				 const uint32_t *__restrict__ ref_of_path, const uint64_t *__restrict__ pos, uint32_t *__restrict__ f_ref,
+				 uint64_t *__restrict__ f_pos)
 {
-	for (int o = 32; o > 0; o >>= 1)
-		v += __shfl_xor(v, o, 64);
-	return v;
+	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < nrec; i += gridDim.x * C_TPB) {
+		f_ref[i] = ref_of_path[op[rlist[perm[i]]]];
+		f_pos[i] = pos[perm[i]];
+	}
 }
 
 // GT codes, AC, AN, NS and flags: one wave per record, a lane per sample (its slots are consecutive)
@@ -365,10 +312,11 @@ __global__ __launch_bounds__(C_TPB) void k_cl_records(uint32_t nrec, const uint3
 						      const uint32_t *__restrict__ qstatus, const uint8_t *__restrict__ anchored,
 						      const uint32_t *__restrict__ aoff, const uint64_t *__restrict__ ilen, uint16_t *__restrict__ gt,
 						      uint32_t *__restrict__ ac, uint32_t *__restrict__ an, uint32_t *__restrict__ ns,
-						      uint8_t *__restrict__ flags)
+						      uint8_t *__restrict__ flags, const uint32_t *__restrict__ dst)
 {
 	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (C_TPB / 64);
-	for (uint32_t i = blockIdx.x * (C_TPB / 64) + (threadIdx.x >> 6); i < nrec; i += waves) {
+	for (uint32_t i0 = blockIdx.x * (C_TPB / 64) + (threadIdx.x >> 6); i0 < nrec; i0 += waves) {
+		const uint32_t i = dst ? dst[i0] : i0;
 		const uint32_t q = o_q[i], ra = o_ref[i], own = slot_of_path[o_path[i]];
 		const uint64_t base = (uint64_t)qidx[q] * S;
 		uint32_t n_an = 0, n_ns = 0, amb = 0;
@@ -419,11 +367,11 @@ __global__ void k_cl_blocks(uint64_t n2, const uint32_t *__restrict__ need, cons
 }
 __global__ void k_cl_rec_block(uint32_t nrec, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rlist,
 			       const uint32_t *__restrict__ rq, const uint8_t *__restrict__ orv, const uint32_t *__restrict__ boff,
-			       uint32_t *__restrict__ o_block)
+			       uint32_t *__restrict__ o_block, const uint32_t *__restrict__ dst)
 {
 	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < nrec; i += gridDim.x * C_TPB) {
 		const uint32_t t = rlist[perm[i]];
-		o_block[i] = boff[2 * (size_t)rq[t] + orv[t]];
+		o_block[dst ? dst[i] : i] = boff[2 * (size_t)rq[t] + orv[t]];
 	}
 }
 __global__ void k_cl_block_cnt(uint32_t nb, const uint32_t *__restrict__ blist, const uint32_t *__restrict__ aoff, uint64_t *__restrict__ cnt)
@@ -496,14 +444,6 @@ __global__ __launch_bounds__(C_TPB) void k_cl_emit(uint64_t nsp, uint32_t nb, co
 		uint64_t w = s_off[j], wa = a_off[j];
 		const uint32_t m = s.len - 2; // inner steps
 		// the anchor: last base of the first step, and its step text
-		auto put_step = [&](uint32_t x, uint64_t at, uint32_t width) {
-			uint32_t id = vid[x >> 1];
-			o_at[at] = (x & 1u) ? '<' : '>';
-			for (uint32_t d = width - 1; d >= 1; d--) {
-				o_at[at + d] = (char)('0' + id % 10);
-				id /= 10;
-			}
-		};
 		if (an) {
 			const uint32_t v = s.first >> 1;
 			const uint64_t b0 = seq_off[v], b1 = seq_off[v + 1];
@@ -518,34 +458,10 @@ __global__ __launch_bounds__(C_TPB) void k_cl_emit(uint64_t nsp, uint32_t nb, co
 			}
 			const uint32_t width = 1 + ndig(vid[v]);
 			if (lane == 0)
-				put_step(s.first, wa, width);
+				put_step(o_at, vid, s.first, wa, width);
 			wa += width;
 		}
-		for (uint32_t k = 0; k < m; k++) {
-			const uint32_t x = inner_step(s, steps, k), v = x >> 1;
-			const uint64_t b0 = seq_off[v], n = seq_off[v + 1] - b0;
-			for (uint64_t i = lane; i < n; i += 64) {
-				const uint8_t c = (uint8_t)seq[(x & 1u) ? b0 + n - 1 - i : b0 + i], r = comp(c);
-				if (!r)
-					atomicMin(bad, (unsigned long long)v);
-				o_seq[w + i] = (char)((x & 1u) ? r : c);
-			}
-			w += n;
-		}
-		for (uint32_t k0 = 0; k0 < m; k0 += 64) {
-			const uint32_t k = k0 + lane;
-			const uint32_t x = k < m ? inner_step(s, steps, k) : 0;
-			const uint32_t width = k < m ? 1 + ndig(vid[x >> 1]) : 0;
-			uint32_t incl = width; // wave inclusive prefix sum of the widths
-			for (int o = 1; o < 64; o <<= 1) {
-				const uint32_t y = __shfl_up(incl, o, 64);
-				if ((int)lane >= o)
-					incl += y;
-			}
-			if (k < m)
-				put_step(x, wa + incl - width, width);
-			wa += __shfl(incl, 63, 64);
-		}
+		emit_steps(lane, m, [&](uint32_t k) { return inner_step(s, steps, k); }, seq_off, seq, vid, w, wa, o_seq, o_at, bad);
 	}
 }
 
@@ -602,7 +518,7 @@ namespace
 {
 struct CallsOwner {
 	povu_hip_calls view{}; // first member: the owner is recovered from it in povu_hip_calls_free
-	PinnedVec<uint32_t> query, path, first, ref_allele, n_alleles, an, ns, block, ac;
+	PinnedVec<uint32_t> query, path, first, ref_allele, n_alleles, an, ns, block, ac, n_steps;
 	PinnedVec<uint64_t> pos, ac_off, block_off, seq_off, at_off;
 	PinnedVec<uint8_t> flags;
 	PinnedVec<uint16_t> gt;
@@ -667,6 +583,7 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 			[&](CallTimer &tm, const QueryLayout &more) { return query_front(ctx, qa, qz, qor, ctx->tr_ws, tm, more); },
 			opts, timer);
 		const uint32_t R = d.R, n_al = d.n_al;
+		const bool inversions = opts && (opts->flags & POVU_HIP_T_INVERSIONS);
 
 		// ---- the reference steps
 		std::vector<uint64_t> path_off((size_t)P + 1), ref_base((size_t)nR + 1, 0);
@@ -773,21 +690,21 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 		check_call_32(nrec, "records");
 		uint64_t ref_bases = 0;
 		HIP_CHECK(copy_async(&ref_bases, roff + NR, 8, hipMemcpyDeviceToHost, s));
-		const size_t r1 = (size_t)nrec + 1;
+		const uint32_t nfl = nrec; // the flubble records; nrec: all records
 		// the per-record arrays and the spelling's inputs (cl_rec)
-		uint32_t *o_q, *o_path, *o_first, *o_ref, *o_nal, *o_an, *o_ns, *o_block, *need, *boff, *blist;
+		uint32_t *o_q, *o_path, *o_first, *o_ref, *o_nal, *o_an, *o_ns, *o_block, *o_nsteps, *need, *boff, *blist;
 		uint64_t *o_pos, *nalt, *ac_off, *bcnt, *block_off;
 		uint8_t *o_flags;
 		uint16_t *gt;
 		const size_t n2 = 2 * (size_t)n + 1;
 		HIP_CHECK(hipStreamSynchronize(s));
-		if (nrec) {
-			KLAUNCH(k_cl_pos, dim3(cblk(nrec)), dim3(C_TPB), 0, s, nrec, rlist, d.rq, d.op, d.of, d_ref_of_path, d_ref_base, roff, anchored,
+		if (nfl) {
+			KLAUNCH(k_cl_pos, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, rlist, d.rq, d.op, d.of, d_ref_of_path, d_ref_base, roff, anchored,
 				pos, perm);
 			uint32_t *cur = perm, *nxt = perm2;
 			auto pass = [&](int which, unsigned bits) {
-				KLAUNCH(k_cl_key, dim3(cblk(nrec)), dim3(C_TPB), 0, s, nrec, which, cur, rlist, d.op, d_ref_of_path, pos, key);
-				sort_pairs_u32(key, key2, cur, nxt, nrec, bits, sort_tmp, sort_a, s);
+				KLAUNCH(k_cl_key, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, which, cur, rlist, d.op, d_ref_of_path, pos, key);
+				sort_pairs_u32(key, key2, cur, nxt, nfl, bits, sort_tmp, sort_a, s);
 				std::swap(cur, nxt);
 			};
 			pass(0, 32);
@@ -797,17 +714,43 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 				pass(2, bits_for(nR));
 			perm = cur;
 		}
+		// ---- the inversion records, and every record's row in the one list
+		InvIn iin;
+		InvDevice iv;
+		uint32_t *f_dst = nullptr;
+		if (inversions) {
+			iin.NR = NR, iin.nR = nR, iin.S = S, iin.NS = NS;
+			iin.ref_base = d_ref_base, iin.ref_path = d_ref_path, iin.slot_of_path = d_slot, iin.slot_first = d_slot_first, iin.roff = roff;
+			iin.max_steps = opts->max_steps ? opts->max_steps : 65536;
+			iin.force_tier2 = (opts->flags & POVU_HIP_T_FORCE_TIER2) != 0;
+			iv = inv_find(ctx, iin);
+			check_call_32((uint64_t)nfl + iv.n, "records");
+			if (iv.n) {
+				uint32_t *f_ref;
+				uint64_t *f_pos;
+				carve(ctx->iv_rows, [&](Spans &take) { take((size_t)nfl + 1, f_ref, f_dst, f_pos); });
+				if (nfl)
+					KLAUNCH(k_cl_sorted_keys, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, perm, rlist, d.op, d_ref_of_path, pos, f_ref, f_pos);
+				inv_merge(ctx, iv, nfl, f_ref, f_pos, f_dst);
+				nrec = nfl + iv.n;
+			}
+		}
+		const size_t r1 = (size_t)nrec + 1;
 		carve(ctx->cl_rec, [&](Spans &take) {
-			take(r1, o_q, o_path, o_first, o_ref, o_nal, o_an, o_ns, o_block, o_pos, nalt, ac_off, o_flags);
+			take(r1, o_q, o_path, o_first, o_ref, o_nal, o_an, o_ns, o_block, o_nsteps, o_pos, nalt, ac_off, o_flags);
 			take((size_t)nrec * S + 1, gt);
-			take(n2, need, boff, blist, bcnt, block_off);
-			take(scan64_tmp(std::max(r1, n2)), s64);
+			take(n2, need, boff, blist);
+			take(n2 + iv.n, bcnt, block_off);
+			take(scan64_tmp(std::max(r1, n2 + iv.n)), s64);
 		});
+		HIP_CHECK(hipMemsetAsync(o_nsteps, 0, r1 * 4, s));
+		const InvRows rows{o_q, o_path, o_first, o_ref, o_nal, o_an, o_ns, o_block, o_nsteps, o_pos, nalt, o_flags, gt};
 		HIP_CHECK(hipMemsetAsync(need, 0, n2 * 4, s));
 		HIP_CHECK(hipMemsetAsync(nalt + nrec, 0, 8, s));
-		if (nrec)
-			KLAUNCH(k_cl_rec_fields, dim3(cblk(nrec)), dim3(C_TPB), 0, s, nrec, perm, rlist, pos, d.rq, d.op, d.of, d.oa, d.orv, d.aoff, o_q,
-				o_path, o_first, o_ref, o_nal, o_pos, nalt, need);
+		if (nfl)
+			KLAUNCH(k_cl_rec_fields, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, perm, rlist, pos, d.rq, d.op, d.of, d.oa, d.orv, d.aoff, o_q,
+				o_path, o_first, o_ref, o_nal, o_pos, nalt, need, f_dst);
+		inv_fields(ctx, iin, iv, rows);
 		scan64(nalt, ac_off, r1, s64, s);
 		uint64_t n_ac = 0;
 		HIP_CHECK(copy_async(&n_ac, ac_off + nrec, 8, hipMemcpyDeviceToHost, s));
@@ -817,12 +760,17 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 		HIP_CHECK(hipStreamSynchronize(s));
 		if (n)
 			KLAUNCH(k_cl_blocks, dim3(cblk(2 * (size_t)n)), dim3(C_TPB), 0, s, 2 * (uint64_t)n, need, boff, blist);
+		const uint32_t nfb = nb; // the flubble blocks; the inversion records' blocks follow them, one each: REF, then ALT
+		check_call_32((uint64_t)nfb + iv.n, "blocks");
+		nb = nfb + iv.n;
 		HIP_CHECK(hipMemsetAsync(bcnt + nb, 0, 8, s));
-		if (nb)
-			KLAUNCH(k_cl_block_cnt, dim3(cblk(nb)), dim3(C_TPB), 0, s, nb, blist, d.aoff, bcnt);
+		if (nfb)
+			KLAUNCH(k_cl_block_cnt, dim3(cblk(nfb)), dim3(C_TPB), 0, s, nfb, blist, d.aoff, bcnt);
+		inv_genotypes(ctx, iin, iv, rows, nfb, bcnt);
 		scan64(bcnt, block_off, (size_t)nb + 1, s64, s);
-		uint64_t nsp = 0;
+		uint64_t nsp = 0, nfsp = 0; // spelled alleles: all, those of the flubble blocks
 		HIP_CHECK(copy_async(&nsp, block_off + nb, 8, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(&nfsp, block_off + nfb, 8, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
 
 		// ---- spelling: lengths, offsets, bytes
@@ -837,17 +785,19 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 		});
 		HIP_CHECK(hipMemsetAsync(ac, 0, (n_ac + 1) * 4, s));
 		HIP_CHECK(hipMemsetAsync(bad, 0xFF, 8, s));
-		if (nrec) {
-			const unsigned wg = wblk(nrec);
-			KLAUNCH(k_cl_records, dim3(wg), dim3(C_TPB), 0, s, nrec, o_q, o_path, o_ref, qidx, d_slot, d_slot_first, NS, S, smin, smax, ac_off,
-				d.qstatus, anchored, d.aoff, ilen, gt, ac, o_an, o_ns, o_flags);
-			KLAUNCH(k_cl_rec_block, dim3(cblk(nrec)), dim3(C_TPB), 0, s, nrec, perm, rlist, d.rq, d.orv, boff, o_block);
+		if (nfl) {
+			const unsigned wg = wblk(nfl);
+			KLAUNCH(k_cl_records, dim3(wg), dim3(C_TPB), 0, s, nfl, o_q, o_path, o_ref, qidx, d_slot, d_slot_first, NS, S, smin, smax, ac_off,
+				d.qstatus, anchored, d.aoff, ilen, gt, ac, o_an, o_ns, o_flags, f_dst);
+			KLAUNCH(k_cl_rec_block, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, perm, rlist, d.rq, d.orv, boff, o_block, f_dst);
 		}
+		inv_counts(ctx, iin, iv, rows, ac_off, ac);
 		HIP_CHECK(hipMemsetAsync(slen + nsp, 0, 8, s));
 		HIP_CHECK(hipMemsetAsync(alen + nsp, 0, 8, s));
-		if (nsp)
-			KLAUNCH(k_cl_spell_len, dim3(cblk(nsp)), dim3(C_TPB), 0, s, nsp, nb, block_off, blist, d.aoff, d.afirst, d.rpos, d.rlen,
+		if (nfsp)
+			KLAUNCH(k_cl_spell_len, dim3(cblk(nfsp)), dim3(C_TPB), 0, s, nfsp, nfb, block_off, blist, d.aoff, d.afirst, d.rpos, d.rlen,
 				ctx->path_steps, ctx->seq_off, g.vid, ilen, atl, anchored, slen, alen);
+		inv_spell_len(ctx, iin, iv, slen + nfsp, alen + nfsp);
 		scan64(slen, sp_off, nsp + 1, s64b, s);
 		scan64(alen, at_off, nsp + 1, s64b, s);
 		uint64_t nbytes[2] = {0, 0};
@@ -856,9 +806,10 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 		HIP_CHECK(hipStreamSynchronize(s));
 		char *o_seq, *o_at;
 		carve(ctx->cl_bytes, [&](Spans &take) { take(nbytes[0] + 1, o_seq), take(nbytes[1] + 1, o_at); });
-		if (nsp)
-			KLAUNCH(k_cl_emit, dim3(wblk(nsp)), dim3(C_TPB), 0, s, nsp, nb, block_off, blist, d.aoff, d.afirst, d.rpos, d.rlen,
+		if (nfsp)
+			KLAUNCH(k_cl_emit, dim3(wblk(nfsp)), dim3(C_TPB), 0, s, nfsp, nfb, block_off, blist, d.aoff, d.afirst, d.rpos, d.rlen,
 				ctx->path_steps, ctx->seq_off, ctx->seq, g.vid, anchored, sp_off, at_off, o_seq, o_at, bad);
+		inv_emit(ctx, iin, iv, sp_off + nfsp, at_off + nfsp, o_seq, o_at, bad);
 		uint64_t hbad = 0;
 		HIP_CHECK(copy_async(&hbad, bad, 8, hipMemcpyDeviceToHost, s));
 		std::vector<uint64_t> h_roff(nR ? nR + 1 : 1);
@@ -882,6 +833,7 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 		hand_off(o->an, nrec, o_an, nrec, ctx);
 		hand_off(o->ns, nrec, o_ns, nrec, ctx);
 		hand_off(o->block, nrec, o_block, nrec, ctx);
+		hand_off(o->n_steps, nrec, o_nsteps, nrec, ctx);
 		hand_off(o->pos, nrec, o_pos, nrec, ctx);
 		hand_off(o->flags, nrec, o_flags, nrec, ctx);
 		hand_off(o->ac_off, r1, ac_off, r1, ctx);
@@ -904,6 +856,8 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 		v.n_seq_bytes = nbytes[0];
 		v.n_at_bytes = nbytes[1];
 		v.n_refs = nR;
+		v.n_steps = o->n_steps.data();
+		v.n_inv_records = iv.n, v.n_inv_heads = iv.n_heads, v.n_inv_long = iv.n_long, v.n_inv_tier2 = iv.n_tier2;
 		v.query = o->query.data(), v.path = o->path.data(), v.first = o->first.data(), v.ref_allele = o->ref_allele.data();
 		v.n_alleles = o->n_alleles.data(), v.an = o->an.data(), v.ns = o->ns.data(), v.block = o->block.data();
 		v.pos = o->pos.data(), v.flags = o->flags.data(), v.ac_off = o->ac_off.data(), v.ac = o->ac.data(), v.gt = o->gt.data();

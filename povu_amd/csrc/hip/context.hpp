@@ -341,6 +341,9 @@ struct povu_hip_ctx {
 	// povu_hip_segments_upload: the sequences of the resident graph (u64 offsets by vertex index, then the bytes), of upload
 	// `seq_gen`; povu_hip_call's workspace and outputs (call_kernels.hip)
 	Arena seq_buf, cl_ws, cl_slot, cl_rec, cl_spell, cl_bytes;
+	// povu_hip_call with POVU_HIP_T_INVERSIONS (inv_kernels.hip): the step index and head counts / the run heads, runs and
+	// records / the rows of the flubble records in the merged list
+	Arena iv_ws, iv_heads, iv_rows;
 	uint64_t *seq_off = nullptr;
 	char *seq = nullptr;
 	uint64_t seq_gen = 0;

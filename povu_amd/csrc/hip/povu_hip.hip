@@ -194,6 +194,9 @@ extern "C" int povu_hip_release_workspace(povu_hip_ctx *ctx)
 	ctx->cl_rec.release();
 	ctx->cl_spell.release();
 	ctx->cl_bytes.release();
+	ctx->iv_ws.release();
+	ctx->iv_heads.release();
+	ctx->iv_rows.release();
 	return 0;
 }
 

@@ -22,7 +22,8 @@ static bool ends_with(const std::string &s, const char *suf)
 }
 
 // two records of one bubble >1>4 on reference path 0: an anchored multi-allelic one whose REF is allele 1 of its block, and
-// one with a missing slot; names -> slots, the writer on 1 and 2 threads and for one prefix, everything freed
+// one with a missing slot; names -> slots, the writer on 1 and 2 threads and for one prefix; the same with an inversion (SUBR)
+// record between them; everything freed
 static int check_vcf_writer()
 {
 	const char *path_name[] = {"R#1#c", "S#1#c", "S#2#c", "lone"}, *prefix[] = {"R#", "nobody"};
@@ -58,6 +59,38 @@ static int check_vcf_writer()
 				return 8;
 			povu_hip_buffer_free(vcf);
 		}
+	// the SUBR writer path: an inversion record between the bubble's two (no site: query NIL), REF then ALT in its own block,
+	// both steps backwards (the ID is written forward); then one whose AT strings are empty -- an ID of nothing, no fault
+	{
+		const uint32_t query2[] = {0, POVU_HIP_NIL, 0}, path2[] = {0, 0, 0}, first2[] = {0, 1, 3}, ref2[] = {1, 0, 0}, nal2[] = {3, 2, 2},
+			       an2[] = {4, 2, 3}, ns2[] = {3, 2, 2}, block2[] = {0, 2, 1}, ac2[] = {1, 1, 1, 2}, n_steps2[] = {0, 2, 0};
+		const uint64_t pos2[] = {2, 3, 9}, ac_off2[] = {0, 2, 3, 4}, block_off2[] = {0, 3, 5, 7},
+			       seq_off2[] = {0, 1, 5, 7, 8, 10, 12, 14}, at_off2[] = {0, 2, 6, 10, 12, 14, 19, 24};
+		uint64_t at_off3[] = {0, 2, 6, 10, 12, 14, 14, 14};
+		const uint8_t flags2[] = {POVU_HIP_CALL_ANCHORED | POVU_HIP_CALL_DEL, POVU_HIP_CALL_SUBR, POVU_HIP_CALL_TANGLED};
+		const uint16_t gt2[] = {0, 1, 2, 0, 0, POVU_HIP_GT_MISSING, 1, POVU_HIP_GT_MISSING, 0, 1, POVU_HIP_GT_MISSING, 1};
+		povu_hip_calls c2 = {3, 4, 3, 7, 14, 24, 1, query2, path2, first2, ref2, nal2, an2, ns2, block2, pos2, flags2, ac_off2,
+				     ac2, gt2, block_off2, seq_off2, at_off2, "CCGGTCTAGTACGT", ">1>1>2>1>3>2>3<12<7>7>12", contig_len, 0.0,
+				     n_steps2, 1, 1, 0, 0};
+		for (int round = 0; round < 2; round++) {
+			size_t len = 0;
+			char *vcf = povu_hip_calls_vcf(&c2, sites, nm, path_name, "20240229", nullptr, 2, &len);
+			if (!vcf || strlen(vcf) != len)
+				return 10;
+			const char *want = round ? "R#1#c\t3\t\tAC\tGT\t60\tPASS\tAC=1;AF=0.5;AN=2;NS=2;AT=,;VARTYPE=SUBR;TANGLED=F\tGT\t0\t.|1\t.\n"
+						 : "R#1#c\t3\t>12>7\tAC\tGT\t60\tPASS\tAC=1;AF=0.5;AN=2;NS=2;AT=<12<7,>7>12;VARTYPE=SUBR;TANGLED=F\tGT\t0\t.|1\t.\n";
+			if (!strstr(vcf, want) || std::count((const char *)vcf, (const char *)vcf + len, '\n') < 3)
+				return 11;
+			povu_hip_buffer_free(vcf);
+			c2.at_off = at_off3;
+			c2.n_at_bytes = 14;
+		}
+		const uint32_t nal3[] = {3, 3, 2}; // an inversion record of three alleles is refused
+		c2.n_alleles = nal3;
+		size_t len = 0;
+		if (povu_hip_calls_vcf(&c2, sites, nm, path_name, "20240229", nullptr, 1, &len))
+			return 12;
+	}
 	povu_hip_sites_free(sites);
 	povu_pvst_doc_free(doc);
 	povu_hip_call_names_free(nm);

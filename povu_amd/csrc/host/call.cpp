@@ -27,6 +27,7 @@ struct CallArgs {
 	std::string forest_dir = ".", out_dir;
 	std::vector<std::string> prefixes;
 	bool to_stdout = true;
+	bool inversions = false; // --inversions: SUBR records too (INTEGRATION.md "Inversion calls")
 };
 
 CallArgs parse_call_args(const std::vector<std::string> &a)
@@ -54,6 +55,8 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			c.to_stdout = false;
 		} else if (x == "--stdout") {
 			c.to_stdout = true;
+		} else if (x == "--inversions") {
+			c.inversions = true;
 		} else if (x == "-c" || x == "--chunk-size" || x == "-q" || x == "--queue-length") {
 			need(i); // (streaming has no meaning here: accepted and ignored)
 		} else if (x == "-g" || x == "--restrict" || !x.compare(0, 11, "--restrict=")) {
@@ -168,7 +171,8 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 		fail("paths");
 	if (povu_hip_segments_upload(ctx, V, seq_off.data(), seq.data(), err, sizeof err) != 0)
 		fail("sequences");
-	povu_hip_calls *c = povu_hip_call(ctx, sites, &nm->refs, nm->slot_of_path, nullptr, err, sizeof err);
+	const povu_hip_trav_opts opts{0, ca.inversions ? POVU_HIP_T_INVERSIONS : 0u};
+	povu_hip_calls *c = povu_hip_call(ctx, sites, &nm->refs, nm->slot_of_path, &opts, err, sizeof err);
 	if (!c)
 		fail("call");
 

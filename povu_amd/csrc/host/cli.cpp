@@ -3,8 +3,8 @@
 //   povu [--version] [-v <int>] [-t <int>] decompose -i <gfa> [-o <dir>] [-h|--hairpins] [-s|--subflubbles]
 //   povu ... decompose ... --structure-export <json>   (additive: writes the flubble debug sidecar gfa2vcf writes)
 //   povu ... gfa2vcf -i <gfa> [-h] [-s] [--structure-export <json>] <options of `call`>   (app/cli/cli.cpp:154-193)
-//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout]   (the variant calls
-//   of INTEGRATION.md "Variant calls", on the GPU)
+//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions]   (the
+//   variant calls of INTEGRATION.md "Variant calls" and "Inversion calls", on the GPU)
 #include "decompose.hpp"
 
 #include <cstdlib>
@@ -62,6 +62,8 @@ static void usage(std::ostream &os)
 	      "        -o[output_dir], --output-dir=[output_dir]\n"
 	      "                                          write <output_dir>/<prefix>.vcf per prefix\n"
 	      "        --stdout                          one VCF of every reference path to stdout [default]\n"
+	      "        --inversions                      also call inversions: a VARTYPE=SUBR record for every stretch of two or more\n"
+	      "                                          steps of a reference path that another path walks backwards [default: false]\n"
 	      "        -c, -q                            accepted and ignored (no streaming here)\n";
 }
 

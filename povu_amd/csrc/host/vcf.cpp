@@ -194,9 +194,11 @@ try {
 		return nullptr;
 	const uint64_t n = c->n_records, S = c->n_slots;
 	const uint32_t P = names->n_paths, n_samples = names->refs.n_samples;
-	for (uint64_t i = 0; i < n; i++)
-		if (c->query[i] >= sites->n || c->path[i] >= P)
+	for (uint64_t i = 0; i < n; i++) {
+		const bool subr = c->flags[i] & POVU_HIP_CALL_SUBR; // (its query is POVU_HIP_NIL: it belongs to no site)
+		if ((!subr && c->query[i] >= sites->n) || c->path[i] >= P || (subr && (c->n_alleles[i] != 2 || c->ref_allele[i] != 0)))
 			return nullptr;
+	}
 	std::vector<uint32_t> slot_first(n_samples + 1, 0); // (the slots of a sample are consecutive)
 	for (uint32_t sl = 0; sl < S; sl++) {
 		if (names->refs.sample_of_slot[sl] >= n_samples)
@@ -246,7 +248,24 @@ try {
 			for (uint32_t a = 0; a < na; a++)
 				if (a != ra)
 					order.push_back(b + a);
-			label = (sites->or1[q] ? "<" : ">") + std::to_string(sites->id1[q]) + (sites->or2[q] ? "<" : ">") + std::to_string(sites->id2[q]);
+			const uint8_t f = c->flags[i];
+			const bool subr = f & POVU_HIP_CALL_SUBR;
+			if (subr) {
+				// the first and the last step of the REF AT string, both written '>' when both are '<'
+				const char *at = c->at + c->at_off[b], *end = c->at + c->at_off[b + 1], *last = end;
+				while (last > at && last[-1] != '<' && last[-1] != '>')
+					last--;
+				const char *first_end = at == end ? at : at + 1;
+				while (first_end < end && *first_end != '<' && *first_end != '>')
+					first_end++;
+				label.assign(at, first_end);
+				if (last > at)
+					label.append(last - 1, end);
+				if (at < end && *at == '<' && last > at && last[-1] == '<')
+					label[0] = label[first_end - at] = '>';
+			} else {
+				label = (sites->or1[q] ? "<" : ">") + std::to_string(sites->id1[q]) + (sites->or2[q] ? "<" : ">") + std::to_string(sites->id2[q]);
+			}
 			o += path_name[c->path[i]];
 			o += '\t';
 			o += std::to_string(c->pos[i]);
@@ -273,10 +292,11 @@ try {
 					o += ',';
 				o.append(c->at + c->at_off[order[k]], c->at_off[order[k] + 1] - c->at_off[order[k]]);
 			}
-			const uint8_t f = c->flags[i];
-			o += (f & POVU_HIP_CALL_INS) ? ";VARTYPE=INS" : (f & POVU_HIP_CALL_DEL) ? ";VARTYPE=DEL" : ";VARTYPE=SUB";
+			o += subr ? ";VARTYPE=SUBR" : (f & POVU_HIP_CALL_INS) ? ";VARTYPE=INS" : (f & POVU_HIP_CALL_DEL) ? ";VARTYPE=DEL" : ";VARTYPE=SUB";
 			o += (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
-			o += ";ES=" + label + ";LV=" + std::to_string((long)sites->height[q] - 1) + "\tGT";
+			if (!subr)
+				o += ";ES=" + label + ";LV=" + std::to_string((long)sites->height[q] - 1);
+			o += "\tGT";
 			const uint16_t *row = c->gt + i * S;
 			for (uint32_t sm = 0; sm < n_samples; sm++) {
 				o += '\t';

@@ -99,7 +99,9 @@ class _Calls(C.Structure):
                 [("pos", C.POINTER(C.c_uint64)), ("flags", C.POINTER(C.c_uint8)), ("ac_off", C.POINTER(C.c_uint64)),
                  ("ac", C.POINTER(C.c_uint32)), ("gt", C.POINTER(C.c_uint16)), ("block_off", C.POINTER(C.c_uint64)),
                  ("seq_off", C.POINTER(C.c_uint64)), ("at_off", C.POINTER(C.c_uint64)), ("seq", C.POINTER(C.c_uint8)),
-                 ("at", C.POINTER(C.c_uint8)), ("contig_len", C.POINTER(C.c_uint64)), ("device_ms", C.c_double)])
+                 ("at", C.POINTER(C.c_uint8)), ("contig_len", C.POINTER(C.c_uint64)), ("device_ms", C.c_double),
+                 ("n_steps", C.POINTER(C.c_uint32))] +
+                [(k, C.c_uint64) for k in ("n_inv_records", "n_inv_heads", "n_inv_long", "n_inv_tier2")])
 
 
 class _StageTime(C.Structure):
@@ -124,6 +126,7 @@ F_SUBFLUBBLES = 8192  # all five passes of -s (implies F_LEAF_SUBFLUBBLES): Fore
 W_FORCE_TIER2 = 1  # HipDecomposer.walks: every query through the second-tier kernel (tests)
 WALK_MORE, WALK_LONG, WALK_BUDGET = 1, 2, 4  # status bits of a query
 T_FORCE_TIER2 = 1  # HipDecomposer.traversals: every scan through the wave-per-scan kernel (tests)
+T_INVERSIONS = 2  # HipDecomposer.call: inversion (SUBR) records too (INTEGRATION.md "Inversion calls")
 TRAV_LONG, TRAV_STRAY, TRAV_OPEN = 1, 2, 4  # status bits of a query
 
 _lib = None
@@ -667,6 +670,7 @@ class Shards:
 
 
 CALL_ANCHORED, CALL_TANGLED, CALL_INS, CALL_DEL = 1, 2, 4, 8
+CALL_SUBR = 16  # an inversion record: query 0xFFFFFFFF, first / n_steps the inverted run of its reference path
 GT_MISSING = 0xFFFF
 
 
@@ -717,6 +721,9 @@ class Calls:
         self.seq = _view(c.seq, self.n_seq_bytes, np.uint8)
         self.at = _view(c.at, self.n_at_bytes, np.uint8)
         self.contig_len = _view(c.contig_len, len(self.refs), np.uint64)
+        self.n_steps = _view(c.n_steps, n, np.uint32)
+        self.n_inv_records, self.n_inv_heads = int(c.n_inv_records), int(c.n_inv_heads)
+        self.n_inv_long, self.n_inv_tier2 = int(c.n_inv_long), int(c.n_inv_tier2)
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -924,7 +931,8 @@ class HipDecomposer:
 
     def call(self, forest: Forest, refs, max_steps: int = 65536, flags: int = 0) -> Calls:
         """The variant calls of `forest` (INTEGRATION.md "Variant calls") with the resident paths whose names start with one
-        of the prefixes `refs` as references, on the GPU (paths and sequences uploaded first)."""
+        of the prefixes `refs` as references, on the GPU (paths and sequences uploaded first).  flags: T_FORCE_TIER2,
+        T_INVERSIONS (the SUBR records of "Inversion calls" merged in: Calls.n_steps, flags & CALL_SUBR, the n_inv_* counters)."""
         names = self._path_names
         if isinstance(refs, str):
             refs = [refs]

@@ -599,3 +599,23 @@ def pansn(paths: Paths, samples: int, haps: int = 2, contig: str = "chr1") -> Pa
         rnd = j // (haps * samples)
         names.append(f"sample{sm}#{j % haps + 1}#{contig}" + (f"_{rnd}" if rnd else ""))
     return Paths(names, paths.off, paths.ids, paths.rev)
+
+
+def inverted_haplotypes(paths: Paths, n: int, min_len: int, max_len: int, seed: int, keep=()) -> Paths:
+    """A copy of `paths` in which `n` random intervals of min_len to max_len steps (cut at the path's end), each in a random
+    path whose index is not in `keep`, are replaced by their reverse complement: the steps backwards, every orientation
+    flipped -- the haplotype walks that stretch of the graph the other way round, which is what an inversion call finds
+    against a path that kept it (INTEGRATION.md "Inversion calls").  Intervals may overlap; a path shorter than min_len
+    steps is left alone."""
+    rng = np.random.default_rng(seed)
+    ids, rev = paths.ids.copy(), paths.rev.copy()
+    off = paths.off.astype(np.int64)
+    pool = [k for k in range(len(paths)) if k not in set(keep) and off[k + 1] - off[k] >= max(min_len, 1)]
+    for _ in range(n if pool else 0):
+        k = pool[int(rng.integers(0, len(pool)))]
+        ln = int(rng.integers(min_len, max_len + 1))
+        a = int(off[k]) + int(rng.integers(0, int(off[k + 1] - off[k]) - min_len + 1))
+        b = min(a + ln, int(off[k + 1]))
+        ids[a:b] = ids[a:b][::-1].copy()
+        rev[a:b] = 1 - rev[a:b][::-1]
+    return Paths(list(paths.names), paths.off.copy(), ids, rev)
