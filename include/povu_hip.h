@@ -586,7 +586,8 @@ int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t
 			 uint32_t *next_seen);
 
 /* unit-test hook for the device-wide scans of the path: exclusive scan of in[0..n) (op 0 = sum mod 2^32,
- * 1 = running maximum) and, when in2 is given, an independent sum scan of in2[0..n2) in the same launch */
+ * 1 = running maximum) and, when in2 is given, an independent sum scan of in2[0..n2) in the same launch;
+ * op 2 = sum mod 2^64 of n 64-bit values, in and out holding each as a pair of words, low word first (in2 unused) */
 int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,
 			uint32_t *out2, size_t n2);
 /* unit-test hook for the list ranking of the tree stage: suffix sums (inclusive, mod 2^32) along the lists next[0..n)

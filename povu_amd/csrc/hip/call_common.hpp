@@ -1,16 +1,11 @@
-// call_common.hpp -- what the flubble calls (call_kernels.hip) and the inversion calls (inv_kernels.hip) share: launch
-// shapes, nucleotide complements, the u64 scan, the bases and AT strings of a step sequence (one wave each), and the
-// inversion pipeline's interface to povu_hip_call.
+// call_common.hpp -- what the flubble calls (call_kernels.hip) and the inversion calls (inv_kernels.hip) share beyond
+// query_common.hpp: nucleotide complements, decimal widths, the bases and AT strings of a step sequence (one wave each), and
+// the inversion pipeline's interface to povu_hip_call.
 #pragma once
 #include "query_common.hpp"
 
 namespace povu_hip
 {
-
-static constexpr int C_TPB = 256;
-
-static inline unsigned cblk(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + C_TPB - 1) / C_TPB, 65536)); }
-static inline unsigned wblk(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + 3) / 4, 65536)); } // a wave each
 
 // complement of a nucleotide code (ACGTN, lower case, IUPAC), 0 for any other byte
 __device__ __forceinline__ uint8_t comp(uint8_t c)
@@ -48,32 +43,6 @@ __device__ __forceinline__ uint32_t ndig(uint32_t x)
 	return d;
 }
 
-// the last u with a[u] <= x, a ascending over [0, n)
-__device__ __forceinline__ uint32_t seg_of(const uint64_t *__restrict__ a, uint32_t n, uint64_t x)
-{
-	uint32_t lo = 0, hi = n;
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (a[mid] <= x)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
-// ---- exclusive u64 scan (call_kernels.hip): in == out allowed; tmp holds scan64_tmp(n) words
-size_t scan64_tmp(size_t n);
-void scan64(const uint64_t *in, uint64_t *out, size_t n, uint64_t *tmp, hipStream_t s);
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-	for (int o = 32; o > 0; o >>= 1)
-		v += __shfl_xor(v, o, 64);
-	return v;
-}
-
-
 // ---- the text of a step sequence, one wave: `step(k)` is step k of m
 // '>id' or '<id' of step x at o_at[at .. at + width)
 __device__ __forceinline__ void put_step(char *__restrict__ o_at, const uint32_t *__restrict__ vid, uint32_t x, uint64_t at, uint32_t width)
@@ -107,12 +76,7 @@ __device__ __forceinline__ void emit_steps(uint32_t lane, uint32_t m, StepFn ste
 		const uint32_t k = k0 + lane;
 		const uint32_t x = k < m ? step(k) : 0;
 		const uint32_t width = k < m ? 1 + ndig(vid[x >> 1]) : 0;
-		uint32_t incl = width; // wave inclusive prefix sum of the widths
-		for (int o = 1; o < 64; o <<= 1) {
-			const uint32_t y = __shfl_up(incl, o, 64);
-			if ((int)lane >= o)
-				incl += y;
-		}
+		const uint32_t incl = wave_inclusive_sum(width);
 		if (k < m)
 			put_step(o_at, vid, x, wa + incl - width, width);
 		wa += __shfl(incl, 63, 64);

@@ -21,77 +21,15 @@
 namespace povu_hip
 {
 
-static constexpr int SC_E = 4, SC_N = C_TPB * SC_E; // u64 scan: elements per thread / per block
 static constexpr uint32_t MAX_ALLELES = 65534;
-static constexpr uint64_t ROLE = 1ull << 63; // (trav_kernels.hip: reverse traversals carry it in rpos)
-// step k (S -> Z) of a traversal at path words [pos, pos + len), reversed and flipped when rev (as trav_kernels.hip reads it)
-__device__ __forceinline__ uint32_t tstep(const uint32_t *__restrict__ steps, uint64_t pos, uint32_t len, bool rev, uint32_t k)
-{
-	return rev ? steps[pos + len - 1 - k] ^ 1u : steps[pos + k];
-}
-
-// ---- exclusive u64 scan: per block of SC_N an LDS scan, the block sums scanned recursively, then added
-__global__ __launch_bounds__(C_TPB) void k_c64_scan(const uint64_t *in, uint64_t *out, size_t n, uint64_t *__restrict__ sums)
-{
-	__shared__ uint64_t sh[C_TPB];
-	const size_t base = (size_t)blockIdx.x * SC_N + (size_t)threadIdx.x * SC_E;
-	uint64_t v[SC_E], t = 0;
-	for (int k = 0; k < SC_E; k++) {
-		v[k] = base + k < n ? in[base + k] : 0;
-		t += v[k];
-	}
-	sh[threadIdx.x] = t;
-	__syncthreads();
-	for (int d = 1; d < C_TPB; d <<= 1) {
-		const uint64_t x = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
-		__syncthreads();
-		sh[threadIdx.x] += x;
-		__syncthreads();
-	}
-	uint64_t run = sh[threadIdx.x] - t;
-	for (int k = 0; k < SC_E; k++) {
-		if (base + k < n)
-			out[base + k] = run;
-		run += v[k];
-	}
-	if (threadIdx.x == C_TPB - 1)
-		sums[blockIdx.x] = sh[C_TPB - 1];
-}
-__global__ __launch_bounds__(C_TPB) void k_c64_add(uint64_t *out, size_t n, const uint64_t *__restrict__ offs)
-{
-	const size_t base = (size_t)blockIdx.x * SC_N;
-	const uint64_t o = offs[blockIdx.x];
-	for (size_t i = base + threadIdx.x; i < n && i < base + SC_N; i += C_TPB)
-		out[i] += o;
-}
-size_t scan64_tmp(size_t n)
-{
-	size_t t = 2;
-	while (n > 1) {
-		n = (n + SC_N - 1) / SC_N;
-		t += n + 1;
-	}
-	return t;
-}
-void scan64(const uint64_t *in, uint64_t *out, size_t n, uint64_t *tmp, hipStream_t s)
-{
-	if (!n)
-		return;
-	const size_t nb = (n + SC_N - 1) / SC_N;
-	KLAUNCH(k_c64_scan, dim3((unsigned)nb), dim3(C_TPB), 0, s, in, out, n, tmp);
-	if (nb > 1) {
-		scan64(tmp, tmp, nb, tmp + nb + 1, s);
-		KLAUNCH(k_c64_add, dim3((unsigned)nb), dim3(C_TPB), 0, s, out, n, tmp);
-	}
-}
 
 // ---- reference offsets: length of every reference step (ref_base: first step of every reference in the concatenation)
 __global__ void k_cl_ref_len(uint64_t NR, const uint64_t *__restrict__ ref_base, uint32_t nR, const uint32_t *__restrict__ ref_path,
 			     const uint64_t *__restrict__ path_off, const uint32_t *__restrict__ steps, const uint64_t *__restrict__ seq_off,
 			     uint64_t *__restrict__ len)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * C_TPB + threadIdx.x; i < NR; i += (uint64_t)gridDim.x * C_TPB) {
-		const uint32_t r = seg_of(ref_base, nR, i);
+	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < NR; i += (uint64_t)gridDim.x * Q_TPB) {
+		const uint32_t r = span_of(ref_base, nR, i);
 		const uint32_t x = steps[path_off[ref_path[r]] + (i - ref_base[r])];
 		len[i] = seq_off[(x >> 1) + 1] - seq_off[x >> 1];
 	}
@@ -101,7 +39,7 @@ __global__ void k_cl_ref_len(uint64_t NR, const uint64_t *__restrict__ ref_base,
 __global__ void k_cl_seg_count(uint32_t n, const uint32_t *__restrict__ qa, const uint32_t *__restrict__ qz, const uint32_t *__restrict__ vid,
 			       uint32_t V, uint32_t *__restrict__ cnt, uint32_t *__restrict__ qv)
 {
-	for (uint32_t q = blockIdx.x * C_TPB + threadIdx.x; q < n; q += gridDim.x * C_TPB) {
+	for (uint32_t q = blockIdx.x * Q_TPB + threadIdx.x; q < n; q += gridDim.x * Q_TPB) {
 		const uint32_t a = find_vertex(vid, V, qa[q]), z = find_vertex(vid, V, qz[q]);
 		qv[2 * (size_t)q] = a;
 		qv[2 * (size_t)q + 1] = z;
@@ -114,7 +52,7 @@ __global__ void k_cl_seg_count(uint32_t n, const uint32_t *__restrict__ qa, cons
 __global__ void k_cl_seg_fill(uint32_t n, const uint32_t *__restrict__ qv, const uint32_t *__restrict__ off, uint32_t *__restrict__ cur,
 			      uint32_t *__restrict__ val)
 {
-	for (uint64_t e = (uint64_t)blockIdx.x * C_TPB + threadIdx.x; e < 2 * (uint64_t)n; e += (uint64_t)gridDim.x * C_TPB) {
+	for (uint64_t e = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; e < 2 * (uint64_t)n; e += (uint64_t)gridDim.x * Q_TPB) {
 		const uint32_t v = qv[e];
 		if (v != NO_QUERY)
 			val[off[v] + atomicAdd(cur + v, 1u)] = (uint32_t)e; // (site << 1 | boundary)
@@ -126,8 +64,8 @@ __global__ void k_cl_hits(uint64_t NR, const uint64_t *__restrict__ ref_base, ui
 			  const uint64_t *__restrict__ path_off, const uint32_t *__restrict__ steps, const uint32_t *__restrict__ off,
 			  const uint32_t *__restrict__ val, uint32_t *__restrict__ hit)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * C_TPB + threadIdx.x; i < NR; i += (uint64_t)gridDim.x * C_TPB) {
-		const uint32_t r = seg_of(ref_base, nR, i);
+	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < NR; i += (uint64_t)gridDim.x * Q_TPB) {
+		const uint32_t r = span_of(ref_base, nR, i);
 		const uint32_t v = steps[path_off[ref_path[r]] + (i - ref_base[r])] >> 1;
 		for (uint32_t e = off[v]; e < off[v + 1]; e++) {
 			const uint32_t qr = val[e];
@@ -146,7 +84,7 @@ __device__ __forceinline__ bool bit_of(const uint32_t *__restrict__ w, uint64_t 
 __global__ void k_cl_present(uint64_t nq, uint32_t nR, const uint32_t *__restrict__ hit, const uint32_t *__restrict__ tree,
 			     uint32_t *__restrict__ present)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * C_TPB + threadIdx.x; i < nq * nR; i += (uint64_t)gridDim.x * C_TPB) {
+	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < nq * nR; i += (uint64_t)gridDim.x * Q_TPB) {
 		const uint64_t q = i / nR;
 		const uint32_t r = (uint32_t)(i % nR);
 		if (hits_of(hit, q, nR, r)) {
@@ -162,7 +100,7 @@ __global__ void k_cl_callable(uint32_t n, uint32_t nR, const uint32_t *__restric
 			      const uint32_t *__restrict__ tree, const uint32_t *__restrict__ parent, const uint8_t *__restrict__ fam,
 			      uint8_t *__restrict__ callable, uint8_t *__restrict__ called)
 {
-	for (uint32_t q = blockIdx.x * C_TPB + threadIdx.x; q < n; q += gridDim.x * C_TPB) {
+	for (uint32_t q = blockIdx.x * Q_TPB + threadIdx.x; q < n; q += gridDim.x * Q_TPB) {
 		bool skip = false;
 		for (uint32_t v = q, k = 0; v != NO_QUERY && k <= n; v = parent[v], k++)
 			skip |= is_sub(fam[v]);
@@ -178,7 +116,7 @@ __global__ void k_cl_callable(uint32_t n, uint32_t nR, const uint32_t *__restric
 }
 __global__ void k_cl_unparent(uint32_t n, const uint8_t *__restrict__ callable, const uint32_t *__restrict__ parent, uint8_t *__restrict__ called)
 {
-	for (uint32_t q = blockIdx.x * C_TPB + threadIdx.x; q < n; q += gridDim.x * C_TPB)
+	for (uint32_t q = blockIdx.x * Q_TPB + threadIdx.x; q < n; q += gridDim.x * Q_TPB)
 		if (callable[q] && parent[q] != NO_QUERY)
 			called[parent[q]] = 0;
 }
@@ -186,7 +124,7 @@ __global__ void k_cl_unparent(uint32_t n, const uint8_t *__restrict__ callable, 
 __global__ void k_cl_keep(uint32_t n, const uint8_t *__restrict__ called, const uint32_t *__restrict__ aoff, uint32_t *__restrict__ keep,
 			  uint32_t *__restrict__ maxal)
 {
-	for (uint32_t q = blockIdx.x * C_TPB + threadIdx.x; q <= n; q += gridDim.x * C_TPB) {
+	for (uint32_t q = blockIdx.x * Q_TPB + threadIdx.x; q <= n; q += gridDim.x * Q_TPB) {
 		const uint32_t nal = q < n ? aoff[q + 1] - aoff[q] : 0;
 		keep[q] = q < n && called[q] && nal >= 2;
 		if (keep[q])
@@ -200,15 +138,15 @@ __global__ void k_cl_inner(uint32_t n_al, const uint32_t *__restrict__ afirst, c
 			   const uint64_t *__restrict__ seq_off, const uint32_t *__restrict__ vid, uint64_t *__restrict__ ilen,
 			   uint64_t *__restrict__ atl)
 {
-	for (uint32_t a = blockIdx.x * C_TPB + threadIdx.x; a < n_al; a += gridDim.x * C_TPB) {
+	for (uint32_t a = blockIdx.x * Q_TPB + threadIdx.x; a < n_al; a += gridDim.x * Q_TPB) {
 		const uint32_t t = afirst[a];
 		uint64_t b = 0, w = 0;
 		if (keep[rq[t]]) {
-			const uint64_t p = rpos[t] & ~ROLE;
-			const bool rev = (rpos[t] & ROLE) != 0;
+			const uint64_t p = rpos[t] & ~ROLE_BIT;
+			const bool rev = (rpos[t] & ROLE_BIT) != 0;
 			const uint32_t len = rlen[t];
 			for (uint32_t k = 1; k + 1 < len; k++) {
-				const uint32_t v = tstep(steps, p, len, rev, k) >> 1;
+				const uint32_t v = trav_step(steps, p, len, rev, k) >> 1;
 				b += seq_off[v + 1] - seq_off[v];
 				w += 1 + ndig(vid[v]);
 			}
@@ -220,7 +158,7 @@ __global__ void k_cl_inner(uint32_t n_al, const uint32_t *__restrict__ afirst, c
 __global__ void k_cl_anchored(uint32_t n, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ aoff, const uint64_t *__restrict__ ilen,
 			      uint8_t *__restrict__ anchored)
 {
-	for (uint32_t q = blockIdx.x * C_TPB + threadIdx.x; q < n; q += gridDim.x * C_TPB) {
+	for (uint32_t q = blockIdx.x * Q_TPB + threadIdx.x; q < n; q += gridDim.x * Q_TPB) {
 		bool e = false;
 		if (keep[q])
 			for (uint32_t a = aoff[q]; a < aoff[q + 1]; a++)
@@ -234,7 +172,7 @@ __global__ void k_cl_slots(uint32_t R, const uint32_t *__restrict__ rq, const ui
 			   const uint32_t *__restrict__ keep, const uint32_t *__restrict__ qidx, const uint32_t *__restrict__ slot_of_path,
 			   uint32_t S, uint32_t *__restrict__ smin, uint32_t *__restrict__ smax)
 {
-	for (uint32_t t = blockIdx.x * C_TPB + threadIdx.x; t < R; t += gridDim.x * C_TPB) {
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < R; t += gridDim.x * Q_TPB) {
 		const uint32_t q = rq[t];
 		if (!keep[q])
 			continue;
@@ -246,7 +184,7 @@ __global__ void k_cl_slots(uint32_t R, const uint32_t *__restrict__ rq, const ui
 __global__ void k_cl_rec_flag(uint32_t R, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ op, const uint32_t *__restrict__ keep,
 			      const uint32_t *__restrict__ ref_of_path, uint8_t *__restrict__ flag)
 {
-	for (uint32_t t = blockIdx.x * C_TPB + threadIdx.x; t < R; t += gridDim.x * C_TPB)
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < R; t += gridDim.x * Q_TPB)
 		flag[t] = keep[rq[t]] && ref_of_path[op[t]] != NO_QUERY;
 }
 __global__ void k_cl_pos(uint32_t nrec, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ op,
@@ -254,7 +192,7 @@ __global__ void k_cl_pos(uint32_t nrec, const uint32_t *__restrict__ rlist, cons
 			 const uint64_t *__restrict__ roff, const uint8_t *__restrict__ anchored, uint64_t *__restrict__ pos,
 			 uint32_t *__restrict__ perm)
 {
-	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < nrec; i += gridDim.x * C_TPB) {
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		const uint32_t t = rlist[i];
 		const uint64_t b = ref_base[ref_of_path[op[t]]];
 		pos[i] = roff[b + of[t] + 1] - roff[b] + (anchored[rq[t]] ? 0 : 1);
@@ -266,7 +204,7 @@ __global__ void k_cl_key(uint32_t nrec, int which, const uint32_t *__restrict__ 
 			 const uint32_t *__restrict__ op, const uint32_t *__restrict__ ref_of_path, const uint64_t *__restrict__ pos,
 			 uint32_t *__restrict__ key)
 {
-	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < nrec; i += gridDim.x * C_TPB) {
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		const uint32_t j = perm[i];
 		key[i] = which == 0 ? (uint32_t)pos[j] : which == 1 ? (uint32_t)(pos[j] >> 32) : ref_of_path[op[rlist[j]]];
 	}
@@ -280,7 +218,7 @@ __global__ void k_cl_rec_fields(uint32_t nrec, const uint32_t *__restrict__ perm
 				uint32_t *__restrict__ o_ref, uint32_t *__restrict__ o_nal, uint64_t *__restrict__ o_pos, uint64_t *__restrict__ nalt,
 				uint32_t *__restrict__ need, const uint32_t *__restrict__ dst)
 {
-	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < nrec; i += gridDim.x * C_TPB) {
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		const uint32_t j = perm[i], t = rlist[j], q = rq[t], d = dst ? dst[i] : i;
 		o_q[d] = q;
 		o_path[d] = op[t];
@@ -297,14 +235,14 @@ __global__ void k_cl_sorted_keys(uint32_t nrec, const uint32_t *__restrict__ per
 				 const uint32_t *__restrict__ ref_of_path, const uint64_t *__restrict__ pos, uint32_t *__restrict__ f_ref,
 				 uint64_t *__restrict__ f_pos)
 {
-	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < nrec; i += gridDim.x * C_TPB) {
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		f_ref[i] = ref_of_path[op[rlist[perm[i]]]];
 		f_pos[i] = pos[perm[i]];
 	}
 }
 
 // GT codes, AC, AN, NS and flags: one wave per record, a lane per sample (its slots are consecutive)
-__global__ __launch_bounds__(C_TPB) void k_cl_records(uint32_t nrec, const uint32_t *__restrict__ o_q, const uint32_t *__restrict__ o_path,
+__global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, const uint32_t *__restrict__ o_q, const uint32_t *__restrict__ o_path,
 						      const uint32_t *__restrict__ o_ref, const uint32_t *__restrict__ qidx,
 						      const uint32_t *__restrict__ slot_of_path, const uint32_t *__restrict__ slot_first,
 						      uint32_t n_samples, uint32_t S, const uint32_t *__restrict__ smin,
@@ -314,8 +252,8 @@ __global__ __launch_bounds__(C_TPB) void k_cl_records(uint32_t nrec, const uint3
 						      uint32_t *__restrict__ ac, uint32_t *__restrict__ an, uint32_t *__restrict__ ns,
 						      uint8_t *__restrict__ flags, const uint32_t *__restrict__ dst)
 {
-	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (C_TPB / 64);
-	for (uint32_t i0 = blockIdx.x * (C_TPB / 64) + (threadIdx.x >> 6); i0 < nrec; i0 += waves) {
+	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
+	for (uint32_t i0 = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); i0 < nrec; i0 += waves) {
 		const uint32_t i = dst ? dst[i0] : i0;
 		const uint32_t q = o_q[i], ra = o_ref[i], own = slot_of_path[o_path[i]];
 		const uint64_t base = (uint64_t)qidx[q] * S;
@@ -361,7 +299,7 @@ __global__ __launch_bounds__(C_TPB) void k_cl_records(uint32_t nrec, const uint3
 
 __global__ void k_cl_blocks(uint64_t n2, const uint32_t *__restrict__ need, const uint32_t *__restrict__ boff, uint32_t *__restrict__ blist)
 {
-	for (uint64_t x = (uint64_t)blockIdx.x * C_TPB + threadIdx.x; x < n2; x += (uint64_t)gridDim.x * C_TPB)
+	for (uint64_t x = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; x < n2; x += (uint64_t)gridDim.x * Q_TPB)
 		if (need[x])
 			blist[boff[x]] = (uint32_t)x;
 }
@@ -369,14 +307,14 @@ __global__ void k_cl_rec_block(uint32_t nrec, const uint32_t *__restrict__ perm,
 			       const uint32_t *__restrict__ rq, const uint8_t *__restrict__ orv, const uint32_t *__restrict__ boff,
 			       uint32_t *__restrict__ o_block, const uint32_t *__restrict__ dst)
 {
-	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < nrec; i += gridDim.x * C_TPB) {
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		const uint32_t t = rlist[perm[i]];
 		o_block[dst ? dst[i] : i] = boff[2 * (size_t)rq[t] + orv[t]];
 	}
 }
 __global__ void k_cl_block_cnt(uint32_t nb, const uint32_t *__restrict__ blist, const uint32_t *__restrict__ aoff, uint64_t *__restrict__ cnt)
 {
-	for (uint32_t b = blockIdx.x * C_TPB + threadIdx.x; b < nb; b += gridDim.x * C_TPB) {
+	for (uint32_t b = blockIdx.x * Q_TPB + threadIdx.x; b < nb; b += gridDim.x * Q_TPB) {
 		const uint32_t q = blist[b] >> 1;
 		cnt[b] = aoff[q + 1] - aoff[q];
 	}
@@ -394,21 +332,21 @@ __device__ __forceinline__ Spelled spelled(uint64_t j, uint32_t nb, const uint64
 					   const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ steps)
 {
 	Spelled s;
-	const uint32_t b = seg_of(block_off, nb, j);
+	const uint32_t b = span_of(block_off, nb, j);
 	s.q = blist[b] >> 1;
 	s.o = blist[b] & 1u;
 	s.a = aoff[s.q] + (uint32_t)(j - block_off[b]);
 	s.t = afirst[s.a];
-	s.p = rpos[s.t] & ~ROLE;
-	s.rev = (rpos[s.t] & ROLE) != 0;
+	s.p = rpos[s.t] & ~ROLE_BIT;
+	s.rev = (rpos[s.t] & ROLE_BIT) != 0;
 	s.len = rlen[s.t];
-	s.first = s.o ? tstep(steps, s.p, s.len, s.rev, s.len - 1) ^ 1u : tstep(steps, s.p, s.len, s.rev, 0);
+	s.first = s.o ? trav_step(steps, s.p, s.len, s.rev, s.len - 1) ^ 1u : trav_step(steps, s.p, s.len, s.rev, 0);
 	return s;
 }
 // inner step k (0-based) in the reference's direction
 __device__ __forceinline__ uint32_t inner_step(const Spelled &s, const uint32_t *__restrict__ steps, uint32_t k)
 {
-	return s.o ? tstep(steps, s.p, s.len, s.rev, s.len - 2 - k) ^ 1u : tstep(steps, s.p, s.len, s.rev, k + 1);
+	return s.o ? trav_step(steps, s.p, s.len, s.rev, s.len - 2 - k) ^ 1u : trav_step(steps, s.p, s.len, s.rev, k + 1);
 }
 
 __global__ void k_cl_spell_len(uint64_t nsp, uint32_t nb, const uint64_t *__restrict__ block_off, const uint32_t *__restrict__ blist,
@@ -417,7 +355,7 @@ __global__ void k_cl_spell_len(uint64_t nsp, uint32_t nb, const uint64_t *__rest
 			       const uint32_t *__restrict__ vid, const uint64_t *__restrict__ ilen, const uint64_t *__restrict__ atl,
 			       const uint8_t *__restrict__ anchored, uint64_t *__restrict__ slen, uint64_t *__restrict__ alen)
 {
-	for (uint64_t j = (uint64_t)blockIdx.x * C_TPB + threadIdx.x; j < nsp; j += (uint64_t)gridDim.x * C_TPB) {
+	for (uint64_t j = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; j < nsp; j += (uint64_t)gridDim.x * Q_TPB) {
 		const Spelled s = spelled(j, nb, block_off, blist, aoff, afirst, rpos, rlen, steps);
 		const uint32_t v = s.first >> 1;
 		const bool an = anchored[s.q];
@@ -427,7 +365,7 @@ __global__ void k_cl_spell_len(uint64_t nsp, uint32_t nb, const uint64_t *__rest
 }
 
 // one wave per spelled allele: the bases, then the AT string
-__global__ __launch_bounds__(C_TPB) void k_cl_emit(uint64_t nsp, uint32_t nb, const uint64_t *__restrict__ block_off,
+__global__ __launch_bounds__(Q_TPB) void k_cl_emit(uint64_t nsp, uint32_t nb, const uint64_t *__restrict__ block_off,
 						   const uint32_t *__restrict__ blist, const uint32_t *__restrict__ aoff,
 						   const uint32_t *__restrict__ afirst, const uint64_t *__restrict__ rpos,
 						   const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ steps,
@@ -437,8 +375,8 @@ __global__ __launch_bounds__(C_TPB) void k_cl_emit(uint64_t nsp, uint32_t nb, co
 						   unsigned long long *__restrict__ bad)
 {
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint64_t waves = (uint64_t)gridDim.x * (C_TPB / 64);
-	for (uint64_t j = (uint64_t)blockIdx.x * (C_TPB / 64) + (threadIdx.x >> 6); j < nsp; j += waves) {
+	const uint64_t waves = (uint64_t)gridDim.x * (Q_TPB / 64);
+	for (uint64_t j = (uint64_t)blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); j < nsp; j += waves) {
 		const Spelled s = spelled(j, nb, block_off, blist, aoff, afirst, rpos, rlen, steps);
 		const bool an = anchored[s.q];
 		uint64_t w = s_off[j], wa = a_off[j];
@@ -463,12 +401,6 @@ __global__ __launch_bounds__(C_TPB) void k_cl_emit(uint64_t nsp, uint32_t nb, co
 		}
 		emit_steps(lane, m, [&](uint32_t k) { return inner_step(s, steps, k); }, seq_off, seq, vid, w, wa, o_seq, o_at, bad);
 	}
-}
-
-static void check_call_32(uint64_t v, const char *what)
-{
-	if (v >= 0xFFFFFFFFull)
-		throw HipError(std::string("the call needs ") + std::to_string(v) + " " + what + ": 2^32 or more are refused");
 }
 
 } // namespace povu_hip
@@ -525,346 +457,435 @@ struct CallsOwner {
 	PinnedVec<char> seq, at;
 	std::vector<uint64_t> contig_len;
 };
+
+using namespace povu_hip;
+
+// what a call is given, checked, and the host tables made of it
+struct CallInputs {
+	const povu_hip_sites *sites;
+	const povu_hip_call_refs *refs;
+	const uint32_t *slot_of_path;
+	const povu_hip_trav_opts *opts;
+	uint32_t n, P, nR, S, NS, n_trees = 0;
+	bool inversions;
+	std::vector<uint32_t> ref_of_path, slot_first, qa, qz; // reference number of every path (NO_QUERY: none), first slot of every sample, the queries
+	std::vector<uint8_t> qor;
+};
+// cl_ws and cl_slot: the references, the sites' callability, the slot table, the flubble records before they have rows
+struct CallWs {
+	std::vector<uint64_t> ref_base; // first reference step of every reference, the references concatenated
+	uint64_t NR;			// reference steps
+	uint64_t *d_ref_base, *rlen64, *roff, *ilen, *atl, *s64;
+	uint32_t *d_ref_path, *d_ref_of_path, *d_slot, *d_slot_first, *d_parent, *d_tree, *scnt, *soffv, *scur, *sval, *qv, *hit, *pres, *keep, *qidx,
+		*words;
+	uint8_t *d_fam, *callable, *called, *anchored, *rflag;
+	uint32_t *rlist, *perm, *perm2, *key, *key2; // perm: the flubble records sorted by (reference, POS), once flubble_records has run
+	uint64_t *pos;
+	void *tmp;
+	size_t tmp_bytes;
+	uint32_t nQ = 0, nfl = 0; // kept sites, flubble records
+	uint32_t *smin, *smax;
+};
+// the inversion records and where the flubble records go in the one list
+struct CallInv {
+	InvIn in;
+	InvDevice v;
+	uint32_t *f_dst = nullptr;
+};
+// cl_rec: the per-record arrays and the spelling's inputs
+struct CallRecs {
+	uint32_t nrec = 0, nb = 0, nfb = 0; // records; blocks: all, those of the flubble records
+	uint64_t n_ac = 0, nsp = 0, nfsp = 0; // ALT counts; spelled alleles: all, those of the flubble blocks
+	InvRows rows;
+	uint32_t *need, *boff, *blist;
+	uint64_t *ac_off, *bcnt, *block_off;
+};
+// cl_spell and cl_bytes
+struct CallSpelled {
+	uint32_t *ac;
+	uint64_t *sp_off, *at_off;
+	char *o_seq, *o_at;
+	uint64_t nbytes[2] = {0, 0};
+	std::vector<uint64_t> h_roff; // bases in front of every reference's first step
+};
+
+// the host-side refusals and the host tables
+CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs, const uint32_t *slot_of_path,
+			     const povu_hip_trav_opts *opts)
+{
+	if (!ctx || !sites || !refs)
+		throw HipError("null context, sites or references");
+	if (!ctx->g.block)
+		throw HipError("a call needs a resident graph (povu_hip_graph_upload first)");
+	if (!ctx->seq_valid || ctx->seq_gen != ctx->g.gen)
+		throw HipError("no sequences are resident for the graph now uploaded (povu_hip_segments_upload after povu_hip_graph_upload)");
+	if (!ctx->paths_valid || ctx->paths_gen != ctx->g.gen)
+		throw HipError("no paths are resident for the graph now uploaded (povu_hip_paths_upload after povu_hip_graph_upload)");
+	CallInputs in{sites, refs, slot_of_path, opts, sites->n, ctx->n_paths, refs->n_refs, refs->n_slots, refs->n_samples};
+	const uint32_t n = in.n, P = in.P, nR = in.nR, S = in.S, NS = in.NS;
+	in.inversions = opts && (opts->flags & POVU_HIP_T_INVERSIONS);
+	if (n >= 0x7FFFFFFFu)
+		throw HipError("too many sites");
+	if (n && (!sites->id1 || !sites->id2 || !sites->or1 || !sites->or2 || !sites->parent || !sites->family || !sites->tree))
+		throw HipError("null site arrays");
+	if (!nR || !refs->ref_path)
+		throw HipError("no reference path");
+	if (!slot_of_path || !S || !NS || !refs->sample_of_slot)
+		throw HipError("no genotype slots");
+	in.ref_of_path.assign(P, NO_QUERY);
+	in.slot_first.assign(NS + 1, 0);
+	for (uint32_t r = 0; r < nR; r++) {
+		if (refs->ref_path[r] >= P || (r && refs->ref_path[r] <= refs->ref_path[r - 1]))
+			throw HipError("reference paths must be ascending indices of resident paths");
+		in.ref_of_path[refs->ref_path[r]] = r;
+	}
+	for (uint32_t k = 0; k < P; k++)
+		if (slot_of_path[k] >= S)
+			throw HipError("path " + std::to_string(k) + " has no genotype slot");
+	for (uint32_t sl = 0; sl < S; sl++) {
+		const uint32_t sm = refs->sample_of_slot[sl];
+		if (sm >= NS || (sl && sm < refs->sample_of_slot[sl - 1]) || (sl && sm > refs->sample_of_slot[sl - 1] + 1) || (!sl && sm))
+			throw HipError("the slots of a sample must be consecutive, samples in order");
+		in.slot_first[sm + 1] = sl + 1;
+	}
+	in.qa.resize(n), in.qz.resize(n), in.qor.resize(n);
+	for (uint32_t q = 0; q < n; q++) {
+		if (sites->parent[q] != POVU_HIP_NIL && sites->parent[q] >= n)
+			throw HipError("site " + std::to_string(q) + " has a parent that is no site");
+		in.n_trees = std::max(in.n_trees, sites->tree[q] + 1);
+		in.qa[q] = sites->id1[q];
+		in.qz[q] = sites->id2[q];
+		in.qor[q] = (uint8_t)((sites->or1[q] & 1u) | ((sites->or2[q] & 1u) << 1));
+	}
+	return in;
+}
+
+// the reference steps concatenated, the call's workspace and uploads, the bases in front of every reference step
+void reference_offsets(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
+{
+	const ResidentGraph &g = ctx->g;
+	hipStream_t s = ctx->stream;
+	const uint32_t n = in.n, P = in.P, nR = in.nR, NS = in.NS, R = d.R;
+	std::vector<uint64_t> path_off((size_t)P + 1);
+	w.ref_base.assign((size_t)nR + 1, 0);
+	HIP_CHECK(copy_async(path_off.data(), ctx->path_off, ((size_t)P + 1) * 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	for (uint32_t r = 0; r < nR; r++)
+		w.ref_base[r + 1] = w.ref_base[r] + path_off[in.refs->ref_path[r] + 1] - path_off[in.refs->ref_path[r]];
+	const uint64_t NR = w.NR = w.ref_base[nR];
+	const size_t n1 = (size_t)n + 1, hit_words = ((uint64_t)n * nR * 2 + 31) / 32 + 1, pres_words = ((uint64_t)in.n_trees * nR + 31) / 32 + 1;
+	w.tmp_bytes = std::max(prim_tmp_bytes(std::max<size_t>({(size_t)g.V + 1, n1, 2 * (size_t)n + 1}), false), prim_tmp_bytes((size_t)R + 1, true)) + 256;
+	carve(ctx->cl_ws, [&](Spans &take) {
+		take((size_t)nR + 1, w.d_ref_base, w.d_ref_path);
+		take((size_t)P + 1, w.d_ref_of_path, w.d_slot);
+		take((size_t)NS + 1, w.d_slot_first);
+		take(n1, w.d_parent, w.d_tree, w.d_fam, w.callable, w.called, w.anchored, w.keep, w.qidx);
+		take(NR + 1, w.rlen64, w.roff);
+		take((size_t)g.V + 1, w.scnt, w.soffv, w.scur);
+		take(2 * n1, w.sval, w.qv);
+		take(hit_words, w.hit);
+		take(pres_words, w.pres);
+		take((size_t)d.n_al + 1, w.ilen, w.atl);
+		take((size_t)R + 1, w.rflag, w.rlist, w.perm, w.perm2, w.key, w.key2, w.pos);
+		take(scan_exclusive_u64_tmp(std::max<uint64_t>(NR + 1, 1)), w.s64);
+		take(8, w.words);
+		take(w.tmp_bytes, w.tmp);
+	});
+	HIP_CHECK(copy_async(w.d_ref_base, w.ref_base.data(), ((size_t)nR + 1) * 8, hipMemcpyHostToDevice, s));
+	HIP_CHECK(copy_async(w.d_ref_path, in.refs->ref_path, (size_t)nR * 4, hipMemcpyHostToDevice, s));
+	if (P) {
+		HIP_CHECK(copy_async(w.d_ref_of_path, in.ref_of_path.data(), (size_t)P * 4, hipMemcpyHostToDevice, s));
+		HIP_CHECK(copy_async(w.d_slot, in.slot_of_path, (size_t)P * 4, hipMemcpyHostToDevice, s));
+	}
+	HIP_CHECK(copy_async(w.d_slot_first, in.slot_first.data(), ((size_t)NS + 1) * 4, hipMemcpyHostToDevice, s));
+	if (n) {
+		HIP_CHECK(copy_async(w.d_parent, in.sites->parent, (size_t)n * 4, hipMemcpyHostToDevice, s));
+		HIP_CHECK(copy_async(w.d_tree, in.sites->tree, (size_t)n * 4, hipMemcpyHostToDevice, s));
+		HIP_CHECK(copy_async(w.d_fam, in.sites->family, n, hipMemcpyHostToDevice, s));
+	}
+	HIP_CHECK(hipMemsetAsync(w.words, 0, 32, s));
+	HIP_CHECK(hipMemsetAsync(w.scnt, 0, ((size_t)g.V + 1) * 4, s));
+	HIP_CHECK(hipMemsetAsync(w.scur, 0, ((size_t)g.V + 1) * 4, s));
+	HIP_CHECK(hipMemsetAsync(w.hit, 0, hit_words * 4, s));
+	HIP_CHECK(hipMemsetAsync(w.pres, 0, pres_words * 4, s));
+
+	HIP_CHECK(hipMemsetAsync(w.rlen64 + NR, 0, 8, s));
+	if (NR)
+		KLAUNCH(k_cl_ref_len, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, NR, w.d_ref_base, nR, w.d_ref_path, ctx->path_off, ctx->path_steps, ctx->seq_off,
+			w.rlen64);
+	scan_exclusive_u64(w.rlen64, w.roff, NR + 1, w.s64, s);
+}
+
+// the called sites, those kept (two alleles or more), their alleles' inner lengths
+void callability(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
+{
+	const ResidentGraph &g = ctx->g;
+	hipStream_t s = ctx->stream;
+	const uint32_t n = in.n, nR = in.nR, n_al = d.n_al;
+	const uint64_t NR = w.NR;
+	const size_t n1 = (size_t)n + 1;
+	if (n) {
+		KLAUNCH(k_cl_seg_count, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, d.q.qa, d.q.qz, g.vid, g.V, w.scnt, w.qv);
+		scan_exclusive_u32(w.scnt, w.soffv, (size_t)g.V + 1, w.tmp, w.tmp_bytes, s);
+		KLAUNCH(k_cl_seg_fill, dim3(stride_blocks(2 * (size_t)n)), dim3(Q_TPB), 0, s, n, w.qv, w.soffv, w.scur, w.sval);
+		if (NR)
+			KLAUNCH(k_cl_hits, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, NR, w.d_ref_base, nR, w.d_ref_path, ctx->path_off, ctx->path_steps, w.soffv,
+				w.sval, w.hit);
+		KLAUNCH(k_cl_present, dim3(stride_blocks((size_t)n * nR)), dim3(Q_TPB), 0, s, (uint64_t)n, nR, w.hit, w.d_tree, w.pres);
+		KLAUNCH(k_cl_callable, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, nR, w.hit, w.pres, w.d_tree, w.d_parent, w.d_fam, w.callable, w.called);
+		KLAUNCH(k_cl_unparent, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.callable, w.d_parent, w.called);
+	}
+	KLAUNCH(k_cl_keep, dim3(stride_blocks(n1)), dim3(Q_TPB), 0, s, n, w.called, d.aoff, w.keep, w.words + 1);
+	scan_exclusive_u32(w.keep, w.qidx, n1, w.tmp, w.tmp_bytes, s);
+	uint32_t hw[2] = {0, 0};
+	HIP_CHECK(copy_async(hw, w.qidx + n, 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(hw + 1, w.words + 1, 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	w.nQ = hw[0];
+	if (hw[1] > MAX_ALLELES)
+		throw HipError("a called site has " + std::to_string(hw[1]) + " alleles: more than 65534 in one record are refused");
+	if (n_al) {
+		KLAUNCH(k_cl_inner, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, d.afirst, d.rq, w.keep, d.rpos, d.rlen, ctx->path_steps, ctx->seq_off, g.vid,
+			w.ilen, w.atl);
+	}
+	if (n)
+		KLAUNCH(k_cl_anchored, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, d.aoff, w.ilen, w.anchored);
+}
+
+// per kept site and genotype slot, the min and max allele
+void slot_table(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
+{
+	hipStream_t s = ctx->stream;
+	const size_t cells = (size_t)w.nQ * in.S + 1;
+	carve(ctx->cl_slot, [&](Spans &take) { take(cells, w.smin, w.smax); });
+	HIP_CHECK(hipMemsetAsync(w.smin, 0xFF, cells * 4, s));
+	HIP_CHECK(hipMemsetAsync(w.smax, 0, cells * 4, s));
+	if (d.R && w.nQ)
+		KLAUNCH(k_cl_slots, dim3(stride_blocks(d.R)), dim3(Q_TPB), 0, s, d.R, d.rq, d.op, d.oa, w.keep, w.qidx, w.d_slot, in.S, w.smin, w.smax);
+}
+
+// flag, compact, POS, the sort by (reference, POS)
+void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
+{
+	hipStream_t s = ctx->stream;
+	const uint32_t R = d.R, nR = in.nR;
+	if (R && w.nQ) {
+		KLAUNCH(k_cl_rec_flag, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, d.rq, d.op, w.keep, w.d_ref_of_path, w.rflag);
+		compact_flagged_u8(w.rflag, R, w.rlist, w.words + 2, w.tmp, w.tmp_bytes, s);
+		w.nfl = read_back(w.words + 2, s);
+	}
+	const uint32_t nfl = w.nfl;
+	refuse_2_32(nfl, "the call needs ", "records");
+	const uint64_t ref_bases = read_back(w.roff + w.NR, s);
+	if (!nfl)
+		return;
+	KLAUNCH(k_cl_pos, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.rlist, d.rq, d.op, d.of, w.d_ref_of_path, w.d_ref_base, w.roff, w.anchored, w.pos,
+		w.perm);
+	LsdSort sort{w.perm, w.perm2, w.key, w.key2, nfl, w.tmp, w.tmp_bytes, s};
+	auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
+		KLAUNCH(k_cl_key, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, which, perm, w.rlist, d.op, w.d_ref_of_path, w.pos, k);
+	};
+	sort.pass(0, 32, write_key);
+	if (ref_bases + 1 >= (1ull << 32))
+		sort.pass(1, 32, write_key);
+	if (nR > 1)
+		sort.pass(2, bits_for(nR), write_key);
+	w.perm = sort.cur;
+}
+
+// the inversion records, and every record's row in the one list; gives the number of all records
+uint32_t inversion_rows(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, const CallWs &w, CallInv &inv)
+{
+	hipStream_t s = ctx->stream;
+	const uint32_t nfl = w.nfl;
+	if (!in.inversions)
+		return nfl;
+	InvIn &iin = inv.in;
+	iin.NR = w.NR, iin.nR = in.nR, iin.S = in.S, iin.NS = in.NS;
+	iin.ref_base = w.d_ref_base, iin.ref_path = w.d_ref_path, iin.slot_of_path = w.d_slot, iin.slot_first = w.d_slot_first, iin.roff = w.roff;
+	iin.max_steps = in.opts->max_steps ? in.opts->max_steps : 65536;
+	iin.force_tier2 = (in.opts->flags & POVU_HIP_T_FORCE_TIER2) != 0;
+	inv.v = inv_find(ctx, iin);
+	refuse_2_32((uint64_t)nfl + inv.v.n, "the call needs ", "records");
+	if (!inv.v.n)
+		return nfl;
+	uint32_t *f_ref;
+	uint64_t *f_pos;
+	carve(ctx->iv_rows, [&](Spans &take) { take((size_t)nfl + 1, f_ref, inv.f_dst, f_pos); });
+	if (nfl)
+		KLAUNCH(k_cl_sorted_keys, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, d.op, w.d_ref_of_path, w.pos, f_ref, f_pos);
+	inv_merge(ctx, inv.v, nfl, f_ref, f_pos, inv.f_dst);
+	return nfl + inv.v.n;
+}
+
+// the per-record fields, the AC offsets, the blocks a record needs spelled and their alleles
+void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, const CallWs &w, const CallInv &inv, CallRecs &r)
+{
+	hipStream_t s = ctx->stream;
+	const uint32_t n = in.n, nfl = w.nfl, nrec = r.nrec;
+	const InvDevice &iv = inv.v;
+	const size_t r1 = (size_t)nrec + 1, n2 = 2 * (size_t)n + 1;
+	InvRows &o = r.rows;
+	uint64_t *s64;
+	carve(ctx->cl_rec, [&](Spans &take) {
+		take(r1, o.o_q, o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_an, o.o_ns, o.o_block, o.o_nsteps, o.o_pos, o.nalt, r.ac_off, o.o_flags);
+		take((size_t)nrec * in.S + 1, o.gt);
+		take(n2, r.need, r.boff, r.blist);
+		take(n2 + iv.n, r.bcnt, r.block_off);
+		take(scan_exclusive_u64_tmp(std::max(r1, n2 + iv.n)), s64);
+	});
+	HIP_CHECK(hipMemsetAsync(o.o_nsteps, 0, r1 * 4, s));
+	HIP_CHECK(hipMemsetAsync(r.need, 0, n2 * 4, s));
+	HIP_CHECK(hipMemsetAsync(o.nalt + nrec, 0, 8, s));
+	if (nfl)
+		KLAUNCH(k_cl_rec_fields, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, w.pos, d.rq, d.op, d.of, d.oa, d.orv, d.aoff, o.o_q,
+			o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_pos, o.nalt, r.need, inv.f_dst);
+	inv_fields(ctx, inv.in, iv, o);
+	scan_exclusive_u64(o.nalt, r.ac_off, r1, s64, s);
+	HIP_CHECK(copy_async(&r.n_ac, r.ac_off + nrec, 8, hipMemcpyDeviceToHost, s));
+	scan_exclusive_u32(r.need, r.boff, n2, w.tmp, w.tmp_bytes, s);
+	HIP_CHECK(copy_async(&r.nfb, r.boff + 2 * (size_t)n, 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	if (n)
+		KLAUNCH(k_cl_blocks, dim3(stride_blocks(2 * (size_t)n)), dim3(Q_TPB), 0, s, 2 * (uint64_t)n, r.need, r.boff, r.blist);
+	// the inversion records' blocks follow the flubble blocks, one each: REF, then ALT
+	const uint32_t nfb = r.nfb;
+	refuse_2_32((uint64_t)nfb + iv.n, "the call needs ", "blocks");
+	const uint32_t nb = r.nb = nfb + iv.n;
+	HIP_CHECK(hipMemsetAsync(r.bcnt + nb, 0, 8, s));
+	if (nfb)
+		KLAUNCH(k_cl_block_cnt, dim3(stride_blocks(nfb)), dim3(Q_TPB), 0, s, nfb, r.blist, d.aoff, r.bcnt);
+	inv_genotypes(ctx, inv.in, iv, o, nfb, r.bcnt);
+	scan_exclusive_u64(r.bcnt, r.block_off, (size_t)nb + 1, s64, s);
+	HIP_CHECK(copy_async(&r.nsp, r.block_off + nb, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(&r.nfsp, r.block_off + nfb, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// GT rows and counts, then the spelled alleles: lengths, offsets, bytes, the bad-byte refusal
+void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, const CallWs &w, const CallInv &inv, const CallRecs &r, CallSpelled &sp)
+{
+	const ResidentGraph &g = ctx->g;
+	hipStream_t s = ctx->stream;
+	const uint32_t nR = in.nR, nfl = w.nfl, nfb = r.nfb;
+	const uint64_t nsp = r.nsp, nfsp = r.nfsp;
+	const InvDevice &iv = inv.v;
+	const InvRows &o = r.rows;
+	uint64_t *slen, *alen, *s64;
+	unsigned long long *bad;
+	carve(ctx->cl_spell, [&](Spans &take) {
+		take(r.n_ac + 1, sp.ac);
+		take(nsp + 1, slen, alen, sp.sp_off, sp.at_off);
+		take(scan_exclusive_u64_tmp(nsp + 1), s64);
+		take(1, bad);
+	});
+	HIP_CHECK(hipMemsetAsync(sp.ac, 0, (r.n_ac + 1) * 4, s));
+	HIP_CHECK(hipMemsetAsync(bad, 0xFF, 8, s));
+	if (nfl) {
+		KLAUNCH(k_cl_records, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, o.o_q, o.o_path, o.o_ref, w.qidx, w.d_slot, w.d_slot_first, in.NS, in.S, w.smin,
+			w.smax, r.ac_off, d.qstatus, w.anchored, d.aoff, w.ilen, o.gt, sp.ac, o.o_an, o.o_ns, o.o_flags, inv.f_dst);
+		KLAUNCH(k_cl_rec_block, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, d.rq, d.orv, r.boff, o.o_block, inv.f_dst);
+	}
+	inv_counts(ctx, inv.in, iv, o, r.ac_off, sp.ac);
+	HIP_CHECK(hipMemsetAsync(slen + nsp, 0, 8, s));
+	HIP_CHECK(hipMemsetAsync(alen + nsp, 0, 8, s));
+	if (nfsp)
+		KLAUNCH(k_cl_spell_len, dim3(stride_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, nfb, r.block_off, r.blist, d.aoff, d.afirst, d.rpos, d.rlen,
+			ctx->path_steps, ctx->seq_off, g.vid, w.ilen, w.atl, w.anchored, slen, alen);
+	inv_spell_len(ctx, inv.in, iv, slen + nfsp, alen + nfsp);
+	scan_exclusive_u64(slen, sp.sp_off, nsp + 1, s64, s);
+	scan_exclusive_u64(alen, sp.at_off, nsp + 1, s64, s);
+	HIP_CHECK(copy_async(sp.nbytes, sp.sp_off + nsp, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(sp.nbytes + 1, sp.at_off + nsp, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	carve(ctx->cl_bytes, [&](Spans &take) { take(sp.nbytes[0] + 1, sp.o_seq), take(sp.nbytes[1] + 1, sp.o_at); });
+	if (nfsp)
+		KLAUNCH(k_cl_emit, dim3(wave_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, nfb, r.block_off, r.blist, d.aoff, d.afirst, d.rpos, d.rlen, ctx->path_steps,
+			ctx->seq_off, ctx->seq, g.vid, w.anchored, sp.sp_off, sp.at_off, sp.o_seq, sp.o_at, bad);
+	inv_emit(ctx, inv.in, iv, sp.sp_off + nfsp, sp.at_off + nfsp, sp.o_seq, sp.o_at, bad);
+	uint64_t hbad = 0;
+	HIP_CHECK(copy_async(&hbad, bad, 8, hipMemcpyDeviceToHost, s));
+	sp.h_roff.resize(nR ? nR + 1 : 1);
+	for (uint32_t k = 0; k <= nR; k++)
+		HIP_CHECK(copy_async(sp.h_roff.data() + k, w.roff + w.ref_base[k], 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	if (hbad != ~0ull)
+		throw HipError("segment " + std::to_string(read_back(g.vid + hbad, s)) + " holds a byte that is no nucleotide code (ACGTN, lower case, IUPAC)");
+}
+
+povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const CallInv &inv, const CallRecs &r, const CallSpelled &sp, CallTimer &timer)
+{
+	const uint32_t nrec = r.nrec, nb = r.nb, nR = in.nR, S = in.S;
+	const uint64_t nsp = r.nsp, n_ac = r.n_ac;
+	const size_t r1 = (size_t)nrec + 1;
+	const InvRows &d = r.rows;
+	const InvDevice &iv = inv.v;
+	auto o = std::make_unique<CallsOwner>();
+	hand_off(o->query, nrec, d.o_q, nrec, ctx);
+	hand_off(o->path, nrec, d.o_path, nrec, ctx);
+	hand_off(o->first, nrec, d.o_first, nrec, ctx);
+	hand_off(o->ref_allele, nrec, d.o_ref, nrec, ctx);
+	hand_off(o->n_alleles, nrec, d.o_nal, nrec, ctx);
+	hand_off(o->an, nrec, d.o_an, nrec, ctx);
+	hand_off(o->ns, nrec, d.o_ns, nrec, ctx);
+	hand_off(o->block, nrec, d.o_block, nrec, ctx);
+	hand_off(o->n_steps, nrec, d.o_nsteps, nrec, ctx);
+	hand_off(o->pos, nrec, d.o_pos, nrec, ctx);
+	hand_off(o->flags, nrec, d.o_flags, nrec, ctx);
+	hand_off(o->ac_off, r1, r.ac_off, r1, ctx);
+	hand_off(o->ac, n_ac, sp.ac, n_ac, ctx);
+	hand_off(o->gt, (size_t)nrec * S, d.gt, (size_t)nrec * S, ctx);
+	hand_off(o->block_off, (size_t)nb + 1, r.block_off, (size_t)nb + 1, ctx);
+	hand_off(o->seq_off, nsp + 1, sp.sp_off, nsp + 1, ctx);
+	hand_off(o->at_off, nsp + 1, sp.at_off, nsp + 1, ctx);
+	hand_off(o->seq, sp.nbytes[0], sp.o_seq, sp.nbytes[0], ctx);
+	hand_off(o->at, sp.nbytes[1], sp.o_at, sp.nbytes[1], ctx);
+	o->view.device_ms = timer.stop(ctx->stream);
+	o->contig_len.resize(nR);
+	for (uint32_t k = 0; k < nR; k++)
+		o->contig_len[k] = sp.h_roff[k + 1] - sp.h_roff[k];
+	povu_hip_calls &v = o->view;
+	v.n_records = nrec;
+	v.n_slots = S;
+	v.n_blocks = nb;
+	v.n_spelled = nsp;
+	v.n_seq_bytes = sp.nbytes[0];
+	v.n_at_bytes = sp.nbytes[1];
+	v.n_refs = nR;
+	v.n_steps = o->n_steps.data();
+	v.n_inv_records = iv.n, v.n_inv_heads = iv.n_heads, v.n_inv_long = iv.n_long, v.n_inv_tier2 = iv.n_tier2;
+	v.query = o->query.data(), v.path = o->path.data(), v.first = o->first.data(), v.ref_allele = o->ref_allele.data();
+	v.n_alleles = o->n_alleles.data(), v.an = o->an.data(), v.ns = o->ns.data(), v.block = o->block.data();
+	v.pos = o->pos.data(), v.flags = o->flags.data(), v.ac_off = o->ac_off.data(), v.ac = o->ac.data(), v.gt = o->gt.data();
+	v.block_off = o->block_off.data(), v.seq_off = o->seq_off.data(), v.at_off = o->at_off.data(), v.seq = o->seq.data();
+	v.at = o->at.data(), v.contig_len = o->contig_len.data();
+	CallsOwner *raw = o.release();
+	return &raw->view;
+}
 } // namespace
 
 extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
 					 const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, char *err, size_t errlen)
 {
-	using namespace povu_hip;
 	CallTimer timer;
 	return guarded_call(ctx, err, errlen, (povu_hip_calls *)nullptr, [&] {
-		if (!ctx || !sites || !refs)
-			throw HipError("null context, sites or references");
-		if (!ctx->g.block)
-			throw HipError("a call needs a resident graph (povu_hip_graph_upload first)");
-		if (!ctx->seq_valid || ctx->seq_gen != ctx->g.gen)
-			throw HipError("no sequences are resident for the graph now uploaded (povu_hip_segments_upload after povu_hip_graph_upload)");
-		if (!ctx->paths_valid || ctx->paths_gen != ctx->g.gen)
-			throw HipError("no paths are resident for the graph now uploaded (povu_hip_paths_upload after povu_hip_graph_upload)");
-		const uint32_t n = sites->n, P = ctx->n_paths, nR = refs->n_refs, S = refs->n_slots, NS = refs->n_samples;
-		if (n >= 0x7FFFFFFFu)
-			throw HipError("too many sites");
-		if (n && (!sites->id1 || !sites->id2 || !sites->or1 || !sites->or2 || !sites->parent || !sites->family || !sites->tree))
-			throw HipError("null site arrays");
-		if (!nR || !refs->ref_path)
-			throw HipError("no reference path");
-		if (!slot_of_path || !S || !NS || !refs->sample_of_slot)
-			throw HipError("no genotype slots");
-		std::vector<uint32_t> ref_of_path(P, NO_QUERY), slot_first(NS + 1, 0);
-		for (uint32_t r = 0; r < nR; r++) {
-			if (refs->ref_path[r] >= P || (r && refs->ref_path[r] <= refs->ref_path[r - 1]))
-				throw HipError("reference paths must be ascending indices of resident paths");
-			ref_of_path[refs->ref_path[r]] = r;
-		}
-		for (uint32_t k = 0; k < P; k++)
-			if (slot_of_path[k] >= S)
-				throw HipError("path " + std::to_string(k) + " has no genotype slot");
-		for (uint32_t sl = 0; sl < S; sl++) {
-			const uint32_t sm = refs->sample_of_slot[sl];
-			if (sm >= NS || (sl && sm < refs->sample_of_slot[sl - 1]) || (sl && sm > refs->sample_of_slot[sl - 1] + 1) || (!sl && sm))
-				throw HipError("the slots of a sample must be consecutive, samples in order");
-			slot_first[sm + 1] = sl + 1;
-		}
-		uint32_t n_trees = 0;
-		std::vector<uint32_t> qa(n), qz(n);
-		std::vector<uint8_t> qor(n);
-		for (uint32_t q = 0; q < n; q++) {
-			if (sites->parent[q] != POVU_HIP_NIL && sites->parent[q] >= n)
-				throw HipError("site " + std::to_string(q) + " has a parent that is no site");
-			n_trees = std::max(n_trees, sites->tree[q] + 1);
-			qa[q] = sites->id1[q];
-			qz[q] = sites->id2[q];
-			qor[q] = (uint8_t)((sites->or1[q] & 1u) | ((sites->or2[q] & 1u) << 1));
-		}
-		const ResidentGraph &g = ctx->g;
-		hipStream_t s = ctx->stream;
+		const CallInputs in = check_call_inputs(ctx, sites, refs, slot_of_path, opts);
 		const TravDevice d = trav_pipeline(
 			ctx,
-			[&](CallTimer &tm, const QueryLayout &more) { return query_front(ctx, qa, qz, qor, ctx->tr_ws, tm, more); },
+			[&](CallTimer &tm, const QueryLayout &more) { return query_front(ctx, in.qa, in.qz, in.qor, ctx->tr_ws, tm, more); },
 			opts, timer);
-		const uint32_t R = d.R, n_al = d.n_al;
-		const bool inversions = opts && (opts->flags & POVU_HIP_T_INVERSIONS);
-
-		// ---- the reference steps
-		std::vector<uint64_t> path_off((size_t)P + 1), ref_base((size_t)nR + 1, 0);
-		HIP_CHECK(copy_async(path_off.data(), ctx->path_off, ((size_t)P + 1) * 8, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		for (uint32_t r = 0; r < nR; r++)
-			ref_base[r + 1] = ref_base[r] + path_off[refs->ref_path[r] + 1] - path_off[refs->ref_path[r]];
-		const uint64_t NR = ref_base[nR];
-		const size_t n1 = (size_t)n + 1, hit_words = ((uint64_t)n * nR * 2 + 31) / 32 + 1,
-			     pres_words = ((uint64_t)n_trees * nR + 31) / 32 + 1;
-		const size_t scan32 = scan_tmp_bytes(std::max<size_t>({(size_t)g.V + 1, n1, 2 * (size_t)n + 1})) + 256;
-		const size_t comp_a = compact_tmp_bytes((size_t)R + 1) + 256, sort_a = sort_tmp_bytes((size_t)R + 1) + 256;
-		uint64_t *d_ref_base, *rlen64, *roff, *ilen, *atl, *s64;
-		uint32_t *d_ref_path, *d_ref_of_path, *d_slot, *d_slot_first, *d_parent, *d_tree, *scnt, *soffv, *scur, *sval, *qv, *hit, *pres,
-			*keep, *qidx, *words;
-		uint8_t *d_fam, *callable, *called, *anchored, *rflag;
-		uint32_t *rlist, *perm, *perm2, *key, *key2;
-		uint64_t *pos;
-		void *scan_tmp, *comp_tmp, *sort_tmp;
-		carve(ctx->cl_ws, [&](Spans &take) {
-			take((size_t)nR + 1, d_ref_base, d_ref_path);
-			take((size_t)P + 1, d_ref_of_path, d_slot);
-			take((size_t)NS + 1, d_slot_first);
-			take(n1, d_parent, d_tree, d_fam, callable, called, anchored, keep, qidx);
-			take(NR + 1, rlen64, roff);
-			take((size_t)g.V + 1, scnt, soffv, scur);
-			take(2 * n1, sval, qv);
-			take(hit_words, hit);
-			take(pres_words, pres);
-			take((size_t)n_al + 1, ilen, atl);
-			take((size_t)R + 1, rflag, rlist, perm, perm2, key, key2, pos);
-			take(scan64_tmp(std::max<uint64_t>(NR + 1, 1)), s64);
-			take(8, words);
-			take(scan32, scan_tmp);
-			take(comp_a, comp_tmp);
-			take(sort_a, sort_tmp);
-		});
-		HIP_CHECK(copy_async(d_ref_base, ref_base.data(), ((size_t)nR + 1) * 8, hipMemcpyHostToDevice, s));
-		HIP_CHECK(copy_async(d_ref_path, refs->ref_path, (size_t)nR * 4, hipMemcpyHostToDevice, s));
-		if (P) {
-			HIP_CHECK(copy_async(d_ref_of_path, ref_of_path.data(), (size_t)P * 4, hipMemcpyHostToDevice, s));
-			HIP_CHECK(copy_async(d_slot, slot_of_path, (size_t)P * 4, hipMemcpyHostToDevice, s));
-		}
-		HIP_CHECK(copy_async(d_slot_first, slot_first.data(), ((size_t)NS + 1) * 4, hipMemcpyHostToDevice, s));
-		if (n) {
-			HIP_CHECK(copy_async(d_parent, sites->parent, (size_t)n * 4, hipMemcpyHostToDevice, s));
-			HIP_CHECK(copy_async(d_tree, sites->tree, (size_t)n * 4, hipMemcpyHostToDevice, s));
-			HIP_CHECK(copy_async(d_fam, sites->family, n, hipMemcpyHostToDevice, s));
-		}
-		HIP_CHECK(hipMemsetAsync(words, 0, 32, s));
-		HIP_CHECK(hipMemsetAsync(scnt, 0, ((size_t)g.V + 1) * 4, s));
-		HIP_CHECK(hipMemsetAsync(scur, 0, ((size_t)g.V + 1) * 4, s));
-		HIP_CHECK(hipMemsetAsync(hit, 0, hit_words * 4, s));
-		HIP_CHECK(hipMemsetAsync(pres, 0, pres_words * 4, s));
-
-		// ---- reference offsets
-		HIP_CHECK(hipMemsetAsync(rlen64 + NR, 0, 8, s));
-		if (NR)
-			KLAUNCH(k_cl_ref_len, dim3(cblk(NR)), dim3(C_TPB), 0, s, NR, d_ref_base, nR, d_ref_path, ctx->path_off, ctx->path_steps,
-				ctx->seq_off, rlen64);
-		scan64(rlen64, roff, NR + 1, s64, s);
-
-		// ---- callability
-		if (n) {
-			KLAUNCH(k_cl_seg_count, dim3(cblk(n)), dim3(C_TPB), 0, s, n, d.q.qa, d.q.qz, g.vid, g.V, scnt, qv);
-			scan_exclusive_u32(scnt, soffv, (size_t)g.V + 1, scan_tmp, scan32, s);
-			KLAUNCH(k_cl_seg_fill, dim3(cblk(2 * (size_t)n)), dim3(C_TPB), 0, s, n, qv, soffv, scur, sval);
-			if (NR)
-				KLAUNCH(k_cl_hits, dim3(cblk(NR)), dim3(C_TPB), 0, s, NR, d_ref_base, nR, d_ref_path, ctx->path_off, ctx->path_steps,
-					soffv, sval, hit);
-			KLAUNCH(k_cl_present, dim3(cblk((size_t)n * nR)), dim3(C_TPB), 0, s, (uint64_t)n, nR, hit, d_tree, pres);
-			KLAUNCH(k_cl_callable, dim3(cblk(n)), dim3(C_TPB), 0, s, n, nR, hit, pres, d_tree, d_parent, d_fam, callable, called);
-			KLAUNCH(k_cl_unparent, dim3(cblk(n)), dim3(C_TPB), 0, s, n, callable, d_parent, called);
-		}
-		KLAUNCH(k_cl_keep, dim3(cblk(n1)), dim3(C_TPB), 0, s, n, called, d.aoff, keep, words + 1);
-		scan_exclusive_u32(keep, qidx, n1, scan_tmp, scan32, s);
-		uint32_t hw[2] = {0, 0};
-		HIP_CHECK(copy_async(hw, qidx + n, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(copy_async(hw + 1, words + 1, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		const uint32_t nQ = hw[0];
-		if (hw[1] > MAX_ALLELES)
-			throw HipError("a called site has " + std::to_string(hw[1]) + " alleles: more than 65534 in one record are refused");
-		if (n_al) {
-			KLAUNCH(k_cl_inner, dim3(cblk(n_al)), dim3(C_TPB), 0, s, n_al, d.afirst, d.rq, keep, d.rpos, d.rlen, ctx->path_steps,
-				ctx->seq_off, g.vid, ilen, atl);
-		}
-		if (n)
-			KLAUNCH(k_cl_anchored, dim3(cblk(n)), dim3(C_TPB), 0, s, n, keep, d.aoff, ilen, anchored);
-
-		// ---- slot table and records
-		uint32_t *smin, *smax;
-		carve(ctx->cl_slot, [&](Spans &take) { take((size_t)nQ * S + 1, smin, smax); });
-		HIP_CHECK(hipMemsetAsync(smin, 0xFF, ((size_t)nQ * S + 1) * 4, s));
-		HIP_CHECK(hipMemsetAsync(smax, 0, ((size_t)nQ * S + 1) * 4, s));
-		uint32_t nrec = 0;
-		if (R && nQ) {
-			KLAUNCH(k_cl_slots, dim3(cblk(R)), dim3(C_TPB), 0, s, R, d.rq, d.op, d.oa, keep, qidx, d_slot, S, smin, smax);
-			KLAUNCH(k_cl_rec_flag, dim3(cblk(R)), dim3(C_TPB), 0, s, R, d.rq, d.op, keep, d_ref_of_path, rflag);
-			compact_flagged_u8(rflag, R, rlist, words + 2, comp_tmp, comp_a, s);
-			HIP_CHECK(copy_async(&nrec, words + 2, 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
-		}
-		check_call_32(nrec, "records");
-		uint64_t ref_bases = 0;
-		HIP_CHECK(copy_async(&ref_bases, roff + NR, 8, hipMemcpyDeviceToHost, s));
-		const uint32_t nfl = nrec; // the flubble records; nrec: all records
-		// the per-record arrays and the spelling's inputs (cl_rec)
-		uint32_t *o_q, *o_path, *o_first, *o_ref, *o_nal, *o_an, *o_ns, *o_block, *o_nsteps, *need, *boff, *blist;
-		uint64_t *o_pos, *nalt, *ac_off, *bcnt, *block_off;
-		uint8_t *o_flags;
-		uint16_t *gt;
-		const size_t n2 = 2 * (size_t)n + 1;
-		HIP_CHECK(hipStreamSynchronize(s));
-		if (nfl) {
-			KLAUNCH(k_cl_pos, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, rlist, d.rq, d.op, d.of, d_ref_of_path, d_ref_base, roff, anchored,
-				pos, perm);
-			uint32_t *cur = perm, *nxt = perm2;
-			auto pass = [&](int which, unsigned bits) {
-				KLAUNCH(k_cl_key, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, which, cur, rlist, d.op, d_ref_of_path, pos, key);
-				sort_pairs_u32(key, key2, cur, nxt, nfl, bits, sort_tmp, sort_a, s);
-				std::swap(cur, nxt);
-			};
-			pass(0, 32);
-			if (ref_bases + 1 >= (1ull << 32))
-				pass(1, 32);
-			if (nR > 1)
-				pass(2, bits_for(nR));
-			perm = cur;
-		}
-		// ---- the inversion records, and every record's row in the one list
-		InvIn iin;
-		InvDevice iv;
-		uint32_t *f_dst = nullptr;
-		if (inversions) {
-			iin.NR = NR, iin.nR = nR, iin.S = S, iin.NS = NS;
-			iin.ref_base = d_ref_base, iin.ref_path = d_ref_path, iin.slot_of_path = d_slot, iin.slot_first = d_slot_first, iin.roff = roff;
-			iin.max_steps = opts->max_steps ? opts->max_steps : 65536;
-			iin.force_tier2 = (opts->flags & POVU_HIP_T_FORCE_TIER2) != 0;
-			iv = inv_find(ctx, iin);
-			check_call_32((uint64_t)nfl + iv.n, "records");
-			if (iv.n) {
-				uint32_t *f_ref;
-				uint64_t *f_pos;
-				carve(ctx->iv_rows, [&](Spans &take) { take((size_t)nfl + 1, f_ref, f_dst, f_pos); });
-				if (nfl)
-					KLAUNCH(k_cl_sorted_keys, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, perm, rlist, d.op, d_ref_of_path, pos, f_ref, f_pos);
-				inv_merge(ctx, iv, nfl, f_ref, f_pos, f_dst);
-				nrec = nfl + iv.n;
-			}
-		}
-		const size_t r1 = (size_t)nrec + 1;
-		carve(ctx->cl_rec, [&](Spans &take) {
-			take(r1, o_q, o_path, o_first, o_ref, o_nal, o_an, o_ns, o_block, o_nsteps, o_pos, nalt, ac_off, o_flags);
-			take((size_t)nrec * S + 1, gt);
-			take(n2, need, boff, blist);
-			take(n2 + iv.n, bcnt, block_off);
-			take(scan64_tmp(std::max(r1, n2 + iv.n)), s64);
-		});
-		HIP_CHECK(hipMemsetAsync(o_nsteps, 0, r1 * 4, s));
-		const InvRows rows{o_q, o_path, o_first, o_ref, o_nal, o_an, o_ns, o_block, o_nsteps, o_pos, nalt, o_flags, gt};
-		HIP_CHECK(hipMemsetAsync(need, 0, n2 * 4, s));
-		HIP_CHECK(hipMemsetAsync(nalt + nrec, 0, 8, s));
-		if (nfl)
-			KLAUNCH(k_cl_rec_fields, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, perm, rlist, pos, d.rq, d.op, d.of, d.oa, d.orv, d.aoff, o_q,
-				o_path, o_first, o_ref, o_nal, o_pos, nalt, need, f_dst);
-		inv_fields(ctx, iin, iv, rows);
-		scan64(nalt, ac_off, r1, s64, s);
-		uint64_t n_ac = 0;
-		HIP_CHECK(copy_async(&n_ac, ac_off + nrec, 8, hipMemcpyDeviceToHost, s));
-		scan_exclusive_u32(need, boff, n2, scan_tmp, scan32, s);
-		uint32_t nb = 0;
-		HIP_CHECK(copy_async(&nb, boff + 2 * (size_t)n, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		if (n)
-			KLAUNCH(k_cl_blocks, dim3(cblk(2 * (size_t)n)), dim3(C_TPB), 0, s, 2 * (uint64_t)n, need, boff, blist);
-		const uint32_t nfb = nb; // the flubble blocks; the inversion records' blocks follow them, one each: REF, then ALT
-		check_call_32((uint64_t)nfb + iv.n, "blocks");
-		nb = nfb + iv.n;
-		HIP_CHECK(hipMemsetAsync(bcnt + nb, 0, 8, s));
-		if (nfb)
-			KLAUNCH(k_cl_block_cnt, dim3(cblk(nfb)), dim3(C_TPB), 0, s, nfb, blist, d.aoff, bcnt);
-		inv_genotypes(ctx, iin, iv, rows, nfb, bcnt);
-		scan64(bcnt, block_off, (size_t)nb + 1, s64, s);
-		uint64_t nsp = 0, nfsp = 0; // spelled alleles: all, those of the flubble blocks
-		HIP_CHECK(copy_async(&nsp, block_off + nb, 8, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(copy_async(&nfsp, block_off + nfb, 8, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-
-		// ---- spelling: lengths, offsets, bytes
-		uint32_t *ac;
-		uint64_t *slen, *alen, *sp_off, *at_off, *s64b;
-		unsigned long long *bad;
-		carve(ctx->cl_spell, [&](Spans &take) {
-			take(n_ac + 1, ac);
-			take(nsp + 1, slen, alen, sp_off, at_off);
-			take(scan64_tmp(nsp + 1), s64b);
-			take(1, bad);
-		});
-		HIP_CHECK(hipMemsetAsync(ac, 0, (n_ac + 1) * 4, s));
-		HIP_CHECK(hipMemsetAsync(bad, 0xFF, 8, s));
-		if (nfl) {
-			const unsigned wg = wblk(nfl);
-			KLAUNCH(k_cl_records, dim3(wg), dim3(C_TPB), 0, s, nfl, o_q, o_path, o_ref, qidx, d_slot, d_slot_first, NS, S, smin, smax, ac_off,
-				d.qstatus, anchored, d.aoff, ilen, gt, ac, o_an, o_ns, o_flags, f_dst);
-			KLAUNCH(k_cl_rec_block, dim3(cblk(nfl)), dim3(C_TPB), 0, s, nfl, perm, rlist, d.rq, d.orv, boff, o_block, f_dst);
-		}
-		inv_counts(ctx, iin, iv, rows, ac_off, ac);
-		HIP_CHECK(hipMemsetAsync(slen + nsp, 0, 8, s));
-		HIP_CHECK(hipMemsetAsync(alen + nsp, 0, 8, s));
-		if (nfsp)
-			KLAUNCH(k_cl_spell_len, dim3(cblk(nfsp)), dim3(C_TPB), 0, s, nfsp, nfb, block_off, blist, d.aoff, d.afirst, d.rpos, d.rlen,
-				ctx->path_steps, ctx->seq_off, g.vid, ilen, atl, anchored, slen, alen);
-		inv_spell_len(ctx, iin, iv, slen + nfsp, alen + nfsp);
-		scan64(slen, sp_off, nsp + 1, s64b, s);
-		scan64(alen, at_off, nsp + 1, s64b, s);
-		uint64_t nbytes[2] = {0, 0};
-		HIP_CHECK(copy_async(nbytes, sp_off + nsp, 8, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(copy_async(nbytes + 1, at_off + nsp, 8, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		char *o_seq, *o_at;
-		carve(ctx->cl_bytes, [&](Spans &take) { take(nbytes[0] + 1, o_seq), take(nbytes[1] + 1, o_at); });
-		if (nfsp)
-			KLAUNCH(k_cl_emit, dim3(wblk(nfsp)), dim3(C_TPB), 0, s, nfsp, nfb, block_off, blist, d.aoff, d.afirst, d.rpos, d.rlen,
-				ctx->path_steps, ctx->seq_off, ctx->seq, g.vid, anchored, sp_off, at_off, o_seq, o_at, bad);
-		inv_emit(ctx, iin, iv, sp_off + nfsp, at_off + nfsp, o_seq, o_at, bad);
-		uint64_t hbad = 0;
-		HIP_CHECK(copy_async(&hbad, bad, 8, hipMemcpyDeviceToHost, s));
-		std::vector<uint64_t> h_roff(nR ? nR + 1 : 1);
-		for (uint32_t r = 0; r <= nR; r++)
-			HIP_CHECK(copy_async(h_roff.data() + r, roff + ref_base[r], 8, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		if (hbad != ~0ull) {
-			uint32_t id = 0;
-			HIP_CHECK(copy_async(&id, g.vid + hbad, 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
-			throw HipError("segment " + std::to_string(id) + " holds a byte that is no nucleotide code (ACGTN, lower case, IUPAC)");
-		}
-
-		// ---- to the host
-		auto o = std::make_unique<CallsOwner>();
-		hand_off(o->query, nrec, o_q, nrec, ctx);
-		hand_off(o->path, nrec, o_path, nrec, ctx);
-		hand_off(o->first, nrec, o_first, nrec, ctx);
-		hand_off(o->ref_allele, nrec, o_ref, nrec, ctx);
-		hand_off(o->n_alleles, nrec, o_nal, nrec, ctx);
-		hand_off(o->an, nrec, o_an, nrec, ctx);
-		hand_off(o->ns, nrec, o_ns, nrec, ctx);
-		hand_off(o->block, nrec, o_block, nrec, ctx);
-		hand_off(o->n_steps, nrec, o_nsteps, nrec, ctx);
-		hand_off(o->pos, nrec, o_pos, nrec, ctx);
-		hand_off(o->flags, nrec, o_flags, nrec, ctx);
-		hand_off(o->ac_off, r1, ac_off, r1, ctx);
-		hand_off(o->ac, n_ac, ac, n_ac, ctx);
-		hand_off(o->gt, (size_t)nrec * S, gt, (size_t)nrec * S, ctx);
-		hand_off(o->block_off, (size_t)nb + 1, block_off, (size_t)nb + 1, ctx);
-		hand_off(o->seq_off, nsp + 1, sp_off, nsp + 1, ctx);
-		hand_off(o->at_off, nsp + 1, at_off, nsp + 1, ctx);
-		hand_off(o->seq, nbytes[0], o_seq, nbytes[0], ctx);
-		hand_off(o->at, nbytes[1], o_at, nbytes[1], ctx);
-		o->view.device_ms = timer.stop(s);
-		o->contig_len.resize(nR);
-		for (uint32_t r = 0; r < nR; r++)
-			o->contig_len[r] = h_roff[r + 1] - h_roff[r];
-		povu_hip_calls &v = o->view;
-		v.n_records = nrec;
-		v.n_slots = S;
-		v.n_blocks = nb;
-		v.n_spelled = nsp;
-		v.n_seq_bytes = nbytes[0];
-		v.n_at_bytes = nbytes[1];
-		v.n_refs = nR;
-		v.n_steps = o->n_steps.data();
-		v.n_inv_records = iv.n, v.n_inv_heads = iv.n_heads, v.n_inv_long = iv.n_long, v.n_inv_tier2 = iv.n_tier2;
-		v.query = o->query.data(), v.path = o->path.data(), v.first = o->first.data(), v.ref_allele = o->ref_allele.data();
-		v.n_alleles = o->n_alleles.data(), v.an = o->an.data(), v.ns = o->ns.data(), v.block = o->block.data();
-		v.pos = o->pos.data(), v.flags = o->flags.data(), v.ac_off = o->ac_off.data(), v.ac = o->ac.data(), v.gt = o->gt.data();
-		v.block_off = o->block_off.data(), v.seq_off = o->seq_off.data(), v.at_off = o->at_off.data(), v.seq = o->seq.data();
-		v.at = o->at.data(), v.contig_len = o->contig_len.data();
-		CallsOwner *raw = o.release();
-		return &raw->view;
+		CallWs w;
+		reference_offsets(ctx, in, d, w);
+		callability(ctx, in, d, w);
+		slot_table(ctx, in, d, w);
+		flubble_records(ctx, in, d, w);
+		CallInv inv;
+		CallRecs r;
+		r.nrec = inversion_rows(ctx, in, d, w, inv);
+		record_arrays(ctx, in, d, w, inv, r);
+		CallSpelled sp;
+		spelling(ctx, in, d, w, inv, r, sp);
+		return calls_to_host(ctx, in, inv, r, sp, timer);
 	});
 }
 

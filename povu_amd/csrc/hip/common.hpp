@@ -330,6 +330,9 @@ void scan_exclusive_diff_u32(const uint32_t *in, const uint32_t *sub, uint32_t *
 void scan_exclusive_xor_u128(const ulonglong2 *in, ulonglong2 *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s,
 			     const uint32_t *n_dev = nullptr);
 size_t scan_tmp_bytes(size_t n);
+// exclusive sums of u64 (in == out allowed); tmp holds scan_exclusive_u64_tmp(n) WORDS of 8 bytes
+void scan_exclusive_u64(const uint64_t *in, uint64_t *out, size_t n, uint64_t *tmp, hipStream_t s);
+size_t scan_exclusive_u64_tmp(size_t n);
 // indices of the non-zero bytes of flag[0..n), ascending, into out; their number into *count_dev (device memory).  No
 // prefix array is written: tiles are counted, the counts scanned, the tiles ranked again.
 // ---- bit-rank directory: one 16-byte record per 64 flags = {bits 0..31, bits 32..63, set bits in front of the record, 0}.
@@ -449,6 +452,10 @@ void scan_exclusive_max_u32(const uint32_t *in, uint32_t *out, size_t n, void *t
 void sort_pairs_u32(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits,
 		    void *tmp, size_t tmp_bytes, hipStream_t s);
 size_t sort_tmp_bytes(size_t n);
+// bytes of ONE span that serves every scan, compaction and (with_sort) sort of up to n elements: the primitives of a phase
+// run one after another on one stream and each writes what it reads of its scratch (the scan clears its status words, the
+// sort fills its table, the compaction its tile counts), so they share it
+size_t prim_tmp_bytes(size_t n, bool with_sort);
 
 inline unsigned bits_for(uint64_t max_value)
 {

@@ -38,7 +38,7 @@ struct RefStep {
 __device__ __forceinline__ RefStep ref_step(const InvView &A, uint64_t i)
 {
 	RefStep x;
-	x.r = seg_of(A.ref_base, A.nR, i);
+	x.r = span_of(A.ref_base, A.nR, i);
 	x.path = A.ref_path[x.r];
 	x.begin = A.path_off[x.path];
 	x.end = A.path_off[x.path + 1];
@@ -48,7 +48,7 @@ __device__ __forceinline__ RefStep ref_step(const InvView &A, uint64_t i)
 // is (x, y) the head of a run: y on another path, and (x - 1, y + 1) no match
 __device__ __forceinline__ bool is_head(const InvView &A, const RefStep &x, uint32_t y)
 {
-	const uint32_t pa = seg_of(A.path_off, A.P, y);
+	const uint32_t pa = span_of(A.path_off, A.P, y);
 	if (pa == x.path)
 		return false;
 	if (x.g == x.begin || (uint64_t)y + 1 >= A.path_off[pa + 1])
@@ -56,14 +56,9 @@ __device__ __forceinline__ bool is_head(const InvView &A, const RefStep &x, uint
 	return A.steps[y + 1] != (A.steps[x.g - 1] ^ 1u);
 }
 
-__global__ void k_inv_iota(uint32_t n, uint32_t *__restrict__ a)
-{
-	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < n; i += gridDim.x * C_TPB)
-		a[i] = i;
-}
 __global__ void k_inv_hist(uint32_t N, const uint32_t *__restrict__ steps, uint32_t *__restrict__ cnt)
 {
-	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < N; i += gridDim.x * C_TPB)
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < N; i += gridDim.x * Q_TPB)
 		atomicAdd(cnt + steps[i], 1u);
 }
 
@@ -73,7 +68,7 @@ template <bool EMIT>
 __global__ void k_inv_heads(InvView A, uint32_t long_min, uint64_t *__restrict__ cnt, const uint64_t *__restrict__ hoff,
 			    uint32_t *__restrict__ hx, uint32_t *__restrict__ hy, uint32_t *__restrict__ longs, uint32_t *__restrict__ n_longs)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * C_TPB + threadIdx.x; i < A.NR; i += (uint64_t)gridDim.x * C_TPB) {
+	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < A.NR; i += (uint64_t)gridDim.x * Q_TPB) {
 		const RefStep x = ref_step(A, i);
 		const uint32_t v = A.steps[x.g] ^ 1u, e0 = A.ioff[v], e1 = A.ioff[v + 1];
 		if (e1 - e0 >= long_min) {
@@ -98,12 +93,12 @@ __global__ void k_inv_heads(InvView A, uint32_t long_min, uint64_t *__restrict__
 }
 // ... of the reference steps in `longs`, a wave each, lanes across the list
 template <bool EMIT>
-__global__ __launch_bounds__(C_TPB) void k_inv_heads_wave(InvView A, const uint32_t *__restrict__ longs, uint32_t n_longs,
+__global__ __launch_bounds__(Q_TPB) void k_inv_heads_wave(InvView A, const uint32_t *__restrict__ longs, uint32_t n_longs,
 							  uint64_t *__restrict__ cnt, const uint64_t *__restrict__ hoff,
 							  uint32_t *__restrict__ hx, uint32_t *__restrict__ hy)
 {
-	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (C_TPB / 64);
-	for (uint32_t w = blockIdx.x * (C_TPB / 64) + (threadIdx.x >> 6); w < n_longs; w += waves) {
+	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
+	for (uint32_t w = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); w < n_longs; w += waves) {
 		const uint64_t i = longs[w];
 		const RefStep x = ref_step(A, i);
 		const uint32_t v = A.steps[x.g] ^ 1u, e0 = A.ioff[v], e1 = A.ioff[v + 1];
@@ -136,7 +131,7 @@ __device__ __forceinline__ RunView run_view(const InvView &A, uint32_t i, uint32
 	RunView r;
 	r.gx = x.g;
 	r.y = y;
-	r.pa = seg_of(A.path_off, A.P, y);
+	r.pa = span_of(A.path_off, A.P, y);
 	const uint64_t lx = x.end - x.g, ly = (uint64_t)y - A.path_off[r.pa] + 1;
 	r.lim = min(min(lx, ly), (uint64_t)max_steps + 1);
 	return r;
@@ -146,7 +141,7 @@ __global__ void k_inv_extend(uint32_t H, InvView A, uint32_t max_steps, uint32_t
 			     const uint32_t *__restrict__ hy, uint32_t *__restrict__ hL, uint32_t *__restrict__ hslot,
 			     const uint32_t *__restrict__ slot_of_path, uint32_t *__restrict__ t2, uint32_t *__restrict__ n_t2)
 {
-	for (uint32_t h = blockIdx.x * C_TPB + threadIdx.x; h < H; h += gridDim.x * C_TPB) {
+	for (uint32_t h = blockIdx.x * Q_TPB + threadIdx.x; h < H; h += gridDim.x * Q_TPB) {
 		const RunView r = run_view(A, hx[h], hy[h], max_steps);
 		hslot[h] = slot_of_path[r.pa];
 		const uint64_t cap = min(r.lim, (uint64_t)TIER1_STEPS + 1);
@@ -161,7 +156,7 @@ __global__ void k_inv_extend(uint32_t H, InvView A, uint32_t max_steps, uint32_t
 	}
 }
 // tier 2: a wave per run of `t2`, taken from *next (zeroed before the launch); 64 comparisons a ballot
-__global__ __launch_bounds__(C_TPB) void k_inv_extend_wave(const uint32_t *__restrict__ t2, uint32_t n2, uint32_t *__restrict__ next, InvView A,
+__global__ __launch_bounds__(Q_TPB) void k_inv_extend_wave(const uint32_t *__restrict__ t2, uint32_t n2, uint32_t *__restrict__ next, InvView A,
 							   uint32_t max_steps, const uint32_t *__restrict__ hx, const uint32_t *__restrict__ hy,
 							   uint32_t *__restrict__ hL)
 {
@@ -194,7 +189,7 @@ __global__ __launch_bounds__(C_TPB) void k_inv_extend_wave(const uint32_t *__res
 __global__ void k_inv_report(uint32_t H, uint32_t max_steps, const uint32_t *__restrict__ hx, const uint32_t *__restrict__ hL,
 			     const uint64_t *__restrict__ roff, uint8_t *__restrict__ flag, unsigned long long *__restrict__ n_long)
 {
-	for (uint32_t h = blockIdx.x * C_TPB + threadIdx.x; h < H; h += gridDim.x * C_TPB) {
+	for (uint32_t h = blockIdx.x * Q_TPB + threadIdx.x; h < H; h += gridDim.x * Q_TPB) {
 		const uint32_t L = hL[h];
 		bool keep = false;
 		if (L > max_steps)
@@ -208,7 +203,7 @@ __global__ void k_inv_report(uint32_t H, uint32_t max_steps, const uint32_t *__r
 __global__ void k_inv_key(uint32_t n, int which, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ hx,
 			  const uint32_t *__restrict__ hL, const uint32_t *__restrict__ hslot, uint32_t *__restrict__ key)
 {
-	for (uint32_t t = blockIdx.x * C_TPB + threadIdx.x; t < n; t += gridDim.x * C_TPB) {
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < n; t += gridDim.x * Q_TPB) {
 		const uint32_t h = perm[t];
 		key[t] = which == 0 ? hslot[h] : which == 1 ? hL[h] : hx[h];
 	}
@@ -216,7 +211,7 @@ __global__ void k_inv_key(uint32_t n, int which, const uint32_t *__restrict__ pe
 __global__ void k_inv_group(uint32_t n, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ hx, const uint32_t *__restrict__ hL,
 			    uint32_t *__restrict__ first)
 {
-	for (uint32_t t = blockIdx.x * C_TPB + threadIdx.x; t <= n; t += gridDim.x * C_TPB)
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t <= n; t += gridDim.x * Q_TPB)
 		first[t] = t < n && (t == 0 || hx[perm[t]] != hx[perm[t - 1]] || hL[perm[t]] != hL[perm[t - 1]]);
 }
 __global__ void k_inv_records(uint32_t n, InvView A, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ hx,
@@ -225,12 +220,12 @@ __global__ void k_inv_records(uint32_t n, InvView A, const uint32_t *__restrict_
 			      uint32_t *__restrict__ run_slot, uint32_t *__restrict__ v_ref, uint32_t *__restrict__ v_at,
 			      uint32_t *__restrict__ v_steps, uint64_t *__restrict__ v_pos)
 {
-	for (uint32_t t = blockIdx.x * C_TPB + threadIdx.x; t < n; t += gridDim.x * C_TPB) {
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < n; t += gridDim.x * Q_TPB) {
 		const uint32_t h = perm[t], b = rank[t] + first[t] - 1;
 		run_rec[t] = b;
 		run_slot[t] = hslot[h];
 		if (first[t]) {
-			const uint32_t i = hx[h], r = seg_of(A.ref_base, A.nR, i);
+			const uint32_t i = hx[h], r = span_of(A.ref_base, A.nR, i);
 			v_ref[b] = r;
 			v_at[b] = i;
 			v_steps[b] = hL[h];
@@ -244,7 +239,7 @@ __device__ __forceinline__ bool key_less(uint32_t r0, uint64_t p0, uint32_t r1, 
 __global__ void k_inv_rows_flubble(uint32_t nrec, const uint32_t *__restrict__ f_ref, const uint64_t *__restrict__ f_pos, uint32_t ninv,
 				   const uint32_t *__restrict__ v_ref, const uint64_t *__restrict__ v_pos, uint32_t *__restrict__ f_dst)
 {
-	for (uint32_t i = blockIdx.x * C_TPB + threadIdx.x; i < nrec; i += gridDim.x * C_TPB) {
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		uint32_t lo = 0, hi = ninv; // the inversion records in front: those with a smaller key
 		while (lo < hi) {
 			const uint32_t mid = (lo + hi) >> 1;
@@ -259,7 +254,7 @@ __global__ void k_inv_rows_flubble(uint32_t nrec, const uint32_t *__restrict__ f
 __global__ void k_inv_rows(uint32_t ninv, const uint32_t *__restrict__ v_ref, const uint64_t *__restrict__ v_pos, uint32_t nrec,
 			   const uint32_t *__restrict__ f_ref, const uint64_t *__restrict__ f_pos, uint32_t *__restrict__ v_dst)
 {
-	for (uint32_t b = blockIdx.x * C_TPB + threadIdx.x; b < ninv; b += gridDim.x * C_TPB) {
+	for (uint32_t b = blockIdx.x * Q_TPB + threadIdx.x; b < ninv; b += gridDim.x * Q_TPB) {
 		uint32_t lo = 0, hi = nrec; // the flubble records in front: those whose key is not larger
 		while (lo < hi) {
 			const uint32_t mid = (lo + hi) >> 1;
@@ -276,7 +271,7 @@ __global__ void k_inv_fields(uint32_t ninv, InvView A, const uint32_t *__restric
 			     const uint32_t *__restrict__ v_steps, const uint64_t *__restrict__ v_pos, const uint32_t *__restrict__ v_dst,
 			     InvRows o)
 {
-	for (uint32_t b = blockIdx.x * C_TPB + threadIdx.x; b < ninv; b += gridDim.x * C_TPB) {
+	for (uint32_t b = blockIdx.x * Q_TPB + threadIdx.x; b < ninv; b += gridDim.x * Q_TPB) {
 		const uint32_t d = v_dst[b], r = v_ref[b];
 		o.o_q[d] = NO_QUERY;
 		o.o_path[d] = A.ref_path[r];
@@ -292,7 +287,7 @@ __global__ void k_inv_gt_init(uint64_t n, uint32_t S, uint32_t nb, InvView A, co
 			      const uint32_t *__restrict__ v_dst, const uint32_t *__restrict__ slot_of_path, uint16_t *__restrict__ gt,
 			      uint32_t *__restrict__ o_block, uint64_t *__restrict__ bcnt)
 {
-	for (uint64_t e = (uint64_t)blockIdx.x * C_TPB + threadIdx.x; e < n; e += (uint64_t)gridDim.x * C_TPB) {
+	for (uint64_t e = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; e < n; e += (uint64_t)gridDim.x * Q_TPB) {
 		const uint32_t b = (uint32_t)(e / S), sl = (uint32_t)(e % S);
 		gt[(uint64_t)v_dst[b] * S + sl] = sl == slot_of_path[A.ref_path[v_ref[b]]] ? 0 : POVU_HIP_GT_MISSING;
 		if (sl == 0) {
@@ -306,20 +301,20 @@ __global__ void k_inv_gt_mark(uint32_t n_runs, uint32_t S, InvView A, const uint
 			      const uint32_t *__restrict__ v_ref, const uint32_t *__restrict__ v_dst, const uint32_t *__restrict__ slot_of_path,
 			      uint16_t *__restrict__ gt)
 {
-	for (uint32_t t = blockIdx.x * C_TPB + threadIdx.x; t < n_runs; t += gridDim.x * C_TPB) {
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < n_runs; t += gridDim.x * Q_TPB) {
 		const uint32_t b = run_rec[t], sl = run_slot[t];
 		if (sl != slot_of_path[A.ref_path[v_ref[b]]])
 			gt[(uint64_t)v_dst[b] * S + sl] = 1;
 	}
 }
 // AC, AN, NS and flags: one wave per record, a lane per sample (as k_cl_records)
-__global__ __launch_bounds__(C_TPB) void k_inv_gt_count(uint32_t ninv, uint32_t S, uint32_t n_samples, const uint32_t *__restrict__ slot_first,
+__global__ __launch_bounds__(Q_TPB) void k_inv_gt_count(uint32_t ninv, uint32_t S, uint32_t n_samples, const uint32_t *__restrict__ slot_first,
 							const uint32_t *__restrict__ v_dst, const uint16_t *__restrict__ gt,
 							const uint64_t *__restrict__ ac_off, uint32_t *__restrict__ ac, uint32_t *__restrict__ an,
 							uint32_t *__restrict__ ns, uint8_t *__restrict__ flags)
 {
-	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (C_TPB / 64);
-	for (uint32_t b = blockIdx.x * (C_TPB / 64) + (threadIdx.x >> 6); b < ninv; b += waves) {
+	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
+	for (uint32_t b = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); b < ninv; b += waves) {
 		const uint32_t d = v_dst[b];
 		uint32_t n_an = 0, n_ns = 0, n_ac = 0;
 		for (uint32_t sm = lane; sm < n_samples; sm += 64) {
@@ -347,12 +342,12 @@ __global__ __launch_bounds__(C_TPB) void k_inv_gt_count(uint32_t ninv, uint32_t 
 }
 
 // ---- spelling: REF = the run's steps, ALT = the flipped steps backwards; a wave per record / per spelled allele
-__global__ __launch_bounds__(C_TPB) void k_inv_spell_len(uint32_t ninv, InvView A, const uint32_t *__restrict__ v_at, const uint32_t *__restrict__ v_steps,
+__global__ __launch_bounds__(Q_TPB) void k_inv_spell_len(uint32_t ninv, InvView A, const uint32_t *__restrict__ v_at, const uint32_t *__restrict__ v_steps,
 							 const uint64_t *__restrict__ roff, const uint32_t *__restrict__ vid, uint64_t *__restrict__ slen,
 							 uint64_t *__restrict__ alen)
 {
-	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (C_TPB / 64);
-	for (uint32_t b = blockIdx.x * (C_TPB / 64) + (threadIdx.x >> 6); b < ninv; b += waves) {
+	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
+	for (uint32_t b = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); b < ninv; b += waves) {
 		const uint64_t i = v_at[b], g = ref_step(A, i).g;
 		const uint32_t L = v_steps[b];
 		uint32_t w = 0;
@@ -365,14 +360,14 @@ __global__ __launch_bounds__(C_TPB) void k_inv_spell_len(uint32_t ninv, InvView 
 		}
 	}
 }
-__global__ __launch_bounds__(C_TPB) void k_inv_emit(uint64_t n, InvView A, const uint32_t *__restrict__ v_at, const uint32_t *__restrict__ v_steps,
+__global__ __launch_bounds__(Q_TPB) void k_inv_emit(uint64_t n, InvView A, const uint32_t *__restrict__ v_at, const uint32_t *__restrict__ v_steps,
 						    const uint64_t *__restrict__ seq_off, const char *__restrict__ seq, const uint32_t *__restrict__ vid,
 						    const uint64_t *__restrict__ s_off, const uint64_t *__restrict__ a_off, char *__restrict__ o_seq,
 						    char *__restrict__ o_at, unsigned long long *__restrict__ bad)
 {
 	const uint32_t lane = threadIdx.x & 63u;
-	const uint64_t waves = (uint64_t)gridDim.x * (C_TPB / 64);
-	for (uint64_t j = (uint64_t)blockIdx.x * (C_TPB / 64) + (threadIdx.x >> 6); j < n; j += waves) {
+	const uint64_t waves = (uint64_t)gridDim.x * (Q_TPB / 64);
+	for (uint64_t j = (uint64_t)blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); j < n; j += waves) {
 		const uint32_t b = (uint32_t)(j >> 1), L = v_steps[b];
 		const bool alt = j & 1u;
 		const uint64_t g = ref_step(A, v_at[b]).g;
@@ -388,115 +383,149 @@ static InvView view_of(const povu_hip_ctx *ctx, const InvIn &in, const InvDevice
 	return InvView{in.NR, in.nR, ctx->n_paths, in.ref_base, in.ref_path, ctx->path_off, ctx->path_steps, v.ioff, v.occ};
 }
 
-InvDevice inv_find(povu_hip_ctx *ctx, const InvIn &in)
+namespace
+{
+// iv_ws: the step index, the head counts and offsets of every reference step
+struct InvIndex {
+	uint32_t *longs, *words; // the reference steps with a long list; words: [0] their number, [1] tier-2 runs, [2] tier 2's work counter, [3] reported runs
+	uint64_t *hcnt, *hoff, *s64;
+	unsigned long long *n_long;
+	uint32_t long_min, n_longs = 0;
+};
+// iv_heads: the run heads (x: reference index, y: the other path's global position), their runs
+struct InvHeads {
+	uint32_t H = 0;
+	uint32_t *hx, *hy, *hL, *hslot, *t2, *rlist, *perm2, *key, *key2, *first, *rank;
+	uint8_t *flag;
+	void *tmp;
+	size_t tmp_bytes;
+};
+} // namespace
+
+static InvIndex step_index(povu_hip_ctx *ctx, const InvIn &in, InvDevice &v)
 {
 	hipStream_t s = ctx->stream;
 	const uint64_t N = ctx->n_path_steps, NR = in.NR;
 	const uint32_t V = ctx->g.V;
-	if (N >= 0xFFFFFFFFull - 4096) // (the sort of the step index takes fewer)
-		throw HipError("inversion calls index every path step: " + std::to_string(N) + " steps, 2^32 or more are refused");
-	InvDevice v;
-	if (!N || !NR)
-		return v;
-	// ---- step index
 	const size_t nval = 2 * (size_t)V + 1;
-	const size_t sort_a = sort_tmp_bytes(N + 1) + 256, scan_a = scan_tmp_bytes(nval + 1) + 256;
-	uint32_t *iota, *skey, *occ, *cnt, *ioff, *longs, *words;
-	uint64_t *hcnt, *hoff, *s64;
-	unsigned long long *n_long;
-	void *sort_tmp, *scan_tmp;
+	const size_t tmp_bytes = std::max(sort_tmp_bytes(N + 1), prim_tmp_bytes(nval + 1, false)) + 256;
+	InvIndex x;
+	uint32_t *iota, *skey, *occ, *cnt, *ioff;
+	void *tmp;
 	carve(ctx->iv_ws, [&](Spans &take) {
 		take(N + 1, iota, skey, occ);
 		take(nval + 1, cnt, ioff);
-		take(NR + 1, hcnt, hoff, longs);
-		take(scan64_tmp(NR + 1), s64);
-		take(8, words);
-		take(1, n_long);
-		take(sort_a, sort_tmp);
-		take(scan_a, scan_tmp);
+		take(NR + 1, x.hcnt, x.hoff, x.longs);
+		take(scan_exclusive_u64_tmp(NR + 1), x.s64);
+		take(8, x.words);
+		take(1, x.n_long);
+		take(tmp_bytes, tmp);
 	});
 	HIP_CHECK(hipMemsetAsync(cnt, 0, (nval + 1) * 4, s));
-	HIP_CHECK(hipMemsetAsync(words, 0, 32, s));
-	HIP_CHECK(hipMemsetAsync(n_long, 0, 8, s));
-	HIP_CHECK(hipMemsetAsync(hcnt, 0, (NR + 1) * 8, s));
-	KLAUNCH(k_inv_iota, dim3(cblk(N)), dim3(C_TPB), 0, s, (uint32_t)N, iota);
-	KLAUNCH(k_inv_hist, dim3(cblk(N)), dim3(C_TPB), 0, s, (uint32_t)N, ctx->path_steps, cnt);
-	scan_exclusive_u32(cnt, ioff, nval, scan_tmp, scan_a, s);
-	sort_pairs_u32(ctx->path_steps, skey, iota, occ, N, bits_for(2 * (uint64_t)V), sort_tmp, sort_a, s);
+	HIP_CHECK(hipMemsetAsync(x.words, 0, 32, s));
+	HIP_CHECK(hipMemsetAsync(x.n_long, 0, 8, s));
+	HIP_CHECK(hipMemsetAsync(x.hcnt, 0, (NR + 1) * 8, s));
+	launch_iota((uint32_t)N, iota, s);
+	KLAUNCH(k_inv_hist, dim3(stride_blocks(N)), dim3(Q_TPB), 0, s, (uint32_t)N, ctx->path_steps, cnt);
+	scan_exclusive_u32(cnt, ioff, nval, tmp, tmp_bytes, s);
+	sort_pairs_u32(ctx->path_steps, skey, iota, occ, N, bits_for(2 * (uint64_t)V), tmp, tmp_bytes, s);
 	v.ioff = ioff;
 	v.occ = occ;
-	const InvView A = view_of(ctx, in, v);
-	// ---- run heads: count, scan, check, emit
-	const uint32_t long_min = in.force_tier2 ? 0 : LONG_LIST;
-	KLAUNCH(k_inv_heads<false>, dim3(cblk(NR)), dim3(C_TPB), 0, s, A, long_min, hcnt, hoff, (uint32_t *)nullptr, (uint32_t *)nullptr, longs, words);
-	uint32_t n_longs = 0;
-	HIP_CHECK(copy_async(&n_longs, words, 4, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(hipStreamSynchronize(s));
-	if (n_longs)
-		KLAUNCH(k_inv_heads_wave<false>, dim3(wblk(n_longs)), dim3(C_TPB), 0, s, A, longs, n_longs, hcnt, hoff, (uint32_t *)nullptr,
+	x.long_min = in.force_tier2 ? 0 : LONG_LIST;
+	return x;
+}
+
+// count, scan, check, emit
+static InvHeads run_heads(povu_hip_ctx *ctx, const InvView &A, InvIndex &x, InvDevice &v)
+{
+	hipStream_t s = ctx->stream;
+	const uint64_t NR = A.NR;
+	InvHeads h;
+	KLAUNCH(k_inv_heads<false>, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, A, x.long_min, x.hcnt, x.hoff, (uint32_t *)nullptr, (uint32_t *)nullptr, x.longs,
+		x.words);
+	x.n_longs = read_back(x.words, s);
+	if (x.n_longs)
+		KLAUNCH(k_inv_heads_wave<false>, dim3(wave_blocks(x.n_longs)), dim3(Q_TPB), 0, s, A, x.longs, x.n_longs, x.hcnt, x.hoff, (uint32_t *)nullptr,
 			(uint32_t *)nullptr);
-	scan64(hcnt, hoff, NR + 1, s64, s);
-	uint64_t H64 = 0;
-	HIP_CHECK(copy_async(&H64, hoff + NR, 8, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(hipStreamSynchronize(s));
-	if (H64 >= 0xFFFFFFFFull)
-		throw HipError("the call needs " + std::to_string(H64) + " inversion run heads: 2^32 or more are refused");
-	const uint32_t H = (uint32_t)H64;
+	scan_exclusive_u64(x.hcnt, x.hoff, NR + 1, x.s64, s);
+	const uint64_t H64 = read_back(x.hoff + NR, s);
+	refuse_2_32(H64, "the call needs ", "inversion run heads");
+	const uint32_t H = h.H = (uint32_t)H64;
 	v.n_heads = H;
 	if (!H)
-		return v;
+		return h;
 	const size_t h1 = (size_t)H + 1;
-	const size_t sort_h = sort_tmp_bytes(h1) + 256, comp_h = compact_tmp_bytes(h1) + 256, scan_h = scan_tmp_bytes(h1) + 256;
-	uint32_t *hx, *hy, *hL, *hslot, *t2, *rlist, *perm2, *key, *key2, *first, *rank;
-	uint8_t *flag;
-	void *sort_tmp_h, *comp_tmp, *scan_tmp_h;
+	h.tmp_bytes = prim_tmp_bytes(h1, true) + 256;
 	carve(ctx->iv_heads, [&](Spans &take) {
-		take(h1, hx, hy, hL, hslot, t2, rlist, perm2, key, key2, first, rank, flag);
+		take(h1, h.hx, h.hy, h.hL, h.hslot, h.t2, h.rlist, h.perm2, h.key, h.key2, h.first, h.rank, h.flag);
 		take(h1, v.run_rec, v.run_slot, v.ref, v.at, v.steps, v.dst, v.pos);
-		take(sort_h, sort_tmp_h);
-		take(comp_h, comp_tmp);
-		take(scan_h, scan_tmp_h);
+		take(h.tmp_bytes, h.tmp);
 	});
-	KLAUNCH(k_inv_heads<true>, dim3(cblk(NR)), dim3(C_TPB), 0, s, A, long_min, hcnt, hoff, hx, hy, longs, words);
-	if (n_longs)
-		KLAUNCH(k_inv_heads_wave<true>, dim3(wblk(n_longs)), dim3(C_TPB), 0, s, A, longs, n_longs, hcnt, hoff, hx, hy);
-	// ---- extension
-	KLAUNCH(k_inv_extend, dim3(cblk(H)), dim3(C_TPB), 0, s, H, A, in.max_steps, in.force_tier2 ? 1u : 0u, hx, hy, hL, hslot, in.slot_of_path, t2,
-		words + 1);
-	uint32_t n_t2 = 0;
-	HIP_CHECK(copy_async(&n_t2, words + 1, 4, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(hipStreamSynchronize(s));
+	KLAUNCH(k_inv_heads<true>, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, A, x.long_min, x.hcnt, x.hoff, h.hx, h.hy, x.longs, x.words);
+	if (x.n_longs)
+		KLAUNCH(k_inv_heads_wave<true>, dim3(wave_blocks(x.n_longs)), dim3(Q_TPB), 0, s, A, x.longs, x.n_longs, x.hcnt, x.hoff, h.hx, h.hy);
+	return h;
+}
+
+static void extend(povu_hip_ctx *ctx, const InvIn &in, const InvView &A, const InvIndex &x, const InvHeads &h, InvDevice &v)
+{
+	hipStream_t s = ctx->stream;
+	KLAUNCH(k_inv_extend, dim3(stride_blocks(h.H)), dim3(Q_TPB), 0, s, h.H, A, in.max_steps, in.force_tier2 ? 1u : 0u, h.hx, h.hy, h.hL, h.hslot,
+		in.slot_of_path, h.t2, x.words + 1);
+	const uint32_t n_t2 = read_back(x.words + 1, s);
 	v.n_tier2 = n_t2;
 	if (n_t2)
-		KLAUNCH(k_inv_extend_wave, dim3(wblk(n_t2)), dim3(C_TPB), 0, s, t2, n_t2, words + 2, A, in.max_steps, hx, hy, hL);
-	// ---- reported runs, sorted by (reference index, steps, slot)
-	KLAUNCH(k_inv_report, dim3(cblk(H)), dim3(C_TPB), 0, s, H, in.max_steps, hx, hL, in.roff, flag, n_long);
-	compact_flagged_u8(flag, H, rlist, words + 3, comp_tmp, comp_h, s);
+		KLAUNCH(k_inv_extend_wave, dim3(wave_blocks(n_t2)), dim3(Q_TPB), 0, s, h.t2, n_t2, x.words + 2, A, in.max_steps, h.hx, h.hy, h.hL);
+}
+
+// the reported runs, sorted by (reference index, steps, slot); the first run of every (index, steps) group is a record
+static void records(povu_hip_ctx *ctx, const InvIn &in, const InvView &A, const InvIndex &x, const InvHeads &h, InvDevice &v)
+{
+	hipStream_t s = ctx->stream;
+	const uint32_t H = h.H;
+	KLAUNCH(k_inv_report, dim3(stride_blocks(H)), dim3(Q_TPB), 0, s, H, in.max_steps, h.hx, h.hL, in.roff, h.flag, x.n_long);
+	compact_flagged_u8(h.flag, H, h.rlist, x.words + 3, h.tmp, h.tmp_bytes, s);
 	uint32_t n_runs = 0;
 	unsigned long long h_long = 0;
-	HIP_CHECK(copy_async(&n_runs, words + 3, 4, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(copy_async(&h_long, n_long, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(&n_runs, x.words + 3, 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(&h_long, x.n_long, 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
 	v.n_long = h_long;
 	v.n_runs = n_runs;
 	if (!n_runs)
-		return v;
-	uint32_t *cur = rlist, *nxt = perm2;
-	auto pass = [&](int which, unsigned bits) {
-		KLAUNCH(k_inv_key, dim3(cblk(n_runs)), dim3(C_TPB), 0, s, n_runs, which, cur, hx, hL, hslot, key);
-		sort_pairs_u32(key, key2, cur, nxt, n_runs, bits, sort_tmp_h, sort_h, s);
-		std::swap(cur, nxt);
+		return;
+	LsdSort sort{h.rlist, h.perm2, h.key, h.key2, n_runs, h.tmp, h.tmp_bytes, s};
+	auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
+		KLAUNCH(k_inv_key, dim3(stride_blocks(n_runs)), dim3(Q_TPB), 0, s, n_runs, which, perm, h.hx, h.hL, h.hslot, k);
 	};
 	if (in.S > 1)
-		pass(0, bits_for(in.S - 1));
-	pass(1, bits_for(in.max_steps));
-	pass(2, bits_for(NR));
-	KLAUNCH(k_inv_group, dim3(cblk(h1)), dim3(C_TPB), 0, s, n_runs, cur, hx, hL, first);
-	scan_exclusive_u32(first, rank, (size_t)n_runs + 1, scan_tmp_h, scan_h, s);
-	HIP_CHECK(copy_async(&v.n, rank + n_runs, 4, hipMemcpyDeviceToHost, s));
-	KLAUNCH(k_inv_records, dim3(cblk(n_runs)), dim3(C_TPB), 0, s, n_runs, A, cur, hx, hL, hslot, first, rank, in.roff, v.run_rec, v.run_slot, v.ref,
-		v.at, v.steps, v.pos);
+		sort.pass(0, bits_for(in.S - 1), write_key);
+	sort.pass(1, bits_for(in.max_steps), write_key);
+	sort.pass(2, bits_for(A.NR), write_key);
+	const uint32_t *cur = sort.cur;
+	KLAUNCH(k_inv_group, dim3(stride_blocks((size_t)H + 1)), dim3(Q_TPB), 0, s, n_runs, cur, h.hx, h.hL, h.first);
+	scan_exclusive_u32(h.first, h.rank, (size_t)n_runs + 1, h.tmp, h.tmp_bytes, s);
+	HIP_CHECK(copy_async(&v.n, h.rank + n_runs, 4, hipMemcpyDeviceToHost, s));
+	KLAUNCH(k_inv_records, dim3(stride_blocks(n_runs)), dim3(Q_TPB), 0, s, n_runs, A, cur, h.hx, h.hL, h.hslot, h.first, h.rank, in.roff, v.run_rec,
+		v.run_slot, v.ref, v.at, v.steps, v.pos);
 	HIP_CHECK(hipStreamSynchronize(s));
+}
+
+InvDevice inv_find(povu_hip_ctx *ctx, const InvIn &in)
+{
+	const uint64_t N = ctx->n_path_steps;
+	if (N >= 0xFFFFFFFFull - 4096) // (the sort of the step index takes fewer)
+		throw HipError("inversion calls index every path step: " + std::to_string(N) + " steps, 2^32 or more are refused");
+	InvDevice v;
+	if (!N || !in.NR)
+		return v;
+	InvIndex x = step_index(ctx, in, v);
+	const InvView A = view_of(ctx, in, v);
+	const InvHeads h = run_heads(ctx, A, x, v);
+	if (!h.H)
+		return v;
+	extend(ctx, in, A, x, h, v);
+	records(ctx, in, A, x, h, v);
 	return v;
 }
 
@@ -504,15 +533,15 @@ void inv_merge(povu_hip_ctx *ctx, InvDevice &v, uint32_t nrec, const uint32_t *f
 {
 	hipStream_t s = ctx->stream;
 	if (nrec)
-		KLAUNCH(k_inv_rows_flubble, dim3(cblk(nrec)), dim3(C_TPB), 0, s, nrec, f_ref, f_pos, v.n, v.ref, v.pos, f_dst);
+		KLAUNCH(k_inv_rows_flubble, dim3(stride_blocks(nrec)), dim3(Q_TPB), 0, s, nrec, f_ref, f_pos, v.n, v.ref, v.pos, f_dst);
 	if (v.n)
-		KLAUNCH(k_inv_rows, dim3(cblk(v.n)), dim3(C_TPB), 0, s, v.n, v.ref, v.pos, nrec, f_ref, f_pos, v.dst);
+		KLAUNCH(k_inv_rows, dim3(stride_blocks(v.n)), dim3(Q_TPB), 0, s, v.n, v.ref, v.pos, nrec, f_ref, f_pos, v.dst);
 }
 
 void inv_fields(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o)
 {
 	if (v.n)
-		KLAUNCH(k_inv_fields, dim3(cblk(v.n)), dim3(C_TPB), 0, ctx->stream, v.n, view_of(ctx, in, v), v.ref, v.at, v.steps, v.pos, v.dst, o);
+		KLAUNCH(k_inv_fields, dim3(stride_blocks(v.n)), dim3(Q_TPB), 0, ctx->stream, v.n, view_of(ctx, in, v), v.ref, v.at, v.steps, v.pos, v.dst, o);
 }
 
 void inv_genotypes(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o, uint32_t nb, uint64_t *bcnt)
@@ -521,29 +550,29 @@ void inv_genotypes(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const
 		return;
 	hipStream_t s = ctx->stream;
 	const InvView A = view_of(ctx, in, v);
-	KLAUNCH(k_inv_gt_init, dim3(cblk((size_t)v.n * in.S)), dim3(C_TPB), 0, s, (uint64_t)v.n * in.S, in.S, nb, A, v.ref, v.dst, in.slot_of_path, o.gt,
+	KLAUNCH(k_inv_gt_init, dim3(stride_blocks((size_t)v.n * in.S)), dim3(Q_TPB), 0, s, (uint64_t)v.n * in.S, in.S, nb, A, v.ref, v.dst, in.slot_of_path, o.gt,
 		o.o_block, bcnt);
-	KLAUNCH(k_inv_gt_mark, dim3(cblk(v.n_runs)), dim3(C_TPB), 0, s, v.n_runs, in.S, A, v.run_rec, v.run_slot, v.ref, v.dst, in.slot_of_path, o.gt);
+	KLAUNCH(k_inv_gt_mark, dim3(stride_blocks(v.n_runs)), dim3(Q_TPB), 0, s, v.n_runs, in.S, A, v.run_rec, v.run_slot, v.ref, v.dst, in.slot_of_path, o.gt);
 }
 
 void inv_counts(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o, const uint64_t *ac_off, uint32_t *ac)
 {
 	if (v.n)
-		KLAUNCH(k_inv_gt_count, dim3(wblk(v.n)), dim3(C_TPB), 0, ctx->stream, v.n, in.S, in.NS, in.slot_first, v.dst, o.gt, ac_off, ac, o.o_an,
+		KLAUNCH(k_inv_gt_count, dim3(wave_blocks(v.n)), dim3(Q_TPB), 0, ctx->stream, v.n, in.S, in.NS, in.slot_first, v.dst, o.gt, ac_off, ac, o.o_an,
 			o.o_ns, o.o_flags);
 }
 
 void inv_spell_len(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, uint64_t *slen, uint64_t *alen)
 {
 	if (v.n)
-		KLAUNCH(k_inv_spell_len, dim3(wblk(v.n)), dim3(C_TPB), 0, ctx->stream, v.n, view_of(ctx, in, v), v.at, v.steps, in.roff, ctx->g.vid, slen, alen);
+		KLAUNCH(k_inv_spell_len, dim3(wave_blocks(v.n)), dim3(Q_TPB), 0, ctx->stream, v.n, view_of(ctx, in, v), v.at, v.steps, in.roff, ctx->g.vid, slen, alen);
 }
 
 void inv_emit(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const uint64_t *s_off, const uint64_t *a_off, char *o_seq, char *o_at,
 	      unsigned long long *bad)
 {
 	if (v.n)
-		KLAUNCH(k_inv_emit, dim3(wblk(2 * (size_t)v.n)), dim3(C_TPB), 0, ctx->stream, 2 * (uint64_t)v.n, view_of(ctx, in, v), v.at, v.steps,
+		KLAUNCH(k_inv_emit, dim3(wave_blocks(2 * (size_t)v.n)), dim3(Q_TPB), 0, ctx->stream, 2 * (uint64_t)v.n, view_of(ctx, in, v), v.at, v.steps,
 			ctx->seq_off, ctx->seq, ctx->g.vid, s_off, a_off, o_seq, o_at, bad);
 }
 

@@ -1662,6 +1662,18 @@ extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in
 		HIP_CHECK(hipSetDevice(ctx->device));
 		hipStream_t s = ctx->stream;
 		Arena ar;
+		if (op == 2) { // n u64 values, each a pair of words
+			uint64_t *di, *dout, *tmp;
+			carve(ar, [&](Spans &take) {
+				take(n + 1, di, dout);
+				take(scan_exclusive_u64_tmp(n), tmp);
+			});
+			HIP_CHECK(copy_async(di, in, n * 8, hipMemcpyHostToDevice, s));
+			scan_exclusive_u64(di, dout, n, tmp, s);
+			HIP_CHECK(copy_async(out, dout, n * 8, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipStreamSynchronize(s));
+			return 0;
+		}
 		const size_t tb = scan_tmp_bytes(std::max(n, n2));
 		ar.reserve(2 * Arena::padded(n + 16, 4) + 2 * Arena::padded(n2 + 16, 4) + tb + 4096);
 		uint32_t *di = ar.take<uint32_t>(n + 16), *dout = ar.take<uint32_t>(n + 16);

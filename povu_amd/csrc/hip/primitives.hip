@@ -542,6 +542,62 @@ void totals_u32(const uint32_t *a, const uint32_t *b, uint64_t n, unsigned long 
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// ---- exclusive u64 scan: per block of S64_N an LDS scan, the block sums scanned recursively, then added
+static constexpr int S64_E = 4, S64_N = SC_TPB * S64_E; // elements per thread / per block
+__global__ __launch_bounds__(SC_TPB) void k_u64_scan(const uint64_t *in, uint64_t *out, size_t n, uint64_t *__restrict__ sums)
+{
+	__shared__ uint64_t sh[SC_TPB];
+	const size_t base = (size_t)blockIdx.x * S64_N + (size_t)threadIdx.x * S64_E;
+	uint64_t v[S64_E], t = 0;
+	for (int k = 0; k < S64_E; k++) {
+		v[k] = base + k < n ? in[base + k] : 0;
+		t += v[k];
+	}
+	sh[threadIdx.x] = t;
+	__syncthreads();
+	for (int d = 1; d < SC_TPB; d <<= 1) {
+		const uint64_t x = (int)threadIdx.x >= d ? sh[threadIdx.x - d] : 0;
+		__syncthreads();
+		sh[threadIdx.x] += x;
+		__syncthreads();
+	}
+	uint64_t run = sh[threadIdx.x] - t;
+	for (int k = 0; k < S64_E; k++) {
+		if (base + k < n)
+			out[base + k] = run;
+		run += v[k];
+	}
+	if (threadIdx.x == SC_TPB - 1)
+		sums[blockIdx.x] = sh[SC_TPB - 1];
+}
+__global__ __launch_bounds__(SC_TPB) void k_u64_add(uint64_t *out, size_t n, const uint64_t *__restrict__ offs)
+{
+	const size_t base = (size_t)blockIdx.x * S64_N;
+	const uint64_t o = offs[blockIdx.x];
+	for (size_t i = base + threadIdx.x; i < n && i < base + S64_N; i += SC_TPB)
+		out[i] += o;
+}
+size_t scan_exclusive_u64_tmp(size_t n)
+{
+	size_t t = 2;
+	while (n > 1) {
+		n = (n + S64_N - 1) / S64_N;
+		t += n + 1;
+	}
+	return t;
+}
+void scan_exclusive_u64(const uint64_t *in, uint64_t *out, size_t n, uint64_t *tmp, hipStream_t s)
+{
+	if (!n)
+		return;
+	const size_t nb = (n + S64_N - 1) / S64_N;
+	KLAUNCH(k_u64_scan, dim3((unsigned)nb), dim3(SC_TPB), 0, s, in, out, n, tmp);
+	if (nb > 1) {
+		scan_exclusive_u64(tmp, tmp, nb, tmp + nb + 1, s);
+		KLAUNCH(k_u64_add, dim3((unsigned)nb), dim3(SC_TPB), 0, s, out, n, tmp);
+	}
+}
+
 // ---- exclusive running xor of 128-bit words (the bridge test's two hashes): same two-launch scheme, 2 words per lane
 static constexpr int X128_ITEMS = 2, X128_TILE = SC_TPB * X128_ITEMS;
 struct Xor128Job {
@@ -979,6 +1035,11 @@ size_t sort_tmp_bytes(size_t n)
 {
 	// ping-pong buffer for keys and values + the [digit][tile] table (scanned in place) + the scan's own scratch
 	return 2 * ((n * 4 + 255) & ~size_t(255)) + ((rs_table_words(n) * 4 + 255) & ~size_t(255)) + scan_tmp_bytes(rs_table_words(n)) + 1024;
+}
+
+size_t prim_tmp_bytes(size_t n, bool with_sort)
+{
+	return std::max({scan_tmp_bytes(n), compact_tmp_bytes(n), with_sort ? sort_tmp_bytes(n) : size_t(0)});
 }
 
 void sort_pairs_u32(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits,

@@ -1,13 +1,9 @@
-// query_common.hip -- the front end the walks (walk_kernels.hip) and the traversals (trav_kernels.hip) share: the queries of
-// a forest, their upload and the two checks that resolve them to entered sides (query_common.hpp).
+// query_common.hip -- the front end the query pipelines share: the queries of a forest, their upload and the two checks that
+// resolve them to entered sides; the iota and the 2^32 refusal (query_common.hpp).
 #include "query_common.hpp"
 
 namespace povu_hip
 {
-
-static constexpr int Q_TPB = 256;
-
-static inline unsigned qblk(size_t n) { return (unsigned)((n + Q_TPB - 1) / Q_TPB); }
 
 // segment ids must ascend with the vertex index (binary search; successor order = side order)
 __global__ void k_wk_vid_ascending(uint32_t V, const uint32_t *__restrict__ vid, uint32_t *__restrict__ bad)
@@ -36,9 +32,26 @@ __global__ void k_wk_resolve(uint32_t n, const uint32_t *__restrict__ qa, const 
 	yz[q] = a == z ? NO_QUERY : 2 * z + ((o >> 1) & 1u);
 }
 
+__global__ void k_q_iota(uint32_t n, uint32_t *__restrict__ a)
+{
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < n; i += gridDim.x * Q_TPB)
+		a[i] = i;
+}
+
+void launch_iota(uint32_t n, uint32_t *a, hipStream_t s)
+{
+	KLAUNCH(k_q_iota, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, a);
+}
+
+void refuse_2_32(uint64_t v, const char *who, const char *what, const char *why)
+{
+	if (v >= 0xFFFFFFFFull)
+		throw HipError(std::string(who) + std::to_string(v) + " " + what + ": 2^32 or more are refused" + why);
+}
+
 void launch_vid_ascending(uint32_t V, const uint32_t *vid, uint32_t *bad, hipStream_t s)
 {
-	KLAUNCH(k_wk_vid_ascending, dim3(qblk(V)), dim3(Q_TPB), 0, s, V, vid, bad);
+	KLAUNCH(k_wk_vid_ascending, dim3(lane_blocks(V)), dim3(Q_TPB), 0, s, V, vid, bad);
 }
 
 void check_query_forest(const povu_hip_ctx *ctx, const povu_hip_forest *f, const char *what)
@@ -123,7 +136,7 @@ QueryFront query_front(povu_hip_ctx *ctx, std::vector<uint32_t> qa, std::vector<
 	}
 	launch_vid_ascending(g.V, g.vid, q.words, s);
 	if (q.n)
-		KLAUNCH(k_wk_resolve, dim3(qblk(q.n)), dim3(Q_TPB), 0, s, q.n, d_qa, d_qz, d_qor, g.vid, g.V, ys, yz, q.words);
+		KLAUNCH(k_wk_resolve, dim3(lane_blocks(q.n)), dim3(Q_TPB), 0, s, q.n, d_qa, d_qz, d_qor, g.vid, g.V, ys, yz, q.words);
 	return q;
 }
 

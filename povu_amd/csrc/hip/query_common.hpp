@@ -1,7 +1,10 @@
-// query_common.hpp -- what the walks (walk_kernels.hip) and the traversals (trav_kernels.hip) share: the queries of a forest
-// (every PVST vertex but the roots, tree order then vertex order), the refusals of forests they cannot read, the resolution
-// of a query's boundary steps to entered sides on the device (segment ids must ascend with the vertex index), and the C ABI
-// side of a call: its timing, its errors and the hand-off of its results to the host.  Defined in query_common.hip.
+// query_common.hpp -- what the four query pipelines share (walks: walk_kernels.hip, traversals: trav_kernels.hip, flubble
+// calls: call_kernels.hip, inversion calls: inv_kernels.hip).  Device side: the launch shapes, the step of a traversal, the
+// binary searches, the wave reductions.  Host side: the queries of a forest (every PVST vertex but the roots, tree order then
+// vertex order), the refusals of forests they cannot read, the resolution of a query's boundary steps to entered sides on the
+// device (segment ids must ascend with the vertex index), the steps every pipeline repeats (a one-word read-back, counts to
+// offsets with the 2^32 refusal, a sort by several keys), and the C ABI side of a call: its timing, its errors and the
+// hand-off of its results to the host.  Defined in query_common.hip.
 #pragma once
 #include "context.hpp"
 
@@ -11,6 +14,55 @@ namespace povu_hip
 {
 
 static constexpr uint32_t NO_QUERY = 0xFFFFFFFFu;
+static constexpr int Q_TPB = 256;		 // lanes of a workgroup, every kernel of the four pipelines
+static constexpr uint64_t ROLE_BIT = 1ull << 63; // role of a task, kept in the top bit of its position: reverse traversals carry it in rpos
+
+// ---- launch shapes: workgroups of Q_TPB lanes with a lane per item, the same capped for kernels that stride over their
+// grid, and workgroups with a wave per item (such kernels stride)
+static inline unsigned lane_blocks(size_t n) { return (unsigned)std::max<size_t>(1, (n + Q_TPB - 1) / Q_TPB); }
+static inline unsigned stride_blocks(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + Q_TPB - 1) / Q_TPB, 65536)); }
+static inline unsigned wave_blocks(size_t n) { return (unsigned)std::max<size_t>(1, std::min<size_t>((n + Q_TPB / 64 - 1) / (Q_TPB / 64), 65536)); }
+
+// step k (S -> Z) of the traversal that occupies path words [pos, pos + len), read backwards and flipped when reverse
+__device__ __forceinline__ uint32_t trav_step(const uint32_t *__restrict__ steps, uint64_t pos, uint32_t len, bool rev, uint32_t k)
+{
+	return rev ? steps[pos + len - 1 - k] ^ 1u : steps[pos + k];
+}
+
+// the span x lies in: the last k with off[k] <= x, off ascending over [0, n) (the path of a global step, the reference of a
+// reference step, the block of a spelled allele)
+__device__ __forceinline__ uint32_t span_of(const uint64_t *__restrict__ off, uint32_t n, uint64_t x)
+{
+	uint32_t lo = 0, hi = n;
+	while (hi - lo > 1) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (off[mid] <= x)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+
+// sum over the wave, in every lane
+template <class T>
+__device__ __forceinline__ T wave_sum(T v)
+{
+	for (int o = 32; o > 0; o >>= 1)
+		v += __shfl_xor(v, o, 64);
+	return v;
+}
+// inclusive prefix sum over the wave: lane l gets the sum of lanes 0 .. l
+__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	for (int o = 1; o < 64; o <<= 1) {
+		const uint32_t y = __shfl_up(v, o, 64);
+		if (lane >= o)
+			v += y;
+	}
+	return v;
+}
 
 // vertex index of segment `id` in the ascending `vid`, NO_QUERY when the graph has no such segment
 __device__ __forceinline__ uint32_t find_vertex(const uint32_t *__restrict__ vid, uint32_t V, uint32_t id)
@@ -31,6 +83,59 @@ __device__ __forceinline__ uint32_t find_vertex(const uint32_t *__restrict__ vid
 void check_query_forest(const povu_hip_ctx *ctx, const povu_hip_forest *f, const char *what);
 // bit 0 of *bad when vid does not ascend
 void launch_vid_ascending(uint32_t V, const uint32_t *vid, uint32_t *bad, hipStream_t s);
+// a[i] = i, i < n
+void launch_iota(uint32_t n, uint32_t *a, hipStream_t s);
+
+// one value of device memory, through the stream and waited for
+template <class T>
+T read_back(const T *dev, hipStream_t s)
+{
+	T h{};
+	HIP_CHECK(copy_async(&h, dev, sizeof(T), hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	return h;
+}
+
+// throws "<who><v> <what>: 2^32 or more are refused<why>" when v does not fit the 32-bit indices, scans and sorts
+void refuse_2_32(uint64_t v, const char *who, const char *what, const char *why = "");
+
+// Counts to offsets: the 64-bit totals of cnt[0 .. n) (and cnt2, optional, of the same length) go to `refuse`, which throws
+// in the caller's words when they do not fit; then element n is cleared and off[0 .. n] (off2) are the exclusive sums.
+// tot: two words of device memory.  Waits for the stream (totals_u32).
+template <class Refuse>
+void counts_to_offsets(uint32_t *cnt, uint32_t *off, uint32_t *cnt2, uint32_t *off2, size_t n, unsigned long long *tot, void *tmp,
+		       size_t tmp_bytes, hipStream_t s, Refuse &&refuse)
+{
+	uint64_t total[2] = {0, 0};
+	totals_u32(cnt, cnt2, n, tot, total, s);
+	refuse(total);
+	HIP_CHECK(hipMemsetAsync(cnt + n, 0, 4, s));
+	if (!cnt2) {
+		scan_exclusive_u32(cnt, off, n + 1, tmp, tmp_bytes, s);
+		return;
+	}
+	HIP_CHECK(hipMemsetAsync(cnt2 + n, 0, 4, s));
+	scan_exclusive_u32_pair(cnt, off, n + 1, cnt2, off2, n + 1, tmp, tmp_bytes, s);
+}
+
+// A stable sort of an index list by several keys, least significant first: per key a pass -- `write_key(which, perm, key)`
+// launches the caller's kernel that writes key `which` of entry perm[k] to key[k], then one radix sort of `bits` bits moves
+// the list to its other buffer.  `cur` holds the list, before the first pass and after the last.
+struct LsdSort {
+	uint32_t *cur, *nxt; // the index list and its ping-pong buffer
+	uint32_t *key, *kout;
+	size_t n;
+	void *tmp; // sort_tmp_bytes(n)
+	size_t tmp_bytes;
+	hipStream_t s;
+	template <class WriteKey>
+	void pass(int which, unsigned bits, WriteKey &&write_key)
+	{
+		write_key(which, static_cast<const uint32_t *>(cur), key);
+		sort_pairs_u32(key, kout, cur, nxt, n, bits, tmp, tmp_bytes, s);
+		std::swap(cur, nxt);
+	}
+};
 
 // HIP-event time of a call's device work, from start() to stop(); the events go with the scope on every exit
 class CallTimer

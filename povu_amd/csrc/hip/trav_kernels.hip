@@ -27,15 +27,10 @@
 namespace povu_hip
 {
 
-static constexpr int T_TPB = 256;
 static constexpr uint32_t T_PER_LANE = 16;		 // steps per lane of the start-task passes
-static constexpr uint32_t T_TILE = T_TPB * T_PER_LANE; // steps per workgroup of the start-task passes
+static constexpr uint32_t T_TILE = Q_TPB * T_PER_LANE; // steps per workgroup of the start-task passes
 static constexpr uint32_t T1_STEPS = 64;		 // steps tier 1 looks at before it hands a scan over
-static constexpr uint64_t ROLE_BIT = 1ull << 63;	 // role of a task, kept in the top bit of its position
 static constexpr uint8_t TS_LONG = POVU_HIP_TRAV_LONG, TS_STRAY = POVU_HIP_TRAV_STRAY, TS_OPEN = POVU_HIP_TRAV_OPEN;
-
-static inline unsigned tblk(size_t n) { return (unsigned)((n + T_TPB - 1) / T_TPB); }
-static inline unsigned tgrid(size_t n) { return (unsigned)std::min<size_t>(tblk(n), 65536); } // (grid-stride kernels)
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) // splitmix64's finaliser
 {
@@ -48,32 +43,12 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) // splitmix64's finaliser
 }
 __device__ __forceinline__ uint64_t step_hash(uint32_t k, uint32_t side) { return mix64(((uint64_t)k << 32) | side); }
 
-// step k (S -> Z) of the traversal that occupies path words [pos, pos + len), read backwards and flipped when reverse
-__device__ __forceinline__ uint32_t trav_step(const uint32_t *__restrict__ steps, uint64_t pos, uint32_t len, bool rev, uint32_t k)
-{
-	return rev ? steps[pos + len - 1 - k] ^ 1u : steps[pos + k];
-}
-
-// path of global step `x`: the last k with off[k] <= x
-__device__ __forceinline__ uint32_t path_of(const uint64_t *__restrict__ off, uint32_t n_paths, uint64_t x)
-{
-	uint32_t lo = 0, hi = n_paths;
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (off[mid] <= x)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
 // ---- paths: segment ids -> step words (the ids were copied into `steps`, mapped in place); the lowest step whose id the
 // graph does not have is kept in *bad
 __global__ void k_tr_map_steps(uint64_t N, uint32_t *__restrict__ steps, const uint8_t *__restrict__ rev,
 			       const uint32_t *__restrict__ vid, uint32_t V, unsigned long long *__restrict__ bad)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * T_TPB + threadIdx.x; i < N; i += (uint64_t)gridDim.x * T_TPB) {
+	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < N; i += (uint64_t)gridDim.x * Q_TPB) {
 		const uint32_t v = find_vertex(vid, V, steps[i]);
 		if (v == NO_QUERY) {
 			atomicMin(bad, (unsigned long long)i);
@@ -88,7 +63,7 @@ __global__ void k_tr_map_steps(uint64_t N, uint32_t *__restrict__ steps, const u
 __global__ void k_tr_keys(uint32_t n, uint32_t nS, const uint32_t *__restrict__ ys, const uint32_t *__restrict__ yz,
 			  uint32_t *__restrict__ key, uint32_t *__restrict__ val, uint32_t *__restrict__ cnt)
 {
-	const uint32_t q = blockIdx.x * T_TPB + threadIdx.x;
+	const uint32_t q = blockIdx.x * Q_TPB + threadIdx.x;
 	if (q >= n)
 		return;
 	const bool none = ys[q] == NO_QUERY;
@@ -103,22 +78,17 @@ __global__ void k_tr_keys(uint32_t n, uint32_t nS, const uint32_t *__restrict__ 
 	}
 }
 
-// ---- start tasks.  Lane t of a workgroup looks at steps base + k T_TPB + t, k < T_PER_LANE (coalesced); the emit pass
+// ---- start tasks.  Lane t of a workgroup looks at steps base + k Q_TPB + t, k < T_PER_LANE (coalesced); the emit pass
 // ranks them in step order with a workgroup scan per k.
-__device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t v, uint32_t &total, uint32_t *lds /* [T_TPB / 64 + 1] */)
+__device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t v, uint32_t &total, uint32_t *lds /* [Q_TPB / 64 + 1] */)
 {
 	const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-	uint32_t x = v;
-	for (int o = 1; o < 64; o <<= 1) {
-		const uint32_t y = __shfl_up(x, o);
-		if ((int)lane >= o)
-			x += y;
-	}
+	const uint32_t x = wave_inclusive_sum(v);
 	if (lane == 63)
 		lds[wv] = x;
 	__syncthreads();
 	uint32_t before = 0, all = 0;
-	for (uint32_t w = 0; w < T_TPB / 64; w++) {
+	for (uint32_t w = 0; w < Q_TPB / 64; w++) {
 		const uint32_t c = lds[w];
 		before += w < wv ? c : 0;
 		all += c;
@@ -128,14 +98,14 @@ __device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t v, uint32_t &tota
 	return before + x - v;
 }
 
-__global__ __launch_bounds__(T_TPB) void k_tr_count(uint64_t N, const uint32_t *__restrict__ steps, const uint32_t *__restrict__ boff,
+__global__ __launch_bounds__(Q_TPB) void k_tr_count(uint64_t N, const uint32_t *__restrict__ steps, const uint32_t *__restrict__ boff,
 						    uint32_t *__restrict__ tile_cnt)
 {
-	__shared__ uint32_t lds[T_TPB / 64 + 1];
+	__shared__ uint32_t lds[Q_TPB / 64 + 1];
 	const uint64_t base = (uint64_t)blockIdx.x * T_TILE;
 	uint32_t c = 0;
 	for (uint32_t k = 0; k < T_PER_LANE; k++) {
-		const uint64_t i = base + (uint64_t)k * T_TPB + threadIdx.x;
+		const uint64_t i = base + (uint64_t)k * Q_TPB + threadIdx.x;
 		if (i < N) {
 			const uint32_t x = steps[i];
 			c += boff[x + 1] - boff[x];
@@ -147,15 +117,15 @@ __global__ __launch_bounds__(T_TPB) void k_tr_count(uint64_t N, const uint32_t *
 		tile_cnt[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(T_TPB) void k_tr_emit(uint64_t N, const uint32_t *__restrict__ steps, const uint32_t *__restrict__ boff,
+__global__ __launch_bounds__(Q_TPB) void k_tr_emit(uint64_t N, const uint32_t *__restrict__ steps, const uint32_t *__restrict__ boff,
 						   const uint32_t *__restrict__ bval, const uint32_t *__restrict__ tile_off,
 						   uint64_t *__restrict__ tpos, uint32_t *__restrict__ tkey)
 {
-	__shared__ uint32_t lds[T_TPB / 64 + 1];
+	__shared__ uint32_t lds[Q_TPB / 64 + 1];
 	const uint64_t base = (uint64_t)blockIdx.x * T_TILE;
 	uint32_t at = tile_off[blockIdx.x];
 	for (uint32_t k = 0; k < T_PER_LANE; k++) {
-		const uint64_t i = base + (uint64_t)k * T_TPB + threadIdx.x;
+		const uint64_t i = base + (uint64_t)k * Q_TPB + threadIdx.x;
 		uint32_t b = 0, e = 0;
 		if (i < N) {
 			const uint32_t x = steps[i];
@@ -172,16 +142,10 @@ __global__ __launch_bounds__(T_TPB) void k_tr_emit(uint64_t N, const uint32_t *_
 	}
 }
 
-__global__ void k_tr_iota(uint32_t n, uint32_t *__restrict__ a)
-{
-	for (uint32_t i = blockIdx.x * T_TPB + threadIdx.x; i < n; i += gridDim.x * T_TPB)
-		a[i] = i;
-}
-
 // out[k] = in[perm[k]] (u64 / u32)
 __global__ void k_tr_gather64(uint32_t n, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ in, uint64_t *__restrict__ out)
 {
-	for (uint32_t k = blockIdx.x * T_TPB + threadIdx.x; k < n; k += gridDim.x * T_TPB)
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < n; k += gridDim.x * Q_TPB)
 		out[k] = in[perm[k]];
 }
 
@@ -216,7 +180,7 @@ __device__ __forceinline__ TaskView task_view(const ScanArgs &A, uint32_t q, uin
 	t.a = ys >> 1;
 	t.z = yz >> 1;
 	t.close = t.rev ? ys ^ 1u : yz;
-	const uint64_t end = A.path_off[path_of(A.path_off, A.n_paths, t.pos) + 1];
+	const uint64_t end = A.path_off[span_of(A.path_off, A.n_paths, t.pos) + 1];
 	const uint64_t win = t.pos + A.max_steps; // position pos + max_steps existing: LONG
 	t.lim_is_end = end <= win;
 	t.lim = t.lim_is_end ? end : win;
@@ -229,10 +193,10 @@ __device__ __forceinline__ uint64_t keep_bits(const ScanArgs &A, uint64_t h)
 }
 
 // tier 1: one lane per task (sorted order); a scan not decided within T1_STEPS steps is handed over
-__global__ __launch_bounds__(T_TPB) void k_tr_t1(uint32_t T, ScanArgs A, const uint32_t *__restrict__ tq, const uint64_t *__restrict__ tpos,
+__global__ __launch_bounds__(Q_TPB) void k_tr_t1(uint32_t T, ScanArgs A, const uint32_t *__restrict__ tq, const uint64_t *__restrict__ tpos,
 						 uint32_t force2, ScanOut O, uint8_t *__restrict__ handover)
 {
-	const uint32_t k = blockIdx.x * T_TPB + threadIdx.x;
+	const uint32_t k = blockIdx.x * Q_TPB + threadIdx.x;
 	if (k >= T)
 		return;
 	O.len[k] = 0;
@@ -273,16 +237,9 @@ __global__ __launch_bounds__(T_TPB) void k_tr_t1(uint32_t T, ScanArgs A, const u
 	O.hash[k] = keep_bits(A, h);
 }
 
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t x)
-{
-	for (int o = 32; o > 0; o >>= 1)
-		x += __shfl_xor(x, o);
-	return x;
-}
-
 // tier 2: one wave per task of `list`, every wave taking its next task from *next (zeroed before the launch); 64 steps a
 // ballot to find the end, then 64 steps a pass to hash the sequence
-__global__ __launch_bounds__(T_TPB) void k_tr_t2(const uint32_t *__restrict__ list, uint32_t n2, uint32_t *__restrict__ next, ScanArgs A,
+__global__ __launch_bounds__(Q_TPB) void k_tr_t2(const uint32_t *__restrict__ list, uint32_t n2, uint32_t *__restrict__ next, ScanArgs A,
 						 const uint32_t *__restrict__ tq, const uint64_t *__restrict__ tpos, ScanOut O)
 {
 	const uint32_t lane = threadIdx.x & 63u;
@@ -321,7 +278,7 @@ __global__ __launch_bounds__(T_TPB) void k_tr_t2(const uint32_t *__restrict__ li
 		uint64_t h = 0;
 		for (uint32_t i = lane; i < len; i += 64)
 			h += step_hash(i, trav_step(A.steps, t.pos, len, t.rev, i));
-		h = wave_sum64(h);
+		h = wave_sum(h);
 		if (lane == 0) {
 			O.len[k] = len;
 			O.hash[k] = keep_bits(A, h);
@@ -331,7 +288,7 @@ __global__ __launch_bounds__(T_TPB) void k_tr_t2(const uint32_t *__restrict__ li
 
 __global__ void k_tr_closed(uint32_t T, const uint32_t *__restrict__ len, uint8_t *__restrict__ closed)
 {
-	for (uint32_t k = blockIdx.x * T_TPB + threadIdx.x; k < T; k += gridDim.x * T_TPB)
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < T; k += gridDim.x * Q_TPB)
 		closed[k] = len[k] != 0;
 }
 
@@ -341,7 +298,7 @@ __global__ void k_tr_trav_fields(uint32_t R, const uint32_t *__restrict__ list, 
 				 uint32_t *__restrict__ rq, uint64_t *__restrict__ rpos, uint32_t *__restrict__ rlen,
 				 uint64_t *__restrict__ rhash)
 {
-	for (uint32_t t = blockIdx.x * T_TPB + threadIdx.x; t < R; t += gridDim.x * T_TPB) {
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < R; t += gridDim.x * Q_TPB) {
 		const uint32_t k = list[t];
 		rq[t] = tq[k];
 		rpos[t] = tpos[k];
@@ -353,7 +310,7 @@ __global__ void k_tr_trav_fields(uint32_t R, const uint32_t *__restrict__ list, 
 // trav_off[q] = first traversal of query >= q (the traversals are grouped by query), q in [0, n]
 __global__ void k_tr_query_off(uint32_t n, uint32_t R, const uint32_t *__restrict__ rq, uint32_t *__restrict__ off)
 {
-	const uint32_t q = blockIdx.x * T_TPB + threadIdx.x;
+	const uint32_t q = blockIdx.x * Q_TPB + threadIdx.x;
 	if (q > n)
 		return;
 	uint32_t lo = 0, hi = R;
@@ -371,7 +328,7 @@ __global__ void k_tr_query_off(uint32_t n, uint32_t R, const uint32_t *__restric
 __global__ void k_tr_sort_key(uint32_t R, int which, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ rhash,
 			      const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ rq, uint32_t *__restrict__ key)
 {
-	for (uint32_t k = blockIdx.x * T_TPB + threadIdx.x; k < R; k += gridDim.x * T_TPB) {
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB) {
 		const uint32_t t = perm ? perm[k] : k;
 		key[k] = which == 0 ? (uint32_t)rhash[t] : which == 1 ? (uint32_t)(rhash[t] >> 32) : which == 2 ? rlen[t] : rq[t];
 	}
@@ -381,7 +338,7 @@ __global__ void k_tr_sort_key(uint32_t R, int which, const uint32_t *__restrict_
 __global__ void k_tr_heads(uint32_t R, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ rhash,
 			   const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ rq, uint32_t *__restrict__ mark)
 {
-	for (uint32_t k = blockIdx.x * T_TPB + threadIdx.x; k < R; k += gridDim.x * T_TPB) {
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB) {
 		bool head = k == 0;
 		if (!head) {
 			const uint32_t a = perm[k], b = perm[k - 1];
@@ -408,7 +365,7 @@ __global__ void k_tr_check(uint32_t R, const uint32_t *__restrict__ steps, const
 			   const uint64_t *__restrict__ rpos, const uint32_t *__restrict__ rlen, uint32_t *__restrict__ head,
 			   uint32_t *__restrict__ rep, uint8_t *__restrict__ bad)
 {
-	for (uint32_t k = blockIdx.x * T_TPB + threadIdx.x; k < R; k += gridDim.x * T_TPB) {
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB) {
 		const uint32_t h = max(hmax[k], mark[k]) - 1;
 		head[k] = h;
 		if (h == k) {
@@ -430,7 +387,7 @@ __global__ void k_tr_regroup(uint32_t nb, const uint32_t *__restrict__ bad_heads
 			     const uint32_t *__restrict__ perm, const uint32_t *__restrict__ head, const uint64_t *__restrict__ rpos,
 			     const uint32_t *__restrict__ rlen, uint32_t *__restrict__ rep, unsigned long long *__restrict__ splits)
 {
-	const uint32_t i = blockIdx.x * T_TPB + threadIdx.x;
+	const uint32_t i = blockIdx.x * Q_TPB + threadIdx.x;
 	if (i >= nb)
 		return;
 	const uint32_t h = bad_heads[i];
@@ -454,7 +411,7 @@ __global__ void k_tr_regroup(uint32_t nb, const uint32_t *__restrict__ bad_heads
 // first[t] = 1 when traversal t is the first of its group (its representative)
 __global__ void k_tr_first(uint32_t R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, uint32_t *__restrict__ first)
 {
-	for (uint32_t k = blockIdx.x * T_TPB + threadIdx.x; k < R; k += gridDim.x * T_TPB)
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB)
 		if (rep[k] == k)
 			first[perm[k]] = 1;
 }
@@ -464,7 +421,7 @@ __global__ void k_tr_allele(uint32_t R, const uint32_t *__restrict__ perm, const
 			    const uint32_t *__restrict__ rlen, uint32_t *__restrict__ rallele, uint32_t *__restrict__ afirst,
 			    uint32_t *__restrict__ alen)
 {
-	for (uint32_t k = blockIdx.x * T_TPB + threadIdx.x; k < R; k += gridDim.x * T_TPB) {
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB) {
 		const uint32_t t = perm[k], f = perm[rep[k]], a = aidx[f];
 		rallele[t] = a;
 		if (rep[k] == k) {
@@ -481,9 +438,9 @@ __global__ void k_tr_out(uint32_t R, const uint64_t *__restrict__ path_off, uint
 			 uint32_t *__restrict__ o_first, uint32_t *__restrict__ o_last, uint32_t *__restrict__ o_allele,
 			 uint8_t *__restrict__ o_rev)
 {
-	for (uint32_t t = blockIdx.x * T_TPB + threadIdx.x; t < R; t += gridDim.x * T_TPB) {
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < R; t += gridDim.x * Q_TPB) {
 		const uint64_t pos = rpos[t] & ~ROLE_BIT;
-		const uint32_t p = path_of(path_off, n_paths, pos);
+		const uint32_t p = span_of(path_off, n_paths, pos);
 		o_path[t] = p;
 		o_first[t] = (uint32_t)(pos - path_off[p]);
 		o_last[t] = (uint32_t)(pos - path_off[p]) + rlen[t] - 1;
@@ -495,19 +452,19 @@ __global__ void k_tr_out(uint32_t R, const uint64_t *__restrict__ path_off, uint
 // allele_off[q] = aidx[trav_off[q]]
 __global__ void k_tr_allele_off(uint32_t n, const uint32_t *__restrict__ toff, const uint32_t *__restrict__ aidx, uint32_t *__restrict__ aoff)
 {
-	const uint32_t q = blockIdx.x * T_TPB + threadIdx.x;
+	const uint32_t q = blockIdx.x * Q_TPB + threadIdx.x;
 	if (q <= n)
 		aoff[q] = aidx[toff[q]];
 }
 
 // the steps of every allele (S -> Z), one wave per allele
-__global__ __launch_bounds__(T_TPB) void k_tr_allele_steps(uint32_t n_al, const uint32_t *__restrict__ steps, const uint32_t *__restrict__ vid,
+__global__ __launch_bounds__(Q_TPB) void k_tr_allele_steps(uint32_t n_al, const uint32_t *__restrict__ steps, const uint32_t *__restrict__ vid,
 							   const uint32_t *__restrict__ afirst, const uint64_t *__restrict__ rpos,
 							   const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ soff,
 							   uint32_t *__restrict__ o_id, uint8_t *__restrict__ o_or)
 {
-	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (T_TPB / 64);
-	for (uint32_t a = blockIdx.x * (T_TPB / 64) + (threadIdx.x >> 6); a < n_al; a += waves) {
+	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
+	for (uint32_t a = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); a < n_al; a += waves) {
 		const uint32_t t = afirst[a], len = rlen[t], at = soff[a];
 		const uint64_t p = rpos[t];
 		const bool rev = (p & ROLE_BIT) != 0;
@@ -521,9 +478,7 @@ __global__ __launch_bounds__(T_TPB) void k_tr_allele_steps(uint32_t n_al, const 
 
 static void check_32(uint64_t v, const char *what)
 {
-	if (v >= 0xFFFFFFFFull)
-		throw HipError(std::string("the traversals need ") + std::to_string(v) + " " + what +
-			       ": 2^32 or more are refused for now (the scans and sorts here are 32-bit)");
+	refuse_2_32(v, "the traversals need ", what, " for now (the scans and sorts here are 32-bit)");
 }
 
 static uint32_t hash_bits_hook()
@@ -592,7 +547,7 @@ extern "C" int povu_hip_paths_upload(povu_hip_ctx *ctx, uint32_t n_paths, const 
 		}
 		launch_vid_ascending(g.V, g.vid, words, s);
 		if (N)
-			KLAUNCH(k_tr_map_steps, dim3(tgrid(N)), dim3(T_TPB), 0, s, N, ctx->path_steps, rev, g.vid, g.V, bad);
+			KLAUNCH(k_tr_map_steps, dim3(stride_blocks(N)), dim3(Q_TPB), 0, s, N, ctx->path_steps, rev, g.vid, g.V, bad);
 		uint32_t hw[4] = {0};
 		uint64_t hb = 0;
 		HIP_CHECK(copy_async(hw, words, 16, hipMemcpyDeviceToHost, s));
@@ -624,197 +579,254 @@ struct TraversalsOwner {
 
 namespace povu_hip
 {
+namespace
+{
+// what a call asks for and what is resident
+struct TravParams {
+	povu_hip_ctx *ctx;
+	hipStream_t s;
+	uint32_t max_steps, flags, hbits;
+	uint64_t N, n_tiles; // path steps, their tiles of T_TILE in the start-task passes
+	uint32_t P, nS;
+};
+// phase A (the front end's arena): the queries, the boundary table, the tile counts
+struct TravBoundary {
+	QueryFront q;
+	size_t n1; // queries + 1
+	uint32_t *qstatus, *boff, *bval, *tile_cnt, *tile_off; // bval: the table's (query, role) entries
+	unsigned long long *tot;
+	void *tmp;
+	size_t tmp_bytes;
+};
+// phase B (tr_task): the tasks, sorted by query, and what their scans found
+struct TravTasks {
+	uint32_t T = 0, n2 = 0, R = 0; // tasks, those tier 2 took, those that closed (the traversals)
+	uint32_t *sq, *tlen, *list;    // list: the tasks handed over, then the closed ones
+	uint64_t *spos, *thash;
+	uint8_t *handover, *closed;
+	void *tmp;
+	size_t tmp_bytes;
+};
+// phase C (tr_trav): the traversals, grouped into alleles
+struct TravGroups {
+	uint64_t *rpos;
+	uint32_t *rq, *rlen, *toff, *aoff, *rep, *firstf, *aidx, *rallele, *afirst, *alen, *soff;
+	const uint32_t *sp; // the traversals sorted by (query, length, hash)
+	void *tmp;
+	size_t tmp_bytes;
+	uint32_t n_al = 0;
+	uint64_t n_splits = 0, n_steps = 0;
+};
+} // namespace
+
+static TravBoundary boundary_table(const TravParams &p, const QueryFrontFn &front, CallTimer &timer)
+{
+	hipStream_t s = p.s;
+	TravBoundary b;
+	uint32_t *bkey, *bval, *bkey2, *bcnt;
+	b.q = front(timer, [&](Spans &take, uint32_t n) {
+		const size_t n2q = 2 * (size_t)n + 1;
+		b.tmp_bytes = std::max(prim_tmp_bytes(std::max<size_t>((size_t)p.nS + 1, p.n_tiles + 1), false), sort_tmp_bytes(n2q)) + 256;
+		take((size_t)n + 1, b.qstatus);
+		take(n2q, bkey, bval, bkey2, b.bval);
+		take((size_t)p.nS + 1, bcnt, b.boff);
+		take(p.n_tiles + 1, b.tile_cnt, b.tile_off);
+		take(2, b.tot);
+		take(b.tmp_bytes, b.tmp);
+	});
+	const uint32_t n = b.q.n;
+	b.n1 = (size_t)n + 1;
+	HIP_CHECK(hipMemsetAsync(b.qstatus, 0, b.n1 * 4, s));
+	HIP_CHECK(hipMemsetAsync(bcnt, 0, ((size_t)p.nS + 1) * 4, s));
+	uint32_t hw[8] = {0};
+	HIP_CHECK(copy_async(hw, b.q.words, 32, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	query_refusals(hw[0], "traversals");
+	if (n) {
+		KLAUNCH(k_tr_keys, dim3(lane_blocks(n)), dim3(Q_TPB), 0, s, n, p.nS, b.q.ys, b.q.yz, bkey, bval, bcnt);
+		sort_pairs_u32(bkey, bkey2, bval, b.bval, 2 * (size_t)n, bits_for(p.nS), b.tmp, b.tmp_bytes, s);
+	}
+	scan_exclusive_u32(bcnt, b.boff, (size_t)p.nS + 1, b.tmp, b.tmp_bytes, s);
+	return b;
+}
+
+// count per tile, total, offsets, emit, sort by query
+static TravTasks start_tasks(const TravParams &p, const TravBoundary &b)
+{
+	povu_hip_ctx *ctx = p.ctx;
+	hipStream_t s = p.s;
+	TravTasks t;
+	if (p.n_tiles)
+		KLAUNCH(k_tr_count, dim3((unsigned)p.n_tiles), dim3(Q_TPB), 0, s, p.N, ctx->path_steps, b.boff, b.tile_cnt);
+	counts_to_offsets(b.tile_cnt, b.tile_off, nullptr, nullptr, p.n_tiles, b.tot, b.tmp, b.tmp_bytes, s, [&](const uint64_t *total) {
+		check_32(total[0], "scan tasks");
+		t.T = (uint32_t)total[0];
+	});
+	const uint32_t T = t.T;
+	const size_t T1 = (size_t)T + 1;
+	t.tmp_bytes = prim_tmp_bytes(T1, true) + 256;
+	uint64_t *tpos;
+	uint32_t *tkey, *tval, *perm;
+	carve(ctx->tr_task, [&](Spans &take) {
+		take(T1, tpos, t.spos, t.thash, tkey, tval, t.sq, perm, t.tlen, t.list, t.handover, t.closed);
+		take(t.tmp_bytes, t.tmp);
+	});
+	if (T) {
+		KLAUNCH(k_tr_emit, dim3((unsigned)p.n_tiles), dim3(Q_TPB), 0, s, p.N, ctx->path_steps, b.boff, b.bval, b.tile_off, tpos, tkey);
+		launch_iota(T, tval, s);
+		sort_pairs_u32(tkey, t.sq, tval, perm, T, bits_for(b.q.n), t.tmp, t.tmp_bytes, s);
+		KLAUNCH(k_tr_gather64, dim3(stride_blocks(T)), dim3(Q_TPB), 0, s, T, perm, tpos, t.spos);
+	}
+	return t;
+}
+
+// tier 1, the hand-over, tier 2, the closed tasks
+static void scan_tasks(const TravParams &p, const TravBoundary &b, TravTasks &t)
+{
+	hipStream_t s = p.s;
+	const uint32_t T = t.T, hbits = p.hbits;
+	uint32_t *words = b.q.words;
+	if (!T)
+		return;
+	const ScanArgs SA{p.ctx->path_steps, p.ctx->path_off, p.P, b.q.ys, b.q.yz, p.max_steps,
+			  hbits >= 64 ? 0xFFFFFFFFu : hbits > 32 ? (1u << (hbits - 32)) - 1 : 0u, hbits >= 32 ? 0xFFFFFFFFu : (1u << hbits) - 1};
+	const ScanOut SO{t.tlen, t.thash, b.qstatus};
+	KLAUNCH(k_tr_t1, dim3(lane_blocks(T)), dim3(Q_TPB), 0, s, T, SA, t.sq, t.spos, (p.flags & POVU_HIP_T_FORCE_TIER2) ? 1u : 0u, SO, t.handover);
+	compact_flagged_u8(t.handover, T, t.list, words + 1, t.tmp, t.tmp_bytes, s);
+	t.n2 = read_back(words + 1, s);
+	if (t.n2) {
+		const unsigned wg = (unsigned)std::min<uint64_t>(((uint64_t)t.n2 + Q_TPB / 64 - 1) / (Q_TPB / 64), 4096);
+		KLAUNCH(k_tr_t2, dim3(wg), dim3(Q_TPB), 0, s, t.list, t.n2, words + 2, SA, t.sq, t.spos, SO);
+	}
+	KLAUNCH(k_tr_closed, dim3(stride_blocks(T)), dim3(Q_TPB), 0, s, T, t.tlen, t.closed);
+	compact_flagged_u8(t.closed, T, t.list, words + 3, t.tmp, t.tmp_bytes, s);
+	t.R = read_back(words + 3, s);
+}
+
+// the traversals' fields, the LSD sort by (query, length, hash), run heads, the check of every run, the exact regrouping of
+// the runs with a mismatch.  g.n_splits is on its way to the host when this returns: alleles() waits for it.
+static void dedup(const TravParams &p, const TravBoundary &b, const TravTasks &t, TravGroups &g)
+{
+	povu_hip_ctx *ctx = p.ctx;
+	hipStream_t s = p.s;
+	const uint32_t n = b.q.n, R = t.R, hbits = p.hbits;
+	uint32_t *words = b.q.words;
+	const size_t R1 = (size_t)R + 1, n1 = b.n1;
+	g.tmp_bytes = std::max(prim_tmp_bytes(R1, true), prim_tmp_bytes(n1, false)) + 256;
+	uint64_t *rhash;
+	uint32_t *pa, *pb, *key, *kout, *mark, *hmax, *head, *blist;
+	uint8_t *rbad;
+	carve(ctx->tr_trav, [&](Spans &take) {
+		take(R1, g.rpos, rhash, g.rq, g.rlen, pa, pb, key, kout, mark, hmax, head, g.rep);
+		take(R1, g.firstf, g.aidx, g.rallele, g.afirst, g.alen, g.soff, blist);
+		take(n1, g.toff, g.aoff);
+		take(R1, rbad);
+		take(g.tmp_bytes, g.tmp);
+	});
+	// (`list` of tr_task holds the traversals' task indices)
+	if (R) {
+		KLAUNCH(k_tr_trav_fields, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, t.list, t.sq, t.spos, t.tlen, t.thash, g.rq, g.rpos, g.rlen, rhash);
+	}
+	KLAUNCH(k_tr_query_off, dim3(lane_blocks(n1)), dim3(Q_TPB), 0, s, n, R, g.rq, g.toff);
+	if (!R)
+		return;
+	launch_iota(R, pa, s);
+	LsdSort sort{pa, pb, key, kout, R, g.tmp, g.tmp_bytes, s};
+	auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
+		KLAUNCH(k_tr_sort_key, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, which, perm, rhash, g.rlen, g.rq, k);
+	};
+	sort.pass(0, std::min(hbits, 32u), write_key);
+	if (hbits > 32)
+		sort.pass(1, hbits - 32, write_key);
+	sort.pass(2, bits_for(p.max_steps), write_key);
+	sort.pass(3, bits_for(n), write_key);
+	const uint32_t *sp = g.sp = sort.cur;
+	KLAUNCH(k_tr_heads, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, sp, rhash, g.rlen, g.rq, mark);
+	scan_exclusive_max_u32(mark, hmax, R, g.tmp, g.tmp_bytes, s);
+	HIP_CHECK(hipMemsetAsync(rbad, 0, R1, s));
+	HIP_CHECK(hipMemsetAsync(b.tot, 0, 16, s));
+	KLAUNCH(k_tr_check, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, ctx->path_steps, sp, hmax, mark, g.rpos, g.rlen, head, g.rep, rbad);
+	compact_flagged_u8(rbad, R, blist, words + 4, g.tmp, g.tmp_bytes, s);
+	const uint32_t nb = read_back(words + 4, s);
+	if (nb) {
+		KLAUNCH(k_tr_regroup, dim3(lane_blocks(nb)), dim3(Q_TPB), 0, s, nb, blist, R, ctx->path_steps, sp, head, g.rpos, g.rlen, g.rep, b.tot + 1);
+		HIP_CHECK(copy_async(&g.n_splits, b.tot + 1, 8, hipMemcpyDeviceToHost, s));
+	}
+}
+
+// an allele per group, numbered in traversal order; the alleles of every query; their step offsets
+static void alleles(const TravParams &p, const TravBoundary &b, const TravTasks &t, TravGroups &g)
+{
+	hipStream_t s = p.s;
+	const uint32_t n = b.q.n, R = t.R;
+	const size_t R1 = (size_t)R + 1;
+	if (R) {
+		HIP_CHECK(hipMemsetAsync(g.firstf, 0, R1 * 4, s));
+		KLAUNCH(k_tr_first, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, g.sp, g.rep, g.firstf);
+		scan_exclusive_u32(g.firstf, g.aidx, R1, g.tmp, g.tmp_bytes, s);
+		HIP_CHECK(copy_async(&g.n_al, g.aidx + R, 4, hipMemcpyDeviceToHost, s));
+		KLAUNCH(k_tr_allele, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, g.sp, g.rep, g.aidx, g.rlen, g.rallele, g.afirst, g.alen);
+		HIP_CHECK(hipStreamSynchronize(s));
+	} else {
+		HIP_CHECK(hipMemsetAsync(g.aidx, 0, 4, s));
+	}
+	KLAUNCH(k_tr_allele_off, dim3(lane_blocks(b.n1)), dim3(Q_TPB), 0, s, n, g.toff, g.aidx, g.aoff);
+	if (g.n_al)
+		counts_to_offsets(g.alen, g.soff, nullptr, nullptr, g.n_al, b.tot, g.tmp, g.tmp_bytes, s, [&](const uint64_t *total) {
+			check_32(total[0], "allele steps");
+			g.n_steps = total[0];
+		});
+}
+
+// per traversal and allele steps, in tr_steps
+static TravDevice outputs(const TravParams &p, const TravBoundary &b, const TravTasks &t, const TravGroups &g)
+{
+	povu_hip_ctx *ctx = p.ctx;
+	hipStream_t s = p.s;
+	const uint32_t R = t.R, n_al = g.n_al;
+	TravDevice d;
+	carve(ctx->tr_steps, [&](Spans &take) {
+		take((size_t)R + 1, d.op, d.of, d.ol, d.oa, d.orv);
+		take(g.n_steps + 1, d.sid, d.sor);
+	});
+	if (R)
+		KLAUNCH(k_tr_out, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, ctx->path_off, p.P, g.rq, g.rpos, g.rlen, g.rallele, g.aidx, g.toff, d.op, d.of,
+			d.ol, d.oa, d.orv);
+	if (n_al)
+		KLAUNCH(k_tr_allele_steps, dim3(wave_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, ctx->path_steps, ctx->g.vid, g.afirst, g.rpos, g.rlen, g.soff,
+			d.sid, d.sor);
+	d.q = b.q;
+	d.R = R;
+	d.n_al = n_al;
+	d.n2 = t.n2;
+	d.n_steps = g.n_steps;
+	d.n_splits = g.n_splits;
+	d.toff = g.toff, d.aoff = g.aoff, d.qstatus = b.qstatus;
+	d.soff = g.soff, d.rq = g.rq, d.rlen = g.rlen, d.afirst = g.afirst, d.rpos = g.rpos;
+	return d;
+}
+
 TravDevice trav_pipeline(povu_hip_ctx *ctx, const QueryFrontFn &front, const povu_hip_trav_opts *opts, CallTimer &timer)
 {
 	if (!ctx->paths_valid || ctx->paths_gen != ctx->g.gen)
 		throw HipError("no paths are resident for the graph now uploaded (povu_hip_paths_upload after povu_hip_graph_upload)");
-	uint32_t max_steps = 65536, flags = 0;
+	TravParams p{ctx, ctx->stream, 65536, 0, hash_bits_hook(), ctx->n_path_steps, 0, ctx->n_paths, 2 * ctx->g.V};
 	if (opts) {
 		if (opts->max_steps == 1)
 			throw HipError("max_steps must be at least 2");
 		if (opts->max_steps)
-			max_steps = opts->max_steps;
-		flags = opts->flags;
+			p.max_steps = opts->max_steps;
+		p.flags = opts->flags;
 	}
-	const uint32_t hbits = hash_bits_hook();
-	const ResidentGraph &g = ctx->g;
-	hipStream_t s = ctx->stream;
-	const uint64_t N = ctx->n_path_steps;
-	const uint32_t P = ctx->n_paths, nS = 2 * g.V;
-	const uint64_t n_tiles = (N + T_TILE - 1) / T_TILE;
-	check_32(n_tiles + 1, "start-task tiles");
-
-	// ---- phase A: queries, the boundary table, tile counts
-	uint32_t *qstatus, *bkey, *bval, *bkey2, *bval2, *bcnt, *boff, *tile_cnt, *tile_off;
-	unsigned long long *tot;
-	void *sort_tmp_a, *scan_tmp_a;
-	size_t sort_a = 0;
-	const size_t scan_a = scan_tmp_bytes(std::max<size_t>((size_t)nS + 1, n_tiles + 1)) + 256;
-	const QueryFront q = front(timer, [&](Spans &take, uint32_t n) {
-		const size_t n2q = 2 * (size_t)n + 1;
-		sort_a = sort_tmp_bytes(n2q) + 256;
-		take((size_t)n + 1, qstatus);
-		take(n2q, bkey, bval, bkey2, bval2);
-		take((size_t)nS + 1, bcnt, boff);
-		take(n_tiles + 1, tile_cnt, tile_off);
-		take(2, tot);
-		take(sort_a, sort_tmp_a);
-		take(scan_a, scan_tmp_a);
-	});
-	const uint32_t n = q.n, *ys = q.ys, *yz = q.yz;
-	uint32_t *words = q.words;
-	const size_t n1 = (size_t)n + 1;
-	HIP_CHECK(hipMemsetAsync(qstatus, 0, n1 * 4, s));
-	HIP_CHECK(hipMemsetAsync(bcnt, 0, ((size_t)nS + 1) * 4, s));
-	uint32_t hw[8] = {0};
-	HIP_CHECK(copy_async(hw, words, 32, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(hipStreamSynchronize(s));
-	query_refusals(hw[0], "traversals");
-	if (n) {
-		KLAUNCH(k_tr_keys, dim3(tblk(n)), dim3(T_TPB), 0, s, n, nS, ys, yz, bkey, bval, bcnt);
-		sort_pairs_u32(bkey, bkey2, bval, bval2, 2 * (size_t)n, bits_for(nS), sort_tmp_a, sort_a, s);
-	}
-	scan_exclusive_u32(bcnt, boff, (size_t)nS + 1, scan_tmp_a, scan_a, s);
-
-	// ---- start tasks: count per tile, scan, emit
-	if (n_tiles)
-		KLAUNCH(k_tr_count, dim3((unsigned)n_tiles), dim3(T_TPB), 0, s, N, ctx->path_steps, boff, tile_cnt);
-	HIP_CHECK(hipMemsetAsync(tile_cnt + n_tiles, 0, 4, s));
-	uint64_t T64 = 0;
-	totals_u32(tile_cnt, nullptr, n_tiles, tot, &T64, s);
-	check_32(T64, "scan tasks");
-	const uint32_t T = (uint32_t)T64;
-	scan_exclusive_u32(tile_cnt, tile_off, n_tiles + 1, scan_tmp_a, scan_a, s);
-
-	// ---- phase B: the tasks, sorted by query, and their scans
-	const size_t T1 = (size_t)T + 1;
-	const size_t sort_b = sort_tmp_bytes(T1) + 256, comp_b = compact_tmp_bytes(T1) + 256;
-	uint64_t *tpos, *spos, *thash;
-	uint32_t *tkey, *tval, *sq, *perm, *tlen, *list;
-	uint8_t *handover, *closed;
-	void *sort_tmp_b, *comp_tmp_b;
-	carve(ctx->tr_task, [&](Spans &take) {
-		take(T1, tpos, spos, thash, tkey, tval, sq, perm, tlen, list, handover, closed);
-		take(sort_b, sort_tmp_b);
-		take(comp_b, comp_tmp_b);
-	});
-	uint32_t n2 = 0, R = 0;
-	ScanArgs SA{ctx->path_steps, ctx->path_off, P, ys, yz, max_steps, hbits >= 64 ? 0xFFFFFFFFu : hbits > 32 ? (1u << (hbits - 32)) - 1 : 0u,
-		    hbits >= 32 ? 0xFFFFFFFFu : (1u << hbits) - 1};
-	ScanOut SO{tlen, thash, qstatus};
-	if (T) {
-		KLAUNCH(k_tr_emit, dim3((unsigned)n_tiles), dim3(T_TPB), 0, s, N, ctx->path_steps, boff, bval2, tile_off, tpos, tkey);
-		KLAUNCH(k_tr_iota, dim3(tgrid(T)), dim3(T_TPB), 0, s, T, tval);
-		sort_pairs_u32(tkey, sq, tval, perm, T, bits_for(n), sort_tmp_b, sort_b, s);
-		KLAUNCH(k_tr_gather64, dim3(tgrid(T)), dim3(T_TPB), 0, s, T, perm, tpos, spos);
-		KLAUNCH(k_tr_t1, dim3(tblk(T)), dim3(T_TPB), 0, s, T, SA, sq, spos, (flags & POVU_HIP_T_FORCE_TIER2) ? 1u : 0u, SO, handover);
-		compact_flagged_u8(handover, T, list, words + 1, comp_tmp_b, comp_b, s);
-		HIP_CHECK(copy_async(&n2, words + 1, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		if (n2) {
-			const unsigned wg = (unsigned)std::min<uint64_t>(((uint64_t)n2 + T_TPB / 64 - 1) / (T_TPB / 64), 4096);
-			KLAUNCH(k_tr_t2, dim3(wg), dim3(T_TPB), 0, s, list, n2, words + 2, SA, sq, spos, SO);
-		}
-		KLAUNCH(k_tr_closed, dim3(tgrid(T)), dim3(T_TPB), 0, s, T, tlen, closed);
-		compact_flagged_u8(closed, T, list, words + 3, comp_tmp_b, comp_b, s);
-		HIP_CHECK(copy_async(&R, words + 3, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-	}
-
-	// ---- phase C: the traversals, grouped into alleles
-	const size_t R1 = (size_t)R + 1;
-	const size_t sort_c = sort_tmp_bytes(R1) + 256, scan_c = scan_tmp_bytes(std::max(R1, n1)) + 256, comp_c = compact_tmp_bytes(R1) + 256;
-	uint64_t *rpos, *rhash;
-	uint32_t *rq, *rlen, *pa, *pb, *key, *kout, *mark, *hmax, *head, *rep, *firstf, *aidx, *rallele, *afirst, *alen, *soff, *blist;
-	uint32_t *toff, *aoff;
-	uint8_t *rbad;
-	void *sort_tmp_c, *scan_tmp_c, *comp_tmp_c;
-	carve(ctx->tr_trav, [&](Spans &take) {
-		take(R1, rpos, rhash, rq, rlen, pa, pb, key, kout, mark, hmax, head, rep);
-		take(R1, firstf, aidx, rallele, afirst, alen, soff, blist);
-		take(n1, toff, aoff);
-		take(R1, rbad);
-		take(sort_c, sort_tmp_c);
-		take(scan_c, scan_tmp_c);
-		take(comp_c, comp_tmp_c);
-	});
-	// (`list` of tr_task holds the traversals' task indices)
-	uint64_t n_splits = 0;
-	uint32_t n_al = 0;
-	if (R) {
-		KLAUNCH(k_tr_trav_fields, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, list, sq, spos, tlen, thash, rq, rpos, rlen, rhash);
-	}
-	KLAUNCH(k_tr_query_off, dim3(tblk(n1)), dim3(T_TPB), 0, s, n, R, rq, toff);
-	if (R) {
-		// stable LSD sort of the traversal indices by (query, length, hash): least significant key first
-		KLAUNCH(k_tr_iota, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, pa);
-		uint32_t *cur = pa, *nxt = pb;
-		auto pass = [&](int which, unsigned bits) {
-			KLAUNCH(k_tr_sort_key, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, which, cur, rhash, rlen, rq, key);
-			sort_pairs_u32(key, kout, cur, nxt, R, bits, sort_tmp_c, sort_c, s);
-			std::swap(cur, nxt);
-		};
-		pass(0, std::min(hbits, 32u));
-		if (hbits > 32)
-			pass(1, hbits - 32);
-		pass(2, bits_for(max_steps));
-		pass(3, bits_for(n));
-		const uint32_t *sp = cur;
-		KLAUNCH(k_tr_heads, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, sp, rhash, rlen, rq, mark);
-		scan_exclusive_max_u32(mark, hmax, R, scan_tmp_c, scan_c, s);
-		HIP_CHECK(hipMemsetAsync(rbad, 0, R1, s));
-		HIP_CHECK(hipMemsetAsync(tot, 0, 16, s));
-		KLAUNCH(k_tr_check, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, ctx->path_steps, sp, hmax, mark, rpos, rlen, head, rep, rbad);
-		compact_flagged_u8(rbad, R, blist, words + 4, comp_tmp_c, comp_c, s);
-		uint32_t nb = 0;
-		HIP_CHECK(copy_async(&nb, words + 4, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		if (nb) {
-			KLAUNCH(k_tr_regroup, dim3(tblk(nb)), dim3(T_TPB), 0, s, nb, blist, R, ctx->path_steps, sp, head, rpos, rlen, rep, tot + 1);
-			HIP_CHECK(copy_async(&n_splits, tot + 1, 8, hipMemcpyDeviceToHost, s));
-		}
-		HIP_CHECK(hipMemsetAsync(firstf, 0, R1 * 4, s));
-		KLAUNCH(k_tr_first, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, sp, rep, firstf);
-		scan_exclusive_u32(firstf, aidx, R1, scan_tmp_c, scan_c, s);
-		HIP_CHECK(copy_async(&n_al, aidx + R, 4, hipMemcpyDeviceToHost, s));
-		KLAUNCH(k_tr_allele, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, sp, rep, aidx, rlen, rallele, afirst, alen);
-		HIP_CHECK(hipStreamSynchronize(s));
-	} else {
-		HIP_CHECK(hipMemsetAsync(aidx, 0, 4, s));
-	}
-	KLAUNCH(k_tr_allele_off, dim3(tblk(n1)), dim3(T_TPB), 0, s, n, toff, aidx, aoff);
-	uint64_t n_steps = 0;
-	if (n_al)
-		totals_u32(alen, nullptr, n_al, tot, &n_steps, s);
-	check_32(n_steps, "allele steps");
-	if (n_al) {
-		HIP_CHECK(hipMemsetAsync(alen + n_al, 0, 4, s));
-		scan_exclusive_u32(alen, soff, (size_t)n_al + 1, scan_tmp_c, scan_c, s);
-	}
-
-	// ---- outputs: per traversal and allele steps, in tr_steps
-	uint32_t *op, *of, *ol, *oa, *sid;
-	uint8_t *orv, *sor;
-	carve(ctx->tr_steps, [&](Spans &take) {
-		take(R1, op, of, ol, oa, orv);
-		take(n_steps + 1, sid, sor);
-	});
-	if (R)
-		KLAUNCH(k_tr_out, dim3(tgrid(R)), dim3(T_TPB), 0, s, R, ctx->path_off, P, rq, rpos, rlen, rallele, aidx, toff, op, of, ol, oa, orv);
-	if (n_al)
-		KLAUNCH(k_tr_allele_steps, dim3((unsigned)std::min<uint64_t>(((uint64_t)n_al + 3) / 4, 65536)), dim3(T_TPB), 0, s, n_al,
-			ctx->path_steps, g.vid, afirst, rpos, rlen, soff, sid, sor);
-
-	TravDevice d;
-	d.q = q;
-	d.R = R;
-	d.n_al = n_al;
-	d.n2 = n2;
-	d.n_steps = n_steps;
-	d.n_splits = n_splits;
-	d.op = op, d.of = of, d.ol = ol, d.oa = oa, d.sid = sid, d.toff = toff, d.aoff = aoff, d.qstatus = qstatus;
-	d.soff = soff, d.rq = rq, d.rlen = rlen, d.afirst = afirst, d.orv = orv, d.sor = sor, d.rpos = rpos;
-	return d;
+	p.n_tiles = (p.N + T_TILE - 1) / T_TILE;
+	check_32(p.n_tiles + 1, "start-task tiles");
+	const TravBoundary b = boundary_table(p, front, timer);
+	TravTasks t = start_tasks(p, b);
+	scan_tasks(p, b, t);
+	TravGroups g;
+	dedup(p, b, t, g);
+	alleles(p, b, t, g);
+	return outputs(p, b, t, g);
 }
 } // namespace povu_hip
 

@@ -25,13 +25,10 @@
 namespace povu_hip
 {
 
-static constexpr int W_TPB = 256;
 static constexpr uint32_t T1_DEPTH = 16;	 // frames of a tier-1 stack (LDS: 16 x 256 x 8 B = 32 KiB per block)
 static constexpr uint32_t T1_EXPANSIONS = 4096; // expansions tier 1 spends before it hands a query over
 static constexpr uint32_t SORT_IN_LANE = 64;	 // sides up to this many slots are sorted by one lane
 static constexpr uint8_t ST_MORE = POVU_HIP_WALK_MORE, ST_LONG = POVU_HIP_WALK_LONG, ST_BUDGET = POVU_HIP_WALK_BUDGET;
-
-static inline unsigned wblk(size_t n) { return (unsigned)((n + W_TPB - 1) / W_TPB); }
 
 struct WalkCaps {
 	uint32_t K, L, E;
@@ -44,7 +41,7 @@ struct WalkCaps {
 __global__ void k_wk_ssucc(uint32_t nS, const uint32_t *__restrict__ off, const uint32_t *__restrict__ aoth,
 			      uint32_t *__restrict__ ssucc, uint32_t *__restrict__ hub)
 {
-	const uint32_t x = blockIdx.x * W_TPB + threadIdx.x;
+	const uint32_t x = blockIdx.x * Q_TPB + threadIdx.x;
 	if (x >= nS)
 		return;
 	const uint32_t b = off[x], e = off[x + 1];
@@ -66,7 +63,7 @@ __global__ void k_wk_ssucc(uint32_t nS, const uint32_t *__restrict__ off, const 
 // side of every slot (the key of the second, stable sort of the hub path)
 __global__ void k_wk_slot_side(uint32_t nS, const uint32_t *__restrict__ off, uint32_t *__restrict__ side_of)
 {
-	const uint32_t x = blockIdx.x * W_TPB + threadIdx.x;
+	const uint32_t x = blockIdx.x * Q_TPB + threadIdx.x;
 	if (x >= nS)
 		return;
 	for (uint32_t i = off[x], e = off[x + 1]; i < e; i++)
@@ -89,18 +86,18 @@ struct WalkSink {
 	uint32_t w0, w_end, s0, s_end; // walks [w0, w_end), steps [s0, s_end) of this query
 };
 
-// One lane, stack in LDS: frame k of lane t at [k * W_TPB + t] (consecutive lanes, consecutive banks).
+// One lane, stack in LDS: frame k of lane t at [k * Q_TPB + t] (consecutive lanes, consecutive banks).
 struct LaneStack {
 	uint32_t *sy, *sc;
 	uint32_t t;
 	static constexpr uint32_t cap = T1_DEPTH;
-	__device__ uint32_t y(uint32_t k) const { return sy[k * W_TPB + t]; }
-	__device__ uint32_t cur(uint32_t k) const { return sc[k * W_TPB + t]; }
-	__device__ void set_cur(uint32_t k, uint32_t c) { sc[k * W_TPB + t] = c; }
+	__device__ uint32_t y(uint32_t k) const { return sy[k * Q_TPB + t]; }
+	__device__ uint32_t cur(uint32_t k) const { return sc[k * Q_TPB + t]; }
+	__device__ void set_cur(uint32_t k, uint32_t c) { sc[k * Q_TPB + t] = c; }
 	__device__ void push(uint32_t k, uint32_t yy, uint32_t c)
 	{
-		sy[k * W_TPB + t] = yy;
-		sc[k * W_TPB + t] = c;
+		sy[k * Q_TPB + t] = yy;
+		sc[k * Q_TPB + t] = c;
 	}
 	__device__ void pop(uint32_t) {}
 	__device__ bool on_path(uint32_t u, uint32_t depth) const
@@ -277,14 +274,14 @@ __device__ DfsResult dfs(Stack &st, const uint32_t *__restrict__ off, const uint
 
 // tier 1, count pass: one lane per query.  Hands over (flag) what needs more than T1_DEPTH frames or T1_EXPANSIONS.
 template <bool EMIT>
-__global__ __launch_bounds__(W_TPB) void k_wk_t1(uint32_t n, const uint32_t *__restrict__ off, const uint32_t *__restrict__ ssucc,
+__global__ __launch_bounds__(Q_TPB) void k_wk_t1(uint32_t n, const uint32_t *__restrict__ off, const uint32_t *__restrict__ ssucc,
 						   const uint32_t *__restrict__ ys, const uint32_t *__restrict__ yz, WalkCaps c, uint32_t force2,
 						   uint32_t *__restrict__ cntw, uint32_t *__restrict__ cnts, uint8_t *__restrict__ status,
 						   uint8_t *__restrict__ handover, const uint32_t *__restrict__ woff,
 						   const uint32_t *__restrict__ sbase, WalkSink sink)
 {
-	__shared__ uint32_t sy[T1_DEPTH * W_TPB], sc[T1_DEPTH * W_TPB];
-	const uint32_t q = blockIdx.x * W_TPB + threadIdx.x;
+	__shared__ uint32_t sy[T1_DEPTH * Q_TPB], sc[T1_DEPTH * Q_TPB];
+	const uint32_t q = blockIdx.x * Q_TPB + threadIdx.x;
 	if (q >= n)
 		return;
 	if (EMIT && handover[q])
@@ -313,13 +310,13 @@ __global__ __launch_bounds__(W_TPB) void k_wk_t1(uint32_t n, const uint32_t *__r
 // it is done with one; `lanes` lanes, lane i's words in scratch at [i, i + lanes, ...): 2 L stack words, then 2^tbits path-set
 // slots (zeroed before the launch; every search leaves its set empty)
 template <bool EMIT>
-__global__ __launch_bounds__(W_TPB) void k_wk_t2(const uint32_t *__restrict__ list, uint32_t n2, uint32_t *__restrict__ next,
+__global__ __launch_bounds__(Q_TPB) void k_wk_t2(const uint32_t *__restrict__ list, uint32_t n2, uint32_t *__restrict__ next,
 						 uint32_t lanes, uint32_t tbits, const uint32_t *__restrict__ off, const uint32_t *__restrict__ ssucc,
 						 const uint32_t *__restrict__ ys, const uint32_t *__restrict__ yz, WalkCaps c, uint32_t *scratch,
 						 uint32_t *__restrict__ cntw, uint32_t *__restrict__ cnts, uint8_t *__restrict__ status,
 						 const uint32_t *__restrict__ woff, const uint32_t *__restrict__ sbase, WalkSink sink)
 {
-	const uint32_t lane = blockIdx.x * W_TPB + threadIdx.x;
+	const uint32_t lane = blockIdx.x * Q_TPB + threadIdx.x;
 	if (lane >= lanes)
 		return;
 	GlobalStack st{scratch + lane, scratch + (size_t)lanes * c.L + lane, scratch + (size_t)lanes * 2 * c.L + lane, lanes, c.L, tbits};
@@ -385,15 +382,14 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 		uint32_t *cntw, *cnts, *woff, *sbase, *list2, *ssucc;
 		uint8_t *status, *handover;
 		unsigned long long *tot;
-		void *scan_tmp, *comp_tmp;
-		size_t scan_b = 0, comp_b = 0;
+		void *tmp;
+		size_t tmp_b = 0;
 		const QueryFront q = query_front(ctx, f, ctx->wk_ws, timer, [&](Spans &take, uint32_t n) {
 			const size_t n1 = (size_t)n + 1;
-			scan_b = scan_tmp_bytes(n1) + 256, comp_b = compact_tmp_bytes(n1) + 256;
+			tmp_b = prim_tmp_bytes(n1, false) + 256;
 			take(n1, cntw, cnts, woff, sbase, list2, status, handover);
 			take(2, tot);
-			take(scan_b, scan_tmp);
-			take(comp_b, comp_tmp);
+			take(tmp_b, tmp);
 			take(slots + 8, ssucc);
 		});
 		const uint32_t n = q.n, *ys = q.ys, *yz = q.yz;
@@ -402,7 +398,7 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 		// words: [0] the checks, [1] hand-over count, [2] / [3] tier-2 work counter of the count / emit pass, [4] a side has
 		// more than SORT_IN_LANE slots
 		if (nS)
-			KLAUNCH(k_wk_ssucc, dim3(wblk(nS)), dim3(W_TPB), 0, s, nS, g.off, g.aoth, ssucc, words + 4);
+			KLAUNCH(k_wk_ssucc, dim3(lane_blocks(nS)), dim3(Q_TPB), 0, s, nS, g.off, g.aoth, ssucc, words + 4);
 		uint32_t hw[8] = {0};
 		HIP_CHECK(copy_async(hw, words, 32, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
@@ -415,7 +411,7 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 				take(slots + 8, side_of, k1, v1, k2);
 				take(sort_b, sort_tmp);
 			});
-			KLAUNCH(k_wk_slot_side, dim3(wblk(nS)), dim3(W_TPB), 0, s, nS, g.off, side_of);
+			KLAUNCH(k_wk_slot_side, dim3(lane_blocks(nS)), dim3(Q_TPB), 0, s, nS, g.off, side_of);
 			const unsigned bits = bits_for(nS);
 			sort_pairs_u32(g.aoth, k1, side_of, v1, slots, bits, sort_tmp, sort_b, s);
 			sort_pairs_u32(v1, k2, k1, ssucc, slots, bits, sort_tmp, sort_b, s);
@@ -427,11 +423,10 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 		WalkSink none{};
 		uint32_t n2 = 0;
 		if (n) {
-			KLAUNCH(k_wk_t1<false>, dim3(wblk(n)), dim3(W_TPB), 0, s, n, g.off, ssucc, ys, yz, c, force2 ? 1u : 0u, cntw, cnts,
+			KLAUNCH(k_wk_t1<false>, dim3(lane_blocks(n)), dim3(Q_TPB), 0, s, n, g.off, ssucc, ys, yz, c, force2 ? 1u : 0u, cntw, cnts,
 				status, handover, woff, sbase, none);
-			compact_flagged_u8(handover, n, list2, words + 1, comp_tmp, comp_b, s);
-			HIP_CHECK(copy_async(&n2, words + 1, 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
+			compact_flagged_u8(handover, n, list2, words + 1, tmp, tmp_b, s);
+			n2 = read_back(words + 1, s);
 		}
 		// tier-2 lanes: 2 L stack words + a path set of 2^tbits >= 2 L slots each, at most 16384 lanes and 256 MiB
 		uint32_t lanes = 0;
@@ -442,24 +437,20 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 			lanes = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)n2, 16384, (size_t(256) << 20) / (lane_words * 4)}));
 			carve(ctx->wk_out, [&](Spans &take) { take((size_t)lanes * lane_words, scratch); });
 			HIP_CHECK(hipMemsetAsync(scratch + (size_t)lanes * 2 * c.L, 0, (size_t)lanes * (lane_words - 2 * (size_t)c.L) * 4, s));
-			KLAUNCH(k_wk_t2<false>, dim3(wblk(lanes)), dim3(W_TPB), 0, s, list2, n2, words + 2, lanes, tbits, g.off, ssucc, ys, yz, c,
+			KLAUNCH(k_wk_t2<false>, dim3(lane_blocks(lanes)), dim3(Q_TPB), 0, s, list2, n2, words + 2, lanes, tbits, g.off, ssucc, ys, yz, c,
 				scratch, cntw, cnts, status, woff, sbase, none);
 		}
-		uint64_t ht[2] = {0, 0};
-		if (n)
-			totals_u32(cntw, cnts, n, tot, ht, s);
-		const uint64_t n_walks = ht[0], n_steps = ht[1];
-		if (n_walks >= 0xFFFFFFFFull || n_steps >= 0xFFFFFFFFull)
-			throw HipError("the walks do not fit 32-bit offsets: " + std::to_string(n_walks) + " walks, " + std::to_string(n_steps) +
-				       " steps (lower max_walks / max_steps)");
-
 		// ---- offsets, then the emit pass into them
+		uint64_t n_walks = 0, n_steps = 0;
 		uint32_t *step_off = nullptr, *step_id = nullptr;
 		uint8_t *step_or = nullptr;
 		if (n) {
-			HIP_CHECK(hipMemsetAsync(cntw + n, 0, 4, s));
-			HIP_CHECK(hipMemsetAsync(cnts + n, 0, 4, s));
-			scan_exclusive_u32_pair(cntw, woff, n1, cnts, sbase, n1, scan_tmp, scan_b, s);
+			counts_to_offsets(cntw, woff, cnts, sbase, n, tot, tmp, tmp_b, s, [&](const uint64_t *total) {
+				n_walks = total[0], n_steps = total[1];
+				if (n_walks >= 0xFFFFFFFFull || n_steps >= 0xFFFFFFFFull)
+					throw HipError("the walks do not fit 32-bit offsets: " + std::to_string(n_walks) + " walks, " + std::to_string(n_steps) +
+						       " steps (lower max_walks / max_steps)");
+			});
 			auto out = [&](Spans &take) {
 				if (lanes)
 					take((size_t)lanes * lane_words, scratch);
@@ -479,10 +470,10 @@ extern "C" povu_hip_walks *povu_hip_forest_walks(povu_hip_ctx *ctx, povu_hip_for
 			if (lanes)
 				HIP_CHECK(hipMemsetAsync(scratch + (size_t)lanes * 2 * c.L, 0, (size_t)lanes * (lane_words - 2 * (size_t)c.L) * 4, s));
 			WalkSink sink{step_off, step_id, step_or, g.vid, 0, 0, 0, 0};
-			KLAUNCH(k_wk_t1<true>, dim3(wblk(n)), dim3(W_TPB), 0, s, n, g.off, ssucc, ys, yz, c, 0u, cntw, cnts, status, handover,
+			KLAUNCH(k_wk_t1<true>, dim3(lane_blocks(n)), dim3(Q_TPB), 0, s, n, g.off, ssucc, ys, yz, c, 0u, cntw, cnts, status, handover,
 				woff, sbase, sink);
 			if (lanes)
-				KLAUNCH(k_wk_t2<true>, dim3(wblk(lanes)), dim3(W_TPB), 0, s, list2, n2, words + 3, lanes, tbits, g.off, ssucc, ys, yz, c,
+				KLAUNCH(k_wk_t2<true>, dim3(lane_blocks(lanes)), dim3(Q_TPB), 0, s, list2, n2, words + 3, lanes, tbits, g.off, ssucc, ys, yz, c,
 					scratch, cntw, cnts, status, woff, sbase, sink);
 		}
 

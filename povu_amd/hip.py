@@ -977,9 +977,9 @@ class HipDecomposer:
 
     # ---- parity hooks
     def debug_scan(self, a, op: int = 0, b=None):
-        """Unit-test hook: exclusive scan of `a` on the device (op 0 sum, 1 running max); with `b`, an
-        independent sum scan of `b` in the same launch."""
-        a = np.ascontiguousarray(a, dtype=np.uint32)
+        """Unit-test hook: exclusive scan of `a` on the device (op 0 sum, 1 running max, 2 sum of uint64 values);
+        with `b`, an independent sum scan of `b` in the same launch."""
+        a = np.ascontiguousarray(a, dtype=np.uint64 if op == 2 else np.uint32)
         out = np.empty_like(a)
         if b is None:
             rc = self._lib.povu_hip_debug_scan(self._ctx, op, a.ctypes.data, out.ctypes.data, a.size, None, None, 0)

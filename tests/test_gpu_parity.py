@@ -463,6 +463,18 @@ def test_single_pass_scans(hip, n):
         assert np.array_equal(got_a, want_sum.astype(np.uint32)) and np.array_equal(got_b, want_b.astype(np.uint32))
 
 
+@pytest.mark.parametrize("n", [1, 1023, 1024, 1025, 1024 * 1024 + 3])  # (1024 values a block; the last size takes two levels of block sums)
+def test_scan_exclusive_u64(hip, n):
+    """The device-wide exclusive u64 scan (the offsets of the variant calls) against numpy.cumsum in uint64; the values
+    are up to 2^40, so the running sum crosses 2^32 within the first few elements."""
+    a = np.random.default_rng(n).integers(0, 1 << 40, n, dtype=np.uint64)
+    want = np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(a, dtype=np.uint64)[:-1]])
+    assert n < 2 or int(want[-1]) >= 1 << 32
+    for _ in range(2):
+        got = hip.debug_scan(a, 2)
+        assert got.dtype == np.uint64 and np.array_equal(got, want)
+
+
 # ---- BASELINE.json full-size configurations
 def test_config2_chain_1m_nodes_bit_exact_vs_reference_md5(hip, golden_dir):
     a = json.load(open(os.path.join(golden_dir, "anchors.json")))
