@@ -377,6 +377,7 @@ typedef struct {
 } povu_hip_trav_opts;
 #define POVU_HIP_T_FORCE_TIER2 1u /* run every scan with the wave-per-scan kernel (tests) */
 #define POVU_HIP_T_INVERSIONS 2u  /* povu_hip_call only: SUBR records too ("Inversion calls"); ignored elsewhere */
+#define POVU_HIP_T_NESTED 4u	  /* povu_hip_call only: alleles modulo enclosed sites, levels and parents by geometry ("Nested calls") */
 #define POVU_HIP_TRAV_LONG 1u	  /* status bits per query: a scan would need more than max_steps steps */
 #define POVU_HIP_TRAV_STRAY 2u	  /* a scan met a boundary step that does not close it */
 #define POVU_HIP_TRAV_OPEN 4u	  /* a scan reached the end of its path */
@@ -436,6 +437,10 @@ typedef struct {
  * begins, n_steps its steps, ref_allele 0, n_alleles 2, one AC; its block holds REF (the run's bases) and then ALT (their
  * reverse complement), the AT strings every step of the run and the flipped steps backwards */
 #define POVU_HIP_CALL_SUBR 16u
+/* with POVU_HIP_T_NESTED: the site has fewer classes than exact alleles (the record hides enclosed variation; TANGLED too) /
+ * the `popped` profile kept the record although its level is above max_level, because its ancestors were popped */
+#define POVU_HIP_CALL_COLLAPSED 32u
+#define POVU_HIP_CALL_RESCUED 64u
 #define POVU_HIP_GT_MISSING 0xFFFFu
 typedef struct {
 	uint64_t n_records, n_slots, n_blocks, n_spelled, n_seq_bytes, n_at_bytes, n_refs;
@@ -459,6 +464,18 @@ typedef struct {
 	uint64_t n_inv_heads;	 /* run heads found */
 	uint64_t n_inv_long;	 /* runs of more than max_steps steps (dropped) */
 	uint64_t n_inv_tier2;	 /* runs the wave-per-run kernel extended (longer than 64 steps, or all with _T_FORCE_TIER2) */
+	/* per record.  Without POVU_HIP_T_NESTED: level = the site's height - 1, parent_query = POVU_HIP_NIL, ref_spelled =
+	 * block_off[block] + ref_allele and the counters 0.  With it ("Nested calls") ref_allele, n_alleles, gt and ac count
+	 * classes, a block holds one spelled allele per class (its representative) and REF is spelled allele ref_spelled: the
+	 * block's, or one of its own behind the flubble blocks when the reference's exact allele is not the representative */
+	const uint32_t *level;	      /* [n_records] LV; 0 for an inversion record */
+	const uint32_t *parent_query; /* [n_records] site of the enclosing record (PS), POVU_HIP_NIL: none */
+	const uint64_t *ref_spelled;  /* [n_records] */
+	uint64_t n_enclosed;	      /* records with a parent (before the profile drops any) */
+	uint64_t n_collapsed_sites;   /* called sites of two classes or more that have fewer classes than exact alleles */
+	uint64_t n_popped;	      /* `popped` profile: records reached and dropped as big */
+	uint64_t n_rescued;	      /* `popped` profile: records kept above max_level (POVU_HIP_CALL_RESCUED) */
+	uint64_t nested;	      /* 1: made with POVU_HIP_T_NESTED (the VCF carries PS) */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
@@ -469,6 +486,23 @@ typedef struct {
  * steps or run heads or more.  Free with povu_hip_calls_free. */
 povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
 			      const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, char *err, size_t errlen);
+/* The profiles of a nested call ("Nested calls"): what is kept of the flubble records, decided on the device before any
+ * allele is spelled (inversion records are always kept).  A length of 0 is no limit.  A record is big when its REF is
+ * longer than max_ref_length or any allele it writes is longer than max_allele_length.  _TOP_LEVEL_ONLY keeps level 0;
+ * _POPPED keeps the records that are reached (level <= max_level, or the parent is big and reached) and not big. */
+#define POVU_HIP_PROFILE_RAW_GRAPH 0u
+#define POVU_HIP_PROFILE_TOP_LEVEL_ONLY 1u
+#define POVU_HIP_PROFILE_POPPED 2u
+typedef struct {
+	uint32_t profile; /* POVU_HIP_PROFILE_* */
+	uint32_t max_level;
+	uint64_t max_ref_length, max_allele_length;
+} povu_hip_call_profile_opts;
+/* povu_hip_call under a profile (NULL: povu_hip_call itself).  A profile other than _RAW_GRAPH implies POVU_HIP_T_NESTED;
+ * an unknown profile is refused */
+povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+				      const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile,
+				      char *err, size_t errlen);
 void povu_hip_calls_free(povu_hip_calls *c);
 
 /*
@@ -541,6 +575,16 @@ void povu_hip_sites_free(povu_hip_sites *s);
  * povu_hip_buffer_free; NULL on arguments that do not belong together. */
 char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
 			 const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, size_t *len);
+/* ... of a call made under `profile` (POVU_HIP_PROFILE_*).  povu_hip_calls_vcf reads nothing behind n_inv_tier2 of `c` (a
+ * caller built against the struct of before stays valid) and writes the plain call's text; this entry reads the fields behind it.  A nested call's text
+ * carries one ##INFO line for PS behind the header and PS=<the parent's ID> behind LV of a record with a parent; under
+ * _TOP_LEVEL_ONLY every flubble record's ID gets `:top` and its INFO ORIGIN, PROFILE and PASSTHROUGH, under _POPPED a rescued
+ * record's ID gets `:rescued` and its INFO ORIGIN, PARENT, PROFILE, RESCUED_CHILD and POPPED_PARENT, any other ORIGIN,
+ * PROFILE and PASSTHROUGH; the ##INFO lines of those keys stand before the contig lines.  level, parent_query and
+ * ref_spelled may be NULL (a hand-made povu_hip_calls): then the plain call's values hold.  NULL for an unknown profile */
+char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
+				 const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, uint32_t profile,
+				 size_t *len);
 
 /* ---- measurement (bench.py, povu-stage-cost lines) ---- */
 typedef struct {

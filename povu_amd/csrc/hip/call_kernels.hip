@@ -16,7 +16,13 @@
 //   spelling           per (site, orientation) a record needs, every allele: lengths, u64 scans, then one wave per allele
 //                      copies the bases (reverse-complemented on '<' steps, lanes across a segment's bytes) and writes the
 //                      AT step string (lanes across steps, a wave prefix sum of their decimal widths).
+// With POVU_HIP_T_NESTED (INTEGRATION.md "Nested calls"; nest_kernels.hip) the steps from the kept sites on read classes where
+// they read alleles: `aoff`, `oa` and `afirst` below are then the class offsets of a site, the class of a traversal and the
+// first traversal of a class's representative.  What differs per record is kept per record (rstate): whether it is anchored
+// (REF is the reference's own exact allele, the ALTs the representatives), whether REF has no inner base, whether REF is
+// spelled on its own (an "extra" one-allele block behind the class blocks).  A block is a (site, anchored, orientation).
 #include "call_common.hpp"
+#include "nest_kernels.hpp"
 
 namespace povu_hip
 {
@@ -155,15 +161,70 @@ __global__ void k_cl_inner(uint32_t n_al, const uint32_t *__restrict__ afirst, c
 		atl[a] = w;
 	}
 }
-__global__ void k_cl_anchored(uint32_t n, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ aoff, const uint64_t *__restrict__ ilen,
-			      uint8_t *__restrict__ anchored)
+// alleles without an inner base, per kept site (a record is anchored when REF or one of its ALTs is such an allele)
+__global__ void k_cl_zero_len(uint32_t n, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ aoff, const uint64_t *__restrict__ ilen,
+			      uint32_t *__restrict__ zc)
 {
 	for (uint32_t q = blockIdx.x * Q_TPB + threadIdx.x; q < n; q += gridDim.x * Q_TPB) {
-		bool e = false;
+		uint32_t e = 0;
 		if (keep[q])
 			for (uint32_t a = aoff[q]; a < aoff[q + 1]; a++)
-				e |= ilen[a] == 0;
-		anchored[q] = e;
+				e += ilen[a] == 0;
+		zc[q] = e;
+	}
+}
+// nested: the kept sites with fewer classes than exact alleles
+__global__ void k_cl_collapsed(uint32_t n, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ exact_off, const uint32_t *__restrict__ aoff,
+			       uint8_t *__restrict__ collapsed, uint32_t *__restrict__ count)
+{
+	for (uint32_t q = blockIdx.x * Q_TPB + threadIdx.x; q < n; q += gridDim.x * Q_TPB) {
+		const bool c = keep[q] && aoff[q + 1] - aoff[q] < exact_off[q + 1] - exact_off[q];
+		collapsed[q] = c;
+		if (c)
+			atomicAdd(count, 1u);
+	}
+}
+static constexpr uint8_t RS_ANCHORED = 1, RS_REF_EMPTY = 2, RS_OWN_REF = 4;
+// per flubble record j (before the sort): rstate; the inner bases and AT width of its REF (xilen, xatl: the reference's own
+// exact allele); with want_len the written lengths of REF and of its longest allele.  crep == NULL: not nested (alleles, REF
+// always the block's).
+__global__ void k_cl_rec_state(uint32_t nfl, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ exact_oa,
+			       const uint32_t *__restrict__ exact_off, const uint32_t *__restrict__ oa, const uint32_t *__restrict__ aoff,
+			       const uint32_t *__restrict__ crep, const uint8_t *__restrict__ orv, const uint64_t *__restrict__ rpos,
+			       const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ steps, const uint64_t *__restrict__ seq_off,
+			       const uint32_t *__restrict__ vid, const uint64_t *__restrict__ ilen, const uint64_t *__restrict__ atl,
+			       const uint32_t *__restrict__ zc, uint32_t want_len, uint8_t *__restrict__ rstate, uint64_t *__restrict__ xilen,
+			       uint64_t *__restrict__ xatl, uint64_t *__restrict__ ref_len, uint64_t *__restrict__ max_len)
+{
+	for (uint32_t j = blockIdx.x * Q_TPB + threadIdx.x; j < nfl; j += gridDim.x * Q_TPB) {
+		const uint32_t t = rlist[j], q = rq[t], ec = aoff[q] + oa[t], len = rlen[t];
+		const uint64_t p = rpos[t] & ~ROLE_BIT;
+		const bool rev = (rpos[t] & ROLE_BIT) != 0;
+		const bool own = crep && crep[ec] != exact_off[q] + exact_oa[t];
+		uint64_t b = ilen[ec], w = atl[ec];
+		if (own) {
+			b = w = 0;
+			for (uint32_t k = 1; k + 1 < len; k++) {
+				const uint32_t v = trav_step(steps, p, len, rev, k) >> 1;
+				b += seq_off[v + 1] - seq_off[v];
+				w += 1 + ndig(vid[v]);
+			}
+		}
+		const bool anch = b == 0 || zc[q] - (ilen[ec] == 0 ? 1u : 0u) > 0;
+		rstate[j] = (anch ? RS_ANCHORED : 0) | (b == 0 ? RS_REF_EMPTY : 0) | (own ? RS_OWN_REF : 0);
+		xilen[j] = b;
+		xatl[j] = w;
+		if (want_len) {
+			// the anchor step is the site's boundary the reference enters by, whatever the allele
+			const uint32_t v = (orv[t] ? trav_step(steps, p, len, rev, len - 1) : trav_step(steps, p, len, rev, 0)) >> 1;
+			const uint64_t ab = anch && seq_off[v + 1] > seq_off[v] ? 1 : 0;
+			uint64_t mx = b;
+			for (uint32_t a = aoff[q]; a < aoff[q + 1]; a++)
+				if (a != ec)
+					mx = max(mx, ilen[a]);
+			ref_len[j] = b + ab;
+			max_len[j] = mx + ab;
+		}
 	}
 }
 
@@ -189,14 +250,12 @@ __global__ void k_cl_rec_flag(uint32_t R, const uint32_t *__restrict__ rq, const
 }
 __global__ void k_cl_pos(uint32_t nrec, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ op,
 			 const uint32_t *__restrict__ of, const uint32_t *__restrict__ ref_of_path, const uint64_t *__restrict__ ref_base,
-			 const uint64_t *__restrict__ roff, const uint8_t *__restrict__ anchored, uint64_t *__restrict__ pos,
-			 uint32_t *__restrict__ perm)
+			 const uint64_t *__restrict__ roff, const uint8_t *__restrict__ rstate, uint64_t *__restrict__ pos)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		const uint32_t t = rlist[i];
 		const uint64_t b = ref_base[ref_of_path[op[t]]];
-		pos[i] = roff[b + of[t] + 1] - roff[b] + (anchored[rq[t]] ? 0 : 1);
-		perm[i] = i;
+		pos[i] = roff[b + of[t] + 1] - roff[b] + ((rstate[i] & RS_ANCHORED) ? 0 : 1);
 	}
 }
 // sort key of record perm[i]: 0 = POS low word, 1 = POS high word, 2 = reference
@@ -216,10 +275,15 @@ __global__ void k_cl_rec_fields(uint32_t nrec, const uint32_t *__restrict__ perm
 				const uint32_t *__restrict__ oa, const uint8_t *__restrict__ orv, const uint32_t *__restrict__ aoff,
 				uint32_t *__restrict__ o_q, uint32_t *__restrict__ o_path, uint32_t *__restrict__ o_first,
 				uint32_t *__restrict__ o_ref, uint32_t *__restrict__ o_nal, uint64_t *__restrict__ o_pos, uint64_t *__restrict__ nalt,
-				uint32_t *__restrict__ need, const uint32_t *__restrict__ dst)
+				uint32_t *__restrict__ need, const uint32_t *__restrict__ dst, const uint8_t *__restrict__ rstate,
+				const uint32_t *__restrict__ height, const uint32_t *__restrict__ n_level, const uint32_t *__restrict__ n_parent,
+				uint32_t *__restrict__ o_level, uint32_t *__restrict__ o_parent, uint32_t *__restrict__ xneed)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		const uint32_t j = perm[i], t = rlist[j], q = rq[t], d = dst ? dst[i] : i;
+		o_level[d] = n_level ? n_level[j] : height[q] - 1;
+		o_parent[d] = n_parent ? n_parent[j] : NO_QUERY;
+		xneed[i] = (rstate[j] & RS_OWN_REF) ? 1 : 0;
 		o_q[d] = q;
 		o_path[d] = op[t];
 		o_first[d] = of[t];
@@ -227,7 +291,7 @@ __global__ void k_cl_rec_fields(uint32_t nrec, const uint32_t *__restrict__ perm
 		o_nal[d] = aoff[q + 1] - aoff[q];
 		o_pos[d] = pos[j];
 		nalt[d] = aoff[q + 1] - aoff[q] - 1;
-		need[2 * (size_t)q + orv[t]] = 1;
+		need[4 * (size_t)q + ((rstate[j] & RS_ANCHORED) ? 2 : 0) + orv[t]] = 1;
 	}
 }
 // reference number and POS of the sorted records (the inversion records are merged in by them)
@@ -247,8 +311,9 @@ __global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, const uint3
 						      const uint32_t *__restrict__ slot_of_path, const uint32_t *__restrict__ slot_first,
 						      uint32_t n_samples, uint32_t S, const uint32_t *__restrict__ smin,
 						      const uint32_t *__restrict__ smax, const uint64_t *__restrict__ ac_off,
-						      const uint32_t *__restrict__ qstatus, const uint8_t *__restrict__ anchored,
-						      const uint32_t *__restrict__ aoff, const uint64_t *__restrict__ ilen, uint16_t *__restrict__ gt,
+						      const uint32_t *__restrict__ qstatus, const uint32_t *__restrict__ perm,
+						      const uint8_t *__restrict__ rstate, const uint8_t *__restrict__ collapsed,
+						      const uint8_t *__restrict__ rescued, uint16_t *__restrict__ gt,
 						      uint32_t *__restrict__ ac, uint32_t *__restrict__ an, uint32_t *__restrict__ ns,
 						      uint8_t *__restrict__ flags, const uint32_t *__restrict__ dst)
 {
@@ -288,10 +353,15 @@ __global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, const uint3
 			an[i] = n_an;
 			ns[i] = n_ns;
 			uint8_t f = 0;
-			if (anchored[q])
-				f |= POVU_HIP_CALL_ANCHORED | (ilen[aoff[q] + ra] == 0 ? POVU_HIP_CALL_INS : POVU_HIP_CALL_DEL);
+			const uint32_t j = perm[i0];
+			if (rstate[j] & RS_ANCHORED)
+				f |= POVU_HIP_CALL_ANCHORED | ((rstate[j] & RS_REF_EMPTY) ? POVU_HIP_CALL_INS : POVU_HIP_CALL_DEL);
 			if (qstatus[q] || amb)
 				f |= POVU_HIP_CALL_TANGLED;
+			if (collapsed && collapsed[q])
+				f |= POVU_HIP_CALL_TANGLED | POVU_HIP_CALL_COLLAPSED;
+			if (rescued && rescued[j])
+				f |= POVU_HIP_CALL_RESCUED;
 			flags[i] = f;
 		}
 	}
@@ -305,17 +375,37 @@ __global__ void k_cl_blocks(uint64_t n2, const uint32_t *__restrict__ need, cons
 }
 __global__ void k_cl_rec_block(uint32_t nrec, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rlist,
 			       const uint32_t *__restrict__ rq, const uint8_t *__restrict__ orv, const uint32_t *__restrict__ boff,
-			       uint32_t *__restrict__ o_block, const uint32_t *__restrict__ dst)
+			       uint32_t *__restrict__ o_block, const uint32_t *__restrict__ dst, const uint8_t *__restrict__ rstate,
+			       const uint32_t *__restrict__ xoff, uint32_t *__restrict__ xrow)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
-		const uint32_t t = rlist[perm[i]];
-		o_block[dst ? dst[i] : i] = boff[2 * (size_t)rq[t] + orv[t]];
+		const uint32_t j = perm[i], t = rlist[j], d = dst ? dst[i] : i;
+		o_block[d] = boff[4 * (size_t)rq[t] + ((rstate[j] & RS_ANCHORED) ? 2 : 0) + orv[t]];
+		xrow[d] = (rstate[j] & RS_OWN_REF) ? xoff[i] : NO_QUERY;
 	}
+}
+// the extra blocks (one spelled allele each: the REF of a record that is not its class's representative) and their records
+__global__ void k_cl_extra(uint32_t nrec, const uint32_t *__restrict__ perm, const uint8_t *__restrict__ rstate, const uint32_t *__restrict__ xoff,
+			   uint32_t *__restrict__ xlist, uint64_t *__restrict__ xcnt)
+{
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB)
+		if (rstate[perm[i]] & RS_OWN_REF) {
+			xlist[xoff[i]] = perm[i];
+			xcnt[xoff[i]] = 1;
+		}
+}
+// REF among the spelled alleles: the extra block's one allele, or allele ref_allele of the record's block
+__global__ void k_cl_ref_spelled(uint32_t nrec, const uint32_t *__restrict__ o_block, const uint32_t *__restrict__ o_ref,
+				 const uint32_t *__restrict__ xrow, const uint64_t *__restrict__ block_off, uint32_t nfb,
+				 uint64_t *__restrict__ ref_spelled)
+{
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB)
+		ref_spelled[i] = xrow[i] != NO_QUERY ? block_off[nfb + xrow[i]] : block_off[o_block[i]] + o_ref[i];
 }
 __global__ void k_cl_block_cnt(uint32_t nb, const uint32_t *__restrict__ blist, const uint32_t *__restrict__ aoff, uint64_t *__restrict__ cnt)
 {
 	for (uint32_t b = blockIdx.x * Q_TPB + threadIdx.x; b < nb; b += gridDim.x * Q_TPB) {
-		const uint32_t q = blist[b] >> 1;
+		const uint32_t q = blist[b] >> 2;
 		cnt[b] = aoff[q + 1] - aoff[q];
 	}
 }
@@ -323,20 +413,45 @@ __global__ void k_cl_block_cnt(uint32_t nb, const uint32_t *__restrict__ blist, 
 // what spelled allele j is: its block's site and orientation, its global allele, the first step in the reference's
 // direction (the anchor step)
 struct Spelled {
-	uint32_t q, o, a, t, len, first;
-	uint64_t p;
-	bool rev;
+	uint32_t q, o, t, len, first;
+	uint64_t p, ilen, atl;
+	bool rev, anch;
 };
-__device__ __forceinline__ Spelled spelled(uint64_t j, uint32_t nb, const uint64_t *__restrict__ block_off, const uint32_t *__restrict__ blist,
-					   const uint32_t *__restrict__ aoff, const uint32_t *__restrict__ afirst, const uint64_t *__restrict__ rpos,
-					   const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ steps)
+// the tables a spelled allele is found in: nb blocks of which the first nfb are (site, anchored, orientation) blocks with an
+// allele each of the site, the others extra blocks with the one allele of record xlist[.]
+struct SpellTab {
+	uint32_t nb, nfb;
+	const uint64_t *block_off;
+	const uint32_t *blist, *aoff, *afirst, *xlist, *rlist, *rq;
+	const uint8_t *orv, *rstate;
+	const uint64_t *rpos;
+	const uint32_t *rlen, *steps;
+	const uint64_t *ilen, *atl, *xilen, *xatl;
+};
+__device__ __forceinline__ Spelled spelled(uint64_t j, const SpellTab &T)
 {
 	Spelled s;
-	const uint32_t b = span_of(block_off, nb, j);
-	s.q = blist[b] >> 1;
-	s.o = blist[b] & 1u;
-	s.a = aoff[s.q] + (uint32_t)(j - block_off[b]);
-	s.t = afirst[s.a];
+	const uint32_t b = span_of(T.block_off, T.nb, j);
+	const uint32_t *__restrict__ steps = T.steps;
+	if (b < T.nfb) {
+		s.q = T.blist[b] >> 2;
+		s.anch = (T.blist[b] & 2u) != 0;
+		s.o = T.blist[b] & 1u;
+		const uint32_t a = T.aoff[s.q] + (uint32_t)(j - T.block_off[b]);
+		s.t = T.afirst[a];
+		s.ilen = T.ilen[a];
+		s.atl = T.atl[a];
+	} else {
+		const uint32_t r = T.xlist[b - T.nfb];
+		s.t = T.rlist[r];
+		s.q = T.rq[s.t];
+		s.anch = (T.rstate[r] & RS_ANCHORED) != 0;
+		s.o = T.orv[s.t];
+		s.ilen = T.xilen[r];
+		s.atl = T.xatl[r];
+	}
+	const uint64_t *__restrict__ rpos = T.rpos;
+	const uint32_t *__restrict__ rlen = T.rlen;
 	s.p = rpos[s.t] & ~ROLE_BIT;
 	s.rev = (rpos[s.t] & ROLE_BIT) != 0;
 	s.len = rlen[s.t];
@@ -349,36 +464,30 @@ __device__ __forceinline__ uint32_t inner_step(const Spelled &s, const uint32_t 
 	return s.o ? trav_step(steps, s.p, s.len, s.rev, s.len - 2 - k) ^ 1u : trav_step(steps, s.p, s.len, s.rev, k + 1);
 }
 
-__global__ void k_cl_spell_len(uint64_t nsp, uint32_t nb, const uint64_t *__restrict__ block_off, const uint32_t *__restrict__ blist,
-			       const uint32_t *__restrict__ aoff, const uint32_t *__restrict__ afirst, const uint64_t *__restrict__ rpos,
-			       const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ steps, const uint64_t *__restrict__ seq_off,
-			       const uint32_t *__restrict__ vid, const uint64_t *__restrict__ ilen, const uint64_t *__restrict__ atl,
-			       const uint8_t *__restrict__ anchored, uint64_t *__restrict__ slen, uint64_t *__restrict__ alen)
+__global__ void k_cl_spell_len(uint64_t nsp, SpellTab T, const uint64_t *__restrict__ seq_off, const uint32_t *__restrict__ vid,
+			       uint64_t *__restrict__ slen, uint64_t *__restrict__ alen)
 {
 	for (uint64_t j = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; j < nsp; j += (uint64_t)gridDim.x * Q_TPB) {
-		const Spelled s = spelled(j, nb, block_off, blist, aoff, afirst, rpos, rlen, steps);
+		const Spelled s = spelled(j, T);
 		const uint32_t v = s.first >> 1;
-		const bool an = anchored[s.q];
-		slen[j] = ilen[s.a] + (an && seq_off[v + 1] > seq_off[v] ? 1 : 0);
-		alen[j] = atl[s.a] + (an ? 1 + ndig(vid[v]) : 0);
+		const bool an = s.anch;
+		slen[j] = s.ilen + (an && seq_off[v + 1] > seq_off[v] ? 1 : 0);
+		alen[j] = s.atl + (an ? 1 + ndig(vid[v]) : 0);
 	}
 }
 
 // one wave per spelled allele: the bases, then the AT string
-__global__ __launch_bounds__(Q_TPB) void k_cl_emit(uint64_t nsp, uint32_t nb, const uint64_t *__restrict__ block_off,
-						   const uint32_t *__restrict__ blist, const uint32_t *__restrict__ aoff,
-						   const uint32_t *__restrict__ afirst, const uint64_t *__restrict__ rpos,
-						   const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ steps,
-						   const uint64_t *__restrict__ seq_off, const char *__restrict__ seq, const uint32_t *__restrict__ vid,
-						   const uint8_t *__restrict__ anchored, const uint64_t *__restrict__ s_off,
+__global__ __launch_bounds__(Q_TPB) void k_cl_emit(uint64_t nsp, SpellTab T, const uint64_t *__restrict__ seq_off, const char *__restrict__ seq,
+						   const uint32_t *__restrict__ vid, const uint64_t *__restrict__ s_off,
 						   const uint64_t *__restrict__ a_off, char *__restrict__ o_seq, char *__restrict__ o_at,
 						   unsigned long long *__restrict__ bad)
 {
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint64_t waves = (uint64_t)gridDim.x * (Q_TPB / 64);
 	for (uint64_t j = (uint64_t)blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); j < nsp; j += waves) {
-		const Spelled s = spelled(j, nb, block_off, blist, aoff, afirst, rpos, rlen, steps);
-		const bool an = anchored[s.q];
+		const Spelled s = spelled(j, T);
+		const bool an = s.anch;
+		const uint32_t *__restrict__ steps = T.steps;
 		uint64_t w = s_off[j], wa = a_off[j];
 		const uint32_t m = s.len - 2; // inner steps
 		// the anchor: last base of the first step, and its step text
@@ -450,8 +559,8 @@ namespace
 {
 struct CallsOwner {
 	povu_hip_calls view{}; // first member: the owner is recovered from it in povu_hip_calls_free
-	PinnedVec<uint32_t> query, path, first, ref_allele, n_alleles, an, ns, block, ac, n_steps;
-	PinnedVec<uint64_t> pos, ac_off, block_off, seq_off, at_off;
+	PinnedVec<uint32_t> query, path, first, ref_allele, n_alleles, an, ns, block, ac, n_steps, level, parent_query;
+	PinnedVec<uint64_t> pos, ac_off, block_off, seq_off, at_off, ref_spelled;
 	PinnedVec<uint8_t> flags;
 	PinnedVec<uint16_t> gt;
 	PinnedVec<char> seq, at;
@@ -467,7 +576,8 @@ struct CallInputs {
 	const uint32_t *slot_of_path;
 	const povu_hip_trav_opts *opts;
 	uint32_t n, P, nR, S, NS, n_trees = 0;
-	bool inversions;
+	bool inversions, nested;
+	povu_hip_call_profile_opts prof; // (raw-graph without a profile)
 	std::vector<uint32_t> ref_of_path, slot_first, qa, qz; // reference number of every path (NO_QUERY: none), first slot of every sample, the queries
 	std::vector<uint8_t> qor;
 };
@@ -478,7 +588,17 @@ struct CallWs {
 	uint64_t *d_ref_base, *rlen64, *roff, *ilen, *atl, *s64;
 	uint32_t *d_ref_path, *d_ref_of_path, *d_slot, *d_slot_first, *d_parent, *d_tree, *scnt, *soffv, *scur, *sval, *qv, *hit, *pres, *keep, *qidx,
 		*words;
-	uint8_t *d_fam, *callable, *called, *anchored, *rflag;
+	uint8_t *d_fam, *callable, *called, *rflag;
+	uint32_t *zc, *d_height; // per site: alleles without an inner base, PVST height
+	// what the steps from the kept sites on read as alleles: the exact alleles, or with POVU_HIP_T_NESTED the classes (crep: the
+	// exact allele that represents a class, else null)
+	const uint32_t *aoff, *oa, *afirst, *crep = nullptr;
+	uint32_t n_eal = 0;
+	NestClasses nc;
+	NestRecs nr;
+	uint8_t *collapsed, *rstate;		    // per site / per flubble record before the sort (RS_*)
+	uint64_t *xilen, *xatl, *ref_len, *max_len; // per flubble record: its own REF's inner bases and AT width, its written lengths
+	uint32_t nfl_all = 0, n_collapsed = 0;	    // flubble records before the profile dropped any
 	uint32_t *rlist, *perm, *perm2, *key, *key2; // perm: the flubble records sorted by (reference, POS), once flubble_records has run
 	uint64_t *pos;
 	void *tmp;
@@ -494,7 +614,9 @@ struct CallInv {
 };
 // cl_rec: the per-record arrays and the spelling's inputs
 struct CallRecs {
-	uint32_t nrec = 0, nb = 0, nfb = 0; // records; blocks: all, those of the flubble records
+	uint32_t nrec = 0, nb = 0, nfb = 0, nfc = 0; // records; blocks: all, those of the flubble records, of these the class blocks
+	uint32_t *xneed, *xoff, *xlist, *xrow, *o_level, *o_parent; // the extra blocks (REFs spelled on their own)
+	uint64_t *ref_spelled;
 	uint64_t n_ac = 0, nsp = 0, nfsp = 0; // ALT counts; spelled alleles: all, those of the flubble blocks
 	InvRows rows;
 	uint32_t *need, *boff, *blist;
@@ -511,7 +633,7 @@ struct CallSpelled {
 
 // the host-side refusals and the host tables
 CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs, const uint32_t *slot_of_path,
-			     const povu_hip_trav_opts *opts)
+			     const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile)
 {
 	if (!ctx || !sites || !refs)
 		throw HipError("null context, sites or references");
@@ -524,6 +646,10 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 	CallInputs in{sites, refs, slot_of_path, opts, sites->n, ctx->n_paths, refs->n_refs, refs->n_slots, refs->n_samples};
 	const uint32_t n = in.n, P = in.P, nR = in.nR, S = in.S, NS = in.NS;
 	in.inversions = opts && (opts->flags & POVU_HIP_T_INVERSIONS);
+	in.prof = profile ? *profile : povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
+	if (in.prof.profile > POVU_HIP_PROFILE_POPPED)
+		throw HipError("unknown profile " + std::to_string(in.prof.profile));
+	in.nested = (opts && (opts->flags & POVU_HIP_T_NESTED)) || in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH;
 	if (n >= 0x7FFFFFFFu)
 		throw HipError("too many sites");
 	if (n && (!sites->id1 || !sites->id2 || !sites->or1 || !sites->or2 || !sites->parent || !sites->family || !sites->tree))
@@ -579,14 +705,14 @@ void reference_offsets(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice
 		take((size_t)nR + 1, w.d_ref_base, w.d_ref_path);
 		take((size_t)P + 1, w.d_ref_of_path, w.d_slot);
 		take((size_t)NS + 1, w.d_slot_first);
-		take(n1, w.d_parent, w.d_tree, w.d_fam, w.callable, w.called, w.anchored, w.keep, w.qidx);
+		take(n1, w.d_parent, w.d_tree, w.d_fam, w.callable, w.called, w.zc, w.d_height, w.collapsed, w.keep, w.qidx);
 		take(NR + 1, w.rlen64, w.roff);
 		take((size_t)g.V + 1, w.scnt, w.soffv, w.scur);
 		take(2 * n1, w.sval, w.qv);
 		take(hit_words, w.hit);
 		take(pres_words, w.pres);
 		take((size_t)d.n_al + 1, w.ilen, w.atl);
-		take((size_t)R + 1, w.rflag, w.rlist, w.perm, w.perm2, w.key, w.key2, w.pos);
+		take((size_t)R + 1, w.rflag, w.rlist, w.perm, w.perm2, w.key, w.key2, w.pos, w.rstate, w.xilen, w.xatl, w.ref_len, w.max_len);
 		take(scan_exclusive_u64_tmp(std::max<uint64_t>(NR + 1, 1)), w.s64);
 		take(8, w.words);
 		take(w.tmp_bytes, w.tmp);
@@ -602,6 +728,10 @@ void reference_offsets(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice
 		HIP_CHECK(copy_async(w.d_parent, in.sites->parent, (size_t)n * 4, hipMemcpyHostToDevice, s));
 		HIP_CHECK(copy_async(w.d_tree, in.sites->tree, (size_t)n * 4, hipMemcpyHostToDevice, s));
 		HIP_CHECK(copy_async(w.d_fam, in.sites->family, n, hipMemcpyHostToDevice, s));
+		if (in.sites->height)
+			HIP_CHECK(copy_async(w.d_height, in.sites->height, (size_t)n * 4, hipMemcpyHostToDevice, s));
+		else
+			HIP_CHECK(hipMemsetAsync(w.d_height, 0, (size_t)n * 4, s));
 	}
 	HIP_CHECK(hipMemsetAsync(w.words, 0, 32, s));
 	HIP_CHECK(hipMemsetAsync(w.scnt, 0, ((size_t)g.V + 1) * 4, s));
@@ -616,14 +746,13 @@ void reference_offsets(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice
 	scan_exclusive_u64(w.rlen64, w.roff, NR + 1, w.s64, s);
 }
 
-// the called sites, those kept (two alleles or more), their alleles' inner lengths
+// the called sites
 void callability(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
 {
 	const ResidentGraph &g = ctx->g;
 	hipStream_t s = ctx->stream;
-	const uint32_t n = in.n, nR = in.nR, n_al = d.n_al;
+	const uint32_t n = in.n, nR = in.nR;
 	const uint64_t NR = w.NR;
-	const size_t n1 = (size_t)n + 1;
 	if (n) {
 		KLAUNCH(k_cl_seg_count, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, d.q.qa, d.q.qz, g.vid, g.V, w.scnt, w.qv);
 		scan_exclusive_u32(w.scnt, w.soffv, (size_t)g.V + 1, w.tmp, w.tmp_bytes, s);
@@ -635,7 +764,27 @@ void callability(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, C
 		KLAUNCH(k_cl_callable, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, nR, w.hit, w.pres, w.d_tree, w.d_parent, w.d_fam, w.callable, w.called);
 		KLAUNCH(k_cl_unparent, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.callable, w.d_parent, w.called);
 	}
-	KLAUNCH(k_cl_keep, dim3(stride_blocks(n1)), dim3(Q_TPB), 0, s, n, w.called, d.aoff, w.keep, w.words + 1);
+}
+
+// what the rest of the call reads as the alleles of a site: the exact alleles, or the classes of a nested call
+void site_classes(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
+{
+	w.aoff = d.aoff, w.oa = d.oa, w.afirst = d.afirst, w.n_eal = d.n_al;
+	if (!in.nested)
+		return;
+	w.nc = nest_classes(ctx, d, w.called, in.opts && in.opts->max_steps ? in.opts->max_steps : 65536,
+			    in.opts && (in.opts->flags & POVU_HIP_T_FORCE_TIER2));
+	w.aoff = w.nc.coff, w.oa = w.nc.oc, w.afirst = w.nc.cfirst, w.crep = w.nc.crep, w.n_eal = w.nc.n_cl;
+}
+
+// the sites kept (called, two alleles or more), their alleles' inner lengths
+void kept_sites(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
+{
+	const ResidentGraph &g = ctx->g;
+	hipStream_t s = ctx->stream;
+	const uint32_t n = in.n, n_al = w.n_eal;
+	const size_t n1 = (size_t)n + 1;
+	KLAUNCH(k_cl_keep, dim3(stride_blocks(n1)), dim3(Q_TPB), 0, s, n, w.called, w.aoff, w.keep, w.words + 1);
 	scan_exclusive_u32(w.keep, w.qidx, n1, w.tmp, w.tmp_bytes, s);
 	uint32_t hw[2] = {0, 0};
 	HIP_CHECK(copy_async(hw, w.qidx + n, 4, hipMemcpyDeviceToHost, s));
@@ -645,11 +794,15 @@ void callability(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, C
 	if (hw[1] > MAX_ALLELES)
 		throw HipError("a called site has " + std::to_string(hw[1]) + " alleles: more than 65534 in one record are refused");
 	if (n_al) {
-		KLAUNCH(k_cl_inner, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, d.afirst, d.rq, w.keep, d.rpos, d.rlen, ctx->path_steps, ctx->seq_off, g.vid,
+		KLAUNCH(k_cl_inner, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, w.afirst, d.rq, w.keep, d.rpos, d.rlen, ctx->path_steps, ctx->seq_off, g.vid,
 			w.ilen, w.atl);
 	}
 	if (n)
-		KLAUNCH(k_cl_anchored, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, d.aoff, w.ilen, w.anchored);
+		KLAUNCH(k_cl_zero_len, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, w.aoff, w.ilen, w.zc);
+	if (n && in.nested) {
+		KLAUNCH(k_cl_collapsed, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, d.aoff, w.aoff, w.collapsed, w.words + 3);
+		w.n_collapsed = read_back(w.words + 3, s);
+	}
 }
 
 // per kept site and genotype slot, the min and max allele
@@ -661,7 +814,7 @@ void slot_table(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, Ca
 	HIP_CHECK(hipMemsetAsync(w.smin, 0xFF, cells * 4, s));
 	HIP_CHECK(hipMemsetAsync(w.smax, 0, cells * 4, s));
 	if (d.R && w.nQ)
-		KLAUNCH(k_cl_slots, dim3(stride_blocks(d.R)), dim3(Q_TPB), 0, s, d.R, d.rq, d.op, d.oa, w.keep, w.qidx, w.d_slot, in.S, w.smin, w.smax);
+		KLAUNCH(k_cl_slots, dim3(stride_blocks(d.R)), dim3(Q_TPB), 0, s, d.R, d.rq, d.op, w.oa, w.keep, w.qidx, w.d_slot, in.S, w.smin, w.smax);
 }
 
 // flag, compact, POS, the sort by (reference, POS)
@@ -674,13 +827,32 @@ void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &
 		compact_flagged_u8(w.rflag, R, w.rlist, w.words + 2, w.tmp, w.tmp_bytes, s);
 		w.nfl = read_back(w.words + 2, s);
 	}
-	const uint32_t nfl = w.nfl;
-	refuse_2_32(nfl, "the call needs ", "records");
+	const uint32_t nfl_all = w.nfl_all = w.nfl;
+	refuse_2_32(nfl_all, "the call needs ", "records");
 	const uint64_t ref_bases = read_back(w.roff + w.NR, s);
+	if (!nfl_all)
+		return;
+	// per record: anchored, REF's own lengths; POS; with POVU_HIP_T_NESTED parents, levels and the profile's choice
+	const bool filter = in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH;
+	KLAUNCH(k_cl_rec_state, dim3(stride_blocks(nfl_all)), dim3(Q_TPB), 0, s, nfl_all, w.rlist, d.rq, d.oa, d.aoff, w.oa, w.aoff, w.crep, d.orv, d.rpos, d.rlen,
+		ctx->path_steps, ctx->seq_off, ctx->g.vid, w.ilen, w.atl, w.zc, filter ? 1u : 0u, w.rstate, w.xilen, w.xatl, w.ref_len, w.max_len);
+	KLAUNCH(k_cl_pos, dim3(stride_blocks(nfl_all)), dim3(Q_TPB), 0, s, nfl_all, w.rlist, d.rq, d.op, d.of, w.d_ref_of_path, w.d_ref_base, w.roff, w.rstate,
+		w.pos);
+	if (in.nested) {
+		NestRecIn ri;
+		ri.nfl = nfl_all, ri.rlist = w.rlist, ri.height = w.d_height, ri.ref_len = w.ref_len, ri.max_len = w.max_len;
+		ri.profile = in.prof.profile, ri.max_level = in.prof.max_level;
+		ri.max_ref_length = in.prof.max_ref_length, ri.max_allele_length = in.prof.max_allele_length;
+		w.nr = nest_records(ctx, d, w.nc.ix, ri);
+		w.nfl = w.nr.n_kept;
+		if (w.nfl)
+			HIP_CHECK(copy_async(w.perm, w.nr.kept, (size_t)w.nfl * 4, hipMemcpyDeviceToDevice, s));
+	} else {
+		launch_iota(nfl_all, w.perm, s);
+	}
+	const uint32_t nfl = w.nfl;
 	if (!nfl)
 		return;
-	KLAUNCH(k_cl_pos, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.rlist, d.rq, d.op, d.of, w.d_ref_of_path, w.d_ref_base, w.roff, w.anchored, w.pos,
-		w.perm);
 	LsdSort sort{w.perm, w.perm2, w.key, w.key2, nfl, w.tmp, w.tmp_bytes, s};
 	auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
 		KLAUNCH(k_cl_key, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, which, perm, w.rlist, d.op, w.d_ref_of_path, w.pos, k);
@@ -724,37 +896,52 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d,
 	hipStream_t s = ctx->stream;
 	const uint32_t n = in.n, nfl = w.nfl, nrec = r.nrec;
 	const InvDevice &iv = inv.v;
-	const size_t r1 = (size_t)nrec + 1, n2 = 2 * (size_t)n + 1;
+	const size_t r1 = (size_t)nrec + 1, n2 = 4 * (size_t)n + 1, f1 = (size_t)nfl + 1;
 	InvRows &o = r.rows;
 	uint64_t *s64;
 	carve(ctx->cl_rec, [&](Spans &take) {
 		take(r1, o.o_q, o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_an, o.o_ns, o.o_block, o.o_nsteps, o.o_pos, o.nalt, r.ac_off, o.o_flags);
+		take(r1, r.o_level, r.o_parent, r.xrow, r.ref_spelled);
+		take(f1, r.xneed, r.xoff, r.xlist);
 		take((size_t)nrec * in.S + 1, o.gt);
 		take(n2, r.need, r.boff, r.blist);
-		take(n2 + iv.n, r.bcnt, r.block_off);
-		take(scan_exclusive_u64_tmp(std::max(r1, n2 + iv.n)), s64);
+		take(n2 + nfl + iv.n, r.bcnt, r.block_off);
+		take(scan_exclusive_u64_tmp(std::max(r1, n2 + nfl + iv.n)), s64);
 	});
 	HIP_CHECK(hipMemsetAsync(o.o_nsteps, 0, r1 * 4, s));
 	HIP_CHECK(hipMemsetAsync(r.need, 0, n2 * 4, s));
 	HIP_CHECK(hipMemsetAsync(o.nalt + nrec, 0, 8, s));
+	HIP_CHECK(hipMemsetAsync(r.o_level, 0, r1 * 4, s));
+	HIP_CHECK(hipMemsetAsync(r.o_parent, 0xFF, r1 * 4, s));
+	HIP_CHECK(hipMemsetAsync(r.xrow, 0xFF, r1 * 4, s));
+	HIP_CHECK(hipMemsetAsync(r.xneed, 0, f1 * 4, s));
 	if (nfl)
-		KLAUNCH(k_cl_rec_fields, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, w.pos, d.rq, d.op, d.of, d.oa, d.orv, d.aoff, o.o_q,
-			o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_pos, o.nalt, r.need, inv.f_dst);
+		KLAUNCH(k_cl_rec_fields, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, w.pos, d.rq, d.op, d.of, w.oa, d.orv, w.aoff, o.o_q,
+			o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_pos, o.nalt, r.need, inv.f_dst, w.rstate, w.d_height, in.nested ? w.nr.level : nullptr,
+			in.nested ? w.nr.parent_q : nullptr, r.o_level, r.o_parent, r.xneed);
 	inv_fields(ctx, inv.in, iv, o);
 	scan_exclusive_u64(o.nalt, r.ac_off, r1, s64, s);
 	HIP_CHECK(copy_async(&r.n_ac, r.ac_off + nrec, 8, hipMemcpyDeviceToHost, s));
 	scan_exclusive_u32(r.need, r.boff, n2, w.tmp, w.tmp_bytes, s);
-	HIP_CHECK(copy_async(&r.nfb, r.boff + 2 * (size_t)n, 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(&r.nfc, r.boff + 4 * (size_t)n, 4, hipMemcpyDeviceToHost, s));
+	uint32_t nx = 0; // the extra blocks: a nested call's REFs that are no representatives
+	if (in.nested && nfl) {
+		scan_exclusive_u32(r.xneed, r.xoff, f1, w.tmp, w.tmp_bytes, s);
+		HIP_CHECK(copy_async(&nx, r.xoff + nfl, 4, hipMemcpyDeviceToHost, s));
+	}
 	HIP_CHECK(hipStreamSynchronize(s));
 	if (n)
-		KLAUNCH(k_cl_blocks, dim3(stride_blocks(2 * (size_t)n)), dim3(Q_TPB), 0, s, 2 * (uint64_t)n, r.need, r.boff, r.blist);
-	// the inversion records' blocks follow the flubble blocks, one each: REF, then ALT
-	const uint32_t nfb = r.nfb;
+		KLAUNCH(k_cl_blocks, dim3(stride_blocks(4 * (size_t)n)), dim3(Q_TPB), 0, s, 4 * (uint64_t)n, r.need, r.boff, r.blist);
+	// the extra blocks follow the class blocks; the inversion records' blocks follow the flubble blocks, one each: REF, then ALT
+	refuse_2_32((uint64_t)r.nfc + nx, "the call needs ", "blocks");
+	const uint32_t nfc = r.nfc, nfb = r.nfb = nfc + nx;
 	refuse_2_32((uint64_t)nfb + iv.n, "the call needs ", "blocks");
 	const uint32_t nb = r.nb = nfb + iv.n;
 	HIP_CHECK(hipMemsetAsync(r.bcnt + nb, 0, 8, s));
-	if (nfb)
-		KLAUNCH(k_cl_block_cnt, dim3(stride_blocks(nfb)), dim3(Q_TPB), 0, s, nfb, r.blist, d.aoff, r.bcnt);
+	if (nfc)
+		KLAUNCH(k_cl_block_cnt, dim3(stride_blocks(nfc)), dim3(Q_TPB), 0, s, nfc, r.blist, w.aoff, r.bcnt);
+	if (nx)
+		KLAUNCH(k_cl_extra, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rstate, r.xoff, r.xlist, r.bcnt + nfc);
 	inv_genotypes(ctx, inv.in, iv, o, nfb, r.bcnt);
 	scan_exclusive_u64(r.bcnt, r.block_off, (size_t)nb + 1, s64, s);
 	HIP_CHECK(copy_async(&r.nsp, r.block_off + nb, 8, hipMemcpyDeviceToHost, s));
@@ -783,15 +970,18 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, cons
 	HIP_CHECK(hipMemsetAsync(bad, 0xFF, 8, s));
 	if (nfl) {
 		KLAUNCH(k_cl_records, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, o.o_q, o.o_path, o.o_ref, w.qidx, w.d_slot, w.d_slot_first, in.NS, in.S, w.smin,
-			w.smax, r.ac_off, d.qstatus, w.anchored, d.aoff, w.ilen, o.gt, sp.ac, o.o_an, o.o_ns, o.o_flags, inv.f_dst);
-		KLAUNCH(k_cl_rec_block, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, d.rq, d.orv, r.boff, o.o_block, inv.f_dst);
+			w.smax, r.ac_off, d.qstatus, w.perm, w.rstate, in.nested ? w.collapsed : nullptr, in.nested ? w.nr.rescued : nullptr, o.gt, sp.ac, o.o_an,
+			o.o_ns, o.o_flags, inv.f_dst);
+		KLAUNCH(k_cl_rec_block, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, d.rq, d.orv, r.boff, o.o_block, inv.f_dst, w.rstate,
+			r.xoff, r.xrow);
 	}
 	inv_counts(ctx, inv.in, iv, o, r.ac_off, sp.ac);
 	HIP_CHECK(hipMemsetAsync(slen + nsp, 0, 8, s));
 	HIP_CHECK(hipMemsetAsync(alen + nsp, 0, 8, s));
+	const SpellTab T{nfb,	 r.nfc,	  r.block_off, r.blist, w.aoff,		 w.afirst, r.xlist, w.rlist, d.rq,
+			  d.orv, w.rstate, d.rpos,     d.rlen,	ctx->path_steps, w.ilen,   w.atl,   w.xilen, w.xatl};
 	if (nfsp)
-		KLAUNCH(k_cl_spell_len, dim3(stride_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, nfb, r.block_off, r.blist, d.aoff, d.afirst, d.rpos, d.rlen,
-			ctx->path_steps, ctx->seq_off, g.vid, w.ilen, w.atl, w.anchored, slen, alen);
+		KLAUNCH(k_cl_spell_len, dim3(stride_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, T, ctx->seq_off, g.vid, slen, alen);
 	inv_spell_len(ctx, inv.in, iv, slen + nfsp, alen + nfsp);
 	scan_exclusive_u64(slen, sp.sp_off, nsp + 1, s64, s);
 	scan_exclusive_u64(alen, sp.at_off, nsp + 1, s64, s);
@@ -800,9 +990,10 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, cons
 	HIP_CHECK(hipStreamSynchronize(s));
 	carve(ctx->cl_bytes, [&](Spans &take) { take(sp.nbytes[0] + 1, sp.o_seq), take(sp.nbytes[1] + 1, sp.o_at); });
 	if (nfsp)
-		KLAUNCH(k_cl_emit, dim3(wave_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, nfb, r.block_off, r.blist, d.aoff, d.afirst, d.rpos, d.rlen, ctx->path_steps,
-			ctx->seq_off, ctx->seq, g.vid, w.anchored, sp.sp_off, sp.at_off, sp.o_seq, sp.o_at, bad);
+		KLAUNCH(k_cl_emit, dim3(wave_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, T, ctx->seq_off, ctx->seq, g.vid, sp.sp_off, sp.at_off, sp.o_seq, sp.o_at, bad);
 	inv_emit(ctx, inv.in, iv, sp.sp_off + nfsp, sp.at_off + nfsp, sp.o_seq, sp.o_at, bad);
+	if (r.nrec)
+		KLAUNCH(k_cl_ref_spelled, dim3(stride_blocks(r.nrec)), dim3(Q_TPB), 0, s, r.nrec, o.o_block, o.o_ref, r.xrow, r.block_off, r.nfc, r.ref_spelled);
 	uint64_t hbad = 0;
 	HIP_CHECK(copy_async(&hbad, bad, 8, hipMemcpyDeviceToHost, s));
 	sp.h_roff.resize(nR ? nR + 1 : 1);
@@ -813,7 +1004,8 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, cons
 		throw HipError("segment " + std::to_string(read_back(g.vid + hbad, s)) + " holds a byte that is no nucleotide code (ACGTN, lower case, IUPAC)");
 }
 
-povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const CallInv &inv, const CallRecs &r, const CallSpelled &sp, CallTimer &timer)
+povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, const CallRecs &r, const CallSpelled &sp,
+			      CallTimer &timer)
 {
 	const uint32_t nrec = r.nrec, nb = r.nb, nR = in.nR, S = in.S;
 	const uint64_t nsp = r.nsp, n_ac = r.n_ac;
@@ -832,6 +1024,9 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	hand_off(o->n_steps, nrec, d.o_nsteps, nrec, ctx);
 	hand_off(o->pos, nrec, d.o_pos, nrec, ctx);
 	hand_off(o->flags, nrec, d.o_flags, nrec, ctx);
+	hand_off(o->level, nrec, r.o_level, nrec, ctx);
+	hand_off(o->parent_query, nrec, r.o_parent, nrec, ctx);
+	hand_off(o->ref_spelled, nrec, r.ref_spelled, nrec, ctx);
 	hand_off(o->ac_off, r1, r.ac_off, r1, ctx);
 	hand_off(o->ac, n_ac, sp.ac, n_ac, ctx);
 	hand_off(o->gt, (size_t)nrec * S, d.gt, (size_t)nrec * S, ctx);
@@ -859,6 +1054,9 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	v.pos = o->pos.data(), v.flags = o->flags.data(), v.ac_off = o->ac_off.data(), v.ac = o->ac.data(), v.gt = o->gt.data();
 	v.block_off = o->block_off.data(), v.seq_off = o->seq_off.data(), v.at_off = o->at_off.data(), v.seq = o->seq.data();
 	v.at = o->at.data(), v.contig_len = o->contig_len.data();
+	v.level = o->level.data(), v.parent_query = o->parent_query.data(), v.ref_spelled = o->ref_spelled.data();
+	v.nested = in.nested ? 1 : 0;
+	v.n_enclosed = w.nr.n_enclosed, v.n_collapsed_sites = w.n_collapsed, v.n_popped = w.nr.n_popped, v.n_rescued = w.nr.n_rescued;
 	CallsOwner *raw = o.release();
 	return &raw->view;
 }
@@ -867,9 +1065,16 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
 					 const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, char *err, size_t errlen)
 {
+	return povu_hip_call_profile(ctx, sites, refs, slot_of_path, opts, nullptr, err, errlen);
+}
+
+extern "C" povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+						 const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
+						 const povu_hip_call_profile_opts *profile, char *err, size_t errlen)
+{
 	CallTimer timer;
 	return guarded_call(ctx, err, errlen, (povu_hip_calls *)nullptr, [&] {
-		const CallInputs in = check_call_inputs(ctx, sites, refs, slot_of_path, opts);
+		const CallInputs in = check_call_inputs(ctx, sites, refs, slot_of_path, opts, profile);
 		const TravDevice d = trav_pipeline(
 			ctx,
 			[&](CallTimer &tm, const QueryLayout &more) { return query_front(ctx, in.qa, in.qz, in.qor, ctx->tr_ws, tm, more); },
@@ -877,6 +1082,8 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 		CallWs w;
 		reference_offsets(ctx, in, d, w);
 		callability(ctx, in, d, w);
+		site_classes(ctx, in, d, w);
+		kept_sites(ctx, in, d, w);
 		slot_table(ctx, in, d, w);
 		flubble_records(ctx, in, d, w);
 		CallInv inv;
@@ -885,7 +1092,7 @@ extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites
 		record_arrays(ctx, in, d, w, inv, r);
 		CallSpelled sp;
 		spelling(ctx, in, d, w, inv, r, sp);
-		return calls_to_host(ctx, in, inv, r, sp, timer);
+		return calls_to_host(ctx, in, w, inv, r, sp, timer);
 	});
 }
 

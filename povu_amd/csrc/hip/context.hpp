@@ -344,6 +344,9 @@ struct povu_hip_ctx {
 	// povu_hip_call with POVU_HIP_T_INVERSIONS (inv_kernels.hip): the step index and head counts / the run heads, runs and
 	// records / the rows of the flubble records in the merged list
 	Arena iv_ws, iv_heads, iv_rows;
+	// povu_hip_call with POVU_HIP_T_NESTED (nest_kernels.hip): the index of the called sites' traversals / the classes / the
+	// scratch of both / the records' parents, levels and the profile's choice
+	Arena ns_idx, ns_cls, ns_ws, ns_rec;
 	uint64_t *seq_off = nullptr;
 	char *seq = nullptr;
 	uint64_t seq_gen = 0;

@@ -1,0 +1,488 @@
+// nest_kernels.hip -- the nested calls of povu_hip_call with POVU_HIP_T_NESTED (include/povu_hip.h).
+//
+// The definition is this project's own ("Nested calls"; restated in tests/nested_ref.py).  Nesting is the
+// nesting of traversals along a path, not PVST parentage: traversal t encloses t' of another called site when t' lies within
+// t on the same path and is shorter.  Two steps of povu_hip_call:
+//   classes  (between callability and the slot table)
+//     index     the traversals of the called sites, compacted and radix-sorted by their global path position (which names
+//               the path too); an entry holds its first and last position, its site and its traversal;
+//     cover     per exact allele of a called site of two alleles or more, from its first traversal t: position k of t is
+//               covered when the running maximum of the last positions of the enclosed entries that start before k exceeds
+//               k.  The entries that start inside t are one stretch of the index.  Tier 1: a lane per allele of up to 64
+//               steps walks steps and entries in one merge.  Tier 2: a wave per longer allele, 64 positions a round -- the
+//               round's entries drop their ends into the slot of their start (LDS), a wave prefix maximum over the slots
+//               and the carry of the rounds before give every lane its maximum.  The mask is kept a byte a step, S -> Z;
+//     skeleton  the 64-bit hash (sum of mix(rank, step) over the uncovered steps, S -> Z) and the length of what is left;
+//     classes   the exact alleles grouped by (site, length, hash) and compared skeleton by skeleton (exact_groups.hpp, the
+//               machinery of the traversals' alleles); a class is numbered by the scan of the "lowest allele of its group"
+//               flags, so classes come in the order of their lowest allele.
+//   records  (once the flubble records are known, before they are sorted and before any block is formed)
+//     parent    a wave per record walks the entries that start inside its traversal and offers itself, as (length, record),
+//               to every enclosed entry that is a record too (atomic minimum: the shortest encloser, then the lowest site);
+//     level     a lane per record climbs its chain of parents: the top's PVST height - 1 plus the links climbed;
+//     profile   big from the written lengths, reach by climbing while the level is above max_level, the kept records
+//               compacted -- what is dropped here is never spelled.
+// Work: an entry is visited once per called traversal that encloses (or overlaps) it -- path steps times nesting depth, the
+// bound of the scans themselves.
+#include "nest_kernels.hpp"
+
+#include "exact_groups.hpp"
+
+namespace povu_hip
+{
+
+static constexpr uint32_t N1_STEPS = 64; // steps of the longest allele tier 1 covers
+
+// first entry whose position is at least x
+__device__ __forceinline__ uint32_t first_at_least(const uint64_t *__restrict__ ipos, uint32_t ni, uint64_t x)
+{
+	uint32_t lo = 0, hi = ni;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (ipos[mid] < x)
+			lo = mid + 1;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+
+// ---- index
+__global__ void k_ns_called_flag(uint32_t R, const uint32_t *__restrict__ rq, const uint8_t *__restrict__ called, uint8_t *__restrict__ flag)
+{
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < R; t += gridDim.x * Q_TPB)
+		flag[t] = called[rq[t]];
+}
+__global__ void k_ns_pos_key(uint32_t ni, int which, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ rpos, uint32_t *__restrict__ key)
+{
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < ni; k += gridDim.x * Q_TPB) {
+		const uint64_t p = rpos[perm[k]] & ~ROLE_BIT;
+		key[k] = which ? (uint32_t)(p >> 32) : (uint32_t)p;
+	}
+}
+__global__ void k_ns_index(uint32_t ni, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ rpos, const uint32_t *__restrict__ rlen,
+			   const uint32_t *__restrict__ rq, uint64_t *__restrict__ ipos, uint64_t *__restrict__ iend, uint32_t *__restrict__ iq,
+			   uint32_t *__restrict__ it)
+{
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < ni; k += gridDim.x * Q_TPB) {
+		const uint32_t t = perm[k];
+		const uint64_t p = rpos[t] & ~ROLE_BIT;
+		ipos[k] = p;
+		iend[k] = p + rlen[t] - 1;
+		iq[k] = rq[t];
+		it[k] = t;
+	}
+}
+
+// ---- cover and skeleton
+// site of every exact allele; candidates: the alleles of called sites of two alleles or more
+__global__ void k_ns_allele_site(uint32_t n_al, const uint32_t *__restrict__ afirst, const uint32_t *__restrict__ rq,
+				 const uint32_t *__restrict__ aoff, const uint8_t *__restrict__ called, uint32_t *__restrict__ aq,
+				 uint8_t *__restrict__ cand)
+{
+	for (uint32_t a = blockIdx.x * Q_TPB + threadIdx.x; a < n_al; a += gridDim.x * Q_TPB) {
+		const uint32_t q = rq[afirst[a]];
+		aq[a] = q;
+		cand[a] = called[q] && aoff[q + 1] - aoff[q] >= 2;
+	}
+}
+
+struct CoverArgs {
+	const uint32_t *steps;
+	const uint64_t *rpos;
+	const uint32_t *rlen, *rq, *afirst, *soff;
+	const uint8_t *cand;
+	const uint64_t *ipos, *iend;
+	const uint32_t *iq;
+	uint32_t ni;
+	uint8_t *cov;	// [allele steps] 1: covered, S -> Z
+	uint32_t *slen; // skeleton length
+	uint64_t *shash;
+	uint32_t mask_hi, mask_lo;
+};
+__device__ __forceinline__ uint64_t kept_bits(const CoverArgs &A, uint64_t h) { return h & (((uint64_t)A.mask_hi << 32) | A.mask_lo); }
+// entry e is enclosed by the traversal of site q over [.., end] of len steps (it starts at or after the traversal's start)
+__device__ __forceinline__ bool enclosed(const CoverArgs &A, uint32_t e, uint32_t q, uint64_t end, uint32_t len)
+{
+	const uint64_t ie = A.iend[e];
+	return A.iq[e] != q && ie <= end && ie - A.ipos[e] < (uint64_t)len - 1;
+}
+
+// tier 1: a lane per allele; longer alleles (all candidates with force2) are handed over.  An allele that is no candidate
+// gets a skeleton of its own (length 0, hash = its number): it stays a class of its own.
+__global__ __launch_bounds__(Q_TPB) void k_ns_cover_t1(uint32_t n_al, CoverArgs A, uint32_t force2, uint8_t *__restrict__ hand)
+{
+	const uint32_t a = blockIdx.x * Q_TPB + threadIdx.x;
+	if (a >= n_al)
+		return;
+	hand[a] = 0;
+	if (!A.cand[a]) {
+		A.slen[a] = 0;
+		A.shash[a] = kept_bits(A, a);
+		return;
+	}
+	const uint32_t t = A.afirst[a], len = A.rlen[t];
+	if (force2 || len > N1_STEPS) {
+		hand[a] = 1;
+		return;
+	}
+	const uint64_t pos = A.rpos[t] & ~ROLE_BIT, end = pos + len - 1;
+	const bool rev = (A.rpos[t] & ROLE_BIT) != 0;
+	const uint32_t q = A.rq[t], base = A.soff[a];
+	uint32_t e = first_at_least(A.ipos, A.ni, pos), m = 0;
+	uint64_t top = 0; // the running maximum of the enclosed entries' last positions (every one is at least 1)
+	for (uint64_t k = pos; k <= end; k++) {
+		for (; e < A.ni && A.ipos[e] < k; e++)
+			if (enclosed(A, e, q, end, len))
+				top = max(top, A.iend[e]);
+		const bool c = top > k;
+		A.cov[base + (uint32_t)(rev ? end - k : k - pos)] = c;
+		m += !c;
+	}
+	uint64_t h = 0;
+	uint32_t j = 0;
+	for (uint32_t i = 0; i < len; i++)
+		if (!A.cov[base + i]) // (this lane's own stores)
+			h += step_hash(j++, trav_step(A.steps, pos, len, rev, i));
+	A.slen[a] = m;
+	A.shash[a] = kept_bits(A, h);
+}
+
+__device__ __forceinline__ uint32_t wave_inclusive_max(uint32_t v)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	for (int o = 1; o < 64; o <<= 1) {
+		const uint32_t y = __shfl_up(v, o, 64);
+		if (lane >= o)
+			v = max(v, y);
+	}
+	return v;
+}
+
+// tier 2: a wave (a workgroup of 64 lanes: its barriers are the wave's own) per allele of `list`, 64 positions a round
+__global__ __launch_bounds__(64) void k_ns_cover_t2(const uint32_t *__restrict__ list, uint32_t n2, CoverArgs A)
+{
+	__shared__ uint32_t slot[64];
+	const uint32_t lane = threadIdx.x;
+	for (uint32_t w = blockIdx.x; w < n2; w += gridDim.x) {
+		const uint32_t a = list[w], t = A.afirst[a], len = A.rlen[t], q = A.rq[t], base = A.soff[a];
+		const uint64_t pos = A.rpos[t] & ~ROLE_BIT, end = pos + len - 1;
+		const bool rev = (A.rpos[t] & ROLE_BIT) != 0;
+		uint32_t e = first_at_least(A.ipos, A.ni, pos), carry = 0; // ends relative to pos: at least 1
+		for (uint32_t cb = 0; cb < len; cb += 64) {
+			// the entries that start at the round's positions: their ends into the slot of their start
+			const uint32_t e_hi = first_at_least(A.ipos, A.ni, pos + cb + 64);
+			slot[lane] = 0;
+			__syncthreads();
+			for (uint32_t x = e + lane; x < e_hi; x += 64)
+				if (enclosed(A, x, q, end, len) && A.ipos[x] - pos - cb < 64)
+					atomicMax(&slot[(uint32_t)(A.ipos[x] - pos) - cb], (uint32_t)(A.iend[x] - pos));
+			__syncthreads();
+			const uint32_t incl = wave_inclusive_max(slot[lane]);
+			uint32_t before = __shfl_up(incl, 1, 64); // the entries that start before this lane's position
+			if (lane == 0)
+				before = 0;
+			const uint32_t k = cb + lane;
+			if (k < len)
+				A.cov[base + (rev ? len - 1 - k : k)] = max(carry, before) > k;
+			carry = max(carry, __shfl(incl, 63, 64));
+			e = e_hi;
+			__syncthreads();
+		}
+	}
+}
+__global__ __launch_bounds__(64) void k_ns_skel_t2(const uint32_t *__restrict__ list, uint32_t n2, CoverArgs A)
+{
+	const uint32_t lane = threadIdx.x;
+	const unsigned long long below = (1ull << lane) - 1ull;
+	for (uint32_t w = blockIdx.x; w < n2; w += gridDim.x) {
+		const uint32_t a = list[w], t = A.afirst[a], len = A.rlen[t], base = A.soff[a];
+		const uint64_t pos = A.rpos[t] & ~ROLE_BIT;
+		const bool rev = (A.rpos[t] & ROLE_BIT) != 0;
+		uint32_t m = 0;
+		uint64_t h = 0;
+		for (uint32_t cb = 0; cb < len; cb += 64) {
+			const uint32_t i = cb + lane;
+			const bool open = i < len && !A.cov[base + i];
+			const unsigned long long mask = __ballot(open);
+			if (open)
+				h += step_hash(m + (uint32_t)__popcll(mask & below), trav_step(A.steps, pos, len, rev, i));
+			m += (uint32_t)__popcll(mask);
+		}
+		h = wave_sum(h);
+		if (lane == 0) {
+			A.slen[a] = m;
+			A.shash[a] = kept_bits(A, h);
+		}
+	}
+}
+
+// exact alleles a and b (of one site) have the same skeleton
+struct SameSkeleton {
+	const uint32_t *steps;
+	const uint64_t *rpos;
+	const uint32_t *rlen, *afirst, *soff;
+	const uint8_t *cand, *cov;
+	__device__ __forceinline__ bool operator()(uint32_t a, uint32_t b) const
+	{
+		if (!cand[a])
+			return false; // (two alleles of a site that is no candidate: classes of their own)
+		const uint32_t ta = afirst[a], tb = afirst[b], la = rlen[ta], lb = rlen[tb], ba = soff[a], bb = soff[b];
+		const uint64_t pa = rpos[ta] & ~ROLE_BIT, pb = rpos[tb] & ~ROLE_BIT;
+		const bool ra = (rpos[ta] & ROLE_BIT) != 0, rb = (rpos[tb] & ROLE_BIT) != 0;
+		for (uint32_t i = 0, j = 0;; i++, j++) {
+			while (i < la && cov[ba + i])
+				i++;
+			while (j < lb && cov[bb + j])
+				j++;
+			if (i == la || j == lb)
+				return i == la && j == lb;
+			if (trav_step(steps, pa, la, ra, i) != trav_step(steps, pb, lb, rb, j))
+				return false;
+		}
+	}
+};
+
+// ---- classes
+// class of every allele (global numbering) and, from the group's first allele, the class's representative
+__global__ void k_ns_class_of(uint32_t n_al, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, const uint32_t *__restrict__ cidx,
+			      const uint32_t *__restrict__ afirst, uint32_t *__restrict__ cglob, uint32_t *__restrict__ crep,
+			      uint32_t *__restrict__ cfirst)
+{
+	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < n_al; k += gridDim.x * Q_TPB) {
+		const uint32_t a = perm[k], c = cidx[perm[rep[k]]];
+		cglob[a] = c;
+		if (rep[k] == k) {
+			crep[c] = a;
+			cfirst[c] = afirst[a];
+		}
+	}
+}
+__global__ void k_ns_class_off(uint32_t n, const uint32_t *__restrict__ aoff, const uint32_t *__restrict__ cidx, uint32_t *__restrict__ coff)
+{
+	for (uint32_t q = blockIdx.x * Q_TPB + threadIdx.x; q <= n; q += gridDim.x * Q_TPB)
+		coff[q] = cidx[aoff[q]];
+}
+__global__ void k_ns_trav_class(uint32_t R, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ oa, const uint32_t *__restrict__ aoff,
+				const uint32_t *__restrict__ cglob, const uint32_t *__restrict__ coff, uint32_t *__restrict__ oc)
+{
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < R; t += gridDim.x * Q_TPB) {
+		const uint32_t q = rq[t];
+		oc[t] = cglob[aoff[q] + oa[t]] - coff[q];
+	}
+}
+
+NestClasses nest_classes(povu_hip_ctx *ctx, const TravDevice &d, const uint8_t *called, uint32_t max_steps, bool force_tier2)
+{
+	hipStream_t s = ctx->stream;
+	const uint32_t n = d.q.n, R = d.R, n_al = d.n_al, hbits = hash_bits_hook();
+	const size_t R1 = (size_t)R + 1, A1 = (size_t)n_al + 1, n1 = (size_t)n + 1;
+	NestClasses c;
+	NestIndex &ix = c.ix;
+	uint8_t *flag, *cov, *cand, *hand, *rbad;
+	uint32_t *ilist, *pb, *key, *kout, *words, *slen, *aq, *list2, *ga, *gb, *gkey, *gkout, *mark, *hmax, *head, *rep, *blist, *firstf, *cidx, *cglob;
+	uint64_t *shash;
+	unsigned long long *tot;
+	void *tmp;
+	const size_t tmp_bytes = prim_tmp_bytes(std::max({R1, A1, n1}), true) + 256;
+	carve(ctx->ns_idx, [&](Spans &take) { take(R1, ix.ipos, ix.iend, ix.iq, ix.it); });
+	carve(ctx->ns_cls, [&](Spans &take) {
+		take(n1, c.coff);
+		take(A1, c.crep, c.cfirst);
+		take(R1, c.oc);
+	});
+	carve(ctx->ns_ws, [&](Spans &take) {
+		take(R1, flag, ilist, pb, key, kout);
+		take(d.n_steps + 1, cov);
+		take(A1, shash, slen, aq, list2, ga, gb, gkey, gkout, mark, hmax, head, rep, blist, firstf, cidx, cglob, cand, hand, rbad);
+		take(8, words);
+		take(2, tot);
+		take(tmp_bytes, tmp);
+	});
+	HIP_CHECK(hipMemsetAsync(words, 0, 32, s));
+	// ---- index
+	if (R) {
+		KLAUNCH(k_ns_called_flag, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, d.rq, called, flag);
+		compact_flagged_u8(flag, R, ilist, words, tmp, tmp_bytes, s);
+		ix.ni = read_back(words, s);
+	}
+	const uint32_t ni = ix.ni;
+	if (ni) {
+		LsdSort sort{ilist, pb, key, kout, ni, tmp, tmp_bytes, s};
+		auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
+			KLAUNCH(k_ns_pos_key, dim3(stride_blocks(ni)), dim3(Q_TPB), 0, s, ni, which, perm, d.rpos, k);
+		};
+		sort.pass(0, (unsigned)std::min<uint64_t>(32, bits_for(ctx->n_path_steps)), write_key);
+		if (ctx->n_path_steps >= (1ull << 32))
+			sort.pass(1, 32, write_key);
+		KLAUNCH(k_ns_index, dim3(stride_blocks(ni)), dim3(Q_TPB), 0, s, ni, sort.cur, d.rpos, d.rlen, d.rq, ix.ipos, ix.iend, ix.iq, ix.it);
+	}
+	if (!n_al) {
+		HIP_CHECK(hipMemsetAsync(c.coff, 0, n1 * 4, s));
+		return c;
+	}
+	// ---- cover, skeleton
+	KLAUNCH(k_ns_allele_site, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, d.afirst, d.rq, d.aoff, called, aq, cand);
+	HIP_CHECK(hipMemsetAsync(cov, 0, d.n_steps + 1, s));
+	const CoverArgs CA{ctx->path_steps, d.rpos, d.rlen, d.rq, d.afirst, d.soff, cand, ix.ipos, ix.iend, ix.iq, ni,
+			   cov, slen, shash, hash_mask_hi(hbits), hash_mask_lo(hbits)};
+	KLAUNCH(k_ns_cover_t1, dim3(lane_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, CA, force_tier2 ? 1u : 0u, hand);
+	compact_flagged_u8(hand, n_al, list2, words + 1, tmp, tmp_bytes, s);
+	c.n_tier2 = read_back(words + 1, s);
+	if (c.n_tier2) {
+		const unsigned wg = (unsigned)std::min<uint32_t>(c.n_tier2, 1u << 16);
+		KLAUNCH(k_ns_cover_t2, dim3(wg), dim3(64), 0, s, list2, c.n_tier2, CA);
+		KLAUNCH(k_ns_skel_t2, dim3(wg), dim3(64), 0, s, list2, c.n_tier2, CA);
+	}
+	// ---- classes
+	GroupWs gw{ga, gb, gkey, gkout, mark, hmax, head, rep, blist, rbad, tmp, tmp_bytes};
+	const uint32_t *sp = group_exact(n_al, aq, slen, shash, hbits, bits_for(max_steps), bits_for(n), SameSkeleton{ctx->path_steps, d.rpos, d.rlen, d.afirst, d.soff, cand, cov},
+					 gw, words + 2, tot, &c.n_splits, s);
+	HIP_CHECK(hipMemsetAsync(firstf, 0, A1 * 4, s));
+	KLAUNCH(k_eg_first, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, sp, rep, firstf);
+	scan_exclusive_u32(firstf, cidx, A1, tmp, tmp_bytes, s);
+	c.n_cl = read_back(cidx + n_al, s);
+	KLAUNCH(k_ns_class_of, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, sp, rep, cidx, d.afirst, cglob, c.crep, c.cfirst);
+	KLAUNCH(k_ns_class_off, dim3(stride_blocks(n1)), dim3(Q_TPB), 0, s, n, d.aoff, cidx, c.coff);
+	if (R)
+		KLAUNCH(k_ns_trav_class, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, d.rq, d.oa, d.aoff, cglob, c.coff, c.oc);
+	return c;
+}
+
+// ---- records: parent, level, profile
+__global__ void k_ns_rec_of(uint32_t nfl, const uint32_t *__restrict__ rlist, uint32_t *__restrict__ rec_of)
+{
+	for (uint32_t j = blockIdx.x * Q_TPB + threadIdx.x; j < nfl; j += gridDim.x * Q_TPB)
+		rec_of[rlist[j]] = j;
+}
+// a wave per record: the record offers itself to every record it encloses (par: the minimum of (steps - 1) << 32 | record)
+__global__ __launch_bounds__(Q_TPB) void k_ns_parent(uint32_t nfl, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq,
+						     const uint64_t *__restrict__ rpos, const uint32_t *__restrict__ rlen, NestIndex ix,
+						     const uint32_t *__restrict__ rec_of, unsigned long long *__restrict__ par)
+{
+	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
+	for (uint32_t j = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); j < nfl; j += waves) {
+		const uint32_t t = rlist[j], len = rlen[t], q = rq[t];
+		const uint64_t pos = rpos[t] & ~ROLE_BIT, end = pos + len - 1;
+		const uint32_t lo = first_at_least(ix.ipos, ix.ni, pos), hi = first_at_least(ix.ipos, ix.ni, end + 1);
+		for (uint32_t x = lo + lane; x < hi; x += 64) {
+			const uint64_t ie = ix.iend[x];
+			if (ix.iq[x] == q || ie > end || ie - ix.ipos[x] >= (uint64_t)len - 1)
+				continue;
+			const uint32_t jj = rec_of[ix.it[x]];
+			if (jj != NO_QUERY)
+				atomicMin(par + jj, ((unsigned long long)(len - 1) << 32) | j);
+		}
+	}
+}
+// a lane per record climbs its chain: level, the parent's site; cnt[0] += the records with a parent
+__global__ __launch_bounds__(Q_TPB) void k_ns_level(uint32_t nfl, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq,
+						    const uint32_t *__restrict__ height, const unsigned long long *__restrict__ par,
+						    uint32_t *__restrict__ level, uint32_t *__restrict__ parent_q, unsigned long long *__restrict__ cnt)
+{
+	for (uint32_t j0 = blockIdx.x * Q_TPB; j0 < nfl; j0 += gridDim.x * Q_TPB) {
+		const uint32_t j = j0 + threadIdx.x;
+		uint32_t has = 0;
+		if (j < nfl) {
+			uint32_t cur = j, up = 0;
+			for (uint32_t k = 0; k < nfl && par[cur] != ~0ull; k++, up++)
+				cur = (uint32_t)par[cur];
+			level[j] = height[rq[rlist[cur]]] - 1 + up;
+			has = par[j] != ~0ull;
+			parent_q[j] = has ? rq[rlist[(uint32_t)par[j]]] : NO_QUERY;
+		}
+		has = wave_sum(has);
+		if ((threadIdx.x & 63u) == 0 && has)
+			atomicAdd(cnt, (unsigned long long)has);
+	}
+}
+// the profile's choice: keep[j], rescued[j]; cnt[1] += popped, cnt[2] += rescued
+__global__ __launch_bounds__(Q_TPB) void k_ns_profile(uint32_t nfl, uint32_t profile, uint32_t max_level, uint64_t max_ref, uint64_t max_al,
+						      const uint64_t *__restrict__ ref_len, const uint64_t *__restrict__ max_len,
+						      const unsigned long long *__restrict__ par, const uint32_t *__restrict__ level,
+						      uint8_t *__restrict__ keep, uint8_t *__restrict__ rescued, unsigned long long *__restrict__ cnt)
+{
+	auto big = [&](uint32_t r) { return (max_ref && ref_len[r] > max_ref) || (max_al && max_len[r] > max_al); };
+	for (uint32_t j0 = blockIdx.x * Q_TPB; j0 < nfl; j0 += gridDim.x * Q_TPB) {
+		const uint32_t j = j0 + threadIdx.x;
+		uint32_t popped = 0, saved = 0;
+		if (j < nfl) {
+			bool k = false, r = false;
+			if (profile == POVU_HIP_PROFILE_TOP_LEVEL_ONLY) {
+				k = level[j] == 0;
+			} else {
+				// reach: the level is within max_level, or the parent is big and reached itself
+				bool reach = true;
+				uint32_t cur = j;
+				for (uint32_t it = 0; it < nfl && (int32_t)level[cur] > (int32_t)max_level; it++) {
+					if (par[cur] == ~0ull || !big((uint32_t)par[cur])) {
+						reach = false;
+						break;
+					}
+					cur = (uint32_t)par[cur];
+				}
+				const bool b = big(j);
+				k = reach && !b;
+				r = k && (int32_t)level[j] > (int32_t)max_level;
+				popped = reach && b;
+				saved = r;
+			}
+			keep[j] = k;
+			rescued[j] = r;
+		}
+		popped = wave_sum(popped);
+		saved = wave_sum(saved);
+		if ((threadIdx.x & 63u) == 0) {
+			if (popped)
+				atomicAdd(cnt + 1, (unsigned long long)popped);
+			if (saved)
+				atomicAdd(cnt + 2, (unsigned long long)saved);
+		}
+	}
+}
+
+NestRecs nest_records(povu_hip_ctx *ctx, const TravDevice &d, const NestIndex &ix, const NestRecIn &in)
+{
+	hipStream_t s = ctx->stream;
+	const uint32_t nfl = in.nfl;
+	const size_t F1 = (size_t)nfl + 1, R1 = (size_t)d.R + 1;
+	NestRecs o;
+	unsigned long long *par, *cnt;
+	uint32_t *rec_of, *words;
+	uint8_t *keep;
+	void *tmp;
+	const size_t tmp_bytes = prim_tmp_bytes(F1, false) + 256;
+	carve(ctx->ns_rec, [&](Spans &take) {
+		take(F1, par, o.level, o.parent_q, o.kept, keep, o.rescued);
+		take(R1, rec_of);
+		take(4, cnt);
+		take(2, words);
+		take(tmp_bytes, tmp);
+	});
+	o.n_kept = nfl;
+	HIP_CHECK(hipMemsetAsync(o.rescued, 0, F1, s));
+	if (!nfl)
+		return o;
+	HIP_CHECK(hipMemsetAsync(par, 0xFF, F1 * 8, s));
+	HIP_CHECK(hipMemsetAsync(rec_of, 0xFF, R1 * 4, s));
+	HIP_CHECK(hipMemsetAsync(cnt, 0, 32, s));
+	KLAUNCH(k_ns_rec_of, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, in.rlist, rec_of);
+	KLAUNCH(k_ns_parent, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, in.rlist, d.rq, d.rpos, d.rlen, ix, rec_of, par);
+	KLAUNCH(k_ns_level, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, in.rlist, d.rq, in.height, par, o.level, o.parent_q, cnt);
+	const bool filter = in.profile != POVU_HIP_PROFILE_RAW_GRAPH;
+	if (filter) {
+		KLAUNCH(k_ns_profile, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, in.profile, in.max_level, in.max_ref_length, in.max_allele_length,
+			in.ref_len, in.max_len, par, o.level, keep, o.rescued, cnt);
+		compact_flagged_u8(keep, nfl, o.kept, words, tmp, tmp_bytes, s);
+		HIP_CHECK(copy_async(&o.n_kept, words, 4, hipMemcpyDeviceToHost, s));
+	} else {
+		launch_iota(nfl, o.kept, s);
+	}
+	unsigned long long h[4] = {0, 0, 0, 0};
+	HIP_CHECK(copy_async(h, cnt, 32, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	o.n_enclosed = h[0], o.n_popped = h[1], o.n_rescued = h[2];
+	return o;
+}
+
+} // namespace povu_hip

@@ -1,0 +1,48 @@
+// nest_kernels.hpp -- the nested calls of povu_hip_call with POVU_HIP_T_NESTED (nest_kernels.hip; INTEGRATION.md "Nested
+// calls"): what the call hands the two steps and what they leave on the device (the context's nest arenas, valid until the
+// next nested call on the context).
+#pragma once
+#include "call_common.hpp"
+
+namespace povu_hip
+{
+
+// the traversals of the called sites in path order: entry i is traversal it[i] of site iq[i] over the global path positions
+// [ipos[i], iend[i]], ipos ascending (a global position names the path too: the paths are concatenated)
+struct NestIndex {
+	uint32_t ni = 0;
+	uint64_t *ipos = nullptr, *iend = nullptr;
+	uint32_t *iq = nullptr, *it = nullptr;
+};
+// the classes: of site q the classes [coff[q], coff[q + 1]), numbered in the order of their lowest exact allele; of class c its
+// representative's global allele crep[c] and that allele's first traversal cfirst[c]; of traversal t its class within its
+// site, oc[t]
+struct NestClasses {
+	NestIndex ix;
+	uint32_t n_cl = 0, n_tier2 = 0;
+	uint64_t n_splits = 0;
+	uint32_t *coff = nullptr, *crep = nullptr, *cfirst = nullptr, *oc = nullptr;
+};
+// `called`: [n] the called sites; force_tier2: every candidate allele through the wave kernels
+NestClasses nest_classes(povu_hip_ctx *ctx, const TravDevice &d, const uint8_t *called, uint32_t max_steps, bool force_tier2);
+
+// the records' nesting.  In: the flubble records before they are sorted (record j = traversal rlist[j], a reference
+// traversal of a kept site), the sites' PVST heights, the written lengths of every record's REF and of its longest allele.
+struct NestRecIn {
+	uint32_t nfl = 0;
+	const uint32_t *rlist = nullptr, *height = nullptr;
+	const uint64_t *ref_len = nullptr, *max_len = nullptr;
+	uint32_t profile = 0, max_level = 0; // POVU_HIP_PROFILE_*
+	uint64_t max_ref_length = 0, max_allele_length = 0;
+};
+// Out, per record j: level, the parent's site (NO_QUERY: none), rescued; `kept`: the n_kept records the profile keeps,
+// ascending (raw-graph: all)
+struct NestRecs {
+	uint32_t *level = nullptr, *parent_q = nullptr, *kept = nullptr;
+	uint8_t *rescued = nullptr;
+	uint32_t n_kept = 0;
+	uint64_t n_enclosed = 0, n_popped = 0, n_rescued = 0;
+};
+NestRecs nest_records(povu_hip_ctx *ctx, const TravDevice &d, const NestIndex &ix, const NestRecIn &in);
+
+} // namespace povu_hip

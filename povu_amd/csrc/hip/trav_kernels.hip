@@ -22,7 +22,7 @@
 //                   hash); every member of a run is compared step by step with the run's first member, and a run with a
 //                   mismatch (a hash collision) is grouped exactly by one lane; an allele is numbered by the scan of the
 //                   "first of its group" flags in traversal order, and its steps are copied once from that traversal.
-#include "query_common.hpp"
+#include "exact_groups.hpp"
 
 namespace povu_hip
 {
@@ -31,17 +31,6 @@ static constexpr uint32_t T_PER_LANE = 16;		 // steps per lane of the start-task
 static constexpr uint32_t T_TILE = Q_TPB * T_PER_LANE; // steps per workgroup of the start-task passes
 static constexpr uint32_t T1_STEPS = 64;		 // steps tier 1 looks at before it hands a scan over
 static constexpr uint8_t TS_LONG = POVU_HIP_TRAV_LONG, TS_STRAY = POVU_HIP_TRAV_STRAY, TS_OPEN = POVU_HIP_TRAV_OPEN;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) // splitmix64's finaliser
-{
-	x ^= x >> 30;
-	x *= 0xbf58476d1ce4e5b9ull;
-	x ^= x >> 27;
-	x *= 0x94d049bb133111ebull;
-	x ^= x >> 31;
-	return x;
-}
-__device__ __forceinline__ uint64_t step_hash(uint32_t k, uint32_t side) { return mix64(((uint64_t)k << 32) | side); }
 
 // ---- paths: segment ids -> step words (the ids were copied into `steps`, mapped in place); the lowest step whose id the
 // graph does not have is kept in *bad
@@ -324,30 +313,6 @@ __global__ void k_tr_query_off(uint32_t n, uint32_t R, const uint32_t *__restric
 	off[q] = lo;
 }
 
-// sort keys through the current permutation: which = 0 hash low word, 1 hash high word, 2 length, 3 query
-__global__ void k_tr_sort_key(uint32_t R, int which, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ rhash,
-			      const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ rq, uint32_t *__restrict__ key)
-{
-	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB) {
-		const uint32_t t = perm ? perm[k] : k;
-		key[k] = which == 0 ? (uint32_t)rhash[t] : which == 1 ? (uint32_t)(rhash[t] >> 32) : which == 2 ? rlen[t] : rq[t];
-	}
-}
-
-// run heads of the sorted order: (query, length, hash) differs from the previous one; mark[k] = k + 1 at a head
-__global__ void k_tr_heads(uint32_t R, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ rhash,
-			   const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ rq, uint32_t *__restrict__ mark)
-{
-	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB) {
-		bool head = k == 0;
-		if (!head) {
-			const uint32_t a = perm[k], b = perm[k - 1];
-			head = rq[a] != rq[b] || rlen[a] != rlen[b] || rhash[a] != rhash[b];
-		}
-		mark[k] = head ? k + 1 : 0;
-	}
-}
-
 __device__ __forceinline__ bool same_sequence(const uint32_t *__restrict__ steps, uint64_t pa, uint64_t pb, uint32_t len)
 {
 	const bool ra = (pa & ROLE_BIT) != 0, rb = (pb & ROLE_BIT) != 0;
@@ -359,62 +324,13 @@ __device__ __forceinline__ bool same_sequence(const uint32_t *__restrict__ steps
 	return true;
 }
 
-// every member of a run against the run's first member: rep[k] = the head, or NO_QUERY and the run flagged bad
-__global__ void k_tr_check(uint32_t R, const uint32_t *__restrict__ steps, const uint32_t *__restrict__ perm,
-			   const uint32_t *__restrict__ hmax /* exclusive running max of mark */, const uint32_t *__restrict__ mark,
-			   const uint64_t *__restrict__ rpos, const uint32_t *__restrict__ rlen, uint32_t *__restrict__ head,
-			   uint32_t *__restrict__ rep, uint8_t *__restrict__ bad)
-{
-	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB) {
-		const uint32_t h = max(hmax[k], mark[k]) - 1;
-		head[k] = h;
-		if (h == k) {
-			rep[k] = k;
-			continue;
-		}
-		const uint32_t a = perm[k], b = perm[h];
-		if (same_sequence(steps, rpos[a], rpos[b], rlen[a])) {
-			rep[k] = h;
-		} else {
-			rep[k] = NO_QUERY;
-			bad[h] = 1; // (cleared by a memset before the launch)
-		}
-	}
-}
-
-// a run with a mismatch, grouped exactly by one lane: every member either equals an earlier representative or becomes one
-__global__ void k_tr_regroup(uint32_t nb, const uint32_t *__restrict__ bad_heads, uint32_t R, const uint32_t *__restrict__ steps,
-			     const uint32_t *__restrict__ perm, const uint32_t *__restrict__ head, const uint64_t *__restrict__ rpos,
-			     const uint32_t *__restrict__ rlen, uint32_t *__restrict__ rep, unsigned long long *__restrict__ splits)
-{
-	const uint32_t i = blockIdx.x * Q_TPB + threadIdx.x;
-	if (i >= nb)
-		return;
-	const uint32_t h = bad_heads[i];
-	uint32_t n_new = 0;
-	for (uint32_t k = h + 1; k < R && head[k] == h; k++) {
-		if (rep[k] == h)
-			continue;
-		const uint32_t a = perm[k];
-		uint32_t r = k;
-		for (uint32_t e = h + 1; e < k; e++)
-			if (rep[e] == e && same_sequence(steps, rpos[a], rpos[perm[e]], rlen[a])) {
-				r = e;
-				break;
-			}
-		rep[k] = r;
-		n_new += r == k;
-	}
-	atomicAdd(splits, (unsigned long long)n_new);
-}
-
-// first[t] = 1 when traversal t is the first of its group (its representative)
-__global__ void k_tr_first(uint32_t R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, uint32_t *__restrict__ first)
-{
-	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB)
-		if (rep[k] == k)
-			first[perm[k]] = 1;
-}
+// traversals a and b (of one query and length) spell the same step sequence
+struct SameTraversal {
+	const uint32_t *steps;
+	const uint64_t *rpos;
+	const uint32_t *rlen;
+	__device__ __forceinline__ bool operator()(uint32_t a, uint32_t b) const { return same_sequence(steps, rpos[a], rpos[b], rlen[a]); }
+};
 
 // allele of every traversal (global numbering: aidx of its group's first traversal); the first traversal of every allele
 __global__ void k_tr_allele(uint32_t R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, const uint32_t *__restrict__ aidx,
@@ -479,15 +395,6 @@ __global__ __launch_bounds__(Q_TPB) void k_tr_allele_steps(uint32_t n_al, const 
 static void check_32(uint64_t v, const char *what)
 {
 	refuse_2_32(v, "the traversals need ", what, " for now (the scans and sorts here are 32-bit)");
-}
-
-static uint32_t hash_bits_hook()
-{
-	const char *e = std::getenv("POVU_HIP_TRAV_HASH_BITS"); // (test hook: fewer bits make collisions happen)
-	if (!e || !*e)
-		return 64;
-	const long b = std::strtol(e, nullptr, 10);
-	return b < 1 ? 1 : b > 64 ? 64 : (uint32_t)b;
 }
 
 } // namespace povu_hip
@@ -730,28 +637,9 @@ static void dedup(const TravParams &p, const TravBoundary &b, const TravTasks &t
 	KLAUNCH(k_tr_query_off, dim3(lane_blocks(n1)), dim3(Q_TPB), 0, s, n, R, g.rq, g.toff);
 	if (!R)
 		return;
-	launch_iota(R, pa, s);
-	LsdSort sort{pa, pb, key, kout, R, g.tmp, g.tmp_bytes, s};
-	auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
-		KLAUNCH(k_tr_sort_key, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, which, perm, rhash, g.rlen, g.rq, k);
-	};
-	sort.pass(0, std::min(hbits, 32u), write_key);
-	if (hbits > 32)
-		sort.pass(1, hbits - 32, write_key);
-	sort.pass(2, bits_for(p.max_steps), write_key);
-	sort.pass(3, bits_for(n), write_key);
-	const uint32_t *sp = g.sp = sort.cur;
-	KLAUNCH(k_tr_heads, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, sp, rhash, g.rlen, g.rq, mark);
-	scan_exclusive_max_u32(mark, hmax, R, g.tmp, g.tmp_bytes, s);
-	HIP_CHECK(hipMemsetAsync(rbad, 0, R1, s));
-	HIP_CHECK(hipMemsetAsync(b.tot, 0, 16, s));
-	KLAUNCH(k_tr_check, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, ctx->path_steps, sp, hmax, mark, g.rpos, g.rlen, head, g.rep, rbad);
-	compact_flagged_u8(rbad, R, blist, words + 4, g.tmp, g.tmp_bytes, s);
-	const uint32_t nb = read_back(words + 4, s);
-	if (nb) {
-		KLAUNCH(k_tr_regroup, dim3(lane_blocks(nb)), dim3(Q_TPB), 0, s, nb, blist, R, ctx->path_steps, sp, head, g.rpos, g.rlen, g.rep, b.tot + 1);
-		HIP_CHECK(copy_async(&g.n_splits, b.tot + 1, 8, hipMemcpyDeviceToHost, s));
-	}
+	GroupWs gw{pa, pb, key, kout, mark, hmax, head, g.rep, blist, rbad, g.tmp, g.tmp_bytes};
+	g.sp = group_exact(R, g.rq, g.rlen, rhash, hbits, bits_for(p.max_steps), bits_for(n), SameTraversal{ctx->path_steps, g.rpos, g.rlen}, gw,
+			   words + 4, b.tot + 1, &g.n_splits, s);
 }
 
 // an allele per group, numbered in traversal order; the alleles of every query; their step offsets
@@ -762,7 +650,7 @@ static void alleles(const TravParams &p, const TravBoundary &b, const TravTasks 
 	const size_t R1 = (size_t)R + 1;
 	if (R) {
 		HIP_CHECK(hipMemsetAsync(g.firstf, 0, R1 * 4, s));
-		KLAUNCH(k_tr_first, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, g.sp, g.rep, g.firstf);
+		KLAUNCH(k_eg_first, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, g.sp, g.rep, g.firstf);
 		scan_exclusive_u32(g.firstf, g.aidx, R1, g.tmp, g.tmp_bytes, s);
 		HIP_CHECK(copy_async(&g.n_al, g.aidx + R, 4, hipMemcpyDeviceToHost, s));
 		KLAUNCH(k_tr_allele, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, g.sp, g.rep, g.aidx, g.rlen, g.rallele, g.afirst, g.alen);

@@ -28,6 +28,8 @@ struct CallArgs {
 	std::vector<std::string> prefixes;
 	bool to_stdout = true;
 	bool inversions = false; // --inversions: SUBR records too (INTEGRATION.md "Inversion calls")
+	bool nested = false;	 // --nested, or implied by a profile (INTEGRATION.md "Nested calls")
+	povu_hip_call_profile_opts prof{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 };
 
 CallArgs parse_call_args(const std::vector<std::string> &a)
@@ -40,6 +42,21 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 		if (i + 1 >= a.size())
 			throw std::runtime_error("Flag '" + a[i] + "' requires an argument but received none");
 		return a[++i];
+	};
+	// `--name <n>` or `--name=<n>`, n a decimal number
+	uint64_t n64 = 0;
+	auto number = [&](size_t &i, const std::string &name, uint64_t &out) {
+		std::string v;
+		if (a[i] == name)
+			v = need(i);
+		else if (!a[i].compare(0, name.size() + 1, name + "="))
+			v = a[i].substr(name.size() + 1);
+		else
+			return false;
+		if (v.empty() || !std::all_of(v.begin(), v.end(), [](char ch) { return ch >= '0' && ch <= '9'; }) || v.size() > 18)
+			throw std::runtime_error("Flag '" + name + "' expects a number, not " + v);
+		out = std::stoull(v);
+		return true;
 	};
 	for (size_t i = 0; i < a.size(); i++) {
 		const std::string &x = a[i];
@@ -57,6 +74,26 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			c.to_stdout = true;
 		} else if (x == "--inversions") {
 			c.inversions = true;
+		} else if (x == "--nested") {
+			c.nested = true;
+		} else if (x == "--profile" || !x.compare(0, 10, "--profile=")) {
+			const std::string v = x == "--profile" ? need(i) : x.substr(10);
+			if (v == "raw-graph")
+				c.prof.profile = POVU_HIP_PROFILE_RAW_GRAPH;
+			else if (v == "top-level-only")
+				c.prof.profile = POVU_HIP_PROFILE_TOP_LEVEL_ONLY;
+			else if (v == "popped")
+				c.prof.profile = POVU_HIP_PROFILE_POPPED;
+			else
+				throw std::runtime_error("Flag '--profile' expects raw-graph, top-level-only or popped, not " + v);
+		} else if (number(i, "--max-level", n64)) {
+			if (n64 > 0x7FFFFFFFull)
+				throw std::runtime_error("Flag '--max-level' is too large");
+			c.prof.max_level = (uint32_t)n64;
+		} else if (number(i, "--max-ref-length", n64)) {
+			c.prof.max_ref_length = n64;
+		} else if (number(i, "--max-allele-length", n64)) {
+			c.prof.max_allele_length = n64;
 		} else if (x == "-c" || x == "--chunk-size" || x == "-q" || x == "--queue-length") {
 			need(i); // (streaming has no meaning here: accepted and ignored)
 		} else if (x == "-g" || x == "--restrict" || !x.compare(0, 11, "--restrict=")) {
@@ -171,15 +208,15 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 		fail("paths");
 	if (povu_hip_segments_upload(ctx, V, seq_off.data(), seq.data(), err, sizeof err) != 0)
 		fail("sequences");
-	const povu_hip_trav_opts opts{0, ca.inversions ? POVU_HIP_T_INVERSIONS : 0u};
-	povu_hip_calls *c = povu_hip_call(ctx, sites, &nm->refs, nm->slot_of_path, &opts, err, sizeof err);
+	const povu_hip_trav_opts opts{0, (ca.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (ca.nested ? POVU_HIP_T_NESTED : 0u)};
+	povu_hip_calls *c = povu_hip_call_profile(ctx, sites, &nm->refs, nm->slot_of_path, &opts, &ca.prof, err, sizeof err);
 	if (!c)
 		fail("call");
 
 	// ---- the files: one VCF of every reference (--stdout), or <dir>/<prefix>.vcf per prefix with its references' records
 	auto write = [&](std::ostream &os, const char *only) {
 		size_t len = 0;
-		char *text = povu_hip_calls_vcf(c, sites, nm, names.data(), nullptr, only, (uint32_t)std::max(1, cfg.threads), &len);
+		char *text = povu_hip_calls_vcf_profile(c, sites, nm, names.data(), nullptr, only, (uint32_t)std::max(1, cfg.threads), ca.prof.profile, &len);
 		if (!text)
 			throw std::runtime_error("cannot format the calls as VCF");
 		os.write(text, (std::streamsize)len);

@@ -3,7 +3,7 @@
 //   povu [--version] [-v <int>] [-t <int>] decompose -i <gfa> [-o <dir>] [-h|--hairpins] [-s|--subflubbles]
 //   povu ... decompose ... --structure-export <json>   (additive: writes the flubble debug sidecar gfa2vcf writes)
 //   povu ... gfa2vcf -i <gfa> [-h] [-s] [--structure-export <json>] <options of `call`>   (app/cli/cli.cpp:154-193)
-//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions]   (the
+//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--profile <p>]   (the
 //   variant calls of INTEGRATION.md "Variant calls" and "Inversion calls", on the GPU)
 #include "decompose.hpp"
 
@@ -64,6 +64,13 @@ static void usage(std::ostream &os)
 	      "        --stdout                          one VCF of every reference path to stdout [default]\n"
 	      "        --inversions                      also call inversions: a VARTYPE=SUBR record for every stretch of two or more\n"
 	      "                                          steps of a reference path that another path walks backwards [default: false]\n"
+	      "        --nested                          alleles modulo enclosed sites, LV and PS by the nesting of traversals\n"
+	      "                                          (INTEGRATION.md \"Nested calls\") [default: false]\n"
+	      "        --profile=[raw-graph|top-level-only|popped]\n"
+	      "                                          which records to keep (any but raw-graph implies --nested) [default: raw-graph]\n"
+	      "        --max-level=[n]                   popped: the deepest level kept without rescue [default: 0]\n"
+	      "        --max-ref-length=[n], --max-allele-length=[n]\n"
+	      "                                          popped: a record with a longer REF / allele is big (0: no limit) [default: 0]\n"
 	      "        -c, -q                            accepted and ignored (no streaming here)\n";
 }
 

@@ -30,6 +30,21 @@ const char *VCF_HEADER =
 	"##INFO=<ID=TANGLED,Number=1,Type=String,Description=\"Variant lies in a tangled region of the graph: T or F\">\n"
 	"##INFO=<ID=LV,Number=1,Type=Integer,Description=\"Level in the PVST (0=top level)\">\n"
 	"##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
+// a nested call's own line ("Nested calls"), and the lines of the keys a profile appends (the reference fixture's texts)
+const char *PS_LINE = "##INFO=<ID=PS,Number=1,Type=String,Description=\"ID of the enclosing record of the same reference path\">\n";
+const char *PROFILE_NAME[] = {"raw-graph", "top-level-only", "popped"};
+const char *PROFILE_LINES[] = {
+	"",
+	"##INFO=<ID=ORIGIN,Number=1,Type=String,Description=\"Raw record id\">\n"
+	"##INFO=<ID=PROFILE,Number=1,Type=String,Description=\"Downstream profile name\">\n"
+	"##INFO=<ID=PASSTHROUGH,Number=1,Type=String,Description=\"Record was kept without allele rewrite\">\n",
+	"##INFO=<ID=ORIGIN,Number=1,Type=String,Description=\"Raw record id\">\n"
+	"##INFO=<ID=PARENT,Number=1,Type=String,Description=\"Raw parent record id\">\n"
+	"##INFO=<ID=PROFILE,Number=1,Type=String,Description=\"Downstream profile name\">\n"
+	"##INFO=<ID=PASSTHROUGH,Number=1,Type=String,Description=\"Record was kept without allele rewrite\">\n"
+	"##INFO=<ID=RESCUED_CHILD,Number=1,Type=String,Description=\"Child was kept because its parent was popped\">\n"
+	"##INFO=<ID=POPPED_PARENT,Number=1,Type=String,Description=\"Popped parent id that enabled rescue\">\n",
+};
 
 // (sample, hap) of a path name: `sample#hap#rest` with an all-digit hap, any other name a sample of its own with hap -1
 std::pair<std::string, long long> pansn(const std::string &n)
@@ -187,16 +202,47 @@ extern "C" void povu_hip_sites_free(povu_hip_sites *s)
 	free(s);
 }
 
+namespace
+{
+char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names, const char *const *path_name,
+		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len);
+}
+
 extern "C" char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
 				    const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, size_t *len)
+{
+	// a caller of before may hold a povu_hip_calls that ends with n_inv_tier2: nothing behind it is read
+	return calls_vcf(c, sites, names, path_name, date, only_prefix, threads, POVU_HIP_PROFILE_RAW_GRAPH, false, len);
+}
+
+extern "C" char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
+					    const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads,
+					    uint32_t profile, size_t *len)
+{
+	return calls_vcf(c, sites, names, path_name, date, only_prefix, threads, profile, true, len);
+}
+
+namespace
+{
+char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names, const char *const *path_name,
+		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len)
 try {
-	if (!c || !sites || !names || !path_name || !len || c->n_slots != names->refs.n_slots || c->n_refs != names->refs.n_refs)
+	if (!c || !sites || !names || !path_name || !len || c->n_slots != names->refs.n_slots || c->n_refs != names->refs.n_refs ||
+	    profile > POVU_HIP_PROFILE_POPPED)
 		return nullptr;
+	// the fields of "Nested calls", absent (NULL) for the entry of before and where a hand-made record leaves them out
+	const uint32_t *level = nested_fields ? c->level : nullptr, *parent_query = nested_fields ? c->parent_query : nullptr;
+	const uint64_t *ref_spelled = nested_fields ? c->ref_spelled : nullptr;
+	const bool nested = nested_fields && c->nested;
 	const uint64_t n = c->n_records, S = c->n_slots;
 	const uint32_t P = names->n_paths, n_samples = names->refs.n_samples;
 	for (uint64_t i = 0; i < n; i++) {
 		const bool subr = c->flags[i] & POVU_HIP_CALL_SUBR; // (its query is POVU_HIP_NIL: it belongs to no site)
 		if ((!subr && c->query[i] >= sites->n) || c->path[i] >= P || (subr && (c->n_alleles[i] != 2 || c->ref_allele[i] != 0)))
+			return nullptr;
+		if (parent_query && parent_query[i] != POVU_HIP_NIL && parent_query[i] >= sites->n)
+			return nullptr;
+		if (ref_spelled && ref_spelled[i] >= c->n_spelled)
 			return nullptr;
 	}
 	std::vector<uint32_t> slot_first(n_samples + 1, 0); // (the slots of a sample are consecutive)
@@ -214,7 +260,10 @@ try {
 		date = today;
 	}
 	// ---- header, a contig line per reference path of the prefix, the column line
-	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER;
+	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile];
+	auto site_label = [&](uint32_t q) {
+		return (sites->or1[q] ? "<" : ">") + std::to_string(sites->id1[q]) + (sites->or2[q] ? "<" : ">") + std::to_string(sites->id2[q]);
+	};
 	std::vector<char> keep(P, 0);
 	for (uint32_t r = 0; r < names->refs.n_refs; r++) {
 		const uint32_t p = names->refs.ref_path[r];
@@ -236,7 +285,7 @@ try {
 		std::string &o = chunk[t];
 		const uint64_t lo = n * t / T, hi = n * (t + 1) / T;
 		std::vector<uint64_t> order;
-		std::string label;
+		std::string label, parent;
 		char num[32];
 		for (uint64_t i = lo; i < hi; i++) {
 			if (!keep[c->path[i]])
@@ -244,7 +293,7 @@ try {
 			const uint32_t q = c->query[i], na = c->n_alleles[i], ra = c->ref_allele[i];
 			const uint64_t b = c->block_off[c->block[i]];
 			order.clear();
-			order.push_back(b + ra); // REF first, the others in the query's allele order
+			order.push_back(ref_spelled ? ref_spelled[i] : b + ra); // REF first, the others in the query's allele order
 			for (uint32_t a = 0; a < na; a++)
 				if (a != ra)
 					order.push_back(b + a);
@@ -264,13 +313,21 @@ try {
 				if (at < end && *at == '<' && last > at && last[-1] == '<')
 					label[0] = label[first_end - at] = '>';
 			} else {
-				label = (sites->or1[q] ? "<" : ">") + std::to_string(sites->id1[q]) + (sites->or2[q] ? "<" : ">") + std::to_string(sites->id2[q]);
+				label = site_label(q);
 			}
+			const bool has_parent = !subr && parent_query && parent_query[i] != POVU_HIP_NIL;
+			if (has_parent)
+				parent = site_label(parent_query[i]);
+			const bool rescued = !subr && profile == POVU_HIP_PROFILE_POPPED && (f & POVU_HIP_CALL_RESCUED);
 			o += path_name[c->path[i]];
 			o += '\t';
 			o += std::to_string(c->pos[i]);
 			o += '\t';
 			o += label;
+			if (!subr && profile == POVU_HIP_PROFILE_TOP_LEVEL_ONLY)
+				o += ":top";
+			if (rescued)
+				o += ":rescued";
 			for (size_t k = 0; k < order.size(); k++) {
 				o += k <= 1 ? '\t' : ',';
 				o.append(c->seq + c->seq_off[order[k]], c->seq_off[order[k] + 1] - c->seq_off[order[k]]);
@@ -294,8 +351,19 @@ try {
 			}
 			o += subr ? ";VARTYPE=SUBR" : (f & POVU_HIP_CALL_INS) ? ";VARTYPE=INS" : (f & POVU_HIP_CALL_DEL) ? ";VARTYPE=DEL" : ";VARTYPE=SUB";
 			o += (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
-			if (!subr)
-				o += ";ES=" + label + ";LV=" + std::to_string((long)sites->height[q] - 1);
+			if (!subr) {
+				o += ";ES=" + label + ";LV=" + std::to_string(level ? (long)(int32_t)level[i] : (long)sites->height[q] - 1);
+				if (nested && has_parent)
+					o += ";PS=" + parent;
+				if (profile != POVU_HIP_PROFILE_RAW_GRAPH) {
+					o += ";ORIGIN=" + label;
+					if (rescued)
+						o += ";PARENT=" + (has_parent ? parent : std::string(".")) + ";PROFILE=" + PROFILE_NAME[profile] +
+						     ";RESCUED_CHILD=T;POPPED_PARENT=" + (has_parent ? parent : std::string("."));
+					else
+						o += std::string(";PROFILE=") + PROFILE_NAME[profile] + ";PASSTHROUGH=T";
+				}
+			}
 			o += "\tGT";
 			const uint16_t *row = c->gt + i * S;
 			for (uint32_t sm = 0; sm < n_samples; sm++) {
@@ -342,3 +410,4 @@ try {
 } catch (const std::bad_alloc &) {
 	return nullptr;
 }
+} // namespace

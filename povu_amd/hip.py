@@ -104,6 +104,18 @@ class _Calls(C.Structure):
                 [(k, C.c_uint64) for k in ("n_inv_records", "n_inv_heads", "n_inv_long", "n_inv_tier2")])
 
 
+class _CallsNested(_Calls):
+    """povu_hip_calls as povu_hip_call makes it now: the fields of "Nested calls" behind those above (povu_hip_calls_vcf, the
+    entry of before, reads none of them; povu_hip_calls_vcf_profile does)."""
+    _fields_ = ([("level", C.POINTER(C.c_uint32)), ("parent_query", C.POINTER(C.c_uint32)), ("ref_spelled", C.POINTER(C.c_uint64))] +
+                [(k, C.c_uint64) for k in ("n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "nested")])
+
+
+class _ProfileOpts(C.Structure):
+    _fields_ = [("profile", C.c_uint32), ("max_level", C.c_uint32), ("max_ref_length", C.c_uint64),
+                ("max_allele_length", C.c_uint64)]
+
+
 class _StageTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("launches", C.c_uint32)]
 
@@ -127,7 +139,9 @@ W_FORCE_TIER2 = 1  # HipDecomposer.walks: every query through the second-tier ke
 WALK_MORE, WALK_LONG, WALK_BUDGET = 1, 2, 4  # status bits of a query
 T_FORCE_TIER2 = 1  # HipDecomposer.traversals: every scan through the wave-per-scan kernel (tests)
 T_INVERSIONS = 2  # HipDecomposer.call: inversion (SUBR) records too (INTEGRATION.md "Inversion calls")
+T_NESTED = 4  # HipDecomposer.call: alleles modulo enclosed sites, levels and parents by geometry (INTEGRATION.md "Nested calls")
 TRAV_LONG, TRAV_STRAY, TRAV_OPEN = 1, 2, 4  # status bits of a query
+PROFILES = {"raw-graph": 0, "top-level-only": 1, "popped": 2}  # HipDecomposer.call(profile=...)
 
 _lib = None
 
@@ -186,7 +200,13 @@ def load_lib():
     l.povu_hip_segments_upload.restype = C.c_int
     l.povu_hip_call.argtypes = [C.c_void_p, C.POINTER(_Sites), C.POINTER(_CallRefs), C.POINTER(C.c_uint32), C.POINTER(_TravOpts),
                                 C.c_char_p, C.c_size_t]
-    l.povu_hip_call.restype = C.POINTER(_Calls)
+    l.povu_hip_call.restype = C.POINTER(_CallsNested)
+    l.povu_hip_call_profile.argtypes = [C.c_void_p, C.POINTER(_Sites), C.POINTER(_CallRefs), C.POINTER(C.c_uint32), C.POINTER(_TravOpts),
+                                        C.POINTER(_ProfileOpts), C.c_char_p, C.c_size_t]
+    l.povu_hip_call_profile.restype = C.POINTER(_CallsNested)
+    l.povu_hip_calls_vcf_profile.argtypes = [C.POINTER(_CallsNested), C.POINTER(_Sites), C.POINTER(_CallNames), C.POINTER(C.c_char_p),
+                                             C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
+    l.povu_hip_calls_vcf_profile.restype = C.c_void_p
     l.povu_hip_calls_free.argtypes = [C.POINTER(_Calls)]
     l.povu_hip_call_names_make.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_char_p,
                                            C.c_size_t]
@@ -671,6 +691,8 @@ class Shards:
 
 CALL_ANCHORED, CALL_TANGLED, CALL_INS, CALL_DEL = 1, 2, 4, 8
 CALL_SUBR = 16  # an inversion record: query 0xFFFFFFFF, first / n_steps the inverted run of its reference path
+CALL_COLLAPSED = 32  # nested: the site has fewer classes than exact alleles (TANGLED too)
+CALL_RESCUED = 64  # `popped` profile: kept above max_level because its ancestors were popped
 GT_MISSING = 0xFFFF
 
 
@@ -697,8 +719,9 @@ class Calls:
     """Variant calls (HipDecomposer.call): numpy views of the flat arrays of povu_hip_call, valid as long as this object
     lives, and vcf_text().  It keeps the names record (povu_hip_call_names) and the sites it was made from alive."""
 
-    def __init__(self, lib, ptr, names, names_rec, name_array, sites):
+    def __init__(self, lib, ptr, names, names_rec, name_array, sites, profile="raw-graph"):
         self._lib, self._p = lib, ptr
+        self.profile = profile
         self._names_rec, self._name_array, self._sites = names_rec, name_array, sites
         c, nr = ptr.contents, names_rec.contents
         self.names = names
@@ -724,6 +747,13 @@ class Calls:
         self.n_steps = _view(c.n_steps, n, np.uint32)
         self.n_inv_records, self.n_inv_heads = int(c.n_inv_records), int(c.n_inv_heads)
         self.n_inv_long, self.n_inv_tier2 = int(c.n_inv_long), int(c.n_inv_tier2)
+        # "Nested calls": LV, the enclosing record's site (0xFFFFFFFF: none), REF among the spelled alleles; the counters
+        self.level = _view(c.level, n, np.uint32)
+        self.parent_query = _view(c.parent_query, n, np.uint32)
+        self.ref_spelled = _view(c.ref_spelled, n, np.uint64)
+        self.nested = bool(c.nested)
+        self.n_enclosed, self.n_collapsed_sites = int(c.n_enclosed), int(c.n_collapsed_sites)
+        self.n_popped, self.n_rescued = int(c.n_popped), int(c.n_rescued)
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -733,13 +763,15 @@ class Calls:
             self._lib.povu_hip_call_names_free(self._names_rec)
             self._names_rec = None
 
-    def vcf_text(self, date=None, only=None, threads: int = 1) -> str:
-        """One VCF of every reference path (povu_hip_calls_vcf): header (fileDate today unless given), contig lines, records;
-        with `only` those of the reference paths whose name starts with it."""
+    def vcf_text(self, date=None, only=None, threads: int = 1, profile=None) -> str:
+        """One VCF of every reference path (povu_hip_calls_vcf_profile): header (fileDate today unless given), contig lines,
+        records; with `only` those of the reference paths whose name starts with it.  profile: the one the call was made
+        under unless given."""
         ln = C.c_size_t(0)
-        p = self._lib.povu_hip_calls_vcf(self._p, self._sites._p, self._names_rec, self._name_array,
-                                         None if date is None else str(date).encode(), None if only is None else only.encode(),
-                                         threads, C.byref(ln))
+        p = self._lib.povu_hip_calls_vcf_profile(self._p, self._sites._p, self._names_rec, self._name_array,
+                                                 None if date is None else str(date).encode(),
+                                                 None if only is None else only.encode(), threads,
+                                                 PROFILES[self.profile if profile is None else profile], C.byref(ln))
         if not p:
             raise RuntimeError("the calls, sites and names do not belong together")
         s = C.string_at(p, ln.value).decode()
@@ -929,10 +961,16 @@ class HipDecomposer:
         if self._lib.povu_hip_segments_upload(self._ctx, len(raw), off.ctypes.data, blob.ctypes.data, err, 512) != 0:
             raise RuntimeError(err.value.decode())
 
-    def call(self, forest: Forest, refs, max_steps: int = 65536, flags: int = 0) -> Calls:
+    def call(self, forest: Forest, refs, max_steps: int = 65536, flags: int = 0, profile=None, max_level: int = 0,
+             max_ref_length: int = 0, max_allele_length: int = 0) -> Calls:
         """The variant calls of `forest` (INTEGRATION.md "Variant calls") with the resident paths whose names start with one
         of the prefixes `refs` as references, on the GPU (paths and sequences uploaded first).  flags: T_FORCE_TIER2,
-        T_INVERSIONS (the SUBR records of "Inversion calls" merged in: Calls.n_steps, flags & CALL_SUBR, the n_inv_* counters)."""
+        T_INVERSIONS (the SUBR records of "Inversion calls" merged in: Calls.n_steps, flags & CALL_SUBR, the n_inv_* counters),
+        T_NESTED ("Nested calls": records count classes of alleles modulo enclosed sites; Calls.level, parent_query,
+        ref_spelled, flags & CALL_COLLAPSED, the counters).  profile: None or one of PROFILES; any but "raw-graph" implies
+        T_NESTED and keeps what INTEGRATION.md says ("popped": max_level, max_ref_length, max_allele_length, 0 = no limit)."""
+        if profile is not None and profile not in PROFILES:
+            raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names
         if isinstance(refs, str):
             refs = [refs]
@@ -945,13 +983,15 @@ class HipDecomposer:
         try:
             sites = forest.sites()
             o = _TravOpts(max_steps, flags)
-            p = self._lib.povu_hip_call(self._ctx, sites._p, C.byref(nr.contents.refs), nr.contents.slot_of_path, C.byref(o), err, 512)
+            po = _ProfileOpts(PROFILES[profile or "raw-graph"], max_level, max_ref_length, max_allele_length)
+            p = self._lib.povu_hip_call_profile(self._ctx, sites._p, C.byref(nr.contents.refs), nr.contents.slot_of_path, C.byref(o),
+                                                C.byref(po) if profile is not None else None, err, 512)
             if not p:
                 raise RuntimeError(err.value.decode())
         except Exception:
             self._lib.povu_hip_call_names_free(nr)
             raise
-        return Calls(self._lib, p, names, nr, name_array, sites)
+        return Calls(self._lib, p, names, nr, name_array, sites, profile or "raw-graph")
 
     def traversals(self, forest: Forest, max_steps: int = 65536, flags: int = 0) -> Traversals:
         """The traversals of every flubble of `forest` by the resident paths, on the GPU."""

@@ -619,3 +619,78 @@ def inverted_haplotypes(paths: Paths, n: int, min_len: int, max_len: int, seed: 
         ids[a:b] = ids[a:b][::-1].copy()
         rev[a:b] = 1 - rev[a:b][::-1]
     return Paths(list(paths.names), paths.off.copy(), ids, rev)
+
+
+def _skip_template(depth: int, width: int):
+    """One unit of skip_nested in local numbering (creation order = path order): per segment the skip decisions that remove
+    it and its SNP (number, branch) or (-1, 0); the links; the number of decisions and SNPs."""
+    anc, snp, links, n_dec, n_snp = [], [], [], [0], [0]
+
+    def seg(a, s=(-1, 0)):
+        anc.append(a)
+        snp.append(s)
+        return len(anc) - 1
+
+    def unit(d, a):
+        dec = n_dec[0]
+        n_dec[0] += 1
+        e = seg(a)
+        inner = a + (dec,)
+        prev = seg(inner)  # (a spacer: with it the PVST keeps the chain's sites beside the unit, not under it)
+        links.append((e, prev))
+        for _ in range(width):
+            if d == 0:
+                s = n_snp[0]
+                n_snp[0] += 1
+                first, x, y, last = seg(inner), seg(inner, (s, 0)), seg(inner, (s, 1)), seg(inner)
+                links.extend([(first, x), (first, y), (x, last), (y, last)])
+            else:
+                first, last = unit(d - 1, inner)
+            links.append((prev, first))
+            prev = last
+        z = seg(a)
+        links.extend([(prev, z), (e, z)])
+        return e, z
+    unit(depth, ())
+    return anc, snp, links, n_dec[0], n_snp[0]
+
+
+def skip_nested(n_units: int, depth: int, seed: int = 0, width: int = 2) -> Links:
+    """Nested sites that no PVST nests ("Nested calls"): a unit is an entry segment, a spacer, a chain of `width` links, an
+    exit segment and a skip link from entry to exit; a link of the chain is a unit of depth - 1, at depth 0 a two-way SNP bubble
+    (a, x | y, b).  `n_units` units joined end to end, ids 1.. in path order; 3 + 4 width segments a unit at depth 0,
+    3 + width times the size below at every depth above.  (`seed` is unused: the shape is fixed; skip_haplotypes draws.)"""
+    anc, _, links, _, _ = _skip_template(depth, width)
+    size = len(anc)
+    base = size * np.arange(n_units, dtype=np.int64)[:, None]
+    la = np.array(links, dtype=np.int64)
+    src = (base + la[:, 0][None, :]).reshape(-1)
+    dst = (base + la[:, 1][None, :]).reshape(-1)
+    join = size * np.arange(1, n_units, dtype=np.int64)
+    return from_plus_links(np.arange(1, size * n_units + 1, dtype=np.uint32), np.concatenate([src, join - 1]),
+                           np.concatenate([dst, join]))
+
+
+def skip_haplotypes(n_units: int, depth: int, n: int, seed: int, width: int = 2) -> Paths:
+    """`n` haplotypes of skip_nested(n_units, depth): each walks the units and takes every skip it meets with probability
+    1/4, every SNP branch with probability 1/2; PanSN names, one sample a haplotype (`hap<k>#1#chr1`).  Vectorised over the
+    units of a haplotype."""
+    anc, snp, _, n_dec, n_snp = _skip_template(depth, width)
+    size = len(anc)
+    rng = np.random.default_rng(seed)
+    ids = np.arange(1, size * n_units + 1, dtype=np.uint32).reshape(n_units, size)
+    snp_id = np.array([s[0] for s in snp])
+    snp_br = np.array([s[1] for s in snp])
+    pieces = []
+    for _ in range(n):
+        skip = rng.random((n_units, n_dec)) < 0.25
+        branch = rng.integers(0, 2, size=(n_units, max(n_snp, 1)))
+        present = np.ones((n_units, size), dtype=bool)
+        for k in range(size):
+            for d in anc[k]:
+                present[:, k] &= ~skip[:, d]
+            if snp_id[k] >= 0:
+                present[:, k] &= branch[:, snp_id[k]] == snp_br[k]
+        w = ids[present]
+        pieces.append((w, np.zeros(w.size, dtype=np.uint8)))
+    return _paths([f"hap{h}#1#chr1" for h in range(n)], pieces)
