@@ -441,6 +441,9 @@ typedef struct {
  * the `popped` profile kept the record although its level is above max_level, because its ancestors were popped */
 #define POVU_HIP_CALL_COLLAPSED 32u
 #define POVU_HIP_CALL_RESCUED 64u
+/* under POVU_HIP_PROFILE_LEFT_NORMALIZED: the record was changed by the left-normalisation (pos is the normalised POS, its
+ * normalised alleles are those of block norm_block) */
+#define POVU_HIP_CALL_NORMALIZED 128u
 #define POVU_HIP_GT_MISSING 0xFFFFu
 typedef struct {
 	uint64_t n_records, n_slots, n_blocks, n_spelled, n_seq_bytes, n_at_bytes, n_refs;
@@ -476,6 +479,16 @@ typedef struct {
 	uint64_t n_popped;	      /* `popped` profile: records reached and dropped as big */
 	uint64_t n_rescued;	      /* `popped` profile: records kept above max_level (POVU_HIP_CALL_RESCUED) */
 	uint64_t nested;	      /* 1: made with POVU_HIP_T_NESTED (the VCF carries PS) */
+	/* per record ("Left-normalised calls").  Outside POVU_HIP_PROFILE_LEFT_NORMALIZED, and for a record it left unchanged:
+	 * raw_pos = pos, norm_block = POVU_HIP_NIL, the others 0.  A changed record (POVU_HIP_CALL_NORMALIZED) keeps block and
+	 * ref_spelled (its raw alleles and every AT string) and has a block norm_block of n_alleles spelled alleles of its own,
+	 * REF first and the ALTs in the order they are written, that hold the normalised texts (their AT strings are empty) */
+	const uint64_t *raw_pos;	     /* [n_records] POS before the normalisation */
+	const uint32_t *norm_block;	     /* [n_records] */
+	const uint32_t *norm_shift, *norm_chop, *norm_trim; /* [n_records] s, r and u of the closed form */
+	uint64_t n_normalized;		     /* records with POVU_HIP_CALL_NORMALIZED */
+	uint64_t max_shift;		     /* the largest norm_shift */
+	uint64_t n_norm_compared;	     /* bases the backward walks compared, over every (record, ALT) */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
@@ -493,13 +506,17 @@ povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, co
 #define POVU_HIP_PROFILE_RAW_GRAPH 0u
 #define POVU_HIP_PROFILE_TOP_LEVEL_ONLY 1u
 #define POVU_HIP_PROFILE_POPPED 2u
+/* "Left-normalised calls": every record is kept, an indel is moved to the left end of its repeat and common bases are
+ * chopped and trimmed.  Does not imply POVU_HIP_T_NESTED (may be combined with it and with _T_INVERSIONS); max_level and the
+ * lengths are ignored */
+#define POVU_HIP_PROFILE_LEFT_NORMALIZED 3u
 typedef struct {
 	uint32_t profile; /* POVU_HIP_PROFILE_* */
 	uint32_t max_level;
 	uint64_t max_ref_length, max_allele_length;
 } povu_hip_call_profile_opts;
-/* povu_hip_call under a profile (NULL: povu_hip_call itself).  A profile other than _RAW_GRAPH implies POVU_HIP_T_NESTED;
- * an unknown profile is refused */
+/* povu_hip_call under a profile (NULL: povu_hip_call itself).  _TOP_LEVEL_ONLY and _POPPED imply POVU_HIP_T_NESTED; an unknown
+ * profile is refused */
 povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
 				      const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile,
 				      char *err, size_t errlen);
@@ -581,7 +598,11 @@ char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, c
  * _TOP_LEVEL_ONLY every flubble record's ID gets `:top` and its INFO ORIGIN, PROFILE and PASSTHROUGH, under _POPPED a rescued
  * record's ID gets `:rescued` and its INFO ORIGIN, PARENT, PROFILE, RESCUED_CHILD and POPPED_PARENT, any other ORIGIN,
  * PROFILE and PASSTHROUGH; the ##INFO lines of those keys stand before the contig lines.  level, parent_query and
- * ref_spelled may be NULL (a hand-made povu_hip_calls): then the plain call's values hold.  NULL for an unknown profile */
+ * ref_spelled may be NULL (a hand-made povu_hip_calls): then the plain call's values hold.  Under _LEFT_NORMALIZED a record
+ * with POVU_HIP_CALL_NORMALIZED is written with POS, REF and ALT normalised, `:norm` behind its ID and ORIGIN, RAW_ALT_INDEX,
+ * PROFILE, LEFT_NORMALIZED, RAW_POS, RAW_REF and RAW_ALT behind LV (or PS), any other record as the raw call writes it; raw_pos
+ * or norm_block NULL: no record was changed.  Under the other profiles the fields behind `nested` are not read.  NULL for an
+ * unknown profile */
 char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
 				 const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, uint32_t profile,
 				 size_t *len);

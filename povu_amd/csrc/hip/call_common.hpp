@@ -7,6 +7,10 @@
 namespace povu_hip
 {
 
+// what differs per flubble record before the sort (call_kernels.hip "rstate"): anchored, REF without an inner base, REF spelled
+// on its own, changed by the left-normalisation (norm_kernels.hip)
+static constexpr uint8_t RS_ANCHORED = 1, RS_REF_EMPTY = 2, RS_OWN_REF = 4, RS_NORMALIZED = 8;
+
 // complement of a nucleotide code (ACGTN, lower case, IUPAC), 0 for any other byte
 __device__ __forceinline__ uint8_t comp(uint8_t c)
 {

@@ -23,6 +23,7 @@
 // spelled on its own (an "extra" one-allele block behind the class blocks).  A block is a (site, anchored, orientation).
 #include "call_common.hpp"
 #include "nest_kernels.hpp"
+#include "norm_kernels.hpp"
 
 namespace povu_hip
 {
@@ -184,7 +185,6 @@ __global__ void k_cl_collapsed(uint32_t n, const uint32_t *__restrict__ keep, co
 			atomicAdd(count, 1u);
 	}
 }
-static constexpr uint8_t RS_ANCHORED = 1, RS_REF_EMPTY = 2, RS_OWN_REF = 4;
 // per flubble record j (before the sort): rstate; the inner bases and AT width of its REF (xilen, xatl: the reference's own
 // exact allele); with want_len the written lengths of REF and of its longest allele.  crep == NULL: not nested (alleles, REF
 // always the block's).
@@ -362,6 +362,8 @@ __global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, const uint3
 				f |= POVU_HIP_CALL_TANGLED | POVU_HIP_CALL_COLLAPSED;
 			if (rescued && rescued[j])
 				f |= POVU_HIP_CALL_RESCUED;
+			if (rstate[j] & RS_NORMALIZED)
+				f |= POVU_HIP_CALL_NORMALIZED;
 			flags[i] = f;
 		}
 	}
@@ -559,8 +561,9 @@ namespace
 {
 struct CallsOwner {
 	povu_hip_calls view{}; // first member: the owner is recovered from it in povu_hip_calls_free
-	PinnedVec<uint32_t> query, path, first, ref_allele, n_alleles, an, ns, block, ac, n_steps, level, parent_query;
-	PinnedVec<uint64_t> pos, ac_off, block_off, seq_off, at_off, ref_spelled;
+	PinnedVec<uint32_t> query, path, first, ref_allele, n_alleles, an, ns, block, ac, n_steps, level, parent_query, norm_block, norm_shift, norm_chop,
+		norm_trim;
+	PinnedVec<uint64_t> pos, ac_off, block_off, seq_off, at_off, ref_spelled, raw_pos;
 	PinnedVec<uint8_t> flags;
 	PinnedVec<uint16_t> gt;
 	PinnedVec<char> seq, at;
@@ -576,7 +579,7 @@ struct CallInputs {
 	const uint32_t *slot_of_path;
 	const povu_hip_trav_opts *opts;
 	uint32_t n, P, nR, S, NS, n_trees = 0;
-	bool inversions, nested;
+	bool inversions, nested, normalized;
 	povu_hip_call_profile_opts prof; // (raw-graph without a profile)
 	std::vector<uint32_t> ref_of_path, slot_first, qa, qz; // reference number of every path (NO_QUERY: none), first slot of every sample, the queries
 	std::vector<uint8_t> qor;
@@ -605,6 +608,8 @@ struct CallWs {
 	size_t tmp_bytes;
 	uint32_t nQ = 0, nfl = 0; // kept sites, flubble records
 	uint32_t *smin, *smax;
+	NormIn ni; // left-normalized profile: what the normalisation read, and per flubble record what it found
+	NormRecs nm;
 };
 // the inversion records and where the flubble records go in the one list
 struct CallInv {
@@ -621,6 +626,9 @@ struct CallRecs {
 	InvRows rows;
 	uint32_t *need, *boff, *blist;
 	uint64_t *ac_off, *bcnt, *block_off;
+	NormRows nrows; // left-normalized profile: the rows' fields, the blocks of the changed records (nb0 on, nn of them, from spelled allele nsp0)
+	uint32_t nb0 = 0, nn = 0;
+	uint64_t nsp0 = 0;
 };
 // cl_spell and cl_bytes
 struct CallSpelled {
@@ -647,8 +655,11 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 	const uint32_t n = in.n, P = in.P, nR = in.nR, S = in.S, NS = in.NS;
 	in.inversions = opts && (opts->flags & POVU_HIP_T_INVERSIONS);
 	in.prof = profile ? *profile : povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
-	if (in.prof.profile > POVU_HIP_PROFILE_POPPED)
+	if (in.prof.profile > POVU_HIP_PROFILE_LEFT_NORMALIZED)
 		throw HipError("unknown profile " + std::to_string(in.prof.profile));
+	in.normalized = in.prof.profile == POVU_HIP_PROFILE_LEFT_NORMALIZED; // (keeps every record, ignores the limits, implies nothing)
+	if (in.normalized)
+		in.prof = povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 	in.nested = (opts && (opts->flags & POVU_HIP_T_NESTED)) || in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH;
 	if (n >= 0x7FFFFFFFu)
 		throw HipError("too many sites");
@@ -817,6 +828,17 @@ void slot_table(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, Ca
 		KLAUNCH(k_cl_slots, dim3(stride_blocks(d.R)), dim3(Q_TPB), 0, s, d.R, d.rq, d.op, w.oa, w.keep, w.qidx, w.d_slot, in.S, w.smin, w.smax);
 }
 
+// left-normalized profile: chop, shift and trim of every flubble record, its POS moved before the sort keys are made
+void normalisation(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
+{
+	NormIn &ni = w.ni;
+	ni.nfl = w.nfl_all;
+	ni.rlist = w.rlist, ni.rq = d.rq, ni.op = d.op, ni.aoff = w.aoff, ni.oa = w.oa, ni.afirst = w.afirst, ni.rlen = d.rlen;
+	ni.orv = d.orv, ni.rpos = d.rpos, ni.ilen = w.ilen, ni.xilen = w.xilen, ni.rstate = w.rstate, ni.pos = w.pos;
+	ni.nR = in.nR, ni.ref_of_path = w.d_ref_of_path, ni.ref_path = w.d_ref_path, ni.ref_base = w.d_ref_base, ni.roff = w.roff;
+	w.nm = norm_records(ctx, ni);
+}
+
 // flag, compact, POS, the sort by (reference, POS)
 void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
 {
@@ -838,6 +860,8 @@ void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &
 		ctx->path_steps, ctx->seq_off, ctx->g.vid, w.ilen, w.atl, w.zc, filter ? 1u : 0u, w.rstate, w.xilen, w.xatl, w.ref_len, w.max_len);
 	KLAUNCH(k_cl_pos, dim3(stride_blocks(nfl_all)), dim3(Q_TPB), 0, s, nfl_all, w.rlist, d.rq, d.op, d.of, w.d_ref_of_path, w.d_ref_base, w.roff, w.rstate,
 		w.pos);
+	if (in.normalized)
+		normalisation(ctx, in, d, w);
 	if (in.nested) {
 		NestRecIn ri;
 		ri.nfl = nfl_all, ri.rlist = w.rlist, ri.height = w.d_height, ri.ref_len = w.ref_len, ri.max_len = w.max_len;
@@ -898,6 +922,7 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d,
 	const InvDevice &iv = inv.v;
 	const size_t r1 = (size_t)nrec + 1, n2 = 4 * (size_t)n + 1, f1 = (size_t)nfl + 1;
 	InvRows &o = r.rows;
+	NormRows &nw = r.nrows;
 	uint64_t *s64;
 	carve(ctx->cl_rec, [&](Spans &take) {
 		take(r1, o.o_q, o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_an, o.o_ns, o.o_block, o.o_nsteps, o.o_pos, o.nalt, r.ac_off, o.o_flags);
@@ -905,8 +930,10 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d,
 		take(f1, r.xneed, r.xoff, r.xlist);
 		take((size_t)nrec * in.S + 1, o.gt);
 		take(n2, r.need, r.boff, r.blist);
-		take(n2 + nfl + iv.n, r.bcnt, r.block_off);
-		take(scan_exclusive_u64_tmp(std::max(r1, n2 + nfl + iv.n)), s64);
+		take(n2 + 2 * (size_t)nfl + iv.n, r.bcnt, r.block_off);
+		take(scan_exclusive_u64_tmp(std::max(r1, n2 + 2 * (size_t)nfl + iv.n)), s64);
+		take(in.normalized ? r1 : 1, nw.o_raw_pos, nw.o_block, nw.o_shift, nw.o_chop, nw.o_trim);
+		take(in.normalized ? f1 : 1, nw.need, nw.off, nw.list);
 	});
 	HIP_CHECK(hipMemsetAsync(o.o_nsteps, 0, r1 * 4, s));
 	HIP_CHECK(hipMemsetAsync(r.need, 0, n2 * 4, s));
@@ -920,6 +947,18 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d,
 			o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_pos, o.nalt, r.need, inv.f_dst, w.rstate, w.d_height, in.nested ? w.nr.level : nullptr,
 			in.nested ? w.nr.parent_q : nullptr, r.o_level, r.o_parent, r.xneed);
 	inv_fields(ctx, inv.in, iv, o);
+	if (in.normalized) {
+		// every row as an unchanged record's (the inversion records stay so), then the flubble records' own
+		HIP_CHECK(hipMemsetAsync(nw.o_block, 0xFF, r1 * 4, s));
+		HIP_CHECK(hipMemsetAsync(nw.o_shift, 0, r1 * 4, s));
+		HIP_CHECK(hipMemsetAsync(nw.o_chop, 0, r1 * 4, s));
+		HIP_CHECK(hipMemsetAsync(nw.o_trim, 0, r1 * 4, s));
+		if (nrec)
+			HIP_CHECK(copy_async(nw.o_raw_pos, o.o_pos, (size_t)nrec * 8, hipMemcpyDeviceToDevice, s));
+		norm_row_fields(ctx, w.ni, w.nm, nfl, w.perm, inv.f_dst, nw);
+		scan_exclusive_u32(nw.need, nw.off, f1, w.tmp, w.tmp_bytes, s);
+		HIP_CHECK(copy_async(&r.nn, nw.off + nfl, 4, hipMemcpyDeviceToHost, s));
+	}
 	scan_exclusive_u64(o.nalt, r.ac_off, r1, s64, s);
 	HIP_CHECK(copy_async(&r.n_ac, r.ac_off + nrec, 8, hipMemcpyDeviceToHost, s));
 	scan_exclusive_u32(r.need, r.boff, n2, w.tmp, w.tmp_bytes, s);
@@ -936,15 +975,21 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d,
 	refuse_2_32((uint64_t)r.nfc + nx, "the call needs ", "blocks");
 	const uint32_t nfc = r.nfc, nfb = r.nfb = nfc + nx;
 	refuse_2_32((uint64_t)nfb + iv.n, "the call needs ", "blocks");
-	const uint32_t nb = r.nb = nfb + iv.n;
+	// the blocks of the normalised records follow them all
+	const uint32_t nb0 = r.nb0 = nfb + iv.n;
+	refuse_2_32((uint64_t)nb0 + r.nn, "the call needs ", "blocks");
+	const uint32_t nb = r.nb = nb0 + r.nn;
 	HIP_CHECK(hipMemsetAsync(r.bcnt + nb, 0, 8, s));
 	if (nfc)
 		KLAUNCH(k_cl_block_cnt, dim3(stride_blocks(nfc)), dim3(Q_TPB), 0, s, nfc, r.blist, w.aoff, r.bcnt);
 	if (nx)
 		KLAUNCH(k_cl_extra, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rstate, r.xoff, r.xlist, r.bcnt + nfc);
 	inv_genotypes(ctx, inv.in, iv, o, nfb, r.bcnt);
+	if (r.nn)
+		norm_blocks(ctx, w.ni, nfl, w.perm, inv.f_dst, nw, nb0, r.bcnt);
 	scan_exclusive_u64(r.bcnt, r.block_off, (size_t)nb + 1, s64, s);
 	HIP_CHECK(copy_async(&r.nsp, r.block_off + nb, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(&r.nsp0, r.block_off + nb0, 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(copy_async(&r.nfsp, r.block_off + nfb, 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
 }
@@ -983,6 +1028,8 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, cons
 	if (nfsp)
 		KLAUNCH(k_cl_spell_len, dim3(stride_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, T, ctx->seq_off, g.vid, slen, alen);
 	inv_spell_len(ctx, inv.in, iv, slen + nfsp, alen + nfsp);
+	if (r.nn)
+		norm_spell_len(ctx, w.ni, w.nm, r.nrows, r.nn, r.block_off + r.nb0, nsp - r.nsp0, slen + r.nsp0, alen + r.nsp0);
 	scan_exclusive_u64(slen, sp.sp_off, nsp + 1, s64, s);
 	scan_exclusive_u64(alen, sp.at_off, nsp + 1, s64, s);
 	HIP_CHECK(copy_async(sp.nbytes, sp.sp_off + nsp, 8, hipMemcpyDeviceToHost, s));
@@ -992,6 +1039,8 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, cons
 	if (nfsp)
 		KLAUNCH(k_cl_emit, dim3(wave_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, T, ctx->seq_off, ctx->seq, g.vid, sp.sp_off, sp.at_off, sp.o_seq, sp.o_at, bad);
 	inv_emit(ctx, inv.in, iv, sp.sp_off + nfsp, sp.at_off + nfsp, sp.o_seq, sp.o_at, bad);
+	if (r.nn)
+		norm_emit(ctx, w.ni, w.nm, r.nrows, r.nn, r.block_off + r.nb0, nsp - r.nsp0, sp.sp_off + r.nsp0, sp.o_seq, bad);
 	if (r.nrec)
 		KLAUNCH(k_cl_ref_spelled, dim3(stride_blocks(r.nrec)), dim3(Q_TPB), 0, s, r.nrec, o.o_block, o.o_ref, r.xrow, r.block_off, r.nfc, r.ref_spelled);
 	uint64_t hbad = 0;
@@ -1035,7 +1084,22 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	hand_off(o->at_off, nsp + 1, sp.at_off, nsp + 1, ctx);
 	hand_off(o->seq, sp.nbytes[0], sp.o_seq, sp.nbytes[0], ctx);
 	hand_off(o->at, sp.nbytes[1], sp.o_at, sp.nbytes[1], ctx);
+	const NormRows &nw = r.nrows;
+	if (in.normalized) {
+		hand_off(o->raw_pos, nrec, nw.o_raw_pos, nrec, ctx);
+		hand_off(o->norm_block, nrec, nw.o_block, nrec, ctx);
+		hand_off(o->norm_shift, nrec, nw.o_shift, nrec, ctx);
+		hand_off(o->norm_chop, nrec, nw.o_chop, nrec, ctx);
+		hand_off(o->norm_trim, nrec, nw.o_trim, nrec, ctx);
+	}
 	o->view.device_ms = timer.stop(ctx->stream);
+	if (!in.normalized) { // nothing was normalised: the fields say so, filled here
+		o->raw_pos.assign(o->pos.data(), o->pos.data() + nrec);
+		o->norm_block.assign(nrec, POVU_HIP_NIL);
+		o->norm_shift.assign(nrec, 0u);
+		o->norm_chop.assign(nrec, 0u);
+		o->norm_trim.assign(nrec, 0u);
+	}
 	o->contig_len.resize(nR);
 	for (uint32_t k = 0; k < nR; k++)
 		o->contig_len[k] = sp.h_roff[k + 1] - sp.h_roff[k];
@@ -1057,6 +1121,9 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	v.level = o->level.data(), v.parent_query = o->parent_query.data(), v.ref_spelled = o->ref_spelled.data();
 	v.nested = in.nested ? 1 : 0;
 	v.n_enclosed = w.nr.n_enclosed, v.n_collapsed_sites = w.n_collapsed, v.n_popped = w.nr.n_popped, v.n_rescued = w.nr.n_rescued;
+	v.raw_pos = o->raw_pos.data(), v.norm_block = o->norm_block.data(), v.norm_shift = o->norm_shift.data();
+	v.norm_chop = o->norm_chop.data(), v.norm_trim = o->norm_trim.data();
+	v.n_normalized = w.nm.n_changed, v.max_shift = w.nm.max_shift, v.n_norm_compared = w.nm.n_compared;
 	CallsOwner *raw = o.release();
 	return &raw->view;
 }

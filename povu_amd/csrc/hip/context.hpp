@@ -344,6 +344,7 @@ struct povu_hip_ctx {
 	// povu_hip_call with POVU_HIP_T_INVERSIONS (inv_kernels.hip): the step index and head counts / the run heads, runs and
 	// records / the rows of the flubble records in the merged list
 	Arena iv_ws, iv_heads, iv_rows;
+	Arena nm_ws; // left-normalisation (norm_kernels.hip)
 	// povu_hip_call with POVU_HIP_T_NESTED (nest_kernels.hip): the index of the called sites' traversals / the classes / the
 	// scratch of both / the records' parents, levels and the profile's choice
 	Arena ns_idx, ns_cls, ns_ws, ns_rec;

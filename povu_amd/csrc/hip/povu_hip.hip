@@ -197,6 +197,7 @@ extern "C" int povu_hip_release_workspace(povu_hip_ctx *ctx)
 	ctx->iv_ws.release();
 	ctx->iv_heads.release();
 	ctx->iv_rows.release();
+	ctx->nm_ws.release();
 	return 0;
 }
 

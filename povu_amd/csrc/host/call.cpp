@@ -84,8 +84,10 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 				c.prof.profile = POVU_HIP_PROFILE_TOP_LEVEL_ONLY;
 			else if (v == "popped")
 				c.prof.profile = POVU_HIP_PROFILE_POPPED;
+			else if (v == "left-normalized")
+				c.prof.profile = POVU_HIP_PROFILE_LEFT_NORMALIZED;
 			else
-				throw std::runtime_error("Flag '--profile' expects raw-graph, top-level-only or popped, not " + v);
+				throw std::runtime_error("Flag '--profile' expects raw-graph, top-level-only, popped or left-normalized, not " + v);
 		} else if (number(i, "--max-level", n64)) {
 			if (n64 > 0x7FFFFFFFull)
 				throw std::runtime_error("Flag '--max-level' is too large");

@@ -66,8 +66,9 @@ static void usage(std::ostream &os)
 	      "                                          steps of a reference path that another path walks backwards [default: false]\n"
 	      "        --nested                          alleles modulo enclosed sites, LV and PS by the nesting of traversals\n"
 	      "                                          (INTEGRATION.md \"Nested calls\") [default: false]\n"
-	      "        --profile=[raw-graph|top-level-only|popped]\n"
-	      "                                          which records to keep (any but raw-graph implies --nested) [default: raw-graph]\n"
+	      "        --profile=[raw-graph|top-level-only|popped|left-normalized]\n"
+	      "                                          which records to keep (top-level-only and popped imply --nested); left-normalized\n"
+	      "                                          keeps all and moves every indel to the left end of its repeat [default: raw-graph]\n"
 	      "        --max-level=[n]                   popped: the deepest level kept without rescue [default: 0]\n"
 	      "        --max-ref-length=[n], --max-allele-length=[n]\n"
 	      "                                          popped: a record with a longer REF / allele is big (0: no limit) [default: 0]\n"

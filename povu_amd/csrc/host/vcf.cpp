@@ -32,7 +32,7 @@ const char *VCF_HEADER =
 	"##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
 // a nested call's own line ("Nested calls"), and the lines of the keys a profile appends (the reference fixture's texts)
 const char *PS_LINE = "##INFO=<ID=PS,Number=1,Type=String,Description=\"ID of the enclosing record of the same reference path\">\n";
-const char *PROFILE_NAME[] = {"raw-graph", "top-level-only", "popped"};
+const char *PROFILE_NAME[] = {"raw-graph", "top-level-only", "popped", "left-normalized"};
 const char *PROFILE_LINES[] = {
 	"",
 	"##INFO=<ID=ORIGIN,Number=1,Type=String,Description=\"Raw record id\">\n"
@@ -44,6 +44,14 @@ const char *PROFILE_LINES[] = {
 	"##INFO=<ID=PASSTHROUGH,Number=1,Type=String,Description=\"Record was kept without allele rewrite\">\n"
 	"##INFO=<ID=RESCUED_CHILD,Number=1,Type=String,Description=\"Child was kept because its parent was popped\">\n"
 	"##INFO=<ID=POPPED_PARENT,Number=1,Type=String,Description=\"Popped parent id that enabled rescue\">\n",
+	// "Left-normalised calls" (RAW_ALT_INDEX and RAW_ALT per ALT: a record here may have several)
+	"##INFO=<ID=ORIGIN,Number=1,Type=String,Description=\"Raw record id\">\n"
+	"##INFO=<ID=RAW_ALT_INDEX,Number=A,Type=Integer,Description=\"Raw ALT index\">\n"
+	"##INFO=<ID=PROFILE,Number=1,Type=String,Description=\"Downstream profile name\">\n"
+	"##INFO=<ID=LEFT_NORMALIZED,Number=1,Type=String,Description=\"Record was left-normalized\">\n"
+	"##INFO=<ID=RAW_POS,Number=1,Type=Integer,Description=\"Raw POS before profile rewrite\">\n"
+	"##INFO=<ID=RAW_REF,Number=1,Type=String,Description=\"Raw REF before profile rewrite\">\n"
+	"##INFO=<ID=RAW_ALT,Number=A,Type=String,Description=\"Raw ALT before profile rewrite\">\n",
 };
 
 // (sample, hap) of a path name: `sample#hap#rest` with an all-digit hap, any other name a sample of its own with hap -1
@@ -228,12 +236,14 @@ char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu
 		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len)
 try {
 	if (!c || !sites || !names || !path_name || !len || c->n_slots != names->refs.n_slots || c->n_refs != names->refs.n_refs ||
-	    profile > POVU_HIP_PROFILE_POPPED)
+	    profile > POVU_HIP_PROFILE_LEFT_NORMALIZED)
 		return nullptr;
 	// the fields of "Nested calls", absent (NULL) for the entry of before and where a hand-made record leaves them out
 	const uint32_t *level = nested_fields ? c->level : nullptr, *parent_query = nested_fields ? c->parent_query : nullptr;
 	const uint64_t *ref_spelled = nested_fields ? c->ref_spelled : nullptr;
 	const bool nested = nested_fields && c->nested;
+	// the fields of "Left-normalised calls", read under that profile alone (absent: no record was changed)
+	const bool normalized = nested_fields && profile == POVU_HIP_PROFILE_LEFT_NORMALIZED && c->raw_pos && c->norm_block;
 	const uint64_t n = c->n_records, S = c->n_slots;
 	const uint32_t P = names->n_paths, n_samples = names->refs.n_samples;
 	for (uint64_t i = 0; i < n; i++) {
@@ -243,6 +253,9 @@ try {
 		if (parent_query && parent_query[i] != POVU_HIP_NIL && parent_query[i] >= sites->n)
 			return nullptr;
 		if (ref_spelled && ref_spelled[i] >= c->n_spelled)
+			return nullptr;
+		if (normalized && (c->flags[i] & POVU_HIP_CALL_NORMALIZED) &&
+		    (subr || c->norm_block[i] >= c->n_blocks || c->block_off[c->norm_block[i]] + c->n_alleles[i] > c->n_spelled))
 			return nullptr;
 	}
 	std::vector<uint32_t> slot_first(n_samples + 1, 0); // (the slots of a sample are consecutive)
@@ -319,6 +332,8 @@ try {
 			if (has_parent)
 				parent = site_label(parent_query[i]);
 			const bool rescued = !subr && profile == POVU_HIP_PROFILE_POPPED && (f & POVU_HIP_CALL_RESCUED);
+			const bool norm = normalized && (f & POVU_HIP_CALL_NORMALIZED);
+			const uint64_t nbase = norm ? c->block_off[c->norm_block[i]] : 0; // (its alleles in written order)
 			o += path_name[c->path[i]];
 			o += '\t';
 			o += std::to_string(c->pos[i]);
@@ -328,9 +343,12 @@ try {
 				o += ":top";
 			if (rescued)
 				o += ":rescued";
+			if (norm)
+				o += ":norm";
 			for (size_t k = 0; k < order.size(); k++) {
+				const uint64_t sa = norm ? nbase + k : order[k];
 				o += k <= 1 ? '\t' : ',';
-				o.append(c->seq + c->seq_off[order[k]], c->seq_off[order[k] + 1] - c->seq_off[order[k]]);
+				o.append(c->seq + c->seq_off[sa], c->seq_off[sa + 1] - c->seq_off[sa]);
 			}
 			o += "\t60\tPASS\tAC=";
 			const uint64_t a0 = c->ac_off[i], a1 = c->ac_off[i + 1];
@@ -355,7 +373,16 @@ try {
 				o += ";ES=" + label + ";LV=" + std::to_string(level ? (long)(int32_t)level[i] : (long)sites->height[q] - 1);
 				if (nested && has_parent)
 					o += ";PS=" + parent;
-				if (profile != POVU_HIP_PROFILE_RAW_GRAPH) {
+				if (norm) {
+					o += ";ORIGIN=" + label + ";RAW_ALT_INDEX=";
+					for (size_t k = 1; k < order.size(); k++)
+						o += (k > 1 ? "," : "") + std::to_string(k);
+					o += ";PROFILE=left-normalized;LEFT_NORMALIZED=T;RAW_POS=" + std::to_string(c->raw_pos[i]);
+					for (size_t k = 0; k < order.size(); k++) {
+						o += k == 0 ? ";RAW_REF=" : k == 1 ? ";RAW_ALT=" : ",";
+						o.append(c->seq + c->seq_off[order[k]], c->seq_off[order[k] + 1] - c->seq_off[order[k]]);
+					}
+				} else if (profile != POVU_HIP_PROFILE_RAW_GRAPH && profile != POVU_HIP_PROFILE_LEFT_NORMALIZED) {
 					o += ";ORIGIN=" + label;
 					if (rescued)
 						o += ";PARENT=" + (has_parent ? parent : std::string(".")) + ";PROFILE=" + PROFILE_NAME[profile] +

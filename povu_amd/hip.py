@@ -108,7 +108,11 @@ class _CallsNested(_Calls):
     """povu_hip_calls as povu_hip_call makes it now: the fields of "Nested calls" behind those above (povu_hip_calls_vcf, the
     entry of before, reads none of them; povu_hip_calls_vcf_profile does)."""
     _fields_ = ([("level", C.POINTER(C.c_uint32)), ("parent_query", C.POINTER(C.c_uint32)), ("ref_spelled", C.POINTER(C.c_uint64))] +
-                [(k, C.c_uint64) for k in ("n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "nested")])
+                [(k, C.c_uint64) for k in ("n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "nested")] +
+                # "Left-normalised calls"
+                [("raw_pos", C.POINTER(C.c_uint64))] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("norm_block", "norm_shift", "norm_chop", "norm_trim")] +
+                [(k, C.c_uint64) for k in ("n_normalized", "max_shift", "n_norm_compared")])
 
 
 class _ProfileOpts(C.Structure):
@@ -141,7 +145,7 @@ T_FORCE_TIER2 = 1  # HipDecomposer.traversals: every scan through the wave-per-s
 T_INVERSIONS = 2  # HipDecomposer.call: inversion (SUBR) records too (INTEGRATION.md "Inversion calls")
 T_NESTED = 4  # HipDecomposer.call: alleles modulo enclosed sites, levels and parents by geometry (INTEGRATION.md "Nested calls")
 TRAV_LONG, TRAV_STRAY, TRAV_OPEN = 1, 2, 4  # status bits of a query
-PROFILES = {"raw-graph": 0, "top-level-only": 1, "popped": 2}  # HipDecomposer.call(profile=...)
+PROFILES = {"raw-graph": 0, "top-level-only": 1, "popped": 2, "left-normalized": 3}  # HipDecomposer.call(profile=...)
 
 _lib = None
 
@@ -693,6 +697,7 @@ CALL_ANCHORED, CALL_TANGLED, CALL_INS, CALL_DEL = 1, 2, 4, 8
 CALL_SUBR = 16  # an inversion record: query 0xFFFFFFFF, first / n_steps the inverted run of its reference path
 CALL_COLLAPSED = 32  # nested: the site has fewer classes than exact alleles (TANGLED too)
 CALL_RESCUED = 64  # `popped` profile: kept above max_level because its ancestors were popped
+CALL_NORMALIZED = 128  # `left-normalized` profile: the record was changed (INTEGRATION.md "Left-normalised calls")
 GT_MISSING = 0xFFFF
 
 
@@ -754,6 +759,13 @@ class Calls:
         self.nested = bool(c.nested)
         self.n_enclosed, self.n_collapsed_sites = int(c.n_enclosed), int(c.n_collapsed_sites)
         self.n_popped, self.n_rescued = int(c.n_popped), int(c.n_rescued)
+        # "Left-normalised calls": POS before the normalisation, the block of the normalised alleles (0xFFFFFFFF: unchanged),
+        # shift s, chop r and trim u; the counters
+        self.raw_pos = _view(c.raw_pos, n, np.uint64)
+        for k in ("norm_block", "norm_shift", "norm_chop", "norm_trim"):
+            setattr(self, k, _view(getattr(c, k), n, np.uint32))
+        self.n_normalized, self.max_shift = int(c.n_normalized), int(c.max_shift)
+        self.n_norm_compared = int(c.n_norm_compared)
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -967,8 +979,10 @@ class HipDecomposer:
         of the prefixes `refs` as references, on the GPU (paths and sequences uploaded first).  flags: T_FORCE_TIER2,
         T_INVERSIONS (the SUBR records of "Inversion calls" merged in: Calls.n_steps, flags & CALL_SUBR, the n_inv_* counters),
         T_NESTED ("Nested calls": records count classes of alleles modulo enclosed sites; Calls.level, parent_query,
-        ref_spelled, flags & CALL_COLLAPSED, the counters).  profile: None or one of PROFILES; any but "raw-graph" implies
-        T_NESTED and keeps what INTEGRATION.md says ("popped": max_level, max_ref_length, max_allele_length, 0 = no limit)."""
+        ref_spelled, flags & CALL_COLLAPSED, the counters).  profile: None or one of PROFILES; "top-level-only" and "popped"
+        imply T_NESTED and keep what INTEGRATION.md says ("popped": max_level, max_ref_length, max_allele_length, 0 = no
+        limit); "left-normalized" implies nothing, keeps every record and left-normalises it ("Left-normalised calls":
+        Calls.raw_pos, norm_block, norm_shift, norm_chop, norm_trim, flags & CALL_NORMALIZED, the counters)."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names

@@ -694,3 +694,69 @@ def skip_haplotypes(n_units: int, depth: int, n: int, seed: int, width: int = 2)
         w = ids[present]
         pieces.append((w, np.zeros(w.size, dtype=np.uint8)))
     return _paths([f"hap{h}#1#chr1" for h in range(n)], pieces)
+
+
+_RC = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
+
+
+def _tandem_plan(n_units: int, seed: int, max_copies: int, max_seg: int):
+    """The units of tandem_indels: (sequence of every segment, ids 1.. in path order; per unit the steps every haplotype
+    walks [(id, rev), ...] and the id of its bubble's segment, which follows them; the id of the closing segment)."""
+    rng = np.random.default_rng(seed)
+    seqs, units = [], []
+
+    def seg(text, rev=0):
+        seqs.append(text.encode().translate(_RC)[::-1].decode() if rev else text)
+        return (len(seqs), rev)
+    for _ in range(n_units):
+        steps = [seg("".join("ACGT"[k] for k in rng.integers(0, 4, size=int(rng.integers(2, 9)))))]
+        period = int(rng.integers(1, 7))
+        motif = "".join("ACGT"[k] for k in rng.integers(0, 4, size=period))
+        part = int(rng.integers(0, period))
+        text = motif[period - part:] + motif * int(rng.integers(2, max_copies + 1))
+        at = 0
+        while at < len(text):
+            ln = 1 if rng.random() < 0.5 else int(rng.integers(1, max_seg + 1))
+            piece = text[at:at + ln]
+            at += len(piece)
+            if rng.random() < 0.1:
+                piece = piece.lower()
+            steps.append(seg(piece, int(at < len(text) and rng.random() < 0.25)))  # (the last one, the site's entry, stays '+')
+        units.append((steps, seg(motif)[0]))
+    return seqs, units, seg("".join("ACGT"[k] for k in rng.integers(0, 4, size=4)))[0]
+
+
+def tandem_indels(n_units: int, seed: int, max_copies: int = 40, max_seg: int = 70):
+    """Indels at the right end of tandem repeats ("Left-normalised calls"): (graph, sequence of every segment).  A unit is a
+    flank of 2 to 8 random bases, a tandem repeat of period 1 to 6 with 2 to `max_copies` copies behind a partial one, cut
+    into segments of random lengths (half of them one base, the others up to `max_seg`; a quarter traversed '-', a tenth
+    lower case), and a bubble at the repeat's right end: one more copy of the motif, or the link that skips it.  The units
+    are joined end to end and closed by one more segment; ids 1.. in path order.  tandem_haplotypes draws the paths."""
+    seqs, units, last = _tandem_plan(n_units, seed, max_copies, max_seg)
+    v1, s1, v2, s2 = [], [], [], []
+
+    def link(a, b):
+        v1.append(a[0] - 1), s1.append(L if a[1] else R), v2.append(b[0] - 1), s2.append(R if b[1] else L)
+    for u, (steps, x) in enumerate(units):
+        for a, b in zip(steps, steps[1:]):
+            link(a, b)
+        z = units[u + 1][0][0] if u + 1 < n_units else (last, 0)
+        link(steps[-1], (x, 0)), link((x, 0), z), link(steps[-1], z)
+    return _mk(np.arange(1, len(seqs) + 1), v1, s1, v2, s2), seqs
+
+
+def tandem_haplotypes(n_units: int, seed: int, n: int, max_copies: int = 40, max_seg: int = 70) -> Paths:
+    """`n` haplotypes of tandem_indels(n_units, seed, ...): each walks the units and takes the extra copy of every bubble with
+    probability 1/2 (so the first one, as the reference, sees insertions and deletions alike); PanSN names, one sample a
+    haplotype (`hap<k>#1#chr1`)."""
+    _, units, last = _tandem_plan(n_units, seed, max_copies, max_seg)
+    rng = np.random.default_rng([seed, n])
+    pieces = []
+    for _ in range(n):
+        take = rng.random(n_units) < 0.5
+        ids, rev = [], []
+        for (steps, x), t in zip(units, take.tolist()):
+            ids += [s[0] for s in steps] + ([x] if t else [])
+            rev += [s[1] for s in steps] + ([0] if t else [])
+        pieces.append((ids + [last], rev + [0]))
+    return _paths([f"hap{h}#1#chr1" for h in range(n)], pieces)
