@@ -1,6 +1,7 @@
 // call_common.hpp -- what the flubble calls (call_kernels.hip) and the inversion calls (inv_kernels.hip) share beyond
-// query_common.hpp: nucleotide complements, decimal widths, the bases and AT strings of a step sequence (one wave each), and
-// the inversion pipeline's interface to povu_hip_call.
+// query_common.hpp: nucleotide complements, decimal widths, the bases and AT strings of a step sequence (one wave each), the
+// device views of a call, an allele as a record writes it, the layout of the blocks of spelled alleles, and the inversion
+// pipeline's interface to povu_hip_call.
 #pragma once
 #include "query_common.hpp"
 
@@ -87,14 +88,153 @@ __device__ __forceinline__ void emit_steps(uint32_t lane, uint32_t m, StepFn ste
 	}
 }
 
+// ---- the device views of a call: built once on the host (call_kernels.hip), passed to the kernels by value
+// the arrays of the traversal pipeline the call reads (TravDevice; oa and aoff are the exact alleles)
+struct TravView {
+	uint32_t R;
+	const uint32_t *rq, *op, *of, *oa, *aoff, *rlen, *qstatus;
+	const uint8_t *orv;
+	const uint64_t *rpos;
+};
+static inline TravView trav_view(const TravDevice &d) { return TravView{d.R, d.rq, d.op, d.of, d.oa, d.aoff, d.rlen, d.qstatus, d.orv, d.rpos}; }
+// the reference paths: NR reference steps, the nR reference paths concatenated ("reference index")
+struct RefView {
+	uint64_t NR;
+	uint32_t nR;
+	const uint32_t *ref_of_path, *ref_path; // [P] reference number of a path (NO_QUERY: none), [nR] path of a reference
+	const uint64_t *ref_base;		 // [nR + 1] reference index of every reference path's first step
+	const uint64_t *roff;			 // [NR + 1] bases in front of every reference step (one scan over the concatenation)
+};
+// the genotype slots
+struct SlotsView {
+	uint32_t S, NS;
+	const uint32_t *slot_of_path, *slot_first; // [P], [NS + 1]
+};
+// what the call's kernels read: the views above and the call's own tables.  What a kernel writes is a parameter of its own
+struct CallView {
+	PathsView paths;
+	TravView trav;
+	RefView ref;
+	// the alleles the call reads, per site q [aoff[q], aoff[q + 1]): the exact alleles, or with POVU_HIP_T_NESTED the classes
+	// (crep: the exact allele that represents a class, else null).  oa: allele of a traversal within its site, afirst: an
+	// allele's first traversal, ilen / atl: its inner bases and AT width
+	const uint32_t *aoff, *oa, *afirst, *crep;
+	const uint64_t *ilen, *atl;
+	// per site: kept, alleles without an inner base, PVST height
+	const uint32_t *keep, *zc, *height;
+	// per flubble record j before the sort (traversal rlist[j]): RS_*, the inner bases and AT width of its own REF, the written
+	// lengths of REF and of its longest allele, POS as the graph gives it (read-only once set) and POS as written (the sort
+	// key; the left-normalisation moves it)
+	uint32_t nfl;
+	const uint32_t *rlist;
+	const uint8_t *rstate;
+	const uint64_t *xilen, *xatl, *ref_len, *max_len, *raw_pos, *pos;
+};
+
+// inner bases and AT width of a traversal: its steps but the first and the last
+struct InnerSize {
+	uint64_t bases, at;
+};
+__device__ __forceinline__ InnerSize span_inner_size(const TravSpan &sp, const PathsView &P)
+{
+	InnerSize n{0, 0};
+	for (uint32_t k = 1; k + 1 < sp.len; k++) {
+		const uint32_t v = sp.step(P.steps, k) >> 1;
+		n.bases += P.seq_off[v + 1] - P.seq_off[v];
+		n.at += 1 + ndig(P.vid[v]);
+	}
+	return n;
+}
+
+// ---- an allele as a record writes it, in the reference's direction
+struct WrittenAllele {
+	TravSpan span;
+	bool o;		   // the reference runs Z -> S through the site
+	uint32_t anchor;   // the boundary step the reference enters by
+	bool anchored;	   // the text and the AT string begin with the anchor (RS_ANCHORED) ...
+	bool anchor_base;  // ... and its segment is not empty: the text begins with its last base,
+	uint64_t anchor_at; // which is this byte of the sequences (complemented when the anchor is a '<' step)
+	uint64_t ilen, atl; // inner bases, AT width of the inner steps
+	__device__ __forceinline__ uint32_t inner_steps() const { return span.len - 2; }
+	__device__ __forceinline__ uint32_t inner_step(const uint32_t *__restrict__ steps, uint32_t k) const
+	{
+		return o ? span.step(steps, span.len - 2 - k) ^ 1u : span.step(steps, k + 1);
+	}
+	__device__ __forceinline__ uint64_t text_len() const { return ilen + (anchor_base ? 1 : 0); }
+	__device__ __forceinline__ uint64_t at_len(const PathsView &P) const { return atl + (anchored ? 1 + ndig(P.vid[anchor >> 1]) : 0); }
+};
+// traversal t written with orientation o
+__device__ __forceinline__ WrittenAllele written_allele(const CallView &V, uint32_t t, bool o, bool anchored, uint64_t ilen, uint64_t atl)
+{
+	WrittenAllele s;
+	s.span = trav_span(V.trav.rpos, V.trav.rlen, t);
+	s.o = o;
+	s.anchor = o ? s.span.step(V.paths.steps, s.span.len - 1) ^ 1u : s.span.step(V.paths.steps, 0);
+	s.anchored = anchored;
+	s.anchor_base = false;
+	s.anchor_at = 0;
+	if (anchored) {
+		const uint64_t b0 = V.paths.seq_off[s.anchor >> 1], b1 = V.paths.seq_off[(s.anchor >> 1) + 1];
+		s.anchor_base = b1 > b0;
+		s.anchor_at = (s.anchor & 1u) ? b0 : b1 - 1;
+	}
+	s.ilen = ilen;
+	s.atl = atl;
+	return s;
+}
+// the three ways a spelled allele is found.  Allele `index` of a class block (site << 2 | anchored << 1 | orientation: the
+// block's own bit)
+__device__ __forceinline__ WrittenAllele allele_of_block(const CallView &V, uint32_t block, uint32_t index)
+{
+	const uint32_t a = V.aoff[block >> 2] + index;
+	return written_allele(V, V.afirst[a], block & 1u, (block & 2u) != 0, V.ilen[a], V.atl[a]);
+}
+// the own REF of record j (an extra block): its traversal, oriented as the traversal is
+__device__ __forceinline__ WrittenAllele own_ref_of_record(const CallView &V, uint32_t j)
+{
+	const uint32_t t = V.rlist[j];
+	return written_allele(V, t, V.trav.orv[t] != 0, (V.rstate[j] & RS_ANCHORED) != 0, V.xilen[j], V.xatl[j]);
+}
+// written allele i of record j: 0 its REF, then the other alleles of its site in order, all oriented as the record's traversal
+__device__ __forceinline__ uint32_t other_allele(const CallView &V, uint32_t j, uint32_t i)
+{
+	const uint32_t t = V.rlist[j], ra = V.oa[t];
+	return V.aoff[V.trav.rq[t]] + (i - 1 < ra ? i - 1 : i);
+}
+__device__ __forceinline__ WrittenAllele allele_of_record(const CallView &V, uint32_t j, uint32_t i)
+{
+	if (!i)
+		return own_ref_of_record(V, j);
+	const uint32_t a = other_allele(V, j, i);
+	return written_allele(V, V.afirst[a], V.trav.orv[V.rlist[j]] != 0, (V.rstate[j] & RS_ANCHORED) != 0, V.ilen[a], V.atl[a]);
+}
+
+// ---- the blocks of spelled alleles.  Four families, in this order: the class blocks [0, nfc), one per (site, anchored,
+// orientation) some record needs, an allele each of the site; the extra blocks [nfc, nfb), the one own REF of a nested record
+// that is not its class's representative; the inversion blocks [nfb, nb0), REF and ALT of an inversion record; the
+// normalised blocks [nb0, nb), the written alleles of a record the left-normalisation changed.  block_off, slen, alen,
+// sp_off and at_off run over all of them: the class and the extra blocks hold the spelled alleles [0, nfsp) (one launch
+// spells both), the inversion blocks [nfsp, nsp0), the normalised blocks [nsp0, nsp).
+struct BlockLayout {
+	uint32_t nfc = 0, nfb = 0, nb0 = 0, nb = 0;
+	uint64_t nfsp = 0, nsp0 = 0, nsp = 0;
+	struct Family {
+		uint32_t b0, nb; // first block, blocks
+		uint64_t s0, ns; // first spelled allele, spelled alleles
+	};
+	__host__ __device__ Family flubble() const { return {0, nfb, 0, nfsp}; } // class and extra blocks
+	__host__ __device__ Family inversion() const { return {nfb, nb0 - nfb, nfsp, nsp0 - nfsp}; }
+	__host__ __device__ Family normalised() const { return {nb0, nb - nb0, nsp0, nsp - nsp0}; }
+	__host__ __device__ bool is_class(uint32_t b) const { return b < nfc; }
+	__host__ __device__ uint32_t extra_block(uint32_t x) const { return nfc + x; } // of the x-th own REF
+};
+
 // ---- the inversion calls of povu_hip_call (inv_kernels.hip; INTEGRATION.md "Inversion calls")
 // what povu_hip_call has on the device when it asks for them
 struct InvIn {
-	uint64_t NR = 0;		  // reference steps, the reference paths concatenated ("reference index")
-	uint32_t nR = 0, S = 0, NS = 0;
-	const uint64_t *ref_base = nullptr; // [nR + 1] reference index of every reference path's first step
-	const uint32_t *ref_path = nullptr, *slot_of_path = nullptr, *slot_first = nullptr;
-	const uint64_t *roff = nullptr; // [NR + 1] bases in front of every reference step (one scan over the concatenation)
+	PathsView paths;
+	RefView ref;
+	SlotsView slots;
 	uint32_t max_steps = 65536;
 	bool force_tier2 = false;
 };
@@ -122,13 +262,14 @@ InvDevice inv_find(povu_hip_ctx *ctx, const InvIn &in);
 void inv_merge(povu_hip_ctx *ctx, InvDevice &v, uint32_t nrec, const uint32_t *f_ref, const uint64_t *f_pos, uint32_t *f_dst);
 // the per-record fields of the inversion records (AC count 1 into nalt)
 void inv_fields(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o);
-// their blocks (nb + record, two spelled alleles each: bcnt) and GT rows
-void inv_genotypes(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o, uint32_t nb, uint64_t *bcnt);
+// their blocks (the layout's inversion family, two spelled alleles each: bcnt) and GT rows
+void inv_genotypes(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o, uint32_t first_block, uint64_t *bcnt);
 // their AC, AN, NS and flags
 void inv_counts(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o, const uint64_t *ac_off, uint32_t *ac);
-// lengths of the bases and AT strings of their spelled alleles, slen[2 b + alt] (alt 0 REF, 1 ALT)
-void inv_spell_len(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, uint64_t *slen, uint64_t *alen);
-void inv_emit(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const uint64_t *s_off, const uint64_t *a_off, char *o_seq, char *o_at,
-	      unsigned long long *bad);
+// lengths of the bases and AT strings of their spelled alleles (REF, then ALT), and the strings; slen, alen, s_off and a_off
+// are the whole arrays
+void inv_spell_len(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const BlockLayout &L, uint64_t *slen, uint64_t *alen);
+void inv_emit(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const BlockLayout &L, const uint64_t *s_off, const uint64_t *a_off, char *o_seq,
+	      char *o_at, unsigned long long *bad);
 
 } // namespace povu_hip

@@ -31,14 +31,12 @@ namespace povu_hip
 static constexpr uint32_t MAX_ALLELES = 65534;
 
 // ---- reference offsets: length of every reference step (ref_base: first step of every reference in the concatenation)
-__global__ void k_cl_ref_len(uint64_t NR, const uint64_t *__restrict__ ref_base, uint32_t nR, const uint32_t *__restrict__ ref_path,
-			     const uint64_t *__restrict__ path_off, const uint32_t *__restrict__ steps, const uint64_t *__restrict__ seq_off,
-			     uint64_t *__restrict__ len)
+__global__ void k_cl_ref_len(RefView R, PathsView P, uint64_t *__restrict__ len)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < NR; i += (uint64_t)gridDim.x * Q_TPB) {
-		const uint32_t r = span_of(ref_base, nR, i);
-		const uint32_t x = steps[path_off[ref_path[r]] + (i - ref_base[r])];
-		len[i] = seq_off[(x >> 1) + 1] - seq_off[x >> 1];
+	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < R.NR; i += (uint64_t)gridDim.x * Q_TPB) {
+		const uint32_t r = span_of(R.ref_base, R.nR, i);
+		const uint32_t x = P.steps[P.path_off[R.ref_path[r]] + (i - R.ref_base[r])];
+		len[i] = P.seq_off[(x >> 1) + 1] - P.seq_off[x >> 1];
 	}
 }
 
@@ -67,16 +65,14 @@ __global__ void k_cl_seg_fill(uint32_t n, const uint32_t *__restrict__ qv, const
 }
 
 // ---- (site, reference, boundary) bits met by the reference steps
-__global__ void k_cl_hits(uint64_t NR, const uint64_t *__restrict__ ref_base, uint32_t nR, const uint32_t *__restrict__ ref_path,
-			  const uint64_t *__restrict__ path_off, const uint32_t *__restrict__ steps, const uint32_t *__restrict__ off,
-			  const uint32_t *__restrict__ val, uint32_t *__restrict__ hit)
+__global__ void k_cl_hits(RefView R, PathsView P, const uint32_t *__restrict__ off, const uint32_t *__restrict__ val, uint32_t *__restrict__ hit)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < NR; i += (uint64_t)gridDim.x * Q_TPB) {
-		const uint32_t r = span_of(ref_base, nR, i);
-		const uint32_t v = steps[path_off[ref_path[r]] + (i - ref_base[r])] >> 1;
+	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < R.NR; i += (uint64_t)gridDim.x * Q_TPB) {
+		const uint32_t r = span_of(R.ref_base, R.nR, i);
+		const uint32_t v = P.steps[P.path_off[R.ref_path[r]] + (i - R.ref_base[r])] >> 1;
 		for (uint32_t e = off[v]; e < off[v + 1]; e++) {
 			const uint32_t qr = val[e];
-			const uint64_t bit = ((uint64_t)(qr >> 1) * nR + r) * 2 + (qr & 1u);
+			const uint64_t bit = ((uint64_t)(qr >> 1) * R.nR + r) * 2 + (qr & 1u);
 			atomicOr(hit + (bit >> 5), 1u << (bit & 31));
 		}
 	}
@@ -140,26 +136,15 @@ __global__ void k_cl_keep(uint32_t n, const uint8_t *__restrict__ called, const 
 }
 
 // inner bases and AT width of every allele (of a kept site), S -> Z
-__global__ void k_cl_inner(uint32_t n_al, const uint32_t *__restrict__ afirst, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ keep,
-			   const uint64_t *__restrict__ rpos, const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ steps,
-			   const uint64_t *__restrict__ seq_off, const uint32_t *__restrict__ vid, uint64_t *__restrict__ ilen,
-			   uint64_t *__restrict__ atl)
+__global__ void k_cl_inner(uint32_t n_al, CallView V, uint64_t *__restrict__ ilen, uint64_t *__restrict__ atl)
 {
 	for (uint32_t a = blockIdx.x * Q_TPB + threadIdx.x; a < n_al; a += gridDim.x * Q_TPB) {
-		const uint32_t t = afirst[a];
-		uint64_t b = 0, w = 0;
-		if (keep[rq[t]]) {
-			const uint64_t p = rpos[t] & ~ROLE_BIT;
-			const bool rev = (rpos[t] & ROLE_BIT) != 0;
-			const uint32_t len = rlen[t];
-			for (uint32_t k = 1; k + 1 < len; k++) {
-				const uint32_t v = trav_step(steps, p, len, rev, k) >> 1;
-				b += seq_off[v + 1] - seq_off[v];
-				w += 1 + ndig(vid[v]);
-			}
-		}
-		ilen[a] = b;
-		atl[a] = w;
+		const uint32_t t = V.afirst[a];
+		InnerSize n{0, 0};
+		if (V.keep[V.trav.rq[t]])
+			n = span_inner_size(trav_span(V.trav.rpos, V.trav.rlen, t), V.paths);
+		ilen[a] = n.bases;
+		atl[a] = n.at;
 	}
 }
 // alleles without an inner base, per kept site (a record is anchored when REF or one of its ALTs is such an allele)
@@ -186,44 +171,30 @@ __global__ void k_cl_collapsed(uint32_t n, const uint32_t *__restrict__ keep, co
 	}
 }
 // per flubble record j (before the sort): rstate; the inner bases and AT width of its REF (xilen, xatl: the reference's own
-// exact allele); with want_len the written lengths of REF and of its longest allele.  crep == NULL: not nested (alleles, REF
+// exact allele); with want_len the written lengths of REF and of its longest allele.  V.crep == NULL: not nested (alleles, REF
 // always the block's).
-__global__ void k_cl_rec_state(uint32_t nfl, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ exact_oa,
-			       const uint32_t *__restrict__ exact_off, const uint32_t *__restrict__ oa, const uint32_t *__restrict__ aoff,
-			       const uint32_t *__restrict__ crep, const uint8_t *__restrict__ orv, const uint64_t *__restrict__ rpos,
-			       const uint32_t *__restrict__ rlen, const uint32_t *__restrict__ steps, const uint64_t *__restrict__ seq_off,
-			       const uint32_t *__restrict__ vid, const uint64_t *__restrict__ ilen, const uint64_t *__restrict__ atl,
-			       const uint32_t *__restrict__ zc, uint32_t want_len, uint8_t *__restrict__ rstate, uint64_t *__restrict__ xilen,
-			       uint64_t *__restrict__ xatl, uint64_t *__restrict__ ref_len, uint64_t *__restrict__ max_len)
+__global__ void k_cl_rec_state(CallView V, uint32_t want_len, uint8_t *__restrict__ rstate, uint64_t *__restrict__ xilen, uint64_t *__restrict__ xatl,
+			       uint64_t *__restrict__ ref_len, uint64_t *__restrict__ max_len)
 {
-	for (uint32_t j = blockIdx.x * Q_TPB + threadIdx.x; j < nfl; j += gridDim.x * Q_TPB) {
-		const uint32_t t = rlist[j], q = rq[t], ec = aoff[q] + oa[t], len = rlen[t];
-		const uint64_t p = rpos[t] & ~ROLE_BIT;
-		const bool rev = (rpos[t] & ROLE_BIT) != 0;
-		const bool own = crep && crep[ec] != exact_off[q] + exact_oa[t];
-		uint64_t b = ilen[ec], w = atl[ec];
-		if (own) {
-			b = w = 0;
-			for (uint32_t k = 1; k + 1 < len; k++) {
-				const uint32_t v = trav_step(steps, p, len, rev, k) >> 1;
-				b += seq_off[v + 1] - seq_off[v];
-				w += 1 + ndig(vid[v]);
-			}
-		}
-		const bool anch = b == 0 || zc[q] - (ilen[ec] == 0 ? 1u : 0u) > 0;
-		rstate[j] = (anch ? RS_ANCHORED : 0) | (b == 0 ? RS_REF_EMPTY : 0) | (own ? RS_OWN_REF : 0);
-		xilen[j] = b;
-		xatl[j] = w;
+	for (uint32_t j = blockIdx.x * Q_TPB + threadIdx.x; j < V.nfl; j += gridDim.x * Q_TPB) {
+		const uint32_t t = V.rlist[j], q = V.trav.rq[t], ec = V.aoff[q] + V.oa[t];
+		const bool own = V.crep && V.crep[ec] != V.trav.aoff[q] + V.trav.oa[t];
+		InnerSize n{V.ilen[ec], V.atl[ec]};
+		if (own)
+			n = span_inner_size(trav_span(V.trav.rpos, V.trav.rlen, t), V.paths);
+		const bool anch = n.bases == 0 || V.zc[q] - (V.ilen[ec] == 0 ? 1u : 0u) > 0;
+		rstate[j] = (anch ? RS_ANCHORED : 0) | (n.bases == 0 ? RS_REF_EMPTY : 0) | (own ? RS_OWN_REF : 0);
+		xilen[j] = n.bases;
+		xatl[j] = n.at;
 		if (want_len) {
 			// the anchor step is the site's boundary the reference enters by, whatever the allele
-			const uint32_t v = (orv[t] ? trav_step(steps, p, len, rev, len - 1) : trav_step(steps, p, len, rev, 0)) >> 1;
-			const uint64_t ab = anch && seq_off[v + 1] > seq_off[v] ? 1 : 0;
-			uint64_t mx = b;
-			for (uint32_t a = aoff[q]; a < aoff[q + 1]; a++)
+			const WrittenAllele ref = written_allele(V, t, V.trav.orv[t] != 0, anch, n.bases, n.at);
+			uint64_t mx = n.bases;
+			for (uint32_t a = V.aoff[q]; a < V.aoff[q + 1]; a++)
 				if (a != ec)
-					mx = max(mx, ilen[a]);
-			ref_len[j] = b + ab;
-			max_len[j] = mx + ab;
+					mx = max(mx, V.ilen[a]);
+			ref_len[j] = ref.text_len();
+			max_len[j] = mx + (ref.anchor_base ? 1 : 0);
 		}
 	}
 }
@@ -242,85 +213,78 @@ __global__ void k_cl_slots(uint32_t R, const uint32_t *__restrict__ rq, const ui
 		atomicMax(smax + i, oa[t]);
 	}
 }
-__global__ void k_cl_rec_flag(uint32_t R, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ op, const uint32_t *__restrict__ keep,
-			      const uint32_t *__restrict__ ref_of_path, uint8_t *__restrict__ flag)
+__global__ void k_cl_rec_flag(CallView V, uint8_t *__restrict__ flag)
 {
-	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < R; t += gridDim.x * Q_TPB)
-		flag[t] = keep[rq[t]] && ref_of_path[op[t]] != NO_QUERY;
+	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < V.trav.R; t += gridDim.x * Q_TPB)
+		flag[t] = V.keep[V.trav.rq[t]] && V.ref.ref_of_path[V.trav.op[t]] != NO_QUERY;
 }
-__global__ void k_cl_pos(uint32_t nrec, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ op,
-			 const uint32_t *__restrict__ of, const uint32_t *__restrict__ ref_of_path, const uint64_t *__restrict__ ref_base,
-			 const uint64_t *__restrict__ roff, const uint8_t *__restrict__ rstate, uint64_t *__restrict__ pos)
+// reference number of flubble record j
+__device__ __forceinline__ uint32_t ref_of_record(const CallView &V, uint32_t j) { return V.ref.ref_of_path[V.trav.op[V.rlist[j]]]; }
+__global__ void k_cl_pos(CallView V, uint64_t *__restrict__ pos)
 {
-	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
-		const uint32_t t = rlist[i];
-		const uint64_t b = ref_base[ref_of_path[op[t]]];
-		pos[i] = roff[b + of[t] + 1] - roff[b] + ((rstate[i] & RS_ANCHORED) ? 0 : 1);
+	for (uint32_t j = blockIdx.x * Q_TPB + threadIdx.x; j < V.nfl; j += gridDim.x * Q_TPB) {
+		const uint64_t b = V.ref.ref_base[ref_of_record(V, j)];
+		pos[j] = V.ref.roff[b + V.trav.of[V.rlist[j]] + 1] - V.ref.roff[b] + ((V.rstate[j] & RS_ANCHORED) ? 0 : 1);
 	}
 }
 // sort key of record perm[i]: 0 = POS low word, 1 = POS high word, 2 = reference
-__global__ void k_cl_key(uint32_t nrec, int which, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rlist,
-			 const uint32_t *__restrict__ op, const uint32_t *__restrict__ ref_of_path, const uint64_t *__restrict__ pos,
-			 uint32_t *__restrict__ key)
+__global__ void k_cl_key(uint32_t nrec, int which, const uint32_t *__restrict__ perm, CallView V, uint32_t *__restrict__ key)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		const uint32_t j = perm[i];
-		key[i] = which == 0 ? (uint32_t)pos[j] : which == 1 ? (uint32_t)(pos[j] >> 32) : ref_of_path[op[rlist[j]]];
+		key[i] = which == 0 ? (uint32_t)V.pos[j] : which == 1 ? (uint32_t)(V.pos[j] >> 32) : ref_of_record(V, j);
 	}
 }
 
 // per record (sorted; row dst[i] of the record list when inversion records are merged in, else row i): its fields, the ALT count for the AC offsets, the (site, orientation) it needs spelled
-__global__ void k_cl_rec_fields(uint32_t nrec, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rlist, const uint64_t *__restrict__ pos,
-				const uint32_t *__restrict__ rq, const uint32_t *__restrict__ op, const uint32_t *__restrict__ of,
-				const uint32_t *__restrict__ oa, const uint8_t *__restrict__ orv, const uint32_t *__restrict__ aoff,
-				uint32_t *__restrict__ o_q, uint32_t *__restrict__ o_path, uint32_t *__restrict__ o_first,
-				uint32_t *__restrict__ o_ref, uint32_t *__restrict__ o_nal, uint64_t *__restrict__ o_pos, uint64_t *__restrict__ nalt,
-				uint32_t *__restrict__ need, const uint32_t *__restrict__ dst, const uint8_t *__restrict__ rstate,
-				const uint32_t *__restrict__ height, const uint32_t *__restrict__ n_level, const uint32_t *__restrict__ n_parent,
+__global__ void k_cl_rec_fields(uint32_t nrec, const uint32_t *__restrict__ perm, CallView V, InvRows o, uint32_t *__restrict__ need,
+				const uint32_t *__restrict__ dst, const uint32_t *__restrict__ n_level, const uint32_t *__restrict__ n_parent,
 				uint32_t *__restrict__ o_level, uint32_t *__restrict__ o_parent, uint32_t *__restrict__ xneed)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
-		const uint32_t j = perm[i], t = rlist[j], q = rq[t], d = dst ? dst[i] : i;
-		o_level[d] = n_level ? n_level[j] : height[q] - 1;
-		o_parent[d] = n_parent ? n_parent[j] : NO_QUERY;
-		xneed[i] = (rstate[j] & RS_OWN_REF) ? 1 : 0;
-		o_q[d] = q;
-		o_path[d] = op[t];
-		o_first[d] = of[t];
-		o_ref[d] = oa[t];
-		o_nal[d] = aoff[q + 1] - aoff[q];
-		o_pos[d] = pos[j];
-		nalt[d] = aoff[q + 1] - aoff[q] - 1;
-		need[4 * (size_t)q + ((rstate[j] & RS_ANCHORED) ? 2 : 0) + orv[t]] = 1;
+		const uint32_t j = perm[i], t = V.rlist[j], q = V.trav.rq[t], d = dst ? dst[i] : i;
+		// (what is read, then what is written: the rows' pointers come in a struct and promise the compiler nothing)
+		const uint32_t level = n_level ? n_level[j] : V.height[q] - 1, parent = n_parent ? n_parent[j] : NO_QUERY;
+		const uint32_t path = V.trav.op[t], first = V.trav.of[t], ref = V.oa[t], nal = V.aoff[q + 1] - V.aoff[q];
+		const uint64_t pos = V.pos[j];
+		const uint8_t st = V.rstate[j], orv = V.trav.orv[t];
+		o_level[d] = level;
+		o_parent[d] = parent;
+		xneed[i] = (st & RS_OWN_REF) ? 1 : 0;
+		o.o_q[d] = q;
+		o.o_path[d] = path;
+		o.o_first[d] = first;
+		o.o_ref[d] = ref;
+		o.o_nal[d] = nal;
+		o.o_pos[d] = pos;
+		o.nalt[d] = nal - 1;
+		need[4 * (size_t)q + ((st & RS_ANCHORED) ? 2 : 0) + orv] = 1;
 	}
 }
 // reference number and POS of the sorted records (the inversion records are merged in by them)
-__global__ void k_cl_sorted_keys(uint32_t nrec, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ op,
-				 const uint32_t *__restrict__ ref_of_path, const uint64_t *__restrict__ pos, uint32_t *__restrict__ f_ref,
-				 uint64_t *__restrict__ f_pos)
+__global__ void k_cl_sorted_keys(uint32_t nrec, const uint32_t *__restrict__ perm, CallView V, uint32_t *__restrict__ f_ref, uint64_t *__restrict__ f_pos)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
-		f_ref[i] = ref_of_path[op[rlist[perm[i]]]];
-		f_pos[i] = pos[perm[i]];
+		f_ref[i] = ref_of_record(V, perm[i]);
+		f_pos[i] = V.pos[perm[i]];
 	}
 }
 
 // GT codes, AC, AN, NS and flags: one wave per record, a lane per sample (its slots are consecutive)
-__global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, const uint32_t *__restrict__ o_q, const uint32_t *__restrict__ o_path,
-						      const uint32_t *__restrict__ o_ref, const uint32_t *__restrict__ qidx,
-						      const uint32_t *__restrict__ slot_of_path, const uint32_t *__restrict__ slot_first,
-						      uint32_t n_samples, uint32_t S, const uint32_t *__restrict__ smin,
-						      const uint32_t *__restrict__ smax, const uint64_t *__restrict__ ac_off,
-						      const uint32_t *__restrict__ qstatus, const uint32_t *__restrict__ perm,
-						      const uint8_t *__restrict__ rstate, const uint8_t *__restrict__ collapsed,
-						      const uint8_t *__restrict__ rescued, uint16_t *__restrict__ gt,
-						      uint32_t *__restrict__ ac, uint32_t *__restrict__ an, uint32_t *__restrict__ ns,
-						      uint8_t *__restrict__ flags, const uint32_t *__restrict__ dst)
+__global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, CallView V, SlotsView SL, InvRows o, const uint32_t *__restrict__ qidx,
+						      const uint32_t *__restrict__ smin, const uint32_t *__restrict__ smax,
+						      const uint64_t *__restrict__ ac_off, const uint32_t *__restrict__ perm,
+						      const uint8_t *__restrict__ collapsed, const uint8_t *__restrict__ rescued,
+						      uint32_t *__restrict__ ac, const uint32_t *__restrict__ dst)
 {
 	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
+	// what the loop over the slots reads and writes, out of the structs
+	const uint32_t *__restrict__ slot_first = SL.slot_first;
+	uint16_t *__restrict__ gt = o.gt;
+	const uint32_t n_samples = SL.NS, S = SL.S;
 	for (uint32_t i0 = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); i0 < nrec; i0 += waves) {
 		const uint32_t i = dst ? dst[i0] : i0;
-		const uint32_t q = o_q[i], ra = o_ref[i], own = slot_of_path[o_path[i]];
+		const uint32_t q = o.o_q[i], ra = o.o_ref[i], own = SL.slot_of_path[o.o_path[i]];
 		const uint64_t base = (uint64_t)qidx[q] * S;
 		uint32_t n_an = 0, n_ns = 0, amb = 0;
 		for (uint32_t sm = lane; sm < n_samples; sm += 64) {
@@ -350,21 +314,22 @@ __global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, const uint3
 		n_ns = wave_sum(n_ns);
 		amb = wave_sum(amb);
 		if (lane == 0) {
-			an[i] = n_an;
-			ns[i] = n_ns;
+			o.o_an[i] = n_an;
+			o.o_ns[i] = n_ns;
 			uint8_t f = 0;
 			const uint32_t j = perm[i0];
-			if (rstate[j] & RS_ANCHORED)
-				f |= POVU_HIP_CALL_ANCHORED | ((rstate[j] & RS_REF_EMPTY) ? POVU_HIP_CALL_INS : POVU_HIP_CALL_DEL);
-			if (qstatus[q] || amb)
+			const uint8_t st = V.rstate[j];
+			if (st & RS_ANCHORED)
+				f |= POVU_HIP_CALL_ANCHORED | ((st & RS_REF_EMPTY) ? POVU_HIP_CALL_INS : POVU_HIP_CALL_DEL);
+			if (V.trav.qstatus[q] || amb)
 				f |= POVU_HIP_CALL_TANGLED;
 			if (collapsed && collapsed[q])
 				f |= POVU_HIP_CALL_TANGLED | POVU_HIP_CALL_COLLAPSED;
 			if (rescued && rescued[j])
 				f |= POVU_HIP_CALL_RESCUED;
-			if (rstate[j] & RS_NORMALIZED)
+			if (st & RS_NORMALIZED)
 				f |= POVU_HIP_CALL_NORMALIZED;
-			flags[i] = f;
+			o.o_flags[i] = f;
 		}
 	}
 }
@@ -375,34 +340,33 @@ __global__ void k_cl_blocks(uint64_t n2, const uint32_t *__restrict__ need, cons
 		if (need[x])
 			blist[boff[x]] = (uint32_t)x;
 }
-__global__ void k_cl_rec_block(uint32_t nrec, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rlist,
-			       const uint32_t *__restrict__ rq, const uint8_t *__restrict__ orv, const uint32_t *__restrict__ boff,
-			       uint32_t *__restrict__ o_block, const uint32_t *__restrict__ dst, const uint8_t *__restrict__ rstate,
-			       const uint32_t *__restrict__ xoff, uint32_t *__restrict__ xrow)
+__global__ void k_cl_rec_block(uint32_t nrec, const uint32_t *__restrict__ perm, CallView V, const uint32_t *__restrict__ boff,
+			       uint32_t *__restrict__ o_block, const uint32_t *__restrict__ dst, const uint32_t *__restrict__ xoff,
+			       uint32_t *__restrict__ xrow)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
-		const uint32_t j = perm[i], t = rlist[j], d = dst ? dst[i] : i;
-		o_block[d] = boff[4 * (size_t)rq[t] + ((rstate[j] & RS_ANCHORED) ? 2 : 0) + orv[t]];
-		xrow[d] = (rstate[j] & RS_OWN_REF) ? xoff[i] : NO_QUERY;
+		const uint32_t j = perm[i], t = V.rlist[j], d = dst ? dst[i] : i;
+		o_block[d] = boff[4 * (size_t)V.trav.rq[t] + ((V.rstate[j] & RS_ANCHORED) ? 2 : 0) + V.trav.orv[t]];
+		xrow[d] = (V.rstate[j] & RS_OWN_REF) ? xoff[i] : NO_QUERY;
 	}
 }
 // the extra blocks (one spelled allele each: the REF of a record that is not its class's representative) and their records
 __global__ void k_cl_extra(uint32_t nrec, const uint32_t *__restrict__ perm, const uint8_t *__restrict__ rstate, const uint32_t *__restrict__ xoff,
-			   uint32_t *__restrict__ xlist, uint64_t *__restrict__ xcnt)
+			   BlockLayout L, uint32_t *__restrict__ xlist, uint64_t *__restrict__ bcnt)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB)
 		if (rstate[perm[i]] & RS_OWN_REF) {
 			xlist[xoff[i]] = perm[i];
-			xcnt[xoff[i]] = 1;
+			bcnt[L.extra_block(xoff[i])] = 1;
 		}
 }
 // REF among the spelled alleles: the extra block's one allele, or allele ref_allele of the record's block
 __global__ void k_cl_ref_spelled(uint32_t nrec, const uint32_t *__restrict__ o_block, const uint32_t *__restrict__ o_ref,
-				 const uint32_t *__restrict__ xrow, const uint64_t *__restrict__ block_off, uint32_t nfb,
+				 const uint32_t *__restrict__ xrow, const uint64_t *__restrict__ block_off, BlockLayout L,
 				 uint64_t *__restrict__ ref_spelled)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB)
-		ref_spelled[i] = xrow[i] != NO_QUERY ? block_off[nfb + xrow[i]] : block_off[o_block[i]] + o_ref[i];
+		ref_spelled[i] = xrow[i] != NO_QUERY ? block_off[L.extra_block(xrow[i])] : block_off[o_block[i]] + o_ref[i];
 }
 __global__ void k_cl_block_cnt(uint32_t nb, const uint32_t *__restrict__ blist, const uint32_t *__restrict__ aoff, uint64_t *__restrict__ cnt)
 {
@@ -412,105 +376,61 @@ __global__ void k_cl_block_cnt(uint32_t nb, const uint32_t *__restrict__ blist, 
 	}
 }
 
-// what spelled allele j is: its block's site and orientation, its global allele, the first step in the reference's
-// direction (the anchor step)
-struct Spelled {
-	uint32_t q, o, t, len, first;
-	uint64_t p, ilen, atl;
-	bool rev, anch;
-};
-// the tables a spelled allele is found in: nb blocks of which the first nfb are (site, anchored, orientation) blocks with an
-// allele each of the site, the others extra blocks with the one allele of record xlist[.]
-struct SpellTab {
-	uint32_t nb, nfb;
+// where the flubble family's spelled alleles are found: the blocks' offsets, the class blocks' (site, anchored, orientation),
+// the extra blocks' records
+struct FlubbleBlocks {
+	BlockLayout L;
 	const uint64_t *block_off;
-	const uint32_t *blist, *aoff, *afirst, *xlist, *rlist, *rq;
-	const uint8_t *orv, *rstate;
-	const uint64_t *rpos;
-	const uint32_t *rlen, *steps;
-	const uint64_t *ilen, *atl, *xilen, *xatl;
+	const uint32_t *blist, *xlist;
 };
-__device__ __forceinline__ Spelled spelled(uint64_t j, const SpellTab &T)
+__device__ __forceinline__ WrittenAllele spelled_allele(uint64_t j, const CallView &V, const FlubbleBlocks &B)
 {
-	Spelled s;
-	const uint32_t b = span_of(T.block_off, T.nb, j);
-	const uint32_t *__restrict__ steps = T.steps;
-	if (b < T.nfb) {
-		s.q = T.blist[b] >> 2;
-		s.anch = (T.blist[b] & 2u) != 0;
-		s.o = T.blist[b] & 1u;
-		const uint32_t a = T.aoff[s.q] + (uint32_t)(j - T.block_off[b]);
-		s.t = T.afirst[a];
-		s.ilen = T.ilen[a];
-		s.atl = T.atl[a];
-	} else {
-		const uint32_t r = T.xlist[b - T.nfb];
-		s.t = T.rlist[r];
-		s.q = T.rq[s.t];
-		s.anch = (T.rstate[r] & RS_ANCHORED) != 0;
-		s.o = T.orv[s.t];
-		s.ilen = T.xilen[r];
-		s.atl = T.xatl[r];
-	}
-	const uint64_t *__restrict__ rpos = T.rpos;
-	const uint32_t *__restrict__ rlen = T.rlen;
-	s.p = rpos[s.t] & ~ROLE_BIT;
-	s.rev = (rpos[s.t] & ROLE_BIT) != 0;
-	s.len = rlen[s.t];
-	s.first = s.o ? trav_step(steps, s.p, s.len, s.rev, s.len - 1) ^ 1u : trav_step(steps, s.p, s.len, s.rev, 0);
-	return s;
-}
-// inner step k (0-based) in the reference's direction
-__device__ __forceinline__ uint32_t inner_step(const Spelled &s, const uint32_t *__restrict__ steps, uint32_t k)
-{
-	return s.o ? trav_step(steps, s.p, s.len, s.rev, s.len - 2 - k) ^ 1u : trav_step(steps, s.p, s.len, s.rev, k + 1);
+	const uint32_t b = span_of(B.block_off, B.L.nfb, j);
+	if (B.L.is_class(b))
+		return allele_of_block(V, B.blist[b], (uint32_t)(j - B.block_off[b]));
+	return own_ref_of_record(V, B.xlist[b - B.L.nfc]);
 }
 
-__global__ void k_cl_spell_len(uint64_t nsp, SpellTab T, const uint64_t *__restrict__ seq_off, const uint32_t *__restrict__ vid,
-			       uint64_t *__restrict__ slen, uint64_t *__restrict__ alen)
+__global__ void k_cl_spell_len(CallView V, FlubbleBlocks B, uint64_t *__restrict__ slen, uint64_t *__restrict__ alen)
 {
-	for (uint64_t j = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; j < nsp; j += (uint64_t)gridDim.x * Q_TPB) {
-		const Spelled s = spelled(j, T);
-		const uint32_t v = s.first >> 1;
-		const bool an = s.anch;
-		slen[j] = s.ilen + (an && seq_off[v + 1] > seq_off[v] ? 1 : 0);
-		alen[j] = s.atl + (an ? 1 + ndig(vid[v]) : 0);
+	for (uint64_t j = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; j < B.L.nfsp; j += (uint64_t)gridDim.x * Q_TPB) {
+		const WrittenAllele s = spelled_allele(j, V, B);
+		slen[j] = s.text_len();
+		alen[j] = s.at_len(V.paths);
 	}
 }
 
 // one wave per spelled allele: the bases, then the AT string
-__global__ __launch_bounds__(Q_TPB) void k_cl_emit(uint64_t nsp, SpellTab T, const uint64_t *__restrict__ seq_off, const char *__restrict__ seq,
-						   const uint32_t *__restrict__ vid, const uint64_t *__restrict__ s_off,
-						   const uint64_t *__restrict__ a_off, char *__restrict__ o_seq, char *__restrict__ o_at,
-						   unsigned long long *__restrict__ bad)
+__global__ __launch_bounds__(Q_TPB) void k_cl_emit(CallView V, FlubbleBlocks B, const uint64_t *__restrict__ s_off, const uint64_t *__restrict__ a_off,
+						   char *__restrict__ o_seq, char *__restrict__ o_at, unsigned long long *__restrict__ bad)
 {
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint64_t waves = (uint64_t)gridDim.x * (Q_TPB / 64);
-	for (uint64_t j = (uint64_t)blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); j < nsp; j += waves) {
-		const Spelled s = spelled(j, T);
-		const bool an = s.anch;
-		const uint32_t *__restrict__ steps = T.steps;
+	// what the copy loops read, out of the view
+	const uint32_t *__restrict__ steps = V.paths.steps, *__restrict__ vid = V.paths.vid;
+	const uint64_t *__restrict__ seq_off = V.paths.seq_off;
+	const char *__restrict__ seq = V.paths.seq;
+	for (uint64_t j = (uint64_t)blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); j < B.L.nfsp; j += waves) {
+		const WrittenAllele s = spelled_allele(j, V, B);
 		uint64_t w = s_off[j], wa = a_off[j];
-		const uint32_t m = s.len - 2; // inner steps
 		// the anchor: last base of the first step, and its step text
-		if (an) {
-			const uint32_t v = s.first >> 1;
-			const uint64_t b0 = seq_off[v], b1 = seq_off[v + 1];
-			if (b1 > b0) {
+		if (s.anchored) {
+			const uint32_t v = s.anchor >> 1;
+			if (s.anchor_base) {
 				if (lane == 0) {
-					const uint8_t c = (uint8_t)seq[(s.first & 1u) ? b0 : b1 - 1], r = comp(c);
+					const uint8_t c = (uint8_t)seq[s.anchor_at], r = comp(c);
 					if (!r)
 						atomicMin(bad, (unsigned long long)v);
-					o_seq[w] = (char)((s.first & 1u) ? r : c);
+					o_seq[w] = (char)((s.anchor & 1u) ? r : c);
 				}
 				w++;
 			}
 			const uint32_t width = 1 + ndig(vid[v]);
 			if (lane == 0)
-				put_step(o_at, vid, s.first, wa, width);
+				put_step(o_at, vid, s.anchor, wa, width);
 			wa += width;
 		}
-		emit_steps(lane, m, [&](uint32_t k) { return inner_step(s, steps, k); }, seq_off, seq, vid, w, wa, o_seq, o_at, bad);
+		emit_steps(lane, s.inner_steps(), [&](uint32_t k) { return s.inner_step(steps, k); }, seq_off, seq, vid, w, wa, o_seq, o_at, bad);
 	}
 }
 
@@ -593,10 +513,9 @@ struct CallWs {
 		*words;
 	uint8_t *d_fam, *callable, *called, *rflag;
 	uint32_t *zc, *d_height; // per site: alleles without an inner base, PVST height
-	// what the steps from the kept sites on read as alleles: the exact alleles, or with POVU_HIP_T_NESTED the classes (crep: the
-	// exact allele that represents a class, else null)
-	const uint32_t *aoff, *oa, *afirst, *crep = nullptr;
-	uint32_t n_eal = 0;
+	uint32_t n_eal = 0; // the alleles the call reads: the exact alleles, or with POVU_HIP_T_NESTED the classes
+	CallView v;	    // what the kernels read of all this (call_common.hpp)
+	SlotsView slots;
 	NestClasses nc;
 	NestRecs nr;
 	uint8_t *collapsed, *rstate;		    // per site / per flubble record before the sort (RS_*)
@@ -608,8 +527,7 @@ struct CallWs {
 	size_t tmp_bytes;
 	uint32_t nQ = 0, nfl = 0; // kept sites, flubble records
 	uint32_t *smin, *smax;
-	NormIn ni; // left-normalized profile: what the normalisation read, and per flubble record what it found
-	NormRecs nm;
+	NormRecs nm; // left-normalized profile: per flubble record what the normalisation found
 };
 // the inversion records and where the flubble records go in the one list
 struct CallInv {
@@ -619,16 +537,15 @@ struct CallInv {
 };
 // cl_rec: the per-record arrays and the spelling's inputs
 struct CallRecs {
-	uint32_t nrec = 0, nb = 0, nfb = 0, nfc = 0; // records; blocks: all, those of the flubble records, of these the class blocks
+	uint32_t nrec = 0; // records
+	BlockLayout L;	   // their blocks of spelled alleles
 	uint32_t *xneed, *xoff, *xlist, *xrow, *o_level, *o_parent; // the extra blocks (REFs spelled on their own)
 	uint64_t *ref_spelled;
-	uint64_t n_ac = 0, nsp = 0, nfsp = 0; // ALT counts; spelled alleles: all, those of the flubble blocks
+	uint64_t n_ac = 0; // ALT counts
 	InvRows rows;
 	uint32_t *need, *boff, *blist;
 	uint64_t *ac_off, *bcnt, *block_off;
-	NormRows nrows; // left-normalized profile: the rows' fields, the blocks of the changed records (nb0 on, nn of them, from spelled allele nsp0)
-	uint32_t nb0 = 0, nn = 0;
-	uint64_t nsp0 = 0;
+	NormRows nrows; // left-normalized profile: the rows' fields, the changed records in sorted order
 };
 // cl_spell and cl_bytes
 struct CallSpelled {
@@ -728,6 +645,13 @@ void reference_offsets(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice
 		take(8, w.words);
 		take(w.tmp_bytes, w.tmp);
 	});
+	// the views: everything but the allele table (site_classes) and the number of flubble records (flubble_records)
+	CallView &v = w.v;
+	v.paths = paths_view(ctx), v.trav = trav_view(d), v.ref = RefView{NR, nR, w.d_ref_of_path, w.d_ref_path, w.d_ref_base, w.roff};
+	v.ilen = w.ilen, v.atl = w.atl, v.keep = w.keep, v.zc = w.zc, v.height = w.d_height;
+	v.nfl = 0, v.rlist = w.rlist, v.rstate = w.rstate, v.xilen = w.xilen, v.xatl = w.xatl, v.ref_len = w.ref_len, v.max_len = w.max_len;
+	v.raw_pos = v.pos = w.pos; // (one array until a left-normalisation moves `pos` and keeps the raw POS itself)
+	w.slots = SlotsView{in.S, NS, w.d_slot, w.d_slot_first};
 	HIP_CHECK(copy_async(w.d_ref_base, w.ref_base.data(), ((size_t)nR + 1) * 8, hipMemcpyHostToDevice, s));
 	HIP_CHECK(copy_async(w.d_ref_path, in.refs->ref_path, (size_t)nR * 4, hipMemcpyHostToDevice, s));
 	if (P) {
@@ -752,8 +676,7 @@ void reference_offsets(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice
 
 	HIP_CHECK(hipMemsetAsync(w.rlen64 + NR, 0, 8, s));
 	if (NR)
-		KLAUNCH(k_cl_ref_len, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, NR, w.d_ref_base, nR, w.d_ref_path, ctx->path_off, ctx->path_steps, ctx->seq_off,
-			w.rlen64);
+		KLAUNCH(k_cl_ref_len, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, v.ref, v.paths, w.rlen64);
 	scan_exclusive_u64(w.rlen64, w.roff, NR + 1, w.s64, s);
 }
 
@@ -769,8 +692,7 @@ void callability(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, C
 		scan_exclusive_u32(w.scnt, w.soffv, (size_t)g.V + 1, w.tmp, w.tmp_bytes, s);
 		KLAUNCH(k_cl_seg_fill, dim3(stride_blocks(2 * (size_t)n)), dim3(Q_TPB), 0, s, n, w.qv, w.soffv, w.scur, w.sval);
 		if (NR)
-			KLAUNCH(k_cl_hits, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, NR, w.d_ref_base, nR, w.d_ref_path, ctx->path_off, ctx->path_steps, w.soffv,
-				w.sval, w.hit);
+			KLAUNCH(k_cl_hits, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, w.v.ref, w.v.paths, w.soffv, w.sval, w.hit);
 		KLAUNCH(k_cl_present, dim3(stride_blocks((size_t)n * nR)), dim3(Q_TPB), 0, s, (uint64_t)n, nR, w.hit, w.d_tree, w.pres);
 		KLAUNCH(k_cl_callable, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, nR, w.hit, w.pres, w.d_tree, w.d_parent, w.d_fam, w.callable, w.called);
 		KLAUNCH(k_cl_unparent, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.callable, w.d_parent, w.called);
@@ -780,22 +702,22 @@ void callability(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, C
 // what the rest of the call reads as the alleles of a site: the exact alleles, or the classes of a nested call
 void site_classes(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
 {
-	w.aoff = d.aoff, w.oa = d.oa, w.afirst = d.afirst, w.n_eal = d.n_al;
+	CallView &v = w.v;
+	v.aoff = d.aoff, v.oa = d.oa, v.afirst = d.afirst, v.crep = nullptr, w.n_eal = d.n_al;
 	if (!in.nested)
 		return;
 	w.nc = nest_classes(ctx, d, w.called, in.opts && in.opts->max_steps ? in.opts->max_steps : 65536,
 			    in.opts && (in.opts->flags & POVU_HIP_T_FORCE_TIER2));
-	w.aoff = w.nc.coff, w.oa = w.nc.oc, w.afirst = w.nc.cfirst, w.crep = w.nc.crep, w.n_eal = w.nc.n_cl;
+	v.aoff = w.nc.coff, v.oa = w.nc.oc, v.afirst = w.nc.cfirst, v.crep = w.nc.crep, w.n_eal = w.nc.n_cl;
 }
 
 // the sites kept (called, two alleles or more), their alleles' inner lengths
 void kept_sites(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
 {
-	const ResidentGraph &g = ctx->g;
 	hipStream_t s = ctx->stream;
 	const uint32_t n = in.n, n_al = w.n_eal;
 	const size_t n1 = (size_t)n + 1;
-	KLAUNCH(k_cl_keep, dim3(stride_blocks(n1)), dim3(Q_TPB), 0, s, n, w.called, w.aoff, w.keep, w.words + 1);
+	KLAUNCH(k_cl_keep, dim3(stride_blocks(n1)), dim3(Q_TPB), 0, s, n, w.called, w.v.aoff, w.keep, w.words + 1);
 	scan_exclusive_u32(w.keep, w.qidx, n1, w.tmp, w.tmp_bytes, s);
 	uint32_t hw[2] = {0, 0};
 	HIP_CHECK(copy_async(hw, w.qidx + n, 4, hipMemcpyDeviceToHost, s));
@@ -804,14 +726,12 @@ void kept_sites(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, Ca
 	w.nQ = hw[0];
 	if (hw[1] > MAX_ALLELES)
 		throw HipError("a called site has " + std::to_string(hw[1]) + " alleles: more than 65534 in one record are refused");
-	if (n_al) {
-		KLAUNCH(k_cl_inner, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, w.afirst, d.rq, w.keep, d.rpos, d.rlen, ctx->path_steps, ctx->seq_off, g.vid,
-			w.ilen, w.atl);
-	}
+	if (n_al)
+		KLAUNCH(k_cl_inner, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, w.v, w.ilen, w.atl);
 	if (n)
-		KLAUNCH(k_cl_zero_len, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, w.aoff, w.ilen, w.zc);
+		KLAUNCH(k_cl_zero_len, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, w.v.aoff, w.ilen, w.zc);
 	if (n && in.nested) {
-		KLAUNCH(k_cl_collapsed, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, d.aoff, w.aoff, w.collapsed, w.words + 3);
+		KLAUNCH(k_cl_collapsed, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, d.aoff, w.v.aoff, w.collapsed, w.words + 3);
 		w.n_collapsed = read_back(w.words + 3, s);
 	}
 }
@@ -825,18 +745,7 @@ void slot_table(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, Ca
 	HIP_CHECK(hipMemsetAsync(w.smin, 0xFF, cells * 4, s));
 	HIP_CHECK(hipMemsetAsync(w.smax, 0, cells * 4, s));
 	if (d.R && w.nQ)
-		KLAUNCH(k_cl_slots, dim3(stride_blocks(d.R)), dim3(Q_TPB), 0, s, d.R, d.rq, d.op, w.oa, w.keep, w.qidx, w.d_slot, in.S, w.smin, w.smax);
-}
-
-// left-normalized profile: chop, shift and trim of every flubble record, its POS moved before the sort keys are made
-void normalisation(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
-{
-	NormIn &ni = w.ni;
-	ni.nfl = w.nfl_all;
-	ni.rlist = w.rlist, ni.rq = d.rq, ni.op = d.op, ni.aoff = w.aoff, ni.oa = w.oa, ni.afirst = w.afirst, ni.rlen = d.rlen;
-	ni.orv = d.orv, ni.rpos = d.rpos, ni.ilen = w.ilen, ni.xilen = w.xilen, ni.rstate = w.rstate, ni.pos = w.pos;
-	ni.nR = in.nR, ni.ref_of_path = w.d_ref_of_path, ni.ref_path = w.d_ref_path, ni.ref_base = w.d_ref_base, ni.roff = w.roff;
-	w.nm = norm_records(ctx, ni);
+		KLAUNCH(k_cl_slots, dim3(stride_blocks(d.R)), dim3(Q_TPB), 0, s, d.R, d.rq, d.op, w.v.oa, w.keep, w.qidx, w.d_slot, in.S, w.smin, w.smax);
 }
 
 // flag, compact, POS, the sort by (reference, POS)
@@ -845,29 +754,25 @@ void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &
 	hipStream_t s = ctx->stream;
 	const uint32_t R = d.R, nR = in.nR;
 	if (R && w.nQ) {
-		KLAUNCH(k_cl_rec_flag, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, d.rq, d.op, w.keep, w.d_ref_of_path, w.rflag);
+		KLAUNCH(k_cl_rec_flag, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, w.v, w.rflag);
 		compact_flagged_u8(w.rflag, R, w.rlist, w.words + 2, w.tmp, w.tmp_bytes, s);
 		w.nfl = read_back(w.words + 2, s);
 	}
-	const uint32_t nfl_all = w.nfl_all = w.nfl;
+	const uint32_t nfl_all = w.nfl_all = w.v.nfl = w.nfl;
 	refuse_2_32(nfl_all, "the call needs ", "records");
 	const uint64_t ref_bases = read_back(w.roff + w.NR, s);
 	if (!nfl_all)
 		return;
 	// per record: anchored, REF's own lengths; POS; with POVU_HIP_T_NESTED parents, levels and the profile's choice
 	const bool filter = in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH;
-	KLAUNCH(k_cl_rec_state, dim3(stride_blocks(nfl_all)), dim3(Q_TPB), 0, s, nfl_all, w.rlist, d.rq, d.oa, d.aoff, w.oa, w.aoff, w.crep, d.orv, d.rpos, d.rlen,
-		ctx->path_steps, ctx->seq_off, ctx->g.vid, w.ilen, w.atl, w.zc, filter ? 1u : 0u, w.rstate, w.xilen, w.xatl, w.ref_len, w.max_len);
-	KLAUNCH(k_cl_pos, dim3(stride_blocks(nfl_all)), dim3(Q_TPB), 0, s, nfl_all, w.rlist, d.rq, d.op, d.of, w.d_ref_of_path, w.d_ref_base, w.roff, w.rstate,
-		w.pos);
-	if (in.normalized)
-		normalisation(ctx, in, d, w);
+	KLAUNCH(k_cl_rec_state, dim3(stride_blocks(nfl_all)), dim3(Q_TPB), 0, s, w.v, filter ? 1u : 0u, w.rstate, w.xilen, w.xatl, w.ref_len, w.max_len);
+	KLAUNCH(k_cl_pos, dim3(stride_blocks(nfl_all)), dim3(Q_TPB), 0, s, w.v, w.pos);
+	if (in.normalized) { // chop, shift and trim of every record, its POS moved before the sort keys are made
+		w.nm = norm_records(ctx, w.v, w.rstate, w.pos);
+		w.v.raw_pos = w.nm.raw_pos;
+	}
 	if (in.nested) {
-		NestRecIn ri;
-		ri.nfl = nfl_all, ri.rlist = w.rlist, ri.height = w.d_height, ri.ref_len = w.ref_len, ri.max_len = w.max_len;
-		ri.profile = in.prof.profile, ri.max_level = in.prof.max_level;
-		ri.max_ref_length = in.prof.max_ref_length, ri.max_allele_length = in.prof.max_allele_length;
-		w.nr = nest_records(ctx, d, w.nc.ix, ri);
+		w.nr = nest_records(ctx, w.v, w.nc.ix, in.prof);
 		w.nfl = w.nr.n_kept;
 		if (w.nfl)
 			HIP_CHECK(copy_async(w.perm, w.nr.kept, (size_t)w.nfl * 4, hipMemcpyDeviceToDevice, s));
@@ -879,7 +784,7 @@ void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &
 		return;
 	LsdSort sort{w.perm, w.perm2, w.key, w.key2, nfl, w.tmp, w.tmp_bytes, s};
 	auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
-		KLAUNCH(k_cl_key, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, which, perm, w.rlist, d.op, w.d_ref_of_path, w.pos, k);
+		KLAUNCH(k_cl_key, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, which, perm, w.v, k);
 	};
 	sort.pass(0, 32, write_key);
 	if (ref_bases + 1 >= (1ull << 32))
@@ -890,15 +795,14 @@ void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &
 }
 
 // the inversion records, and every record's row in the one list; gives the number of all records
-uint32_t inversion_rows(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, const CallWs &w, CallInv &inv)
+uint32_t inversion_rows(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, CallInv &inv)
 {
 	hipStream_t s = ctx->stream;
 	const uint32_t nfl = w.nfl;
 	if (!in.inversions)
 		return nfl;
 	InvIn &iin = inv.in;
-	iin.NR = w.NR, iin.nR = in.nR, iin.S = in.S, iin.NS = in.NS;
-	iin.ref_base = w.d_ref_base, iin.ref_path = w.d_ref_path, iin.slot_of_path = w.d_slot, iin.slot_first = w.d_slot_first, iin.roff = w.roff;
+	iin.paths = w.v.paths, iin.ref = w.v.ref, iin.slots = w.slots;
 	iin.max_steps = in.opts->max_steps ? in.opts->max_steps : 65536;
 	iin.force_tier2 = (in.opts->flags & POVU_HIP_T_FORCE_TIER2) != 0;
 	inv.v = inv_find(ctx, iin);
@@ -909,13 +813,13 @@ uint32_t inversion_rows(povu_hip_ctx *ctx, const CallInputs &in, const TravDevic
 	uint64_t *f_pos;
 	carve(ctx->iv_rows, [&](Spans &take) { take((size_t)nfl + 1, f_ref, inv.f_dst, f_pos); });
 	if (nfl)
-		KLAUNCH(k_cl_sorted_keys, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, d.op, w.d_ref_of_path, w.pos, f_ref, f_pos);
+		KLAUNCH(k_cl_sorted_keys, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.v, f_ref, f_pos);
 	inv_merge(ctx, inv.v, nfl, f_ref, f_pos, inv.f_dst);
 	return nfl + inv.v.n;
 }
 
 // the per-record fields, the AC offsets, the blocks a record needs spelled and their alleles
-void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, const CallWs &w, const CallInv &inv, CallRecs &r)
+void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, CallRecs &r)
 {
 	hipStream_t s = ctx->stream;
 	const uint32_t n = in.n, nfl = w.nfl, nrec = r.nrec;
@@ -924,6 +828,7 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d,
 	InvRows &o = r.rows;
 	NormRows &nw = r.nrows;
 	uint64_t *s64;
+	uint32_t nn = 0; // records the normalisation changed
 	carve(ctx->cl_rec, [&](Spans &take) {
 		take(r1, o.o_q, o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_an, o.o_ns, o.o_block, o.o_nsteps, o.o_pos, o.nalt, r.ac_off, o.o_flags);
 		take(r1, r.o_level, r.o_parent, r.xrow, r.ref_spelled);
@@ -943,8 +848,7 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d,
 	HIP_CHECK(hipMemsetAsync(r.xrow, 0xFF, r1 * 4, s));
 	HIP_CHECK(hipMemsetAsync(r.xneed, 0, f1 * 4, s));
 	if (nfl)
-		KLAUNCH(k_cl_rec_fields, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, w.pos, d.rq, d.op, d.of, w.oa, d.orv, w.aoff, o.o_q,
-			o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_pos, o.nalt, r.need, inv.f_dst, w.rstate, w.d_height, in.nested ? w.nr.level : nullptr,
+		KLAUNCH(k_cl_rec_fields, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.v, o, r.need, inv.f_dst, in.nested ? w.nr.level : nullptr,
 			in.nested ? w.nr.parent_q : nullptr, r.o_level, r.o_parent, r.xneed);
 	inv_fields(ctx, inv.in, iv, o);
 	if (in.normalized) {
@@ -955,14 +859,15 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d,
 		HIP_CHECK(hipMemsetAsync(nw.o_trim, 0, r1 * 4, s));
 		if (nrec)
 			HIP_CHECK(copy_async(nw.o_raw_pos, o.o_pos, (size_t)nrec * 8, hipMemcpyDeviceToDevice, s));
-		norm_row_fields(ctx, w.ni, w.nm, nfl, w.perm, inv.f_dst, nw);
+		norm_row_fields(ctx, w.v, w.nm, nfl, w.perm, inv.f_dst, nw);
 		scan_exclusive_u32(nw.need, nw.off, f1, w.tmp, w.tmp_bytes, s);
-		HIP_CHECK(copy_async(&r.nn, nw.off + nfl, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(&nn, nw.off + nfl, 4, hipMemcpyDeviceToHost, s));
 	}
 	scan_exclusive_u64(o.nalt, r.ac_off, r1, s64, s);
 	HIP_CHECK(copy_async(&r.n_ac, r.ac_off + nrec, 8, hipMemcpyDeviceToHost, s));
 	scan_exclusive_u32(r.need, r.boff, n2, w.tmp, w.tmp_bytes, s);
-	HIP_CHECK(copy_async(&r.nfc, r.boff + 4 * (size_t)n, 4, hipMemcpyDeviceToHost, s));
+	BlockLayout &L = r.L;
+	HIP_CHECK(copy_async(&L.nfc, r.boff + 4 * (size_t)n, 4, hipMemcpyDeviceToHost, s));
 	uint32_t nx = 0; // the extra blocks: a nested call's REFs that are no representatives
 	if (in.nested && nfl) {
 		scan_exclusive_u32(r.xneed, r.xoff, f1, w.tmp, w.tmp_bytes, s);
@@ -971,36 +876,36 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d,
 	HIP_CHECK(hipStreamSynchronize(s));
 	if (n)
 		KLAUNCH(k_cl_blocks, dim3(stride_blocks(4 * (size_t)n)), dim3(Q_TPB), 0, s, 4 * (uint64_t)n, r.need, r.boff, r.blist);
-	// the extra blocks follow the class blocks; the inversion records' blocks follow the flubble blocks, one each: REF, then ALT
-	refuse_2_32((uint64_t)r.nfc + nx, "the call needs ", "blocks");
-	const uint32_t nfc = r.nfc, nfb = r.nfb = nfc + nx;
-	refuse_2_32((uint64_t)nfb + iv.n, "the call needs ", "blocks");
-	// the blocks of the normalised records follow them all
-	const uint32_t nb0 = r.nb0 = nfb + iv.n;
-	refuse_2_32((uint64_t)nb0 + r.nn, "the call needs ", "blocks");
-	const uint32_t nb = r.nb = nb0 + r.nn;
-	HIP_CHECK(hipMemsetAsync(r.bcnt + nb, 0, 8, s));
-	if (nfc)
-		KLAUNCH(k_cl_block_cnt, dim3(stride_blocks(nfc)), dim3(Q_TPB), 0, s, nfc, r.blist, w.aoff, r.bcnt);
+	// the four families of blocks in the layout's order: one extra block per own REF, one block per inversion record, one per
+	// record the normalisation changed
+	refuse_2_32((uint64_t)L.nfc + nx, "the call needs ", "blocks");
+	L.nfb = L.nfc + nx;
+	refuse_2_32((uint64_t)L.nfb + iv.n, "the call needs ", "blocks");
+	L.nb0 = L.nfb + iv.n;
+	refuse_2_32((uint64_t)L.nb0 + nn, "the call needs ", "blocks");
+	L.nb = L.nb0 + nn;
+	HIP_CHECK(hipMemsetAsync(r.bcnt + L.nb, 0, 8, s));
+	if (L.nfc)
+		KLAUNCH(k_cl_block_cnt, dim3(stride_blocks(L.nfc)), dim3(Q_TPB), 0, s, L.nfc, r.blist, w.v.aoff, r.bcnt);
 	if (nx)
-		KLAUNCH(k_cl_extra, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rstate, r.xoff, r.xlist, r.bcnt + nfc);
-	inv_genotypes(ctx, inv.in, iv, o, nfb, r.bcnt);
-	if (r.nn)
-		norm_blocks(ctx, w.ni, nfl, w.perm, inv.f_dst, nw, nb0, r.bcnt);
-	scan_exclusive_u64(r.bcnt, r.block_off, (size_t)nb + 1, s64, s);
-	HIP_CHECK(copy_async(&r.nsp, r.block_off + nb, 8, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(copy_async(&r.nsp0, r.block_off + nb0, 8, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(copy_async(&r.nfsp, r.block_off + nfb, 8, hipMemcpyDeviceToHost, s));
+		KLAUNCH(k_cl_extra, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rstate, r.xoff, L, r.xlist, r.bcnt);
+	inv_genotypes(ctx, inv.in, iv, o, L.inversion().b0, r.bcnt);
+	if (nn)
+		norm_blocks(ctx, w.v, nfl, w.perm, inv.f_dst, nw, L.normalised().b0, r.bcnt);
+	scan_exclusive_u64(r.bcnt, r.block_off, (size_t)L.nb + 1, s64, s);
+	HIP_CHECK(copy_async(&L.nsp, r.block_off + L.nb, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(&L.nsp0, r.block_off + L.nb0, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(&L.nfsp, r.block_off + L.nfb, 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
 }
 
 // GT rows and counts, then the spelled alleles: lengths, offsets, bytes, the bad-byte refusal
-void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, const CallWs &w, const CallInv &inv, const CallRecs &r, CallSpelled &sp)
+void spelling(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, const CallRecs &r, CallSpelled &sp)
 {
-	const ResidentGraph &g = ctx->g;
 	hipStream_t s = ctx->stream;
-	const uint32_t nR = in.nR, nfl = w.nfl, nfb = r.nfb;
-	const uint64_t nsp = r.nsp, nfsp = r.nfsp;
+	const uint32_t nR = in.nR, nfl = w.nfl;
+	const BlockLayout &L = r.L;
+	const uint64_t nsp = L.nsp, nfsp = L.flubble().ns;
 	const InvDevice &iv = inv.v;
 	const InvRows &o = r.rows;
 	uint64_t *slen, *alen, *s64;
@@ -1014,22 +919,18 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, cons
 	HIP_CHECK(hipMemsetAsync(sp.ac, 0, (r.n_ac + 1) * 4, s));
 	HIP_CHECK(hipMemsetAsync(bad, 0xFF, 8, s));
 	if (nfl) {
-		KLAUNCH(k_cl_records, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, o.o_q, o.o_path, o.o_ref, w.qidx, w.d_slot, w.d_slot_first, in.NS, in.S, w.smin,
-			w.smax, r.ac_off, d.qstatus, w.perm, w.rstate, in.nested ? w.collapsed : nullptr, in.nested ? w.nr.rescued : nullptr, o.gt, sp.ac, o.o_an,
-			o.o_ns, o.o_flags, inv.f_dst);
-		KLAUNCH(k_cl_rec_block, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.rlist, d.rq, d.orv, r.boff, o.o_block, inv.f_dst, w.rstate,
-			r.xoff, r.xrow);
+		KLAUNCH(k_cl_records, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.v, w.slots, o, w.qidx, w.smin, w.smax, r.ac_off, w.perm,
+			in.nested ? w.collapsed : nullptr, in.nested ? w.nr.rescued : nullptr, sp.ac, inv.f_dst);
+		KLAUNCH(k_cl_rec_block, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.v, r.boff, o.o_block, inv.f_dst, r.xoff, r.xrow);
 	}
 	inv_counts(ctx, inv.in, iv, o, r.ac_off, sp.ac);
 	HIP_CHECK(hipMemsetAsync(slen + nsp, 0, 8, s));
 	HIP_CHECK(hipMemsetAsync(alen + nsp, 0, 8, s));
-	const SpellTab T{nfb,	 r.nfc,	  r.block_off, r.blist, w.aoff,		 w.afirst, r.xlist, w.rlist, d.rq,
-			  d.orv, w.rstate, d.rpos,     d.rlen,	ctx->path_steps, w.ilen,   w.atl,   w.xilen, w.xatl};
+	const FlubbleBlocks B{L, r.block_off, r.blist, r.xlist};
 	if (nfsp)
-		KLAUNCH(k_cl_spell_len, dim3(stride_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, T, ctx->seq_off, g.vid, slen, alen);
-	inv_spell_len(ctx, inv.in, iv, slen + nfsp, alen + nfsp);
-	if (r.nn)
-		norm_spell_len(ctx, w.ni, w.nm, r.nrows, r.nn, r.block_off + r.nb0, nsp - r.nsp0, slen + r.nsp0, alen + r.nsp0);
+		KLAUNCH(k_cl_spell_len, dim3(stride_blocks(nfsp)), dim3(Q_TPB), 0, s, w.v, B, slen, alen);
+	inv_spell_len(ctx, inv.in, iv, L, slen, alen);
+	norm_spell_len(ctx, w.v, w.nm, r.nrows, L, r.block_off, slen, alen);
 	scan_exclusive_u64(slen, sp.sp_off, nsp + 1, s64, s);
 	scan_exclusive_u64(alen, sp.at_off, nsp + 1, s64, s);
 	HIP_CHECK(copy_async(sp.nbytes, sp.sp_off + nsp, 8, hipMemcpyDeviceToHost, s));
@@ -1037,12 +938,11 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, cons
 	HIP_CHECK(hipStreamSynchronize(s));
 	carve(ctx->cl_bytes, [&](Spans &take) { take(sp.nbytes[0] + 1, sp.o_seq), take(sp.nbytes[1] + 1, sp.o_at); });
 	if (nfsp)
-		KLAUNCH(k_cl_emit, dim3(wave_blocks(nfsp)), dim3(Q_TPB), 0, s, nfsp, T, ctx->seq_off, ctx->seq, g.vid, sp.sp_off, sp.at_off, sp.o_seq, sp.o_at, bad);
-	inv_emit(ctx, inv.in, iv, sp.sp_off + nfsp, sp.at_off + nfsp, sp.o_seq, sp.o_at, bad);
-	if (r.nn)
-		norm_emit(ctx, w.ni, w.nm, r.nrows, r.nn, r.block_off + r.nb0, nsp - r.nsp0, sp.sp_off + r.nsp0, sp.o_seq, bad);
+		KLAUNCH(k_cl_emit, dim3(wave_blocks(nfsp)), dim3(Q_TPB), 0, s, w.v, B, sp.sp_off, sp.at_off, sp.o_seq, sp.o_at, bad);
+	inv_emit(ctx, inv.in, iv, L, sp.sp_off, sp.at_off, sp.o_seq, sp.o_at, bad);
+	norm_emit(ctx, w.v, w.nm, r.nrows, L, r.block_off, sp.sp_off, sp.o_seq, bad);
 	if (r.nrec)
-		KLAUNCH(k_cl_ref_spelled, dim3(stride_blocks(r.nrec)), dim3(Q_TPB), 0, s, r.nrec, o.o_block, o.o_ref, r.xrow, r.block_off, r.nfc, r.ref_spelled);
+		KLAUNCH(k_cl_ref_spelled, dim3(stride_blocks(r.nrec)), dim3(Q_TPB), 0, s, r.nrec, o.o_block, o.o_ref, r.xrow, r.block_off, L, r.ref_spelled);
 	uint64_t hbad = 0;
 	HIP_CHECK(copy_async(&hbad, bad, 8, hipMemcpyDeviceToHost, s));
 	sp.h_roff.resize(nR ? nR + 1 : 1);
@@ -1050,60 +950,64 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, cons
 		HIP_CHECK(copy_async(sp.h_roff.data() + k, w.roff + w.ref_base[k], 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
 	if (hbad != ~0ull)
-		throw HipError("segment " + std::to_string(read_back(g.vid + hbad, s)) + " holds a byte that is no nucleotide code (ACGTN, lower case, IUPAC)");
+		throw HipError("segment " + std::to_string(read_back(ctx->g.vid + hbad, s)) + " holds a byte that is no nucleotide code (ACGTN, lower case, IUPAC)");
 }
 
 povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, const CallRecs &r, const CallSpelled &sp,
 			      CallTimer &timer)
 {
-	const uint32_t nrec = r.nrec, nb = r.nb, nR = in.nR, S = in.S;
-	const uint64_t nsp = r.nsp, n_ac = r.n_ac;
-	const size_t r1 = (size_t)nrec + 1;
+	const uint32_t nrec = r.nrec, nb = r.L.nb, nR = in.nR, S = in.S;
+	const uint64_t nsp = r.L.nsp;
 	const InvRows &d = r.rows;
+	const NormRows &nw = r.nrows;
 	const InvDevice &iv = inv.v;
 	auto o = std::make_unique<CallsOwner>();
-	hand_off(o->query, nrec, d.o_q, nrec, ctx);
-	hand_off(o->path, nrec, d.o_path, nrec, ctx);
-	hand_off(o->first, nrec, d.o_first, nrec, ctx);
-	hand_off(o->ref_allele, nrec, d.o_ref, nrec, ctx);
-	hand_off(o->n_alleles, nrec, d.o_nal, nrec, ctx);
-	hand_off(o->an, nrec, d.o_an, nrec, ctx);
-	hand_off(o->ns, nrec, d.o_ns, nrec, ctx);
-	hand_off(o->block, nrec, d.o_block, nrec, ctx);
-	hand_off(o->n_steps, nrec, d.o_nsteps, nrec, ctx);
-	hand_off(o->pos, nrec, d.o_pos, nrec, ctx);
-	hand_off(o->flags, nrec, d.o_flags, nrec, ctx);
-	hand_off(o->level, nrec, r.o_level, nrec, ctx);
-	hand_off(o->parent_query, nrec, r.o_parent, nrec, ctx);
-	hand_off(o->ref_spelled, nrec, r.ref_spelled, nrec, ctx);
-	hand_off(o->ac_off, r1, r.ac_off, r1, ctx);
-	hand_off(o->ac, n_ac, sp.ac, n_ac, ctx);
-	hand_off(o->gt, (size_t)nrec * S, d.gt, (size_t)nrec * S, ctx);
-	hand_off(o->block_off, (size_t)nb + 1, r.block_off, (size_t)nb + 1, ctx);
-	hand_off(o->seq_off, nsp + 1, sp.sp_off, nsp + 1, ctx);
-	hand_off(o->at_off, nsp + 1, sp.at_off, nsp + 1, ctx);
-	hand_off(o->seq, sp.nbytes[0], sp.o_seq, sp.nbytes[0], ctx);
-	hand_off(o->at, sp.nbytes[1], sp.o_at, sp.nbytes[1], ctx);
-	const NormRows &nw = r.nrows;
-	if (in.normalized) {
-		hand_off(o->raw_pos, nrec, nw.o_raw_pos, nrec, ctx);
-		hand_off(o->norm_block, nrec, nw.o_block, nrec, ctx);
-		hand_off(o->norm_shift, nrec, nw.o_shift, nrec, ctx);
-		hand_off(o->norm_chop, nrec, nw.o_chop, nrec, ctx);
-		hand_off(o->norm_trim, nrec, nw.o_trim, nrec, ctx);
-	}
-	o->view.device_ms = timer.stop(ctx->stream);
-	if (!in.normalized) { // nothing was normalised: the fields say so, filled here
-		o->raw_pos.assign(o->pos.data(), o->pos.data() + nrec);
-		o->norm_block.assign(nrec, POVU_HIP_NIL);
-		o->norm_shift.assign(nrec, 0u);
-		o->norm_chop.assign(nrec, 0u);
-		o->norm_trim.assign(nrec, 0u);
-	}
+	povu_hip_calls &v = o->view;
+	// a result array: the owner's vector, the field of the view, the n elements on the device.  The copies go in this order
+	auto give = [&](auto &vec, auto &field, const auto *dev, size_t n) { hand_off(vec, n, dev, n, ctx), field = vec.data(); };
+	// ... of the left-normalisation: per record; without the profile what says that nothing was normalised, filled on the host
+	// once the device time is taken
+	std::vector<std::function<void()>> defaults;
+	auto give_norm = [&](auto &vec, auto &field, const auto *dev, auto fill) {
+		if (in.normalized)
+			return give(vec, field, dev, nrec);
+		defaults.push_back([&vec, &field, fill] { fill(vec), field = vec.data(); });
+	};
+	auto all = [nrec](auto value) { return [=](auto &vec) { vec.assign(nrec, value); }; };
+	give(o->query, v.query, d.o_q, nrec);
+	give(o->path, v.path, d.o_path, nrec);
+	give(o->first, v.first, d.o_first, nrec);
+	give(o->ref_allele, v.ref_allele, d.o_ref, nrec);
+	give(o->n_alleles, v.n_alleles, d.o_nal, nrec);
+	give(o->an, v.an, d.o_an, nrec);
+	give(o->ns, v.ns, d.o_ns, nrec);
+	give(o->block, v.block, d.o_block, nrec);
+	give(o->n_steps, v.n_steps, d.o_nsteps, nrec);
+	give(o->pos, v.pos, d.o_pos, nrec);
+	give(o->flags, v.flags, d.o_flags, nrec);
+	give(o->level, v.level, r.o_level, nrec);
+	give(o->parent_query, v.parent_query, r.o_parent, nrec);
+	give(o->ref_spelled, v.ref_spelled, r.ref_spelled, nrec);
+	give(o->ac_off, v.ac_off, r.ac_off, (size_t)nrec + 1);
+	give(o->ac, v.ac, sp.ac, r.n_ac);
+	give(o->gt, v.gt, d.gt, (size_t)nrec * S);
+	give(o->block_off, v.block_off, r.block_off, (size_t)nb + 1);
+	give(o->seq_off, v.seq_off, sp.sp_off, nsp + 1);
+	give(o->at_off, v.at_off, sp.at_off, nsp + 1);
+	give(o->seq, v.seq, sp.o_seq, sp.nbytes[0]);
+	give(o->at, v.at, sp.o_at, sp.nbytes[1]);
+	give_norm(o->raw_pos, v.raw_pos, nw.o_raw_pos, [&](auto &vec) { vec.assign(o->pos.data(), o->pos.data() + nrec); });
+	give_norm(o->norm_block, v.norm_block, nw.o_block, all(POVU_HIP_NIL));
+	give_norm(o->norm_shift, v.norm_shift, nw.o_shift, all(0u));
+	give_norm(o->norm_chop, v.norm_chop, nw.o_chop, all(0u));
+	give_norm(o->norm_trim, v.norm_trim, nw.o_trim, all(0u));
+	v.device_ms = timer.stop(ctx->stream);
+	for (const auto &fill : defaults)
+		fill();
 	o->contig_len.resize(nR);
 	for (uint32_t k = 0; k < nR; k++)
 		o->contig_len[k] = sp.h_roff[k + 1] - sp.h_roff[k];
-	povu_hip_calls &v = o->view;
+	v.contig_len = o->contig_len.data();
 	v.n_records = nrec;
 	v.n_slots = S;
 	v.n_blocks = nb;
@@ -1111,18 +1015,9 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	v.n_seq_bytes = sp.nbytes[0];
 	v.n_at_bytes = sp.nbytes[1];
 	v.n_refs = nR;
-	v.n_steps = o->n_steps.data();
 	v.n_inv_records = iv.n, v.n_inv_heads = iv.n_heads, v.n_inv_long = iv.n_long, v.n_inv_tier2 = iv.n_tier2;
-	v.query = o->query.data(), v.path = o->path.data(), v.first = o->first.data(), v.ref_allele = o->ref_allele.data();
-	v.n_alleles = o->n_alleles.data(), v.an = o->an.data(), v.ns = o->ns.data(), v.block = o->block.data();
-	v.pos = o->pos.data(), v.flags = o->flags.data(), v.ac_off = o->ac_off.data(), v.ac = o->ac.data(), v.gt = o->gt.data();
-	v.block_off = o->block_off.data(), v.seq_off = o->seq_off.data(), v.at_off = o->at_off.data(), v.seq = o->seq.data();
-	v.at = o->at.data(), v.contig_len = o->contig_len.data();
-	v.level = o->level.data(), v.parent_query = o->parent_query.data(), v.ref_spelled = o->ref_spelled.data();
 	v.nested = in.nested ? 1 : 0;
 	v.n_enclosed = w.nr.n_enclosed, v.n_collapsed_sites = w.n_collapsed, v.n_popped = w.nr.n_popped, v.n_rescued = w.nr.n_rescued;
-	v.raw_pos = o->raw_pos.data(), v.norm_block = o->norm_block.data(), v.norm_shift = o->norm_shift.data();
-	v.norm_chop = o->norm_chop.data(), v.norm_trim = o->norm_trim.data();
 	v.n_normalized = w.nm.n_changed, v.max_shift = w.nm.max_shift, v.n_norm_compared = w.nm.n_compared;
 	CallsOwner *raw = o.release();
 	return &raw->view;
@@ -1155,10 +1050,10 @@ extern "C" povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_h
 		flubble_records(ctx, in, d, w);
 		CallInv inv;
 		CallRecs r;
-		r.nrec = inversion_rows(ctx, in, d, w, inv);
-		record_arrays(ctx, in, d, w, inv, r);
+		r.nrec = inversion_rows(ctx, in, w, inv);
+		record_arrays(ctx, in, w, inv, r);
 		CallSpelled sp;
-		spelling(ctx, in, d, w, inv, r, sp);
+		spelling(ctx, in, w, inv, r, sp);
 		return calls_to_host(ctx, in, w, inv, r, sp, timer);
 	});
 }

@@ -20,14 +20,10 @@ namespace povu_hip
 
 static constexpr uint32_t TIER1_STEPS = 64, LONG_LIST = 64;
 
-// what the kernels read of the resident paths and the references
+// what the kernels read of the references and the resident paths
 struct InvView {
-	uint64_t NR;
-	uint32_t nR, P;
-	const uint64_t *ref_base;
-	const uint32_t *ref_path;
-	const uint64_t *path_off;
-	const uint32_t *steps;
+	RefView ref;
+	PathsView paths;
 	const uint32_t *ioff, *occ; // the step index: positions occ[ioff[x] .. ioff[x + 1]) hold step value x, ascending
 };
 // reference step i: its path, its global position, its path's end
@@ -38,22 +34,22 @@ struct RefStep {
 __device__ __forceinline__ RefStep ref_step(const InvView &A, uint64_t i)
 {
 	RefStep x;
-	x.r = span_of(A.ref_base, A.nR, i);
-	x.path = A.ref_path[x.r];
-	x.begin = A.path_off[x.path];
-	x.end = A.path_off[x.path + 1];
-	x.g = x.begin + (i - A.ref_base[x.r]);
+	x.r = span_of(A.ref.ref_base, A.ref.nR, i);
+	x.path = A.ref.ref_path[x.r];
+	x.begin = A.paths.path_off[x.path];
+	x.end = A.paths.path_off[x.path + 1];
+	x.g = x.begin + (i - A.ref.ref_base[x.r]);
 	return x;
 }
 // is (x, y) the head of a run: y on another path, and (x - 1, y + 1) no match
 __device__ __forceinline__ bool is_head(const InvView &A, const RefStep &x, uint32_t y)
 {
-	const uint32_t pa = span_of(A.path_off, A.P, y);
+	const uint32_t pa = span_of(A.paths.path_off, A.paths.n_paths, y);
 	if (pa == x.path)
 		return false;
-	if (x.g == x.begin || (uint64_t)y + 1 >= A.path_off[pa + 1])
+	if (x.g == x.begin || (uint64_t)y + 1 >= A.paths.path_off[pa + 1])
 		return true;
-	return A.steps[y + 1] != (A.steps[x.g - 1] ^ 1u);
+	return A.paths.steps[y + 1] != (A.paths.steps[x.g - 1] ^ 1u);
 }
 
 __global__ void k_inv_hist(uint32_t N, const uint32_t *__restrict__ steps, uint32_t *__restrict__ cnt)
@@ -68,9 +64,9 @@ template <bool EMIT>
 __global__ void k_inv_heads(InvView A, uint32_t long_min, uint64_t *__restrict__ cnt, const uint64_t *__restrict__ hoff,
 			    uint32_t *__restrict__ hx, uint32_t *__restrict__ hy, uint32_t *__restrict__ longs, uint32_t *__restrict__ n_longs)
 {
-	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < A.NR; i += (uint64_t)gridDim.x * Q_TPB) {
+	for (uint64_t i = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; i < A.ref.NR; i += (uint64_t)gridDim.x * Q_TPB) {
 		const RefStep x = ref_step(A, i);
-		const uint32_t v = A.steps[x.g] ^ 1u, e0 = A.ioff[v], e1 = A.ioff[v + 1];
+		const uint32_t v = A.paths.steps[x.g] ^ 1u, e0 = A.ioff[v], e1 = A.ioff[v + 1];
 		if (e1 - e0 >= long_min) {
 			if (!EMIT)
 				longs[atomicAdd(n_longs, 1u)] = (uint32_t)i;
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(Q_TPB) void k_inv_heads_wave(InvView A, const uint3
 	for (uint32_t w = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); w < n_longs; w += waves) {
 		const uint64_t i = longs[w];
 		const RefStep x = ref_step(A, i);
-		const uint32_t v = A.steps[x.g] ^ 1u, e0 = A.ioff[v], e1 = A.ioff[v + 1];
+		const uint32_t v = A.paths.steps[x.g] ^ 1u, e0 = A.ioff[v], e1 = A.ioff[v + 1];
 		uint64_t c = 0;
 		for (uint32_t b = e0; b < e1; b += 64) { // (e1 + 64 < 2^32: inv_find refuses more steps)
 			const uint32_t e = b + lane;
@@ -131,8 +127,8 @@ __device__ __forceinline__ RunView run_view(const InvView &A, uint32_t i, uint32
 	RunView r;
 	r.gx = x.g;
 	r.y = y;
-	r.pa = span_of(A.path_off, A.P, y);
-	const uint64_t lx = x.end - x.g, ly = (uint64_t)y - A.path_off[r.pa] + 1;
+	r.pa = span_of(A.paths.path_off, A.paths.n_paths, y);
+	const uint64_t lx = x.end - x.g, ly = (uint64_t)y - A.paths.path_off[r.pa] + 1;
 	r.lim = min(min(lx, ly), (uint64_t)max_steps + 1);
 	return r;
 }
@@ -147,7 +143,7 @@ __global__ void k_inv_extend(uint32_t H, InvView A, uint32_t max_steps, uint32_t
 		const uint64_t cap = min(r.lim, (uint64_t)TIER1_STEPS + 1);
 		uint64_t n = 1;
 		if (!force)
-			while (n < cap && A.steps[r.gx + n] == (A.steps[r.y - n] ^ 1u))
+			while (n < cap && A.paths.steps[r.gx + n] == (A.paths.steps[r.y - n] ^ 1u))
 				n++;
 		if (force || n > TIER1_STEPS)
 			t2[atomicAdd(n_t2, 1u)] = h;
@@ -173,7 +169,7 @@ __global__ __launch_bounds__(Q_TPB) void k_inv_extend_wave(const uint32_t *__res
 		uint64_t n = r.lim;
 		for (uint64_t base = 1; base < r.lim; base += 64) {
 			const uint64_t k = base + lane;
-			const bool stop = k < r.lim && A.steps[r.gx + k] != (A.steps[r.y - k] ^ 1u);
+			const bool stop = k < r.lim && A.paths.steps[r.gx + k] != (A.paths.steps[r.y - k] ^ 1u);
 			const unsigned long long m = __ballot(stop);
 			if (m) {
 				n = base + (uint64_t)(__ffsll((long long)m) - 1);
@@ -225,11 +221,11 @@ __global__ void k_inv_records(uint32_t n, InvView A, const uint32_t *__restrict_
 		run_rec[t] = b;
 		run_slot[t] = hslot[h];
 		if (first[t]) {
-			const uint32_t i = hx[h], r = span_of(A.ref_base, A.nR, i);
+			const uint32_t i = hx[h], r = span_of(A.ref.ref_base, A.ref.nR, i);
 			v_ref[b] = r;
 			v_at[b] = i;
 			v_steps[b] = hL[h];
-			v_pos[b] = roff[(uint64_t)i + 1] - roff[A.ref_base[r]] + 1; // the locus of the run's second step
+			v_pos[b] = roff[(uint64_t)i + 1] - roff[A.ref.ref_base[r]] + 1; // the locus of the run's second step
 		}
 	}
 }
@@ -274,8 +270,8 @@ __global__ void k_inv_fields(uint32_t ninv, InvView A, const uint32_t *__restric
 	for (uint32_t b = blockIdx.x * Q_TPB + threadIdx.x; b < ninv; b += gridDim.x * Q_TPB) {
 		const uint32_t d = v_dst[b], r = v_ref[b];
 		o.o_q[d] = NO_QUERY;
-		o.o_path[d] = A.ref_path[r];
-		o.o_first[d] = (uint32_t)(v_at[b] - A.ref_base[r]);
+		o.o_path[d] = A.ref.ref_path[r];
+		o.o_first[d] = (uint32_t)(v_at[b] - A.ref.ref_base[r]);
 		o.o_ref[d] = 0;
 		o.o_nal[d] = 2;
 		o.o_pos[d] = v_pos[b];
@@ -289,7 +285,7 @@ __global__ void k_inv_gt_init(uint64_t n, uint32_t S, uint32_t nb, InvView A, co
 {
 	for (uint64_t e = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; e < n; e += (uint64_t)gridDim.x * Q_TPB) {
 		const uint32_t b = (uint32_t)(e / S), sl = (uint32_t)(e % S);
-		gt[(uint64_t)v_dst[b] * S + sl] = sl == slot_of_path[A.ref_path[v_ref[b]]] ? 0 : POVU_HIP_GT_MISSING;
+		gt[(uint64_t)v_dst[b] * S + sl] = sl == slot_of_path[A.ref.ref_path[v_ref[b]]] ? 0 : POVU_HIP_GT_MISSING;
 		if (sl == 0) {
 			o_block[v_dst[b]] = nb + b;
 			bcnt[nb + b] = 2;
@@ -303,7 +299,7 @@ __global__ void k_inv_gt_mark(uint32_t n_runs, uint32_t S, InvView A, const uint
 {
 	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < n_runs; t += gridDim.x * Q_TPB) {
 		const uint32_t b = run_rec[t], sl = run_slot[t];
-		if (sl != slot_of_path[A.ref_path[v_ref[b]]])
+		if (sl != slot_of_path[A.ref.ref_path[v_ref[b]]])
 			gt[(uint64_t)v_dst[b] * S + sl] = 1;
 	}
 }
@@ -352,7 +348,7 @@ __global__ __launch_bounds__(Q_TPB) void k_inv_spell_len(uint32_t ninv, InvView 
 		const uint32_t L = v_steps[b];
 		uint32_t w = 0;
 		for (uint32_t k = lane; k < L; k += 64)
-			w += 1 + ndig(vid[A.steps[g + k] >> 1]);
+			w += 1 + ndig(vid[A.paths.steps[g + k] >> 1]);
 		w = wave_sum(w);
 		if (lane < 2) {
 			slen[2 * (uint64_t)b + lane] = roff[i + L] - roff[i];
@@ -371,16 +367,16 @@ __global__ __launch_bounds__(Q_TPB) void k_inv_emit(uint64_t n, InvView A, const
 		const uint32_t b = (uint32_t)(j >> 1), L = v_steps[b];
 		const bool alt = j & 1u;
 		const uint64_t g = ref_step(A, v_at[b]).g;
-		const uint32_t *steps = A.steps;
+		const uint32_t *steps = A.paths.steps;
 		emit_steps(
 			lane, L, [&](uint32_t k) { return alt ? steps[g + L - 1 - k] ^ 1u : steps[g + k]; }, seq_off, seq, vid, s_off[j], a_off[j],
 			o_seq, o_at, bad);
 	}
 }
 
-static InvView view_of(const povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v)
+static InvView view_of(const InvIn &in, const InvDevice &v)
 {
-	return InvView{in.NR, in.nR, ctx->n_paths, in.ref_base, in.ref_path, ctx->path_off, ctx->path_steps, v.ioff, v.occ};
+	return InvView{in.ref, in.paths, v.ioff, v.occ};
 }
 
 namespace
@@ -405,7 +401,7 @@ struct InvHeads {
 static InvIndex step_index(povu_hip_ctx *ctx, const InvIn &in, InvDevice &v)
 {
 	hipStream_t s = ctx->stream;
-	const uint64_t N = ctx->n_path_steps, NR = in.NR;
+	const uint64_t N = ctx->n_path_steps, NR = in.ref.NR;
 	const uint32_t V = ctx->g.V;
 	const size_t nval = 2 * (size_t)V + 1;
 	const size_t tmp_bytes = std::max(sort_tmp_bytes(N + 1), prim_tmp_bytes(nval + 1, false)) + 256;
@@ -439,7 +435,7 @@ static InvIndex step_index(povu_hip_ctx *ctx, const InvIn &in, InvDevice &v)
 static InvHeads run_heads(povu_hip_ctx *ctx, const InvView &A, InvIndex &x, InvDevice &v)
 {
 	hipStream_t s = ctx->stream;
-	const uint64_t NR = A.NR;
+	const uint64_t NR = A.ref.NR;
 	InvHeads h;
 	KLAUNCH(k_inv_heads<false>, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, A, x.long_min, x.hcnt, x.hoff, (uint32_t *)nullptr, (uint32_t *)nullptr, x.longs,
 		x.words);
@@ -471,7 +467,7 @@ static void extend(povu_hip_ctx *ctx, const InvIn &in, const InvView &A, const I
 {
 	hipStream_t s = ctx->stream;
 	KLAUNCH(k_inv_extend, dim3(stride_blocks(h.H)), dim3(Q_TPB), 0, s, h.H, A, in.max_steps, in.force_tier2 ? 1u : 0u, h.hx, h.hy, h.hL, h.hslot,
-		in.slot_of_path, h.t2, x.words + 1);
+		in.slots.slot_of_path, h.t2, x.words + 1);
 	const uint32_t n_t2 = read_back(x.words + 1, s);
 	v.n_tier2 = n_t2;
 	if (n_t2)
@@ -483,7 +479,7 @@ static void records(povu_hip_ctx *ctx, const InvIn &in, const InvView &A, const 
 {
 	hipStream_t s = ctx->stream;
 	const uint32_t H = h.H;
-	KLAUNCH(k_inv_report, dim3(stride_blocks(H)), dim3(Q_TPB), 0, s, H, in.max_steps, h.hx, h.hL, in.roff, h.flag, x.n_long);
+	KLAUNCH(k_inv_report, dim3(stride_blocks(H)), dim3(Q_TPB), 0, s, H, in.max_steps, h.hx, h.hL, in.ref.roff, h.flag, x.n_long);
 	compact_flagged_u8(h.flag, H, h.rlist, x.words + 3, h.tmp, h.tmp_bytes, s);
 	uint32_t n_runs = 0;
 	unsigned long long h_long = 0;
@@ -498,15 +494,15 @@ static void records(povu_hip_ctx *ctx, const InvIn &in, const InvView &A, const 
 	auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
 		KLAUNCH(k_inv_key, dim3(stride_blocks(n_runs)), dim3(Q_TPB), 0, s, n_runs, which, perm, h.hx, h.hL, h.hslot, k);
 	};
-	if (in.S > 1)
-		sort.pass(0, bits_for(in.S - 1), write_key);
+	if (in.slots.S > 1)
+		sort.pass(0, bits_for(in.slots.S - 1), write_key);
 	sort.pass(1, bits_for(in.max_steps), write_key);
-	sort.pass(2, bits_for(A.NR), write_key);
+	sort.pass(2, bits_for(A.ref.NR), write_key);
 	const uint32_t *cur = sort.cur;
 	KLAUNCH(k_inv_group, dim3(stride_blocks((size_t)H + 1)), dim3(Q_TPB), 0, s, n_runs, cur, h.hx, h.hL, h.first);
 	scan_exclusive_u32(h.first, h.rank, (size_t)n_runs + 1, h.tmp, h.tmp_bytes, s);
 	HIP_CHECK(copy_async(&v.n, h.rank + n_runs, 4, hipMemcpyDeviceToHost, s));
-	KLAUNCH(k_inv_records, dim3(stride_blocks(n_runs)), dim3(Q_TPB), 0, s, n_runs, A, cur, h.hx, h.hL, h.hslot, h.first, h.rank, in.roff, v.run_rec,
+	KLAUNCH(k_inv_records, dim3(stride_blocks(n_runs)), dim3(Q_TPB), 0, s, n_runs, A, cur, h.hx, h.hL, h.hslot, h.first, h.rank, in.ref.roff, v.run_rec,
 		v.run_slot, v.ref, v.at, v.steps, v.pos);
 	HIP_CHECK(hipStreamSynchronize(s));
 }
@@ -517,10 +513,10 @@ InvDevice inv_find(povu_hip_ctx *ctx, const InvIn &in)
 	if (N >= 0xFFFFFFFFull - 4096) // (the sort of the step index takes fewer)
 		throw HipError("inversion calls index every path step: " + std::to_string(N) + " steps, 2^32 or more are refused");
 	InvDevice v;
-	if (!N || !in.NR)
+	if (!N || !in.ref.NR)
 		return v;
 	InvIndex x = step_index(ctx, in, v);
-	const InvView A = view_of(ctx, in, v);
+	const InvView A = view_of(in, v);
 	const InvHeads h = run_heads(ctx, A, x, v);
 	if (!h.H)
 		return v;
@@ -541,39 +537,42 @@ void inv_merge(povu_hip_ctx *ctx, InvDevice &v, uint32_t nrec, const uint32_t *f
 void inv_fields(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o)
 {
 	if (v.n)
-		KLAUNCH(k_inv_fields, dim3(stride_blocks(v.n)), dim3(Q_TPB), 0, ctx->stream, v.n, view_of(ctx, in, v), v.ref, v.at, v.steps, v.pos, v.dst, o);
+		KLAUNCH(k_inv_fields, dim3(stride_blocks(v.n)), dim3(Q_TPB), 0, ctx->stream, v.n, view_of(in, v), v.ref, v.at, v.steps, v.pos, v.dst, o);
 }
 
-void inv_genotypes(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o, uint32_t nb, uint64_t *bcnt)
+void inv_genotypes(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o, uint32_t first_block, uint64_t *bcnt)
 {
 	if (!v.n)
 		return;
 	hipStream_t s = ctx->stream;
-	const InvView A = view_of(ctx, in, v);
-	KLAUNCH(k_inv_gt_init, dim3(stride_blocks((size_t)v.n * in.S)), dim3(Q_TPB), 0, s, (uint64_t)v.n * in.S, in.S, nb, A, v.ref, v.dst, in.slot_of_path, o.gt,
+	const InvView A = view_of(in, v);
+	KLAUNCH(k_inv_gt_init, dim3(stride_blocks((size_t)v.n * in.slots.S)), dim3(Q_TPB), 0, s, (uint64_t)v.n * in.slots.S, in.slots.S, first_block, A, v.ref, v.dst, in.slots.slot_of_path, o.gt,
 		o.o_block, bcnt);
-	KLAUNCH(k_inv_gt_mark, dim3(stride_blocks(v.n_runs)), dim3(Q_TPB), 0, s, v.n_runs, in.S, A, v.run_rec, v.run_slot, v.ref, v.dst, in.slot_of_path, o.gt);
+	KLAUNCH(k_inv_gt_mark, dim3(stride_blocks(v.n_runs)), dim3(Q_TPB), 0, s, v.n_runs, in.slots.S, A, v.run_rec, v.run_slot, v.ref, v.dst, in.slots.slot_of_path, o.gt);
 }
 
 void inv_counts(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const InvRows &o, const uint64_t *ac_off, uint32_t *ac)
 {
 	if (v.n)
-		KLAUNCH(k_inv_gt_count, dim3(wave_blocks(v.n)), dim3(Q_TPB), 0, ctx->stream, v.n, in.S, in.NS, in.slot_first, v.dst, o.gt, ac_off, ac, o.o_an,
+		KLAUNCH(k_inv_gt_count, dim3(wave_blocks(v.n)), dim3(Q_TPB), 0, ctx->stream, v.n, in.slots.S, in.slots.NS, in.slots.slot_first, v.dst, o.gt, ac_off, ac, o.o_an,
 			o.o_ns, o.o_flags);
 }
 
-void inv_spell_len(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, uint64_t *slen, uint64_t *alen)
+void inv_spell_len(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const BlockLayout &L, uint64_t *slen, uint64_t *alen)
 {
+	const uint64_t s0 = L.inversion().s0;
 	if (v.n)
-		KLAUNCH(k_inv_spell_len, dim3(wave_blocks(v.n)), dim3(Q_TPB), 0, ctx->stream, v.n, view_of(ctx, in, v), v.at, v.steps, in.roff, ctx->g.vid, slen, alen);
+		KLAUNCH(k_inv_spell_len, dim3(wave_blocks(v.n)), dim3(Q_TPB), 0, ctx->stream, v.n, view_of(in, v), v.at, v.steps, in.ref.roff, in.paths.vid,
+			slen + s0, alen + s0);
 }
 
-void inv_emit(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const uint64_t *s_off, const uint64_t *a_off, char *o_seq, char *o_at,
-	      unsigned long long *bad)
+void inv_emit(povu_hip_ctx *ctx, const InvIn &in, const InvDevice &v, const BlockLayout &L, const uint64_t *s_off, const uint64_t *a_off, char *o_seq,
+	      char *o_at, unsigned long long *bad)
 {
+	const uint64_t s0 = L.inversion().s0;
 	if (v.n)
-		KLAUNCH(k_inv_emit, dim3(wave_blocks(2 * (size_t)v.n)), dim3(Q_TPB), 0, ctx->stream, 2 * (uint64_t)v.n, view_of(ctx, in, v), v.at, v.steps,
-			ctx->seq_off, ctx->seq, ctx->g.vid, s_off, a_off, o_seq, o_at, bad);
+		KLAUNCH(k_inv_emit, dim3(wave_blocks(2 * (size_t)v.n)), dim3(Q_TPB), 0, ctx->stream, 2 * (uint64_t)v.n, view_of(in, v), v.at, v.steps,
+			in.paths.seq_off, in.paths.seq, in.paths.vid, s_off + s0, a_off + s0, o_seq, o_at, bad);
 }
 
 } // namespace povu_hip

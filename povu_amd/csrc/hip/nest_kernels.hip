@@ -56,7 +56,7 @@ __global__ void k_ns_called_flag(uint32_t R, const uint32_t *__restrict__ rq, co
 __global__ void k_ns_pos_key(uint32_t ni, int which, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ rpos, uint32_t *__restrict__ key)
 {
 	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < ni; k += gridDim.x * Q_TPB) {
-		const uint64_t p = rpos[perm[k]] & ~ROLE_BIT;
+		const uint64_t p = trav_first_pos(rpos, perm[k]);
 		key[k] = which ? (uint32_t)(p >> 32) : (uint32_t)p;
 	}
 }
@@ -66,9 +66,9 @@ __global__ void k_ns_index(uint32_t ni, const uint32_t *__restrict__ perm, const
 {
 	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < ni; k += gridDim.x * Q_TPB) {
 		const uint32_t t = perm[k];
-		const uint64_t p = rpos[t] & ~ROLE_BIT;
-		ipos[k] = p;
-		iend[k] = p + rlen[t] - 1;
+		const TravSpan sp = trav_span(rpos, rlen, t);
+		ipos[k] = sp.first_pos();
+		iend[k] = sp.last_pos();
 		iq[k] = rq[t];
 		it[k] = t;
 	}
@@ -121,29 +121,29 @@ __global__ __launch_bounds__(Q_TPB) void k_ns_cover_t1(uint32_t n_al, CoverArgs 
 		A.shash[a] = kept_bits(A, a);
 		return;
 	}
-	const uint32_t t = A.afirst[a], len = A.rlen[t];
-	if (force2 || len > N1_STEPS) {
+	const uint32_t t = A.afirst[a];
+	const TravSpan sp = trav_span(A.rpos, A.rlen, t);
+	if (force2 || sp.len > N1_STEPS) {
 		hand[a] = 1;
 		return;
 	}
-	const uint64_t pos = A.rpos[t] & ~ROLE_BIT, end = pos + len - 1;
-	const bool rev = (A.rpos[t] & ROLE_BIT) != 0;
+	const uint64_t pos = sp.first_pos(), end = sp.last_pos();
 	const uint32_t q = A.rq[t], base = A.soff[a];
 	uint32_t e = first_at_least(A.ipos, A.ni, pos), m = 0;
 	uint64_t top = 0; // the running maximum of the enclosed entries' last positions (every one is at least 1)
 	for (uint64_t k = pos; k <= end; k++) {
 		for (; e < A.ni && A.ipos[e] < k; e++)
-			if (enclosed(A, e, q, end, len))
+			if (enclosed(A, e, q, end, sp.len))
 				top = max(top, A.iend[e]);
 		const bool c = top > k;
-		A.cov[base + (uint32_t)(rev ? end - k : k - pos)] = c;
+		A.cov[base + (uint32_t)(sp.rev ? end - k : k - pos)] = c;
 		m += !c;
 	}
 	uint64_t h = 0;
 	uint32_t j = 0;
-	for (uint32_t i = 0; i < len; i++)
+	for (uint32_t i = 0; i < sp.len; i++)
 		if (!A.cov[base + i]) // (this lane's own stores)
-			h += step_hash(j++, trav_step(A.steps, pos, len, rev, i));
+			h += step_hash(j++, sp.step(A.steps, i));
 	A.slen[a] = m;
 	A.shash[a] = kept_bits(A, h);
 }
@@ -165,17 +165,17 @@ __global__ __launch_bounds__(64) void k_ns_cover_t2(const uint32_t *__restrict__
 	__shared__ uint32_t slot[64];
 	const uint32_t lane = threadIdx.x;
 	for (uint32_t w = blockIdx.x; w < n2; w += gridDim.x) {
-		const uint32_t a = list[w], t = A.afirst[a], len = A.rlen[t], q = A.rq[t], base = A.soff[a];
-		const uint64_t pos = A.rpos[t] & ~ROLE_BIT, end = pos + len - 1;
-		const bool rev = (A.rpos[t] & ROLE_BIT) != 0;
+		const uint32_t a = list[w], t = A.afirst[a], q = A.rq[t], base = A.soff[a];
+		const TravSpan sp = trav_span(A.rpos, A.rlen, t);
+		const uint64_t pos = sp.first_pos(), end = sp.last_pos();
 		uint32_t e = first_at_least(A.ipos, A.ni, pos), carry = 0; // ends relative to pos: at least 1
-		for (uint32_t cb = 0; cb < len; cb += 64) {
+		for (uint32_t cb = 0; cb < sp.len; cb += 64) {
 			// the entries that start at the round's positions: their ends into the slot of their start
 			const uint32_t e_hi = first_at_least(A.ipos, A.ni, pos + cb + 64);
 			slot[lane] = 0;
 			__syncthreads();
 			for (uint32_t x = e + lane; x < e_hi; x += 64)
-				if (enclosed(A, x, q, end, len) && A.ipos[x] - pos - cb < 64)
+				if (enclosed(A, x, q, end, sp.len) && A.ipos[x] - pos - cb < 64)
 					atomicMax(&slot[(uint32_t)(A.ipos[x] - pos) - cb], (uint32_t)(A.iend[x] - pos));
 			__syncthreads();
 			const uint32_t incl = wave_inclusive_max(slot[lane]);
@@ -183,8 +183,8 @@ __global__ __launch_bounds__(64) void k_ns_cover_t2(const uint32_t *__restrict__
 			if (lane == 0)
 				before = 0;
 			const uint32_t k = cb + lane;
-			if (k < len)
-				A.cov[base + (rev ? len - 1 - k : k)] = max(carry, before) > k;
+			if (k < sp.len)
+				A.cov[base + (sp.rev ? sp.len - 1 - k : k)] = max(carry, before) > k;
 			carry = max(carry, __shfl(incl, 63, 64));
 			e = e_hi;
 			__syncthreads();
@@ -196,17 +196,16 @@ __global__ __launch_bounds__(64) void k_ns_skel_t2(const uint32_t *__restrict__ 
 	const uint32_t lane = threadIdx.x;
 	const unsigned long long below = (1ull << lane) - 1ull;
 	for (uint32_t w = blockIdx.x; w < n2; w += gridDim.x) {
-		const uint32_t a = list[w], t = A.afirst[a], len = A.rlen[t], base = A.soff[a];
-		const uint64_t pos = A.rpos[t] & ~ROLE_BIT;
-		const bool rev = (A.rpos[t] & ROLE_BIT) != 0;
+		const uint32_t a = list[w], base = A.soff[a];
+		const TravSpan sp = trav_span(A.rpos, A.rlen, A.afirst[a]);
 		uint32_t m = 0;
 		uint64_t h = 0;
-		for (uint32_t cb = 0; cb < len; cb += 64) {
+		for (uint32_t cb = 0; cb < sp.len; cb += 64) {
 			const uint32_t i = cb + lane;
-			const bool open = i < len && !A.cov[base + i];
+			const bool open = i < sp.len && !A.cov[base + i];
 			const unsigned long long mask = __ballot(open);
 			if (open)
-				h += step_hash(m + (uint32_t)__popcll(mask & below), trav_step(A.steps, pos, len, rev, i));
+				h += step_hash(m + (uint32_t)__popcll(mask & below), sp.step(A.steps, i));
 			m += (uint32_t)__popcll(mask);
 		}
 		h = wave_sum(h);
@@ -227,9 +226,8 @@ struct SameSkeleton {
 	{
 		if (!cand[a])
 			return false; // (two alleles of a site that is no candidate: classes of their own)
-		const uint32_t ta = afirst[a], tb = afirst[b], la = rlen[ta], lb = rlen[tb], ba = soff[a], bb = soff[b];
-		const uint64_t pa = rpos[ta] & ~ROLE_BIT, pb = rpos[tb] & ~ROLE_BIT;
-		const bool ra = (rpos[ta] & ROLE_BIT) != 0, rb = (rpos[tb] & ROLE_BIT) != 0;
+		const TravSpan sa = trav_span(rpos, rlen, afirst[a]), sb = trav_span(rpos, rlen, afirst[b]);
+		const uint32_t la = sa.len, lb = sb.len, ba = soff[a], bb = soff[b];
 		for (uint32_t i = 0, j = 0;; i++, j++) {
 			while (i < la && cov[ba + i])
 				i++;
@@ -237,7 +235,7 @@ struct SameSkeleton {
 				j++;
 			if (i == la || j == lb)
 				return i == la && j == lb;
-			if (trav_step(steps, pa, la, ra, i) != trav_step(steps, pb, lb, rb, j))
+			if (sa.step(steps, i) != sb.step(steps, j))
 				return false;
 		}
 	}
@@ -362,16 +360,17 @@ __global__ __launch_bounds__(Q_TPB) void k_ns_parent(uint32_t nfl, const uint32_
 {
 	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
 	for (uint32_t j = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); j < nfl; j += waves) {
-		const uint32_t t = rlist[j], len = rlen[t], q = rq[t];
-		const uint64_t pos = rpos[t] & ~ROLE_BIT, end = pos + len - 1;
+		const uint32_t t = rlist[j], q = rq[t];
+		const TravSpan sp = trav_span(rpos, rlen, t);
+		const uint64_t pos = sp.first_pos(), end = sp.last_pos();
 		const uint32_t lo = first_at_least(ix.ipos, ix.ni, pos), hi = first_at_least(ix.ipos, ix.ni, end + 1);
 		for (uint32_t x = lo + lane; x < hi; x += 64) {
 			const uint64_t ie = ix.iend[x];
-			if (ix.iq[x] == q || ie > end || ie - ix.ipos[x] >= (uint64_t)len - 1)
+			if (ix.iq[x] == q || ie > end || ie - ix.ipos[x] >= (uint64_t)sp.len - 1)
 				continue;
 			const uint32_t jj = rec_of[ix.it[x]];
 			if (jj != NO_QUERY)
-				atomicMin(par + jj, ((unsigned long long)(len - 1) << 32) | j);
+				atomicMin(par + jj, ((unsigned long long)(sp.len - 1) << 32) | j);
 		}
 	}
 }
@@ -441,10 +440,11 @@ __global__ __launch_bounds__(Q_TPB) void k_ns_profile(uint32_t nfl, uint32_t pro
 	}
 }
 
-NestRecs nest_records(povu_hip_ctx *ctx, const TravDevice &d, const NestIndex &ix, const NestRecIn &in)
+NestRecs nest_records(povu_hip_ctx *ctx, const CallView &v, const NestIndex &ix, const povu_hip_call_profile_opts &limits)
 {
 	hipStream_t s = ctx->stream;
-	const uint32_t nfl = in.nfl;
+	const uint32_t nfl = v.nfl;
+	const TravView &d = v.trav;
 	const size_t F1 = (size_t)nfl + 1, R1 = (size_t)d.R + 1;
 	NestRecs o;
 	unsigned long long *par, *cnt;
@@ -466,13 +466,13 @@ NestRecs nest_records(povu_hip_ctx *ctx, const TravDevice &d, const NestIndex &i
 	HIP_CHECK(hipMemsetAsync(par, 0xFF, F1 * 8, s));
 	HIP_CHECK(hipMemsetAsync(rec_of, 0xFF, R1 * 4, s));
 	HIP_CHECK(hipMemsetAsync(cnt, 0, 32, s));
-	KLAUNCH(k_ns_rec_of, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, in.rlist, rec_of);
-	KLAUNCH(k_ns_parent, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, in.rlist, d.rq, d.rpos, d.rlen, ix, rec_of, par);
-	KLAUNCH(k_ns_level, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, in.rlist, d.rq, in.height, par, o.level, o.parent_q, cnt);
-	const bool filter = in.profile != POVU_HIP_PROFILE_RAW_GRAPH;
+	KLAUNCH(k_ns_rec_of, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, v.rlist, rec_of);
+	KLAUNCH(k_ns_parent, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, v.rlist, d.rq, d.rpos, d.rlen, ix, rec_of, par);
+	KLAUNCH(k_ns_level, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, v.rlist, d.rq, v.height, par, o.level, o.parent_q, cnt);
+	const bool filter = limits.profile != POVU_HIP_PROFILE_RAW_GRAPH;
 	if (filter) {
-		KLAUNCH(k_ns_profile, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, in.profile, in.max_level, in.max_ref_length, in.max_allele_length,
-			in.ref_len, in.max_len, par, o.level, keep, o.rescued, cnt);
+		KLAUNCH(k_ns_profile, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, limits.profile, limits.max_level, limits.max_ref_length,
+			limits.max_allele_length, v.ref_len, v.max_len, par, o.level, keep, o.rescued, cnt);
 		compact_flagged_u8(keep, nfl, o.kept, words, tmp, tmp_bytes, s);
 		HIP_CHECK(copy_async(&o.n_kept, words, 4, hipMemcpyDeviceToHost, s));
 	} else {

@@ -26,15 +26,9 @@ struct NestClasses {
 // `called`: [n] the called sites; force_tier2: every candidate allele through the wave kernels
 NestClasses nest_classes(povu_hip_ctx *ctx, const TravDevice &d, const uint8_t *called, uint32_t max_steps, bool force_tier2);
 
-// the records' nesting.  In: the flubble records before they are sorted (record j = traversal rlist[j], a reference
-// traversal of a kept site), the sites' PVST heights, the written lengths of every record's REF and of its longest allele.
-struct NestRecIn {
-	uint32_t nfl = 0;
-	const uint32_t *rlist = nullptr, *height = nullptr;
-	const uint64_t *ref_len = nullptr, *max_len = nullptr;
-	uint32_t profile = 0, max_level = 0; // POVU_HIP_PROFILE_*
-	uint64_t max_ref_length = 0, max_allele_length = 0;
-};
+// the records' nesting, from the call's view: the flubble records before they are sorted (record j = traversal rlist[j], a
+// reference traversal of a kept site), the sites' PVST heights, the written lengths of every record's REF and of its longest
+// allele; `limits`: the profile and its limits.
 // Out, per record j: level, the parent's site (NO_QUERY: none), rescued; `kept`: the n_kept records the profile keeps,
 // ascending (raw-graph: all)
 struct NestRecs {
@@ -43,6 +37,6 @@ struct NestRecs {
 	uint32_t n_kept = 0;
 	uint64_t n_enclosed = 0, n_popped = 0, n_rescued = 0;
 };
-NestRecs nest_records(povu_hip_ctx *ctx, const TravDevice &d, const NestIndex &ix, const NestRecIn &in);
+NestRecs nest_records(povu_hip_ctx *ctx, const CallView &v, const NestIndex &ix, const povu_hip_call_profile_opts &limits);
 
 } // namespace povu_hip

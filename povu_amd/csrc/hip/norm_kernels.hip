@@ -23,98 +23,53 @@ namespace povu_hip
 namespace
 {
 
-struct NormTab {
-	const uint32_t *rlist, *rq, *op, *aoff, *oa, *afirst, *rlen, *steps;
-	const uint8_t *orv, *rstate;
-	const uint64_t *rpos, *ilen, *xilen, *pos; // pos: the raw POS
-	const uint32_t *ref_of_path, *ref_path;
-	const uint64_t *ref_base, *roff, *path_off, *seq_off;
-	const char *seq;
-};
-
-// written allele i of record j (0: REF, the record's own traversal; else the i-th other allele of its site, by its first
-// traversal): where its steps are, whether its text begins with the anchor base, the length of its text
-struct NmAllele {
-	uint64_t p, alen;
-	uint32_t len, first, m; // steps, the anchor step in the reference's direction, inner steps
-	bool rev, o, anc;
-};
-__device__ __forceinline__ NmAllele nm_allele(const NormTab &T, uint32_t j, uint32_t i)
-{
-	const uint32_t t = T.rlist[j], q = T.rq[t], ra = T.oa[t];
-	uint32_t tt = t;
-	uint64_t il = T.xilen[j];
-	if (i) {
-		const uint32_t a = T.aoff[q] + (i - 1 < ra ? i - 1 : i);
-		tt = T.afirst[a];
-		il = T.ilen[a];
-	}
-	NmAllele s;
-	s.p = T.rpos[tt] & ~ROLE_BIT;
-	s.rev = (T.rpos[tt] & ROLE_BIT) != 0;
-	s.len = T.rlen[tt];
-	s.m = s.len - 2;
-	s.o = T.orv[t] != 0;
-	s.first = s.o ? trav_step(T.steps, s.p, s.len, s.rev, s.len - 1) ^ 1u : trav_step(T.steps, s.p, s.len, s.rev, 0);
-	const uint32_t v = s.first >> 1;
-	s.anc = (T.rstate[j] & RS_ANCHORED) && T.seq_off[v + 1] > T.seq_off[v];
-	s.alen = il + (s.anc ? 1 : 0);
-	return s;
-}
-__device__ __forceinline__ uint32_t nm_inner(const NormTab &T, const NmAllele &s, uint32_t k)
-{
-	return s.o ? trav_step(T.steps, s.p, s.len, s.rev, s.len - 2 - k) ^ 1u : trav_step(T.steps, s.p, s.len, s.rev, k + 1);
-}
-__device__ __forceinline__ uint64_t nm_seg_len(const NormTab &T, uint32_t x) { return T.seq_off[(x >> 1) + 1] - T.seq_off[x >> 1]; }
+__device__ __forceinline__ uint64_t nm_seg_len(const PathsView &P, uint32_t x) { return P.seq_off[(x >> 1) + 1] - P.seq_off[x >> 1]; }
 // base `within` of step x as the step spells it (0 for a byte that is no nucleotide code on a '<' step)
-__device__ __forceinline__ uint8_t nm_step_base(const NormTab &T, uint32_t x, uint64_t within)
+__device__ __forceinline__ uint8_t nm_step_base(const PathsView &P, uint32_t x, uint64_t within)
 {
-	const uint64_t b0 = T.seq_off[x >> 1], n = T.seq_off[(x >> 1) + 1] - b0;
-	const uint8_t c = (uint8_t)T.seq[(x & 1u) ? b0 + n - 1 - within : b0 + within];
+	const uint64_t b0 = P.seq_off[x >> 1], n = P.seq_off[(x >> 1) + 1] - b0;
+	const uint8_t c = (uint8_t)P.seq[(x & 1u) ? b0 + n - 1 - within : b0 + within];
 	return (x & 1u) ? comp(c) : c;
 }
 __device__ __forceinline__ uint8_t nm_upper(uint8_t c) { return c >= 'a' && c <= 'z' ? (uint8_t)(c - 32) : c; }
 
-// the bases at distances c0 .. c0 + 63 from the allele's last base, a lane each (0 where the allele has none).  `k` inner
-// steps are not yet left behind, those left behind hold `cum` bases; called with ascending c0, by the whole wave
-struct NmBack {
+// where a walk over an allele's inner steps stands: a step and a count of bases (what they mean: each walk's own)
+struct NmCursor {
 	uint32_t k;
 	uint64_t cum;
 };
-__device__ __forceinline__ uint8_t nm_back_chunk(const NormTab &T, const NmAllele &a, NmBack &cur, uint64_t c0, uint32_t lane)
+// the bases at distances c0 .. c0 + 63 from the last base of the allele's text of alen bases, a lane each (0 where the allele
+// has none).  `k` inner steps are not yet left behind, those left behind hold `cum` bases; called with ascending c0, by the whole wave
+__device__ __forceinline__ uint8_t nm_back_chunk(const PathsView &P, const WrittenAllele &a, uint64_t alen, NmCursor &cur, uint64_t c0, uint32_t lane)
 {
 	const uint64_t d = c0 + lane;
 	uint8_t c = 0;
 	while (cur.k > 0) {
-		const uint32_t x = nm_inner(T, a, cur.k - 1);
-		const uint64_t n = nm_seg_len(T, x);
+		const uint32_t x = a.inner_step(P.steps, cur.k - 1);
+		const uint64_t n = nm_seg_len(P, x);
 		if (d >= cur.cum && d < cur.cum + n)
-			c = nm_step_base(T, x, n - 1 - (d - cur.cum));
+			c = nm_step_base(P, x, n - 1 - (d - cur.cum));
 		if (cur.cum + n > c0 + 64)
 			break; // (the step reaches into the next chunk)
 		cur.cum += n;
 		cur.k--;
 	}
-	if (cur.k == 0 && a.anc && d + 1 == a.alen)
-		c = nm_step_base(T, a.first, nm_seg_len(T, a.first) - 1);
+	if (cur.k == 0 && a.anchor_base && d + 1 == alen)
+		c = nm_step_base(P, a.anchor, nm_seg_len(P, a.anchor) - 1);
 	return c;
 }
 // ... at indices x0 .. x0 + 63 from the allele's first base: `k` the next inner step, `cum` the index of its first base
-struct NmFwd {
-	uint32_t k;
-	uint64_t cum;
-};
-__device__ __forceinline__ uint8_t nm_fwd_chunk(const NormTab &T, const NmAllele &a, NmFwd &cur, uint64_t x0, uint32_t lane)
+__device__ __forceinline__ uint8_t nm_fwd_chunk(const PathsView &P, const WrittenAllele &a, NmCursor &cur, uint64_t x0, uint32_t lane)
 {
 	const uint64_t idx = x0 + lane;
 	uint8_t c = 0;
-	if (a.anc && idx == 0)
-		c = nm_step_base(T, a.first, nm_seg_len(T, a.first) - 1);
-	while (cur.k < a.m) {
-		const uint32_t x = nm_inner(T, a, cur.k);
-		const uint64_t n = nm_seg_len(T, x);
+	if (a.anchor_base && idx == 0)
+		c = nm_step_base(P, a.anchor, nm_seg_len(P, a.anchor) - 1);
+	while (cur.k < a.inner_steps()) {
+		const uint32_t x = a.inner_step(P.steps, cur.k);
+		const uint64_t n = nm_seg_len(P, x);
 		if (idx >= cur.cum && idx < cur.cum + n)
-			c = nm_step_base(T, x, idx - cur.cum);
+			c = nm_step_base(P, x, idx - cur.cum);
 		if (cur.cum + n > x0 + 64)
 			break;
 		cur.cum += n;
@@ -127,15 +82,15 @@ __device__ __forceinline__ uint8_t nm_fwd_chunk(const NormTab &T, const NmAllele
 struct NmRef {
 	uint64_t b, n, gs;
 };
-__device__ __forceinline__ NmRef nm_ref(const NormTab &T, uint32_t j)
+__device__ __forceinline__ NmRef nm_ref(const CallView &V, uint32_t j)
 {
-	const uint32_t r = T.ref_of_path[T.op[T.rlist[j]]];
-	return {T.ref_base[r], T.ref_base[r + 1] - T.ref_base[r], T.path_off[T.ref_path[r]]};
+	const uint32_t r = V.ref.ref_of_path[V.trav.op[V.rlist[j]]];
+	return {V.ref.ref_base[r], V.ref.ref_base[r + 1] - V.ref.ref_base[r], V.paths.path_off[V.ref.ref_path[r]]};
 }
 // base ci (0-based) of the reference path as the path spells it; *seg its segment.  ci is below the path's length
-__device__ __forceinline__ uint8_t nm_ctx_base(const NormTab &T, const NmRef &R, uint64_t ci, uint32_t *seg)
+__device__ __forceinline__ uint8_t nm_ctx_base(const PathsView &P, const uint64_t *__restrict__ roff, const NmRef &R, uint64_t ci, uint32_t *seg)
 {
-	const uint64_t *__restrict__ off = T.roff + R.b;
+	const uint64_t *__restrict__ off = roff + R.b;
 	const uint64_t target = off[0] + ci;
 	uint64_t lo = 0, hi = R.n - 1; // the first step that ends behind the base (steps of no base are passed over)
 	while (lo < hi) {
@@ -145,51 +100,54 @@ __device__ __forceinline__ uint8_t nm_ctx_base(const NormTab &T, const NmRef &R,
 		else
 			lo = mid + 1;
 	}
-	const uint32_t x = T.steps[R.gs + lo];
+	const uint32_t x = P.steps[R.gs + lo];
 	*seg = x >> 1;
-	return nm_step_base(T, x, target - off[lo]);
+	return nm_step_base(P, x, target - off[lo]);
 }
 
 // ALTs of every record (the tasks of k_nm_chop)
-__global__ void k_nm_tasks(uint32_t nfl, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ aoff,
-			   uint64_t *__restrict__ cnt)
+__global__ void k_nm_tasks(CallView V, uint64_t *__restrict__ cnt)
 {
+	const uint32_t nfl = V.nfl;
 	for (uint32_t j = blockIdx.x * Q_TPB + threadIdx.x; j <= nfl; j += gridDim.x * Q_TPB) {
-		const uint32_t q = j < nfl ? rq[rlist[j]] : 0;
-		cnt[j] = j < nfl ? aoff[q + 1] - aoff[q] - 1 : 0;
+		const uint32_t q = j < nfl ? V.trav.rq[V.rlist[j]] : 0;
+		cnt[j] = j < nfl ? V.aoff[q + 1] - V.aoff[q] - 1 : 0;
 	}
 }
 
 // one wave per (record, ALT): the common suffix of E_0 and E_i into rmin[record]; words[0] += bases compared
-__global__ __launch_bounds__(Q_TPB) void k_nm_chop(uint64_t ntask, NormTab T, const uint64_t *__restrict__ toff, uint32_t nfl,
+__global__ __launch_bounds__(Q_TPB) void k_nm_chop(uint64_t ntask, CallView V, const uint64_t *__restrict__ toff,
 						   unsigned long long *__restrict__ rmin, unsigned long long *__restrict__ words)
 {
-	const uint32_t lane = threadIdx.x & 63u;
+	const uint32_t lane = threadIdx.x & 63u, nfl = V.nfl;
+	const PathsView P = V.paths; // (what the walk reads, out of the view)
+	const uint64_t *__restrict__ roff = V.ref.roff;
 	const uint64_t waves = (uint64_t)gridDim.x * (Q_TPB / 64);
 	for (uint64_t task = (uint64_t)blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); task < ntask; task += waves) {
 		const uint32_t j = span_of(toff, nfl, task), i = (uint32_t)(task - toff[j]) + 1;
-		const NmAllele A = nm_allele(T, j, 0), B = nm_allele(T, j, i);
-		if (!A.alen || !B.alen)
+		const WrittenAllele A = allele_of_record(V, j, 0), B = allele_of_record(V, j, i);
+		const uint64_t la = A.text_len(), lb = B.text_len();
+		if (!la || !lb)
 			continue; // (an empty text: the record stays as it is)
-		const NmRef R = nm_ref(T, j);
-		const uint64_t P = T.pos[j], ta = P - 1 + A.alen, tb = P - 1 + B.alen;
+		const NmRef R = nm_ref(V, j);
+		const uint64_t pos = V.raw_pos[j], ta = pos - 1 + la, tb = pos - 1 + lb;
 		// behind `end` nothing is compared: alleles of one length read the same context base from there on, else the shorter
 		// string has ended (and that is a difference)
-		const uint64_t end = A.alen == B.alen ? A.alen : min(ta, tb) + 1;
-		NmBack ca{A.m, 0}, cb{B.m, 0};
+		const uint64_t end = la == lb ? la : min(ta, tb) + 1;
+		NmCursor ca{A.inner_steps(), 0}, cb{B.inner_steps(), 0};
 		uint64_t L = end;
 		uint32_t seg;
 		for (uint64_t c0 = 0; c0 < end; c0 += 64) {
 			const uint64_t d = c0 + lane;
 			uint8_t x = 0, y = 0;
-			if (c0 < A.alen)
-				x = nm_back_chunk(T, A, ca, c0, lane);
-			if (c0 < B.alen)
-				y = nm_back_chunk(T, B, cb, c0, lane);
-			if (d < end && d >= A.alen && d < ta)
-				x = nm_ctx_base(T, R, P - 2 - (d - A.alen), &seg);
-			if (d < end && d >= B.alen && d < tb)
-				y = nm_ctx_base(T, R, P - 2 - (d - B.alen), &seg);
+			if (c0 < la)
+				x = nm_back_chunk(P, A, la, ca, c0, lane);
+			if (c0 < lb)
+				y = nm_back_chunk(P, B, lb, cb, c0, lane);
+			if (d < end && d >= la && d < ta)
+				x = nm_ctx_base(P, roff, R, pos - 2 - (d - la), &seg);
+			if (d < end && d >= lb && d < tb)
+				y = nm_ctx_base(P, roff, R, pos - 2 - (d - lb), &seg);
 			const bool differs = d < end && (d >= ta || d >= tb || nm_upper(x) != nm_upper(y));
 			const unsigned long long mask = __ballot(differs);
 			if (mask) {
@@ -199,7 +157,7 @@ __global__ __launch_bounds__(Q_TPB) void k_nm_chop(uint64_t ntask, NormTab T, co
 		}
 		if (lane == 0) {
 			if (L == end) { // (alleles of one length that never differed: REF's text)
-				atomicAdd(words, (unsigned long long)A.alen);
+				atomicAdd(words, (unsigned long long)la);
 			} else {
 				atomicMin(rmin + j, (unsigned long long)L);
 				atomicAdd(words, (unsigned long long)L + 1);
@@ -209,32 +167,33 @@ __global__ __launch_bounds__(Q_TPB) void k_nm_chop(uint64_t ntask, NormTab T, co
 }
 
 // one wave per record: r, s, u and the new POS from the closed form; words[1] += changed, words[2] max shift, words[3] max chop
-__global__ __launch_bounds__(Q_TPB) void k_nm_record(uint32_t nfl, NormTab T, const unsigned long long *__restrict__ rmin, uint8_t *__restrict__ rstate,
+__global__ __launch_bounds__(Q_TPB) void k_nm_record(CallView V, const unsigned long long *__restrict__ rmin, uint8_t *__restrict__ rstate,
 						     uint64_t *__restrict__ pos, uint64_t *__restrict__ raw_pos, uint64_t *__restrict__ chop,
 						     uint64_t *__restrict__ shift, uint64_t *__restrict__ trim, unsigned long long *__restrict__ words)
 {
-	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
+	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64), nfl = V.nfl;
+	const PathsView P = V.paths;
 	for (uint32_t j = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); j < nfl; j += waves) {
-		const uint32_t t = T.rlist[j], q = T.rq[t], ra = T.oa[t], nal = T.aoff[q + 1] - T.aoff[q];
-		const NmAllele A = nm_allele(T, j, 0);
-		const uint64_t P = T.pos[j];
+		const uint32_t q = V.trav.rq[V.rlist[j]], nal = V.aoff[q + 1] - V.aoff[q];
+		const WrittenAllele A = allele_of_record(V, j, 0);
+		const uint64_t P0 = V.raw_pos[j];
 		uint64_t mn = ~0ull;
 		for (uint32_t i = lane; i < nal; i += 64)
-			mn = min(mn, (i ? T.ilen[T.aoff[q] + (i - 1 < ra ? i - 1 : i)] : T.xilen[j]) + (A.anc ? 1 : 0));
+			mn = min(mn, (i ? V.ilen[other_allele(V, j, i)] : V.xilen[j]) + (A.anchor_base ? 1 : 0));
 		for (int o = 32; o > 0; o >>= 1)
 			mn = min(mn, (uint64_t)__shfl_xor((unsigned long long)mn, o, 64));
 		const uint64_t rm = rmin[j];
 		uint64_t r = 0, s = 0, u = 0;
 		if (mn && rm != ~0ull) {
-			r = min(rm, P + mn - 2);
+			r = min(rm, P0 + mn - 2);
 			s = r + 1 > mn ? r + 1 - mn : 0;
 			if (s == 0 && mn - r > 1) {
 				u = mn - r - 1; // (every chopped allele keeps a base)
 				for (uint32_t i = 1; i < nal && u; i++) {
-					const NmAllele B = nm_allele(T, j, i);
-					NmFwd ca{0, A.anc ? 1u : 0u}, cb{0, B.anc ? 1u : 0u};
+					const WrittenAllele B = allele_of_record(V, j, i);
+					NmCursor ca{0, A.anchor_base ? 1u : 0u}, cb{0, B.anchor_base ? 1u : 0u};
 					for (uint64_t x0 = 0; x0 < u; x0 += 64) {
-						const uint8_t x = nm_fwd_chunk(T, A, ca, x0, lane), y = nm_fwd_chunk(T, B, cb, x0, lane);
+						const uint8_t x = nm_fwd_chunk(P, A, ca, x0, lane), y = nm_fwd_chunk(P, B, cb, x0, lane);
 						const unsigned long long mask = __ballot(x0 + lane < u && nm_upper(x) != nm_upper(y));
 						if (mask) {
 							u = x0 + (uint64_t)(__ffsll((long long)mask) - 1);
@@ -245,13 +204,13 @@ __global__ __launch_bounds__(Q_TPB) void k_nm_record(uint32_t nfl, NormTab T, co
 			}
 		}
 		if (lane == 0) {
-			raw_pos[j] = P;
+			raw_pos[j] = P0;
 			chop[j] = r;
 			shift[j] = s;
 			trim[j] = u;
 			if (r || u) {
 				rstate[j] |= RS_NORMALIZED;
-				pos[j] = P - s + u;
+				pos[j] = P0 - s + u;
 				atomicAdd(words + 1, 1ull);
 				atomicMax(words + 2, (unsigned long long)s);
 				atomicMax(words + 3, (unsigned long long)r);
@@ -278,67 +237,67 @@ __global__ void k_nm_rows(uint32_t nrec, const uint32_t *__restrict__ perm, cons
 	}
 }
 __global__ void k_nm_blocks(uint32_t nrec, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ dst, NormRows o, uint32_t nb0,
-			    const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq, const uint32_t *__restrict__ aoff,
-			    uint64_t *__restrict__ bcnt)
+			    CallView V, uint64_t *__restrict__ bcnt)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		if (!o.need[i])
 			continue;
-		const uint32_t j = perm[i], q = rq[rlist[j]], k = o.off[i];
+		const uint32_t j = perm[i], q = V.trav.rq[V.rlist[j]], k = o.off[i];
 		o.o_block[dst ? dst[i] : i] = nb0 + k;
 		o.list[k] = j;
-		bcnt[nb0 + k] = aoff[q + 1] - aoff[q];
+		bcnt[nb0 + k] = V.aoff[q + 1] - V.aoff[q];
 	}
 }
 
-// the record and the written allele of normalised spelled allele x (block_off: of the normalised blocks, absolute)
-__device__ __forceinline__ uint32_t nm_spelled(uint64_t x, uint32_t nn, const uint64_t *__restrict__ block_off, const uint32_t *__restrict__ list,
-					       uint32_t *i)
+// the record and the written allele of spelled allele g of the normalised family
+__device__ __forceinline__ uint32_t nm_spelled(uint64_t g, const BlockLayout::Family &F, const uint64_t *__restrict__ block_off,
+					       const uint32_t *__restrict__ list, uint32_t *i)
 {
-	const uint64_t g = block_off[0] + x;
-	const uint32_t b = span_of(block_off, nn, g);
-	*i = (uint32_t)(g - block_off[b]);
+	const uint32_t b = span_of(block_off + F.b0, F.nb, g);
+	*i = (uint32_t)(g - block_off[F.b0 + b]);
 	return list[b];
 }
-__global__ void k_nm_spell_len(uint64_t nsp, NormTab T, uint32_t nn, const uint64_t *__restrict__ block_off, const uint32_t *__restrict__ list,
+__global__ void k_nm_spell_len(BlockLayout::Family F, CallView V, const uint64_t *__restrict__ block_off, const uint32_t *__restrict__ list,
 			       const uint64_t *__restrict__ chop, const uint64_t *__restrict__ shift, const uint64_t *__restrict__ trim,
 			       uint64_t *__restrict__ slen, uint64_t *__restrict__ alen)
 {
-	for (uint64_t x = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; x < nsp; x += (uint64_t)gridDim.x * Q_TPB) {
+	for (uint64_t x = F.s0 + (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; x < F.s0 + F.ns; x += (uint64_t)gridDim.x * Q_TPB) {
 		uint32_t i;
-		const uint32_t j = nm_spelled(x, nn, block_off, list, &i);
-		slen[x] = shift[j] + nm_allele(T, j, i).alen - chop[j] - trim[j];
+		const uint32_t j = nm_spelled(x, F, block_off, list, &i);
+		slen[x] = shift[j] + allele_of_record(V, j, i).text_len() - chop[j] - trim[j];
 		alen[x] = 0;
 	}
 }
 // one wave per normalised allele
-__global__ __launch_bounds__(Q_TPB) void k_nm_emit(uint64_t nsp, NormTab T, uint32_t nn, const uint64_t *__restrict__ block_off,
+__global__ __launch_bounds__(Q_TPB) void k_nm_emit(BlockLayout::Family F, CallView V, const uint64_t *__restrict__ block_off,
 						   const uint32_t *__restrict__ list, const uint64_t *__restrict__ chop,
 						   const uint64_t *__restrict__ shift, const uint64_t *__restrict__ trim,
 						   const uint64_t *__restrict__ s_off, char *__restrict__ o_seq, unsigned long long *__restrict__ bad)
 {
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint64_t waves = (uint64_t)gridDim.x * (Q_TPB / 64);
-	for (uint64_t x = (uint64_t)blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); x < nsp; x += waves) {
+	const PathsView P = V.paths;
+	const uint64_t *__restrict__ roff = V.ref.roff;
+	for (uint64_t x = F.s0 + (uint64_t)blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); x < F.s0 + F.ns; x += waves) {
 		uint32_t i;
-		const uint32_t j = nm_spelled(x, nn, block_off, list, &i);
-		const NmAllele A = nm_allele(T, j, i);
-		const NmRef R = nm_ref(T, j);
-		const uint64_t P = T.pos[j], r = chop[j], s = shift[j], u = trim[j], w = s_off[x];
+		const uint32_t j = nm_spelled(x, F, block_off, list, &i);
+		const WrittenAllele A = allele_of_record(V, j, i);
+		const NmRef R = nm_ref(V, j);
+		const uint64_t pos = V.raw_pos[j], la = A.text_len(), r = chop[j], s = shift[j], u = trim[j], w = s_off[x];
 		// (u > 0 only where s == 0: the context bases are never trimmed; an allele shorter than the chop ends inside them)
-		const uint64_t nctx = A.alen < r ? s + A.alen - r : s;
+		const uint64_t nctx = la < r ? s + la - r : s;
 		for (uint64_t z = lane; z < nctx; z += 64) {
 			uint32_t seg;
-			const uint8_t c = nm_ctx_base(T, R, P - 1 - s + z, &seg);
+			const uint8_t c = nm_ctx_base(P, roff, R, pos - 1 - s + z, &seg);
 			if (!comp(c))
 				atomicMin(bad, (unsigned long long)seg);
 			o_seq[w + z] = (char)c;
 		}
-		if (A.alen > r) {
-			const uint64_t cut = A.alen - r;
-			NmFwd cur{0, A.anc ? 1u : 0u};
+		if (la > r) {
+			const uint64_t cut = la - r;
+			NmCursor cur{0, A.anchor_base ? 1u : 0u};
 			for (uint64_t x0 = 0; x0 < cut; x0 += 64) {
-				const uint8_t c = nm_fwd_chunk(T, A, cur, x0, lane);
+				const uint8_t c = nm_fwd_chunk(P, A, cur, x0, lane);
 				const uint64_t idx = x0 + lane;
 				if (idx < cut && idx >= u)
 					o_seq[w + s + idx - u] = (char)c;
@@ -347,18 +306,12 @@ __global__ __launch_bounds__(Q_TPB) void k_nm_emit(uint64_t nsp, NormTab T, uint
 	}
 }
 
-NormTab tab_of(povu_hip_ctx *ctx, const NormIn &in, const uint64_t *raw_pos)
-{
-	return NormTab{in.rlist, in.rq,	 in.op,	   in.aoff, in.oa,	    in.afirst,	 in.rlen,     ctx->path_steps, in.orv,	     in.rstate, in.rpos,
-		       in.ilen,	 in.xilen, raw_pos, in.ref_of_path, in.ref_path, in.ref_base, in.roff,	       ctx->path_off, ctx->seq_off, ctx->seq};
-}
-
 } // namespace
 
-NormRecs norm_records(povu_hip_ctx *ctx, const NormIn &in)
+NormRecs norm_records(povu_hip_ctx *ctx, const CallView &v, uint8_t *rstate, uint64_t *pos)
 {
 	hipStream_t s = ctx->stream;
-	const uint32_t nfl = in.nfl;
+	const uint32_t nfl = v.nfl;
 	NormRecs n;
 	uint64_t *cnt, *toff, *s64;
 	unsigned long long *rmin, *words;
@@ -369,13 +322,12 @@ NormRecs norm_records(povu_hip_ctx *ctx, const NormIn &in)
 	});
 	HIP_CHECK(hipMemsetAsync(rmin, 0xFF, ((size_t)nfl + 1) * 8, s));
 	HIP_CHECK(hipMemsetAsync(words, 0, 32, s));
-	KLAUNCH(k_nm_tasks, dim3(stride_blocks((size_t)nfl + 1)), dim3(Q_TPB), 0, s, nfl, in.rlist, in.rq, in.aoff, cnt);
+	KLAUNCH(k_nm_tasks, dim3(stride_blocks((size_t)nfl + 1)), dim3(Q_TPB), 0, s, v, cnt);
 	scan_exclusive_u64(cnt, toff, (size_t)nfl + 1, s64, s);
 	const uint64_t ntask = read_back(toff + nfl, s);
-	const NormTab T = tab_of(ctx, in, in.pos);
 	if (ntask)
-		KLAUNCH(k_nm_chop, dim3(wave_blocks(ntask)), dim3(Q_TPB), 0, s, ntask, T, toff, nfl, rmin, words);
-	KLAUNCH(k_nm_record, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, T, rmin, in.rstate, in.pos, n.raw_pos, n.chop, n.shift, n.trim, words);
+		KLAUNCH(k_nm_chop, dim3(wave_blocks(ntask)), dim3(Q_TPB), 0, s, ntask, v, toff, rmin, words);
+	KLAUNCH(k_nm_record, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, v, rmin, rstate, pos, n.raw_pos, n.chop, n.shift, n.trim, words);
 	unsigned long long h[4] = {0, 0, 0, 0};
 	HIP_CHECK(copy_async(h, words, 32, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
@@ -384,34 +336,32 @@ NormRecs norm_records(povu_hip_ctx *ctx, const NormIn &in)
 	return n;
 }
 
-void norm_row_fields(povu_hip_ctx *ctx, const NormIn &in, const NormRecs &n, uint32_t nrec, const uint32_t *perm, const uint32_t *dst,
-		     const NormRows &o)
+void norm_row_fields(povu_hip_ctx *ctx, const CallView &v, const NormRecs &n, uint32_t nrec, const uint32_t *perm, const uint32_t *dst, const NormRows &o)
 {
-	KLAUNCH(k_nm_rows, dim3(stride_blocks((size_t)nrec + 1)), dim3(Q_TPB), 0, ctx->stream, nrec, perm, dst, in.rstate, n.raw_pos, n.chop, n.shift, n.trim,
-		o);
+	KLAUNCH(k_nm_rows, dim3(stride_blocks((size_t)nrec + 1)), dim3(Q_TPB), 0, ctx->stream, nrec, perm, dst, v.rstate, n.raw_pos, n.chop, n.shift, n.trim, o);
 }
 
-void norm_blocks(povu_hip_ctx *ctx, const NormIn &in, uint32_t nrec, const uint32_t *perm, const uint32_t *dst, const NormRows &o, uint32_t nb0,
+void norm_blocks(povu_hip_ctx *ctx, const CallView &v, uint32_t nrec, const uint32_t *perm, const uint32_t *dst, const NormRows &o, uint32_t first_block,
 		 uint64_t *bcnt)
 {
 	if (nrec)
-		KLAUNCH(k_nm_blocks, dim3(stride_blocks(nrec)), dim3(Q_TPB), 0, ctx->stream, nrec, perm, dst, o, nb0, in.rlist, in.rq, in.aoff, bcnt);
+		KLAUNCH(k_nm_blocks, dim3(stride_blocks(nrec)), dim3(Q_TPB), 0, ctx->stream, nrec, perm, dst, o, first_block, v, bcnt);
 }
 
-void norm_spell_len(povu_hip_ctx *ctx, const NormIn &in, const NormRecs &n, const NormRows &o, uint32_t nn, const uint64_t *block_off, uint64_t nsp,
+void norm_spell_len(povu_hip_ctx *ctx, const CallView &v, const NormRecs &n, const NormRows &o, const BlockLayout &L, const uint64_t *block_off,
 		    uint64_t *slen, uint64_t *alen)
 {
-	if (nsp)
-		KLAUNCH(k_nm_spell_len, dim3(stride_blocks(nsp)), dim3(Q_TPB), 0, ctx->stream, nsp, tab_of(ctx, in, n.raw_pos), nn, block_off, o.list, n.chop,
-			n.shift, n.trim, slen, alen);
+	const BlockLayout::Family F = L.normalised();
+	if (F.ns)
+		KLAUNCH(k_nm_spell_len, dim3(stride_blocks(F.ns)), dim3(Q_TPB), 0, ctx->stream, F, v, block_off, o.list, n.chop, n.shift, n.trim, slen, alen);
 }
 
-void norm_emit(povu_hip_ctx *ctx, const NormIn &in, const NormRecs &n, const NormRows &o, uint32_t nn, const uint64_t *block_off, uint64_t nsp,
+void norm_emit(povu_hip_ctx *ctx, const CallView &v, const NormRecs &n, const NormRows &o, const BlockLayout &L, const uint64_t *block_off,
 	       const uint64_t *s_off, char *o_seq, unsigned long long *bad)
 {
-	if (nsp)
-		KLAUNCH(k_nm_emit, dim3(wave_blocks(nsp)), dim3(Q_TPB), 0, ctx->stream, nsp, tab_of(ctx, in, n.raw_pos), nn, block_off, o.list, n.chop, n.shift,
-			n.trim, s_off, o_seq, bad);
+	const BlockLayout::Family F = L.normalised();
+	if (F.ns)
+		KLAUNCH(k_nm_emit, dim3(wave_blocks(F.ns)), dim3(Q_TPB), 0, ctx->stream, F, v, block_off, o.list, n.chop, n.shift, n.trim, s_off, o_seq, bad);
 }
 
 } // namespace povu_hip

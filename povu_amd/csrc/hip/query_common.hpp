@@ -28,6 +28,33 @@ __device__ __forceinline__ uint32_t trav_step(const uint32_t *__restrict__ steps
 {
 	return rev ? steps[pos + len - 1 - k] ^ 1u : steps[pos + k];
 }
+// a traversal as rpos / rlen keep it, unpacked: the path words [p, p + len), reverse when rpos carries ROLE_BIT
+struct TravSpan {
+	uint64_t p;
+	uint32_t len;
+	bool rev;
+	__device__ __forceinline__ uint32_t step(const uint32_t *__restrict__ steps, uint32_t k) const { return trav_step(steps, p, len, rev, k); }
+	__device__ __forceinline__ uint64_t first_pos() const { return p; }
+	__device__ __forceinline__ uint64_t last_pos() const { return p + len - 1; }
+};
+__device__ __forceinline__ TravSpan trav_span(uint64_t packed, uint32_t len) { return {packed & ~ROLE_BIT, len, (packed & ROLE_BIT) != 0}; }
+__device__ __forceinline__ TravSpan trav_span(const uint64_t *__restrict__ rpos, const uint32_t *__restrict__ rlen, uint32_t t) { return trav_span(rpos[t], rlen[t]); }
+// the position alone, for those that need no more
+__device__ __forceinline__ uint64_t trav_first_pos(const uint64_t *__restrict__ rpos, uint32_t t) { return trav_span(rpos[t], 0).p; }
+
+// what the kernels read of the resident paths, segments and sequences (paths_view: from the context)
+struct PathsView {
+	uint32_t n_paths;
+	const uint64_t *path_off; // [n_paths + 1] first path word of every path, the paths concatenated
+	const uint32_t *steps;	  // the path words
+	const uint64_t *seq_off;  // [V + 1]
+	const char *seq;
+	const uint32_t *vid; // [V] segment ids, ascending
+};
+static inline PathsView paths_view(const povu_hip_ctx *ctx)
+{
+	return PathsView{ctx->n_paths, ctx->path_off, ctx->path_steps, ctx->seq_off, ctx->seq, ctx->g.vid};
+}
 
 // the span x lies in: the last k with off[k] <= x, off ascending over [0, n) (the path of a global step, the reference of a
 // reference step, the block of a spelled allele)

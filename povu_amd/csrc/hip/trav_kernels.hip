@@ -163,8 +163,9 @@ __device__ __forceinline__ TaskView task_view(const ScanArgs &A, uint32_t q, uin
 {
 	TaskView t;
 	t.q = q;
-	t.rev = (tp & ROLE_BIT) != 0;
-	t.pos = tp & ~ROLE_BIT;
+	const TravSpan sp = trav_span(tp, 0);
+	t.rev = sp.rev;
+	t.pos = sp.p;
 	const uint32_t ys = A.ys[q], yz = A.yz[q];
 	t.a = ys >> 1;
 	t.z = yz >> 1;
@@ -315,11 +316,9 @@ __global__ void k_tr_query_off(uint32_t n, uint32_t R, const uint32_t *__restric
 
 __device__ __forceinline__ bool same_sequence(const uint32_t *__restrict__ steps, uint64_t pa, uint64_t pb, uint32_t len)
 {
-	const bool ra = (pa & ROLE_BIT) != 0, rb = (pb & ROLE_BIT) != 0;
-	pa &= ~ROLE_BIT;
-	pb &= ~ROLE_BIT;
+	const TravSpan a = trav_span(pa, len), b = trav_span(pb, len);
 	for (uint32_t i = 0; i < len; i++)
-		if (trav_step(steps, pa, len, ra, i) != trav_step(steps, pb, len, rb, i))
+		if (a.step(steps, i) != b.step(steps, i))
 			return false;
 	return true;
 }
@@ -355,12 +354,12 @@ __global__ void k_tr_out(uint32_t R, const uint64_t *__restrict__ path_off, uint
 			 uint8_t *__restrict__ o_rev)
 {
 	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < R; t += gridDim.x * Q_TPB) {
-		const uint64_t pos = rpos[t] & ~ROLE_BIT;
-		const uint32_t p = span_of(path_off, n_paths, pos);
+		const TravSpan sp = trav_span(rpos, rlen, t);
+		const uint32_t p = span_of(path_off, n_paths, sp.p);
 		o_path[t] = p;
-		o_first[t] = (uint32_t)(pos - path_off[p]);
-		o_last[t] = (uint32_t)(pos - path_off[p]) + rlen[t] - 1;
-		o_rev[t] = (rpos[t] & ROLE_BIT) ? 1 : 0;
+		o_first[t] = (uint32_t)(sp.first_pos() - path_off[p]);
+		o_last[t] = (uint32_t)(sp.last_pos() - path_off[p]);
+		o_rev[t] = sp.rev ? 1 : 0;
 		o_allele[t] = rallele[t] - aidx[toff[rq[t]]];
 	}
 }
@@ -381,11 +380,10 @@ __global__ __launch_bounds__(Q_TPB) void k_tr_allele_steps(uint32_t n_al, const 
 {
 	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
 	for (uint32_t a = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); a < n_al; a += waves) {
-		const uint32_t t = afirst[a], len = rlen[t], at = soff[a];
-		const uint64_t p = rpos[t];
-		const bool rev = (p & ROLE_BIT) != 0;
-		for (uint32_t i = lane; i < len; i += 64) {
-			const uint32_t x = trav_step(steps, p & ~ROLE_BIT, len, rev, i);
+		const uint32_t at = soff[a];
+		const TravSpan sp = trav_span(rpos, rlen, afirst[a]);
+		for (uint32_t i = lane; i < sp.len; i += 64) {
+			const uint32_t x = sp.step(steps, i);
 			o_id[at + i] = vid[x >> 1];
 			o_or[at + i] = (uint8_t)(x & 1u);
 		}

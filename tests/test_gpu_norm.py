@@ -151,7 +151,8 @@ def _check(d, setup, prefixes, tflags=0):
     line = N.record_line if nested else V.record_line
     if tflags & H.T_INVERSIONS:
         raw = I.merge(raw, I.records(names, steps, sq, prefixes)[0])
-        line = I.record_line
+        flubble_line = line  # (inversions_ref writes a flubble record as vcf_ref does: a nested one keeps nested_ref's line)
+        line = lambda r: I.record_line(r) if r["vartype"] == "SUBR" else flubble_line(r)  # noqa: E731
     want, counters = NR.normalise(raw, steps, sq)
     c = d.call(f, prefixes, flags=tflags, profile=NR.PROFILE)
     assert c.nested == nested
@@ -295,6 +296,34 @@ def test_inversion_records_pass_unchanged(hip):
     subr = lambda x: [ln for ln in x.vcf_text(date=DATE).splitlines() if "VARTYPE=SUBR" in ln]  # noqa: E731
     assert c.n_inv_records > 0 and subr(c) == subr(raw) and counters["n_normalized"] > 0
     assert all(int(c.norm_block[i]) == NIL and c.raw_pos[i] == c.pos[i] for i in range(c.n_records) if c.flags[i] & H.CALL_SUBR)
+
+
+def test_every_family_of_blocks_in_one_call(hip):
+    # the spacer input above at 6 units, one more haplotype that walks units 2 .. 4 of haplotype 0 backwards (the inversion
+    # records), and a second reference: a reference that is not the first path of its class gets its REF spelled on its own.
+    # On the restatement alone (units 6, seed 1): 35 records, of them 5 SUBR, 4 with a REF of their own, 20 normalised, 10 unchanged
+    units, depth = 6, 1
+    g = W.skip_nested(units, depth, seed=1)
+    base = W.skip_haplotypes(units, depth, 8, seed=1)
+    size = len(W._skip_template(depth, 2)[0])
+    st = base.steps(0)
+    a = next(k for k, (i, _) in enumerate(st) if i > 2 * size)
+    b = next(k for k, (i, _) in enumerate(st) if i > 5 * size)
+    back = st[:a] + [(i, 1 - r) for i, r in reversed(st[a:b])] + st[b:]
+    pieces = [base.steps(k) for k in range(len(base))] + [back]
+    p = W.pansn(W._paths(base.names + ["back"], [([i for i, _ in s], [r for _, r in s]) for s in pieces]), samples=5)
+    _, snp, _, _, _ = W._skip_template(depth, 2)
+    seqs = ["A" if s[0] < 0 else "CG"[s[1]] for s in snp] * units
+    setup = _setup(hip, g, seqs, p)
+    flags = H.T_NESTED | H.T_INVERSIONS
+    c, want, counters = _check(hip, setup, ["sample0#1", "sample1#2"], tflags=flags)
+    flubble = [r for r in want if r["vartype"] != "SUBR"]
+    assert len(flubble) < len(want)                         # an inversion block
+    assert any(not r["ref_is_rep"] for r in flubble)        # an extra block
+    assert any(r["normalized"] for r in flubble)            # a normalised block
+    assert any(not r["normalized"] for r in flubble)        # a record that only has its class block
+    c2, _, _ = _check(hip, setup, ["sample0#1", "sample1#2"], tflags=flags | H.T_FORCE_TIER2)
+    assert c2.vcf_text(date=DATE) == c.vcf_text(date=DATE)
 
 
 # ---- unchanged

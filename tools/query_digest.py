@@ -1,6 +1,7 @@
 """A sha256 of everything the query calls return, to compare two builds of the library on the same inputs: every array and
-counter of Walks, of Traversals and of Calls (with and without T_INVERSIONS), and the VCF text with a fixed date.  The inputs
-are those of tools/time_walks.py, time_traversals.py, time_call.py and time_inversions.py, then small ones with every query
+counter of Walks, of Traversals and of Calls (with and without T_INVERSIONS, with T_NESTED, under the profiles
+top-level-only, popped and left-normalized, and left-normalized with T_NESTED | T_INVERSIONS), and the VCF text with a fixed
+date.  The inputs are those of tools/time_walks.py, time_traversals.py and time_calls.py, then small ones with every query
 forced through the second tier, and the traversals once more in a child process with POVU_HIP_TRAV_HASH_BITS=4 (hash
 collisions: the exact regrouping).  One line per digest, "<input> <call> <field> <sha256 or number>"; the device times are
 left out, so two builds that compute the same print the same.
@@ -47,6 +48,20 @@ def show(tag, call, r):
 def show_calls(tag, d, f, H, refs, extra=0):
     for name, flags in (("call", extra), ("call+inv", extra | H.T_INVERSIONS)):
         c = d.call(f, refs, flags=flags)
+        show(tag, name, c)
+        print(tag, name, "vcf", hashlib.sha256(c.vcf_text(date="20000101").encode()).hexdigest(), flush=True)
+        del c
+
+
+def show_profiles(tag, d, f, H, refs, extra=0):
+    """The nested call, the call under every profile, and the left-normalised call with the nested and the inversion records."""
+    popped = dict(profile="popped", max_level=0, max_ref_length=64, max_allele_length=64)
+    for name, kw in (("call+nested", dict(flags=extra | H.T_NESTED)),
+                     ("call/top-level-only", dict(flags=extra, profile="top-level-only")),
+                     ("call/popped", dict(flags=extra, **popped)),
+                     ("call/left-normalized", dict(flags=extra, profile="left-normalized")),
+                     ("call+nested+inv/left-normalized", dict(flags=extra | H.T_NESTED | H.T_INVERSIONS, profile="left-normalized"))):
+        c = d.call(f, refs, **kw)
         show(tag, name, c)
         print(tag, name, "vcf", hashlib.sha256(c.vcf_text(date="20000101").encode()).hexdigest(), flush=True)
         del c
@@ -110,7 +125,7 @@ def main():
             show(tag, "traversals+tier2", d.traversals(f, flags=H.T_FORCE_TIER2))
         del f, g
 
-    # ---- calls (tools/time_call.py)
+    # ---- calls (tools/time_calls.py: chain, and an HPRC-shaped graph)
     k = max(100, int(1e6 * s))
     for tag, g, paths in (("call-chain", W.chain_of_bubbles(k), lambda g: W.chain_haplotypes(k, 32, seed=1)),
                           ("call-hprc", W.hprc_shaped([max(1000, int(6e5 * s)), max(1000, int(3e5 * s))], seed=3, tiny=5),
@@ -124,7 +139,7 @@ def main():
             show_calls(tag + "+tier2", d, f, H, ["sample0#"], extra=H.T_FORCE_TIER2)
         del f, g
 
-    # ---- inversions (tools/time_inversions.py, its defaults)
+    # ---- inversions (tools/time_calls.py: inverted, and the same with every haplotype forward)
     k = max(100, int(1e8 * 0.01 * s / 3))
     g = W.chain_of_bubbles(k)
     base = W.chain_haplotypes(k, 32, seed=1, reverse_every=0)
@@ -138,6 +153,27 @@ def main():
         d.upload_paths(p)
         show_calls(tag, d, f, H, ["sample0#"])
     show_calls("inv-inverted+tier2", d, f, H, ["sample0#"], extra=H.T_FORCE_TIER2)
+    del f, g
+
+    # ---- nested calls and profiles (tools/time_calls.py: skip and tandem at a tenth, the tandem haplotypes with intervals walked
+    # backwards so that the last call has every family of blocks), then small ones through the second tier
+    size = len(W._skip_template(2, 2)[0])
+    for tag, units, haps, extra in (("skip", max(4, int(1e5 * s / size)), 64, 0), ("skip-small+tier2", 40, 16, H.T_FORCE_TIER2)):
+        g = W.skip_nested(units, 2)
+        d.upload(g)
+        f = d.decompose(flags=H.F_NO_STAGE_TIMES)
+        d.upload_paths(W.skip_haplotypes(units, 2, haps, seed=1))
+        d.upload_sequences(W.random_sequences(g, 5, max_len=16))
+        show_profiles(tag, d, f, H, ["hap0#", "hap3#"], extra=extra)
+        del f, g
+    for tag, units, extra in (("tandem", max(20, int(1e4 * s)), 0), ("tandem-small+tier2", 200, H.T_FORCE_TIER2)):
+        g, seqs = W.tandem_indels(units, 1)
+        d.upload(g)
+        f = d.decompose(flags=H.F_NO_STAGE_TIMES)
+        d.upload_paths(W.inverted_haplotypes(W.tandem_haplotypes(units, 1, 8), max(4, units // 10), 3, 9, seed=4, keep=(0,)))
+        d.upload_sequences(seqs)
+        show_profiles(tag, d, f, H, ["hap0#", "hap3#"], extra=extra)
+        del f, g
     d.close()
 
     # ---- hash collisions: a process of its own (the hook is read from the environment)

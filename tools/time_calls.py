@@ -1,0 +1,140 @@
+"""Device time of povu_hip_call (HipDecomposer.call) in its modes on one of four inputs, each at the size it has always been
+timed at:
+
+    chain     the chain of bubbles with 32 closed-form haplotypes, a quarter written reversed (workloads.chain_haplotypes),
+              random sequences of up to 300 bases; 1e6 bubbles
+    inverted  the chain with every haplotype written forward, four of them copies of the reference, and
+              workloads.inverted_haplotypes applied (1000 intervals of up to 2000 steps walked backwards); 333333 bubbles
+    skip      workloads.skip_nested / skip_haplotypes at depth 2 with 64 haplotypes (INTEGRATION.md "Nested calls"); 1e6 segments
+    tandem    workloads.tandem_indels / tandem_haplotypes with 8 haplotypes (an indel of one period at the right end of every
+              tandem repeat, INTEGRATION.md "Left-normalised calls"); 100000 units
+
+and in any of the modes plain, inversions (T_INVERSIONS), nested (T_NESTED), popped (profile `popped`, max_level 0, both length
+limits --max-length) and normalized (profile `left-normalized`); without --modes those the input was made for.  One JSON line
+per mode and run: HIP-event time of the call (query upload to the last byte on the host), records, spelled bytes, the
+counters of the mode; then per mode a line with the median of the runs behind the warm-up runs.
+
+Every mode runs in a child process of its own under its own time limit, one after the other; after a child that fails or
+runs out of time nothing more is started.  --package-root times the library of another checkout on this tree's inputs (only
+keyword arguments of HipDecomposer.call that every build with the mode has are used).
+
+    python tools/time_calls.py --workload chain|inverted|skip|tandem [--modes plain,nested] [--size 1.0] [--warmup 2] [--runs 7]
+                               [--max-length 64] [--limit 300] [--package-root <another checkout>]
+"""
+import argparse
+import importlib.util
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+MODES = ("plain", "inversions", "nested", "popped", "normalized")
+DEFAULT_MODES = dict(chain=("plain",), inverted=("plain", "inversions"), skip=("plain", "nested", "popped"), tandem=("plain", "normalized"))
+
+
+def _load(package_root):
+    """(HipDecomposer, hip module, this tree's workloads): the library of another checkout with --package-root, the inputs
+    always this tree's."""
+    spec = importlib.util.spec_from_file_location("time_calls_workloads", os.path.join(ROOT, "povu_amd", "workloads.py"))
+    w = importlib.util.module_from_spec(spec)
+    sys.modules[spec.name] = w
+    spec.loader.exec_module(w)
+    sys.path.insert(0, os.path.abspath(package_root) if package_root else ROOT)
+    from povu_amd import HipDecomposer
+    from povu_amd import hip
+    return HipDecomposer, hip, w
+
+
+def workload(W, name, size):
+    """(graph, paths, sequences, reference prefix)"""
+    if name == "chain":
+        k = max(100, int(1e6 * size))
+        g = W.chain_of_bubbles(k)
+        return g, W.pansn(W.chain_haplotypes(k, 32, seed=1), samples=32), W.random_sequences(g, 5, max_len=300), "sample0#"
+    if name == "inverted":
+        k = max(100, int(1e8 * 0.01 * size / 3))
+        g = W.chain_of_bubbles(k)
+        base = W.chain_haplotypes(k, 32, seed=1, reverse_every=0)
+        cut = lambda j: (base.ids[int(base.off[j]):int(base.off[j + 1])], base.rev[int(base.off[j]):int(base.off[j + 1])])  # noqa: E731
+        copied = W._paths(base.names, [cut(0 if 1 <= j <= 4 else j) for j in range(32)])
+        p = W.pansn(W.inverted_haplotypes(copied, 1000, 2, 2000, 2, keep=(0,)), samples=32)
+        return g, p, W.random_sequences(g, 1, max_len=30), "sample0#"
+    if name == "skip":
+        units = max(2, int(1e6 * size / len(W._skip_template(2, 2)[0])) + 1)
+        g = W.skip_nested(units, 2)
+        return g, W.skip_haplotypes(units, 2, 64, seed=1), W.random_sequences(g, 5, max_len=16), "hap0#"
+    units = max(2, int(100000 * size))
+    g, seqs = W.tandem_indels(units, 1)
+    return g, W.tandem_haplotypes(units, 1, 8), seqs, "hap0#"
+
+
+def child(a):
+    HipDecomposer, H, W = _load(a.package_root)
+    t0 = time.perf_counter()
+    g, p, seqs, ref = workload(W, a.workload, a.size)
+    gen_s = time.perf_counter() - t0
+    d = HipDecomposer(0)
+    d.upload(g)
+    f = d.decompose(flags=H.F_NO_STAGE_TIMES)
+    d.upload_paths(p)
+    d.upload_sequences(seqs)
+    kw = dict(plain=lambda: {}, inversions=lambda: dict(flags=H.T_INVERSIONS), nested=lambda: dict(flags=H.T_NESTED),
+              popped=lambda: dict(profile="popped", max_level=0, max_ref_length=a.max_length, max_allele_length=a.max_length),
+              normalized=lambda: dict(profile="left-normalized"))[a.child]()
+    counters = ("n_inv_records", "n_inv_tier2", "n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "n_normalized", "max_shift",
+                "n_norm_compared")
+    for run in range(a.warmup + a.runs):
+        t0 = time.perf_counter()
+        c = d.call(f, [ref], **kw)
+        wall = (time.perf_counter() - t0) * 1e3
+        print(json.dumps(dict(
+            workload=a.workload, mode=a.child, run=run, warmup=run < a.warmup, segments=g.n_vtx, links=g.n_links, paths=len(p),
+            path_steps=p.n_steps, records=c.n_records, slots=c.n_slots, spelled_bytes=c.n_seq_bytes, at_bytes=c.n_at_bytes,
+            device_ms=round(c.device_ms, 3), wall_ms=round(wall, 2), generate_s=round(gen_s, 1),
+            **{k: int(getattr(c, k, 0)) for k in counters})), flush=True)
+        del c
+    d.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", choices=sorted(DEFAULT_MODES), required=True)
+    ap.add_argument("--modes", help="comma-separated, of " + ",".join(MODES))
+    ap.add_argument("--size", type=float, default=1.0, help="of the workload's own size")
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--max-length", type=int, default=64, help="popped: max_ref_length and max_allele_length")
+    ap.add_argument("--limit", type=int, default=300, help="seconds a mode may take")
+    ap.add_argument("--package-root", help="import povu_amd from this checkout")
+    ap.add_argument("--child", choices=MODES, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        return child(a)
+    modes = tuple(a.modes.split(",")) if a.modes else DEFAULT_MODES[a.workload]
+    for mode in modes:
+        if mode not in MODES:
+            ap.error("unknown mode " + mode)
+    for mode in modes:
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", mode, "--workload", a.workload,
+               "--size", str(a.size), "--warmup", str(a.warmup), "--runs", str(a.runs), "--max-length", str(a.max_length)]
+        cmd += ["--package-root", a.package_root] if a.package_root else []
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        sys.stdout.write(r.stdout)
+        sys.stdout.flush()
+        if r.returncode != 0:
+            sys.stderr.write(r.stderr[-4000:])
+            print(json.dumps(dict(workload=a.workload, mode=mode, failed=r.returncode)), flush=True)
+            return 1  # (nothing more is started on the GPU)
+        rows = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+        timed = [x["device_ms"] for x in rows if not x["warmup"]]
+        print(json.dumps(dict(workload=a.workload, mode=mode, median_device_ms=round(statistics.median(timed), 3), min_device_ms=min(timed),
+                              max_device_ms=max(timed), runs=len(timed), records=rows[-1]["records"])), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
