@@ -550,7 +550,7 @@ static constexpr int RANK_MAX_LEVELS = 12;
 // the one before it again -- < 3.2 M in all
 static size_t rank_pool_words(size_t n, size_t nh) { return n / 2 + 4 * nh + 64; }
 
-// Where a level-0 rank is read (k_t0_parents, k_bridges, k_tree_emit): R = the inclusive suffix sums of the level-1
+// Where a level-0 rank is read (k_t0_parents, k_tree_emit): R = the inclusive suffix sums of the level-1
 // elements (rb.wa, and rb.wb when TWO), M of them; with TWO, fin = the overflow word (set: the records hold final
 // ranks).  (An owner outside R -- only a slot no tour reaches, which k_t0_parents reports as an error -- reads 0
 // instead of memory past the pool.)
@@ -732,11 +732,17 @@ void debug_list_rank(uint32_t n, const uint32_t *next, const uint8_t *w, const u
 // idx, so a result is reproducible).  This replaces two range-min queries per side over segment trees of the far ends'
 // pre-order numbers, and the forest needs no pre-order numbering at all.
 static constexpr uint32_t T0_RBIT = 0x80000000u;
+// The black-edge test needs two tour positions of the segment's own slots (the first arc of the far side, the first arc
+// of the entered side) -- distances k_t0_parents has in registers while it walks the slots.  It leaves them to k_bridges
+// as one more record per segment, fstr[segment] = {begin | BS_NOARC, end | hash bits}: the stretch [begin, end) of the
+// subtrees hanging off the far side (BS_NOARC: the far side has no arc, no stretch) and the FT_HASH bits of the l and
+// the r side.  Tour positions stay below 2^30 (tree_tour_words), so the two top bits of either word are free.
+static constexpr uint32_t BS_POS = 0x3FFFFFFFu, BS_NOARC = 0x80000000u, BS_HASH_L = 0x40000000u, BS_HASH_R = 0x80000000u;
 __global__ void k_t0_parents(uint32_t V, const uint2 *__restrict__ trec, L0Ranks R, const uint32_t *__restrict__ ckey,
 			     const uint32_t *__restrict__ voff, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
 			     const uint32_t *__restrict__ lle,
 			     const uint32_t *__restrict__ ft, const uint32_t *__restrict__ heads,
-			     uint4 *__restrict__ t0seg, uint4 *__restrict__ xrec, uint32_t C,
+			     uint4 *__restrict__ t0seg, uint2 *__restrict__ fstr, uint4 *__restrict__ xrec, uint32_t C,
 			     const unsigned long long *__restrict__ start_key, uint32_t *__restrict__ err, uint8_t *__restrict__ multi)
 {
 	uint32_t g = BIDX * blockDim.x + threadIdx.x;
@@ -760,7 +766,9 @@ __global__ void k_t0_parents(uint32_t V, const uint2 *__restrict__ trec, L0Ranks
 	// looked at (until round 5 the twin of every forest slot was stored by k_tour_words and its distance gathered here:
 	// 1 GB written, 1 GB read and a scattered 4-byte gather per forest slot on the whole-genome workload).
 	const uint32_t sb = loff[2 * g], sm = loff[2 * g + 1], se = loff[2 * g + 2];
+	const uint2 f2 = *reinterpret_cast<const uint2 *>(ft + 2 * g);
 	uint32_t at_e = NIL, dmin = 0xFFFFFFFFu, dmax = 0u;
+	uint32_t a_l = NIL, a_r = NIL, d_l = 0u, d_r = 0u; // first forest slot of the l and of the r side, and its distance
 	for (uint32_t at0 = sb; at0 < se; at0 += 4) {
 		const uint32_t *r32 = reinterpret_cast<const uint32_t *>(trec + at0);
 		const uint4 lw4 = load4_unaligned(lle + at0), r01 = load4_unaligned(r32), r23 = load4_unaligned(r32 + 4);
@@ -782,19 +790,38 @@ __global__ void k_t0_parents(uint32_t V, const uint2 *__restrict__ trec, L0Ranks
 				at_e = at0 + q;
 			}
 			dmax = max(dmax, ds[q]);
+			if (at0 + q < sm) {
+				if (a_l == NIL)
+					a_l = at0 + q, d_l = ds[q];
+			} else if (a_r == NIL) {
+				a_r = at0 + q, d_r = ds[q];
+			}
 		}
 	}
-	if (at_e == NIL)
-		return; // a component of one segment: its record was written above
-	const uint32_t c = ckey[g];
-	if ((comp_root_side(start_key, voff, c) >> 1) == g)
-		return; // the root segment: all its slots lead to children (record written by the lane of its component)
+	const uint32_t hbits = ((f2.x & FT_HASH) ? BS_HASH_L : 0u) | ((f2.y & FT_HASH) ? BS_HASH_R : 0u);
+	if (at_e == NIL) { // a component of one segment: its record was written above
+		fstr[g] = make_uint2(BS_NOARC, hbits);
+		return;
+	}
+	const uint32_t c = ckey[g], root = comp_root_side(start_key, voff, c);
 	const uint32_t L = 2 * (voff[c + 1] - voff[c] - 1), abase = 2 * (voff[c] - c);
+	if ((root >> 1) == g) { // the root segment: all its slots lead to children (record written by the lane of its component)
+		// the start side's arcs come first, the far side's are the rest of the tour
+		const bool far_r = !(root & 1u);
+		const uint32_t a1 = far_r ? a_r : a_l, d1 = far_r ? d_r : d_l;
+		fstr[g] = a1 == NIL ? make_uint2(BS_NOARC, hbits) : make_uint2((abase + (L - 1 - d1)) & BS_POS, ((abase + L) & BS_POS) | hbits);
+		return;
+	}
 	const uint32_t p_in = abase + (L - 2 - dmax), p_out = abase + (L - 1 - dmin); // tour positions of the arc in and the arc back
 	t0seg[g] = make_uint4(ladj[at_e], (lle[at_e] & LLE_ID) | (at_e >= sm ? T0_RBIT : 0u), p_in, p_out);
+	{ // the far side's arcs, and behind them the arcs of the entered side in front of the entering one, if any: up to the first of those
+		const bool ent_r = at_e >= sm;
+		const uint32_t a1 = ent_r ? a_l : a_r, d1 = ent_r ? d_l : d_r, a3 = ent_r ? a_r : a_l, d3 = ent_r ? d_r : d_l;
+		const uint32_t end = a3 != at_e ? abase + (L - 1 - d3) : p_out;
+		fstr[g] = a1 == NIL ? make_uint2(BS_NOARC, hbits) : make_uint2((abase + (L - 1 - d1)) & BS_POS, (end & BS_POS) | hbits);
+	}
 	// Most segments have no non-tree link, so the values are kept COMPACT (in tour order, only where a side carries
 	// one): here only the bit of the tour position is set; k_tour_values drops the value at its rank among the set bits.
-	const uint2 f2 = *reinterpret_cast<const uint2 *>(ft + 2 * g);
 	if ((f2.x | f2.y) & FT_HASH)
 		atomicOr(reinterpret_cast<unsigned long long *>(&xrec[p_in >> 6]), 1ull << (p_in & 63u));
 }
@@ -850,11 +877,10 @@ static constexpr uint32_t CS_VISITED = 0x40000000u; // (side ids stay below 2^29
 // One lane per SEGMENT: the side a segment is entered through and its far side ask different questions (the hooked link
 // into the segment / the black edge across it), so a lane per side left half of every wave idle in either branch; a lane
 // per segment answers both, loads the segment's record once and stores the words of its two sides together.
-__global__ void k_bridges(uint32_t V, const uint4 *__restrict__ t0seg, const ulonglong2 *__restrict__ xps,
-			  const uint4 *__restrict__ xrec,
-			  const ulonglong2 *__restrict__ hside, const uint32_t *__restrict__ ft,
-			  const uint2 *__restrict__ trec, L0Ranks R, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ lle,
-			  const uint32_t *__restrict__ ckey, const uint32_t *__restrict__ cproc, const uint32_t *__restrict__ voff,
+__global__ void k_bridges(uint32_t V, const uint4 *__restrict__ t0seg, const uint2 *__restrict__ fstr,
+			  const ulonglong2 *__restrict__ xps, const uint4 *__restrict__ xrec,
+			  const ulonglong2 *__restrict__ hside, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ lle,
+			  const uint32_t *__restrict__ ckey, const uint32_t *__restrict__ cproc,
 			  uint8_t *multi, uint32_t *__restrict__ cstate, uint2 *__restrict__ dps)
 {
 	const uint32_t g = BIDX * blockDim.x + threadIdx.x;
@@ -884,22 +910,11 @@ __global__ void k_bridges(uint32_t V, const uint4 *__restrict__ t0seg, const ulo
 		multi[r.x] = 1;
 	}
 	// ---- the far side, across the black edge: what leaves its subtree = its own non-tree links and those of the subtrees
-	// hanging off it
-	const uint2 f2 = *reinterpret_cast<const uint2 *>(ft + 2 * g);
-	const uint32_t fF = (Sf & 1u) ? f2.y : f2.x, fE = (Sf & 1u) ? f2.x : f2.y, a1 = fF & FT_NONE;
-	ulonglong2 x = (fF & FT_HASH) ? hside[Sf] : make_ulonglong2(0ull, 0ull);
-	if (a1 != FT_NONE) {
-		const uint32_t L = 2 * (voff[c + 1] - voff[c] - 1), abase = 2 * (voff[c] - c);
-		const uint32_t a3 = fE & FT_NONE;
-		uint32_t end; // position behind the last of them
-		if (r.x == NIL) // root segment: the start side's arcs come first, the far side's are the rest of the tour
-			end = abase + L;
-		else if (a3 != FT_NONE && (lle[a3] & LLE_ID) != (r.y & ~T0_RBIT)) // arcs of the entered side in front of the entering one follow
-			end = abase + (L - 1 - rank_l0(R, trec[a3]));
-		else
-			end = r.w;
-		x = hx(x, stretch(abase + (L - 1 - rank_l0(R, trec[a1])), end));
-	}
+	// hanging off it, the stretch of the tour k_t0_parents worked out from the segment's own slots (fstr)
+	const uint2 fs = fstr[g];
+	ulonglong2 x = (fs.y & ((Sf & 1u) ? BS_HASH_R : BS_HASH_L)) ? hside[Sf] : make_ulonglong2(0ull, 0ull);
+	if (!(fs.x & BS_NOARC))
+		x = hx(x, stretch(fs.x & BS_POS, fs.y & BS_POS));
 	uint32_t pvF;
 	if (hzero(x)) {
 		pvF = Se | PB_BRIDGE;
@@ -2037,8 +2052,11 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 		tour_r = list_rank_splitters<false>((uint32_t)n_slots, bitsA, tw.dist, nullptr, C, rb, s);
 	const uint32_t XW = NA / 64 + 1; // words of the position bitmap
 	HIP_CHECK(hipMemsetAsync(tw.xrec, 0, ((size_t)XW + 2) * 16, s));
+	// (the far sides' stretches, k_t0_parents -> k_bridges: V 8-byte records over the tour's list words, which the ranking
+	// above has consumed and k_events rewrites, all 3V of them, for the second one; rk_pk holds more than 4V words)
+	uint2 *fstr = reinterpret_cast<uint2 *>(tw.rk_pk);
 	LAUNCH(k_t0_parents, std::max(V, C), s, V, tw.dist, tour_r, cs.ckey, cs.voff, cs.loff, cs.ladj, cs.lle, ft, rb.heads,
-	       tw.t0seg, tw.xrec, C, start_key, pw.err + 2, tw.dvis_slots);
+	       tw.t0seg, fstr, tw.xrec, C, start_key, pw.err + 2, tw.dvis_slots);
 	tm.end(40);
 
 	// ---- 3-4. bridges and 2-edge-connected classes
@@ -2052,7 +2070,7 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 	scan_exclusive_xor_u128(tw.xval, tw.xps, (size_t)V + 1, pw.scan_tmp, pw.scan_tmp_bytes, s, tw.xrank + XW);
 	uint8_t *multi = tw.dvis_slots; // (see tree_spans: sized for max(2E, 2V) + 16; cleared by k_t0_parents)
 	uint32_t *cstate = sw.cur; // [nS+1]
-	LAUNCH(k_bridges, V, s, V, tw.t0seg, tw.xps, tw.xrec, hside, ft, tw.dist, tour_r, cs.loff, cs.lle, cs.ckey, tw.cproc, cs.voff, multi, cstate, tw.dps);
+	LAUNCH(k_bridges, V, s, V, tw.t0seg, fstr, tw.xps, tw.xrec, hside, cs.loff, cs.lle, cs.ckey, tw.cproc, multi, cstate, tw.dps);
 	tm.end(8 + 44);
 
 	// ---- 5-6. entries and the per-class DFS

@@ -27,7 +27,7 @@ struct TreeWs {
 	uint32_t *entry_ps, *entry_list;		  // [2V+1]
 	uint32_t *side_tidx;				  // [2V] tree vertex (T-space) of a side
 	uint32_t *be_cnt;				  // [2V+1] first arc of a side (tour); free afterwards
-	uint32_t *rk_pk, *rk_heads;			  // list ranking: packed list words [4V+8], list heads [C]
+	uint32_t *rk_pk, *rk_heads;			  // list ranking: packed list words [4V+8] (between the first ranking and k_events: the far sides' stretches, [V] 8-byte records), list heads [C]
 	uint32_t *rk_nx, *rk_wa, *rk_wb, *rk_tA, *rk_tB, *rk_tC; // pools of the levels above the list itself
 	uint2 *evt;					  // [4V+2] event records {owner, partial} of the pre-order ranking (ranks {enter count, depth}: rank_l0_pair)
 	uint32_t *cproc;				  // [C+1] 1 = component is decomposed by this shard
