@@ -3,6 +3,7 @@
 #pragma once
 #include "../../../include/povu_hip.h"
 
+#include "forest_wire.hpp"
 #include "graph_kernels.hpp"
 #include "leaf_kernels.hpp"
 #include "par_kernels.hpp"
@@ -118,14 +119,6 @@ struct PinnedVec {
 	const T &operator[](size_t i) const { return p[i]; }
 };
 
-template <typename T>
-struct Span { // just enough of std::vector's surface for the code below
-	T *p = nullptr;
-	T *data() const { return p; }
-	T *begin() const { return p; }
-	T &operator[](size_t i) const { return p[i]; }
-};
-
 struct povu_hip_forest {
 	uint32_t total_components = 0;
 	// the pass that fills this forest: ev0 at its first kernel, ev1 behind its last copy.  `pending` while the arrays may
@@ -158,10 +151,7 @@ struct povu_hip_forest {
 		});
 	}
 	std::shared_ptr<PinnedPool> pool;
-	void *block = nullptr;
-	size_t block_cap = 0, block_bytes = 0, total_entries = 0;
-	int block_seg = -1;	 // shared-memory segment of the block (PinnedPool shared mode), else -1
-	size_t meta_reserve = 0; // trees the block leaves room for behind the arrays (povu_hip_forest_share writes their table there)
+	size_t meta_reserve = 0; // trees a block leaves room for behind the arrays (povu_hip_forest_share writes their table there)
 	static size_t meta_bytes(size_t n_trees) { return 64 + 32 * n_trees; }
 	// the five arrays of a block of `total` PVST vertices, each padded to 64 B: a | z | parent | a_or | z_or; returns the
 	// bytes they take (out == nullptr: only measures)
@@ -179,40 +169,43 @@ struct povu_hip_forest {
 		}
 		return 3 * w + 2 * b;
 	}
-	void alloc(size_t total)
-	{
-		total_entries = total;
-		block = pool->get(layout(nullptr, total) + 64 + meta_bytes(meta_reserve), block_cap, &block_seg);
-		Arrays x;
-		block_bytes = layout(block, total, &x);
-		a_id.p = x.a, z_id.p = x.z, parent.p = x.parent, a_or.p = x.aor, z_or.p = x.zor;
-	}
-	void release_block()
-	{
-		if (block && pool)
-			pool->put(block, block_cap, block_seg);
-		block = nullptr;
-		block_cap = block_bytes = total_entries = 0;
-		block_seg = -1;
-	}
-	// more page-locked blocks with the same five arrays: taken over from other forests or received from other ranks
-	// (povu_hip_forest_merge / povu_hip_comm_gather), so that merging never copies a PVST array
-	struct ExtraBlock : Arrays {
+	static size_t block_bytes_for(size_t total) { return layout(nullptr, total) + 64; } // (what a block takes on the wire)
+	// The PVST arrays live in page-locked blocks: blocks[0] is the one the pass fills (a mixed pass: blocks[1] holds its redone
+	// components); a merged forest holds the blocks it took over from other forests, received from other ranks or mapped
+	// from their segments, so that merging never copies a PVST array.  With a block go the labels of
+	// POVU_HIP_F_LEAF_SUBFLUBBLES (ai / zi, flubbles.cpp:264-290, and the line letter of every PVST vertex, indexed like the
+	// arrays) and the trees after all five passes of -s.
+	struct Block : Arrays {
 		void *p = nullptr;
-		size_t cap = 0, total = 0;
-		int seg = -1;
-		std::shared_ptr<PinnedPool> pool; // null: the memory is not this forest's (a segment of another rank, mapped by the context)
-		PinnedVec<uint32_t> sub_ai, sub_zi; // with POVU_HIP_F_LEAF_SUBFLUBBLES (see the forest's own sub_ai)
+		size_t cap = 0, bytes = 0, total = 0; // of the memory / of the five arrays / PVST vertices
+		int seg = -1;			  // shared-memory segment (PinnedPool shared mode), else -1
+		std::shared_ptr<PinnedPool> pool; // null: the memory is not ours (a segment of another rank, mapped by the context)
+		PinnedVec<uint32_t> sub_ai, sub_zi;
 		PinnedVec<uint8_t> sub_fam;
 		std::shared_ptr<SubForest> subx;
-		void carve(size_t total_entries)
-		{
-			total = total_entries;
-			layout(p, total, this);
-		}
-		static size_t bytes_for(size_t total) { return layout(nullptr, total) + 64; }
 	};
-	std::vector<ExtraBlock> extra;
+	std::vector<Block> blocks;
+	bool labels = false; // the blocks carry sub_ai / sub_zi / sub_fam
+	// `q` (of `cap` bytes; null: out of the forest's pool, with room for the tree table) as a new block of `total` PVST vertices
+	Block &alloc(size_t total, void *q = nullptr, size_t cap = 0)
+	{
+		Block b;
+		b.total = total, b.p = q, b.cap = cap;
+		if (!q) {
+			b.pool = pool;
+			b.p = pool->get(block_bytes_for(total) + meta_bytes(meta_reserve), b.cap, &b.seg);
+		}
+		b.bytes = layout(b.p, total, &b);
+		blocks.push_back(std::move(b));
+		return blocks.back();
+	}
+	void release_blocks()
+	{
+		for (auto &b : blocks)
+			if (b.p && b.pool)
+				b.pool->put(b.p, b.cap, b.seg);
+		blocks.clear();
+	}
 	~povu_hip_forest()
 	{
 		std::call_once(ready_once, [this] { wait_arrays(); }); // (the copy engine may still be writing the blocks)
@@ -222,30 +215,15 @@ struct povu_hip_forest {
 			(void)hipEventDestroy(ev1);
 		for (hipEvent_t e : more_events)
 			(void)hipEventDestroy(e);
-		release_block();
+		release_blocks();
 		if (xblk && pool)
 			pool->put(xblk, xblk_cap, xblk_seg);
-		for (auto &b : extra)
-			if (b.p && b.pool)
-				b.pool->put(b.p, b.cap, b.seg);
 	}
-	struct Tree {
-		uint32_t component_id, n_vtx, n_links, n_pvst;
-		size_t off;	// into the flat arrays below
-		size_t hp_off;	// into hairpins (pairs)
-		uint32_t n_hairpins;
-		int blk = -1;	// -1: the arrays of this forest's own block, else extra[blk]
-		uint32_t sub_c = 0; // with POVU_HIP_F_SUBFLUBBLES: its component in `subx` (of the forest, or of extra[blk])
+	struct Tree : forest_wire::TreeRecord { // (off into the arrays of its block, hp_off into `hairpins` in pairs)
+		int blk = 0; // its block
 	};
 	std::vector<Tree> trees;
-	Span<uint32_t> a_id, z_id, parent;
-	Span<uint8_t> a_or, z_or;
 	std::vector<uint64_t> hairpins;
-	// with POVU_HIP_F_LEAF_SUBFLUBBLES: ai / zi (flubbles.cpp:264-290) and the line letter of every PVST vertex, indexed
-	// like the arrays of this forest's own block
-	PinnedVec<uint32_t> sub_ai, sub_zi;
-	PinnedVec<uint8_t> sub_fam;
-	std::shared_ptr<SubForest> subx; // with POVU_HIP_F_SUBFLUBBLES: the trees after all five passes of -s
 	// povu_hip_forest_share: a second shared-memory segment with what the five arrays do not hold (labels, hairpin
 	// boundaries, the extended trees of -s), kept alive as long as the forest
 	void *xblk = nullptr;
@@ -378,6 +356,9 @@ struct XferScope {
 	}
 };
 
+
+// `m`'s blocks, trees, hairpin boundaries and events move into `out` (m is left empty); shard.hip
+void adopt_forest(povu_hip_forest &out, povu_hip_forest &m);
 
 // Greedy longest-processing-time assignment of n weighted components to `world` ranks, the same on every rank: `order`
 // gets the components heaviest first (stable), owner[c] the least-loaded rank at c's turn (each component adds weight + 1).

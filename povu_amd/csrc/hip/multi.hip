@@ -18,8 +18,6 @@
 #include <set>
 #include <thread>
 
-void adopt_forest(povu_hip_forest &out, povu_hip_forest &m); // shard.hip
-
 namespace
 {
 double now_ms()

@@ -906,10 +906,9 @@ static int64_t parallel_rows(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, c
 	// the result block is allocated as soon as the number of PVST vertices is known (before the emit kernel): the parallel
 	// stages write it straight into pinned host memory, there is no device-to-host copy
 	auto alloc_result_block = [&f](size_t total) -> void * {
-		f.release_block();
-		f.alloc(total);
+		f.release_blocks();
 		void *dev = nullptr;
-		HIP_CHECK(hipHostGetDevicePointer(&dev, f.block, 0));
+		HIP_CHECK(hipHostGetDevicePointer(&dev, f.alloc(total).p, 0));
 		return dev;
 	};
 	run_parallel_dg(ctx->cs, sw, pw, C, t.n_processed, t.n_stack, dense_nb0, alloc_result_block, tm, s, ctx->side, out.tail);
@@ -950,13 +949,15 @@ static void leaf_passes(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, uint32
 	leaf_prepare(ctx->cs, ctx->sw, ctx->pw, ctx->tw, C, ctx->ws_leaf, leaf_state, s);
 	leaf_dense(leaf_state, ctx->sw, ctx->pw, C, s);
 	const size_t n = ctx->pw.d_total;
-	f.sub_ai.resize(n, ctx->pool); // (page-locked, out of the context's pool)
-	f.sub_zi.resize(n, ctx->pool);
-	f.sub_fam.resize(n, ctx->pool);
+	povu_hip_forest::Block &b = f.blocks.empty() ? f.alloc(n) : f.blocks[0]; // (the parallel stages' own)
+	f.labels = n != 0;
+	b.sub_ai.resize(n, ctx->pool); // (page-locked, out of the context's pool)
+	b.sub_zi.resize(n, ctx->pool);
+	b.sub_fam.resize(n, ctx->pool);
 	if (n) {
-		HIP_CHECK(copy_async(f.sub_ai.data(), leaf_state.dense.ai, n * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(copy_async(f.sub_zi.data(), leaf_state.dense.zi, n * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(copy_async(f.sub_fam.data(), leaf_state.dense.fam, n, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(b.sub_ai.data(), leaf_state.dense.ai, n * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(b.sub_zi.data(), leaf_state.dense.zi, n * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(b.sub_fam.data(), leaf_state.dense.fam, n, hipMemcpyDeviceToHost, s));
 	}
 	tm.end(16);
 	HIP_CHECK(hipStreamSynchronize(s));
@@ -967,8 +968,8 @@ static void leaf_passes(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, uint32
 	if (nbad || p.force_redo || p.redo_odd)
 		throw HipError(SUB_REDO_REFUSAL);
 	tm.begin("subflubbles_insert");
-	f.subx = std::make_shared<SubForest>();
-	run_subflubbles(ctx->cs, ctx->sw, ctx->pw, ctx->tw, leaf_state, C, ctx->host, *f.subx, ctx->pool, s, &ctx->ws_sub, &ctx->ws_sub_hint);
+	b.subx = std::make_shared<SubForest>();
+	run_subflubbles(ctx->cs, ctx->sw, ctx->pw, ctx->tw, leaf_state, C, ctx->host, *b.subx, ctx->pool, s, &ctx->ws_sub, &ctx->ws_sub_hint);
 	tm.end(40);
 }
 
@@ -1119,16 +1120,16 @@ static void fetch_seq_pvst(const std::vector<povu_hip_forest::Tree *> &ts, const
 
 // ... and their subflubble labels (leaf_seq wrote them in the same per-component layout)
 static void fetch_seq_labels(const std::vector<povu_hip_forest::Tree *> &ts, const uint32_t *voff, size_t P, const LeafState &ls,
-			     PinnedVec<uint32_t> &ai, PinnedVec<uint32_t> &zi, PinnedVec<uint8_t> &fam, size_t n_total, hipStream_t s)
+			     povu_hip_forest::Block &b, hipStream_t s)
 {
-	ai.assign(n_total, POVU_NIL);
-	zi.assign(n_total, POVU_NIL);
-	fam.assign(n_total, 0);
-	fetch_seq(ts, voff, P, {{ls.p_ai, ai.data(), 4}, {ls.p_zi, zi.data(), 4}, {ls.p_fam, fam.data(), 1}}, false, nullptr, s);
+	b.sub_ai.assign(b.total, POVU_NIL);
+	b.sub_zi.assign(b.total, POVU_NIL);
+	b.sub_fam.assign(b.total, 0);
+	fetch_seq(ts, voff, P, {{ls.p_ai, b.sub_ai.data(), 4}, {ls.p_zi, b.sub_zi.data(), 4}, {ls.p_fam, b.sub_fam.data(), 1}}, false, nullptr, s);
 }
 
-// ---- the result fetch: the dense layout the parallel stages wrote into f's block (a mixed pass: plus a block of its
-// own for the redone components), or the one-lane kernels' per-component layout
+// ---- the result fetch: the dense layout the parallel stages wrote into f.blocks[0] (a mixed pass: plus blocks[1] for the
+// redone components), or the one-lane kernels' per-component layout
 static void fetch_result(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, const uint32_t *voff, const uint32_t *eoff, RowsOut &out,
 			 povu_hip_forest &f, const LeafState &leaf_state, StageTimer &tm)
 {
@@ -1162,22 +1163,23 @@ static void fetch_result(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, const
 	f.hairpins.resize(2 * total_hp);
 	std::vector<povu_hip_forest::Tree *> redone;
 	if (p.all_seq || (out.nbad && !out.mixed)) { // the one-lane kernels' layout for every tree
-		if (f.block && f.total_entries != total)
-			f.release_block();
-		if (!f.block)
+		if (!f.blocks.empty() && f.blocks[0].total != total)
+			f.release_blocks();
+		if (f.blocks.empty())
 			f.alloc(total);
 		for (auto &t : f.trees)
 			redone.push_back(&t);
 		tm.end(0);
-		fetch_seq_pvst(redone, voff, P, ctx->sw, p.hairpins, {f.a_id.p, f.z_id.p, f.parent.p, f.a_or.p, f.z_or.p}, total, f, s);
+		fetch_seq_pvst(redone, voff, P, ctx->sw, p.hairpins, f.blocks[0], total, f, s);
+		f.labels = p.leaf_sub && total;
 		if (p.leaf_sub)
-			fetch_seq_labels(redone, voff, P, leaf_state, f.sub_ai, f.sub_zi, f.sub_fam, total, s);
+			fetch_seq_labels(redone, voff, P, leaf_state, f.blocks[0], s);
 		return;
 	}
-	// the parallel stages wrote every PVST back to back into f's block
+	// the parallel stages wrote every PVST back to back into f.blocks[0]
 	if (!out.mixed && (doff[C] != total || total != ctx->pw.d_total))
 		throw HipError("internal error: dense PVST size mismatch");
-	if (!f.block)
+	if (f.blocks.empty())
 		f.alloc(ctx->pw.d_total);
 	size_t redo_total = 0;
 	for (auto &t : f.trees) {
@@ -1199,17 +1201,13 @@ static void fetch_result(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, const
 		}
 	tm.end(0);
 	if (!redone.empty()) { // the redone components get a block of their own
-		povu_hip_forest::ExtraBlock blk;
-		blk.pool = ctx->pool;
-		blk.p = ctx->pool->get(povu_hip_forest::ExtraBlock::bytes_for(redo_total), blk.cap);
-		blk.carve(redo_total);
-		f.extra.push_back(std::move(blk));
-		povu_hip_forest::ExtraBlock &x = f.extra[0];
+		const int bi = (int)f.blocks.size();
+		povu_hip_forest::Block &x = f.alloc(redo_total);
 		for (auto *t : redone)
-			t->blk = 0;
+			t->blk = bi;
 		fetch_seq_pvst(redone, voff, P, ctx->sw, p.hairpins, x, redo_total, f, s);
 		if (p.leaf_sub)
-			fetch_seq_labels(redone, voff, P, leaf_state, x.sub_ai, x.sub_zi, x.sub_fam, redo_total, s);
+			fetch_seq_labels(redone, voff, P, leaf_state, x, s);
 	} else if (out.fast_tail && out.tail.overlapped && !more) {
 		// the arrays are still on their way: the caller (or the next accessor of the forest) waits for ev1
 		f.pending = true;
@@ -1359,20 +1357,12 @@ extern "C" int povu_hip_forest_get(const povu_hip_forest *f, uint32_t i, povu_hi
 	out->n_vtx = t.n_vtx;
 	out->n_links = t.n_links;
 	out->n_pvst = t.n_pvst;
-	if (t.blk < 0) {
-		out->a_id = f->a_id.data() + t.off;
-		out->z_id = f->z_id.data() + t.off;
-		out->a_or = f->a_or.data() + t.off;
-		out->z_or = f->z_or.data() + t.off;
-		out->parent = f->parent.data() + t.off;
-	} else {
-		const auto &b = f->extra[(size_t)t.blk];
-		out->a_id = b.a + t.off;
-		out->z_id = b.z + t.off;
-		out->a_or = b.aor + t.off;
-		out->z_or = b.zor + t.off;
-		out->parent = b.parent + t.off;
-	}
+	const auto &b = f->blocks[(size_t)t.blk];
+	out->a_id = b.a + t.off;
+	out->z_id = b.z + t.off;
+	out->a_or = b.aor + t.off;
+	out->z_or = b.zor + t.off;
+	out->parent = b.parent + t.off;
 	out->n_hairpins = t.n_hairpins;
 	out->hairpins = t.n_hairpins ? f->hairpins.data() + 2 * t.hp_off : nullptr;
 	return 0;
@@ -1381,18 +1371,24 @@ extern "C" int povu_hip_forest_get(const povu_hip_forest *f, uint32_t i, povu_hi
 extern "C" int povu_hip_forest_raw(const povu_hip_forest *f, const void **block, size_t *bytes, uint64_t *total,
 				   uint64_t offsets[5])
 {
-	if (!f || !block || !bytes || !total || !offsets || !f->extra.empty())
-		return 1; // (a merged forest has one block per rank: no single raw view)
+	if (!f || !block || !bytes || !total || !offsets || f->blocks.size() > 1)
+		return 1; // (several blocks -- a merged forest, a mixed pass: no single raw view)
 	const_cast<povu_hip_forest *>(f)->ready();
-	*block = f->block;
-	*bytes = f->block_bytes;
-	*total = f->total_entries;
-	const char *b = static_cast<const char *>(f->block);
-	offsets[0] = (uint64_t)((const char *)f->a_id.p - b);
-	offsets[1] = (uint64_t)((const char *)f->z_id.p - b);
-	offsets[2] = (uint64_t)((const char *)f->parent.p - b);
-	offsets[3] = (uint64_t)((const char *)f->a_or.p - b);
-	offsets[4] = (uint64_t)((const char *)f->z_or.p - b);
+	if (f->blocks.empty()) { // (a forest without trees, of a shard without components)
+		*block = nullptr, *bytes = 0, *total = 0;
+		std::fill(offsets, offsets + 5, 0ull);
+		return 0;
+	}
+	const auto &b = f->blocks[0];
+	*block = b.p;
+	*bytes = b.bytes;
+	*total = b.total;
+	const char *p = static_cast<const char *>(b.p);
+	offsets[0] = (uint64_t)((const char *)b.a - p);
+	offsets[1] = (uint64_t)((const char *)b.z - p);
+	offsets[2] = (uint64_t)((const char *)b.parent - p);
+	offsets[3] = (uint64_t)((const char *)b.aor - p);
+	offsets[4] = (uint64_t)((const char *)b.zor - p);
 	return 0;
 }
 
@@ -1410,17 +1406,15 @@ extern "C" int povu_hip_forest_get_sub(const povu_hip_forest *f, uint32_t i, con
 	if (!f || i >= f->trees.size())
 		return 1;
 	const auto &t = f->trees[i];
-	const PinnedVec<uint32_t> &va = t.blk < 0 ? f->sub_ai : f->extra[(size_t)t.blk].sub_ai;
-	const PinnedVec<uint32_t> &vz = t.blk < 0 ? f->sub_zi : f->extra[(size_t)t.blk].sub_zi;
-	const PinnedVec<uint8_t> &vf = t.blk < 0 ? f->sub_fam : f->extra[(size_t)t.blk].sub_fam;
-	if (f->sub_fam.empty() || t.off + t.n_pvst > vf.size())
+	const auto &b = f->blocks[(size_t)t.blk];
+	if (!f->labels || t.off + t.n_pvst > b.sub_fam.size())
 		return 3; // the forest was not decomposed with POVU_HIP_F_LEAF_SUBFLUBBLES
 	if (ai)
-		*ai = va.data() + t.off;
+		*ai = b.sub_ai.data() + t.off;
 	if (zi)
-		*zi = vz.data() + t.off;
+		*zi = b.sub_zi.data() + t.off;
 	if (fam)
-		*fam = vf.data() + t.off;
+		*fam = b.sub_fam.data() + t.off;
 	return 0;
 }
 
@@ -1430,7 +1424,7 @@ extern "C" int povu_hip_forest_get_subtree(const povu_hip_forest *f, uint32_t i,
 		return 1;
 	const_cast<povu_hip_forest *>(f)->ready();
 	const auto &t = f->trees[i];
-	const SubForest *x = t.blk < 0 ? f->subx.get() : f->extra[(size_t)t.blk].subx.get();
+	const SubForest *x = f->blocks[(size_t)t.blk].subx.get();
 	if (!x || t.sub_c + 1 >= x->voff.size())
 		return 3; // the forest was not decomposed with POVU_HIP_F_SUBFLUBBLES
 	const uint64_t b = x->voff[t.sub_c], e = x->voff[t.sub_c + 1];

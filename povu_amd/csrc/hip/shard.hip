@@ -424,25 +424,10 @@ extern "C" int povu_hip_forest_globalize(povu_hip_forest *f, const povu_hip_ctx 
 	return 0;
 }
 
-// ---------------------------------------------------------------- forest wire format
+// ---------------------------------------------------------------- forest wire format (forest_wire.hpp)
 namespace
 {
-inline size_t pad64(size_t b) { return (b + 63) & ~size_t(63); }
-struct ForestLayout {
-	size_t meta, a, z, parent, aor, zor, bytes;
-	ForestLayout(size_t n_trees, size_t total)
-	{
-		size_t o = 64;
-		meta = o, o += pad64(n_trees * 16);
-		a = o, o += pad64(total * 4);
-		z = o, o += pad64(total * 4);
-		parent = o, o += pad64(total * 4);
-		aor = o, o += pad64(total);
-		zor = o, o += pad64(total);
-		bytes = o;
-	}
-};
-static constexpr uint64_t FOREST_MAGIC = 0x31747372665F7670ull; // "pv_frst1"
+using namespace forest_wire;
 // copies `n` bytes with a few threads when the block is large (page-locked host memory on both sides)
 void big_copy(void *dst, const void *src, size_t n)
 {
@@ -461,90 +446,83 @@ void big_copy(void *dst, const void *src, size_t n)
 	for (auto &x : th)
 		x.join();
 }
+size_t pvst_total(const povu_hip_forest &f)
+{
+	size_t total = 0;
+	for (const auto &t : f.trees)
+		total += t.n_pvst;
+	return total;
+}
+// the arrays of every tree of `f` back to back into `dst`, tree by tree (their new offsets: the running sum of n_pvst)
+void copy_trees(const povu_hip_forest &f, const povu_hip_forest::Arrays &dst)
+{
+	size_t at = 0;
+	for (const auto &t : f.trees) {
+		const auto &b = f.blocks[(size_t)t.blk];
+		memcpy(dst.a + at, b.a + t.off, (size_t)t.n_pvst * 4);
+		memcpy(dst.z + at, b.z + t.off, (size_t)t.n_pvst * 4);
+		memcpy(dst.parent + at, b.parent + t.off, (size_t)t.n_pvst * 4);
+		memcpy(dst.aor + at, b.aor + t.off, t.n_pvst);
+		memcpy(dst.zor + at, b.zor + t.off, t.n_pvst);
+		at += t.n_pvst;
+	}
+}
 } // namespace
 
 extern "C" size_t povu_hip_forest_pack_size(const povu_hip_forest *f)
 {
-	if (!f)
-		return 0;
-	size_t total = 0;
-	for (const auto &t : f->trees)
-		total += t.n_pvst;
-	return ForestLayout(f->trees.size(), total).bytes;
+	return f ? ForestLayout(f->trees.size(), pvst_total(*f)).bytes : 0;
 }
 
 extern "C" int povu_hip_forest_pack(const povu_hip_forest *f, void *dst, size_t cap)
 {
 	if (!f || !dst)
 		return 1;
-	if (!f->hairpins.empty() || !f->sub_fam.empty())
+	if (!f->hairpins.empty() || f->labels)
 		return 4; // the wire format carries no hairpin boundaries and no subflubble labels: refuse rather than drop them
-	size_t total = 0;
-	for (const auto &t : f->trees)
-		total += t.n_pvst;
+	const size_t total = pvst_total(*f);
 	const ForestLayout L(f->trees.size(), total);
 	if (cap < L.bytes)
 		return 2;
+	const_cast<povu_hip_forest *>(f)->ready(); // (the arrays of a POVU_HIP_F_ASYNC forest may still be on their way)
 	char *b = static_cast<char *>(dst);
-	uint64_t *h = reinterpret_cast<uint64_t *>(b);
-	memset(h, 0, 64);
-	h[0] = f->trees.size(), h[1] = total, h[2] = f->total_components, h[3] = FOREST_MAGIC;
+	ForestLayout::write_header(reinterpret_cast<uint64_t *>(b), f->trees.size(), total, f->total_components);
 	uint32_t *meta = reinterpret_cast<uint32_t *>(b + L.meta);
-	size_t at = 0;
 	for (size_t i = 0; i < f->trees.size(); i++) {
-		povu_hip_tree t;
-		if (povu_hip_forest_get(f, (uint32_t)i, &t) != 0)
-			return 3;
+		const auto &t = f->trees[i];
 		meta[4 * i] = t.component_id, meta[4 * i + 1] = t.n_vtx, meta[4 * i + 2] = t.n_links, meta[4 * i + 3] = t.n_pvst;
-		memcpy(b + L.a + at * 4, t.a_id, (size_t)t.n_pvst * 4);
-		memcpy(b + L.z + at * 4, t.z_id, (size_t)t.n_pvst * 4);
-		memcpy(b + L.parent + at * 4, t.parent, (size_t)t.n_pvst * 4);
-		memcpy(b + L.aor + at, t.a_or, t.n_pvst);
-		memcpy(b + L.zor + at, t.z_or, t.n_pvst);
-		at += t.n_pvst;
 	}
+	copy_trees(*f, {(uint32_t *)(b + L.a), (uint32_t *)(b + L.z), (uint32_t *)(b + L.parent), (uint8_t *)(b + L.aor), (uint8_t *)(b + L.zor)});
 	return 0;
 }
 
-// one packed forest -> an extra block of `out` + its trees
-static void adopt_packed(povu_hip_forest &out, std::shared_ptr<PinnedPool> pool, const char *b, size_t bytes)
+// one packed forest -> a block of `out` + its trees
+static void adopt_packed(povu_hip_forest &out, const char *b, size_t bytes)
 {
 	if (bytes < 64)
 		throw HipError("packed forest too short");
-	const uint64_t *h = reinterpret_cast<const uint64_t *>(b);
-	if (h[3] != FOREST_MAGIC)
-		throw HipError("packed forest: bad magic word");
-	// (counts from the wire: bound them by the buffer before any arithmetic that could wrap)
-	if (h[0] > bytes / 16 || h[1] > bytes / 4)
-		throw HipError("packed forest has the wrong size");
-	const size_t n_trees = h[0], total = h[1];
+	size_t n_trees = 0, total = 0;
+	if (const char *e = ForestLayout::read_header(reinterpret_cast<const uint64_t *>(b), bytes, n_trees, total))
+		throw HipError(e);
 	const ForestLayout L(n_trees, total);
-	if (L.bytes > bytes)
-		throw HipError("packed forest has the wrong size");
-	out.total_components = std::max<uint32_t>(out.total_components, (uint32_t)h[2]);
+	out.total_components = std::max<uint32_t>(out.total_components, (uint32_t)reinterpret_cast<const uint64_t *>(b)[2]);
 	if (n_trees == 0)
 		return;
-	povu_hip_forest::ExtraBlock blk;
-	blk.pool = pool;
-	blk.p = pool->get(povu_hip_forest::ExtraBlock::bytes_for(total), blk.cap);
-	blk.carve(total);
+	const int bi = (int)out.blocks.size();
+	const povu_hip_forest::Block &blk = out.alloc(total);
 	big_copy(blk.a, b + L.a, total * 4);
 	big_copy(blk.z, b + L.z, total * 4);
 	big_copy(blk.parent, b + L.parent, total * 4);
 	big_copy(blk.aor, b + L.aor, total);
 	big_copy(blk.zor, b + L.zor, total);
-	const int bi = (int)out.extra.size();
-	out.extra.push_back(std::move(blk));
 	const uint32_t *meta = reinterpret_cast<const uint32_t *>(b + L.meta);
 	size_t at = 0;
 	for (size_t i = 0; i < n_trees; i++) {
 		povu_hip_forest::Tree t{};
 		t.component_id = meta[4 * i], t.n_vtx = meta[4 * i + 1], t.n_links = meta[4 * i + 2], t.n_pvst = meta[4 * i + 3];
 		t.off = at;
-		t.hp_off = 0;
-		t.n_hairpins = 0;
 		t.blk = bi;
-		if (at + t.n_pvst > total)
+		if (t.n_pvst > total - at)
 			throw HipError("packed forest: tree sizes do not add up");
 		at += t.n_pvst;
 		out.trees.push_back(t);
@@ -568,7 +546,7 @@ extern "C" povu_hip_forest *povu_hip_forest_merge(povu_hip_ctx *ctx, const void 
 		auto f = std::make_unique<povu_hip_forest>();
 		f->pool = ctx->pool;
 		for (uint32_t i = 0; i < n; i++)
-			adopt_packed(*f, ctx->pool, static_cast<const char *>(packed[i]), bytes[i]);
+			adopt_packed(*f, static_cast<const char *>(packed[i]), bytes[i]);
 		sort_trees(*f);
 		return f.release();
 	} catch (const std::exception &e) {
@@ -578,8 +556,9 @@ extern "C" povu_hip_forest *povu_hip_forest_merge(povu_hip_ctx *ctx, const void 
 }
 
 // ---------------------------------------------------------------- merging without copies
-// `m`'s blocks, trees, hairpin boundaries and subflubble labels move into `out` (m is left empty): what the root does with
-// its own forest in every gather, and what the one-process engine (multi.hip) does with every worker's forest.
+// `m`'s blocks (with their labels and extended trees), trees and hairpin boundaries move into `out`, m is left empty: what
+// every merge does with a forest of its own process -- the root with its own in a gather or an attach, the one-process
+// engine (multi.hip) with every worker's.
 void adopt_forest(povu_hip_forest &out, povu_hip_forest &m)
 {
 	// a POVU_HIP_F_ASYNC forest whose arrays are still on their way: the blocks change hands now, the event behind their
@@ -595,44 +574,45 @@ void adopt_forest(povu_hip_forest &out, povu_hip_forest &m)
 		m.pending = false;
 		out.pending = true;
 	}
-	const int base = (int)out.extra.size();
-	int own = -1;
-	if (m.block) {
-		povu_hip_forest::ExtraBlock b;
-		b.pool = m.pool;
-		b.p = m.block;
-		b.cap = m.block_cap;
-		b.seg = m.block_seg;
-		b.carve(m.total_entries);
-		b.sub_ai = std::move(m.sub_ai);
-		b.sub_zi = std::move(m.sub_zi);
-		b.sub_fam = std::move(m.sub_fam);
-		b.subx = std::move(m.subx);
-		own = (int)out.extra.size() + (int)m.extra.size();
-		m.block = nullptr;
-		m.block_cap = m.block_bytes = m.total_entries = 0;
-		m.block_seg = -1;
-		for (auto &e : m.extra)
-			out.extra.push_back(std::move(e));
-		out.extra.push_back(std::move(b));
-	} else {
-		for (auto &e : m.extra)
-			out.extra.push_back(std::move(e));
-	}
-	m.extra.clear();
+	const int base = (int)out.blocks.size();
+	for (auto &b : m.blocks)
+		out.blocks.push_back(std::move(b));
+	m.blocks.clear();
 	const size_t hp_base = out.hairpins.size() / 2;
 	out.hairpins.insert(out.hairpins.end(), m.hairpins.begin(), m.hairpins.end());
 	m.hairpins.clear();
 	for (auto t : m.trees) {
-		t.blk = t.blk < 0 ? own : base + t.blk;
+		t.blk += base;
 		t.hp_off += hp_base;
 		out.trees.push_back(t);
 	}
 	m.trees.clear();
 	out.total_components = std::max(out.total_components, m.total_components);
-	for (const auto &e : out.extra)
-		if (!e.sub_fam.empty() && out.sub_fam.empty())
-			out.sub_fam.assign(1, 0); // (povu_hip_forest_get_sub: "this forest carries labels"; the arrays are the blocks' own)
+	out.labels |= m.labels;
+	m.labels = false;
+}
+
+// a forest whose trees sit in several blocks, or in memory that is not its own -> `out`: one block of f's pool, trees
+// back to back, with room for their table.  `out` is an empty forest, or f itself (its old blocks then go back to their
+// pools).  Labels and extended trees do not come along: the callers refuse those first.
+static void compact_forest(povu_hip_forest &f, povu_hip_forest &out)
+{
+	f.ready();
+	povu_hip_forest one;
+	one.pool = f.pool;
+	one.meta_reserve = f.trees.size() + 1;
+	copy_trees(f, one.alloc(pvst_total(f)));
+	std::vector<povu_hip_forest::Tree> trees = f.trees;
+	size_t at = 0;
+	for (auto &t : trees) {
+		t.blk = 0, t.off = at;
+		at += t.n_pvst;
+	}
+	out.release_blocks();
+	out.pool = f.pool, out.meta_reserve = one.meta_reserve, out.total_components = f.total_components;
+	out.blocks = std::move(one.blocks);
+	one.blocks.clear();
+	out.trees = std::move(trees);
 }
 
 extern "C" int povu_hip_shard_component_ids(const povu_hip_ctx *ctx, const uint32_t **ids, uint32_t *n)
@@ -647,58 +627,20 @@ extern "C" int povu_hip_shard_component_ids(const povu_hip_ctx *ctx, const uint3
 // ---------------------------------------------------------------- gather through shared memory (several processes, one node)
 // Every rank's PVST block already sits in page-locked HOST memory when its decompose returns -- copied there by its own
 // GPU over its own PCIe link.  When that memory is a named shared-memory segment (povu_hip_share_results) the root only
-// has to MAP it: no block goes back to a device, over xGMI and down the root's link again.  What travels between the
-// processes is one 64-byte descriptor per rank (any transport: an RCCL all-gather, torch.distributed, a pipe).
-static constexpr uint64_t SHARE_MAGIC = 0x3165726168735F76ull; // "v_share1"
-static constexpr uint64_t SHARE_EMPTY = ~0ull;
-
-// a forest whose trees sit in several blocks -> one block of its own pool, trees back to back (in place)
-static void compact_in_place(povu_hip_forest &f);
-
-// What the five arrays do not hold -- the leaf passes' labels (ai, zi, line letter per PVST vertex), the hairpin boundaries,
-// the extended trees of `-s` -- travels in a SECOND shared-memory segment of the rank's pool, announced in the header of the
-// tree table (words 3..5: segment, its mapped size, bytes used; ~0 = none).  Sections, each padded to 64 bytes, behind a
-// 128-byte header {magic, PVST vertices, hairpin pairs, flags, components + 1 of the extended trees, their vertices, their
-// child entries, bytes}: [ai][zi] u32 x total, [letter] u8 x total | [pairs] 2 x u64 | [voff] u64, [counts] u32 x 3,
-// [letter][or1][or2][route] u8 x vertices, [id1][id2] u32 x vertices, [coff] u32 x (vertices + 1), [child] u32.
-static constexpr uint64_t SHAREX_MAGIC = 0x7865726168735F76ull; // "v_sharex"
-namespace
-{
-struct XLayout {
-	size_t total = 0, pairs = 0, c1 = 0, nv = 0, nc = 0;
-	bool labels = false, hp = false, sub = false;
-	size_t o_ai = 0, o_zi = 0, o_fam = 0, o_hp = 0, o_voff = 0, o_cnt = 0, o_xfam = 0, o_or1 = 0, o_or2 = 0, o_route = 0, o_id1 = 0, o_id2 = 0,
-	       o_coff = 0, o_child = 0, bytes = 0;
-	void plan()
-	{
-		size_t q = 128;
-		auto sec = [&](size_t b) {
-			const size_t r = q;
-			q += (b + 63) & ~size_t(63);
-			return r;
-		};
-		if (labels)
-			o_ai = sec(total * 4), o_zi = sec(total * 4), o_fam = sec(total);
-		if (hp)
-			o_hp = sec(pairs * 16);
-		if (sub) {
-			o_voff = sec(c1 * 8), o_cnt = sec((c1 ? c1 - 1 : 0) * 12);
-			o_xfam = sec(nv), o_or1 = sec(nv), o_or2 = sec(nv), o_route = sec(nv);
-			o_id1 = sec(nv * 4), o_id2 = sec(nv * 4), o_coff = sec((nv + 1) * 4), o_child = sec(nc * 4);
-		}
-		bytes = q;
-	}
-};
-} // namespace
-
+// has to MAP it as one more block of the merged forest: no block goes back to a device, over xGMI and down the root's link
+// again.  What travels between the processes is one 64-byte descriptor per rank (any transport: an RCCL all-gather,
+// torch.distributed, a pipe).  The descriptor, the tree table behind the arrays and the second segment with what the five
+// arrays do not hold are laid out, written and bounded in forest_wire.hpp and nowhere else.
 extern "C" int povu_hip_forest_share(povu_hip_forest *f, uint64_t desc[8])
 {
 	if (!f || !desc)
 		return 1;
 	try {
-		const bool has_x = !f->hairpins.empty() || !f->sub_fam.empty() || f->subx;
-		if (has_x && !f->extra.empty())
-			return 4; // (labels / boundaries of a MERGED forest: share the parts; a rank's own forest has no extra blocks)
+		const bool one_own = f->blocks.size() == 1 && f->blocks[0].pool == f->pool; // (else: a mixed pass, a merged forest)
+		const bool subx = std::any_of(f->blocks.begin(), f->blocks.end(), [](const povu_hip_forest::Block &b) { return b.subx != nullptr; });
+		const bool has_x = !f->hairpins.empty() || f->labels || subx;
+		if (has_x && !one_own)
+			return 4; // (labels / boundaries travel with the ONE block of a rank's own forest: share the parts of a merged one)
 		if (has_x)
 			f->ready(); // (the labels were copied by the pass itself; nothing of them is still in flight after this)
 		// (no wait for a POVU_HIP_F_ASYNC forest here: the descriptor and the tree table do not depend on the arrays still in
@@ -710,41 +652,32 @@ extern "C" int povu_hip_forest_share(povu_hip_forest *f, uint64_t desc[8])
 		desc[5] = f->total_components;
 		if (f->trees.empty())
 			return 0;
-		if (!f->extra.empty())
-			compact_in_place(*f);
-		if (f->block_seg < 0)
+		const size_t nt = f->trees.size();
+		if (!one_own || (!has_x && f->blocks[0].bytes + povu_hip_forest::meta_bytes(nt) > f->blocks[0].cap))
+			compact_forest(*f, *f);
+		const povu_hip_forest::Block &blk = f->blocks[0];
+		if (blk.seg < 0)
 			return 2; // the block is no shared segment: povu_hip_share_results was not called on the context
-		const size_t nt = f->trees.size(), meta_off = f->block_bytes;
-		if (meta_off + povu_hip_forest::meta_bytes(nt) > f->block_cap)
+		const size_t meta_off = blk.bytes;
+		if (meta_off + povu_hip_forest::meta_bytes(nt) > blk.cap)
 			return 3;
-		char *b = static_cast<char *>(f->block);
-		uint32_t *meta = reinterpret_cast<uint32_t *>(b + meta_off + 64);
-		for (size_t i = 0; i < nt; i++) {
-			const auto &t = f->trees[i];
-			if (t.blk >= 0 || t.off + t.n_pvst > f->total_entries)
-				return 3;
-			uint32_t *q = meta + 8 * i;
-			q[0] = t.component_id, q[1] = t.n_vtx, q[2] = t.n_links, q[3] = t.n_pvst;
-			q[4] = (uint32_t)(t.off & 0xFFFFFFFFu), q[5] = (uint32_t)((uint64_t)t.off >> 32), q[6] = q[7] = 0;
-		}
+		char *b = static_cast<char *>(blk.p);
+		if (!encode_tree_table(reinterpret_cast<uint32_t *>(b + meta_off + 64), f->trees.data(), nt, blk.total, has_x))
+			return 3;
 		uint64_t *mh = reinterpret_cast<uint64_t *>(b + meta_off);
-		mh[0] = SHARE_MAGIC, mh[1] = nt, mh[2] = f->total_entries;
+		mh[0] = SHARE_MAGIC, mh[1] = nt, mh[2] = blk.total;
 		mh[3] = ~0ull, mh[4] = mh[5] = 0;
 		if (has_x) {
-			for (size_t i = 0; i < nt; i++) { // hairpin pairs and the component in the extended trees: the table's two spare words
-				meta[8 * i + 6] = f->trees[i].n_hairpins;
-				meta[8 * i + 7] = f->trees[i].sub_c;
-			}
 			XLayout L;
-			L.total = f->total_entries;
-			L.labels = !f->sub_fam.empty();
+			L.total = blk.total;
+			L.labels = f->labels;
 			L.hp = !f->hairpins.empty();
 			L.pairs = f->hairpins.size() / 2;
-			const SubForest *x = f->subx.get();
+			const SubForest *x = blk.subx.get();
 			L.sub = x != nullptr;
 			if (x)
 				L.c1 = x->voff.size(), L.nv = x->n_vtx, L.nc = x->n_child;
-			if (L.labels && (f->sub_ai.size() < L.total || f->sub_zi.size() < L.total || f->sub_fam.size() < L.total))
+			if (L.labels && (blk.sub_ai.size() < L.total || blk.sub_zi.size() < L.total || blk.sub_fam.size() < L.total))
 				return 3;
 			L.plan();
 			if (f->xblk)
@@ -753,14 +686,11 @@ extern "C" int povu_hip_forest_share(povu_hip_forest *f, uint64_t desc[8])
 			if (f->xblk_seg < 0)
 				return 2;
 			char *xb = static_cast<char *>(f->xblk);
-			uint64_t *h = reinterpret_cast<uint64_t *>(xb);
-			std::fill(h, h + 16, 0ull);
-			h[0] = SHAREX_MAGIC, h[1] = L.total, h[2] = L.pairs, h[3] = (L.labels ? 1u : 0u) | (L.hp ? 2u : 0u) | (L.sub ? 4u : 0u);
-			h[4] = L.c1, h[5] = L.nv, h[6] = L.nc, h[7] = L.bytes;
+			L.write_header(reinterpret_cast<uint64_t *>(xb));
 			if (L.labels) {
-				memcpy(xb + L.o_ai, f->sub_ai.data(), L.total * 4);
-				memcpy(xb + L.o_zi, f->sub_zi.data(), L.total * 4);
-				memcpy(xb + L.o_fam, f->sub_fam.data(), L.total);
+				memcpy(xb + L.o_ai, blk.sub_ai.data(), L.total * 4);
+				memcpy(xb + L.o_zi, blk.sub_zi.data(), L.total * 4);
+				memcpy(xb + L.o_fam, blk.sub_fam.data(), L.total);
 			}
 			if (L.hp)
 				memcpy(xb + L.o_hp, f->hairpins.data(), L.pairs * 16);
@@ -769,24 +699,24 @@ extern "C" int povu_hip_forest_share(povu_hip_forest *f, uint64_t desc[8])
 				if (L.c1 > 1)
 					memcpy(xb + L.o_cnt, x->counts.data(), (L.c1 - 1) * 12);
 				if (L.nv) {
-					memcpy(xb + L.o_xfam, x->fam, L.nv);
-					memcpy(xb + L.o_or1, x->or1, L.nv);
-					memcpy(xb + L.o_or2, x->or2, L.nv);
-					memcpy(xb + L.o_route, x->route, L.nv);
-					memcpy(xb + L.o_id1, x->id1, L.nv * 4);
-					memcpy(xb + L.o_id2, x->id2, L.nv * 4);
+					memcpy(xb + L.x.fam, x->fam, L.nv);
+					memcpy(xb + L.x.or1, x->or1, L.nv);
+					memcpy(xb + L.x.or2, x->or2, L.nv);
+					memcpy(xb + L.x.route, x->route, L.nv);
+					memcpy(xb + L.x.id1, x->id1, L.nv * 4);
+					memcpy(xb + L.x.id2, x->id2, L.nv * 4);
 				}
-				memcpy(xb + L.o_coff, x->coff, (L.nv + 1) * 4);
+				memcpy(xb + L.x.coff, x->coff, (L.nv + 1) * 4);
 				if (L.nc)
-					memcpy(xb + L.o_child, x->child, L.nc * 4);
+					memcpy(xb + L.x.child, x->child, L.nc * 4);
 			}
 			mh[3] = (uint64_t)f->xblk_seg, mh[4] = f->xblk_cap, mh[5] = L.bytes;
 		}
 		__atomic_thread_fence(__ATOMIC_RELEASE); // (the descriptor leaves through a system call anyway)
-		desc[1] = (uint64_t)f->block_seg;
-		desc[2] = f->block_cap;
+		desc[1] = (uint64_t)blk.seg;
+		desc[2] = blk.cap;
 		desc[3] = nt;
-		desc[4] = f->total_entries;
+		desc[4] = blk.total;
 		desc[6] = meta_off;
 		return 0;
 	} catch (const std::exception &) {
@@ -806,122 +736,94 @@ extern "C" povu_hip_forest *povu_hip_forest_attach(povu_hip_ctx *ctx, povu_hip_f
 			throw HipError("attach: bad job tag");
 		auto out = std::make_unique<povu_hip_forest>();
 		out->pool = ctx->pool;
+		// maps a segment of another rank read-only (mappings are kept by the context: the ranks reuse their segments)
+		auto map_segment = [&](const std::string &nm, size_t bytes) -> const char * {
+			auto it = ctx->attached.find(nm);
+			if (it == ctx->attached.end()) {
+				const int fd = shm_open(nm.c_str(), O_RDONLY, 0);
+				if (fd < 0)
+					throw HipError("attach: cannot open the result segment " + nm);
+				struct stat st;
+				if (fstat(fd, &st) != 0 || (size_t)st.st_size < bytes) {
+					(void)close(fd);
+					throw HipError("attach: the result segment " + nm + " is smaller than its descriptor says");
+				}
+				void *p = mmap(nullptr, bytes, PROT_READ, MAP_SHARED, fd, 0);
+				(void)close(fd);
+				if (p == MAP_FAILED)
+					throw HipError("attach: cannot map the result segment " + nm);
+				it = ctx->attached.emplace(nm, povu_hip_ctx::Mapped{p, bytes}).first;
+			} else if (it->second.bytes < bytes) {
+				throw HipError("attach: the result segment " + nm + " changed its size");
+			}
+			return static_cast<const char *>(it->second.p);
+		};
 		for (uint32_t i = 0; i < n; i++) {
 			const uint64_t *d = descs + 8 * (size_t)i;
+			const std::string rank = "rank " + std::to_string(d[7]);
 			if (d[0] != SHARE_MAGIC)
-				throw HipError("attach: bad descriptor from rank " + std::to_string(d[7]));
+				throw HipError("attach: bad descriptor from " + rank);
 			if (d[7] >= n) // (the rank word comes from another process and names a segment: it must be one of the n ranks)
-				throw HipError("attach: descriptor " + std::to_string(i) + " names rank " + std::to_string(d[7]) + " of " + std::to_string(n));
+				throw HipError("attach: descriptor " + std::to_string(i) + " names " + rank + " of " + std::to_string(n));
 			out->total_components = std::max<uint32_t>(out->total_components, (uint32_t)d[5]);
 			if (own && d[7] == own_rank)
 				continue; // the root's own trees stay where they are (below)
 			if (d[1] == SHARE_EMPTY)
 				continue;
-			const std::string name = PinnedPool::segment_name(std::string(job_tag) + "." + std::to_string(d[7]), (int)d[1]);
+			const std::string seg_tag = std::string(job_tag) + "." + std::to_string(d[7]);
 			const size_t seg_bytes = d[2], nt = d[3], total = d[4], meta_off = d[6];
 			// (numbers from another process: bound them before any arithmetic on them)
 			if (nt == 0 || nt > seg_bytes / 32 || total > seg_bytes / 4 || meta_off > seg_bytes ||
-			    meta_off + povu_hip_forest::meta_bytes(nt) > seg_bytes || povu_hip_forest::ExtraBlock::bytes_for(total) - 64 > meta_off)
-				throw HipError("attach: descriptor of rank " + std::to_string(d[7]) + " does not fit its segment");
-			// maps a segment of another rank read-only (mappings are kept by the context: the ranks reuse their segments)
-			auto map_segment = [&](const std::string &nm, size_t bytes) -> const char * {
-				auto it = ctx->attached.find(nm);
-				if (it == ctx->attached.end()) {
-					const int fd = shm_open(nm.c_str(), O_RDONLY, 0);
-					if (fd < 0)
-						throw HipError("attach: cannot open the result segment " + nm);
-					struct stat st;
-					if (fstat(fd, &st) != 0 || (size_t)st.st_size < bytes) {
-						(void)close(fd);
-						throw HipError("attach: the result segment " + nm + " is smaller than its descriptor says");
-					}
-					void *p = mmap(nullptr, bytes, PROT_READ, MAP_SHARED, fd, 0);
-					(void)close(fd);
-					if (p == MAP_FAILED)
-						throw HipError("attach: cannot map the result segment " + nm);
-					it = ctx->attached.emplace(nm, povu_hip_ctx::Mapped{p, bytes}).first;
-				} else if (it->second.bytes < bytes) {
-					throw HipError("attach: the result segment " + nm + " changed its size");
-				}
-				return static_cast<const char *>(it->second.p);
-			};
-			const char *b = map_segment(name, seg_bytes);
+			    meta_off + povu_hip_forest::meta_bytes(nt) > seg_bytes || povu_hip_forest::layout(nullptr, total) > meta_off)
+				throw HipError("attach: descriptor of " + rank + " does not fit its segment");
+			const char *b = map_segment(PinnedPool::segment_name(seg_tag, (int)d[1]), seg_bytes);
 			const uint64_t *mh = reinterpret_cast<const uint64_t *>(b + meta_off);
 			if (mh[0] != SHARE_MAGIC || mh[1] != nt || mh[2] != total)
-				throw HipError("attach: the tree table of rank " + std::to_string(d[7]) + " does not match its descriptor");
-			povu_hip_forest::ExtraBlock blk; // (no pool: the memory is the other rank's)
-			blk.p = const_cast<char *>(b);
-			blk.cap = seg_bytes;
-			blk.carve(total);
+				throw HipError("attach: the tree table of " + rank + " does not match its descriptor");
+			const int bi = (int)out->blocks.size();
+			povu_hip_forest::Block &blk = out->alloc(total, const_cast<char *>(b), seg_bytes); // (no pool: the memory is the other rank's)
 			// what the five arrays do not hold (povu_hip_forest_share): labels, hairpin boundaries, the extended trees of -s
 			XLayout L;
 			const char *xb = nullptr;
 			if (mh[3] != ~0ull) {
 				const size_t xcap = mh[4], xbytes = mh[5];
 				if (xbytes < 128 || xbytes > xcap)
-					throw HipError("attach: bad extras segment of rank " + std::to_string(d[7]));
-				xb = map_segment(PinnedPool::segment_name(std::string(job_tag) + "." + std::to_string(d[7]), (int)mh[3]), xcap);
-				const uint64_t *h = reinterpret_cast<const uint64_t *>(xb);
-				if (h[0] != SHAREX_MAGIC || h[1] != total || h[7] != xbytes)
-					throw HipError("attach: the extras segment of rank " + std::to_string(d[7]) + " does not match its forest");
-				L.total = total, L.pairs = h[2], L.labels = h[3] & 1u, L.hp = h[3] & 2u, L.sub = h[3] & 4u;
-				L.c1 = h[4], L.nv = h[5], L.nc = h[6];
-				// (numbers from another process: bound them before they size anything)
-				if (L.pairs > xbytes / 16 || L.c1 > xbytes / 8 || L.nv > xbytes || L.nc > xbytes / 4)
-					throw HipError("attach: the extras segment of rank " + std::to_string(d[7]) + " names sizes beyond itself");
-				L.plan();
-				if (L.bytes != xbytes)
-					throw HipError("attach: the extras segment of rank " + std::to_string(d[7]) + " has another layout than its header says");
+					throw HipError("attach: bad extras segment of " + rank);
+				xb = map_segment(PinnedPool::segment_name(seg_tag, (int)mh[3]), xcap);
+				if (const char *e = L.read_header(reinterpret_cast<const uint64_t *>(xb), xbytes, total))
+					throw HipError("attach: the extras segment of " + rank + " " + e);
 				if (L.labels) {
 					blk.sub_ai.assign(reinterpret_cast<const uint32_t *>(xb + L.o_ai), reinterpret_cast<const uint32_t *>(xb + L.o_ai) + total);
 					blk.sub_zi.assign(reinterpret_cast<const uint32_t *>(xb + L.o_zi), reinterpret_cast<const uint32_t *>(xb + L.o_zi) + total);
 					blk.sub_fam.assign(reinterpret_cast<const uint8_t *>(xb + L.o_fam), reinterpret_cast<const uint8_t *>(xb + L.o_fam) + total);
-					if (out->sub_fam.empty())
-						out->sub_fam.assign(1, 0); // (povu_hip_forest_get_sub: "this forest carries labels"; the arrays are the blocks' own)
+					out->labels = true;
 				}
 				if (L.sub) { // a view into the mapped segment (no pool, no block of its own: nothing to give back)
 					auto x = std::make_shared<SubForest>();
+					x->point(xb, L.x);
 					const uint64_t *vo = reinterpret_cast<const uint64_t *>(xb + L.o_voff);
+					if (const char *e = validate_subforest(vo, L.c1, x->coff, L.nv, x->child, L.nc))
+						throw HipError("attach: " + rank + ": " + e);
 					x->voff.assign(vo, vo + L.c1);
 					const uint32_t *cn = reinterpret_cast<const uint32_t *>(xb + L.o_cnt);
 					x->counts.assign(cn, cn + (L.c1 ? 3 * (L.c1 - 1) : 0));
 					x->n_vtx = L.nv, x->n_child = L.nc;
-					if (!x->voff.empty() && x->voff.back() != L.nv)
-						throw HipError("attach: the extended trees of rank " + std::to_string(d[7]) + " do not add up");
-					x->fam = reinterpret_cast<const uint8_t *>(xb + L.o_xfam), x->or1 = reinterpret_cast<const uint8_t *>(xb + L.o_or1);
-					x->or2 = reinterpret_cast<const uint8_t *>(xb + L.o_or2), x->route = reinterpret_cast<const uint8_t *>(xb + L.o_route);
-					x->id1 = reinterpret_cast<const uint32_t *>(xb + L.o_id1), x->id2 = reinterpret_cast<const uint32_t *>(xb + L.o_id2);
-					x->coff = reinterpret_cast<const uint32_t *>(xb + L.o_coff), x->child = reinterpret_cast<const uint32_t *>(xb + L.o_child);
 					blk.subx = x;
 				}
 			}
-			const int bi = (int)out->extra.size();
-			out->extra.push_back(std::move(blk));
-			const uint32_t *meta = reinterpret_cast<const uint32_t *>(b + meta_off + 64);
-			size_t hp_seen = 0;
-			for (size_t k = 0; k < nt; k++) {
-				const uint32_t *q = meta + 8 * k;
-				povu_hip_forest::Tree t{};
-				t.component_id = q[0], t.n_vtx = q[1], t.n_links = q[2], t.n_pvst = q[3];
-				t.off = (size_t)q[4] | ((size_t)q[5] << 32);
-				t.blk = bi;
-				if (t.off > total || t.n_pvst > total - t.off)
-					throw HipError("attach: a tree of rank " + std::to_string(d[7]) + " lies outside its block");
-				if (xb) {
-					t.n_hairpins = L.hp ? q[6] : 0;
-					t.sub_c = q[7];
-					if (L.sub && (size_t)t.sub_c + 1 >= L.c1)
-						throw HipError("attach: a tree of rank " + std::to_string(d[7]) + " names a component its extended trees do not have");
-					if (t.n_hairpins) { // the rank's pairs sit in tree order: they go behind the merged forest's, tree by tree
-						if (hp_seen + t.n_hairpins > L.pairs)
-							throw HipError("attach: the hairpin boundaries of rank " + std::to_string(d[7]) + " do not add up");
-						const uint64_t *hp = reinterpret_cast<const uint64_t *>(xb + L.o_hp) + 2 * hp_seen;
-						t.hp_off = out->hairpins.size() / 2;
-						out->hairpins.insert(out->hairpins.end(), hp, hp + 2 * (size_t)t.n_hairpins);
-						hp_seen += t.n_hairpins;
-					}
-				}
-				out->trees.push_back(t);
+			const size_t first = out->trees.size(), hp_base = out->hairpins.size() / 2;
+			if (const char *e = decode_tree_table(reinterpret_cast<const uint32_t *>(b + meta_off + 64), TREE_WORDS * nt, nt, total, xb != nullptr,
+							      L.hp ? L.pairs : 0, L.sub ? L.c1 : 0, out->trees))
+				throw HipError("attach: " + rank + ": " + e);
+			size_t n_hp = 0; // the rank's pairs sit in tree order: they go behind the merged forest's
+			for (size_t k = first; k < out->trees.size(); k++) {
+				out->trees[k].blk = bi;
+				out->trees[k].hp_off += hp_base;
+				n_hp += out->trees[k].n_hairpins;
+			}
+			if (n_hp) {
+				const uint64_t *hp = reinterpret_cast<const uint64_t *>(xb + L.o_hp);
+				out->hairpins.insert(out->hairpins.end(), hp, hp + 2 * n_hp);
 			}
 		}
 		if (own)
@@ -1101,56 +1003,9 @@ extern "C" int povu_hip_comm_scatter(povu_hip_comm *c, const povu_hip_shards *sh
 	}
 }
 
-// a forest whose trees sit in several blocks (sequential redo of some components) -> one block, trees back to back
-static std::unique_ptr<povu_hip_forest> compact_forest(const povu_hip_forest *f)
-{
-	auto out = std::make_unique<povu_hip_forest>();
-	out->pool = f->pool;
-	out->total_components = f->total_components;
-	size_t total = 0;
-	for (const auto &t : f->trees)
-		total += t.n_pvst;
-	out->meta_reserve = f->trees.size() + 1;
-	out->alloc(total);
-	size_t at = 0;
-	for (size_t i = 0; i < f->trees.size(); i++) {
-		povu_hip_tree t;
-		if (povu_hip_forest_get(f, (uint32_t)i, &t) != 0)
-			throw HipError("gather: bad forest");
-		memcpy(out->a_id.p + at, t.a_id, (size_t)t.n_pvst * 4);
-		memcpy(out->z_id.p + at, t.z_id, (size_t)t.n_pvst * 4);
-		memcpy(out->parent.p + at, t.parent, (size_t)t.n_pvst * 4);
-		memcpy(out->a_or.p + at, t.a_or, t.n_pvst);
-		memcpy(out->z_or.p + at, t.z_or, t.n_pvst);
-		povu_hip_forest::Tree nt = f->trees[i];
-		nt.blk = -1;
-		nt.off = at;
-		out->trees.push_back(nt);
-		at += t.n_pvst;
-	}
-	return out;
-}
-
-static void compact_in_place(povu_hip_forest &f)
-{
-	f.ready();
-	std::unique_ptr<povu_hip_forest> c = compact_forest(&f);
-	f.release_block();
-	for (auto &b : f.extra)
-		if (b.p && b.pool)
-			b.pool->put(b.p, b.cap, b.seg);
-	f.extra.clear();
-	f.block = c->block, f.block_cap = c->block_cap, f.block_bytes = c->block_bytes, f.total_entries = c->total_entries;
-	f.block_seg = c->block_seg;
-	f.a_id = c->a_id, f.z_id = c->z_id, f.parent = c->parent, f.a_or = c->a_or, f.z_or = c->z_or;
-	f.trees = std::move(c->trees);
-	c->block = nullptr;
-	c->block_cap = c->block_bytes = c->total_entries = 0;
-}
-
 extern "C" povu_hip_forest *povu_hip_comm_gather(povu_hip_comm *c, const povu_hip_forest *mine, char *err, size_t errlen)
 {
-	std::unique_ptr<povu_hip_forest> compacted;
+	povu_hip_forest compacted; // (a copy of `mine` in one block, where it has several: lives until the sends are done)
 	bool in_group = false;
 	try {
 		if (!c || !c->ctx)
@@ -1174,28 +1029,21 @@ extern "C" povu_hip_forest *povu_hip_comm_gather(povu_hip_comm *c, const povu_hi
 			const_cast<povu_hip_forest *>(mine)->ready();
 			if (!mine->hairpins.empty())
 				throw HipError("gather: hairpin boundaries do not travel");
-			if (!mine->sub_fam.empty())
+			if (mine->labels)
 				throw HipError("gather: subflubble labels do not travel");
-			if (!mine->extra.empty()) { // (rare: some components went through the sequential redo)
-				compacted = compact_forest(mine);
-				mine = compacted.get();
+			if (!root && mine->blocks.size() > 1) { // (rare: some components went through the sequential redo; one block travels)
+				compact_forest(*const_cast<povu_hip_forest *>(mine), compacted);
+				mine = &compacted;
 			}
-			nt = mine->trees.size(), total = mine->total_entries;
+			nt = mine->trees.size(), total = mine->blocks.empty() ? 0 : mine->blocks[0].total;
 			if (!root && nt) { // tree table + block go through device staging, one message each
-				mb = nt * 32, bb = povu_hip_forest::ExtraBlock::bytes_for(total); // 8 words per tree
+				mb = nt * TREE_WORDS * 4, bb = povu_hip_forest::block_bytes_for(total);
 				c->stage.reserve(mb + bb + 512);
 				dmeta = c->stage.take<uint32_t>(mb / 4);
 				dblk = c->stage.take<char>(bb);
-				hmeta = ctx->host.take<uint32_t>(8 * nt);
-				for (size_t i = 0; i < nt; i++) {
-					const auto &t = mine->trees[i];
-					if (t.blk >= 0)
-						throw HipError("gather: unexpected merged forest");
-					if (t.off + t.n_pvst > total)
-						throw HipError("gather: tree outside its block");
-					uint32_t *q = hmeta + 8 * i;
-					q[0] = t.component_id, q[1] = t.n_vtx, q[2] = t.n_links, q[3] = t.n_pvst, q[4] = (uint32_t)t.off, q[5] = q[6] = q[7] = 0;
-				}
+				hmeta = ctx->host.take<uint32_t>(TREE_WORDS * nt);
+				if (!encode_tree_table(hmeta, mine->trees.data(), nt, total, false))
+					throw HipError("gather: tree outside its block");
 			}
 		} catch (const std::exception &e) {
 			my_error = e.what();
@@ -1229,14 +1077,14 @@ extern "C" povu_hip_forest *povu_hip_comm_gather(povu_hip_comm *c, const povu_hi
 				size_t need = 1024;
 				for (uint32_t r = 1; r < c->world; r++)
 					if (all[4 * r])
-						need += pad256(all[4 * r] * 32) + pad256(povu_hip_forest::ExtraBlock::bytes_for(all[4 * r + 1])) + 512;
+						need += pad256(all[4 * r] * TREE_WORDS * 4) + pad256(povu_hip_forest::block_bytes_for(all[4 * r + 1])) + 512;
 				c->stage.reserve(need);
 				for (uint32_t r = 1; r < c->world; r++) {
 					if (!all[4 * r])
 						continue;
 					In x{r, (size_t)all[4 * r], (size_t)all[4 * r + 1], 0, 0, nullptr, nullptr};
-					x.mb = x.nt * 32;
-					x.bb = povu_hip_forest::ExtraBlock::bytes_for(x.total);
+					x.mb = x.nt * TREE_WORDS * 4;
+					x.bb = povu_hip_forest::block_bytes_for(x.total);
 					x.dmeta = c->stage.take<uint32_t>(x.mb / 4);
 					x.dblk = c->stage.take<char>(x.bb);
 					in.push_back(x);
@@ -1257,8 +1105,8 @@ extern "C" povu_hip_forest *povu_hip_comm_gather(povu_hip_comm *c, const povu_hi
 		out->pool = ctx->pool;
 		if (!root) {
 			if (nt) {
-				HIP_CHECK(copy_async(dmeta, hmeta, nt * 32, hipMemcpyHostToDevice, s));
-				HIP_CHECK(copy_async(dblk, mine->block, bb, hipMemcpyHostToDevice, s));
+				HIP_CHECK(copy_async(dmeta, hmeta, mb, hipMemcpyHostToDevice, s));
+				HIP_CHECK(copy_async(dblk, mine->blocks[0].p, bb, hipMemcpyHostToDevice, s));
 				NCCL_CHECK(R.GroupStart());
 				in_group = true;
 				NCCL_CHECK(R.Send(dmeta, mb, ncclChar, 0, c->comm, s));
@@ -1282,49 +1130,21 @@ extern "C" povu_hip_forest *povu_hip_comm_gather(povu_hip_comm *c, const povu_hi
 		uint32_t tc = mine->total_components;
 		std::vector<uint32_t *> hmetas;
 		for (auto &x : in) {
-			povu_hip_forest::ExtraBlock blk;
-			blk.pool = ctx->pool;
-			blk.p = ctx->pool->get(x.bb, blk.cap);
-			blk.carve(x.total);
-			out->extra.push_back(std::move(blk));
-			uint32_t *hm = ctx->host.take<uint32_t>(8 * x.nt);
+			void *p = out->alloc(x.total).p;
+			uint32_t *hm = ctx->host.take<uint32_t>(TREE_WORDS * x.nt);
 			hmetas.push_back(hm);
-			HIP_CHECK(copy_async(hm, x.dmeta, x.nt * 32, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(blk.p, x.dblk, x.bb, hipMemcpyDeviceToHost, s)); // same layout as the sender's block
+			HIP_CHECK(copy_async(hm, x.dmeta, x.mb, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(copy_async(p, x.dblk, x.bb, hipMemcpyDeviceToHost, s)); // same layout as the sender's block
 			tc = std::max<uint32_t>(tc, (uint32_t)all[4 * x.rank + 2]);
 		}
-		// the root's own trees stay where they are: the merged forest takes over the block of `mine`
-		povu_hip_forest *m = const_cast<povu_hip_forest *>(mine);
-		if (m->block) {
-			povu_hip_forest::ExtraBlock own;
-			own.pool = m->pool;
-			own.p = m->block;
-			own.cap = m->block_cap;
-			own.seg = m->block_seg;
-			own.carve(m->total_entries);
-			const int bi = (int)out->extra.size();
-			out->extra.push_back(std::move(own));
-			for (auto t : m->trees) {
-				t.blk = bi;
-				out->trees.push_back(t);
-			}
-			m->block = nullptr;
-			m->block_cap = m->block_bytes = m->total_entries = 0;
-			m->block_seg = -1;
-			m->trees.clear();
-		}
+		adopt_forest(*out, *const_cast<povu_hip_forest *>(mine)); // the root's own trees stay where they are
 		HIP_CHECK(hipStreamSynchronize(s));
 		for (size_t k = 0; k < in.size(); k++) {
-			for (size_t i = 0; i < in[k].nt; i++) {
-				povu_hip_forest::Tree t{};
-				const uint32_t *q = hmetas[k] + 8 * i;
-				t.component_id = q[0], t.n_vtx = q[1], t.n_links = q[2], t.n_pvst = q[3];
-				t.off = q[4];
-				t.blk = (int)k;
-				if (t.off + t.n_pvst > in[k].total)
-					throw HipError("gather: a rank's tree lies outside its block");
-				out->trees.push_back(t);
-			}
+			const size_t first = out->trees.size();
+			if (decode_tree_table(hmetas[k], TREE_WORDS * in[k].nt, in[k].nt, in[k].total, false, 0, 0, out->trees))
+				throw HipError("gather: a rank's tree lies outside its block");
+			for (size_t i = first; i < out->trees.size(); i++)
+				out->trees[i].blk = (int)k;
 		}
 		out->total_components = tc;
 		sort_trees(*out);

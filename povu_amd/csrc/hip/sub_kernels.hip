@@ -1878,35 +1878,29 @@ void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, cons
 	uint8_t *d_fam = dev8((size_t)NV + 4), *d_or1 = dev8((size_t)NV + 4), *d_or2 = dev8((size_t)NV + 4), *d_route = dev8((size_t)NV + 4);
 	uint32_t *d_id1 = dev32((size_t)NV + 4), *d_id2 = dev32((size_t)NV + 4), *d_coff = dev32((size_t)NV + 4);
 	LAUNCH(k_sub_compact, NV, s, NV, C, dvoff, xoff, X, coff, d_fam, d_or1, d_or2, d_route, d_id1, d_id2, d_coff);
-	// one page-locked block: fam | or1 | or2 | route | id1 | id2 | coff (+ 1) | child
-	auto pad = [](size_t b) { return (b + 63) & ~size_t(63); };
-	const size_t b8 = pad((size_t)NV + 1), b32 = pad(((size_t)NV + 1) * 4), bch = pad(((size_t)NCH + 1) * 4);
-	const size_t total_bytes = 4 * b8 + 3 * b32 + bch + 64;
+	// one page-locked block: fam | or1 | or2 | route | id1 | id2 | coff (+ 1) | child, one spare entry each
+	const forest_wire::SubBlockLayout L(NV, NCH, 0, 1);
 	if (!pool)
 		throw HipError("subflubble passes: no pool of page-locked memory (internal)");
 	out.pool = pool;
-	out.blk = pool->get(total_bytes, out.blk_cap, &out.blk_seg);
+	out.blk = pool->get(L.end + 64, out.blk_cap, &out.blk_seg);
 	char *hb = static_cast<char *>(out.blk);
-	uint8_t *o_fam = reinterpret_cast<uint8_t *>(hb), *o_or1 = o_fam + b8, *o_or2 = o_or1 + b8, *o_route = o_or2 + b8;
-	uint32_t *o_id1 = reinterpret_cast<uint32_t *>(hb + 4 * b8), *o_id2 = reinterpret_cast<uint32_t *>(hb + 4 * b8 + b32);
-	uint32_t *o_coff = reinterpret_cast<uint32_t *>(hb + 4 * b8 + 2 * b32), *o_child = reinterpret_cast<uint32_t *>(hb + 4 * b8 + 3 * b32);
-	auto d2h = [&](void *dst, const void *src, size_t bytes) {
+	auto d2h = [&](size_t at, const void *src, size_t bytes) {
 		if (bytes)
-			HIP_CHECK(copy_async(dst, src, bytes, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(copy_async(hb + at, src, bytes, hipMemcpyDeviceToHost, s));
 	};
-	d2h(o_fam, d_fam, NV);
-	d2h(o_or1, d_or1, NV);
-	d2h(o_or2, d_or2, NV);
-	d2h(o_route, d_route, NV);
-	d2h(o_id1, d_id1, (size_t)NV * 4);
-	d2h(o_id2, d_id2, (size_t)NV * 4);
-	d2h(o_coff, d_coff, (size_t)NV * 4);
-	d2h(o_child, child, (size_t)NCH * 4); // (the lists are compact already, in vertex order)
+	d2h(L.fam, d_fam, NV);
+	d2h(L.or1, d_or1, NV);
+	d2h(L.or2, d_or2, NV);
+	d2h(L.route, d_route, NV);
+	d2h(L.id1, d_id1, (size_t)NV * 4);
+	d2h(L.id2, d_id2, (size_t)NV * 4);
+	d2h(L.coff, d_coff, (size_t)NV * 4);
+	d2h(L.child, child, (size_t)NCH * 4); // (the lists are compact already, in vertex order)
 	HIP_CHECK(hipStreamSynchronize(s));
-	o_coff[NV] = NCH;
+	reinterpret_cast<uint32_t *>(hb + L.coff)[NV] = NCH;
 	out.n_vtx = n_vtx, out.n_child = NCH;
-	out.fam = o_fam, out.or1 = o_or1, out.or2 = o_or2, out.route = o_route;
-	out.id1 = o_id1, out.id2 = o_id2, out.coff = o_coff, out.child = o_child;
+	out.point(hb, L);
 	if (arena_hint)
 		*arena_hint = need; // (the next call on this context reserves that much up front)
 	mark("to the host");

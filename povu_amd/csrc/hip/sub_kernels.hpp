@@ -1,6 +1,7 @@
 // sub_kernels.hpp -- the three inserting passes of `povu decompose -s`: find_concealed, find_midi,
 // find_smothered, see sub_kernels.hip
 #pragma once
+#include "forest_wire.hpp"
 #include "leaf_kernels.hpp"
 
 #include <memory>
@@ -34,6 +35,12 @@ struct SubForest {
 	SubForest(const SubForest &) = delete;
 	SubForest &operator=(const SubForest &) = delete;
 	~SubForest();
+	void point(const char *base, const forest_wire::SubBlockLayout &L) // the eight arrays: sections of one block
+	{
+		fam = (const uint8_t *)(base + L.fam), or1 = (const uint8_t *)(base + L.or1), or2 = (const uint8_t *)(base + L.or2);
+		route = (const uint8_t *)(base + L.route), id1 = (const uint32_t *)(base + L.id1), id2 = (const uint32_t *)(base + L.id2);
+		coff = (const uint32_t *)(base + L.coff), child = (const uint32_t *)(base + L.child);
+	}
 };
 
 // Runs find_concealed, find_midi and find_smothered on the state leaf_prepare / leaf_dense left (an all-parallel pass whose

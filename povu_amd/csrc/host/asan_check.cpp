@@ -3,8 +3,10 @@
 // Usage: host_asan_check <file.gfa|file.pvst>...   Every .gfa goes through the tokenizer (1 and 4 threads, with
 // labels and paths), every .pvst through the reader and, where it parses, through the sites of the call's host half
 // (host/vcf.cpp); the names builder and the VCF writer run once over a small hand-made povu_hip_calls.  Malformed inputs
-// must fail with an error, not with a fault.
+// must fail with an error, not with a fault.  The forest's wire formats (hip/forest_wire.hpp: what one process reads of
+// another's forest) run first, on hand-made tables, headers and extended trees: good ones round-trip, bad ones are refused.
 #include "../../../include/povu_hip.h"
+#include "../hip/forest_wire.hpp"
 #include "gfa.hpp"
 
 #include <algorithm>
@@ -14,6 +16,7 @@
 #include <iterator>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 static bool ends_with(const std::string &s, const char *suf)
 {
@@ -97,9 +100,163 @@ static int check_vcf_writer()
 	return 0;
 }
 
+// hip/forest_wire.hpp; returns 0 or the line of the first check that failed
+static int check_forest_wire()
+{
+	using namespace forest_wire;
+#define WANT(x)                                                                                                                              \
+	do {                                                                                                                                 \
+		if (!(x))                                                                                                                    \
+			return __LINE__;                                                                                                     \
+	} while (0)
+	// ---- tree tables: 0, 1 and 5 trees, with and without the extras words; the last tree's offset needs the high word
+	const uint64_t big = (1ull << 32) + 1000;
+	const TreeRecord five[5] = {{1, 10, 12, 7, 0, 0, 2, 0}, {2, 3, 2, 0, 7, 2, 0, 1}, {4, 9, 9, 5, 7, 2, 1, 2}, {7, 1, 0, 1, 12, 3, 0, 2},
+				    {9, 50, 70, 900, big - 900, 3, 3, 3}};
+	for (size_t n : {size_t(0), size_t(1), size_t(5)})
+		for (bool extras : {false, true}) {
+			std::vector<uint32_t> w(TREE_WORDS * n + 1, 0xABABABABu);
+			WANT(encode_tree_table(w.data(), five, n, big, extras) && w[TREE_WORDS * n] == 0xABABABABu);
+			std::vector<TreeRecord> got;
+			WANT(!decode_tree_table(w.data(), TREE_WORDS * n, n, big, extras, 6, 5, got) && got.size() == n);
+			for (size_t i = 0; i < n; i++) {
+				WANT(got[i].component_id == five[i].component_id && got[i].n_vtx == five[i].n_vtx && got[i].n_links == five[i].n_links);
+				WANT(got[i].n_pvst == five[i].n_pvst && got[i].off == five[i].off);
+				WANT(got[i].n_hairpins == (extras ? five[i].n_hairpins : 0) && got[i].sub_c == (extras ? five[i].sub_c : 0));
+				WANT(!extras || got[i].hp_off == five[i].hp_off);
+			}
+			if (n == 5)
+				WANT(w[TREE_WORDS * 4 + 5] == 1 && w[5] == 0); // (the high word: only where the offset needs it)
+		}
+	{
+		std::vector<TreeRecord> got;
+		std::vector<uint32_t> w(TREE_WORDS * 5);
+		WANT(encode_tree_table(w.data(), five, 5, big, true));
+		WANT(!encode_tree_table(w.data(), five, 5, big - 1, true)); // (the sender's own table: the last tree ends behind the block)
+		WANT(encode_tree_table(w.data(), five, 5, big, true));
+		WANT(decode_tree_table(w.data(), w.size(), 5, big - 1, true, 6, 5, got));	  // n_pvst > total - off
+		// off > total and nothing else wrong (n_pvst 0: `total - off` alone would wrap and let it through), decoded and encoded
+		const TreeRecord behind = {3, 1, 0, 0, 12, 0, 0, 0};
+		uint32_t qb[TREE_WORDS] = {3, 1, 0, 0, 12, 0, 0, 0};
+		std::vector<TreeRecord> edge;
+		WANT(decode_tree_table(qb, TREE_WORDS, 1, 11, false, 0, 0, edge) && !encode_tree_table(qb, &behind, 1, 11, false) && edge.empty());
+		WANT(encode_tree_table(qb, &behind, 1, 12, false) && !decode_tree_table(qb, TREE_WORDS, 1, 12, false, 0, 0, edge) && edge.size() == 1);
+		WANT(decode_tree_table(w.data(), w.size(), 5, big, true, 6, 4, got));		  // sub_c + 1 >= c1
+		WANT(decode_tree_table(w.data(), w.size(), 5, big, true, 5, 5, got));		  // hairpin counts beyond `pairs`
+		WANT(decode_tree_table(w.data(), w.size() - 1, 5, big, true, 6, 5, got));	  // more trees than the buffer holds
+		WANT(decode_tree_table(w.data(), w.size(), ~size_t(0) / 2, big, true, 6, 5, got)); // (and a count whose size would wrap)
+		got.clear();
+		WANT(!decode_tree_table(w.data(), w.size(), 5, big, false, 0, 0, got) && got.size() == 5 && got[4].n_hairpins == 0);
+		// off + n_pvst wraps in 32 bits / in 64 bits
+		uint32_t q32[TREE_WORDS] = {1, 1, 1, 0x20, 0xFFFFFFF0u, 0, 0, 0}, q64[TREE_WORDS] = {1, 1, 1, 16, 0xFFFFFFFBu, 0xFFFFFFFFu, 0, 0};
+		WANT(decode_tree_table(q32, TREE_WORDS, 1, 0xFFFFFFF8ull, false, 0, 0, got));
+		WANT(decode_tree_table(q64, TREE_WORDS, 1, ~0ull, false, 0, 0, got));
+		WANT(got.size() == 5);
+	}
+	// ---- the packed forest's header
+	{
+		const ForestLayout L(5, 1000);
+		WANT(L.meta == 64 && L.a == 64 + 128 && L.z == L.a + 4032 && L.parent == L.z + 4032 && L.aor == L.parent + 4032);
+		WANT(L.zor == L.aor + 1024 && L.bytes == L.zor + 1024);
+		uint64_t h[8];
+		size_t n_trees = 0, total = 0;
+		ForestLayout::write_header(h, 5, 1000, 9);
+		WANT(!ForestLayout::read_header(h, L.bytes, n_trees, total) && n_trees == 5 && total == 1000 && h[2] == 9);
+		WANT(ForestLayout::read_header(h, L.bytes - 1, n_trees, total)); // the buffer is shorter than the plan
+		h[0] = ~0ull / 16;
+		WANT(ForestLayout::read_header(h, L.bytes, n_trees, total)); // sizes beyond the buffer (their bytes would wrap)
+		h[0] = 5, h[1] = ~0ull / 4;
+		WANT(ForestLayout::read_header(h, L.bytes, n_trees, total));
+		h[1] = 1000, h[3] ^= 1;
+		WANT(ForestLayout::read_header(h, L.bytes, n_trees, total)); // bad magic word
+	}
+	// ---- the extras segment: every combination of the three flags
+	for (unsigned flags = 0; flags < 8; flags++) {
+		XLayout L;
+		L.labels = flags & 1u, L.hp = flags & 2u, L.sub = flags & 4u;
+		L.total = 77, L.pairs = L.hp ? 5 : 0;
+		if (L.sub)
+			L.c1 = 4, L.nv = 130, L.nc = 129;
+		L.plan();
+		size_t want = 128;
+		if (L.labels) {
+			WANT(L.o_ai == want && L.o_zi == want + 320 && L.o_fam == want + 640);
+			want += 640 + 128;
+		}
+		if (L.hp) {
+			WANT(L.o_hp == want);
+			want += 128;
+		}
+		if (L.sub) {
+			WANT(L.o_voff == want && L.o_cnt == want + 64 && L.x.fam == want + 128);
+			want += 128;
+			WANT(L.x.or1 == want + 192 && L.x.or2 == want + 384 && L.x.route == want + 576 && L.x.id1 == want + 768);
+			WANT(L.x.id2 == L.x.id1 + 576 && L.x.coff == L.x.id2 + 576 && L.x.child == L.x.coff + 576 && L.x.end == L.x.child + 576);
+			want = L.x.end;
+		}
+		WANT(L.bytes == want);
+		uint64_t h[16];
+		L.write_header(h);
+		XLayout R;
+		WANT(!R.read_header(h, L.bytes, 77) && R.bytes == L.bytes && R.labels == L.labels && R.hp == L.hp && R.sub == L.sub);
+		WANT(R.o_ai == L.o_ai && R.o_hp == L.o_hp && R.o_voff == L.o_voff && R.x.child == L.x.child && R.x.end == L.x.end);
+		WANT(R.read_header(h, L.bytes, 78));	  // another forest's
+		WANT(R.read_header(h, L.bytes + 64, 77)); // `bytes` disagrees with what is mapped
+		h[7] += 64;
+		WANT(R.read_header(h, L.bytes + 64, 77)); // ... and with the plan
+		h[7] -= 64;
+		for (int k : {2, 4, 5, 6}) { // sizes beyond the segment
+			const uint64_t keep = h[k];
+			h[k] = ~0ull / 8;
+			WANT(R.read_header(h, L.bytes, 77));
+			h[k] = keep;
+		}
+		WANT(!R.read_header(h, L.bytes, 77));
+	}
+	{ // the -s result block: the same eight sections with one spare entry each, from 0
+		const SubBlockLayout B(130, 129, 0, 1);
+		WANT(B.fam == 0 && B.or1 == 192 && B.id1 == 768 && B.id2 == 768 + 576 && B.coff == B.id2 + 576 && B.child == B.coff + 576);
+		WANT(B.end == B.child + 576);
+		const SubBlockLayout Z(63, 15, 0, 1); // (the spare entry takes a section over a boundary)
+		WANT(Z.or1 == 64 && Z.id1 == 256 && Z.coff == 256 + 512 && Z.child == Z.coff + 256 && Z.end == Z.child + 64);
+	}
+	// ---- extended trees: three components (the second without vertices) of 3 and 2 vertices
+	{
+		const uint64_t voff[4] = {0, 3, 3, 5};
+		const uint32_t coff[6] = {0, 2, 2, 2, 3, 3}, child[3] = {1, 2, 1};
+		WANT(!validate_subforest(voff, 4, coff, 5, child, 3));
+		WANT(!validate_subforest(voff, 0, coff, 0, child, 0) && validate_subforest(voff, 0, coff, 5, child, 3));
+		auto bad = [&](int what) {
+			std::vector<uint64_t> v(voff, voff + 4);
+			std::vector<uint32_t> c(coff, coff + 6), ch(child, child + 3);
+			size_t nv = 5, nc = 3;
+			switch (what) {
+			case 0: v[1] = 4, v[2] = 3; break;	// voff decreasing
+			case 1: v[3] = 4; break;		// voff.back() != nv
+			case 2: c[2] = 1; break;		// coff decreasing
+			case 3: c[5] = 2; break;		// coff[nv] != nc
+			case 4: ch[2] = 2; break;		// a child equal to its component's vertex count
+			case 5: ch[0] = 3; break;		// (the same in the first component)
+			case 6: v[0] = 1; break;		// vertices before the first component
+			case 7: c[1] = 0xFFFFFFF0u; break; // (an offset far behind `child`: found before anything is read there)
+			}
+			return validate_subforest(v.data(), 4, c.data(), nv, ch.data(), nc) != nullptr;
+		};
+		for (int what = 0; what < 8; what++)
+			WANT(bad(what));
+	}
+#undef WANT
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	unsigned long ok = 0, rejected = 0;
+	if (int line = check_forest_wire()) {
+		fprintf(stderr, "host_asan_check: forest_wire check failed at line %d\n", line);
+		return 13;
+	}
+	printf("host_asan_check: forest_wire ok\n");
 	if (int rc = check_vcf_writer())
 		return rc;
 	for (int i = 1; i < argc; i++) {

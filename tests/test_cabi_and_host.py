@@ -522,7 +522,8 @@ def test_pvst_reader_subflubble_lines():
 def test_host_code_under_address_and_ub_sanitizers(golden_dir, tmp_path):
     """The tokenizer, the PVST reader and the call's host half (sites of every PVST that parses; names and the VCF writer on a
     hand-made povu_hip_calls) under -fsanitize=address,undefined (CPU build; the GPU pool has no sanitizer runs) over every
-    golden input, the malformed fixtures and truncated PVST texts."""
+    golden input, the malformed fixtures and truncated PVST texts; before those, the wire formats of a forest on hand-made
+    tables, headers and extended trees (good ones round-trip, bad ones are refused)."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     subprocess.check_call(["make", "-C", os.path.join(root, "povu_amd", "csrc"), "asan", "-s"])
     exe = os.path.join(root, "build", "obj", "host_asan_check")
@@ -545,6 +546,7 @@ def test_host_code_under_address_and_ub_sanitizers(golden_dir, tmp_path):
     assert r.returncode == 0, r.stderr[-3000:]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     assert "parsed" in r.stdout
+    assert "forest_wire ok" in r.stdout  # (the tree table, the pack / share headers and the extended trees: hip/forest_wire.hpp)
 
 
 def test_gfa_writer_is_the_inverse_of_the_loader_contract(tmp_path):

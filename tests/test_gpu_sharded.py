@@ -264,7 +264,7 @@ def _shared_extras_worker(rank, world, port, out_path):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     dev = torch.device("cpu")
     from povu_amd import HipDecomposer
-    from povu_amd.hip import F_HAIRPINS, F_LEAF_SUBFLUBBLES, F_SUBFLUBBLES
+    from povu_amd.hip import F_HAIRPINS, F_LEAF_SUBFLUBBLES, F_REDO_ODD, F_SUBFLUBBLES
     work = HipDecomposer(0)
     tag = [f"x{os.getpid()}" if rank == 0 else None]
     dist.broadcast_object_list(tag, src=0)
@@ -274,13 +274,18 @@ def _shared_extras_worker(rank, world, port, out_path):
         full = HipDecomposer(0)
         full.upload(_graph())
     res, keep = {}, []
-    for name, flags in (("leaf", F_LEAF_SUBFLUBBLES), ("all", F_SUBFLUBBLES), ("hairpins", F_HAIRPINS), ("plain", 0), ("all2", F_SUBFLUBBLES)):
+    for name, flags in (("leaf", F_LEAF_SUBFLUBBLES), ("all", F_SUBFLUBBLES), ("hairpins", F_HAIRPINS), ("plain", 0), ("all2", F_SUBFLUBBLES),
+                        ("mixed", F_REDO_ODD)):
         sharded.scatter_over_dist(full, work, rank, world, dev)
         f = work.decompose_shard(flags=flags)
+        if name == "plain":
+            f.raw()  # (a rank's own plain forest is one block: it has a raw view)
         merged = sharded.gather_shared(work, f, rank, world, dev, tag[0])
         keep.append(f)  # (the root reads this rank's segments in place)
         if rank == 0:
             res[name] = {str(k): v for k, v in merged.texts().items()}
+            with pytest.raises(RuntimeError):  # (one block per rank: no single raw view)
+                merged.raw()
             if name == "hairpins":
                 res["hp"] = {str(merged.tree(i).component_id): merged.tree(i).hairpins.tolist() for i in range(len(merged))}
             if name.startswith("all"):
@@ -315,12 +320,58 @@ def test_shared_memory_gather_carries_labels_boundaries_and_extended_trees(tmp_p
     assert as_int(got["all"]) == want_all and as_int(got["all2"]) == want_all
     assert sum(c[0] for c in got["all_counts"]) > 0
     assert as_int(got["plain"]) == O.decompose(g) == as_int(got["hairpins"])
+    # every second component of each rank through the redo: two blocks per rank, copied into one before they are shared
+    # (the root's too: every rank shares); a merge that takes two-block forests over as they are is the one-process engine's
+    assert as_int(got["mixed"]) == O.decompose(g)
     one = HipDecomposer(0)
     one.upload(g)
     fh = one.decompose(flags=F_HAIRPINS)
     assert {int(k): v for k, v in got["hp"].items()} == {fh.tree(i).component_id: fh.tree(i).hairpins.tolist() for i in range(len(fh))}
     assert any(v for v in got["hp"].values())
     one.close()
+
+
+# md5 of Forest.pack() of a plain pass and of one with F_REDO_ODD over the graph of the test below, taken at the commit before
+# the forest got one block type: the packed bytes are a wire format and stay what they were
+_PACK_MD5 = {"plain": "57bc8b171f56fa740585be4738995527", "redo_odd": "57bc8b171f56fa740585be4738995527"}
+
+
+def test_forest_of_several_blocks_packs_and_reads_like_one():
+    """A mixed pass (F_REDO_ODD: every second component through the redo) leaves a forest of two blocks, each with a tree at
+    a non-zero offset: it packs to the same bytes as ever, the packed bytes merge back to the oracle's texts, and with the
+    leaf passes' labels tree(i), sub(i) and texts() read every tree out of the block it lives in; labels still do not pack."""
+    import hashlib
+    from povu_amd import HipDecomposer
+    from povu_amd.hip import F_LEAF_SUBFLUBBLES, F_REDO_ODD
+    g = W.hprc_shaped([40, 25, 30, 20], seed=1, tiny=3)
+    hip = HipDecomposer(0)
+    hip.upload(g)
+    want = O.decompose(g)
+    for name, flags in (("plain", 0), ("redo_odd", F_REDO_ODD)):
+        f = hip.decompose(flags=flags)
+        assert (hip.seq_redo_count() > 0) == (name == "redo_odd")
+        packed = f.pack()
+        digest = hashlib.md5(packed.tobytes()).hexdigest()
+        print(name, "pack md5", digest)
+        assert digest == _PACK_MD5[name]
+        assert f.texts() == want and hip.merge_forests([packed]).texts() == want
+        if name == "redo_odd":
+            with pytest.raises(RuntimeError):
+                f.raw()
+    want = O.decompose(g, leaf=True)
+    f = hip.decompose(flags=F_REDO_ODD | F_LEAF_SUBFLUBBLES)
+    assert hip.seq_redo_count() > 0 and f.texts() == want and len(f) == len(want)
+    for i in range(len(f)):
+        t = f.tree(i)
+        ai, zi, fam = f.sub(i)
+        lines = [ln.split("\t") for ln in want[t.component_id].splitlines()[1:]]
+        assert len(lines) == len(t.a_id) == len(fam) == len(ai) == len(zi)
+        for v, ln in enumerate(lines):
+            label = "." if v == 0 else "><"[int(t.a_or[v] != 0)] + str(t.a_id[v]) + "><"[int(t.z_or[v] != 0)] + str(t.z_id[v])
+            assert ln[:3] == [chr(fam[v]), str(v), label], (t.component_id, v)
+    with pytest.raises(RuntimeError, match="forest pack failed"):
+        f.pack()
+    hip.close()
 
 
 def test_one_process_engine_three_ranks_on_one_device():
@@ -347,6 +398,9 @@ def test_one_process_engine_three_ranks_on_one_device():
     assert f2.texts() == want and f.texts() == want
     # what does not travel between processes does move inside one: subflubble labels and hairpin boundaries
     assert md.decompose(F_LEAF_SUBFLUBBLES).texts() == O.decompose(g, leaf=True)
+    # ... also when every worker's forest has two blocks (every second component of a shard through the redo)
+    from povu_amd.hip import F_REDO_ODD
+    assert md.decompose(F_REDO_ODD | F_LEAF_SUBFLUBBLES).texts() == O.decompose(g, leaf=True)
     from povu_amd.hip import F_SUBFLUBBLES
     assert md.decompose(F_SUBFLUBBLES).texts() == O.decompose(g, leaf=2)  # all five passes of -s: the extended trees move too
     one = HipDecomposer(0)
