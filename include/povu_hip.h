@@ -489,6 +489,26 @@ typedef struct {
 	uint64_t n_normalized;		     /* records with POVU_HIP_CALL_NORMALIZED */
 	uint64_t max_shift;		     /* the largest norm_shift */
 	uint64_t n_norm_compared;	     /* bases the backward walks compared, over every (record, ALT) */
+	/* per row ("Decomposed calls"), in (reference path, row POS, record, ALT, alignment order).  Outside
+	 * POVU_HIP_PROFILE_DECOMPOSED: n_rows 0, the arrays NULL, the counters 0.  A row is one primitive of the alignment of
+	 * its record's REF and ALT row_alt, or that ALT kept whole; the record arrays above stay the raw call's.  The row's REF
+	 * is row_lead (when not 0) and then bytes [row_ref_start, row_ref_start + row_ref_len) of the record's REF text, its
+	 * ALT row_lead and then bytes [row_alt_start, row_alt_start + row_alt_len) of that ALT's text */
+	uint64_t n_rows;
+	const uint32_t *row_record; /* [n_rows] record of the row */
+	const uint32_t *row_alt;    /* [n_rows] its ALT, 1-based */
+	const uint8_t *row_kind;    /* [n_rows] POVU_HIP_ROW_* */
+	const uint8_t *row_reason;  /* [n_rows] POVU_HIP_REASON_* of a _ROW_PASS row, else 0 */
+	const uint32_t *row_index;  /* [n_rows] k of snp<k>, ins<k>, del<k>: counts within the kind and the ALT from 1; else 0 */
+	const uint64_t *row_pos;    /* [n_rows] POS */
+	const uint32_t *row_ref_start, *row_ref_len, *row_alt_start, *row_alt_len;
+	const uint8_t *row_lead;    /* [n_rows] 0, or the anchor base of an indel written in front of both: the REF base in
+				     * front of it, the reference path's base in front of POS for an indel at offset 0 */
+	const uint32_t *row_ac, *row_an, *row_ns; /* [n_rows] counted on the projected genotypes (0 stays, row_alt is 1, else missing) */
+	uint64_t n_decomposed_alts;  /* (record, ALT) written as primitives */
+	uint64_t n_passthrough_alts; /* (record, ALT) kept whole (_ROW_PASS); a _ROW_RAW row counts as neither */
+	uint64_t n_prim_tier2;	     /* pairs the striped kernel aligned (a text longer than 64 bytes, or all with _T_FORCE_TIER2) */
+	uint64_t n_prim_cells;	     /* sum of (len REF + 1) * (len ALT + 1) over the aligned pairs */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
@@ -510,6 +530,25 @@ povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, co
  * chopped and trimmed.  Does not imply POVU_HIP_T_NESTED (may be combined with it and with _T_INVERSIONS); max_level and the
  * lengths are ignored */
 #define POVU_HIP_PROFILE_LEFT_NORMALIZED 3u
+/* "Decomposed calls": every record is kept and every (REF, ALT) of a flubble record is aligned (unit-cost edit distance, gaps
+ * as far left as the optimum allows) and written as its primitives, one row each (povu_hip_calls.n_rows, row_*).  Does not
+ * imply POVU_HIP_T_NESTED (may be combined with it and with _T_INVERSIONS); max_level and max_ref_length are ignored,
+ * max_allele_length is the longest text that is aligned: 0 means POVU_HIP_PRIM_MAX_LENGTH, more than that is refused */
+/* (povu_hip_calls_vcf_profile writes such rows; the device step that makes them is not in this build, and
+ * povu_hip_call_profile refuses the profile as unknown) */
+#define POVU_HIP_PROFILE_DECOMPOSED 4u
+#define POVU_HIP_PRIM_MAX_LENGTH 512u
+#define POVU_HIP_ROW_RAW 0u /* the record as the raw call writes it: its one ALT is one primitive that spells POS, REF and ALT */
+#define POVU_HIP_ROW_SNP 1u
+#define POVU_HIP_ROW_INS 2u
+#define POVU_HIP_ROW_DEL 3u
+#define POVU_HIP_ROW_PASS 4u /* the ALT kept whole */
+#define POVU_HIP_REASON_NONE 0u
+#define POVU_HIP_REASON_MAX_ALLELE_LENGTH 1u /* a text is longer than the cap */
+#define POVU_HIP_REASON_CONTIG_START 2u	     /* an indel at offset 0 of a record at POS 1: no base to anchor it on */
+#define POVU_HIP_REASON_EMPTY_ALLELE 3u
+#define POVU_HIP_REASON_EQUALS_REF 4u /* the texts are equal after upper-casing */
+#define POVU_HIP_REASON_SUBR 5u	      /* an inversion record: passes through whole */
 typedef struct {
 	uint32_t profile; /* POVU_HIP_PROFILE_* */
 	uint32_t max_level;
@@ -601,8 +640,10 @@ char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, c
  * ref_spelled may be NULL (a hand-made povu_hip_calls): then the plain call's values hold.  Under _LEFT_NORMALIZED a record
  * with POVU_HIP_CALL_NORMALIZED is written with POS, REF and ALT normalised, `:norm` behind its ID and ORIGIN, RAW_ALT_INDEX,
  * PROFILE, LEFT_NORMALIZED, RAW_POS, RAW_REF and RAW_ALT behind LV (or PS), any other record as the raw call writes it; raw_pos
- * or norm_block NULL: no record was changed.  Under the other profiles the fields behind `nested` are not read.  NULL for an
- * unknown profile */
+ * or norm_block NULL: no record was changed.  Under _DECOMPOSED the rows are written instead of the records (INTEGRATION.md
+ * "Decomposed calls": IDs `<label>:<alt>:snp<k>` / `ins<k>` / `del<k>` / `passthrough`, `<label>:subr-passthrough`; a _ROW_RAW row is
+ * its record's raw line); NULL row arrays: the raw records.  Under the other profiles the fields behind `nested` are not
+ * read.  NULL for an unknown profile */
 char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
 				 const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, uint32_t profile,
 				 size_t *len);

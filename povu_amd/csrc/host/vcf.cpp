@@ -32,7 +32,7 @@ const char *VCF_HEADER =
 	"##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
 // a nested call's own line ("Nested calls"), and the lines of the keys a profile appends (the reference fixture's texts)
 const char *PS_LINE = "##INFO=<ID=PS,Number=1,Type=String,Description=\"ID of the enclosing record of the same reference path\">\n";
-const char *PROFILE_NAME[] = {"raw-graph", "top-level-only", "popped", "left-normalized"};
+const char *PROFILE_NAME[] = {"raw-graph", "top-level-only", "popped", "left-normalized", "decomposed"};
 const char *PROFILE_LINES[] = {
 	"",
 	"##INFO=<ID=ORIGIN,Number=1,Type=String,Description=\"Raw record id\">\n"
@@ -52,7 +52,20 @@ const char *PROFILE_LINES[] = {
 	"##INFO=<ID=RAW_POS,Number=1,Type=Integer,Description=\"Raw POS before profile rewrite\">\n"
 	"##INFO=<ID=RAW_REF,Number=1,Type=String,Description=\"Raw REF before profile rewrite\">\n"
 	"##INFO=<ID=RAW_ALT,Number=A,Type=String,Description=\"Raw ALT before profile rewrite\">\n",
+	// "Decomposed calls" (a row has one ALT)
+	"##INFO=<ID=ORIGIN,Number=1,Type=String,Description=\"Raw record id\">\n"
+	"##INFO=<ID=RAW_ALT_INDEX,Number=1,Type=Integer,Description=\"Raw ALT index\">\n"
+	"##INFO=<ID=PROFILE,Number=1,Type=String,Description=\"Downstream profile name\">\n"
+	"##INFO=<ID=DECOMPOSED,Number=1,Type=String,Description=\"Record came from allele decomposition\">\n"
+	"##INFO=<ID=PASSTHROUGH,Number=1,Type=String,Description=\"Record was kept because policy forbids decomposition\">\n"
+	"##INFO=<ID=PASS_THROUGH_REASON,Number=1,Type=String,Description=\"Reason pass-through was selected\">\n"
+	"##INFO=<ID=RAW_POS,Number=1,Type=Integer,Description=\"Raw POS before profile rewrite\">\n"
+	"##INFO=<ID=RAW_REF,Number=1,Type=String,Description=\"Raw REF before profile rewrite\">\n"
+	"##INFO=<ID=RAW_ALT,Number=1,Type=String,Description=\"Raw ALT before profile rewrite\">\n"
+	"##INFO=<ID=SUBR_ORIGIN,Number=1,Type=String,Description=\"Raw SUBR semantics were preserved\">\n",
 };
+const char *ROW_KIND_NAME[] = {"raw", "snp", "ins", "del", "passthrough"};
+const char *ROW_REASON_NAME[] = {"", "max_allele_length", "contig_start", "empty_allele", "equals_ref", "subr_inversion_preservation"};
 
 // (sample, hap) of a path name: `sample#hap#rest` with an all-digit hap, any other name a sample of its own with hap -1
 std::pair<std::string, long long> pansn(const std::string &n)
@@ -236,7 +249,7 @@ char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu
 		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len)
 try {
 	if (!c || !sites || !names || !path_name || !len || c->n_slots != names->refs.n_slots || c->n_refs != names->refs.n_refs ||
-	    profile > POVU_HIP_PROFILE_LEFT_NORMALIZED)
+	    profile > POVU_HIP_PROFILE_DECOMPOSED)
 		return nullptr;
 	// the fields of "Nested calls", absent (NULL) for the entry of before and where a hand-made record leaves them out
 	const uint32_t *level = nested_fields ? c->level : nullptr, *parent_query = nested_fields ? c->parent_query : nullptr;
@@ -244,9 +257,13 @@ try {
 	const bool nested = nested_fields && c->nested;
 	// the fields of "Left-normalised calls", read under that profile alone (absent: no record was changed)
 	const bool normalized = nested_fields && profile == POVU_HIP_PROFILE_LEFT_NORMALIZED && c->raw_pos && c->norm_block;
-	const uint64_t n = c->n_records, S = c->n_slots;
+	// the rows of "Decomposed calls", read under that profile alone (absent: the raw records are written)
+	const bool rows = nested_fields && profile == POVU_HIP_PROFILE_DECOMPOSED && c->row_record && c->row_alt && c->row_kind && c->row_reason &&
+			  c->row_index && c->row_pos && c->row_ref_start && c->row_ref_len && c->row_alt_start && c->row_alt_len && c->row_lead &&
+			  c->row_ac && c->row_an && c->row_ns;
+	const uint64_t n_records = c->n_records, n = rows ? c->n_rows : n_records, S = c->n_slots;
 	const uint32_t P = names->n_paths, n_samples = names->refs.n_samples;
-	for (uint64_t i = 0; i < n; i++) {
+	for (uint64_t i = 0; i < n_records; i++) {
 		const bool subr = c->flags[i] & POVU_HIP_CALL_SUBR; // (its query is POVU_HIP_NIL: it belongs to no site)
 		if ((!subr && c->query[i] >= sites->n) || c->path[i] >= P || (subr && (c->n_alleles[i] != 2 || c->ref_allele[i] != 0)))
 			return nullptr;
@@ -256,6 +273,18 @@ try {
 			return nullptr;
 		if (normalized && (c->flags[i] & POVU_HIP_CALL_NORMALIZED) &&
 		    (subr || c->norm_block[i] >= c->n_blocks || c->block_off[c->norm_block[i]] + c->n_alleles[i] > c->n_spelled))
+			return nullptr;
+	}
+	for (uint64_t k = 0; rows && k < n; k++) {
+		const uint64_t i = c->row_record[k];
+		if (i >= n_records || !c->row_alt[k] || c->row_alt[k] >= c->n_alleles[i] || c->row_kind[k] > POVU_HIP_ROW_PASS ||
+		    c->row_reason[k] > POVU_HIP_REASON_SUBR)
+			return nullptr;
+		// its stretches lie inside the record's REF and that ALT
+		const uint32_t ra = c->ref_allele[i], a = c->row_alt[k] - 1 < ra ? c->row_alt[k] - 1 : c->row_alt[k];
+		const uint64_t sr = ref_spelled ? ref_spelled[i] : c->block_off[c->block[i]] + ra, sa = c->block_off[c->block[i]] + a;
+		if (sa >= c->n_spelled || (uint64_t)c->row_ref_start[k] + c->row_ref_len[k] > c->seq_off[sr + 1] - c->seq_off[sr] ||
+		    (uint64_t)c->row_alt_start[k] + c->row_alt_len[k] > c->seq_off[sa + 1] - c->seq_off[sa])
 			return nullptr;
 	}
 	std::vector<uint32_t> slot_first(n_samples + 1, 0); // (the slots of a sample are consecutive)
@@ -300,9 +329,12 @@ try {
 		std::vector<uint64_t> order;
 		std::string label, parent;
 		char num[32];
-		for (uint64_t i = lo; i < hi; i++) {
+		for (uint64_t at = lo; at < hi; at++) {
+			const uint64_t i = rows ? c->row_record[at] : at;
 			if (!keep[c->path[i]])
 				continue;
+			// a row of "Decomposed calls" that is no raw record: one ALT, its own POS, texts and counts, the GT row projected
+			const bool prim_row = rows && c->row_kind[at] != POVU_HIP_ROW_RAW;
 			const uint32_t q = c->query[i], na = c->n_alleles[i], ra = c->ref_allele[i];
 			const uint64_t b = c->block_off[c->block[i]];
 			order.clear();
@@ -327,6 +359,70 @@ try {
 					label[0] = label[first_end - at] = '>';
 			} else {
 				label = site_label(q);
+			}
+			if (prim_row) {
+				const uint32_t k = c->row_alt[at], kind = c->row_kind[at];
+				const bool passed = kind == POVU_HIP_ROW_PASS;
+				const uint64_t sr = order[0], sa = order[k];
+				const char lead = (char)c->row_lead[at];
+				o += path_name[c->path[i]];
+				o += '\t';
+				o += std::to_string(c->row_pos[at]);
+				o += '\t';
+				o += label;
+				if (subr)
+					o += ":subr-passthrough";
+				else
+					o += ":" + std::to_string(k) + ":" + ROW_KIND_NAME[kind] + (passed ? std::string() : std::to_string(c->row_index[at]));
+				o += '\t';
+				if (lead)
+					o += lead;
+				o.append(c->seq + c->seq_off[sr] + c->row_ref_start[at], c->row_ref_len[at]);
+				o += '\t';
+				if (lead)
+					o += lead;
+				o.append(c->seq + c->seq_off[sa] + c->row_alt_start[at], c->row_alt_len[at]);
+				const uint32_t an = c->row_an[at];
+				snprintf(num, sizeof num, "%.1f", an ? (double)c->row_ac[at] / an : 0.0);
+				o += "\t60\tPASS\tAC=" + std::to_string(c->row_ac[at]) + ";AF=" + num + ";AN=" + std::to_string(an) +
+				     ";NS=" + std::to_string(c->row_ns[at]) + ";AT=";
+				o.append(c->at + c->at_off[sr], c->at_off[sr + 1] - c->at_off[sr]);
+				o += ',';
+				o.append(c->at + c->at_off[sa], c->at_off[sa + 1] - c->at_off[sa]);
+				if (passed)
+					o += subr ? ";VARTYPE=SUBR" : (f & POVU_HIP_CALL_INS) ? ";VARTYPE=INS" : (f & POVU_HIP_CALL_DEL) ? ";VARTYPE=DEL" : ";VARTYPE=SUB";
+				else
+					o += kind == POVU_HIP_ROW_SNP ? ";VARTYPE=SUB" : kind == POVU_HIP_ROW_INS ? ";VARTYPE=INS" : ";VARTYPE=DEL";
+				o += passed && (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
+				o += ";ORIGIN=" + label + ";RAW_ALT_INDEX=" + std::to_string(k) + ";PROFILE=decomposed;";
+				o += passed ? std::string("PASSTHROUGH=T;PASS_THROUGH_REASON=") + ROW_REASON_NAME[c->row_reason[at]] : std::string("DECOMPOSED=T");
+				if (subr) {
+					o += ";SUBR_ORIGIN=T";
+				} else {
+					o += ";RAW_POS=" + std::to_string(c->pos[i]) + ";RAW_REF=";
+					o.append(c->seq + c->seq_off[sr], c->seq_off[sr + 1] - c->seq_off[sr]);
+					o += ";RAW_ALT=";
+					o.append(c->seq + c->seq_off[sa], c->seq_off[sa + 1] - c->seq_off[sa]);
+				}
+				o += "\tGT";
+				const uint16_t *grow = c->gt + i * S;
+				for (uint32_t sm = 0; sm < n_samples; sm++) {
+					o += '\t';
+					bool any = false;
+					for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++)
+						any |= grow[sl] == 0 || grow[sl] == k;
+					if (!any) {
+						o += '.';
+						continue;
+					}
+					for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++) {
+						if (sl > slot_first[sm])
+							o += '|';
+						o += grow[sl] == 0 ? "0" : grow[sl] == k ? "1" : ".";
+					}
+				}
+				o += '\n';
+				continue;
 			}
 			const bool has_parent = !subr && parent_query && parent_query[i] != POVU_HIP_NIL;
 			if (has_parent)
@@ -382,7 +478,7 @@ try {
 						o += k == 0 ? ";RAW_REF=" : k == 1 ? ";RAW_ALT=" : ",";
 						o.append(c->seq + c->seq_off[order[k]], c->seq_off[order[k] + 1] - c->seq_off[order[k]]);
 					}
-				} else if (profile != POVU_HIP_PROFILE_RAW_GRAPH && profile != POVU_HIP_PROFILE_LEFT_NORMALIZED) {
+				} else if (profile == POVU_HIP_PROFILE_TOP_LEVEL_ONLY || profile == POVU_HIP_PROFILE_POPPED) {
 					o += ";ORIGIN=" + label;
 					if (rescued)
 						o += ";PARENT=" + (has_parent ? parent : std::string(".")) + ";PROFILE=" + PROFILE_NAME[profile] +

@@ -112,7 +112,15 @@ class _CallsNested(_Calls):
                 # "Left-normalised calls"
                 [("raw_pos", C.POINTER(C.c_uint64))] +
                 [(k, C.POINTER(C.c_uint32)) for k in ("norm_block", "norm_shift", "norm_chop", "norm_trim")] +
-                [(k, C.c_uint64) for k in ("n_normalized", "max_shift", "n_norm_compared")])
+                [(k, C.c_uint64) for k in ("n_normalized", "max_shift", "n_norm_compared")] +
+                # "Decomposed calls"
+                [("n_rows", C.c_uint64), ("row_record", C.POINTER(C.c_uint32)), ("row_alt", C.POINTER(C.c_uint32)),
+                 ("row_kind", C.POINTER(C.c_uint8)), ("row_reason", C.POINTER(C.c_uint8)), ("row_index", C.POINTER(C.c_uint32)),
+                 ("row_pos", C.POINTER(C.c_uint64))] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("row_ref_start", "row_ref_len", "row_alt_start", "row_alt_len")] +
+                [("row_lead", C.POINTER(C.c_uint8))] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("row_ac", "row_an", "row_ns")] +
+                [(k, C.c_uint64) for k in ("n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells")])
 
 
 class _ProfileOpts(C.Structure):
@@ -145,7 +153,11 @@ T_FORCE_TIER2 = 1  # HipDecomposer.traversals: every scan through the wave-per-s
 T_INVERSIONS = 2  # HipDecomposer.call: inversion (SUBR) records too (INTEGRATION.md "Inversion calls")
 T_NESTED = 4  # HipDecomposer.call: alleles modulo enclosed sites, levels and parents by geometry (INTEGRATION.md "Nested calls")
 TRAV_LONG, TRAV_STRAY, TRAV_OPEN = 1, 2, 4  # status bits of a query
-PROFILES = {"raw-graph": 0, "top-level-only": 1, "popped": 2, "left-normalized": 3}  # HipDecomposer.call(profile=...)
+PROFILES = {"raw-graph": 0, "top-level-only": 1, "popped": 2, "left-normalized": 3, "decomposed": 4}  # HipDecomposer.call(profile=...)
+PRIM_MAX_LENGTH = 512  # `decomposed` profile: the longest allele that is aligned, and the most max_allele_length may ask for
+# kind of a row of the `decomposed` profile (Calls.row_kind) and why a ROW_PASS row was kept whole (Calls.row_reason)
+ROW_RAW, ROW_SNP, ROW_INS, ROW_DEL, ROW_PASS = 0, 1, 2, 3, 4
+REASON_NONE, REASON_MAX_ALLELE_LENGTH, REASON_CONTIG_START, REASON_EMPTY_ALLELE, REASON_EQUALS_REF, REASON_SUBR = 0, 1, 2, 3, 4, 5
 
 _lib = None
 
@@ -766,6 +778,16 @@ class Calls:
             setattr(self, k, _view(getattr(c, k), n, np.uint32))
         self.n_normalized, self.max_shift = int(c.n_normalized), int(c.max_shift)
         self.n_norm_compared = int(c.n_norm_compared)
+        # "Decomposed calls": the rows (none outside the profile) and the counters
+        m = self.n_rows = int(c.n_rows)
+        for k in ("row_record", "row_alt", "row_index", "row_ref_start", "row_ref_len", "row_alt_start", "row_alt_len", "row_ac",
+                  "row_an", "row_ns"):
+            setattr(self, k, _view(getattr(c, k), m, np.uint32))
+        for k in ("row_kind", "row_reason", "row_lead"):
+            setattr(self, k, _view(getattr(c, k), m, np.uint8))
+        self.row_pos = _view(c.row_pos, m, np.uint64)
+        self.n_decomposed_alts, self.n_passthrough_alts = int(c.n_decomposed_alts), int(c.n_passthrough_alts)
+        self.n_prim_tier2, self.n_prim_cells = int(c.n_prim_tier2), int(c.n_prim_cells)
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -982,7 +1004,9 @@ class HipDecomposer:
         ref_spelled, flags & CALL_COLLAPSED, the counters).  profile: None or one of PROFILES; "top-level-only" and "popped"
         imply T_NESTED and keep what INTEGRATION.md says ("popped": max_level, max_ref_length, max_allele_length, 0 = no
         limit); "left-normalized" implies nothing, keeps every record and left-normalises it ("Left-normalised calls":
-        Calls.raw_pos, norm_block, norm_shift, norm_chop, norm_trim, flags & CALL_NORMALIZED, the counters)."""
+        Calls.raw_pos, norm_block, norm_shift, norm_chop, norm_trim, flags & CALL_NORMALIZED, the counters); "decomposed"
+        ("Decomposed calls": Calls.n_rows, row_*, the counters) is defined and written by Calls.vcf_text, but the device step
+        that makes its rows is not in this build: povu_hip_call_profile refuses it as an unknown profile."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names

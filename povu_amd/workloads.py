@@ -760,3 +760,90 @@ def tandem_haplotypes(n_units: int, seed: int, n: int, max_copies: int = 40, max
             rev += [s[1] for s in steps] + ([0] if t else [])
         pieces.append((ids + [last], rev + [0]))
     return _paths([f"hap{h}#1#chr1" for h in range(n)], pieces)
+
+
+def _complex_plan(n_units: int, seed: int):
+    """The units of complex_alleles: (sequence of every segment, ids 1.. in path order; per unit the id of its flank and the
+    ids of its alleles' segments, 0 for an allele without a base (the link that skips the bubble); the closing segment)."""
+    rng = np.random.default_rng([seed, 77])
+    seqs, units = [], []
+
+    def seg(text):
+        seqs.append(text)
+        return len(seqs)
+
+    def draw(n, two):
+        return "".join(two[int(k)] if rng.random() < 0.7 else "ACGT"[int(rng.integers(0, 4))] for k in rng.integers(0, 2, size=n))
+    for u in range(n_units):
+        two = ["AC", "AT", "CG", "GT"][int(rng.integers(0, 4))]
+        # unit 0 begins the contig (an empty flank: its record has POS 1) with alleles that differ in a leading run; one unit in
+        # sixteen has an empty flank too, so that its skipped allele is an empty text
+        bare = u == 0 or rng.random() < 1 / 16
+        flank = seg("" if bare else draw(int(rng.integers(2, 7)), "ACGT"[:2]) + "ACGT"[int(rng.integers(0, 4))])
+        if u == 0:
+            alleles = ["AAC", "AC", "AAAC"]
+        else:
+            ref = draw(int(rng.integers(1, 11)), two)
+            alleles = [ref]
+            for _ in range(int(rng.integers(2, 5))):
+                b = list(ref)
+                for _ in range(int(rng.integers(1, 5))):
+                    r, p, k = rng.random(), int(rng.integers(0, len(b) + 1)), int(rng.integers(1, 4))
+                    if r < 0.4 and p < len(b):
+                        b[p] = draw(1, two)
+                    elif r < 0.7:
+                        b[p:p] = list(draw(k, two))
+                    else:
+                        del b[p:p + k]
+                alleles.append("".join(b))
+            if bare:
+                alleles[-1] = ""  # (behind an empty flank the skipped allele is an empty text)
+            elif rng.random() < 0.1:
+                alleles[-1] = ref.lower()  # (REF's text after upper-casing)
+            if rng.random() < 0.1:
+                alleles = [a.lower() if k % 2 else a for k, a in enumerate(alleles)]
+        ids, seen_empty = [], False
+        for a in alleles:
+            if a:
+                ids.append(seg(a))
+            elif not seen_empty:
+                ids.append(0)
+                seen_empty = True
+        units.append((flank, ids))
+    return seqs, units, seg(draw(4, "AC"))
+
+
+def complex_alleles(n_units: int, seed: int):
+    """Bubbles of several small edits ("Decomposed calls"): (graph, sequence of every segment).  A unit is a flank of 3 to 7
+    bases and a bubble of parallel segments: a REF of 1 to 10 bases over a two-letter-biased alphabet and two to four ALTs
+    derived from it by one to four random substitutions, insertions and deletions of one to three bases (an allele that lost
+    every base is the link that skips the bubble; a tenth of the units carry REF's text once more in lower case).  Unit 0
+    has an empty flank and alleles that differ in a leading run, one later unit in sixteen an empty flank and a skipped allele.  The units are
+    joined end to end and closed by one more segment; ids 1.. in path order.  complex_haplotypes draws the paths."""
+    seqs, units, last = _complex_plan(n_units, seed)
+    v1, s1, v2, s2 = [], [], [], []
+    for u, (flank, ids) in enumerate(units):
+        z = units[u + 1][0] if u + 1 < n_units else last
+        for x in ids:
+            if x:
+                v1.append(flank - 1), s1.append(R), v2.append(x - 1), s2.append(L)
+                v1.append(x - 1), s1.append(R), v2.append(z - 1), s2.append(L)
+            else:
+                v1.append(flank - 1), s1.append(R), v2.append(z - 1), s2.append(L)
+    return _mk(np.arange(1, len(seqs) + 1), v1, s1, v2, s2), seqs
+
+
+def complex_haplotypes(n_units: int, seed: int, n: int) -> Paths:
+    """`n` haplotypes of complex_alleles(n_units, seed): each takes the first allele of a bubble with probability 1/2, else
+    one of the others; PanSN names, one sample a haplotype (`hap<k>#1#chr1`)."""
+    _, units, last = _complex_plan(n_units, seed)
+    rng = np.random.default_rng([seed, n, 78])
+    pieces = []
+    for _ in range(n):
+        ids = []
+        for flank, al in units:
+            k = 0 if rng.random() < 0.5 else int(rng.integers(1, len(al)))
+            ids += [flank] + ([al[k]] if al[k] else [])
+        ids.append(last)
+        pieces.append((ids, [0] * len(ids)))
+    return _paths([f"hap{h}#1#chr1" for h in range(n)], pieces)
