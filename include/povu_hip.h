@@ -534,8 +534,6 @@ povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, co
  * as far left as the optimum allows) and written as its primitives, one row each (povu_hip_calls.n_rows, row_*).  Does not
  * imply POVU_HIP_T_NESTED (may be combined with it and with _T_INVERSIONS); max_level and max_ref_length are ignored,
  * max_allele_length is the longest text that is aligned: 0 means POVU_HIP_PRIM_MAX_LENGTH, more than that is refused */
-/* (povu_hip_calls_vcf_profile writes such rows; the device step that makes them is not in this build, and
- * povu_hip_call_profile refuses the profile as unknown) */
 #define POVU_HIP_PROFILE_DECOMPOSED 4u
 #define POVU_HIP_PRIM_MAX_LENGTH 512u
 #define POVU_HIP_ROW_RAW 0u /* the record as the raw call writes it: its one ALT is one primitive that spells POS, REF and ALT */

@@ -131,6 +131,41 @@ struct CallView {
 	const uint64_t *xilen, *xatl, *ref_len, *max_len, *raw_pos, *pos;
 };
 
+// ---- a base of a step and of a reference path
+__device__ __forceinline__ uint64_t path_step_len(const PathsView &P, uint32_t x) { return P.seq_off[(x >> 1) + 1] - P.seq_off[x >> 1]; }
+// base `within` of step x as the step spells it (0 for a byte that is no nucleotide code on a '<' step)
+__device__ __forceinline__ uint8_t path_step_base(const PathsView &P, uint32_t x, uint64_t within)
+{
+	const uint64_t b0 = P.seq_off[x >> 1], n = P.seq_off[(x >> 1) + 1] - b0;
+	const uint8_t c = (uint8_t)P.seq[(x & 1u) ? b0 + n - 1 - within : b0 + within];
+	return (x & 1u) ? comp(c) : c;
+}
+// reference path r: its slice of roff (n steps from reference index b) and its first path word
+struct RefPathSlice {
+	uint64_t b, n, gs;
+};
+__device__ __forceinline__ RefPathSlice ref_path_slice(const RefView &R, const PathsView &P, uint32_t r)
+{
+	return {R.ref_base[r], R.ref_base[r + 1] - R.ref_base[r], P.path_off[R.ref_path[r]]};
+}
+// base ci (0-based) of the reference path as the path spells it; *seg its segment.  ci is below the path's length
+__device__ __forceinline__ uint8_t ref_path_base(const PathsView &P, const uint64_t *__restrict__ roff, const RefPathSlice &R, uint64_t ci, uint32_t *seg)
+{
+	const uint64_t *__restrict__ off = roff + R.b;
+	const uint64_t target = off[0] + ci;
+	uint64_t lo = 0, hi = R.n - 1; // the first step that ends behind the base (steps of no base are passed over)
+	while (lo < hi) {
+		const uint64_t mid = (lo + hi) >> 1;
+		if (off[mid + 1] > target)
+			hi = mid;
+		else
+			lo = mid + 1;
+	}
+	const uint32_t x = P.steps[R.gs + lo];
+	*seg = x >> 1;
+	return path_step_base(P, x, target - off[lo]);
+}
+
 // inner bases and AT width of a traversal: its steps but the first and the last
 struct InnerSize {
 	uint64_t bases, at;

@@ -24,6 +24,7 @@
 #include "call_common.hpp"
 #include "nest_kernels.hpp"
 #include "norm_kernels.hpp"
+#include "prim_kernels.hpp"
 
 namespace povu_hip
 {
@@ -485,6 +486,10 @@ struct CallsOwner {
 		norm_trim;
 	PinnedVec<uint64_t> pos, ac_off, block_off, seq_off, at_off, ref_spelled, raw_pos;
 	PinnedVec<uint8_t> flags;
+	// the rows of the `decomposed` profile
+	PinnedVec<uint32_t> row_record, row_alt, row_index, row_ref_start, row_ref_len, row_alt_start, row_alt_len, row_ac, row_an, row_ns;
+	PinnedVec<uint8_t> row_kind, row_reason, row_lead;
+	PinnedVec<uint64_t> row_pos;
 	PinnedVec<uint16_t> gt;
 	PinnedVec<char> seq, at;
 	std::vector<uint64_t> contig_len;
@@ -499,7 +504,8 @@ struct CallInputs {
 	const uint32_t *slot_of_path;
 	const povu_hip_trav_opts *opts;
 	uint32_t n, P, nR, S, NS, n_trees = 0;
-	bool inversions, nested, normalized;
+	bool inversions, nested, normalized, decomposed;
+	uint32_t prim_cap = 0; // decomposed: the longest text that is aligned
 	povu_hip_call_profile_opts prof; // (raw-graph without a profile)
 	std::vector<uint32_t> ref_of_path, slot_first, qa, qz; // reference number of every path (NO_QUERY: none), first slot of every sample, the queries
 	std::vector<uint8_t> qor;
@@ -572,10 +578,17 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 	const uint32_t n = in.n, P = in.P, nR = in.nR, S = in.S, NS = in.NS;
 	in.inversions = opts && (opts->flags & POVU_HIP_T_INVERSIONS);
 	in.prof = profile ? *profile : povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
-	if (in.prof.profile > POVU_HIP_PROFILE_LEFT_NORMALIZED)
+	if (in.prof.profile > POVU_HIP_PROFILE_DECOMPOSED)
 		throw HipError("unknown profile " + std::to_string(in.prof.profile));
 	in.normalized = in.prof.profile == POVU_HIP_PROFILE_LEFT_NORMALIZED; // (keeps every record, ignores the limits, implies nothing)
-	if (in.normalized)
+	in.decomposed = in.prof.profile == POVU_HIP_PROFILE_DECOMPOSED;	     // (the same; max_allele_length is the cap of the aligner)
+	if (in.decomposed) {
+		if (in.prof.max_allele_length > POVU_HIP_PRIM_MAX_LENGTH)
+			throw HipError("max_allele_length " + std::to_string(in.prof.max_allele_length) + " is above the ceiling " +
+				       std::to_string(POVU_HIP_PRIM_MAX_LENGTH) + " of the decomposed profile");
+		in.prim_cap = in.prof.max_allele_length ? (uint32_t)in.prof.max_allele_length : POVU_HIP_PRIM_MAX_LENGTH;
+	}
+	if (in.normalized || in.decomposed)
 		in.prof = povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 	in.nested = (opts && (opts->flags & POVU_HIP_T_NESTED)) || in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH;
 	if (n >= 0x7FFFFFFFu)
@@ -953,8 +966,24 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const Ca
 		throw HipError("segment " + std::to_string(read_back(ctx->g.vid + hbad, s)) + " holds a byte that is no nucleotide code (ACGTN, lower case, IUPAC)");
 }
 
+// the rows of the `decomposed` profile: every (REF, ALT) of the records as they are written, aligned and split (prim_kernels.hip)
+PrimRows primitive_rows(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallRecs &r, const CallSpelled &sp)
+{
+	const InvRows &o = r.rows;
+	PrimIn p{};
+	p.nrec = r.nrec, p.n_pairs = r.n_ac;
+	p.ac_off = r.ac_off, p.pos = o.o_pos, p.ref_spelled = r.ref_spelled;
+	p.path = o.o_path, p.ref_allele = o.o_ref, p.block = o.o_block, p.flags = o.o_flags, p.gt = o.gt;
+	p.block_off = r.block_off, p.sp_off = sp.sp_off, p.seq = sp.o_seq;
+	p.paths = w.v.paths, p.ref = w.v.ref, p.slots = w.slots;
+	p.cap = in.prim_cap;
+	p.force_tier2 = in.opts && (in.opts->flags & POVU_HIP_T_FORCE_TIER2);
+	p.ref_bases = sp.h_roff.back() - sp.h_roff.front();
+	return prim_rows(ctx, p);
+}
+
 povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, const CallRecs &r, const CallSpelled &sp,
-			      CallTimer &timer)
+			      const PrimRows &pr, CallTimer &timer)
 {
 	const uint32_t nrec = r.nrec, nb = r.L.nb, nR = in.nR, S = in.S;
 	const uint64_t nsp = r.L.nsp;
@@ -1001,6 +1030,23 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	give_norm(o->norm_shift, v.norm_shift, nw.o_shift, all(0u));
 	give_norm(o->norm_chop, v.norm_chop, nw.o_chop, all(0u));
 	give_norm(o->norm_trim, v.norm_trim, nw.o_trim, all(0u));
+	if (in.decomposed) { // (outside the profile: no rows, the arrays NULL)
+		const size_t m = (size_t)pr.n_rows;
+		give(o->row_record, v.row_record, pr.record, m);
+		give(o->row_alt, v.row_alt, pr.alt, m);
+		give(o->row_kind, v.row_kind, pr.kind, m);
+		give(o->row_reason, v.row_reason, pr.reason, m);
+		give(o->row_index, v.row_index, pr.index, m);
+		give(o->row_pos, v.row_pos, pr.pos, m);
+		give(o->row_ref_start, v.row_ref_start, pr.ref_start, m);
+		give(o->row_ref_len, v.row_ref_len, pr.ref_len, m);
+		give(o->row_alt_start, v.row_alt_start, pr.alt_start, m);
+		give(o->row_alt_len, v.row_alt_len, pr.alt_len, m);
+		give(o->row_lead, v.row_lead, pr.lead, m);
+		give(o->row_ac, v.row_ac, pr.ac, m);
+		give(o->row_an, v.row_an, pr.an, m);
+		give(o->row_ns, v.row_ns, pr.ns, m);
+	}
 	v.device_ms = timer.stop(ctx->stream);
 	for (const auto &fill : defaults)
 		fill();
@@ -1019,6 +1065,8 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	v.nested = in.nested ? 1 : 0;
 	v.n_enclosed = w.nr.n_enclosed, v.n_collapsed_sites = w.n_collapsed, v.n_popped = w.nr.n_popped, v.n_rescued = w.nr.n_rescued;
 	v.n_normalized = w.nm.n_changed, v.max_shift = w.nm.max_shift, v.n_norm_compared = w.nm.n_compared;
+	v.n_rows = pr.n_rows;
+	v.n_decomposed_alts = pr.n_decomposed, v.n_passthrough_alts = pr.n_passthrough, v.n_prim_tier2 = pr.n_tier2, v.n_prim_cells = pr.n_cells;
 	CallsOwner *raw = o.release();
 	return &raw->view;
 }
@@ -1054,7 +1102,8 @@ extern "C" povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_h
 		record_arrays(ctx, in, w, inv, r);
 		CallSpelled sp;
 		spelling(ctx, in, w, inv, r, sp);
-		return calls_to_host(ctx, in, w, inv, r, sp, timer);
+		const PrimRows pr = in.decomposed ? primitive_rows(ctx, in, w, r, sp) : PrimRows{};
+		return calls_to_host(ctx, in, w, inv, r, sp, pr, timer);
 	});
 }
 

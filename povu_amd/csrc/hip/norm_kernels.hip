@@ -23,14 +23,6 @@ namespace povu_hip
 namespace
 {
 
-__device__ __forceinline__ uint64_t nm_seg_len(const PathsView &P, uint32_t x) { return P.seq_off[(x >> 1) + 1] - P.seq_off[x >> 1]; }
-// base `within` of step x as the step spells it (0 for a byte that is no nucleotide code on a '<' step)
-__device__ __forceinline__ uint8_t nm_step_base(const PathsView &P, uint32_t x, uint64_t within)
-{
-	const uint64_t b0 = P.seq_off[x >> 1], n = P.seq_off[(x >> 1) + 1] - b0;
-	const uint8_t c = (uint8_t)P.seq[(x & 1u) ? b0 + n - 1 - within : b0 + within];
-	return (x & 1u) ? comp(c) : c;
-}
 __device__ __forceinline__ uint8_t nm_upper(uint8_t c) { return c >= 'a' && c <= 'z' ? (uint8_t)(c - 32) : c; }
 
 // where a walk over an allele's inner steps stands: a step and a count of bases (what they mean: each walk's own)
@@ -46,16 +38,16 @@ __device__ __forceinline__ uint8_t nm_back_chunk(const PathsView &P, const Writt
 	uint8_t c = 0;
 	while (cur.k > 0) {
 		const uint32_t x = a.inner_step(P.steps, cur.k - 1);
-		const uint64_t n = nm_seg_len(P, x);
+		const uint64_t n = path_step_len(P, x);
 		if (d >= cur.cum && d < cur.cum + n)
-			c = nm_step_base(P, x, n - 1 - (d - cur.cum));
+			c = path_step_base(P, x, n - 1 - (d - cur.cum));
 		if (cur.cum + n > c0 + 64)
 			break; // (the step reaches into the next chunk)
 		cur.cum += n;
 		cur.k--;
 	}
 	if (cur.k == 0 && a.anchor_base && d + 1 == alen)
-		c = nm_step_base(P, a.anchor, nm_seg_len(P, a.anchor) - 1);
+		c = path_step_base(P, a.anchor, path_step_len(P, a.anchor) - 1);
 	return c;
 }
 // ... at indices x0 .. x0 + 63 from the allele's first base: `k` the next inner step, `cum` the index of its first base
@@ -64,12 +56,12 @@ __device__ __forceinline__ uint8_t nm_fwd_chunk(const PathsView &P, const Writte
 	const uint64_t idx = x0 + lane;
 	uint8_t c = 0;
 	if (a.anchor_base && idx == 0)
-		c = nm_step_base(P, a.anchor, nm_seg_len(P, a.anchor) - 1);
+		c = path_step_base(P, a.anchor, path_step_len(P, a.anchor) - 1);
 	while (cur.k < a.inner_steps()) {
 		const uint32_t x = a.inner_step(P.steps, cur.k);
-		const uint64_t n = nm_seg_len(P, x);
+		const uint64_t n = path_step_len(P, x);
 		if (idx >= cur.cum && idx < cur.cum + n)
-			c = nm_step_base(P, x, idx - cur.cum);
+			c = path_step_base(P, x, idx - cur.cum);
 		if (cur.cum + n > x0 + 64)
 			break;
 		cur.cum += n;
@@ -78,33 +70,11 @@ __device__ __forceinline__ uint8_t nm_fwd_chunk(const PathsView &P, const Writte
 	return c;
 }
 
-// the reference path of a record: its slice of roff (n steps from reference index b) and its first path word
-struct NmRef {
-	uint64_t b, n, gs;
-};
-__device__ __forceinline__ NmRef nm_ref(const CallView &V, uint32_t j)
+// the reference path of record j
+__device__ __forceinline__ RefPathSlice nm_ref(const CallView &V, uint32_t j)
 {
-	const uint32_t r = V.ref.ref_of_path[V.trav.op[V.rlist[j]]];
-	return {V.ref.ref_base[r], V.ref.ref_base[r + 1] - V.ref.ref_base[r], V.paths.path_off[V.ref.ref_path[r]]};
+	return ref_path_slice(V.ref, V.paths, V.ref.ref_of_path[V.trav.op[V.rlist[j]]]);
 }
-// base ci (0-based) of the reference path as the path spells it; *seg its segment.  ci is below the path's length
-__device__ __forceinline__ uint8_t nm_ctx_base(const PathsView &P, const uint64_t *__restrict__ roff, const NmRef &R, uint64_t ci, uint32_t *seg)
-{
-	const uint64_t *__restrict__ off = roff + R.b;
-	const uint64_t target = off[0] + ci;
-	uint64_t lo = 0, hi = R.n - 1; // the first step that ends behind the base (steps of no base are passed over)
-	while (lo < hi) {
-		const uint64_t mid = (lo + hi) >> 1;
-		if (off[mid + 1] > target)
-			hi = mid;
-		else
-			lo = mid + 1;
-	}
-	const uint32_t x = P.steps[R.gs + lo];
-	*seg = x >> 1;
-	return nm_step_base(P, x, target - off[lo]);
-}
-
 // ALTs of every record (the tasks of k_nm_chop)
 __global__ void k_nm_tasks(CallView V, uint64_t *__restrict__ cnt)
 {
@@ -129,7 +99,7 @@ __global__ __launch_bounds__(Q_TPB) void k_nm_chop(uint64_t ntask, CallView V, c
 		const uint64_t la = A.text_len(), lb = B.text_len();
 		if (!la || !lb)
 			continue; // (an empty text: the record stays as it is)
-		const NmRef R = nm_ref(V, j);
+		const RefPathSlice R = nm_ref(V, j);
 		const uint64_t pos = V.raw_pos[j], ta = pos - 1 + la, tb = pos - 1 + lb;
 		// behind `end` nothing is compared: alleles of one length read the same context base from there on, else the shorter
 		// string has ended (and that is a difference)
@@ -145,9 +115,9 @@ __global__ __launch_bounds__(Q_TPB) void k_nm_chop(uint64_t ntask, CallView V, c
 			if (c0 < lb)
 				y = nm_back_chunk(P, B, lb, cb, c0, lane);
 			if (d < end && d >= la && d < ta)
-				x = nm_ctx_base(P, roff, R, pos - 2 - (d - la), &seg);
+				x = ref_path_base(P, roff, R, pos - 2 - (d - la), &seg);
 			if (d < end && d >= lb && d < tb)
-				y = nm_ctx_base(P, roff, R, pos - 2 - (d - lb), &seg);
+				y = ref_path_base(P, roff, R, pos - 2 - (d - lb), &seg);
 			const bool differs = d < end && (d >= ta || d >= tb || nm_upper(x) != nm_upper(y));
 			const unsigned long long mask = __ballot(differs);
 			if (mask) {
@@ -282,13 +252,13 @@ __global__ __launch_bounds__(Q_TPB) void k_nm_emit(BlockLayout::Family F, CallVi
 		uint32_t i;
 		const uint32_t j = nm_spelled(x, F, block_off, list, &i);
 		const WrittenAllele A = allele_of_record(V, j, i);
-		const NmRef R = nm_ref(V, j);
+		const RefPathSlice R = nm_ref(V, j);
 		const uint64_t pos = V.raw_pos[j], la = A.text_len(), r = chop[j], s = shift[j], u = trim[j], w = s_off[x];
 		// (u > 0 only where s == 0: the context bases are never trimmed; an allele shorter than the chop ends inside them)
 		const uint64_t nctx = la < r ? s + la - r : s;
 		for (uint64_t z = lane; z < nctx; z += 64) {
 			uint32_t seg;
-			const uint8_t c = nm_ctx_base(P, roff, R, pos - 1 - s + z, &seg);
+			const uint8_t c = ref_path_base(P, roff, R, pos - 1 - s + z, &seg);
 			if (!comp(c))
 				atomicMin(bad, (unsigned long long)seg);
 			o_seq[w + z] = (char)c;

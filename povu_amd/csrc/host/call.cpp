@@ -86,8 +86,10 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 				c.prof.profile = POVU_HIP_PROFILE_POPPED;
 			else if (v == "left-normalized")
 				c.prof.profile = POVU_HIP_PROFILE_LEFT_NORMALIZED;
+			else if (v == "decomposed")
+				c.prof.profile = POVU_HIP_PROFILE_DECOMPOSED;
 			else
-				throw std::runtime_error("Flag '--profile' expects raw-graph, top-level-only, popped or left-normalized, not " + v);
+				throw std::runtime_error("Flag '--profile' expects raw-graph, top-level-only, popped, left-normalized or decomposed, not " + v);
 		} else if (number(i, "--max-level", n64)) {
 			if (n64 > 0x7FFFFFFFull)
 				throw std::runtime_error("Flag '--max-level' is too large");

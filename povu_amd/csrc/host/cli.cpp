@@ -69,9 +69,13 @@ static void usage(std::ostream &os)
 	      "        --profile=[raw-graph|top-level-only|popped|left-normalized]\n"
 	      "                                          which records to keep (top-level-only and popped imply --nested); left-normalized\n"
 	      "                                          keeps all and moves every indel to the left end of its repeat [default: raw-graph]\n"
+	      "        --profile=decomposed              keeps all and writes every (REF, ALT) as the SNPs, insertions and deletions of\n"
+	      "                                          its alignment (INTEGRATION.md \"Decomposed calls\")\n"
 	      "        --max-level=[n]                   popped: the deepest level kept without rescue [default: 0]\n"
 	      "        --max-ref-length=[n], --max-allele-length=[n]\n"
 	      "                                          popped: a record with a longer REF / allele is big (0: no limit) [default: 0]\n"
+	      "                                          decomposed: --max-allele-length is the longest allele that is aligned, a longer\n"
+	      "                                          one is kept whole (0: 512, the most) [default: 0]\n"
 	      "        -c, -q                            accepted and ignored (no streaming here)\n";
 }
 

@@ -1005,8 +1005,9 @@ class HipDecomposer:
         imply T_NESTED and keep what INTEGRATION.md says ("popped": max_level, max_ref_length, max_allele_length, 0 = no
         limit); "left-normalized" implies nothing, keeps every record and left-normalises it ("Left-normalised calls":
         Calls.raw_pos, norm_block, norm_shift, norm_chop, norm_trim, flags & CALL_NORMALIZED, the counters); "decomposed"
-        ("Decomposed calls": Calls.n_rows, row_*, the counters) is defined and written by Calls.vcf_text, but the device step
-        that makes its rows is not in this build: povu_hip_call_profile refuses it as an unknown profile."""
+        implies nothing either, keeps every record and writes every (REF, ALT) as the primitives of its alignment ("Decomposed
+        calls": Calls.n_rows, row_*, the counters; max_allele_length is the longest text that is aligned, 0 = PRIM_MAX_LENGTH,
+        more is refused; T_FORCE_TIER2 also sends every aligned pair through the striped kernel)."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names
