@@ -689,11 +689,41 @@ int povu_hip_debug_edge_ids(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, 
 int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t *tree_vtx, uint32_t *cls,
 			 uint32_t *next_seen);
 
-/* unit-test hook for the device-wide scans of the path: exclusive scan of in[0..n) (op 0 = sum mod 2^32,
- * 1 = running maximum) and, when in2 is given, an independent sum scan of in2[0..n2) in the same launch;
- * op 2 = sum mod 2^64 of n 64-bit values, in and out holding each as a pair of words, low word first (in2 unused) */
+/* ---- unit-test hooks for the device-wide primitives (primitives.hip; tests/test_gpu_primitives.py) ----
+ * Each call works in device memory of its own and uses nothing of the context but its stream.  The primitive's scratch
+ * has exactly the size the primitive asks for and is filled with a non-zero byte before the call; every device output
+ * lies between two guard bands (at least 64 words of a fixed pattern each) that are read back after the call.
+ * 0 = ok, 1 = bad arguments, 2 = device error, 5 = the primitive changed a guard byte. */
+/* exclusive scan of in[0..n) (op 0 = sum mod 2^32, 1 = running maximum) and, when in2 is given, an independent sum scan
+ * of in2[0..n2) in the same launch; op 2 = sum mod 2^64 of n 64-bit values, in and out holding each as a pair of
+ * words, low word first (in2 unused).
+ * op 3: in / in2 hold n / n2 BYTES, one element each (scan_exclusive_u8; in2 optional, either length may be 0);
+ * op 4: sums of in[i] - in2[i], both of n words (scan_exclusive_diff_u32; out2 unused);
+ * op 5: running xor of in and of in2, both of n words (scan_exclusive_xor_u32_pair);
+ * op 6: running xor of n 16-byte words (scan_exclusive_xor_u128; in2 unused).  With POVU_HIP_SCAN_N_DEV or-ed on, n2 is
+ *       placed in a device word and passed as n_dev: only the first min(n2 + 1, n) words exist and are written, and the
+ *       rest of the output counts as a guard band.
+ * POVU_HIP_SCAN_IN_PLACE, or-ed onto op 0, 1 or 2 (without in2): the output IS the input on the device. */
+#define POVU_HIP_SCAN_SUM 0
+#define POVU_HIP_SCAN_MAX 1
+#define POVU_HIP_SCAN_U64 2
+#define POVU_HIP_SCAN_U8 3
+#define POVU_HIP_SCAN_DIFF 4
+#define POVU_HIP_SCAN_XOR_PAIR 5
+#define POVU_HIP_SCAN_XOR_U128 6
+#define POVU_HIP_SCAN_IN_PLACE 0x100
+#define POVU_HIP_SCAN_N_DEV 0x200
 int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,
 			uint32_t *out2, size_t n2);
+/* sort_pairs_u32: the n pairs (keys[i], vals[i]) in the stable order of the low `bits` bits of the keys (0 counts as 1);
+ * inputs and outputs are distinct device buffers */
+int povu_hip_debug_sort(povu_hip_ctx *ctx, const uint32_t *keys, const uint32_t *vals, size_t n, unsigned bits,
+			uint32_t *keys_out, uint32_t *vals_out);
+/* compact_flagged_u8: the indices of the non-zero bytes of flags[0..n), ascending, into out (room for n), their number
+ * into *count; the device output behind the first *count indices counts as a guard band */
+int povu_hip_debug_compact(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, uint32_t *out, uint32_t *count);
+/* totals_u32: tot[0] = the 64-bit sum of a[0..n), tot[1] = that of b[0..n) (0 when b is NULL) */
+int povu_hip_debug_totals(povu_hip_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t n, uint64_t tot[2]);
 /* unit-test hook for the list ranking of the tree stage: suffix sums (inclusive, mod 2^32) along the lists next[0..n)
  * (NIL = end of a list; heads[0..nh) = their first elements, NIL entries allowed) -- mode 0: ra of the 0/1 weights w;
  * mode 1: the pre-order events' two sums (element x enters when x % 3 == 0, see tree_kernels.hip), ra and rb.  bits =

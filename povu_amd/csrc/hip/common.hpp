@@ -448,7 +448,8 @@ size_t compact_tmp_bytes(size_t n);
 void totals_u32(const uint32_t *a, const uint32_t *b, uint64_t n, unsigned long long *tot, uint64_t *h, hipStream_t s);
 // exclusive running maximum (identity 0)
 void scan_exclusive_max_u32(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s);
-// stable LSD radix sort of (key,value) pairs on the low `bits` bits of the key
+// stable LSD radix sort of (key,value) pairs on the low `bits` bits of the key.  Inputs and outputs must not alias (kin !=
+// kout, vin != vout): with an odd number of places the first place would scatter into the array it is still reading.
 void sort_pairs_u32(const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits,
 		    void *tmp, size_t tmp_bytes, hipStream_t s);
 size_t sort_tmp_bytes(size_t n);

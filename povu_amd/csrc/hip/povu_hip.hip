@@ -1647,47 +1647,226 @@ extern "C" uint32_t povu_hip_last_seq_redo(const povu_hip_ctx *ctx) { return ctx
 
 extern "C" uint64_t povu_hip_last_links_processed(const povu_hip_ctx *ctx) { return ctx ? ctx->last_links : 0; }
 
-// ---- unit-test hook for the scans
+// ---- unit-test hooks for the device-wide primitives (primitives.hip).  Each call carves an arena of its own and touches
+// nothing of the context but its stream.  Two things hold for all of them: the primitive's scratch is filled with a
+// non-zero byte before the call (nothing may rely on scratch that happens to be zero: the look-back's status words and
+// ticket, the compaction's tile counts, the sort's table), and every device output lies between two guard bands of a
+// fixed byte, at least 64 words each, which are read back afterwards -- a changed guard byte is return code 5.
+namespace
+{
+constexpr size_t DBG_GUARD = 256; // bytes in front of an output; behind it: as many, plus the padding of its span
+constexpr int DBG_GUARD_BYTE = 0xC5, DBG_POISON_BYTE = 0xA7;
+constexpr int DBG_RC_GUARD = 5;
+struct DbgOut {
+	char *base = nullptr;
+	size_t bytes = 0, span = 0; // payload, and the whole stretch with both guards
+	template <class T>
+	T *data() const
+	{
+		return reinterpret_cast<T *>(base + DBG_GUARD);
+	}
+};
+size_t dbg_out_span(size_t bytes) { return DBG_GUARD + Arena::padded(bytes, 1) + DBG_GUARD; }
+// a guarded output of `bytes`, 256-byte aligned; guards AND payload hold the guard byte until the primitive writes
+DbgOut dbg_out(Arena &ar, size_t bytes, hipStream_t s)
+{
+	DbgOut o;
+	o.bytes = bytes;
+	o.span = dbg_out_span(bytes);
+	o.base = ar.take<char>(o.span);
+	HIP_CHECK(hipMemsetAsync(o.base, DBG_GUARD_BYTE, o.span, s));
+	return o;
+}
+void *dbg_scratch(Arena &ar, size_t bytes, hipStream_t s)
+{
+	char *p = ar.take<char>(bytes);
+	if (bytes)
+		HIP_CHECK(hipMemsetAsync(p, DBG_POISON_BYTE, bytes, s));
+	return p;
+}
+bool dbg_all_guard(const void *host, size_t from, size_t to)
+{
+	const unsigned char *p = static_cast<const unsigned char *>(host);
+	for (size_t i = from; i < to; i++)
+		if (p[i] != (unsigned char)DBG_GUARD_BYTE)
+			return false;
+	return true;
+}
+// both guard bands still hold the pattern (waits for the stream)
+bool dbg_guards_intact(const DbgOut &o, hipStream_t s)
+{
+	if (!o.base)
+		return true;
+	const size_t back = o.span - DBG_GUARD - o.bytes;
+	std::vector<unsigned char> h(DBG_GUARD + back);
+	HIP_CHECK(copy_async(h.data(), o.base, DBG_GUARD, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(copy_async(h.data() + DBG_GUARD, o.base + DBG_GUARD + o.bytes, back, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	return dbg_all_guard(h.data(), 0, h.size());
+}
+// device copy of a host input, 256-byte aligned, with a little slack behind it
+template <class T>
+T *dbg_in(Arena &ar, const T *host, size_t n, hipStream_t s)
+{
+	T *d = ar.take<T>(n + 16);
+	if (n)
+		HIP_CHECK(copy_async(d, host, n * sizeof(T), hipMemcpyHostToDevice, s));
+	return d;
+}
+size_t dbg_in_span(size_t n, size_t elem) { return Arena::padded(n + 16, elem) + 256; }
+} // namespace
+
 extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,
 				   uint32_t *out2, size_t n2)
 {
-	if (!ctx || !in || !out || (in2 && !out2))
+	const int kind = op & 0xFF;
+	const bool in_place = (op & POVU_HIP_SCAN_IN_PLACE) != 0, with_len = (op & POVU_HIP_SCAN_N_DEV) != 0;
+	if (!ctx || kind > POVU_HIP_SCAN_XOR_U128 || (op & ~(0xFF | POVU_HIP_SCAN_IN_PLACE | POVU_HIP_SCAN_N_DEV)))
+		return 1;
+	if (kind == POVU_HIP_SCAN_U8) {
+		if ((n && (!in || !out)) || (in2 && n2 && !out2))
+			return 1;
+	} else if (!in || !out || (in2 && !out2 && kind != POVU_HIP_SCAN_DIFF)) {
+		return 1;
+	}
+	if ((in_place && (kind > POVU_HIP_SCAN_U64 || in2)) || (with_len && kind != POVU_HIP_SCAN_XOR_U128) ||
+	    ((kind == POVU_HIP_SCAN_DIFF || kind == POVU_HIP_SCAN_XOR_PAIR) && !in2))
+		return 1;
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		hipStream_t s = ctx->stream;
+		// element sizes, the length of the second input and whether it has an output of its own
+		const size_t e_in = kind == POVU_HIP_SCAN_U8 ? 1 : kind == POVU_HIP_SCAN_U64 ? 8 : kind == POVU_HIP_SCAN_XOR_U128 ? 16 : 4;
+		const size_t e_out = kind == POVU_HIP_SCAN_U64 ? 8 : kind == POVU_HIP_SCAN_XOR_U128 ? 16 : 4;
+		const bool pair = in2 && (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8 || kind == POVU_HIP_SCAN_XOR_PAIR);
+		const bool second_in = pair || kind == POVU_HIP_SCAN_DIFF;
+		const size_t m = !second_in ? 0 : (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8) ? n2 : n;
+		const size_t tb = kind == POVU_HIP_SCAN_U64 ? scan_exclusive_u64_tmp(n) * 8 : scan_tmp_bytes(std::max(n, m));
+		Arena ar;
+		ar.reserve(dbg_in_span(n, e_in) + dbg_in_span(m, e_in) + 2 * (dbg_out_span(std::max(n, m) * e_out) + 256) + tb + 4096);
+		const DbgOut o1 = dbg_out(ar, n * e_out, s), o2 = pair ? dbg_out(ar, m * e_out, s) : DbgOut{};
+		void *tmp = dbg_scratch(ar, tb, s);
+		const char *di = nullptr, *di2 = nullptr;
+		if (in_place) {
+			HIP_CHECK(copy_async(o1.data<char>(), in, n * e_in, hipMemcpyHostToDevice, s));
+			di = o1.data<char>();
+		} else {
+			di = dbg_in(ar, reinterpret_cast<const char *>(in), n * e_in, s);
+		}
+		if (second_in)
+			di2 = dbg_in(ar, reinterpret_cast<const char *>(in2), m * e_in, s);
+		uint32_t *len_dev = nullptr;
+		if (with_len) {
+			const uint32_t len = (uint32_t)n2;
+			len_dev = ar.take<uint32_t>(1);
+			HIP_CHECK(hipMemcpyAsync(len_dev, &len, 4, hipMemcpyHostToDevice, s));
+			HIP_CHECK(hipStreamSynchronize(s)); // (`len` leaves scope)
+		}
+		const uint32_t *w1 = reinterpret_cast<const uint32_t *>(di), *w2 = reinterpret_cast<const uint32_t *>(di2);
+		switch (kind) {
+		case POVU_HIP_SCAN_SUM:
+			if (pair)
+				scan_exclusive_u32_pair(w1, o1.data<uint32_t>(), n, w2, o2.data<uint32_t>(), m, tmp, tb, s);
+			else
+				scan_exclusive_u32(w1, o1.data<uint32_t>(), n, tmp, tb, s);
+			break;
+		case POVU_HIP_SCAN_MAX: scan_exclusive_max_u32(w1, o1.data<uint32_t>(), n, tmp, tb, s); break;
+		case POVU_HIP_SCAN_U64: // n u64 values, each a pair of words
+			scan_exclusive_u64(reinterpret_cast<const uint64_t *>(di), o1.data<uint64_t>(), n, static_cast<uint64_t *>(tmp), s);
+			break;
+		case POVU_HIP_SCAN_U8:
+			scan_exclusive_u8(reinterpret_cast<const uint8_t *>(di), o1.data<uint32_t>(), n,
+					  pair ? reinterpret_cast<const uint8_t *>(di2) : nullptr, pair ? o2.data<uint32_t>() : nullptr, m, tmp, tb, s);
+			break;
+		case POVU_HIP_SCAN_DIFF: scan_exclusive_diff_u32(w1, w2, o1.data<uint32_t>(), n, tmp, tb, s); break;
+		case POVU_HIP_SCAN_XOR_PAIR: scan_exclusive_xor_u32_pair(w1, o1.data<uint32_t>(), w2, o2.data<uint32_t>(), n, tmp, tb, s); break;
+		default:
+			scan_exclusive_xor_u128(reinterpret_cast<const ulonglong2 *>(di), o1.data<ulonglong2>(), n, tmp, tb, s, len_dev);
+			break;
+		}
+		if (n)
+			HIP_CHECK(copy_async(out, o1.data<char>(), n * e_out, hipMemcpyDeviceToHost, s));
+		if (pair && m)
+			HIP_CHECK(copy_async(out2, o2.data<char>(), m * e_out, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		if (!dbg_guards_intact(o1, s) || !dbg_guards_intact(o2, s))
+			return DBG_RC_GUARD;
+		// (only the first n2 + 1 words exist: what lies behind them is a guard as well)
+		if (with_len && !dbg_all_guard(out, std::min<size_t>(n2 + 1, n) * 16, n * 16))
+			return DBG_RC_GUARD;
+		return 0;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
+extern "C" int povu_hip_debug_sort(povu_hip_ctx *ctx, const uint32_t *keys, const uint32_t *vals, size_t n, unsigned bits,
+				   uint32_t *keys_out, uint32_t *vals_out)
+{
+	if (!ctx || bits > 32 || (n && (!keys || !vals || !keys_out || !vals_out)))
+		return 1;
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		hipStream_t s = ctx->stream;
+		const size_t tb = sort_tmp_bytes(n);
+		Arena ar;
+		ar.reserve(2 * dbg_in_span(n, 4) + 2 * (dbg_out_span(n * 4) + 256) + tb + 4096);
+		const DbgOut ko = dbg_out(ar, n * 4, s), vo = dbg_out(ar, n * 4, s);
+		void *tmp = dbg_scratch(ar, tb, s);
+		const uint32_t *dk = dbg_in(ar, keys, n, s), *dv = dbg_in(ar, vals, n, s);
+		sort_pairs_u32(dk, ko.data<uint32_t>(), dv, vo.data<uint32_t>(), n, bits, tmp, tb, s);
+		if (n) {
+			HIP_CHECK(copy_async(keys_out, ko.data<char>(), n * 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(copy_async(vals_out, vo.data<char>(), n * 4, hipMemcpyDeviceToHost, s));
+		}
+		HIP_CHECK(hipStreamSynchronize(s));
+		return dbg_guards_intact(ko, s) && dbg_guards_intact(vo, s) ? 0 : DBG_RC_GUARD;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
+extern "C" int povu_hip_debug_compact(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, uint32_t *out, uint32_t *count)
+{
+	if (!ctx || !count || n >= (size_t(1) << 32) || (n && (!flags || !out)))
+		return 1;
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		hipStream_t s = ctx->stream;
+		const size_t tb = compact_tmp_bytes(n);
+		Arena ar;
+		ar.reserve(dbg_in_span(n, 1) + dbg_out_span(n * 4) + dbg_out_span(4) + 512 + tb + 4096);
+		const DbgOut oo = dbg_out(ar, n * 4, s), oc = dbg_out(ar, 4, s);
+		void *tmp = dbg_scratch(ar, tb, s);
+		const uint8_t *df = dbg_in(ar, flags, n, s);
+		compact_flagged_u8(df, n, oo.data<uint32_t>(), oc.data<uint32_t>(), tmp, tb, s);
+		if (n)
+			HIP_CHECK(copy_async(out, oo.data<char>(), n * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(count, oc.data<char>(), 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		if (!dbg_guards_intact(oo, s) || !dbg_guards_intact(oc, s))
+			return DBG_RC_GUARD;
+		// (`count` indices were due: what lies behind them is a guard as well)
+		return dbg_all_guard(out, std::min<size_t>(*count, n) * 4, n * 4) ? 0 : DBG_RC_GUARD;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
+extern "C" int povu_hip_debug_totals(povu_hip_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t n, uint64_t tot[2])
+{
+	if (!ctx || !tot || (n && !a))
 		return 1;
 	try {
 		HIP_CHECK(hipSetDevice(ctx->device));
 		hipStream_t s = ctx->stream;
 		Arena ar;
-		if (op == 2) { // n u64 values, each a pair of words
-			uint64_t *di, *dout, *tmp;
-			carve(ar, [&](Spans &take) {
-				take(n + 1, di, dout);
-				take(scan_exclusive_u64_tmp(n), tmp);
-			});
-			HIP_CHECK(copy_async(di, in, n * 8, hipMemcpyHostToDevice, s));
-			scan_exclusive_u64(di, dout, n, tmp, s);
-			HIP_CHECK(copy_async(out, dout, n * 8, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
-			return 0;
-		}
-		const size_t tb = scan_tmp_bytes(std::max(n, n2));
-		ar.reserve(2 * Arena::padded(n + 16, 4) + 2 * Arena::padded(n2 + 16, 4) + tb + 4096);
-		uint32_t *di = ar.take<uint32_t>(n + 16), *dout = ar.take<uint32_t>(n + 16);
-		uint32_t *di2 = ar.take<uint32_t>(n2 + 16), *dout2 = ar.take<uint32_t>(n2 + 16);
-		void *tmp = ar.take<char>(tb);
-		HIP_CHECK(copy_async(di, in, n * 4, hipMemcpyHostToDevice, s));
-		if (in2)
-			HIP_CHECK(copy_async(di2, in2, n2 * 4, hipMemcpyHostToDevice, s));
-		if (in2 && op == 0)
-			scan_exclusive_u32_pair(di, dout, n, di2, dout2, n2, tmp, tb, s);
-		else if (op == 0)
-			scan_exclusive_u32(di, dout, n, tmp, tb, s);
-		else
-			scan_exclusive_max_u32(di, dout, n, tmp, tb, s);
-		HIP_CHECK(copy_async(out, dout, n * 4, hipMemcpyDeviceToHost, s));
-		if (in2 && op == 0)
-			HIP_CHECK(copy_async(out2, dout2, n2 * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		return 0;
+		ar.reserve(2 * dbg_in_span(n, 4) + dbg_out_span(16) + 256 + 4096);
+		const DbgOut ot = dbg_out(ar, b ? 16 : 8, s); // (one array: the second total's word is a guard)
+		const uint32_t *da = dbg_in(ar, a, n, s), *db = b ? dbg_in(ar, b, n, s) : nullptr;
+		tot[0] = tot[1] = 0;
+		totals_u32(da, db, n, ot.data<unsigned long long>(), tot, s);
+		return dbg_guards_intact(ot, s) ? 0 : DBG_RC_GUARD;
 	} catch (const std::exception &) {
 		return 2;
 	}

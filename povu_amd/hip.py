@@ -19,6 +19,15 @@ class HipUnavailable(RuntimeError):
     pass
 
 
+class GuardBandError(RuntimeError):
+    """A device-wide primitive wrote outside its output (raised by its unit-test hook, which guards every output)."""
+
+
+# ops of povu_hip_debug_scan (include/povu_hip.h)
+SCAN_SUM, SCAN_MAX, SCAN_U64, SCAN_U8, SCAN_DIFF, SCAN_XOR_PAIR, SCAN_XOR_U128 = range(7)
+SCAN_IN_PLACE, SCAN_N_DEV = 0x100, 0x200
+
+
 def lib_path() -> str:
     return os.path.join(_HERE, "lib", "libpovu_hip.so")
 
@@ -266,6 +275,12 @@ def load_lib():
     l.povu_hip_debug_scan.restype = C.c_int
     l.povu_hip_debug_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                       C.c_size_t]
+    l.povu_hip_debug_sort.restype = C.c_int
+    l.povu_hip_debug_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p]
+    l.povu_hip_debug_compact.restype = C.c_int
+    l.povu_hip_debug_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
+    l.povu_hip_debug_totals.restype = C.c_int
+    l.povu_hip_debug_totals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
     l.povu_hip_debug_list_rank.restype = C.c_int
     l.povu_hip_debug_list_rank.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1055,23 +1070,116 @@ class HipDecomposer:
         return int(self._lib.povu_hip_last_links_processed(self._ctx))
 
     # ---- parity hooks
-    def debug_scan(self, a, op: int = 0, b=None):
+    @staticmethod
+    def _prim_rc(rc: int, primitive: str):
+        """Return code of a primitive's unit-test hook: 5 = the primitive wrote outside its output."""
+        if rc == 5:
+            raise GuardBandError(f"{primitive}: a guard band around a device output changed")
+        if rc:
+            raise RuntimeError(f"{primitive}: debug hook failed ({rc})")
+
+    def debug_scan(self, a, op: int = 0, b=None, in_place: bool = False):
         """Unit-test hook: exclusive scan of `a` on the device (op 0 sum, 1 running max, 2 sum of uint64 values);
-        with `b`, an independent sum scan of `b` in the same launch."""
+        with `b`, an independent sum scan of `b` in the same launch.  `in_place`: the output is the input on the device."""
         a = np.ascontiguousarray(a, dtype=np.uint64 if op == 2 else np.uint32)
         out = np.empty_like(a)
+        name = ("scan_exclusive_u32", "scan_exclusive_max_u32", "scan_exclusive_u64")[op]
         if b is None:
-            rc = self._lib.povu_hip_debug_scan(self._ctx, op, a.ctypes.data, out.ctypes.data, a.size, None, None, 0)
-            if rc:
-                raise RuntimeError(f"debug_scan failed ({rc})")
+            rc = self._lib.povu_hip_debug_scan(self._ctx, op | (SCAN_IN_PLACE if in_place else 0), a.ctypes.data,
+                                               out.ctypes.data, a.size, None, None, 0)
+            self._prim_rc(rc, name + (" (in place)" if in_place else ""))
             return out
         b = np.ascontiguousarray(b, dtype=np.uint32)
         out2 = np.empty_like(b)
         rc = self._lib.povu_hip_debug_scan(self._ctx, op, a.ctypes.data, out.ctypes.data, a.size, b.ctypes.data,
                                            out2.ctypes.data, b.size)
-        if rc:
-            raise RuntimeError(f"debug_scan failed ({rc})")
+        self._prim_rc(rc, "scan_exclusive_u32_pair" if op == 0 else name)
         return out, out2
+
+    def debug_scan_u8(self, a, b=None):
+        """Unit-test hook of scan_exclusive_u8: exclusive sums (uint32) of the bytes `a`; with `b`, of both in the same
+        launch.  Either may be empty."""
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        out = np.empty(a.size, dtype=np.uint32)
+        if b is None:
+            rc = self._lib.povu_hip_debug_scan(self._ctx, SCAN_U8, a.ctypes.data, out.ctypes.data, a.size, None, None, 0)
+            self._prim_rc(rc, "scan_exclusive_u8")
+            return out
+        b = np.ascontiguousarray(b, dtype=np.uint8)
+        out2 = np.empty(b.size, dtype=np.uint32)
+        rc = self._lib.povu_hip_debug_scan(self._ctx, SCAN_U8, a.ctypes.data, out.ctypes.data, a.size, b.ctypes.data,
+                                           out2.ctypes.data, b.size)
+        self._prim_rc(rc, "scan_exclusive_u8 (two jobs)")
+        return out, out2
+
+    def debug_scan_diff(self, a, sub):
+        """Unit-test hook of scan_exclusive_diff_u32: exclusive sums of a[i] - sub[i] mod 2^32."""
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        sub = np.ascontiguousarray(sub, dtype=np.uint32)
+        assert a.size == sub.size
+        out = np.empty_like(a)
+        rc = self._lib.povu_hip_debug_scan(self._ctx, SCAN_DIFF, a.ctypes.data, out.ctypes.data, a.size, sub.ctypes.data,
+                                           None, sub.size)
+        self._prim_rc(rc, "scan_exclusive_diff_u32")
+        return out
+
+    def debug_scan_xor_pair(self, a, b):
+        """Unit-test hook of scan_exclusive_xor_u32_pair: the exclusive running xor of `a` and of `b` (same length)."""
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        b = np.ascontiguousarray(b, dtype=np.uint32)
+        assert a.size == b.size
+        out, out2 = np.empty_like(a), np.empty_like(b)
+        rc = self._lib.povu_hip_debug_scan(self._ctx, SCAN_XOR_PAIR, a.ctypes.data, out.ctypes.data, a.size,
+                                           b.ctypes.data, out2.ctypes.data, b.size)
+        self._prim_rc(rc, "scan_exclusive_xor_u32_pair")
+        return out, out2
+
+    def debug_scan_xor_u128(self, a, n_dev=None):
+        """Unit-test hook of scan_exclusive_xor_u128: the exclusive running xor of the 16-byte words a[i] (an (n, 2)
+        array of uint64).  With `n_dev`, that value goes into a device word: only the first min(n_dev + 1, n) words
+        exist, and only those are returned (the hook has checked that the rest of the output still holds its guard
+        pattern)."""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        assert a.ndim == 2 and a.shape[1] == 2
+        out = np.empty_like(a)
+        op = SCAN_XOR_U128 | (SCAN_N_DEV if n_dev is not None else 0)
+        rc = self._lib.povu_hip_debug_scan(self._ctx, op, a.ctypes.data, out.ctypes.data, a.shape[0], None, None,
+                                           n_dev or 0)
+        self._prim_rc(rc, "scan_exclusive_xor_u128")
+        return out if n_dev is None else out[:min(n_dev + 1, a.shape[0])]
+
+    def debug_sort(self, keys, vals, bits: int):
+        """Unit-test hook of sort_pairs_u32: (keys, vals) in the stable order of the keys' low `bits` bits."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        vals = np.ascontiguousarray(vals, dtype=np.uint32)
+        assert keys.size == vals.size
+        ko, vo = np.empty_like(keys), np.empty_like(vals)
+        rc = self._lib.povu_hip_debug_sort(self._ctx, keys.ctypes.data, vals.ctypes.data, keys.size, bits,
+                                           ko.ctypes.data, vo.ctypes.data)
+        self._prim_rc(rc, "sort_pairs_u32")
+        return ko, vo
+
+    def debug_compact(self, flags):
+        """Unit-test hook of compact_flagged_u8: the indices of the non-zero bytes of `flags`, ascending."""
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        out = np.empty(flags.size, dtype=np.uint32)
+        cnt = C.c_uint32(0)
+        rc = self._lib.povu_hip_debug_compact(self._ctx, flags.ctypes.data, flags.size, out.ctypes.data, C.byref(cnt))
+        self._prim_rc(rc, "compact_flagged_u8")
+        if cnt.value > flags.size:
+            raise RuntimeError(f"compact_flagged_u8: count {cnt.value} of {flags.size} flags")
+        return out[:cnt.value], int(cnt.value)
+
+    def debug_totals(self, a, b=None):
+        """Unit-test hook of totals_u32: the 64-bit sum of `a`, and of `b` (same length) when given."""
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        tot = (C.c_uint64 * 2)()
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.uint32)
+            assert a.size == b.size
+        rc = self._lib.povu_hip_debug_totals(self._ctx, a.ctypes.data, b.ctypes.data if b is not None else None, a.size, tot)
+        self._prim_rc(rc, "totals_u32")
+        return int(tot[0]) if b is None else (int(tot[0]), int(tot[1]))
 
     def debug_list_rank(self, nxt, w, heads, events: bool = False, bits: int = 0):
         """Unit-test hook: the tree stage's list ranking of the lists `nxt` (NIL ends a list) headed by `heads`,
