@@ -724,6 +724,32 @@ int povu_hip_debug_sort(povu_hip_ctx *ctx, const uint32_t *keys, const uint32_t 
 int povu_hip_debug_compact(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, uint32_t *out, uint32_t *count);
 /* totals_u32: tot[0] = the 64-bit sum of a[0..n), tot[1] = that of b[0..n) (0 when b is NULL) */
 int povu_hip_debug_totals(povu_hip_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t n, uint64_t tot[2]);
+/* ---- unit-test hooks for the look-up structures above the primitives (segtree.hpp, common.hpp; tests/test_gpu_lookups.py) ----
+ * Same conventions: device memory of the call's own, nothing of the context but its stream, scratch and unwritten outputs
+ * filled with a non-zero byte, every device output between guard bands.  0 = ok, 1 = bad arguments, 2 = device error,
+ * 5 = a guard byte changed.  The hooks call the real functions; their own kernels only shape the inputs. */
+/* Coarse min segment tree: seg_build over val[0..n) (n = 0 allowed), then one lane per query.  The device copy of the
+ * values is 16-byte aligned and padded to the next multiple of 16 with ZEROS; the tree buffer has exactly
+ * SegTree::tree_words(n) words.  queries: nq x (kind, l, r, x), kind one of the three below (x unused by MIN); out[i] =
+ * seg_min(l, r) / seg_first_less(l, r, x) / seg_last_less(l, r, x), 0xFFFFFFFF for an empty range or no such index.
+ * r > n is refused (1); l > r is an empty range.  tree (optional): the nodes [0, 2 P), node 1 the root, node 0
+ * undefined, P = the number of blocks of 16 values rounded up to a power of two (at least 1); P (optional): that number. */
+#define POVU_HIP_SEG_MIN 0
+#define POVU_HIP_SEG_FIRST_LESS 1
+#define POVU_HIP_SEG_LAST_LESS 2
+int povu_hip_debug_segtree(povu_hip_ctx *ctx, const uint32_t *val, size_t n, const uint32_t *queries, size_t nq, uint32_t *out,
+			   uint32_t *tree, uint32_t *P);
+/* Bit-rank directory over flags[0..n) (a non-zero byte = set): a producer of the shape of the bridge-flag kernel (256
+ * lanes, four flags a lane, bitrank_store_wave), then bitrank_build over n / 64 + 1 records.  rank[i] = bitrank(pos[i])
+ * = set flags in front of pos[i] (pos[i] <= n, else 1); test[i] = bitrank_test(pos[i]) as 0 / 1 where pos[i] < n, left
+ * unwritten (0xC5C5C5C5) where pos[i] == n.  records (optional): the n / 64 + 2 records of four words (bits 0..31, bits
+ * 32..63, set flags in front, 0), the last one the closing record. */
+int povu_hip_debug_bitrank(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, const uint32_t *pos, size_t nq, uint32_t *rank,
+			   uint32_t *test, uint32_t *records);
+/* append_in_order: workgroups of 256 lanes, each over 16 384 positions of flags[0..n), append their set positions to
+ * list (room for n); *count = the length.  A workgroup's positions form one ascending stretch; the order of the
+ * stretches is up to the atomics.  The device list behind the first *count entries counts as a guard band. */
+int povu_hip_debug_append(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, uint32_t *list, uint32_t *count);
 /* unit-test hook for the list ranking of the tree stage: suffix sums (inclusive, mod 2^32) along the lists next[0..n)
  * (NIL = end of a list; heads[0..nh) = their first elements, NIL entries allowed) -- mode 0: ra of the 0/1 weights w;
  * mode 1: the pre-order events' two sums (element x enters when x % 3 == 0, see tree_kernels.hip), ra and rb.  bits =

@@ -2,6 +2,7 @@
 // decompose path.  Mirrors povu::subcommands::decompose::do_decompose
 // (app/subcommand/decompose.cpp:94-160) from "graph built" to "PVST ready to write".
 #include "context.hpp"
+#include "segtree.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1867,6 +1868,189 @@ extern "C" int povu_hip_debug_totals(povu_hip_ctx *ctx, const uint32_t *a, const
 		tot[0] = tot[1] = 0;
 		totals_u32(da, db, n, ot.data<unsigned long long>(), tot, s);
 		return dbg_guards_intact(ot, s) ? 0 : DBG_RC_GUARD;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
+// ---- unit-test hooks for the look-up structures one layer above the primitives: the coarse min segment tree (segtree.hpp),
+// the bit-rank directory and append_in_order (common.hpp).  Same conventions as above.  The kernels here only bring the
+// inputs into the shape the real producers and consumers have; the structures themselves are the real functions.
+namespace
+{
+constexpr uint32_t DBG_SEG_MIN = POVU_HIP_SEG_MIN, DBG_SEG_FIRST = POVU_HIP_SEG_FIRST_LESS, DBG_SEG_LAST = POVU_HIP_SEG_LAST_LESS;
+// one query (kind, l, r, x) a lane, grid-stride: neighbouring lanes hold different queries, as in the real consumers
+__global__ void __launch_bounds__(256) k_dbg_seg_query(SegTree st, uint32_t nq, const uint4 *__restrict__ q, uint32_t *__restrict__ out)
+{
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) {
+		const uint4 a = q[i];
+		out[i] = a.x == DBG_SEG_MIN ? seg_min(st, a.y, a.z) : a.x == DBG_SEG_FIRST ? seg_first_less(st, a.y, a.z, a.w) : seg_last_less(st, a.y, a.z, a.w);
+	}
+}
+// the shape of k_bridge_flags (par_kernels.hip): 256 lanes, four consecutive flags a lane, whole waves over [0, n]
+__global__ void __launch_bounds__(256) k_dbg_bitrank_flags(uint32_t n, const uint8_t *__restrict__ flags, uint4 *__restrict__ rec)
+{
+	const uint32_t t0 = (BIDX * blockDim.x + threadIdx.x) * 4u;
+	uint32_t f = 0;
+	for (uint32_t j = 0; j < 4 && t0 + j < n; j++)
+		f |= (flags[t0 + j] ? 1u : 0u) << j;
+	const uint32_t w0 = (BIDX * blockDim.x + (threadIdx.x & ~63u)) / 16u; // first record of this wave's 256 positions
+	bitrank_store_wave(rec + w0, f, w0 + (threadIdx.x & 63u) <= n / 64u);
+}
+// rank[i] = bitrank(x[i]) (x[i] <= n), test[i] = bitrank_test(x[i]) where x[i] < n (left alone elsewhere)
+__global__ void __launch_bounds__(256) k_dbg_bitrank_query(uint32_t n, const uint4 *__restrict__ rec, uint32_t nq, const uint32_t *__restrict__ x,
+							   uint32_t *__restrict__ rank, uint32_t *__restrict__ test)
+{
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) {
+		const uint32_t p = x[i];
+		rank[i] = bitrank(rec, p);
+		if (p < n)
+			test[i] = bitrank_test(rec, p) ? 1u : 0u;
+	}
+}
+// the shape of k_entry_list (tree_kernels.hip): a workgroup of LIST_TPB lanes over LIST_SPAN positions, bit 4 it + j of fw =
+// position B0 + 1024 it + 4 tid + j
+__global__ void __launch_bounds__(LIST_TPB) k_dbg_append(uint32_t n, const uint8_t *__restrict__ flags, uint32_t *__restrict__ list,
+							  uint32_t *__restrict__ n_list)
+{
+	const uint32_t B0 = BIDX * LIST_SPAN;
+	unsigned long long fw = 0;
+#pragma unroll
+	for (uint32_t it = 0; it < LIST_ITER; it++) {
+		const uint32_t p0 = B0 + it * (LIST_TPB * 4u) + threadIdx.x * 4u;
+		uint32_t f = 0;
+		for (uint32_t j = 0; j < 4 && p0 + j < n; j++)
+			f |= (flags[p0 + j] ? 1u : 0u) << j;
+		fw |= (unsigned long long)f << (4 * it);
+	}
+	append_in_order(fw, B0, list, n_list);
+}
+constexpr size_t DBG_LOOKUP_MAX_N = (size_t(1) << 32) - (size_t(1) << 16); // (positions and their block / span arithmetic stay in 32 bits)
+unsigned dbg_query_blocks(size_t nq) { return (unsigned)std::min<size_t>(std::max<size_t>((nq + 255) / 256, 1), 4096); }
+// the payload of a guarded output holds the poison byte instead of the guard byte
+void dbg_poison_payload(const DbgOut &o, hipStream_t s)
+{
+	if (o.bytes)
+		HIP_CHECK(hipMemsetAsync(o.data<char>(), DBG_POISON_BYTE, o.bytes, s));
+}
+} // namespace
+
+extern "C" int povu_hip_debug_segtree(povu_hip_ctx *ctx, const uint32_t *val, size_t n, const uint32_t *queries, size_t nq, uint32_t *out,
+				      uint32_t *tree, uint32_t *P)
+{
+	if (!ctx || n > DBG_LOOKUP_MAX_N || nq >= (size_t(1) << 32) || (n && !val) || (nq && (!queries || !out)))
+		return 1;
+	for (size_t i = 0; i < nq; i++) // (kind, l, r, x): no call site asks beyond the values; l > r is an empty range
+		if (queries[4 * i] > DBG_SEG_LAST || queries[4 * i + 2] > n)
+			return 1;
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		hipStream_t s = ctx->stream;
+		const size_t padded = (n + SEG_BLK - 1) / SEG_BLK * SEG_BLK, tw = SegTree::tree_words(n);
+		Arena ar;
+		ar.reserve(Arena::padded(padded + SEG_BLK, 4) + 256 + dbg_in_span(4 * nq, 4) + dbg_out_span(tw * 4) + dbg_out_span(nq * 4) + 512 + 4096);
+		const DbgOut ot = dbg_out(ar, tw * 4, s), oq = dbg_out(ar, nq * 4, s);
+		dbg_poison_payload(ot, s);
+		// the values, 16-byte aligned; the tail of the last block holds ZEROS (below every useful threshold and every
+		// minimum: a build or a query that lets a tail value through gives a wrong answer)
+		uint32_t *dv = ar.take<uint32_t>(padded + SEG_BLK);
+		HIP_CHECK(hipMemsetAsync(dv, DBG_POISON_BYTE, (padded + SEG_BLK) * 4, s));
+		if (n)
+			HIP_CHECK(copy_async(dv, val, n * 4, hipMemcpyHostToDevice, s));
+		if (padded > n)
+			HIP_CHECK(hipMemsetAsync(dv + n, 0, (padded - n) * 4, s));
+		const uint32_t *dq = dbg_in(ar, queries, 4 * nq, s);
+		SegTree st;
+		st.tree = ot.data<uint32_t>();
+		seg_build(st, dv, n, s); // (2 P <= tree_words(n): pow2 is monotone)
+		if (nq)
+			KLAUNCH(k_dbg_seg_query, dim3(dbg_query_blocks(nq)), dim3(256), 0, s, st, (uint32_t)nq, reinterpret_cast<const uint4 *>(dq), oq.data<uint32_t>());
+		std::vector<uint32_t> ht(tw);
+		HIP_CHECK(copy_async(ht.data(), ot.data<char>(), tw * 4, hipMemcpyDeviceToHost, s));
+		if (nq)
+			HIP_CHECK(copy_async(out, oq.data<char>(), nq * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		if (P)
+			*P = st.P;
+		if (tree)
+			std::copy(ht.begin(), ht.begin() + 2 * (size_t)st.P, tree);
+		if (!dbg_guards_intact(ot, s) || !dbg_guards_intact(oq, s))
+			return DBG_RC_GUARD;
+		// (the tree has 2 P nodes: the words of the buffer behind them belong to nobody)
+		const unsigned char *hb = reinterpret_cast<const unsigned char *>(ht.data());
+		for (size_t i = 2 * (size_t)st.P * 4; i < tw * 4; i++)
+			if (hb[i] != (unsigned char)DBG_POISON_BYTE)
+				return DBG_RC_GUARD;
+		return 0;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
+extern "C" int povu_hip_debug_bitrank(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, const uint32_t *pos, size_t nq, uint32_t *rank,
+				      uint32_t *test, uint32_t *records)
+{
+	if (!ctx || n > DBG_LOOKUP_MAX_N || nq >= (size_t(1) << 32) || (n && !flags) || (nq && (!pos || !rank || !test)))
+		return 1;
+	for (size_t i = 0; i < nq; i++)
+		if (pos[i] > n)
+			return 1;
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		hipStream_t s = ctx->stream;
+		const size_t n_rec = n / 64 + 1, tb = scan_tmp_bytes(n_rec + 1); // records of [0, n]; one more closes the array
+		Arena ar;
+		ar.reserve(dbg_in_span(n, 1) + dbg_in_span(nq, 4) + dbg_out_span((n_rec + 1) * 16) + dbg_out_span((n_rec + 1) * 4) + 2 * dbg_out_span(nq * 4) +
+			   5 * 256 + tb + 4096);
+		const DbgOut orec = dbg_out(ar, (n_rec + 1) * 16, s), ocnt = dbg_out(ar, (n_rec + 1) * 4, s);
+		const DbgOut ork = dbg_out(ar, nq * 4, s), ots = dbg_out(ar, nq * 4, s);
+		dbg_poison_payload(orec, s);
+		dbg_poison_payload(ocnt, s);
+		void *tmp = dbg_scratch(ar, tb, s);
+		const uint8_t *df = dbg_in(ar, flags, n, s);
+		const uint32_t *dp = dbg_in(ar, pos, nq, s);
+		uint4 *rec = orec.data<uint4>();
+		const size_t waves = n / 256 + 1; // whole waves: every record of [0, n] is written
+		KLAUNCH(k_dbg_bitrank_flags, dim3((unsigned)((waves * 64 + 255) / 256)), dim3(256), 0, s, (uint32_t)n, df, rec);
+		bitrank_build(rec, n_rec, ocnt.data<uint32_t>(), tmp, tb, s);
+		if (nq) {
+			KLAUNCH(k_dbg_bitrank_query, dim3(dbg_query_blocks(nq)), dim3(256), 0, s, (uint32_t)n, rec, (uint32_t)nq, dp, ork.data<uint32_t>(),
+				ots.data<uint32_t>());
+			HIP_CHECK(copy_async(rank, ork.data<char>(), nq * 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(copy_async(test, ots.data<char>(), nq * 4, hipMemcpyDeviceToHost, s));
+		}
+		if (records)
+			HIP_CHECK(copy_async(records, orec.data<char>(), (n_rec + 1) * 16, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		return dbg_guards_intact(orec, s) && dbg_guards_intact(ocnt, s) && dbg_guards_intact(ork, s) && dbg_guards_intact(ots, s) ? 0 : DBG_RC_GUARD;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
+extern "C" int povu_hip_debug_append(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, uint32_t *list, uint32_t *count)
+{
+	if (!ctx || !count || n > DBG_LOOKUP_MAX_N || (n && (!flags || !list)))
+		return 1;
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		hipStream_t s = ctx->stream;
+		Arena ar;
+		ar.reserve(dbg_in_span(n, 1) + dbg_out_span(n * 4) + dbg_out_span(4) + 512 + 4096);
+		const DbgOut ol = dbg_out(ar, n * 4, s), oc = dbg_out(ar, 4, s);
+		HIP_CHECK(hipMemsetAsync(oc.data<char>(), 0, 4, s)); // the list is empty
+		const uint8_t *df = dbg_in(ar, flags, n, s);
+		if (n)
+			KLAUNCH(k_dbg_append, dim3((unsigned)((n + LIST_SPAN - 1) / LIST_SPAN)), dim3(LIST_TPB), 0, s, (uint32_t)n, df, ol.data<uint32_t>(),
+				oc.data<uint32_t>());
+		if (n)
+			HIP_CHECK(copy_async(list, ol.data<char>(), n * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(copy_async(count, oc.data<char>(), 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		if (!dbg_guards_intact(ol, s) || !dbg_guards_intact(oc, s))
+			return DBG_RC_GUARD;
+		// (`count` entries were due: what lies behind them is a guard as well)
+		return dbg_all_guard(list, std::min<size_t>(*count, n) * 4, n * 4) ? 0 : DBG_RC_GUARD;
 	} catch (const std::exception &) {
 		return 2;
 	}

@@ -26,6 +26,8 @@ class GuardBandError(RuntimeError):
 # ops of povu_hip_debug_scan (include/povu_hip.h)
 SCAN_SUM, SCAN_MAX, SCAN_U64, SCAN_U8, SCAN_DIFF, SCAN_XOR_PAIR, SCAN_XOR_U128 = range(7)
 SCAN_IN_PLACE, SCAN_N_DEV = 0x100, 0x200
+# query kinds of povu_hip_debug_segtree
+SEG_MIN, SEG_FIRST_LESS, SEG_LAST_LESS = range(3)
 
 
 def lib_path() -> str:
@@ -281,6 +283,14 @@ def load_lib():
     l.povu_hip_debug_compact.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
     l.povu_hip_debug_totals.restype = C.c_int
     l.povu_hip_debug_totals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+    l.povu_hip_debug_segtree.restype = C.c_int
+    l.povu_hip_debug_segtree.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_uint32)]
+    l.povu_hip_debug_bitrank.restype = C.c_int
+    l.povu_hip_debug_bitrank.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]
+    l.povu_hip_debug_append.restype = C.c_int
+    l.povu_hip_debug_append.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
     l.povu_hip_debug_list_rank.restype = C.c_int
     l.povu_hip_debug_list_rank.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1180,6 +1190,52 @@ class HipDecomposer:
         rc = self._lib.povu_hip_debug_totals(self._ctx, a.ctypes.data, b.ctypes.data if b is not None else None, a.size, tot)
         self._prim_rc(rc, "totals_u32")
         return int(tot[0]) if b is None else (int(tot[0]), int(tot[1]))
+
+    def debug_segtree(self, values, queries, want_tree: bool = False):
+        """Unit-test hook of the coarse min segment tree (segtree.hpp): seg_build over `values`, then one lane per row
+        (kind, l, r, x) of `queries` (kind SEG_MIN / SEG_FIRST_LESS / SEG_LAST_LESS; r <= len(values)).  Returns one
+        word per query (0xFFFFFFFF: empty range, or no such index); with `want_tree` also the nodes [0, 2 P) of the
+        built tree (node 1 the root, node 0 undefined) and P."""
+        values = np.ascontiguousarray(values, dtype=np.uint32)
+        queries = np.ascontiguousarray(queries, dtype=np.uint32).reshape(-1, 4)
+        out = np.empty(queries.shape[0], dtype=np.uint32)
+        P = 1
+        while P * 16 < values.size:
+            P *= 2
+        tree = np.empty(2 * P, dtype=np.uint32) if want_tree else None
+        p_dev = C.c_uint32(0)
+        rc = self._lib.povu_hip_debug_segtree(self._ctx, values.ctypes.data, values.size, queries.ctypes.data, queries.shape[0],
+                                              out.ctypes.data, tree.ctypes.data if want_tree else None, C.byref(p_dev))
+        self._prim_rc(rc, "segment tree (seg_build / seg_min / seg_first_less / seg_last_less)")
+        if p_dev.value != P:
+            raise RuntimeError(f"segment tree: P = {p_dev.value} for {values.size} values, {P} expected")
+        return (out, tree, P) if want_tree else out
+
+    def debug_bitrank(self, flags, positions):
+        """Unit-test hook of the bit-rank directory (bitrank_store_wave, bitrank_build, bitrank, bitrank_test) over the
+        byte flags `flags`: (rank, test, records) -- rank[i] = set flags in front of positions[i] (<= len(flags)),
+        test[i] = flag positions[i] as 0 / 1 (only where positions[i] < len(flags); other entries are meaningless),
+        records = the len(flags) // 64 + 2 records as rows (bits 0..31, bits 32..63, set flags in front, 0)."""
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        positions = np.ascontiguousarray(positions, dtype=np.uint32)
+        rank, test = np.empty(positions.size, dtype=np.uint32), np.empty(positions.size, dtype=np.uint32)
+        records = np.empty((flags.size // 64 + 2, 4), dtype=np.uint32)
+        rc = self._lib.povu_hip_debug_bitrank(self._ctx, flags.ctypes.data, flags.size, positions.ctypes.data, positions.size,
+                                              rank.ctypes.data, test.ctypes.data, records.ctypes.data)
+        self._prim_rc(rc, "bit-rank directory (bitrank_store_wave / bitrank_build)")
+        return rank, test, records
+
+    def debug_append(self, flags):
+        """Unit-test hook of append_in_order: the positions of the non-zero bytes of `flags` as workgroups of 256 lanes,
+        each over 16 384 positions, append them to one list; (list, its length)."""
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        out = np.empty(flags.size, dtype=np.uint32)
+        cnt = C.c_uint32(0)
+        rc = self._lib.povu_hip_debug_append(self._ctx, flags.ctypes.data, flags.size, out.ctypes.data, C.byref(cnt))
+        self._prim_rc(rc, "append_in_order")
+        if cnt.value > flags.size:
+            raise RuntimeError(f"append_in_order: length {cnt.value} of {flags.size} flags")
+        return out[:cnt.value], int(cnt.value)
 
     def debug_list_rank(self, nxt, w, heads, events: bool = False, bits: int = 0):
         """Unit-test hook: the tree stage's list ranking of the lists `nxt` (NIL ends a list) headed by `heads`,
