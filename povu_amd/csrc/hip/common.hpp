@@ -150,8 +150,8 @@ private:
 };
 
 // An arena layout declared once: a list of spans, `take(n, p...)` for n elements of each pointer's type (n bytes for a
-// void *), run first with no arena behind it to measure, then to carve.  The measure holds from any starting offset: every
-// span counts its padded size and one alignment step more.
+// void *; `take.bytes_for(p, b)` for b bytes behind a typed pointer), run first with no arena behind it to measure, then to
+// carve.  The measure holds from any starting offset: every span counts its padded size and one alignment step more.
 struct Spans {
 	Arena *ar = nullptr; // null: measure only
 	size_t bytes = 0;
@@ -173,6 +173,15 @@ struct Spans {
 		one(c, n);
 		if (ar)
 			p = c;
+	}
+	// a span stated in bytes (no whole number of T, or cut up further by its owner)
+	template <typename T>
+	void bytes_for(T *&p, size_t n_bytes)
+	{
+		void *v = nullptr;
+		one(v, n_bytes);
+		if (ar)
+			p = static_cast<T *>(v);
 	}
 };
 template <class List>

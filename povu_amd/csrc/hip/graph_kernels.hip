@@ -843,14 +843,16 @@ void build_global_csr(ResidentGraph &g, Arena &tmp_arena, hipStream_t s)
 {
 	const uint32_t V = g.V, E = g.E;
 	const size_t nS = 2 * (size_t)V;
-	tmp_arena.reserve(Arena::padded(2 * (size_t)E + 2, 4) * 4 + Arena::padded(nS + 2, 4) + sort_tmp_bytes(2 * (size_t)E) +
-			  scan_tmp_bytes(std::max<size_t>(nS, E) + 2) + (1 << 16));
-	uint32_t *keys = tmp_arena.take<uint32_t>(2 * (size_t)E + 1), *vals = tmp_arena.take<uint32_t>(2 * (size_t)E + 1);
-	uint32_t *keys2 = tmp_arena.take<uint32_t>(2 * (size_t)E + 1), *vals2 = tmp_arena.take<uint32_t>(2 * (size_t)E + 1);
-	uint32_t *deg = tmp_arena.take<uint32_t>(nS + 1);
-	size_t sb = sort_tmp_bytes(2 * (size_t)E), cb = scan_tmp_bytes(std::max<size_t>(nS, E) + 2);
-	void *stmp = tmp_arena.take<char>(sb), *ctmp = tmp_arena.take<char>(cb);
-	uint32_t *word = tmp_arena.take<uint32_t>(8); // [0] max vertex degree, [1] first bad link, [2] first bad tip, [3] max side degree, [4] sides without links
+	uint32_t *keys, *vals, *keys2, *vals2, *deg, *word;
+	void *stmp, *ctmp;
+	const size_t sb = sort_tmp_bytes(2 * (size_t)E), cb = scan_tmp_bytes(std::max<size_t>(nS, E) + 2);
+	carve(tmp_arena, [&](Spans &take) {
+		take(2 * (size_t)E + 1, keys, vals, keys2, vals2);
+		take(nS + 1, deg);
+		take(sb, stmp);
+		take(cb, ctmp);
+		take(8, word); // [0] max vertex degree, [1] first bad link, [2] first bad tip, [3] max side degree, [4] sides without links
+	});
 	hipEvent_t ev[3];
 	for (auto &e : ev)
 		HIP_CHECK(hipEventCreate(&e));

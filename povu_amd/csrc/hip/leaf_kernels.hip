@@ -317,72 +317,62 @@ __global__ void k_leaf_seq_eval(uint32_t P, const LeafIn in, const SlotComp comp
 	p_fam[slot] = leaf_label(in, base + p_ai[slot], base + p_zi[slot], base, in.c_ntree[c], has_child[slot] == 0);
 }
 
-template <typename F>
-static void leaf_spans(size_t V, size_t C, size_t total, F &&take)
+namespace
+{
+// what leaf_prepare computes per tree vertex (the redo's arrays and the dense output live in LeafState)
+struct LeafTmp {
+	uint32_t *gp, *nchild, *out_ord, *in_ord, *nself, *in_ext, *Ps, *O, *X, *w, *tail, *B;
+	uint8_t *capf, *simp, *hit1, *hit3, *nx;
+	void *scan;
+	size_t scan_bytes;
+};
+void leaf_spans(LeafTmp &t, LeafState &ls, size_t V, size_t C, size_t total, Spans &take)
 {
 	const size_t T = 2 * V + C, P = V + C;
-	for (int k = 0; k < 12; k++) // gp nchild out_ord in_ord nself in_ext P O X w tail B
-		take((T + 4) * 4);
-	for (int k = 0; k < 5; k++) // capf simp hit1 hit3 nx
-		take(T + 64);
-	take(total * 4 + 64);
-	take(total * 4 + 64);
-	take(total + 64);
-	take((P + 4) * 4); // p_ai p_zi p_fam has_child: the redo's layout
-	take((P + 4) * 4);
-	take(P + 64);
-	take(P + 64);
-	take(scan_tmp_bytes(T + 4));
+	take(T + 4, t.gp, t.nchild, t.out_ord, t.in_ord, t.nself, t.in_ext, t.Ps, t.O, t.X, t.w, t.tail, t.B);
+	take(T + 64, t.capf, t.simp, t.hit1, t.hit3, t.nx);
+	take(total + 16, ls.dense.ai, ls.dense.zi);
+	take(total + 64, ls.dense.fam);
+	take(P + 4, ls.p_ai, ls.p_zi);
+	take(P + 64, ls.p_fam, ls.p_has_child);
+	t.scan_bytes = scan_tmp_bytes(T + 4);
+	take(t.scan_bytes, t.scan);
 }
+} // namespace
 size_t leaf_workspace_bytes(size_t V, size_t C, size_t total)
 {
-	size_t sum = 0;
-	leaf_spans(V, C, total, [&](size_t b) { sum += ((b + 255) & ~size_t(255)) + 256; });
-	return sum + (1 << 16);
+	LeafTmp t{};
+	LeafState ls{};
+	return measure([&](Spans &take) { leaf_spans(t, ls, V, C, total, take); }) + (1 << 16);
 }
 
 void leaf_prepare(const CompState &cs, const SeqWs &sw, const ParWs &pw, const TreeWs &tw, uint32_t C, Arena &ar, LeafState &ls,
 		  hipStream_t s)
 {
 	const uint32_t V = sw.V, T = 2 * V + C;
-	const size_t total = pw.d_total, P = (size_t)V + C;
+	const size_t total = pw.d_total;
 	ar.reserve(leaf_workspace_bytes(V, C, total));
-	uint32_t *w32[12];
-	for (auto &p : w32)
-		p = ar.take<uint32_t>((size_t)T + 4);
-	uint32_t *gp = w32[0], *nchild = w32[1], *out_ord = w32[2], *in_ord = w32[3], *nself = w32[4], *in_ext = w32[5], *Ps = w32[6],
-		 *O = w32[7], *X = w32[8], *w = w32[9], *tail = w32[10], *B = w32[11];
-	uint8_t *w8[5];
-	for (auto &p : w8)
-		p = ar.take<uint8_t>((size_t)T + 64);
-	uint8_t *capf = w8[0], *simp = w8[1], *hit1 = w8[2], *hit3 = w8[3], *nx = w8[4];
-	ls.dense.ai = ar.take<uint32_t>(total + 16);
-	ls.dense.zi = ar.take<uint32_t>(total + 16);
-	ls.dense.fam = ar.take<uint8_t>(total + 64);
-	ls.p_ai = ar.take<uint32_t>(P + 4);
-	ls.p_zi = ar.take<uint32_t>(P + 4);
-	ls.p_fam = ar.take<uint8_t>(P + 64);
-	ls.p_has_child = ar.take<uint8_t>(P + 64);
-	ls.P = P;
-	const size_t tmp_bytes = scan_tmp_bytes((size_t)T + 4);
-	void *tmp = ar.take<char>(tmp_bytes);
+	LeafTmp t{};
+	Spans take{&ar};
+	leaf_spans(t, ls, V, C, total, take);
+	ls.P = (size_t)V + C;
 
-	for (uint32_t *p : {nchild, out_ord, in_ord, nself, in_ext, w, tail})
+	for (uint32_t *p : {t.nchild, t.out_ord, t.in_ord, t.nself, t.in_ext, t.w, t.tail})
 		HIP_CHECK(hipMemsetAsync(p, 0, ((size_t)T + 4) * 4, s));
-	for (uint8_t *p : {capf, simp, hit1, hit3})
+	for (uint8_t *p : {t.capf, t.simp, t.hit1, t.hit3})
 		HIP_CHECK(hipMemsetAsync(p, 0, (size_t)T + 64, s));
 	const CompOf comp_of{cs.voff, C};
-	LAUNCH(k_leaf_tree, T, s, T, sw.t_size, sw.t_par, comp_of, gp, nchild);
+	LAUNCH(k_leaf_tree, T, s, T, sw.t_size, sw.t_par, comp_of, t.gp, t.nchild);
 	const uint32_t NB = pw.nb0 + pw.ncap + pw.nsimp;
-	LAUNCH(k_leaf_edges, NB, s, NB, pw.nb0, pw.ncap, pw.b_src, pw.b_tgt, sw.t_size, sw.t_flags, gp, out_ord, in_ord, nself, in_ext, capf, simp,
-	       hit1, hit3);
-	LAUNCH(k_leaf_extra_counts, (size_t)T + 1, s, T, capf, simp, nx);
-	scan_exclusive_diff_u32(out_ord, in_ord, Ps, (size_t)T + 1, tmp, tmp_bytes, s);
-	scan_exclusive_u32(out_ord, O, (size_t)T + 1, tmp, tmp_bytes, s);
-	scan_exclusive_u8(nx, X, (size_t)T + 1, nullptr, nullptr, 0, tmp, tmp_bytes, s);
-	debug_edge_id_weights(cs, sw, tw, w, tail, s);
-	LAUNCH(k_leaf_closed, T, s, T, sw.t_size, tail, comp_of, sw.c_ntree, w);
-	scan_exclusive_u32(w, B, (size_t)T + 2, tmp, tmp_bytes, s);
+	LAUNCH(k_leaf_edges, NB, s, NB, pw.nb0, pw.ncap, pw.b_src, pw.b_tgt, sw.t_size, sw.t_flags, t.gp, t.out_ord, t.in_ord, t.nself, t.in_ext,
+	       t.capf, t.simp, t.hit1, t.hit3);
+	LAUNCH(k_leaf_extra_counts, (size_t)T + 1, s, T, t.capf, t.simp, t.nx);
+	scan_exclusive_diff_u32(t.out_ord, t.in_ord, t.Ps, (size_t)T + 1, t.scan, t.scan_bytes, s);
+	scan_exclusive_u32(t.out_ord, t.O, (size_t)T + 1, t.scan, t.scan_bytes, s);
+	scan_exclusive_u8(t.nx, t.X, (size_t)T + 1, nullptr, nullptr, 0, t.scan, t.scan_bytes, s);
+	debug_edge_id_weights(cs, sw, tw, t.w, t.tail, s);
+	LAUNCH(k_leaf_closed, T, s, T, sw.t_size, t.tail, comp_of, sw.c_ntree, t.w);
+	scan_exclusive_u32(t.w, t.B, (size_t)T + 2, t.scan, t.scan_bytes, s);
 
 	LeafIn &in = ls.in;
 	in = LeafIn{};
@@ -397,21 +387,21 @@ void leaf_prepare(const CompState &cs, const SeqWs &sw, const ParWs &pw, const T
 	in.s_vtx = pw.s_vtx;
 	in.ns = pw.ns;
 	in.t_size = sw.t_size;
-	in.gp = gp;
-	in.nchild = nchild;
+	in.gp = t.gp;
+	in.nchild = t.nchild;
 	in.t_flags = sw.t_flags;
-	in.out_ord = out_ord;
-	in.in_ord = in_ord;
-	in.nself = nself;
-	in.in_ext = in_ext;
-	in.capf = capf;
-	in.simp = simp;
-	in.hit1 = hit1;
-	in.hit3 = hit3;
-	in.P = Ps;
-	in.O = O;
-	in.X = X;
-	in.B = B;
+	in.out_ord = t.out_ord;
+	in.in_ord = t.in_ord;
+	in.nself = t.nself;
+	in.in_ext = t.in_ext;
+	in.capf = t.capf;
+	in.simp = t.simp;
+	in.hit1 = t.hit1;
+	in.hit3 = t.hit3;
+	in.P = t.Ps;
+	in.O = t.O;
+	in.X = t.X;
+	in.B = t.B;
 }
 
 void leaf_dense(const LeafState &ls, const SeqWs &sw, const ParWs &pw, uint32_t C, hipStream_t s)

@@ -1199,84 +1199,67 @@ void run_parallel_hairpins(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C
 }
 
 // ------------------------------------------------------------- workspace
-template <typename F>
-static void for_each_span(ParWs &pw, size_t V, size_t E, size_t Cmax, int groups, const StageWsOpts &o, F &&take_any)
+static void for_each_span(ParWs &pw, size_t V, size_t E, size_t Cmax, int groups, const StageWsOpts &o, Spans &spans)
 {
 	// Group 1: what the TREE stage already writes (its tree arrays in the layout the class stage reads, the back edges, the
 	// scratch of the primitives).  Group 2: everything first written by the class stage and later -- by then the tree
 	// stage's own workspace is dead but for a few arrays (tree_spans, group 1), and group 2 lies over the rest of it
 	// (stage_workspace_carve).
-	auto take1 = [&](void **p, size_t bytes) {
+	auto take1 = [&](size_t n, auto *&...p) {
 		if (groups & 1)
-			take_any(p, bytes);
+			spans(n, p...);
 	};
-	auto take = [&](void **p, size_t bytes) {
+	auto take = [&](size_t n, auto *&...p) {
 		if (groups & 2)
-			take_any(p, bytes);
+			spans(n, p...);
 	};
 	// brackets: the back edges of from_bd (links outside the tree, one per side without links) and, per tree vertex, at most
 	// ONE edge of the class stage -- a capping edge needs a non-empty bracket list, a simplifying edge an empty one
 	const size_t T = 2 * V + Cmax, NB = o.nb_cap ? std::min(o.nb_cap, E + V + T) : E + V + T, S = V + 1;
 	pw.nb_cap = NB;
 	auto skip = [](auto **p) { *p = nullptr; };
-	for (uint32_t **p : {&pw.hi0, &pw.mpre, &pw.dlt, &pw.incnt, &pw.lsz})
-		take1((void **)p, (T + 2) * 4);
-	for (uint32_t **p : {&pw.b_src, &pw.b_tgt, &pw.b_ord})
-		take1((void **)p, (NB + 2) * 4);
-	take1((void **)&pw.sdl, (V + 4) * 4);
-	take1((void **)&pw.err, 64);
-	take1((void **)&pw.comp_bad, (Cmax + 2) * 4); // (zeroed when the pass starts, ahead of the tree stage)
+	take1(T + 2, pw.hi0, pw.mpre, pw.dlt, pw.incnt, pw.lsz);
+	take1(NB + 2, pw.b_src, pw.b_tgt, pw.b_ord);
+	take1(V + 4, pw.sdl);
+	take1(16, pw.err);
+	take1(Cmax + 2, pw.comp_bad); // (zeroed when the pass starts, ahead of the tree stage)
 	pw.scan_tmp_bytes = std::max(scan_tmp_bytes(std::max(T, NB) + 4), 2 * compact_tmp_bytes(std::max(T, NB) + 4));
 	pw.sort_tmp_bytes = sort_tmp_bytes(std::max(std::max(T, NB), std::max(4 * V, 2 * E) + 8) + 4);
-	take1(&pw.scan_tmp, pw.scan_tmp_bytes);
-	take1(&pw.sort_tmp, pw.sort_tmp_bytes);
+	take1(pw.scan_tmp_bytes, pw.scan_tmp);
+	take1(pw.sort_tmp_bytes, pw.sort_tmp);
 	for (uint32_t **p : {&pw.t_comp, &pw.t_root, &pw.gpar, &pw.gsize, &pw.cov}) {
 		if (o.full_t)
-			take((void **)p, (T + 2) * 4);
+			take(T + 2, *p);
 		else if (groups & 2)
 			skip(p);
 	}
-	for (uint32_t **p : {&pw.psA, &pw.psB, &pw.flagC, &pw.psC, &pw.cap_tgt, &pw.dlt_ps, &pw.psin, &pw.topi, &pw.gcls, &pw.vals_t,
-			     &pw.vals_t2})
-		take((void **)p, (T + 2) * 4);
-	for (uint8_t **p : {&pw.f8a, &pw.f8b, &pw.f8c, &pw.f8d})
-		take((void **)p, T + 32);
-	take((void **)&pw.keys_t, (T + 2) * 4);
-	take((void **)&pw.keys_t2, (T + 2) * 4);
-	take((void **)&pw.dbo, (Cmax + 2) * 4);
-	for (uint32_t **p : {&pw.b_val2, &pw.tgtR})
-		take((void **)p, (NB + 2) * 4);
+	take(T + 2, pw.psA, pw.psB, pw.flagC, pw.psC, pw.cap_tgt, pw.dlt_ps, pw.psin, pw.topi, pw.gcls, pw.vals_t, pw.vals_t2);
+	take(T + 32, pw.f8a, pw.f8b, pw.f8c, pw.f8d);
+	take(T + 2, pw.keys_t, pw.keys_t2);
+	take(Cmax + 2, pw.dbo);
+	take(NB + 2, pw.b_val2, pw.tgtR);
 	for (uint32_t **p : {&pw.b_val, &pw.b_key, &pw.b_key2}) { // (the bracket sort: only behind a sequential tree stage)
 		if (o.sorted_brackets)
-			take((void **)p, (NB + 2) * 4);
+			take(NB + 2, *p);
 		else if (groups & 2)
 			skip(p);
 	}
-	for (uint32_t **p : {&pw.s_vtx, &pw.s_cls, &pw.ns, &pw.prev, &pw.lev, &pw.e_i})
-		take((void **)p, (S + 2) * 4);
+	take(S + 2, pw.s_vtx, pw.s_cls, pw.ns, pw.prev, pw.lev, pw.e_i);
 	// the two directories over the stack positions [0, S]: S / 64 + 1 records and the closing one (+ one of slack)
-	take((void **)&pw.erec, (S / 64 + 3) * 16);
-	take((void **)&pw.crec, (S / 64 + 3) * 16);
-	take((void **)&pw.rk_cnt, (S / 64 + 3) * 4);
-	take((void **)&pw.clist, (Cmax + 2) * 4);
-	take((void **)&pw.walk, (S + 4) * 4);
-	take((void **)&pw.walk_ps, (S + 4) * 4);
-	take((void **)&pw.wrun, (S + 4) * 4);
-	take((void **)&pw.cproc_ps, (Cmax + 2) * 4);
-	take((void **)&pw.doff, (Cmax + 2) * 4);
-	take((void **)&pw.segA.tree, SegTree::tree_words(T + 1) * 4);
-	take((void **)&pw.segB.tree, SegTree::tree_words(NB + 1) * 4);
-	take((void **)&pw.segP.tree, SegTree::tree_words(S + 1) * 4);
-	take((void **)&pw.segL.tree, SegTree::tree_words(S + 1) * 4);
-	take((void **)&pw.stage, ((S + Cmax + 2) * 4 + 64) * 3 + ((S + Cmax + 2) + 64) * 2 + 256);
+	take(S / 64 + 3, pw.erec, pw.crec);
+	take(S / 64 + 3, pw.rk_cnt);
+	take(Cmax + 2, pw.clist);
+	take(S + 4, pw.walk, pw.walk_ps, pw.wrun);
+	take(Cmax + 2, pw.cproc_ps, pw.doff);
+	take(SegTree::tree_words(T + 1), pw.segA.tree);
+	take(SegTree::tree_words(NB + 1), pw.segB.tree);
+	take(SegTree::tree_words(S + 1), pw.segP.tree, pw.segL.tree);
+	take(((S + Cmax + 2) * 4 + 64) * 3 + ((S + Cmax + 2) + 64) * 2 + 256, pw.stage);
 	if (o.hairpins) {
-		take((void **)&pw.hp_b12, (2 * T + 4) * 8);
-		take((void **)&pw.hpf, T + 2);
-		for (uint32_t **p : {&pw.hp1, &pw.hp2, &pw.hp3})
-			take((void **)p, (T + 2) * 4);
-		take((void **)&pw.segH1.tree, SegTree::tree_words(T + 1) * 4);
-		take((void **)&pw.segH2.tree, SegTree::tree_words(T + 1) * 4);
-		take((void **)&pw.segH3.tree, SegTree::tree_words(T + 1) * 4);
+		take(2 * T + 4, pw.hp_b12);
+		take(T + 2, pw.hpf);
+		take(T + 2, pw.hp1, pw.hp2, pw.hp3);
+		take(SegTree::tree_words(T + 1), pw.segH1.tree, pw.segH2.tree, pw.segH3.tree);
 	} else if (groups & 2) {
 		pw.hpf = nullptr;
 		pw.hp_b12 = nullptr;
@@ -1288,14 +1271,13 @@ static void for_each_span(ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 size_t par_workspace_bytes(size_t V, size_t E, size_t Cmax, int groups, const StageWsOpts &o)
 {
 	ParWs tmp{};
-	size_t total = 0;
-	for_each_span(tmp, V, E, Cmax, groups, o, [&](void **, size_t bytes) { total += ((bytes + 255) & ~size_t(255)) + 256; });
-	return total + (1 << 20);
+	return measure([&](Spans &take) { for_each_span(tmp, V, E, Cmax, groups, o, take); }) + (1 << 20);
 }
 
 void par_carve(Arena &ar, ParWs &pw, size_t V, size_t E, size_t Cmax, int groups, const StageWsOpts &o)
 {
-	for_each_span(pw, V, E, Cmax, groups, o, [&](void **dst, size_t bytes) { *dst = ar.take<char>(bytes); });
+	Spans take{&ar};
+	for_each_span(pw, V, E, Cmax, groups, o, take);
 }
 
 // ------------------------------------------------------------- driver

@@ -2,7 +2,6 @@
 // decompose path.  Mirrors povu::subcommands::decompose::do_decompose
 // (app/subcommand/decompose.cpp:94-160) from "graph built" to "PVST ready to write".
 #include "context.hpp"
-#include "segtree.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1648,521 +1647,6 @@ extern "C" uint32_t povu_hip_last_seq_redo(const povu_hip_ctx *ctx) { return ctx
 
 extern "C" uint64_t povu_hip_last_links_processed(const povu_hip_ctx *ctx) { return ctx ? ctx->last_links : 0; }
 
-// ---- unit-test hooks for the device-wide primitives (primitives.hip).  Each call carves an arena of its own and touches
-// nothing of the context but its stream.  Two things hold for all of them: the primitive's scratch is filled with a
-// non-zero byte before the call (nothing may rely on scratch that happens to be zero: the look-back's status words and
-// ticket, the compaction's tile counts, the sort's table), and every device output lies between two guard bands of a
-// fixed byte, at least 64 words each, which are read back afterwards -- a changed guard byte is return code 5.
-namespace
-{
-constexpr size_t DBG_GUARD = 256; // bytes in front of an output; behind it: as many, plus the padding of its span
-constexpr int DBG_GUARD_BYTE = 0xC5, DBG_POISON_BYTE = 0xA7;
-constexpr int DBG_RC_GUARD = 5;
-struct DbgOut {
-	char *base = nullptr;
-	size_t bytes = 0, span = 0; // payload, and the whole stretch with both guards
-	template <class T>
-	T *data() const
-	{
-		return reinterpret_cast<T *>(base + DBG_GUARD);
-	}
-};
-size_t dbg_out_span(size_t bytes) { return DBG_GUARD + Arena::padded(bytes, 1) + DBG_GUARD; }
-// a guarded output of `bytes`, 256-byte aligned; guards AND payload hold the guard byte until the primitive writes
-DbgOut dbg_out(Arena &ar, size_t bytes, hipStream_t s)
-{
-	DbgOut o;
-	o.bytes = bytes;
-	o.span = dbg_out_span(bytes);
-	o.base = ar.take<char>(o.span);
-	HIP_CHECK(hipMemsetAsync(o.base, DBG_GUARD_BYTE, o.span, s));
-	return o;
-}
-void *dbg_scratch(Arena &ar, size_t bytes, hipStream_t s)
-{
-	char *p = ar.take<char>(bytes);
-	if (bytes)
-		HIP_CHECK(hipMemsetAsync(p, DBG_POISON_BYTE, bytes, s));
-	return p;
-}
-bool dbg_all_guard(const void *host, size_t from, size_t to)
-{
-	const unsigned char *p = static_cast<const unsigned char *>(host);
-	for (size_t i = from; i < to; i++)
-		if (p[i] != (unsigned char)DBG_GUARD_BYTE)
-			return false;
-	return true;
-}
-// both guard bands still hold the pattern (waits for the stream)
-bool dbg_guards_intact(const DbgOut &o, hipStream_t s)
-{
-	if (!o.base)
-		return true;
-	const size_t back = o.span - DBG_GUARD - o.bytes;
-	std::vector<unsigned char> h(DBG_GUARD + back);
-	HIP_CHECK(copy_async(h.data(), o.base, DBG_GUARD, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(copy_async(h.data() + DBG_GUARD, o.base + DBG_GUARD + o.bytes, back, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(hipStreamSynchronize(s));
-	return dbg_all_guard(h.data(), 0, h.size());
-}
-// device copy of a host input, 256-byte aligned, with a little slack behind it
-template <class T>
-T *dbg_in(Arena &ar, const T *host, size_t n, hipStream_t s)
-{
-	T *d = ar.take<T>(n + 16);
-	if (n)
-		HIP_CHECK(copy_async(d, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-	return d;
-}
-size_t dbg_in_span(size_t n, size_t elem) { return Arena::padded(n + 16, elem) + 256; }
-} // namespace
-
-extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,
-				   uint32_t *out2, size_t n2)
-{
-	const int kind = op & 0xFF;
-	const bool in_place = (op & POVU_HIP_SCAN_IN_PLACE) != 0, with_len = (op & POVU_HIP_SCAN_N_DEV) != 0;
-	if (!ctx || kind > POVU_HIP_SCAN_XOR_U128 || (op & ~(0xFF | POVU_HIP_SCAN_IN_PLACE | POVU_HIP_SCAN_N_DEV)))
-		return 1;
-	if (kind == POVU_HIP_SCAN_U8) {
-		if ((n && (!in || !out)) || (in2 && n2 && !out2))
-			return 1;
-	} else if (!in || !out || (in2 && !out2 && kind != POVU_HIP_SCAN_DIFF)) {
-		return 1;
-	}
-	if ((in_place && (kind > POVU_HIP_SCAN_U64 || in2)) || (with_len && kind != POVU_HIP_SCAN_XOR_U128) ||
-	    ((kind == POVU_HIP_SCAN_DIFF || kind == POVU_HIP_SCAN_XOR_PAIR) && !in2))
-		return 1;
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		hipStream_t s = ctx->stream;
-		// element sizes, the length of the second input and whether it has an output of its own
-		const size_t e_in = kind == POVU_HIP_SCAN_U8 ? 1 : kind == POVU_HIP_SCAN_U64 ? 8 : kind == POVU_HIP_SCAN_XOR_U128 ? 16 : 4;
-		const size_t e_out = kind == POVU_HIP_SCAN_U64 ? 8 : kind == POVU_HIP_SCAN_XOR_U128 ? 16 : 4;
-		const bool pair = in2 && (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8 || kind == POVU_HIP_SCAN_XOR_PAIR);
-		const bool second_in = pair || kind == POVU_HIP_SCAN_DIFF;
-		const size_t m = !second_in ? 0 : (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8) ? n2 : n;
-		const size_t tb = kind == POVU_HIP_SCAN_U64 ? scan_exclusive_u64_tmp(n) * 8 : scan_tmp_bytes(std::max(n, m));
-		Arena ar;
-		ar.reserve(dbg_in_span(n, e_in) + dbg_in_span(m, e_in) + 2 * (dbg_out_span(std::max(n, m) * e_out) + 256) + tb + 4096);
-		const DbgOut o1 = dbg_out(ar, n * e_out, s), o2 = pair ? dbg_out(ar, m * e_out, s) : DbgOut{};
-		void *tmp = dbg_scratch(ar, tb, s);
-		const char *di = nullptr, *di2 = nullptr;
-		if (in_place) {
-			HIP_CHECK(copy_async(o1.data<char>(), in, n * e_in, hipMemcpyHostToDevice, s));
-			di = o1.data<char>();
-		} else {
-			di = dbg_in(ar, reinterpret_cast<const char *>(in), n * e_in, s);
-		}
-		if (second_in)
-			di2 = dbg_in(ar, reinterpret_cast<const char *>(in2), m * e_in, s);
-		uint32_t *len_dev = nullptr;
-		if (with_len) {
-			const uint32_t len = (uint32_t)n2;
-			len_dev = ar.take<uint32_t>(1);
-			HIP_CHECK(hipMemcpyAsync(len_dev, &len, 4, hipMemcpyHostToDevice, s));
-			HIP_CHECK(hipStreamSynchronize(s)); // (`len` leaves scope)
-		}
-		const uint32_t *w1 = reinterpret_cast<const uint32_t *>(di), *w2 = reinterpret_cast<const uint32_t *>(di2);
-		switch (kind) {
-		case POVU_HIP_SCAN_SUM:
-			if (pair)
-				scan_exclusive_u32_pair(w1, o1.data<uint32_t>(), n, w2, o2.data<uint32_t>(), m, tmp, tb, s);
-			else
-				scan_exclusive_u32(w1, o1.data<uint32_t>(), n, tmp, tb, s);
-			break;
-		case POVU_HIP_SCAN_MAX: scan_exclusive_max_u32(w1, o1.data<uint32_t>(), n, tmp, tb, s); break;
-		case POVU_HIP_SCAN_U64: // n u64 values, each a pair of words
-			scan_exclusive_u64(reinterpret_cast<const uint64_t *>(di), o1.data<uint64_t>(), n, static_cast<uint64_t *>(tmp), s);
-			break;
-		case POVU_HIP_SCAN_U8:
-			scan_exclusive_u8(reinterpret_cast<const uint8_t *>(di), o1.data<uint32_t>(), n,
-					  pair ? reinterpret_cast<const uint8_t *>(di2) : nullptr, pair ? o2.data<uint32_t>() : nullptr, m, tmp, tb, s);
-			break;
-		case POVU_HIP_SCAN_DIFF: scan_exclusive_diff_u32(w1, w2, o1.data<uint32_t>(), n, tmp, tb, s); break;
-		case POVU_HIP_SCAN_XOR_PAIR: scan_exclusive_xor_u32_pair(w1, o1.data<uint32_t>(), w2, o2.data<uint32_t>(), n, tmp, tb, s); break;
-		default:
-			scan_exclusive_xor_u128(reinterpret_cast<const ulonglong2 *>(di), o1.data<ulonglong2>(), n, tmp, tb, s, len_dev);
-			break;
-		}
-		if (n)
-			HIP_CHECK(copy_async(out, o1.data<char>(), n * e_out, hipMemcpyDeviceToHost, s));
-		if (pair && m)
-			HIP_CHECK(copy_async(out2, o2.data<char>(), m * e_out, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		if (!dbg_guards_intact(o1, s) || !dbg_guards_intact(o2, s))
-			return DBG_RC_GUARD;
-		// (only the first n2 + 1 words exist: what lies behind them is a guard as well)
-		if (with_len && !dbg_all_guard(out, std::min<size_t>(n2 + 1, n) * 16, n * 16))
-			return DBG_RC_GUARD;
-		return 0;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
-extern "C" int povu_hip_debug_sort(povu_hip_ctx *ctx, const uint32_t *keys, const uint32_t *vals, size_t n, unsigned bits,
-				   uint32_t *keys_out, uint32_t *vals_out)
-{
-	if (!ctx || bits > 32 || (n && (!keys || !vals || !keys_out || !vals_out)))
-		return 1;
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		hipStream_t s = ctx->stream;
-		const size_t tb = sort_tmp_bytes(n);
-		Arena ar;
-		ar.reserve(2 * dbg_in_span(n, 4) + 2 * (dbg_out_span(n * 4) + 256) + tb + 4096);
-		const DbgOut ko = dbg_out(ar, n * 4, s), vo = dbg_out(ar, n * 4, s);
-		void *tmp = dbg_scratch(ar, tb, s);
-		const uint32_t *dk = dbg_in(ar, keys, n, s), *dv = dbg_in(ar, vals, n, s);
-		sort_pairs_u32(dk, ko.data<uint32_t>(), dv, vo.data<uint32_t>(), n, bits, tmp, tb, s);
-		if (n) {
-			HIP_CHECK(copy_async(keys_out, ko.data<char>(), n * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(vals_out, vo.data<char>(), n * 4, hipMemcpyDeviceToHost, s));
-		}
-		HIP_CHECK(hipStreamSynchronize(s));
-		return dbg_guards_intact(ko, s) && dbg_guards_intact(vo, s) ? 0 : DBG_RC_GUARD;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
-extern "C" int povu_hip_debug_compact(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, uint32_t *out, uint32_t *count)
-{
-	if (!ctx || !count || n >= (size_t(1) << 32) || (n && (!flags || !out)))
-		return 1;
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		hipStream_t s = ctx->stream;
-		const size_t tb = compact_tmp_bytes(n);
-		Arena ar;
-		ar.reserve(dbg_in_span(n, 1) + dbg_out_span(n * 4) + dbg_out_span(4) + 512 + tb + 4096);
-		const DbgOut oo = dbg_out(ar, n * 4, s), oc = dbg_out(ar, 4, s);
-		void *tmp = dbg_scratch(ar, tb, s);
-		const uint8_t *df = dbg_in(ar, flags, n, s);
-		compact_flagged_u8(df, n, oo.data<uint32_t>(), oc.data<uint32_t>(), tmp, tb, s);
-		if (n)
-			HIP_CHECK(copy_async(out, oo.data<char>(), n * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(copy_async(count, oc.data<char>(), 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		if (!dbg_guards_intact(oo, s) || !dbg_guards_intact(oc, s))
-			return DBG_RC_GUARD;
-		// (`count` indices were due: what lies behind them is a guard as well)
-		return dbg_all_guard(out, std::min<size_t>(*count, n) * 4, n * 4) ? 0 : DBG_RC_GUARD;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
-extern "C" int povu_hip_debug_totals(povu_hip_ctx *ctx, const uint32_t *a, const uint32_t *b, size_t n, uint64_t tot[2])
-{
-	if (!ctx || !tot || (n && !a))
-		return 1;
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		hipStream_t s = ctx->stream;
-		Arena ar;
-		ar.reserve(2 * dbg_in_span(n, 4) + dbg_out_span(16) + 256 + 4096);
-		const DbgOut ot = dbg_out(ar, b ? 16 : 8, s); // (one array: the second total's word is a guard)
-		const uint32_t *da = dbg_in(ar, a, n, s), *db = b ? dbg_in(ar, b, n, s) : nullptr;
-		tot[0] = tot[1] = 0;
-		totals_u32(da, db, n, ot.data<unsigned long long>(), tot, s);
-		return dbg_guards_intact(ot, s) ? 0 : DBG_RC_GUARD;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
-// ---- unit-test hooks for the look-up structures one layer above the primitives: the coarse min segment tree (segtree.hpp),
-// the bit-rank directory and append_in_order (common.hpp).  Same conventions as above.  The kernels here only bring the
-// inputs into the shape the real producers and consumers have; the structures themselves are the real functions.
-namespace
-{
-constexpr uint32_t DBG_SEG_MIN = POVU_HIP_SEG_MIN, DBG_SEG_FIRST = POVU_HIP_SEG_FIRST_LESS, DBG_SEG_LAST = POVU_HIP_SEG_LAST_LESS;
-// one query (kind, l, r, x) a lane, grid-stride: neighbouring lanes hold different queries, as in the real consumers
-__global__ void __launch_bounds__(256) k_dbg_seg_query(SegTree st, uint32_t nq, const uint4 *__restrict__ q, uint32_t *__restrict__ out)
-{
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) {
-		const uint4 a = q[i];
-		out[i] = a.x == DBG_SEG_MIN ? seg_min(st, a.y, a.z) : a.x == DBG_SEG_FIRST ? seg_first_less(st, a.y, a.z, a.w) : seg_last_less(st, a.y, a.z, a.w);
-	}
-}
-// the shape of k_bridge_flags (par_kernels.hip): 256 lanes, four consecutive flags a lane, whole waves over [0, n]
-__global__ void __launch_bounds__(256) k_dbg_bitrank_flags(uint32_t n, const uint8_t *__restrict__ flags, uint4 *__restrict__ rec)
-{
-	const uint32_t t0 = (BIDX * blockDim.x + threadIdx.x) * 4u;
-	uint32_t f = 0;
-	for (uint32_t j = 0; j < 4 && t0 + j < n; j++)
-		f |= (flags[t0 + j] ? 1u : 0u) << j;
-	const uint32_t w0 = (BIDX * blockDim.x + (threadIdx.x & ~63u)) / 16u; // first record of this wave's 256 positions
-	bitrank_store_wave(rec + w0, f, w0 + (threadIdx.x & 63u) <= n / 64u);
-}
-// rank[i] = bitrank(x[i]) (x[i] <= n), test[i] = bitrank_test(x[i]) where x[i] < n (left alone elsewhere)
-__global__ void __launch_bounds__(256) k_dbg_bitrank_query(uint32_t n, const uint4 *__restrict__ rec, uint32_t nq, const uint32_t *__restrict__ x,
-							   uint32_t *__restrict__ rank, uint32_t *__restrict__ test)
-{
-	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) {
-		const uint32_t p = x[i];
-		rank[i] = bitrank(rec, p);
-		if (p < n)
-			test[i] = bitrank_test(rec, p) ? 1u : 0u;
-	}
-}
-// the shape of k_entry_list (tree_kernels.hip): a workgroup of LIST_TPB lanes over LIST_SPAN positions, bit 4 it + j of fw =
-// position B0 + 1024 it + 4 tid + j
-__global__ void __launch_bounds__(LIST_TPB) k_dbg_append(uint32_t n, const uint8_t *__restrict__ flags, uint32_t *__restrict__ list,
-							  uint32_t *__restrict__ n_list)
-{
-	const uint32_t B0 = BIDX * LIST_SPAN;
-	unsigned long long fw = 0;
-#pragma unroll
-	for (uint32_t it = 0; it < LIST_ITER; it++) {
-		const uint32_t p0 = B0 + it * (LIST_TPB * 4u) + threadIdx.x * 4u;
-		uint32_t f = 0;
-		for (uint32_t j = 0; j < 4 && p0 + j < n; j++)
-			f |= (flags[p0 + j] ? 1u : 0u) << j;
-		fw |= (unsigned long long)f << (4 * it);
-	}
-	append_in_order(fw, B0, list, n_list);
-}
-constexpr size_t DBG_LOOKUP_MAX_N = (size_t(1) << 32) - (size_t(1) << 16); // (positions and their block / span arithmetic stay in 32 bits)
-unsigned dbg_query_blocks(size_t nq) { return (unsigned)std::min<size_t>(std::max<size_t>((nq + 255) / 256, 1), 4096); }
-// the payload of a guarded output holds the poison byte instead of the guard byte
-void dbg_poison_payload(const DbgOut &o, hipStream_t s)
-{
-	if (o.bytes)
-		HIP_CHECK(hipMemsetAsync(o.data<char>(), DBG_POISON_BYTE, o.bytes, s));
-}
-} // namespace
-
-extern "C" int povu_hip_debug_segtree(povu_hip_ctx *ctx, const uint32_t *val, size_t n, const uint32_t *queries, size_t nq, uint32_t *out,
-				      uint32_t *tree, uint32_t *P)
-{
-	if (!ctx || n > DBG_LOOKUP_MAX_N || nq >= (size_t(1) << 32) || (n && !val) || (nq && (!queries || !out)))
-		return 1;
-	for (size_t i = 0; i < nq; i++) // (kind, l, r, x): no call site asks beyond the values; l > r is an empty range
-		if (queries[4 * i] > DBG_SEG_LAST || queries[4 * i + 2] > n)
-			return 1;
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		hipStream_t s = ctx->stream;
-		const size_t padded = (n + SEG_BLK - 1) / SEG_BLK * SEG_BLK, tw = SegTree::tree_words(n);
-		Arena ar;
-		ar.reserve(Arena::padded(padded + SEG_BLK, 4) + 256 + dbg_in_span(4 * nq, 4) + dbg_out_span(tw * 4) + dbg_out_span(nq * 4) + 512 + 4096);
-		const DbgOut ot = dbg_out(ar, tw * 4, s), oq = dbg_out(ar, nq * 4, s);
-		dbg_poison_payload(ot, s);
-		// the values, 16-byte aligned; the tail of the last block holds ZEROS (below every useful threshold and every
-		// minimum: a build or a query that lets a tail value through gives a wrong answer)
-		uint32_t *dv = ar.take<uint32_t>(padded + SEG_BLK);
-		HIP_CHECK(hipMemsetAsync(dv, DBG_POISON_BYTE, (padded + SEG_BLK) * 4, s));
-		if (n)
-			HIP_CHECK(copy_async(dv, val, n * 4, hipMemcpyHostToDevice, s));
-		if (padded > n)
-			HIP_CHECK(hipMemsetAsync(dv + n, 0, (padded - n) * 4, s));
-		const uint32_t *dq = dbg_in(ar, queries, 4 * nq, s);
-		SegTree st;
-		st.tree = ot.data<uint32_t>();
-		seg_build(st, dv, n, s); // (2 P <= tree_words(n): pow2 is monotone)
-		if (nq)
-			KLAUNCH(k_dbg_seg_query, dim3(dbg_query_blocks(nq)), dim3(256), 0, s, st, (uint32_t)nq, reinterpret_cast<const uint4 *>(dq), oq.data<uint32_t>());
-		std::vector<uint32_t> ht(tw);
-		HIP_CHECK(copy_async(ht.data(), ot.data<char>(), tw * 4, hipMemcpyDeviceToHost, s));
-		if (nq)
-			HIP_CHECK(copy_async(out, oq.data<char>(), nq * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		if (P)
-			*P = st.P;
-		if (tree)
-			std::copy(ht.begin(), ht.begin() + 2 * (size_t)st.P, tree);
-		if (!dbg_guards_intact(ot, s) || !dbg_guards_intact(oq, s))
-			return DBG_RC_GUARD;
-		// (the tree has 2 P nodes: the words of the buffer behind them belong to nobody)
-		const unsigned char *hb = reinterpret_cast<const unsigned char *>(ht.data());
-		for (size_t i = 2 * (size_t)st.P * 4; i < tw * 4; i++)
-			if (hb[i] != (unsigned char)DBG_POISON_BYTE)
-				return DBG_RC_GUARD;
-		return 0;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
-extern "C" int povu_hip_debug_bitrank(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, const uint32_t *pos, size_t nq, uint32_t *rank,
-				      uint32_t *test, uint32_t *records)
-{
-	if (!ctx || n > DBG_LOOKUP_MAX_N || nq >= (size_t(1) << 32) || (n && !flags) || (nq && (!pos || !rank || !test)))
-		return 1;
-	for (size_t i = 0; i < nq; i++)
-		if (pos[i] > n)
-			return 1;
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		hipStream_t s = ctx->stream;
-		const size_t n_rec = n / 64 + 1, tb = scan_tmp_bytes(n_rec + 1); // records of [0, n]; one more closes the array
-		Arena ar;
-		ar.reserve(dbg_in_span(n, 1) + dbg_in_span(nq, 4) + dbg_out_span((n_rec + 1) * 16) + dbg_out_span((n_rec + 1) * 4) + 2 * dbg_out_span(nq * 4) +
-			   5 * 256 + tb + 4096);
-		const DbgOut orec = dbg_out(ar, (n_rec + 1) * 16, s), ocnt = dbg_out(ar, (n_rec + 1) * 4, s);
-		const DbgOut ork = dbg_out(ar, nq * 4, s), ots = dbg_out(ar, nq * 4, s);
-		dbg_poison_payload(orec, s);
-		dbg_poison_payload(ocnt, s);
-		void *tmp = dbg_scratch(ar, tb, s);
-		const uint8_t *df = dbg_in(ar, flags, n, s);
-		const uint32_t *dp = dbg_in(ar, pos, nq, s);
-		uint4 *rec = orec.data<uint4>();
-		const size_t waves = n / 256 + 1; // whole waves: every record of [0, n] is written
-		KLAUNCH(k_dbg_bitrank_flags, dim3((unsigned)((waves * 64 + 255) / 256)), dim3(256), 0, s, (uint32_t)n, df, rec);
-		bitrank_build(rec, n_rec, ocnt.data<uint32_t>(), tmp, tb, s);
-		if (nq) {
-			KLAUNCH(k_dbg_bitrank_query, dim3(dbg_query_blocks(nq)), dim3(256), 0, s, (uint32_t)n, rec, (uint32_t)nq, dp, ork.data<uint32_t>(),
-				ots.data<uint32_t>());
-			HIP_CHECK(copy_async(rank, ork.data<char>(), nq * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(copy_async(test, ots.data<char>(), nq * 4, hipMemcpyDeviceToHost, s));
-		}
-		if (records)
-			HIP_CHECK(copy_async(records, orec.data<char>(), (n_rec + 1) * 16, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		return dbg_guards_intact(orec, s) && dbg_guards_intact(ocnt, s) && dbg_guards_intact(ork, s) && dbg_guards_intact(ots, s) ? 0 : DBG_RC_GUARD;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
-extern "C" int povu_hip_debug_append(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, uint32_t *list, uint32_t *count)
-{
-	if (!ctx || !count || n > DBG_LOOKUP_MAX_N || (n && (!flags || !list)))
-		return 1;
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		hipStream_t s = ctx->stream;
-		Arena ar;
-		ar.reserve(dbg_in_span(n, 1) + dbg_out_span(n * 4) + dbg_out_span(4) + 512 + 4096);
-		const DbgOut ol = dbg_out(ar, n * 4, s), oc = dbg_out(ar, 4, s);
-		HIP_CHECK(hipMemsetAsync(oc.data<char>(), 0, 4, s)); // the list is empty
-		const uint8_t *df = dbg_in(ar, flags, n, s);
-		if (n)
-			KLAUNCH(k_dbg_append, dim3((unsigned)((n + LIST_SPAN - 1) / LIST_SPAN)), dim3(LIST_TPB), 0, s, (uint32_t)n, df, ol.data<uint32_t>(),
-				oc.data<uint32_t>());
-		if (n)
-			HIP_CHECK(copy_async(list, ol.data<char>(), n * 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(copy_async(count, oc.data<char>(), 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-		if (!dbg_guards_intact(ol, s) || !dbg_guards_intact(oc, s))
-			return DBG_RC_GUARD;
-		// (`count` entries were due: what lies behind them is a guard as well)
-		return dbg_all_guard(list, std::min<size_t>(*count, n) * 4, n * 4) ? 0 : DBG_RC_GUARD;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
-// ---- unit-test hook for the list ranking of the tree stage (tree_kernels.hip, debug_list_rank)
-extern "C" int povu_hip_debug_list_rank(povu_hip_ctx *ctx, uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads,
-					uint32_t nh, int mode, uint32_t bits, uint32_t *ra, uint32_t *rb)
-{
-	if (!ctx || !next || !w || (nh && !heads) || !ra || (mode != 0 && !rb) || mode < 0 || mode > 1)
-		return 1;
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		debug_list_rank(n, next, w, heads, nh, mode, bits, ra, rb, ctx->stream);
-		return 0;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
-// ---- timing hook for the scans: `reps` exclusive sum scans of n words (device resident, all ones), ms per scan by HIP events
-extern "C" double povu_hip_debug_scan_time(povu_hip_ctx *ctx, size_t n, int reps, int op)
-{
-	if (!ctx || !n || reps <= 0)
-		return -1.0;
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		hipStream_t s = ctx->stream;
-		Arena ar;
-		const size_t tb = scan_tmp_bytes(n);
-		ar.reserve(2 * Arena::padded(n + 16, 4) + tb + 4096);
-		uint32_t *di = ar.take<uint32_t>(n + 16), *dout = ar.take<uint32_t>(n + 16);
-		void *tmp = ar.take<char>(tb);
-		HIP_CHECK(hipMemsetAsync(di, 1, n * 4, s));
-		hipEvent_t e0, e1;
-		HIP_CHECK(hipEventCreate(&e0));
-		HIP_CHECK(hipEventCreate(&e1));
-		for (int w = 0; w < 2; w++)
-			op ? scan_exclusive_max_u32(di, dout, n, tmp, tb, s) : scan_exclusive_u32(di, dout, n, tmp, tb, s);
-		HIP_CHECK(hipEventRecord(e0, s));
-		for (int r = 0; r < reps; r++)
-			op ? scan_exclusive_max_u32(di, dout, n, tmp, tb, s) : scan_exclusive_u32(di, dout, n, tmp, tb, s);
-		HIP_CHECK(hipEventRecord(e1, s));
-		HIP_CHECK(hipEventSynchronize(e1));
-		float ms = 0;
-		HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-		(void)hipEventDestroy(e0);
-		(void)hipEventDestroy(e1);
-		return (double)ms / reps;
-	} catch (const std::exception &) {
-		return -2.0;
-	}
-}
-
-// ---- stage-level parity hooks
-extern "C" int povu_hip_debug_components(povu_hip_ctx *ctx, uint32_t *comp_of, uint32_t *local_idx)
-{
-	if (!ctx || !ctx->last.valid)
-		return 1;
-	ctx->quiesce();
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		const uint32_t V = ctx->g.V, C = ctx->last.C;
-		std::vector<uint32_t> pos(V), voff(C + 1);
-		HIP_CHECK(hipMemcpy(comp_of, ctx->cs.comp_of, (size_t)V * 4, hipMemcpyDeviceToHost));
-		if (ctx->cs.lean_identity)
-			std::iota(pos.begin(), pos.end(), 0u);
-		else
-			HIP_CHECK(hipMemcpy(pos.data(), ctx->cs.pos, (size_t)V * 4, hipMemcpyDeviceToHost));
-		HIP_CHECK(hipMemcpy(voff.data(), ctx->cs.voff, (size_t)(C + 1) * 4, hipMemcpyDeviceToHost));
-		for (uint32_t v = 0; v < V; v++)
-			local_idx[v] = pos[v] - voff[comp_of[v]];
-		return 0;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
-extern "C" int povu_hip_debug_tree(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, uint32_t *gid, uint8_t *typ,
-				   uint32_t *par, uint32_t *cls)
-{
-	if (!ctx || !ctx->last.valid || comp >= ctx->last.C || !n_tree)
-		return 1;
-	if (cls && ctx->last.mixed)
-		return 4; // classes of a mixed pass sit in two layouts (parallel stage / one-lane kernels): not exported
-	ctx->quiesce();
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		uint32_t voff = 0, N = 0;
-		HIP_CHECK(hipMemcpy(&voff, ctx->cs.voff + comp, 4, hipMemcpyDeviceToHost));
-		HIP_CHECK(hipMemcpy(&N, ctx->sw.c_ntree + comp, 4, hipMemcpyDeviceToHost));
-		*n_tree = N;
-		const size_t tb = 2 * (size_t)voff + comp;
-		if (gid)
-			HIP_CHECK(hipMemcpy(gid, ctx->sw.t_gid + tb, (size_t)N * 4, hipMemcpyDeviceToHost));
-		if (par)
-			HIP_CHECK(hipMemcpy(par, ctx->sw.t_par + tb, (size_t)N * 4, hipMemcpyDeviceToHost));
-		const bool par_cls = !ctx->last.plan.all_seq && (ctx->last.seq_redo == 0 || ctx->last.redo_pvst_only);
-		if (cls && par_cls) {
-			classes_to_tree_space(ctx->pw, ctx->stream);
-			HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		}
-		if (cls) // the parallel class stage keeps the classes in its own T-space array
-			HIP_CHECK(hipMemcpy(cls, (par_cls ? ctx->pw.gcls : ctx->sw.t_cls) + tb, (size_t)N * 4, hipMemcpyDeviceToHost));
-		if (typ)
-			HIP_CHECK(hipMemcpy(typ, ctx->sw.t_flags + tb, N, hipMemcpyDeviceToHost));
-		return 0;
-	} catch (const std::exception &) {
-		return 2;
-	}
-}
-
 extern "C" int povu_hip_last_black_only_classes(const povu_hip_ctx *ctx)
 {
 	return ctx && ctx->last.valid && !ctx->last.plan.all_seq && ctx->pw.black_only_used ? 1 : 0;
@@ -2184,84 +1668,4 @@ extern "C" int povu_hip_last_crossings(povu_hip_ctx *ctx, uint32_t out[2])
 extern "C" int povu_hip_last_laminar_check_ran(const povu_hip_ctx *ctx)
 {
 	return ctx && ctx->last.valid && !ctx->last.plan.all_seq && ctx->pw.laminar_checked ? 1 : 0;
-}
-
-extern "C" int povu_hip_debug_edge_ids(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, uint32_t *tree_edge_id)
-{
-	if (!ctx || !ctx->last.valid || comp >= ctx->last.C || !n_tree)
-		return 1;
-	if (!ctx->last.plan.par_tree)
-		return 3; // the one-lane tree kernels keep no per-side scan state
-	if (ctx->last.mixed)
-		return 4; // (see povu_hip_debug_tree)
-	uint32_t *dw = nullptr;
-	ctx->quiesce();
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		uint32_t voff = 0, N = 0;
-		HIP_CHECK(hipMemcpy(&voff, ctx->cs.voff + comp, 4, hipMemcpyDeviceToHost));
-		HIP_CHECK(hipMemcpy(&N, ctx->sw.c_ntree + comp, 4, hipMemcpyDeviceToHost));
-		*n_tree = N;
-		if (!tree_edge_id || N == 0)
-			return 0;
-		const size_t T = 2 * (size_t)ctx->sw.V + ctx->last.C, tb = 2 * (size_t)voff + comp;
-		HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dw), 2 * T * 4));
-		HIP_CHECK(hipMemsetAsync(dw, 0, 2 * T * 4, ctx->stream));
-		debug_edge_id_weights(ctx->cs, ctx->sw, ctx->tw, dw, dw + T, ctx->stream);
-		std::vector<uint32_t> w(N), tail(N), size(N);
-		HIP_CHECK(copy_async(w.data(), dw + tb, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-		HIP_CHECK(copy_async(tail.data(), dw + T + tb, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-		HIP_CHECK(copy_async(size.data(), ctx->sw.t_size + tb, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
-		HIP_CHECK(hipStreamSynchronize(ctx->stream));
-		HIP_CHECK(hipFree(dw));
-		dw = nullptr;
-		// back edges created before vertex t is discovered: those in front of every vertex up to t, and the tails of
-		// the vertices whose subtree closed before t
-		std::vector<uint32_t> closed((size_t)N + 1, 0);
-		for (uint32_t t = 0; t < N; t++)
-			closed[std::min<size_t>((size_t)t + size[t], N)] += tail[t];
-		uint32_t before = 0;
-		tree_edge_id[0] = POVU_NIL;
-		for (uint32_t t = 0; t < N; t++) {
-			before += w[t] + closed[t];
-			if (t > 0)
-				tree_edge_id[t] = t - 1 + before;
-		}
-		return 0;
-	} catch (const std::exception &) {
-		if (dw)
-			(void)hipFree(dw);
-		return 2;
-	}
-}
-
-extern "C" int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t *tree_vtx, uint32_t *cls,
-				    uint32_t *next_seen)
-{
-	if (!ctx || !ctx->last.valid || comp >= ctx->last.C || !n)
-		return 1;
-	if (ctx->last.mixed)
-		return 4; // the candidate stacks of a mixed pass sit in two layouts: not exported (see povu_hip_debug_tree)
-	ctx->quiesce();
-	try {
-		HIP_CHECK(hipSetDevice(ctx->device));
-		if (ctx->last.stack_export_pending && ctx->last.seq_redo == 0) {
-			export_parallel_stack(ctx->cs, ctx->sw, ctx->pw, ctx->stream);
-			HIP_CHECK(hipStreamSynchronize(ctx->stream));
-			ctx->last.stack_export_pending = false;
-		}
-		uint32_t voff = 0, ns = 0;
-		HIP_CHECK(hipMemcpy(&voff, ctx->cs.voff + comp, 4, hipMemcpyDeviceToHost));
-		HIP_CHECK(hipMemcpy(&ns, ctx->sw.c_nstack + comp, 4, hipMemcpyDeviceToHost));
-		*n = ns;
-		if (tree_vtx)
-			HIP_CHECK(hipMemcpy(tree_vtx, ctx->sw.s_vtx + voff, (size_t)ns * 4, hipMemcpyDeviceToHost));
-		if (cls)
-			HIP_CHECK(hipMemcpy(cls, ctx->sw.s_cls + voff, (size_t)ns * 4, hipMemcpyDeviceToHost));
-		if (next_seen)
-			HIP_CHECK(hipMemcpy(next_seen, ctx->sw.next_seen + voff, (size_t)ns * 4, hipMemcpyDeviceToHost));
-		return 0;
-	} catch (const std::exception &) {
-		return 2;
-	}
 }

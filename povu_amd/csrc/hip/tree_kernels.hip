@@ -1907,53 +1907,60 @@ __global__ void k_dup_flags(uint32_t n, const uint32_t *__restrict__ skey, const
 }
 
 // ------------------------------------------------------------------ workspace
-template <typename F>
-static void tree_spans(TreeWs &tw, size_t V, size_t E, size_t Cmax, int groups, const StageWsOpts &o, F &&take_any)
+// the wave walk's three arrays over nS sides, as whole arena steps (they lie back to back: in the stage block or in an arena
+// of their own): a 32-byte record per side; the stack pool, whose chunks double in size -- a class takes less than three
+// entries per side; the parents
+struct WalkBytes {
+	size_t rec, stk, par;
+	explicit WalkBytes(size_t nS) : rec(Arena::padded(nS, 32)), stk(Arena::padded(3 * nS * 8 + 64, 1)), par(Arena::padded(nS, 4)) {}
+	size_t total() const { return rec + stk + par; }
+};
+
+static void tree_spans(TreeWs &tw, size_t V, size_t E, size_t Cmax, int groups, const StageWsOpts &o, Spans &spans)
 {
 	// Group 1: what outlives the tree stage (the debug hook that recomputes the edge-id weights after a pass reads the DFS
 	// records, the tree index of every side and the duplicate-slot flags).  Group 2: the rest -- dead once the class stage
 	// starts, whose own arrays lie over it (stage_workspace_carve).
-	auto take1 = [&](void **p, size_t bytes) {
+	auto take1 = [&](size_t n, auto *&...p) {
 		if (groups & 1)
-			take_any(p, bytes);
+			spans(n, p...);
 	};
-	auto take = [&](void **p, size_t bytes) {
+	auto take = [&](size_t n, auto *&...p) {
 		if (groups & 2)
-			take_any(p, bytes);
+			spans(n, p...);
 	};
 	const size_t nS = 2 * V + 2, NA = std::max<size_t>(4 * V, 2 * E) + 8; // tour positions; the 8-byte arrays double as slot buffers
 	const size_t NSL = std::max<size_t>(2 * V + 2 * E, 4 * V) + 16; // scan slots of all sides / events of the second ranking
-	take1((void **)&tw.dvis_slots, std::max(2 * E, 2 * V) + 16); // per-slot duplicate flags (hub graphs); earlier: per-side class flags
-	take1((void **)&tw.side_tidx, nS * 4);
-	take1((void **)&tw.dps, nS * 8);
-	take((void **)&tw.dist, (2 * E + 16) * 8);
-	take((void **)&tw.xrec, (NA / 64 + 4) * 16);
-	take((void **)&tw.xrank, (NA / 64 + 4) * 4);
-	take((void **)&tw.evt, NA * 8);
-	take((void **)&tw.t0seg, (V + 2) * 16);
-	for (uint32_t **p : {&tw.entry_ps, &tw.entry_list, &tw.be_cnt})
-		take((void **)p, nS * 4);
-	take((void **)&tw.dvis, nS);
-	take((void **)&tw.wadj, (nS + 2 * E + 8) * 4); // wave walk: class-filtered scan lists (4 bytes a slot); earlier in the pass: twin slots [2E]
-	take((void **)&tw.cproc, (Cmax + 2) * 4);
-	take((void **)&tw.rk_pk, NSL * 4);
-	take((void **)&tw.rk_heads, (Cmax + 2) * 4);
+	if (groups & 1)
+		spans.bytes_for(tw.dvis_slots, std::max(2 * E, 2 * V) + 16); // per-slot duplicate flags (hub graphs); earlier: per-side class flags
+	take1(nS, tw.side_tidx);
+	take1(nS, tw.dps);
+	take(2 * E + 16, tw.dist);
+	take(NA / 64 + 4, tw.xrec);
+	take(NA / 64 + 4, tw.xrank);
+	if (groups & 2)
+		spans.bytes_for(tw.evt, NA * 8);
+	take(V + 2, tw.t0seg);
+	take(nS, tw.entry_ps, tw.entry_list, tw.be_cnt);
+	take(nS, tw.dvis);
+	take(nS + 2 * E + 8, tw.wadj); // wave walk: class-filtered scan lists (4 bytes a slot); earlier in the pass: twin slots [2E]
+	take(Cmax + 2, tw.cproc);
+	take(NSL, tw.rk_pk);
+	take(Cmax + 2, tw.rk_heads);
 	// One block, three tenants that are never at home together: the six level pools of the list rankings (the tour's at the
 	// start, the pre-order's after the class walks); behind the pools the bridge test's values -- one 16-byte value per
 	// segment that carries one (K <= V) and their running xor, live between the first ranking and the class walks, and on
 	// hub graphs once more after the second ranking as the key and value buffers of the slot sort (2E four-byte words each);
 	// and, over all of it, the wave walk's per-side records, stack pool and parents (only while the large classes are
 	// walked).  ~12 GB instead of 21 on the whole-genome workload.
-	auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-	const size_t pool_b = pad(rank_pool_words(NSL, Cmax + 1) * 4);
-	const size_t xv_b = pad((std::max<size_t>(V + 2, E + 8) + 8) * 16);
-	const size_t wrec_b = pad(nS * 32);	     // 32-byte record per side
-	const size_t wstk_b = pad(3 * nS * 8 + 64); // stack pool: chunks double in size, a class takes less than three entries per side
-	const size_t wpar_b = pad(nS * 4);
+	const size_t pool_b = Arena::padded(rank_pool_words(NSL, Cmax + 1), 4);
+	const size_t xv_b = Arena::padded(std::max<size_t>(V + 2, E + 8) + 8, 16);
+	const WalkBytes wb(nS);
 	char *blk = nullptr;
 	// (the walk's third of it is 12 GB on the whole-genome workload against 9 for the other two, and most graphs never need
 	// it: with !walk_inline it comes out of an arena of its own when a pass does have large classes)
-	take((void **)&blk, o.walk_inline ? std::max(6 * pool_b + 2 * xv_b, wrec_b + wstk_b + wpar_b) : 6 * pool_b + 2 * xv_b);
+	if (groups & 2)
+		spans.bytes_for(blk, o.walk_inline ? std::max(6 * pool_b + 2 * xv_b, wb.total()) : 6 * pool_b + 2 * xv_b);
 	if (groups & 2)
 		tw.walk_inline = o.walk_inline;
 	if (blk) {
@@ -1964,8 +1971,8 @@ static void tree_spans(TreeWs &tw, size_t V, size_t E, size_t Cmax, int groups, 
 		tw.xps = reinterpret_cast<decltype(tw.xps)>(blk + 6 * pool_b + xv_b);
 		if (o.walk_inline) {
 			tw.wrec = reinterpret_cast<decltype(tw.wrec)>(blk);
-			tw.wstk = reinterpret_cast<decltype(tw.wstk)>(blk + wrec_b);
-			tw.wpar = reinterpret_cast<decltype(tw.wpar)>(blk + wrec_b + wstk_b);
+			tw.wstk = reinterpret_cast<decltype(tw.wstk)>(blk + wb.rec);
+			tw.wpar = reinterpret_cast<decltype(tw.wpar)>(blk + wb.rec + wb.stk);
 		} else {
 			tw.wrec = nullptr;
 			tw.wstk = nullptr;
@@ -1977,22 +1984,16 @@ static void tree_spans(TreeWs &tw, size_t V, size_t E, size_t Cmax, int groups, 
 size_t tree_workspace_bytes(size_t V, size_t E, size_t Cmax, int groups, const StageWsOpts &o)
 {
 	TreeWs tmp{};
-	size_t total = 0;
-	tree_spans(tmp, V, E, Cmax, groups, o, [&](void **, size_t bytes) { total += ((bytes + 255) & ~size_t(255)) + 256; });
-	return total + (1 << 20);
+	return measure([&](Spans &take) { tree_spans(tmp, V, E, Cmax, groups, o, take); }) + (1 << 20);
 }
 
 void tree_carve(Arena &ar, TreeWs &tw, size_t V, size_t E, size_t Cmax, int groups, const StageWsOpts &o)
 {
-	tree_spans(tw, V, E, Cmax, groups, o, [&](void **dst, size_t bytes) { *dst = ar.take<char>(bytes); });
+	Spans take{&ar};
+	tree_spans(tw, V, E, Cmax, groups, o, take);
 }
 
-size_t walk_workspace_bytes(size_t V)
-{
-	const size_t nS = 2 * V + 2;
-	auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
-	return pad(nS * 32) + pad(3 * nS * 8 + 64) + pad(nS * 4) + 4096;
-}
+size_t walk_workspace_bytes(size_t V) { return WalkBytes(2 * V + 2).total() + 4096; }
 
 // The workspace of the parallel stages: what the tree stage hands to the class stage and what outlives the tree stage side
 // by side; then ONE stretch that holds the tree stage's own arrays first and the class stage's afterwards.
@@ -2129,11 +2130,11 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 		if (!tw.walk_inline) { // the records of all sides, the stack pool and the parents: taken when a pass needs them
 			if (!tw.walk_arena)
 				throw HipError("class walk: no arena for the wave walk's arrays (internal)");
-			const size_t nSw = 2 * (size_t)V + 2;
+			const WalkBytes wb(2 * (size_t)V + 2);
 			tw.walk_arena->reserve(walk_workspace_bytes(V));
-			tw.wrec = reinterpret_cast<decltype(tw.wrec)>(tw.walk_arena->take<char>(nSw * 32));
-			tw.wstk = reinterpret_cast<decltype(tw.wstk)>(tw.walk_arena->take<char>(3 * nSw * 8 + 64));
-			tw.wpar = reinterpret_cast<decltype(tw.wpar)>(tw.walk_arena->take<char>(nSw * 4));
+			tw.wrec = reinterpret_cast<decltype(tw.wrec)>(tw.walk_arena->take<char>(wb.rec));
+			tw.wstk = reinterpret_cast<decltype(tw.wstk)>(tw.walk_arena->take<char>(wb.stk));
+			tw.wpar = reinterpret_cast<decltype(tw.wpar)>(tw.walk_arena->take<char>(wb.par));
 		}
 		uint32_t *pool_top = pw.err + 7, *walk_err = pw.err + 8; // (cleared with the other counters at the start of the pass)
 		LAUNCH(k_class_recs, nS, s, nS, cs.loff, cs.ladj, cstate, cs.ckey, tw.cproc, tw.wadj, tw.wrec, tw.wpar);

@@ -383,6 +383,32 @@ def test_workspace_estimate_of_the_headline_graph():
     assert 0 < small < 64 << 20
 
 
+def test_workspace_sizes_match_the_recorded_bytes(golden_dir):
+    """Every arena layout is a list of spans that is measured and carved by the same code, and rewriting a list must not
+    move a public size: the three size functions give, to the byte, what the build of the commit named in the golden file
+    gave.  The shapes are the smallest at which a max() inside the lists changes sides, plus the headline graph.  Host
+    arithmetic only: no GPU."""
+    import json
+    _built()
+    lib = C.CDLL(os.path.join(LIB, "libpovu_hip.so"))
+    lib.povu_hip_workspace_estimate.restype = C.c_uint64
+    lib.povu_hip_workspace_estimate.argtypes = [C.c_uint32] * 3
+    lib.povu_hip_workspace_breakdown.argtypes = [C.c_uint32] * 3 + [C.POINTER(C.c_uint64)]
+    lib.povu_hip_leaf_workspace_estimate.restype = C.c_uint64
+    lib.povu_hip_leaf_workspace_estimate.argtypes = [C.c_uint32] * 2
+    shapes = json.load(open(os.path.join(golden_dir, "workspace_bytes.json")))["shapes"]
+    assert [(r["V"], r["E"], r["C"]) for r in shapes] == [
+        (1, 0, 1), (3, 2, 1), (1000, 1500, 1), (1000, 1500, 0), (1000, 400, 37), (1000, 5000, 1), (70000, 90000, 70000),
+        (99860187, 122435438, 2024), (99860187, 122435438, 0)]
+    for r in shapes:
+        V, E, Cn = r["V"], r["E"], r["C"]
+        o = (C.c_uint64 * 7)()
+        assert lib.povu_hip_workspace_breakdown(V, E, Cn, o) == 0
+        assert list(o) == r["breakdown"], (V, E, Cn)
+        assert lib.povu_hip_workspace_estimate(V, E, Cn) == r["estimate"], (V, E, Cn)
+        assert lib.povu_hip_leaf_workspace_estimate(V, Cn) == r["leaf_estimate"], (V, E, Cn)
+
+
 def test_cli_gpus_flag_arguments(tmp_path, golden_dir):
     """`--gpus N` (additive; default 1): which device every worker gets is settled on the host before anything touches a
     GPU -- 0 .. N-1 or the N entries of POVU_HIP_DEVICES, each checked against the visible devices -- and a multi-GPU run
