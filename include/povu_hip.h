@@ -378,6 +378,7 @@ typedef struct {
 #define POVU_HIP_T_FORCE_TIER2 1u /* run every scan with the wave-per-scan kernel (tests) */
 #define POVU_HIP_T_INVERSIONS 2u  /* povu_hip_call only: SUBR records too ("Inversion calls"); ignored elsewhere */
 #define POVU_HIP_T_NESTED 4u	  /* povu_hip_call only: alleles modulo enclosed sites, levels and parents by geometry ("Nested calls") */
+#define POVU_HIP_T_MERGE 8u	  /* povu_hip_call_profile under POVU_HIP_PROFILE_DECOMPOSED only: equal primitives merged ("Merged primitives") */
 #define POVU_HIP_TRAV_LONG 1u	  /* status bits per query: a scan would need more than max_steps steps */
 #define POVU_HIP_TRAV_STRAY 2u	  /* a scan met a boundary step that does not close it */
 #define POVU_HIP_TRAV_OPEN 4u	  /* a scan reached the end of its path */
@@ -509,6 +510,21 @@ typedef struct {
 	uint64_t n_passthrough_alts; /* (record, ALT) kept whole (_ROW_PASS); a _ROW_RAW row counts as neither */
 	uint64_t n_prim_tier2;	     /* pairs the striped kernel aligned (a text longer than 64 bytes, or all with _T_FORCE_TIER2) */
 	uint64_t n_prim_cells;	     /* sum of (len REF + 1) * (len ALT + 1) over the aligned pairs */
+	/* per merged row ("Merged primitives"), in the order of their first members among the rows.  Without POVU_HIP_T_MERGE:
+	 * merged 0, n_mrows 0, the arrays NULL, the counters 0.  A merged row is a group of rows that are the same primitive
+	 * (reference path, POS and both written texts after upper-casing; a _ROW_PASS row is a group of its own); its first
+	 * member is its representative.  The row arrays above are those of the call without the flag */
+	uint64_t merged;	     /* 1: made with POVU_HIP_T_MERGE (the VCF is written from the merged rows) */
+	uint64_t n_mrows;
+	const uint64_t *mrow_off;    /* [n_mrows + 1] members of merged row g: mrow_member[mrow_off[g] .. mrow_off[g + 1]) */
+	const uint32_t *mrow_member; /* [n_rows] row indices, the members of a group in row order */
+	const uint8_t *mrow_gt;	     /* [n_mrows * n_slots] the joint genotype of every slot: 0, 1, or 0xFF for '.' */
+	const uint32_t *mrow_ac, *mrow_an, *mrow_ns; /* [n_mrows] counted on mrow_gt */
+	uint64_t n_merged_groups;    /* groups of two members or more */
+	uint64_t n_merged_members;   /* rows in those groups */
+	uint64_t n_merge_splits;     /* groups split off a run of equal (POS, lengths, hash) by the exact comparison */
+	uint64_t n_ref_consistent;   /* (group, slot) entries that are 0 only because the slot's own ALT lies outside the group's span */
+	uint64_t n_gt_conflicts;     /* (group, slot) entries with a vote for 1 and a vote for 0 (written 1) */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
@@ -533,7 +549,9 @@ povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, co
 /* "Decomposed calls": every record is kept and every (REF, ALT) of a flubble record is aligned (unit-cost edit distance, gaps
  * as far left as the optimum allows) and written as its primitives, one row each (povu_hip_calls.n_rows, row_*).  Does not
  * imply POVU_HIP_T_NESTED (may be combined with it and with _T_INVERSIONS); max_level and max_ref_length are ignored,
- * max_allele_length is the longest text that is aligned: 0 means POVU_HIP_PRIM_MAX_LENGTH, more than that is refused */
+ * max_allele_length is the longest text that is aligned: 0 means POVU_HIP_PRIM_MAX_LENGTH, more than that is refused.  With
+ * POVU_HIP_T_MERGE in opts->flags equal primitives of different ALTs and records are merged into one row with joint genotypes
+ * (povu_hip_calls.n_mrows, mrow_*; refused for 2^32 (group, slot) entries or more); the flag with any other profile is refused */
 #define POVU_HIP_PROFILE_DECOMPOSED 4u
 #define POVU_HIP_PRIM_MAX_LENGTH 512u
 #define POVU_HIP_ROW_RAW 0u /* the record as the raw call writes it: its one ALT is one primitive that spells POS, REF and ALT */
@@ -640,7 +658,9 @@ char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, c
  * PROFILE, LEFT_NORMALIZED, RAW_POS, RAW_REF and RAW_ALT behind LV (or PS), any other record as the raw call writes it; raw_pos
  * or norm_block NULL: no record was changed.  Under _DECOMPOSED the rows are written instead of the records (INTEGRATION.md
  * "Decomposed calls": IDs `<label>:<alt>:snp<k>` / `ins<k>` / `del<k>` / `passthrough`, `<label>:subr-passthrough`; a _ROW_RAW row is
- * its record's raw line); NULL row arrays: the raw records.  Under the other profiles the fields behind `nested` are not
+ * its record's raw line); NULL row arrays: the raw records; with mrow_off not NULL the merged rows are written instead of the rows
+ * ("Merged primitives": a group of two or more as its representative with `MERGED=<members>;MERGED_FROM=<ids>` behind
+ * `DECOMPOSED=T`, GT and the counts from mrow_*; NULL when a member index or an offset points outside the rows).  Under the other profiles the fields behind `nested` are not
  * read.  NULL for an unknown profile */
 char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
 				 const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, uint32_t profile,

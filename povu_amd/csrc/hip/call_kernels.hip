@@ -22,6 +22,7 @@
 // (REF is the reference's own exact allele, the ALTs the representatives), whether REF has no inner base, whether REF is
 // spelled on its own (an "extra" one-allele block behind the class blocks).  A block is a (site, anchored, orientation).
 #include "call_common.hpp"
+#include "merge_kernels.hpp"
 #include "nest_kernels.hpp"
 #include "norm_kernels.hpp"
 #include "prim_kernels.hpp"
@@ -490,6 +491,10 @@ struct CallsOwner {
 	PinnedVec<uint32_t> row_record, row_alt, row_index, row_ref_start, row_ref_len, row_alt_start, row_alt_len, row_ac, row_an, row_ns;
 	PinnedVec<uint8_t> row_kind, row_reason, row_lead;
 	PinnedVec<uint64_t> row_pos;
+	// ... merged (POVU_HIP_T_MERGE)
+	PinnedVec<uint64_t> mrow_off;
+	PinnedVec<uint32_t> mrow_member, mrow_ac, mrow_an, mrow_ns;
+	PinnedVec<uint8_t> mrow_gt;
 	PinnedVec<uint16_t> gt;
 	PinnedVec<char> seq, at;
 	std::vector<uint64_t> contig_len;
@@ -504,7 +509,7 @@ struct CallInputs {
 	const uint32_t *slot_of_path;
 	const povu_hip_trav_opts *opts;
 	uint32_t n, P, nR, S, NS, n_trees = 0;
-	bool inversions, nested, normalized, decomposed;
+	bool inversions, nested, normalized, decomposed, merge;
 	uint32_t prim_cap = 0; // decomposed: the longest text that is aligned
 	povu_hip_call_profile_opts prof; // (raw-graph without a profile)
 	std::vector<uint32_t> ref_of_path, slot_first, qa, qz; // reference number of every path (NO_QUERY: none), first slot of every sample, the queries
@@ -582,6 +587,10 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 		throw HipError("unknown profile " + std::to_string(in.prof.profile));
 	in.normalized = in.prof.profile == POVU_HIP_PROFILE_LEFT_NORMALIZED; // (keeps every record, ignores the limits, implies nothing)
 	in.decomposed = in.prof.profile == POVU_HIP_PROFILE_DECOMPOSED;	     // (the same; max_allele_length is the cap of the aligner)
+	in.merge = opts && (opts->flags & POVU_HIP_T_MERGE);
+	if (in.merge && !in.decomposed)
+		throw HipError(std::string("POVU_HIP_T_MERGE merges the rows of the decomposed profile: refused with profile ") +
+			       (const char *[]){"raw-graph", "top-level-only", "popped", "left-normalized"}[in.prof.profile]);
 	if (in.decomposed) {
 		if (in.prof.max_allele_length > POVU_HIP_PRIM_MAX_LENGTH)
 			throw HipError("max_allele_length " + std::to_string(in.prof.max_allele_length) + " is above the ceiling " +
@@ -966,8 +975,9 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const Ca
 		throw HipError("segment " + std::to_string(read_back(ctx->g.vid + hbad, s)) + " holds a byte that is no nucleotide code (ACGTN, lower case, IUPAC)");
 }
 
-// the rows of the `decomposed` profile: every (REF, ALT) of the records as they are written, aligned and split (prim_kernels.hip)
-PrimRows primitive_rows(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallRecs &r, const CallSpelled &sp)
+// what the `decomposed` profile reads: every (REF, ALT) of the records as they are written (prim_kernels.hip aligns and splits
+// them, merge_kernels.hip merges the rows)
+PrimIn primitive_input(const CallInputs &in, const CallWs &w, const CallRecs &r, const CallSpelled &sp)
 {
 	const InvRows &o = r.rows;
 	PrimIn p{};
@@ -979,11 +989,11 @@ PrimRows primitive_rows(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w
 	p.cap = in.prim_cap;
 	p.force_tier2 = in.opts && (in.opts->flags & POVU_HIP_T_FORCE_TIER2);
 	p.ref_bases = sp.h_roff.back() - sp.h_roff.front();
-	return prim_rows(ctx, p);
+	return p;
 }
 
 povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, const CallRecs &r, const CallSpelled &sp,
-			      const PrimRows &pr, CallTimer &timer)
+			      const PrimRows &pr, const MergedRows &mg, CallTimer &timer)
 {
 	const uint32_t nrec = r.nrec, nb = r.L.nb, nR = in.nR, S = in.S;
 	const uint64_t nsp = r.L.nsp;
@@ -1047,6 +1057,15 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 		give(o->row_an, v.row_an, pr.an, m);
 		give(o->row_ns, v.row_ns, pr.ns, m);
 	}
+	if (in.merge) { // (without the flag: the arrays NULL)
+		const size_t g = (size_t)mg.n_mrows;
+		give(o->mrow_off, v.mrow_off, mg.off, g + 1);
+		give(o->mrow_member, v.mrow_member, mg.member, (size_t)pr.n_rows);
+		give(o->mrow_gt, v.mrow_gt, mg.gt, g * S);
+		give(o->mrow_ac, v.mrow_ac, mg.ac, g);
+		give(o->mrow_an, v.mrow_an, mg.an, g);
+		give(o->mrow_ns, v.mrow_ns, mg.ns, g);
+	}
 	v.device_ms = timer.stop(ctx->stream);
 	for (const auto &fill : defaults)
 		fill();
@@ -1067,6 +1086,10 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	v.n_normalized = w.nm.n_changed, v.max_shift = w.nm.max_shift, v.n_norm_compared = w.nm.n_compared;
 	v.n_rows = pr.n_rows;
 	v.n_decomposed_alts = pr.n_decomposed, v.n_passthrough_alts = pr.n_passthrough, v.n_prim_tier2 = pr.n_tier2, v.n_prim_cells = pr.n_cells;
+	v.merged = in.merge ? 1 : 0;
+	v.n_mrows = mg.n_mrows;
+	v.n_merged_groups = mg.n_groups, v.n_merged_members = mg.n_members, v.n_merge_splits = mg.n_splits;
+	v.n_ref_consistent = mg.n_ref_consistent, v.n_gt_conflicts = mg.n_conflicts;
 	CallsOwner *raw = o.release();
 	return &raw->view;
 }
@@ -1102,8 +1125,10 @@ extern "C" povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_h
 		record_arrays(ctx, in, w, inv, r);
 		CallSpelled sp;
 		spelling(ctx, in, w, inv, r, sp);
-		const PrimRows pr = in.decomposed ? primitive_rows(ctx, in, w, r, sp) : PrimRows{};
-		return calls_to_host(ctx, in, w, inv, r, sp, pr, timer);
+		const PrimIn pin = in.decomposed ? primitive_input(in, w, r, sp) : PrimIn{};
+		const PrimRows pr = in.decomposed ? prim_rows(ctx, pin) : PrimRows{};
+		const MergedRows mg = in.merge ? merge_rows(ctx, pin, pr) : MergedRows{};
+		return calls_to_host(ctx, in, w, inv, r, sp, pr, mg, timer);
 	});
 }
 

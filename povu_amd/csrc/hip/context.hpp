@@ -325,6 +325,8 @@ struct povu_hip_ctx {
 	Arena nm_ws; // left-normalisation (norm_kernels.hip)
 	// the `decomposed` profile (prim_kernels.hip): the (record, ALT) pairs / the codes of the striped alignments / the rows
 	Arena pr_ws, pr_slab, pr_rows;
+	// ... with POVU_HIP_T_MERGE (merge_kernels.hip): the grouping's scratch / the merged rows
+	Arena mg_ws, mg_rows;
 	// povu_hip_call with POVU_HIP_T_NESTED (nest_kernels.hip): the index of the called sites' traversals / the classes / the
 	// scratch of both / the records' parents, levels and the profile's choice
 	Arena ns_idx, ns_cls, ns_ws, ns_rec;

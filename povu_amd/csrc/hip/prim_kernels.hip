@@ -538,6 +538,7 @@ PrimRows prim_rows(povu_hip_ctx *ctx, const PrimIn &in)
 		throw HipError("segment " + std::to_string(read_back(ctx->g.vid + h_bad, s)) + " holds a byte that is no nucleotide code (ACGTN, lower case, IUPAC)");
 	out.n_decomposed = h_words[W_DECOMPOSED], out.n_passthrough = h_words[W_PASSTHROUGH];
 	out.n_rows = n_rows;
+	out.pre = PrimPre{P.row_off, u.pos, P.reason, u.lead, u.ref_len}; // (no later step of this call writes them or carves their arenas)
 	if (!nr)
 		return out;
 	// ---- order: stable by (reference, row POS); record, ALT and alignment order follow from the order the rows were made in

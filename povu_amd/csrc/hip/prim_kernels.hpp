@@ -24,6 +24,13 @@ struct PrimIn {
 	bool force_tier2;   // every aligned pair through the striped kernel
 	uint64_t ref_bases; // bases of all reference paths (the width of the POS sort key)
 };
+// what the rows were made from, valid as long as they are: the rows before the sort (those of a pair consecutive, in alignment
+// order, hence ascending by POS) and per pair where its rows lie there (n_pairs + 1 entries) and why it was kept whole
+struct PrimPre {
+	const uint64_t *row_off = nullptr, *pos = nullptr;
+	const uint8_t *reason = nullptr, *lead = nullptr;
+	const uint32_t *ref_len = nullptr;
+};
 // the rows, on the device (the context's arenas of the step, valid until the next call under the profile), in (reference path,
 // row POS, record, ALT, alignment order), and the counters
 struct PrimRows {
@@ -33,6 +40,7 @@ struct PrimRows {
 	uint8_t *kind = nullptr, *reason = nullptr, *lead = nullptr;
 	uint64_t *pos = nullptr;
 	uint64_t n_decomposed = 0, n_passthrough = 0, n_tier2 = 0, n_cells = 0;
+	PrimPre pre; // (for merge_kernels.hip)
 };
 // Refused: 2^32 pairs or rows or more, a context base that is no nucleotide code (the message names the segment), slabs
 // beyond device memory

@@ -29,6 +29,7 @@ struct CallArgs {
 	bool to_stdout = true;
 	bool inversions = false; // --inversions: SUBR records too (INTEGRATION.md "Inversion calls")
 	bool nested = false;	 // --nested, or implied by a profile (INTEGRATION.md "Nested calls")
+	bool merge = false;	 // --merge-primitives, with --profile decomposed alone (INTEGRATION.md "Merged primitives")
 	povu_hip_call_profile_opts prof{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 };
 
@@ -76,6 +77,8 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			c.inversions = true;
 		} else if (x == "--nested") {
 			c.nested = true;
+		} else if (x == "--merge-primitives") {
+			c.merge = true;
 		} else if (x == "--profile" || !x.compare(0, 10, "--profile=")) {
 			const std::string v = x == "--profile" ? need(i) : x.substr(10);
 			if (v == "raw-graph")
@@ -111,6 +114,8 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			by_pos = true;
 		}
 	}
+	if (c.merge && c.prof.profile != POVU_HIP_PROFILE_DECOMPOSED)
+		throw std::runtime_error("Flag '--merge-primitives' merges the rows of --profile decomposed and needs that profile");
 	forms = (int)by_p + (int)!ref_file.empty() + (int)by_pos;
 	if (forms != 1)
 		throw std::runtime_error("call needs exactly one of the reference options: -r <file>, -P <prefix> (repeatable), or "
@@ -212,7 +217,7 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 		fail("paths");
 	if (povu_hip_segments_upload(ctx, V, seq_off.data(), seq.data(), err, sizeof err) != 0)
 		fail("sequences");
-	const povu_hip_trav_opts opts{0, (ca.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (ca.nested ? POVU_HIP_T_NESTED : 0u)};
+	const povu_hip_trav_opts opts{0, (ca.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (ca.nested ? POVU_HIP_T_NESTED : 0u) | (ca.merge ? POVU_HIP_T_MERGE : 0u)};
 	povu_hip_calls *c = povu_hip_call_profile(ctx, sites, &nm->refs, nm->slot_of_path, &opts, &ca.prof, err, sizeof err);
 	if (!c)
 		fail("call");

@@ -3,7 +3,7 @@
 //   povu [--version] [-v <int>] [-t <int>] decompose -i <gfa> [-o <dir>] [-h|--hairpins] [-s|--subflubbles]
 //   povu ... decompose ... --structure-export <json>   (additive: writes the flubble debug sidecar gfa2vcf writes)
 //   povu ... gfa2vcf -i <gfa> [-h] [-s] [--structure-export <json>] <options of `call`>   (app/cli/cli.cpp:154-193)
-//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--profile <p>]   (the
+//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--profile <p>] [--merge-primitives]   (the
 //   variant calls of INTEGRATION.md "Variant calls" and "Inversion calls", on the GPU)
 #include "decompose.hpp"
 
@@ -71,6 +71,8 @@ static void usage(std::ostream &os)
 	      "                                          keeps all and moves every indel to the left end of its repeat [default: raw-graph]\n"
 	      "        --profile=decomposed              keeps all and writes every (REF, ALT) as the SNPs, insertions and deletions of\n"
 	      "                                          its alignment (INTEGRATION.md \"Decomposed calls\")\n"
+	      "        --merge-primitives                decomposed only: equal primitives of different ALTs and records become one\n"
+	      "                                          record with joint genotypes (INTEGRATION.md \"Merged primitives\") [default: false]\n"
 	      "        --max-level=[n]                   popped: the deepest level kept without rescue [default: 0]\n"
 	      "        --max-ref-length=[n], --max-allele-length=[n]\n"
 	      "                                          popped: a record with a longer REF / allele is big (0: no limit) [default: 0]\n"

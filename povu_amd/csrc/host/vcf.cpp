@@ -64,6 +64,9 @@ const char *PROFILE_LINES[] = {
 	"##INFO=<ID=RAW_ALT,Number=1,Type=String,Description=\"Raw ALT before profile rewrite\">\n"
 	"##INFO=<ID=SUBR_ORIGIN,Number=1,Type=String,Description=\"Raw SUBR semantics were preserved\">\n",
 };
+// "Merged primitives": behind the lines of the decomposed profile when the merged rows are written
+const char *MERGE_LINES = "##INFO=<ID=MERGED,Number=1,Type=Integer,Description=\"Rows of equal primitives merged into this record\">\n"
+			  "##INFO=<ID=MERGED_FROM,Number=.,Type=String,Description=\"Decomposed ids of the merged rows\">\n";
 const char *ROW_KIND_NAME[] = {"raw", "snp", "ins", "del", "passthrough"};
 const char *ROW_REASON_NAME[] = {"", "max_allele_length", "contig_start", "empty_allele", "equals_ref", "subr_inversion_preservation"};
 
@@ -261,7 +264,11 @@ try {
 	const bool rows = nested_fields && profile == POVU_HIP_PROFILE_DECOMPOSED && c->row_record && c->row_alt && c->row_kind && c->row_reason &&
 			  c->row_index && c->row_pos && c->row_ref_start && c->row_ref_len && c->row_alt_start && c->row_alt_len && c->row_lead &&
 			  c->row_ac && c->row_an && c->row_ns;
-	const uint64_t n_records = c->n_records, n = rows ? c->n_rows : n_records, S = c->n_slots;
+	// the merged rows of "Merged primitives", written instead of the rows when they are there
+	const bool merged = rows && c->mrow_off;
+	if (merged && (!c->mrow_member || !c->mrow_gt || !c->mrow_ac || !c->mrow_an || !c->mrow_ns))
+		return nullptr;
+	const uint64_t n_records = c->n_records, n = merged ? c->n_mrows : rows ? c->n_rows : n_records, S = c->n_slots;
 	const uint32_t P = names->n_paths, n_samples = names->refs.n_samples;
 	for (uint64_t i = 0; i < n_records; i++) {
 		const bool subr = c->flags[i] & POVU_HIP_CALL_SUBR; // (its query is POVU_HIP_NIL: it belongs to no site)
@@ -275,7 +282,7 @@ try {
 		    (subr || c->norm_block[i] >= c->n_blocks || c->block_off[c->norm_block[i]] + c->n_alleles[i] > c->n_spelled))
 			return nullptr;
 	}
-	for (uint64_t k = 0; rows && k < n; k++) {
+	for (uint64_t k = 0; rows && k < c->n_rows; k++) {
 		const uint64_t i = c->row_record[k];
 		if (i >= n_records || !c->row_alt[k] || c->row_alt[k] >= c->n_alleles[i] || c->row_kind[k] > POVU_HIP_ROW_PASS ||
 		    c->row_reason[k] > POVU_HIP_REASON_SUBR)
@@ -287,6 +294,15 @@ try {
 		    (uint64_t)c->row_alt_start[k] + c->row_alt_len[k] > c->seq_off[sa + 1] - c->seq_off[sa])
 			return nullptr;
 	}
+	// every merged row has members, all of them rows, and together they are the rows
+	if (merged && (c->mrow_off[0] != 0 || c->mrow_off[n] != c->n_rows))
+		return nullptr;
+	for (uint64_t g = 0; merged && g < n; g++)
+		if (c->mrow_off[g] >= c->mrow_off[g + 1] || c->mrow_off[g + 1] > c->n_rows)
+			return nullptr;
+	for (uint64_t k = 0; merged && k < c->n_rows; k++)
+		if (c->mrow_member[k] >= c->n_rows)
+			return nullptr;
 	std::vector<uint32_t> slot_first(n_samples + 1, 0); // (the slots of a sample are consecutive)
 	for (uint32_t sl = 0; sl < S; sl++) {
 		if (names->refs.sample_of_slot[sl] >= n_samples)
@@ -302,7 +318,7 @@ try {
 		date = today;
 	}
 	// ---- header, a contig line per reference path of the prefix, the column line
-	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile];
+	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile] + (merged ? MERGE_LINES : "");
 	auto site_label = [&](uint32_t q) {
 		return (sites->or1[q] ? "<" : ">") + std::to_string(sites->id1[q]) + (sites->or2[q] ? "<" : ">") + std::to_string(sites->id2[q]);
 	};
@@ -329,12 +345,22 @@ try {
 		std::vector<uint64_t> order;
 		std::string label, parent;
 		char num[32];
-		for (uint64_t at = lo; at < hi; at++) {
+		// the kind of a row as a primitive: a _ROW_RAW row is the one primitive of its record
+		auto primitive_kind = [&](uint64_t y) -> uint32_t {
+			if (c->row_kind[y] != POVU_HIP_ROW_RAW)
+				return c->row_kind[y];
+			return !c->row_ref_len[y] ? POVU_HIP_ROW_INS : !c->row_alt_len[y] ? POVU_HIP_ROW_DEL : POVU_HIP_ROW_SNP;
+		};
+		for (uint64_t mrow = lo; mrow < hi; mrow++) {
+			// the row that is written: a merged row's representative
+			const uint64_t at = merged ? c->mrow_member[c->mrow_off[mrow]] : mrow;
+			const uint64_t members = merged ? c->mrow_off[mrow + 1] - c->mrow_off[mrow] : 1;
 			const uint64_t i = rows ? c->row_record[at] : at;
 			if (!keep[c->path[i]])
 				continue;
 			// a row of "Decomposed calls" that is no raw record: one ALT, its own POS, texts and counts, the GT row projected
-			const bool prim_row = rows && c->row_kind[at] != POVU_HIP_ROW_RAW;
+			// (a merged row of two or more is none even when its representative is one)
+			const bool prim_row = rows && (c->row_kind[at] != POVU_HIP_ROW_RAW || members > 1);
 			const uint32_t q = c->query[i], na = c->n_alleles[i], ra = c->ref_allele[i];
 			const uint64_t b = c->block_off[c->block[i]];
 			order.clear();
@@ -361,7 +387,8 @@ try {
 				label = site_label(q);
 			}
 			if (prim_row) {
-				const uint32_t k = c->row_alt[at], kind = c->row_kind[at];
+				const uint32_t k = c->row_alt[at], kind = primitive_kind(at);
+				const uint32_t index = c->row_kind[at] == POVU_HIP_ROW_RAW ? 1 : c->row_index[at];
 				const bool passed = kind == POVU_HIP_ROW_PASS;
 				const uint64_t sr = order[0], sa = order[k];
 				const char lead = (char)c->row_lead[at];
@@ -373,7 +400,7 @@ try {
 				if (subr)
 					o += ":subr-passthrough";
 				else
-					o += ":" + std::to_string(k) + ":" + ROW_KIND_NAME[kind] + (passed ? std::string() : std::to_string(c->row_index[at]));
+					o += ":" + std::to_string(k) + ":" + ROW_KIND_NAME[kind] + (passed ? std::string() : std::to_string(index));
 				o += '\t';
 				if (lead)
 					o += lead;
@@ -382,10 +409,10 @@ try {
 				if (lead)
 					o += lead;
 				o.append(c->seq + c->seq_off[sa] + c->row_alt_start[at], c->row_alt_len[at]);
-				const uint32_t an = c->row_an[at];
-				snprintf(num, sizeof num, "%.1f", an ? (double)c->row_ac[at] / an : 0.0);
-				o += "\t60\tPASS\tAC=" + std::to_string(c->row_ac[at]) + ";AF=" + num + ";AN=" + std::to_string(an) +
-				     ";NS=" + std::to_string(c->row_ns[at]) + ";AT=";
+				const uint32_t ac = merged ? c->mrow_ac[mrow] : c->row_ac[at], an = merged ? c->mrow_an[mrow] : c->row_an[at];
+				snprintf(num, sizeof num, "%.1f", an ? (double)ac / an : 0.0);
+				o += "\t60\tPASS\tAC=" + std::to_string(ac) + ";AF=" + num + ";AN=" + std::to_string(an) +
+				     ";NS=" + std::to_string(merged ? c->mrow_ns[mrow] : c->row_ns[at]) + ";AT=";
 				o.append(c->at + c->at_off[sr], c->at_off[sr + 1] - c->at_off[sr]);
 				o += ',';
 				o.append(c->at + c->at_off[sa], c->at_off[sa + 1] - c->at_off[sa]);
@@ -396,6 +423,17 @@ try {
 				o += passed && (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
 				o += ";ORIGIN=" + label + ";RAW_ALT_INDEX=" + std::to_string(k) + ";PROFILE=decomposed;";
 				o += passed ? std::string("PASSTHROUGH=T;PASS_THROUGH_REASON=") + ROW_REASON_NAME[c->row_reason[at]] : std::string("DECOMPOSED=T");
+				if (members > 1) { // the members' decomposed IDs, the representative's first
+					o += ";MERGED=" + std::to_string(members) + ";MERGED_FROM=";
+					for (uint64_t m = c->mrow_off[mrow]; m < c->mrow_off[mrow + 1]; m++) {
+						const uint64_t y = c->mrow_member[m], iy = c->row_record[y];
+						const bool raw = c->row_kind[y] == POVU_HIP_ROW_RAW;
+						if (m > c->mrow_off[mrow])
+							o += ',';
+						o += ((c->flags[iy] & POVU_HIP_CALL_SUBR) ? label : site_label(c->query[iy])) + ":" + std::to_string(c->row_alt[y]) + ":" +
+						     ROW_KIND_NAME[primitive_kind(y)] + std::to_string(raw ? 1 : c->row_index[y]);
+					}
+				}
 				if (subr) {
 					o += ";SUBR_ORIGIN=T";
 				} else {
@@ -406,11 +444,14 @@ try {
 				}
 				o += "\tGT";
 				const uint16_t *grow = c->gt + i * S;
+				const uint8_t *mgt = merged ? c->mrow_gt + mrow * S : nullptr;
+				// 0, 1 or anything else for '.': the merged row's value, else the record's projected on the ALT
+				auto value = [&](uint32_t sl) -> uint32_t { return mgt ? mgt[sl] : grow[sl] == 0 ? 0u : grow[sl] == k ? 1u : 0xFFu; };
 				for (uint32_t sm = 0; sm < n_samples; sm++) {
 					o += '\t';
 					bool any = false;
 					for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++)
-						any |= grow[sl] == 0 || grow[sl] == k;
+						any |= value(sl) <= 1;
 					if (!any) {
 						o += '.';
 						continue;
@@ -418,7 +459,7 @@ try {
 					for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++) {
 						if (sl > slot_first[sm])
 							o += '|';
-						o += grow[sl] == 0 ? "0" : grow[sl] == k ? "1" : ".";
+						o += value(sl) == 0 ? "0" : value(sl) == 1 ? "1" : ".";
 					}
 				}
 				o += '\n';
@@ -447,17 +488,19 @@ try {
 				o.append(c->seq + c->seq_off[sa], c->seq_off[sa + 1] - c->seq_off[sa]);
 			}
 			o += "\t60\tPASS\tAC=";
+			// (a _ROW_RAW row of a merged call: its record has one ALT, the counts and the GT are the merged row's)
 			const uint64_t a0 = c->ac_off[i], a1 = c->ac_off[i + 1];
-			const uint32_t an = c->an[i];
+			const uint32_t an = merged ? c->mrow_an[mrow] : c->an[i];
+			auto ac_of = [&](uint64_t k) { return merged ? c->mrow_ac[mrow] : c->ac[k]; };
 			for (uint64_t k = a0; k < a1; k++)
-				o += (k > a0 ? "," : "") + std::to_string(c->ac[k]);
+				o += (k > a0 ? "," : "") + std::to_string(ac_of(k));
 			o += ";AF=";
 			for (uint64_t k = a0; k < a1; k++) {
-				snprintf(num, sizeof num, "%.1f", an ? (double)c->ac[k] / an : 0.0);
+				snprintf(num, sizeof num, "%.1f", an ? (double)ac_of(k) / an : 0.0);
 				o += (k > a0 ? "," : "");
 				o += num;
 			}
-			o += ";AN=" + std::to_string(an) + ";NS=" + std::to_string(c->ns[i]) + ";AT=";
+			o += ";AN=" + std::to_string(an) + ";NS=" + std::to_string(merged ? c->mrow_ns[mrow] : c->ns[i]) + ";AT=";
 			for (size_t k = 0; k < order.size(); k++) {
 				if (k)
 					o += ',';
@@ -489,11 +532,13 @@ try {
 			}
 			o += "\tGT";
 			const uint16_t *row = c->gt + i * S;
+			const uint8_t *mgt = merged ? c->mrow_gt + mrow * S : nullptr;
+			auto allele = [&](uint32_t sl) -> uint32_t { return !mgt ? row[sl] : mgt[sl] <= 1 ? mgt[sl] : POVU_HIP_GT_MISSING; };
 			for (uint32_t sm = 0; sm < n_samples; sm++) {
 				o += '\t';
 				bool any = false;
 				for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++)
-					any |= row[sl] != POVU_HIP_GT_MISSING;
+					any |= allele(sl) != POVU_HIP_GT_MISSING;
 				if (!any) {
 					o += '.';
 					continue;
@@ -501,7 +546,7 @@ try {
 				for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++) {
 					if (sl > slot_first[sm])
 						o += '|';
-					o += row[sl] == POVU_HIP_GT_MISSING ? "." : std::to_string(row[sl]);
+					o += allele(sl) == POVU_HIP_GT_MISSING ? "." : std::to_string(allele(sl));
 				}
 			}
 			o += '\n';

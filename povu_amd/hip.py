@@ -104,6 +104,9 @@ class _CallNames(C.Structure):
                 ("sample", C.POINTER(C.c_char_p))]
 
 
+MERGE_COUNTERS = ("n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts")  # of Calls, beside n_mrows
+
+
 class _Calls(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("n_records", "n_slots", "n_blocks", "n_spelled", "n_seq_bytes", "n_at_bytes", "n_refs")] +
                 [(k, C.POINTER(C.c_uint32)) for k in ("query", "path", "first", "ref_allele", "n_alleles", "an", "ns", "block")] +
@@ -131,7 +134,12 @@ class _CallsNested(_Calls):
                 [(k, C.POINTER(C.c_uint32)) for k in ("row_ref_start", "row_ref_len", "row_alt_start", "row_alt_len")] +
                 [("row_lead", C.POINTER(C.c_uint8))] +
                 [(k, C.POINTER(C.c_uint32)) for k in ("row_ac", "row_an", "row_ns")] +
-                [(k, C.c_uint64) for k in ("n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells")])
+                [(k, C.c_uint64) for k in ("n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells")] +
+                # "Merged primitives"
+                [("merged", C.c_uint64), ("n_mrows", C.c_uint64), ("mrow_off", C.POINTER(C.c_uint64)),
+                 ("mrow_member", C.POINTER(C.c_uint32)), ("mrow_gt", C.POINTER(C.c_uint8))] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("mrow_ac", "mrow_an", "mrow_ns")] +
+                [(k, C.c_uint64) for k in MERGE_COUNTERS])
 
 
 class _ProfileOpts(C.Structure):
@@ -163,6 +171,9 @@ WALK_MORE, WALK_LONG, WALK_BUDGET = 1, 2, 4  # status bits of a query
 T_FORCE_TIER2 = 1  # HipDecomposer.traversals: every scan through the wave-per-scan kernel (tests)
 T_INVERSIONS = 2  # HipDecomposer.call: inversion (SUBR) records too (INTEGRATION.md "Inversion calls")
 T_NESTED = 4  # HipDecomposer.call: alleles modulo enclosed sites, levels and parents by geometry (INTEGRATION.md "Nested calls")
+# HipDecomposer.call under profile "decomposed" only: equal primitives merged into one row with joint genotypes (INTEGRATION.md
+# "Merged primitives")
+T_MERGE = 8
 TRAV_LONG, TRAV_STRAY, TRAV_OPEN = 1, 2, 4  # status bits of a query
 PROFILES = {"raw-graph": 0, "top-level-only": 1, "popped": 2, "left-normalized": 3, "decomposed": 4}  # HipDecomposer.call(profile=...)
 PRIM_MAX_LENGTH = 512  # `decomposed` profile: the longest allele that is aligned, and the most max_allele_length may ask for
@@ -813,6 +824,17 @@ class Calls:
         self.row_pos = _view(c.row_pos, m, np.uint64)
         self.n_decomposed_alts, self.n_passthrough_alts = int(c.n_decomposed_alts), int(c.n_passthrough_alts)
         self.n_prim_tier2, self.n_prim_cells = int(c.n_prim_tier2), int(c.n_prim_cells)
+        # "Merged primitives" (T_MERGE): the groups of equal rows (none without the flag), their joint genotypes (0, 1, 0xFF for
+        # '.') and counts; the counters
+        self.merged = bool(c.merged)
+        g = self.n_mrows = int(c.n_mrows)
+        self.mrow_off = _view(c.mrow_off, g + 1 if self.merged else 0, np.uint64)
+        self.mrow_member = _view(c.mrow_member, m if self.merged else 0, np.uint32)
+        self.mrow_gt = _view(c.mrow_gt, g * self.n_slots, np.uint8).reshape(g, self.n_slots)
+        for k in ("mrow_ac", "mrow_an", "mrow_ns"):
+            setattr(self, k, _view(getattr(c, k), g, np.uint32))
+        for k in MERGE_COUNTERS:
+            setattr(self, k, int(getattr(c, k)))
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -1032,7 +1054,9 @@ class HipDecomposer:
         Calls.raw_pos, norm_block, norm_shift, norm_chop, norm_trim, flags & CALL_NORMALIZED, the counters); "decomposed"
         implies nothing either, keeps every record and writes every (REF, ALT) as the primitives of its alignment ("Decomposed
         calls": Calls.n_rows, row_*, the counters; max_allele_length is the longest text that is aligned, 0 = PRIM_MAX_LENGTH,
-        more is refused; T_FORCE_TIER2 also sends every aligned pair through the striped kernel)."""
+        more is refused; T_FORCE_TIER2 also sends every aligned pair through the striped kernel; with T_MERGE, which every other
+        profile refuses, equal primitives are merged: Calls.merged, n_mrows, mrow_*, the counters, and vcf_text writes the merged
+        rows)."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names

@@ -12,8 +12,9 @@ timed at:
               "Decomposed calls"); 100000 units
 
 and in any of the modes plain, inversions (T_INVERSIONS), nested (T_NESTED), popped (profile `popped`, max_level 0, both length
-limits --max-length), normalized (profile `left-normalized`), decomposed (profile `decomposed`) and decomposed-tier2 (the same
-with T_FORCE_TIER2: every aligned pair through the striped kernel, for the cells per second of that tier; asked for by name
+limits --max-length), normalized (profile `left-normalized`), decomposed (profile `decomposed`), merged (the same with T_MERGE:
+equal primitives merged; its time less that of decomposed is the merging step's) and decomposed-tier2 (decomposed with
+T_FORCE_TIER2: every aligned pair through the striped kernel, for the cells per second of that tier; asked for by name
 only); without --modes those the input was made for.  One JSON line
 per mode and run: HIP-event time of the call (query upload to the last byte on the host), records, spelled bytes, the
 counters of the mode; then per mode a line with the median of the runs behind the warm-up runs.
@@ -36,9 +37,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "decomposed-tier2")
+MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2")
 DEFAULT_MODES = dict(chain=("plain",), inverted=("plain", "inversions"), skip=("plain", "nested", "popped"), tandem=("plain", "normalized"),
-                     complex=("plain", "decomposed"))
+                     complex=("plain", "decomposed", "merged"))
 
 
 def _load(package_root):
@@ -94,9 +95,11 @@ def child(a):
     kw = dict(plain=lambda: {}, inversions=lambda: dict(flags=H.T_INVERSIONS), nested=lambda: dict(flags=H.T_NESTED),
               popped=lambda: dict(profile="popped", max_level=0, max_ref_length=a.max_length, max_allele_length=a.max_length),
               normalized=lambda: dict(profile="left-normalized"), decomposed=lambda: dict(profile="decomposed"),
+              merged=lambda: dict(profile="decomposed", flags=H.T_MERGE),
               **{"decomposed-tier2": lambda: dict(profile="decomposed", flags=H.T_FORCE_TIER2)})[a.child]()
     counters = ("n_inv_records", "n_inv_tier2", "n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "n_normalized", "max_shift",
-                "n_norm_compared", "n_rows", "n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells")
+                "n_norm_compared", "n_rows", "n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells", "n_mrows",
+                "n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts")
     for run in range(a.warmup + a.runs):
         t0 = time.perf_counter()
         c = d.call(f, [ref], **kw)
