@@ -379,6 +379,7 @@ typedef struct {
 #define POVU_HIP_T_INVERSIONS 2u  /* povu_hip_call only: SUBR records too ("Inversion calls"); ignored elsewhere */
 #define POVU_HIP_T_NESTED 4u	  /* povu_hip_call only: alleles modulo enclosed sites, levels and parents by geometry ("Nested calls") */
 #define POVU_HIP_T_MERGE 8u	  /* povu_hip_call_profile under POVU_HIP_PROFILE_DECOMPOSED only: equal primitives merged ("Merged primitives") */
+#define POVU_HIP_T_OFFREF 16u	  /* povu_hip_call / _call_profile only: sites no reference path crosses, on a surrogate path ("Off-reference calls") */
 #define POVU_HIP_TRAV_LONG 1u	  /* status bits per query: a scan would need more than max_steps steps */
 #define POVU_HIP_TRAV_STRAY 2u	  /* a scan met a boundary step that does not close it */
 #define POVU_HIP_TRAV_OPEN 4u	  /* a scan reached the end of its path */
@@ -525,6 +526,21 @@ typedef struct {
 	uint64_t n_merge_splits;     /* groups split off a run of equal (POS, lengths, hash) by the exact comparison */
 	uint64_t n_ref_consistent;   /* (group, slot) entries that are 0 only because the slot's own ALT lies outside the group's span */
 	uint64_t n_gt_conflicts;     /* (group, slot) entries with a vote for 1 and a vote for 0 (written 1) */
+	/* with POVU_HIP_T_OFFREF ("Off-reference calls").  Without the flag: offref 0, the counts 0, the arrays NULL.  A site that
+	 * is not callable, lies under no subflubble and has a traversal is a candidate; one with no callable or candidate child is
+	 * called off-reference on its surrogate, the path of its first traversal, whose traversals give its records: `path` is
+	 * then the surrogate, `pos` counts along it.  The host of such a record is the tightest traversal by the same path of a
+	 * site the reference paths call (two alleles or more) that strictly encloses it */
+	uint64_t offref;	      /* 1: made with POVU_HIP_T_OFFREF */
+	const uint8_t *rec_offref;    /* [n_records] 1: an off-reference record */
+	const uint32_t *host_query;   /* [n_records] site of the host, POVU_HIP_NIL: none */
+	const uint32_t *host_allele;  /* [n_records] exact allele of the host traversal within its site, POVU_HIP_NIL: none */
+	uint64_t n_off_contigs;	      /* surrogate paths that are no reference path and carry a record */
+	const uint32_t *off_contig_path; /* [n_off_contigs] ascending */
+	const uint64_t *off_contig_len;	 /* [n_off_contigs] bases of the path */
+	uint64_t n_offref_sites;      /* sites called off-reference with two alleles or more */
+	uint64_t n_offref_records;
+	uint64_t n_offref_hosted;     /* off-reference records with a host */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
@@ -532,7 +548,9 @@ typedef struct {
  * more, a spelled byte that is no nucleotide code (the message names the segment), and output beyond device memory.  With
  * POVU_HIP_T_INVERSIONS in opts->flags the inversion records of the reference paths against every other resident path are
  * merged in ((reference path, POS, query, first, n_steps) order; `sites` may be empty); refused then too for 2^32 path
- * steps or run heads or more.  Free with povu_hip_calls_free. */
+ * steps or run heads or more.  With POVU_HIP_T_OFFREF the off-reference records are added (the record order becomes (path,
+ * POS, query, first); inversion records stay those of the reference paths); the flag is refused together with
+ * POVU_HIP_T_NESTED, POVU_HIP_T_MERGE or any profile other than _RAW_GRAPH.  Free with povu_hip_calls_free. */
 povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
 			      const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, char *err, size_t errlen);
 /* The profiles of a nested call ("Nested calls"): what is kept of the flubble records, decided on the device before any
@@ -665,6 +683,14 @@ char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, c
 char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
 				 const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, uint32_t profile,
 				 size_t *len);
+/* With rec_offref not NULL or offref set (POVU_HIP_T_OFFREF; a call without records has no arrays) _vcf_profile writes the off-reference records too: `;OFFREF=T` and, with a host,
+ * `;HOST=<its label>;HA=<its allele>` behind LV, the ##INFO lines of the three keys in front of the contig lines, and behind
+ * the reference paths' contig lines one for every surrogate of off_contig_path (of those the prefix selects); NULL when a
+ * host_query or an off_contig_path points outside its range.  _vcf_rest is the same text for the records whose CHROM starts
+ * with none of the n_prefixes prefixes: no contig line of a reference path, those of the surrogates that start with none */
+char *povu_hip_calls_vcf_rest(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
+			      const char *const *path_name, const char *date, const char *const *prefix, uint32_t n_prefixes, uint32_t threads,
+			      uint32_t profile, size_t *len);
 
 /* ---- measurement (bench.py, povu-stage-cost lines) ---- */
 typedef struct {

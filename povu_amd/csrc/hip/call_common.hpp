@@ -129,7 +129,18 @@ struct CallView {
 	const uint32_t *rlist;
 	const uint8_t *rstate;
 	const uint64_t *xilen, *xatl, *ref_len, *max_len, *raw_pos, *pos;
+	// which traversals of a kept site are records: those by the reference paths (on_ref: [P] reference number of a path,
+	// NO_QUERY: none), or with POVU_HIP_T_OFFREF for a site called off-reference those by its surrogate (sur: [n] that path,
+	// NO_QUERY for a site the references call; null without the flag).  `ref` then holds the references and the surrogates
+	const uint32_t *on_ref, *sur;
 };
+// traversal t of a kept site q by path p is a record
+__device__ __forceinline__ bool is_record_path(const CallView &V, uint32_t q, uint32_t p)
+{
+	if (V.sur && V.sur[q] != NO_QUERY)
+		return p == V.sur[q];
+	return V.on_ref[p] != NO_QUERY;
+}
 
 // ---- a base of a step and of a reference path
 __device__ __forceinline__ uint64_t path_step_len(const PathsView &P, uint32_t x) { return P.seq_off[(x >> 1) + 1] - P.seq_off[x >> 1]; }

@@ -21,10 +21,14 @@
 // first traversal of a class's representative.  What differs per record is kept per record (rstate): whether it is anchored
 // (REF is the reference's own exact allele, the ALTs the representatives), whether REF has no inner base, whether REF is
 // spelled on its own (an "extra" one-allele block behind the class blocks).  A block is a (site, anchored, orientation).
+// With POVU_HIP_T_OFFREF (INTEGRATION.md "Off-reference calls"; offref_kernels.hip) the sites called off-reference join `called`
+// behind callability, and from surrogate_offsets on the view's "reference paths" are the calling paths: the references and the
+// surrogates, ascending.  Which traversals of a kept site are records is asked of is_record_path (call_common.hpp).
 #include "call_common.hpp"
 #include "merge_kernels.hpp"
 #include "nest_kernels.hpp"
 #include "norm_kernels.hpp"
+#include "offref_kernels.hpp"
 #include "prim_kernels.hpp"
 
 namespace povu_hip
@@ -218,7 +222,7 @@ __global__ void k_cl_slots(uint32_t R, const uint32_t *__restrict__ rq, const ui
 __global__ void k_cl_rec_flag(CallView V, uint8_t *__restrict__ flag)
 {
 	for (uint32_t t = blockIdx.x * Q_TPB + threadIdx.x; t < V.trav.R; t += gridDim.x * Q_TPB)
-		flag[t] = V.keep[V.trav.rq[t]] && V.ref.ref_of_path[V.trav.op[t]] != NO_QUERY;
+		flag[t] = V.keep[V.trav.rq[t]] && is_record_path(V, V.trav.rq[t], V.trav.op[t]);
 }
 // reference number of flubble record j
 __device__ __forceinline__ uint32_t ref_of_record(const CallView &V, uint32_t j) { return V.ref.ref_of_path[V.trav.op[V.rlist[j]]]; }
@@ -498,6 +502,11 @@ struct CallsOwner {
 	PinnedVec<uint16_t> gt;
 	PinnedVec<char> seq, at;
 	std::vector<uint64_t> contig_len;
+	// POVU_HIP_T_OFFREF
+	PinnedVec<uint8_t> rec_offref;
+	PinnedVec<uint32_t> host_query, host_allele;
+	std::vector<uint32_t> off_contig_path;
+	std::vector<uint64_t> off_contig_len;
 };
 
 using namespace povu_hip;
@@ -509,7 +518,7 @@ struct CallInputs {
 	const uint32_t *slot_of_path;
 	const povu_hip_trav_opts *opts;
 	uint32_t n, P, nR, S, NS, n_trees = 0;
-	bool inversions, nested, normalized, decomposed, merge;
+	bool inversions, nested, normalized, decomposed, merge, offref;
 	uint32_t prim_cap = 0; // decomposed: the longest text that is aligned
 	povu_hip_call_profile_opts prof; // (raw-graph without a profile)
 	std::vector<uint32_t> ref_of_path, slot_first, qa, qz; // reference number of every path (NO_QUERY: none), first slot of every sample, the queries
@@ -539,6 +548,13 @@ struct CallWs {
 	uint32_t nQ = 0, nfl = 0; // kept sites, flubble records
 	uint32_t *smin, *smax;
 	NormRecs nm; // left-normalized profile: per flubble record what the normalisation found
+	// POVU_HIP_T_OFFREF: `refs` stays the view of the reference paths (callability and the inversions read it), v.ref becomes
+	// that of the calling paths (references and surrogates, ascending) once surrogate_offsets has run
+	RefView refs;
+	std::vector<uint64_t> path_off, call_base; // the paths' first words; first step of every calling path, concatenated
+	std::vector<uint32_t> call_path;
+	OffrefSites os;
+	OffrefHosts oh;
 };
 // the inversion records and where the flubble records go in the one list
 struct CallInv {
@@ -585,6 +601,17 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 	in.prof = profile ? *profile : povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 	if (in.prof.profile > POVU_HIP_PROFILE_DECOMPOSED)
 		throw HipError("unknown profile " + std::to_string(in.prof.profile));
+	in.offref = opts && (opts->flags & POVU_HIP_T_OFFREF);
+	if (in.offref) {
+		static const char *const name[] = {"raw-graph", "top-level-only", "popped", "left-normalized", "decomposed"};
+		if (opts->flags & POVU_HIP_T_NESTED)
+			throw HipError("POVU_HIP_T_OFFREF (off-reference calls) is refused together with POVU_HIP_T_NESTED");
+		if (opts->flags & POVU_HIP_T_MERGE)
+			throw HipError("POVU_HIP_T_OFFREF (off-reference calls) is refused together with POVU_HIP_T_MERGE");
+		if (in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
+			throw HipError(std::string("POVU_HIP_T_OFFREF (off-reference calls) is refused with profile ") + name[in.prof.profile] +
+				       ": only raw-graph");
+	}
 	in.normalized = in.prof.profile == POVU_HIP_PROFILE_LEFT_NORMALIZED; // (keeps every record, ignores the limits, implies nothing)
 	in.decomposed = in.prof.profile == POVU_HIP_PROFILE_DECOMPOSED;	     // (the same; max_allele_length is the cap of the aligner)
 	in.merge = opts && (opts->flags & POVU_HIP_T_MERGE);
@@ -642,7 +669,8 @@ void reference_offsets(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice
 	const ResidentGraph &g = ctx->g;
 	hipStream_t s = ctx->stream;
 	const uint32_t n = in.n, P = in.P, nR = in.nR, NS = in.NS, R = d.R;
-	std::vector<uint64_t> path_off((size_t)P + 1);
+	std::vector<uint64_t> &path_off = w.path_off;
+	path_off.resize((size_t)P + 1);
 	w.ref_base.assign((size_t)nR + 1, 0);
 	HIP_CHECK(copy_async(path_off.data(), ctx->path_off, ((size_t)P + 1) * 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
@@ -669,7 +697,8 @@ void reference_offsets(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice
 	});
 	// the views: everything but the allele table (site_classes) and the number of flubble records (flubble_records)
 	CallView &v = w.v;
-	v.paths = paths_view(ctx), v.trav = trav_view(d), v.ref = RefView{NR, nR, w.d_ref_of_path, w.d_ref_path, w.d_ref_base, w.roff};
+	v.paths = paths_view(ctx), v.trav = trav_view(d), v.ref = w.refs = RefView{NR, nR, w.d_ref_of_path, w.d_ref_path, w.d_ref_base, w.roff};
+	v.on_ref = w.d_ref_of_path, v.sur = nullptr;
 	v.ilen = w.ilen, v.atl = w.atl, v.keep = w.keep, v.zc = w.zc, v.height = w.d_height;
 	v.nfl = 0, v.rlist = w.rlist, v.rstate = w.rstate, v.xilen = w.xilen, v.xatl = w.xatl, v.ref_len = w.ref_len, v.max_len = w.max_len;
 	v.raw_pos = v.pos = w.pos; // (one array until a left-normalisation moves `pos` and keeps the raw POS itself)
@@ -714,11 +743,43 @@ void callability(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, C
 		scan_exclusive_u32(w.scnt, w.soffv, (size_t)g.V + 1, w.tmp, w.tmp_bytes, s);
 		KLAUNCH(k_cl_seg_fill, dim3(stride_blocks(2 * (size_t)n)), dim3(Q_TPB), 0, s, n, w.qv, w.soffv, w.scur, w.sval);
 		if (NR)
-			KLAUNCH(k_cl_hits, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, w.v.ref, w.v.paths, w.soffv, w.sval, w.hit);
+			KLAUNCH(k_cl_hits, dim3(stride_blocks(NR)), dim3(Q_TPB), 0, s, w.refs, w.v.paths, w.soffv, w.sval, w.hit);
 		KLAUNCH(k_cl_present, dim3(stride_blocks((size_t)n * nR)), dim3(Q_TPB), 0, s, (uint64_t)n, nR, w.hit, w.d_tree, w.pres);
 		KLAUNCH(k_cl_callable, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, nR, w.hit, w.pres, w.d_tree, w.d_parent, w.d_fam, w.callable, w.called);
 		KLAUNCH(k_cl_unparent, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.callable, w.d_parent, w.called);
 	}
+}
+
+// POVU_HIP_T_OFFREF: the sites called off-reference and their surrogates; `called` becomes the union
+void offref_sites_step(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
+{
+	w.os = offref_sites(ctx, d, in.n, w.d_parent, w.d_fam, w.callable, w.called, w.d_ref_of_path);
+	w.v.sur = w.os.sur;
+}
+// ... the offsets of the calling paths, exactly as for the references: their steps concatenated, k_cl_ref_len's gather, one
+// u64 scan; the call's view of "the reference paths" is theirs from here on
+void surrogate_offsets(povu_hip_ctx *ctx, const CallInputs &in, CallWs &w)
+{
+	hipStream_t s = ctx->stream;
+	const uint32_t nC = w.os.n_call;
+	w.call_path.resize(nC);
+	if (nC)
+		HIP_CHECK(copy_async(w.call_path.data(), w.os.call_path, (size_t)nC * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	w.call_base.assign((size_t)nC + 1, 0);
+	for (uint32_t k = 0; k < nC; k++) {
+		if (w.call_path[k] >= in.P)
+			throw HipError("off-reference calls: a calling path is no resident path");
+		w.call_base[k + 1] = w.call_base[k] + w.path_off[w.call_path[k] + 1] - w.path_off[w.call_path[k]];
+	}
+	const uint64_t NC = w.call_base[nC];
+	const OffrefView ov = offref_view(ctx, w.os, NC);
+	HIP_CHECK(copy_async(ov.ref_base, w.call_base.data(), ((size_t)nC + 1) * 8, hipMemcpyHostToDevice, s));
+	w.v.ref = RefView{NC, nC, ov.ref_of_path, w.os.call_path, ov.ref_base, ov.roff};
+	HIP_CHECK(hipMemsetAsync(ov.rlen + NC, 0, 8, s));
+	if (NC)
+		KLAUNCH(k_cl_ref_len, dim3(stride_blocks(NC)), dim3(Q_TPB), 0, s, w.v.ref, w.v.paths, ov.rlen);
+	scan_exclusive_u64(ov.rlen, ov.roff, NC + 1, ov.s64, s);
 }
 
 // what the rest of the call reads as the alleles of a site: the exact alleles, or the classes of a nested call
@@ -774,7 +835,7 @@ void slot_table(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, Ca
 void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, CallWs &w)
 {
 	hipStream_t s = ctx->stream;
-	const uint32_t R = d.R, nR = in.nR;
+	const uint32_t R = d.R, nR = w.v.ref.nR; // (the calling paths)
 	if (R && w.nQ) {
 		KLAUNCH(k_cl_rec_flag, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, w.v, w.rflag);
 		compact_flagged_u8(w.rflag, R, w.rlist, w.words + 2, w.tmp, w.tmp_bytes, s);
@@ -782,7 +843,7 @@ void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &
 	}
 	const uint32_t nfl_all = w.nfl_all = w.v.nfl = w.nfl;
 	refuse_2_32(nfl_all, "the call needs ", "records");
-	const uint64_t ref_bases = read_back(w.roff + w.NR, s);
+	const uint64_t ref_bases = read_back(w.v.ref.roff + w.v.ref.NR, s);
 	if (!nfl_all)
 		return;
 	// per record: anchored, REF's own lengths; POS; with POVU_HIP_T_NESTED parents, levels and the profile's choice
@@ -816,6 +877,28 @@ void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &
 	w.perm = sort.cur;
 }
 
+// POVU_HIP_T_OFFREF: the rows' arrays, and the surrogates that are no reference path with their lengths
+struct CallOffref {
+	OffrefRows rows;
+	std::vector<uint32_t> contig_path;
+	std::vector<uint64_t> contig_len;
+};
+void offref_rows_step(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, const CallRecs &r, CallOffref &o)
+{
+	hipStream_t s = ctx->stream;
+	o.rows = offref_rows(ctx, w.v, w.os, w.oh, r.nrec, w.nfl, w.perm, inv.f_dst);
+	const uint32_t nC = w.os.n_call;
+	std::vector<uint64_t> at((size_t)nC + 1, 0);
+	for (uint32_t k = 0; k <= nC; k++)
+		HIP_CHECK(copy_async(at.data() + k, w.v.ref.roff + w.call_base[k], 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	for (uint32_t k = 0; k < nC; k++)
+		if (in.ref_of_path[w.call_path[k]] == NO_QUERY) {
+			o.contig_path.push_back(w.call_path[k]);
+			o.contig_len.push_back(at[k + 1] - at[k]);
+		}
+}
+
 // the inversion records, and every record's row in the one list; gives the number of all records
 uint32_t inversion_rows(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, CallInv &inv)
 {
@@ -824,7 +907,7 @@ uint32_t inversion_rows(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w
 	if (!in.inversions)
 		return nfl;
 	InvIn &iin = inv.in;
-	iin.paths = w.v.paths, iin.ref = w.v.ref, iin.slots = w.slots;
+	iin.paths = w.v.paths, iin.ref = w.refs, iin.slots = w.slots;
 	iin.max_steps = in.opts->max_steps ? in.opts->max_steps : 65536;
 	iin.force_tier2 = (in.opts->flags & POVU_HIP_T_FORCE_TIER2) != 0;
 	inv.v = inv_find(ctx, iin);
@@ -836,7 +919,13 @@ uint32_t inversion_rows(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w
 	carve(ctx->iv_rows, [&](Spans &take) { take((size_t)nfl + 1, f_ref, inv.f_dst, f_pos); });
 	if (nfl)
 		KLAUNCH(k_cl_sorted_keys, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.v, f_ref, f_pos);
-	inv_merge(ctx, inv.v, nfl, f_ref, f_pos, inv.f_dst);
+	if (in.offref) { // the one list is ordered by the calling paths: the inversion records' references numbered among them
+		InvDevice m = inv.v;
+		m.ref = offref_inv_refs(ctx, inv.v.n, inv.v.ref, w.refs.ref_path, w.v.ref.ref_of_path);
+		inv_merge(ctx, m, nfl, f_ref, f_pos, inv.f_dst);
+	} else {
+		inv_merge(ctx, inv.v, nfl, f_ref, f_pos, inv.f_dst);
+	}
 	return nfl + inv.v.n;
 }
 
@@ -993,7 +1082,7 @@ PrimIn primitive_input(const CallInputs &in, const CallWs &w, const CallRecs &r,
 }
 
 povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, const CallRecs &r, const CallSpelled &sp,
-			      const PrimRows &pr, const MergedRows &mg, CallTimer &timer)
+			      const PrimRows &pr, const MergedRows &mg, const CallOffref &orf, CallTimer &timer)
 {
 	const uint32_t nrec = r.nrec, nb = r.L.nb, nR = in.nR, S = in.S;
 	const uint64_t nsp = r.L.nsp;
@@ -1066,6 +1155,16 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 		give(o->mrow_an, v.mrow_an, mg.an, g);
 		give(o->mrow_ns, v.mrow_ns, mg.ns, g);
 	}
+	if (in.offref) { // (without the flag: the arrays NULL, the counts 0)
+		give(o->rec_offref, v.rec_offref, orf.rows.rec_offref, nrec);
+		give(o->host_query, v.host_query, orf.rows.host_query, nrec);
+		give(o->host_allele, v.host_allele, orf.rows.host_allele, nrec);
+		o->off_contig_path = orf.contig_path, o->off_contig_len = orf.contig_len;
+		v.off_contig_path = o->off_contig_path.data(), v.off_contig_len = o->off_contig_len.data();
+		v.n_off_contigs = orf.contig_path.size();
+		v.offref = 1;
+		v.n_offref_sites = w.os.n_sites, v.n_offref_records = orf.rows.n_records, v.n_offref_hosted = orf.rows.n_hosted;
+	}
 	v.device_ms = timer.stop(ctx->stream);
 	for (const auto &fill : defaults)
 		fill();
@@ -1115,20 +1214,29 @@ extern "C" povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_h
 		CallWs w;
 		reference_offsets(ctx, in, d, w);
 		callability(ctx, in, d, w);
+		if (in.offref) {
+			offref_sites_step(ctx, in, d, w);
+			surrogate_offsets(ctx, in, w);
+		}
 		site_classes(ctx, in, d, w);
 		kept_sites(ctx, in, d, w);
 		slot_table(ctx, in, d, w);
 		flubble_records(ctx, in, d, w);
+		if (in.offref)
+			w.oh = offref_hosts(ctx, d, w.v, w.os);
 		CallInv inv;
 		CallRecs r;
 		r.nrec = inversion_rows(ctx, in, w, inv);
 		record_arrays(ctx, in, w, inv, r);
 		CallSpelled sp;
 		spelling(ctx, in, w, inv, r, sp);
+		CallOffref orf;
+		if (in.offref)
+			offref_rows_step(ctx, in, w, inv, r, orf);
 		const PrimIn pin = in.decomposed ? primitive_input(in, w, r, sp) : PrimIn{};
 		const PrimRows pr = in.decomposed ? prim_rows(ctx, pin) : PrimRows{};
 		const MergedRows mg = in.merge ? merge_rows(ctx, pin, pr) : MergedRows{};
-		return calls_to_host(ctx, in, w, inv, r, sp, pr, mg, timer);
+		return calls_to_host(ctx, in, w, inv, r, sp, pr, mg, orf, timer);
 	});
 }
 

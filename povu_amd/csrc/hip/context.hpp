@@ -330,6 +330,9 @@ struct povu_hip_ctx {
 	// povu_hip_call with POVU_HIP_T_NESTED (nest_kernels.hip): the index of the called sites' traversals / the classes / the
 	// scratch of both / the records' parents, levels and the profile's choice
 	Arena ns_idx, ns_cls, ns_ws, ns_rec;
+	// povu_hip_call with POVU_HIP_T_OFFREF (offref_kernels.hip): the sites' surrogates and the calling paths / the view of the
+	// calling paths / the inversion records' numbers among them / the host index and offers / the rows' arrays
+	Arena or_ws, or_view, or_inv, or_host, or_rows;
 	uint64_t *seq_off = nullptr;
 	char *seq = nullptr;
 	uint64_t seq_gen = 0;

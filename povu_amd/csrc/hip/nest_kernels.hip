@@ -33,20 +33,6 @@ namespace povu_hip
 
 static constexpr uint32_t N1_STEPS = 64; // steps of the longest allele tier 1 covers
 
-// first entry whose position is at least x
-__device__ __forceinline__ uint32_t first_at_least(const uint64_t *__restrict__ ipos, uint32_t ni, uint64_t x)
-{
-	uint32_t lo = 0, hi = ni;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (ipos[mid] < x)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-
 // ---- index
 __global__ void k_ns_called_flag(uint32_t R, const uint32_t *__restrict__ rq, const uint8_t *__restrict__ called, uint8_t *__restrict__ flag)
 {
@@ -72,6 +58,29 @@ __global__ void k_ns_index(uint32_t ni, const uint32_t *__restrict__ perm, const
 		iq[k] = rq[t];
 		it[k] = t;
 	}
+}
+
+// the index of the flagged traversals: compacted, radix-sorted by global position
+void nest_index(povu_hip_ctx *ctx, const TravDevice &d, const uint8_t *flag, NestIndex &ix, const NestIndexWs &w)
+{
+	hipStream_t s = ctx->stream;
+	const uint32_t R = d.R;
+	ix.ni = 0;
+	if (R) {
+		compact_flagged_u8(flag, R, w.ilist, w.count, w.tmp, w.tmp_bytes, s);
+		ix.ni = read_back(w.count, s);
+	}
+	const uint32_t ni = ix.ni;
+	if (!ni)
+		return;
+	LsdSort sort{w.ilist, w.pb, w.key, w.kout, ni, w.tmp, w.tmp_bytes, s};
+	auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
+		KLAUNCH(k_ns_pos_key, dim3(stride_blocks(ni)), dim3(Q_TPB), 0, s, ni, which, perm, d.rpos, k);
+	};
+	sort.pass(0, (unsigned)std::min<uint64_t>(32, bits_for(ctx->n_path_steps)), write_key);
+	if (ctx->n_path_steps >= (1ull << 32))
+		sort.pass(1, 32, write_key);
+	KLAUNCH(k_ns_index, dim3(stride_blocks(ni)), dim3(Q_TPB), 0, s, ni, sort.cur, d.rpos, d.rlen, d.rq, ix.ipos, ix.iend, ix.iq, ix.it);
 }
 
 // ---- cover and skeleton
@@ -299,22 +308,10 @@ NestClasses nest_classes(povu_hip_ctx *ctx, const TravDevice &d, const uint8_t *
 	});
 	HIP_CHECK(hipMemsetAsync(words, 0, 32, s));
 	// ---- index
-	if (R) {
+	if (R)
 		KLAUNCH(k_ns_called_flag, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, d.rq, called, flag);
-		compact_flagged_u8(flag, R, ilist, words, tmp, tmp_bytes, s);
-		ix.ni = read_back(words, s);
-	}
+	nest_index(ctx, d, flag, ix, NestIndexWs{ilist, pb, key, kout, words, tmp, tmp_bytes});
 	const uint32_t ni = ix.ni;
-	if (ni) {
-		LsdSort sort{ilist, pb, key, kout, ni, tmp, tmp_bytes, s};
-		auto write_key = [&](int which, const uint32_t *perm, uint32_t *k) {
-			KLAUNCH(k_ns_pos_key, dim3(stride_blocks(ni)), dim3(Q_TPB), 0, s, ni, which, perm, d.rpos, k);
-		};
-		sort.pass(0, (unsigned)std::min<uint64_t>(32, bits_for(ctx->n_path_steps)), write_key);
-		if (ctx->n_path_steps >= (1ull << 32))
-			sort.pass(1, 32, write_key);
-		KLAUNCH(k_ns_index, dim3(stride_blocks(ni)), dim3(Q_TPB), 0, s, ni, sort.cur, d.rpos, d.rlen, d.rq, ix.ipos, ix.iend, ix.iq, ix.it);
-	}
 	if (!n_al) {
 		HIP_CHECK(hipMemsetAsync(c.coff, 0, n1 * 4, s));
 		return c;

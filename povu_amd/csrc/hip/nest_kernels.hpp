@@ -14,6 +14,28 @@ struct NestIndex {
 	uint64_t *ipos = nullptr, *iend = nullptr;
 	uint32_t *iq = nullptr, *it = nullptr;
 };
+// first entry whose position is at least x
+__device__ __forceinline__ uint32_t first_at_least(const uint64_t *__restrict__ ipos, uint32_t ni, uint64_t x)
+{
+	uint32_t lo = 0, hi = ni;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (ipos[mid] < x)
+			lo = mid + 1;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+// The index of the traversals flagged in flag[0 .. R): ix's arrays (R + 1 entries each, the caller's) filled, ix.ni set.
+// The scratch is the caller's: four lists of R + 1, one cleared word, prim_tmp_bytes(R + 1, true) bytes.  Waits for the stream
+struct NestIndexWs {
+	uint32_t *ilist, *pb, *key, *kout, *count;
+	void *tmp;
+	size_t tmp_bytes;
+};
+void nest_index(povu_hip_ctx *ctx, const TravDevice &d, const uint8_t *flag, NestIndex &ix, const NestIndexWs &w);
+
 // the classes: of site q the classes [coff[q], coff[q + 1]), numbered in the order of their lowest exact allele; of class c its
 // representative's global allele crep[c] and that allele's first traversal cfirst[c]; of traversal t its class within its
 // site, oc[t]

@@ -30,6 +30,7 @@ struct CallArgs {
 	bool inversions = false; // --inversions: SUBR records too (INTEGRATION.md "Inversion calls")
 	bool nested = false;	 // --nested, or implied by a profile (INTEGRATION.md "Nested calls")
 	bool merge = false;	 // --merge-primitives, with --profile decomposed alone (INTEGRATION.md "Merged primitives")
+	bool offref = false;	 // --off-reference: sites no reference path crosses, on a surrogate path (INTEGRATION.md "Off-reference calls")
 	povu_hip_call_profile_opts prof{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 };
 
@@ -79,6 +80,8 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			c.nested = true;
 		} else if (x == "--merge-primitives") {
 			c.merge = true;
+		} else if (x == "--off-reference") {
+			c.offref = true;
 		} else if (x == "--profile" || !x.compare(0, 10, "--profile=")) {
 			const std::string v = x == "--profile" ? need(i) : x.substr(10);
 			if (v == "raw-graph")
@@ -116,6 +119,12 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 	}
 	if (c.merge && c.prof.profile != POVU_HIP_PROFILE_DECOMPOSED)
 		throw std::runtime_error("Flag '--merge-primitives' merges the rows of --profile decomposed and needs that profile");
+	if (c.offref && c.nested)
+		throw std::runtime_error("Flag '--off-reference' cannot be combined with --nested");
+	if (c.offref && c.merge)
+		throw std::runtime_error("Flag '--off-reference' cannot be combined with --merge-primitives");
+	if (c.offref && c.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
+		throw std::runtime_error("Flag '--off-reference' is called under --profile raw-graph alone");
 	forms = (int)by_p + (int)!ref_file.empty() + (int)by_pos;
 	if (forms != 1)
 		throw std::runtime_error("call needs exactly one of the reference options: -r <file>, -P <prefix> (repeatable), or "
@@ -217,7 +226,8 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 		fail("paths");
 	if (povu_hip_segments_upload(ctx, V, seq_off.data(), seq.data(), err, sizeof err) != 0)
 		fail("sequences");
-	const povu_hip_trav_opts opts{0, (ca.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (ca.nested ? POVU_HIP_T_NESTED : 0u) | (ca.merge ? POVU_HIP_T_MERGE : 0u)};
+	const povu_hip_trav_opts opts{0, (ca.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (ca.nested ? POVU_HIP_T_NESTED : 0u) | (ca.merge ? POVU_HIP_T_MERGE : 0u) |
+						 (ca.offref ? POVU_HIP_T_OFFREF : 0u)};
 	povu_hip_calls *c = povu_hip_call_profile(ctx, sites, &nm->refs, nm->slot_of_path, &opts, &ca.prof, err, sizeof err);
 	if (!c)
 		fail("call");
@@ -242,6 +252,22 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 			if (!os)
 				throw std::runtime_error("cannot write " + ca.out_dir + "/" + p + ".vcf");
 			write(os, p.c_str());
+		}
+		// the off-reference records no prefix takes
+		bool rest = false;
+		for (uint64_t i = 0; ca.offref && !rest && i < c->n_records; i++)
+			rest = c->rec_offref[i] && std::none_of(ca.prefixes.begin(), ca.prefixes.end(), [&](const std::string &p) {
+				       return !strncmp(names[c->path[i]], p.c_str(), p.size());
+			       });
+		if (rest) {
+			size_t len = 0;
+			char *text = povu_hip_calls_vcf_rest(c, sites, nm, names.data(), nullptr, prefixes.data(), (uint32_t)prefixes.size(),
+							     (uint32_t)std::max(1, cfg.threads), ca.prof.profile, &len);
+			std::ofstream os(ca.out_dir + "/off-reference.vcf");
+			if (!text || !os)
+				throw std::runtime_error("cannot write " + ca.out_dir + "/off-reference.vcf");
+			os.write(text, (std::streamsize)len);
+			povu_hip_buffer_free(text);
 		}
 	}
 	povu_hip_calls_free(c);

@@ -229,7 +229,8 @@ extern "C" void povu_hip_sites_free(povu_hip_sites *s)
 namespace
 {
 char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names, const char *const *path_name,
-		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len);
+		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len,
+		const char *const *rest_prefix = nullptr, uint32_t n_rest = 0, bool rest = false);
 }
 
 extern "C" char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
@@ -246,10 +247,31 @@ extern "C" char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_
 	return calls_vcf(c, sites, names, path_name, date, only_prefix, threads, profile, true, len);
 }
 
+extern "C" char *povu_hip_calls_vcf_rest(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
+					 const char *const *path_name, const char *date, const char *const *prefix, uint32_t n_prefixes,
+					 uint32_t threads, uint32_t profile, size_t *len)
+{
+	if (n_prefixes && !prefix)
+		return nullptr;
+	for (uint32_t k = 0; k < n_prefixes; k++)
+		if (!prefix[k])
+			return nullptr;
+	return calls_vcf(c, sites, names, path_name, date, nullptr, threads, profile, true, len, prefix, n_prefixes, true);
+}
+
 namespace
 {
+// the lines of "Off-reference calls", behind the header of a call made with POVU_HIP_T_OFFREF
+const char OFFREF_LINES[] =
+	"##INFO=<ID=OFFREF,Number=0,Type=Flag,Description=\"Called off the reference paths: CHROM is the surrogate path, the first path that "
+	"traverses the site\">\n"
+	"##INFO=<ID=HOST,Number=1,Type=String,Description=\"ID of the tightest site called on the reference paths that encloses the record on "
+	"its path\">\n"
+	"##INFO=<ID=HA,Number=1,Type=Integer,Description=\"Allele of the record's path in HOST, numbered in traversal order\">\n";
+
 char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names, const char *const *path_name,
-		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len)
+		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len,
+		const char *const *rest_prefix, uint32_t n_rest, bool rest)
 try {
 	if (!c || !sites || !names || !path_name || !len || c->n_slots != names->refs.n_slots || c->n_refs != names->refs.n_refs ||
 	    profile > POVU_HIP_PROFILE_DECOMPOSED)
@@ -266,6 +288,12 @@ try {
 			  c->row_ac && c->row_an && c->row_ns;
 	// the merged rows of "Merged primitives", written instead of the rows when they are there
 	const bool merged = rows && c->mrow_off;
+	// the arrays of "Off-reference calls" (absent: the text of the call without the flag)
+	// (a call with the flag and no record has no array to show for it: `offref` says so)
+	const bool offref = nested_fields && (c->rec_offref || c->offref);
+	if (offref && ((c->n_records && (!c->rec_offref || !c->host_query || !c->host_allele)) ||
+		       (c->n_off_contigs && (!c->off_contig_path || !c->off_contig_len))))
+		return nullptr;
 	if (merged && (!c->mrow_member || !c->mrow_gt || !c->mrow_ac || !c->mrow_an || !c->mrow_ns))
 		return nullptr;
 	const uint64_t n_records = c->n_records, n = merged ? c->n_mrows : rows ? c->n_rows : n_records, S = c->n_slots;
@@ -277,6 +305,8 @@ try {
 		if (parent_query && parent_query[i] != POVU_HIP_NIL && parent_query[i] >= sites->n)
 			return nullptr;
 		if (ref_spelled && ref_spelled[i] >= c->n_spelled)
+			return nullptr;
+		if (offref && c->host_query[i] != POVU_HIP_NIL && c->host_query[i] >= sites->n)
 			return nullptr;
 		if (normalized && (c->flags[i] & POVU_HIP_CALL_NORMALIZED) &&
 		    (subr || c->norm_block[i] >= c->n_blocks || c->block_off[c->norm_block[i]] + c->n_alleles[i] > c->n_spelled))
@@ -318,7 +348,16 @@ try {
 		date = today;
 	}
 	// ---- header, a contig line per reference path of the prefix, the column line
-	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile] + (merged ? MERGE_LINES : "");
+	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile] + (merged ? MERGE_LINES : "") + (offref ? OFFREF_LINES : "");
+	// the paths whose lines and records are written: those of the prefix (every one without), or with `rest` of no prefix
+	auto takes = [&](const char *name) {
+		if (!rest)
+			return !only_prefix || !strncmp(name, only_prefix, strlen(only_prefix));
+		for (uint32_t k = 0; k < n_rest; k++)
+			if (!strncmp(name, rest_prefix[k], strlen(rest_prefix[k])))
+				return false;
+		return true;
+	};
 	auto site_label = [&](uint32_t q) {
 		return (sites->or1[q] ? "<" : ">") + std::to_string(sites->id1[q]) + (sites->or2[q] ? "<" : ">") + std::to_string(sites->id2[q]);
 	};
@@ -327,10 +366,19 @@ try {
 		const uint32_t p = names->refs.ref_path[r];
 		if (p >= P)
 			return nullptr;
-		if (only_prefix && strncmp(path_name[p], only_prefix, strlen(only_prefix)))
+		if (!takes(path_name[p]))
 			continue;
 		keep[p] = 1;
 		head += std::string("##contig=<ID=") + path_name[p] + ",length=" + std::to_string(c->contig_len[r]) + ">\n";
+	}
+	for (uint64_t k = 0; offref && k < c->n_off_contigs; k++) { // the surrogates that are no reference path
+		const uint32_t p = c->off_contig_path[k];
+		if (p >= P)
+			return nullptr;
+		if (!takes(path_name[p]))
+			continue;
+		keep[p] = 1;
+		head += std::string("##contig=<ID=") + path_name[p] + ",length=" + std::to_string(c->off_contig_len[k]) + ">\n";
 	}
 	head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
 	for (uint32_t sm = 0; sm < n_samples; sm++)
@@ -512,6 +560,11 @@ try {
 				o += ";ES=" + label + ";LV=" + std::to_string(level ? (long)(int32_t)level[i] : (long)sites->height[q] - 1);
 				if (nested && has_parent)
 					o += ";PS=" + parent;
+				if (offref && c->rec_offref[i]) {
+					o += ";OFFREF=T";
+					if (c->host_query[i] != POVU_HIP_NIL)
+						o += ";HOST=" + site_label(c->host_query[i]) + ";HA=" + std::to_string(c->host_allele[i]);
+				}
 				if (norm) {
 					o += ";ORIGIN=" + label + ";RAW_ALT_INDEX=";
 					for (size_t k = 1; k < order.size(); k++)

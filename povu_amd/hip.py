@@ -104,6 +104,7 @@ class _CallNames(C.Structure):
                 ("sample", C.POINTER(C.c_char_p))]
 
 
+OFFREF_COUNTERS = ("n_offref_sites", "n_offref_records", "n_offref_hosted")  # of Calls
 MERGE_COUNTERS = ("n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts")  # of Calls, beside n_mrows
 
 
@@ -139,7 +140,12 @@ class _CallsNested(_Calls):
                 [("merged", C.c_uint64), ("n_mrows", C.c_uint64), ("mrow_off", C.POINTER(C.c_uint64)),
                  ("mrow_member", C.POINTER(C.c_uint32)), ("mrow_gt", C.POINTER(C.c_uint8))] +
                 [(k, C.POINTER(C.c_uint32)) for k in ("mrow_ac", "mrow_an", "mrow_ns")] +
-                [(k, C.c_uint64) for k in MERGE_COUNTERS])
+                [(k, C.c_uint64) for k in MERGE_COUNTERS] +
+                # "Off-reference calls"
+                [("offref", C.c_uint64), ("rec_offref", C.POINTER(C.c_uint8)), ("host_query", C.POINTER(C.c_uint32)),
+                 ("host_allele", C.POINTER(C.c_uint32)), ("n_off_contigs", C.c_uint64), ("off_contig_path", C.POINTER(C.c_uint32)),
+                 ("off_contig_len", C.POINTER(C.c_uint64))] +
+                [(k, C.c_uint64) for k in OFFREF_COUNTERS])
 
 
 class _ProfileOpts(C.Structure):
@@ -174,6 +180,9 @@ T_NESTED = 4  # HipDecomposer.call: alleles modulo enclosed sites, levels and pa
 # HipDecomposer.call under profile "decomposed" only: equal primitives merged into one row with joint genotypes (INTEGRATION.md
 # "Merged primitives")
 T_MERGE = 8
+# HipDecomposer.call under profile "raw-graph" only, not with T_NESTED or T_MERGE: the sites no reference path crosses, called
+# on the first path that traverses them (INTEGRATION.md "Off-reference calls")
+T_OFFREF = 16
 TRAV_LONG, TRAV_STRAY, TRAV_OPEN = 1, 2, 4  # status bits of a query
 PROFILES = {"raw-graph": 0, "top-level-only": 1, "popped": 2, "left-normalized": 3, "decomposed": 4}  # HipDecomposer.call(profile=...)
 PRIM_MAX_LENGTH = 512  # `decomposed` profile: the longest allele that is aligned, and the most max_allele_length may ask for
@@ -245,6 +254,9 @@ def load_lib():
     l.povu_hip_calls_vcf_profile.argtypes = [C.POINTER(_CallsNested), C.POINTER(_Sites), C.POINTER(_CallNames), C.POINTER(C.c_char_p),
                                              C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
     l.povu_hip_calls_vcf_profile.restype = C.c_void_p
+    l.povu_hip_calls_vcf_rest.argtypes = [C.POINTER(_CallsNested), C.POINTER(_Sites), C.POINTER(_CallNames), C.POINTER(C.c_char_p),
+                                          C.c_char_p, C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
+    l.povu_hip_calls_vcf_rest.restype = C.c_void_p
     l.povu_hip_calls_free.argtypes = [C.POINTER(_Calls)]
     l.povu_hip_call_names_make.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_char_p), C.c_char_p,
                                            C.c_size_t]
@@ -835,6 +847,17 @@ class Calls:
             setattr(self, k, _view(getattr(c, k), g, np.uint32))
         for k in MERGE_COUNTERS:
             setattr(self, k, int(getattr(c, k)))
+        # "Off-reference calls" (T_OFFREF): per record whether it is one, its host's site and allele (0xFFFFFFFF: none); the
+        # surrogate paths that are no reference path, with their lengths; the counters.  Without the flag: empty, 0
+        self.offref = bool(c.offref)
+        k = n if self.offref else 0
+        self.rec_offref = _view(c.rec_offref, k, np.uint8)
+        self.host_query = _view(c.host_query, k, np.uint32)
+        self.host_allele = _view(c.host_allele, k, np.uint32)
+        self.off_contig_path = _view(c.off_contig_path, int(c.n_off_contigs), np.uint32)
+        self.off_contig_len = _view(c.off_contig_len, int(c.n_off_contigs), np.uint64)
+        for k in OFFREF_COUNTERS:
+            setattr(self, k, int(getattr(c, k)))
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -853,6 +876,20 @@ class Calls:
                                                  None if date is None else str(date).encode(),
                                                  None if only is None else only.encode(), threads,
                                                  PROFILES[self.profile if profile is None else profile], C.byref(ln))
+        if not p:
+            raise RuntimeError("the calls, sites and names do not belong together")
+        s = C.string_at(p, ln.value).decode()
+        self._lib.povu_hip_buffer_free(p)
+        return s
+
+    def vcf_rest_text(self, prefixes, date=None, threads: int = 1) -> str:
+        """The VCF of the records whose CHROM starts with none of `prefixes` (povu_hip_calls_vcf_rest): the off-reference.vcf of
+        `povu call -o DIR --off-reference`."""
+        ln = C.c_size_t(0)
+        arr = (C.c_char_p * max(1, len(prefixes)))(*[x.encode() for x in prefixes])
+        p = self._lib.povu_hip_calls_vcf_rest(self._p, self._sites._p, self._names_rec, self._name_array,
+                                              None if date is None else str(date).encode(), arr, len(prefixes), threads,
+                                              PROFILES[self.profile], C.byref(ln))
         if not p:
             raise RuntimeError("the calls, sites and names do not belong together")
         s = C.string_at(p, ln.value).decode()
@@ -1056,7 +1093,9 @@ class HipDecomposer:
         calls": Calls.n_rows, row_*, the counters; max_allele_length is the longest text that is aligned, 0 = PRIM_MAX_LENGTH,
         more is refused; T_FORCE_TIER2 also sends every aligned pair through the striped kernel; with T_MERGE, which every other
         profile refuses, equal primitives are merged: Calls.merged, n_mrows, mrow_*, the counters, and vcf_text writes the merged
-        rows)."""
+        rows).  T_OFFREF ("Off-reference calls", raw-graph alone, refused with T_NESTED and T_MERGE): the sites no reference path
+        crosses are called on their surrogate path; Calls.offref, rec_offref, host_query, host_allele, off_contig_*, the
+        counters."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names

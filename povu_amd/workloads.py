@@ -696,6 +696,46 @@ def skip_haplotypes(n_units: int, depth: int, n: int, seed: int, width: int = 2)
     return _paths([f"hap{h}#1#chr1" for h in range(n)], pieces)
 
 
+_INSERTION_UNIT = 8  # entry, two segments of the reference arm, the insertion arm (open, SNP x | y, close), exit
+_INSERTION_LINKS = [(0, 1), (1, 2), (2, 7), (0, 3), (3, 4), (3, 5), (4, 6), (5, 6), (6, 7)]
+
+
+def insertion_units(n_units: int, seed: int = 0) -> Links:
+    """Variation inside sequence a reference does not have ("Off-reference calls"): a unit is an entry segment, a reference arm
+    of two segments, an insertion arm (open, a two-way SNP bubble x | y, close) and an exit segment; `n_units` units joined end
+    to end, ids 1.. in path order, 8 segments a unit.  The unit's site is crossed by every haplotype, the SNP's only by those
+    that carry the insertion.  (`seed` is unused: the shape is fixed; insertion_haplotypes draws.)"""
+    size = _INSERTION_UNIT
+    base = size * np.arange(n_units, dtype=np.int64)[:, None]
+    la = np.array(_INSERTION_LINKS, dtype=np.int64)
+    src = (base + la[:, 0][None, :]).reshape(-1)
+    dst = (base + la[:, 1][None, :]).reshape(-1)
+    join = size * np.arange(1, n_units, dtype=np.int64)
+    return from_plus_links(np.arange(1, size * n_units + 1, dtype=np.uint32), np.concatenate([src, join - 1]),
+                           np.concatenate([dst, join]))
+
+
+def insertion_haplotypes(n_units: int, n: int, seed: int) -> Paths:
+    """`n` haplotypes of insertion_units(n_units): each takes, per unit, the insertion arm with probability 1/2 and then a
+    branch of its SNP with probability 1/2; haplotype 0 always takes the reference arm.  PanSN names, one sample a haplotype
+    (`hap<k>#1#chr1`).  Vectorised over the units of a haplotype."""
+    size = _INSERTION_UNIT
+    rng = np.random.default_rng(seed)
+    ids = np.arange(1, size * n_units + 1, dtype=np.uint32).reshape(n_units, size)
+    pieces = []
+    for h in range(n):
+        ins = rng.random(n_units) < 0.5 if h else np.zeros(n_units, dtype=bool)
+        y = rng.integers(0, 2, size=n_units).astype(bool)
+        present = np.ones((n_units, size), dtype=bool)
+        present[:, 1] = present[:, 2] = ~ins
+        present[:, 3] = present[:, 6] = ins
+        present[:, 4] = ins & ~y
+        present[:, 5] = ins & y
+        w = ids[present]
+        pieces.append((w, np.zeros(w.size, dtype=np.uint8)))
+    return _paths([f"hap{h}#1#chr1" for h in range(n)], pieces)
+
+
 _RC = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
 
 

@@ -1,4 +1,4 @@
-"""Device time of povu_hip_call (HipDecomposer.call) in its modes on one of five inputs, each at the size it has always been
+"""Device time of povu_hip_call (HipDecomposer.call) in its modes on one of six inputs, each at the size it has always been
 timed at:
 
     chain     the chain of bubbles with 32 closed-form haplotypes, a quarter written reversed (workloads.chain_haplotypes),
@@ -10,12 +10,14 @@ timed at:
               tandem repeat, INTEGRATION.md "Left-normalised calls"); 100000 units
     complex   workloads.complex_alleles / complex_haplotypes with 8 haplotypes (bubbles of several small edits, INTEGRATION.md
               "Decomposed calls"); 100000 units
+    insertions workloads.insertion_units / insertion_haplotypes with 64 haplotypes (a SNP inside an insertion the reference does
+              not have, INTEGRATION.md "Off-reference calls"); 125000 units, 1e6 segments
 
 and in any of the modes plain, inversions (T_INVERSIONS), nested (T_NESTED), popped (profile `popped`, max_level 0, both length
 limits --max-length), normalized (profile `left-normalized`), decomposed (profile `decomposed`), merged (the same with T_MERGE:
 equal primitives merged; its time less that of decomposed is the merging step's) and decomposed-tier2 (decomposed with
 T_FORCE_TIER2: every aligned pair through the striped kernel, for the cells per second of that tier; asked for by name
-only); without --modes those the input was made for.  One JSON line
+only) and offref (T_OFFREF: the sites no reference path crosses too; its time less that of plain is the step's); without --modes those the input was made for.  One JSON line
 per mode and run: HIP-event time of the call (query upload to the last byte on the host), records, spelled bytes, the
 counters of the mode; then per mode a line with the median of the runs behind the warm-up runs.
 
@@ -23,7 +25,7 @@ Every mode runs in a child process of its own under its own time limit, one afte
 runs out of time nothing more is started.  --package-root times the library of another checkout on this tree's inputs (only
 keyword arguments of HipDecomposer.call that every build with the mode has are used).
 
-    python tools/time_calls.py --workload chain|inverted|skip|tandem|complex [--modes plain,nested] [--size 1.0] [--warmup 2] [--runs 7]
+    python tools/time_calls.py --workload chain|inverted|skip|tandem|complex|insertions [--modes plain,nested] [--size 1.0] [--warmup 2] [--runs 7]
                                [--max-length 64] [--limit 300] [--package-root <another checkout>]
 """
 import argparse
@@ -37,9 +39,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2")
+MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2", "offref")
 DEFAULT_MODES = dict(chain=("plain",), inverted=("plain", "inversions"), skip=("plain", "nested", "popped"), tandem=("plain", "normalized"),
-                     complex=("plain", "decomposed", "merged"))
+                     complex=("plain", "decomposed", "merged"), insertions=("plain", "offref"))
 
 
 def _load(package_root):
@@ -73,6 +75,10 @@ def workload(W, name, size):
         units = max(2, int(1e6 * size / len(W._skip_template(2, 2)[0])) + 1)
         g = W.skip_nested(units, 2)
         return g, W.skip_haplotypes(units, 2, 64, seed=1), W.random_sequences(g, 5, max_len=16), "hap0#"
+    if name == "insertions":
+        units = max(2, int(125000 * size))
+        g = W.insertion_units(units)
+        return g, W.insertion_haplotypes(units, 64, seed=1), W.random_sequences(g, 5, max_len=16), "hap0#"
     if name == "complex":
         units = max(2, int(100000 * size))
         g, seqs = W.complex_alleles(units, 1)
@@ -95,11 +101,11 @@ def child(a):
     kw = dict(plain=lambda: {}, inversions=lambda: dict(flags=H.T_INVERSIONS), nested=lambda: dict(flags=H.T_NESTED),
               popped=lambda: dict(profile="popped", max_level=0, max_ref_length=a.max_length, max_allele_length=a.max_length),
               normalized=lambda: dict(profile="left-normalized"), decomposed=lambda: dict(profile="decomposed"),
-              merged=lambda: dict(profile="decomposed", flags=H.T_MERGE),
+              merged=lambda: dict(profile="decomposed", flags=H.T_MERGE), offref=lambda: dict(flags=H.T_OFFREF),
               **{"decomposed-tier2": lambda: dict(profile="decomposed", flags=H.T_FORCE_TIER2)})[a.child]()
     counters = ("n_inv_records", "n_inv_tier2", "n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "n_normalized", "max_shift",
                 "n_norm_compared", "n_rows", "n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells", "n_mrows",
-                "n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts")
+                "n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts", "n_offref_sites", "n_offref_records", "n_offref_hosted")
     for run in range(a.warmup + a.runs):
         t0 = time.perf_counter()
         c = d.call(f, [ref], **kw)
