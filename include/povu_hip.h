@@ -707,6 +707,10 @@ uint32_t povu_hip_last_seq_redo(const povu_hip_ctx *ctx);
  * literal hi_2 rule of flubbles.cpp:566-574 picked the second-highest reach everywhere and no hairpins were asked
  * for), 0 when it went over all tree edges */
 int povu_hip_last_black_only_classes(const povu_hip_ctx *ctx);
+/* 1 when the last decompose kept the bracket counts per tree vertex as bytes between the tree stage and the placing of the
+ * brackets (no side of the graph has more than 253 links, and POVU_HIP_WIDE_COUNTS=1 is not set in the environment), 0 when
+ * the word kernels ran */
+int povu_hip_last_narrow_counts(const povu_hip_ctx *ctx);
 /* 1 when the last decompose ran the laminarity check of the candidate stack's (prev, i) intervals (only when the literal
  * hi_2 rule capped differently from the second-highest reach somewhere, or with POVU_HIP_F_CHECK_LAMINAR) */
 int povu_hip_last_laminar_check_ran(const povu_hip_ctx *ctx);
@@ -757,6 +761,10 @@ int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t
 #define POVU_HIP_SCAN_DIFF 4
 #define POVU_HIP_SCAN_XOR_PAIR 5
 #define POVU_HIP_SCAN_XOR_U128 6
+/* op 7: sums of in[i] - in2[i] with `in` n BYTES and in2 n words (scan_exclusive_diff_u8_u32; out2 unused);
+ * op 8: sums of the n words of `in` and of the n2 BYTES of in2 in one launch (scan_exclusive_u32_u8_pair) */
+#define POVU_HIP_SCAN_DIFF_U8 7
+#define POVU_HIP_SCAN_MIXED_PAIR 8
 #define POVU_HIP_SCAN_IN_PLACE 0x100
 #define POVU_HIP_SCAN_N_DEV 0x200
 int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,

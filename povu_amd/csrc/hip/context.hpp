@@ -258,6 +258,8 @@ struct LastPass {
 	// only re-ran add_flubbles (tree, classes and stack are the parallel stages'); stack_export_pending: the parallel
 	// stages' candidate stack is still in its dense layout
 	bool mixed = false, redo_pvst_only = false, stack_export_pending = false;
+	// the parallel stages kept the bracket counts per tree vertex (ordcnt / srccnt, see ParWs) as bytes
+	bool narrow_counts = false;
 };
 
 struct povu_hip_ctx {

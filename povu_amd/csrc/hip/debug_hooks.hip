@@ -102,32 +102,33 @@ extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in
 {
 	const int kind = op & 0xFF;
 	const bool in_place = (op & POVU_HIP_SCAN_IN_PLACE) != 0, with_len = (op & POVU_HIP_SCAN_N_DEV) != 0;
-	if (!ctx || kind > POVU_HIP_SCAN_XOR_U128 || (op & ~(0xFF | POVU_HIP_SCAN_IN_PLACE | POVU_HIP_SCAN_N_DEV)))
+	if (!ctx || kind > POVU_HIP_SCAN_MIXED_PAIR || (op & ~(0xFF | POVU_HIP_SCAN_IN_PLACE | POVU_HIP_SCAN_N_DEV)))
 		return 1;
 	if (kind == POVU_HIP_SCAN_U8) {
 		if ((n && (!in || !out)) || (in2 && n2 && !out2))
 			return 1;
-	} else if (!in || !out || (in2 && !out2 && kind != POVU_HIP_SCAN_DIFF)) {
+	} else if (!in || !out || (in2 && !out2 && kind != POVU_HIP_SCAN_DIFF && kind != POVU_HIP_SCAN_DIFF_U8)) {
 		return 1;
 	}
 	if ((in_place && (kind > POVU_HIP_SCAN_U64 || in2)) || (with_len && kind != POVU_HIP_SCAN_XOR_U128) ||
-	    ((kind == POVU_HIP_SCAN_DIFF || kind == POVU_HIP_SCAN_XOR_PAIR) && !in2))
+	    ((kind == POVU_HIP_SCAN_DIFF || kind == POVU_HIP_SCAN_XOR_PAIR || kind == POVU_HIP_SCAN_DIFF_U8 || kind == POVU_HIP_SCAN_MIXED_PAIR) && !in2))
 		return 1;
 	try {
 		HIP_CHECK(hipSetDevice(ctx->device));
 		hipStream_t s = ctx->stream;
 		// element sizes, the length of the second input and whether it has an output of its own
-		const size_t e_in = kind == POVU_HIP_SCAN_U8 ? 1 : kind == POVU_HIP_SCAN_U64 ? 8 : kind == POVU_HIP_SCAN_XOR_U128 ? 16 : 4;
+		const size_t e_in = (kind == POVU_HIP_SCAN_U8 || kind == POVU_HIP_SCAN_DIFF_U8) ? 1 : kind == POVU_HIP_SCAN_U64 ? 8 : kind == POVU_HIP_SCAN_XOR_U128 ? 16 : 4;
+		const size_t e_in2 = kind == POVU_HIP_SCAN_DIFF_U8 ? 4 : kind == POVU_HIP_SCAN_MIXED_PAIR ? 1 : e_in; // (the mixed forms: bytes and words)
 		const size_t e_out = kind == POVU_HIP_SCAN_U64 ? 8 : kind == POVU_HIP_SCAN_XOR_U128 ? 16 : 4;
-		const bool pair = in2 && (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8 || kind == POVU_HIP_SCAN_XOR_PAIR);
-		const bool second_in = pair || kind == POVU_HIP_SCAN_DIFF;
-		const size_t m = !second_in ? 0 : (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8) ? n2 : n;
+		const bool pair = in2 && (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8 || kind == POVU_HIP_SCAN_XOR_PAIR || kind == POVU_HIP_SCAN_MIXED_PAIR);
+		const bool second_in = pair || kind == POVU_HIP_SCAN_DIFF || kind == POVU_HIP_SCAN_DIFF_U8;
+		const size_t m = !second_in ? 0 : (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8 || kind == POVU_HIP_SCAN_MIXED_PAIR) ? n2 : n;
 		const size_t tb = kind == POVU_HIP_SCAN_U64 ? scan_exclusive_u64_tmp(n) * 8 : scan_tmp_bytes(std::max(n, m));
 		const uint32_t len = (uint32_t)n2;
 		Arena ar;
 		DbgOut o1{n * e_out}, o2{m * e_out, DBG_GUARD_BYTE, pair};
 		DbgScratch scr{tb};
-		DbgIn<char> i1{reinterpret_cast<const char *>(in), n * e_in, !in_place}, i2{reinterpret_cast<const char *>(in2), m * e_in, second_in};
+		DbgIn<char> i1{reinterpret_cast<const char *>(in), n * e_in, !in_place}, i2{reinterpret_cast<const char *>(in2), m * e_in2, second_in};
 		DbgIn<uint32_t> ilen{&len, 1, with_len};
 		dbg_carve(ar, s, o1, o2, scr, i1, i2, ilen);
 		if (in_place)
@@ -153,6 +154,12 @@ extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in
 					  pair ? reinterpret_cast<const uint8_t *>(di2) : nullptr, pair ? o2.data<uint32_t>() : nullptr, m, tmp, tb, s);
 			break;
 		case POVU_HIP_SCAN_DIFF: scan_exclusive_diff_u32(w1, w2, o1.data<uint32_t>(), n, tmp, tb, s); break;
+		case POVU_HIP_SCAN_DIFF_U8:
+			scan_exclusive_diff_u8_u32(reinterpret_cast<const uint8_t *>(di), w2, o1.data<uint32_t>(), n, tmp, tb, s);
+			break;
+		case POVU_HIP_SCAN_MIXED_PAIR:
+			scan_exclusive_u32_u8_pair(w1, o1.data<uint32_t>(), n, reinterpret_cast<const uint8_t *>(di2), o2.data<uint32_t>(), m, tmp, tb, s);
+			break;
 		case POVU_HIP_SCAN_XOR_PAIR: scan_exclusive_xor_u32_pair(w1, o1.data<uint32_t>(), w2, o2.data<uint32_t>(), n, tmp, tb, s); break;
 		default:
 			scan_exclusive_xor_u128(reinterpret_cast<const ulonglong2 *>(di), o1.data<ulonglong2>(), n, tmp, tb, s, ilen.dev);

@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace povu_hip
 {
@@ -63,9 +64,11 @@ __global__ void k_globalize(uint32_t T, const uint32_t *__restrict__ t_comp, con
 	uint32_t t = BIDX * blockDim.x + threadIdx.x;
 	if (t >= T)
 		return;
-	srccnt[t] = 0; // brackets per source, [T+2]
-	if (t == T - 1)
-		srccnt[T] = srccnt[T + 1] = 0;
+	if (srccnt) { // (null: the tree stage keeps the counts as bytes and has cleared the slots without a vertex)
+		srccnt[t] = 0; // brackets per source, [T+2]
+		if (t == T - 1)
+			srccnt[T] = srccnt[T + 1] = 0;
+	}
 	if (cov) { // (not on the dense path: the tree stage left hi0 and the count of bracket ends, and needs no coverage array)
 		hi0[t] = NIL; // k_hi0 takes minima into it
 		cov[t] = 0;   // ... and counts back-edge ends here
@@ -354,14 +357,16 @@ __global__ void __launch_bounds__(TPB) k_flag_tile_counts(uint32_t T, const uint
 // wave covers exactly one tile of 256 vertices and ranks its flags with eight ballots; no LDS, no barrier.
 // (the counts it places by -- ordinary back edges, capping vertices -- are read from the device: the kernel is launched
 // before the host has them, see the driver)
+// OC / SC: the width of the two bracket counts (ParWs::narrow_*)
+template <typename OC, typename SC>
 __global__ void __launch_bounds__(TPB) k_bracket_extra(uint32_t T, uint32_t NB0_host, const uint32_t *__restrict__ nb0_dev, uint32_t ntiles,
 							uint32_t nb_cap, const uint8_t *__restrict__ capf,
 							const uint32_t *__restrict__ tcap, const uint8_t *__restrict__ simp,
 							const uint32_t *__restrict__ tsimp, const uint32_t *__restrict__ cap_tgt,
 							const RootOf root_of, uint32_t *__restrict__ b_src, uint32_t *__restrict__ b_tgt,
-							const uint32_t *__restrict__ ordcnt, const uint32_t *__restrict__ gsize,
+							const OC *__restrict__ ordcnt, const uint32_t *__restrict__ gsize,
 							const uint32_t *__restrict__ mpre, uint32_t *__restrict__ incnt,
-							uint32_t *__restrict__ srccnt)
+							SC *__restrict__ srccnt)
 {
 	const uint32_t NB0 = nb0_dev ? *nb0_dev : NB0_host, ncap = tcap[ntiles];
 	if ((uint64_t)NB0 + ncap + tsimp[ntiles] > nb_cap)
@@ -394,7 +399,12 @@ __global__ void __launch_bounds__(TPB) k_bracket_extra(uint32_t T, uint32_t NB0_
 	uint4 oc = make_uint4(0u, 0u, 0u, 0u), gs = oc, mp = oc;
 	if (ordcnt) {
 		if (v0 + 4 <= T) {
-			oc = *reinterpret_cast<const uint4 *>(ordcnt + v0);
+			if constexpr (sizeof(OC) == 1) { // the lane's four counts in one word
+				const uint32_t w = *reinterpret_cast<const uint32_t *>(ordcnt + v0);
+				oc = make_uint4(w & 0xFFu, (w >> 8) & 0xFFu, (w >> 16) & 0xFFu, w >> 24);
+			} else {
+				oc = *reinterpret_cast<const uint4 *>(ordcnt + v0);
+			}
 			gs = *reinterpret_cast<const uint4 *>(gsize + v0);
 			mp = *reinterpret_cast<const uint4 *>(mpre + v0);
 		} else {
@@ -428,7 +438,7 @@ __global__ void __launch_bounds__(TPB) k_bracket_extra(uint32_t T, uint32_t NB0_
 		}
 		// (dense path) brackets per source, at its place in the list order: known per vertex, no counting pass over the brackets
 		if (ordcnt && gsv[j])
-			srccnt[mpv[j]] = ocv[j] + (c ? 1u : 0u) + (sm ? 1u : 0u);
+			srccnt[mpv[j]] = (SC)(ocv[j] + (c ? 1u : 0u) + (sm ? 1u : 0u)); // (a byte only when ordcnt + 2 < 256 everywhere)
 	}
 }
 __global__ void k_bracket_order(uint32_t NB, uint32_t NB0, uint32_t ncap, uint32_t nsimp, const uint32_t *__restrict__ b_src,
@@ -1219,6 +1229,10 @@ static void for_each_span(ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 	pw.nb_cap = NB;
 	auto skip = [](auto **p) { *p = nullptr; };
 	take1(T + 2, pw.hi0, pw.mpre, pw.dlt, pw.incnt, pw.lsz);
+	if (groups & 1) { // the byte forms of the two bracket counts, inside the word arrays they stand in for (see ParWs)
+		pw.ordcnt8 = reinterpret_cast<uint8_t *>(pw.lsz);
+		pw.srccnt8 = reinterpret_cast<uint8_t *>(pw.dlt);
+	}
 	take1(NB + 2, pw.b_src, pw.b_tgt, pw.b_ord);
 	take1(V + 4, pw.sdl);
 	take1(16, pw.err);
@@ -1341,13 +1355,15 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	// is needed.  A sequential tree stage works per component: its arrays are brought into that form here, and the
 	// hairpin report wants the per-vertex tables too.
 	const bool lean = dense_nb0 >= 0 && !want_hp;
+	// the bracket counts of the parallel tree stage as bytes (it wrote them in the form the caller chose, see ParWs)
+	const bool narrow_oc = dense_nb0 >= 0 && pw.narrow_ordcnt, narrow_sc = narrow_oc && pw.narrow_srccnt;
 	if (lean) {
 		pw.gsize = sw.t_size;
 		pw.gpar = sw.t_par;
 	} else {
 		LAUNCH(k_tcomp_vertices, V, s, V, T, cs.ckey, cs.voff, pw.t_comp);
 		LAUNCH(k_globalize, T, s, T, pw.t_comp, cs.voff, sw.c_ntree, sw.t_par, sw.t_size, pw.gpar, pw.gsize, pw.t_root, pw.hi0,
-		       dense_nb0 >= 0 ? nullptr : pw.cov, sw.t_depth, pw.mpre, pw.incnt, pw.dlt);
+		       dense_nb0 >= 0 ? nullptr : pw.cov, sw.t_depth, pw.mpre, pw.incnt, narrow_sc ? nullptr : pw.dlt);
 	}
 	const RootOf root_of{lean ? nullptr : pw.t_root, cs.voff, C};
 	// pw.comp_bad and pw.err are zeroed by the caller (zero_component_counters)
@@ -1373,7 +1389,9 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	uint4 *brec = reinterpret_cast<uint4 *>(pw.psA);
 	uint32_t *brec_cnt = reinterpret_cast<uint32_t *>(pw.f8a);
 	uint32_t *pscov = pw.psB; // (free until the simplifying flags are scanned)
-	if (dense_nb0 >= 0) // back edges leaving a vertex (counted by the tree stage) minus those arriving (counted by k_hi0)
+	if (narrow_oc) // back edges leaving a vertex (counted by the tree stage) minus those arriving (counted by k_hi0)
+		scan_exclusive_diff_u8_u32(pw.ordcnt8, pw.incnt, pscov, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	else if (dense_nb0 >= 0)
 		scan_exclusive_diff_u32(pw.lsz, pw.incnt, pscov, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	else
 		scan(pw.cov, pscov, (size_t)T + 1);
@@ -1395,10 +1413,23 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	// The stream is not left idle while the host reads them (HostScratch::mark): the kernel that places the capping and
 	// simplifying brackets takes the counts from the device, and the scan behind it does not need them at all.
 	const HostScratch::Token extra_ready = pw.host->mark(s);
-	LAUNCH(k_bracket_extra, ((size_t)T + 3) / 4, s, T, NB0, dense_nb0 == NB0_ON_DEVICE ? pw.err + 6 : nullptr, ntiles,
-	       (uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu), capf, tcap, simp, tsimp, pw.cap_tgt, root_of, pw.b_src, pw.b_tgt,
-	       dense_nb0 >= 0 ? pw.lsz : nullptr, pw.gsize, pw.mpre, pw.incnt, srccnt);
-	if (dense_nb0 >= 0) // ranks inside every source and the counts per source are known: place directly
+	auto bracket_extra = [&](auto *ordcnt, auto *sc) {
+		using OC = std::remove_const_t<std::remove_pointer_t<decltype(ordcnt)>>;
+		using SC = std::remove_pointer_t<decltype(sc)>;
+		LAUNCH((k_bracket_extra<OC, SC>), ((size_t)T + 3) / 4, s, T, NB0, dense_nb0 == NB0_ON_DEVICE ? pw.err + 6 : nullptr, ntiles,
+		       (uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu), capf, tcap, simp, tsimp, pw.cap_tgt, root_of, pw.b_src, pw.b_tgt,
+		       ordcnt, pw.gsize, pw.mpre, pw.incnt, sc);
+	};
+	if (narrow_sc)
+		bracket_extra((const uint8_t *)pw.ordcnt8, pw.srccnt8);
+	else if (narrow_oc)
+		bracket_extra((const uint8_t *)pw.ordcnt8, srccnt);
+	else
+		bracket_extra(dense_nb0 >= 0 ? (const uint32_t *)pw.lsz : nullptr, srccnt);
+	// ranks inside every source and the counts per source are known: place directly
+	if (narrow_sc)
+		scan_exclusive_u32_u8_pair(pw.incnt, pw.psin, (size_t)T + 1, pw.srccnt8, bstart, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	else if (dense_nb0 >= 0)
 		scan2(pw.incnt, pw.psin, (size_t)T + 1, srccnt, bstart, (size_t)T + 1);
 	pw.host->wait(extra_ready);
 	if (dense_nb0 == NB0_ON_DEVICE) {

@@ -42,6 +42,15 @@ struct ParWs {
 	uint32_t *hi0, *cov, *psA, *psB, *flagC, *psC; // exclusive scans of the byte flags below [T+1]; flagC: run marks
 	uint8_t *f8a, *f8b, *f8c, *f8d; // [T+1] one-byte flags (bridge / simplifying / capping / branching vertex, class and stack flags)
 	uint32_t *cap_tgt, *mpre, *dlt, *dlt_ps, *incnt, *psin, *topi, *lsz, *gcls;
+	// The two bracket counts per tree vertex between the tree stage's emit kernel and the placing of the brackets, as BYTES
+	// [T+2]: ordcnt8 (ordinary back edges leaving a vertex: k_tree_emit / k_back_edges -> the difference scan, k_bracket_extra)
+	// lies in the first quarter of lsz, srccnt8 (brackets per mirror pre-order position: k_tree_emit / k_bracket_extra ->
+	// the scan of the range starts) in the first quarter of dlt.  Those are the two word arrays that hold the same counts
+	// in the wide form, so neither has another user in that stretch: lsz is next written by k_top_bracket, dlt by row E.
+	// A pass uses them when no count can reach 256 (narrow_*: set by the caller ahead of the tree stage from the most
+	// links any side has; srccnt <= ordcnt + 2); otherwise the word kernels run.
+	uint8_t *ordcnt8, *srccnt8;
+	bool narrow_ordcnt = false, narrow_srccnt = false; // in (srccnt only together with ordcnt)
 	uint32_t *sdl;		 // [V+2] row E's difference array (k_shift_delta) when the tree stage's emit kernel already filled it
 	bool sdl_filled = false; // ... which it says here
 	uint32_t *vals_t, *vals_t2;

@@ -889,6 +889,7 @@ static int64_t parallel_rows(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, c
 	pw.cproc_ps = sw.tables + 2 * ((size_t)C + 1);
 	ctx->tw.cproc = sw.tables + 3 * ((size_t)C + 1);
 	pw.soff = sw.tables + 4 * ((size_t)C + 1);
+	pw.narrow_ordcnt = pw.narrow_srccnt = false;
 	if (p.seq_tree) {
 		lanes.init(s);
 		tm.begin("tree_seq");
@@ -896,6 +897,15 @@ static int64_t parallel_rows(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, c
 		launch_seq_components(sw, s);
 		tm.end(1);
 	} else {
+		// Bracket counts per tree vertex as bytes (ParWs::ordcnt8 / srccnt8) when none can reach 256: a vertex sends at most one
+		// back edge per link of its side (one, to the root, from a side without links), and a position of the bracket list holds
+		// at most a capping and a simplifying bracket more.  Otherwise -- a hub, a fat side of the dense re-index path -- the
+		// word kernels run.  POVU_HIP_WIDE_COUNTS (A/B hook, read per pass): 1 = words for both, 2 = words for srccnt only.
+		const char *ev = getenv("POVU_HIP_WIDE_COUNTS");
+		const int wide = ev ? atoi(ev) : 0;
+		const bool fits = std::max<uint32_t>(gstats[0], 1u) + 2u <= 255u;
+		pw.narrow_ordcnt = fits && wide != 1;
+		pw.narrow_srccnt = pw.narrow_ordcnt && wide != 2;
 		dense_nb0 = run_parallel_tree(ctx->cs, sw, pw, ctx->tw, C, t.event_lists, gstats[0], p.big_class_dfs, p.sparse_splitters, tm, s);
 	}
 	pw.all_vertex_classes = p.all_vertex_classes;
@@ -1303,6 +1313,7 @@ extern "C" povu_hip_forest *povu_hip_decompose(povu_hip_ctx *ctx, const povu_hip
 			ctx->ws_sub.release(); // (the inserting passes keep their tables' arena from one -s pass to the next, no longer)
 		stage_times(ctx, tm, *f);
 		ctx->last = LastPass{true, p, C, out.nbad, out.mixed, out.redo_pvst_only, out.stack_export_pending};
+		ctx->last.narrow_counts = !p.all_seq && !p.seq_tree && ctx->pw.narrow_ordcnt;
 		if (p.world == 1 && ctx->shard_comp_ids.empty()) { // (povu_hip_forest_walks: a forest of the whole resident graph)
 			f->walk_ctx = ctx;
 			f->walk_gen = g.gen;
@@ -1646,6 +1657,11 @@ extern "C" int povu_hip_last_stage_times(const povu_hip_ctx *ctx, povu_hip_stage
 extern "C" uint32_t povu_hip_last_seq_redo(const povu_hip_ctx *ctx) { return ctx ? ctx->last.seq_redo : 0; }
 
 extern "C" uint64_t povu_hip_last_links_processed(const povu_hip_ctx *ctx) { return ctx ? ctx->last_links : 0; }
+
+extern "C" int povu_hip_last_narrow_counts(const povu_hip_ctx *ctx)
+{
+	return ctx && ctx->last.valid && ctx->last.narrow_counts ? 1 : 0;
+}
 
 extern "C" int povu_hip_last_black_only_classes(const povu_hip_ctx *ctx)
 {

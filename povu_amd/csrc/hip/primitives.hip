@@ -33,7 +33,7 @@ __device__ __forceinline__ uint32_t sc_block_reduce(uint32_t v, uint32_t *sh)
 // are due at the same point of the pass share their two launches.
 struct ScanJob {
 	const uint32_t *in;
-	const uint32_t *sub; // when set (sum scans of words): the element is in[i] - sub[i]
+	const uint32_t *sub; // when set (sum scans): the element is in[i] - sub[i] (in8[i] - sub[i] for a byte input)
 	const uint8_t *in8; // when set: the input is one BYTE per element (flags, small counts) -- a quarter of the reads
 	uint32_t *out;
 	size_t n, chunk;
@@ -68,12 +68,20 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_partials(const ScanJobs jobs)
 		auto bytes4 = [](uint32_t w) {
 			return sc_op<MAX>(sc_op<MAX>(w & 0xFFu, (w >> 8) & 0xFFu), sc_op<MAX>((w >> 16) & 0xFFu, w >> 24));
 		};
+		const uint32_t *__restrict__ sub = J.sub;
 		for (size_t i = b0 + 16 * (size_t)threadIdx.x; i < w1; i += 16 * SC_TPB) {
 			const uint4 a = *reinterpret_cast<const uint4 *>(in8 + i);
 			fold4(make_uint4(bytes4(a.x), bytes4(a.y), bytes4(a.z), bytes4(a.w)));
+			if (sub) { // (sums only: the total of the differences is the difference of the totals)
+#pragma unroll
+				for (int q = 0; q < 4; q++) {
+					const uint4 c = *reinterpret_cast<const uint4 *>(sub + i + 4 * q);
+					acc -= c.x + c.y + c.z + c.w;
+				}
+			}
 		}
 		for (size_t i = w1 + threadIdx.x; i < b1; i += SC_TPB)
-			acc = sc_op<MAX>(acc, in8[i]);
+			acc = sc_op<MAX>(acc, in8[i] - (sub ? sub[i] : 0u));
 	} else {
 		const uint32_t *__restrict__ sub = J.sub;
 		const size_t w1 = b0 + ((b1 - b0) & ~size_t(3));
@@ -102,9 +110,13 @@ __device__ __forceinline__ void sc_load_tile(const ScanJob &J, size_t e0, size_t
 			const uint2 a = *reinterpret_cast<const uint2 *>(in8 + e0);
 			v[0] = a.x & 0xFFu, v[1] = (a.x >> 8) & 0xFFu, v[2] = (a.x >> 16) & 0xFFu, v[3] = a.x >> 24;
 			v[4] = a.y & 0xFFu, v[5] = (a.y >> 8) & 0xFFu, v[6] = (a.y >> 16) & 0xFFu, v[7] = a.y >> 24;
+			if (J.sub) {
+				const uint4 c = *reinterpret_cast<const uint4 *>(J.sub + e0), d = *reinterpret_cast<const uint4 *>(J.sub + e0 + 4);
+				v[0] -= c.x, v[1] -= c.y, v[2] -= c.z, v[3] -= c.w, v[4] -= d.x, v[5] -= d.y, v[6] -= d.z, v[7] -= d.w;
+			}
 		} else {
 			for (int k = 0; k < SC_ITEMS; k++)
-				v[k] = e0 + k < b1 ? in8[e0 + k] : 0u;
+				v[k] = e0 + k < b1 ? in8[e0 + k] - (J.sub ? J.sub[e0 + k] : 0u) : 0u;
 		}
 	} else if (e0 + SC_ITEMS <= b1) {
 		const uint32_t *__restrict__ in = J.in;
@@ -244,6 +256,15 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_lookback(const ScanJobs jobs)
 		for (int q = 0; q < LB_SUB; q++) {
 			v[q][0] = a[q].x & 0xFFu, v[q][1] = (a[q].x >> 8) & 0xFFu, v[q][2] = (a[q].x >> 16) & 0xFFu, v[q][3] = a[q].x >> 24;
 			v[q][4] = a[q].y & 0xFFu, v[q][5] = (a[q].y >> 8) & 0xFFu, v[q][6] = (a[q].y >> 16) & 0xFFu, v[q][7] = a[q].y >> 24;
+		}
+		if (J.sub) { // byte counts minus word counts
+			const uint32_t *__restrict__ sub = J.sub + b0 + (size_t)threadIdx.x * SC_ITEMS;
+#pragma unroll
+			for (int q = 0; q < LB_SUB; q++) {
+				const uint4 c = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE), d = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE + 4);
+				v[q][0] -= c.x, v[q][1] -= c.y, v[q][2] -= c.z, v[q][3] -= c.w;
+				v[q][4] -= d.x, v[q][5] -= d.y, v[q][6] -= d.z, v[q][7] -= d.w;
+			}
 		}
 	} else {
 #pragma unroll
@@ -467,6 +488,41 @@ void scan_exclusive_diff_u32(const uint32_t *in, const uint32_t *sub, uint32_t *
 		return;
 	KLAUNCH(k_scan_partials<0>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
 	KLAUNCH(k_scan_chunks<0>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
+}
+
+void scan_exclusive_diff_u8_u32(const uint8_t *in8, const uint32_t *sub, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes,
+				hipStream_t s)
+{
+	if (n == 0)
+		return;
+	if (tmp_bytes < SC_MAX_BLOCKS * sizeof(uint32_t))
+		throw HipError("scan: temporary storage too small");
+	ScanJobs jobs{};
+	jobs.j[0] = make_scan_job(nullptr, out, n, static_cast<uint32_t *>(tmp), in8, sub);
+	if (scan_lookback<0>(jobs, 1, tmp, tmp_bytes, s))
+		return;
+	KLAUNCH(k_scan_partials<0>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
+	KLAUNCH(k_scan_chunks<0>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
+}
+
+void scan_exclusive_u32_u8_pair(const uint32_t *in0, uint32_t *out0, size_t n0, const uint8_t *in1, uint32_t *out1, size_t n1,
+				void *tmp, size_t tmp_bytes, hipStream_t s)
+{
+	if (n0 == 0 || n1 == 0) {
+		scan_exclusive<0>(in0, out0, n0, tmp, tmp_bytes, s);
+		scan_exclusive_u8(in1, out1, n1, nullptr, nullptr, 0, tmp, tmp_bytes, s);
+		return;
+	}
+	if (tmp_bytes < 2 * SC_MAX_BLOCKS * sizeof(uint32_t))
+		throw HipError("scan: temporary storage too small");
+	ScanJobs jobs{};
+	jobs.j[0] = make_scan_job(in0, out0, n0, static_cast<uint32_t *>(tmp));
+	jobs.j[1] = make_scan_job(nullptr, out1, n1, static_cast<uint32_t *>(tmp) + SC_MAX_BLOCKS, in1);
+	if (scan_lookback<0>(jobs, 2, tmp, tmp_bytes, s))
+		return;
+	const unsigned gx = std::max(jobs.j[0].blocks, jobs.j[1].blocks);
+	KLAUNCH(k_scan_partials<0>, dim3(gx, 2), dim3(SC_TPB), 0, s, jobs);
+	KLAUNCH(k_scan_chunks<0>, dim3(gx, 2), dim3(SC_TPB), 0, s, jobs);
 }
 
 template <int OP>

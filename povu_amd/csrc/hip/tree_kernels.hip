@@ -32,6 +32,7 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace povu_hip
@@ -121,6 +122,9 @@ __device__ __forceinline__ void store2_unaligned(uint32_t *p, uint32_t a, uint32
 	v.y = b;
 	*reinterpret_cast<v2a *>(p) = v;
 }
+// two consecutive zero counts, words or bytes (the class stage's bracket counts come in both widths, see ParWs)
+__device__ __forceinline__ void zero2(uint32_t *p) { store2_unaligned(p, 0u, 0u); }
+__device__ __forceinline__ void zero2(uint8_t *p) { p[0] = p[1] = 0; }
 // adjacency index of the same link in the list of the side at its other end
 __device__ __forceinline__ uint32_t arc_twin(const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
 					     const uint32_t *__restrict__ lle, uint32_t at)
@@ -1534,14 +1538,16 @@ __global__ void k_events(uint32_t V, const uint2 *__restrict__ dps, const uint32
 }
 
 // ------------------------------------------------------------------ 8. tree arrays + back edges
+// OC / SC: the width of ordcnt / srccnt (uint8_t when no count of the pass can reach 256, see ParWs::narrow_ordcnt / narrow_srccnt)
+template <typename OC, typename SC>
 __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks R, const uint8_t *__restrict__ merged,
 			    const uint2 *__restrict__ dps, const uint32_t *__restrict__ ckey,
 			    const uint32_t *__restrict__ cproc, const uint32_t *__restrict__ voff,
 			    const unsigned long long *__restrict__ start_key, const uint32_t *__restrict__ gid_s,
 			    uint32_t *__restrict__ t_gid, uint8_t *__restrict__ t_flags, uint32_t *__restrict__ t_par,
 			    uint32_t *__restrict__ t_size, uint32_t *__restrict__ t_depth, uint32_t *__restrict__ side_tidx,
-			    uint32_t C, uint32_t *__restrict__ c_ntree, uint32_t *__restrict__ ordcnt, uint32_t *__restrict__ hi0,
-			    uint32_t *__restrict__ mpre, uint32_t *__restrict__ srccnt, uint32_t *__restrict__ sdl,
+			    uint32_t C, uint32_t *__restrict__ c_ntree, OC *__restrict__ ordcnt, uint32_t *__restrict__ hi0,
+			    uint32_t *__restrict__ mpre, SC *__restrict__ srccnt, uint32_t *__restrict__ sdl,
 			    uint32_t *__restrict__ incnt)
 {
 	// The class stage works on the tree in T-space (component c owns [2 voff[c] + c, 2 voff[c+1] + c]) and reads, per tree
@@ -1597,7 +1603,7 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 	if (!cproc[c]) {
 		const uint32_t t = tb + 2 * (g - v0);
 		store2_unaligned(t_size + t, 0u, 0u);
-		store2_unaligned(srccnt + t, 0u, 0u);
+		zero2(srccnt + t);
 		store2_unaligned(incnt + t, 0u, 0u);
 		*reinterpret_cast<uint2 *>(side_tidx + 2 * g) = make_uint2(NIL, NIL);
 		return;
@@ -1732,13 +1738,14 @@ __device__ __forceinline__ uint32_t side_back_edges(uint32_t S, uint32_t p, uint
 	}
 	return n;
 }
+template <typename OC>
 __global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
 						     const uint2 *__restrict__ dps, const uint32_t *__restrict__ side_tidx,
 						     const uint32_t *__restrict__ ckey, const uint32_t *__restrict__ voff,
 						     const uint32_t *__restrict__ t_par, uint32_t *__restrict__ total_out,
 						     uint32_t *__restrict__ b_src, uint32_t *__restrict__ b_tgt,
 						     uint32_t *__restrict__ b_ord, const uint8_t *__restrict__ dupflag,
-						     uint32_t *__restrict__ ordcnt, uint32_t *__restrict__ hi0, uint32_t *__restrict__ incnt,
+						     OC *__restrict__ ordcnt, uint32_t *__restrict__ hi0, uint32_t *__restrict__ incnt,
 						     uint32_t cap)
 {
 	const uint32_t S0 = BIDX * BE_SIDES + threadIdx.x;
@@ -1755,7 +1762,7 @@ __global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t 
 						   first2[it][threadIdx.x]);
 			// what the class stage needs per tree vertex, known right here: its ordinary brackets (p's stretch of the
 			// bracket list is sized with it) and the highest vertex they reach (hi_0, flubbles.cpp:515-519)
-			ordcnt[p] = k;
+			ordcnt[p] = (OC)k; // (a byte only when no side of the pass has 254 links)
 			hi0[p] = highest;
 			n += k;
 		}
@@ -2171,9 +2178,20 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 
 	// ---- 8. tree arrays in pre-order and the from_bd back edges
 	tm.begin("tree_emit");
-	LAUNCH(k_tree_emit, std::max(V, C), s, nS, tw.evt, evr, merged, tw.dps, cs.ckey, tw.cproc, cs.voff, start_key, cs.gid_s, sw.t_gid, sw.t_flags,
-	       sw.t_par, sw.t_size, (sw.hairpins || sw.want_depth) ? sw.t_depth : nullptr, tw.side_tidx, C, sw.c_ntree, pw.lsz, pw.hi0, pw.mpre, pw.dlt,
-	       pw.sdl, pw.incnt); // (incnt: k_back_edges counts the brackets that end at a vertex into it)
+	// (incnt: k_back_edges counts the brackets that end at a vertex into it; the two bracket counts as words or bytes)
+	auto tree_emit = [&](auto *ordcnt, auto *srccnt) {
+		using OC = std::remove_pointer_t<decltype(ordcnt)>;
+		using SC = std::remove_pointer_t<decltype(srccnt)>;
+		LAUNCH((k_tree_emit<OC, SC>), std::max(V, C), s, nS, tw.evt, evr, merged, tw.dps, cs.ckey, tw.cproc, cs.voff, start_key, cs.gid_s, sw.t_gid,
+		       sw.t_flags, sw.t_par, sw.t_size, (sw.hairpins || sw.want_depth) ? sw.t_depth : nullptr, tw.side_tidx, C, sw.c_ntree, ordcnt,
+		       pw.hi0, pw.mpre, srccnt, pw.sdl, pw.incnt);
+	};
+	if (pw.narrow_ordcnt && pw.narrow_srccnt)
+		tree_emit(pw.ordcnt8, pw.srccnt8);
+	else if (pw.narrow_ordcnt)
+		tree_emit(pw.ordcnt8, pw.dlt);
+	else
+		tree_emit(pw.lsz, pw.dlt);
 	pw.sdl_filled = true;
 	const uint8_t *dupflag = nullptr;
 	if (max_side_links > 64 && E) { // see k_dup_flags
@@ -2191,9 +2209,15 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 	}
 	tw.last_dupflag = dupflag;
 	uint32_t *nb0_dev = pw.err + 6; // (cleared with the other counters at the start of the pass)
-	KLAUNCH(k_back_edges, dim3((nS + BE_SIDES - 1) / BE_SIDES), dim3(TPB), 0, s, nS, cs.loff, cs.ladj, tw.dps, tw.side_tidx, cs.ckey,
-		cs.voff, sw.t_par, nb0_dev, pw.b_src, pw.b_tgt, pw.b_ord, dupflag, pw.lsz, pw.hi0, pw.incnt,
-		(uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu));
+	auto back_edges = [&](auto *ordcnt) {
+		KLAUNCH((k_back_edges<std::remove_pointer_t<decltype(ordcnt)>>), dim3((nS + BE_SIDES - 1) / BE_SIDES), dim3(TPB), 0, s, nS, cs.loff, cs.ladj, tw.dps, tw.side_tidx, cs.ckey,
+			cs.voff, sw.t_par, nb0_dev, pw.b_src, pw.b_tgt, pw.b_ord, dupflag, ordcnt, pw.hi0, pw.incnt,
+			(uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu));
+	};
+	if (pw.narrow_ordcnt)
+		back_edges(pw.ordcnt8);
+	else
+		back_edges(pw.lsz);
 	// (their number stays on the device: the class stage reads it together with its own counts)
 	tm.end(6);
 	return NB0_ON_DEVICE;
