@@ -348,6 +348,105 @@ size_t scan_tmp_bytes(size_t n);
 // exclusive sums of u64 (in == out allowed); tmp holds scan_exclusive_u64_tmp(n) WORDS of 8 bytes
 void scan_exclusive_u64(const uint64_t *in, uint64_t *out, size_t n, uint64_t *tmp, hipStream_t s);
 size_t scan_exclusive_u64_tmp(size_t n);
+
+// ---- scans inside a wave and a workgroup, written once.  An operation is a type with an associative, commutative
+// operator() whose identity is the all-zero value T{}, and before(inc, v): what the lanes in front of a lane hold together,
+// from the lane's inclusive value and its own.  ScanOp<0|1|2> = sum (mod 2^32) / maximum / xor of u32, Xor128 = xor of
+// 128-bit words.  Everything is inlined, and LDS comes from the caller: a kernel's layout and barriers are its own.
+__device__ __forceinline__ uint32_t lanes_up(uint32_t v, int off) { return __shfl_up(v, off); }
+__device__ __forceinline__ uint32_t lanes_down(uint32_t v, int off) { return __shfl_down(v, off); }
+__device__ __forceinline__ ulonglong2 lanes_up(const ulonglong2 v, int off) { return make_ulonglong2(__shfl_up(v.x, off), __shfl_up(v.y, off)); }
+__device__ __forceinline__ ulonglong2 lanes_down(const ulonglong2 v, int off) { return make_ulonglong2(__shfl_down(v.x, off), __shfl_down(v.y, off)); }
+template <int OP>
+struct ScanOp {
+	__device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return OP == 1 ? (a > b ? a : b) : (OP == 2 ? (a ^ b) : a + b); }
+	__device__ __forceinline__ uint32_t before(uint32_t inc, uint32_t v) const
+	{
+		if (OP == 0)
+			return inc - v;
+		if (OP == 2)
+			return inc ^ v;
+		const uint32_t y = __shfl_up(inc, 1); // (a maximum cannot be undone)
+		return (threadIdx.x & 63u) ? y : 0u;
+	}
+};
+struct Xor128 {
+	__device__ __forceinline__ ulonglong2 operator()(const ulonglong2 a, const ulonglong2 b) const { return make_ulonglong2(a.x ^ b.x, a.y ^ b.y); }
+	__device__ __forceinline__ ulonglong2 before(const ulonglong2 inc, const ulonglong2 v) const { return (*this)(inc, v); }
+};
+// lane l gets the lanes 0 .. l
+template <class T, class Op>
+__device__ __forceinline__ T wave_inclusive_scan(T v, Op op)
+{
+	const int lane = (int)(threadIdx.x & 63u);
+	for (int off = 1; off < 64; off <<= 1) {
+		const T y = lanes_up(v, off);
+		if (lane >= off)
+			v = op(v, y);
+	}
+	return v;
+}
+// lane 0 gets the whole wave
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op)
+{
+	for (int off = 32; off; off >>= 1)
+		v = op(v, lanes_down(v, off));
+	return v;
+}
+// the workgroup (WAVES waves), in every lane; sh: WAVES values, free again on return (one barrier in, one out)
+template <int WAVES, class T, class Op>
+__device__ __forceinline__ T block_reduce(T v, T *sh, Op op)
+{
+	v = wave_reduce(v, op);
+	if ((threadIdx.x & 63u) == 0)
+		sh[threadIdx.x >> 6] = v;
+	__syncthreads();
+	T r = sh[0];
+#pragma unroll
+	for (int w = 1; w < WAVES; w++)
+		r = op(r, sh[w]);
+	__syncthreads();
+	return r;
+}
+// Exclusive prefix over the workgroup in two halves, for kernels that put several scans in front of one barrier:
+// wave_scan_publish returns the lane's inclusive value within its wave and leaves the wave's total in sh[wave]; behind a
+// barrier waves_before returns the waves in front of this one, and the whole workgroup in `total`.
+template <class T, class Op>
+__device__ __forceinline__ T wave_scan_publish(T v, T *sh, Op op)
+{
+	const T inc = wave_inclusive_scan(v, op);
+	if ((threadIdx.x & 63u) == 63u)
+		sh[threadIdx.x >> 6] = inc;
+	return inc;
+}
+template <int WAVES, class T, class Op>
+__device__ __forceinline__ T waves_before(const T *sh, T &total, Op op)
+{
+	const int wave = (int)(threadIdx.x >> 6);
+	T before{};
+	total = T{};
+#pragma unroll
+	for (int w = 0; w < WAVES; w++) {
+		if (w < wave)
+			before = op(before, sh[w]);
+		total = op(total, sh[w]);
+	}
+	return before;
+}
+// ... and in one piece: what the lanes in front of this one hold together, `total` = the whole workgroup.  ONE barrier; a
+// caller that uses `sh` again puts its own behind the last use.
+template <int WAVES, class T, class Op>
+__device__ __forceinline__ T block_exclusive_scan(T v, T *sh, T &total, Op op)
+{
+	const T inc = wave_scan_publish(v, sh, op);
+	__syncthreads();
+	const T before = waves_before<WAVES>(sh, total, op);
+	return op(before, op.before(inc, v));
+}
+__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v) { return wave_inclusive_scan(v, ScanOp<0>{}); }
+__device__ __forceinline__ uint32_t wave_inclusive_max(uint32_t v) { return wave_inclusive_scan(v, ScanOp<1>{}); }
+
 // indices of the non-zero bytes of flag[0..n), ascending, into out; their number into *count_dev (device memory).  No
 // prefix array is written: tiles are counted, the counts scanned, the tiles ranked again.
 // ---- bit-rank directory: one 16-byte record per 64 flags = {bits 0..31, bits 32..63, set bits in front of the record, 0}.
@@ -422,12 +521,7 @@ __device__ __forceinline__ void append_in_order(unsigned long long fw, uint32_t 
 	__syncthreads();
 	if (threadIdx.x < 64) { // rounds first, waves inside a round: exclusive prefix of the 64 counts, the total to the list
 		const uint32_t v = tot[threadIdx.x];
-		uint32_t inc = v;
-		for (int off = 1; off < 64; off <<= 1) {
-			const uint32_t y = __shfl_up(inc, off);
-			if ((int)lane >= off)
-				inc += y;
-		}
+		const uint32_t inc = wave_inclusive_sum(v);
 		tot[threadIdx.x] = inc - v;
 		if (lane == 63)
 			base_sh = inc ? atomicAdd(n_list, inc) : 0u;

@@ -95,6 +95,29 @@ bool dbg_guards_intact(const DbgOut &o, hipStream_t s)
 	HIP_CHECK(hipStreamSynchronize(s));
 	return dbg_all_guard(h.data(), 0, h.size());
 }
+// what povu_hip_debug_scan's arguments mean for each POVU_HIP_SCAN_* op (the row's index)
+enum DbgSecond { DBG_NONE, DBG_PAIR, DBG_SUB }; // in2 is: unused / a job of its own, with out2 / what is subtracted from `in`
+struct DbgScanOp {
+	size_t e_in, e_in2, e_out; // bytes per element of in, in2 and the outputs
+	DbgSecond second;
+	bool need2;	// in2 must be there
+	bool len_n2;	// in2 has n2 elements (else n)
+	bool in_place;	// POVU_HIP_SCAN_IN_PLACE allowed
+	bool n_dev;	// POVU_HIP_SCAN_N_DEV allowed
+	bool nullable;	// an empty array may be a null pointer
+};
+const DbgScanOp DBG_SCAN_OPS[] = {
+	{4, 4, 4, DBG_PAIR, false, true, true, false, false},	  // POVU_HIP_SCAN_SUM
+	{4, 4, 4, DBG_NONE, false, false, true, false, false},	  // POVU_HIP_SCAN_MAX
+	{8, 8, 8, DBG_NONE, false, false, true, false, false},	  // POVU_HIP_SCAN_U64
+	{1, 1, 4, DBG_PAIR, false, true, false, false, true},	  // POVU_HIP_SCAN_U8
+	{4, 4, 4, DBG_SUB, true, false, false, false, false},	  // POVU_HIP_SCAN_DIFF
+	{4, 4, 4, DBG_PAIR, true, false, false, false, false},	  // POVU_HIP_SCAN_XOR_PAIR
+	{16, 16, 16, DBG_NONE, false, false, false, true, false}, // POVU_HIP_SCAN_XOR_U128
+	{1, 4, 4, DBG_SUB, true, false, false, false, false},	  // POVU_HIP_SCAN_DIFF_U8
+	{4, 1, 4, DBG_PAIR, true, true, false, false, false},	  // POVU_HIP_SCAN_MIXED_PAIR
+};
+static_assert(sizeof(DBG_SCAN_OPS) / sizeof(DBG_SCAN_OPS[0]) == POVU_HIP_SCAN_MIXED_PAIR + 1, "one row per op");
 } // namespace
 
 extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,
@@ -104,25 +127,18 @@ extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in
 	const bool in_place = (op & POVU_HIP_SCAN_IN_PLACE) != 0, with_len = (op & POVU_HIP_SCAN_N_DEV) != 0;
 	if (!ctx || kind > POVU_HIP_SCAN_MIXED_PAIR || (op & ~(0xFF | POVU_HIP_SCAN_IN_PLACE | POVU_HIP_SCAN_N_DEV)))
 		return 1;
-	if (kind == POVU_HIP_SCAN_U8) {
-		if ((n && (!in || !out)) || (in2 && n2 && !out2))
-			return 1;
-	} else if (!in || !out || (in2 && !out2 && kind != POVU_HIP_SCAN_DIFF && kind != POVU_HIP_SCAN_DIFF_U8)) {
+	const DbgScanOp &T = DBG_SCAN_OPS[kind];
+	if (T.nullable ? ((n && (!in || !out)) || (in2 && n2 && !out2)) : (!in || !out || (in2 && !out2 && T.second != DBG_SUB)))
 		return 1;
-	}
-	if ((in_place && (kind > POVU_HIP_SCAN_U64 || in2)) || (with_len && kind != POVU_HIP_SCAN_XOR_U128) ||
-	    ((kind == POVU_HIP_SCAN_DIFF || kind == POVU_HIP_SCAN_XOR_PAIR || kind == POVU_HIP_SCAN_DIFF_U8 || kind == POVU_HIP_SCAN_MIXED_PAIR) && !in2))
+	if ((in_place && (!T.in_place || in2)) || (with_len && !T.n_dev) || (T.need2 && !in2))
 		return 1;
 	try {
 		HIP_CHECK(hipSetDevice(ctx->device));
 		hipStream_t s = ctx->stream;
 		// element sizes, the length of the second input and whether it has an output of its own
-		const size_t e_in = (kind == POVU_HIP_SCAN_U8 || kind == POVU_HIP_SCAN_DIFF_U8) ? 1 : kind == POVU_HIP_SCAN_U64 ? 8 : kind == POVU_HIP_SCAN_XOR_U128 ? 16 : 4;
-		const size_t e_in2 = kind == POVU_HIP_SCAN_DIFF_U8 ? 4 : kind == POVU_HIP_SCAN_MIXED_PAIR ? 1 : e_in; // (the mixed forms: bytes and words)
-		const size_t e_out = kind == POVU_HIP_SCAN_U64 ? 8 : kind == POVU_HIP_SCAN_XOR_U128 ? 16 : 4;
-		const bool pair = in2 && (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8 || kind == POVU_HIP_SCAN_XOR_PAIR || kind == POVU_HIP_SCAN_MIXED_PAIR);
-		const bool second_in = pair || kind == POVU_HIP_SCAN_DIFF || kind == POVU_HIP_SCAN_DIFF_U8;
-		const size_t m = !second_in ? 0 : (kind == POVU_HIP_SCAN_SUM || kind == POVU_HIP_SCAN_U8 || kind == POVU_HIP_SCAN_MIXED_PAIR) ? n2 : n;
+		const size_t e_in = T.e_in, e_in2 = T.e_in2, e_out = T.e_out;
+		const bool pair = in2 && T.second == DBG_PAIR, second_in = in2 && T.second != DBG_NONE;
+		const size_t m = !second_in ? 0 : T.len_n2 ? n2 : n;
 		const size_t tb = kind == POVU_HIP_SCAN_U64 ? scan_exclusive_u64_tmp(n) * 8 : scan_tmp_bytes(std::max(n, m));
 		const uint32_t len = (uint32_t)n2;
 		Arena ar;

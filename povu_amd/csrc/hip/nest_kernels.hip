@@ -157,17 +157,6 @@ __global__ __launch_bounds__(Q_TPB) void k_ns_cover_t1(uint32_t n_al, CoverArgs 
 	A.shash[a] = kept_bits(A, h);
 }
 
-__device__ __forceinline__ uint32_t wave_inclusive_max(uint32_t v)
-{
-	const int lane = (int)(threadIdx.x & 63u);
-	for (int o = 1; o < 64; o <<= 1) {
-		const uint32_t y = __shfl_up(v, o, 64);
-		if (lane >= o)
-			v = max(v, y);
-	}
-	return v;
-}
-
 // tier 2: a wave (a workgroup of 64 lanes: its barriers are the wave's own) per allele of `list`, 64 positions a round
 __global__ __launch_bounds__(64) void k_ns_cover_t2(const uint32_t *__restrict__ list, uint32_t n2, CoverArgs A)
 {

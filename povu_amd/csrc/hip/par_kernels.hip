@@ -993,12 +993,7 @@ __global__ void __launch_bounds__(TPB) k_emit_endpoints(uint32_t S, const uint4 
 			fl = (((i0 & 32u) ? r.y : r.x) >> (i0 & 31u)) & 15u;
 		}
 		const uint32_t cnt = (uint32_t)__popc(fl);
-		uint32_t inc = cnt;
-		for (int off = 1; off < 64; off <<= 1) {
-			const uint32_t y = __shfl_up(inc, off);
-			if ((int)lane >= off)
-				inc += y;
-		}
+		const uint32_t inc = wave_inclusive_sum(cnt);
 		const uint32_t total = __shfl(inc, 63);
 		uint32_t at = inc - cnt;
 #pragma unroll

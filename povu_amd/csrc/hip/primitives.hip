@@ -1,40 +1,42 @@
 // primitives.hip -- device-wide primitives between the decompose kernels: exclusive scans and the stable radix sort
 // of (key, value) pairs, all hand-written.
+//
+// The u32 scans (sum / max / xor) share one description of their input and one way to read it.  A ScanSrc says whether a
+// job's elements are words or single BYTES, and whether a word array `sub` is subtracted element by element (sums only).
+// sc_load<Q> loads Q sub-tiles of SC_ITEMS consecutive elements a lane: whole sub-tiles with 16-byte (words) or 8-byte
+// (bytes) loads that are ALL issued before the first is used, anything else element by element with zeros behind the end;
+// the byte unpack (sc_unpack4) and the `- sub` step exist there and nowhere else.  Q = 1 is a tile of the two-launch form
+// (k_scan_chunks), Q = LB_SUB the tile of the one-launch form (k_scan_lookback); sc_store writes a sub-tile back.  The
+// reduction k_scan_partials reads 16 bytes a lane and load instead and selects words / bytes / sub the same way.  A new
+// input form is a line in ScanSrc, sc_load and k_scan_partials.  The scans inside a wave and a workgroup are the helpers
+// of common.hpp, as in every other kernel of this file.
 #include "common.hpp"
 
 namespace povu_hip
 {
 
-// ---- exclusive scans (sum / max) of u32, two launches: per-chunk partials, then every block adds the
+// ---- exclusive scans (sum / max / xor) of u32, two launches: per-chunk partials, then every block adds the
 // partials in front of it and scans its own chunk tile by tile (8 elements per lane, wave shuffles,
 // one LDS exchange per tile).  The arrays here are 1-30 M elements; the second read of the input comes
 // from L2 / Infinity Cache.
-static constexpr int SC_TPB = 256, SC_ITEMS = 8, SC_TILE = SC_TPB * SC_ITEMS, SC_MAX_BLOCKS = 1024;
+static constexpr int SC_TPB = 256, SC_WAVES = SC_TPB / 64, SC_ITEMS = 8, SC_TILE = SC_TPB * SC_ITEMS, SC_MAX_BLOCKS = 1024;
 
-// MAX: 0 = sum (mod 2^32), 1 = maximum, 2 = xor; the identity of all three is 0
-template <int MAX>
-__device__ __forceinline__ uint32_t sc_op(uint32_t a, uint32_t b)
-{
-	return MAX == 1 ? (a > b ? a : b) : (MAX == 2 ? (a ^ b) : a + b);
-}
-template <int MAX>
-__device__ __forceinline__ uint32_t sc_block_reduce(uint32_t v, uint32_t *sh)
-{
-	for (int off = 32; off; off >>= 1)
-		v = sc_op<MAX>(v, __shfl_down(v, off));
-	if ((threadIdx.x & 63) == 0)
-		sh[threadIdx.x >> 6] = v;
-	__syncthreads();
-	uint32_t r = sc_op<MAX>(sc_op<MAX>(sh[0], sh[1]), sc_op<MAX>(sh[2], sh[3]));
-	__syncthreads();
-	return r;
-}
+// what a job scans: words, or one BYTE per element (flags, small counts -- a quarter of the reads); with `sub` (sum scans)
+// the element is in[i] - sub[i]
+struct ScanSrc {
+	const void *in;
+	const uint32_t *sub;
+	bool bytes;
+	static ScanSrc words(const uint32_t *p, const uint32_t *sub = nullptr) { return ScanSrc{p, sub, false}; }
+	static ScanSrc of_bytes(const uint8_t *p, const uint32_t *sub = nullptr) { return ScanSrc{p, sub, true}; }
+	__device__ __forceinline__ const uint32_t *w() const { return static_cast<const uint32_t *>(in); }
+	__device__ __forceinline__ const uint8_t *b() const { return static_cast<const uint8_t *>(in); }
+	__device__ __forceinline__ uint32_t operator[](size_t i) const { return (bytes ? (uint32_t)b()[i] : w()[i]) - (sub ? sub[i] : 0u); }
+};
 // One scan job; a launch carries one or two of them (blockIdx.y picks) so that independent scans that
 // are due at the same point of the pass share their two launches.
 struct ScanJob {
-	const uint32_t *in;
-	const uint32_t *sub; // when set (sum scans): the element is in[i] - sub[i] (in8[i] - sub[i] for a byte input)
-	const uint8_t *in8; // when set: the input is one BYTE per element (flags, small counts) -- a quarter of the reads
+	ScanSrc src;
 	uint32_t *out;
 	size_t n, chunk;
 	uint32_t blocks;
@@ -47,31 +49,45 @@ struct ScanJob {
 struct ScanJobs {
 	ScanJob j[2];
 };
-template <int MAX>
+// the four one-byte elements of a word
+__device__ __forceinline__ void sc_unpack4(uint32_t w, uint32_t *v) { v[0] = w & 0xFFu, v[1] = (w >> 8) & 0xFFu, v[2] = (w >> 16) & 0xFFu, v[3] = w >> 24; }
+__device__ __forceinline__ void sc_minus4(uint32_t *v, const uint4 c) { v[0] -= c.x, v[1] -= c.y, v[2] -= c.z, v[3] -= c.w; }
+template <int OP>
+__device__ __forceinline__ uint32_t sc_fold4(const uint32_t *v)
+{
+	const ScanOp<OP> op;
+	return op(op(v[0], v[1]), op(v[2], v[3]));
+}
+template <int OP>
 __global__ void __launch_bounds__(SC_TPB) k_scan_partials(const ScanJobs jobs)
 {
-	__shared__ uint32_t sh[4];
+	__shared__ uint32_t sh[SC_WAVES];
 	const ScanJob &J = jobs.j[blockIdx.y];
 	if (blockIdx.x >= J.blocks)
 		return;
-	const uint32_t *__restrict__ in = J.in;
-	uint32_t *__restrict__ partial = J.partial;
+	const ScanOp<OP> op;
+	const ScanSrc S = J.src;
+	const uint32_t *__restrict__ sub = S.sub;
 	const size_t n = J.n, chunk = J.chunk;
 	const size_t b0 = (size_t)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
 	uint32_t acc = 0;
 	// chunks start on multiples of the tile and every operand is 16-byte aligned: sixteen bytes per load (four words, or
 	// sixteen one-byte elements), the tail of the last chunk element by element
-	auto fold4 = [&](const uint4 &a) { acc = sc_op<MAX>(acc, sc_op<MAX>(sc_op<MAX>(a.x, a.y), sc_op<MAX>(a.z, a.w))); };
-	if (J.in8) {
-		const uint8_t *__restrict__ in8 = J.in8;
-		const size_t w1 = b0 + ((b1 - b0) & ~size_t(15));
-		auto bytes4 = [](uint32_t w) {
-			return sc_op<MAX>(sc_op<MAX>(w & 0xFFu, (w >> 8) & 0xFFu), sc_op<MAX>((w >> 16) & 0xFFu, w >> 24));
-		};
-		const uint32_t *__restrict__ sub = J.sub;
+	size_t w1;
+	if (S.bytes) {
+		const uint8_t *__restrict__ in8 = S.b();
+		w1 = b0 + ((b1 - b0) & ~size_t(15));
 		for (size_t i = b0 + 16 * (size_t)threadIdx.x; i < w1; i += 16 * SC_TPB) {
 			const uint4 a = *reinterpret_cast<const uint4 *>(in8 + i);
-			fold4(make_uint4(bytes4(a.x), bytes4(a.y), bytes4(a.z), bytes4(a.w)));
+			const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+			uint32_t f[4];
+#pragma unroll
+			for (int q = 0; q < 4; q++) {
+				uint32_t v[4];
+				sc_unpack4(w[q], v);
+				f[q] = sc_fold4<OP>(v);
+			}
+			acc = op(acc, sc_fold4<OP>(f));
 			if (sub) { // (sums only: the total of the differences is the difference of the totals)
 #pragma unroll
 				for (int q = 0; q < 4; q++) {
@@ -80,117 +96,134 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_partials(const ScanJobs jobs)
 				}
 			}
 		}
-		for (size_t i = w1 + threadIdx.x; i < b1; i += SC_TPB)
-			acc = sc_op<MAX>(acc, in8[i] - (sub ? sub[i] : 0u));
 	} else {
-		const uint32_t *__restrict__ sub = J.sub;
-		const size_t w1 = b0 + ((b1 - b0) & ~size_t(3));
+		const uint32_t *__restrict__ in = S.w();
+		w1 = b0 + ((b1 - b0) & ~size_t(3));
 		if (sub) {
 			for (size_t i = b0 + 4 * (size_t)threadIdx.x; i < w1; i += 4 * SC_TPB) {
-				const uint4 a = *reinterpret_cast<const uint4 *>(in + i), c = *reinterpret_cast<const uint4 *>(sub + i);
-				fold4(make_uint4(a.x - c.x, a.y - c.y, a.z - c.z, a.w - c.w));
+				const uint4 a = *reinterpret_cast<const uint4 *>(in + i);
+				uint32_t v[4] = {a.x, a.y, a.z, a.w};
+				sc_minus4(v, *reinterpret_cast<const uint4 *>(sub + i));
+				acc = op(acc, sc_fold4<OP>(v));
 			}
 		} else {
-			for (size_t i = b0 + 4 * (size_t)threadIdx.x; i < w1; i += 4 * SC_TPB)
-				fold4(*reinterpret_cast<const uint4 *>(in + i));
+			for (size_t i = b0 + 4 * (size_t)threadIdx.x; i < w1; i += 4 * SC_TPB) {
+				const uint4 a = *reinterpret_cast<const uint4 *>(in + i);
+				const uint32_t v[4] = {a.x, a.y, a.z, a.w};
+				acc = op(acc, sc_fold4<OP>(v));
+			}
 		}
-		for (size_t i = w1 + threadIdx.x; i < b1; i += SC_TPB)
-			acc = sc_op<MAX>(acc, in[i] - (sub ? sub[i] : 0u));
 	}
-	acc = sc_block_reduce<MAX>(acc, sh);
+	for (size_t i = w1 + threadIdx.x; i < b1; i += SC_TPB)
+		acc = op(acc, S[i]);
+	acc = block_reduce<SC_WAVES>(acc, sh, op);
 	if (threadIdx.x == 0)
-		partial[blockIdx.x] = acc;
+		J.partial[blockIdx.x] = acc;
 }
-// eight consecutive elements of a job starting at e0 (zeros behind b1)
-__device__ __forceinline__ void sc_load_tile(const ScanJob &J, size_t e0, size_t b1, uint32_t (&v)[SC_ITEMS])
+// The lane's SC_ITEMS consecutive elements of each of the Q sub-tiles (SC_TILE elements each) that start at t0 (zeros behind
+// b1).  Whole -- all Q sub-tiles of the workgroup (a uniform test), or for a single one the lane's own elements --: every load
+// of the lane is issued before the first is needed
+template <int Q>
+__device__ __forceinline__ void sc_load(const ScanSrc &S, size_t t0, size_t b1, uint32_t (*v)[SC_ITEMS])
 {
-	if (J.in8) {
-		const uint8_t *__restrict__ in8 = J.in8;
-		if (e0 + SC_ITEMS <= b1) {
-			const uint2 a = *reinterpret_cast<const uint2 *>(in8 + e0);
-			v[0] = a.x & 0xFFu, v[1] = (a.x >> 8) & 0xFFu, v[2] = (a.x >> 16) & 0xFFu, v[3] = a.x >> 24;
-			v[4] = a.y & 0xFFu, v[5] = (a.y >> 8) & 0xFFu, v[6] = (a.y >> 16) & 0xFFu, v[7] = a.y >> 24;
-			if (J.sub) {
-				const uint4 c = *reinterpret_cast<const uint4 *>(J.sub + e0), d = *reinterpret_cast<const uint4 *>(J.sub + e0 + 4);
-				v[0] -= c.x, v[1] -= c.y, v[2] -= c.z, v[3] -= c.w, v[4] -= d.x, v[5] -= d.y, v[6] -= d.z, v[7] -= d.w;
-			}
+	const size_t e0 = t0 + (size_t)threadIdx.x * SC_ITEMS;
+	if (Q > 1 ? t0 + (size_t)Q * SC_TILE <= b1 : e0 + SC_ITEMS <= b1) {
+		if (S.bytes) {
+			const uint8_t *__restrict__ in8 = S.b() + e0;
+			uint2 a[Q];
+#pragma unroll
+			for (int q = 0; q < Q; q++)
+				a[q] = *reinterpret_cast<const uint2 *>(in8 + q * SC_TILE);
+#pragma unroll
+			for (int q = 0; q < Q; q++)
+				sc_unpack4(a[q].x, v[q]), sc_unpack4(a[q].y, v[q] + 4);
 		} else {
-			for (int k = 0; k < SC_ITEMS; k++)
-				v[k] = e0 + k < b1 ? in8[e0 + k] - (J.sub ? J.sub[e0 + k] : 0u) : 0u;
+			const uint32_t *__restrict__ in = S.w() + e0;
+			uint4 a[Q][2];
+#pragma unroll
+			for (int q = 0; q < Q; q++)
+				a[q][0] = *reinterpret_cast<const uint4 *>(in + q * SC_TILE), a[q][1] = *reinterpret_cast<const uint4 *>(in + q * SC_TILE + 4);
+#pragma unroll
+			for (int q = 0; q < Q; q++) {
+				v[q][0] = a[q][0].x, v[q][1] = a[q][0].y, v[q][2] = a[q][0].z, v[q][3] = a[q][0].w;
+				v[q][4] = a[q][1].x, v[q][5] = a[q][1].y, v[q][6] = a[q][1].z, v[q][7] = a[q][1].w;
+			}
 		}
-	} else if (e0 + SC_ITEMS <= b1) {
-		const uint32_t *__restrict__ in = J.in;
-		const uint4 a = *reinterpret_cast<const uint4 *>(in + e0), b = *reinterpret_cast<const uint4 *>(in + e0 + 4);
-		v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
-		if (J.sub) {
-			const uint4 c = *reinterpret_cast<const uint4 *>(J.sub + e0), d = *reinterpret_cast<const uint4 *>(J.sub + e0 + 4);
-			v[0] -= c.x, v[1] -= c.y, v[2] -= c.z, v[3] -= c.w, v[4] -= d.x, v[5] -= d.y, v[6] -= d.z, v[7] -= d.w;
+		if (S.sub) {
+			const uint32_t *__restrict__ sub = S.sub + e0;
+#pragma unroll
+			for (int q = 0; q < Q; q++) {
+				const uint4 c = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE), d = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE + 4);
+				sc_minus4(v[q], c), sc_minus4(v[q] + 4, d);
+			}
 		}
+	} else if constexpr (Q > 1) { // the job's last tile: sub-tile by sub-tile
+#pragma unroll
+		for (int q = 0; q < Q; q++)
+			sc_load<1>(S, t0 + (size_t)q * SC_TILE, b1, v + q);
 	} else {
 		for (int k = 0; k < SC_ITEMS; k++)
-			v[k] = e0 + k < b1 ? J.in[e0 + k] - (J.sub ? J.sub[e0 + k] : 0u) : 0u;
+			v[0][k] = e0 + k < b1 ? S[e0 + k] : 0u;
 	}
 }
-template <int MAX>
+// the lane's exclusive scan of its own elements, in place; returns their total
+template <int OP>
+__device__ __forceinline__ uint32_t sc_lane_scan(uint32_t (&v)[SC_ITEMS])
+{
+	uint32_t tot = 0;
+#pragma unroll
+	for (int k = 0; k < SC_ITEMS; k++) {
+		const uint32_t x = v[k];
+		v[k] = tot;
+		tot = ScanOp<OP>{}(tot, x);
+	}
+	return tot;
+}
+// a scanned sub-tile back: pre = everything in front of the lane, v = the lane's own exclusive scan
+template <int OP>
+__device__ __forceinline__ void sc_store(uint32_t *__restrict__ out, size_t e0, size_t b1, uint32_t pre, const uint32_t (&v)[SC_ITEMS])
+{
+	const ScanOp<OP> op;
+	if (e0 + SC_ITEMS <= b1) {
+		*reinterpret_cast<uint4 *>(out + e0) = make_uint4(op(pre, v[0]), op(pre, v[1]), op(pre, v[2]), op(pre, v[3]));
+		*reinterpret_cast<uint4 *>(out + e0 + 4) = make_uint4(op(pre, v[4]), op(pre, v[5]), op(pre, v[6]), op(pre, v[7]));
+	} else {
+		for (int k = 0; k < SC_ITEMS; k++)
+			if (e0 + k < b1)
+				out[e0 + k] = op(pre, v[k]);
+	}
+}
+template <int OP>
 __global__ void __launch_bounds__(SC_TPB) k_scan_chunks(const ScanJobs jobs)
 {
-	__shared__ uint32_t sh[4];
-	__shared__ uint32_t wave_tot[4];
+	__shared__ uint32_t sh[SC_WAVES];
+	__shared__ uint32_t wave_tot[SC_WAVES];
 	const ScanJob &J = jobs.j[blockIdx.y];
 	if (blockIdx.x >= J.blocks)
 		return;
+	const ScanOp<OP> op;
 	uint32_t *__restrict__ out = J.out;
 	const uint32_t *__restrict__ partial = J.partial;
 	const size_t n = J.n, chunk = J.chunk;
 	uint32_t base = 0;
 	for (uint32_t k = threadIdx.x; k < blockIdx.x; k += SC_TPB)
-		base = sc_op<MAX>(base, partial[k]);
-	uint32_t carry = sc_block_reduce<MAX>(base, sh);
+		base = op(base, partial[k]);
+	uint32_t carry = block_reduce<SC_WAVES>(base, sh, op);
 	const size_t b0 = (size_t)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	// the next tile's loads are issued before this tile's exchange through LDS: two tiles of a block are in flight
 	uint32_t v[SC_ITEMS], nx[SC_ITEMS];
 	if (b0 < b1)
-		sc_load_tile(J, b0 + (size_t)threadIdx.x * SC_ITEMS, b1, v);
+		sc_load<1>(J.src, b0, b1, &v);
 	for (size_t t0 = b0; t0 < b1; t0 += SC_TILE) {
 		const size_t e0 = t0 + (size_t)threadIdx.x * SC_ITEMS;
 		const bool more = t0 + SC_TILE < b1;
 		if (more)
-			sc_load_tile(J, e0 + SC_TILE, b1, nx);
-		uint32_t tot = 0; // lane-local exclusive scan
-		for (int k = 0; k < SC_ITEMS; k++) {
-			const uint32_t x = v[k];
-			v[k] = tot;
-			tot = sc_op<MAX>(tot, x);
-		}
-		uint32_t inc = tot; // inclusive scan of lane totals across the wave
-		for (int off = 1; off < 64; off <<= 1) {
-			const uint32_t y = __shfl_up(inc, off);
-			if (lane >= off)
-				inc = sc_op<MAX>(inc, y);
-		}
-		if (lane == 63)
-			wave_tot[wave] = inc;
-		__syncthreads();
-		uint32_t pre = carry; // everything in front of this lane: carry, earlier waves, earlier lanes
-		for (int w = 0; w < wave; w++)
-			pre = sc_op<MAX>(pre, wave_tot[w]);
-		const uint32_t lane_excl = __shfl_up(inc, 1);
-		if (lane > 0)
-			pre = sc_op<MAX>(pre, lane_excl);
-		const uint32_t tile_tot = sc_op<MAX>(sc_op<MAX>(wave_tot[0], wave_tot[1]), sc_op<MAX>(wave_tot[2], wave_tot[3]));
-		if (e0 + SC_ITEMS <= b1) {
-			uint4 a, b;
-			a.x = sc_op<MAX>(pre, v[0]), a.y = sc_op<MAX>(pre, v[1]), a.z = sc_op<MAX>(pre, v[2]), a.w = sc_op<MAX>(pre, v[3]);
-			b.x = sc_op<MAX>(pre, v[4]), b.y = sc_op<MAX>(pre, v[5]), b.z = sc_op<MAX>(pre, v[6]), b.w = sc_op<MAX>(pre, v[7]);
-			*reinterpret_cast<uint4 *>(out + e0) = a;
-			*reinterpret_cast<uint4 *>(out + e0 + 4) = b;
-		} else {
-			for (int k = 0; k < SC_ITEMS; k++)
-				if (e0 + k < b1)
-					out[e0 + k] = sc_op<MAX>(pre, v[k]);
-		}
-		carry = sc_op<MAX>(carry, tile_tot);
+			sc_load<1>(J.src, t0 + SC_TILE, b1, &nx);
+		const uint32_t tot = sc_lane_scan<OP>(v);
+		uint32_t tile_tot;
+		const uint32_t pre = op(carry, block_exclusive_scan<SC_WAVES>(tot, wave_tot, tile_tot, op)); // carry, earlier waves, earlier lanes
+		sc_store<OP>(out, e0, b1, pre, v);
+		carry = op(carry, tile_tot);
 		__syncthreads();
 		if (more)
 			for (int k = 0; k < SC_ITEMS; k++)
@@ -199,96 +232,40 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_chunks(const ScanJobs jobs)
 }
 
 // ---- the same scans in ONE launch and one read of the input (decoupled look-back).  A workgroup takes a ticket = its
-// tile (LB_TILE elements, all loaded up front: 32 a lane), publishes the tile's aggregate, then its first wave looks back
+// tile (LB_TILE elements, all loaded up front: 64 a lane), publishes the tile's aggregate, then its first wave looks back
 // over the status words of the tiles in front of it, 64 at a time -- aggregates are added up until a tile is met that
 // already knows its inclusive prefix --, publishes its own inclusive prefix and the workgroup writes the tile out.  A tile
 // only ever waits for tiles with smaller tickets, i.e. for workgroups that are already running: no assumption about the
 // order workgroups are dispatched in.  Value and state of a tile share one 64-bit word (read and written with
 // agent-scope atomics: the L2 of another XCD never serves a stale one), so no fence orders anything.  The two-launch form
 // above reads its input twice (4.3 GB of the 170 GB a whole-genome pass moved in round 5, and 1.05 ms for the partials).
+// (Other tilings and ticket-free forms were measured and dropped: DESIGN.md section 4, "Scans ... in one launch".)
 static constexpr unsigned long long LB_AGG = 1ull << 32, LB_PREFIX = 2ull << 32;
-template <int MAX, int LB_SUB, bool TICKET>
+static constexpr int LB_SUB = 8, LB_TILE = SC_TILE * LB_SUB;
+template <int OP>
 __global__ void __launch_bounds__(SC_TPB) k_scan_lookback(const ScanJobs jobs)
 {
-	constexpr int LB_TILE = SC_TILE * LB_SUB;
-	__shared__ uint32_t wave_tot[LB_SUB][4];
+	__shared__ uint32_t wave_tot[LB_SUB][SC_WAVES];
 	__shared__ uint32_t s_tile, s_carry;
 	const ScanJob &J = jobs.j[blockIdx.y];
 	if (blockIdx.x >= J.tiles)
 		return;
+	const ScanOp<OP> op;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	uint32_t t = blockIdx.x;
-	if (TICKET && J.tiles > 1) { // (uniform: a one-tile job needs neither ticket nor status)
+	if (J.tiles > 1) { // (uniform: a one-tile job needs neither ticket nor status)
 		if (threadIdx.x == 0)
 			s_tile = atomicAdd(J.ticket, 1u);
 		__syncthreads();
 		t = s_tile;
 	}
 	const size_t b0 = (size_t)t * LB_TILE, b1 = b0 + LB_TILE < J.n ? b0 + LB_TILE : J.n;
-	uint32_t v[LB_SUB][SC_ITEMS], inc[LB_SUB];
-	if (b0 + LB_TILE <= J.n && !J.in8) { // a whole tile of words (uniform): every load of the lane is issued before the first is needed
-		const uint32_t *__restrict__ in = J.in + b0 + (size_t)threadIdx.x * SC_ITEMS;
-		uint4 a[LB_SUB][2];
-#pragma unroll
-		for (int q = 0; q < LB_SUB; q++)
-			a[q][0] = *reinterpret_cast<const uint4 *>(in + q * SC_TILE), a[q][1] = *reinterpret_cast<const uint4 *>(in + q * SC_TILE + 4);
-		if (J.sub) {
-			const uint32_t *__restrict__ sub = J.sub + b0 + (size_t)threadIdx.x * SC_ITEMS;
-#pragma unroll
-			for (int q = 0; q < LB_SUB; q++) {
-				const uint4 c = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE), d = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE + 4);
-				a[q][0].x -= c.x, a[q][0].y -= c.y, a[q][0].z -= c.z, a[q][0].w -= c.w;
-				a[q][1].x -= d.x, a[q][1].y -= d.y, a[q][1].z -= d.z, a[q][1].w -= d.w;
-			}
-		}
-#pragma unroll
-		for (int q = 0; q < LB_SUB; q++) {
-			v[q][0] = a[q][0].x, v[q][1] = a[q][0].y, v[q][2] = a[q][0].z, v[q][3] = a[q][0].w;
-			v[q][4] = a[q][1].x, v[q][5] = a[q][1].y, v[q][6] = a[q][1].z, v[q][7] = a[q][1].w;
-		}
-	} else if (b0 + LB_TILE <= J.n) { // a whole tile of bytes
-		const uint8_t *__restrict__ in8 = J.in8 + b0 + (size_t)threadIdx.x * SC_ITEMS;
-		uint2 a[LB_SUB];
-#pragma unroll
-		for (int q = 0; q < LB_SUB; q++)
-			a[q] = *reinterpret_cast<const uint2 *>(in8 + q * SC_TILE);
-#pragma unroll
-		for (int q = 0; q < LB_SUB; q++) {
-			v[q][0] = a[q].x & 0xFFu, v[q][1] = (a[q].x >> 8) & 0xFFu, v[q][2] = (a[q].x >> 16) & 0xFFu, v[q][3] = a[q].x >> 24;
-			v[q][4] = a[q].y & 0xFFu, v[q][5] = (a[q].y >> 8) & 0xFFu, v[q][6] = (a[q].y >> 16) & 0xFFu, v[q][7] = a[q].y >> 24;
-		}
-		if (J.sub) { // byte counts minus word counts
-			const uint32_t *__restrict__ sub = J.sub + b0 + (size_t)threadIdx.x * SC_ITEMS;
-#pragma unroll
-			for (int q = 0; q < LB_SUB; q++) {
-				const uint4 c = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE), d = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE + 4);
-				v[q][0] -= c.x, v[q][1] -= c.y, v[q][2] -= c.z, v[q][3] -= c.w;
-				v[q][4] -= d.x, v[q][5] -= d.y, v[q][6] -= d.z, v[q][7] -= d.w;
-			}
-		}
-	} else {
-#pragma unroll
-		for (int q = 0; q < LB_SUB; q++)
-			sc_load_tile(J, b0 + (size_t)q * SC_TILE + (size_t)threadIdx.x * SC_ITEMS, b1, v[q]);
-	}
+	uint32_t v[LB_SUB][SC_ITEMS], before[LB_SUB];
+	sc_load<LB_SUB>(J.src, b0, b1, v);
 #pragma unroll
 	for (int q = 0; q < LB_SUB; q++) {
-		uint32_t tot = 0; // lane-local exclusive scan
-#pragma unroll
-		for (int k = 0; k < SC_ITEMS; k++) {
-			const uint32_t x = v[q][k];
-			v[q][k] = tot;
-			tot = sc_op<MAX>(tot, x);
-		}
-		uint32_t i = tot; // inclusive scan of the lane totals across the wave
-		for (int off = 1; off < 64; off <<= 1) {
-			const uint32_t y = __shfl_up(i, off);
-			if (lane >= off)
-				i = sc_op<MAX>(i, y);
-		}
-		inc[q] = i;
-		if (lane == 63)
-			wave_tot[q][wave] = i;
+		const uint32_t tot = sc_lane_scan<OP>(v[q]);
+		before[q] = op.before(wave_scan_publish(tot, wave_tot[q], op), tot); // the earlier lanes of the wave
 	}
 	__syncthreads();
 	if (wave == 0) {
@@ -296,8 +273,8 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_lookback(const ScanJobs jobs)
 #pragma unroll
 		for (int q = 0; q < LB_SUB; q++)
 #pragma unroll
-			for (int w = 0; w < 4; w++)
-				agg = sc_op<MAX>(agg, wave_tot[q][w]);
+			for (int w = 0; w < SC_WAVES; w++)
+				agg = op(agg, wave_tot[q][w]);
 		uint32_t carry = 0;
 		if (t > 0) {
 			if (lane == 0)
@@ -311,10 +288,8 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_lookback(const ScanJobs jobs)
 				const unsigned long long need = stop >= 63 ? ~0ull : ((2ull << stop) - 1ull);
 				if (unset & need)
 					continue; // some tile up to there has not published yet: its workgroup is running, read again
-				uint32_t x = lane <= stop ? (uint32_t)w : 0u;
-				for (int off = 32; off; off >>= 1)
-					x = sc_op<MAX>(x, __shfl_down(x, off));
-				carry = sc_op<MAX>(carry, __shfl(x, 0));
+				const uint32_t x = wave_reduce(lane <= stop ? (uint32_t)w : 0u, op);
+				carry = op(carry, __shfl(x, 0));
 				if (has_p)
 					break;
 				base -= 64;
@@ -322,7 +297,7 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_lookback(const ScanJobs jobs)
 		}
 		if (lane == 0) {
 			if (J.tiles > 1)
-				__hip_atomic_store(J.status + t, LB_PREFIX | sc_op<MAX>(carry, agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				__hip_atomic_store(J.status + t, LB_PREFIX | op(carry, agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			s_carry = carry;
 		}
 	}
@@ -330,51 +305,25 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_lookback(const ScanJobs jobs)
 	uint32_t pre_sub = s_carry; // everything in front of the sub-tile
 #pragma unroll
 	for (int q = 0; q < LB_SUB; q++) {
-		const size_t e0 = b0 + (size_t)q * SC_TILE + (size_t)threadIdx.x * SC_ITEMS;
-		uint32_t pre = pre_sub; // ... in front of this lane: earlier waves, earlier lanes
-		for (int w = 0; w < wave; w++)
-			pre = sc_op<MAX>(pre, wave_tot[q][w]);
-		const uint32_t lane_excl = __shfl_up(inc[q], 1);
-		if (lane > 0)
-			pre = sc_op<MAX>(pre, lane_excl);
-		if (e0 + SC_ITEMS <= b1) { // (always, in a whole tile)
-			uint4 a, b;
-			a.x = sc_op<MAX>(pre, v[q][0]), a.y = sc_op<MAX>(pre, v[q][1]), a.z = sc_op<MAX>(pre, v[q][2]), a.w = sc_op<MAX>(pre, v[q][3]);
-			b.x = sc_op<MAX>(pre, v[q][4]), b.y = sc_op<MAX>(pre, v[q][5]), b.z = sc_op<MAX>(pre, v[q][6]), b.w = sc_op<MAX>(pre, v[q][7]);
-			*reinterpret_cast<uint4 *>(J.out + e0) = a;
-			*reinterpret_cast<uint4 *>(J.out + e0 + 4) = b;
-		} else {
-			for (int k = 0; k < SC_ITEMS; k++)
-				if (e0 + k < b1)
-					J.out[e0 + k] = sc_op<MAX>(pre, v[q][k]);
-		}
-		pre_sub = sc_op<MAX>(pre_sub, sc_op<MAX>(sc_op<MAX>(wave_tot[q][0], wave_tot[q][1]), sc_op<MAX>(wave_tot[q][2], wave_tot[q][3])));
+		uint32_t sub_tot;
+		const uint32_t pre = op(op(pre_sub, waves_before<SC_WAVES>(wave_tot[q], sub_tot, op)), before[q]);
+		sc_store<OP>(J.out, b0 + (size_t)q * SC_TILE + (size_t)threadIdx.x * SC_ITEMS, b1, pre, v[q]);
+		pre_sub = op(pre_sub, sub_tot);
 	}
 }
 
 static constexpr size_t SC_LEGACY_BYTES = SC_MAX_BLOCKS * 16 + 256; // (two u32 jobs of the two-launch form, or one job of 128-bit words)
-// variants (POVU_HIP_LB_VARIANT, measured with tools/scan_time.py on 10^8 words: two launches 0.268 ms; 0: 0.271; 1: 0.249;
-// 2: 0.242; 3: 0.231): bit 1 = 64 elements a lane instead of 32, bit 0 = the tile is the workgroup's index instead of a
-// ticket (relies on workgroups being dispatched in index order: not the default).  Tried and dropped in round 5: a tile per
-// WAVE (2048 elements, no barrier behind the ticket: 0.248), and as many workgroups as are resident at once, each striding
-// over the tiles without a ticket (0.251) -- a streaming read + write of 8 bytes an element stays at ~3.4 TB/s either way.
-static int lb_variant()
-{
-	static const int v = getenv("POVU_HIP_LB_VARIANT") ? atoi(getenv("POVU_HIP_LB_VARIANT")) : 2;
-	return v;
-}
 // below this many elements the two-launch form is the faster one: its second read comes out of the Infinity Cache
 // (10^7 words: 0.023 ms against 0.035) -- except when every job fits one tile (one launch instead of two, no fill)
 static constexpr size_t LB_MIN = 48u << 20;
-static size_t lb_tile() { return (size_t)SC_TILE * ((lb_variant() & 2) ? 8 : 4); }
-static size_t lb_tiles(size_t n) { return (n + lb_tile() - 1) / lb_tile(); }
+static size_t lb_tiles(size_t n) { return (n + LB_TILE - 1) / LB_TILE; }
 static size_t lb_job_bytes(size_t n) { return 16 + 8 * lb_tiles(n); } // ticket (+ padding), status words
 size_t scan_tmp_bytes(size_t n)
 {
 	return SC_LEGACY_BYTES + 2 * lb_job_bytes(n) + 64; // the partials of the two-launch form, then ticket + status words of two jobs
 }
 // one or two jobs in one launch; false: the temporary storage was sized for fewer elements (the caller takes two launches)
-template <int MAX>
+template <int OP>
 static bool scan_lookback(ScanJobs &jobs, int nj, void *tmp, size_t tmp_bytes, hipStream_t s)
 {
 	static const bool off = getenv("POVU_HIP_SCAN_TWO_LAUNCH") != nullptr; // (A/B hook)
@@ -406,161 +355,86 @@ static bool scan_lookback(ScanJobs &jobs, int nj, void *tmp, size_t tmp_bytes, h
 		return false;
 	if (clear)
 		HIP_CHECK(hipMemsetAsync(static_cast<char *>(tmp) + SC_LEGACY_BYTES, 0, clear, s));
-	switch (lb_variant()) {
-	case 0: KLAUNCH((k_scan_lookback<MAX, 4, true>), dim3(gx, nj), dim3(SC_TPB), 0, s, jobs); break;
-	case 1: KLAUNCH((k_scan_lookback<MAX, 4, false>), dim3(gx, nj), dim3(SC_TPB), 0, s, jobs); break;
-	case 2: KLAUNCH((k_scan_lookback<MAX, 8, true>), dim3(gx, nj), dim3(SC_TPB), 0, s, jobs); break;
-	default: KLAUNCH((k_scan_lookback<MAX, 8, false>), dim3(gx, nj), dim3(SC_TPB), 0, s, jobs); break;
-	}
+	KLAUNCH(k_scan_lookback<OP>, dim3(gx, nj), dim3(SC_TPB), 0, s, jobs);
 	return true;
 }
 
-static ScanJob make_scan_job(const uint32_t *in, uint32_t *out, size_t n, uint32_t *partial, const uint8_t *in8 = nullptr,
-			     const uint32_t *sub = nullptr)
+struct ScanReq {
+	ScanSrc src;
+	uint32_t *out;
+	size_t n;
+};
+static ScanJob make_scan_job(const ScanReq &r, uint32_t *partial)
 {
-	if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(in8) | reinterpret_cast<uintptr_t>(out) |
-	     reinterpret_cast<uintptr_t>(sub)) & 15)
+	if ((reinterpret_cast<uintptr_t>(r.src.in) | reinterpret_cast<uintptr_t>(r.src.sub) | reinterpret_cast<uintptr_t>(r.out)) & 15)
 		throw HipError("scan: operands must be 16-byte aligned");
-	size_t blocks = (n + SC_TILE - 1) / SC_TILE;
+	size_t blocks = (r.n + SC_TILE - 1) / SC_TILE;
 	if (blocks > SC_MAX_BLOCKS)
 		blocks = SC_MAX_BLOCKS;
-	size_t chunk = (n + blocks - 1) / blocks;
+	size_t chunk = (r.n + blocks - 1) / blocks;
 	chunk = (chunk + SC_TILE - 1) / SC_TILE * SC_TILE; // whole tiles: every tile base stays 16-byte aligned
-	blocks = (n + chunk - 1) / chunk;
-	return ScanJob{in, sub, in8, out, n, chunk, (uint32_t)blocks, partial, 0u, nullptr, nullptr};
+	blocks = (r.n + chunk - 1) / chunk;
+	return ScanJob{r.src, r.out, r.n, chunk, (uint32_t)blocks, partial, 0u, nullptr, nullptr};
 }
-
-template <int MAX>
-static void scan_exclusive(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s)
+// the host side of every u32 scan: one job, or two in the same launches.  An empty job is left out, so a pair with one
+// is a single job; the one-launch form where it applies, else partials and chunks
+template <int OP>
+static void scan_run(const ScanReq &r0, const ScanReq &r1, void *tmp, size_t tmp_bytes, hipStream_t s)
 {
-	if (n == 0)
-		return;
-	if (tmp_bytes < SC_MAX_BLOCKS * sizeof(uint32_t))
-		throw HipError("scan: temporary storage too small");
 	ScanJobs jobs{};
-	jobs.j[0] = make_scan_job(in, out, n, static_cast<uint32_t *>(tmp));
-	if (scan_lookback<MAX>(jobs, 1, tmp, tmp_bytes, s))
+	unsigned nj = 0, gx = 0;
+	for (const ScanReq *r : {&r0, &r1})
+		if (r->n) {
+			if (tmp_bytes < (nj + 1) * SC_MAX_BLOCKS * sizeof(uint32_t))
+				throw HipError("scan: temporary storage too small");
+			jobs.j[nj] = make_scan_job(*r, static_cast<uint32_t *>(tmp) + nj * SC_MAX_BLOCKS);
+			gx = std::max(gx, jobs.j[nj++].blocks);
+		}
+	if (!nj || scan_lookback<OP>(jobs, (int)nj, tmp, tmp_bytes, s))
 		return;
-	KLAUNCH(k_scan_partials<MAX>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
-	KLAUNCH(k_scan_chunks<MAX>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
+	KLAUNCH(k_scan_partials<OP>, dim3(gx, nj), dim3(SC_TPB), 0, s, jobs);
+	KLAUNCH(k_scan_chunks<OP>, dim3(gx, nj), dim3(SC_TPB), 0, s, jobs);
 }
-
-// byte inputs: one or two independent jobs in the same two launches (in1 may be null)
-void scan_exclusive_u8(const uint8_t *in0, uint32_t *out0, size_t n0, const uint8_t *in1, uint32_t *out1, size_t n1, void *tmp,
-		       size_t tmp_bytes, hipStream_t s)
-{
-	if (tmp_bytes < 2 * SC_MAX_BLOCKS * sizeof(uint32_t))
-		throw HipError("scan: temporary storage too small");
-	ScanJobs jobs{};
-	unsigned gx = 0, gy = 0;
-	if (n0) {
-		jobs.j[gy] = make_scan_job(nullptr, out0, n0, static_cast<uint32_t *>(tmp) + gy * SC_MAX_BLOCKS, in0);
-		gx = std::max(gx, jobs.j[gy].blocks);
-		gy++;
-	}
-	if (in1 && n1) {
-		jobs.j[gy] = make_scan_job(nullptr, out1, n1, static_cast<uint32_t *>(tmp) + gy * SC_MAX_BLOCKS, in1);
-		gx = std::max(gx, jobs.j[gy].blocks);
-		gy++;
-	}
-	if (!gy)
-		return;
-	if (scan_lookback<0>(jobs, (int)gy, tmp, tmp_bytes, s))
-		return;
-	KLAUNCH(k_scan_partials<0>, dim3(gx, gy), dim3(SC_TPB), 0, s, jobs);
-	KLAUNCH(k_scan_chunks<0>, dim3(gx, gy), dim3(SC_TPB), 0, s, jobs);
-}
+static constexpr ScanReq SC_NONE{};
 
 void scan_exclusive_u32(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s)
 {
-	scan_exclusive<0>(in, out, n, tmp, tmp_bytes, s);
+	scan_run<0>({ScanSrc::words(in), out, n}, SC_NONE, tmp, tmp_bytes, s);
+}
+void scan_exclusive_max_u32(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s)
+{
+	scan_run<1>({ScanSrc::words(in), out, n}, SC_NONE, tmp, tmp_bytes, s);
 }
 void scan_exclusive_diff_u32(const uint32_t *in, const uint32_t *sub, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes,
 			     hipStream_t s)
 {
-	if (n == 0)
-		return;
-	if (tmp_bytes < SC_MAX_BLOCKS * sizeof(uint32_t))
-		throw HipError("scan: temporary storage too small");
-	ScanJobs jobs{};
-	jobs.j[0] = make_scan_job(in, out, n, static_cast<uint32_t *>(tmp), nullptr, sub);
-	if (scan_lookback<0>(jobs, 1, tmp, tmp_bytes, s))
-		return;
-	KLAUNCH(k_scan_partials<0>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
-	KLAUNCH(k_scan_chunks<0>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
+	scan_run<0>({ScanSrc::words(in, sub), out, n}, SC_NONE, tmp, tmp_bytes, s);
 }
-
 void scan_exclusive_diff_u8_u32(const uint8_t *in8, const uint32_t *sub, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes,
 				hipStream_t s)
 {
-	if (n == 0)
-		return;
-	if (tmp_bytes < SC_MAX_BLOCKS * sizeof(uint32_t))
-		throw HipError("scan: temporary storage too small");
-	ScanJobs jobs{};
-	jobs.j[0] = make_scan_job(nullptr, out, n, static_cast<uint32_t *>(tmp), in8, sub);
-	if (scan_lookback<0>(jobs, 1, tmp, tmp_bytes, s))
-		return;
-	KLAUNCH(k_scan_partials<0>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
-	KLAUNCH(k_scan_chunks<0>, dim3(jobs.j[0].blocks, 1), dim3(SC_TPB), 0, s, jobs);
+	scan_run<0>({ScanSrc::of_bytes(in8, sub), out, n}, SC_NONE, tmp, tmp_bytes, s);
 }
-
-void scan_exclusive_u32_u8_pair(const uint32_t *in0, uint32_t *out0, size_t n0, const uint8_t *in1, uint32_t *out1, size_t n1,
-				void *tmp, size_t tmp_bytes, hipStream_t s)
+// byte inputs: one or two independent jobs in the same launches (in1 may be null)
+void scan_exclusive_u8(const uint8_t *in0, uint32_t *out0, size_t n0, const uint8_t *in1, uint32_t *out1, size_t n1, void *tmp,
+		       size_t tmp_bytes, hipStream_t s)
 {
-	if (n0 == 0 || n1 == 0) {
-		scan_exclusive<0>(in0, out0, n0, tmp, tmp_bytes, s);
-		scan_exclusive_u8(in1, out1, n1, nullptr, nullptr, 0, tmp, tmp_bytes, s);
-		return;
-	}
-	if (tmp_bytes < 2 * SC_MAX_BLOCKS * sizeof(uint32_t))
-		throw HipError("scan: temporary storage too small");
-	ScanJobs jobs{};
-	jobs.j[0] = make_scan_job(in0, out0, n0, static_cast<uint32_t *>(tmp));
-	jobs.j[1] = make_scan_job(nullptr, out1, n1, static_cast<uint32_t *>(tmp) + SC_MAX_BLOCKS, in1);
-	if (scan_lookback<0>(jobs, 2, tmp, tmp_bytes, s))
-		return;
-	const unsigned gx = std::max(jobs.j[0].blocks, jobs.j[1].blocks);
-	KLAUNCH(k_scan_partials<0>, dim3(gx, 2), dim3(SC_TPB), 0, s, jobs);
-	KLAUNCH(k_scan_chunks<0>, dim3(gx, 2), dim3(SC_TPB), 0, s, jobs);
+	scan_run<0>({ScanSrc::of_bytes(in0), out0, n0}, {ScanSrc::of_bytes(in1), out1, in1 ? n1 : 0}, tmp, tmp_bytes, s);
 }
-
-template <int OP>
-static void scan_exclusive_pair(const uint32_t *in0, uint32_t *out0, size_t n0, const uint32_t *in1, uint32_t *out1, size_t n1,
-				void *tmp, size_t tmp_bytes, hipStream_t s)
-{
-	if (n0 == 0 || n1 == 0) {
-		scan_exclusive<OP>(in0, out0, n0, tmp, tmp_bytes, s);
-		scan_exclusive<OP>(in1, out1, n1, tmp, tmp_bytes, s);
-		return;
-	}
-	if (tmp_bytes < 2 * SC_MAX_BLOCKS * sizeof(uint32_t))
-		throw HipError("scan: temporary storage too small");
-	ScanJobs jobs{};
-	jobs.j[0] = make_scan_job(in0, out0, n0, static_cast<uint32_t *>(tmp));
-	jobs.j[1] = make_scan_job(in1, out1, n1, static_cast<uint32_t *>(tmp) + SC_MAX_BLOCKS);
-	if (scan_lookback<OP>(jobs, 2, tmp, tmp_bytes, s))
-		return;
-	const unsigned gx = std::max(jobs.j[0].blocks, jobs.j[1].blocks);
-	KLAUNCH(k_scan_partials<OP>, dim3(gx, 2), dim3(SC_TPB), 0, s, jobs);
-	KLAUNCH(k_scan_chunks<OP>, dim3(gx, 2), dim3(SC_TPB), 0, s, jobs);
-}
-
 void scan_exclusive_u32_pair(const uint32_t *in0, uint32_t *out0, size_t n0, const uint32_t *in1, uint32_t *out1, size_t n1,
 			     void *tmp, size_t tmp_bytes, hipStream_t s)
 {
-	scan_exclusive_pair<0>(in0, out0, n0, in1, out1, n1, tmp, tmp_bytes, s);
+	scan_run<0>({ScanSrc::words(in0), out0, n0}, {ScanSrc::words(in1), out1, n1}, tmp, tmp_bytes, s);
 }
-
+void scan_exclusive_u32_u8_pair(const uint32_t *in0, uint32_t *out0, size_t n0, const uint8_t *in1, uint32_t *out1, size_t n1,
+				void *tmp, size_t tmp_bytes, hipStream_t s)
+{
+	scan_run<0>({ScanSrc::words(in0), out0, n0}, {ScanSrc::of_bytes(in1), out1, n1}, tmp, tmp_bytes, s);
+}
 void scan_exclusive_xor_u32_pair(const uint32_t *in0, uint32_t *out0, const uint32_t *in1, uint32_t *out1, size_t n, void *tmp,
 				 size_t tmp_bytes, hipStream_t s)
 {
-	scan_exclusive_pair<2>(in0, out0, n, in1, out1, n, tmp, tmp_bytes, s);
-}
-
-void scan_exclusive_max_u32(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s)
-{
-	scan_exclusive<1>(in, out, n, tmp, tmp_bytes, s);
+	scan_run<2>({ScanSrc::words(in0), out0, n}, {ScanSrc::words(in1), out1, n}, tmp, tmp_bytes, s);
 }
 
 // ---- 64-bit totals of u32 counts: one array, or two of the same length side by side
@@ -671,42 +545,29 @@ __device__ __forceinline__ size_t x128_len(const Xor128Job &J)
 	const size_t m = (size_t)*J.n_dev + 1;
 	return m < J.n ? m : J.n;
 }
-__device__ __forceinline__ ulonglong2 x128(const ulonglong2 a, const ulonglong2 b) { return make_ulonglong2(a.x ^ b.x, a.y ^ b.y); }
-__device__ __forceinline__ ulonglong2 x128_shfl_down(const ulonglong2 v, int off) { return make_ulonglong2(__shfl_down(v.x, off), __shfl_down(v.y, off)); }
-__device__ __forceinline__ ulonglong2 x128_shfl_up(const ulonglong2 v, int off) { return make_ulonglong2(__shfl_up(v.x, off), __shfl_up(v.y, off)); }
-__device__ __forceinline__ ulonglong2 x128_block_reduce(ulonglong2 v, ulonglong2 *sh)
-{
-	for (int off = 32; off; off >>= 1)
-		v = x128(v, x128_shfl_down(v, off));
-	if ((threadIdx.x & 63) == 0)
-		sh[threadIdx.x >> 6] = v;
-	__syncthreads();
-	const ulonglong2 r = x128(x128(sh[0], sh[1]), x128(sh[2], sh[3]));
-	__syncthreads();
-	return r;
-}
 __global__ void __launch_bounds__(SC_TPB) k_xor128_partials(const Xor128Job J)
 {
-	__shared__ ulonglong2 sh[4];
+	__shared__ ulonglong2 sh[SC_WAVES];
+	const Xor128 x128;
 	const size_t n = x128_len(J);
 	const size_t b0 = (size_t)blockIdx.x * J.chunk, b1 = b0 + J.chunk < n ? b0 + J.chunk : n;
 	ulonglong2 acc = make_ulonglong2(0ull, 0ull);
 	for (size_t i = b0 + threadIdx.x; i < b1; i += SC_TPB)
 		acc = x128(acc, J.in[i]);
-	acc = x128_block_reduce(acc, sh);
+	acc = block_reduce<SC_WAVES>(acc, sh, x128);
 	if (threadIdx.x == 0)
 		J.partial[blockIdx.x] = acc;
 }
 __global__ void __launch_bounds__(SC_TPB) k_xor128_chunks(const Xor128Job J)
 {
-	__shared__ ulonglong2 sh[4], wave_tot[4];
+	__shared__ ulonglong2 sh[SC_WAVES], wave_tot[SC_WAVES];
+	const Xor128 x128;
 	ulonglong2 base = make_ulonglong2(0ull, 0ull);
 	for (uint32_t k = threadIdx.x; k < blockIdx.x; k += SC_TPB)
 		base = x128(base, J.partial[k]);
-	ulonglong2 carry = x128_block_reduce(base, sh);
+	ulonglong2 carry = block_reduce<SC_WAVES>(base, sh, x128);
 	const size_t n = x128_len(J);
 	const size_t b0 = (size_t)blockIdx.x * J.chunk, b1 = b0 + J.chunk < n ? b0 + J.chunk : n;
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	for (size_t t0 = b0; t0 < b1; t0 += X128_TILE) {
 		const size_t e0 = t0 + (size_t)threadIdx.x * X128_ITEMS;
 		ulonglong2 v[X128_ITEMS];
@@ -718,22 +579,8 @@ __global__ void __launch_bounds__(SC_TPB) k_xor128_chunks(const Xor128Job J)
 			v[k] = tot;
 			tot = x128(tot, x);
 		}
-		ulonglong2 inc = tot;
-		for (int off = 1; off < 64; off <<= 1) {
-			const ulonglong2 y = x128_shfl_up(inc, off);
-			if (lane >= off)
-				inc = x128(inc, y);
-		}
-		if (lane == 63)
-			wave_tot[wave] = inc;
-		__syncthreads();
-		ulonglong2 pre = carry;
-		for (int w = 0; w < wave; w++)
-			pre = x128(pre, wave_tot[w]);
-		const ulonglong2 lane_excl = x128_shfl_up(inc, 1);
-		if (lane > 0)
-			pre = x128(pre, lane_excl);
-		const ulonglong2 tile_tot = x128(x128(wave_tot[0], wave_tot[1]), x128(wave_tot[2], wave_tot[3]));
+		ulonglong2 tile_tot;
+		const ulonglong2 pre = x128(carry, block_exclusive_scan<SC_WAVES>(tot, wave_tot, tile_tot, x128));
 		for (int k = 0; k < X128_ITEMS; k++)
 			if (e0 + k < b1)
 				J.out[e0 + k] = x128(pre, v[k]);
@@ -782,34 +629,13 @@ __device__ __forceinline__ uint32_t cp_load16(const uint8_t *__restrict__ flag, 
 	}
 	return (uint32_t)__popc(bits);
 }
-__device__ __forceinline__ uint32_t cp_block_exclusive(uint32_t v, uint32_t *sh, uint32_t &total)
-{
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t inc = v;
-	for (int off = 1; off < 64; off <<= 1) {
-		const uint32_t y = __shfl_up(inc, off);
-		if (lane >= off)
-			inc += y;
-	}
-	if (lane == 63)
-		sh[wave] = inc;
-	__syncthreads();
-	uint32_t before = inc - v;
-	total = 0;
-	for (int w = 0; w < CP_TPB / 64; w++) {
-		if (w < wave)
-			before += sh[w];
-		total += sh[w];
-	}
-	return before;
-}
 __global__ void __launch_bounds__(CP_TPB) k_cp_count(const uint8_t *__restrict__ flag, size_t n, uint32_t *__restrict__ tile_cnt)
 {
 	__shared__ uint32_t sh[CP_TPB / 64];
 	uint32_t bits, total;
 	const uint32_t bx = BIDX;
 	const uint32_t c = cp_load16(flag, (size_t)bx * CP_TILE + (size_t)threadIdx.x * CP_ITEMS, n, bits);
-	(void)cp_block_exclusive(c, sh, total);
+	(void)block_exclusive_scan<CP_TPB / 64>(c, sh, total, ScanOp<0>{});
 	if (threadIdx.x == 0)
 		tile_cnt[bx] = total;
 }
@@ -821,22 +647,8 @@ __global__ void __launch_bounds__(1024) k_cp_scan_tiles(uint32_t *tile_cnt, uint
 	uint32_t sum = 0;
 	for (uint32_t k = lo; k < hi; k++)
 		sum += tile_cnt[k];
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint32_t inc = sum;
-	for (int off = 1; off < 64; off <<= 1) {
-		const uint32_t y = __shfl_up(inc, off);
-		if (lane >= off)
-			inc += y;
-	}
-	if (lane == 63)
-		sh[wave] = inc;
-	__syncthreads();
-	uint32_t before = inc - sum, total = 0;
-	for (int w = 0; w < 16; w++) {
-		if (w < wave)
-			before += sh[w];
-		total += sh[w];
-	}
+	uint32_t total;
+	uint32_t before = block_exclusive_scan<16>(sum, sh, total, ScanOp<0>{});
 	for (uint32_t k = lo; k < hi; k++) {
 		const uint32_t c = tile_cnt[k];
 		tile_cnt[k] = before;
@@ -853,7 +665,7 @@ __global__ void __launch_bounds__(CP_TPB) k_cp_write(const uint8_t *__restrict__
 	const size_t e0 = (size_t)bx * CP_TILE + (size_t)threadIdx.x * CP_ITEMS;
 	uint32_t bits, total;
 	const uint32_t c = cp_load16(flag, e0, n, bits);
-	uint32_t at = tile_base[bx] + cp_block_exclusive(c, sh, total);
+	uint32_t at = tile_base[bx] + block_exclusive_scan<CP_TPB / 64>(c, sh, total, ScanOp<0>{});
 	while (bits) {
 		const int k = __ffs((int)bits) - 1;
 		bits &= bits - 1;
@@ -1034,18 +846,8 @@ __global__ void __launch_bounds__(RS_TPB) k_rs_scatter(const uint32_t *__restric
 			mine += run;
 		}
 	}
-	uint32_t inc = mine;
-	for (int off = 1; off < 64; off <<= 1) {
-		const uint32_t y = __shfl_up(inc, off);
-		if ((int)lane >= off)
-			inc += y;
-	}
-	if (lane == 63)
-		wsum[wave] = inc;
-	__syncthreads();
-	uint32_t before = inc - mine;
-	for (uint32_t w = 0; w < wave; w++)
-		before += wsum[w];
+	uint32_t tile_pairs; // (= the tile's live pairs; not needed)
+	uint32_t before = block_exclusive_scan<RS_WAVES>(mine, wsum, tile_pairs, ScanOp<0>{});
 	for (uint32_t k = 0; k < per; k++) {
 		const uint32_t d = threadIdx.x * per + k;
 		if (d < bins) {

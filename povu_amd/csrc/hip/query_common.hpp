@@ -79,17 +79,7 @@ __device__ __forceinline__ T wave_sum(T v)
 		v += __shfl_xor(v, o, 64);
 	return v;
 }
-// inclusive prefix sum over the wave: lane l gets the sum of lanes 0 .. l
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t v)
-{
-	const int lane = (int)(threadIdx.x & 63u);
-	for (int o = 1; o < 64; o <<= 1) {
-		const uint32_t y = __shfl_up(v, o, 64);
-		if (lane >= o)
-			v += y;
-	}
-	return v;
-}
+// (inclusive prefix sum over the wave: wave_inclusive_sum, common.hpp)
 
 // vertex index of segment `id` in the ascending `vid`, NO_QUERY when the graph has no such segment
 __device__ __forceinline__ uint32_t find_vertex(const uint32_t *__restrict__ vid, uint32_t V, uint32_t id)

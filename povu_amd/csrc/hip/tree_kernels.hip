@@ -1770,28 +1770,14 @@ __global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t 
 	}
 	// exclusive prefix of n over the workgroup
 	__shared__ uint32_t wsum[TPB / 64], base;
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	uint32_t inc = n;
-	for (int off = 1; off < 64; off <<= 1) {
-		const uint32_t y = __shfl_up(inc, off);
-		if ((int)lane >= off)
-			inc += y;
-	}
-	if (lane == 63)
-		wsum[wave] = inc;
-	__syncthreads();
-	uint32_t before = 0, all = 0;
-	for (uint32_t w = 0; w < TPB / 64; w++) {
-		if (w < wave)
-			before += wsum[w];
-		all += wsum[w];
-	}
+	uint32_t all;
+	const uint32_t before = block_exclusive_scan<TPB / 64>(n, wsum, all, ScanOp<0>{});
 	if (threadIdx.x == 0)
 		base = all ? atomicAdd(total_out, all) : 0u;
 	__syncthreads();
 	if (!n || base + all > cap) // (more back edges than the list was carved for cannot happen -- the host checks the total --, and must not write)
 		return;
-	uint32_t at = base + before + inc - n;
+	uint32_t at = base + before;
 	for (uint32_t it = 0; it < BE_ITER; it++) {
 		const uint32_t k = cnt8[it][threadIdx.x];
 		if (!k)
