@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "forest_wire.hpp"
+
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -241,7 +243,7 @@ public:
 	template <typename T>
 	T *take(size_t n)
 	{
-		const size_t bytes = (n * sizeof(T) + 63) & ~size_t(63);
+		const size_t bytes = forest_wire::pad64(n * sizeof(T));
 		for (auto &c : chunks_)
 			if (c.cap - c.top >= bytes) {
 				char *r = c.p + c.top;

@@ -153,23 +153,8 @@ struct povu_hip_forest {
 	std::shared_ptr<PinnedPool> pool;
 	size_t meta_reserve = 0; // trees a block leaves room for behind the arrays (povu_hip_forest_share writes their table there)
 	static size_t meta_bytes(size_t n_trees) { return 64 + 32 * n_trees; }
-	// the five arrays of a block of `total` PVST vertices, each padded to 64 B: a | z | parent | a_or | z_or; returns the
-	// bytes they take (out == nullptr: only measures)
-	struct Arrays {
-		uint32_t *a = nullptr, *z = nullptr, *parent = nullptr;
-		uint8_t *aor = nullptr, *zor = nullptr;
-	};
-	static size_t layout(void *q, size_t total, Arrays *out = nullptr)
-	{
-		const size_t w = (total * 4 + 63) & ~size_t(63), b = (total + 63) & ~size_t(63);
-		if (out) {
-			char *c = static_cast<char *>(q);
-			out->a = (uint32_t *)c, out->z = (uint32_t *)(c + w), out->parent = (uint32_t *)(c + 2 * w);
-			out->aor = (uint8_t *)(c + 3 * w), out->zor = (uint8_t *)(c + 3 * w + b);
-		}
-		return 3 * w + 2 * b;
-	}
-	static size_t block_bytes_for(size_t total) { return layout(nullptr, total) + 64; } // (what a block takes on the wire)
+	using Arrays = forest_wire::PvstArrays; // the five arrays of a block: a | z | parent | a_or | z_or
+	static size_t block_bytes_for(size_t total) { return Arrays::layout(nullptr, total) + 64; } // (what a block takes on the wire)
 	// The PVST arrays live in page-locked blocks: blocks[0] is the one the pass fills (a mixed pass: blocks[1] holds its redone
 	// components); a merged forest holds the blocks it took over from other forests, received from other ranks or mapped
 	// from their segments, so that merging never copies a PVST array.  With a block go the labels of
@@ -195,7 +180,7 @@ struct povu_hip_forest {
 			b.pool = pool;
 			b.p = pool->get(block_bytes_for(total) + meta_bytes(meta_reserve), b.cap, &b.seg);
 		}
-		b.bytes = layout(b.p, total, &b);
+		b.bytes = Arrays::layout(b.p, total, &b);
 		blocks.push_back(std::move(b));
 		return blocks.back();
 	}

@@ -12,6 +12,29 @@ namespace forest_wire
 {
 inline size_t pad64(size_t b) { return (b + 63) & ~size_t(63); }
 
+// ---------------------------------------------------------------- a PVST block
+// the five arrays of a block of `total` PVST vertices, each padded to 64 B: a | z | parent | a_or | z_or.  The forest's
+// page-locked blocks, the class stage's device block and the copies between the two all take their offsets from here.
+struct PvstArrays {
+	uint32_t *a = nullptr, *z = nullptr, *parent = nullptr;
+	uint8_t *aor = nullptr, *zor = nullptr; // 0 forward, 1 reverse
+	static size_t word_bytes(size_t total) { return pad64(total * 4); } // one of a, z, parent
+	static size_t flag_bytes(size_t total) { return pad64(total); }	    // one of a_or, z_or
+	// places the arrays in the block at `q`; returns the bytes they take (out == nullptr: only measures)
+	static size_t layout(void *q, size_t total, PvstArrays *out = nullptr)
+	{
+		const size_t w = word_bytes(total), b = flag_bytes(total);
+		if (out) {
+			char *c = static_cast<char *>(q);
+			out->a = (uint32_t *)c, out->z = (uint32_t *)(c + w), out->parent = (uint32_t *)(c + 2 * w);
+			out->aor = (uint8_t *)(c + 3 * w), out->zor = (uint8_t *)(c + 3 * w + b);
+		}
+		return 3 * w + 2 * b;
+	}
+	// what layout() takes at most, linear in `total`: 14 bytes a vertex and one 64 B step per array
+	static size_t bound(size_t total) { return 3 * (total * 4 + 64) + 2 * (total + 64); }
+};
+
 // ---------------------------------------------------------------- the tree table
 // one tree of a block: 8 words {component_id, n_vtx, n_links, n_pvst, off lo, off hi, n_hairpins, sub_c}
 struct TreeRecord {

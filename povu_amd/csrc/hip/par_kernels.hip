@@ -572,7 +572,7 @@ __global__ void k_top_bracket(uint32_t n, const uint32_t *__restrict__ gsize, co
 			i = seg_first_less(segB, lo + np, hi, v);
 	}
 	if (i == NIL) {
-		atomicAdd(&err[0], 1u); // cannot happen: every list holds at least a simplifying bracket
+		atomicAdd(&err[PW_NO_BRACKET], 1u); // cannot happen: every list holds at least a simplifying bracket
 		ckey[q] = NIL;
 		lsz[at] = 0;
 		return;
@@ -1230,7 +1230,7 @@ static void for_each_span(ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 	}
 	take1(NB + 2, pw.b_src, pw.b_tgt, pw.b_ord);
 	take1(V + 4, pw.sdl);
-	take1(16, pw.err);
+	take1(PASS_WORDS, pw.err);
 	take1(Cmax + 2, pw.comp_bad); // (zeroed when the pass starts, ahead of the tree stage)
 	pw.scan_tmp_bytes = std::max(scan_tmp_bytes(std::max(T, NB) + 4), 2 * compact_tmp_bytes(std::max(T, NB) + 4));
 	pw.sort_tmp_bytes = sort_tmp_bytes(std::max(std::max(T, NB), std::max(4 * V, 2 * E) + 8) + 4);
@@ -1263,7 +1263,7 @@ static void for_each_span(ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 	take(SegTree::tree_words(T + 1), pw.segA.tree);
 	take(SegTree::tree_words(NB + 1), pw.segB.tree);
 	take(SegTree::tree_words(S + 1), pw.segP.tree, pw.segL.tree);
-	take(((S + Cmax + 2) * 4 + 64) * 3 + ((S + Cmax + 2) + 64) * 2 + 256, pw.stage);
+	take(forest_wire::PvstArrays::bound(S + Cmax + 2) + 256, pw.stage); // (a PVST block of every stack entry and one root per component)
 	if (o.hairpins) {
 		take(2 * T + 4, pw.hp_b12);
 		take(T + 2, pw.hpf);
@@ -1289,9 +1289,58 @@ void par_carve(Arena &ar, ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 	for_each_span(pw, V, E, Cmax, groups, o, take);
 }
 
+// ------------------------------------------------------------- overlays
+// Every array of ParWs that the class stage uses under another type or meaning than the one it is declared with, named
+// once.  Next to each view: the array under it, and from which kernel to which the view is live (the array's earlier or
+// later tenant in brackets).  The steps below address these arrays through the views only.
+struct ClassViews {
+	// ---- row D, up to the placing of the brackets
+	uint4 *brec;	      // psA: bridge flags as a bit-rank directory over T + 1 positions ((T / 64 + 2) records = T / 4 + 32 bytes); k_bridge_flags -> k_capping [then cps]
+	uint32_t *brec_cnt;   // f8a: the counts its build scans ((T / 64 + 2) words); inside bitrank_build only [then cflag]
+	uint32_t *pscov;      // psB: scan of the coverage differences; the difference scan -> k_bridge_flags [then tsimp]
+	uint8_t *simp, *capf; // f8b, f8c: [T+1] simplifying / capping vertex; k_hi_simp, k_capping -> k_bracket_place [capf: then dflag]
+	uint32_t *br_list;    // vals_t: the bridge vertices, listed; k_hi_simp -> k_capping [then the class sort's values, k_top_bracket]
+	uint32_t *tsimp, *tcap; // psB, psC: simplifying / capping vertices per tile of k_bracket_extra, scanned in place [ntiles + 1], totals in the last word; k_flag_tile_counts -> k_bracket_extra [psC: then lastb]
+	uint32_t *srccnt;     // dlt: brackets per mirror pre-order position, as words; k_globalize / k_tree_emit -> the scan of the range starts [then row E's differences]
+	uint32_t *bstart;     // dlt_ps: first bracket of every position; that scan -> k_top_bracket [all vertices: then the scan of row E's differences]
+	// ---- classes and rows E, F
+	uint32_t *ck, *ck2;   // keys_t, keys_t2: keys of the class sort; k_top_bracket -> the class kernels (and stack_class_ids after a black-only pass)
+	uint8_t *cflag;	      // f8a: "opens a class" per sorted entry; the class kernels -> k_class_scatter / stack_class_ids [before: brec_cnt]
+	uint32_t *cps;	      // psA: its scan [before: brec]
+	uint8_t *dflag;	      // f8c: [S+1] <= [T+1] opens / seen flags of the stack entries; k_class_finish_black / k_dflag -> k_laminar_walk [before: capf]
+	uint32_t *shift_ps;   // topi: black only: scan of row E's differences (dlt_ps still holds the bracket range starts; nobody needs vertex -> stack index there) [all vertices: topi itself, k_stack_emit]
+	uint32_t *mark, *lastb; // flagC, psC: all vertices: run marks (written with the class flags) and their running maximum; k_class_flags -> k_next_from_runs [psC before: tcap]
+	// ---- row G
+	uint8_t *xflag;	      // f8d: [T + 32] >= S entries whose interval is crossed; the memset -> k_resolve_crossings [the branching flags are long compacted]
+	uint32_t *xlist;      // wrun: those entries, listed; compact_flagged_u8 -> k_resolve_crossings [then wrun itself]
+	uint32_t *wb;	      // walk_ps: in place, exclusive -> biased inclusive; k_walk_bias -> k_levels
+	uint32_t *wneg;	      // walk: the steps are dead once k_walk_bias has read them; k_walk_bias -> the max scan
+	uint32_t *wrun;	      // wrun: running minimum (complemented); the max scan -> k_levels
+};
+static ClassViews class_views(const ParWs &pw)
+{
+	ClassViews v;
+	v.brec = reinterpret_cast<uint4 *>(pw.psA);
+	v.brec_cnt = reinterpret_cast<uint32_t *>(pw.f8a);
+	v.pscov = pw.psB;
+	v.simp = pw.f8b, v.capf = pw.f8c;
+	v.br_list = pw.vals_t;
+	v.tsimp = pw.psB, v.tcap = pw.psC;
+	v.srccnt = pw.dlt, v.bstart = pw.dlt_ps;
+	v.ck = pw.keys_t, v.ck2 = pw.keys_t2;
+	v.cflag = pw.f8a, v.cps = pw.psA;
+	v.dflag = pw.f8c;
+	v.shift_ps = pw.topi;
+	v.mark = pw.flagC, v.lastb = pw.psC;
+	v.xflag = pw.f8d;
+	v.xlist = pw.wrun;
+	v.wb = pw.walk_ps, v.wneg = pw.walk, v.wrun = pw.wrun;
+	return v;
+}
+
 // ------------------------------------------------------------- driver
 // Everything the host needs to know about a finished pass, written straight into page-locked host
-// memory: [0..2] error words, then bad[C], status[C], npvst[C], nbry[C], doff[C+1].
+// memory (PassSummary).
 __global__ void k_summary(uint32_t C, const uint32_t *__restrict__ err, const uint32_t *__restrict__ bad,
 			  const uint32_t *__restrict__ status, const uint32_t *__restrict__ npvst,
 			  const uint32_t *__restrict__ nbry, const uint32_t *__restrict__ doff, uint32_t *__restrict__ out)
@@ -1299,20 +1348,20 @@ __global__ void k_summary(uint32_t C, const uint32_t *__restrict__ err, const ui
 	uint32_t i = BIDX * blockDim.x + threadIdx.x;
 	if (i > C)
 		return;
+	const PassSummary o(C, out);
 	if (i == 0) {
-		out[0] = err ? err[0] : 0;
-		out[1] = err ? (err[1] | (err[8] << 1)) : 0; // bit 0: list ranking, bit 1: stack pool of the class walk
-		out[2] = err ? err[2] : 0;
-		out[3] = err ? err[3] : 0;
+		o.err(PassSummary::NO_BRACKET) = err ? err[PW_NO_BRACKET] : 0;
+		o.err(PassSummary::WALK_POOL) = err ? err[PW_WALK_POOL] : 0;
+		o.err(PassSummary::FOREST_SIZE) = err ? err[PW_FOREST_SIZE] : 0;
+		o.err(PassSummary::SPARE) = 0;
 	}
-	uint32_t *o = out + 4;
 	if (i < C) {
-		o[i] = bad ? bad[i] : 0;
-		o[(size_t)C + i] = status[i];
-		o[2 * (size_t)C + i] = npvst[i];
-		o[3 * (size_t)C + i] = nbry[i];
+		o.bad(i) = bad ? bad[i] : 0;
+		o.status(i) = status[i];
+		o.npvst(i) = npvst[i];
+		o.nbry(i) = nbry[i];
 	}
-	o[4 * (size_t)C + i] = doff ? doff[i] : 0;
+	o.doff(i) = doff ? doff[i] : 0;
 }
 
 void pass_summary(const SeqWs &sw, const ParWs *pw, uint32_t C, uint32_t *host_out, hipStream_t s)
@@ -1323,124 +1372,169 @@ void pass_summary(const SeqWs &sw, const ParWs *pw, uint32_t C, uint32_t *host_o
 	       sw.c_nbry, pw ? pw->doff : nullptr, dev_out);
 }
 
-void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint32_t n_processed, uint32_t n_stack,
-		     int64_t dense_nb0, const std::function<void *(size_t)> &alloc_result_block, StageTimer &tm, hipStream_t s,
-		     const SideStream &side, PassTail &tail)
-{
-	const uint32_t V = sw.V, T = 2 * V + C;
-	const bool want_hp = sw.hairpins != nullptr;
-	pw.V = V;
-	pw.E = sw.E;
-	pw.C = C;
-	pw.T = T;
-	auto scan = [&](const uint32_t *in, uint32_t *out, size_t n) {
-		scan_exclusive_u32(in, out, n, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	};
-	auto scan8 = [&](const uint8_t *in, uint32_t *out, size_t n) {
-		scan_exclusive_u8(in, out, n, nullptr, nullptr, 0, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	};
-	auto scan2 = [&](const uint32_t *in0, uint32_t *out0, size_t n0, const uint32_t *in1, uint32_t *out1, size_t n1) {
-		scan_exclusive_u32_pair(in0, out0, n0, in1, out1, n1, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	};
-
-	// ---- T-space + dense back edges
-	tm.begin("par_setup");
+// One pass of rows D-G: what run_parallel_dg's steps share.  The steps run in the order they stand in, each between the
+// stage timer's marks it names; the routes are decided once, at the top.
+struct ClassPass {
+	const CompState &cs;
+	SeqWs &sw;
+	ParWs &pw;
+	StageTimer &tm;
+	hipStream_t s;
+	const SideStream &side;
+	PassTail &tail;
+	const std::function<void *(size_t)> &alloc_result_block;
+	const ClassViews v;
+	const uint32_t C, V, T, S, n_processed; // components, segments, tree-vertex slots, candidate-stack entries, processed components
+	const int64_t dense_nb0;
+	// ---- the routes
+	const bool dense;     // the parallel tree stage left the back edges in b_src / b_tgt (else: a sequential tree stage, densified here)
+	const bool want_hp;   // the hairpin report follows
 	// All-parallel pass: the tree stage wrote sizes (0 = no vertex in this slot), parents (only ever tested against NIL), the
 	// mirror pre-order and the cleared bracket counts in T-space itself; the root of a vertex's tree is looked up where it
 	// is needed.  A sequential tree stage works per component: its arrays are brought into that form here, and the
 	// hairpin report wants the per-vertex tables too.
-	const bool lean = dense_nb0 >= 0 && !want_hp;
-	// the bracket counts of the parallel tree stage as bytes (it wrote them in the form the caller chose, see ParWs)
-	const bool narrow_oc = dense_nb0 >= 0 && pw.narrow_ordcnt, narrow_sc = narrow_oc && pw.narrow_srccnt;
-	if (lean) {
+	const bool lean;
+	const bool narrow_oc, narrow_sc; // the bracket counts of the parallel tree stage as bytes (it wrote them in the form the caller chose, see ParWs)
+	bool black_only = false;	 // classes of the black tree edges only (place_brackets decides)
+	const RootOf root_of;
+	// ---- counts: ordinary / capping / simplifying back edges, all brackets, vertices that get a class
+	uint32_t NB0 = 0, ncap = 0, nsimp = 0, NB = 0, NC = 0;
+	const uint32_t ntiles; // tiles of k_bracket_extra
+	// ---- words on their way to the host
+	uint32_t *extra = nullptr; // [4] capping count | simplifying count | literal-rule flag | back edges of the tree stage
+	HostScratch::Token extra_ready = 0;
+	uint32_t *early = nullptr; // pass_summary's words as of the PVST count
+	HostScratch::Token early_ready = 0;
+	bool use_side = false; // the endpoints and the copies go to the side stream
+
+	ClassPass(const CompState &cs_, SeqWs &sw_, ParWs &pw_, uint32_t C_, uint32_t n_processed_, uint32_t n_stack, int64_t dense_nb0_,
+		  const std::function<void *(size_t)> &alloc, StageTimer &tm_, hipStream_t s_, const SideStream &side_, PassTail &tail_)
+		: cs(cs_), sw(sw_), pw(pw_), tm(tm_), s(s_), side(side_), tail(tail_), alloc_result_block(alloc), v(class_views(pw_)), C(C_),
+		  V(sw_.V), T(2 * sw_.V + C_), S(n_stack), n_processed(n_processed_), dense_nb0(dense_nb0_), dense(dense_nb0_ >= 0),
+		  want_hp(sw_.hairpins != nullptr), lean(dense && !want_hp), narrow_oc(dense && pw_.narrow_ordcnt),
+		  narrow_sc(narrow_oc && pw_.narrow_srccnt), root_of{lean ? nullptr : pw_.t_root, cs_.voff, C_},
+		  ntiles((T + BX_TILE - 1) / BX_TILE)
+	{
+	}
+	void scan(const uint32_t *in, uint32_t *out, size_t n) const { scan_exclusive_u32(in, out, n, pw.scan_tmp, pw.scan_tmp_bytes, s); }
+	void scan8(const uint8_t *in, uint32_t *out, size_t n) const
+	{
+		scan_exclusive_u8(in, out, n, nullptr, nullptr, 0, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	}
+	void scan2(const uint32_t *in0, uint32_t *out0, size_t n0, const uint32_t *in1, uint32_t *out1, size_t n1) const
+	{
+		scan_exclusive_u32_pair(in0, out0, n0, in1, out1, n1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	}
+};
+
+// ---- T-space + dense back edges.  Reads the tree stage's arrays in sw (lean: in place); writes gpar / gsize / t_root /
+// hi0 / mpre and the cleared counts when not lean, b_src / b_tgt behind a sequential tree stage.
+static void t_space_setup(ClassPass &P)
+{
+	ParWs &pw = P.pw;
+	const SeqWs &sw = P.sw;
+	const CompState &cs = P.cs;
+	hipStream_t s = P.s;
+	const uint32_t V = P.V, T = P.T, C = P.C;
+	P.tm.begin("par_setup");
+	if (P.lean) {
 		pw.gsize = sw.t_size;
 		pw.gpar = sw.t_par;
 	} else {
 		LAUNCH(k_tcomp_vertices, V, s, V, T, cs.ckey, cs.voff, pw.t_comp);
 		LAUNCH(k_globalize, T, s, T, pw.t_comp, cs.voff, sw.c_ntree, sw.t_par, sw.t_size, pw.gpar, pw.gsize, pw.t_root, pw.hi0,
-		       dense_nb0 >= 0 ? nullptr : pw.cov, sw.t_depth, pw.mpre, pw.incnt, narrow_sc ? nullptr : pw.dlt);
+		       P.dense ? nullptr : pw.cov, sw.t_depth, pw.mpre, pw.incnt, P.narrow_sc ? nullptr : pw.dlt);
 	}
-	const RootOf root_of{lean ? nullptr : pw.t_root, cs.voff, C};
 	// pw.comp_bad and pw.err are zeroed by the caller (zero_component_counters)
-	uint32_t NB0;
-	if (dense_nb0 >= 0) { // the parallel tree stage already left the back edges in b_src / b_tgt
-		NB0 = dense_nb0 == NB0_ON_DEVICE ? 0u : (uint32_t)dense_nb0; // (on the device: read below, nothing before that needs it)
+	if (P.dense) { // the parallel tree stage already left the back edges in b_src / b_tgt
+		P.NB0 = P.dense_nb0 == NB0_ON_DEVICE ? 0u : (uint32_t)P.dense_nb0; // (on the device: read in place_brackets, nothing before that needs it)
 	} else {
-		scan(sw.c_nbe0, pw.dbo, (size_t)C + 1);
-		NB0 = pw.host->read_u32(pw.dbo + C, s);
-		LAUNCH(k_dense_be, NB0, s, NB0, C, pw.dbo, cs.voff, cs.eoff, sw.be_src, sw.be_tgt, pw.b_src, pw.b_tgt);
+		P.scan(sw.c_nbe0, pw.dbo, (size_t)C + 1);
+		P.NB0 = pw.host->read_u32(pw.dbo + C, s);
+		LAUNCH(k_dense_be, P.NB0, s, P.NB0, C, pw.dbo, cs.voff, cs.eoff, sw.be_src, sw.be_tgt, pw.b_src, pw.b_tgt);
 	}
-	tm.end(7);
+	P.tm.end(7);
+}
 
-	// ---- row D
-	tm.begin("par_classes");
-	if (dense_nb0 < 0)
-		LAUNCH(k_hi0, NB0, s, NB0, pw.b_src, pw.b_tgt, pw.hi0, pw.cov, nullptr);
+// ---- row D, first half: bridge flags, simplifying and capping vertices, and their counts on the way to the host.  Reads
+// hi0, the coverage counts (ordcnt8 / lsz and incnt, or cov), gsize, gpar; writes segA, brec, simp, capf, cap_tgt, br_list,
+// tsimp, tcap and the words PW_N_BRIDGE, PW_LITERAL_RULE.
+static void bridge_and_capping(ClassPass &P)
+{
+	ParWs &pw = P.pw;
+	const ClassViews &v = P.v;
+	hipStream_t s = P.s;
+	const uint32_t T = P.T, ntiles = P.ntiles;
+	P.tm.begin("par_classes");
+	if (!P.dense)
+		LAUNCH(k_hi0, P.NB0, s, P.NB0, pw.b_src, pw.b_tgt, pw.hi0, pw.cov, nullptr);
 	seg_build(pw.segA, pw.hi0, T, s);
-	uint8_t *simp = pw.f8b, *capf = pw.f8c; // [T+1] flags, one byte each
-	uint32_t *pssimp = pw.psB, *pscap = pw.psC;
-	// bridge flags: a bit-rank directory (common.hpp) over T + 1 positions in psA's space: (T / 64 + 2) records of 16 bytes
-	// = T / 4 + 32 bytes, the counts its build scans in f8a's ((T / 64 + 2) words)
-	uint4 *brec = reinterpret_cast<uint4 *>(pw.psA);
-	uint32_t *brec_cnt = reinterpret_cast<uint32_t *>(pw.f8a);
-	uint32_t *pscov = pw.psB; // (free until the simplifying flags are scanned)
-	if (narrow_oc) // back edges leaving a vertex (counted by the tree stage) minus those arriving (counted by k_hi0)
-		scan_exclusive_diff_u8_u32(pw.ordcnt8, pw.incnt, pscov, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	else if (dense_nb0 >= 0)
-		scan_exclusive_diff_u32(pw.lsz, pw.incnt, pscov, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	if (P.narrow_oc) // back edges leaving a vertex (counted by the tree stage) minus those arriving (counted by k_hi0)
+		scan_exclusive_diff_u8_u32(pw.ordcnt8, pw.incnt, v.pscov, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	else if (P.dense)
+		scan_exclusive_diff_u32(pw.lsz, pw.incnt, v.pscov, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	else
-		scan(pw.cov, pscov, (size_t)T + 1);
-	KLAUNCH(k_bridge_flags, dim3(nblk(((size_t)T / 256 + 1) * 64)), dim3(TPB), 0, s, T, pw.gsize, pw.gpar, pscov, brec); // (whole waves: every record of [0, T] is written)
-	bitrank_build(brec, (size_t)T / 64 + 1, brec_cnt, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	uint32_t *br_list = pw.vals_t, *n_br = pw.err + 10; // (the sort's value buffer is free until the class pass; the count was cleared with the other counters)
-	KLAUNCH(k_hi_simp, dim3((unsigned)(((size_t)T + HS_VERTS - 1) / HS_VERTS)), dim3(TPB), 0, s, T, pw.gsize, brec, simp, want_hp ? pw.hpf : nullptr, capf, br_list,
+		P.scan(pw.cov, v.pscov, (size_t)T + 1);
+	KLAUNCH(k_bridge_flags, dim3(nblk(((size_t)T / 256 + 1) * 64)), dim3(TPB), 0, s, T, pw.gsize, pw.gpar, v.pscov, v.brec); // (whole waves: every record of [0, T] is written)
+	bitrank_build(v.brec, (size_t)T / 64 + 1, v.brec_cnt, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	uint32_t *n_br = pw.err + PW_N_BRIDGE;
+	KLAUNCH(k_hi_simp, dim3((unsigned)(((size_t)T + HS_VERTS - 1) / HS_VERTS)), dim3(TPB), 0, s, T, pw.gsize, v.brec, v.simp, P.want_hp ? pw.hpf : nullptr, v.capf, v.br_list,
 		n_br);
-	KLAUNCH(k_capping, dim3(std::min<unsigned>(nblk(T / 8 + 1), 16384)), dim3(TPB), 0, s, n_br, br_list, pw.gsize, pw.hi0, brec, root_of,
-		pw.segA, pw.cap_tgt, capf, pw.err + 5);
+	KLAUNCH(k_capping, dim3(std::min<unsigned>(nblk(T / 8 + 1), 16384)), dim3(TPB), 0, s, n_br, v.br_list, pw.gsize, pw.hi0, v.brec, P.root_of,
+		pw.segA, pw.cap_tgt, v.capf, pw.err + PW_LITERAL_RULE);
 	// capping / simplifying vertices per tile of k_bracket_extra, scanned: [ntiles + 1] each, the totals in the last word
-	const uint32_t ntiles = (T + BX_TILE - 1) / BX_TILE;
-	uint32_t *tsimp = pssimp, *tcap = pscap;
-	KLAUNCH(k_flag_tile_counts, dim3((ntiles + 1 + 15) / 16 + 1), dim3(TPB), 0, s, T, capf, simp, tcap, tsimp, ntiles);
-	scan_exclusive_u32_pair(tsimp, tsimp, (size_t)ntiles + 1, tcap, tcap, (size_t)ntiles + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	uint32_t *srccnt = pw.dlt, *bstart = pw.dlt_ps; // free until row E
-	uint32_t *extra = pw.host->take<uint32_t>(4);
-	publish_words(extra, WordSrc{{tcap + ntiles, tsimp + ntiles, pw.err + 5, pw.err + 6}}, 4, s); // counts | literal-rule flag | back edges of the tree stage
+	KLAUNCH(k_flag_tile_counts, dim3((ntiles + 1 + 15) / 16 + 1), dim3(TPB), 0, s, T, v.capf, v.simp, v.tcap, v.tsimp, ntiles);
+	scan_exclusive_u32_pair(v.tsimp, v.tsimp, (size_t)ntiles + 1, v.tcap, v.tcap, (size_t)ntiles + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	P.extra = pw.host->take<uint32_t>(4);
+	publish_words(P.extra, WordSrc{{v.tcap + ntiles, v.tsimp + ntiles, pw.err + PW_LITERAL_RULE, pw.err + PW_NB0}}, 4, s);
 	// The stream is not left idle while the host reads them (HostScratch::mark): the kernel that places the capping and
 	// simplifying brackets takes the counts from the device, and the scan behind it does not need them at all.
-	const HostScratch::Token extra_ready = pw.host->mark(s);
+	P.extra_ready = pw.host->mark(s);
+}
+
+// ---- row D, second half: the capping and simplifying brackets join the ordinary ones (b_src / b_tgt, the two counts),
+// then, with the counts on the host, every bracket goes to its place in the bracket lists (tgtR, segB; b_val2 for the
+// hairpin report).  Decides black_only.
+static void place_brackets(ClassPass &P)
+{
+	ParWs &pw = P.pw;
+	const ClassViews &v = P.v;
+	hipStream_t s = P.s;
+	const uint32_t T = P.T;
 	auto bracket_extra = [&](auto *ordcnt, auto *sc) {
 		using OC = std::remove_const_t<std::remove_pointer_t<decltype(ordcnt)>>;
 		using SC = std::remove_pointer_t<decltype(sc)>;
-		LAUNCH((k_bracket_extra<OC, SC>), ((size_t)T + 3) / 4, s, T, NB0, dense_nb0 == NB0_ON_DEVICE ? pw.err + 6 : nullptr, ntiles,
-		       (uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu), capf, tcap, simp, tsimp, pw.cap_tgt, root_of, pw.b_src, pw.b_tgt,
+		LAUNCH((k_bracket_extra<OC, SC>), ((size_t)T + 3) / 4, s, T, P.NB0, P.dense_nb0 == NB0_ON_DEVICE ? pw.err + PW_NB0 : nullptr, P.ntiles,
+		       (uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu), v.capf, v.tcap, v.simp, v.tsimp, pw.cap_tgt, P.root_of, pw.b_src, pw.b_tgt,
 		       ordcnt, pw.gsize, pw.mpre, pw.incnt, sc);
 	};
-	if (narrow_sc)
+	if (P.narrow_sc)
 		bracket_extra((const uint8_t *)pw.ordcnt8, pw.srccnt8);
-	else if (narrow_oc)
-		bracket_extra((const uint8_t *)pw.ordcnt8, srccnt);
+	else if (P.narrow_oc)
+		bracket_extra((const uint8_t *)pw.ordcnt8, v.srccnt);
 	else
-		bracket_extra(dense_nb0 >= 0 ? (const uint32_t *)pw.lsz : nullptr, srccnt);
+		bracket_extra(P.dense ? (const uint32_t *)pw.lsz : nullptr, v.srccnt);
 	// ranks inside every source and the counts per source are known: place directly
-	if (narrow_sc)
-		scan_exclusive_u32_u8_pair(pw.incnt, pw.psin, (size_t)T + 1, pw.srccnt8, bstart, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	else if (dense_nb0 >= 0)
-		scan2(pw.incnt, pw.psin, (size_t)T + 1, srccnt, bstart, (size_t)T + 1);
-	pw.host->wait(extra_ready);
-	if (dense_nb0 == NB0_ON_DEVICE) {
-		NB0 = extra[3];
-		if (NB0 > pw.nb_cap)
+	if (P.narrow_sc)
+		scan_exclusive_u32_u8_pair(pw.incnt, pw.psin, (size_t)T + 1, pw.srccnt8, v.bstart, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	else if (P.dense)
+		P.scan2(pw.incnt, pw.psin, (size_t)T + 1, v.srccnt, v.bstart, (size_t)T + 1);
+	pw.host->wait(P.extra_ready);
+	if (P.dense_nb0 == NB0_ON_DEVICE) {
+		P.NB0 = P.extra[3];
+		if (P.NB0 > pw.nb_cap)
 			throw HipError("spanning tree: more back edges than links outside the tree and sides without links (internal sizing bug)");
 	}
-	const uint32_t ncap = extra[0], nsimp = extra[1], NB = NB0 + ncap + nsimp;
+	const uint32_t NB0 = P.NB0, ncap = P.extra[0], nsimp = P.extra[1], NB = NB0 + ncap + nsimp;
+	P.ncap = pw.ncap = ncap;
+	P.nsimp = pw.nsimp = nsimp;
+	P.NB = NB;
 	pw.nb0 = NB0;
-	pw.ncap = ncap;
-	pw.nsimp = nsimp;
 	if ((size_t)NB > pw.nb_cap) // (the bracket arrays are carved for that many entries, see for_each_span)
 		throw HipError("class stage: more brackets than the workspace was sized for (internal sizing bug)");
-	if (dense_nb0 < 0 && !pw.b_key)
+	if (!P.dense && !pw.b_key)
 		throw HipError("class stage: the bracket sort's buffers were not carved for a sequential tree stage (internal)");
-	if (!lean && !pw.t_comp)
+	if (!P.lean && !pw.t_comp)
 		throw HipError("class stage: the per-vertex tables were not carved (internal)");
 	// Classes of the black tree edges only (the candidate stack holds no others: half the vertices to look up, sort and
 	// number).  Per top bracket the reference walks ALL vertices that have it on top, deepest first, and opens a class
@@ -1450,92 +1544,109 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	// under it has ended).  The literal hi_2 rule (flubbles.cpp:566-574) can cap too low; k_capping reports when it
 	// picked another target than the second-highest reach, and hairpin reports want the top bracket of every vertex:
 	// both take the all-vertices pass.
-	const bool black_only = !want_hp && !pw.all_vertex_classes && extra[2] == 0;
-	pw.black_only_used = black_only;
-	if (dense_nb0 >= 0) {
-		LAUNCH(k_bracket_place, NB, s, NB, NB0, ncap, pw.b_src, pw.b_tgt, pw.b_ord, pw.mpre, bstart, capf, simp, pw.tgtR,
-		       want_hp ? pw.b_val2 : nullptr);
+	P.black_only = !P.want_hp && !pw.all_vertex_classes && P.extra[2] == 0;
+	pw.black_only_used = P.black_only;
+	if (P.dense) {
+		LAUNCH(k_bracket_place, NB, s, NB, NB0, ncap, pw.b_src, pw.b_tgt, pw.b_ord, pw.mpre, v.bstart, v.capf, v.simp, pw.tgtR,
+		       P.want_hp ? pw.b_val2 : nullptr);
 	} else {
 		uint32_t *bk = pw.b_key, *bk2 = pw.b_key2;
-		LAUNCH(k_bracket_order, NB, s, NB, NB0, ncap, nsimp, pw.b_src, pw.b_tgt, pw.mpre, bk, pw.b_val, pw.incnt, srccnt);
-		scan2(pw.incnt, pw.psin, (size_t)T + 1, srccnt, bstart, (size_t)T + 1);
+		LAUNCH(k_bracket_order, NB, s, NB, NB0, ncap, nsimp, pw.b_src, pw.b_tgt, pw.mpre, bk, pw.b_val, pw.incnt, v.srccnt);
+		P.scan2(pw.incnt, pw.psin, (size_t)T + 1, v.srccnt, v.bstart, (size_t)T + 1);
 		sort_pairs_u32(bk, bk2, pw.b_val, pw.b_val2, NB, bits_for(T), pw.sort_tmp, pw.sort_tmp_bytes, s);
 		LAUNCH(k_gather_u32, NB, s, NB, pw.b_val2, pw.b_tgt, pw.tgtR);
 	}
 	seg_build(pw.segB, pw.tgtR, NB, s);
-	uint32_t *ck = pw.keys_t, *ck2 = pw.keys_t2;
-	const uint32_t NC = black_only ? V : T; // vertices that get a class
-	const uint32_t S = n_stack;
-	uint8_t *cflag = pw.f8a; // bridge flags are dead by now
-	uint32_t *cps = pw.psA;
-	uint8_t *dflag = pw.f8c; // [S+1] <= [T+1]; capping flags are dead by now
-	if (black_only) {
-		// row E first (it only needs the tree): the stack index of every black vertex, so that the class pass can work
-		// in stack order from the start -- the sort carries stack indices, and classes, next_seen and prev are written
-		// where rows F/G read them
-		uint32_t *sdl = pw.dlt;
-		if (pw.sdl_filled && dense_nb0 >= 0) {
-			sdl = pw.sdl; // the tree stage's emit kernel had both sizes of every segment in hand and left the differences there
-		} else {
-			HIP_CHECK(hipMemsetAsync(pw.dlt, 0, ((size_t)V + 2) * 4, s)); // (the bracket counts that lived here are dead)
-			LAUNCH(k_shift_delta, V, s, V, cs.ckey, sw.c_ntree, pw.gsize, pw.dlt);
-		}
-		uint32_t *shift_ps = pw.topi; // (dlt_ps still holds the bracket range starts; nobody needs vertex -> stack index here)
-		scan(sdl, shift_ps, (size_t)V + 1);
-		const StackPlace sp{cs.voff, pw.soff, sdl, shift_ps, pw.s_vtx};
-		LAUNCH(k_top_bracket<true>, NC, s, NC, pw.gsize, pw.gpar, pw.mpre, bstart, pw.segB, pw.tgtR, pw.psin, ck,
-		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, NB0 + ncap, nullptr, cs.ckey, sw.c_ntree, sp);
-		sort_pairs_u32(ck, ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
-		// invalid entries carry NIL; after the sort on the low bits they sit behind every valid key
-		tm.end(30 + 2 * 22);
-		tm.begin("par_stack");
-		// (the class flags are worked out by the same kernel: invalid entries carry NIL and sort behind every valid key)
-		// (black_only: the literal hi_2 rule did not fire, so the laminarity check -- prev's one reader -- runs only on request)
-		LAUNCH(k_class_finish_black, std::max<size_t>(((size_t)NC + 3) / 4, 1), s, NC, S, ck2, pw.vals_t2, pw.lsz, cflag, pw.ns, pw.prev,
-		       pw.check_laminar, dflag);
-		tm.end(1);
-		tm.begin("par_next_seen"); // (folded into the kernel above)
-		tm.end(0);
-		pw.gcls_valid = false;
-		pw.s_cls_valid = false; // (cflag, the sorted keys and their stack indices stay where they are for stack_class_ids)
+	P.NC = P.black_only ? P.V : T;
+}
+
+// ---- classes of the black tree vertices, in stack order, with rows E and F folded in.  Row E goes first (it only needs
+// the tree): the stack index of every black vertex, so that the class pass can work in stack order from the start -- the
+// sort carries stack indices, and classes, next_seen and prev are written where rows F/G read them.  Writes s_vtx, ns,
+// prev (on request), cflag, dflag; the sorted keys and their stack indices stay where they are for stack_class_ids.
+static void classes_black_only(ClassPass &P)
+{
+	ParWs &pw = P.pw;
+	const ClassViews &v = P.v;
+	const CompState &cs = P.cs;
+	hipStream_t s = P.s;
+	const uint32_t V = P.V, NC = P.NC;
+	uint32_t *sdl = pw.dlt;
+	if (pw.sdl_filled && P.dense) {
+		sdl = pw.sdl; // the tree stage's emit kernel had both sizes of every segment in hand and left the differences there
 	} else {
-		const StackPlace none{nullptr, nullptr, nullptr, nullptr, nullptr};
-		LAUNCH(k_top_bracket<false>, NC, s, NC, pw.gsize, pw.gpar, pw.mpre, bstart, pw.segB, pw.tgtR, pw.psin, ck,
-		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, NB0 + ncap, want_hp ? pw.hpf : nullptr, nullptr, nullptr, none);
-		sort_pairs_u32(ck, ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
-		LAUNCH(k_class_flags<false>, std::max<size_t>(NC, (size_t)V + 2), s, NC, V, ck2, pw.vals_t2, pw.lsz, sw.t_flags, cflag, pw.dlt,
-		       pw.flagC);
-		scan8(cflag, cps, (size_t)NC + 1);
-		LAUNCH(k_class_scatter, NC, s, NC, ck2, pw.vals_t2, cflag, cps, pw.gcls);
-		pw.gcls_valid = true;
-		pw.s_cls_valid = true;
-		tm.end(30 + 2 * 22);
-
-		// ---- row E
-		tm.begin("par_stack");
-		LAUNCH(k_shift_delta, V, s, V, cs.ckey, sw.c_ntree, pw.gsize, pw.dlt);
-		scan(pw.dlt, pw.dlt_ps, (size_t)V + 1);
-		// one candidate-stack entry per black tree edge = per segment of a processed component: the host knows where
-		// every component's entries start (pw.soff) and the total
-		LAUNCH(k_stack_emit, V, s, V, cs.ckey, sw.c_ntree, cs.voff, pw.soff, pw.dlt, pw.dlt_ps, pw.gsize, pw.gcls, pw.s_vtx, pw.s_cls,
-		       pw.topi, pw.ns, pw.prev);
-		tm.end(9);
-
-		// ---- row F
-		tm.begin("par_next_seen");
-		uint32_t *mark = pw.flagC, *lastb = pw.psC; // (the marks were written with the class flags)
-		scan_exclusive_max_u32(mark, lastb, T, pw.scan_tmp, pw.scan_tmp_bytes, s);
-		LAUNCH(k_next_from_runs, T, s, T, mark, lastb, pw.vals_t2, pw.gcls, pw.topi, pw.ns, pw.prev);
-		tm.end(4);
-		LAUNCH(k_dflag, (size_t)S + 1, s, S, pw.ns, pw.prev, dflag);
+		HIP_CHECK(hipMemsetAsync(pw.dlt, 0, ((size_t)V + 2) * 4, s)); // (the bracket counts that lived here are dead)
+		LAUNCH(k_shift_delta, V, s, V, cs.ckey, P.sw.c_ntree, pw.gsize, pw.dlt);
 	}
+	P.scan(sdl, v.shift_ps, (size_t)V + 1);
+	const StackPlace sp{cs.voff, pw.soff, sdl, v.shift_ps, pw.s_vtx};
+	LAUNCH(k_top_bracket<true>, NC, s, NC, pw.gsize, pw.gpar, pw.mpre, v.bstart, pw.segB, pw.tgtR, pw.psin, v.ck,
+	       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, nullptr, cs.ckey, P.sw.c_ntree, sp);
+	sort_pairs_u32(v.ck, v.ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)P.NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
+	// invalid entries carry NIL; after the sort on the low bits they sit behind every valid key
+	P.tm.end(30 + 2 * 22);
+	P.tm.begin("par_stack");
+	// (the class flags are worked out by the same kernel: invalid entries carry NIL and sort behind every valid key)
+	// (black_only: the literal hi_2 rule did not fire, so the laminarity check -- prev's one reader -- runs only on request)
+	LAUNCH(k_class_finish_black, std::max<size_t>(((size_t)NC + 3) / 4, 1), s, NC, P.S, v.ck2, pw.vals_t2, pw.lsz, v.cflag, pw.ns, pw.prev,
+	       pw.check_laminar, v.dflag);
+	P.tm.end(1);
+	P.tm.begin("par_next_seen"); // (folded into the kernel above)
+	P.tm.end(0);
+	pw.gcls_valid = false;
+	pw.s_cls_valid = false;
+}
 
-	// ---- row G
-	tm.begin("par_pvst");
-	// the two directories over the stack positions: flubbles opened in front of an entry, and the entry's component
+// ---- classes of every tree vertex (gcls), then row E (the candidate stack: s_vtx, s_cls, topi) and row F (ns, prev, dflag)
+static void classes_all_vertices(ClassPass &P)
+{
+	ParWs &pw = P.pw;
+	const ClassViews &v = P.v;
+	const CompState &cs = P.cs;
+	const SeqWs &sw = P.sw;
+	hipStream_t s = P.s;
+	const uint32_t V = P.V, T = P.T, NC = P.NC;
+	const StackPlace none{nullptr, nullptr, nullptr, nullptr, nullptr};
+	LAUNCH(k_top_bracket<false>, NC, s, NC, pw.gsize, pw.gpar, pw.mpre, v.bstart, pw.segB, pw.tgtR, pw.psin, v.ck,
+	       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, P.want_hp ? pw.hpf : nullptr, nullptr, nullptr, none);
+	sort_pairs_u32(v.ck, v.ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)P.NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
+	LAUNCH(k_class_flags<false>, std::max<size_t>(NC, (size_t)V + 2), s, NC, V, v.ck2, pw.vals_t2, pw.lsz, sw.t_flags, v.cflag, pw.dlt,
+	       v.mark);
+	P.scan8(v.cflag, v.cps, (size_t)NC + 1);
+	LAUNCH(k_class_scatter, NC, s, NC, v.ck2, pw.vals_t2, v.cflag, v.cps, pw.gcls);
+	pw.gcls_valid = true;
+	pw.s_cls_valid = true;
+	P.tm.end(30 + 2 * 22);
+
+	// ---- row E
+	P.tm.begin("par_stack");
+	LAUNCH(k_shift_delta, V, s, V, cs.ckey, sw.c_ntree, pw.gsize, pw.dlt);
+	P.scan(pw.dlt, pw.dlt_ps, (size_t)V + 1);
+	// one candidate-stack entry per black tree edge = per segment of a processed component: the host knows where
+	// every component's entries start (pw.soff) and the total
+	LAUNCH(k_stack_emit, V, s, V, cs.ckey, sw.c_ntree, cs.voff, pw.soff, pw.dlt, pw.dlt_ps, pw.gsize, pw.gcls, pw.s_vtx, pw.s_cls,
+	       pw.topi, pw.ns, pw.prev);
+	P.tm.end(9);
+
+	// ---- row F
+	P.tm.begin("par_next_seen");
+	scan_exclusive_max_u32(v.mark, v.lastb, T, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	LAUNCH(k_next_from_runs, T, s, T, v.mark, v.lastb, pw.vals_t2, pw.gcls, pw.topi, pw.ns, pw.prev);
+	P.tm.end(4);
+	LAUNCH(k_dflag, (size_t)P.S + 1, s, P.S, pw.ns, pw.prev, v.dflag);
+}
+
+// ---- row G, first part: the two directories over the stack positions (erec: flubbles opened in front of an entry; crec /
+// clist: the entry's component), the PVST size of every component, and the summary on its way to the host
+static void stack_directories(ClassPass &P)
+{
+	ParWs &pw = P.pw;
+	SeqWs &sw = P.sw;
+	hipStream_t s = P.s;
+	const uint32_t C = P.C, S = P.S;
+	P.tm.begin("par_pvst");
 	const size_t n_rec = (size_t)S / 64 + 1;
-	const StackComp comp_of = pw.stack_comp();
-	KLAUNCH(k_pack_opens, dim3(nblk(((size_t)S / 256 + 1) * 64)), dim3(TPB), 0, s, S, dflag, pw.erec); // (whole waves: every record of [0, S] is written)
+	KLAUNCH(k_pack_opens, dim3(nblk(((size_t)S / 256 + 1) * 64)), dim3(TPB), 0, s, S, P.v.dflag, pw.erec); // (whole waves: every record of [0, S] is written)
 	bitrank_build(pw.erec, n_rec, pw.rk_cnt, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	HIP_CHECK(hipMemsetAsync(pw.crec, 0, n_rec * 16, s));
 	LAUNCH(k_comp_starts, (size_t)C, s, C, pw.soff, pw.crec);
@@ -1544,73 +1655,97 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	// What the host needs to lay out the forest -- PVST size and offset of every component, the error words -- goes back in
 	// ONE read together with the PVST count: after this synchronisation only the PVST arrays themselves are still to come.
 	LAUNCH(k_pvst_counts, (size_t)C + 1, s, C, sw.c_ntree, pw.soff, pw.erec, pw.cproc_ps, pw.doff, sw.c_npvst, sw.c_nstack);
-	uint32_t *early = pw.host->take<uint32_t>(5 * (size_t)C + 8);
-	count_kernel_d2h((5 * (size_t)C + 8) * 4);
-	pass_summary(sw, &pw, C, early, s);
-	const bool use_side = S && side.stream;
-	if (use_side) // (everything the endpoints need is computed: the side stream starts from here)
-		HIP_CHECK(hipEventRecord(side.fork, s));
+	P.early = pw.host->take<uint32_t>(PassSummary::words(C));
+	count_kernel_d2h(PassSummary::words(C) * 4);
+	pass_summary(sw, &pw, C, P.early, s);
+	P.use_side = S && P.side.stream;
+	if (P.use_side) // (everything the endpoints need is computed: the side stream starts from here)
+		HIP_CHECK(hipEventRecord(P.side.fork, s));
 	// The stream is not left idle while the host reads the PVST count (HostScratch::mark): levels and parents of the
 	// flubbles need the stack only, their kernels go out first.
-	const HostScratch::Token early_ready = pw.host->mark(s);
+	P.early_ready = pw.host->mark(s);
+}
+
+// ---- row G, second part: the laminarity check (when the classes may not be exact, or on request), crossings resolved in
+// place, and the level and stack index of every emitted flubble (lev, e_i)
+static void laminar_and_levels(ClassPass &P)
+{
+	ParWs &pw = P.pw;
+	const ClassViews &v = P.v;
+	hipStream_t s = P.s;
+	const uint32_t C = P.C, S = P.S;
+	const StackComp comp_of = pw.stack_comp();
 	// The (prev, i) intervals of exact cycle-equivalence classes never cross ("Row G"): the laminarity
 	// check is only needed when the literal hi_2 rule capped differently from the second-highest reach (extra[2]), i.e. when
 	// the classes may not be the exact ones -- or when a caller asks for it.  Without it nothing that follows can flag a
 	// component: the summary the host is about to read is the final one.
-	pw.laminar_checked = pw.check_laminar || extra[2] != 0;
-	uint8_t *xflag = pw.f8d; // [T + 32] >= S (the branching flags are long compacted)
+	pw.laminar_checked = pw.check_laminar || P.extra[2] != 0;
 	if (pw.laminar_checked) {
 		seg_build(pw.segP, pw.prev, S, s); // NIL (= +inf) where a class has no earlier occurrence
-		HIP_CHECK(hipMemsetAsync(xflag, 0, (size_t)S + 1, s));
+		HIP_CHECK(hipMemsetAsync(v.xflag, 0, (size_t)S + 1, s));
 	}
-	LAUNCH(k_laminar_walk, ((size_t)S + 3) / 4, s, S, pw.prev, pw.segP, pw.laminar_checked, comp_of, pw.soff, xflag, dflag, pw.walk);
+	LAUNCH(k_laminar_walk, ((size_t)S + 3) / 4, s, S, pw.prev, pw.segP, pw.laminar_checked, comp_of, pw.soff, v.xflag, v.dflag, pw.walk);
 	if (pw.laminar_checked && S) { // the entries whose interval is crossed: decided in stack order, U undone where the class was popped
-		uint32_t *xlist = pw.wrun, *n_x = pw.err + 11, *n_crossed = pw.err + 12; // (wrun is written by the max-scan below; err words cleared at the start of the pass)
-		compact_flagged_u8(xflag, S, xlist, n_x, pw.scan_tmp, pw.scan_tmp_bytes, s);
-		KLAUNCH(k_resolve_crossings, dim3(std::min<unsigned>(nblk(C), 1024)), dim3(TPB), 0, s, C, pw.soff, n_x, xlist, pw.prev, pw.segP, xflag,
+		uint32_t *n_x = pw.err + PW_N_X, *n_crossed = pw.err + PW_N_CROSSED;
+		compact_flagged_u8(v.xflag, S, v.xlist, n_x, pw.scan_tmp, pw.scan_tmp_bytes, s);
+		KLAUNCH(k_resolve_crossings, dim3(std::min<unsigned>(nblk(C), 1024)), dim3(TPB), 0, s, C, pw.soff, n_x, v.xlist, pw.prev, pw.segP, v.xflag,
 			pw.walk, n_crossed);
 	}
-	scan(pw.walk, pw.walk_ps, (size_t)S);
-	uint32_t *wb = pw.walk_ps; // in place: exclusive -> biased inclusive
-	uint32_t *wneg = pw.walk, *wrun = pw.wrun; // the steps themselves are dead after the bias kernel read them
-	LAUNCH(k_walk_bias, ((size_t)S + 3) / 4, s, S, pw.walk, pw.walk_ps, wb, wneg);
-	scan_exclusive_max_u32(wneg, wrun, (size_t)S, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	LAUNCH(k_levels, ((size_t)S + 3) / 4, s, S, pw.erec, comp_of, pw.soff, wb, wrun, pw.lev, pw.e_i);
-	pw.host->wait(early_ready);
-	const size_t total = early[4 + 4 * (size_t)C + C]; // doff[C] = flubbles + one root per processed component
-	if (total < n_processed || total - n_processed > S)
+	P.scan(pw.walk, pw.walk_ps, (size_t)S);
+	LAUNCH(k_walk_bias, ((size_t)S + 3) / 4, s, S, pw.walk, pw.walk_ps, v.wb, v.wneg);
+	scan_exclusive_max_u32(v.wneg, v.wrun, (size_t)S, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	LAUNCH(k_levels, ((size_t)S + 3) / 4, s, S, pw.erec, comp_of, pw.soff, v.wb, v.wrun, pw.lev, pw.e_i);
+}
+
+// ---- row G, last part: with the PVST count on the host, the result block, the emit kernels and the copies.  Small
+// results are written by the emit kernels straight into the forest's page-locked host block (no copy, no extra launch).
+// Large ones go through a device block of the same layout (forest_wire::PvstArrays): the scattered 4- and 1-byte stores
+// of the emit kernels make poor PCIe packets (~25 GB/s measured), the copy engine moves the finished arrays at link
+// speed -- all copies on the side stream: endpoints and orientations while this one still works out levels and parents,
+// the parents behind them.
+static void emit_and_copy(ClassPass &P)
+{
+	using Pvst = forest_wire::PvstArrays;
+	ParWs &pw = P.pw;
+	const SeqWs &sw = P.sw;
+	const SideStream &side = P.side;
+	PassTail &tail = P.tail;
+	hipStream_t s = P.s;
+	const uint32_t C = P.C, S = P.S;
+	const bool use_side = P.use_side;
+	const StackComp comp_of = pw.stack_comp();
+	pw.host->wait(P.early_ready);
+	const size_t total = PassSummary(C, P.early).total(); // flubbles + one root per processed component
+	if (total < P.n_processed || total - P.n_processed > S)
 		throw HipError("internal error: PVST size out of range");
-	const uint32_t NE = (uint32_t)(total - n_processed);
+	const uint32_t NE = (uint32_t)(total - P.n_processed);
 	pw.n_emitted = NE;
-	tail.early_summary = early;
+	tail.early_summary = P.early;
 	tail.summary_final = true; // (nothing after the count flags a component any more: crossings are resolved in place)
 	tail.overlapped = tail.want_overlap && tail.summary_final;
-	// The five PVST arrays back to back (povu_hip_forest::alloc has the same layout).  Small results are written by the
-	// emit kernels straight into the forest's page-locked host block (no copy, no extra launch).  Large ones go
-	// through a device block of the same layout: the scattered 4- and 1-byte stores of the emit kernels make poor PCIe
-	// packets (~25 GB/s measured), the copy engine moves the finished arrays at link speed -- all copies on the side
-	// stream: endpoints and orientations while this one still works out levels and parents, the parents behind them.
-	const size_t p4 = (total * 4 + 63) & ~size_t(63), p1 = (total + 63) & ~size_t(63);
-	char *host_blk = static_cast<char *>(alloc_result_block(total));
+	Pvst host, dev; // the forest's block (its device view), and where the emit kernels write
+	Pvst::layout(P.alloc_result_block(total), total, &host);
 	const bool staged = total >= PVST_STAGE_MIN && side.stream != nullptr;
 	if (!staged)
 		count_kernel_d2h(total * 14); // (the emit kernels write the five arrays straight into the page-locked block)
-	char *blk = staged ? reinterpret_cast<char *>(pw.stage) : host_blk;
-	pw.d_a = reinterpret_cast<uint32_t *>(blk);
-	pw.d_z = reinterpret_cast<uint32_t *>(blk + p4);
-	pw.d_parent = reinterpret_cast<uint32_t *>(blk + 2 * p4);
-	pw.d_aor = reinterpret_cast<uint8_t *>(blk + 3 * p4);
-	pw.d_zor = reinterpret_cast<uint8_t *>(blk + 3 * p4 + p1);
+	if (staged)
+		Pvst::layout(pw.stage, total, &dev);
+	else
+		dev = host;
+	pw.d_a = dev.a, pw.d_z = dev.z, pw.d_parent = dev.parent, pw.d_aor = dev.aor, pw.d_zor = dev.zor;
 	pw.d_total = total;
+	auto copy_parents = [&](hipStream_t on) {
+		HIP_CHECK(copy_async(host.parent, dev.parent, Pvst::word_bytes(total), hipMemcpyDeviceToHost, on));
+	};
 	if (use_side) {
 		// (the roots' slots with the endpoints: the copies behind them take whole arrays)
 		HIP_CHECK(hipStreamWaitEvent(side.stream, side.fork, 0));
 		KLAUNCH(k_pvst_roots, dim3(nblk((size_t)C)), dim3(TPB), 0, side.stream, C, sw.c_ntree, pw.doff, pw.d_parent, pw.d_a, pw.d_z, pw.d_aor, pw.d_zor);
 		KLAUNCH(k_emit_endpoints, dim3(staged ? nblk((S + 3) / 4) : std::min<unsigned>(nblk((S + 3) / 4), 160)), dim3(TPB), 0, side.stream, S, pw.erec,
 			comp_of, pw.ns, pw.s_vtx, sw.t_flags, sw.t_gid, pw.cproc_ps, pw.d_a, pw.d_z, pw.d_aor, pw.d_zor);
-		if (staged) {
-			HIP_CHECK(copy_async(host_blk, blk, 2 * p4, hipMemcpyDeviceToHost, side.stream));
-			HIP_CHECK(copy_async(host_blk + 3 * p4, blk + 3 * p4, 2 * p1, hipMemcpyDeviceToHost, side.stream));
+		if (staged) { // the arrays a..z, then the two orientation arrays
+			HIP_CHECK(copy_async(host.a, dev.a, 2 * Pvst::word_bytes(total), hipMemcpyDeviceToHost, side.stream));
+			HIP_CHECK(copy_async(host.aor, dev.aor, 2 * Pvst::flag_bytes(total), hipMemcpyDeviceToHost, side.stream));
 		}
 	} else {
 		LAUNCH(k_pvst_roots, (size_t)C, s, C, sw.c_ntree, pw.doff, pw.d_parent, pw.d_a, pw.d_z, pw.d_aor, pw.d_zor);
@@ -1628,7 +1763,7 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 		if (staged) {
 			HIP_CHECK(hipEventRecord(side.fork2, s));
 			HIP_CHECK(hipStreamWaitEvent(side.stream, side.fork2, 0));
-			HIP_CHECK(copy_async(host_blk + 2 * p4, blk + 2 * p4, p4, hipMemcpyDeviceToHost, side.stream));
+			copy_parents(side.stream);
 		}
 		HIP_CHECK(hipEventRecord(side.join, side.stream));
 		if (!tail.overlapped)
@@ -1637,7 +1772,7 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 			last = side.stream; // (the side stream's last work waited for the main stream's last kernel when the result is staged;
 					    //  when it is not, `done` below is recorded on both -- see the caller)
 	} else if (staged) {
-		HIP_CHECK(copy_async(host_blk + 2 * p4, blk + 2 * p4, p4, hipMemcpyDeviceToHost, s));
+		copy_parents(s);
 	}
 	if (tail.done) {
 		if (tail.overlapped && !staged && use_side) { // both streams carry kernels that write the host block: join them on the side
@@ -1649,7 +1784,28 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 			HIP_CHECK(hipEventRecord(tail.done2, last));
 	}
 	pw.n_stack = S; // export_parallel_stack copies the stack into the per-component layout when a debug hook asks
-	tm.end(12 + 3 * 22);
+	P.tm.end(12 + 3 * 22);
+}
+
+void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint32_t n_processed, uint32_t n_stack,
+		     int64_t dense_nb0, const std::function<void *(size_t)> &alloc_result_block, StageTimer &tm, hipStream_t s,
+		     const SideStream &side, PassTail &tail)
+{
+	ClassPass P(cs, sw, pw, C, n_processed, n_stack, dense_nb0, alloc_result_block, tm, s, side, tail);
+	pw.V = P.V;
+	pw.E = sw.E;
+	pw.C = C;
+	pw.T = P.T;
+	t_space_setup(P);
+	bridge_and_capping(P);
+	place_brackets(P);
+	if (P.black_only)
+		classes_black_only(P);
+	else
+		classes_all_vertices(P);
+	stack_directories(P);
+	laminar_and_levels(P);
+	emit_and_copy(P);
 }
 
 // class ids of the stack entries after a black-only pass (debug hooks): the runs of the sorted order, numbered
@@ -1658,8 +1814,9 @@ static void stack_class_ids(ParWs &pw, hipStream_t s)
 	if (pw.s_cls_valid)
 		return;
 	const uint32_t V = pw.V;
-	scan_exclusive_u8(pw.f8a, pw.psA, (size_t)V + 1, nullptr, nullptr, 0, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	LAUNCH(k_class_ids_black, V, s, V, pw.keys_t2, pw.vals_t2, pw.f8a, pw.psA, pw.s_cls);
+	const ClassViews v = class_views(pw);
+	scan_exclusive_u8(v.cflag, v.cps, (size_t)V + 1, nullptr, nullptr, 0, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	LAUNCH(k_class_ids_black, V, s, V, v.ck2, pw.vals_t2, v.cflag, v.cps, pw.s_cls);
 	pw.s_cls_valid = true;
 }
 void classes_to_tree_space(ParWs &pw, hipStream_t s)

@@ -28,6 +28,43 @@ struct SegTree {
 	static size_t tree_words(size_t n) { return 2 * (size_t)pow2((n + BLK - 1) / BLK + 1); }
 };
 
+// The words of ParWs::err: the counters and internal error flags of one pass, cleared together ahead of the tree stage
+// (zero_component_counters).  Each line: who writes the word -> who reads it.  The numbers are part of no interface, but the
+// two crossing words stay adjacent (povu_hip_last_crossings copies them as a pair).
+enum PassWord : uint32_t {
+	PW_NO_BRACKET = 0,   // k_top_bracket: a tree vertex has no live bracket -> k_summary
+	PW_FOREST_SIZE = 2,  // k_t0_parents: the spanning forest of the links has the wrong size -> k_summary
+	PW_N_OVER = 4,	     // k_class_dfs_small: classes handed to the wave walk -> the host (class_walks)
+	PW_LITERAL_RULE = 5, // k_capping: the literal hi_2 rule capped below the second-highest reach -> the host (place_brackets)
+	PW_NB0 = 6,	     // k_back_edges: back edges of the tree stage -> k_bracket_extra, the host (place_brackets)
+	PW_POOL_TOP = 7,     // k_class_walk_wave: entries taken from the walks' stack pool (no other reader)
+	PW_WALK_POOL = 8,    // k_class_walk_wave: the stack pool ran out -> the host (class_walks), k_summary
+	PW_N_ENTRY = 9,	     // k_entry_list: entries of the 2-edge-connected classes -> k_class_dfs_small, the host (F_BIG_CLASS_DFS)
+	PW_N_BRIDGE = 10,    // k_hi_simp: bridge vertices listed -> k_capping
+	PW_N_X = 11,	     // compact_flagged_u8: stack entries with a crossed interval -> k_resolve_crossings, povu_hip_last_crossings
+	PW_N_CROSSED = 12,   // k_resolve_crossings: crossings resolved in place -> povu_hip_last_crossings
+	PW_RANK_OVF = 13,    // list_rank_splitters (the pre-order ranking): records whose partial sum left its 16 bits (its fallback kernel)
+	PASS_WORDS = 16	     // words carved and cleared (1, 3, 14, 15: unused)
+};
+
+// The outcome of a pass as k_summary writes it into page-locked host memory, one view for the kernel and every reader:
+// ERR_WORDS error words, then bad[C], status[C], npvst[C], nbry[C], doff[C+1].
+struct PassSummary {
+	enum Err : uint32_t { NO_BRACKET = 0, WALK_POOL = 1, FOREST_SIZE = 2, SPARE = 3, ERR_WORDS = 4 }; // (SPARE: always 0, keeps bad[] 16-byte aligned)
+	uint32_t C;
+	uint32_t *w;
+	__host__ __device__ PassSummary(uint32_t C_, const uint32_t *w_) : C(C_), w(const_cast<uint32_t *>(w_)) {}
+	__host__ __device__ static size_t words(uint32_t C) { return ERR_WORDS + 5 * (size_t)C + 1 + 3; } // (three words of slack)
+	__host__ __device__ uint32_t &err(uint32_t k) const { return w[k]; }
+	__host__ __device__ uint32_t &bad(uint32_t c) const { return w[ERR_WORDS + c]; } // the component must be redone sequentially
+	__host__ __device__ uint32_t &status(uint32_t c) const { return w[ERR_WORDS + (size_t)C + c]; }
+	__host__ __device__ uint32_t &npvst(uint32_t c) const { return w[ERR_WORDS + 2 * (size_t)C + c]; }
+	__host__ __device__ uint32_t &nbry(uint32_t c) const { return w[ERR_WORDS + 3 * (size_t)C + c]; }
+	__host__ __device__ uint32_t &doff(uint32_t c) const { return w[ERR_WORDS + 4 * (size_t)C + c]; } // c <= C: first dense PVST slot
+	__host__ __device__ uint32_t total() const { return doff(C); } // PVST vertices of all processed components
+};
+
+// (arrays that a pass also uses under another type or meaning: see ClassViews in par_kernels.hip, the one place that names them)
 struct ParWs {
 	HostScratch *host; // pinned read-back scratch of the owning context
 	uint32_t V, E, C, T;
@@ -81,7 +118,7 @@ struct ParWs {
 	uint32_t *d_a, *d_z, *d_parent;	 // [d_total] device views into the forest's page-locked result block
 	uint8_t *d_aor, *d_zor;		 // [d_total] 0 forward, 1 reverse
 	void *stage;			 // device block with the layout of the result block (large results are copied out by the DMA engine)
-	uint32_t *err;			 // [4] internal error words
+	uint32_t *err;			 // [PASS_WORDS] counters and internal error words of the pass (PassWord)
 	SegTree segA, segB, segP, segL;
 	// --hairpins on the parallel path
 	uint8_t *hpf;			 // [T] bit0 simplifying vertex, bit1 top bracket is a simplifying edge
@@ -109,7 +146,7 @@ struct PassTail {
 	bool want_overlap = false;		 // in
 	hipEvent_t done = nullptr;		 // in: recorded when all work of the pass (kernels and copies) is complete
 	hipEvent_t done2 = nullptr;		 // in: a second event recorded at the same point (the context's own)
-	const uint32_t *early_summary = nullptr; // out: pass_summary's words in page-locked host memory, as of the PVST count
+	const uint32_t *early_summary = nullptr; // out: pass_summary's words (PassSummary) in page-locked host memory, as of the PVST count
 	bool summary_final = false;		 // out: nothing after the count changes them (no laminarity check ran)
 	bool overlapped = false;		 // out: the main stream was left free (want_overlap and summary_final)
 };
@@ -130,7 +167,7 @@ void par_carve(Arena &ar, ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 // Runs rows D-G for every processed component from the spanning trees / back edges the tree stage
 // left in `sw`.  Components whose candidate stack is not laminar are flagged in pw.comp_bad (see pass_summary).
 // dense_nb0 < 0: densify the back edges the sequential tree stage wrote; otherwise b_src/b_tgt hold them -- NB0_ON_DEVICE:
-// their number still sits in pw.err[6] (the parallel tree stage does not wait for it: the class stage reads it with the
+// their number still sits in pw.err[PW_NB0] (the parallel tree stage does not wait for it: the class stage reads it with the
 // capping / simplifying counts, one host synchronisation instead of two).
 // alloc_result_block(total) returns the device view of a page-locked host block laid out a | z | parent | a_or |
 // z_or (each padded to 64 B) for `total` PVST vertices; the emit kernels write into it.
@@ -149,9 +186,8 @@ void run_parallel_hairpins(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C
 void classes_to_tree_space(ParWs &pw, hipStream_t s);
 void export_parallel_stack(const CompState &cs, SeqWs &sw, ParWs &pw, hipStream_t s);
 
-// One launch that writes the outcome of a pass into page-locked host memory (5*C + 8 words):
-// [0..3] error words of the parallel stages, then bad[C], status[C], npvst[C], nbry[C], doff[C+1].
-// pw == nullptr (sequential-only pass): error words, bad and doff read as 0.  The caller synchronises.
+// One launch that writes the outcome of a pass into page-locked host memory (PassSummary::words(C) words, read through
+// PassSummary).  pw == nullptr (sequential-only pass): error words, bad and doff read as 0.  The caller synchronises.
 void pass_summary(const SeqWs &sw, const ParWs *pw, uint32_t C, uint32_t *host_out, hipStream_t s);
 
 } // namespace povu_hip

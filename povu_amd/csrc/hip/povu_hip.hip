@@ -781,7 +781,7 @@ static bool carve_stages(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, u
 
 // What the component tables tell the stages.
 struct CompTables {
-	uint32_t event_lists = 0, n_stack = 0, n_processed = 0;
+	uint32_t n_stack = 0, n_processed = 0;
 };
 
 // ---- component tables: launch order, owner (LPT over vertices + links, the same on every rank), processed components
@@ -814,7 +814,6 @@ static CompTables component_tables(povu_hip_ctx *ctx, const PassPlan &p, uint32_
 		const uint32_t nv = voff[c + 1] - voff[c];
 		cproc[c] = (nv >= 3 && (p.world == 1 || owner[c] == p.rank)) ? 1u : 0u;
 		pc[c + 1] = pc[c] + cproc[c];
-		t.event_lists += cproc[c] ? 1u : 2 * nv; // (the event lists of the pre-order ranking)
 		stack_off[c] = t.n_stack;
 		t.n_stack += cproc[c] ? nv : 0u; // one candidate-stack entry per segment (its black tree edge)
 	}
@@ -869,8 +868,8 @@ struct RowsOut {
 // pass_summary's words, read with the stream drained; f's ev1 goes behind them (recorded again if more work follows)
 static const uint32_t *read_summary(povu_hip_ctx *ctx, uint32_t C, bool with_par, const povu_hip_forest &f)
 {
-	uint32_t *h = ctx->host.take<uint32_t>(5 * (size_t)C + 8);
-	count_kernel_d2h((5 * (size_t)C + 8) * 4);
+	uint32_t *h = ctx->host.take<uint32_t>(PassSummary::words(C));
+	count_kernel_d2h(PassSummary::words(C) * 4);
 	pass_summary(ctx->sw, with_par ? &ctx->pw : nullptr, C, h, ctx->stream);
 	HIP_CHECK(hipEventRecord(f.ev1, ctx->stream));
 	HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -906,7 +905,7 @@ static int64_t parallel_rows(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, c
 		const bool fits = std::max<uint32_t>(gstats[0], 1u) + 2u <= 255u;
 		pw.narrow_ordcnt = fits && wide != 1;
 		pw.narrow_srccnt = pw.narrow_ordcnt && wide != 2;
-		dense_nb0 = run_parallel_tree(ctx->cs, sw, pw, ctx->tw, C, t.event_lists, gstats[0], p.big_class_dfs, p.sparse_splitters, tm, s);
+		dense_nb0 = run_parallel_tree(ctx->cs, sw, pw, ctx->tw, C, gstats[0], p.big_class_dfs, p.sparse_splitters, tm, s);
 	}
 	pw.all_vertex_classes = p.all_vertex_classes;
 	pw.check_laminar = p.check_laminar;
@@ -929,19 +928,16 @@ static int64_t parallel_rows(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, c
 	// laminarity check, the test modes) or add to the result (labels, boundaries): then the summary is read again when all
 	// of that is done.
 	out.fast_tail = out.tail.summary_final && !p.leaf_sub && !p.hairpins && !p.force_redo && !p.redo_odd;
-	const uint32_t *sum = out.sum = out.fast_tail ? out.tail.early_summary : read_summary(ctx, C, true, f);
-	if (sum[0])
+	out.sum = out.fast_tail ? out.tail.early_summary : read_summary(ctx, C, true, f);
+	const PassSummary sum(C, out.sum);
+	if (sum.err(PassSummary::NO_BRACKET))
 		throw HipError("parallel class stage: a tree vertex has no live bracket (internal invariant broken)");
-	if (sum[1] & 1u)
-		throw HipError("list ranking: splitter capacity exceeded (internal sizing bug)");
-	if (sum[1] & 2u)
+	if (sum.err(PassSummary::WALK_POOL))
 		throw HipError("class walk: stack pool exhausted (internal sizing bug)");
-	if (sum[2])
+	if (sum.err(PassSummary::FOREST_SIZE))
 		throw HipError("spanning forest of the links has the wrong size (internal)");
-	if (sum[3])
-		throw HipError("candidate stack has the wrong size (internal)");
 	for (uint32_t c = 0; c < C; c++)
-		out.nbad += sum[4 + c] ? 1 : 0;
+		out.nbad += sum.bad(c) ? 1 : 0;
 	return dense_nb0;
 }
 
@@ -1146,27 +1142,25 @@ static void fetch_result(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, const
 	hipStream_t s = ctx->stream;
 	const size_t P = (size_t)ctx->g.V + C;
 	tm.begin("pvst_d2h");
-	const uint32_t *sum = out.sum ? out.sum : read_summary(ctx, C, !p.all_seq, f);
-	const uint32_t *bad = sum + 4, *cstat = sum + 4 + (size_t)C, *npvst = sum + 4 + 2 * (size_t)C, *nbry = sum + 4 + 3 * (size_t)C,
-		       *doff = sum + 4 + 4 * (size_t)C;
+	const PassSummary sum(C, out.sum ? out.sum : read_summary(ctx, C, !p.all_seq, f));
 	for (uint32_t c = 0; c < C; c++)
-		if (cstat[c] == 2)
+		if (sum.status(c) == 2)
 			throw HipError("internal error: the spanning tree of component " + std::to_string(c + 1) + " did not reach every side");
 	f.total_components = C;
 	size_t total = 0, total_hp = 0;
 	for (uint32_t c = 0; c < C; c++) {
-		if (npvst[c] == 0)
+		if (sum.npvst(c) == 0)
 			continue;
 		povu_hip_forest::Tree t;
 		t.component_id = c + 1; // decompose.cpp:129
 		t.n_vtx = voff[c + 1] - voff[c];
 		t.n_links = eoff[c + 1] - eoff[c];
-		t.n_pvst = npvst[c];
+		t.n_pvst = sum.npvst(c);
 		t.off = total;
 		t.hp_off = total_hp;
-		t.n_hairpins = p.hairpins ? nbry[c] : 0;
+		t.n_hairpins = p.hairpins ? sum.nbry(c) : 0;
 		t.sub_c = c;
-		total += npvst[c];
+		total += sum.npvst(c);
 		total_hp += t.n_hairpins;
 		f.trees.push_back(t);
 	}
@@ -1187,18 +1181,18 @@ static void fetch_result(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, const
 		return;
 	}
 	// the parallel stages wrote every PVST back to back into f.blocks[0]
-	if (!out.mixed && (doff[C] != total || total != ctx->pw.d_total))
+	if (!out.mixed && (sum.total() != total || total != ctx->pw.d_total))
 		throw HipError("internal error: dense PVST size mismatch");
 	if (f.blocks.empty())
 		f.alloc(ctx->pw.d_total);
 	size_t redo_total = 0;
 	for (auto &t : f.trees) {
-		if (out.mixed && bad[t.component_id - 1]) {
+		if (out.mixed && sum.bad(t.component_id - 1)) {
 			t.off = redo_total;
 			redo_total += t.n_pvst;
 			redone.push_back(&t);
 		} else {
-			t.off = doff[t.component_id - 1];
+			t.off = sum.doff(t.component_id - 1);
 		}
 	}
 	bool more = false;
@@ -1678,7 +1672,8 @@ extern "C" int povu_hip_last_crossings(povu_hip_ctx *ctx, uint32_t out[2])
 	ctx->quiesce();
 	if (hipSetDevice(ctx->device) != hipSuccess)
 		return 2;
-	return hipMemcpy(out, ctx->pw.err + 11, 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
+	static_assert(PW_N_CROSSED == PW_N_X + 1, "the two crossing words are copied as a pair");
+	return hipMemcpy(out, ctx->pw.err + PW_N_X, 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
 }
 
 extern "C" int povu_hip_last_laminar_check_ran(const povu_hip_ctx *ctx)

@@ -14,6 +14,7 @@
 //            compute_eq_class_metadata     flubbles.cpp:375-410
 //            add_flubbles                  flubbles.cpp:295-367
 #include "seq_kernels.hpp"
+#include "par_kernels.hpp" // PASS_WORDS
 
 #include <algorithm>
 
@@ -550,7 +551,7 @@ __global__ void k_zero_counters(uint32_t n, uint32_t *a, uint32_t *b, uint32_t *
 		if (bad)
 			bad[i] = 0;
 	}
-	if (err && i < 16)
+	if (err && i < PASS_WORDS)
 		err[i] = 0;
 }
 

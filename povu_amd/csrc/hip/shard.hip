@@ -774,7 +774,7 @@ extern "C" povu_hip_forest *povu_hip_forest_attach(povu_hip_ctx *ctx, povu_hip_f
 			const size_t seg_bytes = d[2], nt = d[3], total = d[4], meta_off = d[6];
 			// (numbers from another process: bound them before any arithmetic on them)
 			if (nt == 0 || nt > seg_bytes / 32 || total > seg_bytes / 4 || meta_off > seg_bytes ||
-			    meta_off + povu_hip_forest::meta_bytes(nt) > seg_bytes || povu_hip_forest::layout(nullptr, total) > meta_off)
+			    meta_off + povu_hip_forest::meta_bytes(nt) > seg_bytes || povu_hip_forest::Arrays::layout(nullptr, total) > meta_off)
 				throw HipError("attach: descriptor of " + rank + " does not fit its segment");
 			const char *b = map_segment(PinnedPool::segment_name(seg_tag, (int)d[1]), seg_bytes);
 			const uint64_t *mh = reinterpret_cast<const uint64_t *>(b + meta_off);

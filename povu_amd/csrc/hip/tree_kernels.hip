@@ -833,25 +833,8 @@ __global__ void k_t0_parents(uint32_t V, const uint2 *__restrict__ trec, L0Ranks
 // value (about one in six of a pangenome graph): the values sit compact, in tour order, behind a bitmap of the positions
 // (25 MB for 2e8 positions: cache resident) with the count of set bits in front of every word.
 //   rank(p)  = set bits at positions < p;   running xor in front of position p = xps[rank(p)]
-__global__ void k_bit_counts(uint32_t W, const uint4 *__restrict__ xrec, uint32_t *__restrict__ xrank)
-{
-	uint32_t w = BIDX * blockDim.x + threadIdx.x;
-	if (w <= W)
-		xrank[w] = w < W ? (uint32_t)(__popc(xrec[w].x) + __popc(xrec[w].y)) : 0u;
-}
-__global__ void k_bit_ranks(uint32_t W, const uint32_t *__restrict__ xrank, uint4 *__restrict__ xrec)
-{
-	uint32_t w = BIDX * blockDim.x + threadIdx.x;
-	if (w < W)
-		xrec[w].z = xrank[w];
-}
-// (one 16-byte load: the word of the bitmap and the count in front of it sit together)
-__device__ __forceinline__ uint32_t tour_rank(const uint4 *__restrict__ xrec, uint32_t p)
-{
-	const uint4 r = xrec[p >> 6];
-	const unsigned long long bits = (unsigned long long)r.x | ((unsigned long long)r.y << 32);
-	return r.z + (uint32_t)__popcll(bits & ((1ull << (p & 63u)) - 1ull));
-}
+// (common.hpp's bit-rank directory: bitrank_build fills in the counts, bitrank is one 16-byte load -- the word of the bitmap
+// and the count in front of it sit together)
 // one lane per segment (all reads in segment order): the value of a segment whose position bit is set
 // (two segments a lane -- one 16-byte load of their four ft words -- measured SLOWER: 1.22 ms against 1.00)
 __global__ void k_tour_values(uint32_t V, const uint4 *__restrict__ t0seg, const uint32_t *__restrict__ ft,
@@ -867,7 +850,7 @@ __global__ void k_tour_values(uint32_t V, const uint4 *__restrict__ t0seg, const
 	if (r.x == NIL) // a root is entered by no arc: its value is in no stretch
 		return;
 	const ulonglong2 z = make_ulonglong2(0ull, 0ull);
-	xval[tour_rank(xrec, r.z)] = hx((f2.x & FT_HASH) ? hside[2 * g] : z, (f2.y & FT_HASH) ? hside[2 * g + 1] : z);
+	xval[bitrank(xrec, r.z)] = hx((f2.x & FT_HASH) ? hside[2 * g] : z, (f2.y & FT_HASH) ? hside[2 * g + 1] : z);
 }
 // parent word of side S: its parent in the rooted forest, bit 31 set when the edge to it is a bridge (NIL: S roots its tree).
 // It lives in cstate[S] (below) next to the visited bit -- a separate array of them was 0.8 GB written and read once more.
@@ -896,7 +879,7 @@ __global__ void k_bridges(uint32_t V, const uint4 *__restrict__ t0seg, const uin
 	// xor of the values at the tour positions [p, q): two look-ups into the running xor -- and none at all when no position in
 	// between carries a value (the ranks of both ends agree: the subtree of most segments holds no non-tree link)
 	auto stretch = [&](uint32_t p, uint32_t q) {
-		const uint32_t rp = tour_rank(xrec, p), rq = tour_rank(xrec, q);
+		const uint32_t rp = bitrank(xrec, p), rq = bitrank(xrec, q);
 		return rp == rq ? make_ulonglong2(0ull, 0ull) : hx(xps[rp], xps[rq]);
 	};
 	const uint4 r = t0seg[g];
@@ -2007,6 +1990,41 @@ void stage_workspace_carve(Arena &ar, ParWs &pw, TreeWs &tw, size_t V, size_t E,
 	ar.advance_to(tree_end);
 }
 
+// ------------------------------------------------------------------ overlays
+// Every array the tree stage uses under another type or meaning than the one it is declared with, named once.  Next to
+// each view: the array under it, and from which kernel to which the view is live (the array's other tenant in brackets).
+// The steps below address these arrays through the views only.
+struct TreeViews {
+	ulonglong2 *hside;   // evt: [nS] 16-byte hash words of the sides (evt holds [max(4V, 2E)] 8-byte words); k_tour_words -> k_bridges [then the event records of the second ranking]
+	uint32_t *ft;	     // be_cnt: [nS] first arc of a side | "its hash word was written"; k_tour_words -> k_tour_values [free until the back edges are counted]
+	uint2 *fstr;	     // rk_pk: [V] the far sides' stretches, 8-byte records over the tour's list words, which the first ranking has consumed (rk_pk holds more than 4V words); k_t0_parents -> k_bridges [then k_events rewrites all 3V words for the second ranking]
+	uint8_t *multi;	     // dvis_slots: per-side class flags (sized for max(2E, 2V) + 16, see tree_spans); cleared by k_t0_parents, k_bridges -> k_entry_list [then the per-slot duplicate flags, k_dup_flags]
+	uint32_t *cstate;    // SeqWs::cur: [nS+1] parent word | visited bit of a side; k_bridges -> k_walk_finish
+	uint8_t *merged;     // dvis: [V]; k_events -> k_tree_emit
+	uint32_t *over_list; // entry_ps: entries of the classes handed to the wave walk (a spare array of the entries' size); k_class_dfs_small -> k_class_walk_wave
+	// the slot sort of the duplicate flags (hub graphs): keys and values in the bridge test's value arrays, the side of every
+	// slot in the event records, all free behind k_tree_emit ([NA] 8-byte words each, NA >= 2E); k_slot_keys -> k_dup_flags
+	uint32_t *k1, *k2;   // xval: [2E] each
+	uint32_t *v1, *v2;   // xps: [2E] each
+	uint32_t *side_of;   // evt: [2E]
+};
+static TreeViews tree_views(const TreeWs &tw, uint32_t E, uint32_t *cur = nullptr)
+{
+	const size_t n_slots = 2 * (size_t)E;
+	TreeViews v;
+	v.hside = reinterpret_cast<ulonglong2 *>(tw.evt);
+	v.ft = tw.be_cnt;
+	v.fstr = reinterpret_cast<uint2 *>(tw.rk_pk);
+	v.multi = tw.dvis_slots;
+	v.cstate = cur;
+	v.merged = tw.dvis;
+	v.over_list = tw.entry_ps;
+	v.k1 = reinterpret_cast<uint32_t *>(tw.xval), v.k2 = v.k1 + n_slots;
+	v.v1 = reinterpret_cast<uint32_t *>(tw.xps), v.v2 = v.v1 + n_slots;
+	v.side_of = reinterpret_cast<uint32_t *>(tw.evt);
+	return v;
+}
+
 // ------------------------------------------------------------------ driver
 void tree_tour_words(const CompState &cs, uint32_t V, uint32_t E, TreeWs &tw, bool force_sparse_splitters, hipStream_t s)
 {
@@ -2015,78 +2033,151 @@ void tree_tour_words(const CompState &cs, uint32_t V, uint32_t E, TreeWs &tw, bo
 	if (n_slots >= P0_END || 3 * (size_t)V >= P0_END) // (the first ranking runs over the 2E slots, the second over 3 V events)
 		throw HipError("graph too large for the packed list ranking: 2 * links and 3 * segments must stay below 2^30");
 	const unsigned bitsA = force_sparse_splitters ? 4u : rank_bucket_bits(n_slots);
-	ulonglong2 *hside = reinterpret_cast<ulonglong2 *>(tw.evt); // [nS] 16-byte words (evt, [max(4V, 2E)] 8-byte words, is free until the second ranking)
-	uint32_t *ft = tw.be_cnt;				    // [nS] (free until the back edges are counted)
-	LAUNCH(k_tour_words, nS, s, nS, cs.loff, cs.ladj, cs.lle, tw.rk_pk, bitsA, hside, ft);
+	const TreeViews v = tree_views(tw, E);
+	LAUNCH(k_tour_words, nS, s, nS, cs.loff, cs.ladj, cs.lle, tw.rk_pk, bitsA, v.hside, v.ft);
 	tw.tour_words_done = true;
 }
 
-int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw, uint32_t C, uint32_t event_lists,
-			   uint32_t max_side_links, bool force_big_class_dfs, bool force_sparse_splitters, StageTimer &tm,
-			   hipStream_t s)
+// One pass of the tree stage: what run_parallel_tree's steps share.  The steps run in the order they stand in.
+struct TreePass {
+	const CompState &cs;
+	SeqWs &sw;
+	ParWs &pw;
+	TreeWs &tw;
+	StageTimer &tm;
+	hipStream_t s;
+	const uint32_t C, V, E, nS;
+	const uint32_t max_side_links;
+	const bool force_big_class_dfs, force_sparse_splitters;
+	const TreeViews v;
+	const unsigned long long *start_key;
+	const uint32_t NA;	// arcs of the spanning forest of the segments = positions of the tours
+	const size_t n_slots;	// list elements of the first ranking = adjacency slots (loff[nS] = 2E: every link has one at either end)
+	const uint32_t XW;	// words of the position bitmap
+	const uint32_t n_events; // list elements of the second ranking: three per segment
+	const unsigned bitsA, bitsE; // bucket bits of the two rankings
+	RankBufs rb;
+	L0Ranks tour_r{}, evr{}; // ranks of the tour (records in tw.dist) and of the pre-order events (records in tw.evt)
+	bool events_done = false; // k_events went out early, behind the small walk, and no class overflowed
+	const uint8_t *dupflag = nullptr;
+
+	TreePass(const CompState &cs_, SeqWs &sw_, ParWs &pw_, TreeWs &tw_, uint32_t C_, uint32_t max_side_links_, bool big_dfs, bool sparse,
+		 StageTimer &tm_, hipStream_t s_)
+		: cs(cs_), sw(sw_), pw(pw_), tw(tw_), tm(tm_), s(s_), C(C_), V(sw_.V), E(sw_.E), nS(2 * sw_.V), max_side_links(max_side_links_),
+		  force_big_class_dfs(big_dfs), force_sparse_splitters(sparse), v(tree_views(tw_, sw_.E, sw_.cur)),
+		  start_key((const unsigned long long *)cs_.start_key), NA(2 * (V - C)), n_slots(2 * (size_t)E), XW(NA / 64 + 1), n_events(3 * V),
+		  bitsA(sparse ? 4u : rank_bucket_bits(n_slots)), bitsE(sparse ? 4u : rank_bucket_bits(n_events)),
+		  rb{tw_.rk_pk, tw_.rk_heads, tw_.rk_nx, tw_.rk_wa, tw_.rk_wb, tw_.rk_tA, tw_.rk_tB, tw_.rk_tC}
+	{
+	}
+	// (7.) one list per processed component, one two-event list per side of an unprocessed one
+	void enqueue_events()
+	{
+		HIP_CHECK(hipMemsetAsync(rb.heads, 0xFF, (size_t)C * 4, s)); // components that are not decomposed head no list
+		LAUNCH(k_events, V, s, V, tw.dps, cs.loff, cs.ladj, cs.ckey, tw.cproc, rb.pk, rb.heads, bitsE, v.merged, pw.sdl);
+	}
+};
+
+// ---- 1-2. spanning forest, rooted at the DFS start by an Euler tour.  Writes the tour's ranks (dist, R in the pools:
+// free until the class walks), t0seg, fstr, the bits of xrec, multi (cleared); the word PW_FOREST_SIZE.
+static void root_forest(TreePass &P)
 {
-	const uint32_t V = sw.V, E = sw.E, nS = 2 * V;
-	const unsigned long long *start_key = (const unsigned long long *)cs.start_key;
-
-	// ---- 1-2. spanning forest, rooted at the DFS start by an Euler tour
-	tm.begin("tree_root_forest");
-	const uint32_t NA = 2 * (V - C); // arcs of the spanning forest of the segments = positions of the tours
-	const size_t n_slots = 2 * (size_t)E; // list elements = adjacency slots (loff[nS] = 2E: every link has one at either end)
-	RankBufs rb{tw.rk_pk, tw.rk_heads, tw.rk_nx, tw.rk_wa, tw.rk_wb, tw.rk_tA, tw.rk_tB, tw.rk_tC};
-	const unsigned bitsA = force_sparse_splitters ? 4u : rank_bucket_bits(n_slots);
-	ulonglong2 *hside = reinterpret_cast<ulonglong2 *>(tw.evt); // [nS] 16-byte words (evt, [max(4V, 2E)] 8-byte words, is free until the second ranking)
-	uint32_t *ft = tw.be_cnt;						    // [nS] (free until the back edges are counted)
+	const CompState &cs = P.cs;
+	TreeWs &tw = P.tw;
+	hipStream_t s = P.s;
+	const uint32_t V = P.V, C = P.C;
+	P.tm.begin("tree_root_forest");
 	if (!tw.tour_words_done) // (else: started by povu_hip_decompose while the host still waited for the component sizes)
-		tree_tour_words(cs, V, E, tw, force_sparse_splitters, s);
+		tree_tour_words(cs, V, P.E, tw, P.force_sparse_splitters, s);
 	tw.tour_words_done = false;
-	LAUNCH(k_tour_ends, C, s, C, cs.voff, start_key, cs.loff, cs.ladj, cs.lle, rb.pk, rb.heads);
-	// the tour's ranks stay records (tw.dist), R in the pools (free until the class walks)
-	L0Ranks tour_r{};
-	if (n_slots)
-		tour_r = list_rank_splitters<false>((uint32_t)n_slots, bitsA, tw.dist, nullptr, C, rb, s);
-	const uint32_t XW = NA / 64 + 1; // words of the position bitmap
-	HIP_CHECK(hipMemsetAsync(tw.xrec, 0, ((size_t)XW + 2) * 16, s));
-	// (the far sides' stretches, k_t0_parents -> k_bridges: V 8-byte records over the tour's list words, which the ranking
-	// above has consumed and k_events rewrites, all 3V of them, for the second one; rk_pk holds more than 4V words)
-	uint2 *fstr = reinterpret_cast<uint2 *>(tw.rk_pk);
-	LAUNCH(k_t0_parents, std::max(V, C), s, V, tw.dist, tour_r, cs.ckey, cs.voff, cs.loff, cs.ladj, cs.lle, ft, rb.heads,
-	       tw.t0seg, fstr, tw.xrec, C, start_key, pw.err + 2, tw.dvis_slots);
-	tm.end(40);
+	LAUNCH(k_tour_ends, C, s, C, cs.voff, P.start_key, cs.loff, cs.ladj, cs.lle, P.rb.pk, P.rb.heads);
+	if (P.n_slots)
+		P.tour_r = list_rank_splitters<false>((uint32_t)P.n_slots, P.bitsA, tw.dist, nullptr, C, P.rb, s);
+	HIP_CHECK(hipMemsetAsync(tw.xrec, 0, ((size_t)P.XW + 2) * 16, s));
+	LAUNCH(k_t0_parents, std::max(V, C), s, V, tw.dist, P.tour_r, cs.ckey, cs.voff, cs.loff, cs.ladj, cs.lle, P.v.ft, P.rb.heads,
+	       tw.t0seg, P.v.fstr, tw.xrec, C, P.start_key, P.pw.err + PW_FOREST_SIZE, P.v.multi);
+	P.tm.end(40);
+}
 
-	// ---- 3-4. bridges and 2-edge-connected classes
-	tm.begin("tree_bridges_classes");
-	LAUNCH(k_bit_counts, (size_t)XW + 1, s, XW, tw.xrec, tw.xrank);
-	scan_exclusive_u32(tw.xrank, tw.xrank, (size_t)XW + 1, pw.scan_tmp, pw.scan_tmp_bytes, s); // xrank[XW] = values in all
-	LAUNCH(k_bit_ranks, XW, s, XW, tw.xrank, tw.xrec);
-	LAUNCH(k_tour_values, V, s, V, tw.t0seg, ft, hside, tw.xrec, tw.xval);
+// ---- 3-4. bridges and 2-edge-connected classes: the running xor of the sides' hash words along the tours (xval, xps
+// behind the bit-rank directory xrec) decides every tree edge; writes cstate, multi, dps
+static void bridges_and_classes(TreePass &P)
+{
+	const CompState &cs = P.cs;
+	ParWs &pw = P.pw;
+	TreeWs &tw = P.tw;
+	const TreeViews &v = P.v;
+	hipStream_t s = P.s;
+	const uint32_t V = P.V, XW = P.XW;
+	P.tm.begin("tree_bridges_classes");
+	bitrank_build(tw.xrec, XW, tw.xrank, pw.scan_tmp, pw.scan_tmp_bytes, s); // (leaves xrank[XW] = values in all)
+	LAUNCH(k_tour_values, V, s, V, tw.t0seg, v.ft, v.hside, tw.xrec, tw.xval);
 	// (the number of values stays on the device: the scan is launched for the most there can be, one per segment, and
 	// stops at their count + 1)
 	scan_exclusive_xor_u128(tw.xval, tw.xps, (size_t)V + 1, pw.scan_tmp, pw.scan_tmp_bytes, s, tw.xrank + XW);
-	uint8_t *multi = tw.dvis_slots; // (see tree_spans: sized for max(2E, 2V) + 16; cleared by k_t0_parents)
-	uint32_t *cstate = sw.cur; // [nS+1]
-	LAUNCH(k_bridges, V, s, V, tw.t0seg, fstr, tw.xps, tw.xrec, hside, cs.loff, cs.lle, cs.ckey, tw.cproc, multi, cstate, tw.dps);
-	tm.end(8 + 44);
+	LAUNCH(k_bridges, V, s, V, tw.t0seg, v.fstr, tw.xps, tw.xrec, v.hside, cs.loff, cs.lle, cs.ckey, tw.cproc, v.multi, v.cstate, tw.dps);
+	P.tm.end(8 + 44);
+}
 
-	// ---- 5-6. entries and the per-class DFS
-	tm.begin("tree_class_dfs");
-	uint32_t *n_entry_dev = pw.err + 9; // (cleared with the other counters at the start of the pass)
-	KLAUNCH(k_entry_list, dim3((nS + EL_SIDES - 1) / EL_SIDES), dim3(TPB), 0, s, nS, cstate, multi, cs.ckey, tw.cproc, tw.entry_list, n_entry_dev);
-	// Small classes are walked by the plain walk, one lane each.  A lane that finds its class larger than CLASS_BUDGET sides
-	// gives up and reports the entry; those classes are then walked from the start by the walk with the short dependent
-	// chain, at the price of a filtering pass over the adjacency (it marks visits in its own bytes and rewrites the same
-	// parents, so the abandoned attempt leaves nothing behind).
+// ---- 6. large classes: one wave each, from the start (the walk marks visits in its own bytes and rewrites the same
+// parents, so an abandoned attempt of the small walk leaves nothing behind), at the price of a filtering pass over the
+// adjacency
+static void walk_large_classes(TreePass &P, uint32_t n_big, const uint32_t *big_list)
+{
+	const CompState &cs = P.cs;
+	ParWs &pw = P.pw;
+	TreeWs &tw = P.tw;
+	hipStream_t s = P.s;
+	const uint32_t nS = P.nS;
+	if (!tw.walk_inline) { // the records of all sides, the stack pool and the parents: taken when a pass needs them
+		if (!tw.walk_arena)
+			throw HipError("class walk: no arena for the wave walk's arrays (internal)");
+		const WalkBytes wb(2 * (size_t)P.V + 2);
+		tw.walk_arena->reserve(walk_workspace_bytes(P.V));
+		tw.wrec = reinterpret_cast<decltype(tw.wrec)>(tw.walk_arena->take<char>(wb.rec));
+		tw.wstk = reinterpret_cast<decltype(tw.wstk)>(tw.walk_arena->take<char>(wb.stk));
+		tw.wpar = reinterpret_cast<decltype(tw.wpar)>(tw.walk_arena->take<char>(wb.par));
+	}
+	uint32_t *pool_top = pw.err + PW_POOL_TOP, *walk_err = pw.err + PW_WALK_POOL;
+	LAUNCH(k_class_recs, nS, s, nS, cs.loff, cs.ladj, P.v.cstate, cs.ckey, tw.cproc, tw.wadj, tw.wrec, tw.wpar);
+	const uint32_t route = getenv("POVU_HIP_WALK_ROUTE") ? (uint32_t)atoi(getenv("POVU_HIP_WALK_ROUTE")) : 0u; // (A/B hook)
+	const uint32_t pool_cap = (uint32_t)std::min<size_t>(3 * (size_t)nS, 0xFFFFFFF0u);
+	// the two forms side by side (see k_class_walk_wave): the second on the context's walk stream when there is one
+	hipStream_t s2 = tw.walk_stream ? tw.walk_stream : s;
+	if (s2 != s) {
+		HIP_CHECK(hipEventRecord(tw.walk_fork, s));
+		HIP_CHECK(hipStreamWaitEvent(s2, tw.walk_fork, 0));
+	}
+	KLAUNCH(k_class_walk_wave<false>, dim3(n_big), dim3(64), 0, s2, n_big, big_list, tw.wrec, tw.wadj, tw.wpar, tw.wstk, pool_top, pool_cap,
+		walk_err, nS, route);
+	KLAUNCH(k_class_walk_wave<true>, dim3(n_big), dim3(64), 0, s, n_big, big_list, tw.wrec, tw.wadj, tw.wpar, tw.wstk, pool_top, pool_cap,
+		walk_err, nS, route);
+	if (s2 != s) {
+		HIP_CHECK(hipEventRecord(tw.walk_join, s2));
+		HIP_CHECK(hipStreamWaitEvent(s, tw.walk_join, 0));
+	}
+	LAUNCH(k_walk_finish, nS, s, nS, tw.wpar, P.v.cstate, cs.loff, cs.ladj, tw.dps);
+	if (tw.host->read_u32(walk_err, s)) // (an unfinished walk leaves a broken tree: nothing downstream may run on it)
+		throw HipError("class walk: stack pool exhausted (internal sizing bug)");
+}
+
+// ---- 5-6. entries and the per-class DFS.  Small classes are walked by the plain walk, one lane each.  A lane that finds
+// its class larger than CLASS_BUDGET sides gives up and reports the entry; those classes go to walk_large_classes.
+// Writes entry_list, the DFS parents in cstate / dps; the words PW_N_ENTRY, PW_N_OVER.
+static void class_walks(TreePass &P)
+{
+	const CompState &cs = P.cs;
+	ParWs &pw = P.pw;
+	TreeWs &tw = P.tw;
+	const TreeViews &v = P.v;
+	hipStream_t s = P.s;
+	const uint32_t nS = P.nS;
+	P.tm.begin("tree_class_dfs");
+	uint32_t *n_entry_dev = pw.err + PW_N_ENTRY;
+	KLAUNCH(k_entry_list, dim3((nS + EL_SIDES - 1) / EL_SIDES), dim3(TPB), 0, s, nS, v.cstate, v.multi, cs.ckey, tw.cproc, tw.entry_list, n_entry_dev);
 	const uint32_t *big_list = tw.entry_list;
-	// (7.) one list per processed component, one two-event list per side of an unprocessed one
-	const uint32_t n_events = 3 * V; // three per segment
-	const unsigned bitsE = force_sparse_splitters ? 4u : rank_bucket_bits(n_events);
-	uint8_t *merged = tw.dvis; // [V]
-	bool events_done = false;
-	auto enqueue_events = [&]() {
-		HIP_CHECK(hipMemsetAsync(rb.heads, 0xFF, (size_t)C * 4, s)); // components that are not decomposed head no list
-		LAUNCH(k_events, V, s, V, tw.dps, cs.loff, cs.ladj, cs.ckey, tw.cproc, rb.pk, rb.heads, bitsE, merged, pw.sdl);
-	};
-	uint32_t n_big = force_big_class_dfs ? tw.host->read_u32(n_entry_dev, s) : 0; // (A/B mode: every class through the wave walk)
-	if (!force_big_class_dfs) {
+	uint32_t n_big = P.force_big_class_dfs ? tw.host->read_u32(n_entry_dev, s) : 0; // (A/B mode: every class through the wave walk)
+	if (!P.force_big_class_dfs) {
 		// Lanes in flight = a window of sides whose scattered stores meet again in L2.  Round 4's walk (one tree edge per
 		// three dependent round trips) was best at ~3000 x 64 lanes; with the black follow-through the walk issues fewer,
 		// wider accesses and more lanes in flight pay: 49 152 workgroups measured 0.2 ms faster on 2.3 * 10^7 classes
@@ -2096,80 +2187,59 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 		unsigned dfs_blocks = std::min(all_blocks, 49152u);
 		if (const char *ev = getenv("POVU_HIP_DFS_BLOCKS")) // (tuning hook)
 			dfs_blocks = std::min(all_blocks, std::max(1u, (unsigned)atoi(ev)));
-		uint32_t *n_over = pw.err + 4, *over_list = tw.entry_ps; // (a spare array of the entries' size)
+		uint32_t *n_over = pw.err + PW_N_OVER;
 		uint32_t budget = CLASS_BUDGET;
 		if (const char *ev = getenv("POVU_HIP_CLASS_BUDGET")) // (tuning hook: sides a lane walks before it hands its class to the wave walk)
 			budget = (uint32_t)std::max(16, atoi(ev));
-		KLAUNCH(k_class_dfs_small, dim3(dfs_blocks), dim3(64), 0, s, n_entry_dev, tw.entry_list, cs.loff, cs.ladj, cstate, tw.dps,
-			budget, n_over, over_list);
+		KLAUNCH(k_class_dfs_small, dim3(dfs_blocks), dim3(64), 0, s, n_entry_dev, tw.entry_list, cs.loff, cs.ladj, v.cstate, tw.dps,
+			budget, n_over, v.over_list);
 		// How many classes overflowed is read without leaving the stream idle (HostScratch::mark): behind the word goes the
 		// next stage's first kernel, on the assumption that none did -- with large classes around it ran on half-filled
 		// records and simply runs again behind the walks (it writes every word of its outputs).  Not with stage timers (the
 		// kernel would be booked on this stage).
-		if (!tm.enabled) {
+		if (!P.tm.enabled) {
 			uint32_t *w = tw.host->take<uint32_t>(1);
 			publish_words(w, WordSrc{{n_over}}, 1, s);
 			const HostScratch::Token published = tw.host->mark(s);
-			enqueue_events();
+			P.enqueue_events();
 			tw.host->wait(published);
 			n_big = *w;
-			events_done = n_big == 0;
+			P.events_done = n_big == 0;
 		} else {
 			n_big = tw.host->read_u32(n_over, s);
 		}
-		big_list = over_list;
+		big_list = v.over_list;
 	}
-	if (n_big) { // large classes: one wave each (see section 6)
-		if (!tw.walk_inline) { // the records of all sides, the stack pool and the parents: taken when a pass needs them
-			if (!tw.walk_arena)
-				throw HipError("class walk: no arena for the wave walk's arrays (internal)");
-			const WalkBytes wb(2 * (size_t)V + 2);
-			tw.walk_arena->reserve(walk_workspace_bytes(V));
-			tw.wrec = reinterpret_cast<decltype(tw.wrec)>(tw.walk_arena->take<char>(wb.rec));
-			tw.wstk = reinterpret_cast<decltype(tw.wstk)>(tw.walk_arena->take<char>(wb.stk));
-			tw.wpar = reinterpret_cast<decltype(tw.wpar)>(tw.walk_arena->take<char>(wb.par));
-		}
-		uint32_t *pool_top = pw.err + 7, *walk_err = pw.err + 8; // (cleared with the other counters at the start of the pass)
-		LAUNCH(k_class_recs, nS, s, nS, cs.loff, cs.ladj, cstate, cs.ckey, tw.cproc, tw.wadj, tw.wrec, tw.wpar);
-		const uint32_t route = getenv("POVU_HIP_WALK_ROUTE") ? (uint32_t)atoi(getenv("POVU_HIP_WALK_ROUTE")) : 0u; // (A/B hook)
-		const uint32_t pool_cap = (uint32_t)std::min<size_t>(3 * (size_t)nS, 0xFFFFFFF0u);
-		// the two forms side by side (see k_class_walk_wave): the second on the context's walk stream when there is one
-		hipStream_t s2 = tw.walk_stream ? tw.walk_stream : s;
-		if (s2 != s) {
-			HIP_CHECK(hipEventRecord(tw.walk_fork, s));
-			HIP_CHECK(hipStreamWaitEvent(s2, tw.walk_fork, 0));
-		}
-		KLAUNCH(k_class_walk_wave<false>, dim3(n_big), dim3(64), 0, s2, n_big, big_list, tw.wrec, tw.wadj, tw.wpar, tw.wstk, pool_top, pool_cap,
-			walk_err, nS, route);
-		KLAUNCH(k_class_walk_wave<true>, dim3(n_big), dim3(64), 0, s, n_big, big_list, tw.wrec, tw.wadj, tw.wpar, tw.wstk, pool_top, pool_cap,
-			walk_err, nS, route);
-		if (s2 != s) {
-			HIP_CHECK(hipEventRecord(tw.walk_join, s2));
-			HIP_CHECK(hipStreamWaitEvent(s, tw.walk_join, 0));
-		}
-		LAUNCH(k_walk_finish, nS, s, nS, tw.wpar, cstate, cs.loff, cs.ladj, tw.dps);
-		if (tw.host->read_u32(walk_err, s)) // (an unfinished walk leaves a broken tree: nothing downstream may run on it)
-			throw HipError("class walk: stack pool exhausted (internal sizing bug)");
-	}
-	tm.end(5);
+	if (n_big)
+		walk_large_classes(P, n_big, big_list);
+	P.tm.end(5);
+}
 
-	// ---- 7. pre-order, sizes, depths
-	tm.begin("tree_preorder");
-	(void)max_side_links;
-	if (!events_done)
-		enqueue_events();
-	const L0Ranks evr = list_rank_splitters<true, true>(n_events, bitsE, tw.evt, pw.err + 13, C, rb, s); // records, see k_tree_emit
-	(void)event_lists;
-	tm.end(40);
+// ---- 7. pre-order, sizes, depths: the second ranking, over the events (records in evt, see k_tree_emit)
+static void preorder(TreePass &P)
+{
+	P.tm.begin("tree_preorder");
+	if (!P.events_done)
+		P.enqueue_events();
+	P.evr = list_rank_splitters<true, true>(P.n_events, P.bitsE, P.tw.evt, P.pw.err + PW_RANK_OVF, P.C, P.rb, P.s);
+	P.tm.end(40);
+}
 
-	// ---- 8. tree arrays in pre-order and the from_bd back edges
-	tm.begin("tree_emit");
-	// (incnt: k_back_edges counts the brackets that end at a vertex into it; the two bracket counts as words or bytes)
+// ---- 8. tree arrays in pre-order (sw.t_*, side_tidx, c_ntree; hi0, mpre, sdl and the cleared counts of the class stage);
+// the two bracket counts as words or bytes
+static void emit_tree(TreePass &P)
+{
+	const CompState &cs = P.cs;
+	SeqWs &sw = P.sw;
+	ParWs &pw = P.pw;
+	TreeWs &tw = P.tw;
+	P.tm.begin("tree_emit");
+	// (incnt: k_back_edges counts the brackets that end at a vertex into it)
 	auto tree_emit = [&](auto *ordcnt, auto *srccnt) {
 		using OC = std::remove_pointer_t<decltype(ordcnt)>;
 		using SC = std::remove_pointer_t<decltype(srccnt)>;
-		LAUNCH((k_tree_emit<OC, SC>), std::max(V, C), s, nS, tw.evt, evr, merged, tw.dps, cs.ckey, tw.cproc, cs.voff, start_key, cs.gid_s, sw.t_gid,
-		       sw.t_flags, sw.t_par, sw.t_size, (sw.hairpins || sw.want_depth) ? sw.t_depth : nullptr, tw.side_tidx, C, sw.c_ntree, ordcnt,
+		LAUNCH((k_tree_emit<OC, SC>), std::max(P.V, P.C), P.s, P.nS, tw.evt, P.evr, P.v.merged, tw.dps, cs.ckey, tw.cproc, cs.voff, P.start_key, cs.gid_s, sw.t_gid,
+		       sw.t_flags, sw.t_par, sw.t_size, (sw.hairpins || sw.want_depth) ? sw.t_depth : nullptr, tw.side_tidx, P.C, sw.c_ntree, ordcnt,
 		       pw.hi0, pw.mpre, srccnt, pw.sdl, pw.incnt);
 	};
 	if (pw.narrow_ordcnt && pw.narrow_srccnt)
@@ -2179,33 +2249,59 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 	else
 		tree_emit(pw.lsz, pw.dlt);
 	pw.sdl_filled = true;
-	const uint8_t *dupflag = nullptr;
-	if (max_side_links > 64 && E) { // see k_dup_flags
-		const uint32_t n_slots = 2 * E;
-		// the bridge test's value arrays and the event ranks are free by now ([NA] 8-byte words each, NA >= 2E)
-		uint32_t *k1 = (uint32_t *)tw.xval, *k2 = k1 + n_slots, *v1 = (uint32_t *)tw.xps, *v2 = v1 + n_slots;
-		uint32_t *side_of = (uint32_t *)tw.evt;
-		LAUNCH(k_slot_keys, n_slots, s, n_slots, cs.ladj, k1, v1);
-		sort_pairs_u32(k1, k2, v1, v2, n_slots, bits_for(nS), pw.sort_tmp, pw.sort_tmp_bytes, s);
-		LAUNCH(k_slot_side, nS, s, nS, cs.loff, side_of);
-		LAUNCH(k_gather_keys, n_slots, s, n_slots, v2, side_of, k1);
-		sort_pairs_u32(k1, k2, v2, v1, n_slots, bits_for(nS), pw.sort_tmp, pw.sort_tmp_bytes, s);
-		LAUNCH(k_dup_flags, n_slots, s, n_slots, k2, v1, cs.ladj, tw.dvis_slots);
-		dupflag = tw.dvis_slots;
+}
+
+// ---- (hub graphs) which adjacency slots repeat an earlier link of their side, see k_dup_flags: two sorts of the slots
+static void dup_flags(TreePass &P)
+{
+	const CompState &cs = P.cs;
+	ParWs &pw = P.pw;
+	TreeWs &tw = P.tw;
+	const TreeViews &v = P.v;
+	hipStream_t s = P.s;
+	if (P.max_side_links > 64 && P.E) {
+		const uint32_t n_slots = 2 * P.E, nS = P.nS;
+		LAUNCH(k_slot_keys, n_slots, s, n_slots, cs.ladj, v.k1, v.v1);
+		sort_pairs_u32(v.k1, v.k2, v.v1, v.v2, n_slots, bits_for(nS), pw.sort_tmp, pw.sort_tmp_bytes, s);
+		LAUNCH(k_slot_side, nS, s, nS, cs.loff, v.side_of);
+		LAUNCH(k_gather_keys, n_slots, s, n_slots, v.v2, v.side_of, v.k1);
+		sort_pairs_u32(v.k1, v.k2, v.v2, v.v1, n_slots, bits_for(nS), pw.sort_tmp, pw.sort_tmp_bytes, s);
+		LAUNCH(k_dup_flags, n_slots, s, n_slots, v.k2, v.v1, cs.ladj, tw.dvis_slots);
+		P.dupflag = tw.dvis_slots;
 	}
-	tw.last_dupflag = dupflag;
-	uint32_t *nb0_dev = pw.err + 6; // (cleared with the other counters at the start of the pass)
-	auto back_edges = [&](auto *ordcnt) {
-		KLAUNCH((k_back_edges<std::remove_pointer_t<decltype(ordcnt)>>), dim3((nS + BE_SIDES - 1) / BE_SIDES), dim3(TPB), 0, s, nS, cs.loff, cs.ladj, tw.dps, tw.side_tidx, cs.ckey,
-			cs.voff, sw.t_par, nb0_dev, pw.b_src, pw.b_tgt, pw.b_ord, dupflag, ordcnt, pw.hi0, pw.incnt,
+	tw.last_dupflag = P.dupflag;
+}
+
+// ---- the from_bd back edges (b_src / b_tgt / b_ord, hi0, incnt, the ordinary count); their number stays on the device
+// (PW_NB0): the class stage reads it together with its own counts
+static void back_edges(TreePass &P)
+{
+	const CompState &cs = P.cs;
+	ParWs &pw = P.pw;
+	TreeWs &tw = P.tw;
+	auto launch = [&](auto *ordcnt) {
+		KLAUNCH((k_back_edges<std::remove_pointer_t<decltype(ordcnt)>>), dim3((P.nS + BE_SIDES - 1) / BE_SIDES), dim3(TPB), 0, P.s, P.nS, cs.loff, cs.ladj, tw.dps, tw.side_tidx, cs.ckey,
+			cs.voff, P.sw.t_par, pw.err + PW_NB0, pw.b_src, pw.b_tgt, pw.b_ord, P.dupflag, ordcnt, pw.hi0, pw.incnt,
 			(uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu));
 	};
 	if (pw.narrow_ordcnt)
-		back_edges(pw.ordcnt8);
+		launch(pw.ordcnt8);
 	else
-		back_edges(pw.lsz);
-	// (their number stays on the device: the class stage reads it together with its own counts)
-	tm.end(6);
+		launch(pw.lsz);
+	P.tm.end(6);
+}
+
+int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw, uint32_t C, uint32_t max_side_links,
+			   bool force_big_class_dfs, bool force_sparse_splitters, StageTimer &tm, hipStream_t s)
+{
+	TreePass P(cs, sw, pw, tw, C, max_side_links, force_big_class_dfs, force_sparse_splitters, tm, s);
+	root_forest(P);
+	bridges_and_classes(P);
+	class_walks(P);
+	preorder(P);
+	emit_tree(P);
+	dup_flags(P);
+	back_edges(P);
 	return NB0_ON_DEVICE;
 }
 

@@ -8,13 +8,14 @@
 namespace povu_hip
 {
 
+// (arrays that a pass also uses under another type or meaning: see TreeViews in tree_kernels.hip, the one place that names them)
 struct TreeWs {
 	HostScratch *host; // pinned read-back scratch of the owning context
 	// unrooted spanning forest of the biedged graph H, as arcs
 	uint2 *dist;					  // [2E] record {owner, partial} of an adjacency slot in the Euler-tour ranking (slots of hooked links = arcs; its rank, the arcs behind it: rank_l0, see tree_kernels.hip)
 	ulonglong2 *xval, *xps;				  // [max(V, E) + 16] xor values (two 64-bit hashes) of the segments that have any, in tour order, and their running xor (inside the shared block, see tree_spans)
-	uint4 *xrec;					  // [(4V+8)/64 + 4] per 64 tour positions {which of them carry a value (64 bits), set bits in front of the word, -}
-	uint32_t *xrank;				  // [(4V+8)/64 + 4] scan buffer of the bit counts (the last entry: their total)
+	uint4 *xrec;					  // [(4V+8)/64 + 4] per 64 tour positions {which of them carry a value (64 bits), set bits in front of the word, -}: a bit-rank directory (common.hpp)
+	uint32_t *xrank;				  // [(4V+8)/64 + 4] scan buffer of bitrank_build (the entry behind the last word: the number of values)
 	uint4 *t0seg;					  // [V] rooted forest, per segment: {parent of the entered side, link to it | r bit, tour position in, out}
 	uint2 *dps;					  // [2V] {DFS parent side, scan slot of the parent it was found through}
 	uint8_t *dvis;					  // [2V]
@@ -54,9 +55,8 @@ void tree_tour_words(const CompState &cs, uint32_t V, uint32_t E, TreeWs &tw, bo
 
 // Builds the reference's spanning tree of every processed component (tree arrays in sw, T-space
 // layout) and the dense list of from_bd back edges (pw.b_src / pw.b_tgt).  Returns their count.
-int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw, uint32_t C, uint32_t event_lists,
-			   uint32_t max_side_links, bool force_big_class_dfs, bool force_sparse_splitters, StageTimer &tm,
-			   hipStream_t s);
+int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw, uint32_t C, uint32_t max_side_links,
+			   bool force_big_class_dfs, bool force_sparse_splitters, StageTimer &tm, hipStream_t s);
 
 // unit-test hook: the level-0 ranks of list_rank_splitters for the lists next[] (NIL = end) with heads[nh], as the readers
 // resolve them -- mode 0: ra = suffix sums of the 0/1 weights w; mode 1 (the pre-order events): ra, rb = the two sums of the

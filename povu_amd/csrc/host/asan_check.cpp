@@ -109,6 +109,17 @@ static int check_forest_wire()
 		if (!(x))                                                                                                                    \
 			return __LINE__;                                                                                                     \
 	} while (0)
+	// ---- the five arrays of a PVST block: a | z | parent | a_or | z_or, each padded to 64 B, inside the linear bound
+	for (size_t total : {size_t(0), size_t(1), size_t(15), size_t(16), size_t(17), size_t(1000)}) {
+		std::vector<char> blk(PvstArrays::bound(total) + 1);
+		char *q = blk.data();
+		PvstArrays v;
+		const size_t w = pad64(4 * total), b = pad64(total), bytes = PvstArrays::layout(q, total, &v);
+		WANT(bytes == 3 * w + 2 * b && bytes == PvstArrays::layout(nullptr, total) && bytes <= PvstArrays::bound(total));
+		WANT(w == PvstArrays::word_bytes(total) && b == PvstArrays::flag_bytes(total));
+		WANT((char *)v.a == q && (char *)v.z == q + w && (char *)v.parent == q + 2 * w);
+		WANT((char *)v.aor == q + 3 * w && (char *)v.zor == q + 3 * w + b);
+	}
 	// ---- tree tables: 0, 1 and 5 trees, with and without the extras words; the last tree's offset needs the high word
 	const uint64_t big = (1ull << 32) + 1000;
 	const TreeRecord five[5] = {{1, 10, 12, 7, 0, 0, 2, 0}, {2, 3, 2, 0, 7, 2, 0, 1}, {4, 9, 9, 5, 7, 2, 1, 2}, {7, 1, 0, 1, 12, 3, 0, 2},
