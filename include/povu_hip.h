@@ -707,10 +707,13 @@ uint32_t povu_hip_last_seq_redo(const povu_hip_ctx *ctx);
  * literal hi_2 rule of flubbles.cpp:566-574 picked the second-highest reach everywhere and no hairpins were asked
  * for), 0 when it went over all tree edges */
 int povu_hip_last_black_only_classes(const povu_hip_ctx *ctx);
-/* 1 when the last decompose kept the bracket counts per tree vertex as bytes between the tree stage and the placing of the
- * brackets (no side of the graph has more than 253 links, and POVU_HIP_WIDE_COUNTS=1 is not set in the environment), 0 when
- * the word kernels ran */
+/* non-zero when the last decompose kept the bracket counts per tree vertex as bytes between the tree stage and the placing of
+ * the brackets (no side of the graph has more than 253 links, and POVU_HIP_WIDE_COUNTS=1 is not set in the environment), 0
+ * when the word kernels ran.  The bits say which counts were bytes: 1 ordcnt (always set then), 2 srccnt, 4 incnt */
 int povu_hip_last_narrow_counts(const povu_hip_ctx *ctx);
+/* passes of this context, since it was created, that ran their tree and class stages a second time with word counts
+ * because a byte of incnt would have passed 255 (capping brackets that share one target); such a pass reports 0 above */
+uint64_t povu_hip_wide_repeats(const povu_hip_ctx *ctx);
 /* 1 when the last decompose ran the laminarity check of the candidate stack's (prev, i) intervals (only when the literal
  * hi_2 rule capped differently from the second-highest reach somewhere, or with POVU_HIP_F_CHECK_LAMINAR) */
 int povu_hip_last_laminar_check_ran(const povu_hip_ctx *ctx);
@@ -728,7 +731,9 @@ uint64_t povu_hip_last_links_processed(const povu_hip_ctx *ctx);
 /* copies comp_of[v] (0-based component rank) and local vertex idx for every GLOBAL vertex idx */
 int povu_hip_debug_components(povu_hip_ctx *ctx, uint32_t *comp_of, uint32_t *local_idx);
 /* tree arrays of component `comp` (0-based rank): sizes via n_tree first call with NULLs; `cls` is defined for the
- * child ends of black tree edges, and for the others too only when povu_hip_last_black_only_classes() == 0 */
+ * child ends of black tree edges, and for the others too only when povu_hip_last_black_only_classes() == 0.
+ * typ: bits 0-1 the vertex type (0 l, 1 r, 2 dummy), bit 2 the parent tree edge is black, bit 3 the vertex has no parent
+ * (set by the parallel stages only: a pass with POVU_HIP_F_SEQUENTIAL leaves it clear) */
 int povu_hip_debug_tree(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, uint32_t *gid, uint8_t *typ,
 			uint32_t *par, uint32_t *cls);
 /* id of the tree edge into each tree vertex (tree_edge_id[0] = 0xFFFFFFFF): tree and back edges share one counter in
@@ -765,6 +770,8 @@ int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t
  * op 8: sums of the n words of `in` and of the n2 BYTES of in2 in one launch (scan_exclusive_u32_u8_pair) */
 #define POVU_HIP_SCAN_DIFF_U8 7
 #define POVU_HIP_SCAN_MIXED_PAIR 8
+/* op 9: sums of in[i] - in2[i] with `in` and in2 both n BYTES (scan_exclusive_diff_u8_u8; out2 unused) */
+#define POVU_HIP_SCAN_DIFF_U8_U8 9
 #define POVU_HIP_SCAN_IN_PLACE 0x100
 #define POVU_HIP_SCAN_N_DEV 0x200
 int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,

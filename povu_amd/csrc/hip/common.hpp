@@ -339,6 +339,9 @@ void scan_exclusive_diff_u32(const uint32_t *in, const uint32_t *sub, uint32_t *
 // ... of in8[i] - sub[i]: byte counts (below 256 each) minus word counts
 void scan_exclusive_diff_u8_u32(const uint8_t *in8, const uint32_t *sub, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes,
 				hipStream_t s);
+// ... of in8[i] - sub8[i]: byte counts minus byte counts (the difference wraps mod 2^32 where sub8[i] > in8[i], as with words)
+void scan_exclusive_diff_u8_u8(const uint8_t *in8, const uint8_t *sub8, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes,
+			       hipStream_t s);
 // a word job and a byte job that are due at the same point of the pass, in the same launches
 void scan_exclusive_u32_u8_pair(const uint32_t *in0, uint32_t *out0, size_t n0, const uint8_t *in1, uint32_t *out1, size_t n1,
 				void *tmp, size_t tmp_bytes, hipStream_t s);

@@ -245,6 +245,7 @@ struct LastPass {
 	bool mixed = false, redo_pvst_only = false, stack_export_pending = false;
 	// the parallel stages kept the bracket counts per tree vertex (ordcnt / srccnt, see ParWs) as bytes
 	bool narrow_counts = false;
+	int narrow_forms = 0; // which of them: bit 0 ordcnt, bit 1 srccnt, bit 2 incnt
 };
 
 struct povu_hip_ctx {
@@ -260,6 +261,7 @@ struct povu_hip_ctx {
 	StageTimer timer;
 	std::vector<povu_hip_stage_time> last_times;
 	uint64_t last_links = 0;
+	uint64_t wide_repeats = 0; // passes of this context that ran their tree and class stages a second time with word counts (ParWs::incnt8)
 	// device state of the last decompose (debug / parity hooks)
 	CompState cs{};
 	SeqWs sw{};

@@ -116,8 +116,9 @@ const DbgScanOp DBG_SCAN_OPS[] = {
 	{16, 16, 16, DBG_NONE, false, false, false, true, false}, // POVU_HIP_SCAN_XOR_U128
 	{1, 4, 4, DBG_SUB, true, false, false, false, false},	  // POVU_HIP_SCAN_DIFF_U8
 	{4, 1, 4, DBG_PAIR, true, true, false, false, false},	  // POVU_HIP_SCAN_MIXED_PAIR
+	{1, 1, 4, DBG_SUB, true, false, false, false, false},	  // POVU_HIP_SCAN_DIFF_U8_U8
 };
-static_assert(sizeof(DBG_SCAN_OPS) / sizeof(DBG_SCAN_OPS[0]) == POVU_HIP_SCAN_MIXED_PAIR + 1, "one row per op");
+static_assert(sizeof(DBG_SCAN_OPS) / sizeof(DBG_SCAN_OPS[0]) == POVU_HIP_SCAN_DIFF_U8_U8 + 1, "one row per op");
 } // namespace
 
 extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,
@@ -125,7 +126,7 @@ extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in
 {
 	const int kind = op & 0xFF;
 	const bool in_place = (op & POVU_HIP_SCAN_IN_PLACE) != 0, with_len = (op & POVU_HIP_SCAN_N_DEV) != 0;
-	if (!ctx || kind > POVU_HIP_SCAN_MIXED_PAIR || (op & ~(0xFF | POVU_HIP_SCAN_IN_PLACE | POVU_HIP_SCAN_N_DEV)))
+	if (!ctx || kind > POVU_HIP_SCAN_DIFF_U8_U8 || (op & ~(0xFF | POVU_HIP_SCAN_IN_PLACE | POVU_HIP_SCAN_N_DEV)))
 		return 1;
 	const DbgScanOp &T = DBG_SCAN_OPS[kind];
 	if (T.nullable ? ((n && (!in || !out)) || (in2 && n2 && !out2)) : (!in || !out || (in2 && !out2 && T.second != DBG_SUB)))
@@ -172,6 +173,9 @@ extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in
 		case POVU_HIP_SCAN_DIFF: scan_exclusive_diff_u32(w1, w2, o1.data<uint32_t>(), n, tmp, tb, s); break;
 		case POVU_HIP_SCAN_DIFF_U8:
 			scan_exclusive_diff_u8_u32(reinterpret_cast<const uint8_t *>(di), w2, o1.data<uint32_t>(), n, tmp, tb, s);
+			break;
+		case POVU_HIP_SCAN_DIFF_U8_U8:
+			scan_exclusive_diff_u8_u8(reinterpret_cast<const uint8_t *>(di), reinterpret_cast<const uint8_t *>(di2), o1.data<uint32_t>(), n, tmp, tb, s);
 			break;
 		case POVU_HIP_SCAN_MIXED_PAIR:
 			scan_exclusive_u32_u8_pair(w1, o1.data<uint32_t>(), n, reinterpret_cast<const uint8_t *>(di2), o2.data<uint32_t>(), m, tmp, tb, s);

@@ -59,7 +59,7 @@ __global__ void k_globalize(uint32_t T, const uint32_t *__restrict__ t_comp, con
 			    const uint32_t *__restrict__ t_size, uint32_t *__restrict__ gpar, uint32_t *__restrict__ gsize,
 			    uint32_t *__restrict__ t_root, uint32_t *__restrict__ hi0, uint32_t *__restrict__ cov,
 			    const uint32_t *__restrict__ depth, uint32_t *__restrict__ mpre, uint32_t *__restrict__ incnt,
-			    uint32_t *__restrict__ srccnt)
+			    uint32_t *__restrict__ srccnt, uint8_t *__restrict__ t_flags)
 {
 	uint32_t t = BIDX * blockDim.x + threadIdx.x;
 	if (t >= T)
@@ -87,6 +87,8 @@ __global__ void k_globalize(uint32_t T, const uint32_t *__restrict__ t_comp, con
 	if (l < n) {
 		uint32_t p = t_par[t], sz = t_size[t];
 		gpar[t] = p == NIL ? NIL : base + p;
+		if (p == NIL)
+			t_flags[t] |= TF_ROOT; // (k_tree_emit has set it already; a one-lane tree stage writes the two low fields only)
 		gsize[t] = sz;
 		// mirror pre-order (children visited in DESCENDING idx): the order brackets sit in a bracket list, because each
 		// child's list is spliced in front of its earlier siblings' (flubbles.cpp:586-588).  With q(v) = mpre(v) + v + size(v)
@@ -143,22 +145,26 @@ __global__ void k_hi0(uint32_t NB0, const uint32_t *__restrict__ b_src, const ui
 // bridge(v): no ordinary back edge out of subtree(v) reaches a proper ancestor of v (the bracket list of v would be
 // empty but for simplifying edges): the subtree sum of cov is zero
 // (four vertices a lane, 16-byte loads: see k_entry_list)
-__global__ void __launch_bounds__(TPB) k_bridge_flags(uint32_t T, const uint32_t *__restrict__ gsize, const uint32_t *__restrict__ gpar,
+__global__ void __launch_bounds__(TPB) k_bridge_flags(uint32_t T, const uint32_t *__restrict__ gsize, const uint8_t *__restrict__ t_flags,
 						       const uint32_t *__restrict__ pscov, uint4 *__restrict__ brec)
 {
 	// the flags go out as BITS, 64 to a record of the bit-rank directory (common.hpp): "how many bridge vertices in front of x"
 	// is then one 16-byte look-up into a 50 MB table -- until round 5 a byte per vertex, scanned into a 4-byte prefix per vertex
+	// ("has a parent" is the root bit of the tree stage's flag bytes, four of them in one word: the parents themselves are not read)
 	const uint32_t t0 = (BIDX * blockDim.x + threadIdx.x) * 4u;
 	uint32_t f = 0;
 	if (t0 + 4 <= T) {
-		const uint4 sz = *reinterpret_cast<const uint4 *>(gsize + t0), gp = *reinterpret_cast<const uint4 *>(gpar + t0);
+		const uint4 sz = *reinterpret_cast<const uint4 *>(gsize + t0);
+		const uint32_t tf = *reinterpret_cast<const uint32_t *>(t_flags + t0);
 		const uint4 pc = *reinterpret_cast<const uint4 *>(pscov + t0);
-		f = ((sz.x && gp.x != NIL && pscov[t0 + sz.x] == pc.x) ? 1u : 0u) | ((sz.y && gp.y != NIL && pscov[t0 + 1 + sz.y] == pc.y) ? 2u : 0u) |
-		    ((sz.z && gp.z != NIL && pscov[t0 + 2 + sz.z] == pc.z) ? 4u : 0u) | ((sz.w && gp.w != NIL && pscov[t0 + 3 + sz.w] == pc.w) ? 8u : 0u);
+		f = ((sz.x && !(tf & TF_ROOT) && pscov[t0 + sz.x] == pc.x) ? 1u : 0u) |
+		    ((sz.y && !(tf & (TF_ROOT << 8)) && pscov[t0 + 1 + sz.y] == pc.y) ? 2u : 0u) |
+		    ((sz.z && !(tf & (TF_ROOT << 16)) && pscov[t0 + 2 + sz.z] == pc.z) ? 4u : 0u) |
+		    ((sz.w && !(tf & (TF_ROOT << 24)) && pscov[t0 + 3 + sz.w] == pc.w) ? 8u : 0u);
 	} else {
 		for (uint32_t t = t0; t < T; t++) {
 			const uint32_t sz = gsize[t];
-			f |= ((sz && gpar[t] != NIL && pscov[t + sz] == pscov[t]) ? 1u : 0u) << (t - t0);
+			f |= ((sz && !(t_flags[t] & TF_ROOT) && pscov[t + sz] == pscov[t]) ? 1u : 0u) << (t - t0);
 		}
 	}
 	const uint32_t w0 = (BIDX * blockDim.x + (threadIdx.x & ~63u)) / 16u; // first record of this wave's 256 vertices
@@ -357,16 +363,19 @@ __global__ void __launch_bounds__(TPB) k_flag_tile_counts(uint32_t T, const uint
 // wave covers exactly one tile of 256 vertices and ranks its flags with eight ballots; no LDS, no barrier.
 // (the counts it places by -- ordinary back edges, capping vertices -- are read from the device: the kernel is launched
 // before the host has them, see the driver)
-// OC / SC: the width of the two bracket counts (ParWs::narrow_*)
-template <typename OC, typename SC>
+// OC / SC / IC: the width of the three bracket counts (ParWs::narrow_*).  With incnt as bytes a bracket that ends at a root is
+// not counted (every simplifying bracket; a capping bracket whose target carries the root bit), and a capping target whose
+// byte stands at 255 raises *ovf instead of counting (see ParWs::incnt8): nothing here is indexed by the counts.
+template <typename OC, typename SC, typename IC>
 __global__ void __launch_bounds__(TPB) k_bracket_extra(uint32_t T, uint32_t NB0_host, const uint32_t *__restrict__ nb0_dev, uint32_t ntiles,
 							uint32_t nb_cap, const uint8_t *__restrict__ capf,
 							const uint32_t *__restrict__ tcap, const uint8_t *__restrict__ simp,
 							const uint32_t *__restrict__ tsimp, const uint32_t *__restrict__ cap_tgt,
 							const RootOf root_of, uint32_t *__restrict__ b_src, uint32_t *__restrict__ b_tgt,
 							const OC *__restrict__ ordcnt, const uint32_t *__restrict__ gsize,
-							const uint32_t *__restrict__ mpre, uint32_t *__restrict__ incnt,
-							SC *__restrict__ srccnt)
+							const uint32_t *__restrict__ mpre, IC *__restrict__ incnt,
+							SC *__restrict__ srccnt, const uint8_t *__restrict__ t_flags,
+							uint32_t *__restrict__ ovf)
 {
 	const uint32_t NB0 = nb0_dev ? *nb0_dev : NB0_host, ncap = tcap[ntiles];
 	if ((uint64_t)NB0 + ncap + tsimp[ntiles] > nb_cap)
@@ -425,16 +434,22 @@ __global__ void __launch_bounds__(TPB) k_bracket_extra(uint32_t T, uint32_t NB0_
 			const uint32_t tg = cap_tgt[v];
 			b_src[q] = v;
 			b_tgt[q] = tg;
-			if (ordcnt)
-				atomicAdd(&incnt[tg], 1u);
+			if constexpr (sizeof(IC) == 1) {
+				if (!(t_flags[tg] & TF_ROOT) && incnt_add(incnt, tg) == 255u) {
+					incnt_take_back(incnt, tg);
+					atomicOr(ovf, 1u);
+				}
+			} else if (ordcnt) {
+				incnt_add(incnt, tg);
+			}
 		}
 		if (sm) {
 			const uint32_t q = NB0 + ncap + rs++;
 			const uint32_t root = root_of(v);
 			b_src[q] = v;
 			b_tgt[q] = root;
-			if (ordcnt)
-				atomicAdd(&incnt[root], 1u);
+			if (sizeof(IC) == 4 && ordcnt)
+				incnt_add(incnt, root);
 		}
 		// (dense path) brackets per source, at its place in the list order: known per vertex, no counting pass over the brackets
 		if (ordcnt && gsv[j])
@@ -1224,9 +1239,10 @@ static void for_each_span(ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 	pw.nb_cap = NB;
 	auto skip = [](auto **p) { *p = nullptr; };
 	take1(T + 2, pw.hi0, pw.mpre, pw.dlt, pw.incnt, pw.lsz);
-	if (groups & 1) { // the byte forms of the two bracket counts, inside the word arrays they stand in for (see ParWs)
+	if (groups & 1) { // the byte forms of the three bracket counts, inside the word arrays they stand in for (see ParWs)
 		pw.ordcnt8 = reinterpret_cast<uint8_t *>(pw.lsz);
 		pw.srccnt8 = reinterpret_cast<uint8_t *>(pw.dlt);
+		pw.incnt8 = reinterpret_cast<uint8_t *>(pw.incnt);
 	}
 	take1(NB + 2, pw.b_src, pw.b_tgt, pw.b_ord);
 	take1(V + 4, pw.sdl);
@@ -1394,14 +1410,14 @@ struct ClassPass {
 	// is needed.  A sequential tree stage works per component: its arrays are brought into that form here, and the
 	// hairpin report wants the per-vertex tables too.
 	const bool lean;
-	const bool narrow_oc, narrow_sc; // the bracket counts of the parallel tree stage as bytes (it wrote them in the form the caller chose, see ParWs)
+	const bool narrow_oc, narrow_sc, narrow_ic; // the bracket counts of the parallel tree stage as bytes (it wrote them in the form the caller chose, see ParWs)
 	bool black_only = false;	 // classes of the black tree edges only (place_brackets decides)
 	const RootOf root_of;
 	// ---- counts: ordinary / capping / simplifying back edges, all brackets, vertices that get a class
 	uint32_t NB0 = 0, ncap = 0, nsimp = 0, NB = 0, NC = 0;
 	const uint32_t ntiles; // tiles of k_bracket_extra
 	// ---- words on their way to the host
-	uint32_t *extra = nullptr; // [4] capping count | simplifying count | literal-rule flag | back edges of the tree stage
+	uint32_t *extra = nullptr; // [5] capping count | simplifying count | literal-rule flag | back edges of the tree stage | a byte of incnt8 overflowed
 	HostScratch::Token extra_ready = 0;
 	uint32_t *early = nullptr; // pass_summary's words as of the PVST count
 	HostScratch::Token early_ready = 0;
@@ -1412,7 +1428,7 @@ struct ClassPass {
 		: cs(cs_), sw(sw_), pw(pw_), tm(tm_), s(s_), side(side_), tail(tail_), alloc_result_block(alloc), v(class_views(pw_)), C(C_),
 		  V(sw_.V), T(2 * sw_.V + C_), S(n_stack), n_processed(n_processed_), dense_nb0(dense_nb0_), dense(dense_nb0_ >= 0),
 		  want_hp(sw_.hairpins != nullptr), lean(dense && !want_hp), narrow_oc(dense && pw_.narrow_ordcnt),
-		  narrow_sc(narrow_oc && pw_.narrow_srccnt), root_of{lean ? nullptr : pw_.t_root, cs_.voff, C_},
+		  narrow_sc(narrow_oc && pw_.narrow_srccnt), narrow_ic(narrow_sc && pw_.narrow_incnt), root_of{lean ? nullptr : pw_.t_root, cs_.voff, C_},
 		  ntiles((T + BX_TILE - 1) / BX_TILE)
 	{
 	}
@@ -1420,6 +1436,10 @@ struct ClassPass {
 	void scan8(const uint8_t *in, uint32_t *out, size_t n) const
 	{
 		scan_exclusive_u8(in, out, n, nullptr, nullptr, 0, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	}
+	void scan8pair(const uint8_t *in0, uint32_t *out0, size_t n0, const uint8_t *in1, uint32_t *out1, size_t n1) const
+	{
+		scan_exclusive_u8(in0, out0, n0, in1, out1, n1, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	}
 	void scan2(const uint32_t *in0, uint32_t *out0, size_t n0, const uint32_t *in1, uint32_t *out1, size_t n1) const
 	{
@@ -1443,7 +1463,7 @@ static void t_space_setup(ClassPass &P)
 	} else {
 		LAUNCH(k_tcomp_vertices, V, s, V, T, cs.ckey, cs.voff, pw.t_comp);
 		LAUNCH(k_globalize, T, s, T, pw.t_comp, cs.voff, sw.c_ntree, sw.t_par, sw.t_size, pw.gpar, pw.gsize, pw.t_root, pw.hi0,
-		       P.dense ? nullptr : pw.cov, sw.t_depth, pw.mpre, pw.incnt, P.narrow_sc ? nullptr : pw.dlt);
+		       P.dense ? nullptr : pw.cov, sw.t_depth, pw.mpre, pw.incnt, P.narrow_sc ? nullptr : pw.dlt, sw.t_flags);
 	}
 	// pw.comp_bad and pw.err are zeroed by the caller (zero_component_counters)
 	if (P.dense) { // the parallel tree stage already left the back edges in b_src / b_tgt
@@ -1456,8 +1476,17 @@ static void t_space_setup(ClassPass &P)
 	P.tm.end(7);
 }
 
+// the five words of ClassPass::extra on their way to the host, in one launch
+static void publish_extra(ClassPass &P)
+{
+	ParWs &pw = P.pw;
+	P.extra = pw.host->take<uint32_t>(5);
+	publish_words(P.extra, WordSrc{{P.v.tcap + P.ntiles, P.v.tsimp + P.ntiles, pw.err + PW_LITERAL_RULE, pw.err + PW_NB0, pw.err + PW_INCNT_OVF}}, 5, P.s);
+	P.extra_ready = pw.host->mark(P.s);
+}
+
 // ---- row D, first half: bridge flags, simplifying and capping vertices, and their counts on the way to the host.  Reads
-// hi0, the coverage counts (ordcnt8 / lsz and incnt, or cov), gsize, gpar; writes segA, brec, simp, capf, cap_tgt, br_list,
+// hi0, the coverage counts (ordcnt8 / lsz and incnt, or cov), gsize, the root bits of t_flags; writes segA, brec, simp, capf, cap_tgt, br_list,
 // tsimp, tcap and the words PW_N_BRIDGE, PW_LITERAL_RULE.
 static void bridge_and_capping(ClassPass &P)
 {
@@ -1469,13 +1498,15 @@ static void bridge_and_capping(ClassPass &P)
 	if (!P.dense)
 		LAUNCH(k_hi0, P.NB0, s, P.NB0, pw.b_src, pw.b_tgt, pw.hi0, pw.cov, nullptr);
 	seg_build(pw.segA, pw.hi0, T, s);
-	if (P.narrow_oc) // back edges leaving a vertex (counted by the tree stage) minus those arriving (counted by k_hi0)
+	if (P.narrow_ic) // back edges leaving a vertex minus those arriving (both counted by the tree stage; as bytes: not those that arrive at a root)
+		scan_exclusive_diff_u8_u8(pw.ordcnt8, pw.incnt8, v.pscov, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	else if (P.narrow_oc)
 		scan_exclusive_diff_u8_u32(pw.ordcnt8, pw.incnt, v.pscov, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	else if (P.dense)
 		scan_exclusive_diff_u32(pw.lsz, pw.incnt, v.pscov, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	else
 		P.scan(pw.cov, v.pscov, (size_t)T + 1);
-	KLAUNCH(k_bridge_flags, dim3(nblk(((size_t)T / 256 + 1) * 64)), dim3(TPB), 0, s, T, pw.gsize, pw.gpar, v.pscov, v.brec); // (whole waves: every record of [0, T] is written)
+	KLAUNCH(k_bridge_flags, dim3(nblk(((size_t)T / 256 + 1) * 64)), dim3(TPB), 0, s, T, pw.gsize, P.sw.t_flags, v.pscov, v.brec); // (whole waves: every record of [0, T] is written)
 	bitrank_build(v.brec, (size_t)T / 64 + 1, v.brec_cnt, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	uint32_t *n_br = pw.err + PW_N_BRIDGE;
 	KLAUNCH(k_hi_simp, dim3((unsigned)(((size_t)T + HS_VERTS - 1) / HS_VERTS)), dim3(TPB), 0, s, T, pw.gsize, v.brec, v.simp, P.want_hp ? pw.hpf : nullptr, v.capf, v.br_list,
@@ -1485,41 +1516,54 @@ static void bridge_and_capping(ClassPass &P)
 	// capping / simplifying vertices per tile of k_bracket_extra, scanned: [ntiles + 1] each, the totals in the last word
 	KLAUNCH(k_flag_tile_counts, dim3((ntiles + 1 + 15) / 16 + 1), dim3(TPB), 0, s, T, v.capf, v.simp, v.tcap, v.tsimp, ntiles);
 	scan_exclusive_u32_pair(v.tsimp, v.tsimp, (size_t)ntiles + 1, v.tcap, v.tcap, (size_t)ntiles + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	P.extra = pw.host->take<uint32_t>(4);
-	publish_words(P.extra, WordSrc{{v.tcap + ntiles, v.tsimp + ntiles, pw.err + PW_LITERAL_RULE, pw.err + PW_NB0}}, 4, s);
 	// The stream is not left idle while the host reads them (HostScratch::mark): the kernel that places the capping and
 	// simplifying brackets takes the counts from the device, and the scan behind it does not need them at all.
-	P.extra_ready = pw.host->mark(s);
+	// (byte in-counts: the words go out behind that kernel, which may raise the last of them; the scan still covers the read)
+	if (!P.narrow_ic)
+		publish_extra(P);
 }
 
 // ---- row D, second half: the capping and simplifying brackets join the ordinary ones (b_src / b_tgt, the two counts),
 // then, with the counts on the host, every bracket goes to its place in the bracket lists (tgtR, segB; b_val2 for the
-// hairpin report).  Decides black_only.
-static void place_brackets(ClassPass &P)
+// hairpin report).  Decides black_only.  False: the byte in-counts overflowed, the pass must be repeated with words.
+static bool place_brackets(ClassPass &P)
 {
 	ParWs &pw = P.pw;
 	const ClassViews &v = P.v;
 	hipStream_t s = P.s;
 	const uint32_t T = P.T;
-	auto bracket_extra = [&](auto *ordcnt, auto *sc) {
+	auto bracket_extra = [&](auto *ordcnt, auto *sc, auto *ic) {
 		using OC = std::remove_const_t<std::remove_pointer_t<decltype(ordcnt)>>;
 		using SC = std::remove_pointer_t<decltype(sc)>;
-		LAUNCH((k_bracket_extra<OC, SC>), ((size_t)T + 3) / 4, s, T, P.NB0, P.dense_nb0 == NB0_ON_DEVICE ? pw.err + PW_NB0 : nullptr, P.ntiles,
+		using IC = std::remove_pointer_t<decltype(ic)>;
+		LAUNCH((k_bracket_extra<OC, SC, IC>), ((size_t)T + 3) / 4, s, T, P.NB0, P.dense_nb0 == NB0_ON_DEVICE ? pw.err + PW_NB0 : nullptr, P.ntiles,
 		       (uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu), v.capf, v.tcap, v.simp, v.tsimp, pw.cap_tgt, P.root_of, pw.b_src, pw.b_tgt,
-		       ordcnt, pw.gsize, pw.mpre, pw.incnt, sc);
+		       ordcnt, pw.gsize, pw.mpre, ic, sc, P.sw.t_flags, pw.err + PW_INCNT_OVF);
 	};
-	if (P.narrow_sc)
-		bracket_extra((const uint8_t *)pw.ordcnt8, pw.srccnt8);
+	if (P.narrow_ic)
+		bracket_extra((const uint8_t *)pw.ordcnt8, pw.srccnt8, pw.incnt8);
+	else if (P.narrow_sc)
+		bracket_extra((const uint8_t *)pw.ordcnt8, pw.srccnt8, pw.incnt);
 	else if (P.narrow_oc)
-		bracket_extra((const uint8_t *)pw.ordcnt8, v.srccnt);
+		bracket_extra((const uint8_t *)pw.ordcnt8, v.srccnt, pw.incnt);
 	else
-		bracket_extra(P.dense ? (const uint32_t *)pw.lsz : nullptr, v.srccnt);
+		bracket_extra(P.dense ? (const uint32_t *)pw.lsz : nullptr, v.srccnt, pw.incnt);
+	if (P.narrow_ic)
+		publish_extra(P);
 	// ranks inside every source and the counts per source are known: place directly
-	if (P.narrow_sc)
+	if (P.narrow_ic)
+		P.scan8pair(pw.incnt8, pw.psin, (size_t)T + 1, pw.srccnt8, v.bstart, (size_t)T + 1);
+	else if (P.narrow_sc)
 		scan_exclusive_u32_u8_pair(pw.incnt, pw.psin, (size_t)T + 1, pw.srccnt8, v.bstart, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	else if (P.dense)
 		P.scan2(pw.incnt, pw.psin, (size_t)T + 1, v.srccnt, v.bstart, (size_t)T + 1);
 	pw.host->wait(P.extra_ready);
+	// A byte of incnt8 would have passed 255 (capping brackets that share a target, which no gate bounds): psin is not the scan
+	// of the true counts, and nothing that indexes with it has been launched.  The caller repeats the pass with words.
+	if (P.extra[4]) {
+		P.tm.end(30);
+		return false;
+	}
 	if (P.dense_nb0 == NB0_ON_DEVICE) {
 		P.NB0 = P.extra[3];
 		if (P.NB0 > pw.nb_cap)
@@ -1558,6 +1602,7 @@ static void place_brackets(ClassPass &P)
 	}
 	seg_build(pw.segB, pw.tgtR, NB, s);
 	P.NC = P.black_only ? P.V : T;
+	return true;
 }
 
 // ---- classes of the black tree vertices, in stack order, with rows E and F folded in.  Row E goes first (it only needs
@@ -1787,7 +1832,7 @@ static void emit_and_copy(ClassPass &P)
 	P.tm.end(12 + 3 * 22);
 }
 
-void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint32_t n_processed, uint32_t n_stack,
+bool run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint32_t n_processed, uint32_t n_stack,
 		     int64_t dense_nb0, const std::function<void *(size_t)> &alloc_result_block, StageTimer &tm, hipStream_t s,
 		     const SideStream &side, PassTail &tail)
 {
@@ -1798,7 +1843,8 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	pw.T = P.T;
 	t_space_setup(P);
 	bridge_and_capping(P);
-	place_brackets(P);
+	if (!place_brackets(P))
+		return false;
 	if (P.black_only)
 		classes_black_only(P);
 	else
@@ -1806,6 +1852,7 @@ void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	stack_directories(P);
 	laminar_and_levels(P);
 	emit_and_copy(P);
+	return true;
 }
 
 // class ids of the stack entries after a black-only pass (debug hooks): the runs of the sorted order, numbered

@@ -44,8 +44,23 @@ enum PassWord : uint32_t {
 	PW_N_X = 11,	     // compact_flagged_u8: stack entries with a crossed interval -> k_resolve_crossings, povu_hip_last_crossings
 	PW_N_CROSSED = 12,   // k_resolve_crossings: crossings resolved in place -> povu_hip_last_crossings
 	PW_RANK_OVF = 13,    // list_rank_splitters (the pre-order ranking): records whose partial sum left its 16 bits (its fallback kernel)
-	PASS_WORDS = 16	     // words carved and cleared (1, 3, 14, 15: unused)
+	PW_INCNT_OVF = 14,   // k_bracket_extra: a byte of incnt8 would have passed 255 -> the host (place_brackets: the pass is repeated with words)
+	PASS_WORDS = 16	     // words carved and cleared (1, 3, 15: unused)
 };
+
+// One more bracket ends at tree vertex t; returns the count in front of it.  A byte is incremented by a 32-bit atomic add of
+// 1 << 8 (t & 3) on its aligned word (ParWs::incnt8 is 16-byte aligned): no carry leaves a byte that stays below 256.
+__device__ __forceinline__ uint32_t incnt_add(uint32_t *incnt, uint32_t t) { return atomicAdd(&incnt[t], 1u); }
+__device__ __forceinline__ uint32_t incnt_add(uint8_t *incnt, uint32_t t)
+{
+	const unsigned sh = 8u * (t & 3u);
+	return (atomicAdd(reinterpret_cast<uint32_t *>(incnt + (t & ~3u)), 1u << sh) >> sh) & 0xFFu;
+}
+// ... and taken back (the add found the byte at 255)
+__device__ __forceinline__ void incnt_take_back(uint8_t *incnt, uint32_t t)
+{
+	atomicSub(reinterpret_cast<uint32_t *>(incnt + (t & ~3u)), 1u << (8u * (t & 3u)));
+}
 
 // The outcome of a pass as k_summary writes it into page-locked host memory, one view for the kernel and every reader:
 // ERR_WORDS error words, then bad[C], status[C], npvst[C], nbry[C], doff[C+1].
@@ -88,6 +103,17 @@ struct ParWs {
 	// links any side has; srccnt <= ordcnt + 2); otherwise the word kernels run.
 	uint8_t *ordcnt8, *srccnt8;
 	bool narrow_ordcnt = false, narrow_srccnt = false; // in (srccnt only together with ordcnt)
+	// The third count, incnt (brackets that END at a tree vertex), as bytes [T+2] in the first quarter of incnt itself: cleared by
+	// k_tree_emit, counted into by k_back_edges / k_bracket_extra (incnt_add), last read by the scan of place_brackets; the
+	// next writer of those words is k_tree_emit of the next pass.  The byte form leaves out every bracket that ends at a ROOT
+	// -- the tips' back edges and the simplifying brackets, millions on one word -- because nothing reads a root's count: the
+	// two scans of it are only ever read as differences over the subtree of a vertex WITH a parent (pscov in k_bridge_flags,
+	// psin in k_top_bracket), and a root is in no such subtree.  Away from the roots the ordinary back edges that end at a
+	// vertex are at most the links of its side, which the gate of narrow_ordcnt bounds; the capping brackets that share a
+	// target are not bounded by anything, so k_bracket_extra looks at the byte its add returns, takes the add back at 255 and
+	// raises PW_INCNT_OVF: place_brackets then gives up and the caller repeats the pass with words.
+	uint8_t *incnt8;
+	bool narrow_incnt = false; // in (only together with the other two)
 	uint32_t *sdl;		 // [V+2] row E's difference array (k_shift_delta) when the tree stage's emit kernel already filled it
 	bool sdl_filled = false; // ... which it says here
 	uint32_t *vals_t, *vals_t2;
@@ -171,8 +197,10 @@ void par_carve(Arena &ar, ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 // capping / simplifying counts, one host synchronisation instead of two).
 // alloc_result_block(total) returns the device view of a page-locked host block laid out a | z | parent | a_or |
 // z_or (each padded to 64 B) for `total` PVST vertices; the emit kernels write into it.
+// Returns false when the pass kept incnt as bytes (ParWs::narrow_incnt) and one of them would have passed 255: nothing
+// behind the placing of the brackets has run, and the caller runs the tree stage and this again with narrow_incnt off.
 static constexpr int64_t NB0_ON_DEVICE = int64_t(1) << 40;
-void run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint32_t n_processed, uint32_t n_stack,
+bool run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint32_t n_processed, uint32_t n_stack,
 		     int64_t dense_nb0, const std::function<void *(size_t)> &alloc_result_block, StageTimer &tm, hipStream_t s,
 		     const SideStream &side, PassTail &tail);
 

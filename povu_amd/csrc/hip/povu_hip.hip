@@ -888,7 +888,23 @@ static int64_t parallel_rows(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, c
 	pw.cproc_ps = sw.tables + 2 * ((size_t)C + 1);
 	ctx->tw.cproc = sw.tables + 3 * ((size_t)C + 1);
 	pw.soff = sw.tables + 4 * ((size_t)C + 1);
-	pw.narrow_ordcnt = pw.narrow_srccnt = false;
+	pw.narrow_ordcnt = pw.narrow_srccnt = pw.narrow_incnt = false;
+	// Bracket counts per tree vertex as bytes (ParWs::ordcnt8 / srccnt8 / incnt8) when none can reach 256: a vertex sends at most
+	// one back edge per link of its side (one, to the root, from a side without links), and a position of the bracket list
+	// holds at most a capping and a simplifying bracket more.  Otherwise -- a hub, a fat side of the dense re-index path -- the
+	// word kernels run.  The brackets that END at a vertex away from the roots are bounded by the same gate but for the
+	// capping brackets that share a target: the class stage says when a byte of incnt8 would have overflowed, and the tree
+	// and class stages then run again with all three counts as words (wide_again).
+	// POVU_HIP_WIDE_COUNTS (A/B hook, read per pass): 1 = words for all three, 2 = words for srccnt and incnt, 3 = for incnt only.
+	auto tree_stage = [&](bool wide_again) {
+		const char *ev = getenv("POVU_HIP_WIDE_COUNTS");
+		const int wide = wide_again ? 1 : ev ? atoi(ev) : 0;
+		const bool fits = std::max<uint32_t>(gstats[0], 1u) + 2u <= 255u;
+		pw.narrow_ordcnt = fits && wide != 1;
+		pw.narrow_srccnt = pw.narrow_ordcnt && wide != 2;
+		pw.narrow_incnt = pw.narrow_srccnt && wide != 3;
+		dense_nb0 = run_parallel_tree(ctx->cs, sw, pw, ctx->tw, C, gstats[0], p.big_class_dfs, p.sparse_splitters, tm, s);
+	};
 	if (p.seq_tree) {
 		lanes.init(s);
 		tm.begin("tree_seq");
@@ -896,16 +912,7 @@ static int64_t parallel_rows(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, c
 		launch_seq_components(sw, s);
 		tm.end(1);
 	} else {
-		// Bracket counts per tree vertex as bytes (ParWs::ordcnt8 / srccnt8) when none can reach 256: a vertex sends at most one
-		// back edge per link of its side (one, to the root, from a side without links), and a position of the bracket list holds
-		// at most a capping and a simplifying bracket more.  Otherwise -- a hub, a fat side of the dense re-index path -- the
-		// word kernels run.  POVU_HIP_WIDE_COUNTS (A/B hook, read per pass): 1 = words for both, 2 = words for srccnt only.
-		const char *ev = getenv("POVU_HIP_WIDE_COUNTS");
-		const int wide = ev ? atoi(ev) : 0;
-		const bool fits = std::max<uint32_t>(gstats[0], 1u) + 2u <= 255u;
-		pw.narrow_ordcnt = fits && wide != 1;
-		pw.narrow_srccnt = pw.narrow_ordcnt && wide != 2;
-		dense_nb0 = run_parallel_tree(ctx->cs, sw, pw, ctx->tw, C, gstats[0], p.big_class_dfs, p.sparse_splitters, tm, s);
+		tree_stage(false);
 	}
 	pw.all_vertex_classes = p.all_vertex_classes;
 	pw.check_laminar = p.check_laminar;
@@ -920,7 +927,14 @@ static int64_t parallel_rows(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, c
 		HIP_CHECK(hipHostGetDevicePointer(&dev, f.alloc(total).p, 0));
 		return dev;
 	};
-	run_parallel_dg(ctx->cs, sw, pw, C, t.n_processed, t.n_stack, dense_nb0, alloc_result_block, tm, s, ctx->side, out.tail);
+	if (!run_parallel_dg(ctx->cs, sw, pw, C, t.n_processed, t.n_stack, dense_nb0, alloc_result_block, tm, s, ctx->side, out.tail)) {
+		// a byte of incnt8 overflowed (only a pass with narrow_incnt says so): counters cleared, both stages again with words
+		ctx->wide_repeats++;
+		zero_component_counters(sw, C, pw.comp_bad, pw.err, s);
+		tree_stage(true);
+		if (!run_parallel_dg(ctx->cs, sw, pw, C, t.n_processed, t.n_stack, dense_nb0, alloc_result_block, tm, s, ctx->side, out.tail))
+			throw HipError("class stage: the word form of the bracket counts reported an overflow (internal)");
+	}
 	out.stack_export_pending = true;
 	if (p.redo_odd) // (tests: flag every other component as if its stack were not laminar)
 		mark_odd_u32(pw.comp_bad, C, s);
@@ -1308,6 +1322,7 @@ extern "C" povu_hip_forest *povu_hip_decompose(povu_hip_ctx *ctx, const povu_hip
 		stage_times(ctx, tm, *f);
 		ctx->last = LastPass{true, p, C, out.nbad, out.mixed, out.redo_pvst_only, out.stack_export_pending};
 		ctx->last.narrow_counts = !p.all_seq && !p.seq_tree && ctx->pw.narrow_ordcnt;
+		ctx->last.narrow_forms = !ctx->last.narrow_counts ? 0 : 1 | (ctx->pw.narrow_srccnt ? 2 : 0) | (ctx->pw.narrow_incnt ? 4 : 0);
 		if (p.world == 1 && ctx->shard_comp_ids.empty()) { // (povu_hip_forest_walks: a forest of the whole resident graph)
 			f->walk_ctx = ctx;
 			f->walk_gen = g.gen;
@@ -1654,8 +1669,9 @@ extern "C" uint64_t povu_hip_last_links_processed(const povu_hip_ctx *ctx) { ret
 
 extern "C" int povu_hip_last_narrow_counts(const povu_hip_ctx *ctx)
 {
-	return ctx && ctx->last.valid && ctx->last.narrow_counts ? 1 : 0;
+	return ctx && ctx->last.valid && ctx->last.narrow_counts ? ctx->last.narrow_forms : 0;
 }
+extern "C" uint64_t povu_hip_wide_repeats(const povu_hip_ctx *ctx) { return ctx ? ctx->wide_repeats : 0; }
 
 extern "C" int povu_hip_last_black_only_classes(const povu_hip_ctx *ctx)
 {

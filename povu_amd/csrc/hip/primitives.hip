@@ -2,7 +2,8 @@
 // of (key, value) pairs, all hand-written.
 //
 // The u32 scans (sum / max / xor) share one description of their input and one way to read it.  A ScanSrc says whether a
-// job's elements are words or single BYTES, and whether a word array `sub` is subtracted element by element (sums only).
+// job's elements are words or single BYTES, and whether a word array `sub` -- or, under a byte job, a byte array `sub8` -- is
+// subtracted element by element (sums only).
 // sc_load<Q> loads Q sub-tiles of SC_ITEMS consecutive elements a lane: whole sub-tiles with 16-byte (words) or 8-byte
 // (bytes) loads that are ALL issued before the first is used, anything else element by element with zeros behind the end;
 // the byte unpack (sc_unpack4) and the `- sub` step exist there and nowhere else.  Q = 1 is a tile of the two-launch form
@@ -23,15 +24,21 @@ static constexpr int SC_TPB = 256, SC_WAVES = SC_TPB / 64, SC_ITEMS = 8, SC_TILE
 
 // what a job scans: words, or one BYTE per element (flags, small counts -- a quarter of the reads); with `sub` (sum scans)
 // the element is in[i] - sub[i]
+// (sub8: the subtrahend as BYTES, for a byte job only; the difference still wraps mod 2^32 as with words)
 struct ScanSrc {
 	const void *in;
 	const uint32_t *sub;
 	bool bytes;
+	const uint8_t *sub8 = nullptr;
 	static ScanSrc words(const uint32_t *p, const uint32_t *sub = nullptr) { return ScanSrc{p, sub, false}; }
 	static ScanSrc of_bytes(const uint8_t *p, const uint32_t *sub = nullptr) { return ScanSrc{p, sub, true}; }
+	static ScanSrc bytes_minus_bytes(const uint8_t *p, const uint8_t *sub8) { return ScanSrc{p, nullptr, true, sub8}; }
 	__device__ __forceinline__ const uint32_t *w() const { return static_cast<const uint32_t *>(in); }
 	__device__ __forceinline__ const uint8_t *b() const { return static_cast<const uint8_t *>(in); }
-	__device__ __forceinline__ uint32_t operator[](size_t i) const { return (bytes ? (uint32_t)b()[i] : w()[i]) - (sub ? sub[i] : 0u); }
+	__device__ __forceinline__ uint32_t operator[](size_t i) const
+	{
+		return (bytes ? (uint32_t)b()[i] : w()[i]) - (sub ? sub[i] : sub8 ? (uint32_t)sub8[i] : 0u);
+	}
 };
 // One scan job; a launch carries one or two of them (blockIdx.y picks) so that independent scans that
 // are due at the same point of the pass share their two launches.
@@ -94,6 +101,15 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_partials(const ScanJobs jobs)
 					const uint4 c = *reinterpret_cast<const uint4 *>(sub + i + 4 * q);
 					acc -= c.x + c.y + c.z + c.w;
 				}
+			} else if (S.sub8) {
+				const uint4 c = *reinterpret_cast<const uint4 *>(S.sub8 + i);
+				const uint32_t cw[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+				for (int q = 0; q < 4; q++) {
+					uint32_t v[4];
+					sc_unpack4(cw[q], v);
+					acc -= sc_fold4<0>(v);
+				}
 			}
 		}
 	} else {
@@ -155,6 +171,18 @@ __device__ __forceinline__ void sc_load(const ScanSrc &S, size_t t0, size_t b1, 
 			for (int q = 0; q < Q; q++) {
 				const uint4 c = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE), d = *reinterpret_cast<const uint4 *>(sub + q * SC_TILE + 4);
 				sc_minus4(v[q], c), sc_minus4(v[q] + 4, d);
+			}
+		} else if (S.sub8) {
+			const uint8_t *__restrict__ sub8 = S.sub8 + e0;
+			uint2 c[Q];
+#pragma unroll
+			for (int q = 0; q < Q; q++)
+				c[q] = *reinterpret_cast<const uint2 *>(sub8 + q * SC_TILE);
+#pragma unroll
+			for (int q = 0; q < Q; q++) {
+				uint32_t m[SC_ITEMS];
+				sc_unpack4(c[q].x, m), sc_unpack4(c[q].y, m + 4);
+				sc_minus4(v[q], make_uint4(m[0], m[1], m[2], m[3])), sc_minus4(v[q] + 4, make_uint4(m[4], m[5], m[6], m[7]));
 			}
 		}
 	} else if constexpr (Q > 1) { // the job's last tile: sub-tile by sub-tile
@@ -414,6 +442,11 @@ void scan_exclusive_diff_u8_u32(const uint8_t *in8, const uint32_t *sub, uint32_
 				hipStream_t s)
 {
 	scan_run<0>({ScanSrc::of_bytes(in8, sub), out, n}, SC_NONE, tmp, tmp_bytes, s);
+}
+void scan_exclusive_diff_u8_u8(const uint8_t *in8, const uint8_t *sub8, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes,
+			       hipStream_t s)
+{
+	scan_run<0>({ScanSrc::bytes_minus_bytes(in8, sub8), out, n}, SC_NONE, tmp, tmp_bytes, s);
 }
 // byte inputs: one or two independent jobs in the same launches (in1 may be null)
 void scan_exclusive_u8(const uint8_t *in0, uint32_t *out0, size_t n0, const uint8_t *in1, uint32_t *out1, size_t n1, void *tmp,

@@ -8,6 +8,8 @@ namespace povu_hip
 // tree vertex flags
 #define TF_TYPE_MASK 3u /* 0 = l, 1 = r, 2 = dummy */
 #define TF_BLACK 4u	/* parent tree edge is black */
+#define TF_ROOT 8u	/* no tree parent (t_par = NIL): set by k_tree_emit, or by k_globalize behind a one-lane tree stage, for \
+			   k_bridge_flags -- every other reader masks the bits above */
 
 #define SEQ_STAGE_TREE 1u
 #define SEQ_STAGE_CLASSES 2u

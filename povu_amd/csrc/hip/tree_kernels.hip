@@ -1521,8 +1521,9 @@ __global__ void k_events(uint32_t V, const uint2 *__restrict__ dps, const uint32
 }
 
 // ------------------------------------------------------------------ 8. tree arrays + back edges
-// OC / SC: the width of ordcnt / srccnt (uint8_t when no count of the pass can reach 256, see ParWs::narrow_ordcnt / narrow_srccnt)
-template <typename OC, typename SC>
+// OC / SC / IC: the width of ordcnt / srccnt / incnt (uint8_t when no count of the pass can reach 256, see ParWs::narrow_ordcnt /
+// narrow_srccnt / narrow_incnt)
+template <typename OC, typename SC, typename IC>
 __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks R, const uint8_t *__restrict__ merged,
 			    const uint2 *__restrict__ dps, const uint32_t *__restrict__ ckey,
 			    const uint32_t *__restrict__ cproc, const uint32_t *__restrict__ voff,
@@ -1531,7 +1532,7 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 			    uint32_t *__restrict__ t_size, uint32_t *__restrict__ t_depth, uint32_t *__restrict__ side_tidx,
 			    uint32_t C, uint32_t *__restrict__ c_ntree, OC *__restrict__ ordcnt, uint32_t *__restrict__ hi0,
 			    uint32_t *__restrict__ mpre, SC *__restrict__ srccnt, uint32_t *__restrict__ sdl,
-			    uint32_t *__restrict__ incnt)
+			    IC *__restrict__ incnt)
 {
 	// The class stage works on the tree in T-space (component c owns [2 voff[c] + c, 2 voff[c+1] + c]) and reads, per tree
 	// vertex: t_size (0 marks a slot without a vertex), t_par (NIL = root), mpre = mirror pre-order (children visited in
@@ -1541,7 +1542,7 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 	// every vertex later: only the slots without a vertex are cleared here).  All of it is written right here.
 	uint32_t S = BIDX * blockDim.x + threadIdx.x;
 	// incnt (brackets that end at a vertex: k_back_edges counts into it) is cleared here on the way -- every T-space slot gets
-	// its size from exactly one lane of this kernel, and its zero with it: no fill kernel over 8 * 10^8 bytes
+	// its size from exactly one lane of this kernel, and its zero with it: no fill kernel over 8 * 10^8 bytes (2 * 10^8 as bytes)
 	if (S == 0) {
 		const uint32_t T = 2 * (nS >> 1) + C;
 		hi0[T] = NIL;
@@ -1560,7 +1561,7 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 			c_ntree[S] = Nr + hr;
 			if (hr) {
 				t_gid[tr] = NIL;
-				t_flags[tr] = 2;
+				t_flags[tr] = 2 | TF_ROOT;
 				t_par[tr] = NIL;
 				t_size[tr] = Nr + 1;
 				incnt[tr] = 0;
@@ -1587,7 +1588,7 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 		const uint32_t t = tb + 2 * (g - v0);
 		store2_unaligned(t_size + t, 0u, 0u);
 		zero2(srccnt + t);
-		store2_unaligned(incnt + t, 0u, 0u);
+		zero2(incnt + t);
 		*reinterpret_cast<uint2 *>(side_tidx + 2 * g) = make_uint2(NIL, NIL);
 		return;
 	}
@@ -1616,11 +1617,11 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 	const uint32_t l = hd + pre_e, t = tb + l; // e sits at t, o at t + 1
 	const uint32_t gid = gid_s[g];
 	store2_unaligned(t_gid + t, gid, gid);
-	t_flags[t] = (uint8_t)(e & 1u);
+	t_flags[t] = (uint8_t)((e & 1u) | (par_e == NIL ? TF_ROOT : 0u)); // (no parent and no dummy root: the tree's root; k_bridge_flags reads the bit)
 	t_flags[t + 1] = (uint8_t)((o & 1u) | TF_BLACK);
 	store2_unaligned(t_par + t, par_e, l); // (o's parent is e)
 	store2_unaligned(t_size + t, size_e, size_o);
-	store2_unaligned(incnt + t, 0u, 0u);
+	zero2(incnt + t);
 	if (t_depth) // (only the hairpin report's T-space setup reads the depths again)
 		store2_unaligned(t_depth + t, depth_e + hd, depth_e + 1 + hd);
 	store2_unaligned(mpre + t, tb + (depth_e + hd) + (Nh + hd) - l - size_e, tb + (depth_e + 1 + hd) + (Nh + hd) - (l + 1) - size_o);
@@ -1652,14 +1653,15 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 #define POVU_BE_ITER 8
 #endif
 static constexpr uint32_t BE_ITER = POVU_BE_ITER, BE_SIDES = TPB * BE_ITER;
-template <bool EMIT>
+// IC: the width of incnt.  The byte form does not count the back edges that end at the root (ParWs::incnt8)
+template <bool EMIT, typename IC>
 __device__ __forceinline__ uint32_t side_back_edges(uint32_t S, uint32_t p, uint32_t at,
 						    const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
 						    const uint2 *__restrict__ dps, const uint32_t *__restrict__ side_tidx,
 						    const uint32_t *__restrict__ ckey, const uint32_t *__restrict__ voff,
 						    const uint32_t *__restrict__ t_par, uint32_t *__restrict__ b_src,
 						    uint32_t *__restrict__ b_tgt, uint32_t *__restrict__ b_ord,
-						    const uint8_t *__restrict__ dupflag, uint32_t *__restrict__ incnt, uint32_t &highest,
+						    const uint8_t *__restrict__ dupflag, IC *__restrict__ incnt, uint32_t &highest,
 						    uint32_t *first2)
 {
 	uint32_t n = 0;
@@ -1670,7 +1672,8 @@ __device__ __forceinline__ uint32_t side_back_edges(uint32_t S, uint32_t p, uint
 			b_src[at + n] = p;
 			b_tgt[at + n] = tgt;
 			b_ord[at + n] = n; // later pushed = nearer the top of the bracket list
-			atomicAdd(&incnt[tgt], 1u); // brackets that end at tgt
+			if (sizeof(IC) == 4 || tgt != root)
+				incnt_add(incnt, tgt); // brackets that end at tgt
 		} else {
 			highest = min(highest, tgt);
 			if (n < 2)
@@ -1721,14 +1724,14 @@ __device__ __forceinline__ uint32_t side_back_edges(uint32_t S, uint32_t p, uint
 	}
 	return n;
 }
-template <typename OC>
+template <typename OC, typename IC>
 __global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
 						     const uint2 *__restrict__ dps, const uint32_t *__restrict__ side_tidx,
 						     const uint32_t *__restrict__ ckey, const uint32_t *__restrict__ voff,
 						     const uint32_t *__restrict__ t_par, uint32_t *__restrict__ total_out,
 						     uint32_t *__restrict__ b_src, uint32_t *__restrict__ b_tgt,
 						     uint32_t *__restrict__ b_ord, const uint8_t *__restrict__ dupflag,
-						     OC *__restrict__ ordcnt, uint32_t *__restrict__ hi0, uint32_t *__restrict__ incnt,
+						     OC *__restrict__ ordcnt, uint32_t *__restrict__ hi0, IC *__restrict__ incnt,
 						     uint32_t cap)
 {
 	const uint32_t S0 = BIDX * BE_SIDES + threadIdx.x;
@@ -1741,7 +1744,7 @@ __global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t 
 		uint32_t k = 0;
 		if (p != NIL) {
 			uint32_t highest = NIL;
-			k = side_back_edges<false>(S, p, 0, loff, ladj, dps, side_tidx, ckey, voff, t_par, b_src, b_tgt, b_ord, dupflag, incnt, highest,
+			k = side_back_edges<false, IC>(S, p, 0, loff, ladj, dps, side_tidx, ckey, voff, t_par, b_src, b_tgt, b_ord, dupflag, incnt, highest,
 						   first2[it][threadIdx.x]);
 			// what the class stage needs per tree vertex, known right here: its ordinary brackets (p's stretch of the
 			// bracket list is sized with it) and the highest vertex they reach (hi_0, flubbles.cpp:515-519)
@@ -1767,17 +1770,23 @@ __global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t 
 			continue;
 		const uint32_t S = S0 + it * TPB, p = side_tidx[S];
 		if (k <= 2) {
+			uint32_t root = NIL; // (byte form: the root of p's tree, whose count nobody reads)
+			if constexpr (sizeof(IC) == 1) {
+				const uint32_t c = ckey[S >> 1];
+				root = 2 * voff[c] + c;
+			}
 			for (uint32_t j = 0; j < k; j++) {
 				const uint32_t tgt = first2[it][threadIdx.x][j];
 				b_src[at + j] = p;
 				b_tgt[at + j] = tgt;
 				b_ord[at + j] = j;
-				atomicAdd(&incnt[tgt], 1u);
+				if (tgt != root)
+					incnt_add(incnt, tgt);
 			}
 			at += k;
 		} else {
 			uint32_t unused = NIL;
-			at += side_back_edges<true>(S, p, at, loff, ladj, dps, side_tidx, ckey, voff, t_par, b_src, b_tgt, b_ord, dupflag, incnt, unused,
+			at += side_back_edges<true, IC>(S, p, at, loff, ladj, dps, side_tidx, ckey, voff, t_par, b_src, b_tgt, b_ord, dupflag, incnt, unused,
 						    nullptr);
 		}
 	}
@@ -2235,19 +2244,22 @@ static void emit_tree(TreePass &P)
 	TreeWs &tw = P.tw;
 	P.tm.begin("tree_emit");
 	// (incnt: k_back_edges counts the brackets that end at a vertex into it)
-	auto tree_emit = [&](auto *ordcnt, auto *srccnt) {
+	auto tree_emit = [&](auto *ordcnt, auto *srccnt, auto *incnt) {
 		using OC = std::remove_pointer_t<decltype(ordcnt)>;
 		using SC = std::remove_pointer_t<decltype(srccnt)>;
-		LAUNCH((k_tree_emit<OC, SC>), std::max(P.V, P.C), P.s, P.nS, tw.evt, P.evr, P.v.merged, tw.dps, cs.ckey, tw.cproc, cs.voff, P.start_key, cs.gid_s, sw.t_gid,
+		using IC = std::remove_pointer_t<decltype(incnt)>;
+		LAUNCH((k_tree_emit<OC, SC, IC>), std::max(P.V, P.C), P.s, P.nS, tw.evt, P.evr, P.v.merged, tw.dps, cs.ckey, tw.cproc, cs.voff, P.start_key, cs.gid_s, sw.t_gid,
 		       sw.t_flags, sw.t_par, sw.t_size, (sw.hairpins || sw.want_depth) ? sw.t_depth : nullptr, tw.side_tidx, P.C, sw.c_ntree, ordcnt,
-		       pw.hi0, pw.mpre, srccnt, pw.sdl, pw.incnt);
+		       pw.hi0, pw.mpre, srccnt, pw.sdl, incnt);
 	};
-	if (pw.narrow_ordcnt && pw.narrow_srccnt)
-		tree_emit(pw.ordcnt8, pw.srccnt8);
+	if (pw.narrow_ordcnt && pw.narrow_srccnt && pw.narrow_incnt)
+		tree_emit(pw.ordcnt8, pw.srccnt8, pw.incnt8);
+	else if (pw.narrow_ordcnt && pw.narrow_srccnt)
+		tree_emit(pw.ordcnt8, pw.srccnt8, pw.incnt);
 	else if (pw.narrow_ordcnt)
-		tree_emit(pw.ordcnt8, pw.dlt);
+		tree_emit(pw.ordcnt8, pw.dlt, pw.incnt);
 	else
-		tree_emit(pw.lsz, pw.dlt);
+		tree_emit(pw.lsz, pw.dlt, pw.incnt);
 	pw.sdl_filled = true;
 }
 
@@ -2279,15 +2291,17 @@ static void back_edges(TreePass &P)
 	const CompState &cs = P.cs;
 	ParWs &pw = P.pw;
 	TreeWs &tw = P.tw;
-	auto launch = [&](auto *ordcnt) {
-		KLAUNCH((k_back_edges<std::remove_pointer_t<decltype(ordcnt)>>), dim3((P.nS + BE_SIDES - 1) / BE_SIDES), dim3(TPB), 0, P.s, P.nS, cs.loff, cs.ladj, tw.dps, tw.side_tidx, cs.ckey,
-			cs.voff, P.sw.t_par, pw.err + PW_NB0, pw.b_src, pw.b_tgt, pw.b_ord, P.dupflag, ordcnt, pw.hi0, pw.incnt,
+	auto launch = [&](auto *ordcnt, auto *incnt) {
+		KLAUNCH((k_back_edges<std::remove_pointer_t<decltype(ordcnt)>, std::remove_pointer_t<decltype(incnt)>>), dim3((P.nS + BE_SIDES - 1) / BE_SIDES), dim3(TPB), 0, P.s, P.nS, cs.loff, cs.ladj, tw.dps, tw.side_tidx, cs.ckey,
+			cs.voff, P.sw.t_par, pw.err + PW_NB0, pw.b_src, pw.b_tgt, pw.b_ord, P.dupflag, ordcnt, pw.hi0, incnt,
 			(uint32_t)std::min<size_t>(pw.nb_cap, 0xFFFFFFFFu));
 	};
-	if (pw.narrow_ordcnt)
-		launch(pw.ordcnt8);
+	if (pw.narrow_ordcnt && pw.narrow_srccnt && pw.narrow_incnt)
+		launch(pw.ordcnt8, pw.incnt8);
+	else if (pw.narrow_ordcnt)
+		launch(pw.ordcnt8, pw.incnt);
 	else
-		launch(pw.lsz);
+		launch(pw.lsz, pw.incnt);
 	P.tm.end(6);
 }
 

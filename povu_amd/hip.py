@@ -24,7 +24,7 @@ class GuardBandError(RuntimeError):
 
 
 # ops of povu_hip_debug_scan (include/povu_hip.h)
-SCAN_SUM, SCAN_MAX, SCAN_U64, SCAN_U8, SCAN_DIFF, SCAN_XOR_PAIR, SCAN_XOR_U128, SCAN_DIFF_U8, SCAN_MIXED_PAIR = range(9)
+SCAN_SUM, SCAN_MAX, SCAN_U64, SCAN_U8, SCAN_DIFF, SCAN_XOR_PAIR, SCAN_XOR_U128, SCAN_DIFF_U8, SCAN_MIXED_PAIR, SCAN_DIFF_U8_U8 = range(10)
 SCAN_IN_PLACE, SCAN_N_DEV = 0x100, 0x200
 # query kinds of povu_hip_debug_segtree
 SEG_MIN, SEG_FIRST_LESS, SEG_LAST_LESS = range(3)
@@ -287,6 +287,8 @@ def load_lib():
                                       C.c_void_p, C.c_void_p]
     l.povu_hip_last_narrow_counts.restype = C.c_int
     l.povu_hip_last_narrow_counts.argtypes = [C.c_void_p]
+    l.povu_hip_wide_repeats.restype = C.c_uint64
+    l.povu_hip_wide_repeats.argtypes = [C.c_void_p]
     l.povu_hip_last_black_only_classes.restype = C.c_int
     l.povu_hip_last_black_only_classes.argtypes = [C.c_void_p]
     l.povu_hip_last_crossings.restype = C.c_int
@@ -1209,6 +1211,17 @@ class HipDecomposer:
         self._prim_rc(rc, "scan_exclusive_diff_u8_u32")
         return out
 
+    def debug_scan_diff_u8_u8(self, a, sub):
+        """Unit-test hook of scan_exclusive_diff_u8_u8: exclusive sums of a[i] - sub[i] mod 2^32, both bytes."""
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        sub = np.ascontiguousarray(sub, dtype=np.uint8)
+        assert a.size == sub.size
+        out = np.empty(a.size, dtype=np.uint32)
+        rc = self._lib.povu_hip_debug_scan(self._ctx, SCAN_DIFF_U8_U8, a.ctypes.data, out.ctypes.data, a.size, sub.ctypes.data,
+                                           None, sub.size)
+        self._prim_rc(rc, "scan_exclusive_diff_u8_u8")
+        return out
+
     def debug_scan_mixed_pair(self, a, b):
         """Unit-test hook of scan_exclusive_u32_u8_pair: exclusive sums of the words `a` and of the bytes `b`, one launch."""
         a = np.ascontiguousarray(a, dtype=np.uint32)
@@ -1357,12 +1370,21 @@ class HipDecomposer:
         cls = np.zeros(n.value, dtype=np.uint32)
         self._lib.povu_hip_debug_tree(self._ctx, comp, C.byref(n), gid.ctypes.data, typ.ctypes.data, par.ctypes.data,
                                       cls.ctypes.data)
-        return dict(gid=gid, typ=typ & 3, black=(typ >> 2) & 1, par=par, cls=cls)
+        return dict(gid=gid, typ=typ & 3, black=(typ >> 2) & 1, root=(typ >> 3) & 1, par=par, cls=cls)
 
     def last_narrow_counts(self) -> bool:
         """True when the last pass kept the bracket counts per tree vertex as bytes (no side with more than 253 links);
         False when the word kernels ran (a fat side, or POVU_HIP_WIDE_COUNTS=1 in the environment)."""
         return bool(self._lib.povu_hip_last_narrow_counts(self._ctx))
+
+    def last_narrow_forms(self) -> tuple:
+        """(ordcnt, srccnt, incnt): which of the three counts per tree vertex the last pass kept as bytes."""
+        m = int(self._lib.povu_hip_last_narrow_counts(self._ctx))
+        return bool(m & 1), bool(m & 2), bool(m & 4)
+
+    def wide_repeat_count(self) -> int:
+        """Passes of this context that ran their tree and class stages again with word counts (a byte in-count at 255)."""
+        return int(self._lib.povu_hip_wide_repeats(self._ctx))
 
     def last_black_only_classes(self) -> bool:
         """True when the last pass numbered the cycle classes of the black tree edges only (the fast path)."""
