@@ -60,6 +60,16 @@ struct HipError : std::runtime_error {
 		hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);              \
 		HIP_CHECK(hipGetLastError());                                                     \
 	} while (0)
+// ... of one lane per element on workgroups of TPB lanes; nothing is launched for n == 0
+static constexpr int TPB = 256;
+static inline unsigned nblk(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
+#define LAUNCH(k, n, s, ...)                                                                     \
+	do {                                                                                     \
+		if ((n) > 0) {                                                                   \
+			hipLaunchKernelGGL(k, dim3(nblk(n)), dim3(TPB), 0, s, __VA_ARGS__);      \
+			HIP_CHECK(hipGetLastError());                                            \
+		}                                                                                \
+	} while (0)
 
 // Bytes that cross PCIe, tallied per thread (a context is used by one thread at a time; the C ABI entry points add the
 // difference over a call to their context's totals, povu_hip_transfer_bytes).  Every host<->device copy of the library goes

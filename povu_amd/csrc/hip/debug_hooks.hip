@@ -576,7 +576,7 @@ extern "C" int povu_hip_debug_edge_ids(povu_hip_ctx *ctx, uint32_t comp, uint32_
 		const size_t T = 2 * (size_t)ctx->sw.V + ctx->last.C, tb = 2 * (size_t)voff + comp;
 		HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dw), 2 * T * 4));
 		HIP_CHECK(hipMemsetAsync(dw, 0, 2 * T * 4, ctx->stream));
-		debug_edge_id_weights(ctx->cs, ctx->sw, ctx->tw, dw, dw + T, ctx->stream);
+		edge_id_weights(ctx->cs, ctx->sw, ctx->tw, dw, dw + T, ctx->stream);
 		std::vector<uint32_t> w(N), tail(N), size(N);
 		HIP_CHECK(copy_async(w.data(), dw + tb, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));
 		HIP_CHECK(copy_async(tail.data(), dw + T + tb, (size_t)N * 4, hipMemcpyDeviceToHost, ctx->stream));

@@ -12,9 +12,6 @@
 namespace povu_hip
 {
 
-static constexpr int TPB = 256;
-static inline unsigned nblk(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-
 // ---------------------------------------------------------------- row A: CSR
 // (also validates the operands: the first link that names an unknown vertex or side lands in *bad)
 __global__ void k_side_degree(uint32_t E, uint32_t V, const uint32_t *__restrict__ v1, const uint8_t *__restrict__ s1,

@@ -27,15 +27,6 @@ namespace povu_hip
 {
 
 #define NIL POVU_NIL
-static constexpr int TPB = 256;
-static inline unsigned nblk(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-#define LAUNCH(k, n, s, ...)                                                                     \
-	do {                                                                                     \
-		if ((n) > 0) {                                                                   \
-			hipLaunchKernelGGL(k, dim3(nblk(n)), dim3(TPB), 0, s, __VA_ARGS__);      \
-			HIP_CHECK(hipGetLastError());                                            \
-		}                                                                                \
-	} while (0)
 
 // component of a tree vertex: component c owns [2 voff[c] + c, 2 voff[c+1] + c]
 struct CompOf {
@@ -370,7 +361,7 @@ void leaf_prepare(const CompState &cs, const SeqWs &sw, const ParWs &pw, const T
 	scan_exclusive_diff_u32(t.out_ord, t.in_ord, t.Ps, (size_t)T + 1, t.scan, t.scan_bytes, s);
 	scan_exclusive_u32(t.out_ord, t.O, (size_t)T + 1, t.scan, t.scan_bytes, s);
 	scan_exclusive_u8(t.nx, t.X, (size_t)T + 1, nullptr, nullptr, 0, t.scan, t.scan_bytes, s);
-	debug_edge_id_weights(cs, sw, tw, t.w, t.tail, s);
+	edge_id_weights(cs, sw, tw, t.w, t.tail, s);
 	LAUNCH(k_leaf_closed, T, s, T, sw.t_size, t.tail, comp_of, sw.c_ntree, t.w);
 	scan_exclusive_u32(t.w, t.B, (size_t)T + 2, t.scan, t.scan_bytes, s);
 

@@ -26,16 +26,7 @@ namespace povu_hip
 {
 
 #define NIL POVU_NIL
-static constexpr int TPB = 256;
 static constexpr size_t PVST_STAGE_MIN = size_t(1) << 20; // PVST vertices from which the result goes through a device block
-static inline unsigned nblk(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-#define LAUNCH(k, n, s, ...)                                                                     \
-	do {                                                                                     \
-		if ((n) > 0) {                                                                   \
-			hipLaunchKernelGGL(k, dim3(nblk(n)), dim3(TPB), 0, s, __VA_ARGS__);      \
-			HIP_CHECK(hipGetLastError());                                            \
-		}                                                                                \
-	} while (0)
 
 // ------------------------------------------------------------- T-space setup
 // component c owns the tree-vertex slots [2 voff[c] + c, 2 voff[c+1] + c]: two per segment and one more

@@ -989,7 +989,7 @@ static void leaf_passes(povu_hip_ctx *ctx, const PassPlan &p, uint32_t C, uint32
 		throw HipError(SUB_REDO_REFUSAL);
 	tm.begin("subflubbles_insert");
 	b.subx = std::make_shared<SubForest>();
-	run_subflubbles(ctx->cs, ctx->sw, ctx->pw, ctx->tw, leaf_state, C, ctx->host, *b.subx, ctx->pool, s, &ctx->ws_sub, &ctx->ws_sub_hint);
+	run_subflubbles(ctx->cs, ctx->sw, ctx->pw, ctx->tw, leaf_state, C, ctx->host, *b.subx, ctx->pool, s, ctx->ws_sub);
 	tm.end(40);
 }
 
@@ -1318,7 +1318,7 @@ extern "C" povu_hip_forest *povu_hip_decompose(povu_hip_ctx *ctx, const povu_hip
 						// several GB right after the hipFree of the pass before stalled for over a second once; a
 						// pass without the leaf passes gives it back)
 		if (!p.all_sub)
-			ctx->ws_sub.release(); // (the inserting passes keep their tables' arena from one -s pass to the next, no longer)
+			ctx->ws_sub.release(); // (the inserting passes keep their phase arenas from one -s pass to the next, no longer)
 		stage_times(ctx, tm, *f);
 		ctx->last = LastPass{true, p, C, out.nbad, out.mixed, out.redo_pvst_only, out.stack_export_pending};
 		ctx->last.narrow_counts = !p.all_seq && !p.seq_tree && ctx->pw.narrow_ordcnt;

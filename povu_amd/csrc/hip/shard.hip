@@ -18,8 +18,6 @@
 
 namespace
 {
-constexpr int TPB = 256;
-inline unsigned nblk(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
 constexpr uint64_t SHARD_MAGIC = 0x31647268735F7670ull; // "pv_shrd1"
 
 inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }

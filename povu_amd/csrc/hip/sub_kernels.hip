@@ -42,7 +42,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <string>
 
 namespace povu_hip
@@ -51,45 +50,9 @@ namespace povu_hip
 #ifndef NIL
 #define NIL POVU_NIL
 #endif
-static constexpr int TPB = 256;
-static inline unsigned nblk(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-#define LAUNCH(k, n, s, ...)                                                                     \
-	do {                                                                                     \
-		if ((n) > 0) {                                                                   \
-			hipLaunchKernelGGL(k, dim3(nblk(n)), dim3(TPB), 0, s, __VA_ARGS__);      \
-			HIP_CHECK(hipGetLastError());                                            \
-		}                                                                                \
-	} while (0)
 
 namespace
 {
-// A table of this stage.  Their sizes come out one after the other (the bracket table's from a scan, the records' from the
-// searches ...), so they are taken from the context's arena for this stage while it has room -- it is reserved for what the
-// call before needed -- and from hipMalloc beyond (freed when the stage returns).
-struct DevBuf {
-	void *p = nullptr;
-	bool own = false;
-	~DevBuf()
-	{
-		if (p && own)
-			(void)hipFree(p);
-	}
-	template <typename T>
-	T *get(size_t n, Arena *ar, size_t &need)
-	{
-		const size_t bytes = (n + 16) * sizeof(T);
-		need += ((bytes + 255) & ~size_t(255)) + 256;
-		if (ar && ar->fits(bytes)) {
-			p = ar->take<char>(bytes);
-			own = false;
-		} else {
-			HIP_CHECK(hipMalloc(&p, bytes));
-			own = true;
-		}
-		return static_cast<T *>(p);
-	}
-};
-
 enum : uint32_t { CL_AI_TRUNK = 0, CL_AI_BRANCH = 1, CL_ZI_TRUNK = 2, CL_ZI_BRANCH = 3 };
 enum : uint32_t { E_POOL = 2u, E_LAYOUT = 8u };
 
@@ -239,47 +202,6 @@ __global__ void k_sub_edge_fill(uint32_t NB, const uint32_t *__restrict__ b_src,
 	const uint32_t u = b_src[j], w = b_tgt[j];
 	o_adj[o_off[u] + atomicAdd(&ocur[u], 1u)] = j;
 	i_adj[i_off[w] + atomicAdd(&icur[w], 1u)] = j;
-}
-// in-place sort of a row by one lane: insertion sort while the row is short, heapsort beyond (rows of thousands of entries
-// exist on tangled graphs; their order out of the atomics is arbitrary)
-template <typename Less>
-__device__ void sort_row(uint32_t *a, uint32_t n, Less less)
-{
-	if (n <= 24) {
-		for (uint32_t i = 1; i < n; i++) {
-			const uint32_t y = a[i];
-			uint32_t k = i;
-			while (k > 0 && less(y, a[k - 1])) {
-				a[k] = a[k - 1];
-				k--;
-			}
-			a[k] = y;
-		}
-		return;
-	}
-	auto sift = [&](uint32_t root, uint32_t end) {
-		const uint32_t v = a[root];
-		for (;;) {
-			uint32_t c = 2 * root + 1;
-			if (c >= end)
-				break;
-			if (c + 1 < end && less(a[c], a[c + 1]))
-				c++;
-			if (!less(v, a[c]))
-				break;
-			a[root] = a[c];
-			root = c;
-		}
-		a[root] = v;
-	};
-	for (uint32_t i = n / 2; i-- > 0;)
-		sift(i, n);
-	for (uint32_t end = n - 1; end > 0; end--) {
-		const uint32_t x = a[0];
-		a[0] = a[end];
-		a[end] = x;
-		sift(0, end);
-	}
 }
 // literal hi of every vertex: min over the subtree of hi_0, the root once a simplifying edge was added at or below
 __global__ void k_sub_hi(uint32_t T, const uint32_t *__restrict__ size, const SegTree segH, const uint32_t *__restrict__ simp_ps,
@@ -1605,6 +1527,452 @@ __global__ void k_sub_compact(uint32_t NV, uint32_t C, const uint32_t *__restric
 	id1[d] = X.id1[x], id2[d] = X.id2[x];
 	coff_d[d] = coff[x];
 }
+
+// ------------------------------------------------------------------ the driver: switches, phase layouts, named steps
+// The test and debug switches of the stage, read from the environment at the top of EVERY call (the tests change them between
+// two passes on one context).
+struct SubSwitches {
+	// POVU_HIP_SUB_SERIAL_SPLICE=forward|reverse (tests): X-space filled with a stale forest first, and the splice kernels on
+	// one wave that walks its list in order (reverse: children before their parents) -- the schedule the parallel splice
+	// must not depend on
+	enum { SPLICE_PARALLEL, SPLICE_FORWARD, SPLICE_REVERSE } sched = SPLICE_PARALLEL;
+	bool times = false;	  // POVU_HIP_SUB_TIMES=1: wall-clock of the phases on stderr (each mark synchronises the stream)
+	bool literal_loa = false; // POVU_HIP_SUB_LITERAL_LOA (tests): the reference's heap on every component, whatever its edges
+	bool forbid_heap = false; // POVU_HIP_SUB_FORBID_HEAP (tests): fail when any component would take the one-lane heap
+	static SubSwitches from_env()
+	{
+		SubSwitches o;
+		if (const char *e = getenv("POVU_HIP_SUB_SERIAL_SPLICE"); e && *e) {
+			if (!strcmp(e, "forward"))
+				o.sched = SPLICE_FORWARD;
+			else if (!strcmp(e, "reverse"))
+				o.sched = SPLICE_REVERSE;
+			else
+				throw HipError(std::string("POVU_HIP_SUB_SERIAL_SPLICE: forward or reverse, not ") + e);
+		}
+		o.times = getenv("POVU_HIP_SUB_TIMES") != nullptr;
+		o.literal_loa = getenv("POVU_HIP_SUB_LITERAL_LOA") != nullptr;
+		o.forbid_heap = getenv("POVU_HIP_SUB_FORBID_HEAP") != nullptr;
+		return o;
+	}
+};
+struct PhaseTimer {
+	bool on;
+	hipStream_t s;
+	double t_prev = now();
+	static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+	void mark(const char *what)
+	{
+		if (!on)
+			return;
+		HIP_CHECK(hipStreamSynchronize(s));
+		const double t_now = now();
+		fprintf(stderr, "[subflubbles] %-22s %9.1f ms\n", what, t_now - t_prev);
+		t_prev = t_now;
+	}
+};
+
+// The device tables of the stage.  Their sizes become known at six points of the pass, so there are six layouts, each
+// declared once (measured, then carved into an arena of its own: SubArenas) when its sizes are there.  Every span carries 16
+// entries more than its user asks for, kept from before (the allocator this replaced added them to every table); what a
+// kernel or a scan needs beyond the plain count is said at the span, any other surplus is kept from before as well.
+struct SubSizes {
+	size_t T, NB0, NB, Q, C;		// (a) at entry: tree vertices, ordinary / all back edges, dense PVST slots, components
+	size_t NC = 0, NS = 0;			// (b), (c) concealed and smothered records, from the scans of their counts
+	size_t NX = 0, ps = 0, NCH = 0, NV = 0; // (d) X slots and pool entries, (e) children, (f) vertices of the result
+};
+// (a) sized by T, NB0, NB, Q, C: the tables the searches ask (SubT points into them) and the concealed counts
+struct SubTables {
+	void *scan; // scratch of every scan over T, NB or Q entries
+	size_t scan_bytes;
+	uint32_t *err;
+	uint32_t *depth, *hi0, *eat;
+	uint32_t *ocnt, *icnt, *o_off, *i_off, *o_adj, *i_adj;
+	uint32_t *segH, *segD, *segT; // trees of the segment trees over hi0, depth, tgt_s
+	uint32_t *simp_ps, *hi, *lo, *br_cnt;
+	unsigned long long *ekey;
+	uint32_t *wbefore, *wtail;
+	uint32_t *heap, *has_self, *mx;
+	uint32_t *tgt_s, *slot_s;
+	uint32_t *cn_cnt, *cn_off, *mn;
+};
+void tables_spans(SubTables &t, const SubSizes &n, Spans &take)
+{
+	t.scan_bytes = scan_tmp_bytes(std::max(std::max(n.T, n.NB), n.Q) + 8);
+	take(t.scan_bytes + 16, t.scan);
+	take(4 + 16, t.err); // four words are cleared, the E_ bits are read from word 0
+	take(n.T + 16 + 16, t.depth, t.hi0, t.eat); // T + 1 entries (k_sub_depth_hi0); the segment trees over depth and hi0 read whole blocks of 16
+	take(n.T + 2 + 16, t.ocnt, t.icnt, t.o_off, t.i_off); // scanned over T + 1 entries, cleared over T + 2
+	take(n.NB + 1 + 16, t.o_adj, t.i_adj);
+	take(SegTree::tree_words(n.T + 1) + 16 + 16, t.segH, t.segD);
+	take(n.T + 4 + 16, t.simp_ps, t.hi, t.lo, t.br_cnt); // simp_ps, br_cnt: T + 1 entries (scan, k_sub_br_counts)
+	take(n.NB0 + 2 + 16, t.ekey);
+	take(n.T + 8 + 16, t.wbefore, t.wtail); // cleared over T + 8.  wtail: edge_id_weights writes it, nobody here reads it
+	take(n.NB0 + 4 + 16, t.heap);
+	take(n.C + 4 + 16, t.has_self); // cleared over C + 4
+	take(2 * (size_t)SegTree::pow2(n.T + 1) + 4 + 16, t.mx); // max-tree with pow2(T + 1) leaves, cleared with 4 words more
+	take(n.NB0 + 32 + 16, t.tgt_s, t.slot_s); // tgt_s: the segment tree over it reads whole blocks of 16
+	take(SegTree::tree_words(n.NB0 + 1) + 16 + 16, t.segT);
+	take(n.Q + 4 + 16, t.cn_cnt, t.cn_off); // Q + 1 entries: launch and scan over Q + 1
+	take(2 * n.Q + 4 + 16, t.mn);
+}
+// (b) sized by NC: the concealed records and the smothered counts, one per record
+struct SubConcealed {
+	Slub *cn;
+	uint32_t *sm_cnt, *sm_off;
+};
+void concealed_spans(SubConcealed &t, const SubSizes &n, Spans &take)
+{
+	take(n.NC + 1 + 16, t.cn);
+	take(n.NC + 4 + 16, t.sm_cnt, t.sm_off); // NC + 1 entries: launch and scan over NC + 1
+}
+// (c) sized by NS: the smothered records; with them the three counts a component the host lays the splice out by
+struct SubSmothered {
+	Smo *smo;
+	uint32_t *comp_counts;
+};
+void smothered_spans(SubSmothered &t, const SubSizes &n, Spans &take)
+{
+	take(n.NS + 1 + 16, t.smo);
+	take(3 * n.C + 4 + 16, t.comp_counts);
+}
+// (d) sized by NX and ps (and Q, C): X-space with its pool of children vectors, the sort that seeds the vectors, the
+// scratch of the splice and the children counts.  What only a pass with C && Q uses (ptop .. ctmp) is carved with the rest:
+// a few bytes per PVST slot.
+struct SubXspace {
+	uint32_t *xoff, *poff; // [C + 1]
+	XArrays X;
+	uint32_t *cap_ps;
+	void *scan; // scratch of the scan over NX entries
+	size_t scan_bytes;
+	uint32_t *k0, *k1, *v0, *v1;
+	void *sort;
+	size_t sort_bytes;
+	uint32_t *counts; // [3 C] concealed, midi, smothered vertices per component
+	uint32_t *ptop, *pin, *md_ps, *list, *n_list;
+	uint8_t *act, *touched, *md;
+	void *ctmp;
+	size_t ctmp_bytes;
+	uint32_t *ccnt, *coff;
+};
+void xspace_spans(SubXspace &t, const SubSizes &n, Spans &take)
+{
+	XArrays &X = t.X;
+	take(n.C + 2 + 16, t.xoff, t.poff);
+	take(n.NX + 4 + 16, X.fam, X.or1, X.or2, X.route, X.loc);
+	take(n.NX + 4 + 16, X.id1, X.id2, X.ai, X.zi, X.sl, X.b_up, X.b_lo, X.vbeg, X.vn, X.vcap); // vn, vcap: cleared over NX + 4
+	take(n.ps + 4 + 16, X.pool);
+	take(n.NX + 4 + 16, t.cap_ps, t.ccnt, t.coff); // ccnt, coff: NX + 1 entries (launch and scan over NX + 1)
+	t.scan_bytes = scan_tmp_bytes(n.NX + 8);
+	take(t.scan_bytes + 16, t.scan);
+	take(n.Q + 4 + 16, t.k0, t.k1, t.v0, t.v1, t.pin);
+	t.sort_bytes = sort_tmp_bytes(n.Q + 8);
+	take(t.sort_bytes + 16, t.sort);
+	take(3 * n.C + 4 + 16, t.counts);
+	take(n.C + 4 + 16, t.ptop);
+	take(n.Q + 16 + 16, t.act, t.touched, t.md); // md: Q + 1 entries, md[Q] is cleared for the scan over Q + 1
+	take(n.Q + 8 + 16, t.md_ps, t.list);	     // md_ps: Q + 1 entries
+	take(8 + 16, t.n_list);
+	t.ctmp_bytes = compact_tmp_bytes(n.Q + 8);
+	take(t.ctmp_bytes + 16, t.ctmp);
+}
+// (e) sized by NCH: the children lists, compact
+struct SubChildren {
+	uint32_t *child;
+};
+void children_spans(SubChildren &t, const SubSizes &n, Spans &take) { take(n.NCH + 4 + 16, t.child); }
+// (f) sized by NV: the vertices without the spare slots of X-space, as they go to the host
+struct SubOut {
+	uint32_t *dvoff; // [C + 1]
+	uint8_t *fam, *or1, *or2, *route;
+	uint32_t *id1, *id2, *coff;
+};
+void out_spans(SubOut &t, const SubSizes &n, Spans &take)
+{
+	take(n.C + 2 + 16, t.dvoff);
+	take(n.NV + 4 + 16, t.fam, t.or1, t.or2, t.route);
+	take(n.NV + 4 + 16, t.id1, t.id2, t.coff);
+}
+
+// One pass of the stage: the inputs, the sizes as they become known, the phase tables, the view the kernels take (SubT).
+// The steps run in the order of run_subflubbles below, all on the stream s.
+struct SubPass {
+	const CompState &cs;
+	const SeqWs &sw;
+	const ParWs &pw;
+	const TreeWs &tw;
+	const LeafState &ls;
+	const LeafIn &in;
+	HostScratch &host;
+	SubArenas &ar;
+	hipStream_t s;
+	const SubSwitches opt;
+	PhaseTimer timer;
+	SubSizes n;
+	const uint32_t T, NB0, NB, Q, C; // (n's entry sizes as the kernels take them)
+	uint32_t NC = 0, NS = 0, NX = 0, NCH = 0;
+	SubTables tb{};
+	SubConcealed cn{};
+	SubSmothered sm{};
+	SubXspace xs{};
+	SubChildren ch{};
+	SubOut o{};
+	SubT t{};
+	CompAt comp{}, comp_x{};	    // component of a dense PVST slot / of an X slot
+	uint32_t *h_cc = nullptr; // [3 C] page-locked: PVST vertices, concealed and smothered records per component
+
+	SubPass(const CompState &cs_, const SeqWs &sw_, const ParWs &pw_, const TreeWs &tw_, const LeafState &ls_, uint32_t C_, HostScratch &host_,
+		SubArenas &ar_, hipStream_t s_)
+	    : cs(cs_), sw(sw_), pw(pw_), tw(tw_), ls(ls_), in(ls_.in), host(host_), ar(ar_), s(s_), opt(SubSwitches::from_env()),
+	      timer{opt.times, s_}, T(2 * sw_.V + C_), NB0(pw_.nb0), NB(pw_.nb0 + pw_.ncap + pw_.nsimp), Q((uint32_t)pw_.d_total), C(C_)
+	{
+		n.T = T, n.NB0 = NB0, n.NB = NB, n.Q = Q, n.C = C;
+		comp = CompAt{cs.voff, pw.doff, C};
+	}
+
+	// carves (a).  Writes depth, hi0 -> segH, segD; the back edges by source and by target (o_off / o_adj, i_off / i_adj), eat
+	// = first slot of a vertex's ordinary edges; hi.  Reads the tree stage's sizes and depths, the dense edge list, in.simp.
+	void edge_tables_hi()
+	{
+		carve(ar.tables, [&](Spans &take) { tables_spans(tb, n, take); });
+		HIP_CHECK(hipMemsetAsync(tb.err, 0, 16, s));
+		LAUNCH(k_sub_depth_hi0, (size_t)T + 1, s, T, sw.t_size, sw.t_depth, tb.depth, tb.hi0, tb.eat);
+		HIP_CHECK(hipMemsetAsync(tb.ocnt, 0, ((size_t)T + 2) * 4, s));
+		HIP_CHECK(hipMemsetAsync(tb.icnt, 0, ((size_t)T + 2) * 4, s));
+		LAUNCH(k_sub_edge_counts, NB, s, NB, NB0, pw.b_src, pw.b_tgt, pw.b_ord, tb.ocnt, tb.icnt, tb.hi0, tb.eat);
+		scan_exclusive_u32(tb.ocnt, tb.o_off, (size_t)T + 1, tb.scan, tb.scan_bytes, s);
+		scan_exclusive_u32(tb.icnt, tb.i_off, (size_t)T + 1, tb.scan, tb.scan_bytes, s);
+		HIP_CHECK(hipMemsetAsync(tb.ocnt, 0, ((size_t)T + 2) * 4, s));
+		HIP_CHECK(hipMemsetAsync(tb.icnt, 0, ((size_t)T + 2) * 4, s));
+		LAUNCH(k_sub_edge_fill, NB, s, NB, pw.b_src, pw.b_tgt, tb.o_off, tb.i_off, tb.ocnt, tb.icnt, tb.o_adj, tb.i_adj);
+		// (the rows are in whatever order the atomics came: every question asked of them is about a set -- any, count, deepest --
+		// and sorting them cost 0.6 s on a segment with 2*10^5 links, one lane on its row)
+		SegTree segH;
+		segH.tree = tb.segH;
+		t.segD.tree = tb.segD;
+		seg_build(segH, tb.hi0, (size_t)T + 1, s);
+		seg_build(t.segD, tb.depth, (size_t)T + 1, s);
+		scan_exclusive_u8(in.simp, tb.simp_ps, (size_t)T + 1, nullptr, nullptr, 0, tb.scan, tb.scan_bytes, s);
+		LAUNCH(k_sub_hi, T, s, T, sw.t_size, segH, tb.simp_ps, comp, tb.hi);
+		timer.mark("edge tables, hi");
+	}
+	// Writes ekey (the creation keys of the ordinary edges) and lo (LoA: closed form from the max-tree mx, the reference's
+	// heap where has_self says so).  Reads eat, depth, the tree stage's state (edge_id_weights), in.out_ord / nself / O.
+	void creation_keys_lo()
+	{
+		HIP_CHECK(hipMemsetAsync(tb.wbefore, 0, ((size_t)T + 8) * 4, s));
+		HIP_CHECK(hipMemsetAsync(tb.wtail, 0, ((size_t)T + 8) * 4, s));
+		edge_id_weights(cs, sw, tw, tb.wbefore, tb.wtail, s);
+		LAUNCH(k_sub_edge_keys, T, s, T, sw.t_size, in.out_ord, tb.eat, tb.wbefore, tb.ekey);
+		const uint32_t P2 = SegTree::pow2((size_t)T + 1);
+		HIP_CHECK(hipMemsetAsync(tb.mx, 0, (2 * (size_t)P2 + 4) * 4, s));
+		HIP_CHECK(hipMemsetAsync(tb.has_self, 0, ((size_t)C + 4) * 4, s));
+		LAUNCH(k_sub_lo_mark, NB0, s, NB0, pw.b_src, pw.b_tgt, P2, tb.mx);
+		LAUNCH(k_sub_lo_query, T, s, T, sw.t_size, P2, tb.mx, in.nself, comp, tb.lo, tb.has_self);
+		if (opt.literal_loa)
+			fill_u32(tb.has_self, C, 1u, s);
+		if (opt.forbid_heap) {
+			uint32_t *hs = host.take<uint32_t>(C);
+			HIP_CHECK(copy_async(hs, tb.has_self, (size_t)C * 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipStreamSynchronize(s));
+			for (uint32_t c = 0; c < C; c++)
+				if (hs[c])
+					throw HipError("subflubble passes: component " + std::to_string(c + 1) + " takes the literal LoA heap (POVU_HIP_SUB_FORBID_HEAP is set)");
+		}
+		LAUNCH(k_sub_lo, C, s, C, cs.voff, sw.c_ntree, sw.t_size, tb.depth, in.out_ord, tb.eat, pw.b_tgt, in.O, tb.has_self, tb.heap, tb.lo);
+		timer.mark("creation keys, lo");
+	}
+	// Writes br_cnt (closed form) and the ordinary edges in source order (tgt_s, slot_s) -> segT.  Reads eat, in.gp / P / O.
+	void bracket_rows()
+	{
+		LAUNCH(k_sub_br_counts, (size_t)T + 1, s, T, sw.t_size, in.gp, in.P, in.out_ord, in.nself, tb.br_cnt);
+		LAUNCH(k_sub_edges_by_source, T, s, T, sw.t_size, in.out_ord, tb.eat, in.O, pw.b_tgt, tb.tgt_s, tb.slot_s);
+		t.segT.tree = tb.segT;
+		seg_build(t.segT, tb.tgt_s, NB0, s);
+		timer.mark("bracket rows");
+	}
+	// the view of (a) and of the dense PVST that every later kernel takes (segD and segT were built in place above)
+	void fill_view()
+	{
+		t.T = T, t.C = C, t.NB0 = NB0, t.NB = NB;
+		t.voff = cs.voff, t.c_ntree = sw.c_ntree, t.doff = pw.doff, t.c_npvst = sw.c_npvst;
+		t.size = sw.t_size, t.gp = in.gp, t.nchild = in.nchild, t.depth = tb.depth, t.gid = sw.t_gid, t.flags = sw.t_flags;
+		t.b_src = pw.b_src, t.b_tgt = pw.b_tgt, t.b_ord = pw.b_ord;
+		t.o_off = tb.o_off, t.o_adj = tb.o_adj, t.i_off = tb.i_off, t.i_adj = tb.i_adj;
+		t.br_cnt = tb.br_cnt, t.O = in.O, t.slot_s = tb.slot_s, t.lo = tb.lo, t.hi = tb.hi, t.ekey = tb.ekey;
+		t.p_ai = ls.dense.ai, t.p_zi = ls.dense.zi, t.p_fam = ls.dense.fam;
+		t.p_parent = pw.d_parent, t.p_a = pw.d_a, t.p_z = pw.d_z, t.p_aor = pw.d_aor, t.p_zor = pw.d_zor;
+		t.err = tb.err;
+	}
+	// find_concealed: count per dense slot (cn_cnt, mn), scan (cn_off), NC to the host, carves (b), emit (cn)
+	void search_concealed()
+	{
+		LAUNCH(k_sub_cn_count, (size_t)Q + 1, s, Q, t, comp, tb.cn_cnt, tb.mn);
+		scan_exclusive_u32(tb.cn_cnt, tb.cn_off, (size_t)Q + 1, tb.scan, tb.scan_bytes, s);
+		n.NC = NC = host.read_u32(tb.cn_off + Q, s);
+		carve(ar.concealed, [&](Spans &take) { concealed_spans(cn, n, take); });
+		LAUNCH(k_sub_cn_emit, Q, s, Q, t, comp, tb.cn_off, cn.cn);
+		timer.mark("find_concealed search");
+	}
+	// find_smothered: count per concealed record (sm_cnt), scan (sm_off), NS to the host, carves (c), emit (smo)
+	void search_smothered()
+	{
+		LAUNCH(k_sub_smo_count, (size_t)NC + 1, s, NC, t, comp, cn.cn, cn.sm_cnt);
+		scan_exclusive_u32(cn.sm_cnt, cn.sm_off, (size_t)NC + 1, tb.scan, tb.scan_bytes, s);
+		n.NS = NS = host.read_u32(cn.sm_off + NC, s);
+		carve(ar.smothered, [&](Spans &take) { smothered_spans(sm, n, take); });
+		LAUNCH(k_sub_smo_emit, NC, s, NC, t, comp, cn.cn, cn.sm_off, sm.smo);
+		timer.mark("find_smothered search");
+	}
+	// Layout of the splice: per component its stretch of X-space and of the vector pool.  The host needs three numbers a
+	// component (PVST vertices, concealed and smothered records: h_cc), worked out on the device and read through page-locked
+	// scratch (the whole offset array of the records, 4 bytes per PVST vertex into a pageable vector, took 5 - 20 ms on the
+	// whole-genome workload).  Gives NX and ps, carves (d), uploads xoff and poff.
+	void layout_splice()
+	{
+		h_cc = host.take<uint32_t>(3 * (size_t)C + 4);
+		if (C) {
+			LAUNCH(k_sub_comp_counts, C, s, C, pw.doff, sw.c_npvst, tb.cn_off, cn.sm_off, sm.comp_counts);
+			HIP_CHECK(copy_async(h_cc, sm.comp_counts, 3 * (size_t)C * 4, hipMemcpyDeviceToHost, s));
+		}
+		HIP_CHECK(hipStreamSynchronize(s));
+		uint32_t *h_xoff = host.take<uint32_t>((size_t)C + 1), *h_poff = host.take<uint32_t>((size_t)C + 1);
+		uint64_t x = 0, p = 0;
+		for (uint32_t c = 0; c < C; c++) {
+			h_xoff[c] = (uint32_t)x;
+			h_poff[c] = (uint32_t)p;
+			if (const uint64_t n0 = h_cc[3 * (size_t)c]) {
+				const uint64_t ncn = h_cc[3 * (size_t)c + 1], nsm = h_cc[3 * (size_t)c + 2];
+				x += 2 * n0 + ncn + nsm;
+				p += 32 * n0 + 16 * (ncn + nsm) + 256;
+			}
+			if (x > 0xFFFFFFF0ull || p > 0xFFFFFFF0ull)
+				throw HipError("subflubble passes: more than 2^32 PVST vertices or child slots in one pass");
+		}
+		h_xoff[C] = (uint32_t)x;
+		h_poff[C] = (uint32_t)p;
+		n.NX = NX = (uint32_t)x;
+		n.ps = p;
+		carve(ar.xspace, [&](Spans &take) { xspace_spans(xs, n, take); });
+		HIP_CHECK(copy_async(xs.xoff, h_xoff, ((size_t)C + 1) * 4, hipMemcpyHostToDevice, s));
+		HIP_CHECK(copy_async(xs.poff, h_poff, ((size_t)C + 1) * 4, hipMemcpyHostToDevice, s));
+		comp_x = CompAt{cs.voff, xs.xoff, C};
+	}
+	// The PVST of find_flubbles into X-space: the fields of every vertex (k_sub_x_init; under a serial schedule a stale forest
+	// in every slot first) and its children vector in ascending idx, by a sort of (X slot of the parent, child).
+	void seed_vectors()
+	{
+		const XArrays &X = xs.X;
+		HIP_CHECK(hipMemsetAsync(X.vn, 0, ((size_t)NX + 4) * 4, s));
+		HIP_CHECK(hipMemsetAsync(X.vcap, 0, ((size_t)NX + 4) * 4, s));
+		if (opt.sched != SubSwitches::SPLICE_PARALLEL)
+			LAUNCH(k_sub_x_poison, NX, s, NX, t, comp_x, xs.xoff, X);
+		LAUNCH(k_sub_x_init, Q, s, Q, t, comp, xs.xoff, X);
+		LAUNCH(k_sub_x_keys, Q, s, Q, NX, t, comp, xs.xoff, xs.k0, xs.v0);
+		sort_pairs_u32(xs.k0, xs.k1, xs.v0, xs.v1, Q, bits_for(NX), xs.sort, xs.sort_bytes, s);
+		LAUNCH(k_sub_x_vbeg, Q, s, Q, t, comp, xs.xoff, xs.poff, xs.k1, xs.cap_ps, X);
+		LAUNCH(k_sub_x_place, Q, s, Q, NX, xs.k1, xs.v1, xs.cap_ps, X);
+		timer.mark("layout, PVST vectors");
+	}
+	// add_concealed, find_midi / add_midi, add_smothered on X-space, one wave per listed flubble (one wave in all under a serial
+	// schedule); writes counts = inserted vertices per component and kind.  Reads the records (cn, mn, smo) and the view.
+	void splice()
+	{
+		if (C && Q) {
+			SpliceArgs A{};
+			A.t = t, A.comp = comp, A.xoff = xs.xoff, A.poff = xs.poff, A.ptop = xs.ptop;
+			A.cn_off = tb.cn_off, A.cn = cn.cn, A.mn = tb.mn, A.smo_off = cn.sm_off, A.smo = sm.smo, A.X = xs.X;
+			A.pin = xs.pin, A.act = xs.act, A.touched = xs.touched, A.md = xs.md, A.md_ps = xs.md_ps;
+			uint32_t *list = xs.list, *n_list = xs.n_list;
+			LAUNCH(k_sub_ptop, C, s, C, xs.poff, sw.c_npvst, A.ptop);
+			LAUNCH(k_sub_pin, Q, s, Q, A);
+			const bool reverse = opt.sched == SubSwitches::SPLICE_REVERSE;
+			const unsigned waves = opt.sched == SubSwitches::SPLICE_PARALLEL ? SPLICE_WAVES : 1u;
+			compact_flagged_u8(A.act, Q, list, n_list, xs.ctmp, xs.ctmp_bytes, s);
+			if (reverse)
+				LAUNCH(k_sub_reverse_list, Q / 2 + 1, s, Q, n_list, list);
+			KLAUNCH(k_sub_splice_cn, dim3(waves), dim3(64), 0, s, n_list, list, A);
+			compact_flagged_u8(A.touched, Q, list, n_list, xs.ctmp, xs.ctmp_bytes, s);
+			if (reverse)
+				LAUNCH(k_sub_reverse_list, Q / 2 + 1, s, Q, n_list, list);
+			KLAUNCH(k_sub_midi_find, dim3(waves), dim3(64), 0, s, n_list, list, A);
+			HIP_CHECK(hipMemsetAsync(A.md + Q, 0, 1, s));
+			scan_exclusive_u8(A.md, xs.md_ps, (size_t)Q + 1, nullptr, nullptr, 0, tb.scan, tb.scan_bytes, s);
+			KLAUNCH(k_sub_midi_add, dim3(waves), dim3(64), 0, s, n_list, list, A);
+			if (NS)
+				KLAUNCH(k_sub_smothered, dim3(std::min<unsigned>(NC, waves)), dim3(64), 0, s, NC, A);
+			LAUNCH(k_sub_counts, C, s, C, A, xs.counts);
+		} else if (C) {
+			HIP_CHECK(hipMemsetAsync(xs.counts, 0, 3 * (size_t)C * 4, s));
+		}
+		timer.mark("splice");
+		const uint32_t e = host.read_u32(tb.err, s);
+		if (e & E_POOL)
+			throw HipError("subflubble passes: the children vectors outgrew their pool (internal sizing bug)");
+		if (e & E_LAYOUT)
+			throw HipError("subflubble passes: more inserted vertices than the layout has room for (internal sizing bug)");
+	}
+	// The final children lists, compact and in vertex order: sizes per X slot (ccnt), scan (coff), NCH to the host, carves (e),
+	// gather (child).
+	void compact_children()
+	{
+		LAUNCH(k_sub_child_counts, (size_t)NX + 1, s, NX, xs.xoff, xs.counts, sw.c_npvst, comp_x, xs.X.vn, xs.ccnt);
+		scan_exclusive_u32(xs.ccnt, xs.coff, (size_t)NX + 1, xs.scan, xs.scan_bytes, s);
+		n.NCH = NCH = host.read_u32(xs.coff + NX, s);
+		carve(ar.children, [&](Spans &take) { children_spans(ch, n, take); });
+		LAUNCH(k_sub_child_gather, NCH, s, NCH, NX, xs.coff, xs.X.vbeg, xs.X.pool, ch.child);
+		timer.mark("children lists");
+	}
+	// To the host: counts gives the vertices of every component (out.voff, NV), carves (f); the vertices are compacted on the
+	// device (X-space has spare slots behind every component), then one copy per array into one page-locked block of `pool`.
+	void to_host(SubForest &out, const std::shared_ptr<::PinnedPool> &pool)
+	{
+		uint32_t *h_counts = host.take<uint32_t>(3 * (size_t)C), *h_dvoff = host.take<uint32_t>((size_t)C + 1);
+		if (C)
+			HIP_CHECK(copy_async(h_counts, xs.counts, 3 * (size_t)C * 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		out.voff.assign((size_t)C + 1, 0);
+		uint64_t n_vtx = 0;
+		for (uint32_t c = 0; c < C; c++) {
+			out.voff[c] = n_vtx;
+			h_dvoff[c] = (uint32_t)n_vtx;
+			if (const uint32_t n0 = h_cc[3 * (size_t)c])
+				n_vtx += (uint64_t)n0 + h_counts[3 * c] + h_counts[3 * c + 1] + h_counts[3 * c + 2];
+		}
+		out.voff[C] = n_vtx;
+		h_dvoff[C] = (uint32_t)n_vtx;
+		out.counts.assign(h_counts, h_counts + 3 * (size_t)C);
+		const uint32_t NV = (uint32_t)n_vtx;
+		n.NV = NV;
+		carve(ar.out, [&](Spans &take) { out_spans(o, n, take); });
+		HIP_CHECK(copy_async(o.dvoff, h_dvoff, ((size_t)C + 1) * 4, hipMemcpyHostToDevice, s));
+		LAUNCH(k_sub_compact, NV, s, NV, C, o.dvoff, xs.xoff, xs.X, xs.coff, o.fam, o.or1, o.or2, o.route, o.id1, o.id2, o.coff);
+		// one page-locked block: fam | or1 | or2 | route | id1 | id2 | coff (+ 1) | child, one spare entry each
+		const forest_wire::SubBlockLayout L(NV, NCH, 0, 1);
+		if (!pool)
+			throw HipError("subflubble passes: no pool of page-locked memory (internal)");
+		out.pool = pool;
+		out.blk = pool->get(L.end + 64, out.blk_cap, &out.blk_seg);
+		char *hb = static_cast<char *>(out.blk);
+		auto d2h = [&](size_t at, const void *src, size_t bytes) {
+			if (bytes)
+				HIP_CHECK(copy_async(hb + at, src, bytes, hipMemcpyDeviceToHost, s));
+		};
+		d2h(L.fam, o.fam, NV);
+		d2h(L.or1, o.or1, NV);
+		d2h(L.or2, o.or2, NV);
+		d2h(L.route, o.route, NV);
+		d2h(L.id1, o.id1, (size_t)NV * 4);
+		d2h(L.id2, o.id2, (size_t)NV * 4);
+		d2h(L.coff, o.coff, (size_t)NV * 4);
+		d2h(L.child, ch.child, (size_t)NCH * 4); // (the lists are compact already, in vertex order)
+		HIP_CHECK(hipStreamSynchronize(s));
+		reinterpret_cast<uint32_t *>(hb + L.coff)[NV] = NCH;
+		out.n_vtx = n_vtx, out.n_child = NCH;
+		out.point(hb, L);
+		timer.mark("to the host");
+	}
+};
 } // namespace
 
 SubForest::~SubForest()
@@ -1613,297 +1981,33 @@ SubForest::~SubForest()
 		pool->put(blk, blk_cap, blk_seg);
 }
 
-void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, const TreeWs &tw, const LeafState &ls, uint32_t C,
-		     HostScratch &host, SubForest &out, const std::shared_ptr<::PinnedPool> &pool, hipStream_t s, Arena *arena,
-		     size_t *arena_hint)
+void SubArenas::release()
 {
-	const uint32_t V = sw.V, T = 2 * V + C;
-	const uint32_t NB0 = pw.nb0, NB = pw.nb0 + pw.ncap + pw.nsimp;
-	const uint32_t Q = (uint32_t)pw.d_total; // dense PVST slots
-	const LeafIn &in = ls.in;
-	// POVU_HIP_SUB_SERIAL_SPLICE=forward|reverse (tests; read on every call): X-space filled with a stale forest first, and
-	// the splice kernels on one wave that walks its list in order (reverse: children before their parents) -- the schedule
-	// the parallel splice must not depend on
-	enum { SPLICE_PARALLEL, SPLICE_FORWARD, SPLICE_REVERSE } sched = SPLICE_PARALLEL;
-	if (const char *e = getenv("POVU_HIP_SUB_SERIAL_SPLICE"); e && *e) {
-		if (!strcmp(e, "forward"))
-			sched = SPLICE_FORWARD;
-		else if (!strcmp(e, "reverse"))
-			sched = SPLICE_REVERSE;
-		else
-			throw HipError(std::string("POVU_HIP_SUB_SERIAL_SPLICE: forward or reverse, not ") + e);
-	}
-	// POVU_HIP_SUB_TIMES=1: wall-clock of the phases on stderr (each mark synchronises the stream)
-	const bool times = getenv("POVU_HIP_SUB_TIMES") != nullptr;
-	auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	double t_prev = now();
-	auto mark = [&](const char *what) {
-		if (!times)
-			return;
-		HIP_CHECK(hipStreamSynchronize(s));
-		const double t_now = now();
-		fprintf(stderr, "[subflubbles] %-22s %9.1f ms\n", what, t_now - t_prev);
-		t_prev = t_now;
-	};
-	std::deque<DevBuf> bufs; // (what came from hipMalloc is freed when the stage returns or throws)
-	size_t need = 0;
-	if (arena)
-		arena->reserve(arena_hint ? *arena_hint : 0);
-	auto dev32 = [&](size_t n) { return bufs.emplace_back().get<uint32_t>(n, arena, need); };
-	auto dev8 = [&](size_t n) { return bufs.emplace_back().get<uint8_t>(n, arena, need); };
-	const size_t tmp_bytes = scan_tmp_bytes(std::max<size_t>(std::max<size_t>(T, NB), Q) + 8);
-	void *tmp = bufs.emplace_back().get<char>(tmp_bytes, arena, need);
-	uint32_t *err = dev32(4);
-	HIP_CHECK(hipMemsetAsync(err, 0, 16, s));
+	for (Arena *a : {&tables, &concealed, &smothered, &xspace, &children, &out})
+		a->release();
+}
+size_t SubArenas::capacity() const
+{
+	return tables.capacity() + concealed.capacity() + smothered.capacity() + xspace.capacity() + children.capacity() + out.capacity();
+}
 
-	// ---- tables
-	uint32_t *depth = dev32((size_t)T + 16), *hi0 = dev32((size_t)T + 16), *eat = dev32((size_t)T + 16);
-	LAUNCH(k_sub_depth_hi0, (size_t)T + 1, s, T, sw.t_size, sw.t_depth, depth, hi0, eat);
-	uint32_t *ocnt = dev32((size_t)T + 2), *icnt = dev32((size_t)T + 2), *o_off = dev32((size_t)T + 2), *i_off = dev32((size_t)T + 2);
-	HIP_CHECK(hipMemsetAsync(ocnt, 0, ((size_t)T + 2) * 4, s));
-	HIP_CHECK(hipMemsetAsync(icnt, 0, ((size_t)T + 2) * 4, s));
-	LAUNCH(k_sub_edge_counts, NB, s, NB, NB0, pw.b_src, pw.b_tgt, pw.b_ord, ocnt, icnt, hi0, eat);
-	scan_exclusive_u32(ocnt, o_off, (size_t)T + 1, tmp, tmp_bytes, s);
-	scan_exclusive_u32(icnt, i_off, (size_t)T + 1, tmp, tmp_bytes, s);
-	uint32_t *o_adj = dev32((size_t)NB + 1), *i_adj = dev32((size_t)NB + 1);
-	HIP_CHECK(hipMemsetAsync(ocnt, 0, ((size_t)T + 2) * 4, s));
-	HIP_CHECK(hipMemsetAsync(icnt, 0, ((size_t)T + 2) * 4, s));
-	LAUNCH(k_sub_edge_fill, NB, s, NB, pw.b_src, pw.b_tgt, o_off, i_off, ocnt, icnt, o_adj, i_adj);
-	// (the rows are in whatever order the atomics came: every question asked of them is about a set -- any, count, deepest --
-	// and sorting them cost 0.6 s on a segment with 2*10^5 links, one lane on its row)
-	// literal hi
-	SegTree segH, segD;
-	segH.tree = dev32(SegTree::tree_words((size_t)T + 1) + 16);
-	segD.tree = dev32(SegTree::tree_words((size_t)T + 1) + 16);
-	seg_build(segH, hi0, (size_t)T + 1, s);
-	seg_build(segD, depth, (size_t)T + 1, s);
-	uint32_t *simp_ps = dev32((size_t)T + 4), *hi = dev32((size_t)T + 4);
-	scan_exclusive_u8(in.simp, simp_ps, (size_t)T + 1, nullptr, nullptr, 0, tmp, tmp_bytes, s);
-	const CompAt comp{cs.voff, pw.doff, C};
-	LAUNCH(k_sub_hi, T, s, T, sw.t_size, segH, simp_ps, comp, hi);
-	mark("edge tables, hi");
-	// creation keys of the ordinary edges
-	unsigned long long *ekey = bufs.emplace_back().get<unsigned long long>((size_t)NB0 + 2, arena, need);
-	uint32_t *wbefore = dev32((size_t)T + 8), *wtail = dev32((size_t)T + 8);
-	HIP_CHECK(hipMemsetAsync(wbefore, 0, ((size_t)T + 8) * 4, s));
-	HIP_CHECK(hipMemsetAsync(wtail, 0, ((size_t)T + 8) * 4, s));
-	debug_edge_id_weights(cs, sw, tw, wbefore, wtail, s);
-	LAUNCH(k_sub_edge_keys, T, s, T, sw.t_size, in.out_ord, eat, wbefore, ekey);
-	// LoA
-	uint32_t *lo = dev32((size_t)T + 4), *heap = dev32((size_t)NB0 + 4), *has_self = dev32((size_t)C + 4);
-	{
-		const uint32_t P2 = SegTree::pow2((size_t)T + 1);
-		uint32_t *mx = dev32(2 * (size_t)P2 + 4);
-		HIP_CHECK(hipMemsetAsync(mx, 0, (2 * (size_t)P2 + 4) * 4, s));
-		HIP_CHECK(hipMemsetAsync(has_self, 0, ((size_t)C + 4) * 4, s));
-		LAUNCH(k_sub_lo_mark, NB0, s, NB0, pw.b_src, pw.b_tgt, P2, mx);
-		LAUNCH(k_sub_lo_query, T, s, T, sw.t_size, P2, mx, in.nself, comp, lo, has_self);
-		if (getenv("POVU_HIP_SUB_LITERAL_LOA")) // (tests: the reference's heap on every component, whatever its edges)
-			fill_u32(has_self, C, 1u, s);
-		if (getenv("POVU_HIP_SUB_FORBID_HEAP")) { // (tests: fail when any component would take the one-lane heap)
-			std::vector<uint32_t> hs(C);
-			HIP_CHECK(hipMemcpyAsync(hs.data(), has_self, (size_t)C * 4, hipMemcpyDeviceToHost, s));
-			HIP_CHECK(hipStreamSynchronize(s));
-			for (uint32_t c = 0; c < C; c++)
-				if (hs[c])
-					throw HipError("subflubble passes: component " + std::to_string(c + 1) + " takes the literal LoA heap (POVU_HIP_SUB_FORBID_HEAP is set)");
-		}
-		LAUNCH(k_sub_lo, C, s, C, cs.voff, sw.c_ntree, sw.t_size, depth, in.out_ord, eat, pw.b_tgt, in.O, has_self, heap, lo);
-	}
-	mark("creation keys, lo");
-	// bracket rows: counts in closed form, the edges in source order with a segment tree over their targets
-	uint32_t *br_cnt = dev32((size_t)T + 4);
-	LAUNCH(k_sub_br_counts, (size_t)T + 1, s, T, sw.t_size, in.gp, in.P, in.out_ord, in.nself, br_cnt);
-	uint32_t *tgt_s = dev32((size_t)NB0 + 32), *slot_s = dev32((size_t)NB0 + 32);
-	LAUNCH(k_sub_edges_by_source, T, s, T, sw.t_size, in.out_ord, eat, in.O, pw.b_tgt, tgt_s, slot_s);
-	SegTree segT;
-	segT.tree = dev32(SegTree::tree_words((size_t)NB0 + 1) + 16);
-	seg_build(segT, tgt_s, NB0, s);
-	mark("bracket rows");
-
-	SubT t{};
-	t.T = T, t.C = C, t.NB0 = NB0, t.NB = NB;
-	t.voff = cs.voff, t.c_ntree = sw.c_ntree, t.doff = pw.doff, t.c_npvst = sw.c_npvst;
-	t.size = sw.t_size, t.gp = in.gp, t.nchild = in.nchild, t.depth = depth, t.gid = sw.t_gid, t.flags = sw.t_flags;
-	t.b_src = pw.b_src, t.b_tgt = pw.b_tgt, t.b_ord = pw.b_ord;
-	t.o_off = o_off, t.o_adj = o_adj, t.i_off = i_off, t.i_adj = i_adj;
-	t.br_cnt = br_cnt, t.O = in.O, t.slot_s = slot_s, t.segT = segT, t.lo = lo, t.hi = hi, t.ekey = ekey;
-	segD.val = depth;
-	t.segD = segD;
-	t.p_ai = ls.dense.ai, t.p_zi = ls.dense.zi, t.p_fam = ls.dense.fam;
-	t.p_parent = pw.d_parent, t.p_a = pw.d_a, t.p_z = pw.d_z, t.p_aor = pw.d_aor, t.p_zor = pw.d_zor;
-	t.err = err;
-
-	// ---- find_concealed: count, scan, emit
-	uint32_t *cn_cnt = dev32((size_t)Q + 4), *cn_off = dev32((size_t)Q + 4), *mn = dev32(2 * (size_t)Q + 4);
-	LAUNCH(k_sub_cn_count, (size_t)Q + 1, s, Q, t, comp, cn_cnt, mn);
-	scan_exclusive_u32(cn_cnt, cn_off, (size_t)Q + 1, tmp, tmp_bytes, s);
-	const uint32_t NC = host.read_u32(cn_off + Q, s);
-	Slub *cn = bufs.emplace_back().get<Slub>((size_t)NC + 1, arena, need);
-	LAUNCH(k_sub_cn_emit, Q, s, Q, t, comp, cn_off, cn);
-	mark("find_concealed search");
-	// ---- find_smothered: count, scan, emit
-	uint32_t *sm_cnt = dev32((size_t)NC + 4), *sm_off = dev32((size_t)NC + 4);
-	LAUNCH(k_sub_smo_count, (size_t)NC + 1, s, NC, t, comp, cn, sm_cnt);
-	scan_exclusive_u32(sm_cnt, sm_off, (size_t)NC + 1, tmp, tmp_bytes, s);
-	const uint32_t NS = host.read_u32(sm_off + NC, s);
-	Smo *smo = bufs.emplace_back().get<Smo>((size_t)NS + 1, arena, need);
-	LAUNCH(k_sub_smo_emit, NC, s, NC, t, comp, cn, sm_off, smo);
-	mark("find_smothered search");
-
-	// ---- layout of the splice: per component its stretch of X-space and of the vector pool.  The host needs three numbers a
-	// component (PVST vertices, concealed and smothered records): worked out on the device and read through page-locked
-	// scratch (until round 5 the whole offset array of the records came back, 4 bytes per PVST vertex into a pageable vector:
-	// 5 - 20 ms on the whole-genome workload, depending on what the process's allocator made of a fresh 100 MB)
-	uint32_t *comp_counts = dev32(3 * (size_t)C + 4);
-	uint32_t *h_cc = host.take<uint32_t>(3 * (size_t)C + 4);
-	if (C) {
-		LAUNCH(k_sub_comp_counts, C, s, C, pw.doff, sw.c_npvst, cn_off, sm_off, comp_counts);
-		HIP_CHECK(copy_async(h_cc, comp_counts, 3 * (size_t)C * 4, hipMemcpyDeviceToHost, s));
-	}
-	HIP_CHECK(hipStreamSynchronize(s));
-	std::vector<uint32_t> h_np((size_t)C + 1);
-	std::vector<uint32_t> h_xoff((size_t)C + 1), h_poff((size_t)C + 1);
-	uint64_t xs = 0, ps = 0;
-	for (uint32_t c = 0; c < C; c++) {
-		h_xoff[c] = (uint32_t)xs;
-		h_poff[c] = (uint32_t)ps;
-		const uint64_t n0 = h_np[c] = h_cc[3 * (size_t)c];
-		if (n0) {
-			const uint64_t ncn = h_cc[3 * (size_t)c + 1], nsm = h_cc[3 * (size_t)c + 2];
-			xs += 2 * n0 + ncn + nsm;
-			ps += 32 * n0 + 16 * (ncn + nsm) + 256;
-		}
-		if (xs > 0xFFFFFFF0ull || ps > 0xFFFFFFF0ull)
-			throw HipError("subflubble passes: more than 2^32 PVST vertices or child slots in one pass");
-	}
-	h_xoff[C] = (uint32_t)xs;
-	h_poff[C] = (uint32_t)ps;
-	const uint32_t NX = (uint32_t)xs;
-	uint32_t *xoff = dev32((size_t)C + 2), *poff = dev32((size_t)C + 2);
-	HIP_CHECK(hipMemcpyAsync(xoff, h_xoff.data(), ((size_t)C + 1) * 4, hipMemcpyHostToDevice, s));
-	HIP_CHECK(hipMemcpyAsync(poff, h_poff.data(), ((size_t)C + 1) * 4, hipMemcpyHostToDevice, s));
-	XArrays X{};
-	X.fam = dev8((size_t)NX + 4), X.or1 = dev8((size_t)NX + 4), X.or2 = dev8((size_t)NX + 4), X.route = dev8((size_t)NX + 4);
-	X.loc = dev8((size_t)NX + 4);
-	X.id1 = dev32((size_t)NX + 4), X.id2 = dev32((size_t)NX + 4), X.ai = dev32((size_t)NX + 4), X.zi = dev32((size_t)NX + 4);
-	X.sl = dev32((size_t)NX + 4), X.b_up = dev32((size_t)NX + 4), X.b_lo = dev32((size_t)NX + 4);
-	X.vbeg = dev32((size_t)NX + 4), X.vn = dev32((size_t)NX + 4), X.vcap = dev32((size_t)NX + 4);
-	X.pool = dev32((size_t)ps + 4);
-	HIP_CHECK(hipMemsetAsync(X.vn, 0, ((size_t)NX + 4) * 4, s));
-	HIP_CHECK(hipMemsetAsync(X.vcap, 0, ((size_t)NX + 4) * 4, s));
-	const CompAt comp_q{cs.voff, pw.doff, C}, comp_x{cs.voff, xoff, C};
-	uint32_t *cap_ps = dev32((size_t)NX + 4);
-	const size_t tmpx_bytes = scan_tmp_bytes((size_t)NX + 8);
-	void *tmpx = bufs.emplace_back().get<char>(tmpx_bytes, arena, need);
-	if (sched != SPLICE_PARALLEL)
-		LAUNCH(k_sub_x_poison, NX, s, NX, t, comp_x, xoff, X);
-	LAUNCH(k_sub_x_init, Q, s, Q, t, comp_q, xoff, X);
-	{
-		uint32_t *k0 = dev32((size_t)Q + 4), *k1 = dev32((size_t)Q + 4), *v0 = dev32((size_t)Q + 4), *v1 = dev32((size_t)Q + 4);
-		const size_t sort_bytes = sort_tmp_bytes((size_t)Q + 8);
-		void *sort_tmp = bufs.emplace_back().get<char>(sort_bytes, arena, need);
-		LAUNCH(k_sub_x_keys, Q, s, Q, NX, t, comp_q, xoff, k0, v0);
-		sort_pairs_u32(k0, k1, v0, v1, Q, bits_for(NX), sort_tmp, sort_bytes, s);
-		LAUNCH(k_sub_x_vbeg, Q, s, Q, t, comp_q, xoff, poff, k1, cap_ps, X);
-		LAUNCH(k_sub_x_place, Q, s, Q, NX, k1, v1, cap_ps, X);
-	}
-	mark("layout, PVST vectors");
-	uint32_t *counts = dev32(3 * (size_t)C + 4);
-	if (C && Q) {
-		SpliceArgs A{};
-		A.t = t, A.comp = comp_q, A.xoff = xoff, A.poff = poff, A.ptop = dev32((size_t)C + 4);
-		A.cn_off = cn_off, A.cn = cn, A.mn = mn, A.smo_off = sm_off, A.smo = smo, A.X = X;
-		A.pin = dev32((size_t)Q + 4);
-		A.act = dev8((size_t)Q + 16), A.touched = dev8((size_t)Q + 16), A.md = dev8((size_t)Q + 16);
-		uint32_t *md_ps = dev32((size_t)Q + 8), *list = dev32((size_t)Q + 8), *n_list = dev32(8);
-		A.md_ps = md_ps;
-		const size_t ctmp_bytes = compact_tmp_bytes((size_t)Q + 8);
-		void *ctmp = bufs.emplace_back().get<char>(ctmp_bytes, arena, need);
-		LAUNCH(k_sub_ptop, C, s, C, poff, sw.c_npvst, A.ptop);
-		LAUNCH(k_sub_pin, Q, s, Q, A);
-		const unsigned waves = sched == SPLICE_PARALLEL ? SPLICE_WAVES : 1u;
-		compact_flagged_u8(A.act, Q, list, n_list, ctmp, ctmp_bytes, s);
-		if (sched == SPLICE_REVERSE)
-			LAUNCH(k_sub_reverse_list, Q / 2 + 1, s, Q, n_list, list);
-		KLAUNCH(k_sub_splice_cn, dim3(waves), dim3(64), 0, s, n_list, list, A);
-		compact_flagged_u8(A.touched, Q, list, n_list, ctmp, ctmp_bytes, s);
-		if (sched == SPLICE_REVERSE)
-			LAUNCH(k_sub_reverse_list, Q / 2 + 1, s, Q, n_list, list);
-		KLAUNCH(k_sub_midi_find, dim3(waves), dim3(64), 0, s, n_list, list, A);
-		HIP_CHECK(hipMemsetAsync(A.md + Q, 0, 1, s));
-		scan_exclusive_u8(A.md, md_ps, (size_t)Q + 1, nullptr, nullptr, 0, tmp, tmp_bytes, s);
-		KLAUNCH(k_sub_midi_add, dim3(waves), dim3(64), 0, s, n_list, list, A);
-		if (NS)
-			KLAUNCH(k_sub_smothered, dim3(std::min<unsigned>(NC, waves)), dim3(64), 0, s, NC, A);
-		LAUNCH(k_sub_counts, C, s, C, A, counts);
-	} else if (C) {
-		HIP_CHECK(hipMemsetAsync(counts, 0, 3 * (size_t)C * 4, s));
-	}
-	mark("splice");
-	const uint32_t e = host.read_u32(err, s);
-	if (e & E_POOL)
-		throw HipError("subflubble passes: the children vectors outgrew their pool (internal sizing bug)");
-	if (e & E_LAYOUT)
-		throw HipError("subflubble passes: more inserted vertices than the layout has room for (internal sizing bug)");
-	// ---- the children lists, compact
-	uint32_t *ccnt = dev32((size_t)NX + 4), *coff = dev32((size_t)NX + 4);
-	LAUNCH(k_sub_child_counts, (size_t)NX + 1, s, NX, xoff, counts, sw.c_npvst, comp_x, X.vn, ccnt);
-	scan_exclusive_u32(ccnt, coff, (size_t)NX + 1, tmpx, tmpx_bytes, s);
-	const uint32_t NCH = host.read_u32(coff + NX, s);
-	uint32_t *child = dev32((size_t)NCH + 4);
-	LAUNCH(k_sub_child_gather, NCH, s, NCH, NX, coff, X.vbeg, X.pool, child);
-	mark("children lists");
-
-	// ---- to the host: the vertices compacted on the device (X-space has spare slots behind every component), then one copy
-	// per array straight into the forest's vectors
-	std::vector<uint32_t> h_counts(3 * (size_t)C), h_dvoff((size_t)C + 1);
-	if (C)
-		HIP_CHECK(copy_async(h_counts.data(), counts, 3 * (size_t)C * 4, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(hipStreamSynchronize(s));
-	out.voff.assign((size_t)C + 1, 0);
-	uint64_t n_vtx = 0;
-	for (uint32_t c = 0; c < C; c++) {
-		out.voff[c] = n_vtx;
-		h_dvoff[c] = (uint32_t)n_vtx;
-		if (h_np[c])
-			n_vtx += (uint64_t)h_np[c] + h_counts[3 * c] + h_counts[3 * c + 1] + h_counts[3 * c + 2];
-	}
-	out.voff[C] = n_vtx;
-	h_dvoff[C] = (uint32_t)n_vtx;
-	out.counts = h_counts;
-	const uint32_t NV = (uint32_t)n_vtx;
-	uint32_t *dvoff = dev32((size_t)C + 2);
-	HIP_CHECK(hipMemcpyAsync(dvoff, h_dvoff.data(), ((size_t)C + 1) * 4, hipMemcpyHostToDevice, s));
-	uint8_t *d_fam = dev8((size_t)NV + 4), *d_or1 = dev8((size_t)NV + 4), *d_or2 = dev8((size_t)NV + 4), *d_route = dev8((size_t)NV + 4);
-	uint32_t *d_id1 = dev32((size_t)NV + 4), *d_id2 = dev32((size_t)NV + 4), *d_coff = dev32((size_t)NV + 4);
-	LAUNCH(k_sub_compact, NV, s, NV, C, dvoff, xoff, X, coff, d_fam, d_or1, d_or2, d_route, d_id1, d_id2, d_coff);
-	// one page-locked block: fam | or1 | or2 | route | id1 | id2 | coff (+ 1) | child, one spare entry each
-	const forest_wire::SubBlockLayout L(NV, NCH, 0, 1);
-	if (!pool)
-		throw HipError("subflubble passes: no pool of page-locked memory (internal)");
-	out.pool = pool;
-	out.blk = pool->get(L.end + 64, out.blk_cap, &out.blk_seg);
-	char *hb = static_cast<char *>(out.blk);
-	auto d2h = [&](size_t at, const void *src, size_t bytes) {
-		if (bytes)
-			HIP_CHECK(copy_async(hb + at, src, bytes, hipMemcpyDeviceToHost, s));
-	};
-	d2h(L.fam, d_fam, NV);
-	d2h(L.or1, d_or1, NV);
-	d2h(L.or2, d_or2, NV);
-	d2h(L.route, d_route, NV);
-	d2h(L.id1, d_id1, (size_t)NV * 4);
-	d2h(L.id2, d_id2, (size_t)NV * 4);
-	d2h(L.coff, d_coff, (size_t)NV * 4);
-	d2h(L.child, child, (size_t)NCH * 4); // (the lists are compact already, in vertex order)
-	HIP_CHECK(hipStreamSynchronize(s));
-	reinterpret_cast<uint32_t *>(hb + L.coff)[NV] = NCH;
-	out.n_vtx = n_vtx, out.n_child = NCH;
-	out.point(hb, L);
-	if (arena_hint)
-		*arena_hint = need; // (the next call on this context reserves that much up front)
-	mark("to the host");
+void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, const TreeWs &tw, const LeafState &ls, uint32_t C,
+		     HostScratch &host, SubForest &out, const std::shared_ptr<::PinnedPool> &pool, hipStream_t s, SubArenas &arenas)
+{
+	SubPass p(cs, sw, pw, tw, ls, C, host, arenas, s);
+	p.edge_tables_hi();
+	p.creation_keys_lo();
+	p.bracket_rows();
+	p.fill_view();
+	p.search_concealed();
+	p.search_smothered();
+	p.layout_splice();
+	p.seed_vectors();
+	p.splice();
+	p.compact_children();
+	p.to_host(out, pool);
+	if (p.opt.times)
+		fprintf(stderr, "[subflubbles] %-22s %9.1f MiB\n", "phase arenas", (double)arenas.capacity() / (1 << 20));
 }
 
 } // namespace povu_hip

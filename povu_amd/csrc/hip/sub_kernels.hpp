@@ -43,11 +43,20 @@ struct SubForest {
 	}
 };
 
+// The device tables of the inserting passes: one arena per phase, carved when the phase's sizes are known (sub_kernels.hip:
+// tables_spans .. out_spans; DESIGN.md §4 lists them).  A context keeps them from one -s pass to the next -- an arena only
+// grows, and every pass carves it anew from offset 0 -- and a pass without -s releases them.
+struct SubArenas {
+	Arena tables, concealed, smothered, xspace, children, out;
+	void release();
+	size_t capacity() const; // bytes held, all six together
+};
+
 // Runs find_concealed, find_midi and find_smothered on the state leaf_prepare / leaf_dense left (an all-parallel pass whose
-// tree stage also wrote the depths).  Throws HipError when a table outgrows its bound.  `arena` (optional): where the
-// stage's tables go while it has room; *arena_hint = bytes to reserve there up front, updated to what this call needed.
+// tree stage also wrote the depths), all on the stream s; the result is on the host, in `out`, when it returns.  Throws
+// HipError when a table outgrows its bound.  Reads its test and debug switches (POVU_HIP_SUB_*) from the environment on
+// every call.
 void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, const TreeWs &tw, const LeafState &ls, uint32_t C,
-		     HostScratch &host, SubForest &out, const std::shared_ptr<::PinnedPool> &pool, hipStream_t s, Arena *arena = nullptr,
-		     size_t *arena_hint = nullptr);
+		     HostScratch &host, SubForest &out, const std::shared_ptr<::PinnedPool> &pool, hipStream_t s, SubArenas &arenas);
 
 } // namespace povu_hip

@@ -41,15 +41,6 @@ namespace povu_hip
 #ifndef NIL
 #define NIL POVU_NIL
 #endif
-static constexpr int TPB = 256;
-static inline unsigned nblk(size_t n) { return (unsigned)((n + TPB - 1) / TPB); }
-#define LAUNCH(k, n, s, ...)                                                                     \
-	do {                                                                                     \
-		if ((n) > 0) {                                                                   \
-			hipLaunchKernelGGL(k, dim3(nblk(n)), dim3(TPB), 0, s, __VA_ARGS__);      \
-			HIP_CHECK(hipGetLastError());                                            \
-		}                                                                                \
-	} while (0)
 
 // ---- list-ranking words and splitters (section "work-efficient list ranking" below).
 // Splitters cut every list into short segments.  The index space of a list level is cut into buckets of 2^b
@@ -1848,7 +1839,7 @@ __global__ void k_edge_id_weights(uint32_t nS, const uint32_t *__restrict__ loff
 	}
 	tail[p] = cnt;
 }
-void debug_edge_id_weights(const CompState &cs, const SeqWs &sw, const TreeWs &tw, uint32_t *w, uint32_t *tail, hipStream_t s)
+void edge_id_weights(const CompState &cs, const SeqWs &sw, const TreeWs &tw, uint32_t *w, uint32_t *tail, hipStream_t s)
 {
 	const uint32_t nS = 2 * sw.V;
 	LAUNCH(k_edge_id_weights, nS, s, nS, cs.loff, cs.ladj, tw.dps, tw.side_tidx, cs.ckey, cs.voff, sw.t_par,

@@ -64,8 +64,9 @@ int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw,
 void debug_list_rank(uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads, uint32_t nh, int mode,
 		     unsigned bits, uint32_t *ra, uint32_t *rb, hipStream_t s);
 
-// conformance export: back edges from_bd creates just before each tree vertex (w, T-space) and after the last child of
-// each (tail, T-space); both arrays must be zeroed by the caller.  Reads the state of the last run_parallel_tree.
-void debug_edge_id_weights(const CompState &cs, const SeqWs &sw, const TreeWs &tw, uint32_t *w, uint32_t *tail, hipStream_t s);
+// back edges from_bd creates just before each tree vertex (w, T-space) and after the last child of each (tail, T-space); both
+// arrays must be zeroed by the caller.  Reads the state of the last run_parallel_tree.  Callers: the leaf passes and the
+// inserting passes of -s, and the conformance export (debug_hooks.hip).
+void edge_id_weights(const CompState &cs, const SeqWs &sw, const TreeWs &tw, uint32_t *w, uint32_t *tail, hipStream_t s);
 
 } // namespace povu_hip

@@ -37,9 +37,9 @@ def pinned(copies):
     return disjoint_union([seed_graph(p) for p in PINNED_SEEDS] * copies)
 
 
-def check(hip, g, tips=None, flags=F_SUBFLUBBLES):
+def check(hip, g, tips=None, flags=F_SUBFLUBBLES, texts=None):
     """the device's texts against the oracle's, component by component; returns the line kinds and how often the oracle
-    ran a nesting over a pinned concealed vertex"""
+    ran a nesting over a pinned concealed vertex (texts: a list that takes the device's texts)"""
     sub_stats()
     want = O.decompose(g, tips=tips, leaf=2 if flags & F_SUBFLUBBLES else bool(flags & F_LEAF_SUBFLUBBLES))
     seen = collections.Counter(pinned=sub_stats()["nest_over_pinned"])
@@ -48,6 +48,8 @@ def check(hip, g, tips=None, flags=F_SUBFLUBBLES):
     if flags & F_ASYNC:
         f.wait()
     got = f.texts()
+    if texts is not None:
+        texts.append(got)
     assert got.keys() == want.keys()
     for c in want:
         assert got[c] == want[c], f"component {c}:\n--- HIP\n{got[c]}\n--- oracle\n{want[c]}"
@@ -140,6 +142,30 @@ def test_a_context_reused_on_a_different_graph(monkeypatch):
         check(d, b)
     finally:
         d.close()
+
+
+def test_phase_arenas_grow_shrink_and_stay_empty(monkeypatch):
+    """The tables of `-s` lie in one arena per phase, carved when the phase's sizes are known and kept from pass to pass.  One
+    fresh context, default schedule, through passes whose phases are empty (no concealed vertex: every later phase has
+    nothing), tiny (one record, no smothered one), and full, so that each arena is carved empty, reused while too small and
+    reused while full of a larger forest."""
+    monkeypatch.delenv(ENV, raising=False)
+    zi = rule_graph("zi_trunk")
+    steps = [(W.chain_of_bubbles(50), None), (pinned(20), None), (zi, rule_tips("zi_trunk", zi)), (W.nested_towers(6, 3), None),
+             (pinned(20), None), (W.chain_of_bubbles(6), None)]
+    d = HipDecomposer(0)
+    try:
+        seen, texts = [], []
+        for g, tips in steps:
+            seen.append(check(d, g, tips, texts=texts))
+    finally:
+        d.close()
+    for i in (0, 3, 5):
+        assert seen[i]["C"] == 0 and seen[i]["M"] == 0 and seen[i]["S"] == 0, (i, seen[i])
+    assert seen[2]["C"] == 1 and seen[2]["S"] == 0, seen[2]
+    for i in (1, 4):
+        assert seen[i]["C"] >= 400 and seen[i]["M"] >= 50 and seen[i]["S"] >= 20, (i, seen[i])
+    assert texts[1] == texts[4]
 
 
 def test_one_context_through_every_mode(monkeypatch):
