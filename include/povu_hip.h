@@ -640,6 +640,7 @@ typedef struct {
 	uint32_t n_paths;
 	const uint32_t *slot_of_path; /* [n_paths] for povu_hip_call */
 	const char *const *sample;	/* [refs.n_samples] names, in column order */
+	const int64_t *slot_hap;	/* [refs.n_slots] PanSN hap number of the slot, -1 for a name that has none */
 } povu_hip_call_names;
 /* NULL and a message that lists the prefixes when no name starts with one of them.  Free with _free. */
 povu_hip_call_names *povu_hip_call_names_make(uint32_t n_paths, const char *const *path_name, uint32_t n_prefixes,
@@ -691,6 +692,101 @@ char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *
 char *povu_hip_calls_vcf_rest(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
 			      const char *const *path_name, const char *date, const char *const *prefix, uint32_t n_prefixes, uint32_t threads,
 			      uint32_t profile, size_t *len);
+
+/* ---- VCF checks ("VCF checks": decided here, pinned where the reference states it): does a VCF still
+ * describe the graph?  For every record and every haplotype that carries an allele, the allele's AT walk must occur in a path
+ * of that haplotype (zien::validate::validate_vcf_records, src/zien/validate/validate.cpp, bounded by the path and with the
+ * reverse reading accepted) ---- */
+/* the status of a task: a (record, sample column, phase) with a called allele */
+#define POVU_HIP_V_FOUND_FWD 0u /* the walk occurs contiguously in a path of the task's slot, entirely inside that path */
+#define POVU_HIP_V_FOUND_REV 1u /* not forward, but flip(w[m - 1]) .. flip(w[0]) does (ABSENT under POVU_HIP_V_FORWARD_ONLY) */
+#define POVU_HIP_V_ABSENT 2u
+#define POVU_HIP_V_NO_AT 3u    /* no AT, fewer walks than the allele's number + 1, or an empty walk */
+#define POVU_HIP_V_BAD_STEP 4u /* a step names a segment the graph does not have */
+#define POVU_HIP_V_NO_SLOT 5u  /* no sample has the column's name, or the phase is beyond its slots */
+/* (checked in this order: NO_AT, BAD_STEP, NO_SLOT, FOUND_FWD, FOUND_REV, ABSENT).  As a record's reason also: */
+#define POVU_HIP_V_MISSPELLED 6u
+#define POVU_HIP_V_N_STATUS 6u /* task statuses */
+/* the spelling of an allele (POVU_HIP_V_SPELLING): not checked (the flag is off, no walk, a walk with a bad step or no text for
+ * it), the text is the concatenation of all steps, of the first step's last base and the other steps, or neither */
+#define POVU_HIP_V_SPELL_NONE 0u
+#define POVU_HIP_V_SPELL_WHOLE 1u
+#define POVU_HIP_V_SPELL_ANCHORED 2u
+#define POVU_HIP_V_SPELL_MISSPELLED 3u
+/* povu_hip_vcf_opts.flags */
+#define POVU_HIP_V_FORWARD_ONLY 1u /* the reference's literal rule: a walk found only reversed is ABSENT */
+#define POVU_HIP_V_SPELLING 2u	   /* also compare REF / ALT with the sequences of the walks (needs povu_hip_segments_upload) */
+#define POVU_HIP_V_FORCE_TIER2 4u  /* every search through the wave-per-unit kernel (tests) */
+/* A parsed VCF (host only).  Alleles of a record: REF, then the ALTs (`.`: none), then one without text for every AT walk beyond
+ * them.  An allele's steps are its AT walk ([step_off[a], step_off[a + 1]); allele_walk 0: the record's AT has no such walk, which
+ * differs from an empty one only in the text), its text REF or the ALT as written.  Tasks: per record in (allele, column, phase)
+ * order, the allele numbered within the record (it may lie beyond the record's alleles: NO_AT). */
+typedef struct {
+	uint64_t n_samples, n_records, n_alleles, n_steps, n_text_bytes, n_tasks, n_id_bytes;
+	const char *const *sample;  /* [n_samples] the names of the sample columns */
+	const uint64_t *rec_line;   /* [n_records] line of the text, from 1 */
+	const uint64_t *rec_pos;    /* [n_records] POS */
+	const uint64_t *rec_id_off; /* [n_records + 1] ID of record r: ids[rec_id_off[r] .. rec_id_off[r + 1]) */
+	const char *ids;
+	const uint64_t *allele_off; /* [n_records + 1] alleles of record r */
+	const uint64_t *task_off;   /* [n_records + 1] tasks of record r */
+	const uint64_t *step_off;   /* [n_alleles + 1] */
+	const uint64_t *text_off;   /* [n_alleles + 1] */
+	const uint8_t *allele_walk; /* [n_alleles] 1: AT holds a walk for the allele; bit 1 (2): the allele has a text */
+	const uint32_t *step_id;    /* [n_steps] segment id */
+	const uint8_t *step_or;	    /* [n_steps] 0 '>', 1 '<' */
+	const char *text;	    /* [n_text_bytes] */
+	const uint32_t *task_record, *task_allele, *task_col, *task_phase; /* [n_tasks] */
+} povu_hip_vcf_doc;
+/* Reads VCF text: the #CHROM line names the sample columns; per record ID, POS, REF, ALT, the AT key of INFO (comma-separated,
+ * one walk per allele, REF first; a walk is `[<>]id` repeated) and the GT subfield, whose position is found in FORMAT (a record
+ * without GT has no tasks).  A GT is split at `|` and `/`, entry j is phase j, `.` entries are skipped.  The records are parsed in
+ * chunks on up to `threads` threads.  A malformed line (fewer than 8 columns, a column count that differs from the #CHROM
+ * line's, a POS or a GT entry that is no number, a walk that is no walk, a record in front of the #CHROM line) is refused: NULL and
+ * a message that begins `line <n>: `; of several the first.  Free with povu_hip_vcf_doc_free. */
+povu_hip_vcf_doc *povu_hip_vcf_parse(const char *text, size_t len, uint32_t threads, char *err, size_t errlen);
+void povu_hip_vcf_doc_free(povu_hip_vcf_doc *d);
+/* The samples and slots of the paths named `path_name` by the rule of povu_hip_call_names_make, without reference prefixes
+ * (refs.n_refs is 0).  Free with povu_hip_call_names_free. */
+povu_hip_call_names *povu_hip_vcf_names_make(uint32_t n_paths, const char *const *path_name, char *err, size_t errlen);
+/* Column c, phase j of `doc` is the j-th slot of the sample named like the column: col_first[c] that sample's first slot and
+ * col_slots[c] the number of its slots (0: no sample has the name).  [doc->n_samples] each.  0 on success */
+int povu_hip_vcf_columns(const povu_hip_vcf_doc *doc, const povu_hip_call_names *names, uint32_t *col_first, uint32_t *col_slots);
+typedef struct {
+	uint32_t flags; /* POVU_HIP_V_* */
+} povu_hip_vcf_opts;
+typedef struct {
+	uint64_t n_records, n_tasks, n_alleles;
+	const uint8_t *task_status;  /* [n_tasks] POVU_HIP_V_FOUND_FWD .. _NO_SLOT */
+	const uint8_t *allele_spell; /* [n_alleles] POVU_HIP_V_SPELL_* */
+	const uint8_t *rec_invalid;  /* [n_records] 1: a task is not FOUND_*, or an allele is misspelled */
+	/* the first failure of an invalid record in (allele, column, phase) order, a misspelled allele in front of the tasks of that
+	 * allele: its reason (a status, or POVU_HIP_V_MISSPELLED), its allele within the record and its task (POVU_HIP_NIL for a
+	 * misspelled allele; all three POVU_HIP_NIL / 0xFF for a valid record) */
+	const uint8_t *rec_reason;
+	const uint32_t *rec_allele, *rec_task;
+	uint64_t n_status[POVU_HIP_V_N_STATUS]; /* tasks of every status */
+	uint64_t n_invalid, n_misspelled;
+	uint64_t n_tier2; /* (allele, direction) searches the wave-per-unit kernel ran */
+	double device_ms; /* HIP-event time of the call, first upload to last byte on the host */
+} povu_hip_vcf_report;
+/* Checks `doc` against the graph and the paths resident in `ctx`; names: of the resident paths' names (povu_hip_vcf_names_make or
+ * povu_hip_call_names_make).  One search per (allele, direction) over the index of the occurrences of every path word, whatever
+ * the number of slots that carry the allele.  opts NULL = no flag.  Refused when no graph or no paths are resident, when `names`
+ * is of another number of paths, with POVU_HIP_V_SPELLING when no sequences are resident, when the segment ids do not ascend
+ * with the vertex index, on 2^32 path steps, alleles, steps, tasks or (allele, slot) pairs or more, and when device memory runs
+ * out.  Free with povu_hip_vcf_report_free. */
+povu_hip_vcf_report *povu_hip_vcf_check(povu_hip_ctx *ctx, const povu_hip_vcf_doc *doc, const povu_hip_call_names *names,
+					const povu_hip_vcf_opts *opts, char *err, size_t errlen);
+void povu_hip_vcf_report_free(povu_hip_vcf_report *r);
+/* Both files of `povu vcf --report` (host only; the report may be hand-made).  report.tsv: the reference's header
+ * `rec_idx ID POS AT Hap ID sample` (tabs) and a seventh column `reason`, then one line per invalid record for its first failure:
+ * the record's index, ID and POS, the failing allele's walk written `[<>]id` (empty without one), the PanSN hap number of the
+ * task's slot (1 when the name has none or there is no slot; `.` for a misspelled allele), the column's name (`.` likewise) and
+ * the lower-case status name.  summary.txt: `No errors\n`, or `Error rate: %.2f%%\n` of invalid records over all records.  Both
+ * malloc'd (povu_hip_buffer_free); NULL when the three do not belong together. */
+char *povu_hip_vcf_report_text(const povu_hip_vcf_report *r, const povu_hip_vcf_doc *doc, const povu_hip_call_names *names,
+			       size_t *report_len, char **summary, size_t *summary_len);
 
 /* ---- measurement (bench.py, povu-stage-cost lines) ---- */
 typedef struct {

@@ -304,6 +304,13 @@ struct InvRows {
 	uint16_t *gt;
 };
 InvDevice inv_find(povu_hip_ctx *ctx, const InvIn &in);
+// The step index alone, for the inversion calls and the VCF checks (vcfcheck_kernels.hip): the occurrences of every path word,
+// carved from `A` (from its offset 0) in front of the caller's own spans (`more`) and built on the context's stream.  The
+// caller has refused 2^32 - 4096 path steps or more; at least one step is resident
+struct StepIndex {
+	const uint32_t *ioff, *occ;
+};
+StepIndex build_step_index(povu_hip_ctx *ctx, Arena &A, const std::function<void(Spans &)> &more);
 // rows of the merged list: f_dst[i] for flubble record i (sorted; its reference number f_ref[i] and POS f_pos[i]), v.dst
 void inv_merge(povu_hip_ctx *ctx, InvDevice &v, uint32_t nrec, const uint32_t *f_ref, const uint64_t *f_pos, uint32_t *f_dst);
 // the per-record fields of the inversion records (AC count 1 into nalt)

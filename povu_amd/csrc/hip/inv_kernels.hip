@@ -4,7 +4,8 @@
 // another path matches step i of a reference path when it is the same segment the other way round (path words differ in
 // bit 0 only), a run is a maximal anti-diagonal of matches, a run of 2 .. max_steps steps that spells a base supports the
 // record (reference, first step, steps).  All of it runs on the paths resident in the context:
-//   step index   the global positions of the path steps, stable-sorted by step value, and a CSR over the 2 V values;
+//   step index   the global positions of the path steps, stable-sorted by step value, and a CSR over the 2 V values
+//                (build_step_index, which the VCF checks of vcfcheck_kernels.hip call too);
 //   run heads    per reference step the entries of the opposite value's list on another path whose predecessor
 //                (i - 1, j + 1) is no match: a lane per reference step for lists below 64 entries, a wave per step (lanes
 //                across the list, a ballot per 64) for the others; count, u64 scan, 2^32 check, emit;
@@ -398,35 +399,46 @@ struct InvHeads {
 };
 } // namespace
 
+// The step index of the resident paths, carved from `A` in front of the caller's own spans (`more`) and built on the context's
+// stream: the global positions of the path steps stable-sorted by step value, and a CSR over the 2 V values
+StepIndex build_step_index(povu_hip_ctx *ctx, Arena &A, const std::function<void(Spans &)> &more)
+{
+	hipStream_t s = ctx->stream;
+	const uint64_t N = ctx->n_path_steps;
+	const size_t nval = 2 * (size_t)ctx->g.V + 1;
+	const size_t tmp_bytes = std::max(sort_tmp_bytes(N + 1), prim_tmp_bytes(nval + 1, false)) + 256;
+	uint32_t *iota, *skey, *occ, *cnt, *ioff;
+	void *tmp;
+	carve(A, [&](Spans &take) {
+		take(N + 1, iota, skey, occ);
+		take(nval + 1, cnt, ioff);
+		more(take);
+		take(tmp_bytes, tmp);
+	});
+	HIP_CHECK(hipMemsetAsync(cnt, 0, (nval + 1) * 4, s));
+	launch_iota((uint32_t)N, iota, s);
+	KLAUNCH(k_inv_hist, dim3(stride_blocks(N)), dim3(Q_TPB), 0, s, (uint32_t)N, ctx->path_steps, cnt);
+	scan_exclusive_u32(cnt, ioff, nval, tmp, tmp_bytes, s);
+	sort_pairs_u32(ctx->path_steps, skey, iota, occ, N, bits_for(2 * (uint64_t)ctx->g.V), tmp, tmp_bytes, s);
+	return StepIndex{ioff, occ};
+}
+
 static InvIndex step_index(povu_hip_ctx *ctx, const InvIn &in, InvDevice &v)
 {
 	hipStream_t s = ctx->stream;
-	const uint64_t N = ctx->n_path_steps, NR = in.ref.NR;
-	const uint32_t V = ctx->g.V;
-	const size_t nval = 2 * (size_t)V + 1;
-	const size_t tmp_bytes = std::max(sort_tmp_bytes(N + 1), prim_tmp_bytes(nval + 1, false)) + 256;
+	const uint64_t NR = in.ref.NR;
 	InvIndex x;
-	uint32_t *iota, *skey, *occ, *cnt, *ioff;
-	void *tmp;
-	carve(ctx->iv_ws, [&](Spans &take) {
-		take(N + 1, iota, skey, occ);
-		take(nval + 1, cnt, ioff);
+	const StepIndex ix = build_step_index(ctx, ctx->iv_ws, [&](Spans &take) {
 		take(NR + 1, x.hcnt, x.hoff, x.longs);
 		take(scan_exclusive_u64_tmp(NR + 1), x.s64);
 		take(8, x.words);
 		take(1, x.n_long);
-		take(tmp_bytes, tmp);
 	});
-	HIP_CHECK(hipMemsetAsync(cnt, 0, (nval + 1) * 4, s));
 	HIP_CHECK(hipMemsetAsync(x.words, 0, 32, s));
 	HIP_CHECK(hipMemsetAsync(x.n_long, 0, 8, s));
 	HIP_CHECK(hipMemsetAsync(x.hcnt, 0, (NR + 1) * 8, s));
-	launch_iota((uint32_t)N, iota, s);
-	KLAUNCH(k_inv_hist, dim3(stride_blocks(N)), dim3(Q_TPB), 0, s, (uint32_t)N, ctx->path_steps, cnt);
-	scan_exclusive_u32(cnt, ioff, nval, tmp, tmp_bytes, s);
-	sort_pairs_u32(ctx->path_steps, skey, iota, occ, N, bits_for(2 * (uint64_t)V), tmp, tmp_bytes, s);
-	v.ioff = ioff;
-	v.occ = occ;
+	v.ioff = ix.ioff;
+	v.occ = ix.occ;
 	x.long_min = in.force_tier2 ? 0 : LONG_LIST;
 	return x;
 }

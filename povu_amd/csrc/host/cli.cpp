@@ -5,6 +5,8 @@
 //   povu ... gfa2vcf -i <gfa> [-h] [-s] [--structure-export <json>] <options of `call`>   (app/cli/cli.cpp:154-193)
 //   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--profile <p>] [--merge-primitives] [--off-reference]   (the
 //   variant calls of INTEGRATION.md "Variant calls" and "Inversion calls", on the GPU)
+//   povu ... vcf -i <gfa> -c <vcf> --report -o <dir> [--spelling] [--forward-only]   (the --report half of the reference's `vcf`,
+//   app/cli/cli.cpp; INTEGRATION.md "VCF checks", on the GPU)
 #include "decompose.hpp"
 
 #include <cstdlib>
@@ -28,6 +30,7 @@ static void usage(std::ostream &os)
 	      "        prune                             Reduce GFA to graph structure\n"
 	      "        gfa2vcf                           Convert GFA to VCF (decompose here + `call` of $POVU_CALL_EXE)\n"
 	      "        call                              Call variants of a forest on the GPU and write VCF\n"
+	      "        vcf                               Check a VCF against the graph on the GPU (--report)\n"
 	      "      arguments\n"
 	      "        --version                         The current version of povu\n"
 	      "        -v[verbosity],\n"
@@ -81,7 +84,18 @@ static void usage(std::ostream &os)
 	      "                                          popped: a record with a longer REF / allele is big (0: no limit) [default: 0]\n"
 	      "                                          decomposed: --max-allele-length is the longest allele that is aligned, a longer\n"
 	      "                                          one is kept whole (0: 512, the most) [default: 0]\n"
-	      "        -c, -q                            accepted and ignored (no streaming here)\n";
+	      "        -c, -q                            accepted and ignored (no streaming here)\n\n"
+	      "  vcf OPTIONS:\n"
+	      "        -i[gfa], --input-gfa=[gfa]        path to input gfa [required]\n"
+	      "        -c[vcf], --vcf=[vcf]              path to the VCF to check [required]\n"
+	      "        --report                          check every called allele's AT walk against the paths of its haplotype\n"
+	      "                                          and write report.tsv and summary.txt [required: --tui is not provided]\n"
+	      "        -o[output_dir], --output-dir=[output_dir]\n"
+	      "                                          Output directory [default: .]\n"
+	      "        --spelling                        also compare REF and ALT with the sequences of their walks (raw-graph\n"
+	      "                                          output; rewritten records fail it) [default: false]\n"
+	      "        --forward-only                    the reference's literal rule: a walk found only reversed is absent\n"
+	      "                                          [default: false]\n";
 }
 
 int main(int argc, char **argv)
@@ -124,7 +138,7 @@ int main(int argc, char **argv)
 			print_tips = true; // inside `info`, -t means "print the tips" (cli.cpp:220)
 		} else if (value(i, a, "-t", "--threads", v)) {
 			cfg.threads = atoi(v.c_str());
-		} else if ((command == "decompose" || command == "info" || command == "prune" || command == "gfa2vcf" || command == "call") &&
+		} else if ((command == "decompose" || command == "info" || command == "prune" || command == "gfa2vcf" || command == "call" || command == "vcf") &&
 			   value(i, a, "-i", "--input-gfa", v)) {
 			cfg.input_gfa = v;
 			have_input = true;
@@ -155,7 +169,7 @@ int main(int argc, char **argv)
 				usage(std::cerr);
 				return 1;
 			}
-		} else if (command == "gfa2vcf" || command == "call") {
+		} else if (command == "gfa2vcf" || command == "call" || command == "vcf") {
 			call_args.push_back(a); // streaming / output / reference options of `call` (cli.cpp:28-88)
 		} else if (command.empty() && a[0] != '-') {
 			command = a;
@@ -179,8 +193,8 @@ int main(int argc, char **argv)
 		usage(std::cout);
 		return 0;
 	}
-	if (command != "decompose" && command != "info" && command != "prune" && command != "gfa2vcf" && command != "call") {
-		std::cerr << "povu (MI355X build): only `decompose`, `info`, `prune`, `gfa2vcf` and `call` are provided; `" << command
+	if (command != "decompose" && command != "info" && command != "prune" && command != "gfa2vcf" && command != "call" && command != "vcf") {
+		std::cerr << "povu (MI355X build): only `decompose`, `info`, `prune`, `gfa2vcf`, `call` and `vcf` are provided; `" << command
 			  << "` belongs to the reference CPU tool" << std::endl;
 		return 1;
 	}
@@ -202,6 +216,8 @@ int main(int argc, char **argv)
 			povu_host::do_gfa2vcf(cfg, call_args);
 		else if (command == "call")
 			povu_host::do_call(cfg, call_args);
+		else if (command == "vcf")
+			povu_host::do_vcf(cfg, call_args);
 		else {
 			povu_host::reset_debug_sidecar(cfg);
 			cfg.exit_when_done = true;

@@ -55,6 +55,9 @@ void do_prune(const Config &cfg);
 // `povu call` (INTEGRATION.md "Variant calls"): the PVSTs of -f <dir> called on the GPU with the GFA's paths and sequences,
 // written as VCF; `args` are the options after `call` that main() does not parse itself
 void do_call(const Config &cfg, const std::vector<std::string> &args);
+// `povu vcf --report` (INTEGRATION.md "VCF checks"): the VCF of -c checked on the GPU against the GFA's paths (and, with
+// --spelling, sequences), report.tsv and summary.txt written to -o <dir>; `args` as for do_call
+void do_vcf(const Config &cfg, const std::vector<std::string> &args);
 
 // device of every rank of `--gpus N` (POVU_HIP_DEVICES or 0 .. N-1), checked against the number of visible devices
 std::vector<int> multi_devices(int gpus, const char *env, int visible);

@@ -93,6 +93,7 @@ struct Names {
 	std::vector<uint32_t> ref_path, sample_of_slot, slot_of_path;
 	std::vector<std::string> sample;
 	std::vector<const char *> sample_ptr;
+	std::vector<int64_t> slot_hap;
 };
 
 template <class T> bool grow(const T *&p, size_t n)
@@ -105,8 +106,9 @@ template <class T> bool grow(const T *&p, size_t n)
 
 } // namespace
 
-extern "C" povu_hip_call_names *povu_hip_call_names_make(uint32_t n_paths, const char *const *path_name, uint32_t n_prefixes,
-							 const char *const *prefix, char *err, size_t errlen)
+// need_ref: a call's names (no reference path is refused); else the samples and slots alone ("VCF checks")
+static povu_hip_call_names *names_make(uint32_t n_paths, const char *const *path_name, uint32_t n_prefixes, const char *const *prefix,
+				       bool need_ref, char *err, size_t errlen)
 try {
 	if ((n_paths && !path_name) || (n_prefixes && !prefix)) {
 		set_err(err, errlen, "call names: bad arguments");
@@ -129,7 +131,7 @@ try {
 		if (std::find(hv.begin(), hv.end(), key[k].second) == hv.end())
 			hv.push_back(key[k].second);
 	}
-	if (nm->ref_path.empty()) {
+	if (need_ref && nm->ref_path.empty()) {
 		std::string l;
 		for (uint32_t p = 0; p < n_prefixes; p++)
 			l += std::string(l.empty() ? "" : ", ") + prefix[p];
@@ -143,6 +145,7 @@ try {
 		for (long long h : hv) {
 			slot_id[{nm->sample[si], h}] = (uint32_t)nm->sample_of_slot.size();
 			nm->sample_of_slot.push_back(si);
+			nm->slot_hap.push_back(h);
 		}
 		nm->sample_ptr.push_back(nm->sample[si].c_str());
 	}
@@ -150,11 +153,22 @@ try {
 		nm->slot_of_path.push_back(slot_id[key[k]]);
 	nm->pub = {{(uint32_t)nm->ref_path.size(), nm->ref_path.data(), (uint32_t)nm->sample_of_slot.size(), (uint32_t)nm->sample.size(),
 		    nm->sample_of_slot.data()},
-		   n_paths, nm->slot_of_path.data(), nm->sample_ptr.data()};
+		   n_paths, nm->slot_of_path.data(), nm->sample_ptr.data(), nm->slot_hap.data()};
 	return &nm.release()->pub;
 } catch (const std::bad_alloc &) {
 	set_err(err, errlen, "call names: out of memory");
 	return nullptr;
+}
+
+extern "C" povu_hip_call_names *povu_hip_call_names_make(uint32_t n_paths, const char *const *path_name, uint32_t n_prefixes,
+							 const char *const *prefix, char *err, size_t errlen)
+{
+	return names_make(n_paths, path_name, n_prefixes, prefix, true, err, errlen);
+}
+
+extern "C" povu_hip_call_names *povu_hip_vcf_names_make(uint32_t n_paths, const char *const *path_name, char *err, size_t errlen)
+{
+	return names_make(n_paths, path_name, 0, nullptr, false, err, errlen);
 }
 
 extern "C" void povu_hip_call_names_free(povu_hip_call_names *n) { delete reinterpret_cast<Names *>(n); }

@@ -1,0 +1,424 @@
+// vcfcheck.cpp -- the host half of the VCF checks (INTEGRATION.md "VCF checks"), host only: VCF text to the alleles, walks and
+// tasks povu_hip_vcf_check takes (records parsed in chunks on several threads), the sample columns to slots, and a report to the
+// two files of `povu vcf --report`.  tests/vcfcheck_ref.py restates it as the yardstick.
+#include "../../../include/povu_hip.h"
+#include "../hip/vcfcheck_rules.hpp"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+namespace
+{
+
+using povu_hip::vc_next_step;
+
+void set_err(char *err, size_t n, const std::string &m)
+{
+	if (err && n)
+		snprintf(err, n, "%s", m.c_str());
+}
+
+struct Span {
+	const char *p;
+	size_t n;
+	bool is(const char *s) const { return n == strlen(s) && !memcmp(p, s, n); }
+};
+// the pieces of [p, p + n) between the separators `seps` (one or two bytes)
+void split(const char *p, size_t n, const char *seps, std::vector<Span> &out)
+{
+	out.clear();
+	size_t b = 0;
+	for (size_t i = 0; i <= n; i++)
+		if (i == n || p[i] == seps[0] || (seps[1] && p[i] == seps[1])) {
+			out.push_back({p + b, i - b});
+			b = i + 1;
+		}
+}
+bool number(const Span &s, uint64_t max, uint64_t *v)
+{
+	if (!s.n || s.n > 19)
+		return false;
+	uint64_t x = 0;
+	for (size_t i = 0; i < s.n; i++) {
+		if (s.p[i] < '0' || s.p[i] > '9')
+			return false;
+		x = x * 10 + (uint64_t)(s.p[i] - '0');
+	}
+	*v = x;
+	return x <= max;
+}
+
+struct Line {
+	size_t off, len;
+	uint64_t no;
+};
+struct Task {
+	uint32_t allele, col, phase;
+};
+// what a chunk of records parses to; offsets are the chunk's own
+struct Chunk {
+	std::vector<uint64_t> line, pos, id_off{0}, allele_off{0}, task_off{0}, step_off{0}, text_off{0};
+	std::vector<uint8_t> allele_walk, step_or;
+	std::vector<uint32_t> step_id, task_allele, task_col, task_phase;
+	std::string ids, text;
+	uint64_t bad_line = 0; // the first malformed line, 0: none
+	std::string bad;
+};
+
+struct Malformed {
+	std::string why;
+};
+
+void parse_record(const char *text, const Line &ln, size_t n_samples, Chunk &c)
+{
+	std::vector<Span> f, part, sub, gt;
+	split(text + ln.off, ln.len, "\t", f);
+	if (f.size() < 8)
+		throw Malformed{"a record needs at least 8 columns, this one has " + std::to_string(f.size())};
+	if (f.size() > 8 && f.size() != 9 + n_samples)
+		throw Malformed{"the #CHROM line names " + std::to_string(n_samples) + " sample columns, this record has " +
+				std::to_string(f.size() - 9)};
+	uint64_t pos = 0;
+	if (!number(f[1], ~0ull, &pos))
+		throw Malformed{"POS is no number: " + std::string(f[1].p, f[1].n)};
+	// the texts: REF, then the ALTs
+	std::vector<Span> texts{f[3]};
+	if (!f[4].is(".")) {
+		split(f[4].p, f[4].n, ",", part);
+		texts.insert(texts.end(), part.begin(), part.end());
+	}
+	// the walks
+	std::vector<Span> walks;
+	split(f[7].p, f[7].n, ";", part);
+	for (const Span &kv : part)
+		if (kv.n >= 3 && !memcmp(kv.p, "AT=", 3)) {
+			split(kv.p + 3, kv.n - 3, ",", walks);
+			break;
+		}
+	const size_t n_al = std::max(texts.size(), walks.size());
+	for (size_t a = 0; a < n_al; a++) {
+		if (a < walks.size()) {
+			size_t i = 0;
+			uint32_t id = 0;
+			uint8_t rev = 0;
+			int t;
+			while ((t = vc_next_step(walks[a].p, walks[a].n, &i, &id, &rev)) == povu_hip::VC_TOKEN_STEP) {
+				c.step_id.push_back(id);
+				c.step_or.push_back(rev);
+			}
+			if (t == povu_hip::VC_TOKEN_BAD)
+				throw Malformed{"AT walk " + std::to_string(a) + " is no walk of [<>]id steps: " + std::string(walks[a].p, walks[a].n)};
+		}
+		if (a < texts.size())
+			c.text.append(texts[a].p, texts[a].n);
+		c.allele_walk.push_back((uint8_t)((a < walks.size() ? 1 : 0) | (a < texts.size() ? 2 : 0)));
+		c.step_off.push_back(c.step_id.size());
+		c.text_off.push_back(c.text.size());
+	}
+	// the tasks, in (allele, column, phase) order
+	std::vector<Task> tasks;
+	if (f.size() > 8) {
+		split(f[8].p, f[8].n, ":", part);
+		size_t at = part.size();
+		for (size_t k = 0; k < part.size() && at == part.size(); k++)
+			if (part[k].is("GT"))
+				at = k;
+		for (size_t s = 0; at < part.size() && s < n_samples; s++) {
+			split(f[9 + s].p, f[9 + s].n, ":", sub);
+			if (at >= sub.size())
+				continue;
+			split(sub[at].p, sub[at].n, "|/", gt);
+			for (size_t j = 0; j < gt.size(); j++) {
+				if (gt[j].is("."))
+					continue;
+				uint64_t a = 0;
+				if (!number(gt[j], 0xFFFFFFFEull, &a))
+					throw Malformed{"GT of sample column " + std::to_string(s) + " is no genotype: " + std::string(sub[at].p, sub[at].n)};
+				tasks.push_back({(uint32_t)a, (uint32_t)s, (uint32_t)j});
+			}
+		}
+	}
+	std::stable_sort(tasks.begin(), tasks.end(), [](const Task &x, const Task &y) { return x.allele < y.allele; });
+	for (const Task &t : tasks) {
+		c.task_allele.push_back(t.allele);
+		c.task_col.push_back(t.col);
+		c.task_phase.push_back(t.phase);
+	}
+	c.line.push_back(ln.no);
+	c.pos.push_back(pos);
+	c.ids.append(f[2].p, f[2].n);
+	c.id_off.push_back(c.ids.size());
+	c.allele_off.push_back(c.allele_walk.size());
+	c.task_off.push_back(c.task_allele.size());
+}
+
+void parse_chunk(const char *text, const Line *lines, size_t n, size_t n_samples, Chunk &c)
+{
+	for (size_t k = 0; k < n; k++) {
+		// (what a malformed line has appended so far stays in no array: the chunk is dropped with the parse)
+		try {
+			parse_record(text, lines[k], n_samples, c);
+		} catch (const Malformed &m) {
+			c.bad_line = lines[k].no;
+			c.bad = m.why;
+			return;
+		}
+	}
+}
+
+struct Doc {
+	povu_hip_vcf_doc pub{}; // (first: the handle points at it)
+	std::vector<std::string> sample;
+	std::vector<const char *> sample_ptr;
+	std::vector<uint64_t> line, pos, id_off{0}, allele_off{0}, task_off{0}, step_off{0}, text_off{0};
+	std::vector<uint8_t> allele_walk, step_or;
+	std::vector<uint32_t> step_id, task_record, task_allele, task_col, task_phase;
+	std::string ids, text;
+};
+
+template <class T> void append(std::vector<T> &to, const std::vector<T> &from) { to.insert(to.end(), from.begin(), from.end()); }
+// offsets of a chunk behind those of the document: from[0] is 0
+void append_off(std::vector<uint64_t> &to, const std::vector<uint64_t> &from)
+{
+	const uint64_t base = to.back();
+	for (size_t k = 1; k < from.size(); k++)
+		to.push_back(base + from[k]);
+}
+
+const char *STATUS_NAME[] = {"found_fwd", "found_rev", "absent", "no_at", "bad_step", "no_slot", "misspelled"};
+
+// the sample named `name`, or n_samples
+uint32_t sample_of(const povu_hip_call_names *names, const char *name)
+{
+	for (uint32_t s = 0; s < names->refs.n_samples; s++)
+		if (!strcmp(names->sample[s], name))
+			return s;
+	return names->refs.n_samples;
+}
+
+char *to_buffer(const std::string &s, size_t *len)
+{
+	char *p = static_cast<char *>(malloc(s.size() + 1));
+	if (!p)
+		return nullptr;
+	memcpy(p, s.data(), s.size());
+	p[s.size()] = 0;
+	if (len)
+		*len = s.size();
+	return p;
+}
+
+} // namespace
+
+extern "C" povu_hip_vcf_doc *povu_hip_vcf_parse(const char *text, size_t len, uint32_t threads, char *err, size_t errlen)
+try {
+	if (!text && len) {
+		set_err(err, errlen, "vcf parse: bad arguments");
+		return nullptr;
+	}
+	std::unique_ptr<Doc> d(new Doc);
+	// ---- the lines: the #CHROM line, the records
+	std::vector<Line> lines;
+	bool have_columns = false;
+	uint64_t no = 0;
+	for (size_t b = 0; b < len;) {
+		const char *nl = static_cast<const char *>(memchr(text + b, '\n', len - b));
+		size_t e = nl ? (size_t)(nl - text) : len, n = e - b;
+		no++;
+		if (n && text[b + n - 1] == '\r')
+			n--;
+		if (n && text[b] == '#') {
+			if (n >= 6 && !memcmp(text + b, "#CHROM", 6) && (n == 6 || text[b + 6] == '\t')) {
+				if (have_columns) {
+					set_err(err, errlen, "line " + std::to_string(no) + ": a second #CHROM line");
+					return nullptr;
+				}
+				std::vector<Span> f;
+				split(text + b, n, "\t", f);
+				if (f.size() < 8) {
+					set_err(err, errlen, "line " + std::to_string(no) + ": the #CHROM line needs at least 8 columns, this one has " +
+								     std::to_string(f.size()));
+					return nullptr;
+				}
+				for (size_t k = 9; k < f.size(); k++)
+					d->sample.emplace_back(f[k].p, f[k].n);
+				have_columns = true;
+			}
+		} else if (n) {
+			if (!have_columns) {
+				set_err(err, errlen, "line " + std::to_string(no) + ": a record in front of the #CHROM line");
+				return nullptr;
+			}
+			lines.push_back({b, n, no});
+		}
+		b = e + 1;
+	}
+	// ---- the records, in chunks
+	const size_t R = lines.size();
+	const size_t n_chunks = std::max<size_t>(1, std::min<size_t>(std::max<uint32_t>(1, threads), (R + 255) / 256));
+	std::vector<Chunk> chunks(n_chunks);
+	std::vector<std::string> thrown(n_chunks);
+	auto work = [&](size_t k) {
+		const size_t b = R * k / n_chunks, e = R * (k + 1) / n_chunks;
+		try {
+			parse_chunk(text, lines.data() + b, e - b, d->sample.size(), chunks[k]);
+		} catch (const std::exception &x) {
+			thrown[k] = x.what();
+		}
+	};
+	{
+		std::vector<std::thread> pool;
+		for (size_t k = 1; k < n_chunks; k++)
+			pool.emplace_back(work, k);
+		work(0);
+		for (auto &t : pool)
+			t.join();
+	}
+	for (size_t k = 0; k < n_chunks; k++) {
+		if (!thrown[k].empty()) {
+			set_err(err, errlen, "vcf parse: " + thrown[k]);
+			return nullptr;
+		}
+		if (chunks[k].bad_line) {
+			set_err(err, errlen, "line " + std::to_string(chunks[k].bad_line) + ": " + chunks[k].bad);
+			return nullptr;
+		}
+	}
+	for (const Chunk &c : chunks) {
+		const uint64_t r0 = d->line.size();
+		for (size_t r = 0; r + 1 < c.task_off.size(); r++)
+			d->task_record.insert(d->task_record.end(), c.task_off[r + 1] - c.task_off[r], (uint32_t)(r0 + r));
+		append(d->line, c.line);
+		append(d->pos, c.pos);
+		append_off(d->id_off, c.id_off);
+		append_off(d->allele_off, c.allele_off);
+		append_off(d->task_off, c.task_off);
+		append_off(d->step_off, c.step_off);
+		append_off(d->text_off, c.text_off);
+		append(d->allele_walk, c.allele_walk);
+		append(d->step_or, c.step_or);
+		append(d->step_id, c.step_id);
+		append(d->task_allele, c.task_allele);
+		append(d->task_col, c.task_col);
+		append(d->task_phase, c.task_phase);
+		d->ids += c.ids;
+		d->text += c.text;
+	}
+	if (d->line.size() >= 0xFFFFFFFFull) {
+		set_err(err, errlen, "vcf parse: 2^32 records or more are refused");
+		return nullptr;
+	}
+	for (auto &s : d->sample)
+		d->sample_ptr.push_back(s.c_str());
+	povu_hip_vcf_doc &p = d->pub;
+	p.n_samples = d->sample.size();
+	p.n_records = d->line.size();
+	p.n_alleles = d->allele_walk.size();
+	p.n_steps = d->step_id.size();
+	p.n_text_bytes = d->text.size();
+	p.n_tasks = d->task_allele.size();
+	p.n_id_bytes = d->ids.size();
+	p.sample = d->sample_ptr.data();
+	p.rec_line = d->line.data();
+	p.rec_pos = d->pos.data();
+	p.rec_id_off = d->id_off.data();
+	p.ids = d->ids.data();
+	p.allele_off = d->allele_off.data();
+	p.task_off = d->task_off.data();
+	p.step_off = d->step_off.data();
+	p.text_off = d->text_off.data();
+	p.allele_walk = d->allele_walk.data();
+	p.step_id = d->step_id.data();
+	p.step_or = d->step_or.data();
+	p.text = d->text.data();
+	p.task_record = d->task_record.data();
+	p.task_allele = d->task_allele.data();
+	p.task_col = d->task_col.data();
+	p.task_phase = d->task_phase.data();
+	return &d.release()->pub;
+} catch (const std::exception &x) {
+	set_err(err, errlen, std::string("vcf parse: ") + x.what());
+	return nullptr;
+}
+
+extern "C" void povu_hip_vcf_doc_free(povu_hip_vcf_doc *d) { delete reinterpret_cast<Doc *>(d); }
+
+extern "C" int povu_hip_vcf_columns(const povu_hip_vcf_doc *doc, const povu_hip_call_names *names, uint32_t *col_first, uint32_t *col_slots)
+{
+	if (!doc || !names || (doc->n_samples && (!col_first || !col_slots)))
+		return 1;
+	// the slots of a sample are consecutive
+	std::vector<uint32_t> first(names->refs.n_samples + 1, 0), count(names->refs.n_samples + 1, 0);
+	for (uint32_t sl = names->refs.n_slots; sl-- > 0;) {
+		const uint32_t s = names->refs.sample_of_slot[sl];
+		if (s >= names->refs.n_samples)
+			return 1;
+		first[s] = sl;
+		count[s]++;
+	}
+	for (uint64_t c = 0; c < doc->n_samples; c++) {
+		const uint32_t s = sample_of(names, doc->sample[c]);
+		col_first[c] = first[s];
+		col_slots[c] = count[s];
+	}
+	return 0;
+}
+
+extern "C" char *povu_hip_vcf_report_text(const povu_hip_vcf_report *r, const povu_hip_vcf_doc *doc, const povu_hip_call_names *names,
+					  size_t *report_len, char **summary, size_t *summary_len)
+try {
+	if (!r || !doc || !names || !summary || r->n_records != doc->n_records || r->n_tasks != doc->n_tasks || r->n_alleles != doc->n_alleles)
+		return nullptr;
+	std::vector<uint32_t> col_first(doc->n_samples + 1), col_slots(doc->n_samples + 1);
+	if (povu_hip_vcf_columns(doc, names, col_first.data(), col_slots.data()))
+		return nullptr;
+	std::string out = "rec_idx\tID\tPOS\tAT\tHap ID\tsample\treason\n";
+	uint64_t n_invalid = 0;
+	for (uint64_t i = 0; i < doc->n_records; i++) {
+		if (!r->rec_invalid[i])
+			continue;
+		n_invalid++;
+		const uint32_t reason = r->rec_reason[i], al = r->rec_allele[i], t = r->rec_task[i];
+		if (reason > POVU_HIP_V_MISSPELLED || (reason == POVU_HIP_V_MISSPELLED ? t != POVU_HIP_NIL : t >= doc->n_tasks || doc->task_record[t] != i))
+			return nullptr;
+		out += std::to_string(i) + "\t";
+		out.append(doc->ids + doc->rec_id_off[i], doc->rec_id_off[i + 1] - doc->rec_id_off[i]);
+		out += "\t" + std::to_string(doc->rec_pos[i]) + "\t";
+		const uint64_t a = doc->allele_off[i] + al;
+		if (a < doc->allele_off[i + 1])
+			for (uint64_t k = doc->step_off[a]; k < doc->step_off[a + 1]; k++)
+				out += (doc->step_or[k] ? "<" : ">") + std::to_string(doc->step_id[k]);
+		if (reason == POVU_HIP_V_MISSPELLED) {
+			out += "\t.\t.";
+		} else {
+			const uint32_t c = doc->task_col[t], j = doc->task_phase[t];
+			long long hap = 1;
+			if (c >= doc->n_samples)
+				return nullptr;
+			if (j < col_slots[c] && names->slot_hap && names->slot_hap[col_first[c] + j] >= 0)
+				hap = names->slot_hap[col_first[c] + j];
+			out += "\t" + std::to_string(hap) + "\t" + doc->sample[c];
+		}
+		out += std::string("\t") + STATUS_NAME[reason] + "\n";
+	}
+	char line[64];
+	if (!n_invalid)
+		snprintf(line, sizeof line, "No errors\n");
+	else
+		snprintf(line, sizeof line, "Error rate: %.2f%%\n", (double)n_invalid / (double)doc->n_records * 100.0);
+	*summary = to_buffer(line, summary_len);
+	char *rep = *summary ? to_buffer(out, report_len) : nullptr;
+	if (!rep) {
+		free(*summary);
+		*summary = nullptr;
+	}
+	return rep;
+} catch (const std::bad_alloc &) {
+	return nullptr;
+}

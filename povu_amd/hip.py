@@ -101,7 +101,29 @@ class _CallRefs(C.Structure):
 
 class _CallNames(C.Structure):
     _fields_ = [("refs", _CallRefs), ("n_paths", C.c_uint32), ("slot_of_path", C.POINTER(C.c_uint32)),
-                ("sample", C.POINTER(C.c_char_p))]
+                ("sample", C.POINTER(C.c_char_p)), ("slot_hap", C.POINTER(C.c_int64))]
+
+
+class _VcfDoc(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_samples", "n_records", "n_alleles", "n_steps", "n_text_bytes", "n_tasks", "n_id_bytes")] +
+                [("sample", C.POINTER(C.c_char_p)), ("rec_line", C.POINTER(C.c_uint64)), ("rec_pos", C.POINTER(C.c_uint64)),
+                 ("rec_id_off", C.POINTER(C.c_uint64)), ("ids", C.POINTER(C.c_uint8)), ("allele_off", C.POINTER(C.c_uint64)),
+                 ("task_off", C.POINTER(C.c_uint64)), ("step_off", C.POINTER(C.c_uint64)), ("text_off", C.POINTER(C.c_uint64)),
+                 ("allele_walk", C.POINTER(C.c_uint8)), ("step_id", C.POINTER(C.c_uint32)), ("step_or", C.POINTER(C.c_uint8)),
+                 ("text", C.POINTER(C.c_uint8))] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("task_record", "task_allele", "task_col", "task_phase")])
+
+
+class _VcfOpts(C.Structure):
+    _fields_ = [("flags", C.c_uint32)]
+
+
+class _VcfReport(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_records", "n_tasks", "n_alleles")] +
+                [(k, C.POINTER(C.c_uint8)) for k in ("task_status", "allele_spell", "rec_invalid", "rec_reason")] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("rec_allele", "rec_task")] +
+                [("n_status", C.c_uint64 * 6), ("n_invalid", C.c_uint64), ("n_misspelled", C.c_uint64), ("n_tier2", C.c_uint64),
+                 ("device_ms", C.c_double)])
 
 
 OFFREF_COUNTERS = ("n_offref_sites", "n_offref_records", "n_offref_hosted")  # of Calls
@@ -190,6 +212,13 @@ PRIM_MAX_LENGTH = 512  # `decomposed` profile: the longest allele that is aligne
 ROW_RAW, ROW_SNP, ROW_INS, ROW_DEL, ROW_PASS = 0, 1, 2, 3, 4
 REASON_NONE, REASON_MAX_ALLELE_LENGTH, REASON_CONTIG_START, REASON_EMPTY_ALLELE, REASON_EQUALS_REF, REASON_SUBR = 0, 1, 2, 3, 4, 5
 
+# "VCF checks" (HipDecomposer.check_vcf): the status of a task, V_MISSPELLED as a record's reason beside them; the spelling of an
+# allele; the flags of povu_hip_vcf_check
+V_FOUND_FWD, V_FOUND_REV, V_ABSENT, V_NO_AT, V_BAD_STEP, V_NO_SLOT, V_MISSPELLED = range(7)
+V_STATUS_NAMES = ("found_fwd", "found_rev", "absent", "no_at", "bad_step", "no_slot", "misspelled")
+V_SPELL_NONE, V_SPELL_WHOLE, V_SPELL_ANCHORED, V_SPELL_MISSPELLED = range(4)
+V_FORWARD_ONLY, V_SPELLING, V_FORCE_TIER2 = 1, 2, 4
+
 _lib = None
 
 
@@ -271,6 +300,19 @@ def load_lib():
                                      C.c_char_p, C.c_uint32, C.POINTER(C.c_size_t)]
     l.povu_hip_calls_vcf.restype = C.c_void_p
     l.povu_hip_forest_first.argtypes = [C.c_void_p, C.c_uint32]
+    l.povu_hip_vcf_parse.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_char_p, C.c_size_t]
+    l.povu_hip_vcf_parse.restype = C.POINTER(_VcfDoc)
+    l.povu_hip_vcf_doc_free.argtypes = [C.POINTER(_VcfDoc)]
+    l.povu_hip_vcf_names_make.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.c_char_p, C.c_size_t]
+    l.povu_hip_vcf_names_make.restype = C.POINTER(_CallNames)
+    l.povu_hip_vcf_columns.argtypes = [C.POINTER(_VcfDoc), C.POINTER(_CallNames), C.c_void_p, C.c_void_p]
+    l.povu_hip_vcf_columns.restype = C.c_int
+    l.povu_hip_vcf_check.argtypes = [C.c_void_p, C.POINTER(_VcfDoc), C.POINTER(_CallNames), C.POINTER(_VcfOpts), C.c_char_p, C.c_size_t]
+    l.povu_hip_vcf_check.restype = C.POINTER(_VcfReport)
+    l.povu_hip_vcf_report_free.argtypes = [C.POINTER(_VcfReport)]
+    l.povu_hip_vcf_report_text.argtypes = [C.POINTER(_VcfReport), C.POINTER(_VcfDoc), C.POINTER(_CallNames), C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    l.povu_hip_vcf_report_text.restype = C.c_void_p
     l.povu_hip_forest_pvst_text.restype = C.c_void_p
     l.povu_hip_forest_pvst_text.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]
     l.povu_hip_buffer_free.argtypes = [C.c_void_p]
@@ -901,6 +943,98 @@ class Calls:
         return s
 
 
+class VcfDoc:
+    """A parsed VCF (parse_vcf; povu_hip_vcf_parse): numpy views of the arrays of povu_hip_vcf_doc, valid as long as this object
+    lives -- samples (the column names), rec_line / rec_pos / rec_id per record, allele_off / task_off (per record), step_off /
+    text_off / allele_walk (per allele; bit 0: AT holds a walk, bit 1: it has a text), step_id / step_or, text (bytes),
+    task_record / task_allele / task_col / task_phase."""
+
+    def __init__(self, lib, ptr):
+        self._lib, self._p = lib, ptr
+        d = ptr.contents
+        self.n_records, self.n_alleles, self.n_tasks = int(d.n_records), int(d.n_alleles), int(d.n_tasks)
+        self.n_steps = int(d.n_steps)
+        self.samples = [d.sample[k].decode() for k in range(d.n_samples)]
+        n, na, nk = self.n_records, self.n_alleles, self.n_tasks
+        self.rec_line, self.rec_pos = _view(d.rec_line, n, np.uint64), _view(d.rec_pos, n, np.uint64)
+        self.rec_id_off = _view(d.rec_id_off, n + 1, np.uint64)
+        ids = bytes(_view(d.ids, int(d.n_id_bytes), np.uint8))
+        self.rec_id = [ids[int(self.rec_id_off[r]):int(self.rec_id_off[r + 1])].decode() for r in range(n)]
+        self.allele_off, self.task_off = _view(d.allele_off, n + 1, np.uint64), _view(d.task_off, n + 1, np.uint64)
+        self.step_off, self.text_off = _view(d.step_off, na + 1, np.uint64), _view(d.text_off, na + 1, np.uint64)
+        self.allele_walk = _view(d.allele_walk, na, np.uint8)
+        self.step_id, self.step_or = _view(d.step_id, self.n_steps, np.uint32), _view(d.step_or, self.n_steps, np.uint8)
+        self.text = _view(d.text, int(d.n_text_bytes), np.uint8)
+        for k in ("task_record", "task_allele", "task_col", "task_phase"):
+            setattr(self, k, _view(getattr(d, k), nk, np.uint32))
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            self._lib.povu_hip_vcf_doc_free(self._p)
+            self._p = None
+
+
+def parse_vcf(text, threads: int = 1) -> VcfDoc:
+    """The records, alleles, walks and tasks of VCF text (INTEGRATION.md "VCF checks"; host only).  A malformed line is refused
+    with its line number."""
+    lib = load_lib()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    err = C.create_string_buffer(512)
+    p = lib.povu_hip_vcf_parse(raw, len(raw), threads, err, 512)
+    if not p:
+        raise RuntimeError(err.value.decode())
+    return VcfDoc(lib, p)
+
+
+def _vcf_texts(lib, report_p, doc_p, names_p):
+    """(report.tsv, summary.txt) of povu_hip_vcf_report_text."""
+    ln, sl, sp = C.c_size_t(0), C.c_size_t(0), C.c_void_p(None)
+    p = lib.povu_hip_vcf_report_text(report_p, doc_p, names_p, C.byref(ln), C.byref(sp), C.byref(sl))
+    if not p:
+        raise RuntimeError("the report, the document and the names do not belong together")
+    out = C.string_at(p, ln.value).decode(), C.string_at(sp.value, sl.value).decode()
+    lib.povu_hip_buffer_free(p)
+    lib.povu_hip_buffer_free(sp)
+    return out
+
+
+class VcfReport:
+    """What HipDecomposer.check_vcf found (povu_hip_vcf_report): numpy views, valid as long as this object lives -- task_status
+    (V_FOUND_FWD .. V_NO_SLOT), allele_spell (V_SPELL_*), rec_invalid, and per invalid record its first failure: rec_reason (a
+    status or V_MISSPELLED; 0xFF when valid), rec_allele (within the record), rec_task (0xFFFFFFFF for a misspelled allele); the
+    counters n_records, n_tasks, n_status (per status), n_invalid, n_misspelled, n_tier2; device_ms.  `doc` is the parsed VCF."""
+
+    def __init__(self, lib, ptr, doc: VcfDoc, names_rec):
+        self._lib, self._p, self.doc, self._names_rec = lib, ptr, doc, names_rec
+        r = ptr.contents
+        self.n_records, self.n_tasks, self.n_alleles = int(r.n_records), int(r.n_tasks), int(r.n_alleles)
+        self.task_status = _view(r.task_status, self.n_tasks, np.uint8)
+        self.allele_spell = _view(r.allele_spell, self.n_alleles, np.uint8)
+        for k in ("rec_invalid", "rec_reason"):
+            setattr(self, k, _view(getattr(r, k), self.n_records, np.uint8))
+        for k in ("rec_allele", "rec_task"):
+            setattr(self, k, _view(getattr(r, k), self.n_records, np.uint32))
+        self.n_status = [int(x) for x in r.n_status]
+        self.n_invalid, self.n_misspelled, self.n_tier2 = int(r.n_invalid), int(r.n_misspelled), int(r.n_tier2)
+        self.device_ms = float(r.device_ms)
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            self._lib.povu_hip_vcf_report_free(self._p)
+            self._p = None
+        if getattr(self, "_names_rec", None):
+            self._lib.povu_hip_call_names_free(self._names_rec)
+            self._names_rec = None
+
+    def report_text(self) -> str:
+        """report.tsv of `povu vcf --report`: a line per invalid record, for its first failure."""
+        return _vcf_texts(self._lib, self._p, self.doc._p, self._names_rec)[0]
+
+    def summary_text(self) -> str:
+        """summary.txt: `No errors`, or the rate of invalid records."""
+        return _vcf_texts(self._lib, self._p, self.doc._p, self._names_rec)[1]
+
+
 class HipDecomposer:
     """One context = one GPU, one stream, one workspace arena."""
 
@@ -1123,6 +1257,26 @@ class HipDecomposer:
             self._lib.povu_hip_call_names_free(nr)
             raise
         return Calls(self._lib, p, names, nr, name_array, sites, profile or "raw-graph")
+
+    def check_vcf(self, text, forward_only: bool = False, spelling: bool = False, force_tier2: bool = False, threads: int = 1) -> VcfReport:
+        """Does the VCF `text` (or a VcfDoc of parse_vcf) still describe the graph (INTEGRATION.md "VCF checks")?  For every
+        record and every haplotype that carries an allele, the allele's AT walk must occur in a resident path of that haplotype
+        (paths uploaded first), forward or -- unless forward_only -- reversed; spelling: REF and ALT must also spell their walks
+        (sequences uploaded first; meant for raw-graph output, rewritten records fail it); force_tier2: every search through
+        the wave-per-unit kernel (tests)."""
+        doc = text if isinstance(text, VcfDoc) else parse_vcf(text, threads)
+        names = getattr(self, "_path_names", [])
+        name_array = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        err = C.create_string_buffer(512)
+        nr = self._lib.povu_hip_vcf_names_make(len(names), name_array, err, 512)
+        if not nr:
+            raise RuntimeError(err.value.decode())
+        o = _VcfOpts((V_FORWARD_ONLY if forward_only else 0) | (V_SPELLING if spelling else 0) | (V_FORCE_TIER2 if force_tier2 else 0))
+        p = self._lib.povu_hip_vcf_check(self._ctx, doc._p, nr, C.byref(o), err, 512)
+        if not p:
+            self._lib.povu_hip_call_names_free(nr)
+            raise RuntimeError(err.value.decode())
+        return VcfReport(self._lib, p, doc, nr)
 
     def traversals(self, forest: Forest, max_steps: int = 65536, flags: int = 0) -> Traversals:
         """The traversals of every flubble of `forest` by the resident paths, on the GPU."""
