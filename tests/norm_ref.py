@@ -104,6 +104,10 @@ def normalise(recs: List[dict], paths, seqs: Dict[int, str]):
             if r["path"] not in text:
                 text[r["path"]] = path_text(paths[r["path"]], seqs)
             got = closed_form(text[r["path"]][:r["pos"] - 1], [r["ref"]] + r["alts"])
+            if got is None and r["ref"] and all(r["alts"]):
+                # every ALT's text is REF's: the record stays, and each ALT still counts its allele's length (INTEGRATION.md
+                # "Left-normalised calls", Counters: per (record, ALT))
+                compared += len(r["ref"]) * len(r["alts"])
             if got is not None:
                 compared += got[4]
                 if got[0] or got[2]:

@@ -1,7 +1,13 @@
 """`povu call` argument handling, on the CPU: the reference options are exclusive (one of -r, -P, positional prefixes),
---restrict and --structure-export are refused, and `call` is this build's own (no outside provider)."""
+--restrict and --structure-export are refused, and `call` is this build's own (no outside provider).  On the GPU: one call over
+the wide cohort (tests/cohort_cases.py) written as a GFA, for the host's names maker and the writer with 131 sample columns."""
 import os
 import subprocess
+
+import pytest
+
+import cohort_cases as CC
+import vcf_ref as V
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 POVU = os.path.join(ROOT, "povu_amd", "bin", "povu")
@@ -38,3 +44,27 @@ def test_call_is_listed_in_help():
     r = _run("--help")
     assert r.returncode == 0
     assert "call OPTIONS" in r.stdout and "not part of the MI355X decompose build" not in r.stdout
+
+
+@pytest.mark.gpu
+def test_wide_cohort_through_the_cli(tmp_path):
+    g, p = CC.wide_chain()
+    seqs = CC.wide_gfa_sequences(g)
+    gfa = tmp_path / "wide.gfa"
+    gfa.write_text(g.to_gfa(seqs) + p.to_gfa())
+    forest = tmp_path / "forest"
+    forest.mkdir()
+    r = subprocess.run([POVU, "decompose", "-i", str(gfa), "-o", str(forest)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    refs = list(CC.REFS)
+    r = subprocess.run([POVU, "call", "-i", str(gfa), "-f", str(forest), "-P", refs[0], "-P", refs[1]], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr
+    names, steps = list(p.names), CC.steps_of(p)
+    sq = dict(zip(g.vid.tolist(), seqs))
+    pv = sorted(forest.glob("*.pvst"), key=lambda x: int(x.stem))
+    recs = V.call(V.sites_of_pvst([x.read_text() for x in pv]), names, steps, sq, refs)
+    assert len(recs) == 24 and len(V.slots_of(names)[0]) == 131
+    header = next(ln for ln in r.stdout.splitlines() if ln.startswith("#CHROM")).split("\t")
+    assert len(header) == 9 + 131 and [header[9 + s] for s in CC.BARE] == [f"bare{s}" for s in CC.BARE]
+    assert r.stdout.split("\n", 2)[2] == V.vcf_text(names, steps, sq, recs, refs).split("\n", 2)[2]  # (behind the date line)

@@ -2,7 +2,7 @@
 and VCF text for VCF text, on every graph family with PanSN haplotypes, random-walk and noise paths, reversed references,
 -s forests, several reference prefixes over two components, a graph of more than 10^5 segments and the forced tier-2 scans;
 the ten flubble fixtures through `povu decompose` and `povu call` against the records the reference states for them;
-gfa2vcf end to end; the refusals; two graphs in one context."""
+gfa2vcf end to end; the refusals; two graphs in one context; the wide cohort of 131 samples in 261 slots (tests/cohort_cases.py)."""
 import json
 import os
 import subprocess
@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cohort_cases as CC
 import vcf_ref as V
 from povu_amd import HipDecomposer
 from povu_amd import hip as H
@@ -107,6 +108,19 @@ def test_large_graph_and_tier2(hip):
     assert c.n_records > 10000
     g = W.chain_of_bubbles(400)
     _check(hip, g, W.pansn(W.chain_haplotypes(400, 8, seed=14), samples=4), ["sample0#1"], tflags=H.T_FORCE_TIER2, seed=14)
+
+
+@pytest.mark.parametrize("ref", CC.REFS)
+def test_wide_cohort(hip, ref):
+    """131 samples, 261 slots (tests/cohort_cases.py): the lane-per-sample loop of the record kernel takes three rounds, the
+    reference's slot in the first or in the last; GT by its array as well as by the text."""
+    g, p = CC.wide_chain()
+    for tflags in (0, H.T_FORCE_TIER2):
+        c, want = _check(hip, g, p, [ref], tflags=tflags, seed=CC.SEQ_SEED, max_len=CC.MAX_LEN)
+        assert len(c.samples) == 131 and c.n_slots == 261 and c.n_records == 12
+        assert c.gt.tolist() == [[H.GT_MISSING if v is None else v for v in r["slots"]] for r in want]
+        assert [bool(x & H.CALL_TANGLED) for x in c.flags.tolist()] == [r["tangled"] for r in want]
+        assert sum(r["tangled"] for r in want) == 4 and {r["ns"] for r in want} == {129, 130, 131}
 
 
 def test_refusals_and_two_graphs(hip):

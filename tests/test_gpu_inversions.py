@@ -3,10 +3,12 @@
 reference, random walks, a -s forest, references on two components, haplotypes with inverted intervals (runs of more than
 64 steps: the wave-per-run kernel), a repeat that 70 paths walk backwards (the wave-per-step head kernel), a graph of more
 than 10^5 segments, a small max_steps that drops runs -- each again with the forced second tier --, the same call without
-the flag, two graphs in one context, the refusals."""
+the flag, two graphs in one context, the refusals,
+the wide cohort of 131 samples in 261 slots (tests/cohort_cases.py)."""
 import numpy as np
 import pytest
 
+import cohort_cases as CC
 import inversions_ref as I
 import vcf_ref as V
 from povu_amd import HipDecomposer
@@ -185,6 +187,17 @@ def test_a_graph_of_more_than_1e5_segments_then_a_small_one(hip, tflags):
     # the next, smaller graph in the same context: nothing of the large call's workspace shows
     g, p = chain_case()
     _check(hip, g, p, ["sample0#1"], tflags=tflags)
+
+
+@pytest.mark.parametrize("ref", CC.REFS)
+@pytest.mark.parametrize("tflags", TIERS)
+def test_wide_cohort(hip, tflags, ref):
+    """131 samples, 261 slots (tests/cohort_cases.py): supporters on both sides of lane 63 and past it alone, the reference's
+    slot in the first round or in the last, a slot key of nine bits in the sort."""
+    g, p = CC.wide_chain()
+    c, want, stats = _check(hip, g, p, [ref], tflags=tflags, seed=CC.SEQ_SEED, max_len=CC.MAX_LEN)
+    assert c.n_slots == 261 > 256 and len(_subr(want)) >= 32 and stats["max_opposite"] >= 65
+    assert max(r["ac"][0] for r in _subr(want)) >= 17
 
 
 def test_refusals_and_entry_points_that_ignore_the_flag(hip):

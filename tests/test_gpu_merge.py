@@ -3,7 +3,8 @@ decomposed --merge-primitives`) against the plain-Python restatement (tests/merg
 VCF text, exactly; the record arrays and the row arrays against the same call without the flag.  The reference's two fixtures
 through the library, the CLI and gfa2vcf; a hand-built chain (tests/merge_cases.py, whose conditions tests/test_merge_ref.py
 checks without a GPU); complex_alleles through the striped kernel and under a nested call; skip_nested for groups across
-records; the chain again under a four-bit hash; the refusals; and calls without the flag, which stay as they were."""
+records; the chain again under a four-bit hash; the refusals; calls without the flag, which stay as they were; and
+the wide cohort of 131 samples in 261 slots (tests/cohort_cases.py)."""
 import hashlib
 import os
 import subprocess
@@ -12,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import cohort_cases as CC
 import merge_cases as MC
 import merge_ref as MR
 import prim_cases as PC
@@ -133,6 +135,19 @@ def test_skip_nested_groups_across_records(hip):
     c, raw, rows, merged, counters = _check(hip, setup, ["hap0"])
     MC.carrying(rows, merged, counters)
     assert sum(len({rows[x]["rec"] for x in m["members"]}) > 1 for m in merged) >= 10
+
+
+# ---- more samples than lanes, three times over
+@pytest.mark.parametrize("ref, groups", [(CC.REF_LOW, 4), (CC.REF_HIGH, 1)])
+def test_wide_cohort(hip, ref, groups):
+    """131 samples, 261 slots (tests/cohort_cases.py): the vote's lane-per-sample loop takes three rounds; merged rows and the
+    counters, both tiers."""
+    g, p = CC.wide_chain()
+    setup = _setup(hip, g, CC.wide_sequences(g), p)
+    c, raw, rows, merged, counters = _check(hip, setup, [ref], tflags=H.T_INVERSIONS)
+    assert c.n_slots == 261 and counters["n_merged_groups"] == groups and counters["n_ref_consistent"] >= 100
+    c2, _, _, _, counters2 = _check(hip, setup, [ref], tflags=H.T_INVERSIONS | H.T_FORCE_TIER2)
+    assert counters2 == counters and c2.vcf_text(date=DATE) == c.vcf_text(date=DATE)
 
 
 # ---- collisions

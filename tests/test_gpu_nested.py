@@ -2,7 +2,8 @@
 the plain-Python restatement (tests/nested_ref.py), array for array and VCF text for VCF text: skip_nested graphs of depth
 0, 1 and 3 with PanSN haplotypes, nested_towers and hprc_shaped with random-walk and noise paths, a -s forest, two
 reference prefixes over two components, the forced tier-2 kernels, a narrowed hash in a child process, the three
-profiles, the reference's fixture through the CLI and gfa2vcf, and the plain call left as it was."""
+profiles, the reference's fixture through the CLI and gfa2vcf, the plain call left as it was, and
+the wide cohort of 131 samples in 261 slots (tests/cohort_cases.py)."""
 import hashlib
 import json
 import os
@@ -12,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import cohort_cases as CC
 import nested_ref as N
 import vcf_ref as V
 from povu_amd import HipDecomposer
@@ -114,6 +116,17 @@ def test_skip_nested(hip, units, depth, haps):
     # two references: some REF is not its class's representative
     c3, want3, _ = _check(hip, g, p, ["sample0#1", "sample1#2"], setup=setup)
     assert any(not r["ref_is_rep"] for r in want3)
+
+
+@pytest.mark.parametrize("ref", CC.REFS)
+def test_wide_cohort(hip, ref):
+    """131 samples, 261 slots (tests/cohort_cases.py): three rounds of the lane-per-sample loop under T_NESTED, plain and popped."""
+    g, p = CC.wide_chain()
+    setup = _setup(hip, g, p, seed=CC.SEQ_SEED, max_len=CC.MAX_LEN)
+    c, want, _ = _check(hip, g, p, [ref], setup=setup)
+    assert c.n_slots == 261 and len(want) == 12 and {r["ns"] for r in want} == {129, 130, 131}
+    _check(hip, g, p, [ref], setup=setup, tflags=H.T_FORCE_TIER2)
+    _check(hip, g, p, [ref], setup=setup, profile="popped", max_level=0, max_ref_length=2, max_allele_length=2)
 
 
 def test_long_alleles_take_the_wave_tier(hip):

@@ -4,7 +4,8 @@ exactly: the reference's fixture through the library, the CLI and gfa2vcf; hand-
 on and around the 64-base chunk of the backward walk, cut the context into one-base and long segments, cross it with '-'
 steps, lower case and a reference path that walks the graph backwards, begin the contig with the repeat, give a record
 several ALTs, chop and trim without a shift and make two records swap places; the nested call, the inversion records and
-the forced second tier beside it; graphs that must stay as they are; tandem_indels against the restatement."""
+the forced second tier beside it; graphs that must stay as they are; tandem_indels against the restatement;
+the wide cohort of 131 samples in 261 slots (tests/cohort_cases.py)."""
 import json
 import os
 import subprocess
@@ -12,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cohort_cases as CC
 import inversions_ref as I
 import nested_ref as N
 import norm_ref as NR
@@ -361,3 +363,15 @@ def test_tandem_indels(hip, seed):
     assert counters["n_normalized"] > 0 and counters["max_shift"] >= 64
     if seed == 1:
         _check(hip, setup, ["hap0", "hap3"], tflags=H.T_FORCE_TIER2)
+
+
+# ---- more samples than lanes
+@pytest.mark.parametrize("ref", CC.REFS)
+def test_wide_cohort(hip, ref):
+    """131 samples, 261 slots (tests/cohort_cases.py) under the profile: the records' counts and genotypes ride along unchanged."""
+    g, p = CC.wide_chain()
+    setup = _setup(hip, g, CC.wide_sequences(g), p)
+    c, want, counters = _check(hip, setup, [ref])
+    assert c.n_slots == 261 and len(want) == 12
+    assert c.gt.tolist() == [[H.GT_MISSING if v is None else v for v in r["slots"]] for r in want]
+    _check(hip, setup, [ref], tflags=H.T_FORCE_TIER2 | H.T_INVERSIONS)

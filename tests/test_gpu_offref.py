@@ -2,7 +2,8 @@
 restatement (tests/offref_ref.py), array for array and VCF text for VCF text: the graph the feature was stated on, the hand
 cases and the reference's nested-child-inside-insertion fixture -- plain, with the tier-2 scans forced, under a four-bit hash
 and with inversion records; insertion_units with more samples than a wave has lanes and with diploid samples; skip_nested
-with the reference through skips; 120 random small graphs, each with the flag-less call before and after; -o DIR."""
+with the reference through skips; 120 random small graphs, each with the flag-less call before and after; -o DIR;
+the wide cohort of 131 samples in 261 slots (tests/cohort_cases.py) with a reference that ends in the middle of the chain."""
 import hashlib
 import os
 import subprocess
@@ -11,6 +12,7 @@ import sys
 import numpy as np
 import pytest
 
+import cohort_cases as CC
 import offref_cases as OC
 import offref_ref as F
 import vcf_ref as V
@@ -134,6 +136,16 @@ def test_insertion_units_diploid(hip):
     assert len(c.samples) == 3 and c.n_slots == 6 and c.n_offref_records > 0 and c.n_offref_hosted > 0
     assert len(set(c.off_contig_path.tolist())) > 1
     _check(hip, _workload(hip, g, p, 3), ["sample0#1"], H.T_FORCE_TIER2 | H.T_INVERSIONS)
+
+
+@pytest.mark.parametrize("tflags", [0, H.T_FORCE_TIER2 | H.T_INVERSIONS], ids=["plain", "tier2-inversions"])
+def test_wide_cohort_partial_reference(hip, tflags):
+    """131 samples, 261 slots (tests/cohort_cases.py) with the haplotype that ends in the middle of the chain as the reference: the
+    six sites behind its end are called on a surrogate, the first of more than 256 paths that traverse them."""
+    g, p = CC.wide_chain()
+    c, want, counts = _check(hip, _setup(hip, g, CC.wide_sequences(g), p), [CC.REF_PARTIAL], tflags)
+    assert c.n_slots == 261 and counts["n_offref_sites"] == counts["n_offref_records"] == 6
+    assert all(r["an"] >= 258 for r in want if r["offref"])
 
 
 def test_skip_nested_with_the_reference_through_skips(hip):

@@ -4,7 +4,7 @@ and the VCF text, exactly.  The reference's two fixtures through the library, th
 on and around the stripes of the second-tier kernel and the cap, anchors on the context, the row rules and the sort
 (tests/prim_cases.py, whose conditions tests/test_prim_inputs.py checks without a GPU); complex_alleles against the
 restatement; everything again through the striped kernel; the nested call and the inversion records beside it; the refusals;
-and calls without the profile, which stay as they were."""
+calls without the profile, which stay as they were; and the wide cohort of 131 samples in 261 slots (tests/cohort_cases.py)."""
 import json
 import os
 import subprocess
@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cohort_cases as CC
 import inversions_ref as I
 import nested_ref as N
 import prim_cases as PC
@@ -174,6 +175,18 @@ def test_complex_alleles(hip, seed):
     PC.coverage(rows)
     if seed == 1:
         _check(hip, setup, ["hap0", "hap3"], tflags=H.T_NESTED)
+
+
+# ---- more samples than lanes
+@pytest.mark.parametrize("ref", CC.REFS)
+def test_wide_cohort(hip, ref):
+    """131 samples, 261 slots (tests/cohort_cases.py): the rows' genotype counts come from three rounds of the lane-per-sample
+    loop, plain and with the inversion records."""
+    g, p = CC.wide_chain()
+    setup = _setup(hip, g, CC.wide_sequences(g), p)
+    c, raw, rows, counters = _both_tiers(hip, setup, [ref], tflags=H.T_INVERSIONS)
+    assert c.n_slots == 261 and len(rows) >= 59 and max(r["an"] for r in rows) >= 187
+    _both_tiers(hip, setup, [ref])
 
 
 # ---- refusals

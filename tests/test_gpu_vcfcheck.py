@@ -3,12 +3,16 @@ array for array and text for text, every case again with the forced second tier 
 project's own calls (plain and with inversions, spelling on: no invalid record, no misspelled allele) on the eleven conformance
 GFAs, PanSN haplotypes of a chain and a -s forest; references that run backwards (FOUND_REV, ABSENT under forward_only); walks
 at the ends of paths; walks of 65, 128 and 200 steps; a repeat one path visits 70 times; the slot rules; mutations of a clean
-VCF; two graphs in one context and the refusals."""
+VCF; two graphs in one context and the refusals.  Past 64: the wide cohort's VCF (tests/cohort_cases.py: 131 columns, 261
+tasks a record) and first failures in its later batches of tasks; a record of 71 alleles; segments of 64 to 200 bases in the
+spelling; walks and anchors on the edges of the tiers; documents beyond the capped grids of the counting kernels.  What those
+inputs reach is checked without a GPU in tests/test_cohort_inputs.py."""
 import os
 
 import numpy as np
 import pytest
 
+import cohort_cases as CC
 import vcf_ref as V
 import vcfcheck_cases as K
 import vcfcheck_ref as R
@@ -103,11 +107,12 @@ def n_searches(doc, steps, segments, forward_only, force):
     return n
 
 
-def check(d, text, names, steps, segments, sq=None, forward_only=False, spelling=False):
-    """Both tiers equal the restatement; returns (the report of the first, the restatement's result, its document)."""
-    doc = R.parse(text)
+def check(d, text, names, steps, segments, sq=None, forward_only=False, spelling=False, restated=None):
+    """Both tiers equal the restatement; returns (the report of the first, the restatement's result, its document).  `restated`:
+    (document, result) of the restatement when the caller has them already."""
     segments = set(segments)
-    want = R.check(doc, names, steps, segments, sq, forward_only=forward_only, spelling=spelling)
+    doc = restated[0] if restated else R.parse(text)
+    want = restated[1] if restated else R.check(doc, names, steps, segments, sq, forward_only=forward_only, spelling=spelling)
     first = None
     for force in (False, True):
         rep = d.check_vcf(text, forward_only=forward_only, spelling=spelling, force_tier2=force)
@@ -381,6 +386,251 @@ def test_mutations_of_a_clean_vcf(hip):
             assert not rep.allele_spell.any()
 
 
+# ---- past 64: tasks, alleles, bases, steps and occurrences (the builders at module level; tests/test_cohort_inputs.py
+# checks on the restatement what they reach)
+
+NIL = R.NIL
+other = lambda c: "A" if c != "A" else "C"  # noqa: E731
+
+
+def set_gt(col, phase, allele):
+    """A change for `mutate`: the genotype of sample column `col` at `phase` becomes `allele`."""
+    def change(f):
+        gt = f[9 + col].split("|")
+        gt[phase] = str(allele)
+        return f[:9 + col] + ["|".join(gt)] + f[10 + col:]
+    return change
+
+
+def first_failure_in(text, names, steps, segments, lo, hi, allele=None, pick=lambda f: True):
+    """(record id, column, phase, allele, in-record task index): one genotype of a clean VCF that, set to another allele of its
+    record (to `allele` when given), is that record's first failing task, at an in-record index in [lo, hi)."""
+    head = [ln for ln in text.split("\n") if ln.startswith("#")]
+    for ln in text.split("\n"):
+        f = ln.split("\t")
+        if not ln or ln.startswith("#") or not pick(f):
+            continue
+        for b in (range(1 + len(f[4].split(","))) if allele is None else [allele]):
+            for c in range(len(f) - 9):
+                for j, a in enumerate(f[9 + c].split("|")):
+                    if a in (".", str(b)):
+                        continue
+                    doc = R.parse("\n".join(head + ["\t".join(set_gt(c, j, b)(f))]))
+                    at = doc["records"][0]["tasks"].index((b, c, j))
+                    if lo <= at < hi and R.check(doc, names, steps, segments)["rec_task"][0] == at:
+                        return f[2], c, j, b, at
+    raise AssertionError("no genotype to change")
+
+
+def late_failures(text, names, steps, segments):
+    """Mutations of the wide cohort's clean VCF: (what, text, record, (reason, allele, in-record task or None))."""
+    spelled = lambda f: f[3] and all(f[4].split(","))  # noqa: E731
+    out = []
+    for what, lo, hi in (("the first failing task in the second batch", 64, 128), ("the first failing task in the third batch or later", 128, 1 << 30)):
+        ident, c, j, b, at = first_failure_in(text, names, steps, segments, lo, hi)
+        bad, r = mutate(text, lambda f: f[2] == ident, set_gt(c, j, b))
+        out.append((what, bad, r, (R.ABSENT, b, at)))
+    ident, c, j, b, at = first_failure_in(text, names, steps, segments, 64, 128, allele=0, pick=spelled)
+    alt1 = lambda f: f[:4] + [f[4][:f[4].index(",") - 1] + other(f[4][f[4].index(",") - 1]) + f[4][f[4].index(","):]] + f[5:]  # noqa: E731
+    bad, r = mutate(text, lambda f: f[2] == ident, lambda f: alt1(set_gt(c, j, b)(f)))
+    out.append(("allele 1 misspelled, a task of allele 0 fails in the second batch: the task's reason", bad, r, (R.ABSENT, 0, at)))
+    ref = lambda f: f[:3] + [f[3][:-1] + other(f[3][-1])] + f[4:]  # noqa: E731
+    bad, r = mutate(text, lambda f: f[2] == ident, lambda f: ref(set_gt(c, j, b)(f)))
+    out.append(("allele 0 misspelled and a task of allele 0 fails: misspelled", bad, r, (R.MISSPELLED, 0, None)))
+    return out
+
+
+@pytest.mark.parametrize("ref", CC.REFS)
+def test_wide_cohort_round_trip_and_first_failures_in_later_batches(hip, ref):
+    g, p = CC.wide_chain()
+    seqs = CC.wide_sequences(g)
+    (text, want, doc), _ = round_trip(hip, g, p, seqs, [ref])
+    assert len(doc["samples"]) == 131 and min(len(r["tasks"]) for r in doc["records"]) >= 258
+    names, steps, sq = list(p.names), CC.steps_of(p), dict(zip(g.vid.tolist(), seqs))
+    for what, bad, r, (reason, allele, at) in late_failures(text, names, steps, set(sq)):
+        rep, res, _ = check(hip, bad, names, steps, sq.keys(), sq, spelling=True)
+        task = NIL if at is None else int(rep.doc.task_off[r]) + at
+        assert (int(rep.rec_reason[r]), int(rep.rec_allele[r]), int(rep.rec_task[r])) == (reason, allele, task), what
+        assert rep.rec_invalid.tolist() == [int(k == r) for k in range(len(doc["records"]))], what
+        assert rep.report_text().splitlines()[1].endswith("\t" + R.STATUS_NAME[reason]), what
+
+
+def many_alleles_case(misspelled):
+    """A row of 71 segments under one path and one record of REF >1 and the 70 ALTs >2 .. >71, the ALTs `misspelled` (allele
+    numbers) with a wrong first base: (names, steps, sequences by id, VCF text)."""
+    names, steps = ["s#1#c"], [fwd(range(1, 72))]
+    sq = {i: "ACGT"[i % 4] * (1 + i % 3) for i in range(1, 72)}
+    text = vcf_of(["s"], [("many", [fwd([i]) for i in range(1, 72)], ["0"])], sq)
+
+    def change(f):
+        alts = f[4].split(",")
+        for a in misspelled:
+            alts[a - 1] = other(alts[a - 1][0]) + alts[a - 1][1:]
+        return f[:4] + [",".join(alts)] + f[5:]
+    return names, steps, sq, mutate(text, lambda f: True, change)[0]
+
+
+@pytest.mark.parametrize("misspelled", [(66,), (3, 66)])
+def test_more_than_64_alleles_in_a_record(hip, misspelled):
+    names, steps, sq, text = many_alleles_case(misspelled)
+    resident(hip, chain(71), names, steps, [sq[i] for i in range(1, 72)])
+    rep, want, _ = check(hip, text, names, steps, sq.keys(), sq, spelling=True)
+    assert (int(rep.rec_reason[0]), int(rep.rec_allele[0]), int(rep.rec_task[0])) == (R.MISSPELLED, misspelled[0], NIL)
+    assert rep.n_misspelled == len(misspelled) and rep.allele_spell.tolist() == [R.SPELL_MISSPELLED if a in misspelled else R.SPELL_WHOLE for a in range(71)]
+
+
+LONG = (64, 65, 130, 200)  # bases of segments 2 .. 5 of long_segments_case
+
+
+def long_segments_case():
+    """Segment 1 is AC, segments 2 .. 5 have LONG bases, 6 .. 8 are segment 4 with a byte that is no nucleotide code at index 70,
+    as the last base and as the first.  One record an allele: (names, steps, sequences in id order, VCF text, the spelling
+    expected of every allele).  Every long segment is spelled '>' and '<', whole and behind the anchor base of segment 1,
+    rightly and with one wrong base at oriented index 63, 64, 129 and at the last index, where it has them."""
+    rng = np.random.default_rng(7)
+    seqs = ["AC"] + ["".join("ACGT"[k] for k in rng.integers(0, 4, size=n)) for n in LONG]
+    seqs += [seqs[3][:70] + "Q" + seqs[3][71:], seqs[3][:-1] + "Q", "Q" + seqs[3][1:]]
+    sq = dict(enumerate(seqs, 1))
+    wrong = lambda t, i: t[:i] + other(t[i]) + t[i + 1:]  # noqa: E731
+    rows = [([(2, 0)], seqs[1], R.SPELL_WHOLE, "0")]  # (the one allele with a task)
+    for x, n in zip(range(2, 6), LONG):
+        for o in (0, 1):
+            t = R._oriented((x, o), sq)
+            rows += [([(x, o)], t, R.SPELL_WHOLE, "."), ([(1, 0), (x, o)], "C" + t, R.SPELL_ANCHORED, ".")]
+            for i in sorted({63, 64, 129, n - 1}):
+                if i < n:
+                    rows += [([(x, o)], wrong(t, i), R.SPELL_MISSPELLED, "."), ([(1, 0), (x, o)], "C" + wrong(t, i), R.SPELL_MISSPELLED, ".")]
+    # the first step of an anchored reading gives its last base alone: a byte that is no code elsewhere in it does no harm,
+    # as the last oriented base it does; read whole it does wherever it stands
+    rows += [([(6, 0), (2, 0)], seqs[5][-1] + seqs[1], R.SPELL_ANCHORED, "."), ([(6, 1), (2, 0)], V._COMP[seqs[5][0]] + seqs[1], R.SPELL_ANCHORED, "."),
+             ([(7, 0), (2, 0)], "Q" + seqs[1], R.SPELL_MISSPELLED, "."), ([(8, 1), (2, 0)], "Q" + seqs[1], R.SPELL_MISSPELLED, "."),
+             ([(6, 0)], seqs[5], R.SPELL_MISSPELLED, "."), ([(6, 1)], "".join(V._COMP.get(c, "Q") for c in reversed(seqs[5])), R.SPELL_MISSPELLED, ".")]
+    out = ["##fileformat=VCFv4.2\n", "\t".join(["#CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT", "s"]) + "\n"]
+    for k, (w, t, _, gt) in enumerate(rows):
+        out.append("\t".join(["c", str(k + 1), f"r{k}", t, ".", "60", "PASS", "AT=" + at_of(w), "GT", gt]) + "\n")
+    return ["s#1#c"], [fwd(range(1, 9))], seqs, "".join(out), [r[2] for r in rows]
+
+
+def test_long_segments_in_the_spelling(hip):
+    names, steps, seqs, text, expected = long_segments_case()
+    sq = dict(enumerate(seqs, 1))
+    resident(hip, chain(8), names, steps, seqs)
+    rep, want, _ = check(hip, text, names, steps, sq.keys(), sq, spelling=True)
+    assert want["allele_spell"] == expected and rep.allele_spell.tolist() == expected
+    assert rep.n_misspelled == expected.count(R.SPELL_MISSPELLED) >= 40
+
+
+def tier_edges_case():
+    """(names, steps, records, the status expected of every task that has a slot).  `row` walks 101 .. 200: walks of exactly 64
+    and 65 steps; a64 visits 7 exactly 64 times, a65 visits 8 exactly 65 times; `late` visits 15 sixty-six times and only behind
+    the last visit go 20 .. 90 (a walk of 72 steps); m1, m2 and m3 visit 11 fifty, fifty and forty-one times, 141 times in
+    three slots, and only the last visit goes on to 13."""
+    names = [n + "#1#c" for n in ("row", "a64", "a65", "late", "m1", "m2", "m3")]
+    steps = [fwd(range(101, 201)), fwd([2, 7] * 64), fwd([3, 8] * 65), fwd([15, 14] * 65 + [15] + list(range(20, 91))),
+             fwd([11, 12] * 50), fwd([11, 12] * 50), fwd([11, 12] * 40 + [11, 13])]
+    tail = fwd([15] + list(range(20, 91)))
+    gt = lambda **kw: [kw.get(n.split("#")[0], ".") for n in names]  # noqa: E731
+    miss = lambda w: w[:-1] + [(w[-1][0] + 2, 0)]  # noqa: E731  (the last step differs)
+    w64, w65 = fwd(range(103, 167)), fwd(range(103, 168))
+    recs = [("w64", [w64], gt(row="0")), ("w64x", [miss(w64)], gt(row="0")), ("w65", [w65], gt(row="0")), ("w65x", [miss(w65)], gt(row="0")),
+            ("a64", [fwd([7, 2])], gt(a64="0")), ("a64x", [fwd([7, 3])], gt(a64="0")),
+            ("a65", [fwd([8, 3])], gt(a65="0")), ("a65x", [fwd([8, 2])], gt(a65="0")),
+            ("late", [tail], gt(late="0")), ("latex", [miss(tail)], gt(late="0")), ("lateb", [R.flipped(tail)], gt(late="0")),
+            ("many", [fwd([11, 13])], gt(m1="0", m2="0", m3="0"))]
+    F, B, A = R.FOUND_FWD, R.FOUND_REV, R.ABSENT
+    return names, steps, recs, [F, A, F, A, F, A, F, A, F, A, B, A, A, F]
+
+
+TIER_EDGES_TIER2 = 13  # searches the second tier takes unforced: by the rule of n_searches, counted in tests/test_cohort_inputs.py
+
+
+def test_tier_edges(hip):
+    names, steps, recs, expected = tier_edges_case()
+    sq = {i: "A" for i in range(1, 201)}
+    resident(hip, chain(200), names, steps)
+    text = vcf_of([n.split("#")[0] for n in names], recs, sq)
+    rep, want, doc = check(hip, text, names, steps, sq.keys())
+    assert want["task_status"] == expected
+    # unforced, the second tier takes the walks of 65 and 72 steps and the anchors of 65, 66 and 141 occurrences, not those of 64
+    assert rep.n_tier2 == n_searches(doc, steps, set(sq), False, False) == TIER_EDGES_TIER2
+
+
+# ---- beyond the capped grids: COUNT_BLOCKS = 2048 workgroups of four waves, of 256 lanes
+
+CAP_WAVES, CAP_LANES = 8192, 524288
+
+
+def capped_records_case(n=8300, absent=8250, misspelled=8260):
+    """More records and alleles than the record and the spelling kernels have waves: `n` records of two alleles and one column on
+    a row of six segments, clean but for record `absent` (its genotype's walk skips a segment) and record `misspelled` (its
+    ALT has a wrong base), both from record CAP_WAVES on: (names, steps, sequences by id, VCF text)."""
+    names, steps = ["s#1#c"], [fwd(range(1, 7))]
+    sq = {i: "ACGT"[i % 4] * (1 + i % 3) for i in range(1, 7)}
+    recs = []
+    for k in range(n):
+        a = 1 + k % 4
+        walks = [fwd([a, a + 1]), fwd([a + 1, a + 2])]
+        if k == absent:
+            walks[k % 2] = fwd([a, a + 2])
+        recs.append((f"r{k}", walks, [str(k % 2)]))
+    text = vcf_of(["s"], recs, sq)
+    text, _ = mutate(text, lambda f: f[2] == f"r{misspelled}", lambda f: f[:4] + [other(f[4][0]) + f[4][1:]] + f[5:])
+    return names, steps, sq, text
+
+
+def test_more_records_and_alleles_than_waves(hip):
+    names, steps, sq, text = capped_records_case()
+    resident(hip, chain(6), names, steps, [sq[i] for i in range(1, 7)])
+    rep, want, doc = check(hip, text, names, steps, sq.keys(), sq, spelling=True)
+    assert rep.n_records == 8300 > CAP_WAVES and len(want["allele_spell"]) == 16600
+    assert np.flatnonzero(rep.rec_invalid).tolist() == [8250, 8260] and (rep.n_invalid, rep.n_misspelled) == (2, 1)
+    assert rep.rec_reason[[8250, 8260]].tolist() == [R.ABSENT, R.MISSPELLED] and np.flatnonzero(rep.allele_spell == R.SPELL_MISSPELLED).tolist() == [2 * 8260 + 1]
+
+
+def capped_tasks_case(text, names, steps, segments, copies=168):
+    """More tasks than the task kernel has lanes: the wide cohort's clean VCF `copies` times over, with one genotype of the
+    very last record changed so that the only failing task of the document lies behind task CAP_LANES: (header lines, the
+    record lines of a copy, those of the last copy)."""
+    block = [ln for ln in text.split("\n") if ln and not ln.startswith("#")]
+    head = [ln for ln in text.split("\n") if ln.startswith("#")]
+    ident, c, j, b, at = first_failure_in(text, names, steps, segments, 128, 1 << 30, pick=lambda f: f[2] == block[-1].split("\t")[2])
+    return head, block, block[:-1] + ["\t".join(set_gt(c, j, b)(block[-1].split("\t")))]
+
+
+def restated_copies(head, block, last, copies, names, steps, segments):
+    """(document, result) of the VCF of `head`, `block` copies - 1 times and `last` (as many lines as `block`): the restatement
+    reads and checks one block and the last one, and numpy repeats the first.  A record's tasks, alleles and verdict are its own
+    (vcfcheck_ref.check carries nothing from one record to the next but the count of tasks), so this is the restatement of the
+    whole document; tests/test_cohort_inputs.py compares the two once."""
+    docs = [R.parse("\n".join(head + lines)) for lines in (block, last)]
+    res = [R.check(doc, names, steps, segments) for doc in docs]
+    n, n_tasks = len(block), len(res[0]["task_status"])
+    records = [dict(r, line=r["line"] + c * n) for c in range(copies) for r in docs[c == copies - 1]["records"]]
+    want = {}
+    for k in ("task_status", "allele_spell", "rec_invalid", "rec_reason", "rec_allele"):
+        want[k] = np.concatenate([np.tile(np.array(res[0][k], dtype=np.int64), copies - 1), np.array(res[1][k], dtype=np.int64)]).tolist()
+    task = np.concatenate([np.tile(np.array(res[0]["rec_task"], dtype=np.int64), copies - 1), np.array(res[1]["rec_task"], dtype=np.int64)])
+    want["rec_task"] = np.where(task == NIL, NIL, task + np.repeat(np.arange(copies, dtype=np.int64) * n_tasks, n)).tolist()
+    want["n_status"] = [(copies - 1) * x + y for x, y in zip(res[0]["n_status"], res[1]["n_status"])]
+    for k in ("n_invalid", "n_misspelled"):
+        want[k] = (copies - 1) * res[0][k] + res[1][k]
+    return dict(samples=docs[0]["samples"], records=records), want
+
+
+def test_more_tasks_than_lanes(hip):
+    g, p = CC.wide_chain()
+    seqs = CC.wide_sequences(g)
+    names, steps, sq = list(p.names), CC.steps_of(p), dict(zip(g.vid.tolist(), seqs))
+    (text, _, _), _ = round_trip(hip, g, p, seqs, [CC.REF_LOW])
+    head, block, last = capped_tasks_case(text, names, steps, set(sq))
+    big = "\n".join(head + block * 167 + last) + "\n"
+    rep, want, doc = check(hip, big, names, steps, sq.keys(), restated=restated_copies(head, block, last, 168, names, steps, set(sq)))
+    r = 168 * len(block) - 1
+    assert rep.n_tasks > CAP_LANES and rep.n_records == r + 1 == 2016
+    assert np.flatnonzero(rep.rec_invalid).tolist() == [r] and int(rep.rec_task[r]) >= CAP_LANES and rep.n_status[R.ABSENT] == rep.n_invalid == 1
+    assert int(rep.task_status[int(rep.rec_task[r])]) == R.ABSENT and int(np.count_nonzero(rep.task_status > R.FOUND_REV)) == 1
+
+
 # ---- state
 
 def test_two_graphs_in_one_context_and_the_refusals(hip):
@@ -395,6 +645,16 @@ def test_two_graphs_in_one_context_and_the_refusals(hip):
         hip.check_vcf(text, spelling=True)
     with pytest.raises(RuntimeError, match=r"^line 3: POS is no number: x$"):
         hip.check_vcf(text.replace("\t1\tover\t", "\tx\tover\t"))
+    # segment ids that do not ascend with the vertex index: the path upload refuses them, so no check meets such a graph (its
+    # own refusal of them is never reached) and the paths of the graph before are gone
+    g = chain(6)
+    hip.upload(W._mk(g.vid[::-1].copy(), g.v1, g.s1, g.v2, g.s2))
+    with pytest.raises(RuntimeError, match="paths need segment ids that ascend with the vertex index"):
+        hip.upload_paths(paths_of(names, steps))
+    with pytest.raises(RuntimeError, match="no paths are resident"):
+        hip.check_vcf(text)
+    hip.upload(g)
+    hip.upload_paths(paths_of(names, steps))
     first, _, _ = check(hip, text, names, steps, sq.keys())
     # a larger graph, then the first again: nothing of the other is left
     n2, s2, r2 = repeat_case()
