@@ -75,13 +75,21 @@ __device__ __forceinline__ RefPathSlice nm_ref(const CallView &V, uint32_t j)
 {
 	return ref_path_slice(V.ref, V.paths, V.ref.ref_of_path[V.trav.op[V.rlist[j]]]);
 }
-// ALTs of every record (the tasks of k_nm_chop)
+// ALTs of every record (the tasks of k_nm_chop); none for a record with an empty allele text, which stays as it is: none of
+// its comparisons is made or counted
 __global__ void k_nm_tasks(CallView V, uint64_t *__restrict__ cnt)
 {
 	const uint32_t nfl = V.nfl;
 	for (uint32_t j = blockIdx.x * Q_TPB + threadIdx.x; j <= nfl; j += gridDim.x * Q_TPB) {
-		const uint32_t q = j < nfl ? V.trav.rq[V.rlist[j]] : 0;
-		cnt[j] = j < nfl ? V.aoff[q + 1] - V.aoff[q] - 1 : 0;
+		if (j == nfl) {
+			cnt[j] = 0;
+			continue;
+		}
+		const uint32_t q = V.trav.rq[V.rlist[j]], nal = V.aoff[q + 1] - V.aoff[q];
+		bool empty = false;
+		for (uint32_t i = 0; i < nal && !empty; i++)
+			empty = allele_of_record(V, j, i).text_len() == 0;
+		cnt[j] = empty ? 0 : nal - 1;
 	}
 }
 

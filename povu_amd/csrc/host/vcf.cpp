@@ -302,6 +302,8 @@ try {
 			  c->row_ac && c->row_an && c->row_ns;
 	// the merged rows of "Merged primitives", written instead of the rows when they are there
 	const bool merged = rows && c->mrow_off;
+	// (a call with the flag and no row has no array to show for it: `merged` says so, and the header still names the fields)
+	const bool merged_lines = merged || (nested_fields && profile == POVU_HIP_PROFILE_DECOMPOSED && c->merged && !c->n_rows);
 	// the arrays of "Off-reference calls" (absent: the text of the call without the flag)
 	// (a call with the flag and no record has no array to show for it: `offref` says so)
 	const bool offref = nested_fields && (c->rec_offref || c->offref);
@@ -362,7 +364,7 @@ try {
 		date = today;
 	}
 	// ---- header, a contig line per reference path of the prefix, the column line
-	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile] + (merged ? MERGE_LINES : "") + (offref ? OFFREF_LINES : "");
+	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile] + (merged_lines ? MERGE_LINES : "") + (offref ? OFFREF_LINES : "");
 	// the paths whose lines and records are written: those of the prefix (every one without), or with `rest` of no prefix
 	auto takes = [&](const char *name) {
 		if (!rest)
