@@ -23,6 +23,55 @@ __device__ __forceinline__ uint4 load4_unaligned(const unsigned *__restrict__ p)
 	return make_uint4(v.x, v.y, v.z, v.w);
 }
 
+// ---- conditional gathers that leave together.  `cond ? p[i] : dflt` with a per-lane cond compiles to a branch around the
+// load, and where the address inside the branch comes from an earlier load the first instruction there drains the memory
+// counter (vmcnt(0)): gfx950 counts loads and stores in ONE in-order counter, and the compiler cannot know how many younger
+// loads the branches it skipped have issued.  Four "simultaneous" gathers written that way are four round trips.
+// gather_if and its kin load UNCONDITIONALLY from a clamped index (a 16-byte record: gather_if<uint4>), so that a batch of
+// them is one run of load instructions behind one counted wait.  `safe` is an index the lane may ALWAYS read -- normally its
+// own element, or element 0 of an array that is neither null nor empty on that path: the choice is stated at every call.
+// A clamped load is a real load whose value is dropped, and it costs what a real one costs: the address unit works through
+// every active lane, whatever line it names (all idle lanes on ONE line, element 0, measured slower still than each on its
+// own neighbourhood).  So the idiom pays where cond mostly holds, or where the lanes that fail read next to their own data;
+// where most lanes fail -- the fourth slot of lists that mostly hold one or two -- the branch, which issues no address for
+// them, is the cheaper form (k_events).
+// landed(a, b, ...) closes a batch.  The compiler undoes a batch where it can: a value whose uses all lie behind one branch is
+// sunk into that branch, its load with it, and waits there on its own again; a select right on a load with no other use is
+// turned back into a branch around the load.  landed ties the values to the place where it stands: an empty statement the
+// optimiser cannot see through.  It emits no instruction and no wait is written by hand -- the compiler places its counted
+// wait in front of it.  One statement per batch, so that the register copies it may need stand behind ALL the loads.  Where
+// a value is used although cond failed, the caller selects behind landed().
+#define POVU_W2(v) "+v"((v).x), "+v"((v).y)
+#define POVU_W4(v) "+v"((v).x), "+v"((v).y), "+v"((v).z), "+v"((v).w)
+__device__ __forceinline__ void landed(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)); }
+__device__ __forceinline__ void landed(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d, uint32_t &e)
+{
+	asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e));
+}
+__device__ __forceinline__ void landed(uint2 &a, uint2 &b, uint2 &c, uint2 &d, uint32_t &e, uint32_t &f, uint32_t &g, uint32_t &h)
+{
+	asm volatile("" : POVU_W2(a), POVU_W2(b), POVU_W2(c), POVU_W2(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
+}
+__device__ __forceinline__ void landed(uint4 &a, uint2 &b) { asm volatile("" : POVU_W4(a), POVU_W2(b)); }
+__device__ __forceinline__ void landed(uint4 &a, uint4 &b, uint4 &c, uint4 &d) { asm volatile("" : POVU_W4(a), POVU_W4(b), POVU_W4(c), POVU_W4(d)); }
+#undef POVU_W2
+#undef POVU_W4
+template <class T>
+__device__ __forceinline__ T gather_if(bool cond, const T *__restrict__ p, uint32_t i, uint32_t safe)
+{
+	return p[cond ? i : safe];
+}
+// ... of two words at an even word index (8-byte aligned)
+__device__ __forceinline__ uint2 gather2_if(bool cond, const unsigned *__restrict__ p, uint32_t i, uint32_t safe)
+{
+	return *reinterpret_cast<const uint2 *>(p + (cond ? i : safe));
+}
+// ... of four words from a 4-byte aligned address (load4_unaligned: three words of slack behind `i` AND behind `safe`)
+__device__ __forceinline__ uint4 gather4_unaligned_if(bool cond, const unsigned *__restrict__ p, uint32_t i, uint32_t safe)
+{
+	return load4_unaligned(p + (cond ? i : safe));
+}
+
 // Workgroup index with the 8 XCDs in mind: the dispatcher deals workgroups round-robin over the XCDs (blocks b and b + 8
 // share one, MI355X_MICROARCH.md "Workgroup dispatch"), so neighbouring blocks -- which touch neighbouring lines in
 // almost every kernel here -- land in eight different L2s.  BIDX renumbers the blocks so that every XCD works on one

@@ -158,8 +158,8 @@ __global__ void k_tour_words(uint32_t nS, const uint32_t *__restrict__ loff, con
 	// -- where the link sits in the far side's list (its twin) and which forest slot follows the twin around the segment.
 	// A gather whose 64 lanes hit 64 lines keeps the CU's address unit busy for 64 cycles whatever it returns, and this
 	// kernel is bound by exactly that: four slots are taken a round, in phases, so that the loads of one phase are all in
-	// flight together -- own words (two 16-byte loads), the far segments' offsets, their slot words (a segment with at
-	// most eight slots, nearly all, in one or two 16-byte loads, searched in registers).
+	// flight together -- own words (two 16-byte loads), the far segments' offsets, the first four of their slot words (a
+	// segment with at most eight slots, nearly all, in one or two 16-byte loads, searched in registers).
 	for (uint32_t at0 = lo; at0 < hi; at0 += 4) {
 		const uint32_t rem = hi - at0;
 		const uint4 lw4 = load4_unaligned(lle + at0), w4 = load4_unaligned(ladj + at0);
@@ -167,24 +167,24 @@ __global__ void k_tour_words(uint32_t nS, const uint32_t *__restrict__ loff, con
 		bool tree[4];
 		uint2 o01[4];
 		uint32_t se[4];
+		// (gather_if and its kin, common.hpp: every phase is one run of loads.  A slot that is no forest slot reads in its
+		// place what the lane may always read -- the offsets of its OWN segment, the words of its OWN slots at0.. -- and
+		// drops it; loff, like lle, carries the slack of a 16-byte load behind its last word)
 #pragma unroll
 		for (uint32_t q = 0; q < 4; q++) {
 			tree[q] = q < rem && (lws[q] & LLE_TREE);
-			o01[q] = make_uint2(0u, 0u);
-			se[q] = 0;
-			if (tree[q]) {
-				const uint32_t g2 = ws[q] & ~1u;
-				o01[q] = *reinterpret_cast<const uint2 *>(loff + g2); // (g2 is even: 8-byte aligned)
-				se[q] = loff[g2 + 2];
-			}
+			// (an even index: 8-byte aligned); safe: the lane's own segment
+			o01[q] = gather2_if(tree[q], loff, ws[q] & ~1u, S & ~1u);
+			se[q] = gather_if(tree[q], loff, (ws[q] & ~1u) + 2, (S & ~1u) + 2);
 		}
+		landed(o01[0], o01[1], o01[2], o01[3], se[0], se[1], se[2], se[3]);
 		uint4 a[4];
 #pragma unroll
-		for (uint32_t q = 0; q < 4; q++) {
-			a[q] = make_uint4(0u, 0u, 0u, 0u);
-			if (tree[q] && se[q] - o01[q].x <= 8)
-				a[q] = load4_unaligned(lle + o01[q].x);
+		for (uint32_t q = 0; q < 4; q++) { // safe: the lane's own slots (loaded above, the same line)
+			const uint32_t n = se[q] - o01[q].x;
+			a[q] = gather4_unaligned_if(tree[q] && n <= 8, lle, o01[q].x, at0);
 		}
+		landed(a[0], a[1], a[2], a[3]);
 #pragma unroll
 		for (uint32_t q = 0; q < 4; q++) {
 			if (q >= rem)
@@ -203,6 +203,8 @@ __global__ void k_tour_words(uint32_t nS, const uint32_t *__restrict__ loff, con
 			if (se[q] - sb <= 8) {
 				const uint32_t n = se[q] - sb, tl = wl - sb, th = wh - sb;
 				uint4 c = make_uint4(0u, 0u, 0u, 0u);
+				// (the few segments with five to eight slots.  Batched like the first four words, these loads took the kernel
+				// from 64 to 77 registers -- six waves a SIMD for eight -- and from 2.52 to 2.85 ms: left as they were)
 				if (n > 4)
 					c = load4_unaligned(lle + sb + 4);
 				const uint32_t r[8] = {a[q].x, a[q].y, a[q].z, a[q].w, c.x, c.y, c.z, c.w};
@@ -553,23 +555,31 @@ struct L0Ranks {
 	const uint32_t *ra, *rb, *fin;
 	uint32_t M;
 };
-// rank of an element (the 0/1 weights) from its record {owner, partial} ...
-__device__ __forceinline__ uint32_t rank_l0(const L0Ranks &R, uint2 rec)
+// The gathers are unconditional (gather_if, common.hpp), so that a reader's look-ups leave together as one batch: it gathers
+// R.ra (and R.rb) at l0_at() of every record, puts landed() behind the batch and hands each word to rank_l0* with its record.
+// An owner outside R, a record that holds a final rank (fin) and a record the caller does not want read R[0] in its place --
+// safe: a ranking that ran has M >= 1 elements on level 1, and the callers only get here with records of a ranking that ran
+// (a graph without links has no slot, and its R stays null: root_forest).
+__device__ __forceinline__ uint32_t l0_at(const L0Ranks &R, uint2 rec, bool want = true) { return want && rec.x < R.M ? rec.x : 0u; }
+// rank of an element (the 0/1 weights) from its record {owner, partial} and ra = R.ra[l0_at(R, rec)] ...
+__device__ __forceinline__ uint32_t rank_l0(const L0Ranks &R, uint2 rec, uint32_t ra) { return (rec.x < R.M ? ra : 0u) - rec.y; }
+// ... and with TWO (fin read once per lane by the caller; the words gathered at l0_at(R, rec, !fin)) the first sum or both
+__device__ __forceinline__ uint32_t rank_l0_a(const L0Ranks &R, uint2 rec, bool fin, uint32_t ra)
 {
-	return (rec.x < R.M ? R.ra[rec.x] : 0u) - rec.y;
+	return fin ? rec.x : (rec.x < R.M ? ra : 0u) - (rec.y & REC_MAX);
 }
-// ... and with TWO (fin read once per lane by the caller) the first sum or both
-__device__ __forceinline__ uint32_t rank_l0_a(const L0Ranks &R, uint2 rec, bool fin)
+__device__ __forceinline__ uint2 rank_l0_pair(const L0Ranks &R, uint2 rec, bool fin, uint32_t ra, uint32_t rb)
 {
-	return fin ? rec.x : (rec.x < R.M ? R.ra[rec.x] : 0u) - (rec.y & REC_MAX);
+	const bool in = rec.x < R.M;
+	const uint32_t pa = rec.y & REC_MAX;
+	return fin ? rec : make_uint2((in ? ra : 0u) - pa, (in ? rb : 0u) - pa + (rec.y >> 16));
 }
+// one record on its own
+__device__ __forceinline__ uint32_t rank_l0(const L0Ranks &R, uint2 rec) { return rank_l0(R, rec, R.ra[l0_at(R, rec)]); }
 __device__ __forceinline__ uint2 rank_l0_pair(const L0Ranks &R, uint2 rec, bool fin)
 {
-	if (fin)
-		return rec;
-	const bool in = rec.x < R.M;
-	const uint32_t ra = in ? R.ra[rec.x] : 0u, rb = in ? R.rb[rec.x] : 0u, pa = rec.y & REC_MAX;
-	return make_uint2(ra - pa, rb - pa + (rec.y >> 16));
+	const uint32_t i = l0_at(R, rec, !fin);
+	return rank_l0_pair(R, rec, fin, R.ra[i], R.rb[i]);
 }
 
 // suffix sums (inclusive) along the lists packed in rb.pk, left as level-0 records rec[x] (k_rank_up) to be resolved
@@ -772,10 +782,14 @@ __global__ void k_t0_parents(uint32_t V, const uint2 *__restrict__ trec, L0Ranks
 		bool tree[4];
 		uint32_t ds[4];
 #pragma unroll
-		for (uint32_t q = 0; q < 4; q++) { // (the four gathers of R issued together)
+		for (uint32_t q = 0; q < 4; q++) { // (the four gathers of R issued together; a segment with a slot has a ranking behind it: R[0] is safe)
 			tree[q] = at0 + q < se && (lws[q] & LLE_TREE);
-			ds[q] = tree[q] ? rank_l0(R, rs[q]) : 0u;
+			ds[q] = R.ra[l0_at(R, rs[q], tree[q])];
 		}
+		landed(ds[0], ds[1], ds[2], ds[3]);
+#pragma unroll
+		for (uint32_t q = 0; q < 4; q++)
+			ds[q] = rank_l0(R, rs[q], ds[q]); // (read only where tree[q])
 #pragma unroll
 		for (uint32_t q = 0; q < 4; q++) {
 			if (!tree[q])
@@ -1065,18 +1079,13 @@ __global__ void __launch_bounds__(64) k_class_dfs_small(const uint32_t *__restri
 				// probe at a time paid two per candidate that turned out visited.  Nobody else writes the states of this
 				// class, and a side that is scanned again after a return loads them afresh.
 				const uint32_t rem = n + 1 - k;
-				uint32_t o0, o1, o2, o3;
-				if (k == 0) {
-					const uint4 x = load4_unaligned(ladj + lo);
-					o0 = u ^ 1u, o1 = x.x, o2 = x.y, o3 = x.z;
-				} else {
-					const uint4 x = load4_unaligned(ladj + lo + k - 1);
-					o0 = x.x, o1 = x.y, o2 = x.z, o3 = x.w;
-				}
-				const uint32_t w0 = cstate[o0];
-				const uint32_t w1 = rem > 1 ? cstate[o1] : CS_VISITED;
-				const uint32_t w2 = rem > 2 ? cstate[o2] : CS_VISITED;
-				const uint32_t w3 = rem > 3 ? cstate[o3] : CS_VISITED;
+				const uint4 x = load4_unaligned(ladj + lo + (k ? k - 1 : 0u)); // (one load instruction for either case)
+				const uint32_t o0 = k ? x.x : u ^ 1u, o1 = k ? x.y : x.x, o2 = k ? x.z : x.y, o3 = k ? x.w : x.z;
+				// (gather_if, common.hpp; safe: cstate[0] where a candidate lies behind the list's end -- one line for all the
+				// lanes that have nothing to ask.  The word read there may be one another lane is writing: it is dropped)
+				uint32_t w0 = cstate[o0], w1 = gather_if(rem > 1, cstate, o1, 0u), w2 = gather_if(rem > 2, cstate, o2, 0u), w3 = gather_if(rem > 3, cstate, o3, 0u);
+				landed(w0, w1, w2, w3);
+				w1 = rem > 1 ? w1 : CS_VISITED, w2 = rem > 2 ? w2 : CS_VISITED, w3 = rem > 3 ? w3 : CS_VISITED;
 				// not visited yet (hence no entry of another class), not the way up
 				auto open = [&](uint32_t o, uint32_t w) { return !(w & CS_VISITED) && !(u == s && o == s_up); };
 				const uint32_t j = open(o0, w0) ? 0u : open(o1, w1) ? 1u : open(o2, w2) ? 2u : open(o3, w3) ? 3u : 4u;
@@ -1095,16 +1104,15 @@ __global__ void __launch_bounds__(64) k_class_dfs_small(const uint32_t *__restri
 				// unvisited both tree edges are made here -- three dependent round trips for the pair where one edge at a
 				// time took six, and the partner's state word is not gathered again with the candidates.
 				const uint32_t g2 = o & ~1u, odd = o & 1u;
-				uint32_t l0, l1, l2 = 0, wp = CS_VISITED;
-				if (slot == 0) { // came over the black edge: the partner is u, visited
-					l0 = loff[o], l1 = loff[o + 1];
-				} else { // (the three offsets in one load instruction: the array carries slack behind its last word)
-					const uint4 l4 = load4_unaligned(loff + g2);
-					l0 = l4.x, l1 = l4.y, l2 = l4.z;
-					const uint2 cs2 = *reinterpret_cast<const uint2 *>(cstate + g2);
-					wp = odd ? cs2.x : cs2.y;
-				}
-				const uint32_t nlo = (slot == 0 || !odd) ? l0 : l1, nhi = (slot == 0) ? l1 : (odd ? l2 : l1);
+				// (the three offsets in one load instruction: the array carries slack behind its last word.  Both loads leave
+				// whichever way the step came, with no branch around them: over the black edge the partner is u, visited,
+				// and the state words read are those of segment 0 -- one line for all such lanes -- and dropped)
+				uint4 l4 = load4_unaligned(loff + g2);
+				uint2 cs2 = *reinterpret_cast<const uint2 *>(cstate + (slot ? g2 : 0u));
+				landed(l4, cs2);
+				const uint32_t l0 = l4.x, l1 = l4.y, l2 = l4.z;
+				const uint32_t wp = slot == 0 ? CS_VISITED : (odd ? cs2.x : cs2.y);
+				const uint32_t nlo = odd ? l1 : l0, nhi = odd ? l2 : l1; // the list of o
 				if (depth < DFS_STK)
 					stk[depth][lane] = make_uint4(u, k, lo, n);
 				depth++;
@@ -1588,23 +1596,30 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 	// from the event's record (rank_l0_pair)
 	const bool fin = *R.fin != 0;
 	const uint4 r01 = load4_unaligned(reinterpret_cast<const uint32_t *>(erec + 3 * g)); // records of 3g, 3g + 1
-	const uint2 ent = rank_l0_pair(R, make_uint2(r01.x, r01.y), fin);
-	const uint2 lv_o = make_uint2(rank_l0_a(R, make_uint2(r01.z, r01.w), fin), 0u);
+	const uint2 r2 = erec[3 * g + 2];						     // ... of 3g + 2: the lane's own, read also where the leaves are one event
+	const bool two_leaves = !merged[g];
 	const uint4 d4 = *reinterpret_cast<const uint4 *>(dps + 2 * g); // the DFS records of both sides
 	const uint32_t o = d4.x == 2 * g + 1 ? 2 * g : 2 * g + 1, e = o ^ 1u; // far side: its DFS parent is the other side
 	const uint32_t p = (e & 1u) ? d4.z : d4.x;			       // the entered side's parent
+	// the parent's enter record and its DFS record (a root reads, and drops, those of its own entered side: safe), then the rank
+	// look-ups of all four records as ONE batch (l0_at: R[0] where a record is not wanted)
+	const bool has_p = p != NIL;
+	const uint32_t pp = has_p ? p : e;
+	const uint2 r_p = erec[3 * (pp >> 1)], d_p = dps[pp];
+	const uint2 r0 = make_uint2(r01.x, r01.y), r1 = make_uint2(r01.z, r01.w);
+	const uint32_t i0 = l0_at(R, r0, !fin);
+	uint32_t a0 = R.ra[i0], b0 = R.rb[i0], a1 = R.ra[l0_at(R, r1, !fin)], a2 = R.ra[l0_at(R, r2, !fin && two_leaves)], a_p = R.ra[l0_at(R, r_p, !fin && has_p)];
+	landed(a0, b0, a1, a2, a_p);
+	const uint2 ent = rank_l0_pair(R, r0, fin, a0, b0), lv_o = make_uint2(rank_l0_a(R, r1, fin, a1), 0u);
+	const uint32_t lv_e2 = rank_l0_a(R, r2, fin, a2), ent_p = rank_l0_a(R, r_p, fin, a_p);
 	const uint32_t pre_e = Nh - ent.x, depth_e = 0u - ent.y;
-	uint32_t lv_e = lv_o.x;
-	if (!merged[g]) {
-		lv_e = rank_l0_a(R, erec[3 * g + 2], fin);
-	}
+	const uint32_t lv_e = two_leaves ? lv_e2 : lv_o.x;
 	const uint32_t size_o = ent.x - 1 - lv_o.x, size_e = ent.x - lv_e;
 	uint32_t par_e;
-	if (p == NIL)
+	if (!has_p)
 		par_e = hd ? 0u : NIL;
-	else {
-		par_e = hd + (Nh - rank_l0_a(R, erec[3 * (p >> 1)], fin)) + (dps[p].x == (p ^ 1u) ? 1u : 0u);
-	}
+	else
+		par_e = hd + (Nh - ent_p) + (d_p.x == (p ^ 1u) ? 1u : 0u);
 	const uint32_t l = hd + pre_e, t = tb + l; // e sits at t, o at t + 1
 	const uint32_t gid = gid_s[g];
 	store2_unaligned(t_gid + t, gid, gid);
