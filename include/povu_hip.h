@@ -836,6 +836,11 @@ int povu_hip_debug_tree(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, uint
  * creation order (Tree::add_tree_edge / add_be, spanning_tree.cpp:784-805).  Conformance export only; returns 3 after a
  * pass that built the tree with the one-lane kernels (POVU_HIP_F_SEQUENTIAL / POVU_HIP_F_SEQ_TREE). */
 int povu_hip_debug_edge_ids(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, uint32_t *tree_edge_id);
+/* three counter words of the last pass's class walks (tree stage, parallel form): out[0] = 2-edge-connected classes of
+ * more than one side, out[1] = classes the one-lane walk handed to the wave walk (0 with POVU_HIP_F_BIG_CLASS_DFS: it
+ * did not run), out[2] = entries the wave walks' stacks took from their pool (the sum of their chunk sizes).  Read-only:
+ * adds nothing to a pass.  Returns 3 / 4 like povu_hip_debug_edge_ids. */
+int povu_hip_debug_walk_words(povu_hip_ctx *ctx, uint32_t out[3]);
 /* candidate stack of component `comp`: tree vertex of each entry, class, next_seen */
 int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t *tree_vtx, uint32_t *cls,
 			 uint32_t *next_seen);

@@ -604,6 +604,27 @@ extern "C" int povu_hip_debug_edge_ids(povu_hip_ctx *ctx, uint32_t comp, uint32_
 	}
 }
 
+// the class walks' counter words of the last pass (cleared ahead of the tree stage, written by it alone): read-only, no launch
+extern "C" int povu_hip_debug_walk_words(povu_hip_ctx *ctx, uint32_t out[3])
+{
+	if (!ctx || !ctx->last.valid || !out)
+		return 1;
+	if (!ctx->last.plan.par_tree)
+		return 3; // the one-lane tree kernels walk no classes
+	if (ctx->last.mixed)
+		return 4; // (see povu_hip_debug_tree)
+	ctx->quiesce();
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		const int words[3] = {PW_N_ENTRY, PW_N_OVER, PW_POOL_TOP};
+		for (int i = 0; i < 3; i++)
+			HIP_CHECK(hipMemcpy(out + i, ctx->pw.err + words[i], 4, hipMemcpyDeviceToHost));
+		return 0;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
 extern "C" int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t *tree_vtx, uint32_t *cls,
 				    uint32_t *next_seen)
 {

@@ -339,6 +339,8 @@ def load_lib():
     l.povu_hip_last_laminar_check_ran.argtypes = [C.c_void_p]
     l.povu_hip_debug_edge_ids.restype = C.c_int
     l.povu_hip_debug_edge_ids.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]
+    l.povu_hip_debug_walk_words.restype = C.c_int
+    l.povu_hip_debug_walk_words.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     l.povu_hip_debug_stack.restype = C.c_int
     l.povu_hip_debug_stack.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
                                        C.c_void_p]
@@ -1566,6 +1568,15 @@ class HipDecomposer:
         if self._lib.povu_hip_debug_edge_ids(self._ctx, comp, C.byref(n), ids.ctypes.data) != 0:
             raise RuntimeError("povu_hip_debug_edge_ids failed")
         return ids
+
+    def debug_walk_words(self):
+        """dict(n_entry, n_over, pool_top) of the last pass's class walks (povu_hip_debug_walk_words): classes of more than
+        one side, classes handed from the one-lane walk to the wave walk, stack-pool entries the wave walks took."""
+        o = (C.c_uint32 * 3)()
+        rc = self._lib.povu_hip_debug_walk_words(self._ctx, o)
+        if rc != 0:
+            raise RuntimeError("no parallel-tree state" if rc in (3, 4) else "no decompose state")
+        return dict(n_entry=int(o[0]), n_over=int(o[1]), pool_top=int(o[2]))
 
     def debug_stack(self, comp: int):
         n = C.c_uint32(0)

@@ -87,7 +87,9 @@ def bridges_and_classes(n, edges):
     return bridges, [find(x) for x in range(n)]
 
 
-def model_tree(d, tips):
+def class_setup(d, tips):
+    """Steps (1) and (2) of the model: H, its bridges and classes, the DFS start, every class's entry side with its DFS
+    parent across the bridge.  Returns the state the per-class walks and finish_tree work on."""
     nv, adj = local_graph(d)
     n = 2 * nv
     has_tips = any(tips)
@@ -128,33 +130,51 @@ def model_tree(d, tips):
             entry[ecc[u]] = u
             dpar[u] = par0[u]
             cslot[u] = next(k for o, e, k in scan(par0[u]) if e == pe0[u])
-    # (3) independent DFS inside each class
-    for cls, s in entry.items():
-        vis = {s}
-        cur = {s: 0}
-        u = s
-        while True:
-            lst = scan(u)
-            k = cur[u]
-            adv = False
-            while k < len(lst):
-                o, e, slot = lst[k]
-                k += 1
-                if ecc[o] == cls and o not in vis:
-                    vis.add(o)
-                    dpar[o] = u
-                    cslot[o] = slot
-                    cur[u] = k
-                    cur[o] = 0
-                    u = o
-                    adv = True
-                    break
-            if adv:
-                continue
-            cur[u] = k
-            if u == s:
+    return dict(nv=nv, n=n, adj=adj, vid=vid, has_tips=has_tips, start=start, bridges=bridges, ecc=ecc, scan=scan,
+                entry=entry, dpar=dpar, cslot=cslot)
+
+
+def walk_class(st, cls, s):
+    """Step (3): the sequential DFS inside one class from its entry s; writes dpar / cslot of the sides it reaches."""
+    scan, ecc, dpar, cslot = st["scan"], st["ecc"], st["dpar"], st["cslot"]
+    vis = {s}
+    cur = {s: 0}
+    u = s
+    while True:
+        lst = scan(u)
+        k = cur[u]
+        adv = False
+        while k < len(lst):
+            o, e, slot = lst[k]
+            k += 1
+            if ecc[o] == cls and o not in vis:
+                vis.add(o)
+                dpar[o] = u
+                cslot[o] = slot
+                cur[u] = k
+                cur[o] = 0
+                u = o
+                adv = True
                 break
-            u = dpar[u]
+        if adv:
+            continue
+        cur[u] = k
+        if u == s:
+            break
+        u = dpar[u]
+
+
+def model_tree(d, tips):
+    st = class_setup(d, tips)
+    # (3) independent DFS inside each class
+    for cls, s in st["entry"].items():
+        walk_class(st, cls, s)
+    return finish_tree(st)
+
+
+def finish_tree(st):
+    """Steps (4) and (5) on the DFS parents and scan slots the class walks left in st."""
+    n, adj, vid, has_tips, start, dpar, cslot = (st[k] for k in ("n", "adj", "vid", "has_tips", "start", "dpar", "cslot"))
     # (4) pre-order with children ordered by the parent's scan position
     kids = [[] for _ in range(n)]
     for u in range(n):
@@ -210,26 +230,33 @@ def model_tree(d, tips):
     return dict(par=par, gid=gid, typ=typ, black=black, bes=sorted(bes))
 
 
-def check(g, tips=None):
-    info_tips = None
-    for comp in range(64):
+def component_dumps(g, tips=None, max_comp=64):
+    """(component rank, the oracle's dump with vid_local added, tips of its vertices) of the first max_comp components."""
+    deg = None
+    for comp in range(max_comp):
         d = dump_component(g, comp, tips)
         if d is None:
             break
-        if len(d["gid"]) == 0:
-            continue
         gl = d["gidx"]
         d["vid_local"] = [int(g.vid[v]) for v in gl.tolist()]
         if tips is None:
             # infer tips the way the loader does, on the global graph
-            deg = np.zeros((g.n_vtx, 2), dtype=np.int64)
-            for a, sa, b, sb in zip(g.v1.tolist(), g.s1.tolist(), g.v2.tolist(), g.s2.tolist()):
-                deg[a, sa] += 1
-                if not (a == b and sa == sb):
-                    deg[b, sb] += 1
+            if deg is None:
+                deg = np.zeros((g.n_vtx, 2), dtype=np.int64)
+                for a, sa, b, sb in zip(g.v1.tolist(), g.s1.tolist(), g.v2.tolist(), g.s2.tolist()):
+                    deg[a, sa] += 1
+                    if not (a == b and sa == sb):
+                        deg[b, sb] += 1
             info_tips = [1 if deg[v, 0] == 0 else (2 if deg[v, 1] == 0 else 0) for v in gl.tolist()]
         else:
             info_tips = [int(tips[v]) for v in gl.tolist()]
+        yield comp, d, info_tips
+
+
+def check(g, tips=None):
+    for comp, d, info_tips in component_dumps(g, tips):
+        if len(d["gid"]) == 0:
+            continue
         m = model_tree(d, info_tips)
         assert m["par"] == d["par"].tolist()
         assert m["gid"] == d["gid"].tolist()
