@@ -919,6 +919,25 @@ int povu_hip_debug_append(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, uin
  * 2 = device error. */
 int povu_hip_debug_list_rank(povu_hip_ctx *ctx, uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads,
 			     uint32_t nh, int mode, uint32_t bits, uint32_t *ra, uint32_t *rb);
+/* What the level-0 walk of a list ranking left in its records (tree_kernels.hip: a record is one narrow word -- the owner as
+ * a signed delta to its bucket, the partial sums in small fields -- or, where a field does not fit, an escaped pair of words).
+ * Counted by a kernel of its own that walks the lists again behind the ranking.  hist[33 * d + p] = live elements whose
+ * owner delta needs d bits (zigzag: 2|v| or 2|v| - 1) and whose partial sums need p bits (the events: the wider of the two),
+ * whatever the fields in use are. */
+typedef struct povu_hip_rank_records {
+	uint64_t live;		  /* elements a walk reaches */
+	uint64_t escaped;	  /* ... whose record is escaped (all of them when final_ranks) */
+	uint32_t final_ranks;	  /* the events' 16-bit partials overflowed: the records hold final ranks */
+	uint32_t bucket_bits;	  /* splitter bucket bits of the ranking */
+	uint32_t delta_bits;	  /* field of the signed owner delta: [-2^(delta_bits-1), 2^(delta_bits-1)) */
+	uint32_t partial_bits[2]; /* fields of the partial sums: the tour's one (second: 0); the events' partial(a) and partial(a) - partial(b) */
+	uint64_t hist[33 * 33];
+} povu_hip_rank_records;
+/* which: 0 = the tour's records of the last pass, 1 = its pre-order events' (both collected only when the environment
+ * variable POVU_HIP_RANK_STATS was set while the pass ran), 2 = those of the last povu_hip_debug_list_rank call.  esc
+ * (optional, which == 2 only, n_esc = that call's n): 1 where the element's record carries the escape bit (elements in no
+ * list: undefined).  Read-only.  0 = ok, 1 = bad arguments or no pass, 3 = nothing was collected. */
+int povu_hip_debug_rank_escapes(povu_hip_ctx *ctx, int which, povu_hip_rank_records *out, uint8_t *esc, size_t n_esc);
 /* timing hook (tools/scan_time.py): `reps` exclusive scans (op as above) of n device-resident words, ms per scan by HIP
  * events; < 0 on error */
 double povu_hip_debug_scan_time(povu_hip_ctx *ctx, size_t n, int reps, int op);

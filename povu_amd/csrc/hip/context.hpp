@@ -267,6 +267,9 @@ struct povu_hip_ctx {
 	ParWs pw{};
 	TreeWs tw{};
 	LastPass last;
+	// the records of the last povu_hip_debug_list_rank call: their statistics and the first word of every element's record
+	RankRecStats dbg_rank_stats;
+	std::vector<uint32_t> dbg_rank_plane0;
 	// when the resident graph is a shard (povu_hip_graph_upload_shard): ids of its components in the whole graph
 	// (1-based, ascending = the shard's own component order) and the component count of the whole graph
 	std::vector<uint32_t> shard_comp_ids;

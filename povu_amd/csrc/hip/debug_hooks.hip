@@ -453,11 +453,39 @@ extern "C" int povu_hip_debug_list_rank(povu_hip_ctx *ctx, uint32_t n, const uin
 		return 1;
 	try {
 		HIP_CHECK(hipSetDevice(ctx->device));
-		debug_list_rank(n, next, w, heads, nh, mode, bits, ra, rb, ctx->stream);
+		ctx->dbg_rank_stats.valid = false;
+		debug_list_rank(n, next, w, heads, nh, mode, bits, ra, rb, ctx->stream, &ctx->dbg_rank_stats, &ctx->dbg_rank_plane0);
 		return 0;
 	} catch (const std::exception &) {
 		return 2;
 	}
+}
+
+// ---- what the level-0 walks left in their records (tree_kernels.hip, k_rank_rec_stats): read-only, no launch.  The numbers
+// were counted by a kernel of its own behind the ranking -- in a pass only when POVU_HIP_RANK_STATS was set while it ran
+extern "C" int povu_hip_debug_rank_escapes(povu_hip_ctx *ctx, int which, povu_hip_rank_records *out, uint8_t *esc, size_t n_esc)
+{
+	if (!ctx || !out || which < 0 || which > 2 || (esc && which != 2))
+		return 1;
+	if (which < 2 && !ctx->last.valid)
+		return 1;
+	const RankRecStats &st = which == 2 ? ctx->dbg_rank_stats : ctx->tw.rec_stats[which];
+	if (!st.valid)
+		return 3; // nothing was collected
+	if (esc && n_esc != ctx->dbg_rank_plane0.size())
+		return 1;
+	out->live = st.live;
+	out->escaped = st.esc;
+	out->final_ranks = st.fin;
+	out->bucket_bits = st.bits;
+	out->delta_bits = st.delta_bits;
+	out->partial_bits[0] = st.part_bits[0];
+	out->partial_bits[1] = st.part_bits[1];
+	std::copy(st.hist, st.hist + 33 * 33, out->hist);
+	if (esc)
+		for (size_t x = 0; x < n_esc; x++)
+			esc[x] = st.fin ? 1 : (uint8_t)(ctx->dbg_rank_plane0[x] >> 31);
+	return 0;
 }
 
 // ---- timing hook for the scans: `reps` exclusive sum scans of n words (device resident, all ones), ms per scan by HIP events

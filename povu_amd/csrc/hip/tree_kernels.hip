@@ -370,17 +370,68 @@ __device__ __forceinline__ void rank_l0_weights(uint32_t x, uint32_t p, uint32_t
 		wb = wa ? 1u : 0xFFFFFFFFu;
 	}
 }
-// Level 0 leaves an 8-byte RECORD per element on the walk up, and no walk goes down it again: the lane's id (= the
+// Level 0 leaves a RECORD per element on the walk up, and no walk goes down it again: the lane's id (= the
 // element one level up whose rank the walks above hand out) and the sums from the splitter up to, not including, the
 // element.  Its rank is then R[owner] - partial (rank_l0 / rank_l0_pair), resolved by the kernels that read it -- one
-// store per element, where the way back stored the rank itself.  rec[x] = {owner, partial}; with TWO the second word
+// store per element, where the way back stored the rank itself.  A record is {owner, partial}; with TWO the second word
 // holds partial(a) | (partial(a) - partial(b)) << 16 (both never negative, at most two per element), and a segment
 // whose sums outgrow 16 bits raises *ovf: k_rank_l0_fallback then walks the list once more and stores final ranks.
+//
+// The record array (n 8-byte slots) is used as two PLANES of n words, and nearly every record is one word of plane 0:
+// the owner of x is a lane near bucket x >> b wherever the ids run along the lists, and a partial is bounded by the
+// length of a splitter segment (geometric, mean 2^b).
+//   narrow   plane0[x] = signed(owner - (x >> b)) << 15 | partial(s)         (bit 31 clear; ONE store)
+//   escaped  plane0[x] = REC_ESC | owner,  plane1[x] = the second word        (delta or partial out of its field)
+//   final    plane0[x] = a,  plane1[x] = b                                    (k_rank_l0_fallback; R.fin says so)
+// The delta takes the 16 bits below REC_ESC in both rankings.  The tour: 15 bits of partial.  The events: 7 bits of
+// partial(a), then 7 of partial(a) - partial(b); bit 14 stays clear.  Widths from the distributions in
+// profiles/rank_records_summary.md: on graphs whose ids run along the lists no delta needs more than 16 bits but those of
+// the head-led segments of later components, and no partial more than 8; a wider delta would buy nothing there, and at 16
+// bits both edges of the field can be reached by lists of 2^18 elements (tests/test_gpu_rank_records.py).
 static constexpr uint32_t REC_MAX = 0xFFFFu;
+static constexpr uint32_t REC_ESC = 0x80000000u;
+static constexpr unsigned REC_T_PBITS = 15, REC_T_DBITS = 16;
+static constexpr unsigned REC_E_PBITS = 7, REC_E_DBITS = 16;
+struct RecPlanes {
+	uint32_t *w0, *w1;
+};
+// plane 1 begins at a multiple of four words, so that 16-byte loads of either plane are aligned alike
+static RecPlanes rec_planes(uint2 *rec, size_t n)
+{
+	uint32_t *w = reinterpret_cast<uint32_t *>(rec);
+	return RecPlanes{w, w + ((n + 3) & ~(size_t)3)};
+}
+// the record of element x, walked by lane `owner`, with second word y (the tour: the partial; the events: pa | pd << 16)
+template <bool TWO>
+__device__ __forceinline__ void rec_store(const RecPlanes &rec, uint32_t x, unsigned b, uint32_t owner, uint32_t y)
+{
+	constexpr unsigned PB = TWO ? REC_E_PBITS : REC_T_PBITS, DB = TWO ? REC_E_DBITS : REC_T_DBITS;
+	constexpr uint32_t PMAX = (1u << PB) - 1u, HALF = 1u << (DB - 1);
+	const uint32_t d = owner - (x >> b), pa = TWO ? (y & REC_MAX) : y, pd = TWO ? (y >> 16) : 0u;
+	if (d + HALF < 2u * HALF && pa <= PMAX && pd <= PMAX) {
+		rec.w0[x] = ((d & (2u * HALF - 1u)) << (31u - DB)) | pa | (pd << PB);
+	} else {
+		rec.w0[x] = REC_ESC | owner;
+		rec.w1[x] = y;
+	}
+}
+// ... and back: {owner, second word} from the words of the planes (w1 is looked at only where w0 carries REC_ESC, or fin)
+template <bool TWO>
+__device__ __forceinline__ uint2 rec_decode(uint32_t x, unsigned b, uint32_t w0, uint32_t w1, bool fin = false)
+{
+	constexpr unsigned PB = TWO ? REC_E_PBITS : REC_T_PBITS, DB = TWO ? REC_E_DBITS : REC_T_DBITS;
+	constexpr uint32_t PMAX = (1u << PB) - 1u;
+	if (fin)
+		return make_uint2(w0, w1);
+	if (w0 & REC_ESC)
+		return make_uint2(w0 & ~REC_ESC, w1);
+	const uint32_t d = (uint32_t)((int32_t)(w0 << 1) >> (32 - DB));
+	return make_uint2((x >> b) + d, TWO ? ((w0 & PMAX) | (((w0 >> PB) & PMAX) << 16)) : (w0 & PMAX));
+}
 template <bool L0, bool TWO, bool EVT3 = false>
 __global__ void k_rank_up(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ nx_in, const uint32_t *__restrict__ a_in,
 			  const uint32_t *__restrict__ b_in, const uint32_t *__restrict__ heads, uint32_t *__restrict__ nx_out,
-			  uint32_t *__restrict__ a_out, uint32_t *__restrict__ b_out, uint2 *__restrict__ rec, uint32_t *__restrict__ ovf)
+			  uint32_t *__restrict__ a_out, uint32_t *__restrict__ b_out, RecPlanes rec, uint32_t *__restrict__ ovf)
 {
 	const uint32_t id = BIDX * blockDim.x + threadIdx.x;
 	if (id >= A.M)
@@ -398,9 +449,9 @@ __global__ void k_rank_up(RankLevelArgs A, unsigned b, const uint32_t *__restric
 				rank_l0_weights<EVT3>(x, p, wa, wb);
 				if (TWO) {
 					big |= sa > REC_MAX || sa - sb > REC_MAX;
-					rec[x] = make_uint2(id, sa | ((sa - sb) << 16));
+					rec_store<true>(rec, x, b, id, sa | ((sa - sb) << 16));
 				} else {
-					rec[x] = make_uint2(id, sa);
+					rec_store<false>(rec, x, b, id, sa);
 				}
 				sa += wa;
 				if (TWO)
@@ -427,11 +478,11 @@ __global__ void k_rank_up(RankLevelArgs A, unsigned b, const uint32_t *__restric
 	if (L0 && TWO && big)
 		*ovf = 1u;
 }
-// (a pass whose level-0 walk raised *ovf: the old way back over the list, final ranks {a, b} into rec; a grid-stride loop
+// (a pass whose level-0 walk raised *ovf: the old way back over the list, final ranks a, b into the two planes; a grid-stride loop
 // over the lanes, so that the launch costs next to nothing when the flag is down)
 template <bool EVT3>
 __global__ void k_rank_l0_fallback(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ pk, const uint32_t *__restrict__ heads,
-				   const uint32_t *__restrict__ ra, const uint32_t *__restrict__ rb, uint2 *__restrict__ rec,
+				   const uint32_t *__restrict__ ra, const uint32_t *__restrict__ rb, RecPlanes rec,
 				   const uint32_t *__restrict__ ovf)
 {
 	if (!*ovf)
@@ -445,7 +496,8 @@ __global__ void k_rank_l0_fallback(RankLevelArgs A, unsigned b, const uint32_t *
 			const uint32_t p = pk[x];
 			uint32_t wa, wb;
 			rank_l0_weights<EVT3>(x, p, wa, wb);
-			rec[x] = make_uint2(sa, sb);
+			rec.w0[x] = sa;
+			rec.w1[x] = sb;
 			sa -= wa;
 			sb -= wb;
 			x = p & P0_END;
@@ -554,6 +606,8 @@ static size_t rank_pool_words(size_t n, size_t nh) { return n / 2 + 4 * nh + 64;
 struct L0Ranks {
 	const uint32_t *ra, *rb, *fin;
 	uint32_t M;
+	const uint32_t *w0, *w1; // the two planes of the level-0 records (rec_planes)
+	unsigned b;		  // bucket bits of the ranking (rec_decode)
 };
 // The gathers are unconditional (gather_if, common.hpp), so that a reader's look-ups leave together as one batch: it gathers
 // R.ra (and R.rb) at l0_at() of every record, puts landed() behind the batch and hands each word to rank_l0* with its record.
@@ -574,20 +628,101 @@ __device__ __forceinline__ uint2 rank_l0_pair(const L0Ranks &R, uint2 rec, bool 
 	const uint32_t pa = rec.y & REC_MAX;
 	return fin ? rec : make_uint2((in ? ra : 0u) - pa, (in ? rb : 0u) - pa + (rec.y >> 16));
 }
-// one record on its own
-__device__ __forceinline__ uint32_t rank_l0(const L0Ranks &R, uint2 rec) { return rank_l0(R, rec, R.ra[l0_at(R, rec)]); }
-__device__ __forceinline__ uint2 rank_l0_pair(const L0Ranks &R, uint2 rec, bool fin)
+// one element on its own, from the planes (plane 1 only where the record escaped)
+__device__ __forceinline__ uint32_t rank_l0_of(const L0Ranks &R, uint32_t x)
 {
+	const uint32_t w0 = R.w0[x];
+	const uint2 rec = rec_decode<false>(x, R.b, w0, (w0 & REC_ESC) ? R.w1[x] : 0u);
+	return rank_l0(R, rec, R.ra[l0_at(R, rec)]);
+}
+__device__ __forceinline__ uint2 rank_l0_pair_of(const L0Ranks &R, uint32_t x, bool fin)
+{
+	const uint32_t w0 = R.w0[x];
+	const uint2 rec = rec_decode<true>(x, R.b, w0, (fin || (w0 & REC_ESC)) ? R.w1[x] : 0u, fin);
 	const uint32_t i = l0_at(R, rec, !fin);
 	return rank_l0_pair(R, rec, fin, R.ra[i], R.rb[i]);
+}
+
+// (debug hook povu_hip_debug_rank_escapes) What the level-0 walk left, counted after the fact by a walk of its own over the
+// same segments: the elements it reaches, how many of their records carry REC_ESC, and the histogram of the widths their
+// owner delta (zigzag) and partial sums need (RankRecStats).  out[0] = live, out[1] = escaped, out[2 + 33 d + p] = the histogram.
+__device__ __forceinline__ uint32_t bit_width(uint32_t v) { return 32u - (uint32_t)__clz(v); }
+template <bool TWO, bool EVT3>
+__global__ void k_rank_rec_stats(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ pk, const uint32_t *__restrict__ heads,
+				 const uint32_t *__restrict__ w0, unsigned long long *__restrict__ out)
+{
+	__shared__ uint32_t h[2 + 33 * 33];
+	for (uint32_t i = threadIdx.x; i < 2 + 33 * 33; i += blockDim.x)
+		h[i] = 0;
+	__syncthreads();
+	for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < A.M; id += gridDim.x * blockDim.x) {
+		uint32_t x = rank_lane_start<true>(id, A, b, pk, heads);
+		if (x == NIL)
+			continue;
+		uint32_t sa = 0, sb = 0;
+		do {
+			const uint32_t p = pk[x];
+			uint32_t wa, wb;
+			rank_l0_weights<EVT3>(x, p, wa, wb);
+			const int32_t d = (int32_t)(id - (x >> b));
+			const uint32_t zz = ((uint32_t)d << 1) ^ (uint32_t)(d >> 31);
+			const uint32_t pw = TWO ? max(bit_width(sa), bit_width(sa - sb)) : bit_width(sa);
+			atomicAdd(&h[0], 1u);
+			if (w0[x] & REC_ESC)
+				atomicAdd(&h[1], 1u);
+			atomicAdd(&h[2 + 33 * bit_width(zz) + pw], 1u);
+			sa += wa;
+			if (TWO)
+				sb += wb;
+			x = p & P0_END;
+		} while (!rank_l0_stop(x, b));
+	}
+	__syncthreads();
+	for (uint32_t i = threadIdx.x; i < 2 + 33 * 33; i += blockDim.x)
+		if (h[i])
+			atomicAdd(&out[i], (unsigned long long)h[i]);
+}
+template <bool TWO, bool EVT3>
+static void rank_rec_stats(const RankLevelArgs &A, unsigned b, const RankBufs &rb, const L0Ranks &R, RankRecStats &st, hipStream_t s)
+{
+	constexpr size_t W = 2 + 33 * 33;
+	st = RankRecStats{};
+	unsigned long long *d = nullptr;
+	uint32_t fin = 0;
+	std::vector<unsigned long long> hst(W);
+	HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), W * 8));
+	try {
+		HIP_CHECK(hipMemsetAsync(d, 0, W * 8, s));
+		// (a block's LDS counters are 32 bits wide: at most 2048 blocks of 256 lanes, each lane over M / 2^19 segments)
+		KLAUNCH((k_rank_rec_stats<TWO, EVT3>), dim3(std::min(nblk(A.M), 2048u)), dim3(TPB), 0, s, A, b, rb.pk, rb.heads, R.w0, d);
+		HIP_CHECK(copy_async(hst.data(), d, W * 8, hipMemcpyDeviceToHost, s));
+		if (TWO)
+			HIP_CHECK(copy_async(&fin, R.fin, 4, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+	} catch (...) {
+		(void)hipFree(d);
+		throw;
+	}
+	HIP_CHECK(hipFree(d));
+	st.valid = true;
+	st.fin = fin;
+	st.bits = b;
+	st.delta_bits = TWO ? REC_E_DBITS : REC_T_DBITS;
+	st.part_bits[0] = TWO ? REC_E_PBITS : REC_T_PBITS;
+	st.part_bits[1] = TWO ? REC_E_PBITS : 0u;
+	st.live = hst[0];
+	st.esc = fin ? hst[0] : hst[1];
+	std::copy(hst.begin() + 2, hst.end(), st.hist);
 }
 
 // suffix sums (inclusive) along the lists packed in rb.pk, left as level-0 records rec[x] (k_rank_up) to be resolved
 // by rank_l0 (the 0/1 weights) or rank_l0_pair (TWO: that sum and the sum of the +-1 weights derived from them; `ovf`
 // = a device word for the overflow flag).  R stays valid until the pools are used again.
 template <bool TWO, bool EVT3 = false>
-static L0Ranks list_rank_splitters(uint32_t n, unsigned b, uint2 *rec, uint32_t *ovf, uint32_t nh, RankBufs &rb, hipStream_t s)
+static L0Ranks list_rank_splitters(uint32_t n, unsigned b, uint2 *rec_arr, uint32_t *ovf, uint32_t nh, RankBufs &rb, hipStream_t s,
+				   RankRecStats *st = nullptr)
 {
+	const RecPlanes rec = rec_planes(rec_arr, n);
 	if (n >= P0_END)
 		throw HipError("list ranking: more than 2^30 elements (graph too large for the packed walk)");
 	// plan: level L has lv[L].n elements; its walk has lv[L].M lanes = the elements of level L + 1
@@ -626,7 +761,7 @@ static L0Ranks list_rank_splitters(uint32_t n, unsigned b, uint2 *rec, uint32_t 
 			LAUNCH((k_rank_up<true, TWO, EVT3>), A.M, s, A, b, nxp[0], nullptr, nullptr, rb.heads, nxp[1], wap[1], wbp[1], rec, ovf);
 		else
 			LAUNCH((k_rank_up<false, TWO>), A.M, s, A, b, nxp[L], wap[L], wbp[L], nullptr, nxp[L + 1], wap[L + 1], wbp[L + 1],
-			       nullptr, nullptr);
+			       RecPlanes{nullptr, nullptr}, nullptr);
 	}
 	const uint32_t nt = cur_n; // elements of the top level
 	if (nt <= RANK_TOP) {
@@ -653,26 +788,29 @@ static L0Ranks list_rank_splitters(uint32_t n, unsigned b, uint2 *rec, uint32_t 
 	if (TWO)
 		KLAUNCH((k_rank_l0_fallback<EVT3>), dim3(std::min(nblk(lv[0].M), 2048u)), dim3(TPB), 0, s, lv[0], b, rb.pk, rb.heads, wap[1],
 			wbp[1], rec, ovf);
-	return L0Ranks{wap[1], TWO ? wbp[1] : nullptr, TWO ? ovf : nullptr, lv[0].M};
+	const L0Ranks R{wap[1], TWO ? wbp[1] : nullptr, TWO ? ovf : nullptr, lv[0].M, rec.w0, rec.w1, b};
+	if (st)
+		rank_rec_stats<TWO, EVT3>(lv[0], b, rb, R, *st, s);
+	return R;
 }
 
 // (unit-test hook, debug_list_rank) every element's rank resolved from its record, as the readers do
 template <bool TWO>
-__global__ void k_rank_resolve(uint32_t n, const uint2 *__restrict__ rec, L0Ranks R, uint32_t *__restrict__ ra, uint32_t *__restrict__ rb)
+__global__ void k_rank_resolve(uint32_t n, L0Ranks R, uint32_t *__restrict__ ra, uint32_t *__restrict__ rb)
 {
 	const uint32_t x = BIDX * blockDim.x + threadIdx.x;
 	if (x >= n)
 		return;
 	if (TWO) {
-		const uint2 r = rank_l0_pair(R, rec[x], *R.fin != 0);
+		const uint2 r = rank_l0_pair_of(R, x, *R.fin != 0);
 		ra[x] = r.x;
 		rb[x] = r.y;
 	} else {
-		ra[x] = rank_l0(R, rec[x]);
+		ra[x] = rank_l0_of(R, x);
 	}
 }
 void debug_list_rank(uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads, uint32_t nh, int mode,
-		     unsigned bits, uint32_t *ra, uint32_t *rb, hipStream_t s)
+		     unsigned bits, uint32_t *ra, uint32_t *rb, hipStream_t s, RankRecStats *st, std::vector<uint32_t> *plane0)
 {
 	if (n == 0 || n >= P0_END)
 		throw HipError("debug_list_rank: n must be in [1, 2^30)");
@@ -703,11 +841,15 @@ void debug_list_rank(uint32_t n, const uint32_t *next, const uint8_t *w, const u
 	if (nh)
 		HIP_CHECK(copy_async(rbf.heads, heads, (size_t)nh * 4, hipMemcpyHostToDevice, s));
 	if (mode == 0) {
-		const L0Ranks R = list_rank_splitters<false>(n, b, rec, nullptr, nh, rbf, s);
-		LAUNCH(k_rank_resolve<false>, n, s, n, rec, R, da, nullptr);
+		const L0Ranks R = list_rank_splitters<false>(n, b, rec, nullptr, nh, rbf, s, st);
+		LAUNCH(k_rank_resolve<false>, n, s, n, R, da, nullptr);
 	} else {
-		const L0Ranks R = list_rank_splitters<true, true>(n, b, rec, ovf, nh, rbf, s);
-		LAUNCH(k_rank_resolve<true>, n, s, n, rec, R, da, db);
+		const L0Ranks R = list_rank_splitters<true, true>(n, b, rec, ovf, nh, rbf, s, st);
+		LAUNCH(k_rank_resolve<true>, n, s, n, R, da, db);
+	}
+	if (plane0) {
+		plane0->resize(n);
+		HIP_CHECK(copy_async(plane0->data(), rec, (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	}
 	HIP_CHECK(copy_async(ra, da, (size_t)n * 4, hipMemcpyDeviceToHost, s));
 	if (mode != 0)
@@ -743,7 +885,7 @@ static constexpr uint32_t T0_RBIT = 0x80000000u;
 // subtrees hanging off the far side (BS_NOARC: the far side has no arc, no stretch) and the FT_HASH bits of the l and
 // the r side.  Tour positions stay below 2^30 (tree_tour_words), so the two top bits of either word are free.
 static constexpr uint32_t BS_POS = 0x3FFFFFFFu, BS_NOARC = 0x80000000u, BS_HASH_L = 0x40000000u, BS_HASH_R = 0x80000000u;
-__global__ void k_t0_parents(uint32_t V, const uint2 *__restrict__ trec, L0Ranks R, const uint32_t *__restrict__ ckey,
+__global__ void k_t0_parents(uint32_t V, L0Ranks R, const uint32_t *__restrict__ ckey,
 			     const uint32_t *__restrict__ voff, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
 			     const uint32_t *__restrict__ lle,
 			     const uint32_t *__restrict__ ft, const uint32_t *__restrict__ heads,
@@ -758,7 +900,7 @@ __global__ void k_t0_parents(uint32_t V, const uint2 *__restrict__ trec, L0Ranks
 		t0seg[r >> 1] = make_uint4(NIL, (r & 1u) ? T0_RBIT : 0u, 0u, L ? L - 1 : 0u);
 		// the tour of the component covers all its arcs iff the hooks of the union-find are a spanning tree
 		const uint32_t h = heads[g];
-		if (h == NIL ? L != 0 : rank_l0(R, trec[h]) != L - 1)
+		if (h == NIL ? L != 0 : rank_l0_of(R, h) != L - 1)
 			atomicExch(err, 1u);
 	}
 	if (g >= V)
@@ -775,15 +917,25 @@ __global__ void k_t0_parents(uint32_t V, const uint2 *__restrict__ trec, L0Ranks
 	uint32_t at_e = NIL, dmin = 0xFFFFFFFFu, dmax = 0u;
 	uint32_t a_l = NIL, a_r = NIL, d_l = 0u, d_r = 0u; // first forest slot of the l and of the r side, and its distance
 	for (uint32_t at0 = sb; at0 < se; at0 += 4) {
-		const uint32_t *r32 = reinterpret_cast<const uint32_t *>(trec + at0);
-		const uint4 lw4 = load4_unaligned(lle + at0), r01 = load4_unaligned(r32), r23 = load4_unaligned(r32 + 4);
-		const uint32_t lws[4] = {lw4.x, lw4.y, lw4.z, lw4.w};
-		const uint2 rs[4] = {make_uint2(r01.x, r01.y), make_uint2(r01.z, r01.w), make_uint2(r23.x, r23.y), make_uint2(r23.z, r23.w)};
-		bool tree[4];
+		const uint4 lw4 = load4_unaligned(lle + at0), w4 = load4_unaligned(R.w0 + at0);
+		const uint32_t lws[4] = {lw4.x, lw4.y, lw4.z, lw4.w}, w0s[4] = {w4.x, w4.y, w4.z, w4.w};
+		bool tree[4], esc = false;
+#pragma unroll
+		for (uint32_t q = 0; q < 4; q++) {
+			tree[q] = at0 + q < se && (lws[q] & LLE_TREE);
+			esc |= tree[q] && (w0s[q] & REC_ESC);
+		}
+		// the second words of escaped records: a wave that holds none (nearly all, on graphs whose ids run along the tours)
+		// skips the load; one that does takes all four words of the round (in bounds: the planes have three words of slack)
+		uint4 y4 = make_uint4(0u, 0u, 0u, 0u);
+		if (__any(esc))
+			y4 = load4_unaligned(R.w1 + at0);
+		const uint32_t w1s[4] = {y4.x, y4.y, y4.z, y4.w};
+		uint2 rs[4];
 		uint32_t ds[4];
 #pragma unroll
 		for (uint32_t q = 0; q < 4; q++) { // (the four gathers of R issued together; a segment with a slot has a ranking behind it: R[0] is safe)
-			tree[q] = at0 + q < se && (lws[q] & LLE_TREE);
+			rs[q] = rec_decode<false>(at0 + q, R.b, w0s[q], w1s[q]);
 			ds[q] = R.ra[l0_at(R, rs[q], tree[q])];
 		}
 		landed(ds[0], ds[1], ds[2], ds[3]);
@@ -1523,7 +1675,7 @@ __global__ void k_events(uint32_t V, const uint2 *__restrict__ dps, const uint32
 // OC / SC / IC: the width of ordcnt / srccnt / incnt (uint8_t when no count of the pass can reach 256, see ParWs::narrow_ordcnt /
 // narrow_srccnt / narrow_incnt)
 template <typename OC, typename SC, typename IC>
-__global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks R, const uint8_t *__restrict__ merged,
+__global__ void k_tree_emit(uint32_t nS, L0Ranks R, const uint8_t *__restrict__ merged,
 			    const uint2 *__restrict__ dps, const uint32_t *__restrict__ ckey,
 			    const uint32_t *__restrict__ cproc, const uint32_t *__restrict__ voff,
 			    const unsigned long long *__restrict__ start_key, const uint32_t *__restrict__ gid_s,
@@ -1595,8 +1747,7 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 	// cd(event) = {sides entered from this event to the end of the list, net depth change from here to the end}, worked out
 	// from the event's record (rank_l0_pair)
 	const bool fin = *R.fin != 0;
-	const uint4 r01 = load4_unaligned(reinterpret_cast<const uint32_t *>(erec + 3 * g)); // records of 3g, 3g + 1
-	const uint2 r2 = erec[3 * g + 2];						     // ... of 3g + 2: the lane's own, read also where the leaves are one event
+	const uint4 w4 = load4_unaligned(R.w0 + 3 * g); // first words of the records of 3g, 3g + 1 and 3g + 2 (the lane's own, read also where the leaves are one event)
 	const bool two_leaves = !merged[g];
 	const uint4 d4 = *reinterpret_cast<const uint4 *>(dps + 2 * g); // the DFS records of both sides
 	const uint32_t o = d4.x == 2 * g + 1 ? 2 * g : 2 * g + 1, e = o ^ 1u; // far side: its DFS parent is the other side
@@ -1605,8 +1756,18 @@ __global__ void k_tree_emit(uint32_t nS, const uint2 *__restrict__ erec, L0Ranks
 	// look-ups of all four records as ONE batch (l0_at: R[0] where a record is not wanted)
 	const bool has_p = p != NIL;
 	const uint32_t pp = has_p ? p : e;
-	const uint2 r_p = erec[3 * (pp >> 1)], d_p = dps[pp];
-	const uint2 r0 = make_uint2(r01.x, r01.y), r1 = make_uint2(r01.z, r01.w);
+	const uint32_t xp = 3 * (pp >> 1), wp = R.w0[xp];
+	const uint2 d_p = dps[pp];
+	// the second words: only a wave that holds an escaped record, or a pass whose records hold final ranks, reads plane 1
+	// (the third event of merged leaves and a root's "parent" are in no list: what their words hold says nothing)
+	uint4 y4 = make_uint4(0u, 0u, 0u, 0u);
+	uint32_t yp = 0u;
+	if (__any(fin || ((w4.x | w4.y | (two_leaves ? w4.z : 0u) | (has_p ? wp : 0u)) & REC_ESC))) {
+		y4 = load4_unaligned(R.w1 + 3 * g);
+		yp = R.w1[xp];
+	}
+	const uint2 r0 = rec_decode<true>(3 * g, R.b, w4.x, y4.x, fin), r1 = rec_decode<true>(3 * g + 1, R.b, w4.y, y4.y, fin);
+	const uint2 r2 = rec_decode<true>(3 * g + 2, R.b, w4.z, y4.z, fin), r_p = rec_decode<true>(xp, R.b, wp, yp, fin);
 	const uint32_t i0 = l0_at(R, r0, !fin);
 	uint32_t a0 = R.ra[i0], b0 = R.rb[i0], a1 = R.ra[l0_at(R, r1, !fin)], a2 = R.ra[l0_at(R, r2, !fin && two_leaves)], a_p = R.ra[l0_at(R, r_p, !fin && has_p)];
 	landed(a0, b0, a1, a2, a_p);
@@ -2084,7 +2245,11 @@ struct TreePass {
 		  bitsA(sparse ? 4u : rank_bucket_bits(n_slots)), bitsE(sparse ? 4u : rank_bucket_bits(n_events)),
 		  rb{tw_.rk_pk, tw_.rk_heads, tw_.rk_nx, tw_.rk_wa, tw_.rk_wb, tw_.rk_tA, tw_.rk_tB, tw_.rk_tC}
 	{
+		tw.rec_stats[0].valid = tw.rec_stats[1].valid = false; // (what an earlier pass collected says nothing about this one)
 	}
+	// where ranking k (0 = the tour, 1 = the events) leaves the statistics of its records: nowhere, unless POVU_HIP_RANK_STATS
+	// asks for them (debug hook: a kernel and a wait of its own behind the ranking)
+	RankRecStats *rec_stats(int k) { return getenv("POVU_HIP_RANK_STATS") ? &tw.rec_stats[k] : nullptr; }
 	// (7.) one list per processed component, one two-event list per side of an unprocessed one
 	void enqueue_events()
 	{
@@ -2107,9 +2272,9 @@ static void root_forest(TreePass &P)
 	tw.tour_words_done = false;
 	LAUNCH(k_tour_ends, C, s, C, cs.voff, P.start_key, cs.loff, cs.ladj, cs.lle, P.rb.pk, P.rb.heads);
 	if (P.n_slots)
-		P.tour_r = list_rank_splitters<false>((uint32_t)P.n_slots, P.bitsA, tw.dist, nullptr, C, P.rb, s);
+		P.tour_r = list_rank_splitters<false>((uint32_t)P.n_slots, P.bitsA, tw.dist, nullptr, C, P.rb, s, P.rec_stats(0));
 	HIP_CHECK(hipMemsetAsync(tw.xrec, 0, ((size_t)P.XW + 2) * 16, s));
-	LAUNCH(k_t0_parents, std::max(V, C), s, V, tw.dist, P.tour_r, cs.ckey, cs.voff, cs.loff, cs.ladj, cs.lle, P.v.ft, P.rb.heads,
+	LAUNCH(k_t0_parents, std::max(V, C), s, V, P.tour_r, cs.ckey, cs.voff, cs.loff, cs.ladj, cs.lle, P.v.ft, P.rb.heads,
 	       tw.t0seg, P.v.fstr, tw.xrec, C, P.start_key, P.pw.err + PW_FOREST_SIZE, P.v.multi);
 	P.tm.end(40);
 }
@@ -2236,7 +2401,7 @@ static void preorder(TreePass &P)
 	P.tm.begin("tree_preorder");
 	if (!P.events_done)
 		P.enqueue_events();
-	P.evr = list_rank_splitters<true, true>(P.n_events, P.bitsE, P.tw.evt, P.pw.err + PW_RANK_OVF, P.C, P.rb, P.s);
+	P.evr = list_rank_splitters<true, true>(P.n_events, P.bitsE, P.tw.evt, P.pw.err + PW_RANK_OVF, P.C, P.rb, P.s, P.rec_stats(1));
 	P.tm.end(40);
 }
 
@@ -2254,7 +2419,7 @@ static void emit_tree(TreePass &P)
 		using OC = std::remove_pointer_t<decltype(ordcnt)>;
 		using SC = std::remove_pointer_t<decltype(srccnt)>;
 		using IC = std::remove_pointer_t<decltype(incnt)>;
-		LAUNCH((k_tree_emit<OC, SC, IC>), std::max(P.V, P.C), P.s, P.nS, tw.evt, P.evr, P.v.merged, tw.dps, cs.ckey, tw.cproc, cs.voff, P.start_key, cs.gid_s, sw.t_gid,
+		LAUNCH((k_tree_emit<OC, SC, IC>), std::max(P.V, P.C), P.s, P.nS, P.evr, P.v.merged, tw.dps, cs.ckey, tw.cproc, cs.voff, P.start_key, cs.gid_s, sw.t_gid,
 		       sw.t_flags, sw.t_par, sw.t_size, (sw.hairpins || sw.want_depth) ? sw.t_depth : nullptr, tw.side_tidx, P.C, sw.c_ntree, ordcnt,
 		       pw.hi0, pw.mpre, srccnt, pw.sdl, incnt);
 	};

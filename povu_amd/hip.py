@@ -38,6 +38,11 @@ class _Opts(C.Structure):
     _fields_ = [("rank", C.c_uint32), ("world", C.c_uint32), ("flags", C.c_uint32)]
 
 
+class _RankRecords(C.Structure):
+    _fields_ = [("live", C.c_uint64), ("escaped", C.c_uint64), ("final_ranks", C.c_uint32), ("bucket_bits", C.c_uint32),
+                ("delta_bits", C.c_uint32), ("partial_bits", C.c_uint32 * 2), ("hist", C.c_uint64 * (33 * 33))]
+
+
 class _SubTree(C.Structure):
     _fields_ = [("n_total", C.c_uint32), ("n_flubble_like", C.c_uint32), ("n_concealed", C.c_uint32), ("n_midi", C.c_uint32),
                 ("n_smothered", C.c_uint32), ("fam", C.POINTER(C.c_uint8)), ("or1", C.POINTER(C.c_uint8)),
@@ -362,6 +367,8 @@ def load_lib():
                                          C.c_void_p]
     l.povu_hip_debug_append.restype = C.c_int
     l.povu_hip_debug_append.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_uint32)]
+    l.povu_hip_debug_rank_escapes.restype = C.c_int
+    l.povu_hip_debug_rank_escapes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
     l.povu_hip_debug_list_rank.restype = C.c_int
     l.povu_hip_debug_list_rank.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                            C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -1507,7 +1514,27 @@ class HipDecomposer:
                                                 1 if events else 0, bits, ra.ctypes.data, rb.ctypes.data)
         if rc:
             raise RuntimeError(f"debug_list_rank failed ({rc})")
+        self._last_list_rank_n = nxt.size
         return (ra, rb) if events else ra
+
+    def debug_rank_escapes(self, which: str = "list_rank", flags: bool = False):
+        """Read-only hook: what a level-0 walk left in its records.  `which`: "tour" / "events" of the last pass (run
+        with POVU_HIP_RANK_STATS set), or "list_rank", the last debug_list_rank call.  A dict: live, escaped,
+        final_ranks, bucket_bits, delta_bits, partial_bits, hist[33, 33] (delta bits x partial bits); with `flags`
+        (list_rank only) also esc, one byte per element."""
+        k = {"tour": 0, "events": 1, "list_rank": 2}[which]
+        rec = _RankRecords()
+        esc = np.zeros(self._last_list_rank_n if flags else 0, dtype=np.uint8)
+        rc = self._lib.povu_hip_debug_rank_escapes(self._ctx, k, C.byref(rec), esc.ctypes.data if flags else None, esc.size)
+        if rc:
+            raise RuntimeError(f"debug_rank_escapes failed ({rc})")
+        out = {"live": int(rec.live), "escaped": int(rec.escaped), "final_ranks": bool(rec.final_ranks),
+               "bucket_bits": int(rec.bucket_bits), "delta_bits": int(rec.delta_bits),
+               "partial_bits": (int(rec.partial_bits[0]), int(rec.partial_bits[1])),
+               "hist": np.ctypeslib.as_array(rec.hist).reshape(33, 33).copy()}
+        if flags:
+            out["esc"] = esc
+        return out
 
     def debug_components(self, n_vtx: int):
         comp = np.zeros(n_vtx, dtype=np.uint32)
