@@ -380,6 +380,7 @@ typedef struct {
 #define POVU_HIP_T_NESTED 4u	  /* povu_hip_call only: alleles modulo enclosed sites, levels and parents by geometry ("Nested calls") */
 #define POVU_HIP_T_MERGE 8u	  /* povu_hip_call_profile under POVU_HIP_PROFILE_DECOMPOSED only: equal primitives merged ("Merged primitives") */
 #define POVU_HIP_T_OFFREF 16u	  /* povu_hip_call / _call_profile only: sites no reference path crosses, on a surrogate path ("Off-reference calls") */
+#define POVU_HIP_T_UNTANGLE 32u	  /* povu_hip_call / _call_profile only: per-copy genotypes where a path laps a site, by lap alignment ("Untangled calls") */
 #define POVU_HIP_TRAV_LONG 1u	  /* status bits per query: a scan would need more than max_steps steps */
 #define POVU_HIP_TRAV_STRAY 2u	  /* a scan met a boundary step that does not close it */
 #define POVU_HIP_TRAV_OPEN 4u	  /* a scan reached the end of its path */
@@ -541,6 +542,21 @@ typedef struct {
 	uint64_t n_offref_sites;      /* sites called off-reference with two alleles or more */
 	uint64_t n_offref_records;
 	uint64_t n_offref_hosted;     /* off-reference records with a host */
+	/* with POVU_HIP_T_UNTANGLE ("Untangled calls").  Without the flag: untangled 0, the counts 0, the arrays NULL.  The laps of
+	 * a path through a site are its traversals of it in path order.  Where the reference path and the one path of a slot both
+	 * lap a site in one direction each, at most 64 times, the slot's laps are aligned with the reference's (unit cost, the tie
+	 * rule of "Decomposed calls") and the record of reference lap j takes the slot's allele from the lap aligned with j ('.'
+	 * when none is); every other entry keeps the rule of "Variant calls".  Inversion records: 0 everywhere */
+	uint64_t untangled;	      /* 1: made with POVU_HIP_T_UNTANGLE */
+	const uint8_t *rec_unt;	      /* [n_records] 1: some entry of the record was aligned in a table of two laps or more (written with LN, LC, GT:CN) */
+	const uint32_t *lap;	      /* [n_records] lap of the reference path the record is, from 1 */
+	const uint32_t *n_laps;	      /* [n_records] laps of the reference path through the site */
+	const uint16_t *lap_count;    /* [n_records * n_slots] traversals of the site by the slot's paths, saturating at 65 535 */
+	uint64_t n_unt_tasks;	      /* alignments run: distinct (site, reference path, path) with two laps or more on a side */
+	uint64_t n_unt_records;	      /* records with rec_unt */
+	uint64_t n_unt_missing;	      /* reference laps without a partner, over the alignments */
+	uint64_t n_unt_extra;	      /* laps of the other path without a partner, over the alignments */
+	uint64_t n_unt_fallback;      /* (record, slot) entries of two traversals or more that were left to the rule of "Variant calls" */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
@@ -550,7 +566,10 @@ typedef struct {
  * merged in ((reference path, POS, query, first, n_steps) order; `sites` may be empty); refused then too for 2^32 path
  * steps or run heads or more.  With POVU_HIP_T_OFFREF the off-reference records are added (the record order becomes (path,
  * POS, query, first); inversion records stay those of the reference paths); the flag is refused together with
- * POVU_HIP_T_NESTED, POVU_HIP_T_MERGE or any profile other than _RAW_GRAPH.  Free with povu_hip_calls_free. */
+ * POVU_HIP_T_NESTED, POVU_HIP_T_MERGE or any profile other than _RAW_GRAPH.  With POVU_HIP_T_UNTANGLE the rows of the sites
+ * a path laps are rewritten from lap alignments (the records and their order stay); refused together with POVU_HIP_T_NESTED,
+ * POVU_HIP_T_MERGE, POVU_HIP_T_OFFREF or any profile other than _RAW_GRAPH, for 2^32 (reference run, slot) entries or more and
+ * for a partner table beyond device memory.  Free with povu_hip_calls_free. */
 povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
 			      const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, char *err, size_t errlen);
 /* The profiles of a nested call ("Nested calls"): what is kept of the flubble records, decided on the device before any
@@ -684,7 +703,10 @@ char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, c
 char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
 				 const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, uint32_t profile,
 				 size_t *len);
-/* With rec_offref not NULL or offref set (POVU_HIP_T_OFFREF; a call without records has no arrays) _vcf_profile writes the off-reference records too: `;OFFREF=T` and, with a host,
+/* With rec_unt not NULL or untangled set (POVU_HIP_T_UNTANGLE) _vcf_profile writes the header lines of LN, LC and CN behind those
+ * above and an untangled record with `;LN=<lap>;LC=<n_laps>` behind LV, FORMAT GT:CN and every sample column <GT>:<CN>; NULL when
+ * only some of rec_unt, lap, n_laps and lap_count are given.
+ * With rec_offref not NULL or offref set (POVU_HIP_T_OFFREF; a call without records has no arrays) _vcf_profile writes the off-reference records too: `;OFFREF=T` and, with a host,
  * `;HOST=<its label>;HA=<its allele>` behind LV, the ##INFO lines of the three keys in front of the contig lines, and behind
  * the reference paths' contig lines one for every surrogate of off_contig_path (of those the prefix selects); NULL when a
  * host_query or an off_contig_path points outside its range.  _vcf_rest is the same text for the records whose CHROM starts

@@ -24,12 +24,15 @@
 // With POVU_HIP_T_OFFREF (INTEGRATION.md "Off-reference calls"; offref_kernels.hip) the sites called off-reference join `called`
 // behind callability, and from surrogate_offsets on the view's "reference paths" are the calling paths: the references and the
 // surrogates, ascending.  Which traversals of a kept site are records is asked of is_record_path (call_common.hpp).
+// With POVU_HIP_T_UNTANGLE (INTEGRATION.md "Untangled calls"; untangle_kernels.hip) one step behind the spelling rewrites the GT
+// rows and counts of the sites a path laps; without the flag it is not run and nothing of it is allocated.
 #include "call_common.hpp"
 #include "merge_kernels.hpp"
 #include "nest_kernels.hpp"
 #include "norm_kernels.hpp"
 #include "offref_kernels.hpp"
 #include "prim_kernels.hpp"
+#include "untangle_kernels.hpp"
 
 namespace povu_hip
 {
@@ -507,6 +510,10 @@ struct CallsOwner {
 	PinnedVec<uint32_t> host_query, host_allele;
 	std::vector<uint32_t> off_contig_path;
 	std::vector<uint64_t> off_contig_len;
+	// POVU_HIP_T_UNTANGLE
+	PinnedVec<uint8_t> rec_unt;
+	PinnedVec<uint32_t> lap, n_laps;
+	PinnedVec<uint16_t> lap_count;
 };
 
 using namespace povu_hip;
@@ -518,7 +525,7 @@ struct CallInputs {
 	const uint32_t *slot_of_path;
 	const povu_hip_trav_opts *opts;
 	uint32_t n, P, nR, S, NS, n_trees = 0;
-	bool inversions, nested, normalized, decomposed, merge, offref;
+	bool inversions, nested, normalized, decomposed, merge, offref, untangle;
 	uint32_t prim_cap = 0; // decomposed: the longest text that is aligned
 	povu_hip_call_profile_opts prof; // (raw-graph without a profile)
 	std::vector<uint32_t> ref_of_path, slot_first, qa, qz; // reference number of every path (NO_QUERY: none), first slot of every sample, the queries
@@ -610,6 +617,19 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 			throw HipError("POVU_HIP_T_OFFREF (off-reference calls) is refused together with POVU_HIP_T_MERGE");
 		if (in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
 			throw HipError(std::string("POVU_HIP_T_OFFREF (off-reference calls) is refused with profile ") + name[in.prof.profile] +
+				       ": only raw-graph");
+	}
+	in.untangle = opts && (opts->flags & POVU_HIP_T_UNTANGLE);
+	if (in.untangle) {
+		static const char *const name[] = {"raw-graph", "top-level-only", "popped", "left-normalized", "decomposed"};
+		if (opts->flags & POVU_HIP_T_NESTED)
+			throw HipError("POVU_HIP_T_UNTANGLE (untangled calls) is refused together with POVU_HIP_T_NESTED");
+		if (opts->flags & POVU_HIP_T_MERGE)
+			throw HipError("POVU_HIP_T_UNTANGLE (untangled calls) is refused together with POVU_HIP_T_MERGE");
+		if (opts->flags & POVU_HIP_T_OFFREF)
+			throw HipError("POVU_HIP_T_UNTANGLE (untangled calls) is refused together with POVU_HIP_T_OFFREF");
+		if (in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
+			throw HipError(std::string("POVU_HIP_T_UNTANGLE (untangled calls) is refused with profile ") + name[in.prof.profile] +
 				       ": only raw-graph");
 	}
 	in.normalized = in.prof.profile == POVU_HIP_PROFILE_LEFT_NORMALIZED; // (keeps every record, ignores the limits, implies nothing)
@@ -1064,6 +1084,16 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const Ca
 		throw HipError("segment " + std::to_string(read_back(ctx->g.vid + hbad, s)) + " holds a byte that is no nucleotide code (ACGTN, lower case, IUPAC)");
 }
 
+// POVU_HIP_T_UNTANGLE: the rows of the sites a path laps, rewritten from the lap alignments
+UntangleRows untangle_step(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, const CallRecs &r, const CallSpelled &sp)
+{
+	UntangleIn u{};
+	u.v = w.v, u.slots = w.slots, u.qidx = w.qidx, u.nQ = w.nQ;
+	u.nfl = w.nfl, u.nrec = r.nrec, u.perm = w.perm, u.dst = inv.f_dst;
+	u.rows = r.rows, u.smin = w.smin, u.smax = w.smax, u.ac_off = r.ac_off, u.ac = sp.ac;
+	return untangle_rows(ctx, u);
+}
+
 // what the `decomposed` profile reads: every (REF, ALT) of the records as they are written (prim_kernels.hip aligns and splits
 // them, merge_kernels.hip merges the rows)
 PrimIn primitive_input(const CallInputs &in, const CallWs &w, const CallRecs &r, const CallSpelled &sp)
@@ -1082,7 +1112,7 @@ PrimIn primitive_input(const CallInputs &in, const CallWs &w, const CallRecs &r,
 }
 
 povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const CallInv &inv, const CallRecs &r, const CallSpelled &sp,
-			      const PrimRows &pr, const MergedRows &mg, const CallOffref &orf, CallTimer &timer)
+			      const PrimRows &pr, const MergedRows &mg, const CallOffref &orf, const UntangleRows &un, CallTimer &timer)
 {
 	const uint32_t nrec = r.nrec, nb = r.L.nb, nR = in.nR, S = in.S;
 	const uint64_t nsp = r.L.nsp;
@@ -1165,6 +1195,15 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 		v.offref = 1;
 		v.n_offref_sites = w.os.n_sites, v.n_offref_records = orf.rows.n_records, v.n_offref_hosted = orf.rows.n_hosted;
 	}
+	if (in.untangle) { // (without the flag: the arrays NULL, the counts 0)
+		give(o->rec_unt, v.rec_unt, un.rec_unt, nrec);
+		give(o->lap, v.lap, un.lap, nrec);
+		give(o->n_laps, v.n_laps, un.n_laps, nrec);
+		give(o->lap_count, v.lap_count, un.lap_count, (size_t)nrec * S);
+		v.untangled = 1;
+		v.n_unt_tasks = un.n_tasks, v.n_unt_records = un.n_records, v.n_unt_missing = un.n_missing, v.n_unt_extra = un.n_extra;
+		v.n_unt_fallback = un.n_fallback;
+	}
 	v.device_ms = timer.stop(ctx->stream);
 	for (const auto &fill : defaults)
 		fill();
@@ -1233,10 +1272,11 @@ extern "C" povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_h
 		CallOffref orf;
 		if (in.offref)
 			offref_rows_step(ctx, in, w, inv, r, orf);
+		const UntangleRows un = in.untangle ? untangle_step(ctx, in, w, inv, r, sp) : UntangleRows{};
 		const PrimIn pin = in.decomposed ? primitive_input(in, w, r, sp) : PrimIn{};
 		const PrimRows pr = in.decomposed ? prim_rows(ctx, pin) : PrimRows{};
 		const MergedRows mg = in.merge ? merge_rows(ctx, pin, pr) : MergedRows{};
-		return calls_to_host(ctx, in, w, inv, r, sp, pr, mg, orf, timer);
+		return calls_to_host(ctx, in, w, inv, r, sp, pr, mg, orf, un, timer);
 	});
 }
 

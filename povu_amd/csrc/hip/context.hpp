@@ -324,6 +324,9 @@ struct povu_hip_ctx {
 	// povu_hip_call with POVU_HIP_T_OFFREF (offref_kernels.hip): the sites' surrogates and the calling paths / the view of the
 	// calling paths / the inversion records' numbers among them / the host index and offers / the rows' arrays
 	Arena or_ws, or_view, or_inv, or_host, or_rows;
+	// povu_hip_call with POVU_HIP_T_UNTANGLE (untangle_kernels.hip): the lap runs and the slots' cells / the entries and the
+	// task list / the tasks' row counts and offsets / the partner table / the rows' arrays
+	Arena un_ws, un_task, un_part, un_pair, un_rows;
 	// povu_hip_vcf_check (vcfcheck_kernels.hip): the step index, the uploaded walks, texts and tasks and the results / the
 	// table of (allele, slot) hits
 	Arena vc_ws, vc_hit;

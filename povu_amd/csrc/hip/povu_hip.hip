@@ -198,6 +198,11 @@ extern "C" int povu_hip_release_workspace(povu_hip_ctx *ctx)
 	ctx->iv_heads.release();
 	ctx->iv_rows.release();
 	ctx->nm_ws.release();
+	ctx->un_ws.release();
+	ctx->un_task.release();
+	ctx->un_part.release();
+	ctx->un_pair.release();
+	ctx->un_rows.release();
 	return 0;
 }
 

@@ -31,6 +31,7 @@ struct CallArgs {
 	bool nested = false;	 // --nested, or implied by a profile (INTEGRATION.md "Nested calls")
 	bool merge = false;	 // --merge-primitives, with --profile decomposed alone (INTEGRATION.md "Merged primitives")
 	bool offref = false;	 // --off-reference: sites no reference path crosses, on a surrogate path (INTEGRATION.md "Off-reference calls")
+	bool untangle = false;	 // --untangle: per-copy genotypes where a path laps a site (INTEGRATION.md "Untangled calls")
 	povu_hip_call_profile_opts prof{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 };
 
@@ -82,6 +83,8 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			c.merge = true;
 		} else if (x == "--off-reference") {
 			c.offref = true;
+		} else if (x == "--untangle") {
+			c.untangle = true;
 		} else if (x == "--profile" || !x.compare(0, 10, "--profile=")) {
 			const std::string v = x == "--profile" ? need(i) : x.substr(10);
 			if (v == "raw-graph")
@@ -125,6 +128,14 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 		throw std::runtime_error("Flag '--off-reference' cannot be combined with --merge-primitives");
 	if (c.offref && c.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
 		throw std::runtime_error("Flag '--off-reference' is called under --profile raw-graph alone");
+	if (c.untangle && c.nested)
+		throw std::runtime_error("Flag '--untangle' cannot be combined with --nested");
+	if (c.untangle && c.merge)
+		throw std::runtime_error("Flag '--untangle' cannot be combined with --merge-primitives");
+	if (c.untangle && c.offref)
+		throw std::runtime_error("Flag '--untangle' cannot be combined with --off-reference");
+	if (c.untangle && c.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
+		throw std::runtime_error("Flag '--untangle' is called under --profile raw-graph alone");
 	forms = (int)by_p + (int)!ref_file.empty() + (int)by_pos;
 	if (forms != 1)
 		throw std::runtime_error("call needs exactly one of the reference options: -r <file>, -P <prefix> (repeatable), or "
@@ -227,7 +238,7 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 	if (povu_hip_segments_upload(ctx, V, seq_off.data(), seq.data(), err, sizeof err) != 0)
 		fail("sequences");
 	const povu_hip_trav_opts opts{0, (ca.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (ca.nested ? POVU_HIP_T_NESTED : 0u) | (ca.merge ? POVU_HIP_T_MERGE : 0u) |
-						 (ca.offref ? POVU_HIP_T_OFFREF : 0u)};
+						 (ca.offref ? POVU_HIP_T_OFFREF : 0u) | (ca.untangle ? POVU_HIP_T_UNTANGLE : 0u)};
 	povu_hip_calls *c = povu_hip_call_profile(ctx, sites, &nm->refs, nm->slot_of_path, &opts, &ca.prof, err, sizeof err);
 	if (!c)
 		fail("call");

@@ -3,7 +3,7 @@
 //   povu [--version] [-v <int>] [-t <int>] decompose -i <gfa> [-o <dir>] [-h|--hairpins] [-s|--subflubbles]
 //   povu ... decompose ... --structure-export <json>   (additive: writes the flubble debug sidecar gfa2vcf writes)
 //   povu ... gfa2vcf -i <gfa> [-h] [-s] [--structure-export <json>] <options of `call`>   (app/cli/cli.cpp:154-193)
-//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--profile <p>] [--merge-primitives] [--off-reference]   (the
+//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--profile <p>] [--merge-primitives] [--off-reference] [--untangle]   (the
 //   variant calls of INTEGRATION.md "Variant calls" and "Inversion calls", on the GPU)
 //   povu ... vcf -i <gfa> -c <vcf> --report -o <dir> [--spelling] [--forward-only]   (the --report half of the reference's `vcf`,
 //   app/cli/cli.cpp; INTEGRATION.md "VCF checks", on the GPU)
@@ -79,6 +79,9 @@ static void usage(std::ostream &os)
 	      "        --off-reference                   raw-graph only: also call the sites no reference path crosses, on the first path\n"
 	      "                                          that traverses them (INTEGRATION.md \"Off-reference calls\"); with -o the records\n"
 	      "                                          no prefix takes go to <output_dir>/off-reference.vcf [default: false]\n"
+	      "        --untangle                        raw-graph only: where a haplotype walks a site more than once, align its laps with\n"
+	      "                                          the reference's and genotype every copy on its own: LN, LC and GT:CN\n"
+	      "                                          (INTEGRATION.md \"Untangled calls\") [default: false]\n"
 	      "        --max-level=[n]                   popped: the deepest level kept without rescue [default: 0]\n"
 	      "        --max-ref-length=[n], --max-allele-length=[n]\n"
 	      "                                          popped: a record with a longer REF / allele is big (0: no limit) [default: 0]\n"

@@ -283,6 +283,12 @@ const char OFFREF_LINES[] =
 	"its path\">\n"
 	"##INFO=<ID=HA,Number=1,Type=Integer,Description=\"Allele of the record's path in HOST, numbered in traversal order\">\n";
 
+// the lines of "Untangled calls", behind those of a call made with POVU_HIP_T_UNTANGLE
+const char UNTANGLE_LINES[] =
+	"##INFO=<ID=LN,Number=1,Type=Integer,Description=\"Lap of the reference path through the site this record is, from 1\">\n"
+	"##INFO=<ID=LC,Number=1,Type=Integer,Description=\"Laps of the reference path through the site\">\n"
+	"##FORMAT=<ID=CN,Number=.,Type=Integer,Description=\"Laps of the sample's haplotypes through the site\">\n";
+
 char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names, const char *const *path_name,
 		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len,
 		const char *const *rest_prefix, uint32_t n_rest, bool rest)
@@ -309,6 +315,10 @@ try {
 	const bool offref = nested_fields && (c->rec_offref || c->offref);
 	if (offref && ((c->n_records && (!c->rec_offref || !c->host_query || !c->host_allele)) ||
 		       (c->n_off_contigs && (!c->off_contig_path || !c->off_contig_len))))
+		return nullptr;
+	// the arrays of "Untangled calls" (absent: the text of the call without the flag; `untangled` speaks for a call without a record)
+	const bool untangled = nested_fields && (c->rec_unt || c->untangled);
+	if (untangled && c->n_records && (!c->rec_unt || !c->lap || !c->n_laps || !c->lap_count))
 		return nullptr;
 	if (merged && (!c->mrow_member || !c->mrow_gt || !c->mrow_ac || !c->mrow_an || !c->mrow_ns))
 		return nullptr;
@@ -364,7 +374,7 @@ try {
 		date = today;
 	}
 	// ---- header, a contig line per reference path of the prefix, the column line
-	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile] + (merged_lines ? MERGE_LINES : "") + (offref ? OFFREF_LINES : "");
+	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile] + (merged_lines ? MERGE_LINES : "") + (offref ? OFFREF_LINES : "") + (untangled ? UNTANGLE_LINES : "");
 	// the paths whose lines and records are written: those of the prefix (every one without), or with `rest` of no prefix
 	auto takes = [&](const char *name) {
 		if (!rest)
@@ -581,6 +591,8 @@ try {
 					if (c->host_query[i] != POVU_HIP_NIL)
 						o += ";HOST=" + site_label(c->host_query[i]) + ";HA=" + std::to_string(c->host_allele[i]);
 				}
+				if (untangled && c->rec_unt[i])
+					o += ";LN=" + std::to_string(c->lap[i]) + ";LC=" + std::to_string(c->n_laps[i]);
 				if (norm) {
 					o += ";ORIGIN=" + label + ";RAW_ALT_INDEX=";
 					for (size_t k = 1; k < order.size(); k++)
@@ -599,7 +611,10 @@ try {
 						o += std::string(";PROFILE=") + PROFILE_NAME[profile] + ";PASSTHROUGH=T";
 				}
 			}
-			o += "\tGT";
+			// an untangled record: every sample column is <GT>:<CN>, CN the laps of the sample's slots ('.' for none)
+			const bool with_cn = untangled && !subr && c->rec_unt[i];
+			const uint16_t *laps = with_cn ? c->lap_count + i * S : nullptr;
+			o += with_cn ? "\tGT:CN" : "\tGT";
 			const uint16_t *row = c->gt + i * S;
 			const uint8_t *mgt = merged ? c->mrow_gt + mrow * S : nullptr;
 			auto allele = [&](uint32_t sl) -> uint32_t { return !mgt ? row[sl] : mgt[sl] <= 1 ? mgt[sl] : POVU_HIP_GT_MISSING; };
@@ -608,14 +623,16 @@ try {
 				bool any = false;
 				for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++)
 					any |= allele(sl) != POVU_HIP_GT_MISSING;
-				if (!any) {
+				if (!any)
 					o += '.';
-					continue;
-				}
-				for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++) {
+				for (uint32_t sl = slot_first[sm]; any && sl < slot_first[sm + 1]; sl++) {
 					if (sl > slot_first[sm])
 						o += '|';
 					o += allele(sl) == POVU_HIP_GT_MISSING ? "." : std::to_string(allele(sl));
+				}
+				for (uint32_t sl = slot_first[sm]; with_cn && sl < slot_first[sm + 1]; sl++) {
+					o += sl > slot_first[sm] ? ',' : ':';
+					o += laps[sl] ? std::to_string(laps[sl]) : ".";
 				}
 			}
 			o += '\n';

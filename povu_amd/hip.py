@@ -132,6 +132,7 @@ class _VcfReport(C.Structure):
 
 
 OFFREF_COUNTERS = ("n_offref_sites", "n_offref_records", "n_offref_hosted")  # of Calls
+UNTANGLE_COUNTERS = ("n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback")  # of Calls
 MERGE_COUNTERS = ("n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts")  # of Calls, beside n_mrows
 
 
@@ -172,7 +173,11 @@ class _CallsNested(_Calls):
                 [("offref", C.c_uint64), ("rec_offref", C.POINTER(C.c_uint8)), ("host_query", C.POINTER(C.c_uint32)),
                  ("host_allele", C.POINTER(C.c_uint32)), ("n_off_contigs", C.c_uint64), ("off_contig_path", C.POINTER(C.c_uint32)),
                  ("off_contig_len", C.POINTER(C.c_uint64))] +
-                [(k, C.c_uint64) for k in OFFREF_COUNTERS])
+                [(k, C.c_uint64) for k in OFFREF_COUNTERS] +
+                # "Untangled calls"
+                [("untangled", C.c_uint64), ("rec_unt", C.POINTER(C.c_uint8)), ("lap", C.POINTER(C.c_uint32)),
+                 ("n_laps", C.POINTER(C.c_uint32)), ("lap_count", C.POINTER(C.c_uint16))] +
+                [(k, C.c_uint64) for k in UNTANGLE_COUNTERS])
 
 
 class _ProfileOpts(C.Structure):
@@ -210,6 +215,9 @@ T_MERGE = 8
 # HipDecomposer.call under profile "raw-graph" only, not with T_NESTED or T_MERGE: the sites no reference path crosses, called
 # on the first path that traverses them (INTEGRATION.md "Off-reference calls")
 T_OFFREF = 16
+# HipDecomposer.call under profile "raw-graph" only, not with T_NESTED, T_MERGE or T_OFFREF: where a path walks a site more than
+# once its laps are aligned with the reference's and every copy is genotyped on its own (INTEGRATION.md "Untangled calls")
+T_UNTANGLE = 32
 TRAV_LONG, TRAV_STRAY, TRAV_OPEN = 1, 2, 4  # status bits of a query
 PROFILES = {"raw-graph": 0, "top-level-only": 1, "popped": 2, "left-normalized": 3, "decomposed": 4}  # HipDecomposer.call(profile=...)
 PRIM_MAX_LENGTH = 512  # `decomposed` profile: the longest allele that is aligned, and the most max_allele_length may ask for
@@ -240,6 +248,8 @@ def load_lib():
     l.povu_hip_create.restype = C.c_void_p
     l.povu_hip_create.argtypes = [C.c_int, C.c_char_p, C.c_size_t]
     l.povu_hip_destroy.argtypes = [C.c_void_p]
+    l.povu_hip_release_workspace.restype = C.c_int
+    l.povu_hip_release_workspace.argtypes = [C.c_void_p]
     l.povu_hip_graph_upload.restype = C.c_int
     l.povu_hip_graph_upload.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
@@ -913,6 +923,16 @@ class Calls:
         self.off_contig_len = _view(c.off_contig_len, int(c.n_off_contigs), np.uint64)
         for k in OFFREF_COUNTERS:
             setattr(self, k, int(getattr(c, k)))
+        # "Untangled calls" (T_UNTANGLE): per record whether it is untangled, the reference's lap it is (from 1) and the
+        # reference's laps; per (record, slot) the laps of the slot's paths; the counters.  Without the flag: empty, 0
+        self.untangled = bool(c.untangled)
+        k = n if self.untangled else 0
+        self.rec_unt = _view(c.rec_unt, k, np.uint8)
+        self.lap = _view(c.lap, k, np.uint32)
+        self.n_laps = _view(c.n_laps, k, np.uint32)
+        self.lap_count = _view(c.lap_count, k * self.n_slots, np.uint16).reshape(k, self.n_slots)
+        for k in UNTANGLE_COUNTERS:
+            setattr(self, k, int(getattr(c, k)))
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -1064,6 +1084,12 @@ class HipDecomposer:
 
     def __del__(self):
         self.close()
+
+    def release_workspace(self) -> None:
+        """Gives the stage, query and call workspaces back to the device (povu_hip_release_workspace); the resident graph, paths
+        and sequences stay, and the next call allocates what it needs again."""
+        if self._lib.povu_hip_release_workspace(self._ctx) != 0:
+            raise RuntimeError("no context")
 
     def upload(self, links, tips=None):
         """links: povu_amd.workloads.Links (vertex idx based link arrays)."""
@@ -1242,7 +1268,10 @@ class HipDecomposer:
         profile refuses, equal primitives are merged: Calls.merged, n_mrows, mrow_*, the counters, and vcf_text writes the merged
         rows).  T_OFFREF ("Off-reference calls", raw-graph alone, refused with T_NESTED and T_MERGE): the sites no reference path
         crosses are called on their surrogate path; Calls.offref, rec_offref, host_query, host_allele, off_contig_*, the
-        counters."""
+        counters.  T_UNTANGLE ("Untangled calls", raw-graph alone, refused with T_NESTED, T_MERGE and T_OFFREF): where a path
+        walks a site more than once its laps are aligned with the reference's and every record takes the allele of the lap
+        aligned with its own; Calls.untangled, rec_unt, lap, n_laps, lap_count, the UNTANGLE_COUNTERS, and vcf_text writes
+        LN, LC and GT:CN."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names

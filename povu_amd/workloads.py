@@ -887,3 +887,42 @@ def complex_haplotypes(n_units: int, seed: int, n: int) -> Paths:
         ids.append(last)
         pieces.append((ids, [0] * len(ids)))
     return _paths([f"hap{h}#1#chr1" for h in range(n)], pieces)
+
+
+_VNTR_UNIT = 5  # segments a loop site: flank, entry, two units, exit
+_VNTR_LINKS = [(0, 1), (1, 2), (1, 3), (2, 4), (3, 4), (4, 1), (4, 5)]
+
+
+def vntr_haplotypes(n_sites: int, n_haps: int, max_copies: int, seed: int, reverse_every: int = 0):
+    """Tandem repeats as a graph keeps them ("Untangled calls"): (Links, Paths) of a chain of `n_sites` loop sites and `n_haps`
+    haplotypes through it.  Site i has a flank f = 5 i + 1, an entry a = f + 1, the units x = f + 2 and y = f + 3 and an exit
+    z = f + 4, with links f>a a>x a>y x>z y>z z>a (the loop) and z > the next flank; a last flank closes the chain.  A
+    haplotype walks every site 1 .. `max_copies` times, each copy through a unit chosen at random; every `reverse_every`-th
+    haplotype is written walking the chain backwards ('<' steps from the last flank to the first).  PanSN names, one sample a
+    haplotype (`hap<k>#1#chr1`); haplotype 0, the reference, walks forwards.  Vectorised over the laps of a haplotype."""
+    size = _VNTR_UNIT
+    base = size * np.arange(n_sites, dtype=np.int64)[:, None]
+    la = np.array(_VNTR_LINKS, dtype=np.int64)
+    links = from_plus_links(np.arange(1, size * n_sites + 2, dtype=np.uint32), (base + la[:, 0][None, :]).reshape(-1),
+                            (base + la[:, 1][None, :]).reshape(-1))
+    rng = np.random.default_rng(seed)
+    pieces = []
+    for h in range(n_haps):
+        copies = rng.integers(1, max_copies + 1, size=n_sites)
+        units = rng.integers(0, 2, size=int(copies.sum()))
+        site = np.repeat(np.arange(n_sites, dtype=np.int64), copies)  # of every lap
+        start = np.zeros(n_sites + 1, dtype=np.int64)  # first step of every site: its flank, then three steps a lap
+        np.cumsum(1 + 3 * copies, out=start[1:])
+        first_lap = np.cumsum(copies) - copies
+        at = start[site] + 1 + 3 * (np.arange(site.size, dtype=np.int64) - first_lap[site])
+        w = np.empty(int(start[-1]) + 1, dtype=np.uint32)
+        w[start[:-1]] = size * np.arange(n_sites, dtype=np.int64) + 1
+        w[at] = size * site + 2
+        w[at + 1] = size * site + 3 + units
+        w[at + 2] = size * site + 5
+        w[-1] = size * n_sites + 1
+        if reverse_every and h and h % reverse_every == reverse_every - 1:
+            pieces.append((w[::-1].copy(), np.ones(w.size, dtype=np.uint8)))
+        else:
+            pieces.append((w, np.zeros(w.size, dtype=np.uint8)))
+    return links, _paths([f"hap{h}#1#chr1" for h in range(n_haps)], pieces)

@@ -1,4 +1,4 @@
-"""Device time of povu_hip_call (HipDecomposer.call) in its modes on one of six inputs, each at the size it has always been
+"""Device time of povu_hip_call (HipDecomposer.call) in its modes on one of seven inputs, each at the size it has always been
 timed at:
 
     chain     the chain of bubbles with 32 closed-form haplotypes, a quarter written reversed (workloads.chain_haplotypes),
@@ -12,12 +12,15 @@ timed at:
               "Decomposed calls"); 100000 units
     insertions workloads.insertion_units / insertion_haplotypes with 64 haplotypes (a SNP inside an insertion the reference does
               not have, INTEGRATION.md "Off-reference calls"); 125000 units, 1e6 segments
+    looped    workloads.vntr_haplotypes with 32 haplotypes of 1 .. 6 laps a site, every fourth walking backwards (loop sites,
+              INTEGRATION.md "Untangled calls"); 100000 sites, 5e5 segments
 
 and in any of the modes plain, inversions (T_INVERSIONS), nested (T_NESTED), popped (profile `popped`, max_level 0, both length
 limits --max-length), normalized (profile `left-normalized`), decomposed (profile `decomposed`), merged (the same with T_MERGE:
 equal primitives merged; its time less that of decomposed is the merging step's) and decomposed-tier2 (decomposed with
 T_FORCE_TIER2: every aligned pair through the striped kernel, for the cells per second of that tier; asked for by name
-only) and offref (T_OFFREF: the sites no reference path crosses too; its time less that of plain is the step's); without --modes those the input was made for.  One JSON line
+only), offref (T_OFFREF: the sites no reference path crosses too; its time less that of plain is the step's) and untangled
+(T_UNTANGLE: the laps of every haplotype aligned with the reference's; its time less that of plain is the step's); without --modes those the input was made for.  One JSON line
 per mode and run: HIP-event time of the call (query upload to the last byte on the host), records, spelled bytes, the
 counters of the mode; then per mode a line with the median of the runs behind the warm-up runs.
 
@@ -25,7 +28,7 @@ Every mode runs in a child process of its own under its own time limit, one afte
 runs out of time nothing more is started.  --package-root times the library of another checkout on this tree's inputs (only
 keyword arguments of HipDecomposer.call that every build with the mode has are used).
 
-    python tools/time_calls.py --workload chain|inverted|skip|tandem|complex|insertions [--modes plain,nested] [--size 1.0] [--warmup 2] [--runs 7]
+    python tools/time_calls.py --workload chain|inverted|skip|tandem|complex|insertions|looped [--modes plain,nested] [--size 1.0] [--warmup 2] [--runs 7]
                                [--max-length 64] [--limit 300] [--package-root <another checkout>]
 """
 import argparse
@@ -39,9 +42,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2", "offref")
+MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2", "offref", "untangled")
 DEFAULT_MODES = dict(chain=("plain",), inverted=("plain", "inversions"), skip=("plain", "nested", "popped"), tandem=("plain", "normalized"),
-                     complex=("plain", "decomposed", "merged"), insertions=("plain", "offref"))
+                     complex=("plain", "decomposed", "merged"), insertions=("plain", "offref"), looped=("plain", "untangled"))
 
 
 def _load(package_root):
@@ -79,6 +82,10 @@ def workload(W, name, size):
         units = max(2, int(125000 * size))
         g = W.insertion_units(units)
         return g, W.insertion_haplotypes(units, 64, seed=1), W.random_sequences(g, 5, max_len=16), "hap0#"
+    if name == "looped":
+        sites = max(2, int(100000 * size))
+        g, p = W.vntr_haplotypes(sites, 32, 6, 1, reverse_every=4)
+        return g, p, W.random_sequences(g, 5, max_len=16), "hap0#"
     if name == "complex":
         units = max(2, int(100000 * size))
         g, seqs = W.complex_alleles(units, 1)
@@ -101,11 +108,12 @@ def child(a):
     kw = dict(plain=lambda: {}, inversions=lambda: dict(flags=H.T_INVERSIONS), nested=lambda: dict(flags=H.T_NESTED),
               popped=lambda: dict(profile="popped", max_level=0, max_ref_length=a.max_length, max_allele_length=a.max_length),
               normalized=lambda: dict(profile="left-normalized"), decomposed=lambda: dict(profile="decomposed"),
-              merged=lambda: dict(profile="decomposed", flags=H.T_MERGE), offref=lambda: dict(flags=H.T_OFFREF),
+              merged=lambda: dict(profile="decomposed", flags=H.T_MERGE), offref=lambda: dict(flags=H.T_OFFREF), untangled=lambda: dict(flags=H.T_UNTANGLE),
               **{"decomposed-tier2": lambda: dict(profile="decomposed", flags=H.T_FORCE_TIER2)})[a.child]()
     counters = ("n_inv_records", "n_inv_tier2", "n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "n_normalized", "max_shift",
                 "n_norm_compared", "n_rows", "n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells", "n_mrows",
-                "n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts", "n_offref_sites", "n_offref_records", "n_offref_hosted")
+                "n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts", "n_offref_sites", "n_offref_records", "n_offref_hosted",
+                "n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback")
     for run in range(a.warmup + a.runs):
         t0 = time.perf_counter()
         c = d.call(f, [ref], **kw)
