@@ -936,12 +936,12 @@ int povu_hip_debug_bitrank(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, co
 int povu_hip_debug_append(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, uint32_t *list, uint32_t *count);
 /* unit-test hook for the list ranking of the tree stage: suffix sums (inclusive, mod 2^32) along the lists next[0..n)
  * (NIL = end of a list; heads[0..nh) = their first elements, NIL entries allowed) -- mode 0: ra of the 0/1 weights w;
- * mode 1: the pre-order events' two sums (element x enters when x % 3 == 0, see tree_kernels.hip), ra and rb.  bits =
+ * mode 1: the pre-order events' two sums (element x enters when x % 3 == 0, see list_rank.hip), ra and rb.  bits =
  * splitter bucket bits, 2..6 (0: the default).  Elements in no list get no defined value.  0 = ok, 1 = bad arguments,
  * 2 = device error. */
 int povu_hip_debug_list_rank(povu_hip_ctx *ctx, uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads,
 			     uint32_t nh, int mode, uint32_t bits, uint32_t *ra, uint32_t *rb);
-/* What the level-0 walk of a list ranking left in its records (tree_kernels.hip: a record is one narrow word -- the owner as
+/* What the level-0 walk of a list ranking left in its records (list_rank.hpp: a record is one narrow word -- the owner as
  * a signed delta to its bucket, the partial sums in small fields -- or, where a field does not fit, an escaped pair of words).
  * Counted by a kernel of its own that walks the lists again behind the ranking.  hist[33 * d + p] = live elements whose
  * owner delta needs d bits (zigzag: 2|v| or 2|v| - 1) and whose partial sums need p bits (the events: the wider of the two),

@@ -1,6 +1,7 @@
 // debug_hooks.hip -- the C ABI's unit-test and parity hooks (include/povu_hip.h, povu_hip_debug_*): the device-wide
 // primitives and look-up structures called directly, and the state of the last pass stage by stage.  Not the library.
 #include "context.hpp"
+#include "list_rank.hpp"
 #include "segtree.hpp"
 
 #include <algorithm>
@@ -445,7 +446,7 @@ extern "C" int povu_hip_debug_append(povu_hip_ctx *ctx, const uint8_t *flags, si
 	}
 }
 
-// ---- unit-test hook for the list ranking of the tree stage (tree_kernels.hip, debug_list_rank)
+// ---- unit-test hook for the list ranking (list_rank.hip, debug_list_rank)
 extern "C" int povu_hip_debug_list_rank(povu_hip_ctx *ctx, uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads,
 					uint32_t nh, int mode, uint32_t bits, uint32_t *ra, uint32_t *rb)
 {
@@ -461,7 +462,7 @@ extern "C" int povu_hip_debug_list_rank(povu_hip_ctx *ctx, uint32_t n, const uin
 	}
 }
 
-// ---- what the level-0 walks left in their records (tree_kernels.hip, k_rank_rec_stats): read-only, no launch.  The numbers
+// ---- what the level-0 walks left in their records (list_rank.hip, k_rank_rec_stats): read-only, no launch.  The numbers
 // were counted by a kernel of its own behind the ranking -- in a pass only when POVU_HIP_RANK_STATS was set while it ran
 extern "C" int povu_hip_debug_rank_escapes(povu_hip_ctx *ctx, int which, povu_hip_rank_records *out, uint8_t *esc, size_t n_esc)
 {
@@ -484,7 +485,7 @@ extern "C" int povu_hip_debug_rank_escapes(povu_hip_ctx *ctx, int which, povu_hi
 	std::copy(st.hist, st.hist + 33 * 33, out->hist);
 	if (esc)
 		for (size_t x = 0; x < n_esc; x++)
-			esc[x] = st.fin ? 1 : (uint8_t)(ctx->dbg_rank_plane0[x] >> 31);
+			esc[x] = st.fin ? 1 : (uint8_t)((ctx->dbg_rank_plane0[x] & REC_ESC) != 0);
 	return 0;
 }
 

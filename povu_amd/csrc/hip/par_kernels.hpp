@@ -43,7 +43,7 @@ enum PassWord : uint32_t {
 	PW_N_BRIDGE = 10,    // k_hi_simp: bridge vertices listed -> k_capping
 	PW_N_X = 11,	     // compact_flagged_u8: stack entries with a crossed interval -> k_resolve_crossings, povu_hip_last_crossings
 	PW_N_CROSSED = 12,   // k_resolve_crossings: crossings resolved in place -> povu_hip_last_crossings
-	PW_RANK_OVF = 13,    // list_rank_splitters (the pre-order ranking): records whose partial sum left its 16 bits (its fallback kernel)
+	PW_RANK_OVF = 13,    // rank_events (list_rank.hip, the pre-order ranking): records whose partial sum left its 16 bits (its fallback kernel)
 	PW_INCNT_OVF = 14,   // k_bracket_extra: a byte of incnt8 would have passed 255 -> the host (place_brackets: the pass is repeated with words)
 	PASS_WORDS = 16	     // words carved and cleared (1, 3, 15: unused)
 };

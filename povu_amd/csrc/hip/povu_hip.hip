@@ -780,7 +780,7 @@ static bool carve_stages(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, u
 		return false;
 	if (ctx->tail_pending) // first write into the stage workspace: behind the tail of the pass before
 		HIP_CHECK(hipStreamWaitEvent(ctx->stream, ctx->tail_done, 0));
-	tree_tour_words(ctx->cs, (uint32_t)z.V, (uint32_t)z.E, tw, p.sparse_splitters, ctx->stream);
+	tree_tour_words(ctx->cs, (uint32_t)z.V, (uint32_t)z.E, tw, ctx->stream);
 	return ctx->tail_pending;
 }
 

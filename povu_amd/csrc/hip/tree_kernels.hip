@@ -7,7 +7,7 @@
 // the DFS can enter a 2-edge-connected class only through the unique bridge that leads to the root,
 // and its walk inside a class never depends on the rest of the graph.  So
 //   1. spanning forest of H  (black edges + the links that won a hook in the WCC union-find)
-//   2. root it at the DFS start side: Euler tour over the forest of segments + list ranking (random splitters, recursive)
+//   2. root it at the DFS start side: Euler tour over the forest of segments + list ranking (list_rank.hpp: random splitters, recursive)
 //   3. bridges: a tree edge is a bridge iff the xor of TWO independent hashes of the non-tree links over its subtree's
 //      stretch of the tour vanishes (running xor over the values in tour order, kept compact behind a bitmap of the
 //      positions that carry one)
@@ -41,39 +41,6 @@ namespace povu_hip
 #ifndef NIL
 #define NIL POVU_NIL
 #endif
-
-// ---- list-ranking words and splitters (section "work-efficient list ranking" below).
-// Splitters cut every list into short segments.  The index space of a list level is cut into buckets of 2^b
-// consecutive elements and every bucket names exactly ONE of its elements as a splitter, pseudo-randomly
-// (multiplicative hash of the bucket idx).  So the splitter of bucket q is computed, not looked up; a splitter's id on
-// the next level IS its bucket idx (dense, no flag array, no scan, no compaction), and lane q of a walk kernel works
-// near element q * 2^b (the scattered rank stores of neighbouring lanes meet again in L2).
-// b = 3 (1 in 8): short segments, whose walks are bound by their longest one; b = 4 is kept as an A/B switch.
-static unsigned rank_bucket_bits(size_t n)
-{
-	if (const char *ev = getenv("POVU_HIP_RANK_BITS")) // (tuning hook)
-		return (unsigned)std::min(6, std::max(2, atoi(ev)));
-	(void)n;
-	return 3u; // (1 in 16 measured 0.2 ms slower on 2.4e8 slots once the other kernels had changed; POVU_HIP_F_SPARSE_SPLITTERS still forces it)
-}
-static constexpr uint32_t PK_END = 0x1FFFFFFFu, PK_STOP = 0x80000000u; // words of the levels above the list (their elements number an eighth of it)
-// words of the list itself (level 0): bits 0..29 successor (P0_END = none), bit 30 = the element's 0/1 weight, bit 31 = the
-// element heads a list.  Whether the walk stops behind an element -- its successor is a splitter, or there is none -- is
-// worked out from the successor (three integer operations), not stored: the bit it would take is the difference between
-// 1.8 * 10^8 and 3.6 * 10^8 segments a graph may have.
-static constexpr uint32_t P0_END = 0x3FFFFFFFu, P0_W = 0x40000000u, P0_HEAD = 0x80000000u;
-static constexpr uint32_t FT_NONE = 0x7FFFFFFFu, FT_HASH = 0x80000000u; // ft words: first arc of a side | "its hash word was written"
-__device__ __forceinline__ uint32_t bucket_splitter(uint32_t q, unsigned b) { return (q << b) | ((q * 0x9E3779B1u) >> (32u - b)); }
-__device__ __forceinline__ bool is_splitter(uint32_t i, unsigned b) { return bucket_splitter(i >> b, b) == i; }
-// One word per list element, so that a walk step is ONE dependent load: bits 0..28 successor (PK_END = none),
-// bit 29 = the element's 0/1 weight, bit 30 = the element heads a list (nobody's successor; set by the kernels that
-// know the heads), bit 31 = stop after this element (the successor is a splitter, or there is none).
-__device__ __forceinline__ uint32_t rank_pack(uint32_t nx, uint32_t w, unsigned b)
-{
-	(void)b;
-	return (nx == NIL ? P0_END : nx) | ((w & 1u) ? P0_W : 0u);
-}
-__device__ __forceinline__ bool rank_l0_stop(uint32_t nx, unsigned b) { return nx == P0_END || is_splitter(nx, b); }
 
 // ------------------------------------------------------------------ 1. Euler tour of the spanning forest
 // The forest = every black edge + the links that won a hook in the union-find over the segments.  A black edge never
@@ -144,8 +111,9 @@ __device__ __forceinline__ bool heq(const ulonglong2 a, const ulonglong2 b) { re
 // Also, while the side's links are in hand: hside[S] = xor of the hashes of its non-tree links (a link is in the lists
 // of both its ends, also when they are l and r of one segment), written only where it is not zero (four sides in five
 // of a pangenome graph have no such link); ft[S] = its first arc (FT_NONE: none), bit 31 set when hside[S] was written.
+static constexpr uint32_t FT_NONE = 0x7FFFFFFFu, FT_HASH = 0x80000000u; // ft words: first arc of a side | "its hash word was written"
 __global__ void k_tour_words(uint32_t nS, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
-			     const uint32_t *__restrict__ lle, uint32_t *__restrict__ pk, unsigned b,
+			     const uint32_t *__restrict__ lle, uint32_t *__restrict__ pk,
 			     ulonglong2 *__restrict__ hside, uint32_t *__restrict__ ft)
 {
 	uint32_t S = BIDX * blockDim.x + threadIdx.x;
@@ -232,7 +200,7 @@ __global__ void k_tour_words(uint32_t nS, const uint32_t *__restrict__ loff, con
 					if (lle[jj] & LLE_TREE)
 						nxt = jj;
 			}
-			pk[at] = rank_pack(nxt, 1u, b); // every arc counts 1 (k_tour_ends fixes the closing arc)
+			pk[at] = rank_pack(nxt, 1u); // every arc counts 1 (k_tour_ends fixes the closing arc)
 		}
 	}
 	const bool nz = !hzero(h);
@@ -276,585 +244,6 @@ __global__ void k_tour_ends(uint32_t C, const uint32_t *__restrict__ voff, const
 		return;
 	pk[arc_twin(loff, ladj, lle, a_last)] = P0_END; // no successor, weight 0
 	atomicOr(&pk[a_first], P0_HEAD);		 // (k_tour_words wrote the word in an earlier launch)
-}
-// one launch = several rounds of pointer jumping with two accumulators (suffix sums along the list):
-// HOPS = 3 covers two rounds (every pointer then spans 4x as far), HOPS = 7 three rounds (8x).  More
-// hops per launch mean fewer launches but more loads in total, which pays only while the launches are
-// dispatch-bound (short splitter lists).
-template <int HOPS>
-__global__ void k_wyllie(uint32_t n, const uint32_t *__restrict__ nxt_in, const uint32_t *__restrict__ a_in,
-			 const uint32_t *__restrict__ b_in, uint32_t *__restrict__ nxt_out, uint32_t *__restrict__ a_out,
-			 uint32_t *__restrict__ b_out, const uint32_t *__restrict__ n_dev)
-{
-	uint32_t i = BIDX * blockDim.x + threadIdx.x;
-	if (i >= n || (n_dev && i >= *n_dev))
-		return;
-	uint32_t nx = nxt_in[i], a = a_in[i], b = b_in ? b_in[i] : 0;
-#pragma unroll
-	for (int hop = 0; hop < HOPS; hop++) {
-		if (nx == NIL)
-			break;
-		a += a_in[nx];
-		if (b_in)
-			b += b_in[nx];
-		nx = nxt_in[nx];
-	}
-	nxt_out[i] = nx;
-	a_out[i] = a;
-	if (b_out)
-		b_out[i] = b;
-}
-// `bits` = bits_for(longest possible list); returns which buffer set (0 = A, 1 = B) holds the result
-static int list_rank(uint32_t n, unsigned bits, uint32_t *nxtA, uint32_t *nxtB, uint32_t *aA, uint32_t *aB, uint32_t *bA,
-		     uint32_t *bB, hipStream_t s, const uint32_t *n_dev = nullptr)
-{
-	int cur = 0;
-	const bool small = n < (1u << 21);
-	const unsigned launches = small ? (bits + 2) / 3 : (bits + 1) / 2;
-	for (unsigned r = 0; r < launches; r++) {
-		uint32_t *ni = cur ? nxtB : nxtA, *no = cur ? nxtA : nxtB, *ai = cur ? aB : aA, *ao = cur ? aA : aB;
-		uint32_t *bi = cur ? bB : bA, *bo = cur ? bA : bB;
-		if (small)
-			LAUNCH(k_wyllie<7>, n, s, n, ni, ai, bi, no, ao, bo, n_dev);
-		else
-			LAUNCH(k_wyllie<3>, n, s, n, ni, ai, bi, no, ao, bo, n_dev);
-		cur ^= 1;
-	}
-	return cur;
-}
-
-// ---- work-efficient list ranking, recursive.  Level 0 is the list itself (packed words, 0/1 weights).  One lane per
-// splitter (= per bucket, plus one per list head) walks its segment and leaves {next splitter, segment sums} -- the
-// element of the next level, whose index is the bucket idx.  Levels shrink by 2^b until one workgroup ranks the top in
-// LDS (pointer jumping); then every level above the list hands its elements their suffix sums on the way back down.
-// The list itself is walked once: its walk up leaves a record per element, from which the readers work out the rank
-// (see k_rank_up).  A list of n elements costs about n(1 + 2^-b + ...) dependent loads up and n 2^-b(1 + ...) down.
-// Heads: an element that heads a list is never reached through its bucket (its lane stays idle); head h of the caller's
-// head array is element m + h of every level above 0 (m = buckets of the level below) and is walked by its own lane.
-// TWO: second weight = +1 where the first is 1, -1 where it is 0 (enter / leave events).
-static constexpr uint32_t RANK_TOP = 8192; // elements one workgroup ranks in LDS
-struct RankLevelArgs {
-	uint32_t n;	// elements of this level
-	uint32_t m;	// buckets of this level = hash lanes of the walk
-	uint32_t hbase; // first head element of this level (level 0: unused, heads come from the array)
-	uint32_t M;	// lanes of the walk = elements of the next level = m + heads
-};
-// start element of lane `id`, NIL when the lane has nothing to walk
-template <bool L0>
-__device__ __forceinline__ uint32_t rank_lane_start(uint32_t id, const RankLevelArgs &A, unsigned b, const uint32_t *__restrict__ pk0,
-						    const uint32_t *__restrict__ heads)
-{
-	if (id < A.m) {
-		const uint32_t x = bucket_splitter(id, b);
-		if (x >= A.n)
-			return NIL;
-		if (L0)
-			return (pk0[x] & P0_HEAD) ? NIL : x;
-		return x >= A.hbase ? NIL : x;
-	}
-	return L0 ? heads[id - A.m] : A.hbase + (id - A.m);
-}
-// EVT3 (level 0 only, with TWO): the elements are the events of the pre-order ranking, three per segment, and an
-// element's two weights follow from its index: 3g = enter both sides of segment g (+2 entered, depth +2), 3g + 1 =
-// leave the far side (depth -1, or -2 when the weight bit says the entered side is left with it), 3g + 2 = leave the
-// entered side (depth -1).
-template <bool EVT3>
-__device__ __forceinline__ void rank_l0_weights(uint32_t x, uint32_t p, uint32_t &wa, uint32_t &wb)
-{
-	if (EVT3) {
-		const uint32_t t = x % 3u;
-		wa = t == 0 ? 2u : 0u;
-		wb = t == 0 ? 2u : ((t == 1 && (p & P0_W)) ? 0u - 2u : 0u - 1u);
-	} else {
-		wa = (p & P0_W) ? 1u : 0u;
-		wb = wa ? 1u : 0xFFFFFFFFu;
-	}
-}
-// Level 0 leaves a RECORD per element on the walk up, and no walk goes down it again: the lane's id (= the
-// element one level up whose rank the walks above hand out) and the sums from the splitter up to, not including, the
-// element.  Its rank is then R[owner] - partial (rank_l0 / rank_l0_pair), resolved by the kernels that read it -- one
-// store per element, where the way back stored the rank itself.  A record is {owner, partial}; with TWO the second word
-// holds partial(a) | (partial(a) - partial(b)) << 16 (both never negative, at most two per element), and a segment
-// whose sums outgrow 16 bits raises *ovf: k_rank_l0_fallback then walks the list once more and stores final ranks.
-//
-// The record array (n 8-byte slots) is used as two PLANES of n words, and nearly every record is one word of plane 0:
-// the owner of x is a lane near bucket x >> b wherever the ids run along the lists, and a partial is bounded by the
-// length of a splitter segment (geometric, mean 2^b).
-//   narrow   plane0[x] = signed(owner - (x >> b)) << 15 | partial(s)         (bit 31 clear; ONE store)
-//   escaped  plane0[x] = REC_ESC | owner,  plane1[x] = the second word        (delta or partial out of its field)
-//   final    plane0[x] = a,  plane1[x] = b                                    (k_rank_l0_fallback; R.fin says so)
-// The delta takes the 16 bits below REC_ESC in both rankings.  The tour: 15 bits of partial.  The events: 7 bits of
-// partial(a), then 7 of partial(a) - partial(b); bit 14 stays clear.  Widths from the distributions in
-// profiles/rank_records_summary.md: on graphs whose ids run along the lists no delta needs more than 16 bits but those of
-// the head-led segments of later components, and no partial more than 8; a wider delta would buy nothing there, and at 16
-// bits both edges of the field can be reached by lists of 2^18 elements (tests/test_gpu_rank_records.py).
-static constexpr uint32_t REC_MAX = 0xFFFFu;
-static constexpr uint32_t REC_ESC = 0x80000000u;
-static constexpr unsigned REC_T_PBITS = 15, REC_T_DBITS = 16;
-static constexpr unsigned REC_E_PBITS = 7, REC_E_DBITS = 16;
-struct RecPlanes {
-	uint32_t *w0, *w1;
-};
-// plane 1 begins at a multiple of four words, so that 16-byte loads of either plane are aligned alike
-static RecPlanes rec_planes(uint2 *rec, size_t n)
-{
-	uint32_t *w = reinterpret_cast<uint32_t *>(rec);
-	return RecPlanes{w, w + ((n + 3) & ~(size_t)3)};
-}
-// the record of element x, walked by lane `owner`, with second word y (the tour: the partial; the events: pa | pd << 16)
-template <bool TWO>
-__device__ __forceinline__ void rec_store(const RecPlanes &rec, uint32_t x, unsigned b, uint32_t owner, uint32_t y)
-{
-	constexpr unsigned PB = TWO ? REC_E_PBITS : REC_T_PBITS, DB = TWO ? REC_E_DBITS : REC_T_DBITS;
-	constexpr uint32_t PMAX = (1u << PB) - 1u, HALF = 1u << (DB - 1);
-	const uint32_t d = owner - (x >> b), pa = TWO ? (y & REC_MAX) : y, pd = TWO ? (y >> 16) : 0u;
-	if (d + HALF < 2u * HALF && pa <= PMAX && pd <= PMAX) {
-		rec.w0[x] = ((d & (2u * HALF - 1u)) << (31u - DB)) | pa | (pd << PB);
-	} else {
-		rec.w0[x] = REC_ESC | owner;
-		rec.w1[x] = y;
-	}
-}
-// ... and back: {owner, second word} from the words of the planes (w1 is looked at only where w0 carries REC_ESC, or fin)
-template <bool TWO>
-__device__ __forceinline__ uint2 rec_decode(uint32_t x, unsigned b, uint32_t w0, uint32_t w1, bool fin = false)
-{
-	constexpr unsigned PB = TWO ? REC_E_PBITS : REC_T_PBITS, DB = TWO ? REC_E_DBITS : REC_T_DBITS;
-	constexpr uint32_t PMAX = (1u << PB) - 1u;
-	if (fin)
-		return make_uint2(w0, w1);
-	if (w0 & REC_ESC)
-		return make_uint2(w0 & ~REC_ESC, w1);
-	const uint32_t d = (uint32_t)((int32_t)(w0 << 1) >> (32 - DB));
-	return make_uint2((x >> b) + d, TWO ? ((w0 & PMAX) | (((w0 >> PB) & PMAX) << 16)) : (w0 & PMAX));
-}
-template <bool L0, bool TWO, bool EVT3 = false>
-__global__ void k_rank_up(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ nx_in, const uint32_t *__restrict__ a_in,
-			  const uint32_t *__restrict__ b_in, const uint32_t *__restrict__ heads, uint32_t *__restrict__ nx_out,
-			  uint32_t *__restrict__ a_out, uint32_t *__restrict__ b_out, RecPlanes rec, uint32_t *__restrict__ ovf)
-{
-	const uint32_t id = BIDX * blockDim.x + threadIdx.x;
-	if (id >= A.M)
-		return;
-	uint32_t x = rank_lane_start<L0>(id, A, b, nx_in, heads);
-	uint32_t sa = 0, sb = 0, out = PK_END | PK_STOP;
-	bool big = false;
-	if (x != NIL) {
-		uint32_t p;
-		bool stop;
-		do {
-			p = nx_in[x];
-			if (L0) {
-				uint32_t wa, wb;
-				rank_l0_weights<EVT3>(x, p, wa, wb);
-				if (TWO) {
-					big |= sa > REC_MAX || sa - sb > REC_MAX;
-					rec_store<true>(rec, x, b, id, sa | ((sa - sb) << 16));
-				} else {
-					rec_store<false>(rec, x, b, id, sa);
-				}
-				sa += wa;
-				if (TWO)
-					sb += wb;
-				x = p & P0_END;
-				stop = rank_l0_stop(x, b);
-			} else {
-				sa += a_in[x];
-				if (TWO)
-					sb += b_in[x];
-				x = p & PK_END;
-				stop = (p & PK_STOP) != 0;
-			}
-		} while (!stop);
-		if (x != (L0 ? P0_END : PK_END)) { // the successor is the splitter of its bucket: that bucket is its idx one level up
-			const uint32_t q = x >> b;
-			out = q | (is_splitter(q, b) ? PK_STOP : 0u);
-		}
-	}
-	nx_out[id] = out;
-	a_out[id] = sa;
-	if (TWO)
-		b_out[id] = sb;
-	if (L0 && TWO && big)
-		*ovf = 1u;
-}
-// (a pass whose level-0 walk raised *ovf: the old way back over the list, final ranks a, b into the two planes; a grid-stride loop
-// over the lanes, so that the launch costs next to nothing when the flag is down)
-template <bool EVT3>
-__global__ void k_rank_l0_fallback(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ pk, const uint32_t *__restrict__ heads,
-				   const uint32_t *__restrict__ ra, const uint32_t *__restrict__ rb, RecPlanes rec,
-				   const uint32_t *__restrict__ ovf)
-{
-	if (!*ovf)
-		return;
-	for (uint32_t id = BIDX * blockDim.x + threadIdx.x; id < A.M; id += gridDim.x * blockDim.x) {
-		uint32_t x = rank_lane_start<true>(id, A, b, pk, heads);
-		if (x == NIL)
-			continue;
-		uint32_t sa = ra[id], sb = rb[id];
-		do {
-			const uint32_t p = pk[x];
-			uint32_t wa, wb;
-			rank_l0_weights<EVT3>(x, p, wa, wb);
-			rec.w0[x] = sa;
-			rec.w1[x] = sb;
-			sa -= wa;
-			sb -= wb;
-			x = p & P0_END;
-		} while (!rank_l0_stop(x, b));
-	}
-}
-// the way back (levels >= 1): lane `id` knows the suffix sums at its splitter (ra / rb of the level above) and hands
-// every element of its segment its own, in place of its weights.
-template <bool TWO>
-__global__ void k_rank_down(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ nx_in, uint32_t *a_io, uint32_t *b_io,
-			    const uint32_t *__restrict__ ra, const uint32_t *__restrict__ rb)
-{
-	const uint32_t id = BIDX * blockDim.x + threadIdx.x;
-	if (id >= A.M)
-		return;
-	uint32_t x = rank_lane_start<false>(id, A, b, nx_in, nullptr);
-	if (x == NIL)
-		return;
-	uint32_t sa = ra[id], sb = TWO ? rb[id] : 0, p;
-	do {
-		p = nx_in[x];
-		const uint32_t wa = a_io[x];
-		a_io[x] = sa;
-		sa -= wa;
-		if (TWO) {
-			const uint32_t wb = b_io[x];
-			b_io[x] = sb;
-			sb -= wb;
-		}
-		x = p & PK_END;
-	} while (!(p & PK_STOP));
-}
-// top level: inclusive suffix sums of at most RANK_TOP elements by pointer jumping in LDS, one workgroup
-template <bool TWO>
-__global__ void __launch_bounds__(1024) k_rank_top(uint32_t n, const uint32_t *__restrict__ nx_in, uint32_t *a_io, uint32_t *b_io)
-{
-	__shared__ uint32_t nx[RANK_TOP], sa[RANK_TOP], sb[TWO ? RANK_TOP : 1];
-	for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-		const uint32_t p = nx_in[i] & PK_END;
-		nx[i] = p == PK_END ? NIL : p;
-		sa[i] = a_io[i];
-		if (TWO)
-			sb[i] = b_io[i];
-	}
-	__syncthreads();
-	constexpr int PER = RANK_TOP / 1024;
-	for (uint32_t span = 1; span < n; span <<= 1) {
-		uint32_t tn[PER], ta[PER], tb[PER];
-#pragma unroll
-		for (int k = 0; k < PER; k++) {
-			const uint32_t i = threadIdx.x + k * 1024;
-			tn[k] = NIL, ta[k] = 0, tb[k] = 0;
-			if (i < n && nx[i] != NIL) {
-				const uint32_t j = nx[i];
-				tn[k] = nx[j];
-				ta[k] = sa[j];
-				if (TWO)
-					tb[k] = sb[j];
-			}
-		}
-		__syncthreads();
-#pragma unroll
-		for (int k = 0; k < PER; k++) {
-			const uint32_t i = threadIdx.x + k * 1024;
-			if (i < n && nx[i] != NIL) {
-				nx[i] = tn[k];
-				sa[i] += ta[k];
-				if (TWO)
-					sb[i] += tb[k];
-			}
-		}
-		__syncthreads();
-	}
-	for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-		a_io[i] = sa[i];
-		if (TWO)
-			b_io[i] = sb[i];
-	}
-}
-// (top level too large for one workgroup -- graphs with very many tiny components: the old pointer jumping in global memory)
-__global__ void k_rank_unpack_next(uint32_t n, const uint32_t *__restrict__ nx_in, uint32_t *__restrict__ out)
-{
-	uint32_t i = BIDX * blockDim.x + threadIdx.x;
-	if (i < n) {
-		const uint32_t p = nx_in[i] & PK_END;
-		out[i] = p == PK_END ? NIL : p;
-	}
-}
-
-struct RankBufs {
-	uint32_t *pk;			 // [n+1] packed list words of level 0 (rank_pack)
-	uint32_t *heads;		 // [max heads] level-0 element that heads list h, NIL for none
-	uint32_t *nx, *wa, *wb;		 // pools for the levels above 0 (next words, sums), rank_pool_words() each
-	uint32_t *tA, *tB, *tC;		 // three more pools: ping-pong of the global-memory fallback of the top level
-};
-static constexpr int RANK_MAX_LEVELS = 12;
-// words every pool needs for lists of n elements in total with nh heads: the first level above the list has
-// M = n / 2^b + nh elements (b >= 3), the following ones at least halve until the last, which may be as large as
-// the one before it again -- < 3.2 M in all
-static size_t rank_pool_words(size_t n, size_t nh) { return n / 2 + 4 * nh + 64; }
-
-// Where a level-0 rank is read (k_t0_parents, k_tree_emit): R = the inclusive suffix sums of the level-1
-// elements (rb.wa, and rb.wb when TWO), M of them; with TWO, fin = the overflow word (set: the records hold final
-// ranks).  (An owner outside R -- only a slot no tour reaches, which k_t0_parents reports as an error -- reads 0
-// instead of memory past the pool.)
-struct L0Ranks {
-	const uint32_t *ra, *rb, *fin;
-	uint32_t M;
-	const uint32_t *w0, *w1; // the two planes of the level-0 records (rec_planes)
-	unsigned b;		  // bucket bits of the ranking (rec_decode)
-};
-// The gathers are unconditional (gather_if, common.hpp), so that a reader's look-ups leave together as one batch: it gathers
-// R.ra (and R.rb) at l0_at() of every record, puts landed() behind the batch and hands each word to rank_l0* with its record.
-// An owner outside R, a record that holds a final rank (fin) and a record the caller does not want read R[0] in its place --
-// safe: a ranking that ran has M >= 1 elements on level 1, and the callers only get here with records of a ranking that ran
-// (a graph without links has no slot, and its R stays null: root_forest).
-__device__ __forceinline__ uint32_t l0_at(const L0Ranks &R, uint2 rec, bool want = true) { return want && rec.x < R.M ? rec.x : 0u; }
-// rank of an element (the 0/1 weights) from its record {owner, partial} and ra = R.ra[l0_at(R, rec)] ...
-__device__ __forceinline__ uint32_t rank_l0(const L0Ranks &R, uint2 rec, uint32_t ra) { return (rec.x < R.M ? ra : 0u) - rec.y; }
-// ... and with TWO (fin read once per lane by the caller; the words gathered at l0_at(R, rec, !fin)) the first sum or both
-__device__ __forceinline__ uint32_t rank_l0_a(const L0Ranks &R, uint2 rec, bool fin, uint32_t ra)
-{
-	return fin ? rec.x : (rec.x < R.M ? ra : 0u) - (rec.y & REC_MAX);
-}
-__device__ __forceinline__ uint2 rank_l0_pair(const L0Ranks &R, uint2 rec, bool fin, uint32_t ra, uint32_t rb)
-{
-	const bool in = rec.x < R.M;
-	const uint32_t pa = rec.y & REC_MAX;
-	return fin ? rec : make_uint2((in ? ra : 0u) - pa, (in ? rb : 0u) - pa + (rec.y >> 16));
-}
-// one element on its own, from the planes (plane 1 only where the record escaped)
-__device__ __forceinline__ uint32_t rank_l0_of(const L0Ranks &R, uint32_t x)
-{
-	const uint32_t w0 = R.w0[x];
-	const uint2 rec = rec_decode<false>(x, R.b, w0, (w0 & REC_ESC) ? R.w1[x] : 0u);
-	return rank_l0(R, rec, R.ra[l0_at(R, rec)]);
-}
-__device__ __forceinline__ uint2 rank_l0_pair_of(const L0Ranks &R, uint32_t x, bool fin)
-{
-	const uint32_t w0 = R.w0[x];
-	const uint2 rec = rec_decode<true>(x, R.b, w0, (fin || (w0 & REC_ESC)) ? R.w1[x] : 0u, fin);
-	const uint32_t i = l0_at(R, rec, !fin);
-	return rank_l0_pair(R, rec, fin, R.ra[i], R.rb[i]);
-}
-
-// (debug hook povu_hip_debug_rank_escapes) What the level-0 walk left, counted after the fact by a walk of its own over the
-// same segments: the elements it reaches, how many of their records carry REC_ESC, and the histogram of the widths their
-// owner delta (zigzag) and partial sums need (RankRecStats).  out[0] = live, out[1] = escaped, out[2 + 33 d + p] = the histogram.
-__device__ __forceinline__ uint32_t bit_width(uint32_t v) { return 32u - (uint32_t)__clz(v); }
-template <bool TWO, bool EVT3>
-__global__ void k_rank_rec_stats(RankLevelArgs A, unsigned b, const uint32_t *__restrict__ pk, const uint32_t *__restrict__ heads,
-				 const uint32_t *__restrict__ w0, unsigned long long *__restrict__ out)
-{
-	__shared__ uint32_t h[2 + 33 * 33];
-	for (uint32_t i = threadIdx.x; i < 2 + 33 * 33; i += blockDim.x)
-		h[i] = 0;
-	__syncthreads();
-	for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < A.M; id += gridDim.x * blockDim.x) {
-		uint32_t x = rank_lane_start<true>(id, A, b, pk, heads);
-		if (x == NIL)
-			continue;
-		uint32_t sa = 0, sb = 0;
-		do {
-			const uint32_t p = pk[x];
-			uint32_t wa, wb;
-			rank_l0_weights<EVT3>(x, p, wa, wb);
-			const int32_t d = (int32_t)(id - (x >> b));
-			const uint32_t zz = ((uint32_t)d << 1) ^ (uint32_t)(d >> 31);
-			const uint32_t pw = TWO ? max(bit_width(sa), bit_width(sa - sb)) : bit_width(sa);
-			atomicAdd(&h[0], 1u);
-			if (w0[x] & REC_ESC)
-				atomicAdd(&h[1], 1u);
-			atomicAdd(&h[2 + 33 * bit_width(zz) + pw], 1u);
-			sa += wa;
-			if (TWO)
-				sb += wb;
-			x = p & P0_END;
-		} while (!rank_l0_stop(x, b));
-	}
-	__syncthreads();
-	for (uint32_t i = threadIdx.x; i < 2 + 33 * 33; i += blockDim.x)
-		if (h[i])
-			atomicAdd(&out[i], (unsigned long long)h[i]);
-}
-template <bool TWO, bool EVT3>
-static void rank_rec_stats(const RankLevelArgs &A, unsigned b, const RankBufs &rb, const L0Ranks &R, RankRecStats &st, hipStream_t s)
-{
-	constexpr size_t W = 2 + 33 * 33;
-	st = RankRecStats{};
-	unsigned long long *d = nullptr;
-	uint32_t fin = 0;
-	std::vector<unsigned long long> hst(W);
-	HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d), W * 8));
-	try {
-		HIP_CHECK(hipMemsetAsync(d, 0, W * 8, s));
-		// (a block's LDS counters are 32 bits wide: at most 2048 blocks of 256 lanes, each lane over M / 2^19 segments)
-		KLAUNCH((k_rank_rec_stats<TWO, EVT3>), dim3(std::min(nblk(A.M), 2048u)), dim3(TPB), 0, s, A, b, rb.pk, rb.heads, R.w0, d);
-		HIP_CHECK(copy_async(hst.data(), d, W * 8, hipMemcpyDeviceToHost, s));
-		if (TWO)
-			HIP_CHECK(copy_async(&fin, R.fin, 4, hipMemcpyDeviceToHost, s));
-		HIP_CHECK(hipStreamSynchronize(s));
-	} catch (...) {
-		(void)hipFree(d);
-		throw;
-	}
-	HIP_CHECK(hipFree(d));
-	st.valid = true;
-	st.fin = fin;
-	st.bits = b;
-	st.delta_bits = TWO ? REC_E_DBITS : REC_T_DBITS;
-	st.part_bits[0] = TWO ? REC_E_PBITS : REC_T_PBITS;
-	st.part_bits[1] = TWO ? REC_E_PBITS : 0u;
-	st.live = hst[0];
-	st.esc = fin ? hst[0] : hst[1];
-	std::copy(hst.begin() + 2, hst.end(), st.hist);
-}
-
-// suffix sums (inclusive) along the lists packed in rb.pk, left as level-0 records rec[x] (k_rank_up) to be resolved
-// by rank_l0 (the 0/1 weights) or rank_l0_pair (TWO: that sum and the sum of the +-1 weights derived from them; `ovf`
-// = a device word for the overflow flag).  R stays valid until the pools are used again.
-template <bool TWO, bool EVT3 = false>
-static L0Ranks list_rank_splitters(uint32_t n, unsigned b, uint2 *rec_arr, uint32_t *ovf, uint32_t nh, RankBufs &rb, hipStream_t s,
-				   RankRecStats *st = nullptr)
-{
-	const RecPlanes rec = rec_planes(rec_arr, n);
-	if (n >= P0_END)
-		throw HipError("list ranking: more than 2^30 elements (graph too large for the packed walk)");
-	// plan: level L has lv[L].n elements; its walk has lv[L].M lanes = the elements of level L + 1
-	RankLevelArgs lv[RANK_MAX_LEVELS];
-	uint32_t *nxp[RANK_MAX_LEVELS + 1], *wap[RANK_MAX_LEVELS + 1], *wbp[RANK_MAX_LEVELS + 1];
-	int levels = 0;
-	size_t used = 0;
-	const size_t pool = rank_pool_words(n, nh);
-	nxp[0] = rb.pk, wap[0] = wbp[0] = nullptr;
-	uint32_t cur_n = n, hbase = 0;
-	for (;;) {
-		RankLevelArgs &A = lv[levels];
-		A.n = cur_n;
-		A.m = (cur_n + (1u << b) - 1) >> b;
-		A.hbase = hbase;
-		A.M = A.m + nh;
-		if (used + A.M > pool)
-			throw HipError("list ranking: level pool exhausted (internal sizing bug)");
-		nxp[levels + 1] = rb.nx + used, wap[levels + 1] = rb.wa + used, wbp[levels + 1] = rb.wb + used;
-		used += A.M;
-		levels++;
-		hbase = A.m;
-		const uint32_t next_n = A.M;
-		// stop when one workgroup can finish, or when the heads keep the levels from shrinking
-		if (next_n <= RANK_TOP || next_n > cur_n / 2 || levels == RANK_MAX_LEVELS) {
-			cur_n = next_n;
-			break;
-		}
-		cur_n = next_n;
-	}
-	if (TWO)
-		HIP_CHECK(hipMemsetAsync(ovf, 0, 4, s));
-	for (int L = 0; L < levels; L++) {
-		const RankLevelArgs &A = lv[L];
-		if (L == 0)
-			LAUNCH((k_rank_up<true, TWO, EVT3>), A.M, s, A, b, nxp[0], nullptr, nullptr, rb.heads, nxp[1], wap[1], wbp[1], rec, ovf);
-		else
-			LAUNCH((k_rank_up<false, TWO>), A.M, s, A, b, nxp[L], wap[L], wbp[L], nullptr, nxp[L + 1], wap[L + 1], wbp[L + 1],
-			       RecPlanes{nullptr, nullptr}, nullptr);
-	}
-	const uint32_t nt = cur_n; // elements of the top level
-	if (nt <= RANK_TOP) {
-		KLAUNCH((k_rank_top<TWO>), dim3(1), dim3(1024), 0, s, nt, nxp[levels], wap[levels], wbp[levels]);
-	} else {
-		LAUNCH(k_rank_unpack_next, nt, s, nt, nxp[levels], rb.tA);
-		HIP_CHECK(copy_async(rb.tB, wap[levels], (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
-		if (TWO)
-			HIP_CHECK(copy_async(rb.tC, wbp[levels], (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
-		// ping-pong partners: the level's own arrays (their contents were just copied out)
-		uint32_t *nA = rb.tA, *nB = nxp[levels], *aA = rb.tB, *aB = wap[levels], *bA = rb.tC, *bB = wbp[levels];
-		const int side = list_rank(nt, bits_for(nt) + 1, nA, nB, aA, aB, TWO ? bA : nullptr, TWO ? bB : nullptr, s);
-		if (side == 0) { // result in the A set: bring it home
-			HIP_CHECK(copy_async(wap[levels], aA, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
-			if (TWO)
-				HIP_CHECK(copy_async(wbp[levels], bA, (size_t)nt * 4, hipMemcpyDeviceToDevice, s));
-		}
-	}
-	// (level 0 has no way back: its records are resolved where they are read)
-	for (int L = levels - 1; L >= 1; L--) {
-		const RankLevelArgs &A = lv[L];
-		LAUNCH((k_rank_down<TWO>), A.M, s, A, b, nxp[L], wap[L], wbp[L], wap[L + 1], wbp[L + 1]);
-	}
-	if (TWO)
-		KLAUNCH((k_rank_l0_fallback<EVT3>), dim3(std::min(nblk(lv[0].M), 2048u)), dim3(TPB), 0, s, lv[0], b, rb.pk, rb.heads, wap[1],
-			wbp[1], rec, ovf);
-	const L0Ranks R{wap[1], TWO ? wbp[1] : nullptr, TWO ? ovf : nullptr, lv[0].M, rec.w0, rec.w1, b};
-	if (st)
-		rank_rec_stats<TWO, EVT3>(lv[0], b, rb, R, *st, s);
-	return R;
-}
-
-// (unit-test hook, debug_list_rank) every element's rank resolved from its record, as the readers do
-template <bool TWO>
-__global__ void k_rank_resolve(uint32_t n, L0Ranks R, uint32_t *__restrict__ ra, uint32_t *__restrict__ rb)
-{
-	const uint32_t x = BIDX * blockDim.x + threadIdx.x;
-	if (x >= n)
-		return;
-	if (TWO) {
-		const uint2 r = rank_l0_pair_of(R, x, *R.fin != 0);
-		ra[x] = r.x;
-		rb[x] = r.y;
-	} else {
-		ra[x] = rank_l0_of(R, x);
-	}
-}
-void debug_list_rank(uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads, uint32_t nh, int mode,
-		     unsigned bits, uint32_t *ra, uint32_t *rb, hipStream_t s, RankRecStats *st, std::vector<uint32_t> *plane0)
-{
-	if (n == 0 || n >= P0_END)
-		throw HipError("debug_list_rank: n must be in [1, 2^30)");
-	const unsigned b = bits ? std::min(6u, std::max(2u, bits)) : rank_bucket_bits(n);
-	std::vector<uint32_t> pk(n);
-	for (uint32_t x = 0; x < n; x++) {
-		if (next[x] != NIL && next[x] >= n)
-			throw HipError("debug_list_rank: successor out of range");
-		pk[x] = (next[x] == NIL ? P0_END : next[x]) | (w[x] ? P0_W : 0u);
-	}
-	for (uint32_t h = 0; h < nh; h++)
-		if (heads[h] != NIL) {
-			if (heads[h] >= n)
-				throw HipError("debug_list_rank: head out of range");
-			pk[heads[h]] |= P0_HEAD;
-		}
-	const size_t pool = rank_pool_words(n, nh);
-	Arena ar;
-	ar.reserve(Arena::padded(n + 16, 4) * 3 + Arena::padded(n + 16, 8) + Arena::padded(nh + 1, 4) + 6 * Arena::padded(pool, 4) + 8192, false);
-	RankBufs rbf{};
-	rbf.pk = ar.take<uint32_t>(n + 16);
-	rbf.heads = ar.take<uint32_t>(nh + 1);
-	for (uint32_t **q : {&rbf.nx, &rbf.wa, &rbf.wb, &rbf.tA, &rbf.tB, &rbf.tC})
-		*q = ar.take<uint32_t>(pool);
-	uint32_t *da = ar.take<uint32_t>(n + 16), *db = ar.take<uint32_t>(n + 16), *ovf = ar.take<uint32_t>(4);
-	uint2 *rec = ar.take<uint2>(n + 16);
-	HIP_CHECK(copy_async(rbf.pk, pk.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-	if (nh)
-		HIP_CHECK(copy_async(rbf.heads, heads, (size_t)nh * 4, hipMemcpyHostToDevice, s));
-	if (mode == 0) {
-		const L0Ranks R = list_rank_splitters<false>(n, b, rec, nullptr, nh, rbf, s, st);
-		LAUNCH(k_rank_resolve<false>, n, s, n, R, da, nullptr);
-	} else {
-		const L0Ranks R = list_rank_splitters<true, true>(n, b, rec, ovf, nh, rbf, s, st);
-		LAUNCH(k_rank_resolve<true>, n, s, n, R, da, db);
-	}
-	if (plane0) {
-		plane0->resize(n);
-		HIP_CHECK(copy_async(plane0->data(), rec, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-	}
-	HIP_CHECK(copy_async(ra, da, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-	if (mode != 0)
-		HIP_CHECK(copy_async(rb, db, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-	HIP_CHECK(hipStreamSynchronize(s));
 }
 
 // ------------------------------------------------------------------ 2. rooted forest T0 and 3. its bridges
@@ -1590,13 +979,13 @@ __global__ void k_walk_finish(uint32_t nS, const uint32_t *__restrict__ wpar, co
 // children, so the work stays linear in the degrees.
 // The far side o of a segment always is the first child of the side e it is entered through (black edge first), so a
 // segment needs three events, not four: 3g = enter e and o, 3g + 1 = leave o, 3g + 2 = leave e -- and when e has no
-// other child (the common case) the two leaves are one event (bit 29 of its word) and 3g + 2 stays out of the list.
+// other child (the common case) the two leaves are one event (the weight bit of its word, P0_W) and 3g + 2 stays out of the list.
 // "enter" heads the list of its component iff e is the DFS start of a processed component (segments of other
 // components get inert words).  merged[g] remembers which form the segment took.
 __device__ __forceinline__ uint32_t leave_event(uint32_t p, bool p_is_far) { return 3 * (p >> 1) + (p_is_far ? 1u : 2u); }
 __global__ void k_events(uint32_t V, const uint2 *__restrict__ dps, const uint32_t *__restrict__ loff,
 			 const uint32_t *__restrict__ ladj, const uint32_t *__restrict__ ckey, const uint32_t *__restrict__ cproc,
-			 uint32_t *__restrict__ pk, uint32_t *__restrict__ heads, unsigned b, uint8_t *__restrict__ merged,
+			 uint32_t *__restrict__ pk, uint32_t *__restrict__ heads, uint8_t *__restrict__ merged,
 			 uint32_t *__restrict__ sdl)
 {
 	// One lane per SEGMENT: it needs the first child of the far side o, the next sibling of o (= the first gray child of the
@@ -1651,7 +1040,7 @@ __global__ void k_events(uint32_t V, const uint2 *__restrict__ dps, const uint32
 		const uint32_t ns_e = child_behind(p, lo_p, n_p, slot_e + 1);
 		after_e = ns_e != NIL ? 3 * (ns_e >> 1) : leave_event(p, dps[p].x == (p ^ 1u));
 	}
-	uint32_t enter = rank_pack(c_o != NIL ? 3 * (c_o >> 1) : A + 1, 0u, b);
+	uint32_t enter = rank_pack(c_o != NIL ? 3 * (c_o >> 1) : A + 1, 0u);
 	if (p == NIL) {
 		const uint32_t comp = ckey[g];
 		if (cproc[comp]) {
@@ -1661,11 +1050,11 @@ __global__ void k_events(uint32_t V, const uint2 *__restrict__ dps, const uint32
 	}
 	pk[A] = enter;
 	if (ns_o != NIL) { // the entered side has more children: leave o -> the first of them; leave e on its own
-		pk[A + 1] = rank_pack(3 * (ns_o >> 1), 0u, b);
-		pk[A + 2] = rank_pack(after_e, 0u, b);
+		pk[A + 1] = rank_pack(3 * (ns_o >> 1), 0u);
+		pk[A + 2] = rank_pack(after_e, 0u);
 		merged[g] = 0;
 	} else {
-		pk[A + 1] = rank_pack(after_e, 1u, b); // both leaves in one
+		pk[A + 1] = rank_pack(after_e, 1u); // both leaves in one
 		pk[A + 2] = P0_END;
 		merged[g] = 1;
 	}
@@ -2097,8 +1486,8 @@ static void tree_spans(TreeWs &tw, size_t V, size_t E, size_t Cmax, int groups, 
 	take(nS, tw.dvis);
 	take(nS + 2 * E + 8, tw.wadj); // wave walk: class-filtered scan lists (4 bytes a slot); earlier in the pass: twin slots [2E]
 	take(Cmax + 2, tw.cproc);
-	take(NSL, tw.rk_pk);
-	take(Cmax + 2, tw.rk_heads);
+	take(NSL, tw.rk.pk);
+	take(Cmax + 2, tw.rk.heads);
 	// One block, three tenants that are never at home together: the six level pools of the list rankings (the tour's at the
 	// start, the pre-order's after the class walks); behind the pools the bridge test's values -- one 16-byte value per
 	// segment that carries one (K <= V) and their running xor, live between the first ranking and the class walks, and on
@@ -2116,7 +1505,7 @@ static void tree_spans(TreeWs &tw, size_t V, size_t E, size_t Cmax, int groups, 
 	if (groups & 2)
 		tw.walk_inline = o.walk_inline;
 	if (blk) {
-		uint32_t **pools[6] = {&tw.rk_nx, &tw.rk_wa, &tw.rk_wb, &tw.rk_tA, &tw.rk_tB, &tw.rk_tC};
+		uint32_t **pools[6] = {&tw.rk.nx, &tw.rk.wa, &tw.rk.wb, &tw.rk.tA, &tw.rk.tB, &tw.rk.tC};
 		for (int k = 0; k < 6; k++)
 			*pools[k] = reinterpret_cast<uint32_t *>(blk + (size_t)k * pool_b);
 		tw.xval = reinterpret_cast<decltype(tw.xval)>(blk + 6 * pool_b);
@@ -2173,7 +1562,7 @@ void stage_workspace_carve(Arena &ar, ParWs &pw, TreeWs &tw, size_t V, size_t E,
 struct TreeViews {
 	ulonglong2 *hside;   // evt: [nS] 16-byte hash words of the sides (evt holds [max(4V, 2E)] 8-byte words); k_tour_words -> k_bridges [then the event records of the second ranking]
 	uint32_t *ft;	     // be_cnt: [nS] first arc of a side | "its hash word was written"; k_tour_words -> k_tour_values [free until the back edges are counted]
-	uint2 *fstr;	     // rk_pk: [V] the far sides' stretches, 8-byte records over the tour's list words, which the first ranking has consumed (rk_pk holds more than 4V words); k_t0_parents -> k_bridges [then k_events rewrites all 3V words for the second ranking]
+	uint2 *fstr;	     // rk.pk: [V] the far sides' stretches, 8-byte records over the tour's list words, which the first ranking has consumed (rk.pk holds more than 4V words); k_t0_parents -> k_bridges [then k_events rewrites all 3V words for the second ranking]
 	uint8_t *multi;	     // dvis_slots: per-side class flags (sized for max(2E, 2V) + 16, see tree_spans); cleared by k_t0_parents, k_bridges -> k_entry_list [then the per-slot duplicate flags, k_dup_flags]
 	uint32_t *cstate;    // SeqWs::cur: [nS+1] parent word | visited bit of a side; k_bridges -> k_walk_finish
 	uint8_t *merged;     // dvis: [V]; k_events -> k_tree_emit
@@ -2190,7 +1579,7 @@ static TreeViews tree_views(const TreeWs &tw, uint32_t E, uint32_t *cur = nullpt
 	TreeViews v;
 	v.hside = reinterpret_cast<ulonglong2 *>(tw.evt);
 	v.ft = tw.be_cnt;
-	v.fstr = reinterpret_cast<uint2 *>(tw.rk_pk);
+	v.fstr = reinterpret_cast<uint2 *>(tw.rk.pk);
 	v.multi = tw.dvis_slots;
 	v.cstate = cur;
 	v.merged = tw.dvis;
@@ -2202,15 +1591,14 @@ static TreeViews tree_views(const TreeWs &tw, uint32_t E, uint32_t *cur = nullpt
 }
 
 // ------------------------------------------------------------------ driver
-void tree_tour_words(const CompState &cs, uint32_t V, uint32_t E, TreeWs &tw, bool force_sparse_splitters, hipStream_t s)
+void tree_tour_words(const CompState &cs, uint32_t V, uint32_t E, TreeWs &tw, hipStream_t s)
 {
 	const uint32_t nS = 2 * V;
 	const size_t n_slots = 2 * (size_t)E;
 	if (n_slots >= P0_END || 3 * (size_t)V >= P0_END) // (the first ranking runs over the 2E slots, the second over 3 V events)
 		throw HipError("graph too large for the packed list ranking: 2 * links and 3 * segments must stay below 2^30");
-	const unsigned bitsA = force_sparse_splitters ? 4u : rank_bucket_bits(n_slots);
 	const TreeViews v = tree_views(tw, E);
-	LAUNCH(k_tour_words, nS, s, nS, cs.loff, cs.ladj, cs.lle, tw.rk_pk, bitsA, v.hside, v.ft);
+	LAUNCH(k_tour_words, nS, s, nS, cs.loff, cs.ladj, cs.lle, tw.rk.pk, v.hside, v.ft);
 	tw.tour_words_done = true;
 }
 
@@ -2224,7 +1612,7 @@ struct TreePass {
 	hipStream_t s;
 	const uint32_t C, V, E, nS;
 	const uint32_t max_side_links;
-	const bool force_big_class_dfs, force_sparse_splitters;
+	const bool force_big_class_dfs;
 	const TreeViews v;
 	const unsigned long long *start_key;
 	const uint32_t NA;	// arcs of the spanning forest of the segments = positions of the tours
@@ -2232,7 +1620,6 @@ struct TreePass {
 	const uint32_t XW;	// words of the position bitmap
 	const uint32_t n_events; // list elements of the second ranking: three per segment
 	const unsigned bitsA, bitsE; // bucket bits of the two rankings
-	RankBufs rb;
 	L0Ranks tour_r{}, evr{}; // ranks of the tour (records in tw.dist) and of the pre-order events (records in tw.evt)
 	bool events_done = false; // k_events went out early, behind the small walk, and no class overflowed
 	const uint8_t *dupflag = nullptr;
@@ -2240,10 +1627,9 @@ struct TreePass {
 	TreePass(const CompState &cs_, SeqWs &sw_, ParWs &pw_, TreeWs &tw_, uint32_t C_, uint32_t max_side_links_, bool big_dfs, bool sparse,
 		 StageTimer &tm_, hipStream_t s_)
 		: cs(cs_), sw(sw_), pw(pw_), tw(tw_), tm(tm_), s(s_), C(C_), V(sw_.V), E(sw_.E), nS(2 * sw_.V), max_side_links(max_side_links_),
-		  force_big_class_dfs(big_dfs), force_sparse_splitters(sparse), v(tree_views(tw_, sw_.E, sw_.cur)),
+		  force_big_class_dfs(big_dfs), v(tree_views(tw_, sw_.E, sw_.cur)),
 		  start_key((const unsigned long long *)cs_.start_key), NA(2 * (V - C)), n_slots(2 * (size_t)E), XW(NA / 64 + 1), n_events(3 * V),
-		  bitsA(sparse ? 4u : rank_bucket_bits(n_slots)), bitsE(sparse ? 4u : rank_bucket_bits(n_events)),
-		  rb{tw_.rk_pk, tw_.rk_heads, tw_.rk_nx, tw_.rk_wa, tw_.rk_wb, tw_.rk_tA, tw_.rk_tB, tw_.rk_tC}
+		  bitsA(sparse ? 4u : rank_bucket_bits()), bitsE(sparse ? 4u : rank_bucket_bits())
 	{
 		tw.rec_stats[0].valid = tw.rec_stats[1].valid = false; // (what an earlier pass collected says nothing about this one)
 	}
@@ -2253,8 +1639,8 @@ struct TreePass {
 	// (7.) one list per processed component, one two-event list per side of an unprocessed one
 	void enqueue_events()
 	{
-		HIP_CHECK(hipMemsetAsync(rb.heads, 0xFF, (size_t)C * 4, s)); // components that are not decomposed head no list
-		LAUNCH(k_events, V, s, V, tw.dps, cs.loff, cs.ladj, cs.ckey, tw.cproc, rb.pk, rb.heads, bitsE, v.merged, pw.sdl);
+		HIP_CHECK(hipMemsetAsync(tw.rk.heads, 0xFF, (size_t)C * 4, s)); // components that are not decomposed head no list
+		LAUNCH(k_events, V, s, V, tw.dps, cs.loff, cs.ladj, cs.ckey, tw.cproc, tw.rk.pk, tw.rk.heads, v.merged, pw.sdl);
 	}
 };
 
@@ -2268,13 +1654,13 @@ static void root_forest(TreePass &P)
 	const uint32_t V = P.V, C = P.C;
 	P.tm.begin("tree_root_forest");
 	if (!tw.tour_words_done) // (else: started by povu_hip_decompose while the host still waited for the component sizes)
-		tree_tour_words(cs, V, P.E, tw, P.force_sparse_splitters, s);
+		tree_tour_words(cs, V, P.E, tw, s);
 	tw.tour_words_done = false;
-	LAUNCH(k_tour_ends, C, s, C, cs.voff, P.start_key, cs.loff, cs.ladj, cs.lle, P.rb.pk, P.rb.heads);
+	LAUNCH(k_tour_ends, C, s, C, cs.voff, P.start_key, cs.loff, cs.ladj, cs.lle, tw.rk.pk, tw.rk.heads);
 	if (P.n_slots)
-		P.tour_r = list_rank_splitters<false>((uint32_t)P.n_slots, P.bitsA, tw.dist, nullptr, C, P.rb, s, P.rec_stats(0));
+		P.tour_r = rank_tour((uint32_t)P.n_slots, P.bitsA, tw.dist, C, tw.rk, s, P.rec_stats(0));
 	HIP_CHECK(hipMemsetAsync(tw.xrec, 0, ((size_t)P.XW + 2) * 16, s));
-	LAUNCH(k_t0_parents, std::max(V, C), s, V, P.tour_r, cs.ckey, cs.voff, cs.loff, cs.ladj, cs.lle, P.v.ft, P.rb.heads,
+	LAUNCH(k_t0_parents, std::max(V, C), s, V, P.tour_r, cs.ckey, cs.voff, cs.loff, cs.ladj, cs.lle, P.v.ft, tw.rk.heads,
 	       tw.t0seg, P.v.fstr, tw.xrec, C, P.start_key, P.pw.err + PW_FOREST_SIZE, P.v.multi);
 	P.tm.end(40);
 }
@@ -2401,7 +1787,7 @@ static void preorder(TreePass &P)
 	P.tm.begin("tree_preorder");
 	if (!P.events_done)
 		P.enqueue_events();
-	P.evr = list_rank_splitters<true, true>(P.n_events, P.bitsE, P.tw.evt, P.pw.err + PW_RANK_OVF, P.C, P.rb, P.s, P.rec_stats(1));
+	P.evr = rank_events(P.n_events, P.bitsE, P.tw.evt, P.pw.err + PW_RANK_OVF, P.C, P.tw.rk, P.s, P.rec_stats(1));
 	P.tm.end(40);
 }
 

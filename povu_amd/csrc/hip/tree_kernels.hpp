@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "graph_kernels.hpp"
+#include "list_rank.hpp"
 #include "par_kernels.hpp"
 #include "seq_kernels.hpp"
 
@@ -9,23 +10,10 @@ namespace povu_hip
 {
 
 // (arrays that a pass also uses under another type or meaning: see TreeViews in tree_kernels.hip, the one place that names them)
-// What a level-0 walk of a list ranking left in its records (debug hook povu_hip_debug_rank_escapes; k_rank_rec_stats).
-// hist[33 * d + p]: live elements whose owner delta needs d bits (zigzag) and whose partial sums need p bits (the events: the
-// larger of the two) -- worked out by walking the lists again, so the same for any split of the record word.
-struct RankRecStats {
-	bool valid = false;
-	uint32_t fin = 0;	   // the walk overflowed its 16-bit partials: the records hold final ranks (all count as escaped)
-	uint32_t bits = 0;	   // bucket bits of the ranking
-	uint32_t delta_bits = 0;   // width of the signed owner delta of a narrow record
-	uint32_t part_bits[2] = {}; // widths of its partial(s): the tour's one, the events' two
-	uint64_t live = 0, esc = 0; // elements a walk reaches, and those of them whose record carries the escape bit
-	uint64_t hist[33 * 33] = {};
-};
-
 struct TreeWs {
 	HostScratch *host; // pinned read-back scratch of the owning context
 	// unrooted spanning forest of the biedged graph H, as arcs
-	uint2 *dist;					  // [2E] level-0 records of the adjacency slots in the Euler-tour ranking, as two planes of 2E words (slots of hooked links = arcs; a slot's rank, the arcs behind it: rank_l0 of rec_decode, see tree_kernels.hip)
+	uint2 *dist;					  // [2E] level-0 records of the adjacency slots in the Euler-tour ranking, as two planes of 2E words (slots of hooked links = arcs; a slot's rank, the arcs behind it: rank_l0 of rec_decode, see list_rank.hpp)
 	ulonglong2 *xval, *xps;				  // [max(V, E) + 16] xor values (two 64-bit hashes) of the segments that have any, in tour order, and their running xor (inside the shared block, see tree_spans)
 	uint4 *xrec;					  // [(4V+8)/64 + 4] per 64 tour positions {which of them carry a value (64 bits), set bits in front of the word, -}: a bit-rank directory (common.hpp)
 	uint32_t *xrank;				  // [(4V+8)/64 + 4] scan buffer of bitrank_build (the entry behind the last word: the number of values)
@@ -41,8 +29,7 @@ struct TreeWs {
 	uint32_t *entry_ps, *entry_list;		  // [2V+1]
 	uint32_t *side_tidx;				  // [2V] tree vertex (T-space) of a side
 	uint32_t *be_cnt;				  // [2V+1] first arc of a side (tour); free afterwards
-	uint32_t *rk_pk, *rk_heads;			  // list ranking: packed list words [4V+8] (between the first ranking and k_events: the far sides' stretches, [V] 8-byte records), list heads [C]
-	uint32_t *rk_nx, *rk_wa, *rk_wb, *rk_tA, *rk_tB, *rk_tC; // pools of the levels above the list itself
+	RankBufs rk;					  // list ranking (list_rank.hpp): packed list words pk [4V+8] (between the first ranking and k_events: the far sides' stretches, [V] 8-byte records), list heads [C], the six pools of the levels above the list itself
 	uint2 *evt;					  // [4V+2] level-0 records of the pre-order ranking's events, as two planes of 3V words (ranks {enter count, depth}: rank_l0_pair of rec_decode)
 	uint32_t *cproc;				  // [C+1] 1 = component is decomposed by this shard
 	const uint8_t *last_dupflag;			  // dvis_slots when the last pass filled it, else null
@@ -65,20 +52,12 @@ size_t walk_workspace_bytes(size_t V);
 
 // the tree stage's first kernel (Euler-tour words of the spanning forest): it reads the re-indexed adjacency only, so
 // povu_hip_decompose may start it before the host has the component sizes; run_parallel_tree then skips it
-void tree_tour_words(const CompState &cs, uint32_t V, uint32_t E, TreeWs &tw, bool force_sparse_splitters, hipStream_t s);
+void tree_tour_words(const CompState &cs, uint32_t V, uint32_t E, TreeWs &tw, hipStream_t s);
 
 // Builds the reference's spanning tree of every processed component (tree arrays in sw, T-space
 // layout) and the dense list of from_bd back edges (pw.b_src / pw.b_tgt).  Returns their count.
 int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw, uint32_t C, uint32_t max_side_links,
 			   bool force_big_class_dfs, bool force_sparse_splitters, StageTimer &tm, hipStream_t s);
-
-// unit-test hook: the level-0 ranks of list_rank_splitters for the lists next[] (NIL = end) with heads[nh], as the readers
-// resolve them -- mode 0: ra = suffix sums of the 0/1 weights w; mode 1 (the pre-order events): ra, rb = the two sums of the
-// EVT3 weights.  bits = bucket bits (0: the default).  Elements that are in no list get no defined value.
-// st, plane0 (optional): what the walk left in its records, and the first word of every element's record
-void debug_list_rank(uint32_t n, const uint32_t *next, const uint8_t *w, const uint32_t *heads, uint32_t nh, int mode,
-		     unsigned bits, uint32_t *ra, uint32_t *rb, hipStream_t s, RankRecStats *st = nullptr,
-		     std::vector<uint32_t> *plane0 = nullptr);
 
 // back edges from_bd creates just before each tree vertex (w, T-space) and after the last child of each (tail, T-space); both
 // arrays must be zeroed by the caller.  Reads the state of the last run_parallel_tree.  Callers: the leaf passes and the

@@ -1,4 +1,4 @@
-"""Hand-made lists for the level-0 records of the tree stage's list rankings (tree_kernels.hip: rec_store /
+"""Hand-made lists for the level-0 records of the tree stage's list rankings (list_rank.hip / list_rank.hpp: rec_store /
 rec_decode), and the walk that writes them restated in numpy.
 
 A record is one narrow word -- the owner (the walking lane) as a signed delta to the element's bucket x >> b, the
@@ -10,7 +10,7 @@ import functools
 import numpy as np
 
 NIL = 0xFFFFFFFF
-# field widths (tree_kernels.hip: REC_T_*, REC_E_*); the GPU test compares them with what the hook reports
+# field widths (list_rank.hpp: REC_T_*, REC_E_*); the GPU test compares them with what the hook reports
 DELTA_BITS = 16
 TOUR_PBITS = 15
 EVT_PBITS = 7

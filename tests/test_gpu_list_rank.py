@@ -1,4 +1,4 @@
-"""The tree stage's list ranking (list_rank_splitters, tree_kernels.hip) against a host suffix-sum reference.
+"""The tree stage's list ranking (rank_tour / rank_events, list_rank.hip) against a host suffix-sum reference.
 
 Level 0 of the ranking leaves a record per element on its only walk ({owner, partial sums}); the kernels that
 read a rank resolve it as R[owner] - partial.  These tests resolve every element the same way
@@ -15,7 +15,7 @@ from povu_amd import HipDecomposer, workloads as W
 pytestmark = pytest.mark.gpu
 
 NIL = 0xFFFFFFFF
-RANK_TOP = 8192  # elements the top level ranks in one workgroup (tree_kernels.hip)
+RANK_TOP = 8192  # elements the top level ranks in one workgroup (list_rank.hip)
 
 
 @pytest.fixture(scope="module")
@@ -82,7 +82,7 @@ def bucket_splitter(q, b):
 
 
 def top_level_size(n, nh, b):
-    """Elements of the top level list_rank_splitters plans for n elements and nh heads."""
+    """Elements of the top level the ranking plans for n elements and nh heads."""
     cur, levels = n, 0
     while True:
         m = (cur + (1 << b) - 1) >> b

@@ -1,4 +1,4 @@
-"""The level-0 records of the tree stage's list rankings in their two-plane form (tree_kernels.hip: rec_store /
+"""The level-0 records of the tree stage's list rankings in their two-plane form (list_rank.hip / list_rank.hpp: rec_store /
 rec_decode): a narrow word where the owner's delta to the element's bucket and the partial sums fit their fields, an
 escaped pair of words where they do not, final ranks over both planes where the events' 16-bit partials overflow.
 
