@@ -48,9 +48,9 @@ int povu_hip_device_count(void);
 /* create / destroy a context on `device` */
 povu_hip_ctx *povu_hip_create(int device, char *err, size_t errlen);
 void povu_hip_destroy(povu_hip_ctx *ctx);
-/* gives the decompose and traversal workspaces of `ctx` back to the device, keeping the resident graph and paths (a context
- * kept only for povu_hip_forest_walks / _traversals on a forest it made); the next call reserves them again.  Ends the debug exports of
- * the last pass.  0 on success */
+/* gives every workspace arena of `ctx` back to the device; the resident graph, paths, sequences, a received shard and the
+ * packed shards stay (povu_hip_arena_report says which is which).  The next call reserves what it needs again.  Ends the debug
+ * exports of the last pass.  0 on success */
 int povu_hip_release_workspace(povu_hip_ctx *ctx);
 
 /*
@@ -818,6 +818,10 @@ typedef struct {
 } povu_hip_stage_time;
 /* stage timings of the last povu_hip_decompose on this context */
 int povu_hip_last_stage_times(const povu_hip_ctx *ctx, povu_hip_stage_time *out, int max);
+typedef struct { char name[24]; int resident; uint64_t bytes; } povu_hip_arena_info;
+/* every device arena of the context, in declaration order: its name, whether povu_hip_release_workspace keeps it,
+ * and the bytes it holds now.  Returns the count (fills at most `max`). */
+int povu_hip_arena_report(const povu_hip_ctx *ctx, povu_hip_arena_info *out, int max);
 /* components redone by the one-lane kernels in the last decompose (only the test modes POVU_HIP_F_FORCE_REDO / _REDO_ODD
  * send any: crossing candidate-stack intervals, the one case that used to, are resolved by the parallel stage itself) */
 uint32_t povu_hip_last_seq_redo(const povu_hip_ctx *ctx);

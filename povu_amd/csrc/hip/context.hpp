@@ -248,13 +248,104 @@ struct LastPass {
 	int narrow_forms = 0; // which of them: bit 0 ordcnt, bit 1 srccnt, bit 2 incnt
 };
 
+// Every device arena of a context besides the six of SubArenas, declared once: X(name, kind).  The list makes the members
+// of povu_hip_ctx and its for_each_arena, so povu_hip_release_workspace, povu_hip_destroy and povu_hip_arena_report reach
+// an arena because it exists.  ARENA_RESIDENT survives povu_hip_release_workspace, ARENA_WORKSPACE does not.
+enum ArenaKind { ARENA_WORKSPACE = 0, ARENA_RESIDENT = 1 };
+#define POVU_CTX_ARENAS(X)                                                                                                       \
+	/* povu_hip_decompose: the stage workspaces (ws_b: what the re-index needs beyond the labelling's arrays; ws_leaf: the   \
+	 * leaf passes of -s, kept from one -s pass to the next; ws_walk: the wave walk's arrays, taken by the first pass that   \
+	 * meets large classes) */                                                                                               \
+	X(ws, ARENA_WORKSPACE)                                                                                                   \
+	X(ws_b, ARENA_WORKSPACE)                                                                                                 \
+	X(ws2, ARENA_WORKSPACE)                                                                                                  \
+	X(ws_seq, ARENA_WORKSPACE)                                                                                               \
+	X(ws_leaf, ARENA_WORKSPACE)                                                                                              \
+	X(ws_walk, ARENA_WORKSPACE)                                                                                              \
+	X(upload_tmp, ARENA_WORKSPACE)                                                                                           \
+	X(shard_buf, ARENA_RESIDENT)   /* a shard received from another rank */                                                  \
+	X(graph_arena, ARENA_RESIDENT) /* backs the resident graph */                                                            \
+	/* povu_hip_forest_walks (walk_kernels.hip): queries, counts and tier-2 stacks / the walks themselves */                 \
+	X(wk_ws, ARENA_WORKSPACE)                                                                                                \
+	X(wk_out, ARENA_WORKSPACE)                                                                                               \
+	X(paths_buf, ARENA_RESIDENT) /* povu_hip_paths_upload: the paths of the resident graph */                                \
+	/* povu_hip_forest_traversals (trav_kernels.hip): queries and the boundary table / scan tasks / traversals and dedup /   \
+	 * allele steps */                                                                                                       \
+	X(tr_ws, ARENA_WORKSPACE)                                                                                                \
+	X(tr_task, ARENA_WORKSPACE)                                                                                              \
+	X(tr_trav, ARENA_WORKSPACE)                                                                                              \
+	X(tr_steps, ARENA_WORKSPACE)                                                                                             \
+	X(seq_buf, ARENA_RESIDENT) /* povu_hip_segments_upload: the sequences of the resident graph */                           \
+	/* povu_hip_call's workspace and outputs (call_kernels.hip) */                                                           \
+	X(cl_ws, ARENA_WORKSPACE)                                                                                                \
+	X(cl_slot, ARENA_WORKSPACE)                                                                                              \
+	X(cl_rec, ARENA_WORKSPACE)                                                                                               \
+	X(cl_spell, ARENA_WORKSPACE)                                                                                             \
+	X(cl_bytes, ARENA_WORKSPACE)                                                                                             \
+	/* povu_hip_call with POVU_HIP_T_INVERSIONS (inv_kernels.hip): the step index and head counts / the run heads, runs and  \
+	 * records / the rows of the flubble records in the merged list */                                                       \
+	X(iv_ws, ARENA_WORKSPACE)                                                                                                \
+	X(iv_heads, ARENA_WORKSPACE)                                                                                             \
+	X(iv_rows, ARENA_WORKSPACE)                                                                                              \
+	X(nm_ws, ARENA_WORKSPACE) /* left-normalisation (norm_kernels.hip) */                                                    \
+	/* the `decomposed` profile (prim_kernels.hip): the (record, ALT) pairs / the codes of the striped alignments / the      \
+	 * rows */                                                                                                               \
+	X(pr_ws, ARENA_WORKSPACE)                                                                                                \
+	X(pr_slab, ARENA_WORKSPACE)                                                                                              \
+	X(pr_rows, ARENA_WORKSPACE)                                                                                              \
+	/* ... with POVU_HIP_T_MERGE (merge_kernels.hip): the grouping's scratch / the merged rows */                            \
+	X(mg_ws, ARENA_WORKSPACE)                                                                                                \
+	X(mg_rows, ARENA_WORKSPACE)                                                                                              \
+	/* povu_hip_call with POVU_HIP_T_NESTED (nest_kernels.hip): the index of the called sites' traversals / the classes /    \
+	 * the scratch of both / the records' parents, levels and the profile's choice */                                        \
+	X(ns_idx, ARENA_WORKSPACE)                                                                                               \
+	X(ns_cls, ARENA_WORKSPACE)                                                                                               \
+	X(ns_ws, ARENA_WORKSPACE)                                                                                                \
+	X(ns_rec, ARENA_WORKSPACE)                                                                                               \
+	/* povu_hip_call with POVU_HIP_T_OFFREF (offref_kernels.hip): the sites' surrogates and the calling paths / the view of  \
+	 * the calling paths / the inversion records' numbers among them / the host index and offers / the rows' arrays */       \
+	X(or_ws, ARENA_WORKSPACE)                                                                                                \
+	X(or_view, ARENA_WORKSPACE)                                                                                              \
+	X(or_inv, ARENA_WORKSPACE)                                                                                               \
+	X(or_host, ARENA_WORKSPACE)                                                                                              \
+	X(or_rows, ARENA_WORKSPACE)                                                                                              \
+	/* povu_hip_call with POVU_HIP_T_UNTANGLE (untangle_kernels.hip): the lap runs and the slots' cells / the entries and    \
+	 * the task list / the tasks' row counts and offsets / the partner table / the rows' arrays */                           \
+	X(un_ws, ARENA_WORKSPACE)                                                                                                \
+	X(un_task, ARENA_WORKSPACE)                                                                                              \
+	X(un_part, ARENA_WORKSPACE)                                                                                              \
+	X(un_pair, ARENA_WORKSPACE)                                                                                              \
+	X(un_rows, ARENA_WORKSPACE)                                                                                              \
+	/* povu_hip_vcf_check (vcfcheck_kernels.hip): the step index, the uploaded walks, texts and tasks and the results / the  \
+	 * table of (allele, slot) hits */                                                                                       \
+	X(vc_ws, ARENA_WORKSPACE)                                                                                                \
+	X(vc_hit, ARENA_WORKSPACE)                                                                                               \
+	/* the packed shards of the last povu_hip_shard_partition (kept warm: a step of a sharded job re-partitions) */          \
+	X(part_arena, ARENA_RESIDENT)
+
 struct povu_hip_ctx {
 	int device = 0;
 	hipStream_t stream = nullptr;
 	SideStream side; // PCIe-bound result writes run beside the main stream's kernels
 	ResidentGraph g;
 	SubArenas ws_sub; // tables of the inserting passes of -s, one arena per phase (sub_kernels.hpp); kept from one -s pass to the next
-	Arena ws, ws_b, ws2, ws_seq, ws_leaf, ws_walk, upload_tmp; // (ws_b: what the re-index needs beyond the labelling's arrays; // (ws_walk: the wave walk's arrays, taken by the first pass that meets large classes)
+#define POVU_ARENA_MEMBER(name, kind) Arena name;
+	POVU_CTX_ARENAS(POVU_ARENA_MEMBER)
+#undef POVU_ARENA_MEMBER
+	// every device arena of the context in declaration order, the six of ws_sub first (as "ws_sub.<name>", all workspace):
+	// f(name, arena, kind); the name is only good during the call
+	template <class Ctx, class F>
+	static void visit_arenas(Ctx &c, F &&f)
+	{
+		c.ws_sub.for_each_arena([&](const char *n, auto &a) { f((std::string("ws_sub.") + n).c_str(), a, ARENA_WORKSPACE); });
+#define POVU_ARENA_VISIT(name, kind) f(#name, c.name, kind);
+		POVU_CTX_ARENAS(POVU_ARENA_VISIT)
+#undef POVU_ARENA_VISIT
+	}
+	template <class F>
+	void for_each_arena(F &&f) { visit_arenas(*this, f); }
+	template <class F>
+	void for_each_arena(F &&f) const { visit_arenas(*this, f); }
 	HostScratch host;
 	std::shared_ptr<PinnedPool> pool = std::make_shared<PinnedPool>();
 	StageTimer timer;
@@ -274,8 +365,6 @@ struct povu_hip_ctx {
 	// (1-based, ascending = the shard's own component order) and the component count of the whole graph
 	std::vector<uint32_t> shard_comp_ids;
 	uint32_t shard_total_components = 0;
-	Arena shard_buf;   // a shard received from another rank
-	Arena graph_arena; // backs the resident graph
 	// the tail of the last POVU_HIP_F_ASYNC pass (side-stream kernels and copies that read the stage workspace): recorded
 	// behind it; the next pass waits for it before it touches that workspace, every other entry point before anything
 	hipEvent_t tail_done = nullptr;
@@ -295,46 +384,19 @@ struct povu_hip_ctx {
 			wait_tail();
 		}
 	}
-	Arena wk_ws, wk_out; // povu_hip_forest_walks: queries, counts and tier-2 stacks / the walks themselves (walk_kernels.hip)
 	// povu_hip_paths_upload: the paths of the resident graph, one word a step (vertex index << 1 | '<'), and their u64 step
-	// offsets; they belong to upload `paths_gen` (a later graph upload leaves them stale: refused)
-	Arena paths_buf;
+	// offsets (in paths_buf); they belong to upload `paths_gen` (a later graph upload leaves them stale: refused)
 	uint32_t *path_steps = nullptr;
 	uint64_t *path_off = nullptr;
 	uint32_t n_paths = 0;
 	uint64_t n_path_steps = 0, paths_gen = 0;
 	bool paths_valid = false;
-	// povu_hip_forest_traversals (trav_kernels.hip): queries and the boundary table / scan tasks / traversals and dedup /
-	// allele steps
-	Arena tr_ws, tr_task, tr_trav, tr_steps;
-	// povu_hip_segments_upload: the sequences of the resident graph (u64 offsets by vertex index, then the bytes), of upload
-	// `seq_gen`; povu_hip_call's workspace and outputs (call_kernels.hip)
-	Arena seq_buf, cl_ws, cl_slot, cl_rec, cl_spell, cl_bytes;
-	// povu_hip_call with POVU_HIP_T_INVERSIONS (inv_kernels.hip): the step index and head counts / the run heads, runs and
-	// records / the rows of the flubble records in the merged list
-	Arena iv_ws, iv_heads, iv_rows;
-	Arena nm_ws; // left-normalisation (norm_kernels.hip)
-	// the `decomposed` profile (prim_kernels.hip): the (record, ALT) pairs / the codes of the striped alignments / the rows
-	Arena pr_ws, pr_slab, pr_rows;
-	// ... with POVU_HIP_T_MERGE (merge_kernels.hip): the grouping's scratch / the merged rows
-	Arena mg_ws, mg_rows;
-	// povu_hip_call with POVU_HIP_T_NESTED (nest_kernels.hip): the index of the called sites' traversals / the classes / the
-	// scratch of both / the records' parents, levels and the profile's choice
-	Arena ns_idx, ns_cls, ns_ws, ns_rec;
-	// povu_hip_call with POVU_HIP_T_OFFREF (offref_kernels.hip): the sites' surrogates and the calling paths / the view of the
-	// calling paths / the inversion records' numbers among them / the host index and offers / the rows' arrays
-	Arena or_ws, or_view, or_inv, or_host, or_rows;
-	// povu_hip_call with POVU_HIP_T_UNTANGLE (untangle_kernels.hip): the lap runs and the slots' cells / the entries and the
-	// task list / the tasks' row counts and offsets / the partner table / the rows' arrays
-	Arena un_ws, un_task, un_part, un_pair, un_rows;
-	// povu_hip_vcf_check (vcfcheck_kernels.hip): the step index, the uploaded walks, texts and tasks and the results / the
-	// table of (allele, slot) hits
-	Arena vc_ws, vc_hit;
+	// povu_hip_segments_upload: the sequences of the resident graph (u64 offsets by vertex index, then the bytes; in seq_buf), of
+	// upload `seq_gen`
 	uint64_t *seq_off = nullptr;
 	char *seq = nullptr;
 	uint64_t seq_gen = 0;
 	bool seq_valid = false;
-	Arena part_arena;  // the packed shards of the last povu_hip_shard_partition (kept warm: a step of a sharded job re-partitions)
 	// bytes this context moved over PCIe / to peers since it was created (povu_hip_transfer_bytes)
 	uint64_t xfer_h2d = 0, xfer_d2h = 0, xfer_peer_out = 0, xfer_peer_in = 0;
 	// result segments of other ranks, mapped read-only by name (povu_hip_forest_attach); unmapped with the context

@@ -177,33 +177,30 @@ extern "C" int povu_hip_release_workspace(povu_hip_ctx *ctx)
 	ctx->wait_tail();
 	(void)hipStreamSynchronize(ctx->stream);
 	ctx->last.valid = false; // (the debug exports read the stage workspace)
-	ctx->ws.release();
-	ctx->ws_b.release();
-	ctx->ws2.release();
-	ctx->ws_seq.release();
-	ctx->ws_leaf.release();
-	ctx->ws_walk.release();
-	ctx->ws_sub.release();
-	ctx->upload_tmp.release();
-	ctx->tr_ws.release();
-	ctx->tr_task.release();
-	ctx->tr_trav.release();
-	ctx->tr_steps.release();
-	ctx->cl_ws.release();
-	ctx->cl_slot.release();
-	ctx->cl_rec.release();
-	ctx->cl_spell.release();
-	ctx->cl_bytes.release();
-	ctx->iv_ws.release();
-	ctx->iv_heads.release();
-	ctx->iv_rows.release();
-	ctx->nm_ws.release();
-	ctx->un_ws.release();
-	ctx->un_task.release();
-	ctx->un_part.release();
-	ctx->un_pair.release();
-	ctx->un_rows.release();
+	// The two other streams need no call of their own.  The wave walks' stream is joined into the main stream inside the
+	// tree stage (walk_large_classes), so the synchronisation above covers it.  The side stream either joins the main
+	// stream before the pass ends or, in a POVU_HIP_F_ASYNC pass, carries tail_done behind its last copy: wait_tail.
+	ctx->for_each_arena([](const char *, Arena &a, ArenaKind kind) {
+		if (kind == ARENA_WORKSPACE)
+			a.release();
+	});
 	return 0;
+}
+
+extern "C" int povu_hip_arena_report(const povu_hip_ctx *ctx, povu_hip_arena_info *out, int max)
+{
+	if (!ctx)
+		return 0;
+	int n = 0;
+	ctx->for_each_arena([&](const char *name, const Arena &a, ArenaKind kind) {
+		if (out && n < max) {
+			snprintf(out[n].name, sizeof out[n].name, "%s", name);
+			out[n].resident = kind == ARENA_RESIDENT;
+			out[n].bytes = a.capacity();
+		}
+		n++;
+	});
+	return n;
 }
 
 extern "C" void povu_hip_destroy(povu_hip_ctx *ctx)
@@ -213,17 +210,8 @@ extern "C" void povu_hip_destroy(povu_hip_ctx *ctx)
 	(void)hipSetDevice(ctx->device);
 	ctx->wait_tail();
 	free_resident_graph(ctx->g);
-	ctx->ws.release();
-	ctx->ws2.release();
-	ctx->ws_seq.release();
-	ctx->ws_walk.release();
-	ctx->wk_ws.release();
-	ctx->wk_out.release();
-	ctx->ws_b.release();
-	ctx->upload_tmp.release();
-	ctx->shard_buf.release();
-	ctx->graph_arena.release();
-	ctx->part_arena.release();
+	// every arena goes before the streams and events do (hipFree waits for the device, so nothing still reads one)
+	ctx->for_each_arena([](const char *, Arena &a, ArenaKind) { a.release(); });
 	for (auto &kv : ctx->attached)
 		(void)munmap(kv.second.p, kv.second.bytes);
 	if (ctx->stream)

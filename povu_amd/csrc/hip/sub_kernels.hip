@@ -1983,12 +1983,13 @@ SubForest::~SubForest()
 
 void SubArenas::release()
 {
-	for (Arena *a : {&tables, &concealed, &smothered, &xspace, &children, &out})
-		a->release();
+	for_each_arena([](const char *, Arena &a) { a.release(); });
 }
 size_t SubArenas::capacity() const
 {
-	return tables.capacity() + concealed.capacity() + smothered.capacity() + xspace.capacity() + children.capacity() + out.capacity();
+	size_t bytes = 0;
+	for_each_arena([&](const char *, const Arena &a) { bytes += a.capacity(); });
+	return bytes;
 }
 
 void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, const TreeWs &tw, const LeafState &ls, uint32_t C,

@@ -46,8 +46,23 @@ struct SubForest {
 // The device tables of the inserting passes: one arena per phase, carved when the phase's sizes are known (sub_kernels.hip:
 // tables_spans .. out_spans; DESIGN.md §4 lists them).  A context keeps them from one -s pass to the next -- an arena only
 // grows, and every pass carves it anew from offset 0 -- and a pass without -s releases them.
+// The six are declared once, X(name): the list makes the members and for_each_arena.
+#define POVU_SUB_ARENAS(X) X(tables) X(concealed) X(smothered) X(xspace) X(children) X(out)
 struct SubArenas {
-	Arena tables, concealed, smothered, xspace, children, out;
+#define POVU_ARENA_MEMBER(name) Arena name;
+	POVU_SUB_ARENAS(POVU_ARENA_MEMBER)
+#undef POVU_ARENA_MEMBER
+	template <class Self, class F>
+	static void visit_arenas(Self &s, F &&f) // f(name, arena), in declaration order
+	{
+#define POVU_ARENA_VISIT(name) f(#name, s.name);
+		POVU_SUB_ARENAS(POVU_ARENA_VISIT)
+#undef POVU_ARENA_VISIT
+	}
+	template <class F>
+	void for_each_arena(F &&f) { visit_arenas(*this, f); }
+	template <class F>
+	void for_each_arena(F &&f) const { visit_arenas(*this, f); }
 	void release();
 	size_t capacity() const; // bytes held, all six together
 };

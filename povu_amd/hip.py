@@ -189,6 +189,10 @@ class _StageTime(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("ms", C.c_double), ("launches", C.c_uint32)]
 
 
+class _ArenaInfo(C.Structure):
+    _fields_ = [("name", C.c_char * 24), ("resident", C.c_int), ("bytes", C.c_uint64)]
+
+
 F_HAIRPINS = 1
 F_SEQUENTIAL = 2
 F_SEQ_TREE = 4
@@ -333,6 +337,8 @@ def load_lib():
     l.povu_hip_buffer_free.argtypes = [C.c_void_p]
     l.povu_hip_last_stage_times.restype = C.c_int
     l.povu_hip_last_stage_times.argtypes = [C.c_void_p, C.POINTER(_StageTime), C.c_int]
+    l.povu_hip_arena_report.restype = C.c_int
+    l.povu_hip_arena_report.argtypes = [C.c_void_p, C.POINTER(_ArenaInfo), C.c_int]
     l.povu_hip_last_seq_redo.restype = C.c_uint32
     l.povu_hip_last_seq_redo.argtypes = [C.c_void_p]
     l.povu_hip_last_links_processed.restype = C.c_uint64
@@ -1086,10 +1092,18 @@ class HipDecomposer:
         self.close()
 
     def release_workspace(self) -> None:
-        """Gives the stage, query and call workspaces back to the device (povu_hip_release_workspace); the resident graph, paths
-        and sequences stay, and the next call allocates what it needs again."""
+        """Gives every workspace arena back to the device (povu_hip_release_workspace); the resident graph, paths, sequences, a
+        received shard and the packed shards stay, and the next call allocates what it needs again."""
         if self._lib.povu_hip_release_workspace(self._ctx) != 0:
             raise RuntimeError("no context")
+
+    def arenas(self) -> List[dict]:
+        """Every device arena of the context in declaration order: its name, whether release_workspace keeps it, the bytes it
+        holds now (povu_hip_arena_report)."""
+        n = self._lib.povu_hip_arena_report(self._ctx, None, 0)
+        buf = (_ArenaInfo * n)()
+        n = self._lib.povu_hip_arena_report(self._ctx, buf, n)
+        return [dict(name=buf[i].name.decode(), resident=buf[i].resident, bytes=buf[i].bytes) for i in range(n)]
 
     def upload(self, links, tips=None):
         """links: povu_amd.workloads.Links (vertex idx based link arrays)."""
