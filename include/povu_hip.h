@@ -557,6 +557,11 @@ typedef struct {
 	uint64_t n_unt_missing;	      /* reference laps without a partner, over the alignments */
 	uint64_t n_unt_extra;	      /* laps of the other path without a partner, over the alignments */
 	uint64_t n_unt_fallback;      /* (record, slot) entries of two traversals or more that were left to the rule of "Variant calls" */
+	/* of povu_hip_call_restricted with regions ("Region calls").  Without regions: 0 */
+	uint64_t n_regions;	      /* intervals after normalisation (per path sorted, overlapping and touching ones merged) */
+	uint64_t n_region_sites;      /* sites that pass: their S or Z segment is marked */
+	uint64_t n_region_masked;     /* sites whose scans were masked: n_sites - n_region_sites, 0 where masking is not allowed */
+	uint64_t n_region_dropped;    /* flubble records the late filter dropped (0 under masking) */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
@@ -612,6 +617,31 @@ typedef struct {
 povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
 				      const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile,
 				      char *err, size_t errlen);
+/* "Region calls": the call restricted to intervals of resident paths.  A region holds the 1-based positions [start, end) of
+ * path `path` (any resident path, reference or not); a step of that path is in it when its bases meet the interval (a segment
+ * without bases counts as one position); a segment is marked when a step on it is in a region; a site passes when its S or Z
+ * segment is marked, an inversion record when the segment of its first or last step is.  The records are exactly those the
+ * same call without regions writes for the sites and inversion records that pass, every field the same, in the same order.
+ * Where the call is not nested (no POVU_HIP_T_NESTED, no profile that implies it) the sites that do not pass are masked in
+ * front of the traversal pipeline and cost no scan; a nested call computes over every site and selects its records at the
+ * end.  POVU_HIP_REGION_NO_MASK selects at the end in every call (tests).  Refused: a path index that is no resident path,
+ * start >= end, end >= 2^63, more than 65 536 regions, and regions together with POVU_HIP_T_OFFREF. */
+typedef struct {
+	uint32_t path, reserved;
+	uint64_t start, end; /* [start, end), 1-based */
+} povu_hip_region;
+#define POVU_HIP_REGION_NO_MASK 1u /* tests: scan every site, select records at the end only */
+typedef struct {
+	uint32_t n, flags;
+	const povu_hip_region *region;
+} povu_hip_call_regions;
+/* povu_hip_call_profile restricted to `regions` (NULL or n == 0: povu_hip_call_profile itself, byte for byte) */
+povu_hip_calls *povu_hip_call_restricted(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+					 const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile,
+					 const povu_hip_call_regions *regions, char *err, size_t errlen);
+/* `name:start-end` (split at the last ':' and the first '-' behind it, both numbers of digits alone, at most 18; start < end) to
+ * a region of the path named exactly `name` among names[0 .. n_paths).  Host only.  0, or 1 and the refusal in err */
+int povu_hip_region_parse(const char *text, uint32_t n_paths, const char *const *names, povu_hip_region *out, char *err, size_t errlen);
 void povu_hip_calls_free(povu_hip_calls *c);
 
 /*

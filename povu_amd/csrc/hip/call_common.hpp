@@ -105,6 +105,9 @@ struct RefView {
 	const uint64_t *ref_base;		 // [nR + 1] reference index of every reference path's first step
 	const uint64_t *roff;			 // [NR + 1] bases in front of every reference step (one scan over the concatenation)
 };
+// len[i] of every step of the view's concatenated paths: the bases of its segment (call_kernels.hip).  One exclusive u64 scan
+// of it gives roff; the references, the surrogates and the region paths all get their offsets so
+void launch_ref_len(const RefView &R, const PathsView &P, uint64_t *len, hipStream_t s);
 // the genotype slots
 struct SlotsView {
 	uint32_t S, NS;
@@ -283,6 +286,7 @@ struct InvIn {
 	SlotsView slots;
 	uint32_t max_steps = 65536;
 	bool force_tier2 = false;
+	const uint32_t *marked = nullptr; // region calls: bit v set for a marked segment; a run whose two end steps miss it is no record
 };
 // the records found, on the device (the context's inversion arenas, valid until the next call with inversions): per record, in
 // (reference, first, steps) order, its reference number, reference index, steps and POS; per reported run, in (record, slot)

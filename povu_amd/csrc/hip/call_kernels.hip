@@ -26,12 +26,18 @@
 // surrogates, ascending.  Which traversals of a kept site are records is asked of is_record_path (call_common.hpp).
 // With POVU_HIP_T_UNTANGLE (INTEGRATION.md "Untangled calls"; untangle_kernels.hip) one step behind the spelling rewrites the GT
 // rows and counts of the sites a path laps; without the flag it is not run and nothing of it is allocated.
+// With regions (povu_hip_call_restricted; INTEGRATION.md "Region calls"; region_kernels.hip) the front end marks the segments
+// the regions meet and the sites that pass; where the call is not nested the other sites lose their entered sides there, so
+// the traversal pipeline never scans them; flubble_records selects the records of the passing sites in front of the sort
+// (under the mask it drops nothing) and the inversion records are reported against the marks.  The region arrays live in the
+// front end's arena (tr_ws), which nothing carves again before both have read them.
 #include "call_common.hpp"
 #include "merge_kernels.hpp"
 #include "nest_kernels.hpp"
 #include "norm_kernels.hpp"
 #include "offref_kernels.hpp"
 #include "prim_kernels.hpp"
+#include "region_kernels.hpp"
 #include "untangle_kernels.hpp"
 
 namespace povu_hip
@@ -47,6 +53,10 @@ __global__ void k_cl_ref_len(RefView R, PathsView P, uint64_t *__restrict__ len)
 		const uint32_t x = P.steps[P.path_off[R.ref_path[r]] + (i - R.ref_base[r])];
 		len[i] = P.seq_off[(x >> 1) + 1] - P.seq_off[x >> 1];
 	}
+}
+void launch_ref_len(const RefView &R, const PathsView &P, uint64_t *len, hipStream_t s)
+{
+	KLAUNCH(k_cl_ref_len, dim3(stride_blocks(R.NR)), dim3(Q_TPB), 0, s, R, P, len);
 }
 
 // ---- segment -> (site, boundary) CSR
@@ -562,6 +572,7 @@ struct CallWs {
 	std::vector<uint32_t> call_path;
 	OffrefSites os;
 	OffrefHosts oh;
+	RegionDevice rg; // region calls: the marks and the passing sites (rg.pass null: no regions)
 };
 // the inversion records and where the flubble records go in the one list
 struct CallInv {
@@ -882,6 +893,12 @@ void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &
 	} else {
 		launch_iota(nfl_all, w.perm, s);
 	}
+	if (w.rg.pass && w.nfl) { // region calls: the records of the passing sites alone, in front of the sort
+		const uint32_t kept = region_select(ctx, w.v, w.rg.pass, w.perm, w.nfl, w.rflag, w.key, w.perm2, w.words + 4, w.tmp, w.tmp_bytes);
+		w.rg.n_dropped = w.nfl - kept;
+		w.nfl = kept;
+		std::swap(w.perm, w.perm2);
+	}
 	const uint32_t nfl = w.nfl;
 	if (!nfl)
 		return;
@@ -930,6 +947,7 @@ uint32_t inversion_rows(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w
 	iin.paths = w.v.paths, iin.ref = w.refs, iin.slots = w.slots;
 	iin.max_steps = in.opts->max_steps ? in.opts->max_steps : 65536;
 	iin.force_tier2 = (in.opts->flags & POVU_HIP_T_FORCE_TIER2) != 0;
+	iin.marked = w.rg.marked;
 	inv.v = inv_find(ctx, iin);
 	refuse_2_32((uint64_t)nfl + inv.v.n, "the call needs ", "records");
 	if (!inv.v.n)
@@ -1228,6 +1246,7 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	v.n_mrows = mg.n_mrows;
 	v.n_merged_groups = mg.n_groups, v.n_merged_members = mg.n_members, v.n_merge_splits = mg.n_splits;
 	v.n_ref_consistent = mg.n_ref_consistent, v.n_gt_conflicts = mg.n_conflicts;
+	v.n_regions = w.rg.n_regions, v.n_region_sites = w.rg.n_sites, v.n_region_masked = w.rg.n_masked, v.n_region_dropped = w.rg.n_dropped;
 	CallsOwner *raw = o.release();
 	return &raw->view;
 }
@@ -1243,14 +1262,39 @@ extern "C" povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_h
 						 const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
 						 const povu_hip_call_profile_opts *profile, char *err, size_t errlen)
 {
+	return povu_hip_call_restricted(ctx, sites, refs, slot_of_path, opts, profile, nullptr, err, errlen);
+}
+
+extern "C" povu_hip_calls *povu_hip_call_restricted(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+						    const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
+						    const povu_hip_call_profile_opts *profile, const povu_hip_call_regions *regions, char *err,
+						    size_t errlen)
+{
 	CallTimer timer;
 	return guarded_call(ctx, err, errlen, (povu_hip_calls *)nullptr, [&] {
 		const CallInputs in = check_call_inputs(ctx, sites, refs, slot_of_path, opts, profile);
+		if (in.offref && regions && regions->n)
+			throw HipError("regions (povu_hip_call_restricted) are refused together with POVU_HIP_T_OFFREF: an off-reference site has no "
+				       "locus on a region's path");
+		// region calls: masking is allowed when the call is not nested (a nested call computes its classes over every site)
+		const RegionIn rin = region_prepare(ctx, regions, !in.nested);
+		RegionDevice rg;
 		const TravDevice d = trav_pipeline(
 			ctx,
-			[&](CallTimer &tm, const QueryLayout &more) { return query_front(ctx, in.qa, in.qz, in.qor, ctx->tr_ws, tm, more); },
+			[&](CallTimer &tm, const QueryLayout &more) {
+				if (!rin.active)
+					return query_front(ctx, in.qa, in.qz, in.qor, ctx->tr_ws, tm, more);
+				RegionWs rw; // next to the queries, in the front end's arena
+				const QueryFront q = query_front(ctx, in.qa, in.qz, in.qor, ctx->tr_ws, tm, [&](Spans &take, uint32_t n) {
+					more(take, n);
+					region_spans(ctx, rin, n, rw, take);
+				});
+				rg = region_sites(ctx, rin, q, rw);
+				return q;
+			},
 			opts, timer);
 		CallWs w;
+		w.rg = rg;
 		reference_offsets(ctx, in, d, w);
 		callability(ctx, in, d, w);
 		if (in.offref) {

@@ -183,8 +183,11 @@ __global__ __launch_bounds__(Q_TPB) void k_inv_extend_wave(const uint32_t *__res
 }
 
 // ---- reported runs: 2 .. max_steps steps and a base; the longer ones are counted
-__global__ void k_inv_report(uint32_t H, uint32_t max_steps, const uint32_t *__restrict__ hx, const uint32_t *__restrict__ hL,
-			     const uint64_t *__restrict__ roff, uint8_t *__restrict__ flag, unsigned long long *__restrict__ n_long)
+// With `marked` (region calls) a run whose first and last step both lie on unmarked segments is left out: every run of a
+// (reference index, steps) group shares them, so whole groups go, before the records are numbered
+__global__ void k_inv_report(uint32_t H, uint32_t max_steps, InvView A, const uint32_t *__restrict__ marked, const uint32_t *__restrict__ hx,
+			     const uint32_t *__restrict__ hL, const uint64_t *__restrict__ roff, uint8_t *__restrict__ flag,
+			     unsigned long long *__restrict__ n_long)
 {
 	for (uint32_t h = blockIdx.x * Q_TPB + threadIdx.x; h < H; h += gridDim.x * Q_TPB) {
 		const uint32_t L = hL[h];
@@ -193,6 +196,11 @@ __global__ void k_inv_report(uint32_t H, uint32_t max_steps, const uint32_t *__r
 			atomicAdd(n_long, 1ull);
 		else if (L >= 2)
 			keep = roff[(uint64_t)hx[h] + L] > roff[hx[h]];
+		if (keep && marked) {
+			const uint64_t g = ref_step(A, hx[h]).g;
+			const uint32_t a = A.paths.steps[g] >> 1, z = A.paths.steps[g + L - 1] >> 1;
+			keep = ((marked[a >> 5] >> (a & 31)) | (marked[z >> 5] >> (z & 31))) & 1u;
+		}
 		flag[h] = keep;
 	}
 }
@@ -491,7 +499,7 @@ static void records(povu_hip_ctx *ctx, const InvIn &in, const InvView &A, const 
 {
 	hipStream_t s = ctx->stream;
 	const uint32_t H = h.H;
-	KLAUNCH(k_inv_report, dim3(stride_blocks(H)), dim3(Q_TPB), 0, s, H, in.max_steps, h.hx, h.hL, in.ref.roff, h.flag, x.n_long);
+	KLAUNCH(k_inv_report, dim3(stride_blocks(H)), dim3(Q_TPB), 0, s, H, in.max_steps, A, in.marked, h.hx, h.hL, in.ref.roff, h.flag, x.n_long);
 	compact_flagged_u8(h.flag, H, h.rlist, x.words + 3, h.tmp, h.tmp_bytes, s);
 	uint32_t n_runs = 0;
 	unsigned long long h_long = 0;

@@ -32,6 +32,7 @@ struct CallArgs {
 	bool merge = false;	 // --merge-primitives, with --profile decomposed alone (INTEGRATION.md "Merged primitives")
 	bool offref = false;	 // --off-reference: sites no reference path crosses, on a surrogate path (INTEGRATION.md "Off-reference calls")
 	bool untangle = false;	 // --untangle: per-copy genotypes where a path laps a site (INTEGRATION.md "Untangled calls")
+	std::vector<std::string> regions; // --region <name:start-end>, repeatable (INTEGRATION.md "Region calls")
 	povu_hip_call_profile_opts prof{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 };
 
@@ -109,8 +110,19 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			c.prof.max_allele_length = n64;
 		} else if (x == "-c" || x == "--chunk-size" || x == "-q" || x == "--queue-length") {
 			need(i); // (streaming has no meaning here: accepted and ignored)
+		} else if (x == "--region" || !x.compare(0, 9, "--region=")) {
+			c.regions.push_back(x == "--region" ? need(i) : x.substr(9));
+			povu_hip_region r; // (the form alone: the names are not read yet)
+			char err[512] = {0};
+			const std::string &text = c.regions.back();
+			const size_t colon = text.rfind(':');
+			const std::string name = colon == std::string::npos ? std::string() : text.substr(0, colon);
+			const char *one[1] = {name.c_str()};
+			if (povu_hip_region_parse(text.c_str(), 1, one, &r, err, sizeof err) != 0)
+				throw std::runtime_error(std::string("Flag '--region': ") + err);
 		} else if (x == "-g" || x == "--restrict" || !x.compare(0, 11, "--restrict=")) {
-			throw std::runtime_error("--restrict regions are not supported by this build's `call`");
+			throw std::runtime_error("--restrict regions are not supported by this build's `call`: its --region <name:start-end> "
+						 "(repeatable; 1-based start, exclusive end) restricts a call (INTEGRATION.md \"Region calls\")");
 		} else if (x == "--structure-export" || !x.compare(0, 19, "--structure-export=")) {
 			throw std::runtime_error("--structure-export variant frames are not supported by this build's `call`");
 		} else if (!x.empty() && x[0] == '-') {
@@ -128,6 +140,8 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 		throw std::runtime_error("Flag '--off-reference' cannot be combined with --merge-primitives");
 	if (c.offref && c.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
 		throw std::runtime_error("Flag '--off-reference' is called under --profile raw-graph alone");
+	if (!c.regions.empty() && c.offref)
+		throw std::runtime_error("Flag '--region' cannot be combined with --off-reference");
 	if (c.untangle && c.nested)
 		throw std::runtime_error("Flag '--untangle' cannot be combined with --nested");
 	if (c.untangle && c.merge)
@@ -220,6 +234,13 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 	povu_hip_call_names *nm = povu_hip_call_names_make(P, names.data(), (uint32_t)prefixes.size(), prefixes.data(), err, sizeof err);
 	if (!nm)
 		throw std::runtime_error(err);
+	std::vector<povu_hip_region> regions(ca.regions.size());
+	for (size_t k = 0; k < regions.size(); k++)
+		if (povu_hip_region_parse(ca.regions[k].c_str(), P, names.data(), &regions[k], err, sizeof err) != 0) {
+			povu_hip_call_names_free(nm);
+			throw std::runtime_error(std::string("Flag '--region': ") + err);
+		}
+	const povu_hip_call_regions rg{(uint32_t)regions.size(), 0, regions.data()};
 	povu_hip_sites *sites = read_forest(ca.forest_dir);
 
 	povu_hip_ctx *ctx = povu_hip_create(cfg.device, err, sizeof err);
@@ -239,7 +260,7 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 		fail("sequences");
 	const povu_hip_trav_opts opts{0, (ca.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (ca.nested ? POVU_HIP_T_NESTED : 0u) | (ca.merge ? POVU_HIP_T_MERGE : 0u) |
 						 (ca.offref ? POVU_HIP_T_OFFREF : 0u) | (ca.untangle ? POVU_HIP_T_UNTANGLE : 0u)};
-	povu_hip_calls *c = povu_hip_call_profile(ctx, sites, &nm->refs, nm->slot_of_path, &opts, &ca.prof, err, sizeof err);
+	povu_hip_calls *c = povu_hip_call_restricted(ctx, sites, &nm->refs, nm->slot_of_path, &opts, &ca.prof, regions.empty() ? nullptr : &rg, err, sizeof err);
 	if (!c)
 		fail("call");
 

@@ -2,6 +2,7 @@
 // PanSN slots, PVST vertices to sites, and the records of povu_hip_call to VCF text.  The one place that holds these rules
 // for `povu call` and for povu_amd/hip.py alike; tests/vcf_ref.py restates them as the yardstick.
 #include "../../../include/povu_hip.h"
+#include "../hip/region_rules.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -105,6 +106,32 @@ template <class T> bool grow(const T *&p, size_t n)
 }
 
 } // namespace
+
+// `name:start-end` to a region of the path named exactly so (INTEGRATION.md "Region calls"; the reading: region_rules.hpp)
+extern "C" int povu_hip_region_parse(const char *text, uint32_t n_paths, const char *const *names, povu_hip_region *out, char *err, size_t errlen)
+try {
+	if (!text || !out || (n_paths && !names)) {
+		set_err(err, errlen, "region: bad arguments");
+		return 1;
+	}
+	std::string name;
+	uint64_t s = 0, e = 0;
+	const std::string bad = region::parse(text, name, s, e);
+	if (!bad.empty()) {
+		set_err(err, errlen, bad);
+		return 1;
+	}
+	for (uint32_t k = 0; k < n_paths; k++)
+		if (names[k] && name == names[k]) {
+			*out = povu_hip_region{k, 0, s, e};
+			return 0;
+		}
+	set_err(err, errlen, "region '" + std::string(text) + "': no path is named " + name);
+	return 1;
+} catch (const std::exception &x) {
+	set_err(err, errlen, std::string("region: ") + x.what());
+	return 1;
+}
 
 // need_ref: a call's names (no reference path is refused); else the samples and slots alone ("VCF checks")
 static povu_hip_call_names *names_make(uint32_t n_paths, const char *const *path_name, uint32_t n_prefixes, const char *const *prefix,

@@ -133,6 +133,8 @@ class _VcfReport(C.Structure):
 
 OFFREF_COUNTERS = ("n_offref_sites", "n_offref_records", "n_offref_hosted")  # of Calls
 UNTANGLE_COUNTERS = ("n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback")  # of Calls
+REGION_COUNTERS = ("n_regions", "n_region_sites", "n_region_masked", "n_region_dropped")  # of Calls
+REGION_NO_MASK = 1  # povu_hip_call_regions.flags: scan every site, select the records at the end only (tests)
 MERGE_COUNTERS = ("n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts")  # of Calls, beside n_mrows
 
 
@@ -177,7 +179,17 @@ class _CallsNested(_Calls):
                 # "Untangled calls"
                 [("untangled", C.c_uint64), ("rec_unt", C.POINTER(C.c_uint8)), ("lap", C.POINTER(C.c_uint32)),
                  ("n_laps", C.POINTER(C.c_uint32)), ("lap_count", C.POINTER(C.c_uint16))] +
-                [(k, C.c_uint64) for k in UNTANGLE_COUNTERS])
+                [(k, C.c_uint64) for k in UNTANGLE_COUNTERS] +
+                # "Region calls"
+                [(k, C.c_uint64) for k in REGION_COUNTERS])
+
+
+class _Region(C.Structure):
+    _fields_ = [("path", C.c_uint32), ("reserved", C.c_uint32), ("start", C.c_uint64), ("end", C.c_uint64)]
+
+
+class _CallRegions(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("flags", C.c_uint32), ("region", C.POINTER(_Region))]
 
 
 class _ProfileOpts(C.Structure):
@@ -299,6 +311,11 @@ def load_lib():
     l.povu_hip_call_profile.argtypes = [C.c_void_p, C.POINTER(_Sites), C.POINTER(_CallRefs), C.POINTER(C.c_uint32), C.POINTER(_TravOpts),
                                         C.POINTER(_ProfileOpts), C.c_char_p, C.c_size_t]
     l.povu_hip_call_profile.restype = C.POINTER(_CallsNested)
+    l.povu_hip_call_restricted.argtypes = [C.c_void_p, C.POINTER(_Sites), C.POINTER(_CallRefs), C.POINTER(C.c_uint32), C.POINTER(_TravOpts),
+                                           C.POINTER(_ProfileOpts), C.POINTER(_CallRegions), C.c_char_p, C.c_size_t]
+    l.povu_hip_call_restricted.restype = C.POINTER(_CallsNested)
+    l.povu_hip_region_parse.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(_Region), C.c_char_p, C.c_size_t]
+    l.povu_hip_region_parse.restype = C.c_int
     l.povu_hip_calls_vcf_profile.argtypes = [C.POINTER(_CallsNested), C.POINTER(_Sites), C.POINTER(_CallNames), C.POINTER(C.c_char_p),
                                              C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
     l.povu_hip_calls_vcf_profile.restype = C.c_void_p
@@ -939,6 +956,10 @@ class Calls:
         self.lap_count = _view(c.lap_count, k * self.n_slots, np.uint16).reshape(k, self.n_slots)
         for k in UNTANGLE_COUNTERS:
             setattr(self, k, int(getattr(c, k)))
+        # "Region calls" (regions=...): the intervals after normalisation, the sites that pass, the sites whose scans were masked,
+        # the flubble records the late filter dropped.  Without regions: 0
+        for k in REGION_COUNTERS:
+            setattr(self, k, int(getattr(c, k)))
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -1267,7 +1288,7 @@ class HipDecomposer:
             raise RuntimeError(err.value.decode())
 
     def call(self, forest: Forest, refs, max_steps: int = 65536, flags: int = 0, profile=None, max_level: int = 0,
-             max_ref_length: int = 0, max_allele_length: int = 0) -> Calls:
+             max_ref_length: int = 0, max_allele_length: int = 0, regions=None, region_no_mask: bool = False) -> Calls:
         """The variant calls of `forest` (INTEGRATION.md "Variant calls") with the resident paths whose names start with one
         of the prefixes `refs` as references, on the GPU (paths and sequences uploaded first).  flags: T_FORCE_TIER2,
         T_INVERSIONS (the SUBR records of "Inversion calls" merged in: Calls.n_steps, flags & CALL_SUBR, the n_inv_* counters),
@@ -1285,7 +1306,11 @@ class HipDecomposer:
         counters.  T_UNTANGLE ("Untangled calls", raw-graph alone, refused with T_NESTED, T_MERGE and T_OFFREF): where a path
         walks a site more than once its laps are aligned with the reference's and every record takes the allele of the lap
         aligned with its own; Calls.untangled, rec_unt, lap, n_laps, lap_count, the UNTANGLE_COUNTERS, and vcf_text writes
-        LN, LC and GT:CN."""
+        LN, LC and GT:CN.  regions ("Region calls", refused with T_OFFREF): strings "name:start-end" or tuples (name, start, end),
+        the 1-based bases [start, end) of the resident path named exactly so; the records are those of the same call without
+        regions for the sites with a boundary segment, and the inversions with an end step, that a region meets; the
+        REGION_COUNTERS.  A call that is not nested masks the other sites in front of its scans; region_no_mask makes it scan
+        every site and select the records at the end, as a nested call does (tests)."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names
@@ -1301,14 +1326,39 @@ class HipDecomposer:
             sites = forest.sites()
             o = _TravOpts(max_steps, flags)
             po = _ProfileOpts(PROFILES[profile or "raw-graph"], max_level, max_ref_length, max_allele_length)
-            p = self._lib.povu_hip_call_profile(self._ctx, sites._p, C.byref(nr.contents.refs), nr.contents.slot_of_path, C.byref(o),
-                                                C.byref(po) if profile is not None else None, err, 512)
+            rg = self._regions(regions, names, name_array, region_no_mask)
+            p = self._lib.povu_hip_call_restricted(self._ctx, sites._p, C.byref(nr.contents.refs), nr.contents.slot_of_path, C.byref(o),
+                                                   C.byref(po) if profile is not None else None, rg, err, 512)
             if not p:
                 raise RuntimeError(err.value.decode())
         except Exception:
             self._lib.povu_hip_call_names_free(nr)
             raise
         return Calls(self._lib, p, names, nr, name_array, sites, profile or "raw-graph")
+
+    def _regions(self, regions, names, name_array, no_mask):
+        """povu_hip_call_regions of `regions` (None for none): a string goes through povu_hip_region_parse, a tuple's name is
+        looked up exactly."""
+        if not regions:
+            return None
+        if isinstance(regions, (str, tuple)):
+            regions = [regions]
+        arr = (_Region * len(regions))()
+        for k, r in enumerate(regions):
+            if isinstance(r, str):
+                err = C.create_string_buffer(512)
+                if self._lib.povu_hip_region_parse(r.encode(), len(names), name_array, C.byref(arr[k]), err, 512) != 0:
+                    raise RuntimeError(err.value.decode())
+            else:
+                name, start, end = r
+                if name not in names:
+                    raise RuntimeError(f"region '{name}:{start}-{end}': no path is named {name}")
+                if not (0 <= int(start) < 2 ** 64 and 0 <= int(end) < 2 ** 64):
+                    raise RuntimeError(f"region '{name}:{start}-{end}': start and end must be in [0, 2^64)")
+                arr[k] = _Region(names.index(name), 0, int(start), int(end))
+        rg = _CallRegions(len(regions), REGION_NO_MASK if no_mask else 0, arr)
+        rg._keep = arr
+        return C.byref(rg)
 
     def check_vcf(self, text, forward_only: bool = False, spelling: bool = False, force_tier2: bool = False, threads: int = 1) -> VcfReport:
         """Does the VCF `text` (or a VcfDoc of parse_vcf) still describe the graph (INTEGRATION.md "VCF checks")?  For every

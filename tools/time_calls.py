@@ -20,7 +20,9 @@ limits --max-length), normalized (profile `left-normalized`), decomposed (profil
 equal primitives merged; its time less that of decomposed is the merging step's) and decomposed-tier2 (decomposed with
 T_FORCE_TIER2: every aligned pair through the striped kernel, for the cells per second of that tier; asked for by name
 only), offref (T_OFFREF: the sites no reference path crosses too; its time less that of plain is the step's) and untangled
-(T_UNTANGLE: the laps of every haplotype aligned with the reference's; its time less that of plain is the step's); without --modes those the input was made for.  One JSON line
+(T_UNTANGLE: the laps of every haplotype aligned with the reference's; its time less that of plain is the step's) and region
+(asked for by name only: the plain call restricted to the middle 1 % of the first reference path's bases, INTEGRATION.md "Region
+calls"; the sites outside lose their scans); without --modes those the input was made for.  One JSON line
 per mode and run: HIP-event time of the call (query upload to the last byte on the host), records, spelled bytes, the
 counters of the mode; then per mode a line with the median of the runs behind the warm-up runs.
 
@@ -42,7 +44,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2", "offref", "untangled")
+MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2", "offref", "untangled", "region")
 DEFAULT_MODES = dict(chain=("plain",), inverted=("plain", "inversions"), skip=("plain", "nested", "popped"), tandem=("plain", "normalized"),
                      complex=("plain", "decomposed", "merged"), insertions=("plain", "offref"), looped=("plain", "untangled"))
 
@@ -95,6 +97,17 @@ def workload(W, name, size):
     return g, W.tandem_haplotypes(units, 1, 8), seqs, "hap0#"
 
 
+def middle_region(g, p, seqs, ref):
+    """(name, start, end): the middle 1 % of the bases of the first path whose name starts with `ref`."""
+    import numpy as np
+    k = next(i for i, n in enumerate(p.names) if n.startswith(ref))
+    lens = np.array([len(s) for s in seqs], dtype=np.int64)
+    ids = np.asarray(p.ids[int(p.off[k]):int(p.off[k + 1])])
+    total = int(lens[np.searchsorted(np.asarray(g.vid), ids)].sum())
+    start = 1 + (total * 99) // 200
+    return p.names[k], start, max(start + 1, start + total // 100)
+
+
 def child(a):
     HipDecomposer, H, W = _load(a.package_root)
     t0 = time.perf_counter()
@@ -109,11 +122,13 @@ def child(a):
               popped=lambda: dict(profile="popped", max_level=0, max_ref_length=a.max_length, max_allele_length=a.max_length),
               normalized=lambda: dict(profile="left-normalized"), decomposed=lambda: dict(profile="decomposed"),
               merged=lambda: dict(profile="decomposed", flags=H.T_MERGE), offref=lambda: dict(flags=H.T_OFFREF), untangled=lambda: dict(flags=H.T_UNTANGLE),
+              region=lambda: dict(regions=[middle_region(g, p, seqs, ref)]),
               **{"decomposed-tier2": lambda: dict(profile="decomposed", flags=H.T_FORCE_TIER2)})[a.child]()
     counters = ("n_inv_records", "n_inv_tier2", "n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "n_normalized", "max_shift",
                 "n_norm_compared", "n_rows", "n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells", "n_mrows",
                 "n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts", "n_offref_sites", "n_offref_records", "n_offref_hosted",
-                "n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback")
+                "n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback", "n_regions", "n_region_sites", "n_region_masked",
+                "n_region_dropped")
     for run in range(a.warmup + a.runs):
         t0 = time.perf_counter()
         c = d.call(f, [ref], **kw)
