@@ -863,6 +863,11 @@ int povu_hip_last_black_only_classes(const povu_hip_ctx *ctx);
  * the brackets (no side of the graph has more than 253 links, and POVU_HIP_WIDE_COUNTS=1 is not set in the environment), 0
  * when the word kernels ran.  The bits say which counts were bytes: 1 ordcnt (always set then), 2 srccnt, 4 incnt */
 int povu_hip_last_narrow_counts(const povu_hip_ctx *ctx);
+/* Which prefix sums the class stage of the last pass read as packed count records (one 16-byte record per twelve byte
+ * counts) instead of words: bit 0 = the sums of the in-counts (psin), bit 1 = the range starts of the
+ * bracket lists.  Records are taken exactly where the matching count is a byte (povu_hip_last_narrow_counts bits 2 / 1),
+ * unless POVU_HIP_WORD_PREFIX in the environment (read per pass) says words: 1 = both, 2 = psin, 3 = the range starts. */
+int povu_hip_last_prefix_records(const povu_hip_ctx *ctx);
 /* passes of this context, since it was created, that ran their tree and class stages a second time with word counts
  * because a byte of incnt would have passed 255 (capping brackets that share one target); such a pass reports 0 above */
 uint64_t povu_hip_wide_repeats(const povu_hip_ctx *ctx);
@@ -929,6 +934,8 @@ int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t
 #define POVU_HIP_SCAN_MIXED_PAIR 8
 /* op 9: sums of in[i] - in2[i] with `in` and in2 both n BYTES (scan_exclusive_diff_u8_u8; out2 unused) */
 #define POVU_HIP_SCAN_DIFF_U8_U8 9
+/* op 10: INCLUSIVE sums of the n words of `in` (scan_inclusive_u32; in2 unused) */
+#define POVU_HIP_SCAN_INCLUSIVE 10
 #define POVU_HIP_SCAN_IN_PLACE 0x100
 #define POVU_HIP_SCAN_N_DEV 0x200
 int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,
@@ -964,6 +971,16 @@ int povu_hip_debug_segtree(povu_hip_ctx *ctx, const uint32_t *val, size_t n, con
  * 32..63, set flags in front, 0), the last one the closing record. */
 int povu_hip_debug_bitrank(povu_hip_ctx *ctx, const uint8_t *flags, size_t n, const uint32_t *pos, size_t nq, uint32_t *rank,
 			   uint32_t *test, uint32_t *records);
+/* Count records (common.hpp): scan_count_records_u8 over the n0 BYTES of in0 and, in the same launch, the n1 bytes of in1
+ * (in1 may be NULL, either length may be 0), then one lane per query.  A record is four words: the counts of twelve
+ * consecutive elements as bytes (words 0..2; zero behind the end of the array) and the sum of every count in front of
+ * them (word 3).  rec0 / rec1 (optional): the (n + 11) / 12 records that hold an element; the slack record behind them
+ * must come back unwritten (else 5).  prefix[i] = cntrec_prefix(pos[i]) = the sum in front of element pos[i], count[i] =
+ * cntrec_count(pos[i]) = that element; pos[i] >= n is refused (1).  tile (optional, filled whatever else happens):
+ * elements a tile of the scan's two-launch form / of its one-launch form covers. */
+int povu_hip_debug_count_records(povu_hip_ctx *ctx, const uint8_t *in0, size_t n0, const uint32_t *pos0, size_t nq0, uint32_t *rec0,
+				 uint32_t *prefix0, uint32_t *count0, const uint8_t *in1, size_t n1, const uint32_t *pos1, size_t nq1,
+				 uint32_t *rec1, uint32_t *prefix1, uint32_t *count1, uint64_t tile[2]);
 /* append_in_order: workgroups of 256 lanes, each over 16 384 positions of flags[0..n), append their set positions to
  * list (room for n); *count = the length.  A workgroup's positions form one ascending stretch; the order of the
  * stretches is up to the atomics.  The device list behind the first *count entries counts as a guard band. */

@@ -408,6 +408,14 @@ void scan_exclusive_u32_u8_pair(const uint32_t *in0, uint32_t *out0, size_t n0, 
 // (n_dev, device memory, optional: only the first *n_dev + 1 words exist -- n then is the most there can be and sizes the launch)
 void scan_exclusive_xor_u128(const ulonglong2 *in, ulonglong2 *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s,
 			     const uint32_t *n_dev = nullptr);
+// inclusive prefix sums of words (out[i] = in[0] + ... + in[i])
+void scan_inclusive_u32(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s);
+// exclusive sums of BYTE inputs as packed count records (cntrec_prefix below): rec0 / rec1 take cntrec_records(n0 / n1)
+// records; one job, or two independent ones in the same launches (in1 may be null)
+void scan_count_records_u8(const uint8_t *in0, uint4 *rec0, size_t n0, const uint8_t *in1, uint4 *rec1, size_t n1, void *tmp,
+			   size_t tmp_bytes, hipStream_t s);
+// elements a tile of that scan covers: of its two-launch form / of its one-launch (look-back) form
+void scan_count_records_tiles(size_t *chunk_tile, size_t *lookback_tile);
 size_t scan_tmp_bytes(size_t n);
 // exclusive sums of u64 (in == out allowed); tmp holds scan_exclusive_u64_tmp(n) WORDS of 8 bytes
 void scan_exclusive_u64(const uint64_t *in, uint64_t *out, size_t n, uint64_t *tmp, hipStream_t s);
@@ -529,6 +537,50 @@ __device__ __forceinline__ bool bitrank_test(const uint4 *__restrict__ rec, uint
 	const uint4 r = rec[x >> 6];
 	return (((x & 32u) ? r.y : r.x) >> (x & 31u)) & 1u;
 }
+// ---- count records: the same idea for small COUNTS.  One 16-byte record per CNTREC_N = 12 byte counts = {counts 0..3,
+// counts 4..7, counts 8..11, sum of every count in front of the record}: "sum of the counts in front of element i" is ONE
+// 16-byte load, a mask and three byte sums, and the table is 1.33 bytes an element where the word prefix sums were 4.
+// scan_count_records_u8 writes it from the byte array (which stays).  The count bytes of the last record that lie behind
+// the array's end are zero; the array carries one record of slack (never written, never read for i < n).
+static constexpr uint32_t CNTREC_N = 12;
+inline size_t cntrec_records(size_t n) { return (n + CNTREC_N - 1) / CNTREC_N + 1; }
+// the sum of the four bytes of x, added to acc (v_sad_u8 against zero)
+__device__ __forceinline__ uint32_t cntrec_bytesum(uint32_t x, uint32_t acc) { return __builtin_amdgcn_sad_u8(x, 0u, acc); }
+// the record of element i, and i's place k in it (i / 12 by a multiply-high: 0xAAAAAAAB = ceil(2^35 / 12), exact for 32 bits)
+__device__ __forceinline__ uint4 cntrec_load(const uint4 *__restrict__ rec, uint32_t i, uint32_t &k)
+{
+	const uint32_t r = __umulhi(i, 0xAAAAAAABu) >> 3;
+	k = i - CNTREC_N * r;
+	return rec[r];
+}
+// the low k bytes of a word (k >= 4: all of it; k <= 0: none)
+__device__ __forceinline__ uint32_t cntrec_low_bytes(uint32_t x, int k) { return k >= 4 ? x : k <= 0 ? 0u : x & ((1u << (8 * k)) - 1u); }
+__device__ __forceinline__ uint32_t cntrec_prefix(const uint4 *__restrict__ rec, uint32_t i)
+{
+	uint32_t k;
+	const uint4 r = cntrec_load(rec, i, k);
+	const int kk = (int)k;
+	return cntrec_bytesum(cntrec_low_bytes(r.z, kk - 8), cntrec_bytesum(cntrec_low_bytes(r.y, kk - 4), cntrec_bytesum(cntrec_low_bytes(r.x, kk), r.w)));
+}
+__device__ __forceinline__ uint32_t cntrec_count(const uint4 *__restrict__ rec, uint32_t i)
+{
+	uint32_t k;
+	const uint4 r = cntrec_load(rec, i, k);
+	const uint32_t w = k < 4 ? r.x : k < 8 ? r.y : r.z;
+	return (w >> (8 * (k & 3u))) & 0xFFu;
+}
+// How a kernel reads a prefix-sum array: the words themselves, or count records.  at(i) = the sum in front of element i,
+// count(i) = element i itself (words: two gathers; records: the same record again).
+struct PrefixWords {
+	const uint32_t *__restrict__ p;
+	__device__ __forceinline__ uint32_t at(uint32_t i) const { return p[i]; }
+	__device__ __forceinline__ uint32_t count(uint32_t i) const { return p[i + 1] - p[i]; }
+};
+struct PrefixRecords {
+	const uint4 *__restrict__ p;
+	__device__ __forceinline__ uint32_t at(uint32_t i) const { return cntrec_prefix(p, i); }
+	__device__ __forceinline__ uint32_t count(uint32_t i) const { return cntrec_count(p, i); }
+};
 // Component of a candidate-stack entry, looked up instead of stored (a word per entry was 0.4 GB written and as much read
 // by every consumer).  Entry i belongs to the last non-empty component that starts at or before i: `rec` is a bit-rank
 // directory over the stack positions with a bit where a non-empty component starts, `list` those components in order.

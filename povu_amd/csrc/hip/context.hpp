@@ -246,6 +246,7 @@ struct LastPass {
 	// the parallel stages kept the bracket counts per tree vertex (ordcnt / srccnt, see ParWs) as bytes
 	bool narrow_counts = false;
 	int narrow_forms = 0; // which of them: bit 0 ordcnt, bit 1 srccnt, bit 2 incnt
+	int prefix_records = 0; // the class stage read count records for: bit 0 psin, bit 1 the bracket range starts
 };
 
 // Every device arena of a context besides the six of SubArenas, declared once: X(name, kind).  The list makes the members

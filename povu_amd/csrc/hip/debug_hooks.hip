@@ -118,8 +118,9 @@ const DbgScanOp DBG_SCAN_OPS[] = {
 	{1, 4, 4, DBG_SUB, true, false, false, false, false},	  // POVU_HIP_SCAN_DIFF_U8
 	{4, 1, 4, DBG_PAIR, true, true, false, false, false},	  // POVU_HIP_SCAN_MIXED_PAIR
 	{1, 1, 4, DBG_SUB, true, false, false, false, false},	  // POVU_HIP_SCAN_DIFF_U8_U8
+	{4, 4, 4, DBG_NONE, false, false, true, false, false},	  // POVU_HIP_SCAN_INCLUSIVE
 };
-static_assert(sizeof(DBG_SCAN_OPS) / sizeof(DBG_SCAN_OPS[0]) == POVU_HIP_SCAN_DIFF_U8_U8 + 1, "one row per op");
+static_assert(sizeof(DBG_SCAN_OPS) / sizeof(DBG_SCAN_OPS[0]) == POVU_HIP_SCAN_INCLUSIVE + 1, "one row per op");
 } // namespace
 
 extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in, uint32_t *out, size_t n, const uint32_t *in2,
@@ -127,7 +128,7 @@ extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in
 {
 	const int kind = op & 0xFF;
 	const bool in_place = (op & POVU_HIP_SCAN_IN_PLACE) != 0, with_len = (op & POVU_HIP_SCAN_N_DEV) != 0;
-	if (!ctx || kind > POVU_HIP_SCAN_DIFF_U8_U8 || (op & ~(0xFF | POVU_HIP_SCAN_IN_PLACE | POVU_HIP_SCAN_N_DEV)))
+	if (!ctx || kind > POVU_HIP_SCAN_INCLUSIVE || (op & ~(0xFF | POVU_HIP_SCAN_IN_PLACE | POVU_HIP_SCAN_N_DEV)))
 		return 1;
 	const DbgScanOp &T = DBG_SCAN_OPS[kind];
 	if (T.nullable ? ((n && (!in || !out)) || (in2 && n2 && !out2)) : (!in || !out || (in2 && !out2 && T.second != DBG_SUB)))
@@ -164,6 +165,7 @@ extern "C" int povu_hip_debug_scan(povu_hip_ctx *ctx, int op, const uint32_t *in
 				scan_exclusive_u32(w1, o1.data<uint32_t>(), n, tmp, tb, s);
 			break;
 		case POVU_HIP_SCAN_MAX: scan_exclusive_max_u32(w1, o1.data<uint32_t>(), n, tmp, tb, s); break;
+		case POVU_HIP_SCAN_INCLUSIVE: scan_inclusive_u32(w1, o1.data<uint32_t>(), n, tmp, tb, s); break;
 		case POVU_HIP_SCAN_U64: // n u64 values, each a pair of words
 			scan_exclusive_u64(reinterpret_cast<const uint64_t *>(di), o1.data<uint64_t>(), n, static_cast<uint64_t *>(tmp), s);
 			break;
@@ -309,6 +311,14 @@ __global__ void __launch_bounds__(256) k_dbg_bitrank_query(uint32_t n, const uin
 			test[i] = bitrank_test(rec, p) ? 1u : 0u;
 	}
 }
+__global__ void __launch_bounds__(256) k_dbg_cntrec_query(const uint4 *__restrict__ rec, uint32_t nq, const uint32_t *__restrict__ x,
+							  uint32_t *__restrict__ prefix, uint32_t *__restrict__ count)
+{
+	for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nq; i += gridDim.x * blockDim.x) {
+		prefix[i] = cntrec_prefix(rec, x[i]);
+		count[i] = cntrec_count(rec, x[i]);
+	}
+}
 // the shape of k_entry_list (tree_kernels.hip): a workgroup of LIST_TPB lanes over LIST_SPAN positions, bit 4 it + j of fw =
 // position B0 + 1024 it + 4 tid + j
 __global__ void __launch_bounds__(LIST_TPB) k_dbg_append(uint32_t n, const uint8_t *__restrict__ flags, uint32_t *__restrict__ list,
@@ -413,6 +423,67 @@ extern "C" int povu_hip_debug_bitrank(povu_hip_ctx *ctx, const uint8_t *flags, s
 			HIP_CHECK(copy_async(records, orec.data<char>(), (n_rec + 1) * 16, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
 		return dbg_guards_intact(orec, s) && dbg_guards_intact(ocnt, s) && dbg_guards_intact(ork, s) && dbg_guards_intact(ots, s) ? 0 : DBG_RC_GUARD;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
+extern "C" int povu_hip_debug_count_records(povu_hip_ctx *ctx, const uint8_t *in0, size_t n0, const uint32_t *pos0, size_t nq0, uint32_t *rec0,
+					    uint32_t *prefix0, uint32_t *count0, const uint8_t *in1, size_t n1, const uint32_t *pos1, size_t nq1,
+					    uint32_t *rec1, uint32_t *prefix1, uint32_t *count1, uint64_t tile[2])
+{
+	if (tile) {
+		size_t a = 0, b = 0;
+		scan_count_records_tiles(&a, &b);
+		tile[0] = a, tile[1] = b;
+	}
+	const uint8_t *in[2] = {in0, in1};
+	const size_t n[2] = {n0, in1 ? n1 : 0}, nq[2] = {nq0, in1 ? nq1 : 0};
+	const uint32_t *pos[2] = {pos0, pos1};
+	uint32_t *rec[2] = {rec0, rec1}, *prefix[2] = {prefix0, prefix1}, *count[2] = {count0, count1};
+	if (!ctx)
+		return 1;
+	for (int j = 0; j < 2; j++) {
+		if (n[j] > DBG_LOOKUP_MAX_N || nq[j] >= (size_t(1) << 32) || (n[j] && !in[j]) || (nq[j] && (!pos[j] || !prefix[j] || !count[j])))
+			return 1;
+		for (size_t i = 0; i < nq[j]; i++) // (what the word form can be asked for: [0, n))
+			if (pos[j][i] >= n[j])
+				return 1;
+	}
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		hipStream_t s = ctx->stream;
+		// the records that hold an element; the slack record behind them stays as it was (poison)
+		const size_t nr[2] = {cntrec_records(n[0]) - 1, cntrec_records(n[1]) - 1}, tb = scan_tmp_bytes(std::max(n[0], n[1]));
+		Arena ar;
+		DbgOut orec[2] = {{(nr[0] + 1) * 16, DBG_POISON_BYTE}, {(nr[1] + 1) * 16, DBG_POISON_BYTE}};
+		DbgOut opre[2] = {{nq[0] * 4}, {nq[1] * 4}}, ocnt[2] = {{nq[0] * 4}, {nq[1] * 4}};
+		DbgScratch tmp{tb};
+		DbgIn<uint8_t> di[2] = {{in[0], n[0]}, {in[1], n[1]}};
+		DbgIn<uint32_t> dp[2] = {{pos[0], nq[0]}, {pos[1], nq[1]}};
+		dbg_carve(ar, s, orec[0], orec[1], opre[0], opre[1], ocnt[0], ocnt[1], tmp, di[0], di[1], dp[0], dp[1]);
+		scan_count_records_u8(di[0].dev, orec[0].data<uint4>(), n[0], in1 ? di[1].dev : nullptr, orec[1].data<uint4>(), n[1], tmp.p, tb, s);
+		for (int j = 0; j < 2; j++) {
+			if (nq[j]) {
+				KLAUNCH(k_dbg_cntrec_query, dim3(dbg_query_blocks(nq[j])), dim3(256), 0, s, orec[j].data<uint4>(), (uint32_t)nq[j], dp[j].dev,
+					opre[j].data<uint32_t>(), ocnt[j].data<uint32_t>());
+				HIP_CHECK(copy_async(prefix[j], opre[j].data<char>(), nq[j] * 4, hipMemcpyDeviceToHost, s));
+				HIP_CHECK(copy_async(count[j], ocnt[j].data<char>(), nq[j] * 4, hipMemcpyDeviceToHost, s));
+			}
+			if (rec[j] && nr[j])
+				HIP_CHECK(copy_async(rec[j], orec[j].data<char>(), nr[j] * 16, hipMemcpyDeviceToHost, s));
+		}
+		std::vector<unsigned char> slack(32);
+		for (int j = 0; j < 2; j++)
+			HIP_CHECK(copy_async(slack.data() + 16 * j, orec[j].data<char>() + nr[j] * 16, 16, hipMemcpyDeviceToHost, s));
+		HIP_CHECK(hipStreamSynchronize(s));
+		for (unsigned char c : slack) // (nothing is written behind the last record that holds an element)
+			if (c != (unsigned char)DBG_POISON_BYTE)
+				return DBG_RC_GUARD;
+		for (int j = 0; j < 2; j++)
+			if (!dbg_guards_intact(orec[j], s) || !dbg_guards_intact(opre[j], s) || !dbg_guards_intact(ocnt[j], s))
+				return DBG_RC_GUARD;
+		return 0;
 	} catch (const std::exception &) {
 		return 2;
 	}

@@ -471,24 +471,26 @@ __global__ void k_bracket_order(uint32_t NB, uint32_t NB0, uint32_t ncap, uint32
 // With the per-source rank of every ordinary edge known (parallel tree stage), the list order needs no
 // sort: a bracket's position = (first bracket of its source's mirror pre-order position) + its rank
 // inside the source (simplifying, capping, ordinary edges top first).
+// BS: how the range starts are read (PrefixWords / PrefixRecords, common.hpp)
+template <class BS>
 __global__ void k_bracket_place(uint32_t NB, uint32_t NB0, uint32_t ncap, const uint32_t *__restrict__ b_src,
 				const uint32_t *__restrict__ b_tgt, const uint32_t *__restrict__ b_ord,
-				const uint32_t *__restrict__ mpre, const uint32_t *__restrict__ bstart,
+				const uint32_t *__restrict__ mpre, const BS bstart,
 				const uint8_t *__restrict__ capf, const uint8_t *__restrict__ simp,
 				uint32_t *__restrict__ tgtR, uint32_t *__restrict__ rid)
 {
 	uint32_t j = BIDX * blockDim.x + threadIdx.x;
 	if (j >= NB)
 		return;
-	const uint32_t v = b_src[j];
+	const uint32_t v = b_src[j], m = mpre[v];
 	uint32_t rank;
 	if (j < NB0) // b_ord counts from the bottom of the source's ordinary edges; the list has the later pushed on top
-		rank = bstart[mpre[v] + 1] - bstart[mpre[v]] - 1 - b_ord[j];
+		rank = bstart.count(m) - 1 - b_ord[j];
 	else if (j < NB0 + ncap)
 		rank = simp[v];
 	else
 		rank = 0;
-	const uint32_t pos = bstart[mpre[v]] + rank;
+	const uint32_t pos = bstart.at(m) + rank;
 	tgtR[pos] = b_tgt[j];
 	if (rid) // (which bracket sits at a list position: only the hairpin report asks, k_top_bracket)
 		rid[pos] = j;
@@ -507,17 +509,18 @@ __global__ void k_gather_u32(uint32_t n, const uint32_t *__restrict__ idx, const
 // stable sort by top bracket leaves every group ordered from the deepest vertex up.
 // where the candidate-stack entry of a black vertex goes (row E worked out before the class pass)
 struct StackPlace {
-	const uint32_t *voff, *soff, *dlt, *dlt_ps;
+	const uint32_t *voff, *soff, *shift; // shift: the INCLUSIVE sums of row E's differences (one stream, not the exclusive sums and the differences)
 	uint32_t *s_vtx;
 };
 // BLACK: only the child ends of black tree edges take part (n = V of them: segment slot g of component c is tree
 // vertex 2g + c + [dummy root] + 1, the opposite side follows the entered side in pre-order) -- the candidate stack
 // holds no other edge, see run_parallel_dg for when that is enough.
-template <bool BLACK>
+// PS / BS: how psin and the range starts are read, each on its own (PrefixWords / PrefixRecords, common.hpp).
+template <bool BLACK, class PS, class BS>
 __global__ void k_top_bracket(uint32_t n, const uint32_t *__restrict__ gsize, const uint32_t *__restrict__ gpar,
-			      const uint32_t *__restrict__ mpre, const uint32_t *__restrict__ bstart,
+			      const uint32_t *__restrict__ mpre, const BS bstart,
 			      const SegTree segB, const uint32_t *__restrict__ tgtR,
-			      const uint32_t *__restrict__ psin, uint32_t *__restrict__ ckey, uint32_t *__restrict__ cval,
+			      const PS psin, uint32_t *__restrict__ ckey, uint32_t *__restrict__ cval,
 			      uint32_t *__restrict__ lsz, uint32_t *__restrict__ err, const uint32_t *__restrict__ rid,
 			      uint32_t first_simp_id, uint8_t *__restrict__ hpf, const uint32_t *__restrict__ seg_comp,
 			      const uint32_t *__restrict__ c_ntree, const StackPlace sp)
@@ -543,17 +546,17 @@ __global__ void k_top_bracket(uint32_t n, const uint32_t *__restrict__ gsize, co
 	// entry itself (its tree vertex) is written here; lsz is indexed by stack position too
 	uint32_t at = v;
 	if (BLACK) {
-		at = sp.soff[c] + (g - sp.voff[c]) + sp.dlt_ps[g] + sp.dlt[g];
+		at = sp.soff[c] + (g - sp.voff[c]) + sp.shift[g];
 		sp.s_vtx[at] = v; // (its component is looked up where it is needed: StackComp)
 	}
 	cval[q] = at;
 	uint32_t m = mpre[v];
-	uint32_t lo = bstart[m], hi = bstart[m + sz];
+	uint32_t lo = bstart.at(m), hi = bstart.at(m + sz);
 	// Number of live brackets first (two prefix sums): in a chain of bubbles the brackets of everything below v are closed
 	// inside their bubbles and the few live ones -- a simplifying edge, a tip's edge to the root -- come from the
 	// deepest sources, i.e. sit at the END of the range.  When the last `live` entries are all live they are THE live
 	// ones, and the top bracket is the first of them: no search at all.
-	const uint32_t live = (hi - lo) - (psin[v + sz] - psin[v]);
+	const uint32_t live = (hi - lo) - (psin.at(v + sz) - psin.at(v));
 	uint32_t i = NIL;
 	if (live >= 1 && live <= 4) { // (the four words in one 16-byte load; the array carries slack behind its last entry)
 		const uint4 a = load4_unaligned(tgtR + (hi - live));
@@ -1309,13 +1312,13 @@ struct ClassViews {
 	uint32_t *br_list;    // vals_t: the bridge vertices, listed; k_hi_simp -> k_capping [then the class sort's values, k_top_bracket]
 	uint32_t *tsimp, *tcap; // psB, psC: simplifying / capping vertices per tile of k_bracket_extra, scanned in place [ntiles + 1], totals in the last word; k_flag_tile_counts -> k_bracket_extra [psC: then lastb]
 	uint32_t *srccnt;     // dlt: brackets per mirror pre-order position, as words; k_globalize / k_tree_emit -> the scan of the range starts [then row E's differences]
-	uint32_t *bstart;     // dlt_ps: first bracket of every position; that scan -> k_top_bracket [all vertices: then the scan of row E's differences]
+	uint32_t *bstart;     // dlt_ps: first bracket of every position, as words or (byte counts) as count records in the same span; that scan -> k_top_bracket [all vertices: then the scan of row E's differences]
 	// ---- classes and rows E, F
 	uint32_t *ck, *ck2;   // keys_t, keys_t2: keys of the class sort; k_top_bracket -> the class kernels (and stack_class_ids after a black-only pass)
 	uint8_t *cflag;	      // f8a: "opens a class" per sorted entry; the class kernels -> k_class_scatter / stack_class_ids [before: brec_cnt]
 	uint32_t *cps;	      // psA: its scan [before: brec]
 	uint8_t *dflag;	      // f8c: [S+1] <= [T+1] opens / seen flags of the stack entries; k_class_finish_black / k_dflag -> k_laminar_walk [before: capf]
-	uint32_t *shift_ps;   // topi: black only: scan of row E's differences (dlt_ps still holds the bracket range starts; nobody needs vertex -> stack index there) [all vertices: topi itself, k_stack_emit]
+	uint32_t *shift_ps;   // topi: black only: INCLUSIVE scan of row E's differences (dlt_ps still holds the bracket range starts; nobody needs vertex -> stack index there) [all vertices: topi itself, k_stack_emit]
 	uint32_t *mark, *lastb; // flagC, psC: all vertices: run marks (written with the class flags) and their running maximum; k_class_flags -> k_next_from_runs [psC before: tcap]
 	// ---- row G
 	uint8_t *xflag;	      // f8d: [T + 32] >= S entries whose interval is crossed; the memset -> k_resolve_crossings [the branching flags are long compacted]
@@ -1402,6 +1405,10 @@ struct ClassPass {
 	// hairpin report wants the per-vertex tables too.
 	const bool lean;
 	const bool narrow_oc, narrow_sc, narrow_ic; // the bracket counts of the parallel tree stage as bytes (it wrote them in the form the caller chose, see ParWs)
+	// psin / the range starts as count records (the spans of psin / dlt_ps hold them): exactly where the scan's input is a byte
+	// array, unless POVU_HIP_WORD_PREFIX (A/B hook, read per pass) says words: 1 = both, 2 = psin, 3 = the range starts
+	const int word_prefix;
+	const bool rec_ps, rec_bs;
 	bool black_only = false;	 // classes of the black tree edges only (place_brackets decides)
 	const RootOf root_of;
 	// ---- counts: ordinary / capping / simplifying back edges, all brackets, vertices that get a class
@@ -1419,7 +1426,9 @@ struct ClassPass {
 		: cs(cs_), sw(sw_), pw(pw_), tm(tm_), s(s_), side(side_), tail(tail_), alloc_result_block(alloc), v(class_views(pw_)), C(C_),
 		  V(sw_.V), T(2 * sw_.V + C_), S(n_stack), n_processed(n_processed_), dense_nb0(dense_nb0_), dense(dense_nb0_ >= 0),
 		  want_hp(sw_.hairpins != nullptr), lean(dense && !want_hp), narrow_oc(dense && pw_.narrow_ordcnt),
-		  narrow_sc(narrow_oc && pw_.narrow_srccnt), narrow_ic(narrow_sc && pw_.narrow_incnt), root_of{lean ? nullptr : pw_.t_root, cs_.voff, C_},
+		  narrow_sc(narrow_oc && pw_.narrow_srccnt), narrow_ic(narrow_sc && pw_.narrow_incnt),
+		  word_prefix(getenv("POVU_HIP_WORD_PREFIX") ? atoi(getenv("POVU_HIP_WORD_PREFIX")) : 0), rec_ps(narrow_ic && word_prefix != 1 && word_prefix != 2),
+		  rec_bs(narrow_sc && word_prefix != 1 && word_prefix != 3), root_of{lean ? nullptr : pw_.t_root, cs_.voff, C_},
 		  ntiles((T + BX_TILE - 1) / BX_TILE)
 	{
 	}
@@ -1431,6 +1440,21 @@ struct ClassPass {
 	void scan8pair(const uint8_t *in0, uint32_t *out0, size_t n0, const uint8_t *in1, uint32_t *out1, size_t n1) const
 	{
 		scan_exclusive_u8(in0, out0, n0, in1, out1, n1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	}
+	uint4 *psin_rec() const { return reinterpret_cast<uint4 *>(pw.psin); }
+	uint4 *bstart_rec() const { return reinterpret_cast<uint4 *>(v.bstart); }
+	// f(psin's view, the range starts' view): the four forms of the kernels that read them
+	template <class F>
+	void with_prefix_views(F &&f) const
+	{
+		if (rec_ps && rec_bs)
+			f(PrefixRecords{psin_rec()}, PrefixRecords{bstart_rec()});
+		else if (rec_ps)
+			f(PrefixRecords{psin_rec()}, PrefixWords{v.bstart});
+		else if (rec_bs)
+			f(PrefixWords{pw.psin}, PrefixRecords{bstart_rec()});
+		else
+			f(PrefixWords{pw.psin}, PrefixWords{v.bstart});
 	}
 	void scan2(const uint32_t *in0, uint32_t *out0, size_t n0, const uint32_t *in1, uint32_t *out1, size_t n1) const
 	{
@@ -1542,7 +1566,20 @@ static bool place_brackets(ClassPass &P)
 	if (P.narrow_ic)
 		publish_extra(P);
 	// ranks inside every source and the counts per source are known: place directly
-	if (P.narrow_ic)
+	// (byte counts: as count records, a third of the words' size, in the words' spans -- each array on its own under the A/B hook)
+	const size_t n1 = (size_t)T + 1;
+	if (P.rec_ps && P.rec_bs) {
+		scan_count_records_u8(pw.incnt8, P.psin_rec(), n1, pw.srccnt8, P.bstart_rec(), n1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	} else if (P.rec_ps) {
+		scan_count_records_u8(pw.incnt8, P.psin_rec(), n1, nullptr, nullptr, 0, pw.scan_tmp, pw.scan_tmp_bytes, s);
+		P.scan8(pw.srccnt8, v.bstart, n1);
+	} else if (P.rec_bs) {
+		if (P.narrow_ic)
+			P.scan8(pw.incnt8, pw.psin, n1);
+		else
+			P.scan(pw.incnt, pw.psin, n1);
+		scan_count_records_u8(pw.srccnt8, P.bstart_rec(), n1, nullptr, nullptr, 0, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	} else if (P.narrow_ic)
 		P.scan8pair(pw.incnt8, pw.psin, (size_t)T + 1, pw.srccnt8, v.bstart, (size_t)T + 1);
 	else if (P.narrow_sc)
 		scan_exclusive_u32_u8_pair(pw.incnt, pw.psin, (size_t)T + 1, pw.srccnt8, v.bstart, (size_t)T + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
@@ -1555,6 +1592,7 @@ static bool place_brackets(ClassPass &P)
 		P.tm.end(30);
 		return false;
 	}
+	pw.prefix_records = (P.rec_ps ? 1 : 0) | (P.rec_bs ? 2 : 0);
 	if (P.dense_nb0 == NB0_ON_DEVICE) {
 		P.NB0 = P.extra[3];
 		if (P.NB0 > pw.nb_cap)
@@ -1582,8 +1620,14 @@ static bool place_brackets(ClassPass &P)
 	P.black_only = !P.want_hp && !pw.all_vertex_classes && P.extra[2] == 0;
 	pw.black_only_used = P.black_only;
 	if (P.dense) {
-		LAUNCH(k_bracket_place, NB, s, NB, NB0, ncap, pw.b_src, pw.b_tgt, pw.b_ord, pw.mpre, v.bstart, v.capf, v.simp, pw.tgtR,
-		       P.want_hp ? pw.b_val2 : nullptr);
+		auto place = [&](auto bs) {
+			LAUNCH(k_bracket_place<decltype(bs)>, NB, s, NB, NB0, ncap, pw.b_src, pw.b_tgt, pw.b_ord, pw.mpre, bs, v.capf, v.simp, pw.tgtR,
+			       P.want_hp ? pw.b_val2 : nullptr);
+		};
+		if (P.rec_bs)
+			place(PrefixRecords{P.bstart_rec()});
+		else
+			place(PrefixWords{v.bstart});
 	} else {
 		uint32_t *bk = pw.b_key, *bk2 = pw.b_key2;
 		LAUNCH(k_bracket_order, NB, s, NB, NB0, ncap, nsimp, pw.b_src, pw.b_tgt, pw.mpre, bk, pw.b_val, pw.incnt, v.srccnt);
@@ -1614,10 +1658,12 @@ static void classes_black_only(ClassPass &P)
 		HIP_CHECK(hipMemsetAsync(pw.dlt, 0, ((size_t)V + 2) * 4, s)); // (the bracket counts that lived here are dead)
 		LAUNCH(k_shift_delta, V, s, V, cs.ckey, P.sw.c_ntree, pw.gsize, pw.dlt);
 	}
-	P.scan(sdl, v.shift_ps, (size_t)V + 1);
-	const StackPlace sp{cs.voff, pw.soff, sdl, v.shift_ps, pw.s_vtx};
-	LAUNCH(k_top_bracket<true>, NC, s, NC, pw.gsize, pw.gpar, pw.mpre, v.bstart, pw.segB, pw.tgtR, pw.psin, v.ck,
-	       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, nullptr, cs.ckey, P.sw.c_ntree, sp);
+	scan_inclusive_u32(sdl, v.shift_ps, (size_t)V + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
+	const StackPlace sp{cs.voff, pw.soff, v.shift_ps, pw.s_vtx};
+	P.with_prefix_views([&](auto ps, auto bs) {
+		LAUNCH((k_top_bracket<true, decltype(ps), decltype(bs)>), NC, s, NC, pw.gsize, pw.gpar, pw.mpre, bs, pw.segB, pw.tgtR, ps, v.ck,
+		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, nullptr, cs.ckey, P.sw.c_ntree, sp);
+	});
 	sort_pairs_u32(v.ck, v.ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)P.NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
 	// invalid entries carry NIL; after the sort on the low bits they sit behind every valid key
 	P.tm.end(30 + 2 * 22);
@@ -1642,9 +1688,11 @@ static void classes_all_vertices(ClassPass &P)
 	const SeqWs &sw = P.sw;
 	hipStream_t s = P.s;
 	const uint32_t V = P.V, T = P.T, NC = P.NC;
-	const StackPlace none{nullptr, nullptr, nullptr, nullptr, nullptr};
-	LAUNCH(k_top_bracket<false>, NC, s, NC, pw.gsize, pw.gpar, pw.mpre, v.bstart, pw.segB, pw.tgtR, pw.psin, v.ck,
-	       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, P.want_hp ? pw.hpf : nullptr, nullptr, nullptr, none);
+	const StackPlace none{nullptr, nullptr, nullptr, nullptr};
+	P.with_prefix_views([&](auto ps, auto bs) {
+		LAUNCH((k_top_bracket<false, decltype(ps), decltype(bs)>), NC, s, NC, pw.gsize, pw.gpar, pw.mpre, bs, pw.segB, pw.tgtR, ps, v.ck,
+		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, P.want_hp ? pw.hpf : nullptr, nullptr, nullptr, none);
+	});
 	sort_pairs_u32(v.ck, v.ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)P.NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
 	LAUNCH(k_class_flags<false>, std::max<size_t>(NC, (size_t)V + 2), s, NC, V, v.ck2, pw.vals_t2, pw.lsz, sw.t_flags, v.cflag, pw.dlt,
 	       v.mark);
@@ -1832,6 +1880,7 @@ bool run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint
 	pw.E = sw.E;
 	pw.C = C;
 	pw.T = P.T;
+	pw.prefix_records = 0;
 	t_space_setup(P);
 	bridge_and_capping(P);
 	if (!place_brackets(P))

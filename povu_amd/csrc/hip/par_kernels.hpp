@@ -87,6 +87,7 @@ struct ParWs {
 	bool check_laminar = false;	 // in: run the laminarity check of the candidate stack even when the class stage was exact
 	bool laminar_checked = false;	 // out: the last pass ran it
 	bool black_only_used = false;	 // out: the last pass numbered the classes of the black tree edges only
+	int prefix_records = 0;		 // out: it read count records (common.hpp) for: bit 0 psin, bit 1 the bracket range starts
 	bool s_cls_valid = false;	 // s_cls holds class ids (a black-only pass numbers its classes only when a debug hook asks)
 	bool gcls_valid = false;	 // gcls holds the classes in T-space (a black-only pass keeps them in stack order only)
 	// T-space (global tree vertex idx)

@@ -1316,6 +1316,7 @@ extern "C" povu_hip_forest *povu_hip_decompose(povu_hip_ctx *ctx, const povu_hip
 		ctx->last = LastPass{true, p, C, out.nbad, out.mixed, out.redo_pvst_only, out.stack_export_pending};
 		ctx->last.narrow_counts = !p.all_seq && !p.seq_tree && ctx->pw.narrow_ordcnt;
 		ctx->last.narrow_forms = !ctx->last.narrow_counts ? 0 : 1 | (ctx->pw.narrow_srccnt ? 2 : 0) | (ctx->pw.narrow_incnt ? 4 : 0);
+		ctx->last.prefix_records = ctx->last.narrow_counts ? ctx->pw.prefix_records : 0;
 		if (p.world == 1 && ctx->shard_comp_ids.empty()) { // (povu_hip_forest_walks: a forest of the whole resident graph)
 			f->walk_ctx = ctx;
 			f->walk_gen = g.gen;
@@ -1664,6 +1665,7 @@ extern "C" int povu_hip_last_narrow_counts(const povu_hip_ctx *ctx)
 {
 	return ctx && ctx->last.valid && ctx->last.narrow_counts ? ctx->last.narrow_forms : 0;
 }
+extern "C" int povu_hip_last_prefix_records(const povu_hip_ctx *ctx) { return ctx && ctx->last.valid ? ctx->last.prefix_records : 0; }
 extern "C" uint64_t povu_hip_wide_repeats(const povu_hip_ctx *ctx) { return ctx ? ctx->wide_repeats : 0; }
 
 extern "C" int povu_hip_last_black_only_classes(const povu_hip_ctx *ctx)

@@ -11,6 +11,9 @@
 // reduction k_scan_partials reads 16 bytes a lane and load instead and selects words / bytes / sub the same way.  A new
 // input form is a line in ScanSrc, sc_load and k_scan_partials.  The scans inside a wave and a workgroup are the helpers
 // of common.hpp, as in every other kernel of this file.
+// Two output forms ride on the same loader, lane scan, store, kernels and host driver: an INCLUSIVE job (a flag of the job:
+// the lane scan leaves the inclusive sums) and the count-record scan (template parameter REC, see ScLane: twelve byte
+// counts a lane and sub-tile, the record of common.hpp's cntrec_prefix written instead of twelve words).
 #include "common.hpp"
 
 namespace povu_hip
@@ -21,6 +24,17 @@ namespace povu_hip
 // one LDS exchange per tile).  The arrays here are 1-30 M elements; the second read of the input comes
 // from L2 / Infinity Cache.
 static constexpr int SC_TPB = 256, SC_WAVES = SC_TPB / 64, SC_ITEMS = 8, SC_TILE = SC_TPB * SC_ITEMS, SC_MAX_BLOCKS = 1024;
+// What a lane holds of a sub-tile.  REC = false: SC_ITEMS elements, one a word, scanned in the lane and written back as
+// words.  REC = true (the count-record scan, byte jobs only): the CNTREC_N = 12 count bytes of ONE record exactly as they
+// were loaded (three words) -- the record takes them as they are and the sum in front of the lane, so nothing is unpacked
+// and only the lane's total is worked out.
+template <bool REC>
+struct ScLane {
+	static constexpr int ITEMS = REC ? (int)CNTREC_N : SC_ITEMS, REGS = REC ? 3 : SC_ITEMS, TILE = SC_TPB * ITEMS;
+};
+struct ScBytes12 {
+	uint32_t x, y, z;
+};
 
 // what a job scans: words, or one BYTE per element (flags, small counts -- a quarter of the reads); with `sub` (sum scans)
 // the element is in[i] - sub[i]
@@ -48,6 +62,7 @@ struct ScanJob {
 	size_t n, chunk;
 	uint32_t blocks;
 	uint32_t *partial;
+	bool inclusive; // out[i] takes element i in as well (sc_lane_scan)
 	// single-launch form (k_scan_lookback): tiles of LB_TILE elements, one status word a tile, handed out by a ticket
 	uint32_t tiles;
 	unsigned long long *status;
@@ -139,12 +154,23 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_partials(const ScanJobs jobs)
 // The lane's SC_ITEMS consecutive elements of each of the Q sub-tiles (SC_TILE elements each) that start at t0 (zeros behind
 // b1).  Whole -- all Q sub-tiles of the workgroup (a uniform test), or for a single one the lane's own elements --: every load
 // of the lane is issued before the first is needed
-template <int Q>
-__device__ __forceinline__ void sc_load(const ScanSrc &S, size_t t0, size_t b1, uint32_t (*v)[SC_ITEMS])
+template <int Q, bool REC = false>
+__device__ __forceinline__ void sc_load(const ScanSrc &S, size_t t0, size_t b1, uint32_t (*v)[ScLane<REC>::REGS])
 {
+	constexpr int SC_ITEMS = ScLane<REC>::ITEMS, SC_TILE = ScLane<REC>::TILE;
 	const size_t e0 = t0 + (size_t)threadIdx.x * SC_ITEMS;
 	if (Q > 1 ? t0 + (size_t)Q * SC_TILE <= b1 : e0 + SC_ITEMS <= b1) {
-		if (S.bytes) {
+		if constexpr (REC) { // a record's twelve bytes in one three-word load (tile bases are multiples of 16, e0 of 4)
+			const uint8_t *__restrict__ in8 = S.b() + e0;
+			ScBytes12 a[Q];
+#pragma unroll
+			for (int q = 0; q < Q; q++)
+				a[q] = *reinterpret_cast<const ScBytes12 *>(in8 + q * SC_TILE);
+#pragma unroll
+			for (int q = 0; q < Q; q++)
+				v[q][0] = a[q].x, v[q][1] = a[q].y, v[q][2] = a[q].z;
+			return;
+		} else if (S.bytes) {
 			const uint8_t *__restrict__ in8 = S.b() + e0;
 			uint2 a[Q];
 #pragma unroll
@@ -188,31 +214,46 @@ __device__ __forceinline__ void sc_load(const ScanSrc &S, size_t t0, size_t b1, 
 	} else if constexpr (Q > 1) { // the job's last tile: sub-tile by sub-tile
 #pragma unroll
 		for (int q = 0; q < Q; q++)
-			sc_load<1>(S, t0 + (size_t)q * SC_TILE, b1, v + q);
+			sc_load<1, REC>(S, t0 + (size_t)q * SC_TILE, b1, v + q);
+	} else if constexpr (REC) { // (the count bytes behind the end of the array are zero)
+		v[0][0] = v[0][1] = v[0][2] = 0u;
+#pragma unroll
+		for (int k = 0; k < SC_ITEMS; k++)
+			v[0][k >> 2] |= (e0 + k < b1 ? (uint32_t)S.b()[e0 + k] : 0u) << (8 * (k & 3));
 	} else {
 		for (int k = 0; k < SC_ITEMS; k++)
 			v[0][k] = e0 + k < b1 ? S[e0 + k] : 0u;
 	}
 }
-// the lane's exclusive scan of its own elements, in place; returns their total
-template <int OP>
-__device__ __forceinline__ uint32_t sc_lane_scan(uint32_t (&v)[SC_ITEMS])
+// the lane's exclusive (incl: inclusive) scan of its own elements, in place; returns their total
+// (REC: the total only, the count bytes stay as they are)
+template <int OP, bool REC = false>
+__device__ __forceinline__ uint32_t sc_lane_scan(uint32_t (&v)[ScLane<REC>::REGS], bool incl)
 {
-	uint32_t tot = 0;
+	if constexpr (REC) {
+		return cntrec_bytesum(v[2], cntrec_bytesum(v[1], cntrec_bytesum(v[0], 0u)));
+	} else {
+		uint32_t tot = 0;
 #pragma unroll
-	for (int k = 0; k < SC_ITEMS; k++) {
-		const uint32_t x = v[k];
-		v[k] = tot;
-		tot = ScanOp<OP>{}(tot, x);
+		for (int k = 0; k < SC_ITEMS; k++) {
+			const uint32_t x = v[k], nt = ScanOp<OP>{}(tot, x);
+			v[k] = incl ? nt : tot;
+			tot = nt;
+		}
+		return tot;
 	}
-	return tot;
 }
 // a scanned sub-tile back: pre = everything in front of the lane, v = the lane's own exclusive scan
-template <int OP>
-__device__ __forceinline__ void sc_store(uint32_t *__restrict__ out, size_t e0, size_t b1, uint32_t pre, const uint32_t (&v)[SC_ITEMS])
+// (an inclusive job's v already holds the inclusive sums; REC: the lane's record = its count bytes and pre, out an array of
+// records -- every record that holds an element of [0, b1) is written, whole)
+template <int OP, bool REC = false>
+__device__ __forceinline__ void sc_store(uint32_t *__restrict__ out, size_t e0, size_t b1, uint32_t pre, const uint32_t (&v)[ScLane<REC>::REGS])
 {
 	const ScanOp<OP> op;
-	if (e0 + SC_ITEMS <= b1) {
+	if constexpr (REC) {
+		if (e0 < b1)
+			reinterpret_cast<uint4 *>(out)[e0 / CNTREC_N] = make_uint4(v[0], v[1], v[2], pre);
+	} else if (e0 + SC_ITEMS <= b1) {
 		*reinterpret_cast<uint4 *>(out + e0) = make_uint4(op(pre, v[0]), op(pre, v[1]), op(pre, v[2]), op(pre, v[3]));
 		*reinterpret_cast<uint4 *>(out + e0 + 4) = make_uint4(op(pre, v[4]), op(pre, v[5]), op(pre, v[6]), op(pre, v[7]));
 	} else {
@@ -221,9 +262,10 @@ __device__ __forceinline__ void sc_store(uint32_t *__restrict__ out, size_t e0, 
 				out[e0 + k] = op(pre, v[k]);
 	}
 }
-template <int OP>
+template <int OP, bool REC>
 __global__ void __launch_bounds__(SC_TPB) k_scan_chunks(const ScanJobs jobs)
 {
+	constexpr int SC_ITEMS = ScLane<REC>::ITEMS, SC_TILE = ScLane<REC>::TILE, REGS = ScLane<REC>::REGS;
 	__shared__ uint32_t sh[SC_WAVES];
 	__shared__ uint32_t wave_tot[SC_WAVES];
 	const ScanJob &J = jobs.j[blockIdx.y];
@@ -239,22 +281,23 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_chunks(const ScanJobs jobs)
 	uint32_t carry = block_reduce<SC_WAVES>(base, sh, op);
 	const size_t b0 = (size_t)blockIdx.x * chunk, b1 = b0 + chunk < n ? b0 + chunk : n;
 	// the next tile's loads are issued before this tile's exchange through LDS: two tiles of a block are in flight
-	uint32_t v[SC_ITEMS], nx[SC_ITEMS];
+	uint32_t v[REGS], nx[REGS];
+	const bool incl = J.inclusive;
 	if (b0 < b1)
-		sc_load<1>(J.src, b0, b1, &v);
+		sc_load<1, REC>(J.src, b0, b1, &v);
 	for (size_t t0 = b0; t0 < b1; t0 += SC_TILE) {
 		const size_t e0 = t0 + (size_t)threadIdx.x * SC_ITEMS;
 		const bool more = t0 + SC_TILE < b1;
 		if (more)
-			sc_load<1>(J.src, t0 + SC_TILE, b1, &nx);
-		const uint32_t tot = sc_lane_scan<OP>(v);
+			sc_load<1, REC>(J.src, t0 + SC_TILE, b1, &nx);
+		const uint32_t tot = sc_lane_scan<OP, REC>(v, incl);
 		uint32_t tile_tot;
 		const uint32_t pre = op(carry, block_exclusive_scan<SC_WAVES>(tot, wave_tot, tile_tot, op)); // carry, earlier waves, earlier lanes
-		sc_store<OP>(out, e0, b1, pre, v);
+		sc_store<OP, REC>(out, e0, b1, pre, v);
 		carry = op(carry, tile_tot);
 		__syncthreads();
 		if (more)
-			for (int k = 0; k < SC_ITEMS; k++)
+			for (int k = 0; k < REGS; k++)
 				v[k] = nx[k];
 	}
 }
@@ -270,9 +313,10 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_chunks(const ScanJobs jobs)
 // (Other tilings and ticket-free forms were measured and dropped: DESIGN.md section 4, "Scans ... in one launch".)
 static constexpr unsigned long long LB_AGG = 1ull << 32, LB_PREFIX = 2ull << 32;
 static constexpr int LB_SUB = 8, LB_TILE = SC_TILE * LB_SUB;
-template <int OP>
+template <int OP, bool REC>
 __global__ void __launch_bounds__(SC_TPB) k_scan_lookback(const ScanJobs jobs)
 {
+	constexpr int SC_ITEMS = ScLane<REC>::ITEMS, SC_TILE = ScLane<REC>::TILE, LB_TILE = SC_TILE * LB_SUB;
 	__shared__ uint32_t wave_tot[LB_SUB][SC_WAVES];
 	__shared__ uint32_t s_tile, s_carry;
 	const ScanJob &J = jobs.j[blockIdx.y];
@@ -288,11 +332,12 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_lookback(const ScanJobs jobs)
 		t = s_tile;
 	}
 	const size_t b0 = (size_t)t * LB_TILE, b1 = b0 + LB_TILE < J.n ? b0 + LB_TILE : J.n;
-	uint32_t v[LB_SUB][SC_ITEMS], before[LB_SUB];
-	sc_load<LB_SUB>(J.src, b0, b1, v);
+	uint32_t v[LB_SUB][ScLane<REC>::REGS], before[LB_SUB];
+	const bool incl = J.inclusive;
+	sc_load<LB_SUB, REC>(J.src, b0, b1, v);
 #pragma unroll
 	for (int q = 0; q < LB_SUB; q++) {
-		const uint32_t tot = sc_lane_scan<OP>(v[q]);
+		const uint32_t tot = sc_lane_scan<OP, REC>(v[q], incl);
 		before[q] = op.before(wave_scan_publish(tot, wave_tot[q], op), tot); // the earlier lanes of the wave
 	}
 	__syncthreads();
@@ -335,7 +380,7 @@ __global__ void __launch_bounds__(SC_TPB) k_scan_lookback(const ScanJobs jobs)
 	for (int q = 0; q < LB_SUB; q++) {
 		uint32_t sub_tot;
 		const uint32_t pre = op(op(pre_sub, waves_before<SC_WAVES>(wave_tot[q], sub_tot, op)), before[q]);
-		sc_store<OP>(J.out, b0 + (size_t)q * SC_TILE + (size_t)threadIdx.x * SC_ITEMS, b1, pre, v[q]);
+		sc_store<OP, REC>(J.out, b0 + (size_t)q * SC_TILE + (size_t)threadIdx.x * SC_ITEMS, b1, pre, v[q]);
 		pre_sub = op(pre_sub, sub_tot);
 	}
 }
@@ -344,14 +389,14 @@ static constexpr size_t SC_LEGACY_BYTES = SC_MAX_BLOCKS * 16 + 256; // (two u32 
 // below this many elements the two-launch form is the faster one: its second read comes out of the Infinity Cache
 // (10^7 words: 0.023 ms against 0.035) -- except when every job fits one tile (one launch instead of two, no fill)
 static constexpr size_t LB_MIN = 48u << 20;
-static size_t lb_tiles(size_t n) { return (n + LB_TILE - 1) / LB_TILE; }
-static size_t lb_job_bytes(size_t n) { return 16 + 8 * lb_tiles(n); } // ticket (+ padding), status words
+static size_t lb_tiles(size_t n, size_t tile = LB_TILE) { return (n + tile - 1) / tile; }
+static size_t lb_job_bytes(size_t n) { return 16 + 8 * lb_tiles(n); } // ticket (+ padding), status words (a record job's larger tiles need fewer)
 size_t scan_tmp_bytes(size_t n)
 {
 	return SC_LEGACY_BYTES + 2 * lb_job_bytes(n) + 64; // the partials of the two-launch form, then ticket + status words of two jobs
 }
 // one or two jobs in one launch; false: the temporary storage was sized for fewer elements (the caller takes two launches)
-template <int OP>
+template <int OP, bool REC>
 static bool scan_lookback(ScanJobs &jobs, int nj, void *tmp, size_t tmp_bytes, hipStream_t s)
 {
 	static const bool off = getenv("POVU_HIP_SCAN_TWO_LAUNCH") != nullptr; // (A/B hook)
@@ -362,7 +407,7 @@ static bool scan_lookback(ScanJobs &jobs, int nj, void *tmp, size_t tmp_bytes, h
 	char *at = static_cast<char *>(tmp) + SC_LEGACY_BYTES;
 	for (int j = 0; j < nj; j++) {
 		ScanJob &J = jobs.j[j];
-		const size_t tiles = lb_tiles(J.n);
+		const size_t tiles = lb_tiles(J.n, (size_t)ScLane<REC>::TILE * LB_SUB);
 		if (tiles > 0xFFFFFFF0ull)
 			return false;
 		J.tiles = (uint32_t)tiles;
@@ -383,7 +428,7 @@ static bool scan_lookback(ScanJobs &jobs, int nj, void *tmp, size_t tmp_bytes, h
 		return false;
 	if (clear)
 		HIP_CHECK(hipMemsetAsync(static_cast<char *>(tmp) + SC_LEGACY_BYTES, 0, clear, s));
-	KLAUNCH(k_scan_lookback<OP>, dim3(gx, nj), dim3(SC_TPB), 0, s, jobs);
+	KLAUNCH((k_scan_lookback<OP, REC>), dim3(gx, nj), dim3(SC_TPB), 0, s, jobs);
 	return true;
 }
 
@@ -391,8 +436,9 @@ struct ScanReq {
 	ScanSrc src;
 	uint32_t *out;
 	size_t n;
+	bool inclusive = false;
 };
-static ScanJob make_scan_job(const ScanReq &r, uint32_t *partial)
+static ScanJob make_scan_job(const ScanReq &r, uint32_t *partial, size_t SC_TILE)
 {
 	if ((reinterpret_cast<uintptr_t>(r.src.in) | reinterpret_cast<uintptr_t>(r.src.sub) | reinterpret_cast<uintptr_t>(r.out)) & 15)
 		throw HipError("scan: operands must be 16-byte aligned");
@@ -402,11 +448,12 @@ static ScanJob make_scan_job(const ScanReq &r, uint32_t *partial)
 	size_t chunk = (r.n + blocks - 1) / blocks;
 	chunk = (chunk + SC_TILE - 1) / SC_TILE * SC_TILE; // whole tiles: every tile base stays 16-byte aligned
 	blocks = (r.n + chunk - 1) / chunk;
-	return ScanJob{r.src, r.out, r.n, chunk, (uint32_t)blocks, partial, 0u, nullptr, nullptr};
+	return ScanJob{r.src, r.out, r.n, chunk, (uint32_t)blocks, partial, r.inclusive, 0u, nullptr, nullptr};
 }
 // the host side of every u32 scan: one job, or two in the same launches.  An empty job is left out, so a pair with one
 // is a single job; the one-launch form where it applies, else partials and chunks
-template <int OP>
+// (REC: byte jobs whose outputs are count records, see ScLane)
+template <int OP, bool REC = false>
 static void scan_run(const ScanReq &r0, const ScanReq &r1, void *tmp, size_t tmp_bytes, hipStream_t s)
 {
 	ScanJobs jobs{};
@@ -415,19 +462,23 @@ static void scan_run(const ScanReq &r0, const ScanReq &r1, void *tmp, size_t tmp
 		if (r->n) {
 			if (tmp_bytes < (nj + 1) * SC_MAX_BLOCKS * sizeof(uint32_t))
 				throw HipError("scan: temporary storage too small");
-			jobs.j[nj] = make_scan_job(*r, static_cast<uint32_t *>(tmp) + nj * SC_MAX_BLOCKS);
+			jobs.j[nj] = make_scan_job(*r, static_cast<uint32_t *>(tmp) + nj * SC_MAX_BLOCKS, ScLane<REC>::TILE);
 			gx = std::max(gx, jobs.j[nj++].blocks);
 		}
-	if (!nj || scan_lookback<OP>(jobs, (int)nj, tmp, tmp_bytes, s))
+	if (!nj || scan_lookback<OP, REC>(jobs, (int)nj, tmp, tmp_bytes, s))
 		return;
 	KLAUNCH(k_scan_partials<OP>, dim3(gx, nj), dim3(SC_TPB), 0, s, jobs);
-	KLAUNCH(k_scan_chunks<OP>, dim3(gx, nj), dim3(SC_TPB), 0, s, jobs);
+	KLAUNCH((k_scan_chunks<OP, REC>), dim3(gx, nj), dim3(SC_TPB), 0, s, jobs);
 }
 static constexpr ScanReq SC_NONE{};
 
 void scan_exclusive_u32(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s)
 {
 	scan_run<0>({ScanSrc::words(in), out, n}, SC_NONE, tmp, tmp_bytes, s);
+}
+void scan_inclusive_u32(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s)
+{
+	scan_run<0>({ScanSrc::words(in), out, n, true}, SC_NONE, tmp, tmp_bytes, s);
 }
 void scan_exclusive_max_u32(const uint32_t *in, uint32_t *out, size_t n, void *tmp, size_t tmp_bytes, hipStream_t s)
 {
@@ -453,6 +504,17 @@ void scan_exclusive_u8(const uint8_t *in0, uint32_t *out0, size_t n0, const uint
 		       size_t tmp_bytes, hipStream_t s)
 {
 	scan_run<0>({ScanSrc::of_bytes(in0), out0, n0}, {ScanSrc::of_bytes(in1), out1, in1 ? n1 : 0}, tmp, tmp_bytes, s);
+}
+void scan_count_records_u8(const uint8_t *in0, uint4 *rec0, size_t n0, const uint8_t *in1, uint4 *rec1, size_t n1, void *tmp,
+			   size_t tmp_bytes, hipStream_t s)
+{
+	scan_run<0, true>({ScanSrc::of_bytes(in0), reinterpret_cast<uint32_t *>(rec0), n0},
+			  {ScanSrc::of_bytes(in1), reinterpret_cast<uint32_t *>(rec1), in1 ? n1 : 0}, tmp, tmp_bytes, s);
+}
+void scan_count_records_tiles(size_t *chunk_tile, size_t *lookback_tile)
+{
+	*chunk_tile = ScLane<true>::TILE;
+	*lookback_tile = (size_t)ScLane<true>::TILE * LB_SUB;
 }
 void scan_exclusive_u32_pair(const uint32_t *in0, uint32_t *out0, size_t n0, const uint32_t *in1, uint32_t *out1, size_t n1,
 			     void *tmp, size_t tmp_bytes, hipStream_t s)

@@ -24,7 +24,7 @@ class GuardBandError(RuntimeError):
 
 
 # ops of povu_hip_debug_scan (include/povu_hip.h)
-SCAN_SUM, SCAN_MAX, SCAN_U64, SCAN_U8, SCAN_DIFF, SCAN_XOR_PAIR, SCAN_XOR_U128, SCAN_DIFF_U8, SCAN_MIXED_PAIR, SCAN_DIFF_U8_U8 = range(10)
+SCAN_SUM, SCAN_MAX, SCAN_U64, SCAN_U8, SCAN_DIFF, SCAN_XOR_PAIR, SCAN_XOR_U128, SCAN_DIFF_U8, SCAN_MIXED_PAIR, SCAN_DIFF_U8_U8, SCAN_INCLUSIVE = range(11)
 SCAN_IN_PLACE, SCAN_N_DEV = 0x100, 0x200
 # query kinds of povu_hip_debug_segtree
 SEG_MIN, SEG_FIRST_LESS, SEG_LAST_LESS = range(3)
@@ -395,6 +395,11 @@ def load_lib():
     l.povu_hip_debug_segtree.restype = C.c_int
     l.povu_hip_debug_segtree.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_uint32)]
+    l.povu_hip_last_prefix_records.restype = C.c_int
+    l.povu_hip_last_prefix_records.argtypes = [C.c_void_p]
+    l.povu_hip_debug_count_records.restype = C.c_int
+    l.povu_hip_debug_count_records.argtypes = [C.c_void_p] + 2 * [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                                  C.c_void_p, C.c_void_p] + [C.c_void_p]
     l.povu_hip_debug_bitrank.restype = C.c_int
     l.povu_hip_debug_bitrank.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                          C.c_void_p]
@@ -1429,6 +1434,41 @@ class HipDecomposer:
         self._prim_rc(rc, "scan_exclusive_u32_pair" if op == 0 else name)
         return out, out2
 
+    def debug_scan_inclusive(self, a):
+        """Unit-test hook of scan_inclusive_u32: inclusive sums (mod 2^32) of the words `a`."""
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        out = np.empty_like(a)
+        rc = self._lib.povu_hip_debug_scan(self._ctx, SCAN_INCLUSIVE, a.ctypes.data, out.ctypes.data, a.size, None, None, 0)
+        self._prim_rc(rc, "scan_inclusive_u32")
+        return out
+
+    def count_record_tiles(self) -> tuple:
+        """Elements a tile of the count-record scan covers: (two-launch form, one-launch form)."""
+        tile = (C.c_uint64 * 2)()
+        self._lib.povu_hip_debug_count_records(None, None, 0, None, 0, None, None, None, None, 0, None, 0, None, None, None, tile)
+        return int(tile[0]), int(tile[1])
+
+    def debug_count_records(self, a, pos_a, b=None, pos_b=None):
+        """Unit-test hook of the count records (scan_count_records_u8, cntrec_prefix, cntrec_count) over the bytes `a`
+        and, in the same launch, `b`: per job (records, prefix, count) -- records = the (n + 11) // 12 records as rows
+        (three words of count bytes, the sum in front), prefix[i] = the sum of the bytes in front of positions[i] (<
+        n), count[i] = the byte at positions[i].  Without `b` one such triple, else a pair of them."""
+        jobs, args = [], []
+        for x, pos in ((a, pos_a), (b, pos_b)):
+            if x is None:
+                args += [None, 0, None, 0, None, None, None]
+                continue
+            x = np.ascontiguousarray(x, dtype=np.uint8)
+            pos = np.ascontiguousarray(pos if pos is not None else [], dtype=np.uint32)
+            rec = np.empty(((x.size + 11) // 12, 4), dtype=np.uint32)
+            pre, cnt = np.empty(pos.size, dtype=np.uint32), np.empty(pos.size, dtype=np.uint32)
+            jobs.append((x, pos, rec, pre, cnt))
+            args += [x.ctypes.data, x.size, pos.ctypes.data, pos.size, rec.ctypes.data, pre.ctypes.data, cnt.ctypes.data]
+        rc = self._lib.povu_hip_debug_count_records(self._ctx, *args, None)
+        self._prim_rc(rc, "scan_count_records_u8")
+        out = [(j[2], j[3], j[4]) for j in jobs]
+        return out[0] if b is None else tuple(out)
+
     def debug_scan_u8(self, a, b=None):
         """Unit-test hook of scan_exclusive_u8: exclusive sums (uint32) of the bytes `a`; with `b`, of both in the same
         launch.  Either may be empty."""
@@ -1657,6 +1697,12 @@ class HipDecomposer:
         """(ordcnt, srccnt, incnt): which of the three counts per tree vertex the last pass kept as bytes."""
         m = int(self._lib.povu_hip_last_narrow_counts(self._ctx))
         return bool(m & 1), bool(m & 2), bool(m & 4)
+
+    def last_prefix_records(self) -> int:
+        """Which prefix sums the class stage of the last pass read as packed count records instead of words: bit 0 = the
+        sums of the in-counts, bit 1 = the range starts of the bracket lists (records exactly where the matching count is
+        a byte, unless POVU_HIP_WORD_PREFIX in the environment says words: 1 = both, 2 = the first, 3 = the second)."""
+        return int(self._lib.povu_hip_last_prefix_records(self._ctx))
 
     def wide_repeat_count(self) -> int:
         """Passes of this context that ran their tree and class stages again with word counts (a byte in-count at 255)."""
