@@ -562,6 +562,20 @@ typedef struct {
 	uint64_t n_region_sites;      /* sites that pass: their S or Z segment is marked */
 	uint64_t n_region_masked;     /* sites whose scans were masked: n_sites - n_region_sites, 0 where masking is not allowed */
 	uint64_t n_region_dropped;    /* flubble records the late filter dropped (0 under masking) */
+	/* of povu_hip_call_clustered with a threshold ("Clustered calls").  Without one: cluster_ppm 0, the arrays NULL, the counts
+	 * 0.  With one ref_allele, n_alleles, gt and ac count clusters of exact alleles, a block holds one spelled allele per cluster
+	 * (its representative) and REF is spelled allele ref_spelled, as in a nested call */
+	uint64_t cluster_ppm;	      /* the threshold T = F * 10^6 the call was made with */
+	const uint8_t *rec_clustered; /* [n_records] 1: the record's site has fewer clusters than exact alleles (written with NX, MINSIM) */
+	const uint32_t *cl_minsim;    /* [n_records] the lowest sim_ppm of any member of any of the site's clusters to its representative */
+	const uint32_t *cl_nx;	      /* [ac_off[n_records] + n_records] exact alleles behind written allele i (0: REF) of record r: cl_nx[ac_off[r] + r + i] */
+	uint64_t n_cluster_sites;     /* called sites of two exact alleles or more: the sites that were clustered */
+	uint64_t n_clustered_sites;   /* ... left with two clusters or more and fewer clusters than exact alleles */
+	uint64_t n_cluster_vanished;  /* ... left with one cluster: they give no record */
+	uint64_t n_cluster_keys;      /* inner steps of the exact alleles of those sites: the keys of the bags */
+	uint64_t n_cluster_pairs;     /* (exact allele, representative) pairs the leader loops met */
+	uint64_t n_cluster_pruned;    /* ... of which the weight bound skipped (0 with POVU_HIP_CLUSTER_NO_BOUND) */
+	uint64_t n_cluster_tier2;     /* bags the device-wide sort sorted (more than 64 keys, or all with _T_FORCE_TIER2) */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
@@ -642,6 +656,24 @@ povu_hip_calls *povu_hip_call_restricted(povu_hip_ctx *ctx, const povu_hip_sites
 /* `name:start-end` (split at the last ':' and the first '-' behind it, both numbers of digits alone, at most 18; start < end) to
  * a region of the path named exactly `name` among names[0 .. n_paths).  Host only.  0, or 1 and the refusal in err */
 int povu_hip_region_parse(const char *text, uint32_t n_paths, const char *const *names, povu_hip_region *out, char *err, size_t errlen);
+/* "Clustered calls" (modelled on `vg deconstruct -L`): the exact alleles of a called site whose bags of inner segments are
+ * similar (weighted multiset Jaccard I / U >= min_similarity_ppm / 10^6, compared exactly in integers) are one cluster, found by
+ * leader clustering in allele order (best fit among the representatives, ties to the lowest cluster), and the records count
+ * clusters: ALT i is the representative of cluster i, REF the reference's own exact allele.  Refused together with
+ * POVU_HIP_T_NESTED and the profiles that imply it, the left-normalized and decomposed profiles, POVU_HIP_T_MERGE, _T_OFFREF and
+ * _T_UNTANGLE, for a threshold above 10^6, and for an allele that walks one segment more than 65 536 times.  Composes with
+ * POVU_HIP_T_INVERSIONS and with regions */
+typedef struct {
+	uint32_t min_similarity_ppm; /* T in 1 .. 10^6; 0: not clustered */
+	uint32_t flags;		     /* POVU_HIP_CLUSTER_* */
+} povu_hip_call_cluster_opts;
+#define POVU_HIP_CLUSTER_NO_BOUND 1u /* tests: no pair of bags is skipped by the weight bound */
+/* povu_hip_call_restricted with clusters (cluster NULL or min_similarity_ppm == 0: povu_hip_call_restricted itself, byte for byte) */
+povu_hip_calls *povu_hip_call_clustered(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+					const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile,
+					const povu_hip_call_regions *regions, const povu_hip_call_cluster_opts *cluster, char *err, size_t errlen);
+/* F as decimal text with at most six decimals, 0 < F <= 1, to *ppm = F * 10^6 exactly.  Host only.  0, or 1 and the refusal in err */
+int povu_hip_cluster_parse(const char *text, uint32_t *ppm, char *err, size_t errlen);
 void povu_hip_calls_free(povu_hip_calls *c);
 
 /*

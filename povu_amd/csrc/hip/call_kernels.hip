@@ -31,7 +31,13 @@
 // the traversal pipeline never scans them; flubble_records selects the records of the passing sites in front of the sort
 // (under the mask it drops nothing) and the inversion records are reported against the marks.  The region arrays live in the
 // front end's arena (tr_ws), which nothing carves again before both have read them.
+// With a threshold (povu_hip_call_clustered; INTEGRATION.md "Clustered calls"; cluster_kernels.hip) the classes are the clusters of
+// a site's exact alleles: the same four arrays from another producer, the own-REF path and the extra blocks as in a nested call.
+// What stays a nested call's alone: PS, levels, parents and TANGLED on a collapse.  Per record the call then also says whether
+// its site lost alleles, the site's lowest similarity and the exact alleles behind every written allele (k_cl_provenance).
 #include "call_common.hpp"
+#include "cluster_kernels.hpp"
+#include "cluster_rules.hpp"
 #include "merge_kernels.hpp"
 #include "nest_kernels.hpp"
 #include "norm_kernels.hpp"
@@ -178,15 +184,37 @@ __global__ void k_cl_zero_len(uint32_t n, const uint32_t *__restrict__ keep, con
 		zc[q] = e;
 	}
 }
-// nested: the kept sites with fewer classes than exact alleles
+// a call with classes: the kept sites with fewer classes than exact alleles; vanished: the called sites of two exact alleles or
+// more left with one class
 __global__ void k_cl_collapsed(uint32_t n, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ exact_off, const uint32_t *__restrict__ aoff,
-			       uint8_t *__restrict__ collapsed, uint32_t *__restrict__ count)
+			       const uint8_t *__restrict__ called, uint8_t *__restrict__ collapsed, uint32_t *__restrict__ count,
+			       uint32_t *__restrict__ vanished)
 {
 	for (uint32_t q = blockIdx.x * Q_TPB + threadIdx.x; q < n; q += gridDim.x * Q_TPB) {
 		const bool c = keep[q] && aoff[q + 1] - aoff[q] < exact_off[q + 1] - exact_off[q];
 		collapsed[q] = c;
 		if (c)
 			atomicAdd(count, 1u);
+		if (called[q] && exact_off[q + 1] - exact_off[q] >= 2 && aoff[q + 1] - aoff[q] == 1)
+			atomicAdd(vanished, 1u);
+	}
+}
+// clustered calls, per record (row dst[i], or i): its site lost alleles, the site's lowest similarity, and per written allele
+// (REF's cluster first, the others in order) the exact alleles behind it, at ac_off[row] + row + allele
+__global__ void k_cl_provenance(uint32_t nrec, const uint32_t *__restrict__ perm, CallView V, const uint32_t *__restrict__ dst,
+				const uint8_t *__restrict__ collapsed, const uint32_t *__restrict__ minsim, const uint32_t *__restrict__ csize,
+				const uint64_t *__restrict__ ac_off, uint8_t *__restrict__ rec_clustered, uint32_t *__restrict__ cl_minsim,
+				uint32_t *__restrict__ cl_nx)
+{
+	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
+		const uint32_t t = V.rlist[perm[i]], q = V.trav.rq[t], d = dst ? dst[i] : i, rc = V.oa[t], c0 = V.aoff[q], nc = V.aoff[q + 1] - c0;
+		rec_clustered[d] = collapsed[q];
+		cl_minsim[d] = minsim[q];
+		uint32_t *__restrict__ nx = cl_nx + ac_off[d] + d;
+		nx[0] = csize[c0 + rc];
+		for (uint32_t c = 0, k = 1; c < nc; c++)
+			if (c != rc)
+				nx[k++] = csize[c0 + c];
 	}
 }
 // per flubble record j (before the sort): rstate; the inner bases and AT width of its REF (xilen, xatl: the reference's own
@@ -524,6 +552,9 @@ struct CallsOwner {
 	PinnedVec<uint8_t> rec_unt;
 	PinnedVec<uint32_t> lap, n_laps;
 	PinnedVec<uint16_t> lap_count;
+	// clustered calls
+	PinnedVec<uint8_t> rec_clustered;
+	PinnedVec<uint32_t> cl_minsim, cl_nx;
 };
 
 using namespace povu_hip;
@@ -536,6 +567,9 @@ struct CallInputs {
 	const povu_hip_trav_opts *opts;
 	uint32_t n, P, nR, S, NS, n_trees = 0;
 	bool inversions, nested, normalized, decomposed, merge, offref, untangle;
+	uint32_t cluster_ppm = 0; // clustered calls: the threshold T, 0: not clustered
+	bool cluster_no_bound = false;
+	bool classes() const { return nested || cluster_ppm; } // the call reads classes of exact alleles where it reads alleles
 	uint32_t prim_cap = 0; // decomposed: the longest text that is aligned
 	povu_hip_call_profile_opts prof; // (raw-graph without a profile)
 	std::vector<uint32_t> ref_of_path, slot_first, qa, qz; // reference number of every path (NO_QUERY: none), first slot of every sample, the queries
@@ -554,6 +588,8 @@ struct CallWs {
 	CallView v;	    // what the kernels read of all this (call_common.hpp)
 	SlotsView slots;
 	NestClasses nc;
+	ClusterClasses cc;
+	uint32_t n_vanished = 0;
 	NestRecs nr;
 	uint8_t *collapsed, *rstate;		    // per site / per flubble record before the sort (RS_*)
 	uint64_t *xilen, *xatl, *ref_len, *max_len; // per flubble record: its own REF's inner bases and AT width, its written lengths
@@ -585,6 +621,8 @@ struct CallRecs {
 	uint32_t nrec = 0; // records
 	BlockLayout L;	   // their blocks of spelled alleles
 	uint32_t *xneed, *xoff, *xlist, *xrow, *o_level, *o_parent; // the extra blocks (REFs spelled on their own)
+	uint8_t *rec_clustered; // clustered calls: per record
+	uint32_t *cl_minsim;
 	uint64_t *ref_spelled;
 	uint64_t n_ac = 0; // ALT counts
 	InvRows rows;
@@ -594,7 +632,7 @@ struct CallRecs {
 };
 // cl_spell and cl_bytes
 struct CallSpelled {
-	uint32_t *ac;
+	uint32_t *ac, *cl_nx;
 	uint64_t *sp_off, *at_off;
 	char *o_seq, *o_at;
 	uint64_t nbytes[2] = {0, 0};
@@ -603,7 +641,7 @@ struct CallSpelled {
 
 // the host-side refusals and the host tables
 CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs, const uint32_t *slot_of_path,
-			     const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile)
+			     const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile, const povu_hip_call_cluster_opts *cluster)
 {
 	if (!ctx || !sites || !refs)
 		throw HipError("null context, sites or references");
@@ -658,6 +696,21 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 	if (in.normalized || in.decomposed)
 		in.prof = povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 	in.nested = (opts && (opts->flags & POVU_HIP_T_NESTED)) || in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH;
+	if (cluster && cluster->min_similarity_ppm) {
+		const std::string who = "a clustered call (povu_hip_call_clustered) is refused ";
+		if (cluster->min_similarity_ppm > cluster::PPM)
+			throw HipError(who + "with a threshold of " + std::to_string(cluster->min_similarity_ppm) + " ppm: at most 1000000");
+		if (cluster->flags & ~POVU_HIP_CLUSTER_NO_BOUND)
+			throw HipError(who + "with unknown cluster flags");
+		if (in.nested)
+			throw HipError(who + "together with POVU_HIP_T_NESTED and the profiles that imply it");
+		if (in.normalized || in.decomposed)
+			throw HipError(who + "with profile " + (in.normalized ? "left-normalized" : "decomposed"));
+		if (in.merge || in.offref || in.untangle)
+			throw HipError(who + "together with " + (in.merge ? "POVU_HIP_T_MERGE" : in.offref ? "POVU_HIP_T_OFFREF" : "POVU_HIP_T_UNTANGLE"));
+		in.cluster_ppm = cluster->min_similarity_ppm;
+		in.cluster_no_bound = (cluster->flags & POVU_HIP_CLUSTER_NO_BOUND) != 0;
+	}
 	if (n >= 0x7FFFFFFFu)
 		throw HipError("too many sites");
 	if (n && (!sites->id1 || !sites->id2 || !sites->or1 || !sites->or2 || !sites->parent || !sites->family || !sites->tree))
@@ -818,6 +871,11 @@ void site_classes(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, 
 {
 	CallView &v = w.v;
 	v.aoff = d.aoff, v.oa = d.oa, v.afirst = d.afirst, v.crep = nullptr, w.n_eal = d.n_al;
+	if (in.cluster_ppm) {
+		w.cc = cluster_classes(ctx, d, w.called, in.cluster_ppm, in.cluster_no_bound, in.opts && (in.opts->flags & POVU_HIP_T_FORCE_TIER2));
+		v.aoff = w.cc.coff, v.oa = w.cc.oc, v.afirst = w.cc.cfirst, v.crep = w.cc.crep, w.n_eal = w.cc.n_cl;
+		return;
+	}
 	if (!in.nested)
 		return;
 	w.nc = nest_classes(ctx, d, w.called, in.opts && in.opts->max_steps ? in.opts->max_steps : 65536,
@@ -844,9 +902,10 @@ void kept_sites(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &d, Ca
 		KLAUNCH(k_cl_inner, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, w.v, w.ilen, w.atl);
 	if (n)
 		KLAUNCH(k_cl_zero_len, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, w.v.aoff, w.ilen, w.zc);
-	if (n && in.nested) {
-		KLAUNCH(k_cl_collapsed, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, d.aoff, w.v.aoff, w.collapsed, w.words + 3);
+	if (n && in.classes()) {
+		KLAUNCH(k_cl_collapsed, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, w.keep, d.aoff, w.v.aoff, w.called, w.collapsed, w.words + 3, w.words + 5);
 		w.n_collapsed = read_back(w.words + 3, s);
+		w.n_vanished = read_back(w.words + 5, s);
 	}
 }
 
@@ -981,6 +1040,7 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, con
 	carve(ctx->cl_rec, [&](Spans &take) {
 		take(r1, o.o_q, o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_an, o.o_ns, o.o_block, o.o_nsteps, o.o_pos, o.nalt, r.ac_off, o.o_flags);
 		take(r1, r.o_level, r.o_parent, r.xrow, r.ref_spelled);
+		take(in.cluster_ppm ? r1 : 1, r.rec_clustered, r.cl_minsim);
 		take(f1, r.xneed, r.xoff, r.xlist);
 		take((size_t)nrec * in.S + 1, o.gt);
 		take(n2, r.need, r.boff, r.blist);
@@ -1017,8 +1077,8 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, con
 	scan_exclusive_u32(r.need, r.boff, n2, w.tmp, w.tmp_bytes, s);
 	BlockLayout &L = r.L;
 	HIP_CHECK(copy_async(&L.nfc, r.boff + 4 * (size_t)n, 4, hipMemcpyDeviceToHost, s));
-	uint32_t nx = 0; // the extra blocks: a nested call's REFs that are no representatives
-	if (in.nested && nfl) {
+	uint32_t nx = 0; // the extra blocks: the REFs of a call with classes that are no representatives
+	if (in.classes() && nfl) {
 		scan_exclusive_u32(r.xneed, r.xoff, f1, w.tmp, w.tmp_bytes, s);
 		HIP_CHECK(copy_async(&nx, r.xoff + nfl, 4, hipMemcpyDeviceToHost, s));
 	}
@@ -1061,6 +1121,7 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const Ca
 	unsigned long long *bad;
 	carve(ctx->cl_spell, [&](Spans &take) {
 		take(r.n_ac + 1, sp.ac);
+		take(in.cluster_ppm ? r.n_ac + r.nrec + 1 : 1, sp.cl_nx);
 		take(nsp + 1, slen, alen, sp.sp_off, sp.at_off);
 		take(scan_exclusive_u64_tmp(nsp + 1), s64);
 		take(1, bad);
@@ -1073,6 +1134,14 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const Ca
 		KLAUNCH(k_cl_rec_block, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.v, r.boff, o.o_block, inv.f_dst, r.xoff, r.xrow);
 	}
 	inv_counts(ctx, inv.in, iv, o, r.ac_off, sp.ac);
+	if (in.cluster_ppm) { // (an inversion record: not clustered, no similarity, no exact alleles)
+		HIP_CHECK(hipMemsetAsync(sp.cl_nx, 0, (r.n_ac + r.nrec + 1) * 4, s));
+		HIP_CHECK(hipMemsetAsync(r.rec_clustered, 0, (size_t)r.nrec + 1, s));
+		HIP_CHECK(hipMemsetAsync(r.cl_minsim, 0, ((size_t)r.nrec + 1) * 4, s));
+		if (nfl)
+			KLAUNCH(k_cl_provenance, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.v, inv.f_dst, w.collapsed, w.cc.minsim, w.cc.csize,
+				r.ac_off, r.rec_clustered, r.cl_minsim, sp.cl_nx);
+	}
 	HIP_CHECK(hipMemsetAsync(slen + nsp, 0, 8, s));
 	HIP_CHECK(hipMemsetAsync(alen + nsp, 0, 8, s));
 	const FlubbleBlocks B{L, r.block_off, r.blist, r.xlist};
@@ -1222,6 +1291,14 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 		v.n_unt_tasks = un.n_tasks, v.n_unt_records = un.n_records, v.n_unt_missing = un.n_missing, v.n_unt_extra = un.n_extra;
 		v.n_unt_fallback = un.n_fallback;
 	}
+	if (in.cluster_ppm) { // (without a threshold: the arrays NULL, the counts 0)
+		give(o->rec_clustered, v.rec_clustered, r.rec_clustered, nrec);
+		give(o->cl_minsim, v.cl_minsim, r.cl_minsim, nrec);
+		give(o->cl_nx, v.cl_nx, sp.cl_nx, r.n_ac + nrec);
+		v.cluster_ppm = in.cluster_ppm;
+		v.n_cluster_sites = w.cc.n_sites, v.n_clustered_sites = w.n_collapsed, v.n_cluster_vanished = w.n_vanished;
+		v.n_cluster_keys = w.cc.n_keys, v.n_cluster_pairs = w.cc.n_pairs, v.n_cluster_pruned = w.cc.n_pruned, v.n_cluster_tier2 = w.cc.n_tier2;
+	}
 	v.device_ms = timer.stop(ctx->stream);
 	for (const auto &fill : defaults)
 		fill();
@@ -1238,7 +1315,7 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	v.n_refs = nR;
 	v.n_inv_records = iv.n, v.n_inv_heads = iv.n_heads, v.n_inv_long = iv.n_long, v.n_inv_tier2 = iv.n_tier2;
 	v.nested = in.nested ? 1 : 0;
-	v.n_enclosed = w.nr.n_enclosed, v.n_collapsed_sites = w.n_collapsed, v.n_popped = w.nr.n_popped, v.n_rescued = w.nr.n_rescued;
+	v.n_enclosed = w.nr.n_enclosed, v.n_collapsed_sites = in.nested ? w.n_collapsed : 0, v.n_popped = w.nr.n_popped, v.n_rescued = w.nr.n_rescued;
 	v.n_normalized = w.nm.n_changed, v.max_shift = w.nm.max_shift, v.n_norm_compared = w.nm.n_compared;
 	v.n_rows = pr.n_rows;
 	v.n_decomposed_alts = pr.n_decomposed, v.n_passthrough_alts = pr.n_passthrough, v.n_prim_tier2 = pr.n_tier2, v.n_prim_cells = pr.n_cells;
@@ -1270,9 +1347,17 @@ extern "C" povu_hip_calls *povu_hip_call_restricted(povu_hip_ctx *ctx, const pov
 						    const povu_hip_call_profile_opts *profile, const povu_hip_call_regions *regions, char *err,
 						    size_t errlen)
 {
+	return povu_hip_call_clustered(ctx, sites, refs, slot_of_path, opts, profile, regions, nullptr, err, errlen);
+}
+
+extern "C" povu_hip_calls *povu_hip_call_clustered(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+						   const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
+						   const povu_hip_call_profile_opts *profile, const povu_hip_call_regions *regions,
+						   const povu_hip_call_cluster_opts *cluster, char *err, size_t errlen)
+{
 	CallTimer timer;
 	return guarded_call(ctx, err, errlen, (povu_hip_calls *)nullptr, [&] {
-		const CallInputs in = check_call_inputs(ctx, sites, refs, slot_of_path, opts, profile);
+		const CallInputs in = check_call_inputs(ctx, sites, refs, slot_of_path, opts, profile, cluster);
 		if (in.offref && regions && regions->n)
 			throw HipError("regions (povu_hip_call_restricted) are refused together with POVU_HIP_T_OFFREF: an off-reference site has no "
 				       "locus on a region's path");

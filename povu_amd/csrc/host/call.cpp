@@ -33,6 +33,7 @@ struct CallArgs {
 	bool offref = false;	 // --off-reference: sites no reference path crosses, on a surrogate path (INTEGRATION.md "Off-reference calls")
 	bool untangle = false;	 // --untangle: per-copy genotypes where a path laps a site (INTEGRATION.md "Untangled calls")
 	std::vector<std::string> regions; // --region <name:start-end>, repeatable (INTEGRATION.md "Region calls")
+	uint32_t cluster_ppm = 0;	  // --cluster <F>: F * 10^6, 0 without the flag (INTEGRATION.md "Clustered calls")
 	povu_hip_call_profile_opts prof{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 };
 
@@ -41,8 +42,8 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 	CallArgs c;
 	int forms = 0;
 	bool by_p = false, by_pos = false;
-	std::string ref_file;
-	auto need = [&](size_t &i) -> const std::string & {
+	std::string ref_file, gpus; // gpus: a --gpus flag as it was given (it belongs to `decompose`)
+	auto need =[&](size_t &i) -> const std::string & {
 		if (i + 1 >= a.size())
 			throw std::runtime_error("Flag '" + a[i] + "' requires an argument but received none");
 		return a[++i];
@@ -120,6 +121,15 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			const char *one[1] = {name.c_str()};
 			if (povu_hip_region_parse(text.c_str(), 1, one, &r, err, sizeof err) != 0)
 				throw std::runtime_error(std::string("Flag '--region': ") + err);
+		} else if (x == "--cluster" || !x.compare(0, 10, "--cluster=")) {
+			const std::string v = x == "--cluster" ? need(i) : x.substr(10);
+			char err[512] = {0};
+			if (povu_hip_cluster_parse(v.c_str(), &c.cluster_ppm, err, sizeof err) != 0)
+				throw std::runtime_error(std::string("Flag '--cluster': ") + err);
+		} else if (x == "--gpus" || !x.compare(0, 7, "--gpus=")) {
+			gpus = x;
+			if (x == "--gpus" && i + 1 < a.size())
+				i++;
 		} else if (x == "-g" || x == "--restrict" || !x.compare(0, 11, "--restrict=")) {
 			throw std::runtime_error("--restrict regions are not supported by this build's `call`: its --region <name:start-end> "
 						 "(repeatable; 1-based start, exclusive end) restricts a call (INTEGRATION.md \"Region calls\")");
@@ -132,6 +142,21 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			by_pos = true;
 		}
 	}
+	if (c.cluster_ppm) { // clusters stand where a nested call's classes stand, and no rewriting profile reads them
+		static const char *const name[] = {"raw-graph", "top-level-only", "popped", "left-normalized", "decomposed"};
+		const char *with = c.nested			? "--nested"
+				   : c.merge			? "--merge-primitives"
+				   : c.offref			? "--off-reference"
+				   : c.untangle			? "--untangle"
+				   : !gpus.empty()		? "--gpus"
+								: nullptr;
+		if (c.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
+			throw std::runtime_error(std::string("Flag '--cluster' is called under --profile raw-graph alone, not ") + name[c.prof.profile]);
+		if (with)
+			throw std::runtime_error(std::string("Flag '--cluster' cannot be combined with ") + with);
+	}
+	if (!gpus.empty())
+		throw std::runtime_error("Flag could not be matched: " + gpus);
 	if (c.merge && c.prof.profile != POVU_HIP_PROFILE_DECOMPOSED)
 		throw std::runtime_error("Flag '--merge-primitives' merges the rows of --profile decomposed and needs that profile");
 	if (c.offref && c.nested)
@@ -260,7 +285,9 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 		fail("sequences");
 	const povu_hip_trav_opts opts{0, (ca.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (ca.nested ? POVU_HIP_T_NESTED : 0u) | (ca.merge ? POVU_HIP_T_MERGE : 0u) |
 						 (ca.offref ? POVU_HIP_T_OFFREF : 0u) | (ca.untangle ? POVU_HIP_T_UNTANGLE : 0u)};
-	povu_hip_calls *c = povu_hip_call_restricted(ctx, sites, &nm->refs, nm->slot_of_path, &opts, &ca.prof, regions.empty() ? nullptr : &rg, err, sizeof err);
+	const povu_hip_call_cluster_opts cl{ca.cluster_ppm, 0};
+	povu_hip_calls *c = povu_hip_call_clustered(ctx, sites, &nm->refs, nm->slot_of_path, &opts, &ca.prof, regions.empty() ? nullptr : &rg,
+						    ca.cluster_ppm ? &cl : nullptr, err, sizeof err);
 	if (!c)
 		fail("call");
 

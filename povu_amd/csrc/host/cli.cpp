@@ -3,7 +3,7 @@
 //   povu [--version] [-v <int>] [-t <int>] decompose -i <gfa> [-o <dir>] [-h|--hairpins] [-s|--subflubbles]
 //   povu ... decompose ... --structure-export <json>   (additive: writes the flubble debug sidecar gfa2vcf writes)
 //   povu ... gfa2vcf -i <gfa> [-h] [-s] [--structure-export <json>] <options of `call`>   (app/cli/cli.cpp:154-193)
-//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--profile <p>] [--merge-primitives] [--off-reference] [--untangle] [--region <name:start-end>]...   (the
+//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--profile <p>] [--merge-primitives] [--off-reference] [--untangle] [--region <name:start-end>]... [--cluster <F>]   (the
 //   variant calls of INTEGRATION.md "Variant calls" and "Inversion calls", on the GPU)
 //   povu ... vcf -i <gfa> -c <vcf> --report -o <dir> [--spelling] [--forward-only]   (the --report half of the reference's `vcf`,
 //   app/cli/cli.cpp; INTEGRATION.md "VCF checks", on the GPU)
@@ -86,6 +86,10 @@ static void usage(std::ostream &os)
 	      "                                          end step, in the bases [start, end) of the path named exactly so: 1-based start,\n"
 	      "                                          exclusive end; repeatable, any path (INTEGRATION.md \"Region calls\"); not with\n"
 	      "                                          --off-reference.  (-g / --restrict of the reference tool stay refused)\n"
+	      "        --cluster=[F]                     raw-graph only: the exact alleles of a site whose inner segments are similar\n"
+	      "                                          (weighted Jaccard of at least F, 0 < F <= 1, at most six decimals) become one\n"
+	      "                                          allele, written as its first member, with NX and MINSIM (INTEGRATION.md\n"
+	      "                                          \"Clustered calls\"); with --inversions and --region alone [default: off]\n"
 	      "        --max-level=[n]                   popped: the deepest level kept without rescue [default: 0]\n"
 	      "        --max-ref-length=[n], --max-allele-length=[n]\n"
 	      "                                          popped: a record with a longer REF / allele is big (0: no limit) [default: 0]\n"

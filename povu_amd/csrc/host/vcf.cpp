@@ -2,6 +2,7 @@
 // PanSN slots, PVST vertices to sites, and the records of povu_hip_call to VCF text.  The one place that holds these rules
 // for `povu call` and for povu_amd/hip.py alike; tests/vcf_ref.py restates them as the yardstick.
 #include "../../../include/povu_hip.h"
+#include "../hip/cluster_rules.hpp"
 #include "../hip/region_rules.hpp"
 
 #include <algorithm>
@@ -130,6 +131,24 @@ try {
 	return 1;
 } catch (const std::exception &x) {
 	set_err(err, errlen, std::string("region: ") + x.what());
+	return 1;
+}
+
+// the threshold of "Clustered calls" (the reading: cluster_rules.hpp)
+extern "C" int povu_hip_cluster_parse(const char *text, uint32_t *ppm, char *err, size_t errlen)
+try {
+	if (!text || !ppm) {
+		set_err(err, errlen, "cluster threshold: bad arguments");
+		return 1;
+	}
+	const std::string bad = cluster::parse(text, ppm);
+	if (!bad.empty()) {
+		set_err(err, errlen, bad);
+		return 1;
+	}
+	return 0;
+} catch (const std::exception &x) {
+	set_err(err, errlen, std::string("cluster threshold: ") + x.what());
 	return 1;
 }
 
@@ -316,6 +335,12 @@ const char UNTANGLE_LINES[] =
 	"##INFO=<ID=LC,Number=1,Type=Integer,Description=\"Laps of the reference path through the site\">\n"
 	"##FORMAT=<ID=CN,Number=.,Type=Integer,Description=\"Laps of the sample's haplotypes through the site\">\n";
 
+// the lines of "Clustered calls", behind those of a call made with a threshold (and one line that states it)
+const char CLUSTER_LINES[] =
+	"##INFO=<ID=NX,Number=R,Type=Integer,Description=\"Exact alleles of the site behind every written allele, the cluster of REF first\">\n"
+	"##INFO=<ID=MINSIM,Number=1,Type=Integer,Description=\"Lowest similarity, in parts per million, of an exact allele of the site to the "
+	"representative of its cluster\">\n";
+
 char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names, const char *const *path_name,
 		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len,
 		const char *const *rest_prefix, uint32_t n_rest, bool rest)
@@ -347,7 +372,13 @@ try {
 	const bool untangled = nested_fields && (c->rec_unt || c->untangled);
 	if (untangled && c->n_records && (!c->rec_unt || !c->lap || !c->n_laps || !c->lap_count))
 		return nullptr;
-	if (merged && (!c->mrow_member || !c->mrow_gt || !c->mrow_ac || !c->mrow_an || !c->mrow_ns))
+	// the arrays of "Clustered calls" (cluster_ppm 0: the text of the call without a threshold; an array left out: no record
+	// says NX or MINSIM)
+	const uint64_t cluster_ppm = nested_fields ? c->cluster_ppm : 0;
+	if (cluster_ppm > cluster::PPM)
+		return nullptr;
+	const bool clustered = cluster_ppm && c->rec_clustered && c->cl_minsim && c->cl_nx;
+	if (merged && (!c->mrow_member ||!c->mrow_gt || !c->mrow_ac || !c->mrow_an || !c->mrow_ns))
 		return nullptr;
 	const uint64_t n_records = c->n_records, n = merged ? c->n_mrows : rows ? c->n_rows : n_records, S = c->n_slots;
 	const uint32_t P = names->n_paths, n_samples = names->refs.n_samples;
@@ -402,6 +433,11 @@ try {
 	}
 	// ---- header, a contig line per reference path of the prefix, the column line
 	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile] + (merged_lines ? MERGE_LINES : "") + (offref ? OFFREF_LINES : "") + (untangled ? UNTANGLE_LINES : "");
+	if (cluster_ppm) {
+		char f[64];
+		snprintf(f, sizeof f, "##povu_call_cluster=%u.%06u\n", (unsigned)(cluster_ppm / cluster::PPM), (unsigned)(cluster_ppm % cluster::PPM));
+		head += std::string(CLUSTER_LINES) + f;
+	}
 	// the paths whose lines and records are written: those of the prefix (every one without), or with `rest` of no prefix
 	auto takes = [&](const char *name) {
 		if (!rest)
@@ -613,6 +649,12 @@ try {
 				o += ";ES=" + label + ";LV=" + std::to_string(level ? (long)(int32_t)level[i] : (long)sites->height[q] - 1);
 				if (nested && has_parent)
 					o += ";PS=" + parent;
+				if (clustered && c->rec_clustered[i]) {
+					const uint32_t *nx = c->cl_nx + c->ac_off[i] + i;
+					for (uint32_t k = 0; k < na; k++)
+						o += (k ? "," : ";NX=") + std::to_string(nx[k]);
+					o += ";MINSIM=" + std::to_string(c->cl_minsim[i]);
+				}
 				if (offref && c->rec_offref[i]) {
 					o += ";OFFREF=T";
 					if (c->host_query[i] != POVU_HIP_NIL)

@@ -135,6 +135,9 @@ OFFREF_COUNTERS = ("n_offref_sites", "n_offref_records", "n_offref_hosted")  # o
 UNTANGLE_COUNTERS = ("n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback")  # of Calls
 REGION_COUNTERS = ("n_regions", "n_region_sites", "n_region_masked", "n_region_dropped")  # of Calls
 REGION_NO_MASK = 1  # povu_hip_call_regions.flags: scan every site, select the records at the end only (tests)
+CLUSTER_COUNTERS = ("n_cluster_sites", "n_clustered_sites", "n_cluster_vanished", "n_cluster_keys", "n_cluster_pairs", "n_cluster_pruned",
+                    "n_cluster_tier2")  # of Calls
+CLUSTER_NO_BOUND = 1  # povu_hip_call_cluster_opts.flags: no pair of bags is skipped by the weight bound (tests)
 MERGE_COUNTERS = ("n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts")  # of Calls, beside n_mrows
 
 
@@ -181,7 +184,15 @@ class _CallsNested(_Calls):
                  ("n_laps", C.POINTER(C.c_uint32)), ("lap_count", C.POINTER(C.c_uint16))] +
                 [(k, C.c_uint64) for k in UNTANGLE_COUNTERS] +
                 # "Region calls"
-                [(k, C.c_uint64) for k in REGION_COUNTERS])
+                [(k, C.c_uint64) for k in REGION_COUNTERS] +
+                # "Clustered calls"
+                [("cluster_ppm", C.c_uint64), ("rec_clustered", C.POINTER(C.c_uint8)), ("cl_minsim", C.POINTER(C.c_uint32)),
+                 ("cl_nx", C.POINTER(C.c_uint32))] +
+                [(k, C.c_uint64) for k in CLUSTER_COUNTERS])
+
+
+class _ClusterOpts(C.Structure):
+    _fields_ = [("min_similarity_ppm", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class _Region(C.Structure):
@@ -316,6 +327,11 @@ def load_lib():
     l.povu_hip_call_restricted.restype = C.POINTER(_CallsNested)
     l.povu_hip_region_parse.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(_Region), C.c_char_p, C.c_size_t]
     l.povu_hip_region_parse.restype = C.c_int
+    l.povu_hip_call_clustered.argtypes = [C.c_void_p, C.POINTER(_Sites), C.POINTER(_CallRefs), C.POINTER(C.c_uint32), C.POINTER(_TravOpts),
+                                          C.POINTER(_ProfileOpts), C.POINTER(_CallRegions), C.POINTER(_ClusterOpts), C.c_char_p, C.c_size_t]
+    l.povu_hip_call_clustered.restype = C.POINTER(_CallsNested)
+    l.povu_hip_cluster_parse.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]
+    l.povu_hip_cluster_parse.restype = C.c_int
     l.povu_hip_calls_vcf_profile.argtypes = [C.POINTER(_CallsNested), C.POINTER(_Sites), C.POINTER(_CallNames), C.POINTER(C.c_char_p),
                                              C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t)]
     l.povu_hip_calls_vcf_profile.restype = C.c_void_p
@@ -965,6 +981,21 @@ class Calls:
         # the flubble records the late filter dropped.  Without regions: 0
         for k in REGION_COUNTERS:
             setattr(self, k, int(getattr(c, k)))
+        # "Clustered calls" (cluster=...): the threshold in ppm (0: not clustered); per record whether its site lost alleles and
+        # the site's lowest similarity; per written allele of record r the exact alleles behind it, at ac_off[r] + r + i; the
+        # counters.  Without a threshold: empty, 0
+        self.cluster_ppm = int(c.cluster_ppm)
+        k = n if self.cluster_ppm else 0
+        self.rec_clustered = _view(c.rec_clustered, k, np.uint8)
+        self.cl_minsim = _view(c.cl_minsim, k, np.uint32)
+        self.cl_nx = _view(c.cl_nx, int(self.ac_off[-1]) + n if k else 0, np.uint32)
+        for k in CLUSTER_COUNTERS:
+            setattr(self, k, int(getattr(c, k)))
+
+    def nx(self, i):
+        """The exact alleles behind every written allele of record i of a clustered call, REF's cluster first."""
+        at = int(self.ac_off[i]) + i
+        return self.cl_nx[at:at + int(self.n_alleles[i])].tolist()
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -1293,7 +1324,8 @@ class HipDecomposer:
             raise RuntimeError(err.value.decode())
 
     def call(self, forest: Forest, refs, max_steps: int = 65536, flags: int = 0, profile=None, max_level: int = 0,
-             max_ref_length: int = 0, max_allele_length: int = 0, regions=None, region_no_mask: bool = False) -> Calls:
+             max_ref_length: int = 0, max_allele_length: int = 0, regions=None, region_no_mask: bool = False, cluster=None,
+             cluster_no_bound: bool = False) -> Calls:
         """The variant calls of `forest` (INTEGRATION.md "Variant calls") with the resident paths whose names start with one
         of the prefixes `refs` as references, on the GPU (paths and sequences uploaded first).  flags: T_FORCE_TIER2,
         T_INVERSIONS (the SUBR records of "Inversion calls" merged in: Calls.n_steps, flags & CALL_SUBR, the n_inv_* counters),
@@ -1315,7 +1347,12 @@ class HipDecomposer:
         the 1-based bases [start, end) of the resident path named exactly so; the records are those of the same call without
         regions for the sites with a boundary segment, and the inversions with an end step, that a region meets; the
         REGION_COUNTERS.  A call that is not nested masks the other sites in front of its scans; region_no_mask makes it scan
-        every site and select the records at the end, as a nested call does (tests)."""
+        every site and select the records at the end, as a nested call does (tests).  cluster ("Clustered calls", raw-graph
+        alone, refused with T_NESTED, T_MERGE, T_OFFREF and T_UNTANGLE; composes with T_INVERSIONS and regions): the threshold F
+        as decimal text ("0.9", at most six decimals, 0 < F <= 1) or as an integer of parts per million; the exact alleles of a
+        site whose bags of inner segments are that similar are one allele, written as its first member; Calls.cluster_ppm,
+        rec_clustered, cl_minsim, cl_nx (Calls.nx), the CLUSTER_COUNTERS, and vcf_text writes NX and MINSIM.  cluster_no_bound
+        reads every pair of bags, whatever their weights say (tests)."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names
@@ -1332,8 +1369,19 @@ class HipDecomposer:
             o = _TravOpts(max_steps, flags)
             po = _ProfileOpts(PROFILES[profile or "raw-graph"], max_level, max_ref_length, max_allele_length)
             rg = self._regions(regions, names, name_array, region_no_mask)
-            p = self._lib.povu_hip_call_restricted(self._ctx, sites._p, C.byref(nr.contents.refs), nr.contents.slot_of_path, C.byref(o),
-                                                   C.byref(po) if profile is not None else None, rg, err, 512)
+            co = None
+            if cluster is not None:
+                ppm = C.c_uint32(0)
+                if isinstance(cluster, str):
+                    if self._lib.povu_hip_cluster_parse(cluster.encode(), C.byref(ppm), err, 512) != 0:
+                        raise RuntimeError(err.value.decode())
+                elif isinstance(cluster, int) and not isinstance(cluster, bool) and 1 <= cluster <= 10 ** 6:
+                    ppm = C.c_uint32(cluster)
+                else:
+                    raise RuntimeError(f"cluster threshold '{cluster}': decimal text such as \"0.9\", or parts per million in 1 .. 10^6")
+                co = C.byref(_ClusterOpts(ppm.value, CLUSTER_NO_BOUND if cluster_no_bound else 0))
+            p = self._lib.povu_hip_call_clustered(self._ctx, sites._p, C.byref(nr.contents.refs), nr.contents.slot_of_path, C.byref(o),
+                                                  C.byref(po) if profile is not None else None, rg, co, err, 512)
             if not p:
                 raise RuntimeError(err.value.decode())
         except Exception:

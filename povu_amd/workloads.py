@@ -926,3 +926,63 @@ def vntr_haplotypes(n_sites: int, n_haps: int, max_copies: int, seed: int, rever
         else:
             pieces.append((w, np.zeros(w.size, dtype=np.uint8)))
     return links, _paths([f"hap{h}#1#chr1" for h in range(n_haps)], pieces)
+
+
+def _braid_ids(n_sites: int, layers: int, width: int, seed: int) -> np.ndarray:
+    """Segment id of inner segment (site, layer, position) of braid(): a site's inner ids shuffled, so that a walk's segments
+    do not ascend."""
+    rng = np.random.default_rng(seed)
+    m = layers * width
+    ids = np.empty((n_sites, m), dtype=np.int64)
+    for i in range(n_sites):
+        ids[i] = i * (m + 1) + 2 + rng.permutation(m)
+    return ids.reshape(n_sites, layers, width)
+
+
+def braid(n_sites: int, layers: int, width: int, seed: int = 0) -> Links:
+    """Sites the PVST does not split further ("Clustered calls"): `n_sites` sites joined end to end, site i between its entry
+    segment e = i (layers width + 1) + 1 and the next site's entry, which is its exit.  Between them lie `layers` layers of
+    `width` parallel segments, consecutive layers linked completely (no inner flubble exists), the entry to every segment of the
+    first layer, every segment of the last layer to the exit, and a deletion link entry > exit.  The inner ids of a site are
+    shuffled by `seed` (braid_haplotypes with the same seed walks them)."""
+    m = layers * width
+    ids = _braid_ids(n_sites, layers, width, seed) - 1  # vertex indices: the ids are 1 .. V
+    src, dst = [], []
+    for i in range(n_sites):
+        e, z = i * (m + 1), (i + 1) * (m + 1)
+        src.append(np.array([e])), dst.append(np.array([z]))
+        if not layers:
+            continue
+        src.append(np.full(width, e)), dst.append(ids[i, 0])
+        for k in range(layers - 1):
+            src.append(np.repeat(ids[i, k], width)), dst.append(np.tile(ids[i, k + 1], width))
+        src.append(ids[i, layers - 1]), dst.append(np.full(width, z))
+    return from_plus_links(np.arange(1, n_sites * (m + 1) + 2, dtype=np.uint32), np.concatenate(src), np.concatenate(dst))
+
+
+def braid_haplotypes(n_sites: int, layers: int, width: int, n: int, seed: int = 0, mutate: float = 0.05, skip: float = 0.05,
+                     reverse_every: int = 0) -> Paths:
+    """`n` haplotypes of braid(n_sites, layers, width, seed), near-equal as the haplotypes of a population are: every site has a
+    base walk (a segment of every layer), and a haplotype takes the deletion link with probability `skip`, else the base walk
+    with every layer's segment redrawn with probability `mutate`.  Every `reverse_every`-th haplotype is written walking
+    backwards.  PanSN names, one sample a haplotype (`hap<k>#1#chr1`); haplotype 0 is the reference."""
+    m = layers * width
+    ids = _braid_ids(n_sites, layers, width, seed)
+    rng = np.random.default_rng(seed + 1)
+    base = rng.integers(0, max(width, 1), size=(n_sites, layers))
+    entry = np.arange(n_sites + 1, dtype=np.int64) * (m + 1) + 1
+    pieces = []
+    for h in range(n):
+        gone = rng.random(n_sites) < skip
+        pick = np.where(rng.random((n_sites, layers)) < mutate, rng.integers(0, max(width, 1), size=(n_sites, layers)), base)
+        w = [np.array([1], dtype=np.int64)]
+        for i in range(n_sites):
+            if not gone[i] and layers:
+                w.append(ids[i, np.arange(layers), pick[i]])
+            w.append(entry[i + 1:i + 2])
+        w = np.concatenate(w).astype(np.uint32)
+        if reverse_every and h and h % reverse_every == reverse_every - 1:
+            pieces.append((w[::-1].copy(), np.ones(w.size, dtype=np.uint8)))
+        else:
+            pieces.append((w, np.zeros(w.size, dtype=np.uint8)))
+    return _paths([f"hap{h}#1#chr1" for h in range(n)], pieces)

@@ -1,4 +1,4 @@
-"""Device time of povu_hip_call (HipDecomposer.call) in its modes on one of seven inputs, each at the size it has always been
+"""Device time of povu_hip_call (HipDecomposer.call) in its modes on one of eight inputs, each at the size it has always been
 timed at:
 
     chain     the chain of bubbles with 32 closed-form haplotypes, a quarter written reversed (workloads.chain_haplotypes),
@@ -14,6 +14,9 @@ timed at:
               not have, INTEGRATION.md "Off-reference calls"); 125000 units, 1e6 segments
     looped    workloads.vntr_haplotypes with 32 haplotypes of 1 .. 6 laps a site, every fourth walking backwards (loop sites,
               INTEGRATION.md "Untangled calls"); 100000 sites, 5e5 segments
+    braid     workloads.braid / braid_haplotypes with 64 near-equal haplotypes (sites of 24 layers of 2 parallel segments that the
+              PVST does not split, a layer redrawn with probability 0.02: one changed layer is 23 / 25 similar, two are 22 / 26;
+              INTEGRATION.md "Clustered calls"); 20000 sites, 1e6 segments
 
 and in any of the modes plain, inversions (T_INVERSIONS), nested (T_NESTED), popped (profile `popped`, max_level 0, both length
 limits --max-length), normalized (profile `left-normalized`), decomposed (profile `decomposed`), merged (the same with T_MERGE:
@@ -22,7 +25,8 @@ T_FORCE_TIER2: every aligned pair through the striped kernel, for the cells per 
 only), offref (T_OFFREF: the sites no reference path crosses too; its time less that of plain is the step's) and untangled
 (T_UNTANGLE: the laps of every haplotype aligned with the reference's; its time less that of plain is the step's) and region
 (asked for by name only: the plain call restricted to the middle 1 % of the first reference path's bases, INTEGRATION.md "Region
-calls"; the sites outside lose their scans); without --modes those the input was made for.  One JSON line
+calls"; the sites outside lose their scans) and cluster (the clustered call at T = 900000, INTEGRATION.md "Clustered calls"; its
+time less that of plain is the step's; `alts` counts the ALTs written); without --modes those the input was made for.  One JSON line
 per mode and run: HIP-event time of the call (query upload to the last byte on the host), records, spelled bytes, the
 counters of the mode; then per mode a line with the median of the runs behind the warm-up runs.
 
@@ -30,7 +34,7 @@ Every mode runs in a child process of its own under its own time limit, one afte
 runs out of time nothing more is started.  --package-root times the library of another checkout on this tree's inputs (only
 keyword arguments of HipDecomposer.call that every build with the mode has are used).
 
-    python tools/time_calls.py --workload chain|inverted|skip|tandem|complex|insertions|looped [--modes plain,nested] [--size 1.0] [--warmup 2] [--runs 7]
+    python tools/time_calls.py --workload chain|inverted|skip|tandem|complex|insertions|looped|braid [--modes plain,nested] [--size 1.0] [--warmup 2] [--runs 7]
                                [--max-length 64] [--limit 300] [--package-root <another checkout>]
 """
 import argparse
@@ -44,9 +48,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2", "offref", "untangled", "region")
+MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2", "offref", "untangled", "region", "cluster")
 DEFAULT_MODES = dict(chain=("plain",), inverted=("plain", "inversions"), skip=("plain", "nested", "popped"), tandem=("plain", "normalized"),
-                     complex=("plain", "decomposed", "merged"), insertions=("plain", "offref"), looped=("plain", "untangled"))
+                     complex=("plain", "decomposed", "merged"), insertions=("plain", "offref"), looped=("plain", "untangled"), braid=("plain", "cluster"))
 
 
 def _load(package_root):
@@ -88,6 +92,10 @@ def workload(W, name, size):
         sites = max(2, int(100000 * size))
         g, p = W.vntr_haplotypes(sites, 32, 6, 1, reverse_every=4)
         return g, p, W.random_sequences(g, 5, max_len=16), "hap0#"
+    if name == "braid":
+        sites = max(2, int(20000 * size))
+        g = W.braid(sites, 24, 2, seed=1)
+        return g, W.braid_haplotypes(sites, 24, 2, 64, seed=1, mutate=0.02), W.random_sequences(g, 5, max_len=16), "hap0#"
     if name == "complex":
         units = max(2, int(100000 * size))
         g, seqs = W.complex_alleles(units, 1)
@@ -122,13 +130,13 @@ def child(a):
               popped=lambda: dict(profile="popped", max_level=0, max_ref_length=a.max_length, max_allele_length=a.max_length),
               normalized=lambda: dict(profile="left-normalized"), decomposed=lambda: dict(profile="decomposed"),
               merged=lambda: dict(profile="decomposed", flags=H.T_MERGE), offref=lambda: dict(flags=H.T_OFFREF), untangled=lambda: dict(flags=H.T_UNTANGLE),
-              region=lambda: dict(regions=[middle_region(g, p, seqs, ref)]),
+              region=lambda: dict(regions=[middle_region(g, p, seqs, ref)]), cluster=lambda: dict(cluster=900000),
               **{"decomposed-tier2": lambda: dict(profile="decomposed", flags=H.T_FORCE_TIER2)})[a.child]()
     counters = ("n_inv_records", "n_inv_tier2", "n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "n_normalized", "max_shift",
                 "n_norm_compared", "n_rows", "n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells", "n_mrows",
                 "n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts", "n_offref_sites", "n_offref_records", "n_offref_hosted",
                 "n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback", "n_regions", "n_region_sites", "n_region_masked",
-                "n_region_dropped")
+                "n_region_dropped") + tuple(getattr(H, "CLUSTER_COUNTERS", ()))
     for run in range(a.warmup + a.runs):
         t0 = time.perf_counter()
         c = d.call(f, [ref], **kw)
@@ -136,7 +144,7 @@ def child(a):
         print(json.dumps(dict(
             workload=a.workload, mode=a.child, run=run, warmup=run < a.warmup, segments=g.n_vtx, links=g.n_links, paths=len(p),
             path_steps=p.n_steps, records=c.n_records, slots=c.n_slots, spelled_bytes=c.n_seq_bytes, at_bytes=c.n_at_bytes,
-            device_ms=round(c.device_ms, 3), wall_ms=round(wall, 2), generate_s=round(gen_s, 1),
+            alts=int(c.ac_off[-1]) if c.n_records else 0, device_ms=round(c.device_ms, 3), wall_ms=round(wall, 2), generate_s=round(gen_s, 1),
             **{k: int(getattr(c, k, 0)) for k in counters})), flush=True)
         del c
     d.close()
