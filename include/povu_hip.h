@@ -938,6 +938,34 @@ int povu_hip_debug_walk_words(povu_hip_ctx *ctx, uint32_t out[3]);
 int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t *tree_vtx, uint32_t *cls,
 			 uint32_t *next_seen);
 
+/* ---- rows A and B alone (graph_kernels.hip; tests/test_gpu_rowb.py) ----
+ * Both read arrays the context owns (the resident graph, the row-B workspace), so no guard bands lie around them.
+ * 0 = ok, 1 = bad arguments or no graph resident, 2 = device error. */
+/* What the last upload left: off [2 * n_vtx + 1]; adj / aoth / atwin [off[2 * n_vtx]] (room for 2 * n_links words each);
+ * tip [n_vtx]; words = { adjacency slots, most links on one segment, sides without links, 1 when the slot fill built the
+ * adjacency lists / 0 when the radix sort did }.  Read-only: no kernel is launched. */
+int povu_hip_debug_csr(povu_hip_ctx *ctx, uint32_t *off, uint32_t *adj, uint32_t *aoth, uint32_t *atwin, uint8_t *tip,
+		       uint32_t words[4]);
+/* Runs the row-B step of a pass (labelling, speculative adjacency, re-index: the pass's own function, behind the pass's
+ * own workspace set-up) on the resident graph under the pass flags `flags`, and exports what it left.  The caller gives
+ * room for the largest case: voff / eoff / start_key n_vtx + 1 entries (n_components + 1, n_components + 1 and
+ * n_components are written; a start key of ~0 = the component has no tip), comp / pos n_vtx (0-based component and sorted
+ * position of every segment), loff 2 * n_vtx + 1 (offsets of the local side lists, by sorted side), ladj / lle 2 * n_links
+ * (n_local_slots are written: other sorted side and link word of every local slot).  stats0 = stats[0] as the stages read
+ * it, n_cross = the length of the union-find's cross list.  Invalidates the state of the last pass. */
+#define POVU_HIP_ROWB_IDENTITY 1u      /* one component, or the segments already in (component, idx) order */
+#define POVU_HIP_ROWB_SORT_FREE 2u     /* the sort-free adjacency builder (k_local_adj) */
+#define POVU_HIP_ROWB_LEAN_IDENTITY 4u /* both: sorted space is the global vertex space, nothing is renumbered */
+#define POVU_HIP_ROWB_SELF_LOOPS 8u    /* the labelling saw a self loop */
+#define POVU_HIP_ROWB_DENSE_EDGES 16u  /* the builder that numbers the local links densely ran */
+#define POVU_HIP_ROWB_SPEC_KEPT 32u    /* the adjacency written ahead of the component count was kept */
+typedef struct {
+	uint32_t n_components, n_local_slots, stats0, path_bits, n_cross;
+	uint32_t *voff, *eoff, *comp, *pos, *loff, *ladj, *lle;
+	uint64_t *start_key;
+} povu_hip_rowb;
+int povu_hip_debug_row_b(povu_hip_ctx *ctx, uint32_t flags, povu_hip_rowb *out);
+
 /* ---- unit-test hooks for the device-wide primitives (primitives.hip; tests/test_gpu_primitives.py) ----
  * Each call works in device memory of its own and uses nothing of the context but its stream.  The primitive's scratch
  * has exactly the size the primitive asks for and is filled with a non-zero byte before the call; every device output

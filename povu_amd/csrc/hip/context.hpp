@@ -466,5 +466,16 @@ struct RowBNeeds {
 };
 size_t rowb_carve_label(Arena *ar, const Sizes &z, CompState &cs);
 size_t rowb_carve_reindex(Arena *ar, const Sizes &z, size_t C, const RowBNeeds &need, CompState &cs);
+// The head of a pass (povu_hip.hip), shared by povu_hip_decompose and povu_hip_debug_row_b: the plan the flags make,
+// the set-up ahead of row B, and row B itself -- the component count at once, the components' sizes in page-locked scratch
+// once `sizes` is waited for.
+struct RowB {
+	uint32_t C;
+	const uint32_t *voff, *eoff, *gstats;
+	HostScratch::Token sizes;
+};
+PassPlan plan_pass(const povu_hip_opts *opts);
+Sizes rowb_begin(povu_hip_ctx *ctx, const PassPlan &p);
+RowB row_b(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, StageTimer &tm);
 // Workspace carving (or just measuring when `ar` is null); part 0 = rows A/B state (CompState), see povu_hip.hip
 size_t carve_workspace(Arena *ar, int part, const Sizes &z, CompState &cs, SeqWs &sw, bool hairpins);

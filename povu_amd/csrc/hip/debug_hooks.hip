@@ -621,6 +621,83 @@ extern "C" int povu_hip_debug_components(povu_hip_ctx *ctx, uint32_t *comp_of, u
 	}
 }
 
+// ---- rows A and B alone.  Both hooks read arrays the context owns (the resident graph, the row-B workspace): there is no
+// buffer of their own to put between guard bands.
+extern "C" int povu_hip_debug_csr(povu_hip_ctx *ctx, uint32_t *off, uint32_t *adj, uint32_t *aoth, uint32_t *atwin, uint8_t *tip,
+				  uint32_t words[4])
+{
+	if (!ctx || !ctx->g.block || !off || !adj || !aoth || !atwin || !tip || !words)
+		return 1;
+	ctx->quiesce();
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		const ResidentGraph &g = ctx->g;
+		const size_t V = g.V, n = g.n_slots;
+		HIP_CHECK(hipMemcpy(off, g.off, (2 * V + 1) * 4, hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(tip, g.tip, V, hipMemcpyDeviceToHost));
+		if (n) {
+			HIP_CHECK(hipMemcpy(adj, g.adj, n * 4, hipMemcpyDeviceToHost));
+			HIP_CHECK(hipMemcpy(aoth, g.aoth, n * 4, hipMemcpyDeviceToHost));
+			HIP_CHECK(hipMemcpy(atwin, g.atwin, n * 4, hipMemcpyDeviceToHost));
+		}
+		words[0] = g.n_slots, words[1] = g.max_vdeg, words[2] = g.n_empty_sides, words[3] = g.slot_fill ? 1u : 0u;
+		return 0;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
+extern "C" int povu_hip_debug_row_b(povu_hip_ctx *ctx, uint32_t flags, povu_hip_rowb *out)
+{
+	if (!ctx || !ctx->g.block || !out || !out->voff || !out->eoff || !out->comp || !out->pos || !out->loff || !out->ladj || !out->lle ||
+	    !out->start_key)
+		return 1;
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		ctx->wait_tail();
+		const povu_hip_opts o{0, 1, flags};
+		const PassPlan p = plan_pass(&o);
+		const Sizes z = rowb_begin(ctx, p); // (forgets the pass before: ctx->last)
+		const RowB rb = row_b(ctx, p, z, ctx->timer);
+		ctx->host.wait(rb.sizes);
+		hipStream_t s = ctx->stream;
+		HIP_CHECK(hipStreamSynchronize(s));
+		const ResidentGraph &g = ctx->g;
+		const CompState &cs = ctx->cs;
+		const size_t V = g.V, C = rb.C, nS = 2 * V;
+		out->n_components = rb.C;
+		out->stats0 = rb.gstats[0];
+		out->n_cross = cs.n_cross;
+		const bool identity = rb.C == 1 || cs.comp_sorted;
+		out->path_bits = (identity ? POVU_HIP_ROWB_IDENTITY : 0u) | (sort_free_adjacency(g, p.sorted_adj) ? POVU_HIP_ROWB_SORT_FREE : 0u) |
+				 (cs.lean_identity ? POVU_HIP_ROWB_LEAN_IDENTITY : 0u) | (cs.has_self_loops ? POVU_HIP_ROWB_SELF_LOOPS : 0u) |
+				 (cs.dense_edges ? POVU_HIP_ROWB_DENSE_EDGES : 0u) | (cs.spec_adj_kept ? POVU_HIP_ROWB_SPEC_KEPT : 0u);
+		std::copy(rb.voff, rb.voff + C + 1, out->voff); // (as the pass reads them: published into page-locked memory)
+		std::copy(rb.eoff, rb.eoff + C + 1, out->eoff);
+		HIP_CHECK(hipMemcpy(out->comp, cs.comp_of, V * 4, hipMemcpyDeviceToHost));
+		if (cs.lean_identity)
+			std::iota(out->pos, out->pos + V, 0u);
+		else
+			HIP_CHECK(hipMemcpy(out->pos, cs.pos, V * 4, hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(out->loff, cs.loff, (nS + 1) * 4, hipMemcpyDeviceToHost));
+		const size_t n = out->loff[nS];
+		out->n_local_slots = (uint32_t)n;
+		if (n > 2 * (size_t)g.E)
+			return 2; // (more local slots than two a link: the caller's arrays would not hold them)
+		if (n) {
+			HIP_CHECK(hipMemcpy(out->ladj, cs.ladj, n * 4, hipMemcpyDeviceToHost));
+			HIP_CHECK(hipMemcpy(out->lle, cs.lle, n * 4, hipMemcpyDeviceToHost));
+		}
+		if (C)
+			HIP_CHECK(hipMemcpy(out->start_key, cs.start_key, C * 8, hipMemcpyDeviceToHost));
+		return 0;
+	} catch (const std::exception &) {
+		if (ctx->stream)
+			(void)hipStreamSynchronize(ctx->stream);
+		return 2;
+	}
+}
+
 extern "C" int povu_hip_debug_tree(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, uint32_t *gid, uint8_t *typ,
 				   uint32_t *par, uint32_t *cls)
 {

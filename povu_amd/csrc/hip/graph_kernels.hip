@@ -886,7 +886,8 @@ void build_global_csr(ResidentGraph &g, Arena &tmp_arena, hipStream_t s)
 	if (hw[2] != POVU_NIL)
 		throw HipError("bad tip mark");
 	g.n_slots = hw[0];
-	if (g.n_slots && hw[3] <= FILL_MAX_SIDE_DEGREE) {
+	g.slot_fill = g.n_slots && hw[3] <= FILL_MAX_SIDE_DEGREE;
+	if (g.slot_fill) {
 		HIP_CHECK(hipMemsetAsync(deg, 0, (nS + 1) * 4, s)); // (the degrees live on in g.off: the array now counts filled slots)
 		KLAUNCH(k_slot_fill, dim3(nblk(E)), dim3(TPB), 0, s, E, g.v1, g.s1, g.v2, g.s2, g.off, deg, g.adj);
 		KLAUNCH(k_side_sort, dim3(nblk(nS)), dim3(TPB), 0, s, (uint32_t)nS, g.off, g.adj);
@@ -939,14 +940,15 @@ uint32_t *label_components_enqueue(const ResidentGraph &g, CompState &st, StageT
 	KLAUNCH(k_labels_sorted, dim3(nblk(V)), dim3(TPB), 0, s, V, st.label, st.stats + 9);
 	scan_exclusive_u8(is_root, st.crank, (size_t)V + 1, nullptr, nullptr, 0, st.scan_tmp, st.scan_tmp_bytes, s);
 	tm.end(7);
-	uint32_t *h = st.host->take<uint32_t>(3); // component count, the order flag and the self-loop flag in one round trip
-	publish_words(h, WordSrc{{st.crank + V, st.stats + 9, any_loop}}, 3, s);
+	uint32_t *h = st.host->take<uint32_t>(4); // component count, the order flag, the self-loop flag and the length of the cross list in one round trip
+	publish_words(h, WordSrc{{st.crank + V, st.stats + 9, any_loop, xcount}}, 4, s);
 	return h; // (valid once the stream -- or an event recorded now -- has completed: label_components_finish)
 }
 uint32_t label_components_finish(CompState &st, const uint32_t *h)
 {
 	st.comp_sorted = h[1] == 0;
 	st.has_self_loops = h[2] != 0;
+	st.n_cross = h[3];
 	return h[0];
 }
 uint32_t label_components(const ResidentGraph &g, CompState &st, StageTimer &tm, hipStream_t s)
@@ -981,6 +983,7 @@ void reindex_components(const ResidentGraph &g, CompState &st, uint32_t C, Stage
 	// space is the global vertex space.  The sort-free builder then needs no permutation, position, slot-base, id or tip
 	// array at all -- it reads the resident graph's own (slot base of vertex i = off[2 i]).
 	st.lean_identity = identity && sort_free;
+	st.spec_adj_kept = adj_done && st.lean_identity && !st.has_self_loops; // (adj_done: reindex_speculative_adj wrote exactly this into ladj / lle)
 	KLAUNCH(k_comp_of, dim3(nblk(((size_t)V + 3) / 4)), dim3(TPB), 0, s, V, st.label, st.crank, st.comp_of, st.lean_identity ? nullptr : st.tmp_a, C,
 			   (unsigned long long *)st.start_key);
 	if (identity) { // the key / permutation arrays simply alias what k_comp_of wrote (component ranks, identity permutation)
@@ -1012,7 +1015,7 @@ void reindex_components(const ResidentGraph &g, CompState &st, uint32_t C, Stage
 			KLAUNCH(k_local_degree, dim3(nblk(nS)), dim3(TPB), 0, s, V, perm, pos_or_identity, g.off, g.aoth, ldeg8, st.stats);
 			scan_exclusive_u8(ldeg8, st.loff, nS + 1, nullptr, nullptr, 0, st.scan_tmp, st.scan_tmp_bytes, s);
 		}
-		if (!(adj_done && st.lean_identity && !st.has_self_loops)) // (adj_done: reindex_speculative_adj wrote exactly this into ladj / lle)
+		if (!st.spec_adj_kept)
 			KLAUNCH(k_local_adj, dim3(nblk(nS)), dim3(TPB), 0, s, V, perm, pos_or_identity, g.off, g.aoth, g.atwin, sbase,
 				   st.loff, st.hook, st.ladj, st.lle, st.has_self_loops);
 		KLAUNCH(k_comp_edge_offsets, dim3(nblk((size_t)C + 1)), dim3(TPB), 0, s, C, st.voff, st.loff, st.eoff, st.stats,

@@ -21,6 +21,7 @@ struct ResidentGraph {
 	uint32_t *atwin = nullptr;		    // [n_slots] the slot of the same link at its other end (itself for a same-side self loop)
 	uint32_t max_vdeg = 0;			    // most links on one vertex (both sides)
 	uint32_t n_empty_sides = 0;		    // sides without links (each may start one back edge to the root, spanning_tree.cpp:433-438)
+	bool slot_fill = false;			    // the adjacency lists came from the slot fill + insertion sort (else: the radix sort)
 	// device time of the last upload, by HIP events: host-to-device copies, CSR build, reverse-slot table
 	float h2d_ms = 0, csr_ms = 0, twin_ms = 0;
 	void *block = nullptr;			    // one allocation backing all of the above
@@ -52,6 +53,8 @@ struct CompState {
 	size_t scan_tmp_bytes, sort_tmp_bytes;
 	bool lean_identity; // sorted space = global vertex space and no perm / pos / sbase / vdeg was written (gid_s / tip_s alias the graph's)
 	bool comp_sorted;   // the vertices already are in (component, idx) order: re-indexing keeps every vertex where it is
+	bool spec_adj_kept; // the re-index kept the adjacency reindex_speculative_adj wrote ahead of it
+	uint32_t n_cross;   // length of the union-find's cross list (links whose ends lie in different tiles)
 	HostScratch *host;  // pinned read-back scratch of the owning context
 	uint32_t *host_pub; // device view of a pinned [voff C+1 | eoff C+1 | stats 4] the re-index publishes into (or null)
 };

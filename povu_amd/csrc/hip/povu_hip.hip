@@ -654,9 +654,11 @@ namespace
 static const char *const SUB_REDO_REFUSAL = "subflubble passes: a component went (or was sent) through the sequential redo of add_flubbles, "
 					    "whose PVST layout the inserting passes do not read";
 
+} // namespace
+
 // Every decision a pass takes from its options, in one place.  Refusals that depend on the flags alone are made here;
 // those that depend on what the pass finds (a component the laminarity check flags) where it finds it.
-static PassPlan plan_pass(const povu_hip_opts *opts)
+PassPlan plan_pass(const povu_hip_opts *opts)
 {
 	povu_hip_opts o{0, 1, 0};
 	if (opts)
@@ -687,6 +689,8 @@ static PassPlan plan_pass(const povu_hip_opts *opts)
 	return p;
 }
 
+namespace
+{
 // The tail of the pass before (POVU_HIP_F_ASYNC) reads the stage workspace (ws2) from the side stream.  A pass that may
 // itself overlap waits for it ON THE STREAM, right before its own first write there (carve_stages, component_tables);
 // every other pass -- and any pass whose arenas must grow, which frees them -- waits on the host.
@@ -697,12 +701,23 @@ static void reserve(povu_hip_ctx *ctx, Arena &ar, size_t bytes)
 	ar.reserve(bytes);
 }
 
-// What row B publishes: the component count, and the components' sizes in page-locked scratch once `sizes` is waited for.
-struct RowB {
-	uint32_t C;
-	const uint32_t *voff, *eoff, *gstats;
-	HostScratch::Token sizes;
-};
+} // namespace
+
+// ---- what a pass sets up ahead of row B: the state of the pass before is forgotten, the pinned scratch rewound, the
+// labelling's arrays carved (sized before the component count is known) and the stage timer armed
+Sizes rowb_begin(povu_hip_ctx *ctx, const PassPlan &p)
+{
+	const ResidentGraph &g = ctx->g;
+	const Sizes z{g.V, g.E, g.V, 0, 0, 2 * (size_t)g.V, g.n_slots}; // (rows A/B run before the component count is known)
+	ctx->last = LastPass{};
+	ctx->host.reset();
+	ctx->cs.host = ctx->pw.host = ctx->tw.host = &ctx->host;
+	reserve(ctx, ctx->ws, rowb_carve_label(nullptr, z, ctx->cs));
+	rowb_carve_label(&ctx->ws, z, ctx->cs);
+	ctx->timer.reset();
+	ctx->timer.enabled = p.timed;
+	return z;
+}
 
 // ---- row B: labelling, speculative adjacency, re-index
 // The host has to know the component count (it sizes the workspaces) and then the components' sizes (the tables of the
@@ -713,7 +728,7 @@ struct RowB {
 //      assumption fails its output is simply overwritten by the real re-index);
 //  (2) behind the re-index: the tree stage's first kernel (it reads the re-indexed adjacency only; carve_stages).
 // Not with stage timers (the kernels would be booked on the wrong stage).
-static RowB row_b(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, StageTimer &tm)
+RowB row_b(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, StageTimer &tm)
 {
 	const ResidentGraph &g = ctx->g;
 	CompState &cs = ctx->cs;
@@ -748,6 +763,8 @@ static RowB row_b(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, StageTim
 	return RowB{C, pub, pub + (size_t)C + 1, pub + 2 * ((size_t)C + 1), ctx->host.mark(s)};
 }
 
+namespace
+{
 // ---- stage workspaces, sized with the real component count (z), and the tree stage's first kernel, which goes out
 // before the host waits for the component sizes.  Returns whether the stream already waits for the tail of the pass before.
 static bool carve_stages(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, uint32_t C, const StageTimer &tm)
@@ -1279,15 +1296,8 @@ extern "C" povu_hip_forest *povu_hip_decompose(povu_hip_ctx *ctx, const povu_hip
 		if (!p.overlap_tail)
 			ctx->wait_tail();
 		const ResidentGraph &g = ctx->g;
-		Sizes z{g.V, g.E, g.V, 0, 0, 2 * (size_t)g.V, g.n_slots}; // (rows A/B run before the component count is known)
-		ctx->last = LastPass{};
-		ctx->host.reset();
-		ctx->cs.host = ctx->pw.host = ctx->tw.host = &ctx->host;
-		reserve(ctx, ctx->ws, rowb_carve_label(nullptr, z, ctx->cs));
-		rowb_carve_label(&ctx->ws, z, ctx->cs);
+		Sizes z = rowb_begin(ctx, p);
 		StageTimer &tm = ctx->timer;
-		tm.reset();
-		tm.enabled = p.timed;
 		// the forest owns the two events that time its pass: ev0 at the first kernel, ev1 behind the last byte that reaches the host
 		f = std::make_unique<povu_hip_forest>();
 		f->pool = ctx->pool;

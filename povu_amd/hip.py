@@ -216,6 +216,19 @@ class _ArenaInfo(C.Structure):
     _fields_ = [("name", C.c_char * 24), ("resident", C.c_int), ("bytes", C.c_uint64)]
 
 
+class _Components(C.Structure):
+    _fields_ = [("n_components", C.c_uint32), ("n_vtx", C.c_uint32), ("n_links", C.c_uint32),
+                ("vtx_off", C.POINTER(C.c_uint32)), ("link_off", C.POINTER(C.c_uint32)), ("vtx_id", C.POINTER(C.c_uint32)),
+                ("vtx_tip", C.POINTER(C.c_uint8)), ("l_v1", C.POINTER(C.c_uint32)), ("l_v2", C.POINTER(C.c_uint32)),
+                ("l_s1", C.POINTER(C.c_uint8)), ("l_s2", C.POINTER(C.c_uint8))]
+
+
+class _RowB(C.Structure):
+    _fields_ = [("n_components", C.c_uint32), ("n_local_slots", C.c_uint32), ("stats0", C.c_uint32), ("path_bits", C.c_uint32),
+                ("n_cross", C.c_uint32), ("voff", C.c_void_p), ("eoff", C.c_void_p), ("comp", C.c_void_p), ("pos", C.c_void_p),
+                ("loff", C.c_void_p), ("ladj", C.c_void_p), ("lle", C.c_void_p), ("start_key", C.c_void_p)]
+
+
 F_HAIRPINS = 1
 F_SEQUENTIAL = 2
 F_SEQ_TREE = 4
@@ -230,6 +243,10 @@ F_CHECK_LAMINAR = 1024
 F_LEAF_SUBFLUBBLES = 2048
 F_ASYNC = 4096
 F_SUBFLUBBLES = 8192  # all five passes of -s (implies F_LEAF_SUBFLUBBLES): Forest.texts() then carry C / M / S lines
+
+# HipDecomposer.debug_row_b: the path row B took (povu_hip_rowb.path_bits), and the two parts of a word of `lle`
+ROWB_IDENTITY, ROWB_SORT_FREE, ROWB_LEAN_IDENTITY, ROWB_SELF_LOOPS, ROWB_DENSE_EDGES, ROWB_SPEC_KEPT = 1, 2, 4, 8, 16, 32
+LLE_ID, LLE_TREE = 0x1FFFFFFF, 0x40000000
 
 W_FORCE_TIER2 = 1  # HipDecomposer.walks: every query through the second-tier kernel (tests)
 WALK_MORE, WALK_LONG, WALK_BUDGET = 1, 2, 4  # status bits of a query
@@ -378,6 +395,14 @@ def load_lib():
     l.povu_hip_last_links_processed.argtypes = [C.c_void_p]
     l.povu_hip_debug_components.restype = C.c_int
     l.povu_hip_debug_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    l.povu_hip_debug_csr.restype = C.c_int
+    l.povu_hip_debug_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    l.povu_hip_debug_row_b.restype = C.c_int
+    l.povu_hip_debug_row_b.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_RowB)]
+    l.povu_hip_componetize.restype = C.POINTER(_Components)
+    l.povu_hip_componetize.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+    l.povu_hip_components_free.restype = None
+    l.povu_hip_components_free.argtypes = [C.POINTER(_Components)]
     l.povu_hip_debug_tree.restype = C.c_int
     l.povu_hip_debug_tree.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]
@@ -1723,6 +1748,56 @@ class HipDecomposer:
         if self._lib.povu_hip_debug_components(self._ctx, comp.ctypes.data, loc.ctypes.data) != 0:
             raise RuntimeError("no decompose state")
         return comp, loc
+
+    def componetize(self) -> dict:
+        """Row B on its own (povu_hip_componetize): the components as bd::VG::componetize builds them.  vtx_off / link_off
+        [C + 1]; vtx_id / vtx_tip by local vertex order, component-major; the local links (v1, s1, v2, s2) in local link order,
+        with LOCAL vertex indices."""
+        err = C.create_string_buffer(512)
+        p = self._lib.povu_hip_componetize(self._ctx, err, 512)
+        if not p:
+            raise RuntimeError(err.value.decode())
+        try:
+            c = p.contents
+            nc, nv, ne = c.n_components, c.n_vtx, c.n_links
+            return dict(n_components=nc, vtx_off=_view(c.vtx_off, nc + 1, np.uint32).copy(), link_off=_view(c.link_off, nc + 1, np.uint32).copy(),
+                        vtx_id=_view(c.vtx_id, nv, np.uint32).copy(), vtx_tip=_view(c.vtx_tip, nv, np.uint8).copy(),
+                        v1=_view(c.l_v1, ne, np.uint32).copy(), v2=_view(c.l_v2, ne, np.uint32).copy(),
+                        s1=_view(c.l_s1, ne, np.uint8).copy(), s2=_view(c.l_s2, ne, np.uint8).copy())
+        finally:
+            self._lib.povu_hip_components_free(p)
+
+    def debug_csr(self, n_vtx: int, n_links: int) -> dict:
+        """What the last upload left (povu_hip_debug_csr): off, adj, aoth, atwin, tip, max_vdeg, n_empty_sides and slot_fill
+        (True: slot fill + insertion sort built the lists; False: the radix sort)."""
+        off = np.zeros(2 * n_vtx + 1, dtype=np.uint32)
+        adj, aoth, atwin = (np.zeros(2 * n_links, dtype=np.uint32) for _ in range(3))
+        tip = np.zeros(n_vtx, dtype=np.uint8)
+        w = (C.c_uint32 * 4)()
+        if self._lib.povu_hip_debug_csr(self._ctx, off.ctypes.data, adj.ctypes.data, aoth.ctypes.data, atwin.ctypes.data,
+                                        tip.ctypes.data, w) != 0:
+            raise RuntimeError("povu_hip_debug_csr failed")
+        n = int(w[0])
+        return dict(off=off, adj=adj[:n], aoth=aoth[:n], atwin=atwin[:n], tip=tip, n_slots=n, max_vdeg=int(w[1]),
+                    n_empty_sides=int(w[2]), slot_fill=bool(w[3]))
+
+    def debug_row_b(self, n_vtx: int, n_links: int, flags: int = 0) -> dict:
+        """Runs the row-B step of a pass on the resident graph under the pass flags (povu_hip_debug_row_b) and returns what
+        it left: C, voff, eoff, comp / pos of every segment, loff / ladj / lle over the local slots, start_key [C] (~0: no
+        tip), stats0, the ROWB_* path bits and n_cross."""
+        voff, eoff = np.zeros(n_vtx + 1, dtype=np.uint32), np.zeros(n_vtx + 1, dtype=np.uint32)
+        comp, pos = np.zeros(n_vtx, dtype=np.uint32), np.zeros(n_vtx, dtype=np.uint32)
+        loff = np.zeros(2 * n_vtx + 1, dtype=np.uint32)
+        ladj, lle = np.zeros(2 * n_links, dtype=np.uint32), np.zeros(2 * n_links, dtype=np.uint32)
+        key = np.zeros(n_vtx + 1, dtype=np.uint64)
+        r = _RowB(0, 0, 0, 0, 0, voff.ctypes.data, eoff.ctypes.data, comp.ctypes.data, pos.ctypes.data, loff.ctypes.data,
+                  ladj.ctypes.data, lle.ctypes.data, key.ctypes.data)
+        rc = self._lib.povu_hip_debug_row_b(self._ctx, flags, C.byref(r))
+        if rc != 0:
+            raise RuntimeError(f"povu_hip_debug_row_b failed ({rc})")
+        nc, n = r.n_components, r.n_local_slots
+        return dict(C=nc, voff=voff[:nc + 1], eoff=eoff[:nc + 1], comp=comp, pos=pos, loff=loff, ladj=ladj[:n], lle=lle[:n],
+                    start_key=key[:nc], stats0=r.stats0, bits=r.path_bits, n_cross=r.n_cross)
 
     def debug_tree(self, comp: int):
         n = C.c_uint32(0)
