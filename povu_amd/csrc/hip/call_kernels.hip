@@ -36,6 +36,7 @@
 // What stays a nested call's alone: PS, levels, parents and TANGLED on a collapse.  Per record the call then also says whether
 // its site lost alleles, the site's lowest similarity and the exact alleles behind every written allele (k_cl_provenance).
 #include "call_common.hpp"
+#include "call_modes.hpp"
 #include "cluster_kernels.hpp"
 #include "cluster_rules.hpp"
 #include "merge_kernels.hpp"
@@ -641,7 +642,8 @@ struct CallSpelled {
 
 // the host-side refusals and the host tables
 CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs, const uint32_t *slot_of_path,
-			     const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile, const povu_hip_call_cluster_opts *cluster)
+			     const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile, const povu_hip_call_regions *regions,
+			     const povu_hip_call_cluster_opts *cluster)
 {
 	if (!ctx || !sites || !refs)
 		throw HipError("null context, sites or references");
@@ -653,40 +655,24 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 		throw HipError("no paths are resident for the graph now uploaded (povu_hip_paths_upload after povu_hip_graph_upload)");
 	CallInputs in{sites, refs, slot_of_path, opts, sites->n, ctx->n_paths, refs->n_refs, refs->n_slots, refs->n_samples};
 	const uint32_t n = in.n, P = in.P, nR = in.nR, S = in.S, NS = in.NS;
-	in.inversions = opts && (opts->flags & POVU_HIP_T_INVERSIONS);
+	const uint32_t tflags = opts ? opts->flags : 0;
 	in.prof = profile ? *profile : povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 	if (in.prof.profile > POVU_HIP_PROFILE_DECOMPOSED)
 		throw HipError("unknown profile " + std::to_string(in.prof.profile));
-	in.offref = opts && (opts->flags & POVU_HIP_T_OFFREF);
-	if (in.offref) {
-		static const char *const name[] = {"raw-graph", "top-level-only", "popped", "left-normalized", "decomposed"};
-		if (opts->flags & POVU_HIP_T_NESTED)
-			throw HipError("POVU_HIP_T_OFFREF (off-reference calls) is refused together with POVU_HIP_T_NESTED");
-		if (opts->flags & POVU_HIP_T_MERGE)
-			throw HipError("POVU_HIP_T_OFFREF (off-reference calls) is refused together with POVU_HIP_T_MERGE");
-		if (in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
-			throw HipError(std::string("POVU_HIP_T_OFFREF (off-reference calls) is refused with profile ") + name[in.prof.profile] +
-				       ": only raw-graph");
-	}
-	in.untangle = opts && (opts->flags & POVU_HIP_T_UNTANGLE);
-	if (in.untangle) {
-		static const char *const name[] = {"raw-graph", "top-level-only", "popped", "left-normalized", "decomposed"};
-		if (opts->flags & POVU_HIP_T_NESTED)
-			throw HipError("POVU_HIP_T_UNTANGLE (untangled calls) is refused together with POVU_HIP_T_NESTED");
-		if (opts->flags & POVU_HIP_T_MERGE)
-			throw HipError("POVU_HIP_T_UNTANGLE (untangled calls) is refused together with POVU_HIP_T_MERGE");
-		if (opts->flags & POVU_HIP_T_OFFREF)
-			throw HipError("POVU_HIP_T_UNTANGLE (untangled calls) is refused together with POVU_HIP_T_OFFREF");
-		if (in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
-			throw HipError(std::string("POVU_HIP_T_UNTANGLE (untangled calls) is refused with profile ") + name[in.prof.profile] +
-				       ": only raw-graph");
-	}
-	in.normalized = in.prof.profile == POVU_HIP_PROFILE_LEFT_NORMALIZED; // (keeps every record, ignores the limits, implies nothing)
-	in.decomposed = in.prof.profile == POVU_HIP_PROFILE_DECOMPOSED;	     // (the same; max_allele_length is the cap of the aligner)
-	in.merge = opts && (opts->flags & POVU_HIP_T_MERGE);
-	if (in.merge && !in.decomposed)
-		throw HipError(std::string("POVU_HIP_T_MERGE merges the rows of the decomposed profile: refused with profile ") +
-			       (const char *[]){"raw-graph", "top-level-only", "popped", "left-normalized"}[in.prof.profile]);
+	// which modes combine: call_modes.hpp.  The refusal is thrown at the stage its rule names, among the other checks
+	const uint32_t asked = in.prof.profile;
+	const modes::Rule *no = modes::refused(modes::LIBRARY, modes::set_of(tflags, regions && regions->n, cluster && cluster->min_similarity_ppm), asked);
+	auto refuse = [&](modes::Stage at) {
+		if (no && no->stage == at)
+			throw HipError(modes::message(*no, modes::LIBRARY, asked));
+	};
+	refuse(modes::AT_FLAGS);
+	in.inversions = tflags & POVU_HIP_T_INVERSIONS;
+	in.offref = tflags & POVU_HIP_T_OFFREF;
+	in.untangle = tflags & POVU_HIP_T_UNTANGLE;
+	in.merge = tflags & POVU_HIP_T_MERGE;
+	in.normalized = asked == POVU_HIP_PROFILE_LEFT_NORMALIZED; // (keeps every record, ignores the limits, implies nothing)
+	in.decomposed = asked == POVU_HIP_PROFILE_DECOMPOSED;	   // (the same; max_allele_length is the cap of the aligner)
 	if (in.decomposed) {
 		if (in.prof.max_allele_length > POVU_HIP_PRIM_MAX_LENGTH)
 			throw HipError("max_allele_length " + std::to_string(in.prof.max_allele_length) + " is above the ceiling " +
@@ -695,22 +681,17 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 	}
 	if (in.normalized || in.decomposed)
 		in.prof = povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
-	in.nested = (opts && (opts->flags & POVU_HIP_T_NESTED)) || in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH;
+	in.nested = (tflags & POVU_HIP_T_NESTED) || in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH;
 	if (cluster && cluster->min_similarity_ppm) {
 		const std::string who = "a clustered call (povu_hip_call_clustered) is refused ";
 		if (cluster->min_similarity_ppm > cluster::PPM)
 			throw HipError(who + "with a threshold of " + std::to_string(cluster->min_similarity_ppm) + " ppm: at most 1000000");
 		if (cluster->flags & ~POVU_HIP_CLUSTER_NO_BOUND)
 			throw HipError(who + "with unknown cluster flags");
-		if (in.nested)
-			throw HipError(who + "together with POVU_HIP_T_NESTED and the profiles that imply it");
-		if (in.normalized || in.decomposed)
-			throw HipError(who + "with profile " + (in.normalized ? "left-normalized" : "decomposed"));
-		if (in.merge || in.offref || in.untangle)
-			throw HipError(who + "together with " + (in.merge ? "POVU_HIP_T_MERGE" : in.offref ? "POVU_HIP_T_OFFREF" : "POVU_HIP_T_UNTANGLE"));
 		in.cluster_ppm = cluster->min_similarity_ppm;
 		in.cluster_no_bound = (cluster->flags & POVU_HIP_CLUSTER_NO_BOUND) != 0;
 	}
+	refuse(modes::AT_CLUSTER);
 	if (n >= 0x7FFFFFFFu)
 		throw HipError("too many sites");
 	if (n && (!sites->id1 || !sites->id2 || !sites->or1 || !sites->or2 || !sites->parent || !sites->family || !sites->tree))
@@ -744,6 +725,7 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 		in.qz[q] = sites->id2[q];
 		in.qor[q] = (uint8_t)((sites->or1[q] & 1u) | ((sites->or2[q] & 1u) << 1));
 	}
+	refuse(modes::AT_END);
 	return in;
 }
 
@@ -1327,40 +1309,15 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 	CallsOwner *raw = o.release();
 	return &raw->view;
 }
-} // namespace
 
-extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
-					 const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, char *err, size_t errlen)
-{
-	return povu_hip_call_profile(ctx, sites, refs, slot_of_path, opts, nullptr, err, errlen);
-}
-
-extern "C" povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
-						 const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
-						 const povu_hip_call_profile_opts *profile, char *err, size_t errlen)
-{
-	return povu_hip_call_restricted(ctx, sites, refs, slot_of_path, opts, profile, nullptr, err, errlen);
-}
-
-extern "C" povu_hip_calls *povu_hip_call_restricted(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
-						    const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
-						    const povu_hip_call_profile_opts *profile, const povu_hip_call_regions *regions, char *err,
-						    size_t errlen)
-{
-	return povu_hip_call_clustered(ctx, sites, refs, slot_of_path, opts, profile, regions, nullptr, err, errlen);
-}
-
-extern "C" povu_hip_calls *povu_hip_call_clustered(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
-						   const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
-						   const povu_hip_call_profile_opts *profile, const povu_hip_call_regions *regions,
-						   const povu_hip_call_cluster_opts *cluster, char *err, size_t errlen)
+// a call, with whatever of a profile, regions and a cluster threshold its entry point takes (NULL: none)
+povu_hip_calls *call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs, const uint32_t *slot_of_path,
+		     const povu_hip_trav_opts *opts, const povu_hip_call_profile_opts *profile, const povu_hip_call_regions *regions,
+		     const povu_hip_call_cluster_opts *cluster, char *err, size_t errlen)
 {
 	CallTimer timer;
 	return guarded_call(ctx, err, errlen, (povu_hip_calls *)nullptr, [&] {
-		const CallInputs in = check_call_inputs(ctx, sites, refs, slot_of_path, opts, profile, cluster);
-		if (in.offref && regions && regions->n)
-			throw HipError("regions (povu_hip_call_restricted) are refused together with POVU_HIP_T_OFFREF: an off-reference site has no "
-				       "locus on a region's path");
+		const CallInputs in = check_call_inputs(ctx, sites, refs, slot_of_path, opts, profile, regions, cluster);
 		// region calls: masking is allowed when the call is not nested (a nested call computes its classes over every site)
 		const RegionIn rin = region_prepare(ctx, regions, !in.nested);
 		RegionDevice rg;
@@ -1407,6 +1364,36 @@ extern "C" povu_hip_calls *povu_hip_call_clustered(povu_hip_ctx *ctx, const povu
 		const MergedRows mg = in.merge ? merge_rows(ctx, pin, pr) : MergedRows{};
 		return calls_to_host(ctx, in, w, inv, r, sp, pr, mg, orf, un, timer);
 	});
+}
+} // namespace
+
+extern "C" povu_hip_calls *povu_hip_call(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+					 const uint32_t *slot_of_path, const povu_hip_trav_opts *opts, char *err, size_t errlen)
+{
+	return call(ctx, sites, refs, slot_of_path, opts, nullptr, nullptr, nullptr, err, errlen);
+}
+
+extern "C" povu_hip_calls *povu_hip_call_profile(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+						 const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
+						 const povu_hip_call_profile_opts *profile, char *err, size_t errlen)
+{
+	return call(ctx, sites, refs, slot_of_path, opts, profile, nullptr, nullptr, err, errlen);
+}
+
+extern "C" povu_hip_calls *povu_hip_call_restricted(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+						    const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
+						    const povu_hip_call_profile_opts *profile, const povu_hip_call_regions *regions, char *err,
+						    size_t errlen)
+{
+	return call(ctx, sites, refs, slot_of_path, opts, profile, regions, nullptr, err, errlen);
+}
+
+extern "C" povu_hip_calls *povu_hip_call_clustered(povu_hip_ctx *ctx, const povu_hip_sites *sites, const povu_hip_call_refs *refs,
+						   const uint32_t *slot_of_path, const povu_hip_trav_opts *opts,
+						   const povu_hip_call_profile_opts *profile, const povu_hip_call_regions *regions,
+						   const povu_hip_call_cluster_opts *cluster, char *err, size_t errlen)
+{
+	return call(ctx, sites, refs, slot_of_path, opts, profile, regions, cluster, err, errlen);
 }
 
 extern "C" void povu_hip_calls_free(povu_hip_calls *c)

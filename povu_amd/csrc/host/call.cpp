@@ -4,6 +4,7 @@
 #include "decompose.hpp"
 #include "gfa.hpp"
 
+#include "../hip/call_modes.hpp"
 #include "povu_hip.h"
 
 #include <algorithm>
@@ -36,6 +37,13 @@ struct CallArgs {
 	uint32_t cluster_ppm = 0;	  // --cluster <F>: F * 10^6, 0 without the flag (INTEGRATION.md "Clustered calls")
 	povu_hip_call_profile_opts prof{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 };
+
+// the POVU_HIP_T_* flags of the call
+uint32_t call_flags(const CallArgs &c)
+{
+	return (c.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (c.nested ? POVU_HIP_T_NESTED : 0u) | (c.merge ? POVU_HIP_T_MERGE : 0u) |
+	       (c.offref ? POVU_HIP_T_OFFREF : 0u) | (c.untangle ? POVU_HIP_T_UNTANGLE : 0u);
+}
 
 CallArgs parse_call_args(const std::vector<std::string> &a)
 {
@@ -89,17 +97,11 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			c.untangle = true;
 		} else if (x == "--profile" || !x.compare(0, 10, "--profile=")) {
 			const std::string v = x == "--profile" ? need(i) : x.substr(10);
-			if (v == "raw-graph")
-				c.prof.profile = POVU_HIP_PROFILE_RAW_GRAPH;
-			else if (v == "top-level-only")
-				c.prof.profile = POVU_HIP_PROFILE_TOP_LEVEL_ONLY;
-			else if (v == "popped")
-				c.prof.profile = POVU_HIP_PROFILE_POPPED;
-			else if (v == "left-normalized")
-				c.prof.profile = POVU_HIP_PROFILE_LEFT_NORMALIZED;
-			else if (v == "decomposed")
-				c.prof.profile = POVU_HIP_PROFILE_DECOMPOSED;
-			else
+			uint32_t k = 0;
+			while (k < modes::N_PROFILES && v != modes::PROFILE_NAME[k])
+				k++;
+			c.prof.profile = k;
+			if (k == modes::N_PROFILES)
 				throw std::runtime_error("Flag '--profile' expects raw-graph, top-level-only, popped, left-normalized or decomposed, not " + v);
 		} else if (number(i, "--max-level", n64)) {
 			if (n64 > 0x7FFFFFFFull)
@@ -142,39 +144,12 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			by_pos = true;
 		}
 	}
-	if (c.cluster_ppm) { // clusters stand where a nested call's classes stand, and no rewriting profile reads them
-		static const char *const name[] = {"raw-graph", "top-level-only", "popped", "left-normalized", "decomposed"};
-		const char *with = c.nested			? "--nested"
-				   : c.merge			? "--merge-primitives"
-				   : c.offref			? "--off-reference"
-				   : c.untangle			? "--untangle"
-				   : !gpus.empty()		? "--gpus"
-								: nullptr;
-		if (c.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
-			throw std::runtime_error(std::string("Flag '--cluster' is called under --profile raw-graph alone, not ") + name[c.prof.profile]);
-		if (with)
-			throw std::runtime_error(std::string("Flag '--cluster' cannot be combined with ") + with);
-	}
-	if (!gpus.empty())
-		throw std::runtime_error("Flag could not be matched: " + gpus);
-	if (c.merge && c.prof.profile != POVU_HIP_PROFILE_DECOMPOSED)
-		throw std::runtime_error("Flag '--merge-primitives' merges the rows of --profile decomposed and needs that profile");
-	if (c.offref && c.nested)
-		throw std::runtime_error("Flag '--off-reference' cannot be combined with --nested");
-	if (c.offref && c.merge)
-		throw std::runtime_error("Flag '--off-reference' cannot be combined with --merge-primitives");
-	if (c.offref && c.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
-		throw std::runtime_error("Flag '--off-reference' is called under --profile raw-graph alone");
-	if (!c.regions.empty() && c.offref)
-		throw std::runtime_error("Flag '--region' cannot be combined with --off-reference");
-	if (c.untangle && c.nested)
-		throw std::runtime_error("Flag '--untangle' cannot be combined with --nested");
-	if (c.untangle && c.merge)
-		throw std::runtime_error("Flag '--untangle' cannot be combined with --merge-primitives");
-	if (c.untangle && c.offref)
-		throw std::runtime_error("Flag '--untangle' cannot be combined with --off-reference");
-	if (c.untangle && c.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH)
-		throw std::runtime_error("Flag '--untangle' is called under --profile raw-graph alone");
+	// which modes combine: call_modes.hpp.  --gpus belongs to `decompose`: behind the refusals of --cluster, in front of the others
+	const modes::Rule *no = modes::refused(modes::COMMAND_LINE, modes::set_of(call_flags(c), !c.regions.empty(), c.cluster_ppm != 0), c.prof.profile);
+	if (!gpus.empty() && !(no && no->who == modes::CLUSTER))
+		throw std::runtime_error(c.cluster_ppm ? "Flag '--cluster' cannot be combined with --gpus" : "Flag could not be matched: " + gpus);
+	if (no)
+		throw std::runtime_error(modes::message(*no, modes::COMMAND_LINE, c.prof.profile));
 	forms = (int)by_p + (int)!ref_file.empty() + (int)by_pos;
 	if (forms != 1)
 		throw std::runtime_error("call needs exactly one of the reference options: -r <file>, -P <prefix> (repeatable), or "
@@ -283,8 +258,7 @@ void do_call(const Config &cfg, const std::vector<std::string> &args)
 		fail("paths");
 	if (povu_hip_segments_upload(ctx, V, seq_off.data(), seq.data(), err, sizeof err) != 0)
 		fail("sequences");
-	const povu_hip_trav_opts opts{0, (ca.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (ca.nested ? POVU_HIP_T_NESTED : 0u) | (ca.merge ? POVU_HIP_T_MERGE : 0u) |
-						 (ca.offref ? POVU_HIP_T_OFFREF : 0u) | (ca.untangle ? POVU_HIP_T_UNTANGLE : 0u)};
+	const povu_hip_trav_opts opts{0, call_flags(ca)};
 	const povu_hip_call_cluster_opts cl{ca.cluster_ppm, 0};
 	povu_hip_calls *c = povu_hip_call_clustered(ctx, sites, &nm->refs, nm->slot_of_path, &opts, &ca.prof, regions.empty() ? nullptr : &rg,
 						    ca.cluster_ppm ? &cl : nullptr, err, sizeof err);

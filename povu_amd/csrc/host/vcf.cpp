@@ -2,6 +2,7 @@
 // PanSN slots, PVST vertices to sites, and the records of povu_hip_call to VCF text.  The one place that holds these rules
 // for `povu call` and for povu_amd/hip.py alike; tests/vcf_ref.py restates them as the yardstick.
 #include "../../../include/povu_hip.h"
+#include "../hip/call_modes.hpp"
 #include "../hip/cluster_rules.hpp"
 #include "../hip/region_rules.hpp"
 
@@ -34,7 +35,6 @@ const char *VCF_HEADER =
 	"##FORMAT=<ID=GT,Number=1,Type=String,Description=\"Genotype\">\n";
 // a nested call's own line ("Nested calls"), and the lines of the keys a profile appends (the reference fixture's texts)
 const char *PS_LINE = "##INFO=<ID=PS,Number=1,Type=String,Description=\"ID of the enclosing record of the same reference path\">\n";
-const char *PROFILE_NAME[] = {"raw-graph", "top-level-only", "popped", "left-normalized", "decomposed"};
 const char *PROFILE_LINES[] = {
 	"",
 	"##INFO=<ID=ORIGIN,Number=1,Type=String,Description=\"Raw record id\">\n"
@@ -288,39 +288,6 @@ extern "C" void povu_hip_sites_free(povu_hip_sites *s)
 
 namespace
 {
-char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names, const char *const *path_name,
-		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len,
-		const char *const *rest_prefix = nullptr, uint32_t n_rest = 0, bool rest = false);
-}
-
-extern "C" char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
-				    const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, size_t *len)
-{
-	// a caller of before may hold a povu_hip_calls that ends with n_inv_tier2: nothing behind it is read
-	return calls_vcf(c, sites, names, path_name, date, only_prefix, threads, POVU_HIP_PROFILE_RAW_GRAPH, false, len);
-}
-
-extern "C" char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
-					    const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads,
-					    uint32_t profile, size_t *len)
-{
-	return calls_vcf(c, sites, names, path_name, date, only_prefix, threads, profile, true, len);
-}
-
-extern "C" char *povu_hip_calls_vcf_rest(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
-					 const char *const *path_name, const char *date, const char *const *prefix, uint32_t n_prefixes,
-					 uint32_t threads, uint32_t profile, size_t *len)
-{
-	if (n_prefixes && !prefix)
-		return nullptr;
-	for (uint32_t k = 0; k < n_prefixes; k++)
-		if (!prefix[k])
-			return nullptr;
-	return calls_vcf(c, sites, names, path_name, date, nullptr, threads, profile, true, len, prefix, n_prefixes, true);
-}
-
-namespace
-{
 // the lines of "Off-reference calls", behind the header of a call made with POVU_HIP_T_OFFREF
 const char OFFREF_LINES[] =
 	"##INFO=<ID=OFFREF,Number=0,Type=Flag,Description=\"Called off the reference paths: CHROM is the surrogate path, the first path that "
@@ -341,89 +308,144 @@ const char CLUSTER_LINES[] =
 	"##INFO=<ID=MINSIM,Number=1,Type=Integer,Description=\"Lowest similarity, in parts per million, of an exact allele of the site to the "
 	"representative of its cluster\">\n";
 
-char *calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names, const char *const *path_name,
-		const char *date, const char *only_prefix, uint32_t threads, uint32_t profile, bool nested_fields, size_t *len,
-		const char *const *rest_prefix, uint32_t n_rest, bool rest)
-try {
-	if (!c || !sites || !names || !path_name || !len || c->n_slots != names->refs.n_slots || c->n_refs != names->refs.n_refs ||
+// what a writer is asked for
+struct VcfRequest {
+	const povu_hip_calls *c;
+	const povu_hip_sites *sites;
+	const povu_hip_call_names *names;
+	const char *const *path_name;
+	const char *date; // (NULL: today)
+	// the paths whose lines and records are written: those of only_prefix (NULL: every one), or with `rest` those of no prefix
+	const char *only_prefix;
+	const char *const *rest_prefix;
+	uint32_t n_rest;
+	bool rest;
+	uint32_t threads, profile;
+	bool nested_fields; // false: the entry of before, which reads nothing of `c` behind n_inv_tier2
+};
+
+// which array groups of the calls are read, and the counts the text is made with: the one place that looks at nested_fields
+// and at the optional pointers
+struct VcfShape {
+	bool level, parent_query, ref_spelled; // the fields of "Nested calls", each absent for the entry of before or where a hand-made record leaves it out
+	bool nested;			       // PS is written
+	bool normalized;		       // the fields of "Left-normalised calls", under that profile alone (absent: no record was changed)
+	bool rows;			       // the rows of "Decomposed calls", under that profile alone (absent: the raw records are written)
+	bool merged;			       // the merged rows of "Merged primitives", written instead of the rows when they are there
+	bool merged_lines;		       // (a call with the flag and no row has no array to show for it: the header still names the fields)
+	bool offref;			       // the arrays of "Off-reference calls" (`offref` speaks for a call without a record)
+	bool untangled;			       // the arrays of "Untangled calls" (`untangled` speaks for a call without a record)
+	bool clustered;			       // the arrays of "Clustered calls" (one left out: no record says NX or MINSIM)
+	uint64_t cluster_ppm;		       // 0: the text of the call without a threshold
+	uint64_t n;			       // rows of text: merged rows, rows or records
+	uint32_t S, P, n_samples;
+	std::vector<uint32_t> slot_first; // (the slots of a sample are consecutive)
+};
+
+// false: the request or an index of the calls is out of bounds
+bool calls_shape(const VcfRequest &rq, VcfShape &sh)
+{
+	const povu_hip_calls *c = rq.c;
+	const povu_hip_sites *sites = rq.sites;
+	const povu_hip_call_names *names = rq.names;
+	const uint32_t profile = rq.profile;
+	const bool nested_fields = rq.nested_fields;
+	if (!c || !sites || !names || !rq.path_name || c->n_slots != names->refs.n_slots || c->n_refs != names->refs.n_refs ||
 	    profile > POVU_HIP_PROFILE_DECOMPOSED)
-		return nullptr;
-	// the fields of "Nested calls", absent (NULL) for the entry of before and where a hand-made record leaves them out
-	const uint32_t *level = nested_fields ? c->level : nullptr, *parent_query = nested_fields ? c->parent_query : nullptr;
+		return false;
+	const uint32_t *parent_query = nested_fields ? c->parent_query : nullptr;
 	const uint64_t *ref_spelled = nested_fields ? c->ref_spelled : nullptr;
-	const bool nested = nested_fields && c->nested;
-	// the fields of "Left-normalised calls", read under that profile alone (absent: no record was changed)
-	const bool normalized = nested_fields && profile == POVU_HIP_PROFILE_LEFT_NORMALIZED && c->raw_pos && c->norm_block;
-	// the rows of "Decomposed calls", read under that profile alone (absent: the raw records are written)
-	const bool rows = nested_fields && profile == POVU_HIP_PROFILE_DECOMPOSED && c->row_record && c->row_alt && c->row_kind && c->row_reason &&
-			  c->row_index && c->row_pos && c->row_ref_start && c->row_ref_len && c->row_alt_start && c->row_alt_len && c->row_lead &&
-			  c->row_ac && c->row_an && c->row_ns;
-	// the merged rows of "Merged primitives", written instead of the rows when they are there
-	const bool merged = rows && c->mrow_off;
-	// (a call with the flag and no row has no array to show for it: `merged` says so, and the header still names the fields)
-	const bool merged_lines = merged || (nested_fields && profile == POVU_HIP_PROFILE_DECOMPOSED && c->merged && !c->n_rows);
-	// the arrays of "Off-reference calls" (absent: the text of the call without the flag)
-	// (a call with the flag and no record has no array to show for it: `offref` says so)
-	const bool offref = nested_fields && (c->rec_offref || c->offref);
-	if (offref && ((c->n_records && (!c->rec_offref || !c->host_query || !c->host_allele)) ||
-		       (c->n_off_contigs && (!c->off_contig_path || !c->off_contig_len))))
-		return nullptr;
-	// the arrays of "Untangled calls" (absent: the text of the call without the flag; `untangled` speaks for a call without a record)
-	const bool untangled = nested_fields && (c->rec_unt || c->untangled);
-	if (untangled && c->n_records && (!c->rec_unt || !c->lap || !c->n_laps || !c->lap_count))
-		return nullptr;
-	// the arrays of "Clustered calls" (cluster_ppm 0: the text of the call without a threshold; an array left out: no record
-	// says NX or MINSIM)
-	const uint64_t cluster_ppm = nested_fields ? c->cluster_ppm : 0;
-	if (cluster_ppm > cluster::PPM)
-		return nullptr;
-	const bool clustered = cluster_ppm && c->rec_clustered && c->cl_minsim && c->cl_nx;
-	if (merged && (!c->mrow_member ||!c->mrow_gt || !c->mrow_ac || !c->mrow_an || !c->mrow_ns))
-		return nullptr;
-	const uint64_t n_records = c->n_records, n = merged ? c->n_mrows : rows ? c->n_rows : n_records, S = c->n_slots;
-	const uint32_t P = names->n_paths, n_samples = names->refs.n_samples;
+	sh.level = nested_fields && c->level;
+	sh.parent_query = parent_query, sh.ref_spelled = ref_spelled;
+	sh.nested = nested_fields && c->nested;
+	sh.normalized = nested_fields && profile == POVU_HIP_PROFILE_LEFT_NORMALIZED && c->raw_pos && c->norm_block;
+	sh.rows = nested_fields && profile == POVU_HIP_PROFILE_DECOMPOSED && c->row_record && c->row_alt && c->row_kind && c->row_reason &&
+		  c->row_index && c->row_pos && c->row_ref_start && c->row_ref_len && c->row_alt_start && c->row_alt_len && c->row_lead && c->row_ac &&
+		  c->row_an && c->row_ns;
+	sh.merged = sh.rows && c->mrow_off;
+	sh.merged_lines = sh.merged || (nested_fields && profile == POVU_HIP_PROFILE_DECOMPOSED && c->merged && !c->n_rows);
+	sh.offref = nested_fields && (c->rec_offref || c->offref);
+	if (sh.offref && ((c->n_records && (!c->rec_offref || !c->host_query || !c->host_allele)) ||
+			  (c->n_off_contigs && (!c->off_contig_path || !c->off_contig_len))))
+		return false;
+	sh.untangled = nested_fields && (c->rec_unt || c->untangled);
+	if (sh.untangled && c->n_records && (!c->rec_unt || !c->lap || !c->n_laps || !c->lap_count))
+		return false;
+	sh.cluster_ppm = nested_fields ? c->cluster_ppm : 0;
+	if (sh.cluster_ppm > cluster::PPM)
+		return false;
+	sh.clustered = sh.cluster_ppm && c->rec_clustered && c->cl_minsim && c->cl_nx;
+	if (sh.merged && (!c->mrow_member || !c->mrow_gt || !c->mrow_ac || !c->mrow_an || !c->mrow_ns))
+		return false;
+	const uint64_t n_records = c->n_records, n = sh.merged ? c->n_mrows : sh.rows ? c->n_rows : n_records;
+	sh.n = n, sh.S = c->n_slots, sh.P = names->n_paths, sh.n_samples = names->refs.n_samples;
 	for (uint64_t i = 0; i < n_records; i++) {
 		const bool subr = c->flags[i] & POVU_HIP_CALL_SUBR; // (its query is POVU_HIP_NIL: it belongs to no site)
-		if ((!subr && c->query[i] >= sites->n) || c->path[i] >= P || (subr && (c->n_alleles[i] != 2 || c->ref_allele[i] != 0)))
-			return nullptr;
+		if ((!subr && c->query[i] >= sites->n) || c->path[i] >= sh.P || (subr && (c->n_alleles[i] != 2 || c->ref_allele[i] != 0)))
+			return false;
 		if (parent_query && parent_query[i] != POVU_HIP_NIL && parent_query[i] >= sites->n)
-			return nullptr;
+			return false;
 		if (ref_spelled && ref_spelled[i] >= c->n_spelled)
-			return nullptr;
-		if (offref && c->host_query[i] != POVU_HIP_NIL && c->host_query[i] >= sites->n)
-			return nullptr;
-		if (normalized && (c->flags[i] & POVU_HIP_CALL_NORMALIZED) &&
+			return false;
+		if (sh.offref && c->host_query[i] != POVU_HIP_NIL && c->host_query[i] >= sites->n)
+			return false;
+		if (sh.normalized && (c->flags[i] & POVU_HIP_CALL_NORMALIZED) &&
 		    (subr || c->norm_block[i] >= c->n_blocks || c->block_off[c->norm_block[i]] + c->n_alleles[i] > c->n_spelled))
-			return nullptr;
+			return false;
 	}
-	for (uint64_t k = 0; rows && k < c->n_rows; k++) {
+	for (uint64_t k = 0; sh.rows && k < c->n_rows; k++) {
 		const uint64_t i = c->row_record[k];
 		if (i >= n_records || !c->row_alt[k] || c->row_alt[k] >= c->n_alleles[i] || c->row_kind[k] > POVU_HIP_ROW_PASS ||
 		    c->row_reason[k] > POVU_HIP_REASON_SUBR)
-			return nullptr;
+			return false;
 		// its stretches lie inside the record's REF and that ALT
 		const uint32_t ra = c->ref_allele[i], a = c->row_alt[k] - 1 < ra ? c->row_alt[k] - 1 : c->row_alt[k];
 		const uint64_t sr = ref_spelled ? ref_spelled[i] : c->block_off[c->block[i]] + ra, sa = c->block_off[c->block[i]] + a;
 		if (sa >= c->n_spelled || (uint64_t)c->row_ref_start[k] + c->row_ref_len[k] > c->seq_off[sr + 1] - c->seq_off[sr] ||
 		    (uint64_t)c->row_alt_start[k] + c->row_alt_len[k] > c->seq_off[sa + 1] - c->seq_off[sa])
-			return nullptr;
+			return false;
 	}
 	// every merged row has members, all of them rows, and together they are the rows
-	if (merged && (c->mrow_off[0] != 0 || c->mrow_off[n] != c->n_rows))
-		return nullptr;
-	for (uint64_t g = 0; merged && g < n; g++)
+	if (sh.merged && (c->mrow_off[0] != 0 || c->mrow_off[n] != c->n_rows))
+		return false;
+	for (uint64_t g = 0; sh.merged && g < n; g++)
 		if (c->mrow_off[g] >= c->mrow_off[g + 1] || c->mrow_off[g + 1] > c->n_rows)
-			return nullptr;
-	for (uint64_t k = 0; merged && k < c->n_rows; k++)
+			return false;
+	for (uint64_t k = 0; sh.merged && k < c->n_rows; k++)
 		if (c->mrow_member[k] >= c->n_rows)
-			return nullptr;
-	std::vector<uint32_t> slot_first(n_samples + 1, 0); // (the slots of a sample are consecutive)
-	for (uint32_t sl = 0; sl < S; sl++) {
-		if (names->refs.sample_of_slot[sl] >= n_samples)
-			return nullptr;
-		slot_first[names->refs.sample_of_slot[sl] + 1] = sl + 1;
+			return false;
+	sh.slot_first.assign(sh.n_samples + 1, 0);
+	for (uint32_t sl = 0; sl < sh.S; sl++) {
+		if (names->refs.sample_of_slot[sl] >= sh.n_samples)
+			return false;
+		sh.slot_first[names->refs.sample_of_slot[sl] + 1] = sl + 1;
 	}
+	// the paths that give a contig line: the reference paths, and the surrogates that are none
+	for (uint32_t r = 0; r < names->refs.n_refs; r++)
+		if (names->refs.ref_path[r] >= sh.P)
+			return false;
+	for (uint64_t k = 0; sh.offref && k < c->n_off_contigs; k++)
+		if (c->off_contig_path[k] >= sh.P)
+			return false;
+	return true;
+}
+
+bool takes(const VcfRequest &rq, const char *name)
+{
+	if (!rq.rest)
+		return !rq.only_prefix || !strncmp(name, rq.only_prefix, strlen(rq.only_prefix));
+	for (uint32_t k = 0; k < rq.n_rest; k++)
+		if (!strncmp(name, rq.rest_prefix[k], strlen(rq.rest_prefix[k])))
+			return false;
+	return true;
+}
+
+// fixed lines, the blocks of the modes, a contig line per path that is taken (`keep` marks it), the column line
+std::string vcf_header(const VcfRequest &rq, const VcfShape &sh, std::vector<char> &keep)
+{
+	const povu_hip_calls *c = rq.c;
 	char today[16];
+	const char *date = rq.date;
 	if (!date) {
 		const time_t t = time(nullptr);
 		struct tm tmv;
@@ -431,281 +453,317 @@ try {
 		strftime(today, sizeof today, "%Y%m%d", &tmv);
 		date = today;
 	}
-	// ---- header, a contig line per reference path of the prefix, the column line
-	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (nested ? PS_LINE : "") + PROFILE_LINES[profile] + (merged_lines ? MERGE_LINES : "") + (offref ? OFFREF_LINES : "") + (untangled ? UNTANGLE_LINES : "");
-	if (cluster_ppm) {
+	std::string head = std::string("##fileformat=VCFv4.2\n##fileDate=") + date + "\n" + VCF_HEADER + (sh.nested ? PS_LINE : "") + PROFILE_LINES[rq.profile] +
+			   (sh.merged_lines ? MERGE_LINES : "") + (sh.offref ? OFFREF_LINES : "") + (sh.untangled ? UNTANGLE_LINES : "");
+	if (sh.cluster_ppm) {
 		char f[64];
-		snprintf(f, sizeof f, "##povu_call_cluster=%u.%06u\n", (unsigned)(cluster_ppm / cluster::PPM), (unsigned)(cluster_ppm % cluster::PPM));
+		snprintf(f, sizeof f, "##povu_call_cluster=%u.%06u\n", (unsigned)(sh.cluster_ppm / cluster::PPM), (unsigned)(sh.cluster_ppm % cluster::PPM));
 		head += std::string(CLUSTER_LINES) + f;
 	}
-	// the paths whose lines and records are written: those of the prefix (every one without), or with `rest` of no prefix
-	auto takes = [&](const char *name) {
-		if (!rest)
-			return !only_prefix || !strncmp(name, only_prefix, strlen(only_prefix));
-		for (uint32_t k = 0; k < n_rest; k++)
-			if (!strncmp(name, rest_prefix[k], strlen(rest_prefix[k])))
-				return false;
-		return true;
-	};
-	auto site_label = [&](uint32_t q) {
-		return (sites->or1[q] ? "<" : ">") + std::to_string(sites->id1[q]) + (sites->or2[q] ? "<" : ">") + std::to_string(sites->id2[q]);
-	};
-	std::vector<char> keep(P, 0);
-	for (uint32_t r = 0; r < names->refs.n_refs; r++) {
-		const uint32_t p = names->refs.ref_path[r];
-		if (p >= P)
-			return nullptr;
-		if (!takes(path_name[p]))
-			continue;
+	auto contig = [&](uint32_t p, uint64_t length) {
+		if (!takes(rq, rq.path_name[p]))
+			return;
 		keep[p] = 1;
-		head += std::string("##contig=<ID=") + path_name[p] + ",length=" + std::to_string(c->contig_len[r]) + ">\n";
-	}
-	for (uint64_t k = 0; offref && k < c->n_off_contigs; k++) { // the surrogates that are no reference path
-		const uint32_t p = c->off_contig_path[k];
-		if (p >= P)
-			return nullptr;
-		if (!takes(path_name[p]))
-			continue;
-		keep[p] = 1;
-		head += std::string("##contig=<ID=") + path_name[p] + ",length=" + std::to_string(c->off_contig_len[k]) + ">\n";
-	}
+		head += std::string("##contig=<ID=") + rq.path_name[p] + ",length=" + std::to_string(length) + ">\n";
+	};
+	for (uint32_t r = 0; r < rq.names->refs.n_refs; r++)
+		contig(rq.names->refs.ref_path[r], c->contig_len[r]);
+	for (uint64_t k = 0; sh.offref && k < c->n_off_contigs; k++)
+		contig(c->off_contig_path[k], c->off_contig_len[k]);
 	head += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT";
-	for (uint32_t sm = 0; sm < n_samples; sm++)
-		head += std::string("\t") + names->sample[sm];
+	for (uint32_t sm = 0; sm < sh.n_samples; sm++)
+		head += std::string("\t") + rq.names->sample[sm];
 	head += "\n";
-	// ---- the records as text, in chunks of records on up to `threads` threads
-	const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>(threads, (n + 1023) / 1024));
+	return head;
+}
+
+std::string site_label(const povu_hip_sites *sites, uint32_t q)
+{
+	return (sites->or1[q] ? "<" : ">") + std::to_string(sites->id1[q]) + (sites->or2[q] ? "<" : ">") + std::to_string(sites->id2[q]);
+}
+// the kind of a row as a primitive: a _ROW_RAW row is the one primitive of its record
+uint32_t primitive_kind(const povu_hip_calls *c, uint64_t y)
+{
+	if (c->row_kind[y] != POVU_HIP_ROW_RAW)
+		return c->row_kind[y];
+	return !c->row_ref_len[y] ? POVU_HIP_ROW_INS : !c->row_alt_len[y] ? POVU_HIP_ROW_DEL : POVU_HIP_ROW_SNP;
+}
+const char *vartype(uint8_t f)
+{
+	return (f & POVU_HIP_CALL_SUBR) ? ";VARTYPE=SUBR" : (f & POVU_HIP_CALL_INS) ? ";VARTYPE=INS" : (f & POVU_HIP_CALL_DEL) ? ";VARTYPE=DEL" : ";VARTYPE=SUB";
+}
+
+// one row of the text and what both kinds of row are made of
+struct Row {
+	uint64_t mrow, at, members, i; // the row, the row that is written (a merged row's representative), its members, its record
+	// a row of "Decomposed calls" that is no raw record: one ALT, its own POS, texts and counts, the GT row projected (a merged
+	// row of two or more is none even when its representative is one)
+	bool prim;
+	bool subr;
+	std::vector<uint64_t> order; // its spelled alleles: REF first, the others in the query's allele order
+	std::string label;	     // its ID: the site, or the ends of an inversion
+};
+// false: the row's path is not written
+bool row_of(const VcfRequest &rq, const VcfShape &sh, const std::vector<char> &keep, uint64_t mrow, Row &r)
+{
+	const povu_hip_calls *c = rq.c;
+	r.mrow = mrow;
+	r.at = sh.merged ? c->mrow_member[c->mrow_off[mrow]] : mrow;
+	r.members = sh.merged ? c->mrow_off[mrow + 1] - c->mrow_off[mrow] : 1;
+	const uint64_t i = r.i = sh.rows ? c->row_record[r.at] : r.at;
+	if (!keep[c->path[i]])
+		return false;
+	r.prim = sh.rows && (c->row_kind[r.at] != POVU_HIP_ROW_RAW || r.members > 1);
+	const uint32_t na = c->n_alleles[i], ra = c->ref_allele[i];
+	const uint64_t b = c->block_off[c->block[i]];
+	r.order.clear();
+	r.order.push_back(sh.ref_spelled ? c->ref_spelled[i] : b + ra);
+	for (uint32_t a = 0; a < na; a++)
+		if (a != ra)
+			r.order.push_back(b + a);
+	r.subr = c->flags[i] & POVU_HIP_CALL_SUBR;
+	if (!r.subr) {
+		r.label = site_label(rq.sites, c->query[i]);
+		return true;
+	}
+	// the first and the last step of the REF AT string, both written '>' when both are '<'
+	const char *at = c->at + c->at_off[b], *end = c->at + c->at_off[b + 1], *last = end;
+	while (last > at && last[-1] != '<' && last[-1] != '>')
+		last--;
+	const char *first_end = at == end ? at : at + 1;
+	while (first_end < end && *first_end != '<' && *first_end != '>')
+		first_end++;
+	r.label.assign(at, first_end);
+	if (last > at)
+		r.label.append(last - 1, end);
+	if (at < end && *at == '<' && last > at && last[-1] == '<')
+		r.label[0] = r.label[first_end - at] = '>';
+	return true;
+}
+
+// a number of a sample column (nearly always one digit)
+void put_number(std::string &o, uint32_t v)
+{
+	if (v < 10)
+		o += (char)('0' + v);
+	else
+		o += std::to_string(v);
+}
+// the sample columns: the values of a sample's slots joined by '|', one '.' where no slot has a value.  value(slot): what is
+// written for it, POVU_HIP_GT_MISSING for '.'.  laps (NULL: none): behind a ':' the laps of the sample's slots, '.' for none
+template <class Value> void genotype_columns(const VcfShape &sh, Value &&value, const uint16_t *laps, std::string &o)
+{
+	for (uint32_t sm = 0; sm < sh.n_samples; sm++) {
+		const uint32_t s0 = sh.slot_first[sm], s1 = sh.slot_first[sm + 1];
+		o += '\t';
+		bool any = false;
+		for (uint32_t sl = s0; sl < s1; sl++)
+			any |= value(sl) != POVU_HIP_GT_MISSING;
+		if (!any)
+			o += '.';
+		for (uint32_t sl = s0; any && sl < s1; sl++) {
+			if (sl > s0)
+				o += '|';
+			if (value(sl) == POVU_HIP_GT_MISSING)
+				o += '.';
+			else
+				put_number(o, value(sl));
+		}
+		for (uint32_t sl = s0; laps && sl < s1; sl++) {
+			o += sl > s0 ? ',' : ':';
+			if (!laps[sl])
+				o += '.';
+			else
+				put_number(o, laps[sl]);
+		}
+	}
+	o += '\n';
+}
+// a slot of a merged row: 0, 1 or none
+uint32_t merged_value(uint8_t v) { return v <= 1 ? v : POVU_HIP_GT_MISSING; }
+
+void primitive_row(const VcfRequest &rq, const VcfShape &sh, const Row &r, std::string &o)
+{
+	const povu_hip_calls *c = rq.c;
+	const uint64_t at = r.at, i = r.i, mrow = r.mrow;
+	const bool merged = sh.merged, subr = r.subr;
+	const std::string &label = r.label;
+	const uint8_t f = c->flags[i];
+	char num[32];
+	const uint32_t k = c->row_alt[at], kind = primitive_kind(c, at);
+	const uint32_t index = c->row_kind[at] == POVU_HIP_ROW_RAW ? 1 : c->row_index[at];
+	const bool passed = kind == POVU_HIP_ROW_PASS;
+	const uint64_t sr = r.order[0], sa = r.order[k];
+	const char lead = (char)c->row_lead[at];
+	o += rq.path_name[c->path[i]];
+	o += '\t';
+	o += std::to_string(c->row_pos[at]);
+	o += '\t';
+	o += label;
+	if (subr)
+		o += ":subr-passthrough";
+	else
+		o += ":" + std::to_string(k) + ":" + ROW_KIND_NAME[kind] + (passed ? std::string() : std::to_string(index));
+	o += '\t';
+	if (lead)
+		o += lead;
+	o.append(c->seq + c->seq_off[sr] + c->row_ref_start[at], c->row_ref_len[at]);
+	o += '\t';
+	if (lead)
+		o += lead;
+	o.append(c->seq + c->seq_off[sa] + c->row_alt_start[at], c->row_alt_len[at]);
+	const uint32_t ac = merged ? c->mrow_ac[mrow] : c->row_ac[at], an = merged ? c->mrow_an[mrow] : c->row_an[at];
+	snprintf(num, sizeof num, "%.1f", an ? (double)ac / an : 0.0);
+	o += "\t60\tPASS\tAC=" + std::to_string(ac) + ";AF=" + num + ";AN=" + std::to_string(an) +
+	     ";NS=" + std::to_string(merged ? c->mrow_ns[mrow] : c->row_ns[at]) + ";AT=";
+	o.append(c->at + c->at_off[sr], c->at_off[sr + 1] - c->at_off[sr]);
+	o += ',';
+	o.append(c->at + c->at_off[sa], c->at_off[sa + 1] - c->at_off[sa]);
+	if (passed)
+		o += vartype(f);
+	else
+		o += kind == POVU_HIP_ROW_SNP ? ";VARTYPE=SUB" : kind == POVU_HIP_ROW_INS ? ";VARTYPE=INS" : ";VARTYPE=DEL";
+	o += passed && (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
+	o += ";ORIGIN=" + label + ";RAW_ALT_INDEX=" + std::to_string(k) + ";PROFILE=decomposed;";
+	o += passed ? std::string("PASSTHROUGH=T;PASS_THROUGH_REASON=") + ROW_REASON_NAME[c->row_reason[at]] : std::string("DECOMPOSED=T");
+	if (r.members > 1) { // the members' decomposed IDs, the representative's first
+		o += ";MERGED=" + std::to_string(r.members) + ";MERGED_FROM=";
+		for (uint64_t m = c->mrow_off[mrow]; m < c->mrow_off[mrow + 1]; m++) {
+			const uint64_t y = c->mrow_member[m], iy = c->row_record[y];
+			const bool raw = c->row_kind[y] == POVU_HIP_ROW_RAW;
+			if (m > c->mrow_off[mrow])
+				o += ',';
+			o += ((c->flags[iy] & POVU_HIP_CALL_SUBR) ? label : site_label(rq.sites, c->query[iy])) + ":" + std::to_string(c->row_alt[y]) + ":" +
+			     ROW_KIND_NAME[primitive_kind(c, y)] + std::to_string(raw ? 1 : c->row_index[y]);
+		}
+	}
+	if (subr) {
+		o += ";SUBR_ORIGIN=T";
+	} else {
+		o += ";RAW_POS=" + std::to_string(c->pos[i]) + ";RAW_REF=";
+		o.append(c->seq + c->seq_off[sr], c->seq_off[sr + 1] - c->seq_off[sr]);
+		o += ";RAW_ALT=";
+		o.append(c->seq + c->seq_off[sa], c->seq_off[sa + 1] - c->seq_off[sa]);
+	}
+	o += "\tGT";
+	// the merged row's value, else the record's projected on the ALT
+	const uint16_t *gt = c->gt + i * sh.S;
+	const uint8_t *mgt = merged ? c->mrow_gt + mrow * sh.S : nullptr;
+	genotype_columns(sh, [&](uint32_t sl) -> uint32_t { return mgt ? merged_value(mgt[sl]) : gt[sl] == 0 ? 0u : gt[sl] == k ? 1u : POVU_HIP_GT_MISSING; },
+			 nullptr, o);
+}
+
+void record_row(const VcfRequest &rq, const VcfShape &sh, const Row &r, std::string &o)
+{
+	const povu_hip_calls *c = rq.c;
+	const uint64_t i = r.i, mrow = r.mrow;
+	const uint32_t profile = rq.profile, q = c->query[i], na = c->n_alleles[i];
+	const bool merged = sh.merged, subr = r.subr;
+	const std::vector<uint64_t> &order = r.order;
+	const std::string &label = r.label;
+	const uint8_t f = c->flags[i];
+	char num[32];
+	const bool has_parent = !subr && sh.parent_query && c->parent_query[i] != POVU_HIP_NIL;
+	const std::string parent = has_parent ? site_label(rq.sites, c->parent_query[i]) : std::string(".");
+	const bool rescued = !subr && profile == POVU_HIP_PROFILE_POPPED && (f & POVU_HIP_CALL_RESCUED);
+	const bool norm = sh.normalized && (f & POVU_HIP_CALL_NORMALIZED);
+	const uint64_t nbase = norm ? c->block_off[c->norm_block[i]] : 0; // (its alleles in written order)
+	o += rq.path_name[c->path[i]];
+	o += '\t';
+	o += std::to_string(c->pos[i]);
+	o += '\t';
+	o += label;
+	if (!subr && profile == POVU_HIP_PROFILE_TOP_LEVEL_ONLY)
+		o += ":top";
+	if (rescued)
+		o += ":rescued";
+	if (norm)
+		o += ":norm";
+	for (size_t k = 0; k < order.size(); k++) {
+		const uint64_t sa = norm ? nbase + k : order[k];
+		o += k <= 1 ? '\t' : ',';
+		o.append(c->seq + c->seq_off[sa], c->seq_off[sa + 1] - c->seq_off[sa]);
+	}
+	o += "\t60\tPASS\tAC=";
+	// (a _ROW_RAW row of a merged call: its record has one ALT, the counts and the GT are the merged row's)
+	const uint64_t a0 = c->ac_off[i], a1 = c->ac_off[i + 1];
+	const uint32_t an = merged ? c->mrow_an[mrow] : c->an[i];
+	auto ac_of = [&](uint64_t k) { return merged ? c->mrow_ac[mrow] : c->ac[k]; };
+	for (uint64_t k = a0; k < a1; k++)
+		o += (k > a0 ? "," : "") + std::to_string(ac_of(k));
+	o += ";AF=";
+	for (uint64_t k = a0; k < a1; k++) {
+		snprintf(num, sizeof num, "%.1f", an ? (double)ac_of(k) / an : 0.0);
+		o += (k > a0 ? "," : "");
+		o += num;
+	}
+	o += ";AN=" + std::to_string(an) + ";NS=" + std::to_string(merged ? c->mrow_ns[mrow] : c->ns[i]) + ";AT=";
+	for (size_t k = 0; k < order.size(); k++) {
+		if (k)
+			o += ',';
+		o.append(c->at + c->at_off[order[k]], c->at_off[order[k] + 1] - c->at_off[order[k]]);
+	}
+	o += vartype(f);
+	o += (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
+	if (!subr) {
+		o += ";ES=" + label + ";LV=" + std::to_string(sh.level ? (long)(int32_t)c->level[i] : (long)rq.sites->height[q] - 1);
+		if (sh.nested && has_parent)
+			o += ";PS=" + parent;
+		if (sh.clustered && c->rec_clustered[i]) {
+			const uint32_t *nx = c->cl_nx + c->ac_off[i] + i;
+			for (uint32_t k = 0; k < na; k++)
+				o += (k ? "," : ";NX=") + std::to_string(nx[k]);
+			o += ";MINSIM=" + std::to_string(c->cl_minsim[i]);
+		}
+		if (sh.offref && c->rec_offref[i]) {
+			o += ";OFFREF=T";
+			if (c->host_query[i] != POVU_HIP_NIL)
+				o += ";HOST=" + site_label(rq.sites, c->host_query[i]) + ";HA=" + std::to_string(c->host_allele[i]);
+		}
+		if (sh.untangled && c->rec_unt[i])
+			o += ";LN=" + std::to_string(c->lap[i]) + ";LC=" + std::to_string(c->n_laps[i]);
+		if (norm) {
+			o += ";ORIGIN=" + label + ";RAW_ALT_INDEX=";
+			for (size_t k = 1; k < order.size(); k++)
+				o += (k > 1 ? "," : "") + std::to_string(k);
+			o += ";PROFILE=left-normalized;LEFT_NORMALIZED=T;RAW_POS=" + std::to_string(c->raw_pos[i]);
+			for (size_t k = 0; k < order.size(); k++) {
+				o += k == 0 ? ";RAW_REF=" : k == 1 ? ";RAW_ALT=" : ",";
+				o.append(c->seq + c->seq_off[order[k]], c->seq_off[order[k] + 1] - c->seq_off[order[k]]);
+			}
+		} else if (profile == POVU_HIP_PROFILE_TOP_LEVEL_ONLY || profile == POVU_HIP_PROFILE_POPPED) {
+			o += ";ORIGIN=" + label + (rescued ? ";PARENT=" + parent : std::string()) + ";PROFILE=" + modes::PROFILE_NAME[profile] +
+			     (rescued ? ";RESCUED_CHILD=T;POPPED_PARENT=" + parent : std::string(";PASSTHROUGH=T"));
+		}
+	}
+	// an untangled record: every sample column is <GT>:<CN>, CN the laps of the sample's slots
+	const bool with_cn = sh.untangled && !subr && c->rec_unt[i];
+	o += with_cn ? "\tGT:CN" : "\tGT";
+	const uint16_t *gt = c->gt + i * sh.S;
+	const uint8_t *mgt = merged ? c->mrow_gt + mrow * sh.S : nullptr;
+	genotype_columns(sh, [&](uint32_t sl) -> uint32_t { return mgt ? merged_value(mgt[sl]) : gt[sl]; }, with_cn ? c->lap_count + i * sh.S : nullptr, o);
+}
+
+char *calls_vcf(const VcfRequest &rq, size_t *len)
+try {
+	VcfShape sh;
+	if (!len || !calls_shape(rq, sh))
+		return nullptr;
+	std::vector<char> keep(sh.P, 0);
+	const std::string head = vcf_header(rq, sh, keep);
+	// ---- the rows as text, in chunks of rows on up to `threads` threads
+	const uint64_t n = sh.n;
+	const int T = (int)std::max<uint64_t>(1, std::min<uint64_t>(rq.threads, (n + 1023) / 1024));
 	std::vector<std::string> chunk(T);
 	auto format = [&](int t) {
-		std::string &o = chunk[t];
-		const uint64_t lo = n * t / T, hi = n * (t + 1) / T;
-		std::vector<uint64_t> order;
-		std::string label, parent;
-		char num[32];
-		// the kind of a row as a primitive: a _ROW_RAW row is the one primitive of its record
-		auto primitive_kind = [&](uint64_t y) -> uint32_t {
-			if (c->row_kind[y] != POVU_HIP_ROW_RAW)
-				return c->row_kind[y];
-			return !c->row_ref_len[y] ? POVU_HIP_ROW_INS : !c->row_alt_len[y] ? POVU_HIP_ROW_DEL : POVU_HIP_ROW_SNP;
-		};
-		for (uint64_t mrow = lo; mrow < hi; mrow++) {
-			// the row that is written: a merged row's representative
-			const uint64_t at = merged ? c->mrow_member[c->mrow_off[mrow]] : mrow;
-			const uint64_t members = merged ? c->mrow_off[mrow + 1] - c->mrow_off[mrow] : 1;
-			const uint64_t i = rows ? c->row_record[at] : at;
-			if (!keep[c->path[i]])
+		Row r;
+		for (uint64_t mrow = n * t / T; mrow < n * (t + 1) / T; mrow++)
+			if (!row_of(rq, sh, keep, mrow, r))
 				continue;
-			// a row of "Decomposed calls" that is no raw record: one ALT, its own POS, texts and counts, the GT row projected
-			// (a merged row of two or more is none even when its representative is one)
-			const bool prim_row = rows && (c->row_kind[at] != POVU_HIP_ROW_RAW || members > 1);
-			const uint32_t q = c->query[i], na = c->n_alleles[i], ra = c->ref_allele[i];
-			const uint64_t b = c->block_off[c->block[i]];
-			order.clear();
-			order.push_back(ref_spelled ? ref_spelled[i] : b + ra); // REF first, the others in the query's allele order
-			for (uint32_t a = 0; a < na; a++)
-				if (a != ra)
-					order.push_back(b + a);
-			const uint8_t f = c->flags[i];
-			const bool subr = f & POVU_HIP_CALL_SUBR;
-			if (subr) {
-				// the first and the last step of the REF AT string, both written '>' when both are '<'
-				const char *at = c->at + c->at_off[b], *end = c->at + c->at_off[b + 1], *last = end;
-				while (last > at && last[-1] != '<' && last[-1] != '>')
-					last--;
-				const char *first_end = at == end ? at : at + 1;
-				while (first_end < end && *first_end != '<' && *first_end != '>')
-					first_end++;
-				label.assign(at, first_end);
-				if (last > at)
-					label.append(last - 1, end);
-				if (at < end && *at == '<' && last > at && last[-1] == '<')
-					label[0] = label[first_end - at] = '>';
-			} else {
-				label = site_label(q);
-			}
-			if (prim_row) {
-				const uint32_t k = c->row_alt[at], kind = primitive_kind(at);
-				const uint32_t index = c->row_kind[at] == POVU_HIP_ROW_RAW ? 1 : c->row_index[at];
-				const bool passed = kind == POVU_HIP_ROW_PASS;
-				const uint64_t sr = order[0], sa = order[k];
-				const char lead = (char)c->row_lead[at];
-				o += path_name[c->path[i]];
-				o += '\t';
-				o += std::to_string(c->row_pos[at]);
-				o += '\t';
-				o += label;
-				if (subr)
-					o += ":subr-passthrough";
-				else
-					o += ":" + std::to_string(k) + ":" + ROW_KIND_NAME[kind] + (passed ? std::string() : std::to_string(index));
-				o += '\t';
-				if (lead)
-					o += lead;
-				o.append(c->seq + c->seq_off[sr] + c->row_ref_start[at], c->row_ref_len[at]);
-				o += '\t';
-				if (lead)
-					o += lead;
-				o.append(c->seq + c->seq_off[sa] + c->row_alt_start[at], c->row_alt_len[at]);
-				const uint32_t ac = merged ? c->mrow_ac[mrow] : c->row_ac[at], an = merged ? c->mrow_an[mrow] : c->row_an[at];
-				snprintf(num, sizeof num, "%.1f", an ? (double)ac / an : 0.0);
-				o += "\t60\tPASS\tAC=" + std::to_string(ac) + ";AF=" + num + ";AN=" + std::to_string(an) +
-				     ";NS=" + std::to_string(merged ? c->mrow_ns[mrow] : c->row_ns[at]) + ";AT=";
-				o.append(c->at + c->at_off[sr], c->at_off[sr + 1] - c->at_off[sr]);
-				o += ',';
-				o.append(c->at + c->at_off[sa], c->at_off[sa + 1] - c->at_off[sa]);
-				if (passed)
-					o += subr ? ";VARTYPE=SUBR" : (f & POVU_HIP_CALL_INS) ? ";VARTYPE=INS" : (f & POVU_HIP_CALL_DEL) ? ";VARTYPE=DEL" : ";VARTYPE=SUB";
-				else
-					o += kind == POVU_HIP_ROW_SNP ? ";VARTYPE=SUB" : kind == POVU_HIP_ROW_INS ? ";VARTYPE=INS" : ";VARTYPE=DEL";
-				o += passed && (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
-				o += ";ORIGIN=" + label + ";RAW_ALT_INDEX=" + std::to_string(k) + ";PROFILE=decomposed;";
-				o += passed ? std::string("PASSTHROUGH=T;PASS_THROUGH_REASON=") + ROW_REASON_NAME[c->row_reason[at]] : std::string("DECOMPOSED=T");
-				if (members > 1) { // the members' decomposed IDs, the representative's first
-					o += ";MERGED=" + std::to_string(members) + ";MERGED_FROM=";
-					for (uint64_t m = c->mrow_off[mrow]; m < c->mrow_off[mrow + 1]; m++) {
-						const uint64_t y = c->mrow_member[m], iy = c->row_record[y];
-						const bool raw = c->row_kind[y] == POVU_HIP_ROW_RAW;
-						if (m > c->mrow_off[mrow])
-							o += ',';
-						o += ((c->flags[iy] & POVU_HIP_CALL_SUBR) ? label : site_label(c->query[iy])) + ":" + std::to_string(c->row_alt[y]) + ":" +
-						     ROW_KIND_NAME[primitive_kind(y)] + std::to_string(raw ? 1 : c->row_index[y]);
-					}
-				}
-				if (subr) {
-					o += ";SUBR_ORIGIN=T";
-				} else {
-					o += ";RAW_POS=" + std::to_string(c->pos[i]) + ";RAW_REF=";
-					o.append(c->seq + c->seq_off[sr], c->seq_off[sr + 1] - c->seq_off[sr]);
-					o += ";RAW_ALT=";
-					o.append(c->seq + c->seq_off[sa], c->seq_off[sa + 1] - c->seq_off[sa]);
-				}
-				o += "\tGT";
-				const uint16_t *grow = c->gt + i * S;
-				const uint8_t *mgt = merged ? c->mrow_gt + mrow * S : nullptr;
-				// 0, 1 or anything else for '.': the merged row's value, else the record's projected on the ALT
-				auto value = [&](uint32_t sl) -> uint32_t { return mgt ? mgt[sl] : grow[sl] == 0 ? 0u : grow[sl] == k ? 1u : 0xFFu; };
-				for (uint32_t sm = 0; sm < n_samples; sm++) {
-					o += '\t';
-					bool any = false;
-					for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++)
-						any |= value(sl) <= 1;
-					if (!any) {
-						o += '.';
-						continue;
-					}
-					for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++) {
-						if (sl > slot_first[sm])
-							o += '|';
-						o += value(sl) == 0 ? "0" : value(sl) == 1 ? "1" : ".";
-					}
-				}
-				o += '\n';
-				continue;
-			}
-			const bool has_parent = !subr && parent_query && parent_query[i] != POVU_HIP_NIL;
-			if (has_parent)
-				parent = site_label(parent_query[i]);
-			const bool rescued = !subr && profile == POVU_HIP_PROFILE_POPPED && (f & POVU_HIP_CALL_RESCUED);
-			const bool norm = normalized && (f & POVU_HIP_CALL_NORMALIZED);
-			const uint64_t nbase = norm ? c->block_off[c->norm_block[i]] : 0; // (its alleles in written order)
-			o += path_name[c->path[i]];
-			o += '\t';
-			o += std::to_string(c->pos[i]);
-			o += '\t';
-			o += label;
-			if (!subr && profile == POVU_HIP_PROFILE_TOP_LEVEL_ONLY)
-				o += ":top";
-			if (rescued)
-				o += ":rescued";
-			if (norm)
-				o += ":norm";
-			for (size_t k = 0; k < order.size(); k++) {
-				const uint64_t sa = norm ? nbase + k : order[k];
-				o += k <= 1 ? '\t' : ',';
-				o.append(c->seq + c->seq_off[sa], c->seq_off[sa + 1] - c->seq_off[sa]);
-			}
-			o += "\t60\tPASS\tAC=";
-			// (a _ROW_RAW row of a merged call: its record has one ALT, the counts and the GT are the merged row's)
-			const uint64_t a0 = c->ac_off[i], a1 = c->ac_off[i + 1];
-			const uint32_t an = merged ? c->mrow_an[mrow] : c->an[i];
-			auto ac_of = [&](uint64_t k) { return merged ? c->mrow_ac[mrow] : c->ac[k]; };
-			for (uint64_t k = a0; k < a1; k++)
-				o += (k > a0 ? "," : "") + std::to_string(ac_of(k));
-			o += ";AF=";
-			for (uint64_t k = a0; k < a1; k++) {
-				snprintf(num, sizeof num, "%.1f", an ? (double)ac_of(k) / an : 0.0);
-				o += (k > a0 ? "," : "");
-				o += num;
-			}
-			o += ";AN=" + std::to_string(an) + ";NS=" + std::to_string(merged ? c->mrow_ns[mrow] : c->ns[i]) + ";AT=";
-			for (size_t k = 0; k < order.size(); k++) {
-				if (k)
-					o += ',';
-				o.append(c->at + c->at_off[order[k]], c->at_off[order[k] + 1] - c->at_off[order[k]]);
-			}
-			o += subr ? ";VARTYPE=SUBR" : (f & POVU_HIP_CALL_INS) ? ";VARTYPE=INS" : (f & POVU_HIP_CALL_DEL) ? ";VARTYPE=DEL" : ";VARTYPE=SUB";
-			o += (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
-			if (!subr) {
-				o += ";ES=" + label + ";LV=" + std::to_string(level ? (long)(int32_t)level[i] : (long)sites->height[q] - 1);
-				if (nested && has_parent)
-					o += ";PS=" + parent;
-				if (clustered && c->rec_clustered[i]) {
-					const uint32_t *nx = c->cl_nx + c->ac_off[i] + i;
-					for (uint32_t k = 0; k < na; k++)
-						o += (k ? "," : ";NX=") + std::to_string(nx[k]);
-					o += ";MINSIM=" + std::to_string(c->cl_minsim[i]);
-				}
-				if (offref && c->rec_offref[i]) {
-					o += ";OFFREF=T";
-					if (c->host_query[i] != POVU_HIP_NIL)
-						o += ";HOST=" + site_label(c->host_query[i]) + ";HA=" + std::to_string(c->host_allele[i]);
-				}
-				if (untangled && c->rec_unt[i])
-					o += ";LN=" + std::to_string(c->lap[i]) + ";LC=" + std::to_string(c->n_laps[i]);
-				if (norm) {
-					o += ";ORIGIN=" + label + ";RAW_ALT_INDEX=";
-					for (size_t k = 1; k < order.size(); k++)
-						o += (k > 1 ? "," : "") + std::to_string(k);
-					o += ";PROFILE=left-normalized;LEFT_NORMALIZED=T;RAW_POS=" + std::to_string(c->raw_pos[i]);
-					for (size_t k = 0; k < order.size(); k++) {
-						o += k == 0 ? ";RAW_REF=" : k == 1 ? ";RAW_ALT=" : ",";
-						o.append(c->seq + c->seq_off[order[k]], c->seq_off[order[k] + 1] - c->seq_off[order[k]]);
-					}
-				} else if (profile == POVU_HIP_PROFILE_TOP_LEVEL_ONLY || profile == POVU_HIP_PROFILE_POPPED) {
-					o += ";ORIGIN=" + label;
-					if (rescued)
-						o += ";PARENT=" + (has_parent ? parent : std::string(".")) + ";PROFILE=" + PROFILE_NAME[profile] +
-						     ";RESCUED_CHILD=T;POPPED_PARENT=" + (has_parent ? parent : std::string("."));
-					else
-						o += std::string(";PROFILE=") + PROFILE_NAME[profile] + ";PASSTHROUGH=T";
-				}
-			}
-			// an untangled record: every sample column is <GT>:<CN>, CN the laps of the sample's slots ('.' for none)
-			const bool with_cn = untangled && !subr && c->rec_unt[i];
-			const uint16_t *laps = with_cn ? c->lap_count + i * S : nullptr;
-			o += with_cn ? "\tGT:CN" : "\tGT";
-			const uint16_t *row = c->gt + i * S;
-			const uint8_t *mgt = merged ? c->mrow_gt + mrow * S : nullptr;
-			auto allele = [&](uint32_t sl) -> uint32_t { return !mgt ? row[sl] : mgt[sl] <= 1 ? mgt[sl] : POVU_HIP_GT_MISSING; };
-			for (uint32_t sm = 0; sm < n_samples; sm++) {
-				o += '\t';
-				bool any = false;
-				for (uint32_t sl = slot_first[sm]; sl < slot_first[sm + 1]; sl++)
-					any |= allele(sl) != POVU_HIP_GT_MISSING;
-				if (!any)
-					o += '.';
-				for (uint32_t sl = slot_first[sm]; any && sl < slot_first[sm + 1]; sl++) {
-					if (sl > slot_first[sm])
-						o += '|';
-					o += allele(sl) == POVU_HIP_GT_MISSING ? "." : std::to_string(allele(sl));
-				}
-				for (uint32_t sl = slot_first[sm]; with_cn && sl < slot_first[sm + 1]; sl++) {
-					o += sl > slot_first[sm] ? ',' : ':';
-					o += laps[sl] ? std::to_string(laps[sl]) : ".";
-				}
-			}
-			o += '\n';
-		}
+			else if (r.prim)
+				primitive_row(rq, sh, r, chunk[t]);
+			else
+				record_row(rq, sh, r, chunk[t]);
 	};
 	auto on_threads = [&](auto &&work) {
 		std::vector<std::thread> th;
@@ -734,3 +792,29 @@ try {
 	return nullptr;
 }
 } // namespace
+
+extern "C" char *povu_hip_calls_vcf(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
+				    const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads, size_t *len)
+{
+	// a caller of before may hold a povu_hip_calls that ends with n_inv_tier2: nothing behind it is read
+	return calls_vcf({c, sites, names, path_name, date, only_prefix, nullptr, 0, false, threads, POVU_HIP_PROFILE_RAW_GRAPH, false}, len);
+}
+
+extern "C" char *povu_hip_calls_vcf_profile(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
+					    const char *const *path_name, const char *date, const char *only_prefix, uint32_t threads,
+					    uint32_t profile, size_t *len)
+{
+	return calls_vcf({c, sites, names, path_name, date, only_prefix, nullptr, 0, false, threads, profile, true}, len);
+}
+
+extern "C" char *povu_hip_calls_vcf_rest(const povu_hip_calls *c, const povu_hip_sites *sites, const povu_hip_call_names *names,
+					 const char *const *path_name, const char *date, const char *const *prefix, uint32_t n_prefixes,
+					 uint32_t threads, uint32_t profile, size_t *len)
+{
+	if (n_prefixes && !prefix)
+		return nullptr;
+	for (uint32_t k = 0; k < n_prefixes; k++)
+		if (!prefix[k])
+			return nullptr;
+	return calls_vcf({c, sites, names, path_name, date, nullptr, prefix, n_prefixes, true, threads, profile, true}, len);
+}

@@ -1361,23 +1361,22 @@ class HipDecomposer:
         Calls.raw_pos, norm_block, norm_shift, norm_chop, norm_trim, flags & CALL_NORMALIZED, the counters); "decomposed"
         implies nothing either, keeps every record and writes every (REF, ALT) as the primitives of its alignment ("Decomposed
         calls": Calls.n_rows, row_*, the counters; max_allele_length is the longest text that is aligned, 0 = PRIM_MAX_LENGTH,
-        more is refused; T_FORCE_TIER2 also sends every aligned pair through the striped kernel; with T_MERGE, which every other
-        profile refuses, equal primitives are merged: Calls.merged, n_mrows, mrow_*, the counters, and vcf_text writes the merged
-        rows).  T_OFFREF ("Off-reference calls", raw-graph alone, refused with T_NESTED and T_MERGE): the sites no reference path
-        crosses are called on their surrogate path; Calls.offref, rec_offref, host_query, host_allele, off_contig_*, the
-        counters.  T_UNTANGLE ("Untangled calls", raw-graph alone, refused with T_NESTED, T_MERGE and T_OFFREF): where a path
-        walks a site more than once its laps are aligned with the reference's and every record takes the allele of the lap
-        aligned with its own; Calls.untangled, rec_unt, lap, n_laps, lap_count, the UNTANGLE_COUNTERS, and vcf_text writes
-        LN, LC and GT:CN.  regions ("Region calls", refused with T_OFFREF): strings "name:start-end" or tuples (name, start, end),
-        the 1-based bases [start, end) of the resident path named exactly so; the records are those of the same call without
-        regions for the sites with a boundary segment, and the inversions with an end step, that a region meets; the
-        REGION_COUNTERS.  A call that is not nested masks the other sites in front of its scans; region_no_mask makes it scan
-        every site and select the records at the end, as a nested call does (tests).  cluster ("Clustered calls", raw-graph
-        alone, refused with T_NESTED, T_MERGE, T_OFFREF and T_UNTANGLE; composes with T_INVERSIONS and regions): the threshold F
-        as decimal text ("0.9", at most six decimals, 0 < F <= 1) or as an integer of parts per million; the exact alleles of a
-        site whose bags of inner segments are that similar are one allele, written as its first member; Calls.cluster_ppm,
-        rec_clustered, cl_minsim, cl_nx (Calls.nx), the CLUSTER_COUNTERS, and vcf_text writes NX and MINSIM.  cluster_no_bound
-        reads every pair of bags, whatever their weights say (tests)."""
+        more is refused; T_FORCE_TIER2 also sends every aligned pair through the striped kernel; with T_MERGE equal primitives
+        are merged: Calls.merged, n_mrows, mrow_*, the counters, and vcf_text writes the merged rows).  T_OFFREF ("Off-reference
+        calls"): the sites no reference path crosses are called on their surrogate path; Calls.offref, rec_offref, host_query,
+        host_allele, off_contig_*, the counters.  T_UNTANGLE ("Untangled calls"): where a path walks a site more than once its
+        laps are aligned with the reference's and every record takes the allele of the lap aligned with its own;
+        Calls.untangled, rec_unt, lap, n_laps, lap_count, the UNTANGLE_COUNTERS, and vcf_text writes LN, LC and GT:CN.  regions
+        ("Region calls"): strings "name:start-end" or tuples (name, start, end), the 1-based bases [start, end) of the resident
+        path named exactly so; the records are those of the same call without regions for the sites with a boundary segment, and
+        the inversions with an end step, that a region meets; the REGION_COUNTERS.  A call that is not nested masks the other
+        sites in front of its scans; region_no_mask makes it scan every site and select the records at the end, as a nested call
+        does (tests).  cluster ("Clustered calls"): the threshold F as decimal text ("0.9", at most six decimals, 0 < F <= 1) or
+        as an integer of parts per million; the exact alleles of a site whose bags of inner segments are that similar are one
+        allele, written as its first member; Calls.cluster_ppm, rec_clustered, cl_minsim, cl_nx (Calls.nx), the
+        CLUSTER_COUNTERS, and vcf_text writes NX and MINSIM.  cluster_no_bound reads every pair of bags, whatever their weights
+        say (tests).  Which of the flags, the profiles, regions and cluster combine is declared once, as RULES of
+        povu_amd/csrc/hip/call_modes.hpp, with the message a refused combination raises."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
         names = self._path_names

@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import call_modes_cases as MC
 import cohort_cases as CC
 import vcf_ref as V
 from povu_amd import HipDecomposer
@@ -151,6 +152,35 @@ def test_refusals_and_two_graphs(hip):
     hip.upload_paths(W.pansn(W.chain_haplotypes(30, 4, seed=2), samples=2))
     with pytest.raises(RuntimeError, match="no sequences"):
         hip.call(f2, ["sample0"])
+
+
+def test_which_modes_combine():
+    """Every pair of modes and every (mode, profile) on the worked example of the clustered calls (six segments): the call is
+    refused exactly where the recorded answers say so (tests/golden/call_modes.json, which tests/test_call_modes.py holds the
+    table of call_modes.hpp to), with the recorded library text, and `povu call` refuses the same requests.  A refused call
+    returns before it takes any device memory (the arenas of a context that has made no call stay as they were, so no kernel
+    had anything to run on); an accepted one runs."""
+    d = HipDecomposer(0)
+    try:
+        f = MC.resident_example(d)
+        before = d.arenas()
+        accepted = []
+        for modes, profile in MC.REQUESTS:
+            lib, cli = MC.expected(modes, profile)
+            assert MC.cli_answer(modes, profile) == cli and bool(lib) == bool(cli), (modes, profile)
+            if not lib:
+                accepted.append((modes, profile))
+                continue
+            with pytest.raises(RuntimeError) as e:
+                d.call(f, ["HG1"], **MC.library_kwargs(modes, profile))
+            assert str(e.value) == lib, (modes, profile)
+        assert d.arenas() == before and len(accepted) > 10 and len(accepted) < len(MC.REQUESTS) - 10
+        for modes, profile in accepted:
+            c = d.call(f, ["HG1"], **MC.library_kwargs(modes, profile))
+            assert c.device_ms > 0 and c.vcf_text(date=DATE).startswith("##fileformat=VCFv4.2\n##fileDate=" + DATE), (modes, profile)
+        assert d.arenas() != before  # (a call that runs does take its arenas: the comparison above can tell)
+    finally:
+        d.close()
 
 
 # ---- the CLI

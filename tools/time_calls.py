@@ -28,7 +28,8 @@ only), offref (T_OFFREF: the sites no reference path crosses too; its time less 
 calls"; the sites outside lose their scans) and cluster (the clustered call at T = 900000, INTEGRATION.md "Clustered calls"; its
 time less that of plain is the step's; `alts` counts the ALTs written); without --modes those the input was made for.  One JSON line
 per mode and run: HIP-event time of the call (query upload to the last byte on the host), records, spelled bytes, the
-counters of the mode; then per mode a line with the median of the runs behind the warm-up runs.
+counters of the mode, and the host time of the VCF writer over these calls on one thread (vcf_ms, with the bytes and the MD5 of
+its text); then per mode a line with the median of the runs behind the warm-up runs.
 
 Every mode runs in a child process of its own under its own time limit, one after the other; after a child that fails or
 runs out of time nothing more is started.  --package-root times the library of another checkout on this tree's inputs (only
@@ -116,6 +117,19 @@ def middle_region(g, p, seqs, ref):
     return p.names[k], start, max(start + 1, start + total // 100)
 
 
+def writer(c, H):
+    """(milliseconds, bytes, MD5) of povu_hip_calls_vcf_profile over the calls `c`, the copy into Python left out"""
+    import ctypes as C
+    import hashlib
+    ln = C.c_size_t(0)
+    t0 = time.perf_counter()
+    p = c._lib.povu_hip_calls_vcf_profile(c._p, c._sites._p, c._names_rec, c._name_array, b"00000000", None, 1, H.PROFILES[c.profile], C.byref(ln))
+    ms = (time.perf_counter() - t0) * 1e3
+    digest = hashlib.md5(C.string_at(p, ln.value)).hexdigest()
+    c._lib.povu_hip_buffer_free(p)
+    return ms, ln.value, digest
+
+
 def child(a):
     HipDecomposer, H, W = _load(a.package_root)
     t0 = time.perf_counter()
@@ -141,10 +155,12 @@ def child(a):
         t0 = time.perf_counter()
         c = d.call(f, [ref], **kw)
         wall = (time.perf_counter() - t0) * 1e3
+        vcf_ms, vcf_bytes, vcf_md5 = writer(c, H)
         print(json.dumps(dict(
             workload=a.workload, mode=a.child, run=run, warmup=run < a.warmup, segments=g.n_vtx, links=g.n_links, paths=len(p),
             path_steps=p.n_steps, records=c.n_records, slots=c.n_slots, spelled_bytes=c.n_seq_bytes, at_bytes=c.n_at_bytes,
             alts=int(c.ac_off[-1]) if c.n_records else 0, device_ms=round(c.device_ms, 3), wall_ms=round(wall, 2), generate_s=round(gen_s, 1),
+            vcf_ms=round(vcf_ms, 2), vcf_bytes=vcf_bytes, vcf_md5=vcf_md5,
             **{k: int(getattr(c, k, 0)) for k in counters})), flush=True)
         del c
     d.close()
@@ -182,7 +198,8 @@ def main():
         rows = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
         timed = [x["device_ms"] for x in rows if not x["warmup"]]
         print(json.dumps(dict(workload=a.workload, mode=mode, median_device_ms=round(statistics.median(timed), 3), min_device_ms=min(timed),
-                              max_device_ms=max(timed), runs=len(timed), records=rows[-1]["records"])), flush=True)
+                              max_device_ms=max(timed), median_vcf_ms=round(statistics.median(x["vcf_ms"] for x in rows if not x["warmup"]), 2),
+                              runs=len(timed), records=rows[-1]["records"])), flush=True)
     return 0
 
 
