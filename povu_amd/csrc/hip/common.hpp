@@ -54,6 +54,49 @@ __device__ __forceinline__ void landed(uint2 &a, uint2 &b, uint2 &c, uint2 &d, u
 }
 __device__ __forceinline__ void landed(uint4 &a, uint2 &b) { asm volatile("" : POVU_W4(a), POVU_W2(b)); }
 __device__ __forceinline__ void landed(uint4 &a, uint4 &b, uint4 &c, uint4 &d) { asm volatile("" : POVU_W4(a), POVU_W4(b), POVU_W4(c), POVU_W4(d)); }
+// ... of a batch kept in arrays of N elements (k_back_edges: N = BE_BATCH sides of a lane at a time; the build takes 4, and 2
+// and 8 are there so that POVU_BE_BATCH can be set to them for a measurement)
+#define POVU_A2(a, W) W((a)[0]), W((a)[1])
+#define POVU_A4(a, W) POVU_A2(a, W), W((a)[2]), W((a)[3])
+#define POVU_A8(a, W) POVU_A4(a, W), W((a)[4]), W((a)[5]), W((a)[6]), W((a)[7])
+#define POVU_W1(v) "+v"(v)
+template <uint32_t N>
+__device__ __forceinline__ void landed(uint32_t (&a)[N], uint32_t (&b)[N], uint32_t (&c)[N], uint32_t (&d)[N], uint32_t (&e)[N])
+{
+	static_assert(N == 2 || N == 4 || N == 8, "a batch of 2, 4 or 8");
+	if constexpr (N == 2)
+		asm volatile("" : POVU_A2(a, POVU_W1), POVU_A2(b, POVU_W1), POVU_A2(c, POVU_W1), POVU_A2(d, POVU_W1), POVU_A2(e, POVU_W1));
+	else if constexpr (N == 4)
+		asm volatile("" : POVU_A4(a, POVU_W1), POVU_A4(b, POVU_W1), POVU_A4(c, POVU_W1), POVU_A4(d, POVU_W1), POVU_A4(e, POVU_W1));
+	else
+		asm volatile("" : POVU_A8(a, POVU_W1), POVU_A8(b, POVU_W1), POVU_A8(c, POVU_W1), POVU_A8(d, POVU_W1), POVU_A8(e, POVU_W1));
+}
+template <uint32_t N>
+__device__ __forceinline__ void landed(uint4 (&a)[N], uint32_t (&b)[N])
+{
+	static_assert(N == 2 || N == 4 || N == 8, "a batch of 2, 4 or 8");
+	if constexpr (N == 2)
+		asm volatile("" : POVU_A2(a, POVU_W4), POVU_A2(b, POVU_W1));
+	else if constexpr (N == 4)
+		asm volatile("" : POVU_A4(a, POVU_W4), POVU_A4(b, POVU_W1));
+	else
+		asm volatile("" : POVU_A8(a, POVU_W4), POVU_A8(b, POVU_W1));
+}
+template <uint32_t N>
+__device__ __forceinline__ void landed(uint4 (&a)[N])
+{
+	static_assert(N == 2 || N == 4 || N == 8, "a batch of 2, 4 or 8");
+	if constexpr (N == 2)
+		asm volatile("" : POVU_A2(a, POVU_W4));
+	else if constexpr (N == 4)
+		asm volatile("" : POVU_A4(a, POVU_W4));
+	else
+		asm volatile("" : POVU_A8(a, POVU_W4));
+}
+#undef POVU_A2
+#undef POVU_A4
+#undef POVU_A8
+#undef POVU_W1
 #undef POVU_W2
 #undef POVU_W4
 template <class T>

@@ -1208,7 +1208,38 @@ __global__ void k_tree_emit(uint32_t nS, L0Ranks R, const uint8_t *__restrict__ 
 #ifndef POVU_BE_ITER
 #define POVU_BE_ITER 8
 #endif
+#ifndef POVU_BE_BATCH
+#define POVU_BE_BATCH 4
+#endif
 static constexpr uint32_t BE_ITER = POVU_BE_ITER, BE_SIDES = TPB * BE_ITER;
+// the count phase takes BE_BATCH of a lane's sides at a time: their own words, their first four slot words and the tree
+// vertices behind those are three runs of loads, each behind one wait (common.hpp: landed)
+static constexpr uint32_t BE_BATCH = POVU_BE_BATCH;
+static_assert(BE_ITER % BE_BATCH == 0, "a lane's sides are whole batches");
+// first2 words: "this target is the root of its tree" (tree-vertex indices stay below 2^30, tree_tour_words), so that the
+// emit phase need not look the root up again to leave its count out (ParWs::incnt8)
+static constexpr uint32_t BE_ROOT = 0x80000000u;
+// Word i of an array of fewer than 2^30 words (sides, slots, components, tree vertices: tree_tour_words refuses larger graphs),
+// named by the array in scalar registers and a 32-bit byte offset per lane: half the address registers of p[i], which a
+// batch of sixteen gathers in flight has to hold
+template <uint32_t N>
+__device__ __forceinline__ auto near_words(const uint32_t *__restrict__ p, uint32_t i)
+{
+	typedef uint32_t vNa __attribute__((ext_vector_type(N), aligned(4)));
+	return *reinterpret_cast<const vNa *>(reinterpret_cast<const char *>(p) + (i << 2));
+}
+__device__ __forceinline__ uint32_t near_word(const uint32_t *__restrict__ p, uint32_t i) { return near_words<1>(p, i).x; }
+// ... and the words behind it, from a 4-byte aligned address in one load (see load4_unaligned for the slack)
+__device__ __forceinline__ uint2 near_word2(const uint32_t *__restrict__ p, uint32_t i)
+{
+	const auto v = near_words<2>(p, i);
+	return make_uint2(v.x, v.y);
+}
+__device__ __forceinline__ uint4 near_word4(const uint32_t *__restrict__ p, uint32_t i)
+{
+	const auto v = near_words<4>(p, i);
+	return make_uint4(v.x, v.y, v.z, v.w);
+}
 // IC: the width of incnt.  The byte form does not count the back edges that end at the root (ParWs::incnt8)
 template <bool EMIT, typename IC>
 __device__ __forceinline__ uint32_t side_back_edges(uint32_t S, uint32_t p, uint32_t at,
@@ -1233,7 +1264,7 @@ __device__ __forceinline__ uint32_t side_back_edges(uint32_t S, uint32_t p, uint
 		} else {
 			highest = min(highest, tgt);
 			if (n < 2)
-				first2[n] = tgt; // (LDS: a side with at most two back edges is written from there, without a second walk)
+				first2[n] = tgt | (tgt == root ? BE_ROOT : 0u); // (LDS: a side with at most two back edges is written from there, without a second walk)
 		}
 		n++;
 	};
@@ -1280,8 +1311,15 @@ __device__ __forceinline__ uint32_t side_back_edges(uint32_t S, uint32_t p, uint
 	}
 	return n;
 }
+// (8 waves a SIMD, as its LDS allows: a batch of up to four sides is to fit 64 registers, not to trade waves for them; a
+// batch of eight cannot, and is built for comparison only)
+#if POVU_BE_BATCH <= 4
+#define POVU_BE_WAVES __attribute__((amdgpu_waves_per_eu(8, 8)))
+#else
+#define POVU_BE_WAVES
+#endif
 template <typename OC, typename IC>
-__global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
+__global__ void __launch_bounds__(TPB) POVU_BE_WAVES k_back_edges(uint32_t nS, const uint32_t *__restrict__ loff, const uint32_t *__restrict__ ladj,
 						     const uint2 *__restrict__ dps, const uint32_t *__restrict__ side_tidx,
 						     const uint32_t *__restrict__ ckey, const uint32_t *__restrict__ voff,
 						     const uint32_t *__restrict__ t_par, uint32_t *__restrict__ total_out,
@@ -1294,9 +1332,9 @@ __global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t 
 	__shared__ uint32_t first2[BE_ITER][TPB][2]; // the first two targets of every side of the chunk
 	__shared__ uint8_t cnt8[BE_ITER][TPB];	     // min(its back edges, 255)
 	uint32_t n = 0;
-	for (uint32_t it = 0; it < BE_ITER; it++) {
-		const uint32_t S = S0 + it * TPB;
-		const uint32_t p = S < nS ? side_tidx[S] : NIL;
+	// one side the plain way, its loads one behind the other: every side of a pass with dupflag, and behind a batch the sides
+	// the batch does not settle
+	auto count_side = [&](uint32_t it, uint32_t S, uint32_t p) {
 		uint32_t k = 0;
 		if (p != NIL) {
 			uint32_t highest = NIL;
@@ -1309,6 +1347,107 @@ __global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t 
 			n += k;
 		}
 		cnt8[it][threadIdx.x] = (uint8_t)min(k, 255u);
+	};
+	if (dupflag) { // (hub graphs: whether a slot repeats a link stands in a byte per slot)
+		for (uint32_t it = 0; it < BE_ITER; it++) {
+			const uint32_t S = S0 + it * TPB;
+			count_side(it, S, S < nS ? side_tidx[S] : NIL);
+		}
+	} else {
+		// BE_BATCH sides at a time.  A side with one to four slots is settled out of registers; one without a link (t_par)
+		// or with more than four slots goes through count_side behind its batch.
+		const uint32_t S_end = nS - 1; // a side of this workgroup (it has lanes only because BIDX * BE_SIDES < nS)
+		for (uint32_t it0 = 0; it0 < BE_ITER; it0 += BE_BATCH) {
+			uint32_t p[BE_BATCH], lo[BE_BATCH], hi[BE_BATCH], dp[BE_BATCH], c[BE_BATCH], vo[BE_BATCH], m[BE_BATCH], root[BE_BATCH];
+			uint4 o4[BE_BATCH], x4[BE_BATCH];
+			// the sides' own words.  Unconditional: a lane behind the last side reads the words of the last side, S_end
+			// (loff[nS] is the end of its list)
+#pragma unroll
+			for (uint32_t b = 0; b < BE_BATCH; b++) {
+				const uint32_t Sc = min(S0 + (it0 + b) * TPB, S_end);
+				const uint2 lh = near_word2(loff, Sc);
+				p[b] = near_word(side_tidx, Sc), lo[b] = lh.x, hi[b] = lh.y, dp[b] = dps[Sc].x, c[b] = near_word(ckey, Sc >> 1);
+			}
+			landed(p, lo, hi, dp, c);
+			// their first four slot words -- lo <= 2E whether the side has a link or not, and ladj carries eight words behind
+			// its 2E -- and the first vertex of their component (ckey names one for every segment)
+#pragma unroll
+			for (uint32_t b = 0; b < BE_BATCH; b++) {
+				if (S0 + (it0 + b) * TPB >= nS)
+					p[b] = NIL;
+				o4[b] = near_word4(ladj, lo[b]);
+				vo[b] = near_word(voff, c[b]);
+			}
+			landed(o4, vo);
+			// What the slot words say by themselves (side_back_edges<false> for a side of one round, word for word), as two
+			// masks over the slots a side: ALWAYS = the first l-r self loop when the black child is the far side, ASK = a link
+			// that is neither the tree parent's, nor a repeated one, nor a self loop: a back edge if it leads upwards.
+			// Then the tree vertices behind the slots of either mask.  Every other slot reads the side's own word of
+			// side_tidx again (S_end's for a lane behind the last side) and drops it.
+			uint32_t rest = 0; // the sides of the batch that are left to count_side
+#pragma unroll
+			for (uint32_t b = 0; b < BE_BATCH; b++) {
+				const uint32_t S = S0 + (it0 + b) * TPB, Sc = min(S, S_end), rem = hi[b] - lo[b], d = dp[b];
+				const uint32_t os[4] = {o4[b].x, o4[b].y, o4[b].z, o4[b].w};
+				uint32_t always = 0, ask = 0;
+				if (p[b] != NIL && rem - 1u >= 4u)
+					rest |= 1u << b;
+				else if (p[b] != NIL) {
+					bool loop_seen = false;
+#pragma unroll
+					for (uint32_t q = 0; q < 4; q++) {
+						const uint32_t o = os[q];
+						bool dup = false;
+						for (uint32_t j = 0; j < q; j++) // (a repeated link: the slots in front of this one are in hand)
+							dup = dup || os[j] == o;
+						if (q < rem && o == (S ^ 1)) {
+							if (d == o && !loop_seen)
+								always |= 1u << q;
+							loop_seen = true;
+						} else if (q < rem && o != d && !dup)
+							ask |= 1u << q;
+					}
+				}
+				m[b] = always | ask << 4;
+				root[b] = 2 * vo[b] + c[b];
+				const uint32_t want = always | ask;
+				x4[b].x = near_word(side_tidx, want & 1u ? os[0] : Sc);
+				x4[b].y = near_word(side_tidx, want & 2u ? os[1] : Sc);
+				x4[b].z = near_word(side_tidx, want & 4u ? os[2] : Sc);
+				x4[b].w = near_word(side_tidx, want & 8u ? os[3] : Sc);
+			}
+			landed(x4);
+#pragma unroll
+			for (uint32_t b = 0; b < BE_BATCH; b++) {
+				const uint32_t it = it0 + b, pb = p[b];
+				if (rest >> b & 1u)
+					continue;
+				uint32_t k = 0;
+				if (pb != NIL) {
+					const uint32_t xs[4] = {x4[b].x, x4[b].y, x4[b].z, x4[b].w};
+					uint32_t highest = NIL;
+#pragma unroll
+					for (uint32_t q = 0; q < 4; q++) {
+						const uint32_t x = xs[q];
+						if ((m[b] >> q & 1u) || ((m[b] >> (4 + q) & 1u) && x <= pb)) {
+							highest = min(highest, x);
+							if (k < 2)
+								first2[it][threadIdx.x][k] = x | (x == root[b] ? BE_ROOT : 0u);
+							k++;
+						}
+					}
+					ordcnt[pb] = (OC)k;
+					hi0[pb] = highest;
+					n += k;
+				}
+				cnt8[it][threadIdx.x] = (uint8_t)k;
+			}
+			while (rest) {
+				const uint32_t it = it0 + __ffs(rest) - 1, S = S0 + it * TPB;
+				rest &= rest - 1;
+				count_side(it, S, side_tidx[S]);
+			}
+		}
 	}
 	// exclusive prefix of n over the workgroup
 	__shared__ uint32_t wsum[TPB / 64], base;
@@ -1326,17 +1465,12 @@ __global__ void __launch_bounds__(TPB) k_back_edges(uint32_t nS, const uint32_t 
 			continue;
 		const uint32_t S = S0 + it * TPB, p = side_tidx[S];
 		if (k <= 2) {
-			uint32_t root = NIL; // (byte form: the root of p's tree, whose count nobody reads)
-			if constexpr (sizeof(IC) == 1) {
-				const uint32_t c = ckey[S >> 1];
-				root = 2 * voff[c] + c;
-			}
 			for (uint32_t j = 0; j < k; j++) {
-				const uint32_t tgt = first2[it][threadIdx.x][j];
+				const uint32_t w = first2[it][threadIdx.x][j], tgt = w & ~BE_ROOT;
 				b_src[at + j] = p;
 				b_tgt[at + j] = tgt;
 				b_ord[at + j] = j;
-				if (tgt != root)
+				if (sizeof(IC) == 4 || !(w & BE_ROOT)) // (byte form: nobody reads the count of the root of p's tree)
 					incnt_add(incnt, tgt);
 			}
 			at += k;
