@@ -821,6 +821,10 @@ typedef struct {
 	const uint8_t *step_or;	    /* [n_steps] 0 '>', 1 '<' */
 	const char *text;	    /* [n_text_bytes] */
 	const uint32_t *task_record, *task_allele, *task_col, *task_phase; /* [n_tasks] */
+	/* (behind everything the VCF checks read: what povu_hip_vcf_compare reads beside it) */
+	uint64_t n_chroms;
+	const char *const *chrom;   /* [n_chroms] the distinct CHROM strings, in order of first appearance */
+	const uint32_t *rec_chrom;  /* [n_records] */
 } povu_hip_vcf_doc;
 /* Reads VCF text: the #CHROM line names the sample columns; per record ID, POS, REF, ALT, the AT key of INFO (comma-separated,
  * one walk per allele, REF first; a walk is `[<>]id` repeated) and the GT subfield, whose position is found in FORMAT (a record
@@ -871,6 +875,56 @@ void povu_hip_vcf_report_free(povu_hip_vcf_report *r);
  * malloc'd (povu_hip_buffer_free); NULL when the three do not belong together. */
 char *povu_hip_vcf_report_text(const povu_hip_vcf_report *r, const povu_hip_vcf_doc *doc, const povu_hip_call_names *names,
 			       size_t *report_len, char **summary, size_t *summary_len);
+
+/* ---- VCF comparison ("VCF comparison": this project's own definition; the flag names of `povu vcf --compare`
+ * are those of the reference's unfinished option): how do the calls of document A differ from those of document B?  One item per
+ * (record, ALT) of either document, keyed by (CHROM, POS', REF', ALT') after the case fold and the suffix-then-prefix trim; items
+ * of equal keys form a group; per group and sample column common to both documents the doses of both sides are compared ---- */
+#define POVU_HIP_M_KEYED 0u   /* state of an item */
+#define POVU_HIP_M_SKIPPED 1u /* ALT `*`, symbolic or a breakend, REF empty or `.`: counted, keyed nowhere, group POVU_HIP_NIL */
+#define POVU_HIP_M_SHARED 0u  /* class of a group: members of both sides */
+#define POVU_HIP_M_ONLY_A 1u
+#define POVU_HIP_M_ONLY_B 2u
+typedef struct {
+	uint64_t n_items_a, n_items_b, n_groups, n_common_samples;
+	/* per side and item (document order: record, then ALT): the record, the ALT's number (from 1), the state, POS' and the bytes
+	 * the trims took at the end (first) and at the front of both texts, the group (POVU_HIP_NIL for a skipped item; POS' and
+	 * the trims are 0 then) */
+	const uint32_t *item_record_a, *item_record_b, *item_alt_a, *item_alt_b;
+	const uint8_t *item_state_a, *item_state_b;
+	const uint64_t *item_pos_a, *item_pos_b;
+	const uint32_t *item_suffix_a, *item_suffix_b, *item_prefix_a, *item_prefix_b, *item_group_a, *item_group_b;
+	/* per group, numbered in the order of their first items (A's items, then B's): class, members of either side, the first item
+	 * (an item of A, or n_items_a + an item of B) */
+	const uint8_t *group_class;
+	const uint32_t *group_n_a, *group_n_b, *group_first;
+	/* per common sample, in the order of A's columns: its column in A and in B, the cells of every class */
+	const uint32_t *sample_col_a, *sample_col_b;
+	const uint64_t *sample_tp, *sample_fp, *sample_fn, *sample_gteq;
+	uint64_t n_shared, n_only_a, n_only_b; /* groups */
+	uint64_t n_skipped_a, n_skipped_b;     /* items */
+	uint64_t n_samples_only_a, n_samples_only_b;
+	uint64_t n_tier2;  /* items the wave-per-item kernel trimmed and hashed */
+	uint64_t n_splits; /* groups the exact comparison split off a run of equal hashes */
+	double device_ms;  /* HIP-event time of the call, first upload to last byte on the host */
+} povu_hip_vcf_cmp;
+/* Compares `doc_a` (the calls) with `doc_b` (the other side), both of povu_hip_vcf_parse.  Needs no graph, paths or sequences:
+ * a fresh context will do.  Of opts->flags only POVU_HIP_V_FORCE_TIER2 is read (every item through the wave kernel; tests).
+ * Two documents without a common sample are compared: the per-sample tables are empty then.  Refused: a null context or
+ * document, a document whose arrays do not belong together, 2^32 - 64 or more records, alleles, items, tasks or text bytes in
+ * the two documents together, and when device memory runs out.  Free with povu_hip_vcf_cmp_free. */
+povu_hip_vcf_cmp *povu_hip_vcf_compare(povu_hip_ctx *ctx, const povu_hip_vcf_doc *doc_a, const povu_hip_vcf_doc *doc_b,
+				       const povu_hip_vcf_opts *opts, char *err, size_t errlen);
+void povu_hip_vcf_cmp_free(povu_hip_vcf_cmp *c);
+/* Both files of `povu vcf --compare` (host only; the comparison may be hand-made).  compare.tsv: the header
+ * `side CHROM POS REF ALT rec_idx ID n` (tabs), then one line per ONLY_A / ONLY_B group in group order: `A` or `B`, the trimmed
+ * key (letters in upper case), the first member's record index and ID, the number of members.  summary.txt: the groups of
+ * every class with precision S / (S + X), recall S / (S + Y) and F1 2S / (2S + X + Y) to four decimals (`nan` where the
+ * denominator is 0), the same from the summed tp / fp / fn, one line per common sample, and the skipped items and the
+ * unmatched sample columns when there are any.  Both malloc'd (povu_hip_buffer_free); NULL when the three do not belong
+ * together. */
+char *povu_hip_vcf_cmp_text(const povu_hip_vcf_cmp *c, const povu_hip_vcf_doc *doc_a, const povu_hip_vcf_doc *doc_b, size_t *compare_len,
+			    char **summary, size_t *summary_len);
 
 /* ---- measurement (bench.py, povu-stage-cost lines) ---- */
 typedef struct {

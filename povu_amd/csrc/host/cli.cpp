@@ -7,6 +7,8 @@
 //   variant calls of INTEGRATION.md "Variant calls" and "Inversion calls", on the GPU)
 //   povu ... vcf -i <gfa> -c <vcf> --report -o <dir> [--spelling] [--forward-only]   (the --report half of the reference's `vcf`,
 //   app/cli/cli.cpp; INTEGRATION.md "VCF checks", on the GPU)
+//   povu ... vcf -c <vcf> -d <vcf> --compare -o <dir>   (the reference's flag names, a definition of this project's own:
+//   INTEGRATION.md "VCF comparison", on the GPU; -i is accepted and not read)
 #include "decompose.hpp"
 
 #include <cstdlib>
@@ -106,7 +108,11 @@ static void usage(std::ostream &os)
 	      "        --spelling                        also compare REF and ALT with the sequences of their walks (raw-graph\n"
 	      "                                          output; rewritten records fail it) [default: false]\n"
 	      "        --forward-only                    the reference's literal rule: a walk found only reversed is absent\n"
-	      "                                          [default: false]\n";
+	      "                                          [default: false]\n"
+	      "        --compare                         instead of --report: compare the alleles and genotypes of -c (side A) with those\n"
+	      "                                          of -d (side B) by CHROM, POS, REF and ALT after trimming, and write compare.tsv\n"
+	      "                                          and summary.txt; -i is accepted and not read [default: false]\n"
+	      "        -d[vcf], --other-input-vcf=[vcf]  path to the other VCF [required by --compare]\n";
 }
 
 int main(int argc, char **argv)
@@ -209,7 +215,7 @@ int main(int argc, char **argv)
 			  << "` belongs to the reference CPU tool" << std::endl;
 		return 1;
 	}
-	if (!have_input) {
+	if (!have_input && !(command == "vcf" && povu_host::vcf_args_compare(call_args))) {
 		std::cerr << "Flag 'gfa' is required" << std::endl;
 		usage(std::cerr);
 		return 1;

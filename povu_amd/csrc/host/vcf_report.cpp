@@ -1,6 +1,8 @@
 // vcf_report.cpp -- `povu vcf --report` (INTEGRATION.md "VCF checks"): the GFA's paths (and, with --spelling, sequences) to the
 // GPU, the VCF parsed and checked against them (povu_hip_vcf_check), report.tsv and summary.txt written.  The reader, the
 // slots and both texts are the library's (host/vcfcheck.cpp); what stays here is the command line and the files.
+// `povu vcf --compare` (INTEGRATION.md "VCF comparison") likewise: two VCFs parsed and compared on a fresh context
+// (povu_hip_vcf_compare), compare.tsv and summary.txt written; the GFA is not read.
 #include "decompose.hpp"
 #include "gfa.hpp"
 
@@ -20,8 +22,8 @@ namespace povu_host
 namespace
 {
 struct VcfArgs {
-	std::string vcf, out_dir = ".";
-	bool report = false, spelling = false, forward_only = false;
+	std::string vcf, other_vcf, out_dir = ".";
+	bool report = false, compare = false, spelling = false, forward_only = false;
 };
 
 VcfArgs parse_vcf_args(const std::vector<std::string> &a)
@@ -45,10 +47,12 @@ VcfArgs parse_vcf_args(const std::vector<std::string> &a)
 	};
 	for (size_t i = 0; i < a.size(); i++) {
 		const std::string &x = a[i];
-		if (value(i, "-c", "--vcf", c.vcf) || value(i, "-o", "--output-dir", c.out_dir))
+		if (value(i, "-c", "--vcf", c.vcf) || value(i, "-o", "--output-dir", c.out_dir) || value(i, "-d", "--other-input-vcf", c.other_vcf))
 			continue;
 		if (x == "--report")
 			c.report = true;
+		else if (x == "--compare")
+			c.compare = true;
 		else if (x == "--spelling")
 			c.spelling = true;
 		else if (x == "--forward-only")
@@ -58,26 +62,92 @@ VcfArgs parse_vcf_args(const std::vector<std::string> &a)
 		else
 			throw std::runtime_error("Flag could not be matched: " + x);
 	}
-	if (!c.report)
+	if (c.report && c.compare)
+		throw std::runtime_error("--compare and --report exclude each other");
+	if (!c.other_vcf.empty() && !c.compare)
+		throw std::runtime_error("Flag '-d' (--other-input-vcf) is read by --compare only");
+	if (!c.report && !c.compare)
 		throw std::runtime_error("vcf needs --report (the interactive --tui is not provided by this build)");
+	if (c.compare && c.other_vcf.empty())
+		throw std::runtime_error("--compare needs the other VCF: Flag 'other-input-vcf' is required (-d <vcf>)");
+	if (c.compare && (c.spelling || c.forward_only))
+		throw std::runtime_error(std::string(c.spelling ? "--spelling" : "--forward-only") + " belongs to --report, not to --compare");
 	if (c.vcf.empty())
 		throw std::runtime_error("Flag 'vcf' is required (-c <vcf>)");
 	return c;
 }
+
+std::string read_vcf(const std::string &path)
+{
+	std::ifstream in(path, std::ios::binary);
+	if (!in)
+		throw std::runtime_error("cannot read the VCF " + path);
+	std::stringstream buf;
+	buf << in.rdbuf();
+	return buf.str();
+}
+
+void do_compare(const Config &cfg, const VcfArgs &va)
+{
+	char err[512] = {0};
+	const uint32_t threads = (uint32_t)std::max(1, cfg.threads);
+	povu_hip_vcf_doc *doc[2] = {nullptr, nullptr};
+	povu_hip_ctx *ctx = nullptr;
+	povu_hip_vcf_cmp *cmp = nullptr;
+	char *table = nullptr, *summary = nullptr;
+	std::string bad;
+	for (int k = 0; k < 2 && bad.empty(); k++) {
+		const std::string &path = k ? va.other_vcf : va.vcf;
+		try {
+			const std::string text = read_vcf(path);
+			doc[k] = povu_hip_vcf_parse(text.data(), text.size(), threads, err, sizeof err);
+			if (!doc[k])
+				bad = path + ": " + err;
+		} catch (const std::runtime_error &e) {
+			bad = e.what();
+		}
+	}
+	if (bad.empty() && !(ctx = povu_hip_create(cfg.device, err, sizeof err)))
+		bad = std::string("povu_hip: ") + err;
+	if (bad.empty() && !(cmp = povu_hip_vcf_compare(ctx, doc[0], doc[1], nullptr, err, sizeof err)))
+		bad = std::string("vcf: ") + err;
+	size_t tlen = 0, slen = 0;
+	if (bad.empty() && !(table = povu_hip_vcf_cmp_text(cmp, doc[0], doc[1], &tlen, &summary, &slen)))
+		bad = "cannot format the comparison";
+	if (bad.empty() && mkdir(va.out_dir.c_str(), 0777) != 0 && errno != EEXIST)
+		bad = "cannot create the output directory " + va.out_dir;
+	if (bad.empty()) {
+		std::ofstream t(va.out_dir + "/compare.tsv", std::ios::binary), s(va.out_dir + "/summary.txt", std::ios::binary);
+		t.write(table, (std::streamsize)tlen);
+		s.write(summary, (std::streamsize)slen);
+		if (!t || !s)
+			bad = "cannot write compare.tsv and summary.txt to " + va.out_dir;
+	}
+	povu_hip_buffer_free(table);
+	povu_hip_buffer_free(summary);
+	if (cmp)
+		povu_hip_vcf_cmp_free(cmp);
+	if (ctx)
+		povu_hip_destroy(ctx);
+	for (povu_hip_vcf_doc *d : doc)
+		if (d)
+			povu_hip_vcf_doc_free(d);
+	if (!bad.empty())
+		throw std::runtime_error(bad);
+}
 } // namespace
+
+// the arguments of `vcf` ask for --compare, which reads no GFA (cli.cpp: -i is then not required)
+bool vcf_args_compare(const std::vector<std::string> &args) { return std::find(args.begin(), args.end(), "--compare") != args.end(); }
 
 void do_vcf(const Config &cfg, const std::vector<std::string> &args)
 {
 	const VcfArgs va = parse_vcf_args(args);
-	std::string text;
-	{
-		std::ifstream in(va.vcf, std::ios::binary);
-		if (!in)
-			throw std::runtime_error("cannot read the VCF " + va.vcf);
-		std::stringstream buf;
-		buf << in.rdbuf();
-		text = buf.str();
+	if (va.compare) {
+		do_compare(cfg, va);
+		return;
 	}
+	const std::string text = read_vcf(va.vcf);
 	char err[512] = {0};
 	const uint32_t threads = (uint32_t)std::max(1, cfg.threads);
 	povu_hip_vcf_doc *doc = povu_hip_vcf_parse(text.data(), text.size(), threads, err, sizeof err);

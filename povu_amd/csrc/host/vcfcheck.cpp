@@ -3,6 +3,7 @@
 // two files of `povu vcf --report`.  tests/vcfcheck_ref.py restates it as the yardstick.
 #include "../../../include/povu_hip.h"
 #include "../hip/vcfcheck_rules.hpp"
+#include "../hip/vcfcmp_rules.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -11,6 +12,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 namespace
@@ -67,6 +69,10 @@ struct Chunk {
 	std::vector<uint8_t> allele_walk, step_or;
 	std::vector<uint32_t> step_id, task_allele, task_col, task_phase;
 	std::string ids, text;
+	// the CHROM strings of the chunk in order of first appearance, and every record's among them
+	std::vector<std::string> chrom;
+	std::unordered_map<std::string, uint32_t> chrom_of;
+	std::vector<uint32_t> rec_chrom;
 	uint64_t bad_line = 0; // the first malformed line, 0: none
 	std::string bad;
 };
@@ -152,6 +158,10 @@ void parse_record(const char *text, const Line &ln, size_t n_samples, Chunk &c)
 	}
 	c.line.push_back(ln.no);
 	c.pos.push_back(pos);
+	const auto at_chrom = c.chrom_of.emplace(std::string(f[0].p, f[0].n), (uint32_t)c.chrom.size());
+	if (at_chrom.second)
+		c.chrom.push_back(at_chrom.first->first);
+	c.rec_chrom.push_back(at_chrom.first->second);
 	c.ids.append(f[2].p, f[2].n);
 	c.id_off.push_back(c.ids.size());
 	c.allele_off.push_back(c.allele_walk.size());
@@ -180,6 +190,9 @@ struct Doc {
 	std::vector<uint8_t> allele_walk, step_or;
 	std::vector<uint32_t> step_id, task_record, task_allele, task_col, task_phase;
 	std::string ids, text;
+	std::vector<std::string> chrom;
+	std::vector<const char *> chrom_ptr;
+	std::vector<uint32_t> rec_chrom;
 };
 
 template <class T> void append(std::vector<T> &to, const std::vector<T> &from) { to.insert(to.end(), from.begin(), from.end()); }
@@ -290,8 +303,18 @@ try {
 			return nullptr;
 		}
 	}
+	std::unordered_map<std::string, uint32_t> chrom_of; // of the document: a chunk's new strings behind those of the chunks before
 	for (const Chunk &c : chunks) {
 		const uint64_t r0 = d->line.size();
+		std::vector<uint32_t> global(c.chrom.size());
+		for (size_t k = 0; k < c.chrom.size(); k++) {
+			const auto at = chrom_of.emplace(c.chrom[k], (uint32_t)d->chrom.size());
+			if (at.second)
+				d->chrom.push_back(c.chrom[k]);
+			global[k] = at.first->second;
+		}
+		for (uint32_t k : c.rec_chrom)
+			d->rec_chrom.push_back(global[k]);
 		for (size_t r = 0; r + 1 < c.task_off.size(); r++)
 			d->task_record.insert(d->task_record.end(), c.task_off[r + 1] - c.task_off[r], (uint32_t)(r0 + r));
 		append(d->line, c.line);
@@ -316,6 +339,8 @@ try {
 	}
 	for (auto &s : d->sample)
 		d->sample_ptr.push_back(s.c_str());
+	for (auto &s : d->chrom)
+		d->chrom_ptr.push_back(s.c_str());
 	povu_hip_vcf_doc &p = d->pub;
 	p.n_samples = d->sample.size();
 	p.n_records = d->line.size();
@@ -341,6 +366,9 @@ try {
 	p.task_allele = d->task_allele.data();
 	p.task_col = d->task_col.data();
 	p.task_phase = d->task_phase.data();
+	p.n_chroms = d->chrom.size();
+	p.chrom = d->chrom_ptr.data();
+	p.rec_chrom = d->rec_chrom.data();
 	return &d.release()->pub;
 } catch (const std::exception &x) {
 	set_err(err, errlen, std::string("vcf parse: ") + x.what());
@@ -414,6 +442,88 @@ try {
 		snprintf(line, sizeof line, "Error rate: %.2f%%\n", (double)n_invalid / (double)doc->n_records * 100.0);
 	*summary = to_buffer(line, summary_len);
 	char *rep = *summary ? to_buffer(out, report_len) : nullptr;
+	if (!rep) {
+		free(*summary);
+		*summary = nullptr;
+	}
+	return rep;
+} catch (const std::bad_alloc &) {
+	return nullptr;
+}
+
+// ---- the two files of `povu vcf --compare` (INTEGRATION.md "VCF comparison")
+
+namespace
+{
+// `num / den` to four decimals, `nan` where the denominator is 0
+std::string ratio(uint64_t num, uint64_t den)
+{
+	if (!den)
+		return "nan";
+	char b[32];
+	snprintf(b, sizeof b, "%.4f", (double)num / (double)den);
+	return b;
+}
+std::string rates(uint64_t both, uint64_t only_a, uint64_t only_b)
+{
+	return "precision " + ratio(both, both + only_a) + ", recall " + ratio(both, both + only_b) + ", F1 " + ratio(2 * both, 2 * both + only_a + only_b);
+}
+} // namespace
+
+extern "C" char *povu_hip_vcf_cmp_text(const povu_hip_vcf_cmp *c, const povu_hip_vcf_doc *doc_a, const povu_hip_vcf_doc *doc_b, size_t *compare_len,
+				       char **summary, size_t *summary_len)
+try {
+	using namespace povu_hip;
+	if (!c || !doc_a || !doc_b || !summary)
+		return nullptr;
+	std::string out = "side\tCHROM\tPOS\tREF\tALT\trec_idx\tID\tn\n";
+	for (uint64_t g = 0; g < c->n_groups; g++) {
+		if (c->group_class[g] == POVU_HIP_M_SHARED)
+			continue;
+		const bool b = c->group_class[g] == POVU_HIP_M_ONLY_B;
+		uint64_t i = c->group_first[g];
+		if (b != (i >= c->n_items_a) || i >= c->n_items_a + c->n_items_b)
+			return nullptr;
+		i -= b ? c->n_items_a : 0;
+		const povu_hip_vcf_doc *d = b ? doc_b : doc_a;
+		const uint64_t r = (b ? c->item_record_b : c->item_record_a)[i], k = (b ? c->item_alt_b : c->item_alt_a)[i];
+		const uint64_t s = (b ? c->item_suffix_b : c->item_suffix_a)[i], p = (b ? c->item_prefix_b : c->item_prefix_a)[i];
+		if (r >= d->n_records || !k || d->allele_off[r] + k >= d->allele_off[r + 1] || d->rec_chrom[r] >= d->n_chroms)
+			return nullptr;
+		const uint64_t ar = d->allele_off[r], aa = ar + k;
+		const uint64_t nr = d->text_off[ar + 1] - d->text_off[ar], na = d->text_off[aa + 1] - d->text_off[aa];
+		if (s + p > nr || s + p > na)
+			return nullptr;
+		out += std::string(b ? "B" : "A") + "\t" + d->chrom[d->rec_chrom[r]] + "\t" + std::to_string((b ? c->item_pos_b : c->item_pos_a)[i]) + "\t";
+		for (uint64_t x = p; x < nr - s; x++)
+			out += (char)vm_fold(d->text[d->text_off[ar] + x]);
+		out += "\t";
+		for (uint64_t x = p; x < na - s; x++)
+			out += (char)vm_fold(d->text[d->text_off[aa] + x]);
+		out += "\t" + std::to_string(r) + "\t";
+		out.append(d->ids + d->rec_id_off[r], d->rec_id_off[r + 1] - d->rec_id_off[r]);
+		out += "\t" + std::to_string((uint64_t)c->group_n_a[g] + c->group_n_b[g]) + "\n";
+	}
+	uint64_t tp = 0, fp = 0, fn = 0, gteq = 0;
+	for (uint64_t x = 0; x < c->n_common_samples; x++)
+		tp += c->sample_tp[x], fp += c->sample_fp[x], fn += c->sample_fn[x], gteq += c->sample_gteq[x];
+	std::string sum = "Alleles: shared " + std::to_string(c->n_shared) + ", only A " + std::to_string(c->n_only_a) + ", only B " +
+			  std::to_string(c->n_only_b) + "\n";
+	sum += "Alleles: " + rates(c->n_shared, c->n_only_a, c->n_only_b) + "\n";
+	sum += "Genotypes: tp " + std::to_string(tp) + ", fp " + std::to_string(fp) + ", fn " + std::to_string(fn) + ", gteq " + std::to_string(gteq) + "\n";
+	sum += "Genotypes: " + rates(tp, fp, fn) + "\n";
+	for (uint64_t x = 0; x < c->n_common_samples; x++) {
+		if (c->sample_col_a[x] >= doc_a->n_samples)
+			return nullptr;
+		sum += std::string("Sample ") + doc_a->sample[c->sample_col_a[x]] + ": tp " + std::to_string(c->sample_tp[x]) + ", fp " +
+		       std::to_string(c->sample_fp[x]) + ", fn " + std::to_string(c->sample_fn[x]) + ", gteq " + std::to_string(c->sample_gteq[x]) + "\n";
+	}
+	if (c->n_skipped_a || c->n_skipped_b)
+		sum += "Skipped alleles: A " + std::to_string(c->n_skipped_a) + ", B " + std::to_string(c->n_skipped_b) + "\n";
+	if (c->n_samples_only_a || c->n_samples_only_b)
+		sum += "Unmatched sample columns: A " + std::to_string(c->n_samples_only_a) + ", B " + std::to_string(c->n_samples_only_b) + "\n";
+	*summary = to_buffer(sum, summary_len);
+	char *rep = *summary ? to_buffer(out, compare_len) : nullptr;
 	if (!rep) {
 		free(*summary);
 		*summary = nullptr;

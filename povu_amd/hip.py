@@ -116,7 +116,12 @@ class _VcfDoc(C.Structure):
                  ("task_off", C.POINTER(C.c_uint64)), ("step_off", C.POINTER(C.c_uint64)), ("text_off", C.POINTER(C.c_uint64)),
                  ("allele_walk", C.POINTER(C.c_uint8)), ("step_id", C.POINTER(C.c_uint32)), ("step_or", C.POINTER(C.c_uint8)),
                  ("text", C.POINTER(C.c_uint8))] +
-                [(k, C.POINTER(C.c_uint32)) for k in ("task_record", "task_allele", "task_col", "task_phase")])
+                [(k, C.POINTER(C.c_uint32)) for k in ("task_record", "task_allele", "task_col", "task_phase")] +
+                [("n_chroms", C.c_uint64), ("chrom", C.POINTER(C.c_char_p)), ("rec_chrom", C.POINTER(C.c_uint32))])
+
+
+# the counters of povu_hip_vcf_cmp behind its arrays (VcfComparison carries them under these names)
+VCF_CMP_COUNTERS = ("n_shared", "n_only_a", "n_only_b", "n_skipped_a", "n_skipped_b", "n_samples_only_a", "n_samples_only_b", "n_tier2", "n_splits")
 
 
 class _VcfOpts(C.Structure):
@@ -129,6 +134,19 @@ class _VcfReport(C.Structure):
                 [(k, C.POINTER(C.c_uint32)) for k in ("rec_allele", "rec_task")] +
                 [("n_status", C.c_uint64 * 6), ("n_invalid", C.c_uint64), ("n_misspelled", C.c_uint64), ("n_tier2", C.c_uint64),
                  ("device_ms", C.c_double)])
+
+
+class _VcfCmp(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_items_a", "n_items_b", "n_groups", "n_common_samples")] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("item_record_a", "item_record_b", "item_alt_a", "item_alt_b")] +
+                [(k, C.POINTER(C.c_uint8)) for k in ("item_state_a", "item_state_b")] +
+                [(k, C.POINTER(C.c_uint64)) for k in ("item_pos_a", "item_pos_b")] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("item_suffix_a", "item_suffix_b", "item_prefix_a", "item_prefix_b", "item_group_a",
+                                                      "item_group_b")] +
+                [("group_class", C.POINTER(C.c_uint8))] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("group_n_a", "group_n_b", "group_first", "sample_col_a", "sample_col_b")] +
+                [(k, C.POINTER(C.c_uint64)) for k in ("sample_tp", "sample_fp", "sample_fn", "sample_gteq")] +
+                [(k, C.c_uint64) for k in VCF_CMP_COUNTERS] + [("device_ms", C.c_double)])
 
 
 OFFREF_COUNTERS = ("n_offref_sites", "n_offref_records", "n_offref_hosted")  # of Calls
@@ -275,6 +293,9 @@ V_FOUND_FWD, V_FOUND_REV, V_ABSENT, V_NO_AT, V_BAD_STEP, V_NO_SLOT, V_MISSPELLED
 V_STATUS_NAMES = ("found_fwd", "found_rev", "absent", "no_at", "bad_step", "no_slot", "misspelled")
 V_SPELL_NONE, V_SPELL_WHOLE, V_SPELL_ANCHORED, V_SPELL_MISSPELLED = range(4)
 V_FORWARD_ONLY, V_SPELLING, V_FORCE_TIER2 = 1, 2, 4
+# "VCF comparison" (HipDecomposer.compare_vcfs): the state of an item, the class of a group
+M_KEYED, M_SKIPPED = 0, 1
+M_SHARED, M_ONLY_A, M_ONLY_B = 0, 1, 2
 
 _lib = None
 
@@ -382,6 +403,12 @@ def load_lib():
     l.povu_hip_vcf_report_text.argtypes = [C.POINTER(_VcfReport), C.POINTER(_VcfDoc), C.POINTER(_CallNames), C.POINTER(C.c_size_t),
                                            C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     l.povu_hip_vcf_report_text.restype = C.c_void_p
+    l.povu_hip_vcf_compare.argtypes = [C.c_void_p, C.POINTER(_VcfDoc), C.POINTER(_VcfDoc), C.POINTER(_VcfOpts), C.c_char_p, C.c_size_t]
+    l.povu_hip_vcf_compare.restype = C.POINTER(_VcfCmp)
+    l.povu_hip_vcf_cmp_free.argtypes = [C.POINTER(_VcfCmp)]
+    l.povu_hip_vcf_cmp_text.argtypes = [C.POINTER(_VcfCmp), C.POINTER(_VcfDoc), C.POINTER(_VcfDoc), C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    l.povu_hip_vcf_cmp_text.restype = C.c_void_p
     l.povu_hip_forest_pvst_text.restype = C.c_void_p
     l.povu_hip_forest_pvst_text.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]
     l.povu_hip_buffer_free.argtypes = [C.c_void_p]
@@ -1064,7 +1091,8 @@ class VcfDoc:
     """A parsed VCF (parse_vcf; povu_hip_vcf_parse): numpy views of the arrays of povu_hip_vcf_doc, valid as long as this object
     lives -- samples (the column names), rec_line / rec_pos / rec_id per record, allele_off / task_off (per record), step_off /
     text_off / allele_walk (per allele; bit 0: AT holds a walk, bit 1: it has a text), step_id / step_or, text (bytes),
-    task_record / task_allele / task_col / task_phase."""
+    task_record / task_allele / task_col / task_phase; chroms (the distinct CHROM strings in order of first appearance) and
+    rec_chrom (per record, an index into them)."""
 
     def __init__(self, lib, ptr):
         self._lib, self._p = lib, ptr
@@ -1084,6 +1112,8 @@ class VcfDoc:
         self.text = _view(d.text, int(d.n_text_bytes), np.uint8)
         for k in ("task_record", "task_allele", "task_col", "task_phase"):
             setattr(self, k, _view(getattr(d, k), nk, np.uint32))
+        self.chroms = [d.chrom[k].decode() for k in range(d.n_chroms)]
+        self.rec_chrom = _view(d.rec_chrom, n, np.uint32)
 
     def __del__(self):
         if getattr(self, "_p", None):
@@ -1150,6 +1180,56 @@ class VcfReport:
     def summary_text(self) -> str:
         """summary.txt: `No errors`, or the rate of invalid records."""
         return _vcf_texts(self._lib, self._p, self.doc._p, self._names_rec)[1]
+
+
+class VcfComparison:
+    """What HipDecomposer.compare_vcfs found (povu_hip_vcf_cmp): numpy views, valid as long as this object lives.  Per side
+    (`_a`, `_b`) and item, in document order: item_record, item_alt (from 1), item_state (M_KEYED, M_SKIPPED), item_pos (POS'),
+    item_suffix / item_prefix (the bytes the trims took), item_group (0xFFFFFFFF for a skipped item).  Per group, in the order of
+    their first items: group_class (M_SHARED, M_ONLY_A, M_ONLY_B), group_n_a / group_n_b, group_first (an item of A, or n_items_a +
+    an item of B).  Per common sample: sample_col_a / sample_col_b, sample_tp / _fp / _fn / _gteq.  The counters n_items_a,
+    n_items_b, n_groups, n_common_samples and VCF_CMP_COUNTERS; device_ms.  `doc_a` and `doc_b` are the parsed VCFs."""
+
+    def __init__(self, lib, ptr, doc_a: VcfDoc, doc_b: VcfDoc):
+        self._lib, self._p, self.doc_a, self.doc_b = lib, ptr, doc_a, doc_b
+        c = ptr.contents
+        for k in ("n_items_a", "n_items_b", "n_groups", "n_common_samples") + VCF_CMP_COUNTERS:
+            setattr(self, k, int(getattr(c, k)))
+        for side, n in (("a", self.n_items_a), ("b", self.n_items_b)):
+            for k, dt in (("item_record", np.uint32), ("item_alt", np.uint32), ("item_state", np.uint8), ("item_pos", np.uint64),
+                          ("item_suffix", np.uint32), ("item_prefix", np.uint32), ("item_group", np.uint32)):
+                setattr(self, f"{k}_{side}", _view(getattr(c, f"{k}_{side}"), n, dt))
+        self.group_class = _view(c.group_class, self.n_groups, np.uint8)
+        for k in ("group_n_a", "group_n_b", "group_first"):
+            setattr(self, k, _view(getattr(c, k), self.n_groups, np.uint32))
+        for k in ("sample_col_a", "sample_col_b"):
+            setattr(self, k, _view(getattr(c, k), self.n_common_samples, np.uint32))
+        for k in ("sample_tp", "sample_fp", "sample_fn", "sample_gteq"):
+            setattr(self, k, _view(getattr(c, k), self.n_common_samples, np.uint64))
+        self.device_ms = float(c.device_ms)
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            self._lib.povu_hip_vcf_cmp_free(self._p)
+            self._p = None
+
+    def _texts(self):
+        ln, sl, sp = C.c_size_t(0), C.c_size_t(0), C.c_void_p(None)
+        p = self._lib.povu_hip_vcf_cmp_text(self._p, self.doc_a._p, self.doc_b._p, C.byref(ln), C.byref(sp), C.byref(sl))
+        if not p:
+            raise RuntimeError("the comparison and the documents do not belong together")
+        out = C.string_at(p, ln.value).decode(), C.string_at(sp.value, sl.value).decode()
+        self._lib.povu_hip_buffer_free(p)
+        self._lib.povu_hip_buffer_free(sp)
+        return out
+
+    def compare_text(self) -> str:
+        """compare.tsv of `povu vcf --compare`: a line per group that only one side has, in group order."""
+        return self._texts()[0]
+
+    def summary_text(self) -> str:
+        """summary.txt: the groups of every class, the cells of every class, their rates, a line per common sample."""
+        return self._texts()[1]
 
 
 class HipDecomposer:
@@ -1456,6 +1536,21 @@ class HipDecomposer:
             self._lib.povu_hip_call_names_free(nr)
             raise RuntimeError(err.value.decode())
         return VcfReport(self._lib, p, doc, nr)
+
+    def compare_vcfs(self, a, b, force_tier2: bool = False, threads: int = 1) -> VcfComparison:
+        """How do the calls of VCF `a` differ from those of `b` (text or a VcfDoc of parse_vcf each; INTEGRATION.md "VCF
+        comparison")?  Every (record, ALT) is keyed by (CHROM, POS', REF', ALT') after the case fold and the suffix-then-prefix
+        trim, equal keys form a group (shared, only A, only B), and per group and sample column of both documents the doses
+        of both sides are compared (tp, fp, fn, gteq).  Needs no graph: a fresh context will do.  force_tier2: every item through
+        the wave-per-item kernel (tests)."""
+        doc_a = a if isinstance(a, VcfDoc) else parse_vcf(a, threads)
+        doc_b = b if isinstance(b, VcfDoc) else parse_vcf(b, threads)
+        err = C.create_string_buffer(512)
+        o = _VcfOpts(V_FORCE_TIER2 if force_tier2 else 0)
+        p = self._lib.povu_hip_vcf_compare(self._ctx, doc_a._p, doc_b._p, C.byref(o), err, 512)
+        if not p:
+            raise RuntimeError(err.value.decode())
+        return VcfComparison(self._lib, p, doc_a, doc_b)
 
     def traversals(self, forest: Forest, max_steps: int = 65536, flags: int = 0) -> Traversals:
         """The traversals of every flubble of `forest` by the resident paths, on the GPU."""
