@@ -381,6 +381,9 @@ typedef struct {
 #define POVU_HIP_T_MERGE 8u	  /* povu_hip_call_profile under POVU_HIP_PROFILE_DECOMPOSED only: equal primitives merged ("Merged primitives") */
 #define POVU_HIP_T_OFFREF 16u	  /* povu_hip_call / _call_profile only: sites no reference path crosses, on a surrogate path ("Off-reference calls") */
 #define POVU_HIP_T_UNTANGLE 32u	  /* povu_hip_call / _call_profile only: per-copy genotypes where a path laps a site, by lap alignment ("Untangled calls") */
+/* povu_hip_call and its kin, with POVU_HIP_T_NESTED or a profile that implies it only: a `*` ALT where an enclosing allele deletes
+ * the site ("Spanning alleles").  Refused without a nested call and under the left-normalized and decomposed profiles */
+#define POVU_HIP_T_SPANNING 64u
 #define POVU_HIP_TRAV_LONG 1u	  /* status bits per query: a scan would need more than max_steps steps */
 #define POVU_HIP_TRAV_STRAY 2u	  /* a scan met a boundary step that does not close it */
 #define POVU_HIP_TRAV_OPEN 4u	  /* a scan reached the end of its path */
@@ -576,6 +579,16 @@ typedef struct {
 	uint64_t n_cluster_pairs;     /* (exact allele, representative) pairs the leader loops met */
 	uint64_t n_cluster_pruned;    /* ... of which the weight bound skipped (0 with POVU_HIP_CLUSTER_NO_BOUND) */
 	uint64_t n_cluster_tier2;     /* bags the device-wide sort sorted (more than 64 keys, or all with _T_FORCE_TIER2) */
+	/* with POVU_HIP_T_SPANNING ("Spanning alleles").  Without the flag: spanning 0, rec_star NULL, the counts 0.  An entry
+	 * (record, slot) is spanned when no path of the slot traverses the record's site, the site's search was not cut short and a
+	 * path of the slot traverses the site of some enclosing record (the chain of parent_query, taken before the profile drops
+	 * any).  A record with a spanned entry has one more ALT, its last, written `*`: n_alleles counts it, ac has an entry for it,
+	 * the spanned entries of gt carry its number n_alleles - 1, an and ns count them.  It has no spelled allele: the block of the
+	 * record holds n_alleles - 1 alleles */
+	uint64_t spanning;	      /* 1: made with POVU_HIP_T_SPANNING */
+	const uint8_t *rec_star;      /* [n_records] 1: the record's last ALT is `*` */
+	uint64_t n_star_records;      /* records with rec_star */
+	uint64_t n_star_entries;      /* spanned (record, slot) entries of those records */
 } povu_hip_calls;
 /* The calls of `sites` by the reference paths `refs` among the paths resident in `ctx` (sequences resident too).  opts as
  * for povu_hip_forest_traversals (NULL = defaults).  Refused like the traversals, when no sequences are resident, when a
@@ -788,7 +801,10 @@ char *povu_hip_calls_vcf_rest(const povu_hip_calls *c, const povu_hip_sites *sit
 #define POVU_HIP_V_NO_AT 3u    /* no AT, fewer walks than the allele's number + 1, or an empty walk */
 #define POVU_HIP_V_BAD_STEP 4u /* a step names a segment the graph does not have */
 #define POVU_HIP_V_NO_SLOT 5u  /* no sample has the column's name, or the phase is beyond its slots */
-/* (checked in this order: NO_AT, BAD_STEP, NO_SLOT, FOUND_FWD, FOUND_REV, ABSENT).  As a record's reason also: */
+/* (checked in this order: NO_AT, BAD_STEP, NO_SLOT, FOUND_FWD, FOUND_REV, ABSENT).  In front of them all: a task that names an
+ * allele spelled `*` (the spanning allele of VCF 4.2, "Spanning alleles") is not searched and is FOUND_FWD -- the allele is
+ * absent by an overlapping event and there is nothing to find; its AT entry `*` is read as a walk without steps.  As a
+ * record's reason also: */
 #define POVU_HIP_V_MISSPELLED 6u
 #define POVU_HIP_V_N_STATUS 6u /* task statuses */
 /* the spelling of an allele (POVU_HIP_V_SPELLING): not checked (the flag is off, no walk, a walk with a bad step or no text for

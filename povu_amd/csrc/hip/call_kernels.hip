@@ -287,13 +287,16 @@ __global__ void k_cl_key(uint32_t nrec, int which, const uint32_t *__restrict__ 
 // per record (sorted; row dst[i] of the record list when inversion records are merged in, else row i): its fields, the ALT count for the AC offsets, the (site, orientation) it needs spelled
 __global__ void k_cl_rec_fields(uint32_t nrec, const uint32_t *__restrict__ perm, CallView V, InvRows o, uint32_t *__restrict__ need,
 				const uint32_t *__restrict__ dst, const uint32_t *__restrict__ n_level, const uint32_t *__restrict__ n_parent,
-				uint32_t *__restrict__ o_level, uint32_t *__restrict__ o_parent, uint32_t *__restrict__ xneed)
+				uint32_t *__restrict__ o_level, uint32_t *__restrict__ o_parent, uint32_t *__restrict__ xneed,
+				const uint8_t *__restrict__ star, uint8_t *__restrict__ o_star)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
 		const uint32_t j = perm[i], t = V.rlist[j], q = V.trav.rq[t], d = dst ? dst[i] : i;
 		// (what is read, then what is written: the rows' pointers come in a struct and promise the compiler nothing)
 		const uint32_t level = n_level ? n_level[j] : V.height[q] - 1, parent = n_parent ? n_parent[j] : NO_QUERY;
-		const uint32_t path = V.trav.op[t], first = V.trav.of[t], ref = V.oa[t], nal = V.aoff[q + 1] - V.aoff[q];
+		// ("Spanning alleles": a record with a spanned entry writes one ALT more, `*`, behind its classes)
+		const bool has_star = star && star[j];
+		const uint32_t path = V.trav.op[t], first = V.trav.of[t], ref = V.oa[t], nal = span_n_alleles(V.aoff[q + 1] - V.aoff[q], has_star);
 		const uint64_t pos = V.pos[j];
 		const uint8_t st = V.rstate[j], orv = V.trav.orv[t];
 		o_level[d] = level;
@@ -306,6 +309,8 @@ __global__ void k_cl_rec_fields(uint32_t nrec, const uint32_t *__restrict__ perm
 		o.o_nal[d] = nal;
 		o.o_pos[d] = pos;
 		o.nalt[d] = nal - 1;
+		if (o_star)
+			o_star[d] = has_star;
 		need[4 * (size_t)q + ((st & RS_ANCHORED) ? 2 : 0) + orv] = 1;
 	}
 }
@@ -318,12 +323,15 @@ __global__ void k_cl_sorted_keys(uint32_t nrec, const uint32_t *__restrict__ per
 	}
 }
 
-// GT codes, AC, AN, NS and flags: one wave per record, a lane per sample (its slots are consecutive)
+// GT codes, AC, AN, NS and flags: one wave per record, a lane per sample (its slots are consecutive).  SPAN ("Spanning
+// alleles"): an empty slot whose bit of span_bits is set takes the `*` code; without it the kernel is the one it was
+template <bool SPAN>
 __global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, CallView V, SlotsView SL, InvRows o, const uint32_t *__restrict__ qidx,
 						      const uint32_t *__restrict__ smin, const uint32_t *__restrict__ smax,
 						      const uint64_t *__restrict__ ac_off, const uint32_t *__restrict__ perm,
 						      const uint8_t *__restrict__ collapsed, const uint8_t *__restrict__ rescued,
-						      uint32_t *__restrict__ ac, const uint32_t *__restrict__ dst)
+						      uint32_t *__restrict__ ac, const uint32_t *__restrict__ dst,
+							      const unsigned long long *__restrict__ span_bits, uint32_t span_words)
 {
 	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
 	// what the loop over the slots reads and writes, out of the structs
@@ -334,6 +342,9 @@ __global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, CallView V,
 		const uint32_t i = dst ? dst[i0] : i0;
 		const uint32_t q = o.o_q[i], ra = o.o_ref[i], own = SL.slot_of_path[o.o_path[i]];
 		const uint64_t base = (uint64_t)qidx[q] * S;
+		// "Spanning alleles": the words of the record's spanned entries (k_ns_span, by the record before the sort), its classes
+		const unsigned long long *__restrict__ spanned = SPAN ? span_bits + (uint64_t)perm[i0] * span_words : nullptr;
+		const uint32_t n_classes = SPAN ? V.aoff[q + 1] - V.aoff[q] : 0;
 		uint32_t n_an = 0, n_ns = 0, amb = 0;
 		for (uint32_t sm = lane; sm < n_samples; sm += 64) {
 			bool any = false;
@@ -347,6 +358,8 @@ __global__ __launch_bounds__(Q_TPB) void k_cl_records(uint32_t nrec, CallView V,
 						code = mn == ra ? 0 : mn < ra ? mn + 1 : mn;
 					else if (mn != 0xFFFFFFFFu)
 						amb = 1;
+					else if (SPAN)
+						code = span_gt_code(code, (spanned[sl >> 6] >> (sl & 63u)) & 1ull, n_classes);
 				}
 				gt[(uint64_t)i * S + sl] = (uint16_t)code;
 				if (code != POVU_HIP_GT_MISSING) {
@@ -556,6 +569,8 @@ struct CallsOwner {
 	// clustered calls
 	PinnedVec<uint8_t> rec_clustered;
 	PinnedVec<uint32_t> cl_minsim, cl_nx;
+	// POVU_HIP_T_SPANNING
+	PinnedVec<uint8_t> rec_star;
 };
 
 using namespace povu_hip;
@@ -568,6 +583,7 @@ struct CallInputs {
 	const povu_hip_trav_opts *opts;
 	uint32_t n, P, nR, S, NS, n_trees = 0;
 	bool inversions, nested, normalized, decomposed, merge, offref, untangle;
+	bool spanning = false;	  // POVU_HIP_T_SPANNING: an option of the nested call
 	uint32_t cluster_ppm = 0; // clustered calls: the threshold T, 0: not clustered
 	bool cluster_no_bound = false;
 	bool classes() const { return nested || cluster_ppm; } // the call reads classes of exact alleles where it reads alleles
@@ -623,6 +639,7 @@ struct CallRecs {
 	BlockLayout L;	   // their blocks of spelled alleles
 	uint32_t *xneed, *xoff, *xlist, *xrow, *o_level, *o_parent; // the extra blocks (REFs spelled on their own)
 	uint8_t *rec_clustered; // clustered calls: per record
+	uint8_t *o_star = nullptr; // POVU_HIP_T_SPANNING: per record, its last ALT is `*` (else null)
 	uint32_t *cl_minsim;
 	uint64_t *ref_spelled;
 	uint64_t n_ac = 0; // ALT counts
@@ -682,6 +699,11 @@ CallInputs check_call_inputs(povu_hip_ctx *ctx, const povu_hip_sites *sites, con
 	if (in.normalized || in.decomposed)
 		in.prof = povu_hip_call_profile_opts{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
 	in.nested = (tflags & POVU_HIP_T_NESTED) || in.prof.profile != POVU_HIP_PROFILE_RAW_GRAPH;
+	// the spanning alleles are an option of the nested call, no mode of their own: their refusals stand here, not in the table
+	in.spanning = (tflags & POVU_HIP_T_SPANNING) != 0;
+	if (in.spanning)
+		if (const char *why = span_refused(false, in.nested, asked))
+			throw HipError(why);
 	if (cluster && cluster->min_similarity_ppm) {
 		const std::string who = "a clustered call (povu_hip_call_clustered) is refused ";
 		if (cluster->min_similarity_ppm > cluster::PPM)
@@ -927,7 +949,10 @@ void flubble_records(povu_hip_ctx *ctx, const CallInputs &in, const TravDevice &
 		w.v.raw_pos = w.nm.raw_pos;
 	}
 	if (in.nested) {
-		w.nr = nest_records(ctx, w.v, w.nc.ix, in.prof);
+		NestSpan span;
+		if (in.spanning)
+			span = NestSpan{true, w.qidx, w.smin, w.d_slot, in.S, w.rg.pass};
+		w.nr = nest_records(ctx, w.v, w.nc.ix, in.prof, span);
 		w.nfl = w.nr.n_kept;
 		if (w.nfl)
 			HIP_CHECK(copy_async(w.perm, w.nr.kept, (size_t)w.nfl * 4, hipMemcpyDeviceToDevice, s));
@@ -1023,6 +1048,8 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, con
 		take(r1, o.o_q, o.o_path, o.o_first, o.o_ref, o.o_nal, o.o_an, o.o_ns, o.o_block, o.o_nsteps, o.o_pos, o.nalt, r.ac_off, o.o_flags);
 		take(r1, r.o_level, r.o_parent, r.xrow, r.ref_spelled);
 		take(in.cluster_ppm ? r1 : 1, r.rec_clustered, r.cl_minsim);
+		if (in.spanning) // (without the option the arena is laid out as before)
+			take(r1, r.o_star);
 		take(f1, r.xneed, r.xoff, r.xlist);
 		take((size_t)nrec * in.S + 1, o.gt);
 		take(n2, r.need, r.boff, r.blist);
@@ -1038,9 +1065,11 @@ void record_arrays(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, con
 	HIP_CHECK(hipMemsetAsync(r.o_parent, 0xFF, r1 * 4, s));
 	HIP_CHECK(hipMemsetAsync(r.xrow, 0xFF, r1 * 4, s));
 	HIP_CHECK(hipMemsetAsync(r.xneed, 0, f1 * 4, s));
+	if (in.spanning)
+		HIP_CHECK(hipMemsetAsync(r.o_star, 0, r1, s)); // (an inversion record never carries a `*`)
 	if (nfl)
 		KLAUNCH(k_cl_rec_fields, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.v, o, r.need, inv.f_dst, in.nested ? w.nr.level : nullptr,
-			in.nested ? w.nr.parent_q : nullptr, r.o_level, r.o_parent, r.xneed);
+			in.nested ? w.nr.parent_q : nullptr, r.o_level, r.o_parent, r.xneed, w.nr.star, r.o_star);
 	inv_fields(ctx, inv.in, iv, o);
 	if (in.normalized) {
 		// every row as an unchanged record's (the inversion records stay so), then the flubble records' own
@@ -1111,8 +1140,10 @@ void spelling(povu_hip_ctx *ctx, const CallInputs &in, const CallWs &w, const Ca
 	HIP_CHECK(hipMemsetAsync(sp.ac, 0, (r.n_ac + 1) * 4, s));
 	HIP_CHECK(hipMemsetAsync(bad, 0xFF, 8, s));
 	if (nfl) {
-		KLAUNCH(k_cl_records, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.v, w.slots, o, w.qidx, w.smin, w.smax, r.ac_off, w.perm,
-			in.nested ? w.collapsed : nullptr, in.nested ? w.nr.rescued : nullptr, sp.ac, inv.f_dst);
+		auto *records = w.nr.span_bits ? k_cl_records<true> : k_cl_records<false>;
+		KLAUNCH(records, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.v, w.slots, o, w.qidx, w.smin, w.smax, r.ac_off, w.perm,
+			in.nested ? w.collapsed : nullptr, in.nested ? w.nr.rescued : nullptr, sp.ac, inv.f_dst,
+			w.nr.span_bits, w.nr.span_words);
 		KLAUNCH(k_cl_rec_block, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, w.perm, w.v, r.boff, o.o_block, inv.f_dst, r.xoff, r.xrow);
 	}
 	inv_counts(ctx, inv.in, iv, o, r.ac_off, sp.ac);
@@ -1280,6 +1311,11 @@ povu_hip_calls *calls_to_host(povu_hip_ctx *ctx, const CallInputs &in, const Cal
 		v.cluster_ppm = in.cluster_ppm;
 		v.n_cluster_sites = w.cc.n_sites, v.n_clustered_sites = w.n_collapsed, v.n_cluster_vanished = w.n_vanished;
 		v.n_cluster_keys = w.cc.n_keys, v.n_cluster_pairs = w.cc.n_pairs, v.n_cluster_pruned = w.cc.n_pruned, v.n_cluster_tier2 = w.cc.n_tier2;
+	}
+	if (in.spanning) { // (without the flag: the array NULL, the counts 0)
+		give(o->rec_star, v.rec_star, r.o_star, nrec);
+		v.spanning = 1;
+		v.n_star_records = w.nr.n_star_records, v.n_star_entries = w.nr.n_star_entries;
 	}
 	v.device_ms = timer.stop(ctx->stream);
 	for (const auto &fill : defaults)

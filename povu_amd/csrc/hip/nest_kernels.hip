@@ -21,7 +21,11 @@
 //               to every enclosed entry that is a record too (atomic minimum: the shortest encloser, then the lowest site);
 //     level     a lane per record climbs its chain of parents: the top's PVST height - 1 plus the links climbed;
 //     profile   big from the written lengths, reach by climbing while the level is above max_level, the kept records
-//               compacted -- what is dropped here is never spelled.
+//               compacted -- what is dropped here is never spelled;
+//     span      with POVU_HIP_T_SPANNING ("Spanning alleles") a wave per record: the rows of its ancestors' sites in the (site,
+//               slot) table, 64 ancestors a round in the lanes' registers, then the slots 64 a round -- a lane whose slot is
+//               empty at the record's site looks for an ancestor row where it is not; a ballot per slot round is the word of
+//               the record's spanned entries.
 // Work: an entry is visited once per called traversal that encloses (or overlaps) it -- path steps times nesting depth, the
 // bound of the scans themselves.
 #include "nest_kernels.hpp"
@@ -426,7 +430,72 @@ __global__ __launch_bounds__(Q_TPB) void k_ns_profile(uint32_t nfl, uint32_t pro
 	}
 }
 
-NestRecs nest_records(povu_hip_ctx *ctx, const CallView &v, const NestIndex &ix, const povu_hip_call_profile_opts &limits)
+// the spanned entries: a wave per record j.  The chain of parents is walked by the whole wave (every lane reads the same
+// par[]), lane k keeps the table row of ancestor k of the round; a lane climbs nothing on its own.  The first round (the 64
+// nearest ancestors) is walked once and stays in the registers over all slot rounds; a chain longer than that is walked on
+// from ancestor 64 only while some lane of the slot round still looks.  bits[j * W + w]: the ballot of slot round w; star[j];
+// cnt[3] += records with a spanned entry, cnt[4] += spanned entries, both of the records that are written (keep, pass).  The
+// grid is capped (SPAN_BLOCKS): a wave strides over its records and adds what it counted once, so the two counters see
+// thousands of atomics on one address, not two a record
+static constexpr unsigned SPAN_BLOCKS = 4096; // (the device's wave slots at Q_TPB lanes a workgroup, twice over)
+__global__ __launch_bounds__(Q_TPB) void k_ns_span(uint32_t nfl, const uint32_t *__restrict__ rlist, const uint32_t *__restrict__ rq,
+						   const uint32_t *__restrict__ op, const uint32_t *__restrict__ qstatus,
+						   const unsigned long long *__restrict__ par, NestSpan A, uint32_t W, const uint8_t *__restrict__ keep,
+						   unsigned long long *__restrict__ bits, uint8_t *__restrict__ star, unsigned long long *__restrict__ cnt)
+{
+	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64), S = A.S;
+	unsigned long long n_records = 0, n_entries = 0; // of the wave's records that are written: one atomic each at its end
+	for (uint32_t j = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); j < nfl; j += waves) {
+		const uint32_t t = rlist[j], q = rq[t], own = A.slot_of_path[op[t]];
+		const uint64_t base = (uint64_t)A.qidx[q] * S;
+		const uint8_t status = qstatus[q] ? 1 : 0; // (any bit: the search was cut short)
+		uint32_t row0 = 0, n0 = 0, cur = j;
+		for (; n0 < SPAN_ROUND && par[cur] != ~0ull; n0++) {
+			cur = (uint32_t)par[cur];
+			if (lane == n0)
+				row0 = A.qidx[rq[rlist[cur]]];
+		}
+		const uint32_t cur64 = cur;
+		uint32_t n_star = 0;
+		for (uint32_t w = 0; w < W; w++) {
+			const uint32_t sl = w * 64 + lane;
+			const bool need = n0 && sl < S && span_candidate(span_slot_empty(A.smin[base + sl]), status, sl == own);
+			bool hit = false;
+			uint32_t row = row0, n = n0, at = cur64;
+			for (;;) {
+				for (uint32_t k = 0; k < n && __ballot(need && !hit); k++) {
+					const uint32_t r = __shfl(row, (int)k, 64);
+					if (need && !hit)
+						hit = !span_slot_empty(A.smin[(uint64_t)r * S + sl]);
+				}
+				if (n < SPAN_ROUND || !__ballot(need && !hit) || par[at] == ~0ull)
+					break;
+				for (n = 0; n < SPAN_ROUND && par[at] != ~0ull; n++) {
+					at = (uint32_t)par[at];
+					if (lane == n)
+						row = A.qidx[rq[rlist[at]]];
+				}
+			}
+			const unsigned long long mask = __ballot(hit);
+			if (lane == 0)
+				bits[(uint64_t)j * W + w] = mask;
+			n_star += (uint32_t)__popcll(mask);
+		}
+		if (lane == 0) {
+			star[j] = n_star != 0;
+			if (n_star && (!keep || keep[j]) && (!A.pass || A.pass[q])) {
+				n_records++;
+				n_entries += n_star;
+			}
+		}
+	}
+	if (lane == 0 && n_records) {
+		atomicAdd(cnt + 3, n_records);
+		atomicAdd(cnt + 4, n_entries);
+	}
+}
+
+NestRecs nest_records(povu_hip_ctx *ctx, const CallView &v, const NestIndex &ix, const povu_hip_call_profile_opts &limits, const NestSpan &span)
 {
 	hipStream_t s = ctx->stream;
 	const uint32_t nfl = v.nfl;
@@ -438,20 +507,27 @@ NestRecs nest_records(povu_hip_ctx *ctx, const CallView &v, const NestIndex &ix,
 	uint8_t *keep;
 	void *tmp;
 	const size_t tmp_bytes = prim_tmp_bytes(F1, false) + 256;
+	constexpr size_t N_CNT = 6; // enclosed, popped, rescued, records with a `*`, spanned entries; one spare
+	const uint32_t W = span.on ? (span.S + 63) / 64 : 0;
 	carve(ctx->ns_rec, [&](Spans &take) {
 		take(F1, par, o.level, o.parent_q, o.kept, keep, o.rescued);
 		take(R1, rec_of);
-		take(4, cnt);
+		take(N_CNT, cnt);
 		take(2, words);
 		take(tmp_bytes, tmp);
+		if (span.on) { // (without the option the arena is laid out as before)
+			take((size_t)nfl * W + 1, o.span_bits);
+			take(F1, o.star);
+		}
 	});
+	o.span_words = W;
 	o.n_kept = nfl;
 	HIP_CHECK(hipMemsetAsync(o.rescued, 0, F1, s));
 	if (!nfl)
 		return o;
 	HIP_CHECK(hipMemsetAsync(par, 0xFF, F1 * 8, s));
 	HIP_CHECK(hipMemsetAsync(rec_of, 0xFF, R1 * 4, s));
-	HIP_CHECK(hipMemsetAsync(cnt, 0, 32, s));
+	HIP_CHECK(hipMemsetAsync(cnt, 0, N_CNT * 8, s));
 	KLAUNCH(k_ns_rec_of, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, v.rlist, rec_of);
 	KLAUNCH(k_ns_parent, dim3(wave_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, v.rlist, d.rq, d.rpos, d.rlen, ix, rec_of, par);
 	KLAUNCH(k_ns_level, dim3(stride_blocks(nfl)), dim3(Q_TPB), 0, s, nfl, v.rlist, d.rq, v.height, par, o.level, o.parent_q, cnt);
@@ -464,10 +540,13 @@ NestRecs nest_records(povu_hip_ctx *ctx, const CallView &v, const NestIndex &ix,
 	} else {
 		launch_iota(nfl, o.kept, s);
 	}
-	unsigned long long h[4] = {0, 0, 0, 0};
-	HIP_CHECK(copy_async(h, cnt, 32, hipMemcpyDeviceToHost, s));
+	if (span.on) // (after the profile: the counters are those of the kept records)
+		KLAUNCH(k_ns_span, dim3(std::min(wave_blocks(nfl), SPAN_BLOCKS)), dim3(Q_TPB), 0, s, nfl, v.rlist, d.rq, d.op, d.qstatus, par, span, W, filter ? keep : nullptr,
+			o.span_bits, o.star, cnt);
+	unsigned long long h[N_CNT] = {};
+	HIP_CHECK(copy_async(h, cnt, N_CNT * 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
-	o.n_enclosed = h[0], o.n_popped = h[1], o.n_rescued = h[2];
+	o.n_enclosed = h[0], o.n_popped = h[1], o.n_rescued = h[2], o.n_star_records = h[3], o.n_star_entries = h[4];
 	return o;
 }
 

@@ -3,6 +3,7 @@
 // next nested call on the context).
 #pragma once
 #include "call_common.hpp"
+#include "span_rules.hpp"
 
 namespace povu_hip
 {
@@ -58,7 +59,23 @@ struct NestRecs {
 	uint8_t *rescued = nullptr;
 	uint32_t n_kept = 0;
 	uint64_t n_enclosed = 0, n_popped = 0, n_rescued = 0;
+	// with NestSpan::on ("Spanning alleles"), per record j: star[j] = 1 when some entry of the record is spanned, and a word
+	// per 64 slots, span_bits[j * span_words + sl / 64] bit sl % 64 = entry (j, sl) is spanned.  The counters are those of the
+	// records the profile keeps and the regions pass.  Else: null, 0
+	uint8_t *star = nullptr;
+	unsigned long long *span_bits = nullptr;
+	uint32_t span_words = 0;
+	uint64_t n_star_records = 0, n_star_entries = 0;
 };
-NestRecs nest_records(povu_hip_ctx *ctx, const CallView &v, const NestIndex &ix, const povu_hip_call_profile_opts &limits);
+// POVU_HIP_T_SPANNING: what k_ns_span reads beside the records -- the (kept site, slot) table of the call (the minimum allele,
+// SPAN_SLOT_EMPTY where no path of the slot traverses the site), the kept sites' rows, the slots, and the sites the regions
+// pass (null: no regions).  on == false: nothing is launched
+struct NestSpan {
+	bool on = false;
+	const uint32_t *qidx = nullptr, *smin = nullptr, *slot_of_path = nullptr;
+	uint32_t S = 0;
+	const uint8_t *pass = nullptr;
+};
+NestRecs nest_records(povu_hip_ctx *ctx, const CallView &v, const NestIndex &ix, const povu_hip_call_profile_opts &limits, const NestSpan &span = NestSpan{});
 
 } // namespace povu_hip

@@ -21,7 +21,7 @@ namespace povu_hip
 {
 
 static constexpr uint32_t TIER1_STEPS = 64, TIER1_CANDIDATES = 64;
-static constexpr uint8_t AS_NO_AT = 1, AS_BAD_STEP = 2; // state of an allele
+// (the state of an allele is VC_AS_* of vcfcheck_rules.hpp: no walk, a step the graph lacks, a `*` allele; 0: it is searched)
 // counters: [0, POVU_HIP_V_N_STATUS) tasks of every status, then invalid records, misspelled alleles
 static constexpr uint32_t CN_INVALID = POVU_HIP_V_N_STATUS, CN_MISSPELLED = CN_INVALID + 1, CN_WORDS = 8;
 // the kernels that count stride over a grid of at most this many workgroups (the device's wave slots at 256 lanes a workgroup):
@@ -37,7 +37,7 @@ struct VcView {
 	uint32_t nA;			// alleles
 	const uint32_t *soff;		// [nA + 1] steps of an allele
 	const uint32_t *w;		// the walks as path words, NO_QUERY for a step the graph lacks
-	const uint8_t *astate;		// [nA] AS_*
+	const uint8_t *astate;		// [nA] VC_AS_*
 	uint8_t *hit;			// [2][nA][S] the forward plane, then the reverse plane
 	__device__ __forceinline__ uint8_t *hit_of(uint32_t a, bool rev, uint32_t slot) const
 	{
@@ -54,16 +54,13 @@ __global__ void k_vc_resolve(uint32_t n, const uint32_t *__restrict__ sid, const
 	}
 }
 __global__ void k_vc_alleles(uint32_t nA, const uint32_t *__restrict__ soff, const uint32_t *__restrict__ w, const uint8_t *__restrict__ awalk,
-			     uint8_t *__restrict__ astate)
+			     const uint64_t *__restrict__ toff, const char *__restrict__ text, uint8_t *__restrict__ astate)
 {
 	for (uint32_t a = blockIdx.x * Q_TPB + threadIdx.x; a < nA; a += gridDim.x * Q_TPB) {
-		uint8_t st = 0;
-		if (!(awalk[a] & 1u) || soff[a] == soff[a + 1])
-			st = AS_NO_AT;
-		for (uint32_t k = soff[a]; !st && k < soff[a + 1]; k++)
-			if (w[k] == NO_QUERY)
-				st = AS_BAD_STEP;
-		astate[a] = st;
+		bool unknown = false;
+		for (uint32_t k = soff[a]; !unknown && k < soff[a + 1]; k++)
+			unknown = w[k] == NO_QUERY;
+		astate[a] = vc_allele_state(awalk[a] & 2u, text + toff[a], toff[a + 1] - toff[a], awalk[a] & 1u, soff[a + 1] - soff[a], unknown);
 	}
 }
 
@@ -194,13 +191,14 @@ __global__ __launch_bounds__(Q_TPB) void k_vc_tasks(VcTasks K, VcView A, uint32_
 			const uint32_t r = K.t_rec[t], al = K.t_al[t], c = K.t_col[t], j = K.t_phase[t];
 			const uint32_t a = K.aoff[r] + al; // (read only when the record has the allele)
 			const bool has = al < K.aoff[r + 1] - K.aoff[r];
-			const bool no_at = !has || (A.astate[a] & AS_NO_AT), bad = has && (A.astate[a] & AS_BAD_STEP), no_slot = j >= K.col_slots[c];
+			const uint8_t as = has ? A.astate[a] : 0;
+			const bool no_slot = j >= K.col_slots[c];
 			bool fwd = false, rev = false;
-			if (!no_at && !bad && !no_slot) {
+			if (has && !as && !no_slot) {
 				fwd = *A.hit_of(a, false, K.col_first[c] + j);
 				rev = *A.hit_of(a, true, K.col_first[c] + j);
 			}
-			st = vc_status(no_at, bad, no_slot, fwd, rev, forward_only != 0);
+			st = vc_task_status(has, as, no_slot, fwd, rev, forward_only != 0);
 			status[t] = (uint8_t)st;
 		}
 #pragma unroll
@@ -381,7 +379,7 @@ static povu_hip_vcf_report *vcf_check(povu_hip_ctx *ctx, const povu_hip_vcf_doc 
 	if (nS)
 		KLAUNCH(k_vc_resolve, dim3(stride_blocks(nS)), dim3(Q_TPB), 0, s, nS, sid, sor, ctx->g.vid, ctx->g.V, w);
 	if (nA)
-		KLAUNCH(k_vc_alleles, dim3(stride_blocks(nA)), dim3(Q_TPB), 0, s, nA, soff, w, awalk, astate);
+		KLAUNCH(k_vc_alleles, dim3(stride_blocks(nA)), dim3(Q_TPB), 0, s, nA, soff, w, awalk, toff, text, astate);
 	uint32_t n_t2 = 0;
 	if (N && nA && S) {
 		KLAUNCH(k_vc_search, dim3(stride_blocks(2 * (size_t)nA)), dim3(Q_TPB), 0, s, 2 * nA, A, force ? 1u : 0u, forward_only ? 1u : 0u, t2, words + 1);

@@ -61,6 +61,21 @@ VCFCHECK_FN bool vc_occurs_at(const uint32_t *steps, uint64_t g, uint64_t path_e
 	return vc_fits(g, m, path_end) && vc_equal_steps(steps, g, w, m, rev, 0, m);
 }
 
+// ---- the spanning allele `*` (VCF 4.2; INTEGRATION.md "Spanning alleles").  An allele spelled `*` is absent because of an
+// overlapping event: it has no walk of its own, its AT entry is the one character `*` (read as a walk without steps, no bad
+// step), and a genotype entry that names it is not searched and is never a failure
+VCFCHECK_FN bool vc_star_text(const char *s, size_t n) { return n == 1 && s[0] == '*'; }
+// the state of an allele (VC_AS_*; 0: its walk is searched).  `*` comes first: such an allele is not NO_AT for the walk it lacks
+enum { VC_AS_NO_AT = 1, VC_AS_BAD_STEP = 2, VC_AS_STAR = 4 };
+VCFCHECK_FN uint8_t vc_allele_state(bool has_text, const char *text, size_t n_text, bool has_walk, size_t n_steps, bool unknown_step)
+{
+	if (has_text && vc_star_text(text, n_text))
+		return VC_AS_STAR;
+	if (!has_walk || !n_steps)
+		return VC_AS_NO_AT;
+	return unknown_step ? VC_AS_BAD_STEP : 0;
+}
+
 // ---- the status of a task from what was found for its allele in its slot (POVU_HIP_V_* of include/povu_hip.h)
 VCFCHECK_FN uint8_t vc_status(bool no_at, bool bad_step, bool no_slot, bool fwd, bool rev, bool forward_only)
 {
@@ -75,6 +90,14 @@ VCFCHECK_FN uint8_t vc_status(bool no_at, bool bad_step, bool no_slot, bool fwd,
 	if (rev && !forward_only)
 		return 1; // POVU_HIP_V_FOUND_REV
 	return 2;	  // POVU_HIP_V_ABSENT
+}
+// ... from the state of its allele (`has`: the record has the allele at all).  A task of a `*` allele reads found_fwd: there
+// is nothing to find, and no other status is no failure
+VCFCHECK_FN uint8_t vc_task_status(bool has, uint8_t astate, bool no_slot, bool fwd, bool rev, bool forward_only)
+{
+	if (has && (astate & VC_AS_STAR))
+		return 0; // POVU_HIP_V_FOUND_FWD
+	return vc_status(!has || (astate & VC_AS_NO_AT), has && (astate & VC_AS_BAD_STEP), no_slot, fwd, rev, forward_only);
 }
 
 } // namespace povu_hip

@@ -5,6 +5,7 @@
 #include "gfa.hpp"
 
 #include "../hip/call_modes.hpp"
+#include "../hip/span_rules.hpp"
 #include "povu_hip.h"
 
 #include <algorithm>
@@ -33,6 +34,7 @@ struct CallArgs {
 	bool merge = false;	 // --merge-primitives, with --profile decomposed alone (INTEGRATION.md "Merged primitives")
 	bool offref = false;	 // --off-reference: sites no reference path crosses, on a surrogate path (INTEGRATION.md "Off-reference calls")
 	bool untangle = false;	 // --untangle: per-copy genotypes where a path laps a site (INTEGRATION.md "Untangled calls")
+	bool spanning = false;	 // --spanning-alleles: an option of the nested call (INTEGRATION.md "Spanning alleles")
 	std::vector<std::string> regions; // --region <name:start-end>, repeatable (INTEGRATION.md "Region calls")
 	uint32_t cluster_ppm = 0;	  // --cluster <F>: F * 10^6, 0 without the flag (INTEGRATION.md "Clustered calls")
 	povu_hip_call_profile_opts prof{POVU_HIP_PROFILE_RAW_GRAPH, 0, 0, 0};
@@ -42,7 +44,7 @@ struct CallArgs {
 uint32_t call_flags(const CallArgs &c)
 {
 	return (c.inversions ? POVU_HIP_T_INVERSIONS : 0u) | (c.nested ? POVU_HIP_T_NESTED : 0u) | (c.merge ? POVU_HIP_T_MERGE : 0u) |
-	       (c.offref ? POVU_HIP_T_OFFREF : 0u) | (c.untangle ? POVU_HIP_T_UNTANGLE : 0u);
+	       (c.offref ? POVU_HIP_T_OFFREF : 0u) | (c.untangle ? POVU_HIP_T_UNTANGLE : 0u) | (c.spanning ? POVU_HIP_T_SPANNING : 0u);
 }
 
 CallArgs parse_call_args(const std::vector<std::string> &a)
@@ -95,6 +97,8 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 			c.offref = true;
 		} else if (x == "--untangle") {
 			c.untangle = true;
+		} else if (x == "--spanning-alleles") {
+			c.spanning = true;
 		} else if (x == "--profile" || !x.compare(0, 10, "--profile=")) {
 			const std::string v = x == "--profile" ? need(i) : x.substr(10);
 			uint32_t k = 0;
@@ -150,6 +154,13 @@ CallArgs parse_call_args(const std::vector<std::string> &a)
 		throw std::runtime_error(c.cluster_ppm ? "Flag '--cluster' cannot be combined with --gpus" : "Flag could not be matched: " + gpus);
 	if (no)
 		throw std::runtime_error(modes::message(*no, modes::COMMAND_LINE, c.prof.profile));
+	// the spanning alleles are an option of the nested call, no mode of the table: refused without one, and under the profiles
+	// that rewrite alleles
+	if (c.spanning) {
+		const bool nested = c.nested || c.prof.profile == POVU_HIP_PROFILE_TOP_LEVEL_ONLY || c.prof.profile == POVU_HIP_PROFILE_POPPED;
+		if (const char *why = povu_hip::span_refused(true, nested, c.prof.profile))
+			throw std::runtime_error(why);
+	}
 	forms = (int)by_p + (int)!ref_file.empty() + (int)by_pos;
 	if (forms != 1)
 		throw std::runtime_error("call needs exactly one of the reference options: -r <file>, -P <prefix> (repeatable), or "

@@ -3,7 +3,7 @@
 //   povu [--version] [-v <int>] [-t <int>] decompose -i <gfa> [-o <dir>] [-h|--hairpins] [-s|--subflubbles]
 //   povu ... decompose ... --structure-export <json>   (additive: writes the flubble debug sidecar gfa2vcf writes)
 //   povu ... gfa2vcf -i <gfa> [-h] [-s] [--structure-export <json>] <options of `call`>   (app/cli/cli.cpp:154-193)
-//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--profile <p>] [--merge-primitives] [--off-reference] [--untangle] [--region <name:start-end>]... [--cluster <F>]   (the
+//   povu ... call -i <gfa> [-f <dir>] (-r <file> | -P <prefix>... | <prefix>...) [-o <dir> | --stdout] [--inversions] [--nested] [--spanning-alleles] [--profile <p>] [--merge-primitives] [--off-reference] [--untangle] [--region <name:start-end>]... [--cluster <F>]   (the
 //   variant calls of INTEGRATION.md "Variant calls" and "Inversion calls", on the GPU)
 //   povu ... vcf -i <gfa> -c <vcf> --report -o <dir> [--spelling] [--forward-only]   (the --report half of the reference's `vcf`,
 //   app/cli/cli.cpp; INTEGRATION.md "VCF checks", on the GPU)
@@ -71,6 +71,9 @@ static void usage(std::ostream &os)
 	      "                                          steps of a reference path that another path walks backwards [default: false]\n"
 	      "        --nested                          alleles modulo enclosed sites, LV and PS by the nesting of traversals\n"
 	      "                                          (INTEGRATION.md \"Nested calls\") [default: false]\n"
+	      "        --spanning-alleles                nested calls only: a '*' ALT, last, for the haplotypes that cross an enclosing site\n"
+	      "                                          on an allele without this one, instead of '.' (INTEGRATION.md \"Spanning alleles\");\n"
+	      "                                          not with the left-normalized and decomposed profiles [default: false]\n"
 	      "        --profile=[raw-graph|top-level-only|popped|left-normalized]\n"
 	      "                                          which records to keep (top-level-only and popped imply --nested); left-normalized\n"
 	      "                                          keeps all and moves every indel to the left end of its repeat [default: raw-graph]\n"

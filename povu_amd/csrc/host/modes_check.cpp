@@ -4,6 +4,7 @@
 // their own here, which pin the wording.  With `--table` it prints the first refusal of both sides for every request;
 // tests/test_call_modes.py compares that with the recorded answers of tests/golden/call_modes.json.
 #include "../hip/call_modes.hpp"
+#include "../hip/span_rules.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -140,6 +141,21 @@ int main(int argc, char **argv)
 	CHECK(says(md::LIBRARY, C | M, 0, "POVU_HIP_T_MERGE merges the rows of the decomposed profile: refused with profile raw-graph") &&
 	      says(md::COMMAND_LINE, C | M, 0, PINNED[10].cli) && says(md::COMMAND_LINE, C | M, 4, "Flag '--cluster' is called under --profile raw-graph alone, not decomposed"));
 	CHECK(says(md::LIBRARY, C | O | R, 0, PINNED[11].lib) && says(md::COMMAND_LINE, M | O, 0, PINNED[7].cli) && says(md::LIBRARY, M | O, 0, PINNED[1].lib));
+	// the spanning alleles are an option of the nested call and no line of the table (span_rules.hpp): POVU_HIP_T_SPANNING sets
+	// no mode, and its own refusals name the flag on both sides, the rewriting profiles in front of "not nested"
+	CHECK(md::set_of(POVU_HIP_T_SPANNING, false, false) == 0 && md::set_of(POVU_HIP_T_SPANNING | POVU_HIP_T_NESTED, false, false) == N);
+	for (int cli = 0; cli < 2; cli++) {
+		const char *flag = cli ? "'--spanning-alleles'" : "POVU_HIP_T_SPANNING";
+		for (uint32_t p = 0; p < md::N_PROFILES; p++)
+			for (int nested = 0; nested < 2; nested++) {
+				const bool implied = nested || p == POVU_HIP_PROFILE_TOP_LEVEL_ONLY || p == POVU_HIP_PROFILE_POPPED;
+				const char *why = povu_hip::span_refused(cli != 0, implied, p);
+				const bool rewriting = p == POVU_HIP_PROFILE_LEFT_NORMALIZED || p == POVU_HIP_PROFILE_DECOMPOSED;
+				CHECK((why != nullptr) == (rewriting || !implied));
+				CHECK(!why || strstr(why, flag));
+				CHECK(!why || !rewriting || strstr(why, md::PROFILE_NAME[p]));
+			}
+	}
 	if (!table)
 		puts("modes_check: ok");
 	return 0;

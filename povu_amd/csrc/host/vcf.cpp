@@ -337,6 +337,7 @@ struct VcfShape {
 	bool untangled;			       // the arrays of "Untangled calls" (`untangled` speaks for a call without a record)
 	bool clustered;			       // the arrays of "Clustered calls" (one left out: no record says NX or MINSIM)
 	uint64_t cluster_ppm;		       // 0: the text of the call without a threshold
+	bool star;			       // rec_star of "Spanning alleles" (absent: no record has a `*` ALT)
 	uint64_t n;			       // rows of text: merged rows, rows or records
 	uint32_t S, P, n_samples;
 	std::vector<uint32_t> slot_first; // (the slots of a sample are consecutive)
@@ -375,6 +376,7 @@ bool calls_shape(const VcfRequest &rq, VcfShape &sh)
 	if (sh.cluster_ppm > cluster::PPM)
 		return false;
 	sh.clustered = sh.cluster_ppm && c->rec_clustered && c->cl_minsim && c->cl_nx;
+	sh.star = nested_fields && c->rec_star;
 	if (sh.merged && (!c->mrow_member || !c->mrow_gt || !c->mrow_ac || !c->mrow_an || !c->mrow_ns))
 		return false;
 	const uint64_t n_records = c->n_records, n = sh.merged ? c->n_mrows : sh.rows ? c->n_rows : n_records;
@@ -388,6 +390,12 @@ bool calls_shape(const VcfRequest &rq, VcfShape &sh)
 		if (ref_spelled && ref_spelled[i] >= c->n_spelled)
 			return false;
 		if (sh.offref && c->host_query[i] != POVU_HIP_NIL && c->host_query[i] >= sites->n)
+			return false;
+		// a `*` ALT is the last of at least three alleles (REF, an ALT of the site, `*`), has an AC entry and no spelled
+		// allele; never on an inversion record, and no profile rewrites such a record
+		if (sh.star && c->rec_star[i] &&
+		    (subr || c->n_alleles[i] < 3 || c->ref_allele[i] >= c->n_alleles[i] - 1 || c->ac_off[i + 1] - c->ac_off[i] != c->n_alleles[i] - 1 ||
+		     sh.rows || sh.normalized))
 			return false;
 		if (sh.normalized && (c->flags[i] & POVU_HIP_CALL_NORMALIZED) &&
 		    (subr || c->norm_block[i] >= c->n_blocks || c->block_off[c->norm_block[i]] + c->n_alleles[i] > c->n_spelled))
@@ -500,6 +508,7 @@ struct Row {
 	// row of two or more is none even when its representative is one)
 	bool prim;
 	bool subr;
+	bool star; // its last ALT is `*`: no spelled allele, nothing of `seq` / `at` is read for it
 	std::vector<uint64_t> order; // its spelled alleles: REF first, the others in the query's allele order
 	std::string label;	     // its ID: the site, or the ends of an inversion
 };
@@ -514,7 +523,8 @@ bool row_of(const VcfRequest &rq, const VcfShape &sh, const std::vector<char> &k
 	if (!keep[c->path[i]])
 		return false;
 	r.prim = sh.rows && (c->row_kind[r.at] != POVU_HIP_ROW_RAW || r.members > 1);
-	const uint32_t na = c->n_alleles[i], ra = c->ref_allele[i];
+	r.star = sh.star && c->rec_star[i];
+	const uint32_t na = c->n_alleles[i] - (r.star ? 1u : 0u), ra = c->ref_allele[i]; // (the alleles the block spells)
 	const uint64_t b = c->block_off[c->block[i]];
 	r.order.clear();
 	r.order.push_back(sh.ref_spelled ? c->ref_spelled[i] : b + ra);
@@ -684,6 +694,8 @@ void record_row(const VcfRequest &rq, const VcfShape &sh, const Row &r, std::str
 		o += k <= 1 ? '\t' : ',';
 		o.append(c->seq + c->seq_off[sa], c->seq_off[sa + 1] - c->seq_off[sa]);
 	}
+	if (r.star)
+		o += ",*";
 	o += "\t60\tPASS\tAC=";
 	// (a _ROW_RAW row of a merged call: its record has one ALT, the counts and the GT are the merged row's)
 	const uint64_t a0 = c->ac_off[i], a1 = c->ac_off[i + 1];
@@ -703,6 +715,8 @@ void record_row(const VcfRequest &rq, const VcfShape &sh, const Row &r, std::str
 			o += ',';
 		o.append(c->at + c->at_off[order[k]], c->at_off[order[k] + 1] - c->at_off[order[k]]);
 	}
+	if (r.star)
+		o += ",*";
 	o += vartype(f);
 	o += (f & POVU_HIP_CALL_TANGLED) ? ";TANGLED=T" : ";TANGLED=F";
 	if (!subr) {

@@ -109,7 +109,8 @@ void parse_record(const char *text, const Line &ln, size_t n_samples, Chunk &c)
 		}
 	const size_t n_al = std::max(texts.size(), walks.size());
 	for (size_t a = 0; a < n_al; a++) {
-		if (a < walks.size()) {
+		// (the AT entry of a spanning allele is the one character `*`: a walk without steps, no bad step)
+		if (a < walks.size() && !povu_hip::vc_star_text(walks[a].p, walks[a].n)) {
 			size_t i = 0;
 			uint32_t id = 0;
 			uint8_t rev = 0;

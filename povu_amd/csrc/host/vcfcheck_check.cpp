@@ -7,6 +7,11 @@
 //                                    occurrences of its anchor as the device does
 //   vcf <threads> <bytes>            then the bytes of a VCF  -> the document (`S` samples, `R` record, `A` allele, `T` task
 //                                    lines), or `error <message>`
+//   report <paths> <bytes>           then a line `<sample column> <phase> <path words ...>` per path and the bytes of a VCF  -> the
+//                                    report of `povu vcf --report` as the device makes it, over the document's tasks: a line `V
+//                                    <record> ok`, or `V <record> <status> <allele>` of the record's first failing task, the
+//                                    allele states and the task statuses by the rules (a walk's steps are path words as written:
+//                                    <id> << 1 | '<'), searched in the path of the task's (column, phase)
 #include "../../../include/povu_hip.h"
 #include "../hip/vcfcheck_rules.hpp"
 
@@ -82,6 +87,69 @@ static void do_vcf(const std::string &text, uint32_t threads)
 	povu_hip_vcf_doc_free(d);
 }
 
+static const char *const STATUS[] = {"found_fwd", "found_rev", "absent", "no_at", "bad_step", "no_slot"};
+static int do_report(std::istream &in, uint32_t P, size_t bytes)
+{
+	struct Path {
+		uint32_t col, phase;
+		std::vector<uint32_t> steps;
+	};
+	std::vector<Path> paths(P);
+	std::string line;
+	for (Path &p : paths) {
+		std::getline(in, line);
+		std::istringstream ls(line);
+		ls >> p.col >> p.phase;
+		for (uint32_t x; ls >> x;)
+			p.steps.push_back(x);
+	}
+	std::string text(bytes, '\0');
+	in.read(&text[0], (std::streamsize)bytes);
+	if ((size_t)in.gcount() != bytes)
+		return 1;
+	char err[256] = {0};
+	povu_hip_vcf_doc *d = povu_hip_vcf_parse(text.data(), text.size(), 1, err, sizeof err);
+	if (!d) {
+		printf("error %s\n", err);
+		return 0;
+	}
+	for (uint64_t r = 0; r < d->n_records; r++) {
+		bool failed = false;
+		for (uint64_t t = d->task_off[r]; t < d->task_off[r + 1] && !failed; t++) {
+			const uint32_t al = d->task_allele[t], c = d->task_col[t], j = d->task_phase[t];
+			const bool has = al < d->allele_off[r + 1] - d->allele_off[r];
+			const uint64_t a = d->allele_off[r] + al;
+			std::vector<uint32_t> w;
+			uint8_t as = 0;
+			if (has) {
+				for (uint64_t k = d->step_off[a]; k < d->step_off[a + 1]; k++)
+					w.push_back(d->step_id[k] << 1 | d->step_or[k]);
+				as = vc_allele_state(d->allele_walk[a] & 2u, d->text + d->text_off[a], d->text_off[a + 1] - d->text_off[a], d->allele_walk[a] & 1u,
+						     w.size(), false);
+			}
+			bool no_slot = true, fwd = false, rev = false;
+			for (const Path &p : paths) {
+				if (p.col != c || p.phase != j)
+					continue;
+				no_slot = false;
+				for (uint64_t g = 0; has && !as && g < p.steps.size(); g++) {
+					fwd |= vc_occurs_at(p.steps.data(), g, p.steps.size(), w.data(), (uint32_t)w.size(), false);
+					rev |= vc_occurs_at(p.steps.data(), g, p.steps.size(), w.data(), (uint32_t)w.size(), true);
+				}
+			}
+			const uint8_t st = vc_task_status(has, as, no_slot, fwd, rev, false);
+			if (st > 1) {
+				printf("V %llu %s %u\n", (unsigned long long)r, STATUS[st], al);
+				failed = true;
+			}
+		}
+		if (!failed)
+			printf("V %llu ok\n", (unsigned long long)r);
+	}
+	povu_hip_vcf_doc_free(d);
+	return 0;
+}
+
 int main()
 {
 	std::string line;
@@ -109,6 +177,14 @@ int main()
 				return 1;
 			}
 			do_vcf(text, threads);
+		} else if (cmd == "report") {
+			uint32_t P = 0;
+			size_t bytes = 0;
+			ls >> P >> bytes;
+			if (do_report(std::cin, P, bytes)) {
+				fprintf(stderr, "vcfcheck_check: short input\n");
+				return 1;
+			}
 		} else if (!cmd.empty()) {
 			fprintf(stderr, "vcfcheck_check: unknown block %s\n", cmd.c_str());
 			return 1;

@@ -156,6 +156,7 @@ REGION_NO_MASK = 1  # povu_hip_call_regions.flags: scan every site, select the r
 CLUSTER_COUNTERS = ("n_cluster_sites", "n_clustered_sites", "n_cluster_vanished", "n_cluster_keys", "n_cluster_pairs", "n_cluster_pruned",
                     "n_cluster_tier2")  # of Calls
 CLUSTER_NO_BOUND = 1  # povu_hip_call_cluster_opts.flags: no pair of bags is skipped by the weight bound (tests)
+SPAN_COUNTERS = ("n_star_records", "n_star_entries")  # of Calls
 MERGE_COUNTERS = ("n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts")  # of Calls, beside n_mrows
 
 
@@ -206,7 +207,10 @@ class _CallsNested(_Calls):
                 # "Clustered calls"
                 [("cluster_ppm", C.c_uint64), ("rec_clustered", C.POINTER(C.c_uint8)), ("cl_minsim", C.POINTER(C.c_uint32)),
                  ("cl_nx", C.POINTER(C.c_uint32))] +
-                [(k, C.c_uint64) for k in CLUSTER_COUNTERS])
+                [(k, C.c_uint64) for k in CLUSTER_COUNTERS] +
+                # "Spanning alleles"
+                [("spanning", C.c_uint64), ("rec_star", C.POINTER(C.c_uint8))] +
+                [(k, C.c_uint64) for k in SPAN_COUNTERS])
 
 
 class _ClusterOpts(C.Structure):
@@ -280,6 +284,9 @@ T_OFFREF = 16
 # HipDecomposer.call under profile "raw-graph" only, not with T_NESTED, T_MERGE or T_OFFREF: where a path walks a site more than
 # once its laps are aligned with the reference's and every copy is genotyped on its own (INTEGRATION.md "Untangled calls")
 T_UNTANGLE = 32
+# HipDecomposer.call with T_NESTED or a profile that implies it only: a `*` ALT where an enclosing allele deletes the site
+# (INTEGRATION.md "Spanning alleles"; HipDecomposer.call(..., spanning=True) sets it)
+T_SPANNING = 64
 TRAV_LONG, TRAV_STRAY, TRAV_OPEN = 1, 2, 4  # status bits of a query
 PROFILES = {"raw-graph": 0, "top-level-only": 1, "popped": 2, "left-normalized": 3, "decomposed": 4}  # HipDecomposer.call(profile=...)
 PRIM_MAX_LENGTH = 512  # `decomposed` profile: the longest allele that is aligned, and the most max_allele_length may ask for
@@ -1043,6 +1050,12 @@ class Calls:
         self.cl_nx = _view(c.cl_nx, int(self.ac_off[-1]) + n if k else 0, np.uint32)
         for k in CLUSTER_COUNTERS:
             setattr(self, k, int(getattr(c, k)))
+        # "Spanning alleles" (T_SPANNING): per record whether its last ALT is `*` (n_alleles counts it, the spanned entries of
+        # gt carry n_alleles - 1); the records with one and the spanned entries.  Without the flag: empty, 0
+        self.spanning = bool(c.spanning)
+        self.rec_star = _view(c.rec_star, n if self.spanning else 0, np.uint8)
+        for k in SPAN_COUNTERS:
+            setattr(self, k, int(getattr(c, k)))
 
     def nx(self, i):
         """The exact alleles behind every written allele of record i of a clustered call, REF's cluster first."""
@@ -1430,7 +1443,7 @@ class HipDecomposer:
 
     def call(self, forest: Forest, refs, max_steps: int = 65536, flags: int = 0, profile=None, max_level: int = 0,
              max_ref_length: int = 0, max_allele_length: int = 0, regions=None, region_no_mask: bool = False, cluster=None,
-             cluster_no_bound: bool = False) -> Calls:
+             cluster_no_bound: bool = False, spanning: bool = False) -> Calls:
         """The variant calls of `forest` (INTEGRATION.md "Variant calls") with the resident paths whose names start with one
         of the prefixes `refs` as references, on the GPU (paths and sequences uploaded first).  flags: T_FORCE_TIER2,
         T_INVERSIONS (the SUBR records of "Inversion calls" merged in: Calls.n_steps, flags & CALL_SUBR, the n_inv_* counters),
@@ -1455,7 +1468,10 @@ class HipDecomposer:
         as an integer of parts per million; the exact alleles of a site whose bags of inner segments are that similar are one
         allele, written as its first member; Calls.cluster_ppm, rec_clustered, cl_minsim, cl_nx (Calls.nx), the
         CLUSTER_COUNTERS, and vcf_text writes NX and MINSIM.  cluster_no_bound reads every pair of bags, whatever their weights
-        say (tests).  Which of the flags, the profiles, regions and cluster combine is declared once, as RULES of
+        say (tests).  spanning (or T_SPANNING in flags; "Spanning alleles"): an option of the nested call -- an entry whose
+        slot has no traversal of the record's site but traverses the site of an enclosing record is written as a `*` ALT, the
+        record's last, instead of '.'; Calls.spanning, rec_star, the SPAN_COUNTERS; refused without T_NESTED or a profile that
+        implies it, and under "left-normalized" and "decomposed".  Which of the flags, the profiles, regions and cluster combine is declared once, as RULES of
         povu_amd/csrc/hip/call_modes.hpp, with the message a refused combination raises."""
         if profile is not None and profile not in PROFILES:
             raise ValueError(f"profile must be one of {sorted(PROFILES)}")
@@ -1470,7 +1486,7 @@ class HipDecomposer:
             raise RuntimeError(err.value.decode())
         try:
             sites = forest.sites()
-            o = _TravOpts(max_steps, flags)
+            o = _TravOpts(max_steps, flags | (T_SPANNING if spanning else 0))
             po = _ProfileOpts(PROFILES[profile or "raw-graph"], max_level, max_ref_length, max_allele_length)
             rg = self._regions(regions, names, name_array, region_no_mask)
             co = None

@@ -26,7 +26,9 @@ only), offref (T_OFFREF: the sites no reference path crosses too; its time less 
 (T_UNTANGLE: the laps of every haplotype aligned with the reference's; its time less that of plain is the step's) and region
 (asked for by name only: the plain call restricted to the middle 1 % of the first reference path's bases, INTEGRATION.md "Region
 calls"; the sites outside lose their scans) and cluster (the clustered call at T = 900000, INTEGRATION.md "Clustered calls"; its
-time less that of plain is the step's; `alts` counts the ALTs written); without --modes those the input was made for.  One JSON line
+time less that of plain is the step's; `alts` counts the ALTs written) and spanning / popped-spanning (asked for by name only:
+nested and popped with T_SPANNING, INTEGRATION.md "Spanning alleles"; their time less that of nested / popped is the option's);
+without --modes those the input was made for.  One JSON line
 per mode and run: HIP-event time of the call (query upload to the last byte on the host), records, spelled bytes, the
 counters of the mode, and the host time of the VCF writer over these calls on one thread (vcf_ms, with the bytes and the MD5 of
 its text); then per mode a line with the median of the runs behind the warm-up runs.
@@ -49,7 +51,8 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2", "offref", "untangled", "region", "cluster")
+MODES = ("plain", "inversions", "nested", "popped", "normalized", "decomposed", "merged", "decomposed-tier2", "offref", "untangled", "region", "cluster",
+         "spanning", "popped-spanning")
 DEFAULT_MODES = dict(chain=("plain",), inverted=("plain", "inversions"), skip=("plain", "nested", "popped"), tandem=("plain", "normalized"),
                      complex=("plain", "decomposed", "merged"), insertions=("plain", "offref"), looped=("plain", "untangled"), braid=("plain", "cluster"))
 
@@ -145,12 +148,15 @@ def child(a):
               normalized=lambda: dict(profile="left-normalized"), decomposed=lambda: dict(profile="decomposed"),
               merged=lambda: dict(profile="decomposed", flags=H.T_MERGE), offref=lambda: dict(flags=H.T_OFFREF), untangled=lambda: dict(flags=H.T_UNTANGLE),
               region=lambda: dict(regions=[middle_region(g, p, seqs, ref)]), cluster=lambda: dict(cluster=900000),
-              **{"decomposed-tier2": lambda: dict(profile="decomposed", flags=H.T_FORCE_TIER2)})[a.child]()
+              spanning=lambda: dict(flags=H.T_NESTED | H.T_SPANNING),
+              **{"decomposed-tier2": lambda: dict(profile="decomposed", flags=H.T_FORCE_TIER2),
+                 "popped-spanning": lambda: dict(profile="popped", flags=H.T_SPANNING, max_level=0, max_ref_length=a.max_length,
+                                                 max_allele_length=a.max_length)})[a.child]()
     counters = ("n_inv_records", "n_inv_tier2", "n_enclosed", "n_collapsed_sites", "n_popped", "n_rescued", "n_normalized", "max_shift",
                 "n_norm_compared", "n_rows", "n_decomposed_alts", "n_passthrough_alts", "n_prim_tier2", "n_prim_cells", "n_mrows",
                 "n_merged_groups", "n_merged_members", "n_merge_splits", "n_ref_consistent", "n_gt_conflicts", "n_offref_sites", "n_offref_records", "n_offref_hosted",
                 "n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback", "n_regions", "n_region_sites", "n_region_masked",
-                "n_region_dropped") + tuple(getattr(H, "CLUSTER_COUNTERS", ()))
+                "n_region_dropped") + tuple(getattr(H, "CLUSTER_COUNTERS", ())) + tuple(getattr(H, "SPAN_COUNTERS", ()))
     for run in range(a.warmup + a.runs):
         t0 = time.perf_counter()
         c = d.call(f, [ref], **kw)
