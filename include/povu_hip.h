@@ -942,6 +942,98 @@ void povu_hip_vcf_cmp_free(povu_hip_vcf_cmp *c);
 char *povu_hip_vcf_cmp_text(const povu_hip_vcf_cmp *c, const povu_hip_vcf_doc *doc_a, const povu_hip_vcf_doc *doc_b, size_t *compare_len,
 			    char **summary, size_t *summary_len);
 
+/* ---- Haplotype comparison ("Haplotype comparison": this project's own definition): per region, sample and
+ * phase, do documents A and B spell the same bases?  Every (record, ALT) of a placed record becomes an edit (s, e, T) -- the
+ * reference bases [s, e), 0-based and half-open, replaced by T -- by the full suffix-then-prefix trim; the spans of the records
+ * of both documents (widened, with a reference, by the reach of every indel through its repeat) fall into windows; per (window,
+ * common sample, phase) cell the edits either side's GT entries name are applied to the window's text and the two haplotypes
+ * compared byte by byte ---- */
+#define POVU_HIP_H_EDIT 0u	/* state of an item: it has an edit */
+#define POVU_HIP_H_UNSPELLED 1u /* ALT `*`, symbolic or a breakend (the skip rule of the VCF comparison) */
+#define POVU_HIP_H_UNPLACED 2u	/* its record is unplaced */
+/* the status of a cell, the first that applies */
+#define POVU_HIP_H_INCONSISTENT 0u /* a REF field of the window differs from the window's text */
+#define POVU_HIP_H_NOCALL_A 1u	   /* no record of the window on side A has a GT entry for (sample, phase) */
+#define POVU_HIP_H_NOCALL_B 2u
+#define POVU_HIP_H_UNSPELLED_A 3u /* an entry names an unspelled ALT, or one beyond the record's ALTs */
+#define POVU_HIP_H_UNSPELLED_B 4u
+#define POVU_HIP_H_CONFLICT_A 5u /* two applied edits overlap, or two insertions stand at one point */
+#define POVU_HIP_H_CONFLICT_B 6u
+#define POVU_HIP_H_EQUAL_REF 7u /* both haplotypes are the window's text: no edit on either side */
+#define POVU_HIP_H_EQUAL 8u	/* the same bytes */
+#define POVU_HIP_H_DIFFER 9u
+#define POVU_HIP_H_N_STATUS 10u
+#define POVU_HIP_H_MAX_REACH_DEFAULT 256u
+#define POVU_HIP_H_MAX_REACH_MOST 65536u
+typedef struct {
+	uint32_t flags;	    /* POVU_HIP_V_FORCE_TIER2 alone is read */
+	uint32_t max_reach; /* bases an indel's reach may run in either direction, 0 .. POVU_HIP_H_MAX_REACH_MOST */
+} povu_hip_vcf_hap_opts;
+typedef struct {
+	uint64_t n_records_a, n_records_b, n_items_a, n_items_b, n_groups, n_windows, n_cells, n_common_samples;
+	/* per side and record: 1 when placed, its window (POVU_HIP_NIL when unplaced) */
+	const uint8_t *rec_placed_a, *rec_placed_b;
+	const uint32_t *rec_window_a, *rec_window_b;
+	/* per side and item (document order: record, then ALT): the record, the ALT's number (from 1), the state, the edit's s and
+	 * e, the bytes the trims took at the end and at the front, the reach to the left and to the right, the edit group (equal
+	 * edits of either side share one; numbered in the order of their first items, A's first).  An item that is no _H_EDIT has
+	 * 0 everywhere and group POVU_HIP_NIL */
+	const uint32_t *item_record_a, *item_record_b, *item_alt_a, *item_alt_b;
+	const uint8_t *item_state_a, *item_state_b;
+	const int64_t *item_s_a, *item_s_b, *item_e_a, *item_e_b;
+	const uint32_t *item_suffix_a, *item_suffix_b, *item_prefix_a, *item_prefix_b, *item_left_a, *item_left_b, *item_right_a, *item_right_b;
+	const uint32_t *item_group_a, *item_group_b;
+	/* per window, in (CHROM, lo) order: the CHROM (numbered by first appearance in A, then B's new ones), [lo, hi), the records
+	 * of either side, 1 when inconsistent and then the lowest offending record (a record of A, or n_records_a + a record of B;
+	 * else POVU_HIP_NIL) */
+	const uint32_t *win_chrom;
+	const int64_t *win_lo, *win_hi;
+	const uint32_t *win_n_a, *win_n_b;
+	const uint8_t *win_inconsistent;
+	const uint32_t *win_offender;
+	/* per cell, in (window, common sample, phase) order: the status, the distinct edits applied on either side, and for a cell
+	 * that was compared (_EQUAL_REF, _EQUAL, _DIFFER) both haplotype lengths (else 0); for a _DIFFER cell the first differing
+	 * index, the shorter length when one haplotype is a prefix of the other (else all ones) */
+	const uint32_t *cell_window, *cell_sample, *cell_phase;
+	const uint8_t *cell_status;
+	const uint32_t *cell_edits_a, *cell_edits_b;
+	const uint64_t *cell_len_a, *cell_len_b, *cell_first_diff;
+	/* per common sample, in the order of A's columns: its column in A and in B, its cells of every status
+	 * (sample_status[x * POVU_HIP_H_N_STATUS + status]) */
+	const uint32_t *sample_col_a, *sample_col_b;
+	const uint64_t *sample_status;
+	uint64_t n_status[POVU_HIP_H_N_STATUS]; /* cells of every status */
+	uint64_t n_inconsistent;		   /* windows */
+	uint64_t n_unplaced_a, n_unplaced_b;	   /* records */
+	uint64_t n_reach_capped;		   /* edits whose reach the cap stopped */
+	uint64_t n_tier2;			   /* items the wave-per-item kernel trimmed and hashed */
+	uint64_t n_splits;			   /* edit groups the exact comparison split off a run of equal hashes */
+	uint32_t reference;			   /* 1: reference mode */
+	double device_ms;			   /* HIP-event time of the call, first upload to last byte on the host */
+} povu_hip_vcf_hap;
+/* Compares the haplotypes `doc_a` and `doc_b` (both of povu_hip_vcf_parse) spell.  path_name NULL: no reference -- a record is
+ * placed when its REF is neither empty nor `.`, a window's text is taken from the REF fields over it (where several cover a
+ * base, the greatest folded byte; any disagreement makes the window inconsistent) and no graph need be resident.  Else
+ * reference mode: path_name[n_paths] names the resident paths (povu_hip_paths_upload, povu_hip_segments_upload), CHROM names a
+ * path exactly, a record must lie within its path, and every indel reaches through its repeat.  opts NULL: no flag, max_reach
+ * POVU_HIP_H_MAX_REACH_DEFAULT.  Refused: null context or documents, documents whose arrays do not belong together, a POS of
+ * 2^40 or more, 2^32 - 64 or more records, alleles, items, tasks, text bytes or window-text bytes in the two documents together,
+ * reference mode without resident paths and sequences or with another number of path names, max_reach above
+ * POVU_HIP_H_MAX_REACH_MOST, and when device memory runs out.  Free with povu_hip_vcf_hap_free. */
+povu_hip_vcf_hap *povu_hip_vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_doc *doc_a, const povu_hip_vcf_doc *doc_b,
+					  const char *const *path_name, uint32_t n_paths, const povu_hip_vcf_hap_opts *opts, char *err,
+					  size_t errlen);
+void povu_hip_vcf_hap_free(povu_hip_vcf_hap *h);
+/* Both files of `povu vcf --compare --haplotypes` (host only; the result may be hand-made).  haplotypes.tsv: the header
+ * `CHROM START END sample phase status len_a len_b first_diff edits_a edits_b` (tabs; START 1-based, END inclusive), then one
+ * line per cell that is neither _EQUAL_REF nor _EQUAL, in cell order; the lengths and the first difference are `.` but for a
+ * _DIFFER cell.  hap_summary.txt: the windows and the inconsistent ones, the cells of every status, `Concordance`
+ * (EQUAL_REF + EQUAL) / (those + DIFFER) and `Non-reference concordance` EQUAL / (EQUAL + DIFFER) to four decimals (`nan` at a
+ * zero denominator), one line per common sample in A's column order, the unplaced records and the capped reaches when there
+ * are any.  Both malloc'd (povu_hip_buffer_free); NULL when the three do not belong together. */
+char *povu_hip_vcf_hap_text(const povu_hip_vcf_hap *h, const povu_hip_vcf_doc *doc_a, const povu_hip_vcf_doc *doc_b, size_t *haplotypes_len,
+			    char **summary, size_t *summary_len);
+
 /* ---- measurement (bench.py, povu-stage-cost lines) ---- */
 typedef struct {
 	char name[48];	  /* kernel group */

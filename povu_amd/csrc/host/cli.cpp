@@ -9,6 +9,8 @@
 //   app/cli/cli.cpp; INTEGRATION.md "VCF checks", on the GPU)
 //   povu ... vcf -c <vcf> -d <vcf> --compare -o <dir>   (the reference's flag names, a definition of this project's own:
 //   INTEGRATION.md "VCF comparison", on the GPU; -i is accepted and not read)
+//   povu ... vcf -c <vcf> -d <vcf> --compare --haplotypes [-i <gfa>] [--max-reach <n>] -o <dir>   (INTEGRATION.md "Haplotype
+//   comparison", on the GPU: with -i the GFA's paths are the reference, without it the REF fields are)
 #include "decompose.hpp"
 
 #include <cstdlib>
@@ -115,7 +117,12 @@ static void usage(std::ostream &os)
 	      "        --compare                         instead of --report: compare the alleles and genotypes of -c (side A) with those\n"
 	      "                                          of -d (side B) by CHROM, POS, REF and ALT after trimming, and write compare.tsv\n"
 	      "                                          and summary.txt; -i is accepted and not read [default: false]\n"
-	      "        -d[vcf], --other-input-vcf=[vcf]  path to the other VCF [required by --compare]\n";
+	      "        -d[vcf], --other-input-vcf=[vcf]  path to the other VCF [required by --compare]\n"
+	      "        --haplotypes                      with --compare: also compare, per region, sample and phase, the bases the two VCFs\n"
+	      "                                          spell, and write haplotypes.tsv and hap_summary.txt; with -i the GFA's paths are\n"
+	      "                                          the reference, without it the REF fields are [default: false]\n"
+	      "        --max-reach=[n]                   with --haplotypes and -i: bases an indel may reach through its repeat in either\n"
+	      "                                          direction, 0 to 65536 [default: 256]\n";
 }
 
 int main(int argc, char **argv)

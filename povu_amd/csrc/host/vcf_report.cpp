@@ -2,7 +2,9 @@
 // GPU, the VCF parsed and checked against them (povu_hip_vcf_check), report.tsv and summary.txt written.  The reader, the
 // slots and both texts are the library's (host/vcfcheck.cpp); what stays here is the command line and the files.
 // `povu vcf --compare` (INTEGRATION.md "VCF comparison") likewise: two VCFs parsed and compared on a fresh context
-// (povu_hip_vcf_compare), compare.tsv and summary.txt written; the GFA is not read.
+// (povu_hip_vcf_compare), compare.tsv and summary.txt written; the GFA is not read.  With --haplotypes (INTEGRATION.md
+// "Haplotype comparison") the haplotypes the two spell are compared too (povu_hip_vcf_haplotypes) and haplotypes.tsv and
+// hap_summary.txt written beside them: against the paths and sequences of the GFA when -i names one, else by the REF fields.
 #include "decompose.hpp"
 #include "gfa.hpp"
 
@@ -23,7 +25,8 @@ namespace
 {
 struct VcfArgs {
 	std::string vcf, other_vcf, out_dir = ".";
-	bool report = false, compare = false, spelling = false, forward_only = false;
+	bool report = false, compare = false, spelling = false, forward_only = false, haplotypes = false, have_max_reach = false;
+	uint32_t max_reach = POVU_HIP_H_MAX_REACH_DEFAULT;
 };
 
 VcfArgs parse_vcf_args(const std::vector<std::string> &a)
@@ -49,8 +52,19 @@ VcfArgs parse_vcf_args(const std::vector<std::string> &a)
 		const std::string &x = a[i];
 		if (value(i, "-c", "--vcf", c.vcf) || value(i, "-o", "--output-dir", c.out_dir) || value(i, "-d", "--other-input-vcf", c.other_vcf))
 			continue;
+		std::string reach;
+		if (value(i, "--max-reach", "--max-reach", reach)) {
+			char *end = nullptr;
+			const unsigned long long v = strtoull(reach.c_str(), &end, 10);
+			if (reach.empty() || *end || reach[0] == '-' || v > POVU_HIP_H_MAX_REACH_MOST)
+				throw std::runtime_error("Flag '--max-reach' expects a number of bases between 0 and " + std::to_string(POVU_HIP_H_MAX_REACH_MOST));
+			c.max_reach = (uint32_t)v, c.have_max_reach = true;
+			continue;
+		}
 		if (x == "--report")
 			c.report = true;
+		else if (x == "--haplotypes")
+			c.haplotypes = true;
 		else if (x == "--compare")
 			c.compare = true;
 		else if (x == "--spelling")
@@ -62,6 +76,11 @@ VcfArgs parse_vcf_args(const std::vector<std::string> &a)
 		else
 			throw std::runtime_error("Flag could not be matched: " + x);
 	}
+	if ((c.haplotypes || c.have_max_reach) && (c.report || !c.compare))
+		throw std::runtime_error(std::string(c.haplotypes ? "--haplotypes" : "--max-reach") +
+					 (c.report ? " belongs to --compare, not to --report" : " is read by --compare only"));
+	if (c.have_max_reach && !c.haplotypes)
+		throw std::runtime_error("--max-reach is read by --haplotypes only");
 	if (c.report && c.compare)
 		throw std::runtime_error("--compare and --report exclude each other");
 	if (!c.other_vcf.empty() && !c.compare)
@@ -87,6 +106,44 @@ std::string read_vcf(const std::string &path)
 	return buf.str();
 }
 
+// The haplotypes of both documents compared on `ctx`: with a GFA (-i) its graph, paths and sequences go to the context first and
+// the paths are the reference, else the REF fields are
+povu_hip_vcf_hap *compare_haplotypes(const Config &cfg, const VcfArgs &va, povu_hip_ctx *ctx, const povu_hip_vcf_doc *a, const povu_hip_vcf_doc *b)
+{
+	char err[512] = {0};
+	const povu_hip_vcf_hap_opts opts{0u, va.max_reach};
+	povu_hip_vcf_hap *hap = nullptr;
+	if (cfg.input_gfa.empty()) {
+		hap = povu_hip_vcf_haplotypes(ctx, a, b, nullptr, 0, &opts, err, sizeof err);
+	} else {
+		GfaGraph g = load_gfa(cfg.input_gfa, true, true, std::max(1, cfg.threads));
+		const uint32_t V = (uint32_t)g.vid.size(), P = (uint32_t)g.paths.size();
+		std::vector<const char *> names(P);
+		for (uint32_t k = 0; k < P; k++)
+			names[k] = g.paths[k].name.c_str();
+		if (povu_hip_graph_upload(ctx, V, g.vid.data(), (uint32_t)g.v1.size(), g.v1.data(), g.s1.data(), g.v2.data(), g.s2.data(), nullptr, err,
+					  sizeof err) != 0)
+			throw std::runtime_error(std::string("povu_hip: ") + err);
+		const FlatPaths fp = flatten_paths(g.paths);
+		if (povu_hip_paths_upload(ctx, P, fp.off.data(), fp.ids.data(), fp.rev.data(), err, sizeof err) != 0)
+			throw std::runtime_error(std::string("paths: ") + err);
+		std::vector<uint64_t> seq_off((size_t)V + 1, 0);
+		std::string seq;
+		for (uint32_t v = 0; v < V; v++) {
+			if (g.seq[v] == "*")
+				throw std::runtime_error("sequences: segment " + std::to_string(g.vid[v]) + " has no sequence ('*'): a reference needs every sequence");
+			seq_off[v + 1] = seq_off[v] + g.seq[v].size();
+			seq += g.seq[v];
+		}
+		if (povu_hip_segments_upload(ctx, V, seq_off.data(), seq.data(), err, sizeof err) != 0)
+			throw std::runtime_error(std::string("sequences: ") + err);
+		hap = povu_hip_vcf_haplotypes(ctx, a, b, names.data(), P, &opts, err, sizeof err);
+	}
+	if (!hap)
+		throw std::runtime_error(std::string("vcf: ") + err);
+	return hap;
+}
+
 void do_compare(const Config &cfg, const VcfArgs &va)
 {
 	char err[512] = {0};
@@ -94,7 +151,8 @@ void do_compare(const Config &cfg, const VcfArgs &va)
 	povu_hip_vcf_doc *doc[2] = {nullptr, nullptr};
 	povu_hip_ctx *ctx = nullptr;
 	povu_hip_vcf_cmp *cmp = nullptr;
-	char *table = nullptr, *summary = nullptr;
+	povu_hip_vcf_hap *hap = nullptr;
+	char *table = nullptr, *summary = nullptr, *hap_table = nullptr, *hap_summary = nullptr;
 	std::string bad;
 	for (int k = 0; k < 2 && bad.empty(); k++) {
 		const std::string &path = k ? va.other_vcf : va.vcf;
@@ -123,6 +181,27 @@ void do_compare(const Config &cfg, const VcfArgs &va)
 		if (!t || !s)
 			bad = "cannot write compare.tsv and summary.txt to " + va.out_dir;
 	}
+	if (bad.empty() && va.haplotypes) {
+		try {
+			hap = compare_haplotypes(cfg, va, ctx, doc[0], doc[1]);
+		} catch (const std::runtime_error &e) {
+			bad = e.what();
+		}
+		size_t hlen = 0, hslen = 0;
+		if (bad.empty() && !(hap_table = povu_hip_vcf_hap_text(hap, doc[0], doc[1], &hlen, &hap_summary, &hslen)))
+			bad = "cannot format the haplotype comparison";
+		if (bad.empty()) {
+			std::ofstream t(va.out_dir + "/haplotypes.tsv", std::ios::binary), s(va.out_dir + "/hap_summary.txt", std::ios::binary);
+			t.write(hap_table, (std::streamsize)hlen);
+			s.write(hap_summary, (std::streamsize)hslen);
+			if (!t || !s)
+				bad = "cannot write haplotypes.tsv and hap_summary.txt to " + va.out_dir;
+		}
+	}
+	povu_hip_buffer_free(hap_table);
+	povu_hip_buffer_free(hap_summary);
+	if (hap)
+		povu_hip_vcf_hap_free(hap);
 	povu_hip_buffer_free(table);
 	povu_hip_buffer_free(summary);
 	if (cmp)

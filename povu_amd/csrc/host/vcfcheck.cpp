@@ -533,3 +533,65 @@ try {
 } catch (const std::bad_alloc &) {
 	return nullptr;
 }
+
+// ---- the two files of `povu vcf --compare --haplotypes` (INTEGRATION.md "Haplotype comparison")
+
+extern "C" char *povu_hip_vcf_hap_text(const povu_hip_vcf_hap *h, const povu_hip_vcf_doc *doc_a, const povu_hip_vcf_doc *doc_b, size_t *haplotypes_len,
+				       char **summary, size_t *summary_len)
+try {
+	static const char *NAME[POVU_HIP_H_N_STATUS] = {"inconsistent", "nocall_a", "nocall_b", "unspelled_a", "unspelled_b",
+							"conflict_a",	"conflict_b", "equal_ref", "equal",	  "differ"};
+	if (!h || !doc_a || !doc_b || !summary)
+		return nullptr;
+	// the CHROM strings as the comparison numbers them: A's in order of first appearance, then B's new ones
+	std::vector<std::string> chrom;
+	for (const povu_hip_vcf_doc *d : {doc_a, doc_b})
+		for (uint64_t k = 0; k < d->n_chroms; k++)
+			if (d->chrom[k] && std::find(chrom.begin(), chrom.end(), d->chrom[k]) == chrom.end())
+				chrom.push_back(d->chrom[k]);
+	std::string out = "CHROM\tSTART\tEND\tsample\tphase\tstatus\tlen_a\tlen_b\tfirst_diff\tedits_a\tedits_b\n";
+	for (uint64_t c = 0; c < h->n_cells; c++) {
+		const uint32_t st = h->cell_status[c], w = h->cell_window[c], x = h->cell_sample[c];
+		if (st >= POVU_HIP_H_N_STATUS || w >= h->n_windows || x >= h->n_common_samples || h->win_chrom[w] >= chrom.size() ||
+		    h->sample_col_a[x] >= doc_a->n_samples)
+			return nullptr;
+		if (st == POVU_HIP_H_EQUAL_REF || st == POVU_HIP_H_EQUAL)
+			continue;
+		const bool compared = st == POVU_HIP_H_DIFFER;
+		out += chrom[h->win_chrom[w]] + "\t" + std::to_string(h->win_lo[w] + 1) + "\t" + std::to_string(h->win_hi[w]) + "\t" +
+		       doc_a->sample[h->sample_col_a[x]] + "\t" + std::to_string(h->cell_phase[c]) + "\t" + NAME[st] + "\t";
+		out += (compared ? std::to_string(h->cell_len_a[c]) : std::string(".")) + "\t" + (compared ? std::to_string(h->cell_len_b[c]) : std::string(".")) +
+		       "\t" + (compared ? std::to_string(h->cell_first_diff[c]) : std::string(".")) + "\t";
+		out += std::to_string(h->cell_edits_a[c]) + "\t" + std::to_string(h->cell_edits_b[c]) + "\n";
+	}
+	auto counts = [&](const uint64_t *n) {
+		std::string s;
+		for (uint32_t k = 0; k < POVU_HIP_H_N_STATUS; k++)
+			s += std::string(k ? ", " : "") + NAME[k] + " " + std::to_string(n[k]);
+		return s;
+	};
+	const uint64_t *n = h->n_status;
+	const uint64_t same = n[POVU_HIP_H_EQUAL_REF] + n[POVU_HIP_H_EQUAL];
+	std::string sum = "Windows: " + std::to_string(h->n_windows) + ", inconsistent " + std::to_string(h->n_inconsistent) + "\n";
+	sum += "Cells: " + counts(n) + "\n";
+	sum += "Concordance: " + ratio(same, same + n[POVU_HIP_H_DIFFER]) + "\n";
+	sum += "Non-reference concordance: " + ratio(n[POVU_HIP_H_EQUAL], n[POVU_HIP_H_EQUAL] + n[POVU_HIP_H_DIFFER]) + "\n";
+	for (uint64_t x = 0; x < h->n_common_samples; x++) {
+		if (h->sample_col_a[x] >= doc_a->n_samples)
+			return nullptr;
+		sum += std::string("Sample ") + doc_a->sample[h->sample_col_a[x]] + ": " + counts(h->sample_status + x * POVU_HIP_H_N_STATUS) + "\n";
+	}
+	if (h->n_unplaced_a || h->n_unplaced_b)
+		sum += "Unplaced records: A " + std::to_string(h->n_unplaced_a) + ", B " + std::to_string(h->n_unplaced_b) + "\n";
+	if (h->n_reach_capped)
+		sum += "Capped reaches: " + std::to_string(h->n_reach_capped) + "\n";
+	*summary = to_buffer(sum, summary_len);
+	char *rep = *summary ? to_buffer(out, haplotypes_len) : nullptr;
+	if (!rep) {
+		free(*summary);
+		*summary = nullptr;
+	}
+	return rep;
+} catch (const std::bad_alloc &) {
+	return nullptr;
+}

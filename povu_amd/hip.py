@@ -149,6 +149,40 @@ class _VcfCmp(C.Structure):
                 [(k, C.c_uint64) for k in VCF_CMP_COUNTERS] + [("device_ms", C.c_double)])
 
 
+# the counters of povu_hip_vcf_hap behind its arrays (HapComparison carries them under these names)
+VCF_HAP_COUNTERS = ("n_inconsistent", "n_unplaced_a", "n_unplaced_b", "n_reach_capped", "n_tier2", "n_splits")
+_HAP_ITEM_ARRAYS = (("item_record", C.c_uint32), ("item_alt", C.c_uint32), ("item_state", C.c_uint8), ("item_s", C.c_int64), ("item_e", C.c_int64),
+                    ("item_suffix", C.c_uint32), ("item_prefix", C.c_uint32), ("item_left", C.c_uint32), ("item_right", C.c_uint32),
+                    ("item_group", C.c_uint32))
+_HAP_WIN_ARRAYS = (("win_chrom", C.c_uint32), ("win_lo", C.c_int64), ("win_hi", C.c_int64), ("win_n_a", C.c_uint32), ("win_n_b", C.c_uint32),
+                   ("win_inconsistent", C.c_uint8), ("win_offender", C.c_uint32))
+_HAP_CELL_ARRAYS = (("cell_window", C.c_uint32), ("cell_sample", C.c_uint32), ("cell_phase", C.c_uint32), ("cell_status", C.c_uint8),
+                    ("cell_edits_a", C.c_uint32), ("cell_edits_b", C.c_uint32), ("cell_len_a", C.c_uint64), ("cell_len_b", C.c_uint64),
+                    ("cell_first_diff", C.c_uint64))
+
+
+class _VcfHapOpts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("max_reach", C.c_uint32)]
+
+
+class _VcfHap(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("n_records_a", "n_records_b", "n_items_a", "n_items_b", "n_groups", "n_windows", "n_cells",
+                                           "n_common_samples")] +
+                [(k, C.POINTER(C.c_uint8)) for k in ("rec_placed_a", "rec_placed_b")] +
+                [(k, C.POINTER(C.c_uint32)) for k in ("rec_window_a", "rec_window_b")] +
+                [(f"{k}_{side}", C.POINTER(t)) for k, t in _HAP_ITEM_ARRAYS[:2] for side in "ab"] +
+                [(f"{k}_{side}", C.POINTER(t)) for k, t in _HAP_ITEM_ARRAYS[2:3] for side in "ab"] +
+                [(f"{k}_{side}", C.POINTER(t)) for k, t in _HAP_ITEM_ARRAYS[3:5] for side in "ab"] +
+                [(f"{k}_{side}", C.POINTER(t)) for k, t in _HAP_ITEM_ARRAYS[5:9] for side in "ab"] +
+                [(f"{k}_{side}", C.POINTER(t)) for k, t in _HAP_ITEM_ARRAYS[9:] for side in "ab"] +
+                [(k, C.POINTER(t)) for k, t in (_HAP_WIN_ARRAYS[0], _HAP_WIN_ARRAYS[1], _HAP_WIN_ARRAYS[2], _HAP_WIN_ARRAYS[3], _HAP_WIN_ARRAYS[4],
+                                               _HAP_WIN_ARRAYS[5], _HAP_WIN_ARRAYS[6])] +
+                [(k, C.POINTER(t)) for k, t in _HAP_CELL_ARRAYS] +
+                [("sample_col_a", C.POINTER(C.c_uint32)), ("sample_col_b", C.POINTER(C.c_uint32)), ("sample_status", C.POINTER(C.c_uint64)),
+                 ("n_status", C.c_uint64 * 10)] + [(k, C.c_uint64) for k in VCF_HAP_COUNTERS] +
+                [("reference", C.c_uint32), ("device_ms", C.c_double)])
+
+
 OFFREF_COUNTERS = ("n_offref_sites", "n_offref_records", "n_offref_hosted")  # of Calls
 UNTANGLE_COUNTERS = ("n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback")  # of Calls
 REGION_COUNTERS = ("n_regions", "n_region_sites", "n_region_masked", "n_region_dropped")  # of Calls
@@ -303,6 +337,11 @@ V_FORWARD_ONLY, V_SPELLING, V_FORCE_TIER2 = 1, 2, 4
 # "VCF comparison" (HipDecomposer.compare_vcfs): the state of an item, the class of a group
 M_KEYED, M_SKIPPED = 0, 1
 M_SHARED, M_ONLY_A, M_ONLY_B = 0, 1, 2
+# "Haplotype comparison" (HipDecomposer.compare_haplotypes): the state of an item, the status of a cell
+H_EDIT, H_UNSPELLED, H_UNPLACED = 0, 1, 2
+(H_INCONSISTENT, H_NOCALL_A, H_NOCALL_B, H_UNSPELLED_A, H_UNSPELLED_B, H_CONFLICT_A, H_CONFLICT_B, H_EQUAL_REF, H_EQUAL, H_DIFFER) = range(10)
+H_STATUS_NAMES = ("inconsistent", "nocall_a", "nocall_b", "unspelled_a", "unspelled_b", "conflict_a", "conflict_b", "equal_ref", "equal", "differ")
+H_MAX_REACH_DEFAULT, H_MAX_REACH_MOST = 256, 65536
 
 _lib = None
 
@@ -416,6 +455,13 @@ def load_lib():
     l.povu_hip_vcf_cmp_text.argtypes = [C.POINTER(_VcfCmp), C.POINTER(_VcfDoc), C.POINTER(_VcfDoc), C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     l.povu_hip_vcf_cmp_text.restype = C.c_void_p
+    l.povu_hip_vcf_haplotypes.argtypes = [C.c_void_p, C.POINTER(_VcfDoc), C.POINTER(_VcfDoc), C.POINTER(C.c_char_p), C.c_uint32,
+                                          C.POINTER(_VcfHapOpts), C.c_char_p, C.c_size_t]
+    l.povu_hip_vcf_haplotypes.restype = C.POINTER(_VcfHap)
+    l.povu_hip_vcf_hap_free.argtypes = [C.POINTER(_VcfHap)]
+    l.povu_hip_vcf_hap_text.argtypes = [C.POINTER(_VcfHap), C.POINTER(_VcfDoc), C.POINTER(_VcfDoc), C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    l.povu_hip_vcf_hap_text.restype = C.c_void_p
     l.povu_hip_forest_pvst_text.restype = C.c_void_p
     l.povu_hip_forest_pvst_text.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]
     l.povu_hip_buffer_free.argtypes = [C.c_void_p]
@@ -1245,6 +1291,62 @@ class VcfComparison:
         return self._texts()[1]
 
 
+class HapComparison:
+    """What HipDecomposer.compare_haplotypes found (povu_hip_vcf_hap): numpy views, valid as long as this object lives.  Per side
+    (`_a`, `_b`) and record: rec_placed, rec_window (0xFFFFFFFF when unplaced).  Per side and item, in document order:
+    item_record, item_alt (from 1), item_state (H_EDIT, H_UNSPELLED, H_UNPLACED), item_s / item_e (0-based, half-open),
+    item_suffix / item_prefix (the bytes the trims took), item_left / item_right (the reaches), item_group.  Per window:
+    win_chrom (an index into `chroms`), win_lo / win_hi, win_n_a / win_n_b, win_inconsistent, win_offender.  Per cell, in
+    (window, sample, phase) order: cell_window, cell_sample, cell_phase, cell_status (H_INCONSISTENT .. H_DIFFER),
+    cell_edits_a / _b, cell_len_a / _b, cell_first_diff.  Per common sample: sample_col_a / sample_col_b and sample_status
+    ([n_common_samples, 10]).  n_status (per status), the counters VCF_HAP_COUNTERS, reference, device_ms.  `doc_a` and `doc_b`
+    are the parsed VCFs."""
+
+    def __init__(self, lib, ptr, doc_a: VcfDoc, doc_b: VcfDoc):
+        self._lib, self._p, self.doc_a, self.doc_b = lib, ptr, doc_a, doc_b
+        h = ptr.contents
+        for k in ("n_records_a", "n_records_b", "n_items_a", "n_items_b", "n_groups", "n_windows", "n_cells", "n_common_samples") + VCF_HAP_COUNTERS:
+            setattr(self, k, int(getattr(h, k)))
+        for side, nr, ni in (("a", self.n_records_a, self.n_items_a), ("b", self.n_records_b, self.n_items_b)):
+            setattr(self, f"rec_placed_{side}", _view(getattr(h, f"rec_placed_{side}"), nr, np.uint8))
+            setattr(self, f"rec_window_{side}", _view(getattr(h, f"rec_window_{side}"), nr, np.uint32))
+            for k, t in _HAP_ITEM_ARRAYS:
+                setattr(self, f"{k}_{side}", _view(getattr(h, f"{k}_{side}"), ni, np.dtype(t)))
+        for k, t in _HAP_WIN_ARRAYS:
+            setattr(self, k, _view(getattr(h, k), self.n_windows, np.dtype(t)))
+        for k, t in _HAP_CELL_ARRAYS:
+            setattr(self, k, _view(getattr(h, k), self.n_cells, np.dtype(t)))
+        for k in ("sample_col_a", "sample_col_b"):
+            setattr(self, k, _view(getattr(h, k), self.n_common_samples, np.uint32))
+        self.sample_status = _view(h.sample_status, self.n_common_samples * 10, np.uint64).reshape(self.n_common_samples, 10)
+        self.n_status = [int(x) for x in h.n_status]
+        self.reference, self.device_ms = bool(h.reference), float(h.device_ms)
+        self.chroms = list(doc_a.chroms) + [c for c in doc_b.chroms if c not in doc_a.chroms]
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            self._lib.povu_hip_vcf_hap_free(self._p)
+            self._p = None
+
+    def _texts(self):
+        ln, sl, sp = C.c_size_t(0), C.c_size_t(0), C.c_void_p(None)
+        p = self._lib.povu_hip_vcf_hap_text(self._p, self.doc_a._p, self.doc_b._p, C.byref(ln), C.byref(sp), C.byref(sl))
+        if not p:
+            raise RuntimeError("the haplotype comparison and the documents do not belong together")
+        out = C.string_at(p, ln.value).decode(), C.string_at(sp.value, sl.value).decode()
+        self._lib.povu_hip_buffer_free(p)
+        self._lib.povu_hip_buffer_free(sp)
+        return out
+
+    def haplotypes_text(self) -> str:
+        """haplotypes.tsv of `povu vcf --compare --haplotypes`: a line per cell that is neither equal_ref nor equal."""
+        return self._texts()[0]
+
+    def summary_text(self) -> str:
+        """hap_summary.txt: the windows, the cells of every status, both concordances, a line per common sample."""
+        return self._texts()[1]
+
+
 class HipDecomposer:
     """One context = one GPU, one stream, one workspace arena."""
 
@@ -1567,6 +1669,29 @@ class HipDecomposer:
         if not p:
             raise RuntimeError(err.value.decode())
         return VcfComparison(self._lib, p, doc_a, doc_b)
+
+    def compare_haplotypes(self, a, b, reference: bool = False, max_reach: int = H_MAX_REACH_DEFAULT, force_tier2: bool = False,
+                           threads: int = 1) -> HapComparison:
+        """Per region, sample and phase: do VCF `a` and VCF `b` (text or a VcfDoc of parse_vcf each) spell the same bases
+        (INTEGRATION.md "Haplotype comparison")?  Every (record, ALT) becomes an edit by the full suffix-then-prefix trim, the
+        records of both fall into windows, and per (window, common sample, phase) the edits either side's GT entries name are
+        applied to the window's text and the haplotypes compared.  reference: the resident paths and sequences are the reference
+        (CHROM names a path; every indel reaches up to max_reach bases through its repeat), else the REF fields are and no graph
+        is needed.  force_tier2: every item through the wave-per-item kernel (tests)."""
+        doc_a = a if isinstance(a, VcfDoc) else parse_vcf(a, threads)
+        doc_b = b if isinstance(b, VcfDoc) else parse_vcf(b, threads)
+        if not 0 <= int(max_reach) < 2 ** 32:
+            raise ValueError("max_reach must be in [0, 2^32)")
+        err = C.create_string_buffer(512)
+        o = _VcfHapOpts(V_FORCE_TIER2 if force_tier2 else 0, int(max_reach))
+        names, name_array = [], None
+        if reference:
+            names = getattr(self, "_path_names", [])
+            name_array = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        p = self._lib.povu_hip_vcf_haplotypes(self._ctx, doc_a._p, doc_b._p, name_array, len(names), C.byref(o), err, 512)
+        if not p:
+            raise RuntimeError(err.value.decode())
+        return HapComparison(self._lib, p, doc_a, doc_b)
 
     def traversals(self, forest: Forest, max_steps: int = 65536, flags: int = 0) -> Traversals:
         """The traversals of every flubble of `forest` by the resident paths, on the GPU."""
