@@ -1,6 +1,8 @@
-// exact_groups.hpp -- grouping items of a query by exact equality behind a hash, the one copy that the alleles of the
-// traversals (trav_kernels.hip: items = traversals, equal = the same step sequence) and the classes of the nested calls
-// (nest_kernels.hip: items = exact alleles, equal = the same skeleton) share.
+// exact_groups.hpp -- grouping items of a query by exact equality behind a hash, and numbering the groups: the one copy that
+// the alleles of the traversals (trav_kernels.hip: items = traversals, equal = the same step sequence), the classes of the
+// nested calls (nest_kernels.hip: exact alleles, the same skeleton), the merged primitives (merge_kernels.hip: rows, the same
+// written texts), the VCF comparison (vcfcmp_kernels.hip: (record, ALT) items, the same trimmed key) and the haplotype
+// comparison (vcfhap_kernels.hip: items, the same edit) share.
 //
 // The items are stably sorted by (query, length, hash); every member of a run is compared with the run's first member by the
 // caller's `same(a, b)`, and a run with a mismatch (a hash collision) is grouped exactly by one lane.  rep[k] of sorted
@@ -108,12 +110,23 @@ __global__ void k_eg_regroup(uint32_t nb, const uint32_t *__restrict__ bad_heads
 	atomicAdd(splits, (unsigned long long)n_new);
 }
 
-// first[t] = 1 when item t is the first of its group (its representative)
-static __global__ void k_eg_first(uint32_t R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, uint32_t *__restrict__ first)
+// first[t] = 1 when item t is the first of its group (its representative) and kept (keep: null, or a byte per item -- an item
+// with a 0 there is the first of no group)
+static __global__ void k_eg_first(uint32_t R, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, const uint8_t *__restrict__ keep,
+				  uint32_t *__restrict__ first)
 {
 	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < R; k += gridDim.x * Q_TPB)
-		if (rep[k] == k)
+		if (rep[k] == k && (!keep || keep[perm[k]]))
 			first[perm[k]] = 1;
+}
+// group number of every item, from its group's first member (gidx: number_groups); NO_QUERY for an item that is not kept
+[[maybe_unused]] static __global__ void k_eg_group_of(uint32_t n, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, const uint32_t *__restrict__ gidx,
+				     const uint8_t *__restrict__ keep, uint32_t *__restrict__ gid)
+{
+	for (uint64_t k = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; k < n; k += (uint64_t)gridDim.x * Q_TPB) {
+		const uint32_t r = rep[k], i = perm[k];
+		gid[i] = keep && !keep[i] ? NO_QUERY : gidx[perm[r < n ? r : k]];
+	}
 }
 
 // the arrays of a grouping, R + 1 entries each (rbad: bytes); tmp: prim_tmp_bytes(R + 1, true)
@@ -154,6 +167,17 @@ const uint32_t *group_exact(uint32_t R, const uint32_t *rq, const uint32_t *rlen
 		HIP_CHECK(copy_async(h_splits, splits, 8, hipMemcpyDeviceToHost, s));
 	}
 	return sp;
+}
+
+// Numbers the groups of group_exact's order `sp` and w.rep in the order of their first items: gidx[i] = the kept groups whose
+// first item is below i, so gidx[first item] is a group's number and gidx[n] their count (on the device: the caller reads it
+// back).  firstf, gidx: n + 1 entries; tmp: prim_tmp_bytes(n + 1, false)
+inline void number_groups(uint32_t n, const uint32_t *sp, const uint32_t *rep, uint32_t *firstf, uint32_t *gidx, const uint8_t *keep, void *tmp,
+			  size_t tmp_bytes, hipStream_t s)
+{
+	HIP_CHECK(hipMemsetAsync(firstf, 0, ((size_t)n + 1) * 4, s));
+	KLAUNCH(k_eg_first, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, sp, rep, keep, firstf);
+	scan_exclusive_u32(firstf, gidx, (size_t)n + 1, tmp, tmp_bytes, s);
 }
 
 } // namespace povu_hip

@@ -119,16 +119,6 @@ struct SameRow {
 	}
 };
 
-// group number of every row, from its group's first member
-__global__ void k_mg_group_of(uint32_t n, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, const uint32_t *__restrict__ gidx,
-			      uint32_t *__restrict__ gid)
-{
-	for (uint64_t k = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; k < n; k += (uint64_t)gridDim.x * Q_TPB) {
-		const uint32_t r = rep[k];
-		gid[perm[k]] = gidx[perm[r < n ? r : k]];
-	}
-}
-
 __global__ void k_mg_group_key(uint32_t n, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ gid, uint32_t *__restrict__ key)
 {
 	for (uint64_t x = (uint64_t)blockIdx.x * Q_TPB + threadIdx.x; x < n; x += (uint64_t)gridDim.x * Q_TPB)
@@ -251,11 +241,9 @@ MergedRows merge_rows(povu_hip_ctx *ctx, const PrimIn &in, const PrimRows &rows)
 		KLAUNCH(k_mg_keys, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, T, flag, run_before, hash_mask_hi(hbits), hash_mask_lo(hbits), rq, rlen, rhash);
 		// ---- groups (a run number is below n)
 		const uint32_t *sp = group_exact(n, rq, rlen, rhash, hbits, 2 * LEN_BITS, bits_for(n), SameRow{T}, gw, count, splits, &out.n_splits, s);
-		HIP_CHECK(hipMemsetAsync(firstf, 0, n1 * 4, s));
-		KLAUNCH(k_eg_first, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, sp, gw.rep, firstf);
-		scan_exclusive_u32(firstf, gidx, n1, gw.tmp, gw.tmp_bytes, s);
+		number_groups(n, sp, gw.rep, firstf, gidx, nullptr, gw.tmp, gw.tmp_bytes, s);
 		out.n_mrows = read_back(gidx + n, s); // (waits for the stream: n_splits has arrived)
-		KLAUNCH(k_mg_group_of, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, sp, gw.rep, gidx, gid);
+		KLAUNCH(k_eg_group_of, dim3(stride_blocks(n)), dim3(Q_TPB), 0, s, n, sp, gw.rep, gidx, nullptr, gid);
 	}
 	const uint64_t nm = out.n_mrows;
 	refuse_2_32(nm * S, "the merged primitives need ", "(group, slot) entries");

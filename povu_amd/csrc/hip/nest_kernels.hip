@@ -326,9 +326,7 @@ NestClasses nest_classes(povu_hip_ctx *ctx, const TravDevice &d, const uint8_t *
 	GroupWs gw{ga, gb, gkey, gkout, mark, hmax, head, rep, blist, rbad, tmp, tmp_bytes};
 	const uint32_t *sp = group_exact(n_al, aq, slen, shash, hbits, bits_for(max_steps), bits_for(n), SameSkeleton{ctx->path_steps, d.rpos, d.rlen, d.afirst, d.soff, cand, cov},
 					 gw, words + 2, tot, &c.n_splits, s);
-	HIP_CHECK(hipMemsetAsync(firstf, 0, A1 * 4, s));
-	KLAUNCH(k_eg_first, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, sp, rep, firstf);
-	scan_exclusive_u32(firstf, cidx, A1, tmp, tmp_bytes, s);
+	number_groups(n_al, sp, rep, firstf, cidx, nullptr, tmp, tmp_bytes, s);
 	c.n_cl = read_back(cidx + n_al, s);
 	KLAUNCH(k_ns_class_of, dim3(stride_blocks(n_al)), dim3(Q_TPB), 0, s, n_al, sp, rep, cidx, d.afirst, cglob, c.crep, c.cfirst);
 	KLAUNCH(k_ns_class_off, dim3(stride_blocks(n1)), dim3(Q_TPB), 0, s, n, d.aoff, cidx, c.coff);

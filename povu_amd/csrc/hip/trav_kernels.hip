@@ -645,11 +645,8 @@ static void alleles(const TravParams &p, const TravBoundary &b, const TravTasks 
 {
 	hipStream_t s = p.s;
 	const uint32_t n = b.q.n, R = t.R;
-	const size_t R1 = (size_t)R + 1;
 	if (R) {
-		HIP_CHECK(hipMemsetAsync(g.firstf, 0, R1 * 4, s));
-		KLAUNCH(k_eg_first, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, g.sp, g.rep, g.firstf);
-		scan_exclusive_u32(g.firstf, g.aidx, R1, g.tmp, g.tmp_bytes, s);
+		number_groups(R, g.sp, g.rep, g.firstf, g.aidx, nullptr, g.tmp, g.tmp_bytes, s);
 		HIP_CHECK(copy_async(&g.n_al, g.aidx + R, 4, hipMemcpyDeviceToHost, s));
 		KLAUNCH(k_tr_allele, dim3(stride_blocks(R)), dim3(Q_TPB), 0, s, R, g.sp, g.rep, g.aidx, g.rlen, g.rallele, g.afirst, g.alen);
 		HIP_CHECK(hipStreamSynchronize(s));

@@ -1,26 +1,20 @@
 // vcfcmp_kernels.hip -- povu_hip_vcf_compare (include/povu_hip.h): how do the calls of one parsed VCF differ from another's?
 //
 // The definition is INTEGRATION.md "VCF comparison" (restated in tests/vcfcmp_ref.py; the rules that are plain arithmetic are
-// vcfcmp_rules.hpp).  It reads no graph, no paths and no sequences.  Both documents are uploaded as one: A's records, alleles,
-// texts and tasks, then B's, the CHROM strings interned over both.
-//   items    one per (record, ALT): the host sums the ALT counts to offsets, a lane per item finds its record in them;
-//   keys     the skip rule, the two trims and the hash of the trimmed key.  A lane per item while the shorter text has at most
-//            TIER1_BYTES bytes, else a wave per item: 64 bytes a ballot backwards, then forwards, the hash a sum of per-lane
-//            partial polynomials (the same value whichever kernel computes it);
-//   groups   exact_groups.hpp over (CHROM id, |REF'| + |ALT'|, hash), the comparison the rules' key equality; the groups
-//            numbered by a scan over their first items, the member list the items stably sorted by that number;
+// vcfcmp_rules.hpp).  It reads no graph, no paths and no sequences.  Both documents are uploaded as one (vcf_pair.hpp: the
+// host builder, the view, the items).
+//   keys     the skip rule, the two trims and the hash of the trimmed key: the two tiers of vcf_pair.hpp over KeyPolicy, which
+//            trims to vm_trim_limit, hashes REF' and ALT' and writes a key or a skipped item;
+//   groups   exact_groups.hpp over (CHROM id, |REF'| + |ALT'|, hash), the comparison the rules' key equality; the groups of the
+//            keyed items numbered in first-item order (number_groups), the member list the items stably sorted by that number;
 //   classes  a lane per group: members of either side (A's items come first in a group's stretch), the class, the first item;
 //   doses    a wave per group, lanes across the common samples in batches of 64: the members in rounds of 64 (a lane finds the
 //            tasks of its member's ALT by two bisections), the tasks of a member in rounds of 64, a lane counting those of its
 //            column; per-sample counts stay in the lane over all groups of the wave and are added once per wave and batch.
 // Every shuffle and ballot runs with all 64 lanes (trip counts around them are wave-uniform); every store is inside the range
 // the host carved: items below nI, groups below nG <= nI, samples below nC.
-#include "call_common.hpp"
 #include "exact_groups.hpp"
-#include "vcfcmp_rules.hpp"
-
-#include <string>
-#include <unordered_map>
+#include "vcf_pair.hpp"
 
 namespace povu_hip
 {
@@ -28,33 +22,11 @@ namespace povu_hip
 namespace
 {
 
-constexpr uint32_t TIER1_BYTES = 32;
-constexpr unsigned COUNT_BLOCKS = 2048; // (the device's wave slots at 256 lanes a workgroup: what the counting kernels stride over)
 enum { CN_SHARED = 0, CN_ONLY_A, CN_ONLY_B, CN_SKIPPED_A, CN_SKIPPED_B, CN_WORDS = 8 };
 
-// both documents as one, and the items
-struct VmView {
-	uint32_t nI, nIa, nRa;	 // items, those of A, records of A
-	const uint32_t *aoff;	 // [records + 1] alleles of a record
-	const uint64_t *toff;	 // [alleles + 1]
-	const char *text;
-	const uint64_t *pos;	 // [records]
-	const uint32_t *chrom;	 // [records] CHROM id over both documents
-	uint32_t *it_rec, *it_k; // [nI] the record within its document, the ALT
-	struct Texts {
-		const char *ref, *alt;
-		uint64_t nr, na;
-	};
-	__device__ __forceinline__ uint32_t record_of(uint32_t i) const { return it_rec[i] + (i >= nIa ? nRa : 0u); }
-	__device__ __forceinline__ Texts texts(uint32_t i) const
-	{
-		const uint32_t ar = aoff[record_of(i)], aa = ar + it_k[i];
-		return {text + toff[ar], text + toff[aa], toff[ar + 1] - toff[ar], toff[aa + 1] - toff[aa]};
-	}
-};
 // what the keys kernels write per item
 struct VmKeys {
-	uint8_t *state;
+	uint8_t *state, *keep; // (keep: 1 for a keyed item, which the group numbering counts)
 	uint64_t *pos;
 	uint32_t *suffix, *prefix;
 	uint32_t *rq, *rlen; // the grouping's query (CHROM id; n_chroms for a skipped item) and length
@@ -63,106 +35,40 @@ struct VmKeys {
 	uint32_t n_chroms;
 };
 
-__global__ void k_vm_items(VmView A, uint32_t nR, const uint32_t *__restrict__ ioff)
-{
-	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < A.nI; i += gridDim.x * Q_TPB) {
-		uint32_t lo = 0, hi = nR; // the last record whose items begin at or before i (ioff[0] = 0, nI > 0 hence nR > 0)
-		while (hi - lo > 1) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (ioff[mid] <= i)
-				lo = mid;
-			else
-				hi = mid;
-		}
-		A.it_rec[i] = lo - (lo >= A.nRa ? A.nRa : 0u);
-		A.it_k[i] = i - ioff[lo] + 1;
-	}
-}
-
 __device__ __forceinline__ void write_skipped(const VmKeys &O, uint32_t i)
 {
-	O.state[i] = POVU_HIP_M_SKIPPED;
+	O.state[i] = POVU_HIP_M_SKIPPED, O.keep[i] = 0;
 	O.pos[i] = 0, O.suffix[i] = 0, O.prefix[i] = 0;
 	O.rq[i] = O.n_chroms, O.rlen[i] = 0, O.rhash[i] = vm_mix64(i) & O.mask; // (equal to no item: SameKey)
 }
-__device__ __forceinline__ void write_key(const VmKeys &O, const VmView &A, uint32_t i, const VmView::Texts &T, uint64_t s, uint64_t p,
+__device__ __forceinline__ void write_key(const VmKeys &O, const PairView &A, uint32_t i, const PairView::Texts &T, uint64_t s, uint64_t p,
 					  uint64_t ref_hash, uint64_t alt_hash)
 {
 	const uint32_t r = A.record_of(i);
 	const uint64_t pos = A.pos[r] + p, nr = T.nr - s - p, na = T.na - s - p;
-	O.state[i] = POVU_HIP_M_KEYED;
+	O.state[i] = POVU_HIP_M_KEYED, O.keep[i] = 1;
 	O.pos[i] = pos, O.suffix[i] = (uint32_t)s, O.prefix[i] = (uint32_t)p;
 	O.rq[i] = A.chrom[r], O.rlen[i] = (uint32_t)(nr + na), O.rhash[i] = vm_key_hash(pos, nr, na, ref_hash, alt_hash) & O.mask;
 }
 
-// tier 1: a lane per item; the items whose shorter text is long (or every item, with force) go to `t2`
-__global__ void k_vm_keys(VmView A, VmKeys O, uint32_t force, uint32_t *__restrict__ t2, uint32_t *__restrict__ n_t2)
-{
-	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < A.nI; i += gridDim.x * Q_TPB) {
-		const VmView::Texts T = A.texts(i);
-		if (force || min(T.nr, T.na) > TIER1_BYTES) {
-			t2[atomicAdd(n_t2, 1u)] = i; // (at most nI of them)
-			continue;
-		}
-		if (vm_skipped(T.ref, T.nr, T.alt, T.na)) {
-			write_skipped(O, i);
-			continue;
-		}
-		const uint64_t s = vm_suffix(T.ref, T.nr, T.alt, T.na), p = vm_prefix(T.ref, T.nr, T.alt, T.na, s);
-		write_key(O, A, i, T, s, p, vm_text_hash(T.ref + p, T.nr - s - p), vm_text_hash(T.alt + p, T.na - s - p));
+// the keys as a policy of the two tiers (vcf_pair.hpp): no item is settled before its texts are looked at
+struct KeyPolicy {
+	VmKeys O;
+	static constexpr bool HASH_REF = true;
+	static __device__ __forceinline__ uint64_t trim_limit(uint64_t nr, uint64_t na) { return vm_trim_limit(nr, na); }
+	__device__ __forceinline__ bool refused(const PairView &, uint32_t) const { return false; }
+	__device__ __forceinline__ void on_refused(uint32_t) const {}
+	__device__ __forceinline__ void on_skipped(uint32_t i) const { write_skipped(O, i); }
+	__device__ __forceinline__ void on_trimmed(const PairView &A, uint32_t i, const PairView::Texts &T, uint64_t s, uint64_t p, uint64_t ref_hash,
+					      uint64_t alt_hash) const
+	{
+		write_key(O, A, i, T, s, p, ref_hash, alt_hash);
 	}
-}
-
-// the polynomial hash of t[0, n), lanes across the bytes
-__device__ __forceinline__ uint64_t wave_text_hash(const char *__restrict__ t, uint64_t n, uint32_t lane)
-{
-	uint64_t h = 0, power = vm_pow(lane);
-	const uint64_t stride = vm_pow(64);
-	for (uint64_t x = lane; x < n; x += 64, power *= stride)
-		h += vm_term(t[x], power);
-	return wave_sum(h);
-}
-// tier 2: a wave per item of `t2`
-__global__ __launch_bounds__(Q_TPB) void k_vm_keys_wave(const uint32_t *__restrict__ t2, uint32_t n2, VmView A, VmKeys O)
-{
-	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
-	for (uint32_t x = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); x < n2; x += waves) {
-		const uint32_t i = t2[x];
-		const VmView::Texts T = A.texts(i);
-		bool skip = vm_skip_head(T.ref, T.nr, T.alt, T.na);
-		for (uint64_t c0 = 0; !skip && c0 < T.na; c0 += 64)
-			skip = __ballot(c0 + lane < T.na && vm_skip_byte(T.alt[c0 + lane])) != 0;
-		if (skip) {
-			if (lane == 0)
-				write_skipped(O, i);
-			continue;
-		}
-		uint64_t limit = vm_trim_limit(T.nr, T.na), s = limit;
-		for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-			const unsigned long long m = __ballot(c0 + lane < limit && vm_suffix_differs(T.ref, T.nr, T.alt, T.na, c0 + lane));
-			if (m) {
-				s = c0 + (uint64_t)(__ffsll((long long)m) - 1);
-				break;
-			}
-		}
-		limit = vm_trim_limit(T.nr - s, T.na - s);
-		uint64_t p = limit;
-		for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-			const unsigned long long m = __ballot(c0 + lane < limit && vm_prefix_differs(T.ref, T.alt, c0 + lane));
-			if (m) {
-				p = c0 + (uint64_t)(__ffsll((long long)m) - 1);
-				break;
-			}
-		}
-		const uint64_t hr = wave_text_hash(T.ref + p, T.nr - s - p, lane), ha = wave_text_hash(T.alt + p, T.na - s - p, lane);
-		if (lane == 0)
-			write_key(O, A, i, T, s, p, hr, ha);
-	}
-}
+};
 
 // items a and b of one CHROM have the same key
 struct SameKey {
-	VmView A;
+	PairView A;
 	const uint8_t *state;
 	const uint64_t *pos;
 	const uint32_t *suffix, *prefix;
@@ -170,28 +76,12 @@ struct SameKey {
 	{
 		if (state[a] != POVU_HIP_M_KEYED || state[b] != POVU_HIP_M_KEYED)
 			return false;
-		const VmView::Texts Ta = A.texts(a), Tb = A.texts(b);
+		const PairView::Texts Ta = A.texts(a), Tb = A.texts(b);
 		const uint64_t pa = prefix[a], pb = prefix[b], ca = pa + suffix[a], cb = pb + suffix[b];
 		return vm_same_key(pos[a], Ta.ref + pa, Ta.nr - ca, Ta.alt + pa, Ta.na - ca, pos[b], Tb.ref + pb, Tb.nr - cb, Tb.alt + pb, Tb.na - cb);
 	}
 };
 
-// a skipped item is the first of no group
-__global__ void k_vm_keyed_firsts(uint32_t n, const uint8_t *__restrict__ state, uint32_t *__restrict__ firstf)
-{
-	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < n; i += gridDim.x * Q_TPB)
-		if (state[i] != POVU_HIP_M_KEYED)
-			firstf[i] = 0;
-}
-// group number of every item, from its group's first member
-__global__ void k_vm_group_of(uint32_t n, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, const uint32_t *__restrict__ gidx,
-			      const uint8_t *__restrict__ state, uint32_t *__restrict__ gid)
-{
-	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < n; k += gridDim.x * Q_TPB) {
-		const uint32_t r = rep[k], i = perm[k];
-		gid[i] = state[i] != POVU_HIP_M_KEYED ? NO_QUERY : gidx[perm[r < n ? r : k]];
-	}
-}
 // (the skipped items sort behind every group)
 __global__ void k_vm_group_key(uint32_t n, uint32_t nG, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ gid, uint32_t *__restrict__ key)
 {
@@ -285,7 +175,7 @@ __device__ __forceinline__ uint32_t first_task_of(const uint32_t *__restrict__ t
 	}
 	return lo;
 }
-__global__ __launch_bounds__(Q_TPB) void k_vm_doses(VmView A, VmDoses D)
+__global__ __launch_bounds__(Q_TPB) void k_vm_doses(PairView A, VmDoses D)
 {
 	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64), wave = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6);
 	for (uint32_t c0 = 0; c0 < D.nC; c0 += 64) {
@@ -335,133 +225,30 @@ __global__ __launch_bounds__(Q_TPB) void k_vm_doses(VmView A, VmDoses D)
 
 struct CmpOwner {
 	povu_hip_vcf_cmp view{}; // first member: the owner is recovered from it in povu_hip_vcf_cmp_free
-	PinnedVec<uint32_t> it_rec, it_k, suffix, prefix, gid, g_na, g_nb, g_first;
-	PinnedVec<uint8_t> state, g_class;
-	PinnedVec<uint64_t> pos;
-	PinnedVec<unsigned long long> tp, fp, fn, gteq;
+	PinnedVec<uint8_t> block; // every array of the view that came from the device, in one page-locked block (HostSpans)
 	std::vector<uint32_t> col_a, col_b;
 };
-
-// what the kernels index by must lie within what they index (all true of povu_hip_vcf_parse)
-void check_cmp_doc(const povu_hip_vcf_doc *d, const char *which)
-{
-	auto ascends = [](const uint64_t *off, uint64_t n, uint64_t total) {
-		if (!off || off[0] != 0 || off[n] != total)
-			return false;
-		for (uint64_t k = 0; k < n; k++)
-			if (off[k] > off[k + 1])
-				return false;
-		return true;
-	};
-	bool ok = ascends(d->allele_off, d->n_records, d->n_alleles) && ascends(d->task_off, d->n_records, d->n_tasks) &&
-		  ascends(d->text_off, d->n_alleles, d->n_text_bytes) && (!d->n_records || (d->rec_chrom && d->chrom && d->rec_pos)) &&
-		  (!d->n_alleles || d->allele_walk) && (!d->n_text_bytes || d->text) && (!d->n_samples || d->sample) &&
-		  (!d->n_tasks || (d->task_record && d->task_allele && d->task_col));
-	for (uint64_t c = 0; ok && c < d->n_samples; c++)
-		ok = d->sample[c] != nullptr;
-	for (uint64_t r = 0; ok && r < d->n_records; r++) {
-		ok = d->rec_chrom[r] < d->n_chroms && d->chrom[d->rec_chrom[r]];
-		for (uint64_t t = d->task_off[r]; ok && t < d->task_off[r + 1]; t++)
-			ok = d->task_record[t] == r && d->task_col[t] < d->n_samples && (t == d->task_off[r] || d->task_allele[t - 1] <= d->task_allele[t]);
-	}
-	if (!ok)
-		throw HipError(std::string("the offsets, tasks and CHROM ids of document ") + which + " do not belong together");
-}
-// the ALTs of record r: its alleles with a text, REF first, but REF
-uint64_t alts_of(const povu_hip_vcf_doc *d, uint64_t r)
-{
-	uint64_t n = 0;
-	for (uint64_t a = d->allele_off[r]; a < d->allele_off[r + 1] && (d->allele_walk[a] & 2u); a++)
-		n++;
-	return n ? n - 1 : 0;
-}
 
 } // namespace
 
 static povu_hip_vcf_cmp *vcf_compare(povu_hip_ctx *ctx, const povu_hip_vcf_doc *da, const povu_hip_vcf_doc *db, uint32_t flags, CallTimer &timer)
 {
-	if (!ctx || !da || !db)
-		throw HipError("null context or document");
+	PairWant want{};
+	want.tkoff = want.t_al = want.t_col = true;
+	PairUpload U = pair_build(ctx, da, db, "the VCF comparison needs ", want);
 	const bool force = flags & POVU_HIP_V_FORCE_TIER2;
-	const povu_hip_vcf_doc *docs[2] = {da, db};
-	const char *who = "the VCF comparison needs ";
-	for (const povu_hip_vcf_doc *d : docs) { // (a side first: the sums below do not wrap)
-		refuse_2_32(d->n_records + 64, who, "records of a document");
-		refuse_2_32(d->n_alleles + 64, who, "alleles of a document");
-		refuse_2_32(d->n_tasks + 64, who, "tasks of a document");
-		refuse_2_32(d->n_text_bytes + 64, who, "text bytes of a document");
-		refuse_2_32(d->n_samples + 64, who, "sample columns of a document");
-	}
-	refuse_2_32(da->n_records + db->n_records + 64, who, "records");
-	refuse_2_32(da->n_alleles + db->n_alleles + 64, who, "alleles");
-	refuse_2_32(da->n_tasks + db->n_tasks + 64, who, "tasks");
-	refuse_2_32(da->n_text_bytes + db->n_text_bytes + 64, who, "text bytes");
-	check_cmp_doc(da, "A");
-	check_cmp_doc(db, "B");
-	const uint32_t nRa = (uint32_t)da->n_records, nR = nRa + (uint32_t)db->n_records, nAl = (uint32_t)(da->n_alleles + db->n_alleles);
-	const uint32_t nT = (uint32_t)(da->n_tasks + db->n_tasks), hbits = hash_bits_hook();
-	const uint64_t n_text = da->n_text_bytes + db->n_text_bytes;
-
-	// ---- both documents as one; the items' offsets; the CHROM ids; the common samples
-	std::vector<uint32_t> h_aoff((size_t)nR + 1), h_tkoff((size_t)nR + 1), h_ioff((size_t)nR + 1), h_chrom(nR), h_tal(nT), h_tcol(nT);
-	std::vector<uint64_t> h_toff((size_t)nAl + 1), h_pos(nR);
-	std::unordered_map<std::string, uint32_t> chrom_of;
-	uint64_t n_items = 0, n_items_a = 0, longest = 0;
-	{
-		uint64_t r0 = 0, a0 = 0, t0 = 0, x0 = 0;
-		for (int side = 0; side < 2; side++) { // (by side, not by pointer: a document may be compared with itself)
-			const povu_hip_vcf_doc *d = docs[side];
-			std::vector<uint32_t> id(d->n_chroms);
-			for (uint64_t k = 0; k < d->n_chroms; k++)
-				id[k] = d->chrom[k] ? chrom_of.emplace(d->chrom[k], (uint32_t)chrom_of.size()).first->second : 0u;
-			for (uint64_t r = 0; r < d->n_records; r++) {
-				h_aoff[r0 + r] = (uint32_t)(a0 + d->allele_off[r]);
-				h_tkoff[r0 + r] = (uint32_t)(t0 + d->task_off[r]);
-				h_ioff[r0 + r] = (uint32_t)std::min<uint64_t>(n_items, 0xFFFFFFFFull);
-				h_pos[r0 + r] = d->rec_pos[r];
-				h_chrom[r0 + r] = id[d->rec_chrom[r]];
-				const uint64_t alts = alts_of(d, r), ar = d->allele_off[r];
-				n_items += alts;
-				for (uint64_t k = 0; k <= alts && ar + k < d->allele_off[r + 1]; k++)
-					longest = std::max(longest, d->text_off[ar + k + 1] - d->text_off[ar + k]);
-			}
-			for (uint64_t a = 0; a < d->n_alleles; a++)
-				h_toff[a0 + a] = x0 + d->text_off[a];
-			for (uint64_t t = 0; t < d->n_tasks; t++)
-				h_tal[t0 + t] = d->task_allele[t], h_tcol[t0 + t] = d->task_col[t];
-			r0 += d->n_records, a0 += d->n_alleles, t0 += d->n_tasks, x0 += d->n_text_bytes;
-			if (side == 0)
-				n_items_a = n_items;
-		}
-		h_aoff[nR] = nAl, h_tkoff[nR] = nT, h_toff[nAl] = n_text;
-	}
-	refuse_2_32(n_items + 64, who, "(record, ALT) items");
-	h_ioff[nR] = (uint32_t)n_items;
-	const uint32_t nI = (uint32_t)n_items, nIa = (uint32_t)n_items_a, n_chroms = (uint32_t)chrom_of.size();
-	auto o = std::make_unique<CmpOwner>();
-	{
-		std::unordered_map<std::string, uint32_t> col_of_b; // (of several columns of one name the first counts)
-		for (uint64_t c = 0; c < db->n_samples; c++)
-			col_of_b.emplace(db->sample[c], (uint32_t)c);
-		for (uint64_t c = 0; c < da->n_samples; c++) {
-			const auto at = col_of_b.find(da->sample[c]);
-			if (at == col_of_b.end())
-				continue;
-			o->col_a.push_back((uint32_t)c), o->col_b.push_back(at->second);
-			col_of_b.erase(at);
-		}
-	}
-	const uint32_t nC = (uint32_t)o->col_a.size();
+	const uint32_t nRa = U.nRa, nR = U.nR, nAl = U.nAl, nT = U.nT, nI = U.nI, nIa = U.nIa, nC = U.nC, n_chroms = U.n_chroms, hbits = hash_bits_hook();
 	const size_t i1 = (size_t)nI + 1;
+	auto o = std::make_unique<CmpOwner>();
 
 	HIP_CHECK(hipSetDevice(ctx->device));
 	ctx->wait_tail();
-	hipStream_t s = ctx->stream;
+	hipStream_t s = U.s = ctx->stream;
 	// ---- the layout: what is uploaded and worked on (vc_ws), the results (vc_hit)
 	uint32_t *aoff, *tkoff, *ioff, *chrom, *t_al, *t_col, *col_a, *col_b, *it_rec, *it_k, *suffix, *prefix, *rq, *rlen, *t2, *firstf, *gidx, *gid, *member,
 		*goff, *words, *g_na, *g_nb, *g_first;
 	uint64_t *toff, *pos, *kpos, *rhash;
-	uint8_t *state, *g_class;
+	uint8_t *state, *keep, *g_class;
 	char *text;
 	unsigned long long *cnt, *splits, *tp, *fp, *fn, *gteq;
 	GroupWs gw;
@@ -470,13 +257,13 @@ static povu_hip_vcf_cmp *vcf_compare(povu_hip_ctx *ctx, const povu_hip_vcf_doc *
 	carve(ctx->vc_ws, [&](Spans &take) {
 		take((size_t)nR + 1, aoff, tkoff, ioff, chrom, pos);
 		take((size_t)nAl + 1, toff);
-		take(n_text + 1, text);
+		take(U.n_text + 1, text);
 		take((size_t)nT + 1, t_al, t_col);
 		take((size_t)nC + 1, col_a, col_b);
 		take(i1, rq, rlen, t2, firstf, gw.pa, gw.pb, gw.key, gw.kout, gw.mark, gw.hmax, gw.head, gw.rep, gw.blist, member);
 		take(i1 + 1, gidx, goff);
 		take(i1, rhash);
-		take(i1, gw.rbad);
+		take(i1, gw.rbad, keep);
 		take(8, words);
 		take(CN_WORDS, cnt);
 		take(1, splits);
@@ -488,47 +275,27 @@ static povu_hip_vcf_cmp *vcf_compare(povu_hip_ctx *ctx, const povu_hip_vcf_doc *
 		take(i1, state, g_class);
 		take((size_t)nC + 1, tp, fp, fn, gteq);
 	});
-	auto up = [&](void *dst, const void *src, size_t bytes) {
-		if (bytes)
-			HIP_CHECK(copy_async(dst, src, bytes, hipMemcpyHostToDevice, s));
-	};
-	up(aoff, h_aoff.data(), ((size_t)nR + 1) * 4);
-	up(tkoff, h_tkoff.data(), ((size_t)nR + 1) * 4);
-	up(ioff, h_ioff.data(), ((size_t)nR + 1) * 4);
-	up(chrom, h_chrom.data(), (size_t)nR * 4);
-	up(pos, h_pos.data(), (size_t)nR * 8);
-	up(toff, h_toff.data(), ((size_t)nAl + 1) * 8);
-	up(text, da->text, da->n_text_bytes);
-	up(text + da->n_text_bytes, db->text, db->n_text_bytes);
-	up(t_al, h_tal.data(), (size_t)nT * 4);
-	up(t_col, h_tcol.data(), (size_t)nT * 4);
-	up(col_a, o->col_a.data(), (size_t)nC * 4);
-	up(col_b, o->col_b.data(), (size_t)nC * 4);
+	U.up(aoff, U.aoff), U.up(tkoff, U.tkoff), U.up(ioff, U.ioff), U.up(chrom, U.chrom), U.up(pos, U.pos), U.up(toff, U.toff);
+	U.up_text(text);
+	U.up(t_al, U.t_al), U.up(t_col, U.t_col), U.up(col_a, U.col_a), U.up(col_b, U.col_b);
 	HIP_CHECK(hipMemsetAsync(words, 0, 32, s));
 	HIP_CHECK(hipMemsetAsync(cnt, 0, CN_WORDS * 8, s));
 	for (unsigned long long *p : {tp, fp, fn, gteq})
 		HIP_CHECK(hipMemsetAsync(p, 0, ((size_t)nC + 1) * 8, s));
 
 	// ---- items, keys
-	const VmView A{nI, nIa, nRa, aoff, toff, text, pos, chrom, it_rec, it_k};
-	const VmKeys K{state, kpos, suffix, prefix, rq, rlen, rhash, ((uint64_t)hash_mask_hi(hbits) << 32) | hash_mask_lo(hbits), n_chroms};
+	const PairView A{nR, nRa, nI, nIa, aoff, ioff, toff, text, pos, chrom, it_rec, it_k};
+	const KeyPolicy K{{state, keep, kpos, suffix, prefix, rq, rlen, rhash, ((uint64_t)hash_mask_hi(hbits) << 32) | hash_mask_lo(hbits), n_chroms}};
 	uint32_t n_t2 = 0, nG = 0;
 	uint64_t n_splits = 0;
 	if (nI) {
-		KLAUNCH(k_vm_items, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, A, nR, ioff);
-		KLAUNCH(k_vm_keys, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, A, K, force ? 1u : 0u, t2, words + 1);
-		n_t2 = read_back(words + 1, s);
-		if (n_t2)
-			KLAUNCH(k_vm_keys_wave, dim3(wave_blocks(n_t2)), dim3(Q_TPB), 0, s, t2, n_t2, A, K);
+		n_t2 = launch_tiers(A, K, force, t2, words + 1, s);
 		// ---- groups: the trimmed texts of a key have at most 2 * longest bytes, a CHROM id is at most n_chroms (a skipped item's)
-		const uint32_t *sp = group_exact(nI, rq, rlen, rhash, hbits, bits_for(2 * longest), bits_for(n_chroms), SameKey{A, state, kpos, suffix, prefix}, gw,
-						 words + 2, splits, &n_splits, s);
-		HIP_CHECK(hipMemsetAsync(firstf, 0, i1 * 4, s));
-		KLAUNCH(k_eg_first, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, nI, sp, gw.rep, firstf);
-		KLAUNCH(k_vm_keyed_firsts, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, nI, state, firstf);
-		scan_exclusive_u32(firstf, gidx, i1, gw.tmp, gw.tmp_bytes, s);
+		const uint32_t *sp = group_exact(nI, rq, rlen, rhash, hbits, bits_for(2 * U.longest), bits_for(n_chroms), SameKey{A, state, kpos, suffix, prefix},
+						 gw, words + 2, splits, &n_splits, s);
+		number_groups(nI, sp, gw.rep, firstf, gidx, keep, gw.tmp, gw.tmp_bytes, s);
 		nG = read_back(gidx + nI, s); // (waits for the stream: n_splits has arrived)
-		KLAUNCH(k_vm_group_of, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, nI, sp, gw.rep, gidx, state, gid);
+		KLAUNCH(k_eg_group_of, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, nI, sp, gw.rep, gidx, keep, gid);
 		// ---- members: the items stably sorted by group, so those of a group stay in item order, A's first
 		launch_iota(nI, gw.pa, s);
 		LsdSort sort{gw.pa, gw.pb, gw.key, gw.kout, nI, gw.tmp, gw.tmp_bytes, s};
@@ -547,37 +314,27 @@ static povu_hip_vcf_cmp *vcf_compare(povu_hip_ctx *ctx, const povu_hip_vcf_doc *
 
 	// ---- to the host
 	uint64_t h_cnt[CN_WORDS] = {0};
-	hand_off(o->it_rec, i1, it_rec, nI, ctx);
-	hand_off(o->it_k, i1, it_k, nI, ctx);
-	hand_off(o->state, i1, state, nI, ctx);
-	hand_off(o->pos, i1, kpos, nI, ctx);
-	hand_off(o->suffix, i1, suffix, nI, ctx);
-	hand_off(o->prefix, i1, prefix, nI, ctx);
-	hand_off(o->gid, i1, gid, nI, ctx);
-	hand_off(o->g_class, (size_t)nG + 1, g_class, nG, ctx);
-	hand_off(o->g_na, (size_t)nG + 1, g_na, nG, ctx);
-	hand_off(o->g_nb, (size_t)nG + 1, g_nb, nG, ctx);
-	hand_off(o->g_first, (size_t)nG + 1, g_first, nG, ctx);
-	hand_off(o->tp, (size_t)nC + 1, tp, nC, ctx);
-	hand_off(o->fp, (size_t)nC + 1, fp, nC, ctx);
-	hand_off(o->fn, (size_t)nC + 1, fn, nC, ctx);
-	hand_off(o->gteq, (size_t)nC + 1, gteq, nC, ctx);
-	HIP_CHECK(copy_async(h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, s));
 	povu_hip_vcf_cmp &v = o->view;
-	v.device_ms = timer.stop(s);
-	v.n_items_a = nIa, v.n_items_b = nI - nIa, v.n_groups = nG, v.n_common_samples = nC;
-	v.item_record_a = o->it_rec.data(), v.item_record_b = o->it_rec.data() + nIa;
-	v.item_alt_a = o->it_k.data(), v.item_alt_b = o->it_k.data() + nIa;
-	v.item_state_a = o->state.data(), v.item_state_b = o->state.data() + nIa;
-	v.item_pos_a = o->pos.data(), v.item_pos_b = o->pos.data() + nIa;
-	v.item_suffix_a = o->suffix.data(), v.item_suffix_b = o->suffix.data() + nIa;
-	v.item_prefix_a = o->prefix.data(), v.item_prefix_b = o->prefix.data() + nIa;
-	v.item_group_a = o->gid.data(), v.item_group_b = o->gid.data() + nIa;
-	v.group_class = o->g_class.data(), v.group_n_a = o->g_na.data(), v.group_n_b = o->g_nb.data(), v.group_first = o->g_first.data();
-	v.sample_col_a = o->col_a.data(), v.sample_col_b = o->col_b.data();
 	static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are read as uint64_t");
-	v.sample_tp = reinterpret_cast<const uint64_t *>(o->tp.data()), v.sample_fp = reinterpret_cast<const uint64_t *>(o->fp.data());
-	v.sample_fn = reinterpret_cast<const uint64_t *>(o->fn.data()), v.sample_gteq = reinterpret_cast<const uint64_t *>(o->gteq.data());
+	const size_t g1 = (size_t)nG + 1, c1 = (size_t)nC + 1;
+	hand_off_block(o->block, ctx, [&](HostSpans &take) {
+		const uint32_t *h_rec = take(it_rec, nI, i1), *h_k = take(it_k, nI, i1);
+		const uint8_t *h_state = take(state, nI, i1);
+		const uint64_t *h_pos = take(kpos, nI, i1);
+		const uint32_t *h_suffix = take(suffix, nI, i1), *h_prefix = take(prefix, nI, i1), *h_gid = take(gid, nI, i1);
+		v.group_class = take(g_class, nG, g1), v.group_n_a = take(g_na, nG, g1), v.group_n_b = take(g_nb, nG, g1), v.group_first = take(g_first, nG, g1);
+		v.sample_tp = reinterpret_cast<const uint64_t *>(take(tp, nC, c1)), v.sample_fp = reinterpret_cast<const uint64_t *>(take(fp, nC, c1));
+		v.sample_fn = reinterpret_cast<const uint64_t *>(take(fn, nC, c1)), v.sample_gteq = reinterpret_cast<const uint64_t *>(take(gteq, nC, c1));
+		v.item_record_a = h_rec, v.item_record_b = h_rec + nIa, v.item_alt_a = h_k, v.item_alt_b = h_k + nIa;
+		v.item_state_a = h_state, v.item_state_b = h_state + nIa, v.item_pos_a = h_pos, v.item_pos_b = h_pos + nIa;
+		v.item_suffix_a = h_suffix, v.item_suffix_b = h_suffix + nIa, v.item_prefix_a = h_prefix, v.item_prefix_b = h_prefix + nIa;
+		v.item_group_a = h_gid, v.item_group_b = h_gid + nIa;
+	});
+	HIP_CHECK(copy_async(h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, s));
+	v.device_ms = timer.stop(s);
+	o->col_a = std::move(U.col_a), o->col_b = std::move(U.col_b);
+	v.n_items_a = nIa, v.n_items_b = nI - nIa, v.n_groups = nG, v.n_common_samples = nC;
+	v.sample_col_a = o->col_a.data(), v.sample_col_b = o->col_b.data();
 	v.n_shared = h_cnt[CN_SHARED], v.n_only_a = h_cnt[CN_ONLY_A], v.n_only_b = h_cnt[CN_ONLY_B];
 	v.n_skipped_a = h_cnt[CN_SKIPPED_A], v.n_skipped_b = h_cnt[CN_SKIPPED_B];
 	v.n_samples_only_a = da->n_samples - nC, v.n_samples_only_b = db->n_samples - nC;

@@ -1,8 +1,9 @@
 // vcfcmp_rules.hpp -- the rules of the VCF comparison (INTEGRATION.md "VCF comparison"; restated in tests/vcfcmp_ref.py) that
 // are plain arithmetic: which (record, ALT) is skipped, the case fold, how many bytes the two trims take at either end of REF
 // and ALT, when two trimmed keys are equal, the hash of a key and the class of a (group, sample) cell from its two doses.
-// Free of HIP: vcfcmp_kernels.hip runs them per lane and, chunk by chunk, per wave; host/vcfcheck.cpp writes the texts with
-// them; host/vcfcmp_check.cpp runs them on the CPU under the sanitizers, the wave's chunks included.
+// Free of HIP, the wave's loops included ("a wave at a time" below): the tier kernels of vcf_pair.hpp run them per lane and
+// per wave for the VCF comparison and for the haplotype comparison; host/vcfcheck.cpp writes the texts with them;
+// host/vcfcmp_check.cpp and host/vcfhap_check.cpp run the same text on the CPU under the sanitizers, over an emulated wave.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -43,22 +44,29 @@ VCFCMP_FN bool vm_suffix_differs(const char *ref, uint64_t nr, const char *alt, 
 	return vm_fold(ref[nr - 1 - i]) != vm_fold(alt[na - 1 - i]);
 }
 VCFCMP_FN bool vm_prefix_differs(const char *ref, const char *alt, uint64_t i) { return vm_fold(ref[i]) != vm_fold(alt[i]); }
-VCFCMP_FN uint64_t vm_suffix(const char *ref, uint64_t nr, const char *alt, uint64_t na)
+// (under any limit: the haplotype comparison's lets a text become empty)
+VCFCMP_FN uint64_t vm_suffix_upto(const char *ref, uint64_t nr, const char *alt, uint64_t na, uint64_t limit)
 {
-	const uint64_t limit = vm_trim_limit(nr, na);
 	uint64_t s = 0;
 	while (s < limit && !vm_suffix_differs(ref, nr, alt, na, s))
 		s++;
 	return s;
 }
-// (nr, na: the lengths before the suffix trim took s bytes)
-VCFCMP_FN uint64_t vm_prefix(const char *ref, uint64_t nr, const char *alt, uint64_t na, uint64_t s)
+VCFCMP_FN uint64_t vm_prefix_upto(const char *ref, const char *alt, uint64_t limit)
 {
-	const uint64_t limit = vm_trim_limit(nr - s, na - s);
 	uint64_t p = 0;
 	while (p < limit && !vm_prefix_differs(ref, alt, p))
 		p++;
 	return p;
+}
+VCFCMP_FN uint64_t vm_suffix(const char *ref, uint64_t nr, const char *alt, uint64_t na)
+{
+	return vm_suffix_upto(ref, nr, alt, na, vm_trim_limit(nr, na));
+}
+// (nr, na: the lengths before the suffix trim took s bytes)
+VCFCMP_FN uint64_t vm_prefix(const char *ref, uint64_t nr, const char *alt, uint64_t na, uint64_t s)
+{
+	return vm_prefix_upto(ref, alt, vm_trim_limit(nr - s, na - s));
 }
 
 // two trimmed keys of one CHROM are equal: POS', both lengths, the folded bytes
@@ -111,6 +119,51 @@ VCFCMP_FN uint64_t vm_key_hash(uint64_t pos, uint64_t nr, uint64_t na, uint64_t 
 	h = vm_mix64(h ^ (nr << 32) ^ na);
 	h = vm_mix64(h ^ ref_hash);
 	return vm_mix64(h + alt_hash);
+}
+
+// ---- a wave at a time: the skip rule's scan, both trims and the text hash with 64 lanes across the bytes.  `w` is the wave:
+// w.ballot(f) gives the 64-bit mask of the lanes l for which f(l) holds, w.sum(f) the sum of f(l) over the lanes.  On the
+// device w holds the calling lane and every lane of the wave makes the same calls (LaneWave of vcf_pair.hpp: __ballot and
+// wave_sum); the check programs loop l over 0 .. 63 (host/wave_emu.hpp).  The bounds (`limit`, `n`) belong to the item and
+// the item to the wave, so the trip counts are wave-uniform and every ballot and shuffle runs with all 64 lanes.
+// The first index below `limit` at which pred holds, else `limit`: 64 a chunk, to the first ballot that is not empty
+template <class W, class Pred>
+VCFCMP_FN uint64_t wave_first(uint64_t limit, const W &w, Pred &&pred)
+{
+	for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
+		const uint64_t m = w.ballot([&](uint32_t l) { return c0 + l < limit && pred(c0 + l); });
+		if (m)
+			return c0 + (uint64_t)__builtin_ctzll(m);
+	}
+	return limit;
+}
+template <class W>
+VCFCMP_FN bool wave_skipped(const char *ref, uint64_t nr, const char *alt, uint64_t na, const W &w)
+{
+	return vm_skip_head(ref, nr, alt, na) || wave_first(na, w, [&](uint64_t i) { return vm_skip_byte(alt[i]); }) != na;
+}
+// (limit_of: vm_trim_limit, or the haplotype comparison's vh_trim_limit)
+template <class W, class Limit>
+VCFCMP_FN uint64_t wave_suffix(const char *ref, uint64_t nr, const char *alt, uint64_t na, Limit &&limit_of, const W &w)
+{
+	return wave_first(limit_of(nr, na), w, [&](uint64_t i) { return vm_suffix_differs(ref, nr, alt, na, i); });
+}
+template <class W, class Limit>
+VCFCMP_FN uint64_t wave_prefix(const char *ref, uint64_t nr, const char *alt, uint64_t na, uint64_t s, Limit &&limit_of, const W &w)
+{
+	return wave_first(limit_of(nr - s, na - s), w, [&](uint64_t i) { return vm_prefix_differs(ref, alt, i); });
+}
+// vm_text_hash of t[0, n): lane l sums the terms l, l + 64, ...
+template <class W>
+VCFCMP_FN uint64_t wave_text_hash(const char *t, uint64_t n, const W &w)
+{
+	const uint64_t stride = vm_pow(64);
+	return w.sum([&](uint32_t l) {
+		uint64_t h = 0, power = vm_pow(l);
+		for (uint64_t x = l; x < n; x += 64, power *= stride)
+			h += vm_term(t[x], power);
+		return h;
+	});
 }
 
 // ---- the class of a (group, common sample) cell from the doses of both sides

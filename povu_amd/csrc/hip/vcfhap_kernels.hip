@@ -2,15 +2,16 @@
 // the same bases?
 //
 // The definition is INTEGRATION.md "Haplotype comparison" (restated in tests/vcfhap_ref.py; the rules that are plain arithmetic
-// are vcfhap_rules.hpp).  Both documents are uploaded as one, as the VCF comparison does: A's records, alleles, texts and tasks,
-// then B's, the CHROM strings interned over both.  Coordinates on the device carry one more than the 0-based value (bs, be,
-// lo, hi: POS names base POS), so that POS 0 has no negative start; the host takes the one off.
+// are vcfhap_rules.hpp).  Both documents are uploaded as one (vcf_pair.hpp: the host builder, the view, the items).
+// Coordinates on the device carry one more than the 0-based value (bs, be, lo, hi: POS names base POS), so that POS 0 has no
+// negative start; the host takes the one off.
 //   place    a lane per record: placed or not, its span [POS, POS + |REF|);
-//   edits    the skip rule, the full trim and the hash of (s, e, T).  A lane per item while the shorter text has at most
-//            TIER1_BYTES bytes, else a wave per item, 64 bytes a ballot (the VCF comparison's two tiers);
+//   edits    the skip rule, the full trim and the hash of (s, e, T): the two tiers of vcf_pair.hpp over EditPolicy, which
+//            settles the items of unplaced records first, trims to vh_trim_limit, hashes T and writes an edit or none;
 //   reach    reference mode: a wave per indel edit, 64 reference bases a ballot to the right, then to the left, through a
 //            RefView over the CHROM paths (launch_ref_len + scan_exclusive_u64); the record's span is widened by atomics;
-//   groups   exact_groups.hpp over (CHROM id, |T|, hash), the comparison the bytes of T with s and e; the items then sorted
+//   groups   exact_groups.hpp over (CHROM id, |T|, hash), the comparison the bytes of T with s and e, the groups of the items
+//            with an edit numbered in first-item order (number_groups); the items then sorted
 //            by (s, e, group): an item's place in that order is what its tasks sort by;
 //   windows  the records sorted by (CHROM, span start); every span bisects for the last span that starts at or before its end,
 //            an exclusive running maximum of those marks the heads, scans give the window ids and the text offsets;
@@ -24,9 +25,9 @@
 // the host carved: records below nR, items below nI, windows below nW <= nR, tasks, cells and distinct edits below nV <= nT.
 #include "call_common.hpp"
 #include "exact_groups.hpp"
+#include "vcf_pair.hpp"
 #include "vcfhap_rules.hpp"
 
-#include <string>
 #include <unordered_map>
 
 namespace povu_hip
@@ -35,38 +36,10 @@ namespace povu_hip
 namespace
 {
 
-constexpr uint32_t TIER1_BYTES = 32;
-constexpr unsigned COUNT_BLOCKS = 2048;
 constexpr uint64_t POS_LIMIT = 1ull << 40;
 enum { CN_PLACED_A = 0, CN_PLACED_B, CN_CAPPED, CN_BAD_WINDOWS, CN_TASKS, CN_WORDS = 8 };
 enum { KIND_REF = 0, KIND_UNSPELLED = 1, KIND_EDIT = 2 };
 
-// both documents as one, and the items
-struct VhView {
-	uint32_t nR, nRa, nI, nIa;
-	const uint32_t *aoff;	 // [nR + 1] alleles of a record
-	const uint32_t *ioff;	 // [nR + 1] items of a record
-	const uint64_t *toff;	 // [alleles + 1]
-	const char *text;
-	const uint64_t *pos;	 // [nR]
-	const uint32_t *chrom;	 // [nR] CHROM id over both documents
-	uint32_t *it_rec, *it_k; // [nI] the record within its document, the ALT
-	struct Texts {
-		const char *ref, *alt;
-		uint64_t nr, na;
-	};
-	__device__ __forceinline__ uint32_t record_of(uint32_t i) const { return it_rec[i] + (i >= nIa ? nRa : 0u); }
-	__device__ __forceinline__ uint64_t ref_len(uint32_t r) const
-	{
-		const uint32_t ar = aoff[r];
-		return aoff[r + 1] > ar ? toff[ar + 1] - toff[ar] : 0;
-	}
-	__device__ __forceinline__ Texts texts(uint32_t i) const
-	{
-		const uint32_t ar = aoff[record_of(i)], aa = ar + it_k[i];
-		return {text + toff[ar], text + toff[aa], toff[ar + 1] - toff[ar], toff[aa + 1] - toff[aa]};
-	}
-};
 // the reference: CHROM id -> reference number (NO_QUERY: no path of that name), the view over those paths
 struct VhRef {
 	uint32_t on;
@@ -83,7 +56,7 @@ struct VhRef {
 };
 // what the edit kernels write per item
 struct VhEdits {
-	uint8_t *state;
+	uint8_t *state, *keep; // (keep: 1 for an item with an edit, which the group numbering counts)
 	uint64_t *bs, *be, *t_at; // [s, e) with one added; where T begins in the uploaded text
 	uint32_t *t_len, *suffix, *prefix;
 	uint32_t *rq, *rlen; // the grouping's query (CHROM id; n_chroms for an item without an edit) and length
@@ -93,7 +66,7 @@ struct VhEdits {
 	const uint8_t *placed;
 };
 
-__global__ __launch_bounds__(Q_TPB) void k_vh_place(VhView A, VhRef F, uint8_t *__restrict__ placed, uint64_t *__restrict__ sp_lo,
+__global__ __launch_bounds__(Q_TPB) void k_vh_place(PairView A, VhRef F, uint8_t *__restrict__ placed, uint64_t *__restrict__ sp_lo,
 						     uint64_t *__restrict__ sp_hi, unsigned long long *__restrict__ cnt)
 {
 	const uint32_t lane = threadIdx.x & 63u;
@@ -120,118 +93,43 @@ __global__ __launch_bounds__(Q_TPB) void k_vh_place(VhView A, VhRef F, uint8_t *
 		atomicAdd(cnt + CN_PLACED_B, nb);
 }
 
-__global__ void k_vh_items(VhView A)
-{
-	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < A.nI; i += gridDim.x * Q_TPB) {
-		uint32_t lo = 0, hi = A.nR; // the last record whose items begin at or before i (ioff[0] = 0, nI > 0 hence nR > 0)
-		while (hi - lo > 1) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (A.ioff[mid] <= i)
-				lo = mid;
-			else
-				hi = mid;
-		}
-		A.it_rec[i] = lo - (lo >= A.nRa ? A.nRa : 0u);
-		A.it_k[i] = i - A.ioff[lo] + 1;
-	}
-}
-
 __device__ __forceinline__ void write_none(const VhEdits &O, uint32_t i, uint8_t state)
 {
-	O.state[i] = state;
+	O.state[i] = state, O.keep[i] = 0;
 	O.bs[i] = 0, O.be[i] = 0, O.t_at[i] = 0, O.t_len[i] = 0, O.suffix[i] = 0, O.prefix[i] = 0;
 	O.rq[i] = O.n_chroms, O.rlen[i] = 0, O.rhash[i] = vm_mix64(i) & O.mask; // (equal to no item: SameEdit)
 }
-__device__ __forceinline__ void write_edit(const VhEdits &O, const VhView &A, uint32_t i, const VhView::Texts &T, uint64_t s, uint64_t p, uint64_t t_hash)
+__device__ __forceinline__ void write_edit(const VhEdits &O, const PairView &A, uint32_t i, const PairView::Texts &T, uint64_t s, uint64_t p, uint64_t t_hash)
 {
 	const uint32_t r = A.record_of(i);
 	const VhEdit e = vh_edit(A.pos[r], T.nr, T.na, s, p);
-	O.state[i] = POVU_HIP_H_EDIT;
+	O.state[i] = POVU_HIP_H_EDIT, O.keep[i] = 1;
 	O.bs[i] = e.bs, O.be[i] = e.be, O.t_at[i] = (uint64_t)(T.alt - A.text) + e.t_at, O.t_len[i] = (uint32_t)e.t_len;
 	O.suffix[i] = (uint32_t)s, O.prefix[i] = (uint32_t)p;
 	O.rq[i] = A.chrom[r], O.rlen[i] = (uint32_t)e.t_len, O.rhash[i] = vh_edit_hash(e.bs, e.be, e.t_len, t_hash) & O.mask;
 }
 
-// tier 1: a lane per item; the items whose shorter text is long (or every item, with force) go to `t2`
-__global__ void k_vh_edits(VhView A, VhEdits O, uint32_t force, uint32_t *__restrict__ t2, uint32_t *__restrict__ n_t2)
-{
-	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < A.nI; i += gridDim.x * Q_TPB) {
-		const VhView::Texts T = A.texts(i);
-		if (force || min(T.nr, T.na) > TIER1_BYTES) {
-			t2[atomicAdd(n_t2, 1u)] = i; // (at most nI of them)
-			continue;
-		}
-		if (!O.placed[A.record_of(i)]) {
-			write_none(O, i, POVU_HIP_H_UNPLACED);
-			continue;
-		}
-		if (vm_skipped(T.ref, T.nr, T.alt, T.na)) {
-			write_none(O, i, POVU_HIP_H_UNSPELLED);
-			continue;
-		}
-		const uint64_t s = vh_suffix(T.ref, T.nr, T.alt, T.na), p = vh_prefix(T.ref, T.nr, T.alt, T.na, s);
-		write_edit(O, A, i, T, s, p, vm_text_hash(T.alt + p, T.na - s - p));
+// the edits as a policy of the two tiers (vcf_pair.hpp): the items of an unplaced record are settled before their texts
+struct EditPolicy {
+	VhEdits O;
+	static constexpr bool HASH_REF = false;
+	static __device__ __forceinline__ uint64_t trim_limit(uint64_t nr, uint64_t na) { return vh_trim_limit(nr, na); }
+	__device__ __forceinline__ bool refused(const PairView &A, uint32_t i) const { return !O.placed[A.record_of(i)]; }
+	__device__ __forceinline__ void on_refused(uint32_t i) const { write_none(O, i, POVU_HIP_H_UNPLACED); }
+	__device__ __forceinline__ void on_skipped(uint32_t i) const { write_none(O, i, POVU_HIP_H_UNSPELLED); }
+	__device__ __forceinline__ void on_trimmed(const PairView &A, uint32_t i, const PairView::Texts &T, uint64_t s, uint64_t p, uint64_t, uint64_t t_hash) const
+	{
+		write_edit(O, A, i, T, s, p, t_hash);
 	}
-}
-
-// the polynomial hash of t[0, n), lanes across the bytes
-__device__ __forceinline__ uint64_t wave_text_hash(const char *__restrict__ t, uint64_t n, uint32_t lane)
-{
-	uint64_t h = 0, power = vm_pow(lane);
-	const uint64_t stride = vm_pow(64);
-	for (uint64_t x = lane; x < n; x += 64, power *= stride)
-		h += vm_term(t[x], power);
-	return wave_sum(h);
-}
-// tier 2: a wave per item of `t2`
-__global__ __launch_bounds__(Q_TPB) void k_vh_edits_wave(const uint32_t *__restrict__ t2, uint32_t n2, VhView A, VhEdits O)
-{
-	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
-	for (uint32_t x = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); x < n2; x += waves) {
-		const uint32_t i = t2[x];
-		const VhView::Texts T = A.texts(i);
-		if (!O.placed[A.record_of(i)]) {
-			if (lane == 0)
-				write_none(O, i, POVU_HIP_H_UNPLACED);
-			continue;
-		}
-		bool skip = vm_skip_head(T.ref, T.nr, T.alt, T.na);
-		for (uint64_t c0 = 0; !skip && c0 < T.na; c0 += 64)
-			skip = __ballot(c0 + lane < T.na && vm_skip_byte(T.alt[c0 + lane])) != 0;
-		if (skip) {
-			if (lane == 0)
-				write_none(O, i, POVU_HIP_H_UNSPELLED);
-			continue;
-		}
-		uint64_t limit = vh_trim_limit(T.nr, T.na), s = limit;
-		for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-			const unsigned long long m = __ballot(c0 + lane < limit && vm_suffix_differs(T.ref, T.nr, T.alt, T.na, c0 + lane));
-			if (m) {
-				s = c0 + (uint64_t)(__ffsll((long long)m) - 1);
-				break;
-			}
-		}
-		limit = vh_trim_limit(T.nr - s, T.na - s);
-		uint64_t p = limit;
-		for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-			const unsigned long long m = __ballot(c0 + lane < limit && vm_prefix_differs(T.ref, T.alt, c0 + lane));
-			if (m) {
-				p = c0 + (uint64_t)(__ffsll((long long)m) - 1);
-				break;
-			}
-		}
-		const uint64_t ht = wave_text_hash(T.alt + p, T.na - s - p, lane);
-		if (lane == 0)
-			write_edit(O, A, i, T, s, p, ht);
-	}
-}
+};
 
 // ---- reach: a wave per item (those that are no indel edit pass), reference mode only
-__global__ __launch_bounds__(Q_TPB) void k_vh_reach(VhView A, VhEdits O, VhRef F, uint32_t max_reach, uint32_t *__restrict__ left,
+__global__ __launch_bounds__(Q_TPB) void k_vh_reach(PairView A, VhEdits O, VhRef F, uint32_t max_reach, uint32_t *__restrict__ left,
 						     uint32_t *__restrict__ right, unsigned long long *__restrict__ sp_lo,
 						     unsigned long long *__restrict__ sp_hi, unsigned long long *__restrict__ cnt)
 {
-	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
+	const LaneWave w{threadIdx.x & 63u};
+	const uint32_t lane = w.lane, waves = gridDim.x * (Q_TPB / 64);
 	const uint64_t limit = (uint64_t)max_reach + 1; // (one step beyond the cap tells a capped reach from one that ends at it)
 	for (uint32_t i = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6); i < A.nI; i += waves) {
 		if (O.state[i] != POVU_HIP_H_EDIT)
@@ -243,27 +141,8 @@ __global__ __launch_bounds__(Q_TPB) void k_vh_reach(VhView A, VhEdits O, VhRef F
 		const uint64_t plen = F.path_len(c), s0 = bs - 1, e0 = be - 1;
 		const char *unit = bs == be ? A.text + O.t_at[i] : A.text + A.toff[A.aoff[r]] + O.prefix[i];
 		const uint64_t m = bs == be ? tl : be - bs;
-		uint64_t kr = limit, kl = limit;
-		for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-			const uint64_t x = c0 + lane;
-			const bool in = x < limit;
-			const bool ok = in && e0 + x < plen && vh_reach_right_ok(unit, m, x, F.base(c, e0 + x));
-			const unsigned long long bad = __ballot(in && !ok);
-			if (bad) {
-				kr = c0 + (uint64_t)(__ffsll((long long)bad) - 1);
-				break;
-			}
-		}
-		for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-			const uint64_t x = c0 + lane;
-			const bool in = x < limit;
-			const bool ok = in && x < s0 && vh_reach_left_ok(unit, m, x, F.base(c, s0 - 1 - x));
-			const unsigned long long bad = __ballot(in && !ok);
-			if (bad) {
-				kl = c0 + (uint64_t)(__ffsll((long long)bad) - 1);
-				break;
-			}
-		}
+		const uint64_t kr = wave_first(limit, w, [&](uint64_t x) { return !(e0 + x < plen && vh_reach_right_ok(unit, m, x, F.base(c, e0 + x))); });
+		const uint64_t kl = wave_first(limit, w, [&](uint64_t x) { return !(x < s0 && vh_reach_left_ok(unit, m, x, F.base(c, s0 - 1 - x))); });
 		if (lane == 0) {
 			const uint32_t l = (uint32_t)min(kl, (uint64_t)max_reach), rt = (uint32_t)min(kr, (uint64_t)max_reach);
 			left[i] = l, right[i] = rt;
@@ -294,22 +173,6 @@ struct SameEdit {
 		return true;
 	}
 };
-// an item without an edit is the first of no group
-__global__ void k_vh_edit_firsts(uint32_t n, const uint8_t *__restrict__ state, uint32_t *__restrict__ firstf)
-{
-	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < n; i += gridDim.x * Q_TPB)
-		if (state[i] != POVU_HIP_H_EDIT)
-			firstf[i] = 0;
-}
-// group number of every item, from its group's first member
-__global__ void k_vh_group_of(uint32_t n, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ rep, const uint32_t *__restrict__ gidx,
-			      const uint8_t *__restrict__ state, uint32_t *__restrict__ gid)
-{
-	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < n; k += gridDim.x * Q_TPB) {
-		const uint32_t r = rep[k], i = perm[k];
-		gid[i] = state[i] != POVU_HIP_H_EDIT ? NO_QUERY : gidx[perm[r < n ? r : k]];
-	}
-}
 // the items' order by (s, e, group): which = 0 group, 1 / 2 e's low and high word, 3 / 4 s's
 __global__ void k_vh_item_key(uint32_t n, int which, uint32_t nG, const uint32_t *__restrict__ perm, const uint32_t *__restrict__ gid,
 			      const uint64_t *__restrict__ bs, const uint64_t *__restrict__ be, uint32_t *__restrict__ key)
@@ -393,7 +256,7 @@ __global__ void k_vh_fill_ref(uint64_t total, uint32_t nW, const uint64_t *__res
 	}
 }
 // a wave per placed record: its folded REF into the text, the greater byte standing (the text's words are cleared first)
-__global__ __launch_bounds__(Q_TPB) void k_vh_fill_rec(VhView A, const uint8_t *__restrict__ placed, const uint32_t *__restrict__ rec_window,
+__global__ __launch_bounds__(Q_TPB) void k_vh_fill_rec(PairView A, const uint8_t *__restrict__ placed, const uint32_t *__restrict__ rec_window,
 							const uint64_t *__restrict__ woff, VhWindows W, uint32_t *__restrict__ words)
 {
 	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
@@ -417,7 +280,7 @@ __global__ __launch_bounds__(Q_TPB) void k_vh_fill_rec(VhView A, const uint8_t *
 	}
 }
 // a wave per placed record: a REF field that differs from the text at its place makes the window inconsistent
-__global__ __launch_bounds__(Q_TPB) void k_vh_verify(VhView A, const uint8_t *__restrict__ placed, const uint32_t *__restrict__ rec_window,
+__global__ __launch_bounds__(Q_TPB) void k_vh_verify(PairView A, const uint8_t *__restrict__ placed, const uint32_t *__restrict__ rec_window,
 						      const uint64_t *__restrict__ woff, VhWindows W, const uint8_t *__restrict__ wtext)
 {
 	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64);
@@ -453,7 +316,7 @@ struct VhTasks {
 	uint32_t *win, *smp, *item;		      // [nT] window (nW: takes no part), common sample, item of a KIND_EDIT task
 	uint8_t *sk;				      // [nT] side << 2 | kind
 };
-__global__ __launch_bounds__(Q_TPB) void k_vh_tasks(VhView A, VhTasks K, uint32_t nW, uint32_t n_cols_a, const uint32_t *__restrict__ colmap,
+__global__ __launch_bounds__(Q_TPB) void k_vh_tasks(PairView A, VhTasks K, uint32_t nW, uint32_t n_cols_a, const uint32_t *__restrict__ colmap,
 						     const uint8_t *__restrict__ placed, const uint32_t *__restrict__ rec_window,
 						     const uint8_t *__restrict__ state, unsigned long long *__restrict__ cnt)
 {
@@ -666,88 +529,19 @@ struct HapOwner {
 	PinnedVec<uint8_t> block; // every array of the view that came from the device, in one page-locked block (HostSpans)
 	std::vector<uint32_t> col_a, col_b;
 };
-// The arrays of a result in one page-locked block: `take(dev, n, size)` gives room for `size` elements and copies the first n
-// from the device.  Declared once as a list and run twice, as Spans: to measure (no base), then to place and copy.  One
-// block, because the context's pool keeps a bounded number of blocks whatever their size: thirty arrays a call would push
-// each other out of it and be page-locked again on the next call
-struct HostSpans {
-	uint8_t *base = nullptr; // null: measure only
-	hipStream_t s = nullptr;
-	size_t bytes = 0;
-	template <typename T>
-	T *operator()(const T *dev, size_t n, size_t size)
-	{
-		const size_t at = bytes;
-		bytes += (size * sizeof(T) + 63) & ~size_t(63);
-		if (!base)
-			return nullptr;
-		T *h = reinterpret_cast<T *>(base + at);
-		if (n)
-			HIP_CHECK(copy_async(h, dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
-		return h;
-	}
-};
-
-// what the kernels index by must lie within what they index (all true of povu_hip_vcf_parse)
-void check_hap_doc(const povu_hip_vcf_doc *d, const char *which)
-{
-	auto ascends = [](const uint64_t *off, uint64_t n, uint64_t total) {
-		if (!off || off[0] != 0 || off[n] != total)
-			return false;
-		for (uint64_t k = 0; k < n; k++)
-			if (off[k] > off[k + 1])
-				return false;
-		return true;
-	};
-	bool ok = ascends(d->allele_off, d->n_records, d->n_alleles) && ascends(d->task_off, d->n_records, d->n_tasks) &&
-		  ascends(d->text_off, d->n_alleles, d->n_text_bytes) && (!d->n_records || (d->rec_chrom && d->chrom && d->rec_pos)) &&
-		  (!d->n_alleles || d->allele_walk) && (!d->n_text_bytes || d->text) && (!d->n_samples || d->sample) &&
-		  (!d->n_tasks || (d->task_record && d->task_allele && d->task_col && d->task_phase));
-	for (uint64_t c = 0; ok && c < d->n_samples; c++)
-		ok = d->sample[c] != nullptr;
-	for (uint64_t r = 0; ok && r < d->n_records; r++) {
-		ok = d->rec_chrom[r] < d->n_chroms && d->chrom[d->rec_chrom[r]];
-		for (uint64_t t = d->task_off[r]; ok && t < d->task_off[r + 1]; t++)
-			ok = d->task_record[t] == r && d->task_col[t] < d->n_samples;
-	}
-	if (!ok)
-		throw HipError(std::string("the offsets, tasks and CHROM ids of document ") + which + " do not belong together");
-}
-// the ALTs of record r: its alleles with a text, REF first, but REF
-uint64_t alts_of(const povu_hip_vcf_doc *d, uint64_t r)
-{
-	uint64_t n = 0;
-	for (uint64_t a = d->allele_off[r]; a < d->allele_off[r + 1] && (d->allele_walk[a] & 2u); a++)
-		n++;
-	return n ? n - 1 : 0;
-}
-
 } // namespace
 
 static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_doc *da, const povu_hip_vcf_doc *db, const char *const *path_name,
 					uint32_t n_paths, const povu_hip_vcf_hap_opts *opts, CallTimer &timer)
 {
-	if (!ctx || !da || !db)
-		throw HipError("null context or document");
 	const bool force = opts && (opts->flags & POVU_HIP_V_FORCE_TIER2), reference = path_name != nullptr;
 	const uint32_t max_reach = opts ? opts->max_reach : POVU_HIP_H_MAX_REACH_DEFAULT;
-	if (max_reach > POVU_HIP_H_MAX_REACH_MOST)
-		throw HipError("max_reach " + std::to_string(max_reach) + ": more than " + std::to_string(POVU_HIP_H_MAX_REACH_MOST) + " is refused");
-	const povu_hip_vcf_doc *docs[2] = {da, db};
 	const char *who = "the haplotype comparison needs ";
-	for (const povu_hip_vcf_doc *d : docs) { // (a side first: the sums below do not wrap)
-		refuse_2_32(d->n_records + 64, who, "records of a document");
-		refuse_2_32(d->n_alleles + 64, who, "alleles of a document");
-		refuse_2_32(d->n_tasks + 64, who, "tasks of a document");
-		refuse_2_32(d->n_text_bytes + 64, who, "text bytes of a document");
-		refuse_2_32(d->n_samples + 64, who, "sample columns of a document");
-	}
-	refuse_2_32(da->n_records + db->n_records + 64, who, "records");
-	refuse_2_32(da->n_alleles + db->n_alleles + 64, who, "alleles");
-	refuse_2_32(da->n_tasks + db->n_tasks + 64, who, "tasks");
-	refuse_2_32(da->n_text_bytes + db->n_text_bytes + 64, who, "text bytes");
-	check_hap_doc(da, "A");
-	check_hap_doc(db, "B");
+	if (ctx && da && db && max_reach > POVU_HIP_H_MAX_REACH_MOST) // (null arguments are the builder's to refuse, first)
+		throw HipError("max_reach " + std::to_string(max_reach) + ": more than " + std::to_string(POVU_HIP_H_MAX_REACH_MOST) + " is refused");
+	PairWant want{};
+	want.t_rec = want.t_al = want.t_col = want.t_ph = want.colmap = true;
+	PairUpload U = pair_build(ctx, da, db, who, want, POS_LIMIT);
 	if (reference) {
 		if (!ctx->g.block || !ctx->paths_valid || ctx->paths_gen != ctx->g.gen)
 			throw HipError("reference mode needs the paths of the graph now uploaded (povu_hip_paths_upload after povu_hip_graph_upload)");
@@ -759,77 +553,13 @@ static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_do
 			if (!path_name[k])
 				throw HipError("null path name");
 	}
-	const uint32_t nRa = (uint32_t)da->n_records, nR = nRa + (uint32_t)db->n_records, nAl = (uint32_t)(da->n_alleles + db->n_alleles);
-	const uint32_t nT = (uint32_t)(da->n_tasks + db->n_tasks), hbits = hash_bits_hook();
-	const uint32_t n_cols_a = (uint32_t)da->n_samples, n_cols = n_cols_a + (uint32_t)db->n_samples;
-	const uint64_t n_text = da->n_text_bytes + db->n_text_bytes;
-
-	// ---- both documents as one; the items' offsets; the CHROM ids; the common samples
-	std::vector<uint32_t> h_aoff((size_t)nR + 1), h_ioff((size_t)nR + 1), h_chrom(nR), h_trec(nT), h_tal(nT), h_tcol(nT), h_tph(nT);
-	std::vector<uint64_t> h_toff((size_t)nAl + 1), h_pos(nR);
-	std::unordered_map<std::string, uint32_t> chrom_of;
-	std::vector<std::string> chrom_name;
-	uint64_t n_items = 0, n_items_a = 0, longest = 0;
-	uint32_t max_phase = 0;
-	{
-		uint64_t r0 = 0, a0 = 0, t0 = 0, x0 = 0;
-		for (int side = 0; side < 2; side++) { // (by side, not by pointer: a document may be compared with itself)
-			const povu_hip_vcf_doc *d = docs[side];
-			std::vector<uint32_t> id(d->n_chroms);
-			for (uint64_t k = 0; k < d->n_chroms; k++) {
-				id[k] = d->chrom[k] ? chrom_of.emplace(d->chrom[k], (uint32_t)chrom_of.size()).first->second : 0u;
-				if (chrom_name.size() < chrom_of.size())
-					chrom_name.push_back(d->chrom[k]);
-			}
-			for (uint64_t r = 0; r < d->n_records; r++) {
-				if (d->rec_pos[r] >= POS_LIMIT)
-					throw HipError(std::string("document ") + (side ? "B" : "A") + ", record " + std::to_string(r) + ": POS " +
-						       std::to_string(d->rec_pos[r]) + ": 2^40 or more is refused");
-				h_aoff[r0 + r] = (uint32_t)(a0 + d->allele_off[r]);
-				h_ioff[r0 + r] = (uint32_t)std::min<uint64_t>(n_items, 0xFFFFFFFFull);
-				h_pos[r0 + r] = d->rec_pos[r];
-				h_chrom[r0 + r] = id[d->rec_chrom[r]];
-				const uint64_t alts = alts_of(d, r), ar = d->allele_off[r];
-				n_items += alts;
-				for (uint64_t k = 0; k <= alts && ar + k < d->allele_off[r + 1]; k++)
-					longest = std::max(longest, d->text_off[ar + k + 1] - d->text_off[ar + k]);
-			}
-			for (uint64_t a = 0; a < d->n_alleles; a++)
-				h_toff[a0 + a] = x0 + d->text_off[a];
-			for (uint64_t t = 0; t < d->n_tasks; t++) {
-				h_trec[t0 + t] = (uint32_t)(r0 + d->task_record[t]), h_tal[t0 + t] = d->task_allele[t];
-				h_tcol[t0 + t] = d->task_col[t], h_tph[t0 + t] = d->task_phase[t];
-				max_phase = std::max(max_phase, d->task_phase[t]);
-			}
-			r0 += d->n_records, a0 += d->n_alleles, t0 += d->n_tasks, x0 += d->n_text_bytes;
-			if (side == 0)
-				n_items_a = n_items;
-		}
-		h_aoff[nR] = nAl, h_toff[nAl] = n_text;
-	}
-	refuse_2_32(n_items + 64, who, "(record, ALT) items");
-	h_ioff[nR] = (uint32_t)n_items;
-	const uint32_t nI = (uint32_t)n_items, nIa = (uint32_t)n_items_a, n_chroms = (uint32_t)chrom_of.size();
+	const uint32_t nRa = U.nRa, nR = U.nR, nAl = U.nAl, nT = U.nT, nI = U.nI, nIa = U.nIa, nC = U.nC, n_chroms = U.n_chroms, hbits = hash_bits_hook();
+	const uint32_t n_cols_a = U.n_cols_a, n_cols = U.n_cols, max_phase = U.max_phase;
 	auto o = std::make_unique<HapOwner>();
-	std::vector<uint32_t> h_colmap((size_t)n_cols + 1, NO_QUERY);
-	{
-		std::unordered_map<std::string, uint32_t> col_of_b; // (of several columns of one name the first counts)
-		for (uint64_t c = 0; c < db->n_samples; c++)
-			col_of_b.emplace(db->sample[c], (uint32_t)c);
-		for (uint64_t c = 0; c < da->n_samples; c++) {
-			const auto at = col_of_b.find(da->sample[c]);
-			if (at == col_of_b.end())
-				continue;
-			h_colmap[c] = h_colmap[n_cols_a + at->second] = (uint32_t)o->col_a.size();
-			o->col_a.push_back((uint32_t)c), o->col_b.push_back(at->second);
-			col_of_b.erase(at);
-		}
-	}
-	const uint32_t nC = (uint32_t)o->col_a.size();
 
 	HIP_CHECK(hipSetDevice(ctx->device));
 	ctx->wait_tail();
-	hipStream_t s = ctx->stream;
+	hipStream_t s = U.s = ctx->stream;
 	// ---- the reference: the paths the CHROMs name, one after another (a "reference index" over them, as the calls build it)
 	std::vector<uint32_t> h_chrom_ref((size_t)n_chroms + 1, NO_QUERY), h_ref_path;
 	std::vector<uint64_t> h_ref_base(1, 0);
@@ -841,7 +571,7 @@ static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_do
 		HIP_CHECK(copy_async(path_off.data(), ctx->path_off, ((size_t)n_paths + 1) * 8, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
 		for (uint32_t c = 0; c < n_chroms; c++) {
-			const auto at = path_of.find(chrom_name[c]);
+			const auto at = path_of.find(U.chrom_name[c]);
 			if (at == path_of.end())
 				continue;
 			h_chrom_ref[c] = (uint32_t)h_ref_path.size();
@@ -859,7 +589,7 @@ static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_do
 		*u_item, *words;
 	uint64_t *toff, *pos, *ref_base, *ref_len, *roff, *s64, *bs, *be, *t_at, *rhash, *sp_lo, *sp_hi, *wlen, *woff, *dpos, *u_key;
 	unsigned long long *w_lo, *w_hi, *cnt, *splits;
-	uint8_t *placed, *state, *w_bad, *tk_sk;
+	uint8_t *placed, *state, *keep, *w_bad, *tk_sk;
 	char *text;
 	GroupWs gw;
 	gw.tmp_bytes = prim_tmp_bytes(big + 1, true) + 256;
@@ -871,7 +601,7 @@ static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_do
 		take(r1, w_lo, w_hi);
 		take(r1, placed, w_bad);
 		take((size_t)nAl + 1, toff);
-		take(n_text + 1, text);
+		take(U.n_text + 1, text);
 		take(t1, t_rec, t_al, t_col, t_ph, tk_win, tk_smp, tk_item, cidx, uidx, c_x0, u_item);
 		take(t1, dpos, u_key);
 		take(t1, tk_sk);
@@ -884,32 +614,17 @@ static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_do
 		take(i1, it_rec, it_k, suffix, prefix, left, right, t_len, rq, rlen, t2, firstf, gid, place, gw.head, gw.rep, gw.blist);
 		take(i1 + 1, gidx);
 		take(i1, bs, be, t_at, rhash);
-		take(i1, state, gw.rbad);
+		take(i1, state, keep, gw.rbad);
 		take(big, gw.pa, gw.pb, gw.key, gw.kout, gw.mark, gw.hmax);
 		take(8, words);
 		take(CN_WORDS, cnt);
 		take(1, splits);
 		take(gw.tmp_bytes, gw.tmp);
 	});
-	auto up = [&](void *dst, const void *src, size_t bytes) {
-		if (bytes)
-			HIP_CHECK(copy_async(dst, src, bytes, hipMemcpyHostToDevice, s));
-	};
-	up(aoff, h_aoff.data(), r1 * 4);
-	up(ioff, h_ioff.data(), r1 * 4);
-	up(chrom, h_chrom.data(), (size_t)nR * 4);
-	up(pos, h_pos.data(), (size_t)nR * 8);
-	up(toff, h_toff.data(), ((size_t)nAl + 1) * 8);
-	up(text, da->text, da->n_text_bytes);
-	up(text + da->n_text_bytes, db->text, db->n_text_bytes);
-	up(t_rec, h_trec.data(), (size_t)nT * 4);
-	up(t_al, h_tal.data(), (size_t)nT * 4);
-	up(t_col, h_tcol.data(), (size_t)nT * 4);
-	up(t_ph, h_tph.data(), (size_t)nT * 4);
-	up(colmap, h_colmap.data(), ((size_t)n_cols + 1) * 4);
-	up(chrom_ref, h_chrom_ref.data(), ((size_t)n_chroms + 1) * 4);
-	up(ref_path, h_ref_path.data(), (size_t)nRef * 4);
-	up(ref_base, h_ref_base.data(), ((size_t)nRef + 1) * 8);
+	U.up(aoff, U.aoff), U.up(ioff, U.ioff), U.up(chrom, U.chrom), U.up(pos, U.pos), U.up(toff, U.toff);
+	U.up_text(text);
+	U.up(t_rec, U.t_rec), U.up(t_al, U.t_al), U.up(t_col, U.t_col), U.up(t_ph, U.t_ph), U.up(colmap, U.colmap);
+	U.up(chrom_ref, h_chrom_ref), U.up(ref_path, h_ref_path), U.up(ref_base, h_ref_base);
 	HIP_CHECK(hipMemsetAsync(words, 0, 32, s));
 	HIP_CHECK(hipMemsetAsync(cnt, 0, CN_WORDS * 8, s));
 	HIP_CHECK(hipMemsetAsync(rec_window, 0xFF, r1 * 4, s));
@@ -926,8 +641,8 @@ static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_do
 			launch_ref_len(R, P, ref_len, s);
 		scan_exclusive_u64(ref_len, roff, NRs + 1, s64, s);
 	}
-	const VhView A{nR, nRa, nI, nIa, aoff, ioff, toff, text, pos, chrom, it_rec, it_k};
-	const VhEdits E{state, bs, be, t_at, t_len, suffix, prefix, rq, rlen, rhash, ((uint64_t)hash_mask_hi(hbits) << 32) | hash_mask_lo(hbits), n_chroms, placed};
+	const PairView A{nR, nRa, nI, nIa, aoff, ioff, toff, text, pos, chrom, it_rec, it_k};
+	const EditPolicy E{{state, keep, bs, be, t_at, t_len, suffix, prefix, rq, rlen, rhash, ((uint64_t)hash_mask_hi(hbits) << 32) | hash_mask_lo(hbits), n_chroms, placed}};
 	const VhWindows W{w_chrom, w_na, w_nb, w_off, w_lo, w_hi, w_bad};
 	uint64_t h_cnt[CN_WORDS] = {0};
 	uint32_t n_t2 = 0, nG = 0, nW = 0, nV = 0, nCells = 0;
@@ -936,23 +651,16 @@ static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_do
 		KLAUNCH(k_vh_place, dim3(std::min(stride_blocks(nR), COUNT_BLOCKS)), dim3(Q_TPB), 0, s, A, F, placed, sp_lo, sp_hi, cnt);
 	// ---- items, edits, reaches, groups, the items' order
 	if (nI) {
-		KLAUNCH(k_vh_items, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, A);
-		KLAUNCH(k_vh_edits, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, A, E, force ? 1u : 0u, t2, words + 1);
-		n_t2 = read_back(words + 1, s);
-		if (n_t2)
-			KLAUNCH(k_vh_edits_wave, dim3(wave_blocks(n_t2)), dim3(Q_TPB), 0, s, t2, n_t2, A, E);
+		n_t2 = launch_tiers(A, E, force, t2, words + 1, s);
 		if (reference)
-			KLAUNCH(k_vh_reach, dim3(wave_blocks(nI)), dim3(Q_TPB), 0, s, A, E, F, max_reach, left, right, reinterpret_cast<unsigned long long *>(sp_lo),
+			KLAUNCH(k_vh_reach, dim3(wave_blocks(nI)), dim3(Q_TPB), 0, s, A, E.O, F, max_reach, left, right, reinterpret_cast<unsigned long long *>(sp_lo),
 				reinterpret_cast<unsigned long long *>(sp_hi), cnt);
 		// (T has at most `longest` bytes, a CHROM id is at most n_chroms: an item's without an edit)
-		const uint32_t *sp = group_exact(nI, rq, rlen, rhash, hbits, bits_for(longest), bits_for(n_chroms), SameEdit{text, state, bs, be, t_at, t_len}, gw,
+		const uint32_t *sp = group_exact(nI, rq, rlen, rhash, hbits, bits_for(U.longest), bits_for(n_chroms), SameEdit{text, state, bs, be, t_at, t_len}, gw,
 						 words + 2, splits, &n_splits, s);
-		HIP_CHECK(hipMemsetAsync(firstf, 0, i1 * 4, s));
-		KLAUNCH(k_eg_first, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, nI, sp, gw.rep, firstf);
-		KLAUNCH(k_vh_edit_firsts, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, nI, state, firstf);
-		scan_exclusive_u32(firstf, gidx, i1, gw.tmp, gw.tmp_bytes, s);
+		number_groups(nI, sp, gw.rep, firstf, gidx, keep, gw.tmp, gw.tmp_bytes, s);
 		nG = read_back(gidx + nI, s); // (waits for the stream: n_splits has arrived)
-		KLAUNCH(k_vh_group_of, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, nI, sp, gw.rep, gidx, state, gid);
+		KLAUNCH(k_eg_group_of, dim3(stride_blocks(nI)), dim3(Q_TPB), 0, s, nI, sp, gw.rep, gidx, keep, gid);
 		launch_iota(nI, gw.pa, s);
 		LsdSort sort{gw.pa, gw.pb, gw.key, gw.kout, nI, gw.tmp, gw.tmp_bytes, s};
 		auto key = [&](int which, const uint32_t *cur, uint32_t *k) {
@@ -1088,11 +796,7 @@ static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_do
 		v.win_lo = reinterpret_cast<const int64_t *>(h_lo), v.win_hi = reinterpret_cast<const int64_t *>(h_hi);
 		v.sample_status = reinterpret_cast<const uint64_t *>(h_ss);
 	};
-	HostSpans measure;
-	results(measure);
-	o->block.resize(measure.bytes, ctx->pool);
-	HostSpans filled{o->block.data(), s};
-	results(filled);
+	hand_off_block(o->block, ctx, results);
 	HIP_CHECK(copy_async(h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, s));
 	v.device_ms = timer.stop(s);
 	// (the coordinates carried one more than their 0-based value; an item without an edit has 0 in both)
@@ -1103,6 +807,7 @@ static povu_hip_vcf_hap *vcf_haplotypes(povu_hip_ctx *ctx, const povu_hip_vcf_do
 		h_lo[w] -= 1, h_hi[w] -= 1;
 	v.n_records_a = nRa, v.n_records_b = nR - nRa, v.n_items_a = nIa, v.n_items_b = nI - nIa, v.n_groups = nG, v.n_windows = nW, v.n_cells = nCells;
 	v.n_common_samples = nC;
+	o->col_a = std::move(U.col_a), o->col_b = std::move(U.col_b);
 	v.sample_col_a = o->col_a.data(), v.sample_col_b = o->col_b.data();
 	for (uint32_t x = 0; x < nC; x++)
 		for (uint32_t k = 0; k < POVU_HIP_H_N_STATUS; k++)

@@ -1,8 +1,8 @@
 // vcfhap_rules.hpp -- the rules of the haplotype comparison (INTEGRATION.md "Haplotype comparison"; restated in
 // tests/vcfhap_ref.py) that are plain arithmetic: the full trim that makes an edit, one step of a reach, when a sorted span
 // opens a window, when an edit of a sorted list conflicts with those in front of it, where byte h of a haplotype comes from,
-// and the order of the statuses.  Free of HIP: vcfhap_kernels.hip runs them per lane and, chunk by chunk, per wave;
-// host/vcfhap_check.cpp runs them on the CPU under the sanitizers, the wave's chunks included.
+// and the order of the statuses.  Free of HIP: vcfhap_kernels.hip runs them per lane and, chunk by chunk, per wave (the
+// trims through the wave loops of vcfcmp_rules.hpp); host/vcfhap_check.cpp runs them on the CPU under the sanitizers.
 // Coordinates are kept with one added (POS for the base POS names), so that a record at POS 0 has no negative start.
 #pragma once
 #include "vcfcmp_rules.hpp"
@@ -15,19 +15,11 @@ namespace povu_hip
 VCFCMP_FN uint64_t vh_trim_limit(uint64_t nr, uint64_t na) { return nr < na ? nr : na; }
 VCFCMP_FN uint64_t vh_suffix(const char *ref, uint64_t nr, const char *alt, uint64_t na)
 {
-	const uint64_t limit = vh_trim_limit(nr, na);
-	uint64_t s = 0;
-	while (s < limit && !vm_suffix_differs(ref, nr, alt, na, s))
-		s++;
-	return s;
+	return vm_suffix_upto(ref, nr, alt, na, vh_trim_limit(nr, na));
 }
 VCFCMP_FN uint64_t vh_prefix(const char *ref, uint64_t nr, const char *alt, uint64_t na, uint64_t s)
 {
-	const uint64_t limit = vh_trim_limit(nr - s, na - s);
-	uint64_t p = 0;
-	while (p < limit && !vm_prefix_differs(ref, alt, p))
-		p++;
-	return p;
+	return vm_prefix_upto(ref, alt, vh_trim_limit(nr - s, na - s));
 }
 // the edit of (POS, REF, ALT) from the two trims: [bs, be) with one added, T = ALT[p, na - s)
 struct VhEdit {

@@ -1,15 +1,16 @@
 // vcfcmp_check.cpp -- the rules of the VCF comparison as the device runs them (hip/vcfcmp_rules.hpp) and the CHROM table of
 // the VCF reader (host/vcfcheck.cpp), on the CPU.  Built with -fsanitize=address,undefined (`make vcfcmp_check`) and driven by
 // tests/test_vcfcmp_ref.py, which compares every line with the restatement.  Blocks on stdin (a text `_` is the empty text):
-//   key <pos> <ref> <alt>            -> `skipped`, or `<POS'> <suffix> <prefix> <REF'> <ALT'> <hash>`: the lane's loops, and again as
-//                                    a wave runs them -- 64 bytes a ballot backwards, then forwards, the hash as the sum of 64
-//                                    partial polynomials; the two must agree or the program fails
+//   key <pos> <ref> <alt>            -> `skipped`, or `<POS'> <suffix> <prefix> <REF'> <ALT'> <hash>`: the lane's loops, and again
+//                                    through the wave loops the tier-2 kernel calls (wave_skipped, wave_suffix, wave_prefix,
+//                                    wave_text_hash) over an emulated wave (wave_emu.hpp); the two must agree or the program fails
 //   same <pos> <ref> <alt> <pos> <ref> <alt>  -> 1 when the trimmed keys are equal (and then their hashes are), else 0
 //   cell <dose a> <dose b>           -> `<class> <gteq>`, the class none, tp, fp or fn
 //   chroms <threads> <bytes>         then the bytes of a VCF  -> `C` and the CHROM strings, `R` and every record's index
 //                                    among them, or `error <message>`
 #include "../../../include/povu_hip.h"
 #include "../hip/vcfcmp_rules.hpp"
+#include "wave_emu.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -47,56 +48,20 @@ static Key lane_key(uint64_t pos, const std::vector<char> &ref, const std::vecto
 	return k;
 }
 
-// a ballot: the lanes whose predicate holds
-template <class F> static uint64_t ballot(F &&f)
-{
-	uint64_t m = 0;
-	for (uint32_t lane = 0; lane < 64; lane++)
-		if (f(lane))
-			m |= 1ull << lane;
-	return m;
-}
-static uint64_t wave_text_hash(const char *t, uint64_t n)
-{
-	uint64_t sum = 0;
-	for (uint32_t lane = 0; lane < 64; lane++) {
-		uint64_t h = 0, power = vm_pow(lane);
-		for (uint64_t x = lane; x < n; x += 64, power *= vm_pow(64))
-			h += vm_term(t[x], power);
-		sum += h;
-	}
-	return sum;
-}
+// the key as tier_items_wave of hip/vcf_pair.hpp computes it: the same calls, the wave emulated
 static Key wave_key(uint64_t pos, const std::vector<char> &ref, const std::vector<char> &alt)
 {
 	Key k{};
+	const EmuWave w;
 	const uint64_t nr = ref.size(), na = alt.size();
-	k.skipped = vm_skip_head(ref.data(), nr, alt.data(), na);
-	for (uint64_t c0 = 0; !k.skipped && c0 < na; c0 += 64)
-		k.skipped = ballot([&](uint32_t l) { return c0 + l < na && vm_skip_byte(alt[c0 + l]); }) != 0;
-	if (k.skipped)
+	const auto limit = [](uint64_t a, uint64_t b) { return vm_trim_limit(a, b); };
+	if ((k.skipped = wave_skipped(ref.data(), nr, alt.data(), na, w)))
 		return k;
-	uint64_t limit = vm_trim_limit(nr, na);
-	k.s = limit;
-	for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-		const uint64_t m = ballot([&](uint32_t l) { return c0 + l < limit && vm_suffix_differs(ref.data(), nr, alt.data(), na, c0 + l); });
-		if (m) {
-			k.s = c0 + (uint64_t)__builtin_ctzll(m);
-			break;
-		}
-	}
-	limit = vm_trim_limit(nr - k.s, na - k.s);
-	k.p = limit;
-	for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-		const uint64_t m = ballot([&](uint32_t l) { return c0 + l < limit && vm_prefix_differs(ref.data(), alt.data(), c0 + l); });
-		if (m) {
-			k.p = c0 + (uint64_t)__builtin_ctzll(m);
-			break;
-		}
-	}
+	k.s = wave_suffix(ref.data(), nr, alt.data(), na, limit, w);
+	k.p = wave_prefix(ref.data(), nr, alt.data(), na, k.s, limit, w);
 	k.pos = pos + k.p;
-	k.hash = vm_key_hash(k.pos, nr - k.s - k.p, na - k.s - k.p, wave_text_hash(ref.data() + k.p, nr - k.s - k.p),
-			     wave_text_hash(alt.data() + k.p, na - k.s - k.p));
+	k.hash = vm_key_hash(k.pos, nr - k.s - k.p, na - k.s - k.p, wave_text_hash(ref.data() + k.p, nr - k.s - k.p, w),
+			     wave_text_hash(alt.data() + k.p, na - k.s - k.p, w));
 	return k;
 }
 

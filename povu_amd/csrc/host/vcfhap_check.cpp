@@ -1,17 +1,18 @@
 // vcfhap_check.cpp -- the rules of the haplotype comparison as the device runs them (hip/vcfhap_rules.hpp), on the CPU.  Built
 // with -fsanitize=address,undefined (`make vcfhap_check`) and driven by tests/test_vcfhap_ref.py, which compares every line
 // with the restatement.  Blocks on stdin (a text `_` is the empty text):
-//   edit <pos> <ref> <alt>          -> `<s> <e> <suffix> <prefix> <T> <hash>`: the lane's loops, and again as a wave runs them --
-//                                   64 bytes a ballot backwards, then forwards, the hash of T as the sum of 64 partial
-//                                   polynomials; the two must agree or the program fails
-//   reach <path> <s> <e> <unit> <max>  -> `<left> <right> <capped>`: 64 bases a ballot to the right, then to the left, one step
-//                                   beyond the cap
+//   edit <pos> <ref> <alt>          -> `<s> <e> <suffix> <prefix> <T> <hash>`: the lane's loops, and again through the wave loops
+//                                   the tier-2 kernel calls (wave_suffix, wave_prefix, wave_text_hash of hip/vcfcmp_rules.hpp)
+//                                   over an emulated wave (wave_emu.hpp); the two must agree or the program fails
+//   reach <path> <s> <e> <unit> <max>  -> `<left> <right> <capped>`: k_vh_reach's two calls of wave_first, to the right, then to
+//                                   the left, one step beyond the cap
 //   heads <n> then n marks          -> a 0 or 1 per sorted span: the running maximum in chunks of 64 with a carry, then the test
 //   conflict <n> then n pairs s e   -> 0 or 1: the sorted list in chunks of 64, the maximum end and the last edit carried
 //   hap <text> <lo> <n> then n triples s e T  -> the haplotype, every byte by the locator
 //   status <7 flags>                -> the status, or `compare`;  compared <equal> <edits a> <edits b> -> the status
 #include "../../../include/povu_hip.h"
 #include "../hip/vcfhap_rules.hpp"
+#include "wave_emu.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -27,26 +28,6 @@ using namespace povu_hip;
 static std::vector<char> exact(const std::string &t) { return std::vector<char>(t.begin(), t.end()); }
 static std::string text_of(const std::string &token) { return token == "_" ? "" : token; }
 
-template <class F> static uint64_t ballot(F &&f)
-{
-	uint64_t m = 0;
-	for (uint32_t lane = 0; lane < 64; lane++)
-		if (f(lane))
-			m |= 1ull << lane;
-	return m;
-}
-static uint64_t wave_text_hash(const char *t, uint64_t n)
-{
-	uint64_t sum = 0;
-	for (uint32_t lane = 0; lane < 64; lane++) {
-		uint64_t h = 0, power = vm_pow(lane);
-		for (uint64_t x = lane; x < n; x += 64, power *= vm_pow(64))
-			h += vm_term(t[x], power);
-		sum += h;
-	}
-	return sum;
-}
-
 struct Edit {
 	uint64_t s, p, hash;
 	VhEdit e;
@@ -61,30 +42,17 @@ static Edit lane_edit(uint64_t pos, const std::vector<char> &ref, const std::vec
 	k.hash = vh_edit_hash(k.e.bs, k.e.be, k.e.t_len, vm_text_hash(alt.data() + k.p, na - k.s - k.p));
 	return k;
 }
+// the edit as tier_items_wave of hip/vcf_pair.hpp computes it: the same calls, the wave emulated
 static Edit wave_edit(uint64_t pos, const std::vector<char> &ref, const std::vector<char> &alt)
 {
 	Edit k{};
+	const EmuWave w;
 	const uint64_t nr = ref.size(), na = alt.size();
-	uint64_t limit = vh_trim_limit(nr, na);
-	k.s = limit;
-	for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-		const uint64_t m = ballot([&](uint32_t l) { return c0 + l < limit && vm_suffix_differs(ref.data(), nr, alt.data(), na, c0 + l); });
-		if (m) {
-			k.s = c0 + (uint64_t)__builtin_ctzll(m);
-			break;
-		}
-	}
-	limit = vh_trim_limit(nr - k.s, na - k.s);
-	k.p = limit;
-	for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-		const uint64_t m = ballot([&](uint32_t l) { return c0 + l < limit && vm_prefix_differs(ref.data(), alt.data(), c0 + l); });
-		if (m) {
-			k.p = c0 + (uint64_t)__builtin_ctzll(m);
-			break;
-		}
-	}
+	const auto limit = [](uint64_t a, uint64_t b) { return vh_trim_limit(a, b); };
+	k.s = wave_suffix(ref.data(), nr, alt.data(), na, limit, w);
+	k.p = wave_prefix(ref.data(), nr, alt.data(), na, k.s, limit, w);
 	k.e = vh_edit(pos, nr, na, k.s, k.p);
-	k.hash = vh_edit_hash(k.e.bs, k.e.be, k.e.t_len, wave_text_hash(alt.data() + k.p, na - k.s - k.p));
+	k.hash = vh_edit_hash(k.e.bs, k.e.be, k.e.t_len, wave_text_hash(alt.data() + k.p, na - k.s - k.p, w));
 	return k;
 }
 
@@ -92,27 +60,9 @@ static Edit wave_edit(uint64_t pos, const std::vector<char> &ref, const std::vec
 static void do_reach(const std::vector<char> &path, uint64_t s0, uint64_t e0, const std::vector<char> &unit, uint64_t max_reach)
 {
 	const uint64_t limit = max_reach + 1, plen = path.size(), m = unit.size();
-	uint64_t kr = limit, kl = limit;
-	for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-		const uint64_t bad = ballot([&](uint32_t l) {
-			const uint64_t x = c0 + l;
-			return x < limit && !(e0 + x < plen && vh_reach_right_ok(unit.data(), m, x, (uint8_t)path[e0 + x]));
-		});
-		if (bad) {
-			kr = c0 + (uint64_t)__builtin_ctzll(bad);
-			break;
-		}
-	}
-	for (uint64_t c0 = 0; c0 < limit; c0 += 64) {
-		const uint64_t bad = ballot([&](uint32_t l) {
-			const uint64_t x = c0 + l;
-			return x < limit && !(x < s0 && vh_reach_left_ok(unit.data(), m, x, (uint8_t)path[s0 - 1 - x]));
-		});
-		if (bad) {
-			kl = c0 + (uint64_t)__builtin_ctzll(bad);
-			break;
-		}
-	}
+	const EmuWave w;
+	const uint64_t kr = wave_first(limit, w, [&](uint64_t x) { return !(e0 + x < plen && vh_reach_right_ok(unit.data(), m, x, (uint8_t)path[e0 + x])); });
+	const uint64_t kl = wave_first(limit, w, [&](uint64_t x) { return !(x < s0 && vh_reach_left_ok(unit.data(), m, x, (uint8_t)path[s0 - 1 - x])); });
 	printf("%llu %llu %d\n", (unsigned long long)std::min(kl, max_reach), (unsigned long long)std::min(kr, max_reach), kl > max_reach || kr > max_reach ? 1 : 0);
 }
 
@@ -127,7 +77,7 @@ static bool chunked_conflict(const std::vector<uint64_t> &bs, const std::vector<
 			s[l] = c0 + l < n ? bs[c0 + l] : 0, e[l] = c0 + l < n ? be[c0 + l] : 0;
 			incl[l] = std::max(e[l], l ? incl[l - 1] : 0);
 		}
-		const uint64_t hit = ballot([&](uint32_t l) {
+		const uint64_t hit = EmuWave{}.ballot([&](uint32_t l) {
 			const uint64_t before = std::max(l ? incl[l - 1] : 0, carry_end);
 			return c0 + l < n && vh_conflict(s[l], e[l], c0 + l > 0, before, l ? s[l - 1] : carry_bs, l ? e[l - 1] : carry_be);
 		});
