@@ -1072,6 +1072,13 @@ int povu_hip_last_laminar_check_ran(const povu_hip_ctx *ctx);
  * interval holds an entry that reaches back beyond it, out[1] = those whose class had really been popped off
  * add_flubbles' stack by then (flubbles.cpp:326-343) -- decided in place by the parallel stage, no sequential redo */
 int povu_hip_last_crossings(povu_hip_ctx *ctx, uint32_t out[2]);
+/* after a pass that numbered the classes of the black tree edges only: out[0] = the bits of the class sort's payload that
+ * carried the size of an entry's bracket list above its stack index (32 - the bits of the number of stack entries, at most 8;
+ * POVU_HIP_LSZ_FIELD in the environment, read per pass, lowers that cap, 0 = no field), out[1] = the candidate-stack
+ * entries whose size did not fit (>= 2^out[0] - 1) and was looked up in the per-entry array instead -- all of them when
+ * out[0] is 0; they are counted by this call, from the sorted order the pass left on the device (tests and profiles
+ * only: one more kernel).  (0, 0) behind any other pass. */
+int povu_hip_last_lsz_field(povu_hip_ctx *ctx, uint32_t out[2]);
 /* number of links in the components this shard processed in the last decompose */
 uint64_t povu_hip_last_links_processed(const povu_hip_ctx *ctx);
 

@@ -48,11 +48,21 @@ __device__ __forceinline__ void landed(uint32_t &a, uint32_t &b, uint32_t &c, ui
 {
 	asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e));
 }
+__device__ __forceinline__ void landed(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t &d, uint32_t &e, uint32_t &f)
+{
+	asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
+}
 __device__ __forceinline__ void landed(uint2 &a, uint2 &b, uint2 &c, uint2 &d, uint32_t &e, uint32_t &f, uint32_t &g, uint32_t &h)
 {
 	asm volatile("" : POVU_W2(a), POVU_W2(b), POVU_W2(c), POVU_W2(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h));
 }
+__device__ __forceinline__ void landed(uint4 &a) { asm volatile("" : POVU_W4(a)); }
 __device__ __forceinline__ void landed(uint4 &a, uint2 &b) { asm volatile("" : POVU_W4(a), POVU_W2(b)); }
+__device__ __forceinline__ void landed(uint32_t &a, uint4 &b, uint4 &c, uint4 &d) { asm volatile("" : "+v"(a), POVU_W4(b), POVU_W4(c), POVU_W4(d)); }
+__device__ __forceinline__ void landed(uint32_t &a, uint32_t &b, uint32_t &c, uint4 &d, uint4 &e, uint4 &f)
+{
+	asm volatile("" : "+v"(a), "+v"(b), "+v"(c), POVU_W4(d), POVU_W4(e), POVU_W4(f));
+}
 __device__ __forceinline__ void landed(uint4 &a, uint4 &b, uint4 &c, uint4 &d) { asm volatile("" : POVU_W4(a), POVU_W4(b), POVU_W4(c), POVU_W4(d)); }
 // ... of a batch kept in arrays of N elements (k_back_edges: N = BE_BATCH sides of a lane at a time; the build takes 4, and 2
 // and 8 are there so that POVU_BE_BATCH can be set to them for a measurement)

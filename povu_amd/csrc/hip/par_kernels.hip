@@ -186,20 +186,35 @@ struct RootOf {
 		return 2 * voff[lo] + lo;
 	}
 };
+// rank(x) out of the record that holds x (bitrank, common.hpp)
+__device__ __forceinline__ uint32_t bitrank_in(const uint4 &r, uint32_t x)
+{
+	const unsigned long long bits = (unsigned long long)r.x | ((unsigned long long)r.y << 32);
+	return r.z + (uint32_t)__popcll(bits & ((1ull << (x & 63u)) - 1ull));
+}
+// the smallest of the first n (1 .. 8) of eight words
+__device__ __forceinline__ uint32_t min_of_first(const uint4 &a, const uint4 &b, uint32_t n)
+{
+	uint32_t m = a.x;
+	m = min(m, n > 1 ? a.y : NIL), m = min(m, n > 2 ? a.z : NIL), m = min(m, n > 3 ? a.w : NIL);
+	m = min(m, n > 4 ? b.x : NIL), m = min(m, n > 5 ? b.y : NIL), m = min(m, n > 6 ? b.z : NIL), m = min(m, n > 7 ? b.w : NIL);
+	return m;
+}
 __device__ __forceinline__ void capping_of(uint32_t v, const uint32_t *__restrict__ gsize, const uint32_t *__restrict__ hi0,
 					   const uint4 *__restrict__ brec, const RootOf &root_of,
 					   const SegTree &segA, uint32_t *__restrict__ cap_tgt,
-					   uint8_t *__restrict__ capf, uint32_t *__restrict__ literal_rule_seen)
+					   uint8_t *__restrict__ capf, uint32_t *__restrict__ literal_rule_seen, uint32_t hi0_words)
 {
-	const uint32_t end = v + gsize[v];
 	uint32_t root = NIL; // of v's tree, looked up at most once
+	auto root_once = [&]() __attribute__((always_inline)) {
+		if (root == NIL)
+			root = root_of(v);
+		return root;
+	};
 	auto hi_of = [&](uint32_t c) {
 		const uint32_t cs = max(gsize[c], 1u);
-		if (bitrank(brec, c + cs) != bitrank(brec, c)) { // a bridge vertex in subtree(c): a simplifying edge sits at or below it
-			if (root == NIL)
-				root = root_of(v);
-			return root;
-		}
+		if (bitrank(brec, c + cs) != bitrank(brec, c)) // a bridge vertex in subtree(c): a simplifying edge sits at or below it
+			return root_once();
 		if (cs <= 8) { // a small branch: its hi0 values share a cache line or two
 			uint32_t m = NIL;
 			for (uint32_t k = c; k < c + cs; k++)
@@ -210,10 +225,9 @@ __device__ __forceinline__ void capping_of(uint32_t v, const uint32_t *__restric
 	};
 	// one sweep over the children: the first child that attains the minimum (hi_child), and the first two children
 	// whose hi lies above v in the tree -- hi_2 belongs to the first of them that is not hi_child
-	uint32_t hi_1 = NIL, hi_child = NIL, lt_c[2] = {NIL, NIL}, lt_h[2] = {NIL, NIL};
+	uint32_t hi_1 = NIL, hi_child = NIL, lt_c0 = NIL, lt_c1 = NIL, lt_h0 = NIL, lt_h1 = NIL;
 	uint32_t second = NIL; // the second smallest hi over the children, with multiplicity: what hi_2 "should" be
-	for (uint32_t c = v + 1; c < end; c += max(gsize[c], 1u)) {
-		const uint32_t h = hi_of(c);
+	auto take = [&](uint32_t c, uint32_t h) __attribute__((always_inline)) { // (three call sites: kept in registers only when inlined)
 		if (h < hi_1 || hi_child == NIL) {
 			second = hi_1;
 			hi_1 = h;
@@ -221,20 +235,55 @@ __device__ __forceinline__ void capping_of(uint32_t v, const uint32_t *__restric
 		} else {
 			second = min(second, h);
 		}
-		if (h < v) {
-			if (lt_c[0] == NIL)
-				lt_c[0] = c, lt_h[0] = h;
-			else if (lt_c[1] == NIL)
-				lt_c[1] = c, lt_h[1] = h;
+		// (as selects: written as branches, the four words ended up in scratch memory behind a selected address)
+		const bool f0 = h < v && lt_c0 == NIL, f1 = h < v && !f0 && lt_c1 == NIL;
+		lt_c0 = f0 ? c : lt_c0, lt_h0 = f0 ? h : lt_h0;
+		lt_c1 = f1 ? c : lt_c1, lt_h1 = f1 ? h : lt_h1;
+	};
+	// The first two children -- a branching vertex has them, and mostly no more -- without the chain child -> its size ->
+	// the records behind its subtree -> its hi0 words -> next child: ONE run of loads takes everything at v and at the
+	// first child that does not depend on the child's size (both sizes, hi0[v], the bit-rank record at the child, the eight
+	// hi0 words from the child on: a subtree of up to eight vertices needs no more), a second run the same at the second
+	// child, whose record is also the one the first child's subtree ends in.  The eight words are read whatever the
+	// subtree's size: they must lie inside hi0's hi0_words words, or the vertex goes through the loop below as a whole
+	// (the last few vertices of the tree space).  Further children: the loop, as before.
+	uint32_t c = v + 1, end, hv;
+	if (c + 8 <= hi0_words) {
+		uint32_t szv = gsize[v], g1 = gsize[c];
+		hv = hi0[v];
+		uint4 r1 = brec[c >> 6], a1 = load4_unaligned(hi0 + c), b1 = load4_unaligned(hi0 + c + 4);
+		landed(szv, hv, g1, r1, a1, b1);
+		end = v + szv;
+		const uint32_t cs1 = max(g1, 1u), c2 = c + cs1; // c2 < end <= T: the list holds vertices with a second child only (k_hi_simp)
+		if (c2 + 8 <= hi0_words) {
+			uint32_t g2 = gsize[c2];
+			uint4 r2 = brec[c2 >> 6], a2 = load4_unaligned(hi0 + c2), b2 = load4_unaligned(hi0 + c2 + 4);
+			landed(g2, r2, a2, b2);
+			const uint32_t cs2 = max(g2, 1u), c3 = c2 + cs2; // c3 <= end: its record exists (rank(T) is asked for)
+			// (mostly the record in hand.  Tied to registers first: the plain select became a flat load from a selected
+			// address, with the record in hand stored to scratch memory for it)
+			uint4 r3 = r2;
+			landed(r3);
+			if ((c3 >> 6) != (c2 >> 6))
+				r3 = brec[c3 >> 6];
+			const uint32_t k1 = bitrank_in(r1, c), k2 = bitrank_in(r2, c2), k3 = bitrank_in(r3, c3);
+			take(c, k2 != k1 ? root_once() : cs1 <= 8 ? min_of_first(a1, b1, cs1) : seg_min(segA, c, c2));
+			take(c2, k3 != k2 ? root_once() : cs2 <= 8 ? min_of_first(a2, b2, cs2) : seg_min(segA, c2, c3));
+			c = c3;
 		}
+	} else {
+		end = v + gsize[v];
+		hv = hi0[v];
 	}
-	const uint32_t hi_2 = lt_c[0] != hi_child ? lt_h[0] : lt_h[1];
+	for (; c < end; c += max(gsize[c], 1u))
+		take(c, hi_of(c));
+	const uint32_t hi_2 = lt_c0 != hi_child ? lt_h0 : lt_h1;
 	// The literal rule (first other child in idx order with hi < v, not the one reaching highest) can leave a capping
 	// edge that ends too early; only then can a bracket come back on top with MORE brackets under it than before.
 	// The black-edge-only class pass relies on that never happening (see run_parallel_dg), so say when it might.
 	if (hi_2 != (second < v ? second : NIL))
 		*literal_rule_seen = 1u;
-	if (hi_2 < hi0[v]) {
+	if (hi_2 < hv) {
 		cap_tgt[v] = hi_2;
 		capf[v] = 1;
 	}
@@ -302,11 +351,12 @@ __global__ void __launch_bounds__(TPB) k_hi_simp(uint32_t T, const uint32_t *__r
 }
 __global__ void k_capping(const uint32_t *__restrict__ n_list, const uint32_t *__restrict__ list, const uint32_t *__restrict__ gsize,
 			  const uint32_t *__restrict__ hi0, const uint4 *__restrict__ brec, const RootOf root_of, const SegTree segA,
-			  uint32_t *__restrict__ cap_tgt, uint8_t *__restrict__ capf, uint32_t *__restrict__ literal_rule_seen)
+			  uint32_t *__restrict__ cap_tgt, uint8_t *__restrict__ capf, uint32_t *__restrict__ literal_rule_seen,
+			  uint32_t hi0_words)
 {
 	const uint32_t n = *n_list; // (the count only exists on the device: grid-stride)
 	for (uint32_t i = BIDX * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-		capping_of(list[i], gsize, hi0, brec, root_of, segA, cap_tgt, capf, literal_rule_seen);
+		capping_of(list[i], gsize, hi0, brec, root_of, segA, cap_tgt, capf, literal_rule_seen, hi0_words);
 }
 // Bracket list order = (mirror pre-order of the source) and, inside one source, the later pushed
 // first: simplifying, capping, ordinary edges by descending creation idx (flubbles.cpp:608-643).
@@ -523,7 +573,7 @@ __global__ void k_top_bracket(uint32_t n, const uint32_t *__restrict__ gsize, co
 			      const PS psin, uint32_t *__restrict__ ckey, uint32_t *__restrict__ cval,
 			      uint32_t *__restrict__ lsz, uint32_t *__restrict__ err, const uint32_t *__restrict__ rid,
 			      uint32_t first_simp_id, uint8_t *__restrict__ hpf, const uint32_t *__restrict__ seg_comp,
-			      const uint32_t *__restrict__ c_ntree, const StackPlace sp)
+			      const uint32_t *__restrict__ c_ntree, const StackPlace sp, const LszField lf)
 {
 	const uint32_t q = BIDX * blockDim.x + threadIdx.x;
 	if (q >= n)
@@ -543,15 +593,18 @@ __global__ void k_top_bracket(uint32_t n, const uint32_t *__restrict__ gsize, co
 		return;
 	}
 	// BLACK: everything downstream lives in candidate-stack order, so the sort carries the entry's stack index and the
-	// entry itself (its tree vertex) is written here; lsz is indexed by stack position too
+	// entry itself (its tree vertex) is written here; lsz is indexed by stack position too -- and written only where the
+	// size does not fit the field the payload has for it (LszField, par_kernels.hpp)
 	uint32_t at = v;
 	if (BLACK) {
 		at = sp.soff[c] + (g - sp.voff[c]) + sp.shift[g];
 		sp.s_vtx[at] = v; // (its component is looked up where it is needed: StackComp)
 	}
-	cval[q] = at;
 	uint32_t m = mpre[v];
 	uint32_t lo = bstart.at(m), hi = bstart.at(m + sz);
+	// (The look-ups above and below were also tried as two batches ahead of the branch on the size -- mpre with gsize, then
+	// the four sums, from indices an empty slot may read too: 1.160 against 1.178 ms, below what two runs of one build
+	// differ by, and taken out again; profiles/class_payload_summary.md.)
 	// Number of live brackets first (two prefix sums): in a chain of bubbles the brackets of everything below v are closed
 	// inside their bubbles and the few live ones -- a simplifying edge, a tip's edge to the root -- come from the
 	// deepest sources, i.e. sit at the END of the range.  When the last `live` entries are all live they are THE live
@@ -583,10 +636,22 @@ __global__ void k_top_bracket(uint32_t n, const uint32_t *__restrict__ gsize, co
 	if (i == NIL) {
 		atomicAdd(&err[PW_NO_BRACKET], 1u); // cannot happen: every list holds at least a simplifying bracket
 		ckey[q] = NIL;
-		lsz[at] = 0;
+		cval[q] = at; // (nobody reads a payload or a list size behind a NIL key)
+		if (!BLACK)
+			lsz[at] = 0;
 		return;
 	}
-	lsz[at] = live;
+	if (BLACK) {
+		cval[q] = lf.pack(at, live);
+		if (live >= lf.lmax)
+			lsz[at] = live;
+		// (Saturated entries are NOT counted here.  One atomic add per wave that has any, on one word, was measured: with
+		// every entry saturated -- no field, 10^8 entries -- this kernel took 17.8 ms instead of 1.4.  Who wants the number
+		// counts it from the sorted payload afterwards: count_saturated.)
+	} else {
+		cval[q] = at;
+		lsz[at] = live;
+	}
 	ckey[q] = i;
 	if (hpf && rid[i] >= first_simp_id) // the top bracket is a simplifying edge (flubbles.cpp:644-656)
 		hpf[v] |= 2;
@@ -709,7 +774,7 @@ static constexpr uint32_t DF_OPENS = 1u, DF_SEEN = 2u;
 // classes as numbers; the debug hooks number them on demand (k_class_ids_black).
 __global__ void k_class_finish_black(uint32_t n, uint32_t S, const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sval,
 				     const uint32_t *__restrict__ lsz, uint8_t *__restrict__ flag, uint32_t *__restrict__ ns,
-				     uint32_t *__restrict__ prev, bool write_prev, uint8_t *__restrict__ dflag)
+				     uint32_t *__restrict__ prev, bool write_prev, uint8_t *__restrict__ dflag, const LszField lf)
 {
 	// prev is a word per entry at scattered addresses, and with exact classes all the walk asks of it is "is there one":
 	// that goes into bit 1 (DF_SEEN) of the flag byte written anyway.  Only the laminarity check reads the word itself.
@@ -722,6 +787,10 @@ __global__ void k_class_finish_black(uint32_t n, uint32_t S, const uint32_t *__r
 	if (q0 >= n)
 		return;
 	uint32_t K[6], U[6], L[6]; // positions q0 - 1 .. q0 + 4
+	// (the neighbours' words leave with the lane's own: unconditional loads from clamped indices -- 0 <= q0 - 1 or 0, and
+	// q0 + 4 or n - 1, all below n -- selected behind landed())
+	const uint32_t qa = q0 ? q0 - 1 : 0u, qz = min(q0 + 4, n - 1);
+	uint32_t ka = skey[qa], ua = sval[qa], kz = skey[qz], uz = sval[qz];
 	if (q0 + 4 <= n) {
 		const uint4 k4 = *reinterpret_cast<const uint4 *>(skey + q0), u4 = *reinterpret_cast<const uint4 *>(sval + q0);
 		K[1] = k4.x, K[2] = k4.y, K[3] = k4.z, K[4] = k4.w;
@@ -732,11 +801,33 @@ __global__ void k_class_finish_black(uint32_t n, uint32_t S, const uint32_t *__r
 			U[j] = q0 + j - 1 < n ? sval[q0 + j - 1] : 0u;
 		}
 	}
-	K[0] = q0 ? skey[q0 - 1] : NIL, U[0] = q0 ? sval[q0 - 1] : 0u;
-	K[5] = q0 + 4 < n ? skey[q0 + 4] : NIL, U[5] = q0 + 4 < n ? sval[q0 + 4] : 0u;
+	landed(ka, ua, kz, uz);
+	K[0] = q0 ? ka : NIL, U[0] = q0 ? ua : 0u;
+	K[5] = q0 + 4 < n ? kz : NIL, U[5] = q0 + 4 < n ? uz : 0u;
+	// The payload is the stack index under the list size (LszField); an invalid entry's payload is anything, and nothing
+	// of it is used.  A size that filled its field is looked up: all six of a lane in one batch, behind one test the whole
+	// wave agrees on -- in a chain of bubbles hardly a wave has one.  Two saturated neighbours compare their true sizes,
+	// and a saturated size (>= lmax) differs from every unsaturated one by itself.
+	bool sat[6], any_sat = false;
 #pragma unroll
-	for (int j = 0; j < 6; j++)
-		L[j] = K[j] != NIL ? lsz[U[j]] : 0u;
+	for (int j = 0; j < 6; j++) {
+		L[j] = K[j] != NIL ? lf.size(U[j]) : 0u;
+		U[j] = lf.index(U[j]);
+		sat[j] = K[j] != NIL && L[j] == lf.lmax;
+		any_sat |= sat[j];
+	}
+	if (__any(any_sat)) {
+		uint32_t t[6];
+		// (gather_if, common.hpp; safe: lsz[q0], next to nothing in particular but the lane's own and always there -- q0 <
+		// n <= V, and lsz has T + 2 > V words)
+#pragma unroll
+		for (int j = 0; j < 6; j++)
+			t[j] = gather_if(sat[j], lsz, U[j], q0);
+		landed(t[0], t[1], t[2], t[3], t[4], t[5]);
+#pragma unroll
+		for (int j = 0; j < 6; j++)
+			L[j] = sat[j] ? t[j] : L[j];
+	}
 	bool fresh[6];
 	fresh[0] = true;
 #pragma unroll
@@ -766,11 +857,23 @@ __global__ void k_class_finish_black(uint32_t n, uint32_t S, const uint32_t *__r
 	}
 }
 __global__ void k_class_ids_black(uint32_t n, const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sval,
-				  const uint8_t *__restrict__ fresh, const uint32_t *__restrict__ ps, uint32_t *__restrict__ s_cls)
+				  const uint8_t *__restrict__ fresh, const uint32_t *__restrict__ ps, uint32_t *__restrict__ s_cls,
+				  const LszField lf)
 {
 	uint32_t q = BIDX * blockDim.x + threadIdx.x;
 	if (q < n && skey[q] != NIL)
-		s_cls[sval[q]] = ps[q] + fresh[q] - 1; // inclusive scan - 1
+		s_cls[lf.index(sval[q])] = ps[q] + fresh[q] - 1; // inclusive scan - 1 (the payload: the stack index under the list size)
+}
+// Entries of the sorted order whose list size filled its field (debug hook after a BLACK pass).  One atomic add per wave from a
+// ballot, none when the wave has none; every lane of the workgroup gets here.
+__global__ void k_count_saturated(uint32_t n, const uint32_t *__restrict__ skey, const uint32_t *__restrict__ sval, const LszField lf,
+				  uint32_t *__restrict__ count)
+{
+	const uint32_t q = BIDX * blockDim.x + threadIdx.x;
+	const bool sat = q < n && skey[q] != NIL && lf.size(sval[q]) == lf.lmax;
+	const unsigned long long sm = __ballot(sat);
+	if (sm && (threadIdx.x & 63u) == 0)
+		atomicAdd(count, (uint32_t)__popcll(sm));
 }
 // classes of the black tree vertices back in T-space (debug hook after a BLACK pass)
 __global__ void k_cls_from_stack(uint32_t S, const uint32_t *__restrict__ s_vtx, const uint32_t *__restrict__ s_cls,
@@ -1409,6 +1512,9 @@ struct ClassPass {
 	// array, unless POVU_HIP_WORD_PREFIX (A/B hook, read per pass) says words: 1 = both, 2 = psin, 3 = the range starts
 	const int word_prefix;
 	const bool rec_ps, rec_bs;
+	// bits of the class sort's payload that carry the list size in a black-only pass (LszField, par_kernels.hpp), at most:
+	// POVU_HIP_LSZ_FIELD (A/B hook, read per pass) lowers the cap, 0 = the bare stack index and every size looked up
+	const unsigned lsz_cap;
 	bool black_only = false;	 // classes of the black tree edges only (place_brackets decides)
 	const RootOf root_of;
 	// ---- counts: ordinary / capping / simplifying back edges, all brackets, vertices that get a class
@@ -1428,7 +1534,8 @@ struct ClassPass {
 		  want_hp(sw_.hairpins != nullptr), lean(dense && !want_hp), narrow_oc(dense && pw_.narrow_ordcnt),
 		  narrow_sc(narrow_oc && pw_.narrow_srccnt), narrow_ic(narrow_sc && pw_.narrow_incnt),
 		  word_prefix(getenv("POVU_HIP_WORD_PREFIX") ? atoi(getenv("POVU_HIP_WORD_PREFIX")) : 0), rec_ps(narrow_ic && word_prefix != 1 && word_prefix != 2),
-		  rec_bs(narrow_sc && word_prefix != 1 && word_prefix != 3), root_of{lean ? nullptr : pw_.t_root, cs_.voff, C_},
+		  rec_bs(narrow_sc && word_prefix != 1 && word_prefix != 3),
+		  lsz_cap(getenv("POVU_HIP_LSZ_FIELD") ? (unsigned)std::min(std::max(atoi(getenv("POVU_HIP_LSZ_FIELD")), 0), (int)LSZ_FIELD_CAP) : LSZ_FIELD_CAP), root_of{lean ? nullptr : pw_.t_root, cs_.voff, C_},
 		  ntiles((T + BX_TILE - 1) / BX_TILE)
 	{
 	}
@@ -1527,7 +1634,7 @@ static void bridge_and_capping(ClassPass &P)
 	KLAUNCH(k_hi_simp, dim3((unsigned)(((size_t)T + HS_VERTS - 1) / HS_VERTS)), dim3(TPB), 0, s, T, pw.gsize, v.brec, v.simp, P.want_hp ? pw.hpf : nullptr, v.capf, v.br_list,
 		n_br);
 	KLAUNCH(k_capping, dim3(std::min<unsigned>(nblk(T / 8 + 1), 16384)), dim3(TPB), 0, s, n_br, v.br_list, pw.gsize, pw.hi0, v.brec, P.root_of,
-		pw.segA, pw.cap_tgt, v.capf, pw.err + PW_LITERAL_RULE);
+		pw.segA, pw.cap_tgt, v.capf, pw.err + PW_LITERAL_RULE, T + 2); // (hi0 is carved with T + 2 words: for_each_span)
 	// capping / simplifying vertices per tile of k_bracket_extra, scanned: [ntiles + 1] each, the totals in the last word
 	KLAUNCH(k_flag_tile_counts, dim3((ntiles + 1 + 15) / 16 + 1), dim3(TPB), 0, s, T, v.capf, v.simp, v.tcap, v.tsimp, ntiles);
 	scan_exclusive_u32_pair(v.tsimp, v.tsimp, (size_t)ntiles + 1, v.tcap, v.tcap, (size_t)ntiles + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
@@ -1660,9 +1767,11 @@ static void classes_black_only(ClassPass &P)
 	}
 	scan_inclusive_u32(sdl, v.shift_ps, (size_t)V + 1, pw.scan_tmp, pw.scan_tmp_bytes, s);
 	const StackPlace sp{cs.voff, pw.soff, v.shift_ps, pw.s_vtx};
+	// (a stack index is below S, the total of pw.soff, which the host had before the launch)
+	const LszField lf = pw.lsz_field = lsz_field(P.S, P.lsz_cap);
 	P.with_prefix_views([&](auto ps, auto bs) {
 		LAUNCH((k_top_bracket<true, decltype(ps), decltype(bs)>), NC, s, NC, pw.gsize, pw.gpar, pw.mpre, bs, pw.segB, pw.tgtR, ps, v.ck,
-		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, nullptr, cs.ckey, P.sw.c_ntree, sp);
+		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, nullptr, cs.ckey, P.sw.c_ntree, sp, lf);
 	});
 	sort_pairs_u32(v.ck, v.ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)P.NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
 	// invalid entries carry NIL; after the sort on the low bits they sit behind every valid key
@@ -1671,7 +1780,7 @@ static void classes_black_only(ClassPass &P)
 	// (the class flags are worked out by the same kernel: invalid entries carry NIL and sort behind every valid key)
 	// (black_only: the literal hi_2 rule did not fire, so the laminarity check -- prev's one reader -- runs only on request)
 	LAUNCH(k_class_finish_black, std::max<size_t>(((size_t)NC + 3) / 4, 1), s, NC, P.S, v.ck2, pw.vals_t2, pw.lsz, v.cflag, pw.ns, pw.prev,
-	       pw.check_laminar, v.dflag);
+	       pw.check_laminar, v.dflag, lf);
 	P.tm.end(1);
 	P.tm.begin("par_next_seen"); // (folded into the kernel above)
 	P.tm.end(0);
@@ -1689,9 +1798,10 @@ static void classes_all_vertices(ClassPass &P)
 	hipStream_t s = P.s;
 	const uint32_t V = P.V, T = P.T, NC = P.NC;
 	const StackPlace none{nullptr, nullptr, nullptr, nullptr};
+	pw.lsz_field = LszField{0, 32, 0}; // (no field: the size of every vertex's list goes through lsz)
 	P.with_prefix_views([&](auto ps, auto bs) {
 		LAUNCH((k_top_bracket<false, decltype(ps), decltype(bs)>), NC, s, NC, pw.gsize, pw.gpar, pw.mpre, bs, pw.segB, pw.tgtR, ps, v.ck,
-		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, P.want_hp ? pw.hpf : nullptr, nullptr, nullptr, none);
+		       pw.vals_t, pw.lsz, pw.err, pw.b_val2, P.NB0 + P.ncap, P.want_hp ? pw.hpf : nullptr, nullptr, nullptr, none, pw.lsz_field);
 	});
 	sort_pairs_u32(v.ck, v.ck2, pw.vals_t, pw.vals_t2, NC, bits_for((uint64_t)P.NB + 1), pw.sort_tmp, pw.sort_tmp_bytes, s);
 	LAUNCH(k_class_flags<false>, std::max<size_t>(NC, (size_t)V + 2), s, NC, V, v.ck2, pw.vals_t2, pw.lsz, sw.t_flags, v.cflag, pw.dlt,
@@ -1903,8 +2013,17 @@ static void stack_class_ids(ParWs &pw, hipStream_t s)
 	const uint32_t V = pw.V;
 	const ClassViews v = class_views(pw);
 	scan_exclusive_u8(v.cflag, v.cps, (size_t)V + 1, nullptr, nullptr, 0, pw.scan_tmp, pw.scan_tmp_bytes, s);
-	LAUNCH(k_class_ids_black, V, s, V, v.ck2, pw.vals_t2, v.cflag, v.cps, pw.s_cls);
+	LAUNCH(k_class_ids_black, V, s, V, v.ck2, pw.vals_t2, v.cflag, v.cps, pw.s_cls, pw.lsz_field);
 	pw.s_cls_valid = true;
+}
+uint32_t count_saturated(ParWs &pw, hipStream_t s)
+{
+	if (!pw.black_only_used)
+		return 0;
+	const ClassViews v = class_views(pw);
+	HIP_CHECK(hipMemsetAsync(pw.err + PW_LSZ_SAT, 0, 4, s));
+	LAUNCH(k_count_saturated, pw.V, s, pw.V, v.ck2, pw.vals_t2, pw.lsz_field, pw.err + PW_LSZ_SAT);
+	return pw.host->read_u32(pw.err + PW_LSZ_SAT, s);
 }
 void classes_to_tree_space(ParWs &pw, hipStream_t s)
 {

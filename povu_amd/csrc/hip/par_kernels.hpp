@@ -45,8 +45,41 @@ enum PassWord : uint32_t {
 	PW_N_CROSSED = 12,   // k_resolve_crossings: crossings resolved in place -> povu_hip_last_crossings
 	PW_RANK_OVF = 13,    // rank_events (list_rank.hip, the pre-order ranking): records whose partial sum left its 16 bits (its fallback kernel)
 	PW_INCNT_OVF = 14,   // k_bracket_extra: a byte of incnt8 would have passed 255 -> the host (place_brackets: the pass is repeated with words)
-	PASS_WORDS = 16	     // words carved and cleared (1, 3, 15: unused)
+	PW_LSZ_SAT = 15,     // k_count_saturated (on demand, behind the pass): stack entries whose list size did not fit the payload's field (LszField) -> povu_hip_last_lsz_field
+	PASS_WORDS = 16	     // words carved and cleared (1, 3: unused)
 };
+
+// The payload of the black-only class sort: the stack index of an entry in the low `abits` bits and, above them, the size of
+// its bracket list in `w` bits, saturating at lmax.  A size below lmax is all a reader needs; a saturated one (>= lmax) is
+// looked up in ParWs::lsz, which k_top_bracket<true> writes for those entries only.  The sort looks at key bits and is
+// stable, so the payload is opaque to it.  w = the bits a stack index below S leaves free, at most `cap`; w = 0 (lmax = 0):
+// every entry is saturated and the payload is the bare index -- the form every pass had before, so no graph is refused.
+struct LszField {
+	unsigned w, abits; // abits = 32 - w >= 24
+	uint32_t lmax;	   // 2^w - 1
+	__host__ __device__ constexpr uint32_t mask() const { return 0xFFFFFFFFu >> w; }
+	// (two shifts: abits = 32 must give 0, and a shift by the full width is undefined)
+	__host__ __device__ constexpr uint32_t pack(uint32_t at, uint32_t live) const { return at | (((live < lmax ? live : lmax) << 1) << (abits - 1)); }
+	__host__ __device__ constexpr uint32_t index(uint32_t u) const { return u & mask(); }
+	__host__ __device__ constexpr uint32_t size(uint32_t u) const { return (u >> 1) >> (abits - 1); }
+};
+static constexpr unsigned LSZ_FIELD_CAP = 8;
+constexpr LszField lsz_field(uint64_t S, unsigned cap = LSZ_FIELD_CAP)
+{
+	unsigned b = 1; // bits_for(S), common.hpp
+	while (b < 32 && (uint64_t(1) << b) <= S)
+		b++;
+	const unsigned w = 32 - b < cap ? 32 - b : cap;
+	return LszField{w, 32 - w, (uint32_t(1) << w) - 1};
+}
+static_assert(lsz_field(1).w == 8 && lsz_field(1).abits == 24 && lsz_field(1).lmax == 255, "the cap");
+static_assert(lsz_field((1u << 24) - 1).w == 8 && lsz_field(1u << 24).w == 7 && lsz_field(1u << 24).abits == 25, "S = 2^24");
+static_assert(lsz_field((1u << 27) - 1).w == 5 && lsz_field(1u << 27).w == 4 && lsz_field(1u << 27).lmax == 15, "S = 2^27 - 1, 2^27");
+static_assert(lsz_field(1u << 29).w == 2 && lsz_field(1u << 29).mask() == 0x3FFFFFFFu, "S = 2^29");
+static_assert(lsz_field(0xFFFFFFFFull).w == 0 && lsz_field(0xFFFFFFFFull).lmax == 0 && lsz_field(0xFFFFFFFFull).mask() == 0xFFFFFFFFu, "S = 2^32 - 1: no field");
+static_assert(lsz_field(0xFFFFFFFFull).pack(0xFFFFFFFEu, 7) == 0xFFFFFFFEu && lsz_field(0xFFFFFFFFull).size(0xFFFFFFFEu) == 0, "no field: the bare index");
+static_assert(lsz_field(1u << 24, 3).w == 3 && lsz_field(1u << 29, 3).w == 2 && lsz_field(5, 0).w == 0, "a lower cap");
+static_assert(lsz_field(1u << 27).pack((1u << 27) - 1, 99) == 0xF7FFFFFFu && lsz_field(1u << 27).index(0xF7FFFFFFu) == (1u << 27) - 1 && lsz_field(1u << 27).size(0xF7FFFFFFu) == 15, "the largest index under a saturated size");
 
 // One more bracket ends at tree vertex t; returns the count in front of it.  A byte is incremented by a 32-bit atomic add of
 // 1 << 8 (t & 3) on its aligned word (ParWs::incnt8 is 16-byte aligned): no carry leaves a byte that stays below 256.
@@ -88,6 +121,7 @@ struct ParWs {
 	bool laminar_checked = false;	 // out: the last pass ran it
 	bool black_only_used = false;	 // out: the last pass numbered the classes of the black tree edges only
 	int prefix_records = 0;		 // out: it read count records (common.hpp) for: bit 0 psin, bit 1 the bracket range starts
+	LszField lsz_field{0, 32, 0};	 // out: the payload format of the last black-only class sort (w = 0 also behind an all-vertices pass)
 	bool s_cls_valid = false;	 // s_cls holds class ids (a black-only pass numbers its classes only when a debug hook asks)
 	bool gcls_valid = false;	 // gcls holds the classes in T-space (a black-only pass keeps them in stack order only)
 	// T-space (global tree vertex idx)
@@ -213,6 +247,9 @@ void run_parallel_hairpins(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C
 // debug hooks (and the sequential kernels) use; not needed by the pass itself.
 // debug hook after a black-only pass: the classes of the black tree vertices into pw.gcls (NIL elsewhere)
 void classes_to_tree_space(ParWs &pw, hipStream_t s);
+// debug hook after a black-only pass: the stack entries whose list size filled the payload's field (LszField), counted from the
+// sorted order the pass left behind into pw.err[PW_LSZ_SAT]; 0 behind any other pass
+uint32_t count_saturated(ParWs &pw, hipStream_t s);
 void export_parallel_stack(const CompState &cs, SeqWs &sw, ParWs &pw, hipStream_t s);
 
 // One launch that writes the outcome of a pass into page-locked host memory (PassSummary::words(C) words, read through

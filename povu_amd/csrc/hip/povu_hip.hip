@@ -1697,6 +1697,25 @@ extern "C" int povu_hip_last_crossings(povu_hip_ctx *ctx, uint32_t out[2])
 	return hipMemcpy(out, ctx->pw.err + PW_N_X, 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
 }
 
+extern "C" int povu_hip_last_lsz_field(povu_hip_ctx *ctx, uint32_t out[2])
+{
+	if (!ctx || !out)
+		return 1;
+	out[0] = out[1] = 0;
+	if (!ctx->last.valid || ctx->last.plan.all_seq || !ctx->pw.black_only_used)
+		return 0;
+	ctx->quiesce();
+	if (hipSetDevice(ctx->device) != hipSuccess)
+		return 2;
+	try {
+		out[0] = ctx->pw.lsz_field.w;
+		out[1] = count_saturated(ctx->pw, ctx->stream);
+	} catch (const std::exception &) {
+		return 2;
+	}
+	return 0;
+}
+
 extern "C" int povu_hip_last_laminar_check_ran(const povu_hip_ctx *ctx)
 {
 	return ctx && ctx->last.valid && !ctx->last.plan.all_seq && ctx->pw.laminar_checked ? 1 : 0;

@@ -494,6 +494,8 @@ def load_lib():
     l.povu_hip_last_black_only_classes.argtypes = [C.c_void_p]
     l.povu_hip_last_crossings.restype = C.c_int
     l.povu_hip_last_crossings.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    l.povu_hip_last_lsz_field.restype = C.c_int
+    l.povu_hip_last_lsz_field.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     l.povu_hip_last_laminar_check_ran.restype = C.c_int
     l.povu_hip_last_laminar_check_ran.argtypes = [C.c_void_p]
     l.povu_hip_debug_edge_ids.restype = C.c_int
@@ -2076,6 +2078,15 @@ class HipDecomposer:
         o = (C.c_uint32 * 2)()
         if self._lib.povu_hip_last_crossings(self._ctx, o) != 0:
             raise RuntimeError("povu_hip_last_crossings failed")
+        return int(o[0]), int(o[1])
+
+    def last_lsz_field(self):
+        """(bits, saturated) of the last black-only class pass: the bits of the class sort's payload that carried an entry's
+        bracket-list size (POVU_HIP_LSZ_FIELD in the environment caps them, 0 = none), and the candidate-stack entries whose
+        size did not fit (>= 2^bits - 1) and was looked up instead (povu_hip_last_lsz_field); (0, 0) behind any other pass."""
+        o = (C.c_uint32 * 2)()
+        if self._lib.povu_hip_last_lsz_field(self._ctx, o) != 0:
+            raise RuntimeError("povu_hip_last_lsz_field failed")
         return int(o[0]), int(o[1])
 
     def last_laminar_check_ran(self) -> bool:
