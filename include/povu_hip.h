@@ -1103,6 +1103,10 @@ int povu_hip_debug_edge_ids(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n_tree, 
  * did not run), out[2] = entries the wave walks' stacks took from their pool (the sum of their chunk sizes).  Read-only:
  * adds nothing to a pass.  Returns 3 / 4 like povu_hip_debug_edge_ids. */
 int povu_hip_debug_walk_words(povu_hip_ctx *ctx, uint32_t out[3]);
+/* the children-vector pool of the last pass's splice (POVU_HIP_F_SUBFLUBBLES), component `comp`: out[0] = slots the vectors
+ * took, out[1] = slots the layout gave the component.  Read-only: adds no launch, copy or synchronisation to a pass.
+ * Returns 3 when the last pass ran without the inserting passes, 5 when it had no component `comp`. */
+int povu_hip_debug_splice_pool(povu_hip_ctx *ctx, uint32_t comp, uint32_t out[2]);
 /* candidate stack of component `comp`: tree vertex of each entry, class, next_seen */
 int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t *tree_vtx, uint32_t *cls,
 			 uint32_t *next_seen);

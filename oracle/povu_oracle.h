@@ -133,6 +133,9 @@ char *orc_subflubbles_text(const orc_tree *t, orc_pvst *p, size_t *len);
  * target), children moved under one, reads of the stale tail in smothered::nest, depth[] of an invalid index, self-loop
  * targets pushed by compute_LoA, override_ji_trunk answers */
 void orc_sub_stats(uint64_t *out, int reset);
+/* how wide the children vectors were where those passes copy or walk one, since the last reset: out[69], laid out as the
+ * SW_ enums of povu_oracle_sub.inc say (tests/splice_width_cases.py names the words).  Does not change any output. */
+void orc_sub_widths(uint64_t *out, int reset);
 
 /* which rule decided, counted since the last reset (tests: does the fuzz reach every rule?): out[11] = leaves whose Y is
  * empty, tiny by a bracket to ai, tiny by an ordinary / a capping-or-simplifying back-edge INDEX equal to ai, parallel by

@@ -54,6 +54,109 @@ void orc_sub_stats(uint64_t *out, int reset)
 		memset(g_sub_stats, 0, sizeof g_sub_stats);
 }
 
+/* how WIDE the children vectors were where the reference copies or walks one, since the last orc_sub_widths(reset): what
+ * the tests of the device's splice (one wave per flubble, 64 children a round) need to know of an input.  "max" words hold
+ * the greatest value seen, "calls" words count calls, "sum" words add up; an index or a round is stored + 1 (0 = never).
+ * Per nesting kind NK_* (SW_NK words each, kind-major):
+ *   copy_len   max   length of the copied vector the nesting runs over
+ *   movers     max   children that leave in one call;     stayers  max  children that stay
+ *   mover_ge64 calls with a mover at index >= 64 of the copy
+ *   stay_behind_ge64 calls with a stayer at index >= 64 behind a mover (write cursor != read index in a later round)
+ *   mixed_round calls where one round of 64 holds movers and stayers
+ *   mover_idx  max   index + 1 of a mover;   stay_behind_idx  max  index + 1 of a stayer behind a mover
+ *   mixed_rnd  max   round + 1 that holds movers and stayers
+ *   tail_movers calls over more than 64 children whose last round holds movers only
+ *   reserve_copy max entries the destination's vector holds when a round's movers do not fit and it is copied, under the
+ *              device's rule (room for the round's movers at once, capacity doubling from 4); 0 for the z-side trunk
+ *              nesting, which pushes into the children instead
+ *   stay_behind_n max stayers at an index >= 64 behind a mover in one call
+ * then the scalar words SW_PUSH_LEN .. (see the enum). */
+enum { NK_AI_TRUNK, NK_AI_BRANCH, NK_ZI_TRUNK, NK_MIDI, NK_N };
+enum { SWK_COPY_LEN, SWK_MOVERS, SWK_STAYERS, SWK_MOVER_GE64, SWK_STAY_BEHIND_GE64, SWK_MIXED_ROUND, SWK_MOVER_IDX, SWK_STAY_BEHIND_IDX,
+       SWK_MIXED_RND, SWK_TAIL_MOVERS, SWK_RESERVE_COPY, SWK_STAY_BEHIND_N, SW_NK };
+enum { SW_PUSH_LEN = NK_N * SW_NK, /* max length of a vector at a push onto it */
+       SW_PUSH_FULL_F,	    /* max length of a FULL vector at a push, by the device's rule (capacity = seeded length, then doubling from 4): */
+       SW_PUSH_FULL_C,	    /*   of a find_flubbles vertex, a concealed, a smothered one (the pushes of a nesting's movers */
+       SW_PUSH_FULL_S,	    /*   under a new vertex are counted by reserve_copy instead) */
+       SW_FIRST_PUSH_SEEDED, /* max length of a seeded vector at the first push onto it */
+       SW_MIDI_FIRST_IDX, SW_MIDI_SECOND_IDX, /* find_midi: max index + 1 of the first / second trunk concealed child */
+       SW_MIDI_NTRUNK,	    /* max trunk concealed children of one flubble */
+       SW_MIDI_SPLIT_ROUNDS, /* calls: the first two in different rounds of 64 */
+       SW_MIDI_THIRD_LATER,  /* calls: a third one in a later round than the first two */
+       SW_MIDI_FIND_LEN,	    /* max length of a vector find_midi walks */
+       SW_SMO_OLD_END, SW_SMO_ERASURES, SW_SMO_STALE, /* smothered::nest: max old_end, erasures and stale reads in one call */
+       SW_CN_PER_FLUBBLE, SW_SMO_PER_CN, /* max concealed records of a flubble, smothered records of a concealed vertex */
+       SW_PINNED_WIDE, SW_PINNED_LEN,	  /* nest_over_pinned: calls over >= 64 children, max length */
+       SW_CN_LIST,	    /* sum: flubbles with records of their own or a pinned vertex pushed in (the device's first list) */
+       SW_N_CONCEALED, SW_N_SMO_CN, /* sum: concealed vertices; those with smothered records */
+       SW_N };
+static uint64_t g_sub_w[SW_N];
+static void sw_max(int i, uint64_t v)
+{
+	uint64_t o = __atomic_load_n(&g_sub_w[i], __ATOMIC_RELAXED);
+	while (o < v && !__atomic_compare_exchange_n(&g_sub_w[i], &o, v, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED))
+		;
+}
+#define SW_ADD(i, v) ((void)__atomic_fetch_add(&g_sub_w[i], (uint64_t)(v), __ATOMIC_RELAXED))
+void orc_sub_widths(uint64_t *out, int reset)
+{
+	if (out)
+		memcpy(out, g_sub_w, sizeof g_sub_w);
+	if (reset)
+		memset(g_sub_w, 0, sizeof g_sub_w);
+}
+/* one nesting: moved[k] says whether child k of the copy left */
+static void sw_nesting(int kind, const uint8_t *moved, uint32_t nch)
+{
+	const int b = kind * SW_NK;
+	uint32_t nm = 0, first_m = NIL, dn = 0, dcap = 0, n_behind = 0;
+	int ge64 = 0, behind = 0, mixed = 0;
+	sw_max(b + SWK_COPY_LEN, nch);
+	for (uint32_t r0 = 0; r0 < nch; r0 += 64) {
+		uint32_t m = 0, st = 0;
+		for (uint32_t k = r0; k < nch && k < r0 + 64; k++) {
+			if (moved[k]) {
+				m++;
+				if (first_m == NIL)
+					first_m = k;
+				if (k >= 64)
+					ge64 = 1;
+				sw_max(b + SWK_MOVER_IDX, (uint64_t)k + 1);
+			} else {
+				st++;
+				if (first_m != NIL) {
+					sw_max(b + SWK_STAY_BEHIND_IDX, (uint64_t)k + 1);
+					if (k >= 64)
+						behind = 1, n_behind++;
+				}
+			}
+		}
+		if (m && st) {
+			mixed = 1;
+			sw_max(b + SWK_MIXED_RND, (uint64_t)r0 / 64 + 1);
+		}
+		if (m && !st && r0 + 64 >= nch && nch > 64)
+			SW_ADD(b + SWK_TAIL_MOVERS, 1);
+		if (m && kind != NK_ZI_TRUNK) { /* Splice::reserve(dest, m) of the device */
+			if (dn + m > dcap) {
+				sw_max(b + SWK_RESERVE_COPY, dn);
+				if (!dcap)
+					dcap = 4;
+				while (dcap < dn + m)
+					dcap *= 2;
+			}
+			dn += m;
+		}
+		nm += m;
+	}
+	sw_max(b + SWK_MOVERS, nm);
+	sw_max(b + SWK_STAYERS, nch - nm);
+	sw_max(b + SWK_STAY_BEHIND_N, n_behind);
+	SW_ADD(b + SWK_MOVER_GE64, ge64);
+	SW_ADD(b + SWK_STAY_BEHIND_GE64, behind);
+	SW_ADD(b + SWK_MIXED_ROUND, mixed);
+}
+
 /* ---- gen_tree_meta beyond the bracket table: depth (tree_utils.cpp:576-598), lo (:224-273), LCA (:330-475) */
 typedef struct {
 	tree_meta m;
@@ -222,6 +325,8 @@ typedef struct {
 	uint8_t cnb_or;
 	uint32_t b_up, b_lo; /* bounds_t of a concealed / smothered vertex; g / s PVST idx of a midi bubble */
 	uint32_t *ch, nch, cap;
+	uint32_t dcap;	/* orc_sub_widths only: the capacity the device's vector has (seeded length, then doubling from 4) */
+	uint8_t seeded; /* ... and whether it still is the seeded one */
 } svtx;
 typedef struct {
 	svtx *v;
@@ -239,11 +344,24 @@ static uint32_t sp_add_vertex(spvst *p, const svtx *x)
 	p->v[p->n] = *x;
 	p->v[p->n].ch = NULL;
 	p->v[p->n].nch = p->v[p->n].cap = 0;
+	p->v[p->n].dcap = 0;
+	p->v[p->n].seeded = 0;
 	return p->n++;
 }
-static void sp_add_edge(spvst *p, uint32_t parent, uint32_t child)
+static void sp_add_edge_w(spvst *p, uint32_t parent, uint32_t child, int counted)
 {
 	svtx *v = &p->v[parent];
+	if (counted)
+		sw_max(SW_PUSH_LEN, v->nch);
+	if (v->nch == v->dcap) { /* (the device's vector is full: it moves) */
+		if (counted) {
+			sw_max(v->fam == 'C' ? SW_PUSH_FULL_C : v->fam == 'S' ? SW_PUSH_FULL_S : SW_PUSH_FULL_F, v->nch);
+			if (v->seeded)
+				sw_max(SW_FIRST_PUSH_SEEDED, v->nch);
+		}
+		v->dcap = v->dcap ? 2 * v->dcap : 4;
+	}
+	v->seeded = 0;
 	if (v->nch == v->cap) {
 		v->cap = v->cap ? 2 * v->cap : 4;
 		v->ch = realloc(v->ch, (size_t)v->cap * 4);
@@ -252,6 +370,9 @@ static void sp_add_edge(spvst *p, uint32_t parent, uint32_t child)
 	}
 	v->ch[v->nch++] = child;
 }
+static void sp_add_edge(spvst *p, uint32_t parent, uint32_t child) { sp_add_edge_w(p, parent, child, 1); }
+/* a nesting's mover goes under the new vertex: the device reserves room for a round's movers at once (sw_nesting counts it) */
+static void sp_add_edge_moved(spvst *p, uint32_t parent, uint32_t child) { sp_add_edge_w(p, parent, child, 0); }
 static void sp_del_edge(spvst *p, uint32_t parent, uint32_t child)
 {
 	svtx *v = &p->v[parent];
@@ -610,9 +731,15 @@ static void sub_find_concealed(const orc_tree *t, const sub_meta *s, spvst *p)
 		}
 		fls[nf++] = (fl_sls){f, m, n, first, n_ai, all.n - first - n_ai};
 	}
+	uint8_t *listed = xcalloc((size_t)n0 + 1, 1); /* (orc_sub_widths: has records or takes a pinned vertex in) */
+	for (uint32_t q = 0; q < nf; q++)
+		listed[fls[q].fl] = 1;
+	SW_ADD(SW_CN_LIST, nf);
+	SW_ADD(SW_N_CONCEALED, all.n);
 	for (uint32_t q = 0; q < nf; q++) {
 		const fl_sls *F = &fls[q];
 		const uint32_t f = F->fl, ai = p->v[f].ai, zi = p->v[f].zi;
+		sw_max(SW_CN_PER_FLUBBLE, F->n_ai + F->n_zi);
 		const int is_leaf = f < t->n && n_children(s, f) == 0; /* (sic) the SPANNING TREE's vertex f, concealed.cpp:1188 */
 		const uint32_t own0 = p->n; /* f's own concealed vertices from here on: one in [n0, own0) was pushed by its parent */
 		for (uint32_t k = 0; k < F->n_ai + F->n_zi; k++) {
@@ -634,8 +761,11 @@ static void sub_find_concealed(const orc_tree *t, const sub_meta *s, spvst *p)
 				for (uint32_t c_k = 0; c_k < nch; c_k++)
 					if (ch[c_k] >= n0 && ch[c_k] < own0) {
 						SS_INC(SS_NEST_OVER_PINNED);
+						sw_max(SW_PINNED_LEN, nch);
+						SW_ADD(SW_PINNED_WIDE, nch >= 64);
 						break;
 					}
+			uint8_t *moved = xcalloc((size_t)nch + 1, 1);
 			for (uint32_t c_k = 0; c_k < nch; c_k++) {
 				const uint32_t c = ch[c_k];
 				if (!fl_like(p->v[c].fam))
@@ -644,8 +774,9 @@ static void sub_find_concealed(const orc_tree *t, const sub_meta *s, spvst *p)
 				if (x->loc == CL_AI_TRUNK) { /* nest_trunk_ai, :945-979 */
 					if (s->depth[x->sl_st] > s->depth[c_zi] || st_is_desc(t, x->sl_st, c_ai)) {
 						SS_INC(SS_NEST_TRUNK_AI);
+						moved[c_k] = 1;
 						sp_del_edge(p, f, c);
-						sp_add_edge(p, sl_v, c);
+						sp_add_edge_moved(p, sl_v, c);
 					}
 				} else if (x->loc == CL_AI_BRANCH && k < F->n_ai) { /* nest_branch_ai, :984-1034 */
 					int has_br = 0; /* a bracket of c's zi that STARTS at ai (sic: get_src, :1006) */
@@ -653,21 +784,31 @@ static void sub_find_concealed(const orc_tree *t, const sub_meta *s, spvst *p)
 						has_br = t->be_src[s->m.be[b]] == ai;
 					if (st_is_desc(t, x->sl_st, c_ai) && has_br) {
 						SS_INC(SS_NEST_BRANCH_AI);
+						moved[c_k] = 1;
 						sp_del_edge(p, f, c);
-						sp_add_edge(p, sl_v, c);
+						sp_add_edge_moved(p, sl_v, c);
 					}
 				} else if (x->loc == CL_ZI_TRUNK) { /* nest_trunk_zi, :1054-1081: (sic) the edge goes from the child to the slubble */
 					if (st_is_desc(t, F->n, c_ai) && !st_is_desc(t, zi, c_zi)) {
 						SS_INC(SS_NEST_TRUNK_ZI);
+						moved[c_k] = 1;
+						if (c < n0 && !listed[c]) {
+							listed[c] = 1;
+							SW_ADD(SW_CN_LIST, 1);
+						}
 						sp_del_edge(p, f, c);
 						sp_add_edge(p, c, sl_v);
 					}
 				}
 				/* zi_branch: add_conc_zi asks for ai_branch (:1134) and ends in "sl type: unknown" */
 			}
+			if (x->loc != CL_ZI_BRANCH)
+				sw_nesting(x->loc == CL_AI_TRUNK ? NK_AI_TRUNK : x->loc == CL_AI_BRANCH ? NK_AI_BRANCH : NK_ZI_TRUNK, moved, nch);
+			free(moved);
 			free(ch);
 		}
 	}
+	free(listed);
 	free(all.x);
 	free(fls);
 }
@@ -684,7 +825,8 @@ static void sub_find_midi(const orc_tree *t, const sub_meta *s, spvst *p)
 	for (uint32_t f = 0; f < n0; f++) {
 		if (p->v[f].fam != 'F')
 			continue;
-		uint32_t n_cn = 0, trunk[2] = {NIL, NIL}, n_trunk = 0;
+		uint32_t n_cn = 0, trunk[2] = {NIL, NIL}, n_trunk = 0, at[2] = {0, 0};
+		int third_later = 0;
 		const uint32_t zi = p->v[f].zi;
 		for (uint32_t k = 0; k < p->v[f].nch; k++) {
 			const uint32_t c = p->v[f].ch[k];
@@ -693,10 +835,23 @@ static void sub_find_midi(const orc_tree *t, const sub_meta *s, spvst *p)
 			n_cn++;
 			if (p->v[c].sl_st < zi) { /* in_trunk, :163-166 */
 				if (n_trunk < 2)
-					trunk[n_trunk] = c;
+					trunk[n_trunk] = c, at[n_trunk] = k;
+				else if (k / 64 > at[1] / 64)
+					third_later = 1;
 				n_trunk++;
 			}
 			/* else: the branch case -- undefined in the reference, nothing here (see the header) */
+		}
+		if (n_cn) { /* (the device looks at the flubbles that got a concealed child) */
+			sw_max(SW_MIDI_FIND_LEN, p->v[f].nch);
+			sw_max(SW_MIDI_NTRUNK, n_trunk);
+			if (n_trunk >= 1)
+				sw_max(SW_MIDI_FIRST_IDX, (uint64_t)at[0] + 1);
+			if (n_trunk >= 2) {
+				sw_max(SW_MIDI_SECOND_IDX, (uint64_t)at[1] + 1);
+				SW_ADD(SW_MIDI_SPLIT_ROUNDS, at[0] / 64 != at[1] / 64);
+			}
+			SW_ADD(SW_MIDI_THIRD_LATER, third_later);
 		}
 		if (n_cn < 2 || n_trunk != 2)
 			continue;
@@ -736,6 +891,7 @@ static void sub_find_midi(const orc_tree *t, const sub_meta *s, spvst *p)
 		nv.b_up = up, nv.b_lo = lo;
 		const uint32_t mv = sp_add_vertex(p, &nv);
 		sp_add_edge(p, f, mv);
+		uint8_t *moved = xcalloc((size_t)nch + 1, 1);
 		for (uint32_t k = 0; k < nch; k++) {
 			const uint32_t c = ch[k];
 			if (p->v[c].fam != 'F')
@@ -743,10 +899,13 @@ static void sub_find_midi(const orc_tree *t, const sub_meta *s, spvst *p)
 			/* (sic) spanning-tree depths at the PVST indices of the two concealed vertices */
 			if (sm_depth(t, s, up) < s->depth[p->v[c].ai] && sm_depth(t, s, lo) > s->depth[p->v[c].zi]) {
 				SS_INC(SS_MIDI_NEST);
+				moved[k] = 1;
 				sp_del_edge(p, f, c);
-				sp_add_edge(p, mv, c);
+				sp_add_edge_moved(p, mv, c);
 			}
 		}
+		sw_nesting(NK_MIDI, moved, nch);
+		free(moved);
 		free(ch);
 	}
 	free(ms);
@@ -934,8 +1093,12 @@ static void sub_find_smothered(const orc_tree *t, const sub_meta *s, spvst *p)
 		}
 	}
 	/* add_smothered, :349-383: the records are already grouped by concealed vertex, ascending */
-	for (uint32_t q = 0; q < all.n; q++) {
+	for (uint32_t q = 0, run = 0; q < all.n; q++) {
 		const uint32_t cv = all.x[q].cn;
+		run = q && all.x[q - 1].cn == cv ? run + 1 : 1;
+		sw_max(SW_SMO_PER_CN, run);
+		SW_ADD(SW_N_SMO_CN, run == 1);
+		uint32_t n_erased = 0, n_stale = 0;
 		const uint32_t sv = sp_add_vertex(p, &all.x[q].v);
 		sp_add_edge(p, cv, sv);
 		/* nest, :332-347: a range-for over children_v[cv] while del_edge erases from it -- as libstdc++ runs it */
@@ -943,8 +1106,10 @@ static void sub_find_smothered(const orc_tree *t, const sub_meta *s, spvst *p)
 		const uint32_t old_end = p->v[cv].nch;
 		for (uint32_t k = 0; k < old_end; k++) {
 			const uint32_t c = p->v[cv].ch[k]; /* (slots behind the live end hold what erase left there) */
-			if (k >= p->v[cv].nch)
+			if (k >= p->v[cv].nch) {
 				SS_INC(SS_SMO_STALE_READ);
+				n_stale++;
+			}
 			uint32_t c_up, c_lo;
 			if (fl_like(p->v[c].fam))
 				c_up = p->v[c].ai, c_lo = p->v[c].zi;
@@ -956,10 +1121,14 @@ static void sub_find_smothered(const orc_tree *t, const sub_meta *s, spvst *p)
 				continue; /* (a concealed child with an open bound never occurs: concealed vertices have no concealed children) */
 			if (st_is_desc(t, up, c_up) && st_is_desc(t, c_lo, lo)) {
 				SS_INC(SS_SMO_NEST);
+				n_erased++;
 				sp_del_edge(p, cv, c);
 				sp_add_edge(p, sv, c);
 			}
 		}
+		sw_max(SW_SMO_OLD_END, old_end);
+		sw_max(SW_SMO_ERASURES, n_erased);
+		sw_max(SW_SMO_STALE, n_stale);
 	}
 	free(all.x);
 }
@@ -984,7 +1153,9 @@ char *orc_subflubbles_text(const orc_tree *t, orc_pvst *pv, size_t *len)
 		sp_add_vertex(&p, &x);
 	}
 	for (uint32_t v = 1; v < pv->n; v++)
-		sp_add_edge(&p, pv->parent[v], v);
+		sp_add_edge_w(&p, pv->parent[v], v, 0);
+	for (uint32_t v = 0; v < p.n; v++) /* (orc_sub_widths: the device seeds every vector full) */
+		p.v[v].dcap = p.v[v].nch, p.v[v].seeded = 1;
 	sub_find_concealed(t, &s, &p);
 	sub_find_midi(t, &s, &p);
 	sub_find_smothered(t, &s, &p);

@@ -802,6 +802,32 @@ extern "C" int povu_hip_debug_walk_words(povu_hip_ctx *ctx, uint32_t out[3])
 	}
 }
 
+// how full the splice of the last -s pass left component comp's stretch of the children-vector pool: out[0] = slots taken
+// (ptop - poff), out[1] = slots it had (layout_splice's budget).  Read-only, no launch; the pass itself records two pointers.
+extern "C" int povu_hip_debug_splice_pool(povu_hip_ctx *ctx, uint32_t comp, uint32_t out[2])
+{
+	if (!ctx || !ctx->last.valid || !out)
+		return 1;
+	if (!ctx->last.plan.all_sub || !ctx->ws_sub.pool_off)
+		return 3; // the last pass ran no inserting passes
+	if (comp >= ctx->last.C || comp >= ctx->ws_sub.pool_comps)
+		return 5; // no such component
+	ctx->quiesce();
+	try {
+		HIP_CHECK(hipSetDevice(ctx->device));
+		uint32_t off[2] = {0, 0}, top = 0;
+		HIP_CHECK(hipMemcpy(off, ctx->ws_sub.pool_off + comp, 8, hipMemcpyDeviceToHost));
+		top = off[0];
+		if (ctx->ws_sub.pool_top)
+			HIP_CHECK(hipMemcpy(&top, ctx->ws_sub.pool_top + comp, 4, hipMemcpyDeviceToHost));
+		out[0] = top - off[0];
+		out[1] = off[1] - off[0];
+		return 0;
+	} catch (const std::exception &) {
+		return 2;
+	}
+}
+
 extern "C" int povu_hip_debug_stack(povu_hip_ctx *ctx, uint32_t comp, uint32_t *n, uint32_t *tree_vtx, uint32_t *cls,
 				    uint32_t *next_seen)
 {

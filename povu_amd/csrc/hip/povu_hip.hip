@@ -184,6 +184,7 @@ extern "C" int povu_hip_release_workspace(povu_hip_ctx *ctx)
 		if (kind == ARENA_WORKSPACE)
 			a.release();
 	});
+	ctx->ws_sub.release(); // (its arenas went above; this drops what it remembers of their contents)
 	return 0;
 }
 

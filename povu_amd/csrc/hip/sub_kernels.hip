@@ -1906,6 +1906,7 @@ struct SubPass {
 			HIP_CHECK(hipMemsetAsync(xs.counts, 0, 3 * (size_t)C * 4, s));
 		}
 		timer.mark("splice");
+		ar.pool_off = xs.poff, ar.pool_top = C && Q ? xs.ptop : nullptr, ar.pool_comps = C;
 		const uint32_t e = host.read_u32(tb.err, s);
 		if (e & E_POOL)
 			throw HipError("subflubble passes: the children vectors outgrew their pool (internal sizing bug)");
@@ -1984,6 +1985,8 @@ SubForest::~SubForest()
 void SubArenas::release()
 {
 	for_each_arena([](const char *, Arena &a) { a.release(); });
+	pool_off = pool_top = nullptr;
+	pool_comps = 0;
 }
 size_t SubArenas::capacity() const
 {
@@ -1996,6 +1999,8 @@ void run_subflubbles(const CompState &cs, const SeqWs &sw, const ParWs &pw, cons
 		     HostScratch &host, SubForest &out, const std::shared_ptr<::PinnedPool> &pool, hipStream_t s, SubArenas &arenas)
 {
 	SubPass p(cs, sw, pw, tw, ls, C, host, arenas, s);
+	arenas.pool_off = arenas.pool_top = nullptr; // (until this pass has spliced)
+	arenas.pool_comps = 0;
 	p.edge_tables_hi();
 	p.creation_keys_lo();
 	p.bracket_rows();

@@ -65,6 +65,11 @@ struct SubArenas {
 	void for_each_arena(F &&f) const { visit_arenas(*this, f); }
 	void release();
 	size_t capacity() const; // bytes held, all six together
+	// Where the last pass left the splice's pool layout in `xspace` (tests: povu_hip_debug_splice_pool reads how full each
+	// component's stretch got): poff[C + 1], and ptop[C] when the splice ran (null: no PVST vertex, nothing was pushed).
+	// Pointers into the arena, valid until the next pass carves or releases it.
+	const uint32_t *pool_off = nullptr, *pool_top = nullptr;
+	uint32_t pool_comps = 0;
 };
 
 // Runs find_concealed, find_midi and find_smothered on the state leaf_prepare / leaf_dense left (an all-parallel pass whose

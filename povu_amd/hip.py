@@ -502,6 +502,8 @@ def load_lib():
     l.povu_hip_debug_edge_ids.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]
     l.povu_hip_debug_walk_words.restype = C.c_int
     l.povu_hip_debug_walk_words.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    l.povu_hip_debug_splice_pool.restype = C.c_int
+    l.povu_hip_debug_splice_pool.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
     l.povu_hip_debug_stack.restype = C.c_int
     l.povu_hip_debug_stack.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
                                        C.c_void_p]
@@ -2112,6 +2114,16 @@ class HipDecomposer:
         if rc != 0:
             raise RuntimeError("no parallel-tree state" if rc in (3, 4) else "no decompose state")
         return dict(n_entry=int(o[0]), n_over=int(o[1]), pool_top=int(o[2]))
+
+    def debug_splice_pool(self, comp: int):
+        """(used, room) of component `comp` (0-based) in the children-vector pool of the last `-s` pass's splice
+        (povu_hip_debug_splice_pool)"""
+        o = (C.c_uint32 * 2)()
+        rc = self._lib.povu_hip_debug_splice_pool(self._ctx, comp, o)
+        if rc != 0:
+            raise RuntimeError("the last pass ran no inserting passes" if rc == 3 else
+                               f"the last pass had no component {comp}" if rc == 5 else "no decompose state")
+        return int(o[0]), int(o[1])
 
     def debug_stack(self, comp: int):
         n = C.c_uint32(0)
