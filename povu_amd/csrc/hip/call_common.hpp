@@ -167,14 +167,8 @@ __device__ __forceinline__ uint8_t ref_path_base(const PathsView &P, const uint6
 {
 	const uint64_t *__restrict__ off = roff + R.b;
 	const uint64_t target = off[0] + ci;
-	uint64_t lo = 0, hi = R.n - 1; // the first step that ends behind the base (steps of no base are passed over)
-	while (lo < hi) {
-		const uint64_t mid = (lo + hi) >> 1;
-		if (off[mid + 1] > target)
-			hi = mid;
-		else
-			lo = mid + 1;
-	}
+	// the first step that ends behind the base (steps of no base are passed over)
+	const uint64_t lo = first_not(uint64_t(0), R.n - 1, [=](uint64_t k) { return off[k + 1] <= target; });
 	const uint32_t x = P.steps[R.gs + lo];
 	*seg = x >> 1;
 	return path_step_base(P, x, target - off[lo]);

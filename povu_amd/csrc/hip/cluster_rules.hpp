@@ -4,6 +4,8 @@
 // and the leader loop over them.  Included by cluster_kernels.hip (the device functions), by host/vcf.cpp (the parser) and by
 // host/cluster_check.cpp, which runs all of it under the sanitizers.  There is no floating point in here.
 #pragma once
+#include "search_rules.hpp"
+
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -77,37 +79,12 @@ CL_HD bool prunable(uint64_t wa, uint64_t wr, uint32_t T, bool has_best, Frac be
 	return !similar(b, T) || (has_best && !better(b, best));
 }
 
-// first index of [lo, hi) whose key is at least / above s
-template <class Key>
-CL_HD uint32_t lower_key(const Key *key, uint32_t lo, uint32_t hi, Key s)
-{
-	while (lo < hi) {
-		const uint32_t mid = lo + (hi - lo) / 2;
-		if (key[mid] < s)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-template <class Key>
-CL_HD uint32_t upper_key(const Key *key, uint32_t lo, uint32_t hi, Key s)
-{
-	while (lo < hi) {
-		const uint32_t mid = lo + (hi - lo) / 2;
-		if (key[mid] <= s)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
 // key (s, o) of one bag, o its ordinal among the equal segments of its bag, counts towards I when the other bag holds s more
 // than o times
 template <class Key>
 CL_HD bool key_counts(const Key *other, uint32_t lo, uint32_t hi, Key s, uint32_t o)
 {
-	return upper_key(other, lo, hi, s) - lower_key(other, lo, hi, s) > o;
+	return povu_hip::upper_bound(other, lo, hi, s) - povu_hip::lower_bound(other, lo, hi, s) > o;
 }
 
 #if !defined(__HIP_DEVICE_COMPILE__)

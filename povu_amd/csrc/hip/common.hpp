@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "forest_wire.hpp"
+#include "search_rules.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -476,15 +477,19 @@ size_t scan_exclusive_u64_tmp(size_t n);
 
 // ---- scans inside a wave and a workgroup, written once.  An operation is a type with an associative, commutative
 // operator() whose identity is the all-zero value T{}, and before(inc, v): what the lanes in front of a lane hold together,
-// from the lane's inclusive value and its own.  ScanOp<0|1|2> = sum (mod 2^32) / maximum / xor of u32, Xor128 = xor of
+// from the lane's inclusive value and its own.  ScanOp<0|1|2> = sum (mod 2^32, 2^64) / maximum / xor of u32 and u64, Xor128 = xor of
 // 128-bit words.  Everything is inlined, and LDS comes from the caller: a kernel's layout and barriers are its own.
-__device__ __forceinline__ uint32_t lanes_up(uint32_t v, int off) { return __shfl_up(v, off); }
-__device__ __forceinline__ uint32_t lanes_down(uint32_t v, int off) { return __shfl_down(v, off); }
+// (a lane's value from the lane `off` in front / behind / across; any 32- or 64-bit scalar, and 128-bit words)
+template <class T> __device__ __forceinline__ T lanes_up(T v, int off) { return __shfl_up(v, off); }
+template <class T> __device__ __forceinline__ T lanes_down(T v, int off) { return __shfl_down(v, off); }
+template <class T> __device__ __forceinline__ T lanes_xor(T v, int off) { return __shfl_xor(v, off); }
+__device__ __forceinline__ uint2 lanes_down(const uint2 v, int off) { return make_uint2(__shfl_down(v.x, off), __shfl_down(v.y, off)); }
 __device__ __forceinline__ ulonglong2 lanes_up(const ulonglong2 v, int off) { return make_ulonglong2(__shfl_up(v.x, off), __shfl_up(v.y, off)); }
 __device__ __forceinline__ ulonglong2 lanes_down(const ulonglong2 v, int off) { return make_ulonglong2(__shfl_down(v.x, off), __shfl_down(v.y, off)); }
 template <int OP>
 struct ScanOp {
 	__device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b) const { return OP == 1 ? (a > b ? a : b) : (OP == 2 ? (a ^ b) : a + b); }
+	template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return OP == 1 ? (a > b ? a : b) : (OP == 2 ? (a ^ b) : a + b); } // (64-bit values)
 	__device__ __forceinline__ uint32_t before(uint32_t inc, uint32_t v) const
 	{
 		if (OP == 0)
@@ -494,6 +499,10 @@ struct ScanOp {
 		const uint32_t y = __shfl_up(inc, 1); // (a maximum cannot be undone)
 		return (threadIdx.x & 63u) ? y : 0u;
 	}
+};
+// the minimum, for reductions alone (its identity is not the zero the scans start from)
+struct MinOp {
+	template <class T> __device__ __forceinline__ T operator()(T a, T b) const { return a < b ? a : b; }
 };
 struct Xor128 {
 	__device__ __forceinline__ ulonglong2 operator()(const ulonglong2 a, const ulonglong2 b) const { return make_ulonglong2(a.x ^ b.x, a.y ^ b.y); }
@@ -517,6 +526,14 @@ __device__ __forceinline__ T wave_reduce(T v, Op op)
 {
 	for (int off = 32; off; off >>= 1)
 		v = op(v, lanes_down(v, off));
+	return v;
+}
+// every lane gets the whole wave (a xor butterfly)
+template <class T, class Op>
+__device__ __forceinline__ T wave_all_reduce(T v, Op op)
+{
+	for (int off = 32; off; off >>= 1)
+		v = op(v, lanes_xor(v, off));
 	return v;
 }
 // the workgroup (WAVES waves), in every lane; sh: WAVES values, free again on return (one barrier in, one out)
@@ -642,6 +659,23 @@ struct StackComp {
 	const uint4 *rec;
 	const uint32_t *list;
 	__device__ __forceinline__ uint32_t operator()(uint32_t i) const { return list[bitrank(rec, i + 1) - 1u]; }
+};
+// Component of a tree vertex / of a slot of the per-component layouts, looked up in the vertex offsets of the C components
+// (C > 0): component c owns the tree vertices [2 voff[c] + c, 2 voff[c + 1] + c] and the slots from voff[c] + c.  The keys
+// ascend strictly, whatever components are empty.
+struct CompSpans {
+	const uint32_t *voff;
+	uint32_t C;
+	__device__ __forceinline__ uint32_t of_tree(uint32_t t) const
+	{
+		const uint32_t *v = voff;
+		return last_upto(0u, C, [=](uint32_t c) { return 2 * v[c] + c <= t; });
+	}
+	__device__ __forceinline__ uint32_t of_slot(uint32_t slot) const
+	{
+		const uint32_t *v = voff;
+		return last_upto(0u, C, [=](uint32_t c) { return v[c] + c <= slot; });
+	}
 };
 // spreads the low 16 bits of x to every fourth bit position (bit k -> bit 4 k)
 __device__ __forceinline__ unsigned long long spread4(unsigned long long x)

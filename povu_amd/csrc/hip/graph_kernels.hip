@@ -108,17 +108,7 @@ __global__ void k_slot_twin(uint32_t E, const uint32_t *__restrict__ off, const 
 	if (e >= E)
 		return;
 	const uint32_t a = 2 * v1[e] + s1[e], b = 2 * v2[e] + s2[e];
-	auto find = [&](uint32_t side) {
-		uint32_t lo = off[side], hi = off[side + 1];
-		while (lo < hi) {
-			uint32_t mid = (lo + hi) >> 1;
-			if (adj[mid] < e)
-				lo = mid + 1;
-			else
-				hi = mid;
-		}
-		return lo;
-	};
+	auto find = [&](uint32_t side) { return lower_bound(adj, off[side], off[side + 1], e); };
 	const uint32_t ka = find(a), kb = a == b ? ka : find(b);
 	atwin[ka] = kb;
 	atwin[kb] = ka;
@@ -625,9 +615,7 @@ __global__ void k_local_degree(uint32_t V, const uint32_t *__restrict__ perm, co
 			ldeg[2 * V] = 0; // closes the array the scan turns into loff
 	}
 	__shared__ uint32_t sh[TPB / 64];
-	uint32_t m = cnt;
-	for (int o = 32; o; o >>= 1)
-		m = max(m, __shfl_down(m, o));
+	uint32_t m = wave_reduce(cnt, ScanOp<1>{});
 	if ((threadIdx.x & 63) == 0)
 		sh[threadIdx.x >> 6] = m;
 	__syncthreads();
@@ -760,6 +748,9 @@ __global__ void k_local_slots(uint32_t n, const uint32_t *__restrict__ origin, c
 	lle[k] = le | (tgray[le] ? LLE_TREE : 0u); // (here the id is the dense first-encounter rank: same order, same agreement)
 }
 
+struct MaxAndSum {
+	__device__ __forceinline__ uint2 operator()(const uint2 a, const uint2 b) const { return make_uint2(max(a.x, b.x), a.y + b.y); }
+};
 // maximum of v[0..n); with `zeros` also the number of entries that are 0 (sides without links)
 __global__ void k_max_u32(uint32_t n, const uint32_t *__restrict__ v, uint32_t *out, uint32_t *zeros)
 {
@@ -770,10 +761,8 @@ __global__ void k_max_u32(uint32_t n, const uint32_t *__restrict__ v, uint32_t *
 		m = max(m, x);
 		z += x == 0 ? 1u : 0u;
 	}
-	for (int off = 32; off; off >>= 1) {
-		m = max(m, __shfl_down(m, off));
-		z += __shfl_down(z, off);
-	}
+	const uint2 mz = wave_reduce(make_uint2(m, z), MaxAndSum{}); // (one loop over both)
+	m = mz.x, z = mz.y;
 	if ((threadIdx.x & 63) == 0) {
 		sh[threadIdx.x >> 6] = m;
 		shz[threadIdx.x >> 6] = z;

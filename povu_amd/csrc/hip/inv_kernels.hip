@@ -245,30 +245,16 @@ __global__ void k_inv_rows_flubble(uint32_t nrec, const uint32_t *__restrict__ f
 				   const uint32_t *__restrict__ v_ref, const uint64_t *__restrict__ v_pos, uint32_t *__restrict__ f_dst)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < nrec; i += gridDim.x * Q_TPB) {
-		uint32_t lo = 0, hi = ninv; // the inversion records in front: those with a smaller key
-		while (lo < hi) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (key_less(v_ref[mid], v_pos[mid], f_ref[i], f_pos[i]))
-				lo = mid + 1;
-			else
-				hi = mid;
-		}
-		f_dst[i] = i + lo;
+		// the inversion records in front: those with a smaller key
+		f_dst[i] = i + first_not(0u, ninv, [=](uint32_t k) { return key_less(v_ref[k], v_pos[k], f_ref[i], f_pos[i]); });
 	}
 }
 __global__ void k_inv_rows(uint32_t ninv, const uint32_t *__restrict__ v_ref, const uint64_t *__restrict__ v_pos, uint32_t nrec,
 			   const uint32_t *__restrict__ f_ref, const uint64_t *__restrict__ f_pos, uint32_t *__restrict__ v_dst)
 {
 	for (uint32_t b = blockIdx.x * Q_TPB + threadIdx.x; b < ninv; b += gridDim.x * Q_TPB) {
-		uint32_t lo = 0, hi = nrec; // the flubble records in front: those whose key is not larger
-		while (lo < hi) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (!key_less(v_ref[b], v_pos[b], f_ref[mid], f_pos[mid]))
-				lo = mid + 1;
-			else
-				hi = mid;
-		}
-		v_dst[b] = b + lo;
+		// the flubble records in front: those whose key is not larger
+		v_dst[b] = b + first_not(0u, nrec, [=](uint32_t k) { return !key_less(v_ref[b], v_pos[b], f_ref[k], f_pos[k]); });
 	}
 }
 

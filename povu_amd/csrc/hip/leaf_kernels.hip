@@ -28,26 +28,10 @@ namespace povu_hip
 
 #define NIL POVU_NIL
 
-// component of a tree vertex: component c owns [2 voff[c] + c, 2 voff[c+1] + c]
-struct CompOf {
-	const uint32_t *voff;
-	uint32_t C;
-	__device__ __forceinline__ uint32_t operator()(uint32_t t) const
-	{
-		uint32_t lo = 0, hi = C;
-		while (hi - lo > 1) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (2 * voff[mid] + mid <= t)
-				lo = mid;
-			else
-				hi = mid;
-		}
-		return lo;
-	}
-};
+// (component of a tree vertex, of a slot of the one-lane layout: CompSpans, common.hpp)
 
 // global parent and child counts
-__global__ void k_leaf_tree(uint32_t T, const uint32_t *__restrict__ t_size, const uint32_t *__restrict__ t_par, const CompOf comp_of,
+__global__ void k_leaf_tree(uint32_t T, const uint32_t *__restrict__ t_size, const uint32_t *__restrict__ t_par, const CompSpans comp,
 			    uint32_t *__restrict__ gp, uint32_t *__restrict__ nchild)
 {
 	uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -55,8 +39,8 @@ __global__ void k_leaf_tree(uint32_t T, const uint32_t *__restrict__ t_size, con
 		return;
 	uint32_t g = NIL;
 	if (t_size[t] && t_par[t] != NIL) {
-		const uint32_t c = comp_of(t);
-		g = 2 * comp_of.voff[c] + c + t_par[t];
+		const uint32_t c = comp.of_tree(t);
+		g = 2 * comp.voff[c] + c + t_par[t];
 		atomicAdd(&nchild[g], 1u);
 	}
 	gp[t] = g;
@@ -109,7 +93,7 @@ __global__ void k_leaf_extra_counts(uint32_t T, const uint8_t *__restrict__ capf
 // w[t] = ordinary back edges created just before t is discovered (by its parent); add the ones created after the last
 // child of every vertex whose subtree ends right before t.  The tails of subtrees that end with their component are
 // created after the component's last discovery and count for nobody.
-__global__ void k_leaf_closed(uint32_t T, const uint32_t *__restrict__ t_size, const uint32_t *__restrict__ tail, const CompOf comp_of,
+__global__ void k_leaf_closed(uint32_t T, const uint32_t *__restrict__ t_size, const uint32_t *__restrict__ tail, const CompSpans comp,
 			      const uint32_t *__restrict__ c_ntree, uint32_t *__restrict__ w)
 {
 	uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -118,7 +102,7 @@ __global__ void k_leaf_closed(uint32_t T, const uint32_t *__restrict__ t_size, c
 	const uint32_t sz = t_size[t], tl = tail[t];
 	if (!sz || !tl)
 		return;
-	const uint32_t c = comp_of(t), base = 2 * comp_of.voff[c] + c, end = t + sz;
+	const uint32_t c = comp.of_tree(t), base = 2 * comp.voff[c] + c, end = t + sz;
 	if (end < base + c_ntree[c])
 		atomicAdd(&w[end], tl);
 }
@@ -262,42 +246,26 @@ __global__ void k_leaf_roots(uint32_t C, const uint32_t *__restrict__ c_ntree, c
 
 // ---- components whose add_flubbles went through the sequential redo: their PVST sits in the per-component layout of the
 // one-lane kernels (component c owns the slots from voff[c] + c; seq_pvst also left ai / zi there)
-struct SlotComp {
-	const uint32_t *voff;
-	uint32_t C;
-	__device__ __forceinline__ uint32_t operator()(uint32_t slot) const
-	{
-		uint32_t lo = 0, hi = C; // last c with voff[c] + c <= slot
-		while (hi - lo > 1) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (voff[mid] + mid <= slot)
-				lo = mid;
-			else
-				hi = mid;
-		}
-		return lo;
-	}
-};
-__global__ void k_leaf_seq_children(uint32_t P, const SlotComp comp_of, const uint32_t *__restrict__ comp_bad,
+__global__ void k_leaf_seq_children(uint32_t P, const CompSpans comp, const uint32_t *__restrict__ comp_bad,
 				    const uint32_t *__restrict__ c_npvst, const uint32_t *__restrict__ p_parent,
 				    uint8_t *__restrict__ has_child)
 {
 	uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
 	if (slot >= P)
 		return;
-	const uint32_t c = comp_of(slot), pb = comp_of.voff[c] + c, k = slot - pb;
+	const uint32_t c = comp.of_slot(slot), pb = comp.voff[c] + c, k = slot - pb;
 	if (!comp_bad[c] || k == 0 || k >= c_npvst[c])
 		return;
 	has_child[pb + p_parent[slot]] = 1;
 }
-__global__ void k_leaf_seq_eval(uint32_t P, const LeafIn in, const SlotComp comp_of, const uint32_t *__restrict__ comp_bad,
+__global__ void k_leaf_seq_eval(uint32_t P, const LeafIn in, const CompSpans comp, const uint32_t *__restrict__ comp_bad,
 				const uint32_t *__restrict__ c_npvst, const uint32_t *__restrict__ p_ai,
 				const uint32_t *__restrict__ p_zi, const uint8_t *__restrict__ has_child, uint8_t *__restrict__ p_fam)
 {
 	uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
 	if (slot >= P)
 		return;
-	const uint32_t c = comp_of(slot), pb = comp_of.voff[c] + c, k = slot - pb;
+	const uint32_t c = comp.of_slot(slot), pb = comp.voff[c] + c, k = slot - pb;
 	if (!comp_bad[c] || k >= c_npvst[c])
 		return;
 	if (k == 0) {
@@ -352,8 +320,8 @@ void leaf_prepare(const CompState &cs, const SeqWs &sw, const ParWs &pw, const T
 		HIP_CHECK(hipMemsetAsync(p, 0, ((size_t)T + 4) * 4, s));
 	for (uint8_t *p : {t.capf, t.simp, t.hit1, t.hit3})
 		HIP_CHECK(hipMemsetAsync(p, 0, (size_t)T + 64, s));
-	const CompOf comp_of{cs.voff, C};
-	LAUNCH(k_leaf_tree, T, s, T, sw.t_size, sw.t_par, comp_of, t.gp, t.nchild);
+	const CompSpans comp{cs.voff, C};
+	LAUNCH(k_leaf_tree, T, s, T, sw.t_size, sw.t_par, comp, t.gp, t.nchild);
 	const uint32_t NB = pw.nb0 + pw.ncap + pw.nsimp;
 	LAUNCH(k_leaf_edges, NB, s, NB, pw.nb0, pw.ncap, pw.b_src, pw.b_tgt, sw.t_size, sw.t_flags, t.gp, t.out_ord, t.in_ord, t.nself, t.in_ext,
 	       t.capf, t.simp, t.hit1, t.hit3);
@@ -362,7 +330,7 @@ void leaf_prepare(const CompState &cs, const SeqWs &sw, const ParWs &pw, const T
 	scan_exclusive_u32(t.out_ord, t.O, (size_t)T + 1, t.scan, t.scan_bytes, s);
 	scan_exclusive_u8(t.nx, t.X, (size_t)T + 1, nullptr, nullptr, 0, t.scan, t.scan_bytes, s);
 	edge_id_weights(cs, sw, tw, t.w, t.tail, s);
-	LAUNCH(k_leaf_closed, T, s, T, sw.t_size, t.tail, comp_of, sw.c_ntree, t.w);
+	LAUNCH(k_leaf_closed, T, s, T, sw.t_size, t.tail, comp, sw.c_ntree, t.w);
 	scan_exclusive_u32(t.w, t.B, (size_t)T + 2, t.scan, t.scan_bytes, s);
 
 	LeafIn &in = ls.in;
@@ -404,10 +372,10 @@ void leaf_dense(const LeafState &ls, const SeqWs &sw, const ParWs &pw, uint32_t 
 void leaf_seq(const LeafState &ls, const CompState &cs, const SeqWs &sw, const uint32_t *comp_bad, uint32_t C, hipStream_t s)
 {
 	const uint32_t P = (uint32_t)ls.P;
-	const SlotComp comp_of{cs.voff, C};
+	const CompSpans comp{cs.voff, C};
 	HIP_CHECK(hipMemsetAsync(ls.p_has_child, 0, ls.P + 64, s));
-	LAUNCH(k_leaf_seq_children, P, s, P, comp_of, comp_bad, sw.c_npvst, sw.p_parent, ls.p_has_child);
-	LAUNCH(k_leaf_seq_eval, P, s, P, ls.in, comp_of, comp_bad, sw.c_npvst, ls.p_ai, ls.p_zi, ls.p_has_child, ls.p_fam);
+	LAUNCH(k_leaf_seq_children, P, s, P, comp, comp_bad, sw.c_npvst, sw.p_parent, ls.p_has_child);
+	LAUNCH(k_leaf_seq_eval, P, s, P, ls.in, comp, comp_bad, sw.c_npvst, ls.p_ai, ls.p_zi, ls.p_has_child, ls.p_fam);
 }
 
 } // namespace povu_hip

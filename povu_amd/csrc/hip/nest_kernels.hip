@@ -142,7 +142,7 @@ __global__ __launch_bounds__(Q_TPB) void k_ns_cover_t1(uint32_t n_al, CoverArgs 
 	}
 	const uint64_t pos = sp.first_pos(), end = sp.last_pos();
 	const uint32_t q = A.rq[t], base = A.soff[a];
-	uint32_t e = first_at_least(A.ipos, A.ni, pos), m = 0;
+	uint32_t e = lower_bound(A.ipos, 0u, A.ni, pos), m = 0;
 	uint64_t top = 0; // the running maximum of the enclosed entries' last positions (every one is at least 1)
 	for (uint64_t k = pos; k <= end; k++) {
 		for (; e < A.ni && A.ipos[e] < k; e++)
@@ -170,10 +170,10 @@ __global__ __launch_bounds__(64) void k_ns_cover_t2(const uint32_t *__restrict__
 		const uint32_t a = list[w], t = A.afirst[a], q = A.rq[t], base = A.soff[a];
 		const TravSpan sp = trav_span(A.rpos, A.rlen, t);
 		const uint64_t pos = sp.first_pos(), end = sp.last_pos();
-		uint32_t e = first_at_least(A.ipos, A.ni, pos), carry = 0; // ends relative to pos: at least 1
+		uint32_t e = lower_bound(A.ipos, 0u, A.ni, pos), carry = 0; // ends relative to pos: at least 1
 		for (uint32_t cb = 0; cb < sp.len; cb += 64) {
 			// the entries that start at the round's positions: their ends into the slot of their start
-			const uint32_t e_hi = first_at_least(A.ipos, A.ni, pos + cb + 64);
+			const uint32_t e_hi = lower_bound(A.ipos, 0u, A.ni, pos + cb + 64);
 			slot[lane] = 0;
 			__syncthreads();
 			for (uint32_t x = e + lane; x < e_hi; x += 64)
@@ -351,7 +351,7 @@ __global__ __launch_bounds__(Q_TPB) void k_ns_parent(uint32_t nfl, const uint32_
 		const uint32_t t = rlist[j], q = rq[t];
 		const TravSpan sp = trav_span(rpos, rlen, t);
 		const uint64_t pos = sp.first_pos(), end = sp.last_pos();
-		const uint32_t lo = first_at_least(ix.ipos, ix.ni, pos), hi = first_at_least(ix.ipos, ix.ni, end + 1);
+		const uint32_t lo = lower_bound(ix.ipos, 0u, ix.ni, pos), hi = lower_bound(ix.ipos, 0u, ix.ni, end + 1);
 		for (uint32_t x = lo + lane; x < hi; x += 64) {
 			const uint64_t ie = ix.iend[x];
 			if (ix.iq[x] == q || ie > end || ie - ix.ipos[x] >= (uint64_t)sp.len - 1)

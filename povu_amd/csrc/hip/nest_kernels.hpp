@@ -15,19 +15,7 @@ struct NestIndex {
 	uint64_t *ipos = nullptr, *iend = nullptr;
 	uint32_t *iq = nullptr, *it = nullptr;
 };
-// first entry whose position is at least x
-__device__ __forceinline__ uint32_t first_at_least(const uint64_t *__restrict__ ipos, uint32_t ni, uint64_t x)
-{
-	uint32_t lo = 0, hi = ni;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (ipos[mid] < x)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
+// (the first entry whose position is at least x: lower_bound(ipos, 0u, ni, x))
 // The index of the traversals flagged in flag[0 .. R): ix's arrays (R + 1 entries each, the caller's) filled, ix.ni set.
 // The scratch is the caller's: four lists of R + 1, one cleared word, prim_tmp_bytes(R + 1, true) bytes.  Waits for the stream
 struct NestIndexWs {

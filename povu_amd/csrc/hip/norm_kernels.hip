@@ -158,8 +158,7 @@ __global__ __launch_bounds__(Q_TPB) void k_nm_record(CallView V, const unsigned 
 		uint64_t mn = ~0ull;
 		for (uint32_t i = lane; i < nal; i += 64)
 			mn = min(mn, (i ? V.ilen[other_allele(V, j, i)] : V.xilen[j]) + (A.anchor_base ? 1 : 0));
-		for (int o = 32; o > 0; o >>= 1)
-			mn = min(mn, (uint64_t)__shfl_xor((unsigned long long)mn, o, 64));
+		mn = wave_all_reduce(mn, MinOp{});
 		const uint64_t rm = rmin[j];
 		uint64_t r = 0, s = 0, u = 0;
 		if (mn && rm != ~0ull) {

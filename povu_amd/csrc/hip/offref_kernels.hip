@@ -177,7 +177,7 @@ __global__ __launch_bounds__(Q_TPB) void k_or_offer(NestIndex ix, uint32_t nfl, 
 			continue;
 		const uint64_t pos = ix.ipos[x0], end = ix.iend[x0];
 		const unsigned long long mine = offref_host_key((uint32_t)(end - pos + 1), q);
-		const uint32_t lo = first_at_least(ix.ipos, ix.ni, pos), hi = first_at_least(ix.ipos, ix.ni, end + 1);
+		const uint32_t lo = lower_bound(ix.ipos, 0u, ix.ni, pos), hi = lower_bound(ix.ipos, 0u, ix.ni, end + 1);
 		for (uint32_t x = lo + lane; x < hi; x += 64) {
 			if (sur[ix.iq[x]] == NO_QUERY || !offref_encloses(pos, end, ix.ipos[x], ix.iend[x]))
 				continue;

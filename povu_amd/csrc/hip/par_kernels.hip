@@ -99,15 +99,7 @@ __global__ void k_dense_be(uint32_t NB0, uint32_t C, const uint32_t *__restrict_
 	uint32_t j = BIDX * blockDim.x + threadIdx.x;
 	if (j >= NB0)
 		return;
-	uint32_t lo = 0, hi = C; // last c with dbo[c] <= j
-	while (hi - lo > 1) {
-		uint32_t mid = (lo + hi) >> 1;
-		if (dbo[mid] <= j)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	uint32_t c = lo, b = j - dbo[c];
+	uint32_t c = span_of(dbo, C, j), b = j - dbo[c];
 	uint64_t tb = 2ull * voff[c] + c, bb = (uint64_t)eoff[c] + voff[c] + 2 * tb;
 	b_src[j] = (uint32_t)tb + be_src[bb + b];
 	b_tgt[j] = (uint32_t)tb + be_tgt[bb + b];
@@ -175,15 +167,8 @@ struct RootOf {
 	{
 		if (t_root)
 			return t_root[t];
-		uint32_t lo = 0, hi = C; // last c with 2 voff[c] + c <= t
-		while (hi - lo > 1) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (2 * voff[mid] + mid <= t)
-				lo = mid;
-			else
-				hi = mid;
-		}
-		return 2 * voff[lo] + lo;
+		const uint32_t c = CompSpans{voff, C}.of_tree(t);
+		return 2 * voff[c] + c;
 	}
 };
 // rank(x) out of the record that holds x (bitrank, common.hpp)
@@ -984,15 +969,7 @@ __global__ void k_resolve_crossings(uint32_t C, const uint32_t *__restrict__ sof
 	const uint32_t nx = *n_x;
 	for (uint32_t c = BIDX * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x) {
 		// this component's stretch of the list
-		uint32_t lo = 0, hi = nx;
-		const uint32_t b = soff[c], e = soff[c + 1];
-		while (lo < hi) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (xlist[mid] < b)
-				lo = mid + 1;
-			else
-				hi = mid;
-		}
+		const uint32_t b = soff[c], e = soff[c + 1], lo = lower_bound(xlist, 0u, nx, b);
 		uint32_t crossed = 0;
 		for (uint32_t t = lo; t < nx; t++) {
 			const uint32_t i = xlist[t];

@@ -85,8 +85,7 @@ __global__ __launch_bounds__(Q_TPB) void k_pr_pairs(PrimIn I, PrPairs P, uint8_t
 			longest = n > m ? n : m;
 		}
 		cells = wave_sum(cells);
-		for (int o = 32; o > 0; o >>= 1)
-			longest = max(longest, __shfl_xor(longest, o, 64));
+		longest = wave_all_reduce(longest, ScanOp<1>{});
 		if (lane == 0 && cells)
 			atomicAdd(words + W_CELLS, cells);
 		if (lane == 0 && longest >= (1ull << 32))

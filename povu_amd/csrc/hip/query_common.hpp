@@ -56,42 +56,21 @@ static inline PathsView paths_view(const povu_hip_ctx *ctx)
 	return PathsView{ctx->n_paths, ctx->path_off, ctx->path_steps, ctx->seq_off, ctx->seq, ctx->g.vid};
 }
 
-// the span x lies in: the last k with off[k] <= x, off ascending over [0, n) (the path of a global step, the reference of a
-// reference step, the block of a spelled allele)
-__device__ __forceinline__ uint32_t span_of(const uint64_t *__restrict__ off, uint32_t n, uint64_t x)
-{
-	uint32_t lo = 0, hi = n;
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (off[mid] <= x)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	return lo;
-}
+// (the span a position lies in -- the path of a global step, the reference of a reference step, the block of a spelled
+// allele: span_of, search_rules.hpp)
 
 // sum over the wave, in every lane
 template <class T>
 __device__ __forceinline__ T wave_sum(T v)
 {
-	for (int o = 32; o > 0; o >>= 1)
-		v += __shfl_xor(v, o, 64);
-	return v;
+	return wave_all_reduce(v, ScanOp<0>{});
 }
 // (inclusive prefix sum over the wave: wave_inclusive_sum, common.hpp)
 
 // vertex index of segment `id` in the ascending `vid`, NO_QUERY when the graph has no such segment
 __device__ __forceinline__ uint32_t find_vertex(const uint32_t *__restrict__ vid, uint32_t V, uint32_t id)
 {
-	uint32_t lo = 0, hi = V;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (vid[mid] < id)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
+	const uint32_t lo = lower_bound(vid, 0u, V, id);
 	return (lo < V && vid[lo] == id) ? lo : NO_QUERY;
 }
 

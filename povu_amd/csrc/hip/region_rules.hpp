@@ -8,6 +8,7 @@
 // [off + 1, off + 1 + max(len, 1)), off the bases in front of it: a segment without bases counts as one position.
 #pragma once
 #include "prim_align.hpp"
+#include "search_rules.hpp"
 
 #include <algorithm>
 #include <string>
@@ -32,15 +33,8 @@ PRIM_HD bool step_in_region(uint64_t off, uint64_t len, uint64_t s, uint64_t e)
 PRIM_HD bool step_in_any(const uint64_t *iv_s, const uint64_t *iv_e, uint32_t lo, uint32_t hi, uint64_t off, uint64_t len)
 {
 	const uint64_t last = off + 1 + (len ? len : 1);
-	const uint32_t first = lo;
-	while (lo < hi) { // the first interval with s >= last
-		const uint32_t mid = lo + ((hi - lo) >> 1);
-		if (iv_s[mid] < last)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo > first && step_in_region(off, len, iv_s[lo - 1], iv_e[lo - 1]);
+	const uint32_t at = povu_hip::lower_bound(iv_s, lo, hi, last); // the first interval with s >= last
+	return at > lo && step_in_region(off, len, iv_s[at - 1], iv_e[at - 1]);
 }
 
 // ---- the parser: `name:start-end`, split at the last ':' and at the first '-' behind it.  Gives "" or the refusal

@@ -137,30 +137,9 @@ struct SubT {
 struct CompAt { // component of a global tree vertex / of a dense PVST slot
 	const uint32_t *voff, *doff;
 	uint32_t C;
-	__device__ __forceinline__ uint32_t of_tree(uint32_t t) const
-	{
-		uint32_t lo = 0, hi = C;
-		while (hi - lo > 1) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (2 * voff[mid] + mid <= t)
-				lo = mid;
-			else
-				hi = mid;
-		}
-		return lo;
-	}
-	__device__ __forceinline__ uint32_t of_slot(uint32_t q) const // last c with doff[c] <= q (components without a PVST own no slot)
-	{
-		uint32_t lo = 0, hi = C;
-		while (hi - lo > 1) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (doff[mid] <= q)
-				lo = mid;
-			else
-				hi = mid;
-		}
-		return lo;
-	}
+	__device__ __forceinline__ uint32_t of_tree(uint32_t t) const { return CompSpans{voff, C}.of_tree(t); }
+	// last c with doff[c] <= q (components without a PVST own no slot)
+	__device__ __forceinline__ uint32_t of_slot(uint32_t q) const { return span_of(doff, C, q); }
 };
 
 // ------------------------------------------------------------------ tables
@@ -1038,18 +1017,6 @@ __global__ void k_sub_x_poison(uint32_t NX, const SubT t, const CompAt comp_x, c
 }
 // where the children of X slot x begin among the sorted (parent slot, child) pairs = how many pairs have a smaller key: a
 // binary search per slot (counting them with atomics put a million adds on the word of a chromosome's root)
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *__restrict__ a, uint32_t n, uint32_t x)
-{
-	uint32_t lo = 0, hi = n;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (a[mid] < x)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
 __global__ void k_sub_x_vbeg(uint32_t Q, const SubT t, const CompAt comp, const uint32_t *__restrict__ xoff,
 			     const uint32_t *__restrict__ poff, const uint32_t *__restrict__ key, uint32_t *__restrict__ cap_ps, XArrays X)
 {
@@ -1057,7 +1024,7 @@ __global__ void k_sub_x_vbeg(uint32_t Q, const SubT t, const CompAt comp, const 
 	if (q >= Q)
 		return;
 	const uint32_t c = comp.of_slot(q), x = xoff[c] + (q - t.doff[c]);
-	const uint32_t b = lower_bound_u32(key, Q, x), e = lower_bound_u32(key, Q, x + 1), b0 = lower_bound_u32(key, Q, xoff[c]);
+	const uint32_t b = lower_bound(key, 0u, Q, x), e = lower_bound(key, 0u, Q, x + 1), b0 = lower_bound(key, 0u, Q, xoff[c]);
 	cap_ps[x] = b;
 	X.vbeg[x] = poff[c] + (b - b0);
 	X.vn[x] = X.vcap[x] = e - b;
@@ -1496,15 +1463,8 @@ __global__ void k_sub_child_gather(uint32_t NCH, uint32_t NX, const uint32_t *__
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= NCH)
 		return;
-	uint32_t lo = 0, hi = NX; // coff[lo] <= i < coff[hi]
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (coff[mid] <= i)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	out[i] = pool[vbeg[lo] + (i - coff[lo])];
+	const uint32_t x = span_of(coff, NX, i);
+	out[i] = pool[vbeg[x] + (i - coff[x])];
 }
 // the vertices of every component without the spare slots of X-space: dense slot d = dvoff[c] + (index inside the component)
 __global__ void k_sub_compact(uint32_t NV, uint32_t C, const uint32_t *__restrict__ dvoff, const uint32_t *__restrict__ xoff, const XArrays X,
@@ -1514,15 +1474,8 @@ __global__ void k_sub_compact(uint32_t NV, uint32_t C, const uint32_t *__restric
 	const uint32_t d = blockIdx.x * blockDim.x + threadIdx.x;
 	if (d >= NV)
 		return;
-	uint32_t lo = 0, hi = C; // last c with dvoff[c] <= d (components without a PVST own no slot)
-	while (hi - lo > 1) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (dvoff[mid] <= d)
-			lo = mid;
-		else
-			hi = mid;
-	}
-	const uint32_t x = xoff[lo] + (d - dvoff[lo]);
+	const uint32_t c = span_of(dvoff, C, d); // (components without a PVST own no slot)
+	const uint32_t x = xoff[c] + (d - dvoff[c]);
 	fam[d] = X.fam[x], or1[d] = X.or1[x], or2[d] = X.or2[x], route[d] = X.route[x];
 	id1[d] = X.id1[x], id2[d] = X.id2[x];
 	coff_d[d] = coff[x];

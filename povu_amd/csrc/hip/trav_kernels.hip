@@ -303,15 +303,7 @@ __global__ void k_tr_query_off(uint32_t n, uint32_t R, const uint32_t *__restric
 	const uint32_t q = blockIdx.x * Q_TPB + threadIdx.x;
 	if (q > n)
 		return;
-	uint32_t lo = 0, hi = R;
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) >> 1;
-		if (rq[mid] < q)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	off[q] = lo;
+	off[q] = lower_bound(rq, 0u, R, q);
 }
 
 __device__ __forceinline__ bool same_sequence(const uint32_t *__restrict__ steps, uint64_t pa, uint64_t pb, uint32_t len)

@@ -50,22 +50,19 @@ namespace povu_hip
 // or stored per arc: the twin of a slot is found in the (short, ascending) list of the side at the other end, and
 // the arcs around a segment are taken in slot order -- the slots of its l side, then those of its r side, which are
 // one contiguous index range [loff[2w], loff[2w + 2]) -- so the subtrees hanging off ONE side are contiguous in the tour.
-// slot (1-based) of the link with id `le` (LLE_ID bits of its lle words) in the list of side w (ascending by link id)
+// where the link with id `le` (LLE_ID bits of its lle words) sits in the stretch [lo, hi) of a side's list (ascending by link id)
+__device__ __forceinline__ uint32_t link_at(const uint32_t *__restrict__ lle, uint32_t lo, uint32_t hi, uint32_t le)
+{
+	return first_not(lo, hi, [=](uint32_t k) { return (lle[k] & LLE_ID) < le; });
+}
+// slot (1-based) of that link in the list of side w
 __device__ __forceinline__ uint32_t find_link_slot(const uint32_t *__restrict__ loff, const uint32_t *__restrict__ lle, uint32_t w,
 						   uint32_t le)
 {
 	uint32_t lo = loff[w], hi = loff[w + 1];
 	const uint32_t l0 = lo;
-	if (hi - lo > 8) {
-		while (lo < hi) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if ((lle[mid] & LLE_ID) < le)
-				lo = mid + 1;
-			else
-				hi = mid;
-		}
-		return lo - l0 + 1;
-	}
+	if (hi - lo > 8)
+		return link_at(lle, lo, hi, le) - l0 + 1;
 	for (uint32_t j = lo; j < hi; j++)
 		if ((lle[j] & LLE_ID) == le)
 			return j - l0 + 1;
@@ -463,15 +460,7 @@ __global__ void k_bridges(uint32_t V, const uint4 *__restrict__ t0seg, const uin
 	if (entryE && pvE != NIL) { // (NIL: DFS start of the component) a gray bridge: its slot in the parent's list (ascending link id)
 		const uint32_t p = pvE & ~PB_BRIDGE;
 		recE.x = p;
-		uint32_t le = r.y & ~T0_RBIT, lo = loff[p], hi = loff[p + 1];
-		while (lo < hi) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if ((lle[mid] & LLE_ID) < le)
-				lo = mid + 1;
-			else
-				hi = mid;
-		}
-		recE.y = lo - loff[p] + 1;
+		recE.y = link_at(lle, loff[p], loff[p + 1], r.y & ~T0_RBIT) - loff[p] + 1;
 	}
 	if (entryF)
 		recF.x = Se; // (the black edge: slot 0, scanned first)

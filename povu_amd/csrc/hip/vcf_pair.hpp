@@ -53,14 +53,7 @@ struct PairView {
 [[maybe_unused]] static __global__ void k_pair_items(PairView A)
 {
 	for (uint32_t i = blockIdx.x * Q_TPB + threadIdx.x; i < A.nI; i += gridDim.x * Q_TPB) {
-		uint32_t lo = 0, hi = A.nR; // the last record whose items begin at or before i (ioff[0] = 0, nI > 0 hence nR > 0)
-		while (hi - lo > 1) {
-			const uint32_t mid = (lo + hi) >> 1;
-			if (A.ioff[mid] <= i)
-				lo = mid;
-			else
-				hi = mid;
-		}
+		const uint32_t lo = span_of(A.ioff, A.nR, i); // the last record whose items begin at or before i (ioff[0] = 0, nI > 0 hence nR > 0)
 		A.it_rec[i] = lo - (lo >= A.nRa ? A.nRa : 0u);
 		A.it_k[i] = i - A.ioff[lo] + 1;
 	}

@@ -118,14 +118,7 @@ __global__ __launch_bounds__(Q_TPB) void k_vm_classes(uint32_t nG, uint32_t nIa,
 		uint32_t cls = 3; // (no group)
 		if (g < nG) {
 			const uint32_t m0 = goff[g], m1 = goff[g + 1];
-			uint32_t lo = m0, hi = m1; // the first member that is an item of B: the members ascend
-			while (lo < hi) {
-				const uint32_t mid = lo + ((hi - lo) >> 1);
-				if (member[mid] < nIa)
-					lo = mid + 1;
-				else
-					hi = mid;
-			}
+			const uint32_t lo = lower_bound(member, m0, m1, nIa); // the first member that is an item of B: the members ascend
 			cls = vm_group_class(lo - m0, m1 - lo);
 			g_class[g] = (uint8_t)cls, g_na[g] = lo - m0, g_nb[g] = m1 - lo, g_first[g] = member[m0];
 		}
@@ -163,18 +156,6 @@ struct VmDoses {
 	const uint32_t *col_a, *col_b;	// [nC] the columns of a common sample
 	unsigned long long *tp, *fp, *fn, *gteq; // [nC]
 };
-// the first task of [lo, hi) whose allele is k or more
-__device__ __forceinline__ uint32_t first_task_of(const uint32_t *__restrict__ t_al, uint32_t lo, uint32_t hi, uint32_t k)
-{
-	while (lo < hi) {
-		const uint32_t mid = lo + ((hi - lo) >> 1);
-		if (t_al[mid] < k)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
 __global__ __launch_bounds__(Q_TPB) void k_vm_doses(PairView A, VmDoses D)
 {
 	const uint32_t lane = threadIdx.x & 63u, waves = gridDim.x * (Q_TPB / 64), wave = blockIdx.x * (Q_TPB / 64) + (threadIdx.x >> 6);
@@ -190,8 +171,8 @@ __global__ __launch_bounds__(Q_TPB) void k_vm_doses(PairView A, VmDoses D)
 				if (mb + lane < m1) {
 					const uint32_t i = D.member[mb + lane], r = A.record_of(i), k = A.it_k[i];
 					side = i >= A.nIa;
-					t0 = first_task_of(D.t_al, D.tkoff[r], D.tkoff[r + 1], k);
-					t1 = first_task_of(D.t_al, t0, D.tkoff[r + 1], k + 1);
+					t0 = lower_bound(D.t_al, D.tkoff[r], D.tkoff[r + 1], k); // the first task whose allele is k or more
+					t1 = lower_bound(D.t_al, t0, D.tkoff[r + 1], k + 1);
 				}
 				const uint32_t n_members = min(64u, m1 - mb);
 				for (uint32_t j = 0; j < n_members; j++) {

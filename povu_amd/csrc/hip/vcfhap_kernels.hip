@@ -206,15 +206,8 @@ __global__ void k_vh_span_reach(uint32_t nP, const uint32_t *__restrict__ sorted
 	for (uint32_t k = blockIdx.x * Q_TPB + threadIdx.x; k < nP; k += gridDim.x * Q_TPB) {
 		const uint32_t r = sorted[k], c = chrom[r];
 		const uint64_t end = sp_hi[r];
-		uint32_t lo = k, hi = nP; // (span k itself starts before its end)
-		while (hi - lo > 1) {
-			const uint32_t mid = lo + ((hi - lo) >> 1), q = sorted[mid];
-			if (chrom[q] == c && sp_lo[q] <= end) // (behind k the CHROM ids ascend: another CHROM is a greater one)
-				lo = mid;
-			else
-				hi = mid;
-		}
-		mark[k] = lo + 1;
+		// (span k itself starts before its end; behind k the CHROM ids ascend: another CHROM is a greater one)
+		mark[k] = 1 + last_upto(k, nP, [=](uint32_t m) { return chrom[sorted[m]] == c && sp_lo[sorted[m]] <= end; });
 	}
 }
 __global__ void k_vh_heads(uint32_t nP, const uint32_t *__restrict__ reached, uint32_t *__restrict__ headf)
@@ -417,23 +410,7 @@ struct VhReplay {
 // the first sorted task of [lo, hi) whose (side, kind) is v or more
 __device__ __forceinline__ uint32_t first_of_kind(const VhReplay &Y, uint32_t lo, uint32_t hi, uint32_t v)
 {
-	while (lo < hi) {
-		const uint32_t mid = lo + ((hi - lo) >> 1);
-		if (Y.sk[Y.sorted[mid]] < v)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
-	return lo;
-}
-__device__ __forceinline__ uint64_t wave_inclusive_max_u64(uint64_t v, uint32_t lane)
-{
-	for (int off = 1; off < 64; off <<= 1) {
-		const uint64_t y = __shfl_up((unsigned long long)v, off, 64);
-		if ((int)lane >= off)
-			v = max(v, y);
-	}
-	return v;
+	return first_not(lo, hi, [&](uint32_t k) { return Y.sk[Y.sorted[k]] < v; });
 }
 // the distinct edits [u0, u1) of a side, in (s, e) order: does one conflict with those in front of it?
 __device__ __forceinline__ bool side_conflict(const VhCells &C, const VhReplay &Y, uint32_t u0, uint32_t u1, uint32_t lane)
@@ -445,7 +422,7 @@ __device__ __forceinline__ bool side_conflict(const VhCells &C, const VhReplay &
 		const bool in = u < u1;
 		const uint32_t i = in ? C.u_item[u] : 0;
 		const uint64_t bs = in ? Y.bs[i] : 0, be = in ? Y.be[i] : 0;
-		const uint64_t incl = wave_inclusive_max_u64(be, lane);
+		const uint64_t incl = wave_inclusive_scan(be, ScanOp<1>{});
 		uint64_t before = __shfl_up((unsigned long long)incl, 1, 64), pbs = __shfl_up((unsigned long long)bs, 1, 64),
 			 pbe = __shfl_up((unsigned long long)be, 1, 64);
 		if (lane == 0)

@@ -5,6 +5,7 @@
 // trims through the wave loops of vcfcmp_rules.hpp); host/vcfhap_check.cpp runs them on the CPU under the sanitizers.
 // Coordinates are kept with one added (POS for the base POS names), so that a record at POS 0 has no negative start.
 #pragma once
+#include "search_rules.hpp"
 #include "vcfcmp_rules.hpp"
 
 namespace povu_hip
@@ -56,14 +57,7 @@ VCFCMP_FN bool vh_conflict(uint64_t bs, uint64_t be, bool has_prev, uint64_t max
 template <class Start>
 VCFCMP_FN uint32_t vh_locate(uint64_t h, uint32_t n, Start &&start)
 {
-	uint32_t lo = 0, hi = n; // the first edit that begins behind h
-	while (lo < hi) {
-		const uint32_t mid = lo + ((hi - lo) >> 1);
-		if (start(mid) <= h)
-			lo = mid + 1;
-		else
-			hi = mid;
-	}
+	const uint32_t lo = first_not(0u, n, [&](uint32_t u) { return start(u) <= h; }); // the first edit that begins behind h
 	return lo ? lo - 1 : n;
 }
 struct VhSource {
