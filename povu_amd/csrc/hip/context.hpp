@@ -220,17 +220,19 @@ struct povu_hip_forest {
 	uint64_t walk_gen = 0;
 };
 
-// What a pass does, decided once from its options (plan_pass in povu_hip.hip).
+// What a pass does, decided once from its options and the environment hooks (plan_pass in povu_hip.hip).
 // all_seq: every stage on the one-lane kernels; seq_tree / par_tree: the tree stage on the one-lane / parallel kernels;
 // leaf_sub: the leaf subflubble passes (find_tiny, find_parallel); all_sub: all five passes of -s; timed: stage times;
 // overlap_tail: POVU_HIP_F_ASYNC on the one pass that has that form (the tail may overlap the next pass); heaviest_first:
-// components in LPT order (shard assignment, launch order of the one-lane kernels).
+// components in LPT order (shard assignment, launch order of the one-lane kernels); hooks: the A/B and tuning hooks of the
+// environment as this pass read them (pass_hooks.hpp).
 struct PassPlan {
 	uint32_t rank = 0, world = 1;
 	bool hairpins = false, all_seq = false, seq_tree = false, par_tree = true, leaf_sub = false, all_sub = false;
 	bool sorted_adj = false, force_redo = false, redo_odd = false;
 	bool big_class_dfs = false, sparse_splitters = false, all_vertex_classes = false, check_laminar = false;
 	bool timed = true, overlap_tail = false, heaviest_first = false;
+	PassHooks hooks;
 };
 
 // What the last decompose of a context left in its stage workspace (debug / parity hooks): with plan.par_tree the
@@ -466,6 +468,7 @@ struct RowBNeeds {
 };
 size_t rowb_carve_label(Arena *ar, const Sizes &z, CompState &cs);
 size_t rowb_carve_reindex(Arena *ar, const Sizes &z, size_t C, const RowBNeeds &need, CompState &cs);
+size_t rowb_speculative_adj_bytes(const Sizes &z);
 // The head of a pass (povu_hip.hip), shared by povu_hip_decompose and povu_hip_debug_row_b: the plan the flags make,
 // the set-up ahead of row B, and row B itself -- the component count at once, the components' sizes in page-locked scratch
 // once `sizes` is waited for.
@@ -477,5 +480,7 @@ struct RowB {
 PassPlan plan_pass(const povu_hip_opts *opts);
 Sizes rowb_begin(povu_hip_ctx *ctx, const PassPlan &p);
 RowB row_b(povu_hip_ctx *ctx, const PassPlan &p, const Sizes &z, StageTimer &tm);
-// Workspace carving (or just measuring when `ar` is null); part 0 = rows A/B state (CompState), see povu_hip.hip
+// Workspace carving (or just measuring when `ar` is null); part 0 = rows A/B state (CompState), see context.hip
 size_t carve_workspace(Arena *ar, int part, const Sizes &z, CompState &cs, SeqWs &sw, bool hairpins);
+// what the stage workspace of a pass has to hold (context.hip)
+StageWsOpts stage_opts(size_t V, size_t E, size_t C, size_t empty_sides, bool seq_tree, bool hairpins);

@@ -22,12 +22,7 @@ namespace povu_hip
 // the next level IS its bucket idx (dense, no flag array, no scan, no compaction), and lane q of a walk kernel works
 // near element q * 2^b (the scattered rank stores of neighbouring lanes meet again in L2).
 // b = 3 (1 in 8): short segments, whose walks are bound by their longest one; b = 4 is kept as an A/B switch.
-unsigned rank_bucket_bits()
-{
-	if (const char *ev = getenv("POVU_HIP_RANK_BITS")) // (tuning hook)
-		return (unsigned)std::min(6, std::max(2, atoi(ev)));
-	return 3u; // (1 in 16 measured 0.2 ms slower on 2.4e8 slots once the other kernels had changed; POVU_HIP_F_SPARSE_SPLITTERS still forces it)
-}
+unsigned rank_bucket_bits(const PassHooks &hooks) { return hooks.rank_bits; } // (tuning hook; the default and its measurement: pass_hooks.hpp)
 // words of the levels above the list (their elements number an eighth of it), so that a walk step is ONE dependent load:
 // bits 0..28 successor (PK_END = none), bit 31 = stop after this element (the successor is a splitter, or there is none).
 // Their weights are words of their own (the sums of the level below).
@@ -496,7 +491,7 @@ void debug_list_rank(uint32_t n, const uint32_t *next, const uint8_t *w, const u
 {
 	if (n == 0 || n >= P0_END)
 		throw HipError("debug_list_rank: n must be in [1, 2^30)");
-	const unsigned b = bits ? std::min(6u, std::max(2u, bits)) : rank_bucket_bits();
+	const unsigned b = bits ? std::min(6u, std::max(2u, bits)) : rank_bucket_bits(read_pass_hooks()); // (a debug hook outside any pass)
 	std::vector<uint32_t> pk(n);
 	for (uint32_t x = 0; x < n; x++) {
 		if (next[x] != NIL && next[x] >= n)

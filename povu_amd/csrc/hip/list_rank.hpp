@@ -19,6 +19,7 @@
 // (a graph without links has no slot, and its R stays null: root_forest).
 #pragma once
 #include "common.hpp"
+#include "pass_hooks.hpp"
 
 namespace povu_hip
 {
@@ -115,8 +116,8 @@ struct RankBufs {
 };
 // words every pool needs for lists of n elements in total with nh heads
 size_t rank_pool_words(size_t n, size_t nh);
-// bucket bits of a ranking: 3 (one element in 8 is a splitter), or what POVU_HIP_RANK_BITS says
-unsigned rank_bucket_bits();
+// bucket bits of a ranking: 3 (one element in 8 is a splitter), or what the hooks of the pass say (PassHooks::rank_bits)
+unsigned rank_bucket_bits(const PassHooks &hooks);
 
 // What a level-0 walk of a list ranking left in its records (debug hook povu_hip_debug_rank_escapes; k_rank_rec_stats).
 // hist[33 * d + p]: live elements whose owner delta needs d bits (zigzag) and whose partial sums need p bits (the events: the

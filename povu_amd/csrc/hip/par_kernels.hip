@@ -1486,11 +1486,11 @@ struct ClassPass {
 	const bool lean;
 	const bool narrow_oc, narrow_sc, narrow_ic; // the bracket counts of the parallel tree stage as bytes (it wrote them in the form the caller chose, see ParWs)
 	// psin / the range starts as count records (the spans of psin / dlt_ps hold them): exactly where the scan's input is a byte
-	// array, unless POVU_HIP_WORD_PREFIX (A/B hook, read per pass) says words: 1 = both, 2 = psin, 3 = the range starts
+	// array, unless PassHooks::word_prefix (POVU_HIP_WORD_PREFIX, an A/B hook) says words: 1 = both, 2 = psin, 3 = the range starts
 	const int word_prefix;
 	const bool rec_ps, rec_bs;
 	// bits of the class sort's payload that carry the list size in a black-only pass (LszField, par_kernels.hpp), at most:
-	// POVU_HIP_LSZ_FIELD (A/B hook, read per pass) lowers the cap, 0 = the bare stack index and every size looked up
+	// PassHooks::lsz_field (POVU_HIP_LSZ_FIELD, an A/B hook) lowers the cap, 0 = the bare stack index and every size looked up
 	const unsigned lsz_cap;
 	bool black_only = false;	 // classes of the black tree edges only (place_brackets decides)
 	const RootOf root_of;
@@ -1505,14 +1505,14 @@ struct ClassPass {
 	bool use_side = false; // the endpoints and the copies go to the side stream
 
 	ClassPass(const CompState &cs_, SeqWs &sw_, ParWs &pw_, uint32_t C_, uint32_t n_processed_, uint32_t n_stack, int64_t dense_nb0_,
-		  const std::function<void *(size_t)> &alloc, StageTimer &tm_, hipStream_t s_, const SideStream &side_, PassTail &tail_)
+		  const PassHooks &hooks, const std::function<void *(size_t)> &alloc, StageTimer &tm_, hipStream_t s_, const SideStream &side_, PassTail &tail_)
 		: cs(cs_), sw(sw_), pw(pw_), tm(tm_), s(s_), side(side_), tail(tail_), alloc_result_block(alloc), v(class_views(pw_)), C(C_),
 		  V(sw_.V), T(2 * sw_.V + C_), S(n_stack), n_processed(n_processed_), dense_nb0(dense_nb0_), dense(dense_nb0_ >= 0),
 		  want_hp(sw_.hairpins != nullptr), lean(dense && !want_hp), narrow_oc(dense && pw_.narrow_ordcnt),
 		  narrow_sc(narrow_oc && pw_.narrow_srccnt), narrow_ic(narrow_sc && pw_.narrow_incnt),
-		  word_prefix(getenv("POVU_HIP_WORD_PREFIX") ? atoi(getenv("POVU_HIP_WORD_PREFIX")) : 0), rec_ps(narrow_ic && word_prefix != 1 && word_prefix != 2),
+		  word_prefix(hooks.word_prefix), rec_ps(narrow_ic && word_prefix != 1 && word_prefix != 2),
 		  rec_bs(narrow_sc && word_prefix != 1 && word_prefix != 3),
-		  lsz_cap(getenv("POVU_HIP_LSZ_FIELD") ? (unsigned)std::min(std::max(atoi(getenv("POVU_HIP_LSZ_FIELD")), 0), (int)LSZ_FIELD_CAP) : LSZ_FIELD_CAP), root_of{lean ? nullptr : pw_.t_root, cs_.voff, C_},
+		  lsz_cap(hooks.lsz_field), root_of{lean ? nullptr : pw_.t_root, cs_.voff, C_},
 		  ntiles((T + BX_TILE - 1) / BX_TILE)
 	{
 	}
@@ -1959,10 +1959,10 @@ static void emit_and_copy(ClassPass &P)
 }
 
 bool run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint32_t n_processed, uint32_t n_stack,
-		     int64_t dense_nb0, const std::function<void *(size_t)> &alloc_result_block, StageTimer &tm, hipStream_t s,
-		     const SideStream &side, PassTail &tail)
+		     int64_t dense_nb0, const PassHooks &hooks, const std::function<void *(size_t)> &alloc_result_block, StageTimer &tm,
+		     hipStream_t s, const SideStream &side, PassTail &tail)
 {
-	ClassPass P(cs, sw, pw, C, n_processed, n_stack, dense_nb0, alloc_result_block, tm, s, side, tail);
+	ClassPass P(cs, sw, pw, C, n_processed, n_stack, dense_nb0, hooks, alloc_result_block, tm, s, side, tail);
 	pw.V = P.V;
 	pw.E = sw.E;
 	pw.C = C;

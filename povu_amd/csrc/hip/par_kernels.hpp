@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "graph_kernels.hpp"
+#include "pass_hooks.hpp"
 #include "seq_kernels.hpp"
 
 #include <functional>
@@ -63,7 +64,6 @@ struct LszField {
 	__host__ __device__ constexpr uint32_t index(uint32_t u) const { return u & mask(); }
 	__host__ __device__ constexpr uint32_t size(uint32_t u) const { return (u >> 1) >> (abits - 1); }
 };
-static constexpr unsigned LSZ_FIELD_CAP = 8;
 constexpr LszField lsz_field(uint64_t S, unsigned cap = LSZ_FIELD_CAP)
 {
 	unsigned b = 1; // bits_for(S), common.hpp
@@ -236,8 +236,8 @@ void par_carve(Arena &ar, ParWs &pw, size_t V, size_t E, size_t Cmax, int groups
 // behind the placing of the brackets has run, and the caller runs the tree stage and this again with narrow_incnt off.
 static constexpr int64_t NB0_ON_DEVICE = int64_t(1) << 40;
 bool run_parallel_dg(const CompState &cs, SeqWs &sw, ParWs &pw, uint32_t C, uint32_t n_processed, uint32_t n_stack,
-		     int64_t dense_nb0, const std::function<void *(size_t)> &alloc_result_block, StageTimer &tm, hipStream_t s,
-		     const SideStream &side, PassTail &tail);
+		     int64_t dense_nb0, const PassHooks &hooks, const std::function<void *(size_t)> &alloc_result_block, StageTimer &tm,
+		     hipStream_t s, const SideStream &side, PassTail &tail);
 
 // Hairpin boundaries (`--hairpins`, flubbles.cpp:531-535, 621-656, 712-717) from the parallel class stage's
 // per-vertex flags; writes sw.hairpins / sw.c_nbry like the sequential kernels do.

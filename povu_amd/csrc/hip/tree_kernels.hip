@@ -402,7 +402,6 @@ static constexpr uint32_t PB_BRIDGE = 0x80000000u;
 // cstate (forest parent, bridge bit, visited bit: one load tells a walk "not yet visited", which covers "not across a
 // bridge" on the way down) and, for an ENTRY -- a root or the lower end of a bridge: the one side of its class the DFS
 // reaches first --, its DFS record dps = {parent across the bridge, scan slot of the parent it is found through}.
-static constexpr uint32_t CLASS_BUDGET = 256;  // sides a lane walks before it hands its class to the big-class walk
 static constexpr uint32_t CS_VISITED = 0x40000000u; // (side ids stay below 2^29, bit 31 is PB_BRIDGE)
 // One lane per SEGMENT: the side a segment is entered through and its far side ask different questions (the hooked link
 // into the segment / the black edge across it), so a lane per side left half of every wave idle in either branch; a lane
@@ -1736,6 +1735,7 @@ struct TreePass {
 	const uint32_t C, V, E, nS;
 	const uint32_t max_side_links;
 	const bool force_big_class_dfs;
+	const PassHooks &hooks;
 	const TreeViews v;
 	const unsigned long long *start_key;
 	const uint32_t NA;	// arcs of the spanning forest of the segments = positions of the tours
@@ -1748,17 +1748,17 @@ struct TreePass {
 	const uint8_t *dupflag = nullptr;
 
 	TreePass(const CompState &cs_, SeqWs &sw_, ParWs &pw_, TreeWs &tw_, uint32_t C_, uint32_t max_side_links_, bool big_dfs, bool sparse,
-		 StageTimer &tm_, hipStream_t s_)
+		 const PassHooks &hooks_, StageTimer &tm_, hipStream_t s_)
 		: cs(cs_), sw(sw_), pw(pw_), tw(tw_), tm(tm_), s(s_), C(C_), V(sw_.V), E(sw_.E), nS(2 * sw_.V), max_side_links(max_side_links_),
-		  force_big_class_dfs(big_dfs), v(tree_views(tw_, sw_.E, sw_.cur)),
+		  force_big_class_dfs(big_dfs), hooks(hooks_), v(tree_views(tw_, sw_.E, sw_.cur)),
 		  start_key((const unsigned long long *)cs_.start_key), NA(2 * (V - C)), n_slots(2 * (size_t)E), XW(NA / 64 + 1), n_events(3 * V),
-		  bitsA(sparse ? 4u : rank_bucket_bits()), bitsE(sparse ? 4u : rank_bucket_bits())
+		  bitsA(sparse ? 4u : rank_bucket_bits(hooks_)), bitsE(sparse ? 4u : rank_bucket_bits(hooks_))
 	{
 		tw.rec_stats[0].valid = tw.rec_stats[1].valid = false; // (what an earlier pass collected says nothing about this one)
 	}
-	// where ranking k (0 = the tour, 1 = the events) leaves the statistics of its records: nowhere, unless POVU_HIP_RANK_STATS
+	// where ranking k (0 = the tour, 1 = the events) leaves the statistics of its records: nowhere, unless PassHooks::rank_stats
 	// asks for them (debug hook: a kernel and a wait of its own behind the ranking)
-	RankRecStats *rec_stats(int k) { return getenv("POVU_HIP_RANK_STATS") ? &tw.rec_stats[k] : nullptr; }
+	RankRecStats *rec_stats(int k) { return hooks.rank_stats ? &tw.rec_stats[k] : nullptr; }
 	// (7.) one list per processed component, one two-event list per side of an unprocessed one
 	void enqueue_events()
 	{
@@ -1829,7 +1829,7 @@ static void walk_large_classes(TreePass &P, uint32_t n_big, const uint32_t *big_
 	}
 	uint32_t *pool_top = pw.err + PW_POOL_TOP, *walk_err = pw.err + PW_WALK_POOL;
 	LAUNCH(k_class_recs, nS, s, nS, cs.loff, cs.ladj, P.v.cstate, cs.ckey, tw.cproc, tw.wadj, tw.wrec, tw.wpar);
-	const uint32_t route = getenv("POVU_HIP_WALK_ROUTE") ? (uint32_t)atoi(getenv("POVU_HIP_WALK_ROUTE")) : 0u; // (A/B hook)
+	const uint32_t route = P.hooks.walk_route; // (A/B hook)
 	const uint32_t pool_cap = (uint32_t)std::min<size_t>(3 * (size_t)nS, 0xFFFFFFF0u);
 	// the two forms side by side (see k_class_walk_wave): the second on the context's walk stream when there is one
 	hipStream_t s2 = tw.walk_stream ? tw.walk_stream : s;
@@ -1873,13 +1873,9 @@ static void class_walks(TreePass &P)
 		// (gpurun_out r5m / r5n: 3072 -> 2.96 ms, 24 576 -> 2.83, 49 152 -> 2.76, 196 608 -> 2.73).  The number of classes
 		// stays on the device: the launch is a grid-stride loop, one synchronisation (how many classes overflowed) serves both.
 		const unsigned all_blocks = (nS + 63) / 64;
-		unsigned dfs_blocks = std::min(all_blocks, 49152u);
-		if (const char *ev = getenv("POVU_HIP_DFS_BLOCKS")) // (tuning hook)
-			dfs_blocks = std::min(all_blocks, std::max(1u, (unsigned)atoi(ev)));
+		const unsigned dfs_blocks = std::min(all_blocks, P.hooks.dfs_blocks); // (tuning hook; the default is the 49 152 above)
 		uint32_t *n_over = pw.err + PW_N_OVER;
-		uint32_t budget = CLASS_BUDGET;
-		if (const char *ev = getenv("POVU_HIP_CLASS_BUDGET")) // (tuning hook: sides a lane walks before it hands its class to the wave walk)
-			budget = (uint32_t)std::max(16, atoi(ev));
+		const uint32_t budget = P.hooks.class_budget; // (tuning hook; the default is CLASS_BUDGET)
 		KLAUNCH(k_class_dfs_small, dim3(dfs_blocks), dim3(64), 0, s, n_entry_dev, tw.entry_list, cs.loff, cs.ladj, v.cstate, tw.dps,
 			budget, n_over, v.over_list);
 		// How many classes overflowed is read without leaving the stream idle (HostScratch::mark): behind the word goes the
@@ -1986,9 +1982,9 @@ static void back_edges(TreePass &P)
 }
 
 int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw, uint32_t C, uint32_t max_side_links,
-			   bool force_big_class_dfs, bool force_sparse_splitters, StageTimer &tm, hipStream_t s)
+			   bool force_big_class_dfs, bool force_sparse_splitters, const PassHooks &hooks, StageTimer &tm, hipStream_t s)
 {
-	TreePass P(cs, sw, pw, tw, C, max_side_links, force_big_class_dfs, force_sparse_splitters, tm, s);
+	TreePass P(cs, sw, pw, tw, C, max_side_links, force_big_class_dfs, force_sparse_splitters, hooks, tm, s);
 	root_forest(P);
 	bridges_and_classes(P);
 	class_walks(P);

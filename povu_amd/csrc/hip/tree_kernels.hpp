@@ -38,7 +38,7 @@ struct TreeWs {
 	hipEvent_t walk_fork = nullptr, walk_join = nullptr;
 	Arena *walk_arena = nullptr;			  // where the wave walk's arrays are taken from when the pass needs them and they are not inside the stage block
 	bool walk_inline = true;
-	RankRecStats rec_stats[2];			  // the tour's and the events' records of the last pass (collected only under POVU_HIP_RANK_STATS)
+	RankRecStats rec_stats[2];			  // the tour's and the events' records of the last pass (collected only when PassHooks::rank_stats asks)
 };
 
 // groups: bit 0 = the arrays that outlive the tree stage, bit 1 = those that are dead when the class stage starts (tree_spans)
@@ -57,7 +57,7 @@ void tree_tour_words(const CompState &cs, uint32_t V, uint32_t E, TreeWs &tw, hi
 // Builds the reference's spanning tree of every processed component (tree arrays in sw, T-space
 // layout) and the dense list of from_bd back edges (pw.b_src / pw.b_tgt).  Returns their count.
 int64_t run_parallel_tree(const CompState &cs, SeqWs &sw, ParWs &pw, TreeWs &tw, uint32_t C, uint32_t max_side_links,
-			   bool force_big_class_dfs, bool force_sparse_splitters, StageTimer &tm, hipStream_t s);
+			   bool force_big_class_dfs, bool force_sparse_splitters, const PassHooks &hooks, StageTimer &tm, hipStream_t s);
 
 // back edges from_bd creates just before each tree vertex (w, T-space) and after the last child of each (tail, T-space); both
 // arrays must be zeroed by the caller.  Reads the state of the last run_parallel_tree.  Callers: the leaf passes and the

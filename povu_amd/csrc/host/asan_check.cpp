@@ -5,8 +5,12 @@
 // (host/vcf.cpp); the names builder and the VCF writer run once over a small hand-made povu_hip_calls.  Malformed inputs
 // must fail with an error, not with a fault.  The forest's wire formats (hip/forest_wire.hpp: what one process reads of
 // another's forest) run first, on hand-made tables, headers and extended trees: good ones round-trip, bad ones are refused.
+// Then the PVST writer (host/pvst_io.cpp) against the plain std::string writer it replaced, kept here as its restatement, on
+// generated trees, and its refusals; every .pvst that parses in full is also written back and compared byte for byte.  Then
+// the environment hooks of a pass (hip/pass_hooks.hpp) against a table of what the code they came from gave.
 #include "../../../include/povu_hip.h"
 #include "../hip/forest_wire.hpp"
+#include "../hip/pass_hooks.hpp"
 #include "gfa.hpp"
 
 #include <algorithm>
@@ -260,9 +264,294 @@ static int check_forest_wire()
 	return 0;
 }
 
+// ---- the PVST writer
+// The writer the library had for a tree with its -s vertices before pvst_emit served every form: a growing string and a
+// library call per number.  Kept only here, as the naive restatement of the line format.
+static std::string naive_pvst_text(const povu_hip_subtree *t)
+{
+	std::string o;
+	o += "H\t0.0.3\t.\t.\t.\n";
+	for (uint32_t v = 0; v < t->n_total; v++) {
+		o += (char)t->fam[v];
+		o += '\t';
+		o += std::to_string(v);
+		o += '\t';
+		if (t->fam[v] == 'D') {
+			o += '.';
+		} else { // id_or_t::as_str, include/povu/graph/types.hpp:85-95
+			o += t->or1[v] ? '<' : '>';
+			o += std::to_string(t->id1[v]);
+			o += t->or2[v] ? '<' : '>';
+			o += std::to_string(t->id2[v]);
+		}
+		o += '\t';
+		const uint32_t c0 = t->child_off[v], c1 = t->child_off[v + 1];
+		if (c0 == c1) {
+			o += '.';
+		} else { // print_with_comma, include/povu/common/utils.hpp:44-55
+			for (uint32_t k = c0; k < c1; k++) {
+				o += std::to_string(t->child[k]);
+				if (k + 1 < c1)
+					o += ", ";
+			}
+		}
+		o += '\t';
+		if (t->route[v])
+			o += (char)t->route[v];
+		else
+			o += '.';
+		o += '\n';
+	}
+	return o;
+}
+
+// a tree in both forms of the writer's input: the arrays of a PVST (parent) and the extended tree of -s (children lists)
+struct TextTree {
+	std::vector<uint8_t> fam, or1, or2, route;
+	std::vector<uint32_t> id1, id2, parent, coff, child;
+	void add(char letter, uint32_t par, uint32_t a, uint32_t z, uint8_t o1 = 0, uint8_t o2 = 0, char r = 'L')
+	{
+		fam.push_back((uint8_t)letter), parent.push_back(par), id1.push_back(a), id2.push_back(z), or1.push_back(o1), or2.push_back(o2);
+		route.push_back(letter == 'D' ? 0 : (uint8_t)r);
+	}
+	void children_from_parents()
+	{
+		const uint32_t n = (uint32_t)fam.size();
+		coff.assign(n + 1, 0);
+		for (uint32_t v = 1; v < n; v++)
+			coff[parent[v] + 1]++;
+		for (uint32_t v = 0; v < n; v++)
+			coff[v + 1] += coff[v];
+		child.assign(coff[n] + 1, 0); // (+1: never an empty vector's null data())
+		std::vector<uint32_t> at(coff.begin(), coff.end() - 1);
+		for (uint32_t v = 1; v < n; v++)
+			child[at[parent[v]]++] = v;
+	}
+	povu_hip_subtree view() const
+	{
+		povu_hip_subtree t{};
+		t.n_total = t.n_flubble_like = (uint32_t)fam.size();
+		t.fam = fam.data(), t.or1 = or1.data(), t.or2 = or2.data(), t.route = route.data();
+		t.id1 = id1.data(), t.id2 = id2.data(), t.child_off = coff.data(), t.child = child.data();
+		return t;
+	}
+};
+
+// the subtree form against the restatement; with `arrays` also the array form (the letters given, and left out when they are
+// D / F) against the same bytes
+static bool same_text(const TextTree &x, bool arrays)
+{
+	const povu_hip_subtree t = x.view();
+	const std::string want = naive_pvst_text(&t);
+	auto is = [&](char *got, size_t len) {
+		const bool eq = got && len == want.size() && memcmp(got, want.data(), len) == 0 && got[len] == 0;
+		povu_hip_buffer_free(got);
+		return eq;
+	};
+	size_t len = 0;
+	char *got = povu_hip_pvst_format_subtree(&t, &len);
+	if (!is(got, len))
+		return false;
+	if (!arrays)
+		return true;
+	const uint32_t n = t.n_total;
+	got = povu_hip_pvst_format_fam(n, t.id1, t.id2, t.or1, t.or2, x.parent.data(), t.fam, &len);
+	if (!is(got, len))
+		return false;
+	bool plain = true;
+	for (uint32_t v = 1; v < n; v++)
+		plain = plain && t.fam[v] == 'F';
+	if (plain) {
+		got = povu_hip_pvst_format(n, t.id1, t.id2, t.or1, t.or2, x.parent.data(), &len);
+		if (!is(got, len))
+			return false;
+	}
+	return true;
+}
+
+static int check_pvst_writer()
+{
+#define WANT(c)                                                                                                                   \
+	do {                                                                                                                      \
+		if (!(c))                                                                                                         \
+			return __LINE__;                                                                                          \
+	} while (0)
+	const uint32_t NIL = POVU_HIP_NIL;
+	// every line letter, both routes and none, both orientations (the letters C M S and the route R: the subtree form only)
+	{
+		TextTree x;
+		x.add('D', NIL, 0, 0);
+		const char letters[] = "FTOCMS";
+		for (int k = 0; k < 6; k++)
+			x.add(letters[k], k < 3 ? 0 : (uint32_t)k - 2, 10 + k, 20 + k, k & 1, (k >> 1) & 1, k % 3 == 0 ? 'L' : k % 3 == 1 ? 'R' : 0);
+		x.children_from_parents();
+		WANT(same_text(x, false));
+		TextTree y; // (the letters and the route the array form knows)
+		y.add('D', NIL, 0, 0);
+		for (int k = 0; k < 6; k++)
+			y.add(letters[k % 3], (uint32_t)k / 2, 10 + k, 20 + k, k & 1, (k >> 1) & 1);
+		y.children_from_parents();
+		WANT(same_text(y, true));
+	}
+	// segment ids at every edge of the digit count
+	{
+		TextTree x;
+		x.add('D', NIL, 0, 0);
+		const uint32_t edge[] = {0, 1, 9, 10, 99, 100, 999, 1000, 9999, 10000, 99999, 100000, 999999, 1000000, 9999999, 10000000,
+					 99999999, 100000000, 999999999, 1000000000, 4294967295u};
+		const uint32_t ne = sizeof edge / sizeof *edge;
+		for (uint32_t k = 0; k < ne; k++)
+			x.add('F', 0, edge[k], edge[ne - 1 - k], k & 1, ~k & 1);
+		x.children_from_parents();
+		WANT(same_text(x, true));
+	}
+	// vertices with 1 000, 2, 1 and 0 children
+	{
+		TextTree x;
+		x.add('D', NIL, 0, 0);
+		for (uint32_t v = 1; v <= 1003; v++)
+			x.add('F', v <= 1000 ? 0 : v <= 1002 ? 1 : 2, v, v + 1);
+		x.children_from_parents();
+		WANT(x.coff[1] == 1000 && x.coff[2] - x.coff[1] == 2 && x.coff[3] - x.coff[2] == 1 && x.coff[4] == x.coff[3]);
+		WANT(same_text(x, true));
+	}
+	// chains and stars of 1, 2 and 3 vertices
+	for (uint32_t n = 1; n <= 3; n++)
+		for (int star = 0; star < 2; star++) {
+			TextTree x;
+			x.add('D', NIL, 0, 0);
+			for (uint32_t v = 1; v < n; v++)
+				x.add('F', star ? 0 : v - 1, 2 * v, 2 * v + 1);
+			x.children_from_parents();
+			WANT(same_text(x, true));
+		}
+	// every id ten digits wide: no text of that many lines is longer
+	{
+		TextTree x;
+		x.add('D', NIL, 0, 0);
+		for (uint32_t v = 1; v < 50; v++)
+			x.add('F', (v - 1) / 2, 4294967295u, 4000000000u + v, 1, 1);
+		x.children_from_parents();
+		WANT(same_text(x, true));
+	}
+	// an extended tree that lists its vertices far more often than once (a concealed vertex is listed under two parents;
+	// here every vertex under every vertex, 40 times): the text is much longer than a tree's of as many lines
+	{
+		TextTree x;
+		x.add('D', NIL, 0, 0);
+		x.add('C', 0, 4294967295u, 4294967294u, 1, 1, 'R');
+		x.add('M', 0, 4294967293u, 4294967292u, 1, 1, 'R');
+		x.coff.assign(1, 0);
+		for (uint32_t v = 0; v < 3; v++) {
+			for (uint32_t k = 0; k < 120; k++)
+				x.child.push_back(k % 3);
+			x.coff.push_back((uint32_t)x.child.size());
+		}
+		WANT(x.child.size() > 3 - 1);
+		WANT(same_text(x, false));
+	}
+	// the refusals
+	{
+		const uint32_t id[] = {0, 1, 2}, par[] = {NIL, 0, 1}, par_self[] = {NIL, 1, 1}, par_late[] = {NIL, 0, 5};
+		const uint8_t orr[] = {0, 0, 1}, fam[] = {'D', 'T', 'O'};
+		size_t len = 0;
+		char *ok = povu_hip_pvst_format_fam(3, id, id, orr, orr, par, fam, &len);
+		WANT(ok && len);
+		povu_hip_buffer_free(ok);
+		WANT(!povu_hip_pvst_format_fam(0, id, id, orr, orr, par, fam, &len) && !povu_hip_pvst_format(0, id, id, orr, orr, par, &len));
+		WANT(!povu_hip_pvst_format_fam(3, nullptr, id, orr, orr, par, fam, &len) && !povu_hip_pvst_format(3, nullptr, id, orr, orr, par, &len));
+		WANT(!povu_hip_pvst_format_fam(3, id, nullptr, orr, orr, par, fam, &len) && !povu_hip_pvst_format(3, id, nullptr, orr, orr, par, &len));
+		WANT(!povu_hip_pvst_format_fam(3, id, id, nullptr, orr, par, fam, &len) && !povu_hip_pvst_format(3, id, id, nullptr, orr, par, &len));
+		WANT(!povu_hip_pvst_format_fam(3, id, id, orr, nullptr, par, fam, &len) && !povu_hip_pvst_format(3, id, id, orr, nullptr, par, &len));
+		WANT(!povu_hip_pvst_format_fam(3, id, id, orr, orr, nullptr, fam, &len) && !povu_hip_pvst_format(3, id, id, orr, orr, nullptr, &len));
+		for (const char *bad : {"FTO", "DDO", "DTD", "DCO", "DTM", "DSF", "DXF", "dTO"}) // (a letter outside D / F, T, O, or in the other's place)
+			WANT(!povu_hip_pvst_format_fam(3, id, id, orr, orr, par, reinterpret_cast<const uint8_t *>(bad), &len));
+		WANT(!povu_hip_pvst_format_fam(3, id, id, orr, orr, par_self, fam, &len) && !povu_hip_pvst_format(3, id, id, orr, orr, par_self, &len));
+		WANT(!povu_hip_pvst_format_fam(3, id, id, orr, orr, par_late, fam, &len) && !povu_hip_pvst_format(3, id, id, orr, orr, par_late, &len));
+		WANT(!povu_hip_pvst_format_subtree(nullptr, &len));
+	}
+#undef WANT
+	return 0;
+}
+
+// a .pvst that parsed, written back through the array form of the writer (the letters of the file given): the bytes of the
+// file.  Only for files that number their lines by row and hold the letters that form knows.
+static bool pvst_round_trip(const povu_pvst_doc *d, const std::string &text)
+{
+	size_t len = 0;
+	char *got = povu_hip_pvst_format_fam(d->n, d->a_id, d->z_id, d->a_or, d->z_or, d->parent, reinterpret_cast<const uint8_t *>(d->type), &len);
+	const bool eq = got && len == text.size() && memcmp(got, text.data(), len) == 0;
+	povu_hip_buffer_free(got);
+	return eq;
+}
+
+// ---- the environment hooks of a pass: read_pass_hooks() against what the expressions it replaced gave for the same text.
+// Those stood at their points of use (the line numbers: the files as they were before pass_hooks.hpp), `ev` = the variable's text:
+//   POVU_HIP_WIDE_COUNTS  povu_hip.hip:911-912      ev ? atoi(ev) : 0
+//   POVU_HIP_WORD_PREFIX  par_kernels.hip:1513      ev ? atoi(ev) : 0
+//   POVU_HIP_LSZ_FIELD    par_kernels.hip:1515      ev ? (unsigned)min(max(atoi(ev), 0), (int)LSZ_FIELD_CAP) : LSZ_FIELD_CAP    (the cap: 8)
+//   POVU_HIP_WALK_ROUTE   tree_kernels.hip:1832     ev ? (uint32_t)atoi(ev) : 0u
+//   POVU_HIP_DFS_BLOCKS   tree_kernels.hip:1876-78  min(all_blocks, ev ? max(1u, (unsigned)atoi(ev)) : 49152u)    (the value before the min)
+//   POVU_HIP_CLASS_BUDGET tree_kernels.hip:1880-82  ev ? (uint32_t)max(16, atoi(ev)) : CLASS_BUDGET    (256)
+//   POVU_HIP_RANK_STATS   tree_kernels.hip:1761     ev != nullptr
+//   POVU_HIP_RANK_BITS    list_rank.hip:27-29       ev ? (unsigned)min(6, max(2, atoi(ev))) : 3u
+// atoi of "" and of text without digits is 0; a negative number converted to unsigned wraps.
+static int check_pass_hooks()
+{
+	using povu_hip::PassHooks;
+	struct Row {
+		const char *text; // null: unset
+		int64_t want;
+	};
+	struct Hook {
+		const char *name;
+		int64_t (*get)(const PassHooks &);
+		std::vector<Row> rows;
+	};
+	const std::vector<Hook> hooks = {
+		{"POVU_HIP_WIDE_COUNTS", [](const PassHooks &h) { return (int64_t)h.wide_counts; },
+		 {{nullptr, 0}, {"1", 1}, {"2", 2}, {"3", 3}, {"0", 0}, {"-1", -1}, {"9", 9}, {"", 0}, {"words", 0}}},
+		{"POVU_HIP_WORD_PREFIX", [](const PassHooks &h) { return (int64_t)h.word_prefix; },
+		 {{nullptr, 0}, {"1", 1}, {"2", 2}, {"3", 3}, {"0", 0}, {"-1", -1}, {"9", 9}, {"", 0}, {"words", 0}}},
+		{"POVU_HIP_LSZ_FIELD", [](const PassHooks &h) { return (int64_t)h.lsz_field; },
+		 {{nullptr, 8}, {"5", 5}, {"0", 0}, {"8", 8}, {"-3", 0}, {"9", 8}, {"99", 8}, {"", 0}, {"wide", 0}}},
+		{"POVU_HIP_WALK_ROUTE", [](const PassHooks &h) { return (int64_t)h.walk_route; },
+		 {{nullptr, 0}, {"1", 1}, {"2", 2}, {"-1", 4294967295ll}, {"", 0}, {"left", 0}}},
+		{"POVU_HIP_DFS_BLOCKS", [](const PassHooks &h) { return (int64_t)h.dfs_blocks; },
+		 {{nullptr, 49152}, {"3072", 3072}, {"1", 1}, {"0", 1}, {"-5", 4294967291ll}, {"196608", 196608}, {"", 1}, {"many", 1}}},
+		{"POVU_HIP_CLASS_BUDGET", [](const PassHooks &h) { return (int64_t)h.class_budget; },
+		 {{nullptr, 256}, {"64", 64}, {"16", 16}, {"15", 16}, {"0", 16}, {"-7", 16}, {"100000", 100000}, {"", 16}, {"big", 16}}},
+		{"POVU_HIP_RANK_STATS", [](const PassHooks &h) { return (int64_t)h.rank_stats; },
+		 {{nullptr, 0}, {"1", 1}, {"0", 1}, {"", 1}, {"no", 1}}},
+		{"POVU_HIP_RANK_BITS", [](const PassHooks &h) { return (int64_t)h.rank_bits; },
+		 {{nullptr, 3}, {"4", 4}, {"2", 2}, {"6", 6}, {"1", 2}, {"-4", 2}, {"7", 6}, {"40", 6}, {"", 2}, {"bits", 2}}},
+	};
+	for (const Hook &k : hooks)
+		unsetenv(k.name);
+	for (const Hook &k : hooks) {
+		for (const Row &r : k.rows) {
+			if (r.text)
+				setenv(k.name, r.text, 1);
+			else
+				unsetenv(k.name);
+			const PassHooks h = povu_hip::read_pass_hooks();
+			if (k.get(h) != r.want) {
+				fprintf(stderr, "host_asan_check: %s=%s gives %lld, not %lld\n", k.name, r.text ? r.text : "(unset)", (long long)k.get(h),
+					(long long)r.want);
+				return 1;
+			}
+			for (const Hook &o : hooks) // (a variable moves its own field only)
+				if (&o != &k && o.get(h) != o.rows[0].want)
+					return 2;
+		}
+		unsetenv(k.name);
+	}
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
-	unsigned long ok = 0, rejected = 0;
+	unsigned long ok = 0, rejected = 0, written_back = 0;
 	if (int line = check_forest_wire()) {
 		fprintf(stderr, "host_asan_check: forest_wire check failed at line %d\n", line);
 		return 13;
@@ -270,6 +559,14 @@ int main(int argc, char **argv)
 	printf("host_asan_check: forest_wire ok\n");
 	if (int rc = check_vcf_writer())
 		return rc;
+	if (int line = check_pvst_writer()) {
+		fprintf(stderr, "host_asan_check: PVST writer check failed at line %d\n", line);
+		return 14;
+	}
+	printf("host_asan_check: pvst_writer ok\n");
+	if (check_pass_hooks())
+		return 15;
+	printf("host_asan_check: pass_hooks ok\n");
 	for (int i = 1; i < argc; i++) {
 		const std::string path = argv[i];
 		if (ends_with(path, ".gfa")) {
@@ -304,6 +601,13 @@ int main(int argc, char **argv)
 						if ((s->parent[q] != POVU_HIP_NIL && s->parent[q] >= s->n) || s->height[q] > d->n)
 							return 9;
 					povu_hip_sites_free(s);
+					if (len == text.size()) {
+						if (!pvst_round_trip(d, text)) {
+							fprintf(stderr, "host_asan_check: %s is not what the writer makes of its parse\n", path.c_str());
+							return 16;
+						}
+						written_back++;
+					}
 					povu_pvst_doc_free(d);
 					ok++;
 				} else {
@@ -314,6 +618,6 @@ int main(int argc, char **argv)
 			}
 		}
 	}
-	printf("host_asan_check: %lu parsed, %lu rejected\n", ok, rejected);
+	printf("host_asan_check: %lu parsed, %lu rejected, %lu written back\n", ok, rejected, written_back);
 	return 0;
 }

@@ -1,5 +1,6 @@
-// pvst_io.cpp -- reader for the PVST wire format (the consumer side of row H).
-// Follows mto::from_pvst::read_pvst (src/mto/from_pvst.cpp:162-302) and pvst::Tree::comp_heights
+// pvst_io.cpp -- writer and reader of the PVST wire format (row H and its consumer side).
+// The writer: one emitter (pvst_emit) over one view of a tree's lines behind povu_hip_pvst_format, _format_fam and
+// _format_subtree; follows mto::to_pvst::write_pvst (src/mto/to_pvst.cpp:23-109).  The reader follows mto::from_pvst::read_pvst (src/mto/from_pvst.cpp:162-302) and pvst::Tree::comp_heights
 // (include/povu/graph/pvst.hpp:807-836): five tab-separated columns per line, header `H <version>`
 // (only 0.0.3 is supported, :37-76), vertex lines D/F/T/O/M/C/S with label `<or><id><or><id>`
 // (:136-158), children as comma-separated FILE vertex ids (:83-130, :284-297), route L/R (:155-157).
@@ -8,7 +9,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -87,6 +90,135 @@ extern "C" int povu_hip_gfa_write(const char *path, uint32_t n_vtx, const uint32
 		return 1;
 	}
 	return 0;
+}
+
+// ---- the PVST text of one tree
+namespace
+{
+// What the writer needs of every vertex v < n of a tree, whichever arrays it comes from.
+struct PvstLines {
+	uint32_t n;
+	const uint8_t *letter;		   // line letter; null: D for vertex 0, F below it
+	const uint32_t *id1, *id2;	   // the two oriented endpoints (or: 0 = '>', else '<'); a D line has none
+	const uint8_t *or1, *or2;
+	const uint32_t *child_off, *child; // children of v: child[child_off[v] .. child_off[v + 1])
+	const uint8_t *route;		   // route letter, 0 = none; null: none on a D line, L on every other
+};
+
+char *put_u32(char *o, uint32_t v)
+{
+	static const char D2[] = "0001020304050607080910111213141516171819202122232425262728293031323334353637383940414243444546474849"
+				 "5051525354555657585960616263646566676869707172737475767778798081828384858687888990919293949596979899";
+	const int len = v < 10u ? 1 : v < 100u ? 2 : v < 1000u ? 3 : v < 10000u ? 4 : v < 100000u ? 5 : v < 1000000u ? 6 :
+			v < 10000000u ? 7 : v < 100000000u ? 8 : v < 1000000000u ? 9 : 10;
+	char *e = o + len;
+	o = e;
+	while (v >= 100u) {
+		const uint32_t r = v % 100u;
+		v /= 100u;
+		e -= 2;
+		e[0] = D2[2 * r], e[1] = D2[2 * r + 1];
+	}
+	if (v >= 10u)
+		e[-2] = D2[2 * v], e[-1] = D2[2 * v + 1];
+	else
+		e[-1] = (char)('0' + v);
+	return o;
+}
+
+// write_pvst, src/mto/to_pvst.cpp:23-109.  One buffer of the largest size the text can have, written front to back (a
+// 10^6-vertex PVST is 5 * 10^6 numbers: a library call per number and a growing string were most of the CLI's write
+// time).  The size comes from what the view lists, not from what a tree would: a vertex may be listed under several parents.
+char *pvst_emit(const PvstLines &t, size_t *len)
+{
+	const uint32_t n = t.n;
+	size_t listed = 0; // child entries the lines below will print
+	for (uint32_t v = 0; v < n; v++)
+		listed += t.child_off[v + 1] > t.child_off[v] ? t.child_off[v + 1] - t.child_off[v] : 0;
+	// header 14 and the closing 0; per line at most: letter + tab 2, vertex 10, tab 1, the two oriented endpoints 22, tab 1,
+	// '.' 1, closing field 3; per child entry 10 + ", "
+	const size_t cap = 16 + (size_t)n * 40 + listed * 12;
+	char *buf = (char *)malloc(cap);
+	if (!buf)
+		return nullptr;
+	char *o = buf;
+	memcpy(o, "H\t0.0.3\t.\t.\t.\n", 14); // to_pvst.cpp:23-28
+	o += 14;
+	for (uint32_t v = 0; v < n; v++) {
+		const char letter = t.letter ? (char)t.letter[v] : (v == 0 ? 'D' : 'F'); // to_pvst.cpp:52-79: the line identifier follows the vertex family
+		*o++ = letter;
+		*o++ = '\t';
+		o = put_u32(o, v);
+		*o++ = '\t';
+		if (letter == 'D') {
+			*o++ = '.';
+		} else { // id_or_t::as_str, include/povu/graph/types.hpp:85-95
+			*o++ = t.or1[v] ? '<' : '>';
+			o = put_u32(o, t.id1[v]);
+			*o++ = t.or2[v] ? '<' : '>';
+			o = put_u32(o, t.id2[v]);
+		}
+		*o++ = '\t';
+		const uint32_t c0 = t.child_off[v], c1 = t.child_off[v + 1];
+		if (c0 == c1) {
+			*o++ = '.';
+		} else { // print_with_comma, include/povu/common/utils.hpp:44-55
+			for (uint32_t k = c0; k < c1; k++) {
+				o = put_u32(o, t.child[k]);
+				if (k + 1 < c1)
+					*o++ = ',', *o++ = ' ';
+			}
+		}
+		*o++ = '\t';
+		const char route = t.route ? (char)t.route[v] : (letter == 'D' ? 0 : 'L');
+		*o++ = route ? route : '.';
+		*o++ = '\n';
+	}
+	*o = 0;
+	if (len)
+		*len = (size_t)(o - buf);
+	return buf;
+}
+} // namespace
+
+// ... of a tree with its -s vertices
+extern "C" char *povu_hip_pvst_format_subtree(const povu_hip_subtree *t, size_t *len)
+{
+	if (!t)
+		return nullptr;
+	return pvst_emit(PvstLines{t->n_total, t->fam, t->id1, t->id2, t->or1, t->or2, t->child_off, t->child, t->route}, len);
+}
+
+extern "C" char *povu_hip_pvst_format(uint32_t n_pvst, const uint32_t *a_id, const uint32_t *z_id, const uint8_t *a_or,
+				      const uint8_t *z_or, const uint32_t *parent, size_t *len)
+{
+	return povu_hip_pvst_format_fam(n_pvst, a_id, z_id, a_or, z_or, parent, nullptr, len);
+}
+
+// ... of a PVST in its arrays, with the line letters of --leaf-subflubbles if given
+extern "C" char *povu_hip_pvst_format_fam(uint32_t n_pvst, const uint32_t *a_id, const uint32_t *z_id, const uint8_t *a_or,
+					  const uint8_t *z_or, const uint32_t *parent, const uint8_t *fam, size_t *len)
+{
+	if (n_pvst == 0 || !a_id || !z_id || !a_or || !z_or || !parent)
+		return nullptr;
+	if (fam)
+		for (uint32_t v = 0; v < n_pvst; v++)
+			if (fam[v] != (v == 0 ? 'D' : 'F') && (v == 0 || (fam[v] != 'T' && fam[v] != 'O')))
+				return nullptr; // line letters this writer knows: D for the root, F / T / O below it
+	for (uint32_t v = 1; v < n_pvst; v++)
+		if (parent[v] >= v)
+			return nullptr; // a PVST parent always precedes its children (emission order)
+	const uint32_t n = n_pvst;
+	// children of every PVST vertex in emission order (children_v push_back, pvst.hpp:882-892)
+	std::unique_ptr<uint32_t[]> coff(new uint32_t[(size_t)n + 2]), cadj(new uint32_t[n]); // (uninitialised)
+	std::fill(coff.get(), coff.get() + n + 2, 0u);
+	for (uint32_t v = 1; v < n; v++)
+		coff[parent[v] + 2]++; // (shifted by one: after the sums coff[p + 1] is where p's children start, and the fill
+	for (uint32_t v = 0; v < n; v++) //  below advances it to where they end = where those of p + 1 start)
+		coff[v + 2] += coff[v + 1];
+	for (uint32_t v = 1; v < n; v++)
+		cadj[coff[parent[v] + 1]++] = v;
+	return pvst_emit(PvstLines{n, fam, a_id, z_id, a_or, z_or, coff.get(), cadj.get(), nullptr}, len);
 }
 
 extern "C" povu_pvst_doc *povu_pvst_parse(const char *text, size_t len, char *err, size_t errlen)

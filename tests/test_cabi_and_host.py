@@ -573,6 +573,11 @@ def test_host_code_under_address_and_ub_sanitizers(golden_dir, tmp_path):
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
     assert "parsed" in r.stdout
     assert "forest_wire ok" in r.stdout  # (the tree table, the pack / share headers and the extended trees: hip/forest_wire.hpp)
+    # the PVST writer against its naive restatement and its refusals; the hooks of a pass against the table of what they gave
+    # where they used to be read; every golden PVST written back from its parse, byte for byte
+    assert "pvst_writer ok" in r.stdout and "pass_hooks ok" in r.stdout
+    n_pvst = len(glob.glob(os.path.join(golden_dir, "pvst", "*.pvst")))
+    assert n_pvst >= 13 and f"{n_pvst} written back" in r.stdout
 
 
 def test_gfa_writer_is_the_inverse_of_the_loader_contract(tmp_path):

@@ -17,10 +17,12 @@ HIP = os.path.join(ROOT, "povu_amd", "csrc", "hip")
 def test_constants_mirror_the_sources():
     tree = open(os.path.join(HIP, "tree_kernels.hip")).read()
     step = open(os.path.join(HIP, "walk_step.inc")).read()
+    hooks = open(os.path.join(HIP, "pass_hooks.hpp")).read()  # (the budget and its floor: with the hooks of a pass)
 
-    def const(name):
-        return int(re.search(r"constexpr uint32_t %s = (\d+);" % name, tree).group(1))
-    assert const("CLASS_BUDGET") == M.CLASS_BUDGET and "std::max(16, atoi(ev))" in tree and M.BUDGET_FLOOR == 16
+    def const(name, text=tree):
+        return int(re.search(r"constexpr uint32_t %s = (\d+);" % name, text).group(1))
+    assert const("CLASS_BUDGET", hooks) == M.CLASS_BUDGET and "std::max(16, atoi(ev))" in hooks and M.BUDGET_FLOOR == 16
+    assert "uint32_t class_budget = CLASS_BUDGET;" in hooks and "budget = P.hooks.class_budget;" in tree
     assert "if (sides > budget)" in tree  # (tested after each advance; a follow-through pair counts two)
     assert const("DFS_STK") == M.DFS_STK and "k = up.y + 1;" in tree
     assert const("W_INLINE") == M.W_INLINE and "if (e0.x > W_INLINE)" in step
