@@ -1034,6 +1034,69 @@ void povu_hip_vcf_hap_free(povu_hip_vcf_hap *h);
 char *povu_hip_vcf_hap_text(const povu_hip_vcf_hap *h, const povu_hip_vcf_doc *doc_a, const povu_hip_vcf_doc *doc_b, size_t *haplotypes_len,
 			    char **summary, size_t *summary_len);
 
+/* ---- consensus haplotypes: a document's calls applied to the paths its CHROMs name (INTEGRATION.md "Consensus haplotypes") ---- */
+#define POVU_HIP_C_ROUNDTRIP 1u /* povu_hip_vcf_cons_opts.flags: compare every haplotype with the one path of its slot */
+#define POVU_HIP_C_NO_TEXT 2u	/* lengths, counts and the round trip only: the text stays on the device */
+#define POVU_HIP_C_TIME_WRITE 8u /* write_ms is measured: an event pair around the materialiser, and the call waits for it there */
+/* (POVU_HIP_V_FORCE_TIER2, 4, is read beside them: every item through the wave-per-item kernel; tests) */
+/* bytes of the output a workgroup of the materialiser writes: 256 lanes, one 16-byte store each (DESIGN.md "Consensus
+ * haplotypes") */
+#define POVU_HIP_C_TILE_BYTES 4096u
+/* the round trip of a haplotype */
+#define POVU_HIP_C_RT_NONE 0u	   /* not asked for */
+#define POVU_HIP_C_RT_EQUAL 1u	   /* the consensus spells the path, letters folded */
+#define POVU_HIP_C_RT_DIFFER 2u	   /* rt_first_diff: the first differing offset, the shorter length when one is a prefix */
+#define POVU_HIP_C_RT_NO_PATH 3u   /* no path in the slot (and the contig); the column names no sample; a phase beyond its slots */
+#define POVU_HIP_C_RT_AMBIGUOUS 4u /* more than one */
+#define POVU_HIP_C_N_RT 5u
+typedef struct {
+	uint32_t flags;		      /* POVU_HIP_C_*, POVU_HIP_V_FORCE_TIER2 */
+	uint32_t n_select;	      /* entries of both lists below */
+	const uint32_t *select_col;   /* [n_select] sample columns, or NULL: every column */
+	const uint32_t *select_chrom; /* [n_select] CHROM ids of the document, or NULL: every CHROM.  Both lists are read as sets
+				       * (an entry may repeat): the haplotypes are those of a selected column on a selected CHROM */
+} povu_hip_vcf_cons_opts;
+typedef struct {
+	uint64_t n_haps; /* haplotypes, in (CHROM id, column, phase) order: one per (CHROM, column, phase) with a task on a placed
+			  * record of the CHROM */
+	const uint32_t *hap_chrom, *hap_col, *hap_phase; /* [n_haps] */
+	const uint64_t *hap_len, *hap_off;		 /* [n_haps] bytes, and where they begin in `text` */
+	/* [n_haps] kept edits; edits dropped as duplicates, as enclosed, as overlapping; tasks that name an unspelled ALT or one
+	 * beyond the record's; placed records of the CHROM without a task */
+	const uint32_t *n_applied, *n_duplicate, *n_enclosed, *n_overlap, *n_unspelled, *n_nocall;
+	const uint8_t *rt_status;  /* [n_haps] POVU_HIP_C_RT_* */
+	const uint32_t *rt_path;   /* [n_haps] the path compared with (POVU_HIP_NIL: none) */
+	const uint64_t *rt_path_len, *rt_first_diff; /* [n_haps] its bases (0: none); ~0 unless _RT_DIFFER */
+	const char *text;	   /* [n_text_bytes] the haplotypes one after another; NULL under POVU_HIP_C_NO_TEXT */
+	uint64_t n_text_bytes;	   /* the sum of hap_len */
+	uint64_t n_unplaced;	   /* records */
+	uint64_t n_tier2;	   /* items the wave-per-item kernel trimmed */
+	uint32_t roundtrip;	   /* 1: POVU_HIP_C_ROUNDTRIP was set */
+	double device_ms;	   /* HIP-event time of the call, first upload to last byte on the host */
+	double write_ms;	   /* ... of the materialiser alone under POVU_HIP_C_TIME_WRITE, else 0 */
+} povu_hip_vcf_cons;
+/* Applies the calls of `doc` (of povu_hip_vcf_parse) to the resident paths its CHROMs name (path_name[n_paths]: the resident
+ * paths' names; of several paths of one name the first counts) and gives every haplotype's text.  opts NULL: no flag, no
+ * selection.  Refused: null context or document, a document whose arrays do not belong together, no resident paths or
+ * sequences, another number of path names, a selected column or CHROM the document does not have, a POS of 2^40 or more,
+ * 2^32 - 64 or more records, alleles, items, tasks or text bytes, an output of 2^32 - 64 bytes or more (the message gives the
+ * byte count: select fewer columns or CHROMs per call), and when device memory runs out.  A document without a haplotype is
+ * not refused: n_haps is 0.  Free with povu_hip_vcf_cons_free. */
+povu_hip_vcf_cons *povu_hip_vcf_consensus(povu_hip_ctx *ctx, const povu_hip_vcf_doc *doc, const char *const *path_name, uint32_t n_paths,
+					  const povu_hip_vcf_cons_opts *opts, char *err, size_t errlen);
+void povu_hip_vcf_cons_free(povu_hip_vcf_cons *c);
+/* The three files of `povu vcf --consensus` (host only; the result may be hand-made).  consensus.fa: per haplotype a record
+ * `>{sample}#{hap}#{CHROM}` -- hap the PanSN hap number of the slot (names: povu_hip_vcf_names_make of path_name) where the
+ * sample has one for the phase, else the phase -- and its text in lines of `width` bytes (0: one line; an empty haplotype has
+ * no line); empty when c->text is NULL.  roundtrip.tsv: the header `CHROM sample phase status len path path_len first_diff
+ * applied duplicate enclosed overlap unspelled nocall` (tabs), then one line per haplotype that is not _RT_EQUAL; path and
+ * path_len are `.` without a path, first_diff is `.` unless _RT_DIFFER.  cons_summary.txt: the haplotypes and their bases, the
+ * haplotypes of every round-trip status, the edits of every kind, the unplaced records when there are any.  All malloc'd
+ * (povu_hip_buffer_free); NULL when the arguments do not belong together. */
+char *povu_hip_vcf_cons_text(const povu_hip_vcf_cons *c, const povu_hip_vcf_doc *doc, const povu_hip_call_names *names,
+			     const char *const *path_name, uint32_t width, size_t *fasta_len, char **roundtrip, size_t *roundtrip_len, char **summary,
+			     size_t *summary_len);
+
 /* ---- measurement (bench.py, povu-stage-cost lines) ---- */
 typedef struct {
 	char name[48];	  /* kernel group */

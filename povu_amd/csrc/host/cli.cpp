@@ -11,6 +11,8 @@
 //   INTEGRATION.md "VCF comparison", on the GPU; -i is accepted and not read)
 //   povu ... vcf -c <vcf> -d <vcf> --compare --haplotypes [-i <gfa>] [--max-reach <n>] -o <dir>   (INTEGRATION.md "Haplotype
 //   comparison", on the GPU: with -i the GFA's paths are the reference, without it the REF fields are)
+//   povu ... vcf -i <gfa> -c <vcf> --consensus [--roundtrip] [--no-fasta] [--sample <name>]... [--chrom <name>]... [--line-width <n>]
+//   -o <dir>   (INTEGRATION.md "Consensus haplotypes", on the GPU)
 #include "decompose.hpp"
 
 #include <cstdlib>
@@ -122,7 +124,15 @@ static void usage(std::ostream &os)
 	      "                                          spell, and write haplotypes.tsv and hap_summary.txt; with -i the GFA's paths are\n"
 	      "                                          the reference, without it the REF fields are [default: false]\n"
 	      "        --max-reach=[n]                   with --haplotypes and -i: bases an indel may reach through its repeat in either\n"
-	      "                                          direction, 0 to 65536 [default: 256]\n";
+	      "                                          direction, 0 to 65536 [default: 256]\n"
+	      "        --consensus                       instead of --report: apply the calls of -c to the paths of -i their CHROMs name and\n"
+	      "                                          write consensus.fa (a record per sample, phase and CHROM), roundtrip.tsv and\n"
+	      "                                          cons_summary.txt [default: false]\n"
+	      "        --roundtrip                       with --consensus: compare every haplotype with the path of its sample and phase\n"
+	      "        --no-fasta                        with --consensus: lengths, counts and the round trip only, no consensus.fa\n"
+	      "        --sample=[name]...                with --consensus: only these sample columns\n"
+	      "        --chrom=[name]...                 with --consensus: only these CHROMs\n"
+	      "        --line-width=[n]                  with --consensus: bases a line of consensus.fa, 0 for no wrap [default: 60]\n";
 }
 
 int main(int argc, char **argv)
@@ -225,7 +235,7 @@ int main(int argc, char **argv)
 			  << "` belongs to the reference CPU tool" << std::endl;
 		return 1;
 	}
-	if (!have_input && !(command == "vcf" && povu_host::vcf_args_compare(call_args))) {
+	if (!have_input && !(command == "vcf" && povu_host::vcf_args_check_gfa_themselves(call_args))) {
 		std::cerr << "Flag 'gfa' is required" << std::endl;
 		usage(std::cerr);
 		return 1;

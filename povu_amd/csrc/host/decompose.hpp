@@ -59,8 +59,9 @@ void do_call(const Config &cfg, const std::vector<std::string> &args);
 // --spelling, sequences), report.tsv and summary.txt written to -o <dir>; `args` as for do_call
 void do_vcf(const Config &cfg, const std::vector<std::string> &args);
 // ... with --compare ("VCF comparison"): the VCF of -c compared on the GPU with that of -d, compare.tsv and summary.txt written;
-// no GFA is read, so main() does not ask for -i when the arguments hold --compare
-bool vcf_args_compare(const std::vector<std::string> &args);
+// no GFA is read, so main() does not ask for -i when the arguments hold --compare; nor when they hold --consensus, which refuses a
+// missing -i in its own words
+bool vcf_args_check_gfa_themselves(const std::vector<std::string> &args);
 
 // device of every rank of `--gpus N` (POVU_HIP_DEVICES or 0 .. N-1), checked against the number of visible devices
 std::vector<int> multi_devices(int gpus, const char *env, int visible);

@@ -595,3 +595,70 @@ try {
 } catch (const std::bad_alloc &) {
 	return nullptr;
 }
+
+// ---- the three files of `povu vcf --consensus` (INTEGRATION.md "Consensus haplotypes")
+
+extern "C" char *povu_hip_vcf_cons_text(const povu_hip_vcf_cons *c, const povu_hip_vcf_doc *doc, const povu_hip_call_names *names,
+					const char *const *path_name, uint32_t width, size_t *fasta_len, char **roundtrip, size_t *roundtrip_len,
+					char **summary, size_t *summary_len)
+try {
+	static const char *NAME[POVU_HIP_C_N_RT] = {"none", "equal", "differ", "no_path", "ambiguous"};
+	if (!c || !doc || !names || !roundtrip || !summary || (names->n_paths && !path_name))
+		return nullptr;
+	std::vector<uint32_t> col_first(doc->n_samples + 1), col_slots(doc->n_samples + 1);
+	if (povu_hip_vcf_columns(doc, names, col_first.data(), col_slots.data()))
+		return nullptr;
+	std::string fa, rt = "CHROM\tsample\tphase\tstatus\tlen\tpath\tpath_len\tfirst_diff\tapplied\tduplicate\tenclosed\toverlap\tunspelled\tnocall\n";
+	uint64_t n_rt[POVU_HIP_C_N_RT] = {0}, n_kind[6] = {0};
+	for (uint64_t h = 0; h < c->n_haps; h++) {
+		const uint32_t ch = c->hap_chrom[h], col = c->hap_col[h], j = c->hap_phase[h], st = c->rt_status[h], p = c->rt_path[h];
+		if (ch >= doc->n_chroms || !doc->chrom[ch] || col >= doc->n_samples || st >= POVU_HIP_C_N_RT || (p != POVU_HIP_NIL && p >= names->n_paths) ||
+		    (c->text && c->hap_off[h] + c->hap_len[h] > c->n_text_bytes))
+			return nullptr;
+		const uint32_t counts[6] = {c->n_applied[h], c->n_duplicate[h], c->n_enclosed[h], c->n_overlap[h], c->n_unspelled[h], c->n_nocall[h]};
+		n_rt[st]++;
+		for (int k = 0; k < 6; k++)
+			n_kind[k] += counts[k];
+		if (c->text) {
+			long long hap = j;
+			if (j < col_slots[col] && names->slot_hap && names->slot_hap[col_first[col] + j] >= 0)
+				hap = names->slot_hap[col_first[col] + j];
+			fa += std::string(">") + doc->sample[col] + "#" + std::to_string(hap) + "#" + doc->chrom[ch] + "\n";
+			const char *t = c->text + c->hap_off[h];
+			const uint64_t n = c->hap_len[h], step = width ? width : (n ? n : 1);
+			for (uint64_t k = 0; k < n; k += step) {
+				fa.append(t + k, std::min(step, n - k));
+				fa += "\n";
+			}
+		}
+		if (st == POVU_HIP_C_RT_EQUAL)
+			continue;
+		rt += std::string(doc->chrom[ch]) + "\t" + doc->sample[col] + "\t" + std::to_string(j) + "\t" + NAME[st] + "\t" + std::to_string(c->hap_len[h]) + "\t";
+		rt += (p != POVU_HIP_NIL ? std::string(path_name[p]) : std::string(".")) + "\t" + (p != POVU_HIP_NIL ? std::to_string(c->rt_path_len[h]) : std::string(".")) + "\t";
+		rt += st == POVU_HIP_C_RT_DIFFER ? std::to_string(c->rt_first_diff[h]) : std::string(".");
+		for (int k = 0; k < 6; k++)
+			rt += "\t" + std::to_string(counts[k]);
+		rt += "\n";
+	}
+	static const char *KIND[6] = {"applied", "duplicate", "enclosed", "overlap", "unspelled", "nocall"};
+	std::string sum = "Haplotypes: " + std::to_string(c->n_haps) + ", bases " + std::to_string(c->n_text_bytes) + "\nRound trip: ";
+	for (uint32_t k = 0; k < POVU_HIP_C_N_RT; k++)
+		sum += std::string(k ? ", " : "") + NAME[k] + " " + std::to_string(n_rt[k]);
+	sum += "\nEdits: ";
+	for (int k = 0; k < 6; k++)
+		sum += std::string(k ? ", " : "") + KIND[k] + " " + std::to_string(n_kind[k]);
+	sum += "\n";
+	if (c->n_unplaced)
+		sum += "Unplaced records: " + std::to_string(c->n_unplaced) + "\n";
+	*summary = to_buffer(sum, summary_len);
+	*roundtrip = *summary ? to_buffer(rt, roundtrip_len) : nullptr;
+	char *out = *roundtrip ? to_buffer(fa, fasta_len) : nullptr;
+	if (!out) {
+		free(*summary);
+		free(*roundtrip);
+		*summary = *roundtrip = nullptr;
+	}
+	return out;
+} catch (const std::bad_alloc &) {
+	return nullptr;
+}

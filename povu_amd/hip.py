@@ -183,6 +183,22 @@ class _VcfHap(C.Structure):
                 [("reference", C.c_uint32), ("device_ms", C.c_double)])
 
 
+_CONS_ARRAYS = (("hap_chrom", C.c_uint32), ("hap_col", C.c_uint32), ("hap_phase", C.c_uint32), ("hap_len", C.c_uint64), ("hap_off", C.c_uint64),
+                ("n_applied", C.c_uint32), ("n_duplicate", C.c_uint32), ("n_enclosed", C.c_uint32), ("n_overlap", C.c_uint32),
+                ("n_unspelled", C.c_uint32), ("n_nocall", C.c_uint32), ("rt_status", C.c_uint8), ("rt_path", C.c_uint32),
+                ("rt_path_len", C.c_uint64), ("rt_first_diff", C.c_uint64))
+
+
+class _VcfConsOpts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("n_select", C.c_uint32), ("select_col", C.POINTER(C.c_uint32)), ("select_chrom", C.POINTER(C.c_uint32))]
+
+
+class _VcfCons(C.Structure):
+    _fields_ = ([("n_haps", C.c_uint64)] + [(k, C.POINTER(t)) for k, t in _CONS_ARRAYS] +
+                [("text", C.POINTER(C.c_uint8)), ("n_text_bytes", C.c_uint64), ("n_unplaced", C.c_uint64), ("n_tier2", C.c_uint64),
+                 ("roundtrip", C.c_uint32), ("device_ms", C.c_double), ("write_ms", C.c_double)])
+
+
 OFFREF_COUNTERS = ("n_offref_sites", "n_offref_records", "n_offref_hosted")  # of Calls
 UNTANGLE_COUNTERS = ("n_unt_tasks", "n_unt_records", "n_unt_missing", "n_unt_extra", "n_unt_fallback")  # of Calls
 REGION_COUNTERS = ("n_regions", "n_region_sites", "n_region_masked", "n_region_dropped")  # of Calls
@@ -342,6 +358,11 @@ H_EDIT, H_UNSPELLED, H_UNPLACED = 0, 1, 2
 (H_INCONSISTENT, H_NOCALL_A, H_NOCALL_B, H_UNSPELLED_A, H_UNSPELLED_B, H_CONFLICT_A, H_CONFLICT_B, H_EQUAL_REF, H_EQUAL, H_DIFFER) = range(10)
 H_STATUS_NAMES = ("inconsistent", "nocall_a", "nocall_b", "unspelled_a", "unspelled_b", "conflict_a", "conflict_b", "equal_ref", "equal", "differ")
 H_MAX_REACH_DEFAULT, H_MAX_REACH_MOST = 256, 65536
+# "Consensus haplotypes" (HipDecomposer.consensus): the flags, the materialiser's tile, the round trip of a haplotype
+C_ROUNDTRIP, C_NO_TEXT, C_TIME_WRITE = 1, 2, 8
+C_TILE_BYTES = 4096
+C_RT_NONE, C_RT_EQUAL, C_RT_DIFFER, C_RT_NO_PATH, C_RT_AMBIGUOUS = range(5)
+C_RT_NAMES = ("none", "equal", "differ", "no_path", "ambiguous")
 
 _lib = None
 
@@ -462,6 +483,14 @@ def load_lib():
     l.povu_hip_vcf_hap_text.argtypes = [C.POINTER(_VcfHap), C.POINTER(_VcfDoc), C.POINTER(_VcfDoc), C.POINTER(C.c_size_t),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     l.povu_hip_vcf_hap_text.restype = C.c_void_p
+    l.povu_hip_vcf_consensus.argtypes = [C.c_void_p, C.POINTER(_VcfDoc), C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(_VcfConsOpts), C.c_char_p,
+                                         C.c_size_t]
+    l.povu_hip_vcf_consensus.restype = C.POINTER(_VcfCons)
+    l.povu_hip_vcf_cons_free.argtypes = [C.POINTER(_VcfCons)]
+    l.povu_hip_vcf_cons_text.argtypes = [C.POINTER(_VcfCons), C.POINTER(_VcfDoc), C.POINTER(_CallNames), C.POINTER(C.c_char_p), C.c_uint32,
+                                         C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_size_t)]
+    l.povu_hip_vcf_cons_text.restype = C.c_void_p
     l.povu_hip_forest_pvst_text.restype = C.c_void_p
     l.povu_hip_forest_pvst_text.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]
     l.povu_hip_buffer_free.argtypes = [C.c_void_p]
@@ -1351,6 +1380,69 @@ class HapComparison:
         return self._texts()[1]
 
 
+def cons_texts(lib, cons_p, doc_p, names, width: int = 60):
+    """(consensus.fa, roundtrip.tsv, cons_summary.txt) of povu_hip_vcf_cons_text for a result (which may be hand-made), a parsed
+    document and the path names."""
+    name_array = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    err = C.create_string_buffer(512)
+    nr = lib.povu_hip_vcf_names_make(len(names), name_array, err, 512)
+    if not nr:
+        raise RuntimeError(err.value.decode())
+    try:
+        fl, rl, sl, rp, sp = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_void_p(None), C.c_void_p(None)
+        p = lib.povu_hip_vcf_cons_text(cons_p, doc_p, nr, name_array, width, C.byref(fl), C.byref(rp), C.byref(rl), C.byref(sp), C.byref(sl))
+        if not p:
+            raise RuntimeError("the consensus, the document and the names do not belong together")
+        out = C.string_at(p, fl.value).decode(), C.string_at(rp.value, rl.value).decode(), C.string_at(sp.value, sl.value).decode()
+        for b in (p, rp, sp):
+            lib.povu_hip_buffer_free(b)
+        return out
+    finally:
+        lib.povu_hip_call_names_free(nr)
+
+
+class Consensus:
+    """What HipDecomposer.consensus made (povu_hip_vcf_cons): numpy views, valid as long as this object lives.  Per haplotype,
+    in (CHROM id, column, phase) order: hap_chrom (an index into doc.chroms), hap_col, hap_phase, hap_len, hap_off (into
+    `text`), n_applied / n_duplicate / n_enclosed / n_overlap / n_unspelled / n_nocall, rt_status (C_RT_*), rt_path (0xFFFFFFFF:
+    none), rt_path_len, rt_first_diff.  text (bytes; None under text=False), n_haps, n_text_bytes, n_unplaced, n_tier2,
+    roundtrip, device_ms, write_ms (the materialiser alone, under time_write).  `doc` is the parsed VCF."""
+
+    def __init__(self, lib, ptr, doc: VcfDoc, names):
+        self._lib, self._p, self.doc, self._names = lib, ptr, doc, list(names)
+        c = ptr.contents
+        for k in ("n_haps", "n_text_bytes", "n_unplaced", "n_tier2"):
+            setattr(self, k, int(getattr(c, k)))
+        for k, t in _CONS_ARRAYS:
+            setattr(self, k, _view(getattr(c, k), self.n_haps, np.dtype(t)))
+        self.text = _view(c.text, self.n_text_bytes, np.uint8) if c.text else None
+        self.roundtrip, self.device_ms, self.write_ms = bool(c.roundtrip), float(c.device_ms), float(c.write_ms)
+
+    def __del__(self):
+        if getattr(self, "_p", None):
+            self._lib.povu_hip_vcf_cons_free(self._p)
+            self._p = None
+
+    def sequence(self, i: int) -> str:
+        """The text of haplotype i."""
+        if self.text is None:
+            raise RuntimeError("the consensus was made without its text (text=False)")
+        at, n = int(self.hap_off[i]), int(self.hap_len[i])
+        return bytes(self.text[at:at + n]).decode()
+
+    def fasta_text(self, width: int = 60) -> str:
+        """consensus.fa of `povu vcf --consensus`: `>{sample}#{hap}#{CHROM}` and the text in lines of `width` bytes (0: one)."""
+        return cons_texts(self._lib, self._p, self.doc._p, self._names, width)[0]
+
+    def roundtrip_text(self) -> str:
+        """roundtrip.tsv: a line per haplotype whose round trip is not `equal`."""
+        return cons_texts(self._lib, self._p, self.doc._p, self._names)[1]
+
+    def summary_text(self) -> str:
+        """cons_summary.txt: the haplotypes of every round-trip status, the edits of every kind."""
+        return cons_texts(self._lib, self._p, self.doc._p, self._names)[2]
+
+
 class HipDecomposer:
     """One context = one GPU, one stream, one workspace arena."""
 
@@ -1696,6 +1788,43 @@ class HipDecomposer:
         if not p:
             raise RuntimeError(err.value.decode())
         return HapComparison(self._lib, p, doc_a, doc_b)
+
+    def consensus(self, vcf, roundtrip: bool = False, text: bool = True, samples=None, chroms=None, force_tier2: bool = False,
+                  threads: int = 1, time_write: bool = False) -> Consensus:
+        """The haplotypes the calls of `vcf` (text or a VcfDoc of parse_vcf) spell on the resident paths their CHROMs name
+        (INTEGRATION.md "Consensus haplotypes"; paths and sequences uploaded first): per (CHROM, sample column, phase) the
+        path's bases with the edits of the named ALTs applied, an edit inside or across one in front of it dropped and counted.
+        roundtrip: every haplotype is compared with the one path of its slot.  text=False: lengths, counts and the round trip
+        only.  samples / chroms: names of the sample columns / CHROMs to restrict the call to.  force_tier2: every item through
+        the wave-per-item kernel (tests).  time_write: Consensus.write_ms is measured (the call then waits for the materialiser)."""
+        doc = vcf if isinstance(vcf, VcfDoc) else parse_vcf(vcf, threads)
+        names = getattr(self, "_path_names", [])
+        name_array = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+        cols = chr_ids = None
+        if samples is not None:
+            missing = [x for x in samples if x not in doc.samples]
+            if missing:
+                raise ValueError(f"no sample column is named {missing[0]}")
+            cols = sorted({c for c, n in enumerate(doc.samples) if n in samples})
+        if chroms is not None:
+            missing = [x for x in chroms if x not in doc.chroms]
+            if missing:
+                raise ValueError(f"no record has the CHROM {missing[0]}")
+            chr_ids = sorted({doc.chroms.index(x) for x in chroms})
+        # (the two lists have one length: the shorter is padded with its own first entry)
+        n = max(len(cols or []), len(chr_ids or []))
+        pad = lambda v: None if v is None else (C.c_uint32 * max(n, 1))(*(list(v) + [v[0]] * (n - len(v)) if v else []))  # noqa: E731
+        if (cols is not None and not cols) or (chr_ids is not None and not chr_ids):
+            raise ValueError("an empty selection")
+        ca, ha = pad(cols), pad(chr_ids)
+        o = _VcfConsOpts((C_ROUNDTRIP if roundtrip else 0) | (0 if text else C_NO_TEXT) | (V_FORCE_TIER2 if force_tier2 else 0) |
+                         (C_TIME_WRITE if time_write else 0), n,
+                         C.cast(ca, C.POINTER(C.c_uint32)) if ca is not None else None, C.cast(ha, C.POINTER(C.c_uint32)) if ha is not None else None)
+        err = C.create_string_buffer(512)
+        p = self._lib.povu_hip_vcf_consensus(self._ctx, doc._p, name_array, len(names), C.byref(o), err, 512)
+        if not p:
+            raise RuntimeError(err.value.decode())
+        return Consensus(self._lib, p, doc, names)
 
     def traversals(self, forest: Forest, max_steps: int = 65536, flags: int = 0) -> Traversals:
         """The traversals of every flubble of `forest` by the resident paths, on the GPU."""
